@@ -14,7 +14,11 @@ A "step" is one pass of the hot path over the rank's resident batch.  Frames / s
 independent, so ranks share nothing: the only collectives are the barriers around the timed region
 and the MAX(elapsed) / SUM(frames) reductions of the report (RCCL) -- weak scaling.
 
-Workloads (BASELINE.json configs), `--workload all` (default) runs the three of them:
+A plain run (no --full) renders the headline workload's inputs, warms up --warmup steps, times exactly --steps steps and
+prints the line; --dump-outputs DIR then writes a fixed sample of what the last timed step computed.  --full adds every
+other figure: the secondary workloads, stage profiles, repeated timed blocks, roofline, CPU baseline, host path, latency rows.
+
+Workloads (BASELINE.json configs), `--workload all` (the default with --full) runs the four of them:
   kitti  (HEADLINE `value`) configs[2]: 1241x376 stereo, nFeatures=2000, ORBextractor::operator() on L and R
          (src/ORBextractor.cc:1119-1197) + Frame::ComputeStereoMatches (src/Frame.cc:512-686)
   tum    (secondary)        configs[1]: 640x480 mono stream, nFeatures=1000, extract only
@@ -26,8 +30,8 @@ Workloads (BASELINE.json configs), `--workload all` (default) runs the three of 
   kitti_seq                 configs[4]: the KITTI 00-07 sequence lengths sharded over the ranks by shard.py's
          `sequence` (one sequence per GPU) and `round_robin` (balanced) plans -- strong scaling, both reported
 Inputs are synthetic (no datasets offline), rendered before the GPU is touched and resident in HBM
-before the timed region starts.  Every workload is checked against the CPU oracle on >= 3 frames
-outside the timed region (keypoints, descriptors and match outputs bit-identical) on every run.
+before the timed region starts.  With --full every workload is checked against the CPU oracle on >= 3 frames
+outside the timed region (keypoints, descriptors and match outputs bit-identical).
 """
 from __future__ import annotations
 
@@ -565,12 +569,92 @@ class GpuWorkload:
         return rep, work
 
 
+DUMP_UNITS = 16  # units (frames / stereo pairs) of the last timed step that --dump-outputs writes: a fixed seeded sample
+
+
+def dump_outputs(g, out_dir):
+    """--dump-outputs: what a caller of the timed path receives from its last step, for DUMP_UNITS units drawn with a fixed
+    seed, as float32 .npy files named <workload>_<array>.npy.  Keypoints are the valid records only (the 7 cv::KeyPoint
+    fields in KP_DTYPE order), concatenated image by image; `keypoint_counts` splits them."""
+    from orb_slam2_annotate_amd import KP_DTYPE
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    units = np.sort(np.random.default_rng(0).choice(g.B, size=min(g.B, DUMP_UNITS), replace=False))
+    ipu = 2 if g.stereo else 1
+    imgs = (units[:, None] * ipu + np.arange(ipu)).ravel()
+
+    def rows(t, idx):  # the sampled rows of a device array, gathered on the device before the copy
+        return t[g.torch.as_tensor(idx, dtype=g.torch.long, device=g.dev)].cpu().numpy()
+
+    n = rows(g.d_n, imgs)  # image j of the sample is image imgs[j] of the batch; its unit's left image is j - j % ipu
+    rec = rows(g.d_kp, imgs).view(KP_DTYPE)[..., 0]
+    desc = rows(g.d_desc, imgs)
+    arrays = {
+        "keypoint_counts": n,
+        "keypoints": np.concatenate([np.stack([rec[j, :n[j]][f].astype(np.float32) for f in KP_DTYPE.names], axis=1)
+                                     for j in range(len(imgs))]),
+        "descriptors": np.concatenate([desc[j, :n[j]] for j in range(len(imgs))]),
+    }
+    n_left = n[::ipu]
+    if g.raw:  # the rectified images the step wrote (cv::remap of the raw pair), one row in 16 of each
+        arrays["rectified_rows"] = rows(g.d_rect, imgs)[:, ::16]
+    if g.stereo:  # mvuRight / mvDepth of every left keypoint, and the number of stereo matches per pair
+        u, dep = rows(g.d_u, units), rows(g.d_dep, units)
+        arrays["stereo_match_counts"] = rows(g.d_ns, units)
+        arrays["mvuRight"] = np.concatenate([u[j, :n_left[j]] for j in range(len(units))])
+        arrays["mvDepth"] = np.concatenate([dep[j, :n_left[j]] for j in range(len(units))])
+    if g.bow:  # SearchByBoW(unit k-1 as the key frame, unit k): match count and the match of every (left) keypoint of unit k
+        has_prev = np.nonzero(units > 0)[0]
+        m = rows(g.d_match, units[has_prev] - 1)
+        arrays["bow_match_counts"] = rows(g.d_nm, units[has_prev] - 1)
+        arrays["bow_matches"] = np.concatenate([m[i, :n_left[j]] for i, j in enumerate(has_prev)] + [np.zeros(0, np.int32)])
+    for k, a in arrays.items():
+        np.save(out / f"{g.name}_{k}.npy", np.ascontiguousarray(a, dtype=np.float32))
+
+
+def run_plain(g, S, args, use_dist, dist, torch):
+    """The plain run: W warm-up steps and exactly K timed steps in the timed configuration, nothing else on the GPU."""
+    ext = g.ext
+    ext.profile(False)
+    ext.set_streams(S)
+    ext.set_schedule(args.schedule == "lanes")
+    for _ in range(args.warmup):
+        g.step()
+    g.sync()
+    if use_dist:
+        dist.barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        g.step()
+    g.sync()
+    if use_dist:
+        dist.barrier()
+    dt, total_units = reduce_report(time.perf_counter() - t0, float(g.B * args.steps), torch, dist, use_dist, g.dev)
+    return dt, total_units
+
+
 def run_gpu_workload(name, frames, args, rank, world, local_rank, torch, dist, use_dist, voc_arrays, batches):
     wl = WORKLOADS[name]
     B = batches[name]
     g = GpuWorkload(name, frames, B, local_rank, torch, voc_arrays)
     ext, NI = g.ext, g.NI
     S = max(1, min(32, args.streams if args.streams > 0 else wl.get("streams", 8)))
+
+    if not args.full:
+        dt, total_units = run_plain(g, S, args, use_dist, dist, torch)
+        res = None
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(g, args.dump_outputs)
+            res = {"workload": wl["name"], "key": name, "value": total_units / dt,
+                   "unit": "stereo frames/s" if g.stereo else "frames/s", "ms_per_step": 1e3 * dt / args.steps,
+                   "units_per_gpu_per_step": B, "images_per_gpu_per_step": NI,
+                   "keypoints_per_image": float(g.d_n.float().mean().item()),
+                   "stereo_matches_per_frame": float(g.d_ns.float().mean().item()) if g.stereo else None,
+                   "parity_check": {"ok": None, "skipped": "plain run: the outputs are checked against the CPU oracle by --full"}}
+        del g
+        torch.cuda.empty_cache()
+        return res
 
     def barrier():
         g.sync()
@@ -623,6 +707,8 @@ def run_gpu_workload(name, frames, args, rank, world, local_rank, torch, dist, u
         blocks.append(dt_blk)
         if sum(blocks) >= args.min_seconds or len(blocks) >= args.max_repeats:
             break
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(g, args.dump_outputs)
     prof = ext.profile_get()
     ext.profile(False)
     dt_max = float(np.median(blocks))
@@ -878,6 +964,8 @@ def run_kitti_seq(frames, args, rank, world, local_rank, torch, dist, use_dist, 
         dt_max, total = reduce_report(dt, float(mine * args.steps), torch, dist, use_dist, g.dev)
         out[mode] = {"value": total / dt_max, "ms_per_step": 1e3 * dt_max / args.steps, "stereo_frames_per_step": total / args.steps,
                      "frames_of_rank0": mine, "max_frames_of_a_rank": longest}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(g, args.dump_outputs)
     check = g.check(None)[0] if rank == 0 else None
     del g
     return out, lengths, check
@@ -1018,7 +1106,7 @@ def stub_worker(args, rank, world):
     dt_max, total = reduce_report(dt, float(units * args.steps), torch, dist, use_dist, torch.device("cpu"))
     out = {"metric": "stub", "value": total / dt_max, "unit": "units/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": 1e3 * dt_max / args.steps, "stub": True, "total_units": total}
-    if world > 1:  # the shape of the real line for --gpus N > 1: the configs[4] plans as a `secondary`
+    if world > 1 and args.full:  # the shape of the real --full line for --gpus N > 1: the configs[4] plans as a `secondary`
         from orb_slam2_annotate_amd import shard
         lengths = [max(1, int(round(n * args.seq_scale))) for n in shard.KITTI_00_07]
         plans = {}
@@ -1046,15 +1134,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--min-seconds", type=float, default=1.5, help="repeat the timed block of K steps until this much has been "
-                    "timed per workload; value = median block (min / max / repeats reported)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the secondary workloads, the "
+                    "single-stream and live stage profiles, repeated timed blocks, roofline, parity check against the CPU oracle, "
+                    "CPU baseline, host-path rate, latency rows, the kitti_seq plans on N > 1 GPUs and the detail file.  Without it "
+                    "a run warms up, times exactly --steps steps of the headline workload and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed "
+                    "(a fixed sample of %d units per workload) as DIR/<workload>_<array>.npy, float32" % DUMP_UNITS)
+    ap.add_argument("--min-seconds", type=float, default=1.5, help="--full: repeat the timed block of K steps until this much has "
+                    "been timed per workload; value = median block (min / max / repeats reported)")
     ap.add_argument("--max-repeats", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=0, help="units (frames / stereo pairs) resident per GPU and processed "
                     "per step; 0 = per-workload default (tum 4096, kitti 512, euroc 2048)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["all", "auto", "kitti_seq"], default="auto",
-                    help="auto (default) = all four workloads on ONE GPU; with --gpus N > 1 the headline only (kitti, the fast path: "
-                         "a rank renders and runs one workload) plus the configs[4] kitti_seq plans; 'all' forces the secondaries on N > 1 too")
+                    help="auto (default) = the headline (kitti); with --full all four workloads on ONE GPU, and with --gpus N > 1 "
+                         "the headline plus the configs[4] kitti_seq plans; 'all' forces the secondaries on N > 1 too")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="CPU-baseline budget per variant and workload")
     ap.add_argument("--streams", type=int, default=0,
@@ -1087,10 +1181,13 @@ def main():
                     "collective, i.e. after the extractor's streams exist (LazyDist: RCCL created first costs the pipeline 11 %%)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--full-line", action="store_true", help="print the FULL result dict as the stdout line (tens of KB: stage tables, "
-                    "CPU variants, e2e, latency rows) instead of the compact contract line; what the tools/ scripts parse")
+                    "CPU variants, e2e, latency rows) instead of the compact contract line; what the tools/ scripts parse; implies --full")
     ap.add_argument("--detail-out", default=None, help="file for the full result dict (default: gpurun_out/bench_detail.json)")
     ap.add_argument("--no-detail", action="store_true", help="do not write the detail file")
     args = ap.parse_args()
+    args.full = args.full or args.full_line  # the full dict is that of a full run
+    if not args.full:
+        args.no_detail = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # the parent only spawns, waits and relays: no torch, no HIP
@@ -1104,7 +1201,7 @@ def main():
         return stub_worker(args, rank, world)
 
     if args.workload == "auto":
-        args.workload = "all" if world == 1 else "kitti"
+        args.workload = "all" if world == 1 and args.full else "kitti"
     names = ["kitti", "tum", "euroc", "euroc_stereo"] if args.workload == "all" else (["kitti"] if args.workload == "kitti_seq" else [args.workload])
     batches = {nm: (args.batch if args.batch > 0 else WORKLOADS[nm]["batch"]) for nm in names}
     global SINGLE_SCENE, STEREO_SCENE, VOC_SHAPE
@@ -1163,7 +1260,7 @@ def main():
                 "plans": plans, "parity_check": check}, args)
     else:
         results = []
-        kitti_frames = inputs.get("kitti") if world > 1 else None  # (kept for the configs[4] plans below)
+        kitti_frames = inputs.get("kitti") if world > 1 and args.full else None  # (kept for the configs[4] plans below)
         for nm in names:
             r = run_gpu_workload(nm, inputs.pop(nm), args, rank, world, local_rank, torch, dist, use_dist, voc_arrays, batches)
             results.append(r)
@@ -1186,7 +1283,7 @@ def main():
                            "images_per_gpu_per_step": head["images_per_gpu_per_step"],
                            "keypoints_per_image": head["keypoints_per_image"],
                            "sharding": f"independent frames, one resident batch per GPU x{world}, no data-path collective"},
-                "roofline": head["roofline"], "parity_check": head["parity_check"],
+                "roofline": head.get("roofline"), "parity_check": head["parity_check"],
             }
             if ranks_per_gpu > 1:
                 out["config"]["ranks_per_gpu"] = ranks_per_gpu  # oversubscribed rehearsal: the value is not a rate of N GPUs
@@ -1195,7 +1292,7 @@ def main():
                     out[k] = head[k]
             if len(results) > 1:
                 out["secondary"] = results[1:]
-            if world == 1 and not args.no_latency and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_latency and not args.no_cpu_baseline:
                 # the live system's call pattern (one call at a time): tools/matcher_latency.py, GPU next to the CPU oracle
                 sys.path.insert(0, str(ROOT / "tools"))
                 import matcher_latency

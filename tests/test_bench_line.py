@@ -5,6 +5,8 @@ import json
 import sys
 from pathlib import Path
 
+import pytest
+
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
@@ -64,3 +66,38 @@ def test_emit_writes_the_detail_file_and_prints_the_line_last(tmp_path, capsys):
     assert len(last) < 4096 and json.loads(last)["detail"].endswith("d.json")
     kept = json.loads((tmp_path / "d.json").read_text())
     assert kept["latency"]["rows"] and kept["secondary"][0]["roofline"]["stages"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps of the headline and reports their ms_per_step; --dump-outputs writes the
+    last step's keypoints / descriptors / stereo matches of a fixed sample of pairs, equal to the CPU oracle's."""
+    import os
+    import subprocess
+    import numpy as np
+    import oracle_lib as orc
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "20",
+                        "--render-procs", "1", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "stereo frames/s" and out["higher_is_better"] is True
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 20 * 1e3 / out["ms_per_step"]) < 1e-3 * out["value"]
+    assert "secondary" not in out and "cpu_baseline" not in out and "roofline" not in out
+    d = {f.stem[len("kitti_"):]: np.load(f) for f in tmp_path.glob("kitti_*.npy")}
+    assert set(d) == {"keypoint_counts", "keypoints", "descriptors", "stereo_match_counts", "mvuRight", "mvDepth"}
+    assert all(a.dtype == np.float32 for a in d.values())
+    units = np.sort(np.random.default_rng(0).choice(20, size=bench.DUMP_UNITS, replace=False))
+    frames = bench.render_inputs(["kitti"], {"kitti": 20}, 0, 1)["kitti"]
+    wl = bench.WORKLOADS["kitti"]
+    o = orc.Oracle(wl["nfeatures"], 1.2, 8, wl["ini"], wl["mn"])
+    kps, descs, pyrs = zip(*(o.extract(frames[i], want_pyramid=True) for u in units for i in (2 * u, 2 * u + 1)))
+    assert np.array_equal(d["keypoint_counts"], [len(k) for k in kps])
+    ref_kp = np.concatenate([np.stack([k[f].astype(np.float32) for f in k.dtype.names], axis=1) for k in kps])
+    assert np.array_equal(d["keypoints"], ref_kp) and np.array_equal(d["descriptors"], np.concatenate(descs))
+    mbf = np.float32(wl["bf"])
+    st = [o.stereo(wl["w"], wl["h"], kps[j], descs[j], kps[j + 1], descs[j + 1], pyrs[j], pyrs[j + 1], float(mbf),
+                   float(np.float32(mbf / np.float32(wl["fx"])))) for j in range(0, len(kps), 2)]
+    assert np.array_equal(d["mvuRight"], np.concatenate([u for u, _ in st]))
+    assert np.array_equal(d["mvDepth"], np.concatenate([dep for _, dep in st]))
+    assert np.array_equal(d["stereo_match_counts"], [(u >= 0).sum() for u, _ in st])

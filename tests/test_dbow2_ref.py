@@ -1,7 +1,8 @@
 """Pins the FeatureVector / BowVector container semantics against the REFERENCE's own code: the only
-part of /root/reference that compiles here (Thirdparty/DBoW2/DBoW2/{FeatureVector,BowVector}.cpp ->
-oracle/_ref/libdbow2_ref.so).  Checked against it: the oracle's FeatVec, the host-side CSR FeatureVector
-of the C-ABI, the Python BowVector accumulation of ORBVocabulary.transform, and (GPU) k_vocab_featvec."""
+part of the reference that compiles without OpenCV (Thirdparty/DBoW2/DBoW2/{FeatureVector,BowVector}.cpp), whose
+results on these inputs are recorded in tests/golden/dbow2_ref.npz (tests/ref_lib.py).  Checked against it: the
+oracle's FeatVec, the host-side CSR FeatureVector of the C-ABI, the Python BowVector accumulation of
+ORBVocabulary.transform, and (GPU) k_vocab_featvec."""
 import numpy as np
 import pytest
 
@@ -9,8 +10,6 @@ import oracle_lib as orc
 import ref_lib
 from orb_slam2_annotate_amd import synth
 from orb_slam2_annotate_amd.vocabulary import write_synthetic_vocabulary
-
-pytestmark = pytest.mark.skipif(not ref_lib.available(), reason="oracle/_ref/libdbow2_ref.so not built and no /root/reference")
 
 
 def _cases():

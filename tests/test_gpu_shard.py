@@ -20,7 +20,7 @@ ROOT = Path(__file__).resolve().parent.parent
 def test_two_ranks_run_the_sharded_plans_on_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     scale = 0.02
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--batch", "16", "--steps", "2",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--dist-backend", "gloo", "--batch", "16", "--steps", "2",
            "--warmup", "1", "--min-seconds", "0", "--max-repeats", "1", "--seq-scale", str(scale), "--no-cpu-baseline",
            "--render-procs", "1", "--detail-out", str(tmp_path / "detail.json")]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)

@@ -85,7 +85,7 @@ def test_bench_launcher_starts_the_ranks_itself():
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--stub", "--steps", "3"], env=env,
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--stub", "--full", "--steps", "3"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -126,7 +126,7 @@ def test_bench_launcher_world8_keeps_the_compact_line():
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "8", "--stub", "--steps", "2", "--no-detail"], env=env,
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "8", "--stub", "--full", "--steps", "2", "--no-detail"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = p.stdout.strip().splitlines()

@@ -54,8 +54,8 @@ for W in $WLS; do
   rm -rf $OUT/${TAG}_${W}_stats1
   rm -rf $OUT/${TAG}_${W}_pmc_valu $OUT/${TAG}_${W}_pmc_fetch $OUT/${TAG}_${W}_pmc_write $OUT/${TAG}_${W}_stats   # (raw traces: tens of MB)
 done
-# the default run: stdout = the compact contract line (what the driver parses), --detail-out = the full result dict
-timeout -k 10 600 python3 bench.py --input-cache $CACHE --detail-out $OUT/${TAG}_bench.json > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
+# the full run: stdout = the compact contract line (what the driver parses), --detail-out = the full result dict
+timeout -k 10 600 python3 bench.py --full --input-cache $CACHE --detail-out $OUT/${TAG}_bench.json > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
 note "bench rc=$?"
 rm -rf $CACHE
 tail -c 4200 $OUT/${TAG}_bench_line.json; echo
