@@ -492,8 +492,11 @@ const orbfe_frame_view *orbfe_frame_get_view(const orbfe_frame *f);
  * (mvKeysUn / mvuRight / mDescriptors as the caller has them after its own constructor steps); view->n records are taken.
  *   orbfe_frame_from_extractor: frame `frame` of the handle's last orbfe_extract / small orbfe_extract_batch call
  *       (ORBFE_ERR_INVALID after a device-batch or pipelined call: those outputs are the caller's);
+ *       The handle's next call that rewrites its output block waits (on the device) for the build to finish reading it;
  *   orbfe_frame_from_device:    any device arrays in the extractor's output layout (orbfe_extract_batch_device outputs at
- *       d_keypoints + frame * capacity, d_descriptors + frame * capacity * 32), complete when the call is made.
+ *       d_keypoints + frame * capacity, d_descriptors + frame * capacity * 32), complete when the call is made.  The
+ *       build reads them on the calling thread's stream after the call has returned: they must stay unmodified and
+ *       allocated until orbfe_frame_synchronize(*out) has returned (or a search on the frame has returned).
  * Like orbfe_frame_upload neither waits for the device: searches are ordered behind the build by the frame's own event.
  * Released slabs are pooled (no hipMalloc / hipFree -- which waits for the whole device -- per key frame). */
 #define ORBFE_FRAME_XY_FROM_VIEW 1 /* x / y come from `view` (undistorted by the caller: cameras with distortion) */
@@ -502,8 +505,26 @@ int orbfe_frame_from_extractor(orbfe_extractor *e, int frame, const orbfe_frame_
 int orbfe_frame_from_device(int device, const orbfe_keypoint *d_keypoints, const uint8_t *d_descriptors,
                             const orbfe_frame_view *view, const orbfe_featvec *fv, int flags, orbfe_frame **out);
 /* Frame::ComputeBoW runs after the constructor (src/Tracking.cc:836-843, src/Frame.cc:433-440): attach the FeatureVector
- * to a frame made resident without one.  Call it before other threads use the handle. */
+ * to a frame made resident without one.  Call it before any search uses the frame (it rewrites the frame's index list);
+ * the calling thread may differ from the one that built the frame: the index copy is ordered behind the frame's build,
+ * and the call returns once both have completed. */
 int orbfe_frame_set_featvec(orbfe_frame *f, const orbfe_featvec *fv);
+/* Returns once the frame's build (upload / copy from device records + grid build) has completed on the device: after it,
+ * the device arrays given to orbfe_frame_from_device may be reused. */
+int orbfe_frame_synchronize(const orbfe_frame *f);
+
+/* Test hooks (tests/stream_order.py), never used by a product path.  A one-wave kernel that holds a stream for `usec`
+ * microseconds (0 .. 1 000 000; 0 = a marker that completes at once) and writes no memory; the call returns without
+ * waiting.  `stream` of an extractor: 0 = its stream 0, 1 .. 31 = sub-batch stream 1 .. 31 (the lane schedule: P = 1,
+ * V = 2, T = 0), ORBFE_DEBUG_STREAM_H2D / _D2H = the copy streams of the pipelined host path; a stream the handle has not
+ * created yet is ORBFE_ERR_INVALID.  The thread form holds the calling thread's matcher stream on `device` (created if
+ * needed).  The _idle queries return 1 when everything enqueued on the stream has completed, 0 while work is pending. */
+#define ORBFE_DEBUG_STREAM_H2D (-1)
+#define ORBFE_DEBUG_STREAM_D2H (-2)
+int orbfe_debug_stall_extractor_stream(orbfe_extractor *e, int stream, int usec);
+int orbfe_debug_extractor_stream_idle(orbfe_extractor *e, int stream);
+int orbfe_debug_stall_thread_stream(int device, int usec);
+int orbfe_debug_thread_stream_idle(int device);
 
 /* Frame::AssignFeaturesToGrid + Frame::GetFeaturesInArea (src/Frame.cc:246-267, 358-427) for
  * n_queries windows at once: count[q] features lie in the window of query q; the first

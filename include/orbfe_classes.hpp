@@ -199,6 +199,8 @@ class FrameArrays {
   }
   // Frame::ComputeBoW (src/Frame.cc:433-440) runs after the constructor: attach mFeatVec to the resident frame
   void setFeatVec(const FeatureVectorCSR& mFeatVec) { check(orbfe_frame_set_featvec(resident_, &mFeatVec.c), "FrameArrays::setFeatVec"); }
+  // returns once the resident build has completed on the device (device arrays a build from them read may be reused)
+  void synchronize() const { check(orbfe_frame_synchronize(resident_), "FrameArrays::synchronize"); }
   const orbfe_frame* resident() const { return resident_; }
 
   // vector<size_t> Frame::GetFeaturesInArea(x, y, r, minLevel, maxLevel) const

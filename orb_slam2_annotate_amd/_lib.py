@@ -22,6 +22,7 @@ assert KP_DTYPE.itemsize == 28
 
 STAGES = ["h2d", "pyramid", "fast", "octree", "blur", "orient_desc", "d2h", "match"]
 ORBFE_OK, ERR_INVALID, ERR_CAPACITY, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4
+DEBUG_STREAM_H2D, DEBUG_STREAM_D2H = -1, -2  # orbfe_debug_stall_extractor_stream: the pipelined path's copy streams
 
 
 class OrbfeError(RuntimeError):
@@ -63,7 +64,8 @@ EXPORTS = [
     "orbfe_search_by_projection_sim3", "orbfe_search_for_initialization", "orbfe_debug_last_claim_rounds", "orbfe_fuse_search", "orbfe_search_by_sim3",
     "orbfe_init_undistort_rectify_map", "orbfe_rectifier_create", "orbfe_rectifier_destroy", "orbfe_remap", "orbfe_remap_batch_device", "orbfe_extract_stereo_rectified_batch_device_async",
     "orbfe_undistort_points", "orbfe_undistort_keypoints_batch_device", "orbfe_compute_image_bounds",
-    "orbfe_stereo_from_rgbd",
+    "orbfe_stereo_from_rgbd", "orbfe_frame_synchronize", "orbfe_debug_stall_extractor_stream", "orbfe_debug_extractor_stream_idle",
+    "orbfe_debug_stall_thread_stream", "orbfe_debug_thread_stream_idle",
 ]
 
 _lib = None
@@ -189,6 +191,11 @@ def load():
     L.orbfe_frame_from_extractor.argtypes = [vp, ci, fwp, vp, ci, C.POINTER(C.c_void_p)]
     L.orbfe_frame_from_device.argtypes = [ci, vp, vp, fwp, vp, ci, C.POINTER(C.c_void_p)]
     L.orbfe_frame_set_featvec.argtypes = [vp, vp]
+    L.orbfe_frame_synchronize.argtypes = [vp]
+    L.orbfe_debug_stall_extractor_stream.argtypes = [vp, ci, ci]
+    L.orbfe_debug_extractor_stream_idle.argtypes = [vp, ci]
+    L.orbfe_debug_stall_thread_stream.argtypes = [ci, ci]
+    L.orbfe_debug_thread_stream_idle.argtypes = [ci]
     L.orbfe_init_undistort_rectify_map.argtypes = [ci, vp, vp, ci, vp, vp, ci, ci, vp, vp]
     L.orbfe_rectifier_create.argtypes = [ci, vp, vp, ci, ci, ci, C.POINTER(C.c_void_p)]
     L.orbfe_rectifier_destroy.argtypes = [vp]

@@ -66,6 +66,11 @@ struct orbfe_extractor {
   bool tailPending[kMaxStreams] = {};
   hipEvent_t evChunkDone[kMaxStreams] = {};
   hipEvent_t evConsumerDone = nullptr;
+  // a resident frame built from the output block (orbfe_frame_from_extractor) reads it on the building thread's matcher
+  // stream: evReaderDone marks the end of that build, and the next call that writes the block waits for it (run_pipeline)
+  hipEvent_t evReaderDone = nullptr;
+  hipStream_t readerStream = nullptr;
+  bool readerPending = false;
   int chunksPending = 0;                     // sub-batch streams 1..chunksPending-1 carry an unrecorded-for-consumer event
   bool consumerPending = false;
   int lastSplitFrames = -1, lastSplitStreams = -1;
@@ -296,7 +301,15 @@ void free_workspace(orbfe_extractor* e) {
   e->octreeWorkStride = 0;
   e->capFrames = 0;
 }
+// host wait for the last frame build that reads the output block (before the block is freed, or as part of sync_all)
+int reader_settle(orbfe_extractor* e) {
+  if (!e->readerPending) return ORBFE_OK;
+  HIPCHK(hipEventSynchronize(e->evReaderDone));
+  e->readerPending = false;
+  return ORBFE_OK;
+}
 void free_outputs(orbfe_extractor* e) {
+  (void)reader_settle(e);
   dfree(&e->d_outBlock);
   e->d_kpOut = nullptr; e->d_descOut = nullptr; e->d_nOut = nullptr;
   e->outCap = 0;
@@ -806,9 +819,17 @@ int run_pipeline(orbfe_extractor* e, LevelView level0, int nFrames, orbfe_keypoi
   e->lastPer = per;
   e->lastS = S;
   e->lastLanes = lanes;
+  // a frame build still reading the output block this call overwrites: every stream that writes the block waits for it
+  // (stream 0 included -- the build runs on another thread's matcher stream)
+  if (e->readerPending) {
+    if (hipEventQuery(e->evReaderDone) == hipSuccess) e->readerPending = false;
+    (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is not an error
+  }
+  const bool readerWait = e->readerPending && d_kp == e->d_kpOut;
   if (lanes) {
     hipStream_t sP = e->extra[0], sV = e->extra[1], sT = e->stream;
     if (e->consumerPending) HIPCHK(hipStreamWaitEvent(sP, e->evConsumerDone, 0));  // a matcher still reads the last pyramid
+    if (readerWait) HIPCHK(hipStreamWaitEvent(sP, e->evReaderDone, 0));  // (V and T start behind P's events)
     for (int k = 0; k < nWait; k++) {  // e.g. the H2D copy of this chunk (read by P, V and T), the D2H of its output block (T)
       HIPCHK(hipStreamWaitEvent(sP, waitFor[k], 0));
       HIPCHK(hipStreamWaitEvent(sT, waitFor[k], 0));
@@ -842,6 +863,7 @@ int run_pipeline(orbfe_extractor* e, LevelView level0, int nFrames, orbfe_keypoi
     if (n <= 0) break;
     hipStream_t s = i == 0 ? e->stream : e->extra[i - 1];
     if (i > 0 && e->consumerPending) HIPCHK(hipStreamWaitEvent(s, e->evConsumerDone, 0));
+    if (readerWait) HIPCHK(hipStreamWaitEvent(s, e->evReaderDone, 0));
     for (int k = 0; k < nWait; k++) HIPCHK(hipStreamWaitEvent(s, waitFor[k], 0));  // e.g. the H2D copy of this chunk
     if (pre && pre->fn) {
       StageTimer t(e, ORBFE_STAGE_H2D, 2, n, i, s);  // "h2d" = the ingest stage of a call: here the rectification
@@ -865,7 +887,7 @@ int sync_all(orbfe_extractor* e) {
   HIPCHK(hipStreamSynchronize(e->stream));
   for (int i = 0; i < orbfe_extractor::kMaxStreams - 1; i++)
     if (e->extra[i]) HIPCHK(hipStreamSynchronize(e->extra[i]));
-  return ORBFE_OK;
+  return reader_settle(e);
 }
 
 }  // namespace
@@ -983,6 +1005,7 @@ extern "C" void orbfe_extractor_destroy(orbfe_extractor* e) {
     if (e->evTail[i]) (void)hipEventDestroy(e->evTail[i]);
   }
   if (e->evConsumerDone) (void)hipEventDestroy(e->evConsumerDone);
+  if (e->evReaderDone) (void)hipEventDestroy(e->evReaderDone);
   stream_put(e->device, 0, e->stream);
   delete e;
 }
@@ -1106,6 +1129,7 @@ extern "C" int orbfe_extract_stereo_rectified_batch_device_async(
     int rcs = sync_all(e);  // the workspace is about to be re-allocated
     if (rcs) return rcs;
   }
+  e->outLastFrames = 0;  // (as orbfe_extract_batch_device_async: the outputs are the caller's)
   if ((rc = ensure_geometry(e, wl, hl))) return rc;
   if ((rc = ensure_workspace(e, n_frames))) return rc;
   next_event_slot(e);
@@ -1326,6 +1350,7 @@ extern "C" int orbfe_extract_batch_pipelined(orbfe_extractor* e, const uint8_t* 
   HIPCHK(hipSetDevice(e->device));
   int rc;
   if ((rc = sync_all(e))) return rc;
+  e->outLastFrames = 0;  // (as orbfe_extract_batch_device_async: the outputs are the caller's)
   if ((rc = ensure_geometry(e, width, height))) return rc;
   int C = chunk_frames > 0 ? chunk_frames : 256;
   if (C > n_frames) C = n_frames;
@@ -1637,6 +1662,20 @@ extern "C" int orbfe_extractor_consumer_end_(orbfe_extractor* e) {
   }
   HIPCHK(hipEventRecord(e->evConsumerDone, e->stream));
   e->consumerPending = true;
+  return ORBFE_OK;
+}
+
+// internal (matcher.hip, orbfe_frame_from_extractor): a frame build that reads the output block was enqueued on `s`;
+// the next call that writes the block waits for it on the device.  Builds on one stream are ordered by that stream, so
+// one event covers them; a build on another thread's stream first settles the one before it (rare: one handle, two threads)
+extern "C" int orbfe_extractor_reader_end_(orbfe_extractor* e, hipStream_t s) {
+  if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
+  HIPCHK(hipSetDevice(e->device));
+  if (!e->evReaderDone) HIPCHK(hipEventCreateWithFlags(&e->evReaderDone, hipEventDisableTiming));
+  if (e->readerPending && e->readerStream != s) { int rc = reader_settle(e); if (rc) return rc; }
+  HIPCHK(hipEventRecord(e->evReaderDone, s));
+  e->readerStream = s;
+  e->readerPending = true;
   return ORBFE_OK;
 }
 
@@ -2041,4 +2080,58 @@ extern "C" int orbfe_debug_resize_tables(int sw, int sh, int dw, int dh, int32_t
   std::memcpy(yofs, t.yofs.data(), t.yofs.size() * 4);
   std::memcpy(beta, t.beta.data(), t.beta.size() * 2);
   return ORBFE_OK;
+}
+
+// ---- test hook: hold one of the library's streams back (tests/stream_order.py) ----
+// One wave; lane 0 polls the 100 MHz constant clock and sleeps between polls.  The kernel writes no memory: whatever
+// is enqueued behind it on the same stream simply starts later.  Never used by a product path.
+namespace {
+__global__ void __launch_bounds__(64) k_debug_stall(long long ticks) {
+  if (threadIdx.x != 0) return;
+  const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
+  while ((long long)__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
+}
+}  // namespace
+
+// internal (matcher.hip): the stall on any stream; usec = 0 is a marker that completes at once
+extern "C" int orbfe_debug_stall_launch_(hipStream_t s, int usec) {
+  if (usec < 0 || usec > 1000000) return fail(ORBFE_ERR_INVALID, "debug_stall: usec must be 0 .. 1000000");
+  hipLaunchKernelGGL(k_debug_stall, dim3(1), dim3(64), 0, s, (long long)usec * 100);
+  HIPCHK(hipGetLastError());
+  return ORBFE_OK;
+}
+
+// internal: 1 when everything enqueued on `s` has completed, 0 while work is pending
+extern "C" int orbfe_debug_stream_idle_(hipStream_t s) {
+  const hipError_t q = hipStreamQuery(s);
+  if (q == hipSuccess) return 1;
+  (void)hipGetLastError();  // hipErrorNotReady is the answer, not an error
+  if (q == hipErrorNotReady) return 0;
+  return fail(ORBFE_ERR_HIP, std::string("debug_stream_idle: ") + hipGetErrorString(q));
+}
+
+namespace {
+int extractor_stream(orbfe_extractor* e, int stream, hipStream_t* s) {
+  if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
+  *s = nullptr;
+  if (stream == 0) *s = e->stream;
+  else if (stream > 0 && stream < orbfe_extractor::kMaxStreams) *s = e->extra[stream - 1];
+  else if (stream == ORBFE_DEBUG_STREAM_H2D) *s = e->sH2D;
+  else if (stream == ORBFE_DEBUG_STREAM_D2H) *s = e->sD2H;
+  if (!*s) return fail(ORBFE_ERR_INVALID, "debug_stall: the handle has no stream " + std::to_string(stream) + " (yet)");
+  HIPCHK(hipSetDevice(e->device));
+  return ORBFE_OK;
+}
+}  // namespace
+
+extern "C" int orbfe_debug_stall_extractor_stream(orbfe_extractor* e, int stream, int usec) {
+  hipStream_t s;
+  int rc = extractor_stream(e, stream, &s);
+  return rc ? rc : orbfe_debug_stall_launch_(s, usec);
+}
+
+extern "C" int orbfe_debug_extractor_stream_idle(orbfe_extractor* e, int stream) {
+  hipStream_t s;
+  int rc = extractor_stream(e, stream, &s);
+  return rc ? rc : orbfe_debug_stream_idle_(s);
 }

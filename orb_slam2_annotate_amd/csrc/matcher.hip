@@ -673,6 +673,8 @@ extern "C" int orbfe_frame_from_device(int device, const orbfe_keypoint* d_keypo
 extern "C" int orbfe_extractor_output_device_(orbfe_extractor* e, int frame, const orbfe_keypoint** d_kp, const uint8_t** d_desc,
                                               int* n, int* device);
 
+extern "C" int orbfe_extractor_reader_end_(orbfe_extractor* e, hipStream_t s);
+
 extern "C" int orbfe_frame_from_extractor(orbfe_extractor* e, int frame, const orbfe_frame_view* view, const orbfe_featvec* fv,
                                           int flags, orbfe_frame** out) {
   if (!out) return mfail(ORBFE_ERR_INVALID, "frame_from_extractor: NULL argument");
@@ -683,12 +685,20 @@ extern "C" int orbfe_frame_from_extractor(orbfe_extractor* e, int frame, const o
   int rc = orbfe_extractor_output_device_(e, frame, &dkp, &ddesc, &n, &device);
   if (rc != ORBFE_OK) return rc;
   if (!view || view->n > n) return mfail(ORBFE_ERR_INVALID, "frame_from_extractor: the view holds more keypoints than the extractor produced for this frame");
-  return orbfe_frame_from_device(device, dkp, ddesc, view, fv, flags, out);
+  rc = orbfe_frame_from_device(device, dkp, ddesc, view, fv, flags, out);
+  if (rc != ORBFE_OK) return rc;
+  // the build reads the handle's output block on this thread's stream without a host wait: the handle's next call that
+  // rewrites the block waits for it
+  rc = orbfe_extractor_reader_end_(e, t_arenas[device].stream);
+  if (rc != ORBFE_OK) { orbfe_frame_release(*out); *out = nullptr; }
+  return rc;
 }
 
 // Frame::ComputeBoW runs after the constructor (src/Tracking.cc:836-843, src/Frame.cc:433-440): attach the FeatureVector
-// to a frame that was made resident without one.  Call it before the handle is shared with other threads.
+// to a frame that was made resident without one.  Call it before any search uses the frame (it rewrites the index list);
+// the calling thread may differ from the building one (LocalMapping's KeyFrame::ComputeBoW): frame_use orders the copy.
 extern "C" int orbfe_frame_set_featvec(orbfe_frame* f, const orbfe_featvec* fv) {
+  UnsettledScope unsettledScope;
   if (!f || !fv) return mfail(ORBFE_ERR_INVALID, "frame_set_featvec: NULL argument");
   if (!featvec_ok(fv, f->n)) return mfail(ORBFE_ERR_INVALID, "frame_set_featvec: malformed FeatureVector");
   const size_t nIdx = fv->n_nodes > 0 ? (size_t)fv->offsets[fv->n_nodes] : 0;
@@ -706,13 +716,45 @@ extern "C" int orbfe_frame_set_featvec(orbfe_frame* f, const orbfe_featvec* fv) 
   Arena* ar;
   hipError_t err = arena_begin(f->device, 1024, &ar);
   if (err == hipSuccess) err = staging_reserve_(nIdx * 4);
+  // the frame's own build copy covers the index region and may still be queued on the building thread's stream
+  if (err == hipSuccess) err = frame_use(ar, f);
   if (err == hipSuccess) {
     std::memcpy(staging_ptr_(), f->hindices.data(), nIdx * 4);
     err = hipMemcpyAsync(f->dindices, staging_ptr_(), nIdx * 4, hipMemcpyHostToDevice, ar->stream);
   }
   if (err == hipSuccess) err = hipStreamSynchronize(ar->stream);  // (the handle may be in use on other streams afterwards)
   if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("frame_set_featvec: ") + hipGetErrorString(err));
+  frames_settle();
   return ORBFE_OK;
+}
+
+extern "C" int orbfe_frame_synchronize(const orbfe_frame* f) {
+  if (!f) return mfail(ORBFE_ERR_INVALID, "frame_synchronize: NULL frame");
+  if (f->settled.load(std::memory_order_acquire)) return ORBFE_OK;
+  hipError_t err = hipSetDevice(f->device);
+  if (err == hipSuccess) err = hipEventSynchronize(f->ready);
+  if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("frame_synchronize: ") + hipGetErrorString(err));
+  f->settled.store(true, std::memory_order_release);
+  return ORBFE_OK;
+}
+
+// ---- test hook (tests/stream_order.py): hold back / query the calling thread's matcher stream on `device` ----
+extern "C" int orbfe_debug_stall_launch_(hipStream_t s, int usec);
+extern "C" int orbfe_debug_stream_idle_(hipStream_t s);
+
+extern "C" int orbfe_debug_stall_thread_stream(int device, int usec) {
+  if (usec < 0 || usec > 1000000) return mfail(ORBFE_ERR_INVALID, "debug_stall: usec must be 0 .. 1000000");
+  Arena* ar;
+  hipError_t err = arena_begin(device, 0, &ar);
+  if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("debug_stall: ") + hipGetErrorString(err));
+  return orbfe_debug_stall_launch_(ar->stream, usec);
+}
+
+extern "C" int orbfe_debug_thread_stream_idle(int device) {
+  Arena* ar;
+  hipError_t err = arena_begin(device, 0, &ar);
+  if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("debug_stream_idle: ") + hipGetErrorString(err));
+  return orbfe_debug_stream_idle_(ar->stream);
 }
 
 // ---- the FeatureVector searches on resident frames: per call only the shared-node list, the map-point masks and

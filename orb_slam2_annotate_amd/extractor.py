@@ -208,6 +208,15 @@ class ORBextractor:
     def synchronize(self):
         check(self._L.orbfe_extractor_synchronize(self._h))
 
+    # ---- test hooks (tests/stream_order.py): hold one of the handle's streams back ----
+    def debug_stall_stream(self, stream: int, usec: int):
+        """stream 0 = the handle's stream 0, 1..31 = sub-batch stream k (lanes: P = 1, V = 2, T = 0), _lib.DEBUG_STREAM_H2D /
+        _D2H = the pipelined path's copy streams.  usec = 0 is a marker that completes at once; returns at once."""
+        check(self._L.orbfe_debug_stall_extractor_stream(self._h, int(stream), int(usec)))
+
+    def debug_stream_idle(self, stream: int) -> bool:
+        return check(self._L.orbfe_debug_extractor_stream_idle(self._h, int(stream))) == 1
+
     # ---- mvImagePyramid, include/ORBextractor.h:86 ----
     def pyramid_level(self, level: int, frame: int = 0) -> np.ndarray:
         if self._last_shape is None:

@@ -131,6 +131,11 @@ class ResidentFrame:
         """Frame::ComputeBoW after the constructor (src/Tracking.cc:836-843): attach the FeatureVector."""
         check(self._L.orbfe_frame_set_featvec(self._h, C.byref(fv.c)))
 
+    def synchronize(self):
+        """Returns once the frame's build has completed (orbfe_frame_synchronize): the device arrays a frame built with
+        d_keypoints / d_descriptors read may be reused after it."""
+        check(self._L.orbfe_frame_synchronize(self._h))
+
     def close(self):
         if getattr(self, "_handle", None):
             self._L.orbfe_frame_release(self._handle)
@@ -139,6 +144,17 @@ class ResidentFrame:
 
     __del__ = close
     GetFeaturesInArea = FrameView.GetFeaturesInArea  # (reads self.c only: no frame data travels)
+
+
+def debug_stall_thread_stream(usec: int, device: int = 0):
+    """Test hook (tests/stream_order.py): hold the calling thread's matcher stream for `usec` microseconds (0 = a marker
+    that completes at once); returns at once."""
+    check(_lib.load().orbfe_debug_stall_thread_stream(int(device), int(usec)))
+
+
+def debug_thread_stream_idle(device: int = 0) -> bool:
+    """True when everything enqueued on the calling thread's matcher stream has completed."""
+    return check(_lib.load().orbfe_debug_thread_stream_idle(int(device))) == 1
 
 
 def _f32(a):
