@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "host_internal.h"
 #include "kernels.h"
 #include "match_kernels.h"
 #include "octree_host.h"
@@ -22,7 +23,7 @@
 using namespace orbfe;
 
 static thread_local std::string g_err = "";
-static int fail(int code, const std::string& msg) {
+int orbfe::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
@@ -34,7 +35,6 @@ static int fail(int code, const std::string& msg) {
   } while (0)
 
 extern "C" const char* orbfe_last_error(void) { return g_err.c_str(); }
-int orbfe_set_error_(int code, const char* msg) { return fail(code, msg); }  // used by matcher.hip, vocabulary.hip
 extern "C" int orbfe_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1083,9 +1083,6 @@ extern "C" int orbfe_extract_batch_device_async(orbfe_extractor* e, const uint8_
 // calls of the stereo Frame constructor (src/Frame.cc:78-81), for a device-resident batch of raw pairs: sub-batch by
 // sub-batch, on the sub-batch's own stream -- rectified frames are written interleaved (L0, R0, L1, R1, ...), the layout
 // orbfe_stereo_match_batch_device reads.
-extern "C" int orbfe_remap_launch_(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride,
-                                   size_t sFrame, uint8_t* d_dst, int dstride, size_t dFrame, hipStream_t stream, int* w, int* h,
-                                   int* device);
 namespace {
 struct RectifyCtx {
   orbfe_rectifier *rl, *rr;
@@ -1160,10 +1157,6 @@ extern "C" int orbfe_extract_batch_device(orbfe_extractor* e, const uint8_t* d_i
   if (rc) return rc;
   return orbfe_extractor_synchronize(e);
 }
-
-extern "C" int orbfe_extract_batch_pipelined(orbfe_extractor* e, const uint8_t* images, int n_frames, int width, int height,
-                                             int stride, size_t frame_stride, orbfe_keypoint* keypoints,
-                                             uint8_t* descriptors, int capacity, int* n_out, int chunk_frames);
 
 extern "C" int orbfe_extract_batch(orbfe_extractor* e, const uint8_t* images, int n_frames, int width,
                                    int height, int stride, size_t frame_stride,
@@ -1593,7 +1586,6 @@ extern "C" int orbfe_resize_linear(int device, const uint8_t* src, int sw, int s
   return ORBFE_OK;
 }
 
-extern "C" int orbfe_gaussian_blur7_spec(int device, int spec, const uint8_t* src, int w, int h, int sstride, uint8_t* dst, int dstride);
 extern "C" int orbfe_gaussian_blur7(int device, const uint8_t* src, int w, int h, int sstride, uint8_t* dst, int dstride) {
   return orbfe_gaussian_blur7_spec(device, kBlurSpecCv4, src, w, h, sstride, dst, dstride);
 }

@@ -7,15 +7,15 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "host_internal.h"
 #include "kernels.h"
 #include "orb_spec.h"
 
-int orbfe_set_error_(int code, const char* msg);
-static int ifail(int code, const std::string& m) { return orbfe_set_error_(code, m.c_str()); }
+using orbfe::fail;
 #define IHIP(expr)                                                                                   \
   do {                                                                                               \
     hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) return ifail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    if (_e != hipSuccess) return fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
 namespace {
@@ -87,7 +87,7 @@ extern "C" int orbfe_cvt_gray(int device, const uint8_t* src, int width, int hei
                               int rgb_order, uint8_t* dst, int dst_stride) {
   if (!src || !dst || width <= 0 || height <= 0 || (channels != 3 && channels != 4) || stride < width * channels ||
       dst_stride < width)
-    return ifail(ORBFE_ERR_INVALID, "cvt_gray: bad argument");
+    return fail(ORBFE_ERR_INVALID, "cvt_gray: bad argument");
   IHIP(hipSetDevice(device));
   uint8_t *ds = nullptr, *dd = nullptr;
   const size_t sb = (size_t)width * channels * height, db = (size_t)width * height;
@@ -103,7 +103,7 @@ extern "C" int orbfe_cvt_gray(int device, const uint8_t* src, int width, int hei
   if (err == hipSuccess) err = hipMemcpy2D(dst, dst_stride, dd, width, width, height, hipMemcpyDeviceToHost);
   (void)hipFree(ds);
   if (dd) (void)hipFree(dd);
-  if (err != hipSuccess) return ifail(ORBFE_ERR_HIP, std::string("cvt_gray: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("cvt_gray: ") + hipGetErrorString(err));
   return ORBFE_OK;
 }
 
@@ -112,7 +112,7 @@ extern "C" int orbfe_cvt_gray_batch_device(int device, const uint8_t* d_src, int
                                            uint8_t* d_dst, int dst_stride, size_t dst_frame_stride) {
   if (!d_src || !d_dst || n_frames < 0 || width <= 0 || height <= 0 || (channels != 3 && channels != 4) ||
       stride < width * channels || dst_stride < width)
-    return ifail(ORBFE_ERR_INVALID, "cvt_gray_batch_device: bad argument");
+    return fail(ORBFE_ERR_INVALID, "cvt_gray_batch_device: bad argument");
   if (n_frames == 0) return ORBFE_OK;
   IHIP(hipSetDevice(device));
   hipLaunchKernelGGL(k_cvt_gray, dim3((width + 1023) / 1024, height, n_frames), dim3(256), 0, 0, d_src, width, height,
@@ -125,12 +125,12 @@ extern "C" int orbfe_cvt_gray_batch_device(int device, const uint8_t* d_src, int
 extern "C" int orbfe_distinctive_descriptors(int device, const uint8_t* descriptors, const int32_t* offsets,
                                              int n_points, int32_t* best_index) {
   if (n_points < 0 || (n_points > 0 && (!descriptors || !offsets || !best_index)))
-    return ifail(ORBFE_ERR_INVALID, "distinctive_descriptors: bad argument");
+    return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: bad argument");
   if (n_points == 0) return ORBFE_OK;
   for (int i = 0; i < n_points; i++)
     if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 65535)
-      return ifail(ORBFE_ERR_INVALID, "distinctive_descriptors: bad offsets (or more than 65535 observations)");
-  if (offsets[0] != 0) return ifail(ORBFE_ERR_INVALID, "distinctive_descriptors: offsets[0] != 0");
+      return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: bad offsets (or more than 65535 observations)");
+  if (offsets[0] != 0) return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: offsets[0] != 0");
   const size_t total = (size_t)offsets[n_points];
   IHIP(hipSetDevice(device));
   uint8_t* dd = nullptr; int32_t *doff = nullptr, *dbest = nullptr;
@@ -147,7 +147,7 @@ extern "C" int orbfe_distinctive_descriptors(int device, const uint8_t* descript
   (void)hipFree(dd);
   if (doff) (void)hipFree(doff);
   if (dbest) (void)hipFree(dbest);
-  if (err != hipSuccess) return ifail(ORBFE_ERR_HIP, std::string("distinctive_descriptors: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("distinctive_descriptors: ") + hipGetErrorString(err));
   return ORBFE_OK;
 }
 
@@ -251,7 +251,7 @@ int remap_launch(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw,
 extern "C" int orbfe_remap_launch_(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride,
                                    size_t sFrame, uint8_t* d_dst, int dstride, size_t dFrame, hipStream_t stream, int* w, int* h,
                                    int* device) {
-  if (!r) return ifail(ORBFE_ERR_INVALID, "NULL rectifier");
+  if (!r) return fail(ORBFE_ERR_INVALID, "NULL rectifier");
   if (w) *w = r->width;
   if (h) *h = r->height;
   if (device) *device = r->device;
@@ -262,7 +262,7 @@ extern "C" int orbfe_remap_launch_(orbfe_rectifier* r, const uint8_t* d_src, int
 extern "C" int orbfe_rectifier_create(int device, const float* map_x, const float* map_y, int width, int height,
                                   int map_stride, orbfe_rectifier** out) {
   if (!map_x || !map_y || !out || width <= 0 || height <= 0 || map_stride < width || width > 32767 || height > 32767)
-    return ifail(ORBFE_ERR_INVALID, "remap_create: bad argument");
+    return fail(ORBFE_ERR_INVALID, "remap_create: bad argument");
   IHIP(hipSetDevice(device));
   orbfe_rectifier* r = new orbfe_rectifier();
   r->device = device; r->width = width; r->height = height; r->pitch = (width + 3) & ~3;
@@ -286,7 +286,7 @@ extern "C" int orbfe_rectifier_create(int device, const float* map_x, const floa
     if (r->xy) (void)hipFree(r->xy);
     if (r->phase) (void)hipFree(r->phase);
     delete r;
-    return ifail(err == hipErrorOutOfMemory ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP, std::string("remap_create: ") + hipGetErrorString(err));
+    return fail(err == hipErrorOutOfMemory ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP, std::string("remap_create: ") + hipGetErrorString(err));
   }
   *out = r;
   return ORBFE_OK;
@@ -303,7 +303,7 @@ extern "C" void orbfe_rectifier_destroy(orbfe_rectifier* r) {
 extern "C" int orbfe_remap(orbfe_rectifier* r, const uint8_t* src, int src_width, int src_height, int src_stride,
                            uint8_t* dst, int dst_stride) {
   if (!r || !src || !dst || src_width <= 0 || src_height <= 0 || src_stride < src_width || dst_stride < r->width)
-    return ifail(ORBFE_ERR_INVALID, "remap: bad argument");
+    return fail(ORBFE_ERR_INVALID, "remap: bad argument");
   IHIP(hipSetDevice(r->device));
   uint8_t *ds = nullptr, *dd = nullptr;
   IHIP(hipMalloc((void**)&ds, (size_t)src_width * src_height));
@@ -315,7 +315,7 @@ extern "C" int orbfe_remap(orbfe_rectifier* r, const uint8_t* src, int src_width
   if (err == hipSuccess && rc == ORBFE_OK) err = hipMemcpy2D(dst, dst_stride, dd, r->pitch, r->width, r->height, hipMemcpyDeviceToHost);
   (void)hipFree(ds);
   if (dd) (void)hipFree(dd);
-  if (err != hipSuccess) return ifail(ORBFE_ERR_HIP, std::string("remap: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("remap: ") + hipGetErrorString(err));
   return rc;
 }
 
@@ -324,7 +324,7 @@ extern "C" int orbfe_remap_batch_device(orbfe_rectifier* r, const uint8_t* d_src
                                         int dst_stride, size_t dst_frame_stride) {
   if (!r || !d_src || !d_dst || n_frames < 0 || src_width <= 0 || src_height <= 0 || src_stride < src_width ||
       dst_stride < r->width)
-    return ifail(ORBFE_ERR_INVALID, "remap_batch_device: bad argument");
+    return fail(ORBFE_ERR_INVALID, "remap_batch_device: bad argument");
   if (n_frames == 0) return ORBFE_OK;
   IHIP(hipSetDevice(r->device));
   const int rc = remap_launch(r, d_src, n_frames, src_width, src_height, src_stride, src_frame_stride, d_dst, dst_stride,
@@ -449,7 +449,7 @@ extern "C" int orbfe_init_undistort_rectify_map(int device, const double* K, con
                                                 const double* P, int width, int height, float* map_x, float* map_y) {
   if (!K || width <= 0 || height <= 0 || !map_x || !map_y || !(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8) ||
       (n_dist > 0 && !D))
-    return ifail(ORBFE_ERR_INVALID, "init_undistort_rectify_map: bad argument (K, the maps and 0 / 4 / 5 / 8 distortion coefficients are required)");
+    return fail(ORBFE_ERR_INVALID, "init_undistort_rectify_map: bad argument (K, the maps and 0 / 4 / 5 / 8 distortion coefficients are required)");
   static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   const double *Rm = R ? R : I3, *Ar = P ? P : K;
   // iR = (P * R)^-1: nine dot products and cv::invert's closed 3 x 3 form -- a dozen double operations of set-up, evaluated
@@ -462,7 +462,7 @@ extern "C" int orbfe_init_undistort_rectify_map(int device, const double* K, con
       M[3 * i + j] = acc;
     }
   double d = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-  if (d == 0) return ifail(ORBFE_ERR_INVALID, "init_undistort_rectify_map: P * R is singular");
+  if (d == 0) return fail(ORBFE_ERR_INVALID, "init_undistort_rectify_map: P * R is singular");
   d = 1. / d;
   RectifyMapParams p;
   p.ir[0] = (M[4] * M[8] - M[5] * M[7]) * d; p.ir[1] = (M[2] * M[7] - M[1] * M[8]) * d; p.ir[2] = (M[1] * M[5] - M[2] * M[4]) * d;
@@ -481,7 +481,7 @@ extern "C" int orbfe_init_undistort_rectify_map(int device, const double* K, con
   if (err == hipSuccess) err = hipMemcpy(map_x, dmap, n * 4, hipMemcpyDeviceToHost);
   if (err == hipSuccess) err = hipMemcpy(map_y, dmap + n, n * 4, hipMemcpyDeviceToHost);
   (void)hipFree(dmap);
-  if (err != hipSuccess) return ifail(ORBFE_ERR_HIP, std::string("init_undistort_rectify_map: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("init_undistort_rectify_map: ") + hipGetErrorString(err));
   return ORBFE_OK;
 }
 
@@ -489,7 +489,7 @@ extern "C" int orbfe_undistort_points(int device, const float* xy, int n, const 
                                       int n_dist, float* out_xy) {
   UndistortParams p;
   if (n < 0 || (n > 0 && (!xy || !out_xy)) || !undistort_params(K4, dist, n_dist, &p))
-    return ifail(ORBFE_ERR_INVALID, "undistort_points: bad argument");
+    return fail(ORBFE_ERR_INVALID, "undistort_points: bad argument");
   if (n == 0) return ORBFE_OK;
   IHIP(hipSetDevice(device));
   float *din = nullptr, *dout = nullptr;
@@ -503,7 +503,7 @@ extern "C" int orbfe_undistort_points(int device, const float* xy, int n, const 
   if (err == hipSuccess) err = hipMemcpy(out_xy, dout, (size_t)n * 8, hipMemcpyDeviceToHost);
   (void)hipFree(din);
   if (dout) (void)hipFree(dout);
-  if (err != hipSuccess) return ifail(ORBFE_ERR_HIP, std::string("undistort_points: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("undistort_points: ") + hipGetErrorString(err));
   return ORBFE_OK;
 }
 
@@ -513,7 +513,7 @@ extern "C" int orbfe_undistort_keypoints_batch_device(int device, const orbfe_ke
                                                       orbfe_keypoint* d_keypoints_un) {
   UndistortParams p;
   if (!d_keypoints || !d_n || !d_keypoints_un || n_frames < 0 || capacity <= 0 || !undistort_params(K4, dist, n_dist, &p))
-    return ifail(ORBFE_ERR_INVALID, "undistort_keypoints_batch_device: bad argument");
+    return fail(ORBFE_ERR_INVALID, "undistort_keypoints_batch_device: bad argument");
   if (n_frames == 0) return ORBFE_OK;
   IHIP(hipSetDevice(device));
   hipLaunchKernelGGL(k_undistort_keypoints, dim3((capacity + 255) / 256, n_frames), dim3(256), 0, 0, p,
@@ -525,7 +525,7 @@ extern "C" int orbfe_undistort_keypoints_batch_device(int device, const orbfe_ke
 
 extern "C" int orbfe_compute_image_bounds(int device, int cols, int rows, const float* K4, const float* dist,
                                           int n_dist, float* bounds4) {
-  if (!bounds4 || cols <= 0 || rows <= 0) return ifail(ORBFE_ERR_INVALID, "compute_image_bounds: bad argument");
+  if (!bounds4 || cols <= 0 || rows <= 0) return fail(ORBFE_ERR_INVALID, "compute_image_bounds: bad argument");
   if (n_dist > 0 && dist && dist[0] != 0.0) {
     const float in[8] = {0.0f, 0.0f, (float)cols, 0.0f, 0.0f, (float)rows, (float)cols, (float)rows};
     float out[8];
@@ -546,10 +546,10 @@ extern "C" int orbfe_stereo_from_rgbd(int device, const float* kx, const float* 
                                       float* u_right, float* depth) {
   if (n < 0 || width <= 0 || height <= 0 || stride_floats < width || !depth_image ||
       (n > 0 && (!kx || !ky || !kux || !u_right || !depth)))
-    return ifail(ORBFE_ERR_INVALID, "stereo_from_rgbd: bad argument");
+    return fail(ORBFE_ERR_INVALID, "stereo_from_rgbd: bad argument");
   for (int i = 0; i < n; i++)
     if (!(kx[i] >= 0 && ky[i] >= 0 && (int)kx[i] < width && (int)ky[i] < height))
-      return ifail(ORBFE_ERR_INVALID, "stereo_from_rgbd: keypoint outside the depth image");
+      return fail(ORBFE_ERR_INVALID, "stereo_from_rgbd: keypoint outside the depth image");
   if (n == 0) return ORBFE_OK;
   IHIP(hipSetDevice(device));
   float* buf = nullptr;
@@ -567,6 +567,6 @@ extern "C" int orbfe_stereo_from_rgbd(int device, const float* kx, const float* 
   if (err == hipSuccess) err = hipMemcpy(u_right, dur, (size_t)n * 4, hipMemcpyDeviceToHost);
   if (err == hipSuccess) err = hipMemcpy(depth, ddp, (size_t)n * 4, hipMemcpyDeviceToHost);
   (void)hipFree(buf);
-  if (err != hipSuccess) return ifail(ORBFE_ERR_HIP, std::string("stereo_from_rgbd: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("stereo_from_rgbd: ") + hipGetErrorString(err));
   return ORBFE_OK;
 }

@@ -14,14 +14,11 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "host_internal.h"
 #include "kernels.h"
 #include "match_kernels.h"
 
 using namespace orbfe;
-
-static thread_local std::string g_merr = "";
-extern "C" const char* orbfe_last_error(void);  // extractor.hip owns the generic one
-static int mfail(int code, const std::string& msg);
 
 namespace {
 
@@ -34,6 +31,7 @@ struct Arena {
   // dirty range in ONE host-to-device copy before the first kernel of the call
   uint8_t* hmirror = nullptr;
   size_t hcap = 0, dirtyLo = 0, dirtyHi = 0;
+  bool sizing = false;  // arena_stage()'s first pass: carve() only advances `used`, up() / up_fill() copy nothing
   ~Arena() {
     if (device >= 0) {
       (void)hipSetDevice(device);
@@ -73,7 +71,7 @@ template <typename T>
 T* carve(Arena* a, size_t n) {
   size_t off = (a->used + 255) & ~(size_t)255;
   a->used = off + n * sizeof(T);
-  return reinterpret_cast<T*>(a->base + off);
+  return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(a->base) + off);
 }
 inline size_t pad(size_t bytes) { return ((bytes + 255) & ~(size_t)255) + 256; }
 
@@ -102,7 +100,7 @@ inline void mark_dirty(Arena* a, size_t off, size_t bytes) {
 template <typename T>
 hipError_t up(Arena* a, T** d, const T* h, size_t n) {
   *d = carve<T>(a, n ? n : 1);
-  if (n == 0) return hipSuccess;
+  if (n == 0 || a->sizing) return hipSuccess;
   const size_t off = (size_t)(reinterpret_cast<uint8_t*>(*d) - a->base), bytes = n * sizeof(T);
   hipError_t e = grow_mirror(a, off + bytes);
   if (e != hipSuccess) return e;
@@ -115,6 +113,7 @@ hipError_t up(Arena* a, T** d, const T* h, size_t n) {
 template <typename T>
 hipError_t up_fill(Arena* a, T** d, size_t n, int byteValue) {
   *d = carve<T>(a, n ? n : 1);
+  if (a->sizing) return hipSuccess;
   const size_t off = (size_t)(reinterpret_cast<uint8_t*>(*d) - a->base), bytes = (n ? n : 1) * sizeof(T);
   hipError_t e = grow_mirror(a, off + bytes);
   if (e != hipSuccess) return e;
@@ -144,6 +143,60 @@ hipError_t flush(Arena* a) {
   return e;
 }
 
+// Stages a call: runs `stage` -- the up() / up_fill() / carve() calls of the call -- twice, first on a sizing arena that
+// only counts, then on the calling thread's arena of `device`, begun with exactly what the first pass carved: the size
+// cannot drift from the carving.  `stage` must compute the same sizes in both passes.
+template <typename F>
+hipError_t arena_stage(int device, Arena** out, F&& stage) {
+  Arena sizing;
+  sizing.sizing = true;
+  hipError_t e = stage(&sizing);
+  if (e == hipSuccess) e = arena_begin(device, sizing.used, out);
+  if (e == hipSuccess) e = stage(*out);
+  return e;
+}
+
+// Pinned staging of the calling thread: every input array of a call is packed into it and travels in
+// ONE host-to-device copy, counts + candidate lists come back in ONE copy (13 + 2 small transfers of
+// ~7 us each were most of a call before).
+struct Staging {
+  uint8_t* h = nullptr;
+  size_t cap = 0;
+  hipEvent_t pending = nullptr;  // an asynchronous copy OUT of the buffer that nobody waited for (orbfe_frame_upload): the
+  bool isPending = false;        // next use of the buffer waits for it first
+  ~Staging() {
+    if (h) (void)hipHostFree(h);
+    if (pending) (void)hipEventDestroy(pending);
+  }
+};
+thread_local Staging t_staging;
+
+hipError_t staging_reserve(size_t bytes) {
+  if (t_staging.isPending) {  // (normally long done: the copy took microseconds, the caller's next call comes later)
+    hipError_t e = hipEventSynchronize(t_staging.pending);
+    if (e != hipSuccess) return e;
+    t_staging.isPending = false;
+  }
+  if (bytes <= t_staging.cap) return hipSuccess;
+  if (t_staging.h) (void)hipHostFree(t_staging.h);
+  t_staging.h = nullptr;
+  t_staging.cap = 0;
+  const size_t want = bytes + bytes / 2 + (1u << 16);
+  hipError_t e = hipHostMalloc((void**)&t_staging.h, want, hipHostMallocDefault);
+  if (e == hipSuccess) t_staging.cap = want;
+  return e;
+}
+// an asynchronous copy out of the staging buffer was enqueued on `s` and nobody waits for it: the next staging_reserve() does
+hipError_t staging_mark_pending(hipStream_t s) {
+  if (!t_staging.pending) {
+    hipError_t e = hipEventCreateWithFlags(&t_staging.pending, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+  }
+  hipError_t e = hipEventRecord(t_staging.pending, s);
+  if (e == hipSuccess) t_staging.isPending = true;
+  return e;
+}
+
 // merge-walk of the two ascending node-id lists (the std::map iteration + lower_bound of
 // src/ORBmatcher.cc:211-300)
 void shared_nodes(const orbfe_featvec* f1, const orbfe_featvec* f2, std::vector<NodePair>* out) {
@@ -159,11 +212,6 @@ void shared_nodes(const orbfe_featvec* f1, const orbfe_featvec* f2, std::vector<
     else b++;
   }
 }
-
-// pinned staging of the calling thread (defined with the window searches below)
-hipError_t staging_reserve_(size_t bytes);
-uint8_t* staging_ptr_();
-hipError_t staging_mark_pending_(hipStream_t s);
 
 bool featvec_ok(const orbfe_featvec* f, int n) {
   if (!f || f->n_nodes < 0) return false;
@@ -182,19 +230,20 @@ bool featvec_ok(const orbfe_featvec* f, int n) {
 
 }  // namespace
 
-static int mfail(int code, const std::string& msg) {
-  // route through the shared thread-local error text
-  extern int orbfe_set_error_(int, const char*);
-  return orbfe_set_error_(code, msg.c_str());
-}
 #define MHIP(expr)                                                                       \
   do {                                                                                   \
     hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    if (_e != hipSuccess) return fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+// (in a function that returns hipError_t)
+#define TRY(expr)                      \
+  do {                                 \
+    hipError_t _e = (expr);            \
+    if (_e != hipSuccess) return _e;   \
   } while (0)
 
 extern "C" int orbfe_descriptor_distance(int device, const uint8_t* a, const uint8_t* b, int n, int32_t* out) {
-  if (n < 0 || (n > 0 && (!a || !b || !out))) return mfail(ORBFE_ERR_INVALID, "descriptor_distance: bad argument");
+  if (n < 0 || (n > 0 && (!a || !b || !out))) return fail(ORBFE_ERR_INVALID, "descriptor_distance: bad argument");
   if (n == 0) return ORBFE_OK;
   Arena* ar;
   MHIP(arena_begin(device, 2 * pad((size_t)n * 32) + pad((size_t)n * 4), &ar));
@@ -212,7 +261,7 @@ extern "C" int orbfe_descriptor_distance(int device, const uint8_t* a, const uin
 
 extern "C" int orbfe_hamming_matrix(int device, const uint8_t* d1, int n1, const uint8_t* d2, int n2, int32_t* out) {
   if (n1 < 0 || n2 < 0 || ((n1 > 0 && n2 > 0) && (!d1 || !d2 || !out)))
-    return mfail(ORBFE_ERR_INVALID, "hamming_matrix: bad argument");
+    return fail(ORBFE_ERR_INVALID, "hamming_matrix: bad argument");
   if (n1 == 0 || n2 == 0) return ORBFE_OK;
   Arena* ar;
   MHIP(arena_begin(device, pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + pad((size_t)n1 * n2 * 4), &ar));
@@ -226,153 +275,6 @@ extern "C" int orbfe_hamming_matrix(int device, const uint8_t* d1, int n1, const
   MHIP(hipMemcpyAsync(out, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost, ar->stream));
   MHIP(hipStreamSynchronize(ar->stream));
   return ORBFE_OK;
-}
-
-static int bow_common(int device, const uint8_t* desc1, const uint8_t* has_mp1, const float* angle1, int n1,
-                      const orbfe_featvec* fv1, const uint8_t* desc2, const uint8_t* has_mp2, const float* angle2,
-                      int n2, const orbfe_featvec* fv2, float nnratio, int check_ori, int kfkf, int32_t* match) {
-  if (n1 < 0 || n2 < 0 || !match) return mfail(ORBFE_ERR_INVALID, "search_by_bow: bad argument");
-  const int nOut = kfkf ? n1 : n2;
-  for (int i = 0; i < nOut; i++) match[i] = -1;
-  if (n1 == 0 || n2 == 0) return 0;
-  if (!desc1 || !has_mp1 || !angle1 || !desc2 || !angle2 || (kfkf && !has_mp2))
-    return mfail(ORBFE_ERR_INVALID, "search_by_bow: NULL input");
-  if (!featvec_ok(fv1, n1) || !featvec_ok(fv2, n2)) return mfail(ORBFE_ERR_INVALID, "search_by_bow: malformed FeatureVector");
-  std::vector<NodePair> pairs;
-  shared_nodes(fv1, fv2, &pairs);
-  if (pairs.empty()) return 0;
-  int maxCnt2 = 0;
-  for (const NodePair& p : pairs) maxCnt2 = p.cnt2 > maxCnt2 ? p.cnt2 : maxCnt2;
-  if (maxCnt2 > 65535) return mfail(ORBFE_ERR_INVALID, "search_by_bow: more than 65535 features in one node");
-  const size_t t1 = fv1->offsets[fv1->n_nodes], t2 = fv2->offsets[fv2->n_nodes];
-  Arena* ar;
-  MHIP(arena_begin(device, pad(pairs.size() * sizeof(NodePair)) + pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + 2 * pad(n1) +
-                               2 * pad(n2) + 2 * pad((size_t)n1 * 4) + 2 * pad((size_t)n2 * 4) + pad(t1 * 4) + pad(t2 * 4) + 4096, &ar));
-  BowArgs a = {};
-  NodePair* dp;
-  MHIP(up(ar, &dp, pairs.data(), pairs.size()));
-  uint8_t *dd1, *dd2, *dm1, *dm2 = nullptr;
-  float *da1, *da2;
-  uint32_t *di1, *di2;
-  MHIP(up(ar, &dd1, desc1, (size_t)n1 * 32));
-  MHIP(up(ar, &dd2, desc2, (size_t)n2 * 32));
-  MHIP(up(ar, &dm1, has_mp1, (size_t)n1));
-  if (kfkf) MHIP(up(ar, &dm2, has_mp2, (size_t)n2));
-  MHIP(up(ar, &da1, angle1, (size_t)n1));
-  MHIP(up(ar, &da2, angle2, (size_t)n2));
-  MHIP(up(ar, &di1, fv1->indices, t1));
-  MHIP(up(ar, &di2, fv2->indices, t2));
-  int32_t* dmatch;
-  int8_t* dbin;
-  MHIP(up_fill(ar, &dmatch, (size_t)nOut, 0xff));
-  int32_t* dcount = carve<int32_t>(ar, 1);
-  MHIP(up_fill(ar, &dbin, (size_t)nOut, 0));
-  a.pairs = dp; a.desc1 = dd1; a.hasMp1 = dm1; a.angle1 = da1; a.indices1 = di1;
-  a.desc2 = dd2; a.hasMp2 = dm2; a.angle2 = da2; a.indices2 = di2;
-  a.angleStride = 1;
-  a.nnratio = nnratio; a.strictLow = kfkf; a.match = dmatch; a.bin = dbin;
-  MHIP(flush(ar));
-  launch_search_by_bow(ar->stream, a, (int)pairs.size(), maxCnt2);
-  launch_rot_prune(ar->stream, dmatch, dbin, nOut, check_ori, dcount);
-  MHIP(hipGetLastError());
-  MHIP(down_range(ar, dmatch, dcount + 1));  // match[nOut] and the count, contiguous in the arena
-  MHIP(hipStreamSynchronize(ar->stream));
-  std::memcpy(match, mirror_of(ar, dmatch), (size_t)nOut * 4);
-  return *mirror_of(ar, dcount);
-}
-
-extern "C" int orbfe_search_by_bow(int device, const uint8_t* desc1, const uint8_t* has_mp1, const float* angle1,
-                                   int n1, const orbfe_featvec* fv1, const uint8_t* desc2, const float* angle2,
-                                   int n2, const orbfe_featvec* fv2, float nnratio, int check_orientation,
-                                   int32_t* match_f) {
-  return bow_common(device, desc1, has_mp1, angle1, n1, fv1, desc2, nullptr, angle2, n2, fv2, nnratio,
-                    check_orientation, 0, match_f);
-}
-extern "C" int orbfe_search_by_bow_kf(int device, const uint8_t* desc1, const uint8_t* has_mp1, const float* angle1,
-                                      int n1, const orbfe_featvec* fv1, const uint8_t* desc2,
-                                      const uint8_t* has_mp2, const float* angle2, int n2,
-                                      const orbfe_featvec* fv2, float nnratio, int check_orientation,
-                                      int32_t* match12) {
-  return bow_common(device, desc1, has_mp1, angle1, n1, fv1, desc2, has_mp2, angle2, n2, fv2, nnratio,
-                    check_orientation, 1, match12);
-}
-
-extern "C" int orbfe_search_for_triangulation(int device, const uint8_t* desc1, const uint8_t* has_mp1,
-                                              const float* x1, const float* y1, const float* angle1,
-                                              const uint8_t* stereo1, int n1, const orbfe_featvec* fv1,
-                                              const uint8_t* desc2, const uint8_t* has_mp2, const float* x2,
-                                              const float* y2, const float* angle2, const int32_t* octave2,
-                                              const uint8_t* stereo2, int n2, const orbfe_featvec* fv2,
-                                              const float* F12, float ex, float ey, const float* scale_factors2,
-                                              const float* level_sigma2_2, int n_levels2, int only_stereo,
-                                              int check_orientation, int32_t* match12) {
-  if (n1 < 0 || n2 < 0 || !match12) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation: bad argument");
-  for (int i = 0; i < n1; i++) match12[i] = -1;
-  if (n1 == 0 || n2 == 0) return 0;
-  if (!desc1 || !has_mp1 || !x1 || !y1 || !angle1 || !stereo1 || !desc2 || !has_mp2 || !x2 || !y2 || !angle2 ||
-      !octave2 || !stereo2 || !F12 || !scale_factors2 || !level_sigma2_2 || n_levels2 <= 0 || n_levels2 > ORBFE_MAX_LEVELS)
-    return mfail(ORBFE_ERR_INVALID, "search_for_triangulation: NULL input");
-  if (!featvec_ok(fv1, n1) || !featvec_ok(fv2, n2)) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation: malformed FeatureVector");
-  for (int i = 0; i < n2; i++)
-    if (octave2[i] < 0 || octave2[i] >= n_levels2) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation: octave out of range");
-  std::vector<NodePair> pairs;
-  shared_nodes(fv1, fv2, &pairs);
-  std::vector<TriQuery> queries;
-  for (const NodePair& p : pairs) {
-    if (p.cnt2 > 65535) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation: more than 65535 features in one node");
-    for (int i = 0; i < p.cnt1; i++) {
-      const uint32_t idx1 = fv1->indices[p.off1 + i];
-      if (has_mp1[idx1]) continue;                    // :800-803
-      if (only_stereo && !stereo1[idx1]) continue;    // :807-809
-      queries.push_back(TriQuery{idx1, p.off2, p.cnt2});
-    }
-  }
-  if (queries.empty()) return 0;
-  const size_t t2 = fv2->offsets[fv2->n_nodes];
-  Arena* ar;
-  MHIP(arena_begin(device, pad(queries.size() * sizeof(TriQuery)) + pad((size_t)n1 * 32) + pad((size_t)n2 * 32) +
-                               4 * pad((size_t)n1 * 4) + 6 * pad((size_t)n2 * 4) + 2 * pad(n1) + 2 * pad(n2) + pad(t2 * 4) + 8192, &ar));
-  TriArgs a = {};
-  TriQuery* dq;
-  MHIP(up(ar, &dq, queries.data(), queries.size()));
-  uint8_t *dd1, *dd2, *ds1, *ds2, *dm2;
-  float *dx1, *dy1, *da1, *dx2, *dy2, *da2, *dF, *dsf, *dsg;
-  int32_t* doc2;
-  uint32_t* di2;
-  MHIP(up(ar, &dd1, desc1, (size_t)n1 * 32));
-  MHIP(up(ar, &dd2, desc2, (size_t)n2 * 32));
-  MHIP(up(ar, &ds1, stereo1, (size_t)n1));
-  MHIP(up(ar, &ds2, stereo2, (size_t)n2));
-  MHIP(up(ar, &dm2, has_mp2, (size_t)n2));
-  MHIP(up(ar, &dx1, x1, (size_t)n1));
-  MHIP(up(ar, &dy1, y1, (size_t)n1));
-  MHIP(up(ar, &da1, angle1, (size_t)n1));
-  MHIP(up(ar, &dx2, x2, (size_t)n2));
-  MHIP(up(ar, &dy2, y2, (size_t)n2));
-  MHIP(up(ar, &da2, angle2, (size_t)n2));
-  MHIP(up(ar, &doc2, octave2, (size_t)n2));
-  MHIP(up(ar, &di2, fv2->indices, t2));
-  MHIP(up(ar, &dF, F12, (size_t)9));
-  MHIP(up(ar, &dsf, scale_factors2, (size_t)n_levels2));
-  MHIP(up(ar, &dsg, level_sigma2_2, (size_t)n_levels2));
-  int32_t* dmatch;
-  int8_t* dbin;
-  MHIP(up_fill(ar, &dmatch, (size_t)n1, 0xff));
-  int32_t* dcount = carve<int32_t>(ar, 1);
-  MHIP(up_fill(ar, &dbin, (size_t)n1, 0));
-  a.queries = dq; a.nQueries = (int)queries.size();
-  a.desc1 = dd1; a.x1 = dx1; a.y1 = dy1; a.angle1 = da1; a.stereo1 = ds1;
-  a.desc2 = dd2; a.hasMp2 = dm2; a.x2 = dx2; a.y2 = dy2; a.angle2 = da2; a.octave2 = doc2; a.stereo2 = ds2;
-  a.indices2 = di2; a.F12 = dF; a.ex = ex; a.ey = ey; a.scaleFactors2 = dsf; a.levelSigma2_2 = dsg;
-  a.onlyStereo = only_stereo; a.match = dmatch; a.bin = dbin;
-  MHIP(flush(ar));
-  launch_search_triangulation(ar->stream, a);
-  launch_rot_prune(ar->stream, dmatch, dbin, n1, check_orientation, dcount);
-  MHIP(hipGetLastError());
-  MHIP(down_range(ar, dmatch, dcount + 1));  // match12[n1] and the count, contiguous in the arena
-  MHIP(hipStreamSynchronize(ar->stream));
-  std::memcpy(match12, mirror_of(ar, dmatch), (size_t)n1 * 4);
-  return *mirror_of(ar, dcount);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -512,11 +414,11 @@ int frame_host_init(const char* who, int device, const orbfe_frame_view* v, cons
                     FrameLayout* L, size_t* nIdxOut) {
   if (!v || v->n < 0 || v->n > GRID_MAX_FEATURES || !(v->max_x > v->min_x) || !(v->max_y > v->min_y) ||
       (v->n > 0 && (!v->x || !v->y || !v->octave || !v->desc)))
-    return mfail(ORBFE_ERR_INVALID, std::string(who) + ": bad frame view (x, y, octave, desc and the image bounds are required)");
+    return fail(ORBFE_ERR_INVALID, std::string(who) + ": bad frame view (x, y, octave, desc and the image bounds are required)");
   const int n = v->n;
-  if (fv && !featvec_ok(fv, n)) return mfail(ORBFE_ERR_INVALID, std::string(who) + ": malformed FeatureVector");
+  if (fv && !featvec_ok(fv, n)) return fail(ORBFE_ERR_INVALID, std::string(who) + ": malformed FeatureVector");
   orbfe_frame* f = new (std::nothrow) orbfe_frame();
-  if (!f) return mfail(ORBFE_ERR_NOMEM, "out of memory");
+  if (!f) return fail(ORBFE_ERR_NOMEM, "out of memory");
   f->device = device; f->n = n;
   f->hx.assign(v->x, v->x + n); f->hy.assign(v->y, v->y + n); f->hoct.assign(v->octave, v->octave + n);
   f->hdesc.assign(v->desc, v->desc + (size_t)n * 32);
@@ -562,7 +464,7 @@ int frame_host_init(const char* who, int device, const orbfe_frame_view* v, cons
   if (err != hipSuccess) {
     const int code = err == hipErrorOutOfMemory ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP;
     orbfe_frame_release(f);
-    return mfail(code, std::string(who) + ": " + hipGetErrorString(err));
+    return fail(code, std::string(who) + ": " + hipGetErrorString(err));
   }
   f->settled.store(false);
   uint8_t* b = f->slab;
@@ -589,7 +491,7 @@ hipError_t frame_finish(Arena* ar, orbfe_frame* f, const orbfe_frame_view* v) {
 }  // namespace
 
 extern "C" int orbfe_frame_upload(int device, const orbfe_frame_view* v, const orbfe_featvec* fv, orbfe_frame** out) {
-  if (!out) return mfail(ORBFE_ERR_INVALID, "frame_upload: NULL argument");
+  if (!out) return fail(ORBFE_ERR_INVALID, "frame_upload: NULL argument");
   *out = nullptr;
   orbfe_frame* f = nullptr;
   FrameLayout L;
@@ -602,9 +504,9 @@ extern "C" int orbfe_frame_upload(int device, const orbfe_frame_view* v, const o
   Arena* ar;
   // staged through the thread's pinned mirror: one copy up, then the grid build (Frame::AssignFeaturesToGrid, once)
   hipError_t err = arena_begin(device, 1024, &ar);
-  if (err == hipSuccess) err = staging_reserve_(upBytes);
+  if (err == hipSuccess) err = staging_reserve(upBytes);
   if (err == hipSuccess) {
-    uint8_t* h = staging_ptr_();
+    uint8_t* h = t_staging.h;
     if (n) {
       std::memcpy(h + L.oX, f->hx.data(), (size_t)n * 4); std::memcpy(h + L.oY, f->hy.data(), (size_t)n * 4);
       if (v->angle) std::memcpy(h + L.oA, f->hangle.data(), (size_t)n * 4); else std::memset(h + L.oA, 0, (size_t)n * 4);
@@ -616,10 +518,10 @@ extern "C" int orbfe_frame_upload(int device, const orbfe_frame_view* v, const o
     if (nIdx) std::memcpy(h + L.oI, f->hindices.data(), nIdx * 4);
     // ONE copy (every further hipMemcpyAsync costs the host ~5 us)
     err = hipMemcpyAsync(f->slab, h, upBytes, hipMemcpyHostToDevice, ar->stream);
-    if (err == hipSuccess) err = staging_mark_pending_(ar->stream);  // the next use of the staging buffer waits for these copies
+    if (err == hipSuccess) err = staging_mark_pending(ar->stream);  // the next use of the staging buffer waits for these copies
   }
   if (err == hipSuccess) err = frame_finish(ar, f, v);
-  if (err != hipSuccess) { orbfe_frame_release(f); return mfail(ORBFE_ERR_HIP, std::string("frame_upload: ") + hipGetErrorString(err)); }
+  if (err != hipSuccess) { orbfe_frame_release(f); return fail(ORBFE_ERR_HIP, std::string("frame_upload: ") + hipGetErrorString(err)); }
   *out = f;
   return ORBFE_OK;
 }
@@ -632,9 +534,9 @@ extern "C" int orbfe_frame_upload(int device, const orbfe_frame_view* v, const o
 // UndistortKeyPoints); view->n records are taken.
 extern "C" int orbfe_frame_from_device(int device, const orbfe_keypoint* d_keypoints, const uint8_t* d_descriptors,
                                        const orbfe_frame_view* view, const orbfe_featvec* fv, int flags, orbfe_frame** out) {
-  if (!out) return mfail(ORBFE_ERR_INVALID, "frame_from_device: NULL argument");
+  if (!out) return fail(ORBFE_ERR_INVALID, "frame_from_device: NULL argument");
   *out = nullptr;
-  if (view && view->n > 0 && (!d_keypoints || !d_descriptors)) return mfail(ORBFE_ERR_INVALID, "frame_from_device: NULL device arrays");
+  if (view && view->n > 0 && (!d_keypoints || !d_descriptors)) return fail(ORBFE_ERR_INVALID, "frame_from_device: NULL device arrays");
   orbfe_frame* f = nullptr;
   FrameLayout L;
   size_t nIdx = 0;
@@ -648,15 +550,15 @@ extern "C" int orbfe_frame_from_device(int device, const orbfe_keypoint* d_keypo
   // ONE copy through the pinned staging
   const size_t hostBytes = xyFromView ? L.oA : L.oX;
   const bool anyHost = view->u_right || nIdx || xyFromView;
-  if (err == hipSuccess && anyHost) err = staging_reserve_(hostBytes);
+  if (err == hipSuccess && anyHost) err = staging_reserve(hostBytes);
   if (err == hipSuccess && n && anyHost) {
-    uint8_t* h = staging_ptr_();
+    uint8_t* h = t_staging.h;
     if (view->u_right) { std::memcpy(h + L.oU, f->hur.data(), (size_t)n * 4); std::memcpy(h + L.oS, f->hstereo.data(), (size_t)n); }
     else { std::memset(h + L.oU, 0, (size_t)n * 4); std::memset(h + L.oS, 0, (size_t)n); }
     if (nIdx) std::memcpy(h + L.oI, f->hindices.data(), nIdx * 4);
     if (xyFromView) { std::memcpy(h + L.oX, f->hx.data(), (size_t)n * 4); std::memcpy(h + L.oY, f->hy.data(), (size_t)n * 4); }
     err = hipMemcpyAsync(f->slab, h, hostBytes, hipMemcpyHostToDevice, ar->stream);
-    if (err == hipSuccess) err = staging_mark_pending_(ar->stream);
+    if (err == hipSuccess) err = staging_mark_pending(ar->stream);
   }
   if (err == hipSuccess && n) {
     launch_frame_from_records(ar->stream, reinterpret_cast<const float*>(d_keypoints), d_descriptors, n, xyFromView ? nullptr : f->dx,
@@ -664,27 +566,21 @@ extern "C" int orbfe_frame_from_device(int device, const orbfe_keypoint* d_keypo
     err = hipGetLastError();
   }
   if (err == hipSuccess) err = frame_finish(ar, f, view);
-  if (err != hipSuccess) { orbfe_frame_release(f); return mfail(ORBFE_ERR_HIP, std::string("frame_from_device: ") + hipGetErrorString(err)); }
+  if (err != hipSuccess) { orbfe_frame_release(f); return fail(ORBFE_ERR_HIP, std::string("frame_from_device: ") + hipGetErrorString(err)); }
   *out = f;
   return ORBFE_OK;
 }
 
-// implemented in extractor.hip: device pointers of frame `frame` of the handle's own output block (the host-buffer calls)
-extern "C" int orbfe_extractor_output_device_(orbfe_extractor* e, int frame, const orbfe_keypoint** d_kp, const uint8_t** d_desc,
-                                              int* n, int* device);
-
-extern "C" int orbfe_extractor_reader_end_(orbfe_extractor* e, hipStream_t s);
-
 extern "C" int orbfe_frame_from_extractor(orbfe_extractor* e, int frame, const orbfe_frame_view* view, const orbfe_featvec* fv,
                                           int flags, orbfe_frame** out) {
-  if (!out) return mfail(ORBFE_ERR_INVALID, "frame_from_extractor: NULL argument");
+  if (!out) return fail(ORBFE_ERR_INVALID, "frame_from_extractor: NULL argument");
   *out = nullptr;
   const orbfe_keypoint* dkp = nullptr;
   const uint8_t* ddesc = nullptr;
   int n = 0, device = 0;
   int rc = orbfe_extractor_output_device_(e, frame, &dkp, &ddesc, &n, &device);
   if (rc != ORBFE_OK) return rc;
-  if (!view || view->n > n) return mfail(ORBFE_ERR_INVALID, "frame_from_extractor: the view holds more keypoints than the extractor produced for this frame");
+  if (!view || view->n > n) return fail(ORBFE_ERR_INVALID, "frame_from_extractor: the view holds more keypoints than the extractor produced for this frame");
   rc = orbfe_frame_from_device(device, dkp, ddesc, view, fv, flags, out);
   if (rc != ORBFE_OK) return rc;
   // the build reads the handle's output block on this thread's stream without a host wait: the handle's next call that
@@ -699,10 +595,10 @@ extern "C" int orbfe_frame_from_extractor(orbfe_extractor* e, int frame, const o
 // the calling thread may differ from the building one (LocalMapping's KeyFrame::ComputeBoW): frame_use orders the copy.
 extern "C" int orbfe_frame_set_featvec(orbfe_frame* f, const orbfe_featvec* fv) {
   UnsettledScope unsettledScope;
-  if (!f || !fv) return mfail(ORBFE_ERR_INVALID, "frame_set_featvec: NULL argument");
-  if (!featvec_ok(fv, f->n)) return mfail(ORBFE_ERR_INVALID, "frame_set_featvec: malformed FeatureVector");
+  if (!f || !fv) return fail(ORBFE_ERR_INVALID, "frame_set_featvec: NULL argument");
+  if (!featvec_ok(fv, f->n)) return fail(ORBFE_ERR_INVALID, "frame_set_featvec: malformed FeatureVector");
   const size_t nIdx = fv->n_nodes > 0 ? (size_t)fv->offsets[fv->n_nodes] : 0;
-  if (nIdx > (size_t)(f->n ? f->n : 1)) return mfail(ORBFE_ERR_INVALID, "frame_set_featvec: more indices than features");
+  if (nIdx > (size_t)(f->n ? f->n : 1)) return fail(ORBFE_ERR_INVALID, "frame_set_featvec: more indices than features");
   if (fv->n_nodes > 0) {
     f->nodeIds.assign(fv->node_ids, fv->node_ids + fv->n_nodes);
     f->offsets.assign(fv->offsets, fv->offsets + fv->n_nodes + 1);
@@ -715,188 +611,156 @@ extern "C" int orbfe_frame_set_featvec(orbfe_frame* f, const orbfe_featvec* fv) 
   if (nIdx == 0) return ORBFE_OK;
   Arena* ar;
   hipError_t err = arena_begin(f->device, 1024, &ar);
-  if (err == hipSuccess) err = staging_reserve_(nIdx * 4);
+  if (err == hipSuccess) err = staging_reserve(nIdx * 4);
   // the frame's own build copy covers the index region and may still be queued on the building thread's stream
   if (err == hipSuccess) err = frame_use(ar, f);
   if (err == hipSuccess) {
-    std::memcpy(staging_ptr_(), f->hindices.data(), nIdx * 4);
-    err = hipMemcpyAsync(f->dindices, staging_ptr_(), nIdx * 4, hipMemcpyHostToDevice, ar->stream);
+    std::memcpy(t_staging.h, f->hindices.data(), nIdx * 4);
+    err = hipMemcpyAsync(f->dindices, t_staging.h, nIdx * 4, hipMemcpyHostToDevice, ar->stream);
   }
   if (err == hipSuccess) err = hipStreamSynchronize(ar->stream);  // (the handle may be in use on other streams afterwards)
-  if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("frame_set_featvec: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("frame_set_featvec: ") + hipGetErrorString(err));
   frames_settle();
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_frame_synchronize(const orbfe_frame* f) {
-  if (!f) return mfail(ORBFE_ERR_INVALID, "frame_synchronize: NULL frame");
+  if (!f) return fail(ORBFE_ERR_INVALID, "frame_synchronize: NULL frame");
   if (f->settled.load(std::memory_order_acquire)) return ORBFE_OK;
   hipError_t err = hipSetDevice(f->device);
   if (err == hipSuccess) err = hipEventSynchronize(f->ready);
-  if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("frame_synchronize: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("frame_synchronize: ") + hipGetErrorString(err));
   f->settled.store(true, std::memory_order_release);
   return ORBFE_OK;
 }
 
 // ---- test hook (tests/stream_order.py): hold back / query the calling thread's matcher stream on `device` ----
-extern "C" int orbfe_debug_stall_launch_(hipStream_t s, int usec);
-extern "C" int orbfe_debug_stream_idle_(hipStream_t s);
-
 extern "C" int orbfe_debug_stall_thread_stream(int device, int usec) {
-  if (usec < 0 || usec > 1000000) return mfail(ORBFE_ERR_INVALID, "debug_stall: usec must be 0 .. 1000000");
+  if (usec < 0 || usec > 1000000) return fail(ORBFE_ERR_INVALID, "debug_stall: usec must be 0 .. 1000000");
   Arena* ar;
   hipError_t err = arena_begin(device, 0, &ar);
-  if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("debug_stall: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("debug_stall: ") + hipGetErrorString(err));
   return orbfe_debug_stall_launch_(ar->stream, usec);
 }
 
 extern "C" int orbfe_debug_thread_stream_idle(int device) {
   Arena* ar;
   hipError_t err = arena_begin(device, 0, &ar);
-  if (err != hipSuccess) return mfail(ORBFE_ERR_HIP, std::string("debug_stream_idle: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("debug_stream_idle: ") + hipGetErrorString(err));
   return orbfe_debug_stream_idle_(ar->stream);
 }
 
-// ---- the FeatureVector searches on resident frames: per call only the shared-node list, the map-point masks and
-//      the result arrays travel ----
-static int bow_resident(const orbfe_frame* k1, const uint8_t* has_mp1, const orbfe_frame* k2, const uint8_t* has_mp2,
-                        float nnratio, int check_ori, int kfkf, int32_t* match) {
-  UnsettledScope unsettledScope;
-  if (!k1 || !k2 || !match) return mfail(ORBFE_ERR_INVALID, "search_by_bow_resident: NULL argument");
-  if (k1->device != k2->device) return mfail(ORBFE_ERR_INVALID, "search_by_bow_resident: frames on different devices");
-  const int n1 = k1->n, n2 = k2->n, nOut = kfkf ? n1 : n2;
-  for (int i = 0; i < nOut; i++) match[i] = -1;
-  if (n1 == 0 || n2 == 0) return 0;
-  if (!k1->haveFv || !k2->haveFv || k1->hangle.empty() || k2->hangle.empty() || !has_mp1 || (kfkf && !has_mp2))
-    return mfail(ORBFE_ERR_INVALID, "search_by_bow_resident: the frames were uploaded without FeatureVector / angles, or a mask is NULL");
-  std::vector<NodePair> pairs;
-  shared_nodes(&k1->fv, &k2->fv, &pairs);
-  if (pairs.empty()) return 0;
-  int maxCnt2 = 0;
-  for (const NodePair& p : pairs) maxCnt2 = p.cnt2 > maxCnt2 ? p.cnt2 : maxCnt2;
-  if (maxCnt2 > 65535) return mfail(ORBFE_ERR_INVALID, "search_by_bow: more than 65535 features in one node");
-  Arena* ar;
-  MHIP(arena_begin(k1->device, pad(pairs.size() * sizeof(NodePair)) + pad(n1) + pad(n2) + 2 * pad((size_t)nOut * 4) + 4096, &ar));
-  MHIP(frame_use(ar, k1));
-  MHIP(frame_use(ar, k2));
-  NodePair* dp;
-  uint8_t *dm1, *dm2 = nullptr;
-  MHIP(up(ar, &dp, pairs.data(), pairs.size()));
-  MHIP(up(ar, &dm1, has_mp1, (size_t)n1));
-  if (kfkf) MHIP(up(ar, &dm2, has_mp2, (size_t)n2));
-  int32_t* dmatch;
-  int8_t* dbin;
-  MHIP(up_fill(ar, &dmatch, (size_t)nOut, 0xff));
-  int32_t* dcount = carve<int32_t>(ar, 1);
-  MHIP(up_fill(ar, &dbin, (size_t)nOut, 0));
-  BowArgs a = {};
-  a.pairs = dp; a.desc1 = k1->ddesc; a.hasMp1 = dm1; a.angle1 = k1->dangle; a.indices1 = k1->dindices;
-  a.desc2 = k2->ddesc; a.hasMp2 = dm2; a.angle2 = k2->dangle; a.indices2 = k2->dindices;
-  a.angleStride = 1;
-  a.nnratio = nnratio; a.strictLow = kfkf; a.match = dmatch; a.bin = dbin;
-  MHIP(flush(ar));
-  launch_search_by_bow(ar->stream, a, (int)pairs.size(), maxCnt2);
-  launch_rot_prune(ar->stream, dmatch, dbin, nOut, check_ori, dcount);
-  MHIP(hipGetLastError());
-  MHIP(down_range(ar, dmatch, dcount + 1));
-  MHIP(hipStreamSynchronize(ar->stream));
-  frames_settle();
-  std::memcpy(match, mirror_of(ar, dmatch), (size_t)nOut * 4);
-  return *mirror_of(ar, dcount);
+// ---------------------------------------------------------------------------------------------
+// The FeatureVector searches, ORBmatcher::SearchByBoW and SearchForTriangulation: ONE implementation each, of one
+// operand against K others.  The entry points differ only in where an operand's arrays are -- host arrays travel with
+// the call, a resident frame has them on the device -- and in K.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// One side of a search.  h*: host arrays -- what a side without a frame uploads, and what the query list and the octave
+// check read; d*: what the kernels read.  Only what the search needs is set (SearchByBoW: no x / y / octave / stereo).
+struct FvSide {
+  int n = 0;
+  const orbfe_featvec* fv = nullptr;
+  const orbfe_frame* frame = nullptr;  // resident: the d* are the frame's own, frame_use() orders the call behind its upload
+  const uint8_t *hdesc = nullptr, *hstereo = nullptr;
+  const float *hangle = nullptr, *hx = nullptr, *hy = nullptr;
+  const int32_t* hoct = nullptr;
+  uint8_t *ddesc = nullptr, *dstereo = nullptr;
+  float *dangle = nullptr, *dx = nullptr, *dy = nullptr;
+  int32_t* doct = nullptr;
+  uint32_t* dindices = nullptr;
+};
+FvSide side_of_frame(const orbfe_frame* f) {
+  FvSide s;
+  s.n = f->n; s.fv = &f->fv; s.frame = f; s.hstereo = f->hstereo.data(); s.hoct = f->hoct.data();
+  s.ddesc = f->ddesc; s.dstereo = f->dstereo; s.dangle = f->dangle; s.dx = f->dx; s.dy = f->dy; s.doct = f->doct;
+  s.dindices = f->dindices;
+  return s;
+}
+// the host arrays of a side that no resident frame backs, into the arena
+hipError_t side_upload(Arena* a, FvSide* s, bool withIndices) {
+  const size_t n = (size_t)s->n;
+  if (s->frame) return hipSuccess;
+  if (s->hdesc) TRY(up(a, &s->ddesc, s->hdesc, n * 32));
+  if (s->hstereo) TRY(up(a, &s->dstereo, s->hstereo, n));
+  if (s->hx) TRY(up(a, &s->dx, s->hx, n));
+  if (s->hy) TRY(up(a, &s->dy, s->hy, n));
+  if (s->hangle) TRY(up(a, &s->dangle, s->hangle, n));
+  if (s->hoct) TRY(up(a, &s->doct, s->hoct, n));
+  if (withIndices && s->fv->n_nodes > 0) TRY(up(a, &s->dindices, s->fv->indices, (size_t)s->fv->offsets[s->fv->n_nodes]));
+  return hipSuccess;
 }
 
-extern "C" int orbfe_search_by_bow_resident(const orbfe_frame* kf, const uint8_t* has_mp_kf, const orbfe_frame* f,
-                                            float nnratio, int check_orientation, int32_t* match_f) {
-  return bow_resident(kf, has_mp_kf, f, nullptr, nnratio, check_orientation, 0, match_f);
-}
-extern "C" int orbfe_search_by_bow_kf_resident(const orbfe_frame* kf1, const uint8_t* has_mp1, const orbfe_frame* kf2,
-                                               const uint8_t* has_mp2, float nnratio, int check_orientation,
-                                               int32_t* match12) {
-  return bow_resident(kf1, has_mp1, kf2, has_mp2, nnratio, check_orientation, 1, match12);
-}
-
-// ORBmatcher::SearchByBoW of ONE frame / key frame against K candidate key frames in one call: Tracking::Relocalization
-// runs SearchByBoW(pKF_k, mCurrentFrame, ...) over every candidate (src/Tracking.cc:1478-1498), LoopClosing::ComputeSim3
-// SearchByBoW(mpCurrentKF, pKF_k, ...) (src/LoopClosing.cc:294-321).  A single resident call is a round trip of ~0.16 ms
-// whatever it computes; here the K shared-node lists and masks go up in ONE copy, K + 1 launches run back to back on one
-// stream, and the K match arrays with their counts come back in ONE copy.
-//   kfkf = 0: (KF_k, F):   key frame k on the `1` side (mask has_mp_k[k]), `one` = the frame; match [k * one->n + i2]
-//   kfkf = 1: (KF, KF_k):  `one` = the current key frame on the `1` side (mask has_mp_one), candidate k on the `2` side
-//                          (mask has_mp_k[k]); match [k * one->n + i1]
-static int bow_multi(const orbfe_frame* one, const uint8_t* has_mp_one, int K, const orbfe_frame* const* many,
-                     const uint8_t* const* has_mp_k, float nnratio, int check_ori, int kfkf, int32_t* match,
-                     int32_t* n_matches) {
+// SearchByBoW (src/ORBmatcher.cc:185-325, :327-464) of `one` against many[0 .. K): one upload, one group of launches,
+// one download, one synchronisation.
+//   kfkf = 0, (KF_k, F):  `one` is the frame (the `2` side), many[k] key frame k with mask masks[k]; match[k * one->n + i2]
+//   kfkf = 1, (KF, KF_k): `one` is the `1` side with mask maskOne, many[k] the `2` side with masks[k]; match[k * one->n + i1]
+// batch = 0 (K = 1): the single-problem kernels, and nothing runs when the two share no node.  The caller has checked the
+// operands and initialised match / n_matches; an empty many[k] is skipped.
+int bow_run(const char* who, int device, FvSide* one, const uint8_t* maskOne, int K, FvSide* many, const uint8_t* const* masks,
+            float nnratio, int check_ori, int kfkf, int batch, int32_t* match, int32_t* n_matches) {
   UnsettledScope unsettledScope;
-  if (!one || K < 0 || (K > 0 && (!many || !has_mp_k || !match || !n_matches)))
-    return mfail(ORBFE_ERR_INVALID, "search_by_bow_multi: bad argument");
   const int nOut = one->n;
-  for (size_t i = 0; i < (size_t)K * nOut; i++) match[i] = -1;
-  for (int k = 0; k < K; k++) n_matches[k] = 0;
-  if (K == 0 || nOut == 0) return ORBFE_OK;
-  if (!one->haveFv || one->hangle.empty() || (kfkf && !has_mp_one))
-    return mfail(ORBFE_ERR_INVALID, "search_by_bow_multi: frame uploaded without FeatureVector / angles, or NULL mask");
   std::vector<std::vector<NodePair>> pairs((size_t)K);
-  std::vector<int> maxCnt2((size_t)K, 0);
-  size_t bytes = pad((size_t)nOut) + 2 * pad((size_t)K * nOut * 4) + pad((size_t)K * 4) + pad((size_t)K * sizeof(BowArgs)) + pad((size_t)K * 4) + 8192;
+  int total = 0, maxCnt2 = 0;
   for (int k = 0; k < K; k++) {
-    const orbfe_frame* c = many[k];
-    if (!c || (c->n > 0 && !has_mp_k[k])) return mfail(ORBFE_ERR_INVALID, "search_by_bow_multi: NULL candidate or mask");
-    if (c->device != one->device) return mfail(ORBFE_ERR_INVALID, "search_by_bow_multi: frames on different devices");
-    if (c->n == 0) continue;
-    if (!c->haveFv || c->hangle.empty())
-      return mfail(ORBFE_ERR_INVALID, "search_by_bow_multi: candidate uploaded without FeatureVector / angles");
-    if (kfkf) shared_nodes(&one->fv, &c->fv, &pairs[k]); else shared_nodes(&c->fv, &one->fv, &pairs[k]);
-    for (const NodePair& p : pairs[k]) maxCnt2[k] = p.cnt2 > maxCnt2[k] ? p.cnt2 : maxCnt2[k];
-    if (maxCnt2[k] > 65535) return mfail(ORBFE_ERR_INVALID, "search_by_bow: more than 65535 features in one node");
-    bytes += pad(pairs[k].size() * sizeof(NodePair)) + pad((size_t)c->n);
+    if (many[k].n == 0) continue;
+    if (kfkf) shared_nodes(one->fv, many[k].fv, &pairs[k]); else shared_nodes(many[k].fv, one->fv, &pairs[k]);
+    for (const NodePair& p : pairs[k]) maxCnt2 = p.cnt2 > maxCnt2 ? p.cnt2 : maxCnt2;
+    if (maxCnt2 > 65535) return fail(ORBFE_ERR_INVALID, std::string(who) + ": more than 65535 features in one node");
+    total += (int)pairs[k].size();
   }
-  Arena* ar;
-  MHIP(arena_begin(one->device, bytes, &ar));
-  MHIP(frame_use(ar, one));
-  for (int k = 0; k < K; k++) MHIP(frame_use(ar, many[k]));
-  std::vector<NodePair*> dp((size_t)K, nullptr);
-  std::vector<uint8_t*> dmk((size_t)K, nullptr);
-  uint8_t* dmOne = nullptr;
-  if (kfkf) MHIP(up(ar, &dmOne, has_mp_one, (size_t)nOut));
-  for (int k = 0; k < K; k++) {
-    if (pairs[k].empty()) continue;
-    MHIP(up(ar, &dp[k], pairs[k].data(), pairs[k].size()));
-    MHIP(up(ar, &dmk[k], has_mp_k[k], (size_t)many[k]->n));
-  }
-  int32_t* dmatch;
-  int8_t* dbin;
-  MHIP(up_fill(ar, &dmatch, (size_t)K * nOut, 0xff));  // match arrays and counts adjacent: one copy back
-  int32_t* dcount;
-  MHIP(up_fill(ar, &dcount, (size_t)K, 0));
-  MHIP(up_fill(ar, &dbin, (size_t)K * nOut, 0));
-  // the K problems as ONE launch: operands of problem k in hargs[k], its node pairs numbered from pairStart[k]
+  if (!batch && total == 0) return ORBFE_OK;
+  // the problems as ONE launch: operands of problem k in hargs[k], its node pairs numbered from pairStart[k]
   std::vector<BowArgs> hargs;
   std::vector<int32_t> pairStart;
-  int total = 0, maxAll = 0;
-  for (int k = 0; k < K; k++) {
-    if (pairs[k].empty()) continue;
-    const orbfe_frame* c = many[k];
-    const orbfe_frame *f1 = kfkf ? one : c, *f2 = kfkf ? c : one;
-    BowArgs a = {};
-    a.pairs = dp[k];
-    a.desc1 = f1->ddesc; a.hasMp1 = kfkf ? dmOne : dmk[k]; a.angle1 = f1->dangle; a.indices1 = f1->dindices;
-    a.desc2 = f2->ddesc; a.hasMp2 = kfkf ? dmk[k] : nullptr; a.angle2 = f2->dangle; a.indices2 = f2->dindices;
-    a.angleStride = 1;
-    a.nnratio = nnratio; a.strictLow = kfkf; a.match = dmatch + (size_t)k * nOut; a.bin = dbin + (size_t)k * nOut;
-    hargs.push_back(a);
-    pairStart.push_back(total);
-    total += (int)pairs[k].size();
-    maxAll = maxCnt2[k] > maxAll ? maxCnt2[k] : maxAll;
-  }
   BowArgs* dargs = nullptr;
-  int32_t* dstart = nullptr;
-  if (!hargs.empty()) {
-    MHIP(up(ar, &dargs, hargs.data(), hargs.size()));
-    MHIP(up(ar, &dstart, pairStart.data(), pairStart.size()));
-  }
+  int32_t *dstart = nullptr, *dmatch = nullptr, *dcount = nullptr;
+  int8_t* dbin = nullptr;
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    uint8_t* dmOne = nullptr;
+    TRY(side_upload(a, one, true));
+    for (int k = 0; k < K; k++) TRY(side_upload(a, &many[k], true));
+    if (kfkf) TRY(up(a, &dmOne, maskOne, (size_t)nOut));
+    TRY(up_fill(a, &dmatch, (size_t)K * nOut, 0xff));  // match arrays and counts adjacent: one copy back
+    TRY(up_fill(a, &dcount, (size_t)K, 0));
+    TRY(up_fill(a, &dbin, (size_t)K * nOut, 0));
+    hargs.clear();
+    pairStart.clear();
+    for (int k = 0, start = 0; k < K; start += (int)pairs[k].size(), k++) {
+      if (pairs[k].empty()) continue;
+      const FvSide *f1 = kfkf ? one : &many[k], *f2 = kfkf ? &many[k] : one;
+      NodePair* dp;
+      uint8_t* dmk;
+      TRY(up(a, &dp, pairs[k].data(), pairs[k].size()));
+      TRY(up(a, &dmk, masks[k], (size_t)many[k].n));
+      BowArgs b = {};
+      b.pairs = dp;
+      b.desc1 = f1->ddesc; b.hasMp1 = kfkf ? dmOne : dmk; b.angle1 = f1->dangle; b.indices1 = f1->dindices;
+      b.desc2 = f2->ddesc; b.hasMp2 = kfkf ? dmk : nullptr; b.angle2 = f2->dangle; b.indices2 = f2->dindices;
+      b.angleStride = 1;
+      b.nnratio = nnratio; b.strictLow = kfkf; b.match = dmatch + (size_t)k * nOut; b.bin = dbin + (size_t)k * nOut;
+      hargs.push_back(b);
+      pairStart.push_back(start);
+    }
+    if (batch && !hargs.empty()) {
+      TRY(up(a, &dargs, hargs.data(), hargs.size()));
+      TRY(up(a, &dstart, pairStart.data(), pairStart.size()));
+    }
+    return hipSuccess;
+  };
+  MHIP(arena_stage(device, &ar, stage));
+  MHIP(frame_use(ar, one->frame));
+  for (int k = 0; k < K; k++) MHIP(frame_use(ar, many[k].frame));
   MHIP(flush(ar));
-  launch_search_by_bow_multi(ar->stream, dargs, dstart, (int)hargs.size(), total, maxAll);
-  launch_rot_prune_batch(ar->stream, dmatch, dbin, nOut, K, check_ori, dcount);  // all K histograms in one launch
+  if (batch) {
+    launch_search_by_bow_multi(ar->stream, dargs, dstart, (int)hargs.size(), total, maxCnt2);
+    launch_rot_prune_batch(ar->stream, dmatch, dbin, nOut, K, check_ori, dcount);  // all K histograms in one launch
+  } else {
+    launch_search_by_bow(ar->stream, hargs[0], total, maxCnt2);
+    launch_rot_prune(ar->stream, dmatch, dbin, nOut, check_ori, dcount);
+  }
   MHIP(hipGetLastError());
   MHIP(down_range(ar, dmatch, dcount + K));
   MHIP(hipStreamSynchronize(ar->stream));
@@ -906,6 +770,190 @@ static int bow_multi(const orbfe_frame* one, const uint8_t* has_mp_one, int K, c
   return ORBFE_OK;
 }
 
+// SearchForTriangulation (src/ORBmatcher.cc:657-822) of s1 against the neighbours many[0 .. K) (LocalMapping::
+// CreateNewMapPoints, src/LocalMapping.cc:256-315: the same mpCurrentKeyFrame, a new F12 per neighbour), in one round
+// trip as bow_run.  F12: [K * 9]; ex, ey: [K]; match12[k * s1->n + i1].  batch = 0 (K = 1): the single-array prune, and
+// nothing runs without a query.
+int tri_run(const char* who, int device, FvSide* s1, const uint8_t* has_mp1, int K, FvSide* many, const uint8_t* const* has_mp2,
+            const float* F12, const float* ex, const float* ey, const float* scale_factors2, const float* level_sigma2_2,
+            int n_levels2, int only_stereo, int check_ori, int batch, int32_t* match12, int32_t* n_matches) {
+  UnsettledScope unsettledScope;
+  const int n1 = s1->n;
+  // host: the shared nodes and the query list of every neighbour (:787-811)
+  std::vector<std::vector<TriQuery>> queries((size_t)K);
+  std::vector<NodePair> pairs;
+  size_t nQueries = 0;
+  for (int k = 0; k < K; k++) {
+    const FvSide& s2 = many[k];
+    for (int i = 0; i < s2.n; i++)
+      if (s2.hoct[i] < 0 || s2.hoct[i] >= n_levels2) return fail(ORBFE_ERR_INVALID, std::string(who) + ": octave out of range");
+    pairs.clear();
+    if (s2.n > 0) shared_nodes(s1->fv, s2.fv, &pairs);
+    for (const NodePair& p : pairs) {
+      if (p.cnt2 > 65535) return fail(ORBFE_ERR_INVALID, std::string(who) + ": more than 65535 features in one node");
+      for (int i = 0; i < p.cnt1; i++) {
+        const uint32_t idx1 = s1->fv->indices[p.off1 + i];
+        if (has_mp1[idx1]) continue;                       // :800-803
+        if (only_stereo && !s1->hstereo[idx1]) continue;   // :807-809
+        queries[k].push_back(TriQuery{idx1, p.off2, p.cnt2});
+      }
+    }
+    nQueries += queries[k].size();
+  }
+  if (!batch && nQueries == 0) return ORBFE_OK;
+  // the problems run as ONE launch: their argument blocks and first workgroups travel with the inputs
+  std::vector<TriArgs> targs;
+  std::vector<int32_t> blockStart;
+  int totalBlocks = 0;
+  TriArgs* dargs = nullptr;
+  int32_t *dstart = nullptr, *dmatch = nullptr, *dcount = nullptr;
+  int8_t* dbin = nullptr;
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    float *dF, *dsf, *dsg;
+    TRY(side_upload(a, s1, false));  // (the queries carry the `1` side's indices)
+    for (int k = 0; k < K; k++) TRY(side_upload(a, &many[k], true));
+    TRY(up(a, &dF, F12, (size_t)K * 9));
+    TRY(up(a, &dsf, scale_factors2, (size_t)n_levels2));
+    TRY(up(a, &dsg, level_sigma2_2, (size_t)n_levels2));
+    TRY(up_fill(a, &dmatch, (size_t)K * n1, 0xff));  // match arrays and counts adjacent: one copy back
+    TRY(up_fill(a, &dcount, (size_t)K, 0));
+    TRY(up_fill(a, &dbin, (size_t)K * n1, 0));
+    targs.clear();
+    blockStart.clear();
+    totalBlocks = 0;
+    for (int k = 0; k < K; k++) {
+      if (queries[k].empty()) continue;
+      const FvSide& s2 = many[k];
+      TriQuery* dq;
+      uint8_t* dm2;
+      TRY(up(a, &dq, queries[k].data(), queries[k].size()));
+      TRY(up(a, &dm2, has_mp2[k], (size_t)s2.n));
+      TriArgs t = {};
+      t.queries = dq; t.nQueries = (int)queries[k].size();
+      t.desc1 = s1->ddesc; t.x1 = s1->dx; t.y1 = s1->dy; t.angle1 = s1->dangle; t.stereo1 = s1->dstereo;
+      t.desc2 = s2.ddesc; t.hasMp2 = dm2; t.x2 = s2.dx; t.y2 = s2.dy; t.angle2 = s2.dangle; t.octave2 = s2.doct;
+      t.stereo2 = s2.dstereo; t.indices2 = s2.dindices;
+      t.F12 = dF + (size_t)k * 9; t.ex = ex[k]; t.ey = ey[k]; t.scaleFactors2 = dsf; t.levelSigma2_2 = dsg;
+      t.onlyStereo = only_stereo; t.match = dmatch + (size_t)k * n1; t.bin = dbin + (size_t)k * n1;
+      targs.push_back(t);
+      blockStart.push_back(totalBlocks);
+      totalBlocks += (t.nQueries + 3) / 4;
+    }
+    if (batch && !targs.empty()) {
+      TRY(up(a, &dargs, targs.data(), targs.size()));
+      TRY(up(a, &dstart, blockStart.data(), blockStart.size()));
+    }
+    return hipSuccess;
+  };
+  MHIP(arena_stage(device, &ar, stage));
+  MHIP(frame_use(ar, s1->frame));
+  for (int k = 0; k < K; k++) MHIP(frame_use(ar, many[k].frame));
+  MHIP(flush(ar));
+  if (targs.size() == 1) launch_search_triangulation(ar->stream, targs[0]);
+  else if (!targs.empty()) launch_search_triangulation_multi(ar->stream, dargs, dstart, (int)targs.size(), totalBlocks);
+  if (batch) launch_rot_prune_batch(ar->stream, dmatch, dbin, n1, K, check_ori, dcount);  // all K histograms in one launch
+  else launch_rot_prune(ar->stream, dmatch, dbin, n1, check_ori, dcount);
+  MHIP(hipGetLastError());
+  MHIP(down_range(ar, dmatch, dcount + K));
+  MHIP(hipStreamSynchronize(ar->stream));
+  frames_settle();
+  std::memcpy(match12, mirror_of(ar, dmatch), (size_t)K * n1 * 4);
+  std::memcpy(n_matches, mirror_of(ar, dcount), (size_t)K * 4);
+  return ORBFE_OK;
+}
+
+// the single forms in the reference's operand order.  (KF, F): the frame is bow_run's `one`, the key frame its only other
+int bow_one(const char* who, int device, FvSide* s1, const uint8_t* has_mp1, FvSide* s2, const uint8_t* has_mp2,
+            float nnratio, int check_ori, int kfkf, int32_t* match) {
+  int32_t count = 0;
+  const int rc = kfkf ? bow_run(who, device, s1, has_mp1, 1, s2, &has_mp2, nnratio, check_ori, 1, 0, match, &count)
+                      : bow_run(who, device, s2, nullptr, 1, s1, &has_mp1, nnratio, check_ori, 0, 0, match, &count);
+  return rc ? rc : count;
+}
+
+int bow_host(int device, const uint8_t* desc1, const uint8_t* has_mp1, const float* angle1, int n1, const orbfe_featvec* fv1,
+             const uint8_t* desc2, const uint8_t* has_mp2, const float* angle2, int n2, const orbfe_featvec* fv2,
+             float nnratio, int check_ori, int kfkf, int32_t* match) {
+  if (n1 < 0 || n2 < 0 || !match) return fail(ORBFE_ERR_INVALID, "search_by_bow: bad argument");
+  const int nOut = kfkf ? n1 : n2;
+  for (int i = 0; i < nOut; i++) match[i] = -1;
+  if (n1 == 0 || n2 == 0) return 0;
+  if (!desc1 || !has_mp1 || !angle1 || !desc2 || !angle2 || (kfkf && !has_mp2))
+    return fail(ORBFE_ERR_INVALID, "search_by_bow: NULL input");
+  if (!featvec_ok(fv1, n1) || !featvec_ok(fv2, n2)) return fail(ORBFE_ERR_INVALID, "search_by_bow: malformed FeatureVector");
+  FvSide s1, s2;
+  s1.n = n1; s1.fv = fv1; s1.hdesc = desc1; s1.hangle = angle1;
+  s2.n = n2; s2.fv = fv2; s2.hdesc = desc2; s2.hangle = angle2;
+  return bow_one("search_by_bow", device, &s1, has_mp1, &s2, has_mp2, nnratio, check_ori, kfkf, match);
+}
+
+// on resident frames: per call only the shared-node list, the map-point masks and the result arrays travel
+int bow_resident(const orbfe_frame* k1, const uint8_t* has_mp1, const orbfe_frame* k2, const uint8_t* has_mp2,
+                 float nnratio, int check_ori, int kfkf, int32_t* match) {
+  if (!k1 || !k2 || !match) return fail(ORBFE_ERR_INVALID, "search_by_bow_resident: NULL argument");
+  if (k1->device != k2->device) return fail(ORBFE_ERR_INVALID, "search_by_bow_resident: frames on different devices");
+  const int n1 = k1->n, n2 = k2->n, nOut = kfkf ? n1 : n2;
+  for (int i = 0; i < nOut; i++) match[i] = -1;
+  if (n1 == 0 || n2 == 0) return 0;
+  if (!k1->haveFv || !k2->haveFv || k1->hangle.empty() || k2->hangle.empty() || !has_mp1 || (kfkf && !has_mp2))
+    return fail(ORBFE_ERR_INVALID, "search_by_bow_resident: the frames were uploaded without FeatureVector / angles, or a mask is NULL");
+  FvSide s1 = side_of_frame(k1), s2 = side_of_frame(k2);
+  return bow_one("search_by_bow_resident", k1->device, &s1, has_mp1, &s2, has_mp2, nnratio, check_ori, kfkf, match);
+}
+
+// ONE frame / key frame against K candidate key frames in one call: Tracking::Relocalization runs
+// SearchByBoW(pKF_k, mCurrentFrame, ...) over every candidate (src/Tracking.cc:1478-1498), LoopClosing::ComputeSim3
+// SearchByBoW(mpCurrentKF, pKF_k, ...) (src/LoopClosing.cc:294-321).  A single resident call is a round trip of ~0.16 ms
+// whatever it computes; here the K problems share one.
+int bow_multi(const orbfe_frame* one, const uint8_t* has_mp_one, int K, const orbfe_frame* const* many,
+              const uint8_t* const* has_mp_k, float nnratio, int check_ori, int kfkf, int32_t* match, int32_t* n_matches) {
+  if (!one || K < 0 || (K > 0 && (!many || !has_mp_k || !match || !n_matches)))
+    return fail(ORBFE_ERR_INVALID, "search_by_bow_multi: bad argument");
+  for (size_t i = 0; i < (size_t)K * one->n; i++) match[i] = -1;
+  for (int k = 0; k < K; k++) n_matches[k] = 0;
+  if (K == 0 || one->n == 0) return ORBFE_OK;
+  if (!one->haveFv || one->hangle.empty() || (kfkf && !has_mp_one))
+    return fail(ORBFE_ERR_INVALID, "search_by_bow_multi: frame uploaded without FeatureVector / angles, or NULL mask");
+  std::vector<FvSide> sides((size_t)K);
+  for (int k = 0; k < K; k++) {
+    const orbfe_frame* c = many[k];
+    if (!c || (c->n > 0 && !has_mp_k[k])) return fail(ORBFE_ERR_INVALID, "search_by_bow_multi: NULL candidate or mask");
+    if (c->device != one->device) return fail(ORBFE_ERR_INVALID, "search_by_bow_multi: frames on different devices");
+    if (c->n > 0 && (!c->haveFv || c->hangle.empty()))
+      return fail(ORBFE_ERR_INVALID, "search_by_bow_multi: candidate uploaded without FeatureVector / angles");
+    sides[(size_t)k] = side_of_frame(c);
+  }
+  FvSide s = side_of_frame(one);
+  return bow_run("search_by_bow_multi", one->device, &s, has_mp_one, K, sides.data(), has_mp_k, nnratio, check_ori, kfkf, 1,
+                 match, n_matches);
+}
+}  // namespace
+
+extern "C" int orbfe_search_by_bow(int device, const uint8_t* desc1, const uint8_t* has_mp1, const float* angle1,
+                                   int n1, const orbfe_featvec* fv1, const uint8_t* desc2, const float* angle2,
+                                   int n2, const orbfe_featvec* fv2, float nnratio, int check_orientation,
+                                   int32_t* match_f) {
+  return bow_host(device, desc1, has_mp1, angle1, n1, fv1, desc2, nullptr, angle2, n2, fv2, nnratio, check_orientation, 0,
+                  match_f);
+}
+extern "C" int orbfe_search_by_bow_kf(int device, const uint8_t* desc1, const uint8_t* has_mp1, const float* angle1,
+                                      int n1, const orbfe_featvec* fv1, const uint8_t* desc2,
+                                      const uint8_t* has_mp2, const float* angle2, int n2,
+                                      const orbfe_featvec* fv2, float nnratio, int check_orientation,
+                                      int32_t* match12) {
+  return bow_host(device, desc1, has_mp1, angle1, n1, fv1, desc2, has_mp2, angle2, n2, fv2, nnratio, check_orientation, 1,
+                  match12);
+}
+extern "C" int orbfe_search_by_bow_resident(const orbfe_frame* kf, const uint8_t* has_mp_kf, const orbfe_frame* f,
+                                            float nnratio, int check_orientation, int32_t* match_f) {
+  return bow_resident(kf, has_mp_kf, f, nullptr, nnratio, check_orientation, 0, match_f);
+}
+extern "C" int orbfe_search_by_bow_kf_resident(const orbfe_frame* kf1, const uint8_t* has_mp1, const orbfe_frame* kf2,
+                                               const uint8_t* has_mp2, float nnratio, int check_orientation,
+                                               int32_t* match12) {
+  return bow_resident(kf1, has_mp1, kf2, has_mp2, nnratio, check_orientation, 1, match12);
+}
 extern "C" int orbfe_search_by_bow_multi(int n_keyframes, const orbfe_frame* const* kf, const uint8_t* const* has_mp_kf,
                                          const orbfe_frame* f, float nnratio, int check_orientation, int32_t* match_f,
                                          int32_t* n_matches) {
@@ -917,112 +965,59 @@ extern "C" int orbfe_search_by_bow_kf_multi(const orbfe_frame* kf1, const uint8_
   return bow_multi(kf1, has_mp1, n_keyframes, kf2, has_mp2, nnratio, check_orientation, 1, match12, n_matches);
 }
 
-// ORBmatcher::SearchForTriangulation of ONE key frame against K neighbours (LocalMapping::CreateNewMapPoints,
-// src/LocalMapping.cc:256-315: the same mpCurrentKeyFrame, a new F12 per neighbour): one upload of the K query lists,
-// masks and matrices, 2 K launches on one stream, one download of the K match arrays.
+extern "C" int orbfe_search_for_triangulation(int device, const uint8_t* desc1, const uint8_t* has_mp1,
+                                              const float* x1, const float* y1, const float* angle1,
+                                              const uint8_t* stereo1, int n1, const orbfe_featvec* fv1,
+                                              const uint8_t* desc2, const uint8_t* has_mp2, const float* x2,
+                                              const float* y2, const float* angle2, const int32_t* octave2,
+                                              const uint8_t* stereo2, int n2, const orbfe_featvec* fv2,
+                                              const float* F12, float ex, float ey, const float* scale_factors2,
+                                              const float* level_sigma2_2, int n_levels2, int only_stereo,
+                                              int check_orientation, int32_t* match12) {
+  if (n1 < 0 || n2 < 0 || !match12) return fail(ORBFE_ERR_INVALID, "search_for_triangulation: bad argument");
+  for (int i = 0; i < n1; i++) match12[i] = -1;
+  if (n1 == 0 || n2 == 0) return 0;
+  if (!desc1 || !has_mp1 || !x1 || !y1 || !angle1 || !stereo1 || !desc2 || !has_mp2 || !x2 || !y2 || !angle2 ||
+      !octave2 || !stereo2 || !F12 || !scale_factors2 || !level_sigma2_2 || n_levels2 <= 0 || n_levels2 > ORBFE_MAX_LEVELS)
+    return fail(ORBFE_ERR_INVALID, "search_for_triangulation: NULL input");
+  if (!featvec_ok(fv1, n1) || !featvec_ok(fv2, n2)) return fail(ORBFE_ERR_INVALID, "search_for_triangulation: malformed FeatureVector");
+  FvSide s1, s2;
+  s1.n = n1; s1.fv = fv1; s1.hdesc = desc1; s1.hstereo = stereo1; s1.hx = x1; s1.hy = y1; s1.hangle = angle1;
+  s2.n = n2; s2.fv = fv2; s2.hdesc = desc2; s2.hstereo = stereo2; s2.hx = x2; s2.hy = y2; s2.hangle = angle2; s2.hoct = octave2;
+  int32_t count = 0;
+  const int rc = tri_run("search_for_triangulation", device, &s1, has_mp1, 1, &s2, &has_mp2, F12, &ex, &ey, scale_factors2,
+                         level_sigma2_2, n_levels2, only_stereo, check_orientation, 0, match12, &count);
+  return rc ? rc : count;
+}
+
 extern "C" int orbfe_search_for_triangulation_multi(const orbfe_frame* kf1, const uint8_t* has_mp1, int n_neighbours,
                                                     const orbfe_frame* const* kf2, const uint8_t* const* has_mp2,
                                                     const float* F12, const float* ex, const float* ey,
                                                     const float* scale_factors2, const float* level_sigma2_2,
                                                     int n_levels2, int only_stereo, int check_orientation,
                                                     int32_t* match12, int32_t* n_matches) {
-  UnsettledScope unsettledScope;
   if (!kf1 || n_neighbours < 0 || (n_neighbours > 0 && (!kf2 || !has_mp2 || !F12 || !ex || !ey || !match12 || !n_matches)) ||
       !scale_factors2 || !level_sigma2_2 || n_levels2 <= 0 || n_levels2 > ORBFE_MAX_LEVELS)
-    return mfail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: bad argument");
   const int n1 = kf1->n, K = n_neighbours;
   for (size_t i = 0; i < (size_t)K * n1; i++) match12[i] = -1;
   for (int k = 0; k < K; k++) n_matches[k] = 0;
   if (K == 0 || n1 == 0) return ORBFE_OK;
   if (!has_mp1 || !kf1->haveFv || kf1->hangle.empty())
-    return mfail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: key frame uploaded without FeatureVector / angles, or NULL mask");
-  // host: the shared nodes and the query list of every neighbour (:787-811)
-  std::vector<std::vector<TriQuery>> queries((size_t)K);
-  size_t bytes = pad((size_t)K * 9 * 4) + 2 * pad((size_t)n_levels2 * 4) + 2 * pad((size_t)K * n1 * 4) + pad((size_t)K * 4) + 8192 +
-                 pad((size_t)K * sizeof(TriArgs)) + pad((size_t)K * 4);
-  std::vector<NodePair> pairs;
+    return fail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: key frame uploaded without FeatureVector / angles, or NULL mask");
+  std::vector<FvSide> sides((size_t)K);
   for (int k = 0; k < K; k++) {
     const orbfe_frame* k2 = kf2[k];
-    if (!k2 || (!has_mp2[k] && k2->n > 0)) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: NULL neighbour");
-    if (k2->device != kf1->device) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: frames on different devices");
+    if (!k2 || (!has_mp2[k] && k2->n > 0)) return fail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: NULL neighbour");
+    if (k2->device != kf1->device) return fail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: frames on different devices");
     if (k2->n > 0 && (!k2->haveFv || k2->hangle.empty()))
-      return mfail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: neighbour uploaded without FeatureVector / angles");
-    for (int i = 0; i < k2->n; i++)
-      if (k2->hoct[i] < 0 || k2->hoct[i] >= n_levels2) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation: octave out of range");
-    pairs.clear();
-    if (k2->n > 0) shared_nodes(&kf1->fv, &k2->fv, &pairs);
-    for (const NodePair& p : pairs) {
-      if (p.cnt2 > 65535) return mfail(ORBFE_ERR_INVALID, "search_for_triangulation: more than 65535 features in one node");
-      for (int i = 0; i < p.cnt1; i++) {
-        const uint32_t idx1 = kf1->hindices[p.off1 + i];
-        if (has_mp1[idx1]) continue;                         // :800-803
-        if (only_stereo && !kf1->hstereo[idx1]) continue;    // :807-809
-        queries[k].push_back(TriQuery{idx1, p.off2, p.cnt2});
-      }
-    }
-    bytes += pad(queries[k].size() * sizeof(TriQuery)) + pad((size_t)k2->n);
+      return fail(ORBFE_ERR_INVALID, "search_for_triangulation_multi: neighbour uploaded without FeatureVector / angles");
+    sides[(size_t)k] = side_of_frame(k2);
   }
-  Arena* ar;
-  MHIP(arena_begin(kf1->device, bytes, &ar));
-  MHIP(frame_use(ar, kf1));
-  for (int k = 0; k < K; k++) MHIP(frame_use(ar, kf2[k]));
-  float *dF, *dsf, *dsg;
-  MHIP(up(ar, &dF, F12, (size_t)K * 9));
-  MHIP(up(ar, &dsf, scale_factors2, (size_t)n_levels2));
-  MHIP(up(ar, &dsg, level_sigma2_2, (size_t)n_levels2));
-  std::vector<TriQuery*> dq((size_t)K, nullptr);
-  std::vector<uint8_t*> dm2((size_t)K, nullptr);
-  for (int k = 0; k < K; k++) {
-    if (queries[k].empty()) continue;
-    MHIP(up(ar, &dq[k], queries[k].data(), queries[k].size()));
-    MHIP(up(ar, &dm2[k], has_mp2[k], (size_t)kf2[k]->n));
-  }
-  int32_t* dmatch;
-  int8_t* dbin;
-  MHIP(up_fill(ar, &dmatch, (size_t)K * n1, 0xff));   // match arrays and counts adjacent: one copy back
-  int32_t* dcount;
-  MHIP(up_fill(ar, &dcount, (size_t)K, 0));
-  MHIP(up_fill(ar, &dbin, (size_t)K * n1, 0));
-  // the K problems run as ONE launch: their argument blocks and first workgroups travel with the inputs
-  std::vector<TriArgs> targs;
-  std::vector<int32_t> blockStart;
-  int totalBlocks = 0;
-  for (int k = 0; k < K; k++) {
-    if (queries[k].empty()) continue;
-    const orbfe_frame* k2 = kf2[k];
-    TriArgs a = {};
-    a.queries = dq[k]; a.nQueries = (int)queries[k].size();
-    a.desc1 = kf1->ddesc; a.x1 = kf1->dx; a.y1 = kf1->dy; a.angle1 = kf1->dangle; a.stereo1 = kf1->dstereo;
-    a.desc2 = k2->ddesc; a.hasMp2 = dm2[k]; a.x2 = k2->dx; a.y2 = k2->dy; a.angle2 = k2->dangle; a.octave2 = k2->doct;
-    a.stereo2 = k2->dstereo; a.indices2 = k2->dindices;
-    a.F12 = dF + (size_t)k * 9; a.ex = ex[k]; a.ey = ey[k]; a.scaleFactors2 = dsf; a.levelSigma2_2 = dsg;
-    a.onlyStereo = only_stereo; a.match = dmatch + (size_t)k * n1; a.bin = dbin + (size_t)k * n1;
-    targs.push_back(a);
-    blockStart.push_back(totalBlocks);
-    totalBlocks += (a.nQueries + 3) / 4;
-  }
-  TriArgs* dargs = nullptr;
-  int32_t* dstart = nullptr;
-  if (!targs.empty()) {
-    MHIP(up(ar, &dargs, targs.data(), targs.size()));
-    MHIP(up(ar, &dstart, blockStart.data(), blockStart.size()));
-  }
-  MHIP(flush(ar));
-  if (targs.size() == 1) launch_search_triangulation(ar->stream, targs[0]);
-  else if (!targs.empty()) launch_search_triangulation_multi(ar->stream, dargs, dstart, (int)targs.size(), totalBlocks);
-  launch_rot_prune_batch(ar->stream, dmatch, dbin, n1, K, check_orientation, dcount);  // all K histograms in one launch
-  MHIP(hipGetLastError());
-  MHIP(down_range(ar, dmatch, dcount + K));
-  MHIP(hipStreamSynchronize(ar->stream));
-  frames_settle();
-  std::memcpy(match12, mirror_of(ar, dmatch), (size_t)K * n1 * 4);
-  std::memcpy(n_matches, mirror_of(ar, dcount), (size_t)K * 4);
-  return ORBFE_OK;
+  FvSide s1 = side_of_frame(kf1);
+  return tri_run("search_for_triangulation_multi", kf1->device, &s1, has_mp1, K, sides.data(), has_mp2, F12, ex, ey,
+                 scale_factors2, level_sigma2_2, n_levels2, only_stereo, check_orientation, 1, match12, n_matches);
 }
-
-// implemented in extractor.hip (needs the handle internals)
-extern "C" int orbfe_stereo_views_(orbfe_extractor* e, int frame, PyramidViews* pv, float* scale, float* invScale,
-                                   int* nlevels, int* device, const float** d_scaleTab);
 
 extern "C" int orbfe_compute_stereo_matches(orbfe_extractor* left, int frameL, orbfe_extractor* right, int frameR,
                                             const orbfe_keypoint* kpL, const uint8_t* descL, int N,
@@ -1030,10 +1025,10 @@ extern "C" int orbfe_compute_stereo_matches(orbfe_extractor* left, int frameL, o
                                             float mb, float* uRight, float* depth) {
   if (!left || !right || N < 0 || Nr < 0 || (N > 0 && (!kpL || !descL || !uRight || !depth)) ||
       (Nr > 0 && (!kpR || !descR)))
-    return mfail(ORBFE_ERR_INVALID, "compute_stereo_matches: bad argument");
+    return fail(ORBFE_ERR_INVALID, "compute_stereo_matches: bad argument");
   for (int i = 0; i < N; i++) { uRight[i] = -1.0f; depth[i] = -1.0f; }
   if (N == 0 || Nr == 0) return 0;
-  if (Nr >= (1 << 20)) return mfail(ORBFE_ERR_INVALID, "compute_stereo_matches: too many right keypoints");
+  if (Nr >= (1 << 20)) return fail(ORBFE_ERR_INVALID, "compute_stereo_matches: too many right keypoints");
   StereoArgs a = {};
   int nlL = 0, nlR = 0, devL = 0, devR = 0;
   float scL[kMaxLevels], iscL[kMaxLevels], scR[kMaxLevels], iscR[kMaxLevels];
@@ -1041,19 +1036,19 @@ extern "C" int orbfe_compute_stereo_matches(orbfe_extractor* left, int frameL, o
   int rc;
   if ((rc = orbfe_stereo_views_(left, frameL, &a.pyrL, scL, iscL, &nlL, &devL, &a.scaleTab))) return rc;
   if ((rc = orbfe_stereo_views_(right, frameR, &a.pyrR, scR, iscR, &nlR, &devR, &dTabR))) return rc;
-  if (nlL != nlR || devL != devR) return mfail(ORBFE_ERR_INVALID, "compute_stereo_matches: extractors differ");
+  if (nlL != nlR || devL != devR) return fail(ORBFE_ERR_INVALID, "compute_stereo_matches: extractors differ");
   for (int l = 0; l < nlL; l++)
     if (a.pyrL.lv[l].w != a.pyrR.lv[l].w || a.pyrL.lv[l].h != a.pyrR.lv[l].h)
-      return mfail(ORBFE_ERR_INVALID, "compute_stereo_matches: left/right pyramids differ in size");
+      return fail(ORBFE_ERR_INVALID, "compute_stereo_matches: left/right pyramids differ in size");
   // host operands are checked here (the reference indexes mvInvScaleFactor / mvImagePyramid / vRowIndices with them
   // unchecked, src/Frame.cc:537-538,560,600-610); the device-operand form cannot look and answers "no stereo" instead
   const float W0 = (float)a.pyrL.lv[0].w, H0 = (float)a.pyrL.lv[0].h;
   for (int side = 0; side < 2; side++) {
     const orbfe_keypoint* kp = side ? kpR : kpL;
     for (int i = 0, n = side ? Nr : N; i < n; i++) {
-      if (kp[i].octave < 0 || kp[i].octave >= nlL) return mfail(ORBFE_ERR_INVALID, "compute_stereo_matches: octave out of range");
+      if (kp[i].octave < 0 || kp[i].octave >= nlL) return fail(ORBFE_ERR_INVALID, "compute_stereo_matches: octave out of range");
       if (!(kp[i].x >= 0.f && kp[i].x < W0 && kp[i].y >= 0.f && kp[i].y < H0))  // (false for NaN too)
-        return mfail(ORBFE_ERR_INVALID, "compute_stereo_matches: keypoint outside the image (or not finite)");
+        return fail(ORBFE_ERR_INVALID, "compute_stereo_matches: keypoint outside the image (or not finite)");
     }
   }
   Arena* ar;
@@ -1111,51 +1106,6 @@ bool frame_ok(const orbfe_frame_view* f) {
   return true;
 }
 
-// Pinned staging of the calling thread: every input array of a call is packed into it and travels in
-// ONE host-to-device copy, counts + candidate lists come back in ONE copy (13 + 2 small transfers of
-// ~7 us each were most of a call before).
-struct Staging {
-  uint8_t* h = nullptr;
-  size_t cap = 0;
-  hipEvent_t pending = nullptr;  // an asynchronous copy OUT of the buffer that nobody waited for (orbfe_frame_upload): the
-  bool isPending = false;        // next use of the buffer waits for it first
-  ~Staging() {
-    if (h) (void)hipHostFree(h);
-    if (pending) (void)hipEventDestroy(pending);
-  }
-};
-thread_local Staging t_staging;
-
-hipError_t staging_reserve(size_t bytes);
-}  // namespace
-namespace {
-hipError_t staging_reserve_(size_t bytes) { return staging_reserve(bytes); }
-uint8_t* staging_ptr_() { return t_staging.h; }
-hipError_t staging_mark_pending_(hipStream_t s) {
-  if (!t_staging.pending) {
-    hipError_t e = hipEventCreateWithFlags(&t_staging.pending, hipEventDisableTiming);
-    if (e != hipSuccess) return e;
-  }
-  hipError_t e = hipEventRecord(t_staging.pending, s);
-  if (e == hipSuccess) t_staging.isPending = true;
-  return e;
-}
-hipError_t staging_reserve(size_t bytes) {
-  if (t_staging.isPending) {  // (normally long done: the copy took microseconds, the caller's next call comes later)
-    hipError_t e = hipEventSynchronize(t_staging.pending);
-    if (e != hipSuccess) return e;
-    t_staging.isPending = false;
-  }
-  if (bytes <= t_staging.cap) return hipSuccess;
-  if (t_staging.h) (void)hipHostFree(t_staging.h);
-  t_staging.h = nullptr;
-  t_staging.cap = 0;
-  const size_t want = bytes + bytes / 2 + (1u << 16);
-  hipError_t e = hipHostMalloc((void**)&t_staging.h, want, hipHostMallocDefault);
-  if (e == hipSuccess) t_staging.cap = want;
-  return e;
-}
-
 // One window search = one frame + one set of query windows.  Several jobs of a call (Fuse against K neighbour key frames,
 // the two directions of SearchBySim3) share ONE upload, one group of launches, one download and one synchronisation.
 struct WindowJob {
@@ -1210,7 +1160,7 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
     Lay& L = lay[j];
     const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
     L.res = J.f->resident != nullptr;
-    if (L.res && J.f->resident->device != device) return mfail(ORBFE_ERR_INVALID, "resident frame lives on another device");
+    if (L.res && J.f->resident->device != device) return fail(ORBFE_ERR_INVALID, "resident frame lives on another device");
     L.withDesc = J.f->desc && J.qdesc;
     L.withUr = J.qur && J.f->u_right;
     L.oX = L.oY = L.oOct = L.oUr = L.oDesc = L.oAng = L.oBlk = L.oBval = L.oQang = L.oScr = 0;
@@ -1239,8 +1189,8 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
       L.oQdesc = shared >= 0 ? lay[shared].oQdesc : place(q * 32);
     }
     if (J.claim) {
-      if (J.nq > 0x1fffff) return mfail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
-      if (nClaim && claimInit != (J.claim->mode == CLAIM_INIT)) return mfail(ORBFE_ERR_INVALID, "mixed claim forms in one call");
+      if (J.nq > 0x1fffff) return fail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
+      if (nClaim && claimInit != (J.claim->mode == CLAIM_INIT)) return fail(ORBFE_ERR_INVALID, "mixed claim forms in one call");
       claimInit = J.claim->mode == CLAIM_INIT;
       nClaim++;
       if (J.claim->checkOri && !L.res) L.oAng = place(n * 4);  // (a resident frame has its angles on the device)
@@ -1482,7 +1432,7 @@ extern "C" int orbfe_features_in_area(int device, const orbfe_frame_view* frame,
   frame = canon(frame);
   if (!frame_ok(frame) || n_queries < 0 || capacity < 0 ||
       (n_queries > 0 && (!x || !y || !r || !min_level || !max_level || !count || (capacity > 0 && !indices))))
-    return mfail(ORBFE_ERR_INVALID, "features_in_area: bad argument");
+    return fail(ORBFE_ERR_INVALID, "features_in_area: bad argument");
   if (n_queries == 0) return ORBFE_OK;
   WindowResult res;
   const int rc = window_search(device, frame, n_queries, x, y, r, min_level, max_level, nullptr, nullptr, nullptr,
@@ -1495,7 +1445,7 @@ extern "C" int orbfe_features_in_area(int device, const orbfe_frame_view* frame,
     if (res.count[i] > capacity) over = true;
     for (int c = 0; c < m; c++) indices[(size_t)i * capacity + c] = (int32_t)(res.cand[(size_t)i * res.K + c] & 0xffffu);
   }
-  if (over) return mfail(ORBFE_ERR_CAPACITY, "features_in_area: a window holds more features than capacity (counts are exact)");
+  if (over) return fail(ORBFE_ERR_CAPACITY, "features_in_area: a window holds more features than capacity (counts are exact)");
   return ORBFE_OK;
 }
 
@@ -1508,10 +1458,10 @@ extern "C" int orbfe_search_by_projection(int device, const orbfe_frame_view* F,
   F = canon(F);
   if (!frame_ok(F) || !scale_factors || n_levels <= 0 || n_mp < 0 || !n_matches || (F->n > 0 && (!match || !F->desc)) ||
       (n_mp > 0 && (!in_view || !level || !view_cos || !proj_x || !proj_y || !mp_desc)) || (F->u_right && n_mp > 0 && !proj_xr))
-    return mfail(ORBFE_ERR_INVALID, "search_by_projection: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_by_projection: bad argument");
   for (int i = 0; i < n_mp; i++)
     if (in_view[i] && (level[i] < 0 || level[i] >= n_levels))
-      return mfail(ORBFE_ERR_INVALID, "search_by_projection: predicted level outside the pyramid");
+      return fail(ORBFE_ERR_INVALID, "search_by_projection: predicted level outside the pyramid");
   for (int i = 0; i < F->n; i++) match[i] = -1;
   *n_matches = 0;
   if (n_mp == 0 || F->n == 0) return ORBFE_OK;
@@ -1550,10 +1500,10 @@ extern "C" int orbfe_search_by_projection_last_frame(int device, const orbfe_fra
       (Cur->n > 0 && (!match_cur || !Cur->desc)) || (check_orientation && Cur->n > 0 && !Cur->angle) ||
       (n_last > 0 && (!valid || !u || !v || !last_octave || !mp_desc || (check_orientation && !last_angle))) ||
       (Cur->u_right && n_last > 0 && !invzc))
-    return mfail(ORBFE_ERR_INVALID, "search_by_projection_last_frame: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_by_projection_last_frame: bad argument");
   for (int i = 0; i < n_last; i++)
     if (valid[i] && (last_octave[i] < 0 || last_octave[i] >= n_levels))
-      return mfail(ORBFE_ERR_INVALID, "search_by_projection_last_frame: octave outside the pyramid");
+      return fail(ORBFE_ERR_INVALID, "search_by_projection_last_frame: octave outside the pyramid");
   for (int i = 0; i < Cur->n; i++) match_cur[i] = -1;
   *n_matches = 0;
   if (n_last == 0 || Cur->n == 0) return ORBFE_OK;
@@ -1592,7 +1542,7 @@ int level_queries(const char* who, int n, const uint8_t* valid, const int32_t* l
     int lv = 0;
     if (valid[i]) {
       lv = level[i];
-      if (lv < 0 || lv >= n_levels) return mfail(ORBFE_ERR_INVALID, std::string(who) + ": level outside the pyramid");
+      if (lv < 0 || lv >= n_levels) return fail(ORBFE_ERR_INVALID, std::string(who) + ": level outside the pyramid");
     }
     (*qr)[i] = th * sf[lv];
     (*qmin)[i] = no_filter ? -1 : lv + lo;
@@ -1613,7 +1563,7 @@ extern "C" int orbfe_search_by_projection_keyframe(int device, const orbfe_frame
   if (!frame_ok(Cur) || !scale_factors || n_levels <= 0 || n < 0 || !n_matches ||
       (Cur->n > 0 && (!match_cur || !Cur->desc)) || (check_orientation && Cur->n > 0 && !Cur->angle) ||
       (n > 0 && (!valid || !u || !v || !level || !mp_desc || (check_orientation && !kf_angle))))
-    return mfail(ORBFE_ERR_INVALID, "search_by_projection_keyframe: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_by_projection_keyframe: bad argument");
   std::vector<float> qr;
   std::vector<int32_t> qmin, qmax;
   int rc = level_queries("search_by_projection_keyframe", n, valid, level, scale_factors, n_levels, th, -1, +1, false,
@@ -1649,14 +1599,14 @@ extern "C" int orbfe_search_by_projection_keyframe_multi(int device, const orbfe
   if (!frame_ok(Cur) || !scale_factors || n_levels <= 0 || K < 0 ||
       (K > 0 && (!n || !valid || !u || !v || !level || !mp_desc || !th || !orb_dist || !n_matches || (check_orientation && !kf_angle))) ||
       (Cur->n > 0 && K > 0 && (!match_cur || !Cur->desc)) || (check_orientation && Cur->n > 0 && !Cur->angle))
-    return mfail(ORBFE_ERR_INVALID, "search_by_projection_keyframe_multi: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_by_projection_keyframe_multi: bad argument");
   std::vector<std::vector<float>> qr((size_t)K);
   std::vector<std::vector<int32_t>> qmin((size_t)K), qmax((size_t)K);
   std::vector<ClaimSpec> claims((size_t)K);
   std::vector<WindowJob> wj;
   for (int k = 0; k < K; k++) {
     if (n[k] < 0 || (n[k] > 0 && (!valid[k] || !u[k] || !v[k] || !level[k] || !mp_desc[k] || (check_orientation && !kf_angle[k]))))
-      return mfail(ORBFE_ERR_INVALID, "search_by_projection_keyframe_multi: NULL array of a candidate");
+      return fail(ORBFE_ERR_INVALID, "search_by_projection_keyframe_multi: NULL array of a candidate");
     int rc = level_queries("search_by_projection_keyframe_multi", n[k], valid[k], level[k], scale_factors, n_levels, th[k], -1, +1,
                            false, &qr[k], &qmin[k], &qmax[k]);
     if (rc != ORBFE_OK) return rc;
@@ -1684,7 +1634,7 @@ extern "C" int orbfe_search_by_projection_sim3(int device, const orbfe_frame_vie
   KF = canon(KF);
   if (!frame_ok(KF) || !scale_factors || n_levels <= 0 || n < 0 || !n_matches || (KF->n > 0 && (!match || !KF->desc)) ||
       (n > 0 && (!valid || !u || !v || !level || !mp_desc)))
-    return mfail(ORBFE_ERR_INVALID, "search_by_projection_sim3: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_by_projection_sim3: bad argument");
   std::vector<float> qr;
   std::vector<int32_t> qmin, qmax;
   // the reference gathers the window without a level filter and then keeps octaves [level-1, level]
@@ -1712,7 +1662,7 @@ extern "C" int orbfe_search_for_initialization(int device, const orbfe_frame_vie
   if (!frame_ok(F1) || !frame_ok(F2) || !n_matches || window_size < 0 ||
       (F1->n > 0 && (!match12 || !prev_x || !prev_y || !F1->desc)) || (F2->n > 0 && !F2->desc) ||
       (check_orientation && ((F1->n > 0 && !F1->angle) || (F2->n > 0 && !F2->angle))))
-    return mfail(ORBFE_ERR_INVALID, "search_for_initialization: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_for_initialization: bad argument");
   const int n1 = F1->n;
   for (int i = 0; i < n1; i++) match12[i] = -1;
   *n_matches = 0;
@@ -1789,15 +1739,15 @@ extern "C" int orbfe_fuse_search_multi(int device, int n_keyframes, const orbfe_
                                        int32_t* best_idx) {
   if (n_keyframes < 0 || n < 0 || !scale_factors || n_levels <= 0 || (n_keyframes > 0 && !KF) ||
       (n_keyframes > 0 && n > 0 && (!valid || !u || !v || !level || !mp_desc || !best_idx)) || (chi2_gate && !inv_level_sigma2))
-    return mfail(ORBFE_ERR_INVALID, "fuse_search_multi: bad argument");
+    return fail(ORBFE_ERR_INVALID, "fuse_search_multi: bad argument");
   std::vector<BestJob> jobs;
   for (int k = 0; k < n_keyframes; k++) {
     const orbfe_frame_view* f = canon(KF[k]);
     if (!frame_ok(f) || (f->n > 0 && !f->desc) || (chi2_gate && f->u_right && n > 0 && !ur))
-      return mfail(ORBFE_ERR_INVALID, "fuse_search_multi: bad key frame view");
+      return fail(ORBFE_ERR_INVALID, "fuse_search_multi: bad key frame view");
     for (int i = 0; i < f->n; i++)
       if (chi2_gate && (f->octave[i] < 0 || f->octave[i] >= n_levels))
-        return mfail(ORBFE_ERR_INVALID, "fuse_search_multi: keypoint octave outside the pyramid");
+        return fail(ORBFE_ERR_INVALID, "fuse_search_multi: keypoint octave outside the pyramid");
     const size_t o = (size_t)k * n;
     jobs.push_back(BestJob{f, scale_factors, inv_level_sigma2, n, valid + o, u + o, v + o, ur ? ur + o : nullptr, level + o,
                            mp_desc, best_idx + o});
@@ -1814,10 +1764,10 @@ extern "C" int orbfe_fuse_search(int device, const orbfe_frame_view* KF, const f
   if (!frame_ok(KF) || !scale_factors || n_levels <= 0 || n < 0 || (KF->n > 0 && !KF->desc) ||
       (n > 0 && (!valid || !u || !v || !level || !mp_desc || !best_idx)) ||
       (chi2_gate && (!inv_level_sigma2 || (KF->u_right && n > 0 && !ur))))
-    return mfail(ORBFE_ERR_INVALID, "fuse_search: bad argument");
+    return fail(ORBFE_ERR_INVALID, "fuse_search: bad argument");
   for (int i = 0; i < KF->n; i++)
     if (chi2_gate && (KF->octave[i] < 0 || KF->octave[i] >= n_levels))
-      return mfail(ORBFE_ERR_INVALID, "fuse_search: keypoint octave outside the pyramid");
+      return fail(ORBFE_ERR_INVALID, "fuse_search: keypoint octave outside the pyramid");
   return window_best("fuse_search", device, KF, scale_factors, n_levels, inv_level_sigma2, n, valid, u, v, ur, level,
                      mp_desc, th, chi2_gate != 0, 50 /* TH_LOW */, best_idx);
 }
@@ -1833,7 +1783,7 @@ extern "C" int orbfe_search_by_sim3(int device, const orbfe_frame_view* KF1, con
   if (!frame_ok(KF1) || !frame_ok(KF2) || !scale_factors1 || !scale_factors2 || n_levels <= 0 || !n_found ||
       (KF1->n > 0 && (!valid1 || !u1 || !v1 || !level1 || !desc1 || !match12 || !KF1->desc)) ||
       (KF2->n > 0 && (!valid2 || !u2 || !v2 || !level2 || !desc2 || !KF2->desc)))
-    return mfail(ORBFE_ERR_INVALID, "search_by_sim3: bad argument");
+    return fail(ORBFE_ERR_INVALID, "search_by_sim3: bad argument");
   std::vector<int32_t> m1(KF1->n ? KF1->n : 1), m2(KF2->n ? KF2->n : 1);
   // both directions (src/ORBmatcher.cc:1190-1275 and :1277-1358) as one upload / launch group / download
   BestJob jobs[2] = {{KF2, scale_factors2, nullptr, KF1->n, valid1, u1, v1, nullptr, level1, desc1, m1.data()},

@@ -28,17 +28,16 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "host_internal.h"
 #include "kernels.h"
 #include "match_kernels.h"
 
 using namespace orbfe;
 
-int orbfe_set_error_(int code, const char* msg);
-static int vfail(int code, const std::string& m) { return orbfe_set_error_(code, m.c_str()); }
 #define VHIP(expr)                                                                                   \
   do {                                                                                               \
     hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) return vfail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    if (_e != hipSuccess) return fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
 struct orbfe_vocabulary {
@@ -282,13 +281,13 @@ static int vocab_upload(orbfe_vocabulary* v, const int32_t* parent, const uint8_
   const int n = v->nNodes;
   std::vector<int32_t> off((size_t)n + 1, 0), idx((size_t)(n > 1 ? n - 1 : 1), 0);
   for (int i = 1; i < n; i++) {
-    if (parent[i] < 0 || parent[i] >= n) return vfail(ORBFE_ERR_INVALID, "vocabulary: parent id out of range");
+    if (parent[i] < 0 || parent[i] >= n) return fail(ORBFE_ERR_INVALID, "vocabulary: parent id out of range");
     // every descent must terminate: a child's id is larger than its parent's in a well-formed file
-    if (parent[i] >= i) return vfail(ORBFE_ERR_INVALID, "vocabulary: node listed before its parent");
+    if (parent[i] >= i) return fail(ORBFE_ERR_INVALID, "vocabulary: node listed before its parent");
     off[parent[i] + 1]++;
   }
   for (int i = 0; i < n; i++) {
-    if (off[i + 1] > 32) return vfail(ORBFE_ERR_INVALID, "vocabulary: a node has more than 32 children");
+    if (off[i + 1] > 32) return fail(ORBFE_ERR_INVALID, "vocabulary: a node has more than 32 children");
     off[i + 1] += off[i];
   }
   std::vector<int32_t> cur(off.begin(), off.begin() + n);
@@ -302,7 +301,7 @@ static int vocab_upload(orbfe_vocabulary* v, const int32_t* parent, const uint8_
     pos[id] = q;
     for (int c = off[id]; c < off[id + 1]; c++) order[filled++] = idx[c];
   }
-  if (filled != n) return vfail(ORBFE_ERR_INVALID, "vocabulary: unreachable nodes");
+  if (filled != n) return fail(ORBFE_ERR_INVALID, "vocabulary: unreachable nodes");
   std::vector<VocabNode> rec((size_t)n);
   std::vector<double> wpos((size_t)n);
   for (int q = 0; q < n; q++) {
@@ -338,10 +337,10 @@ static int vocab_finish(orbfe_vocabulary* v, const std::vector<int32_t>& parent,
 }
 
 extern "C" int orbfe_vocabulary_load_text(const char* path, int device, orbfe_vocabulary** out) {
-  if (!path || !out) return vfail(ORBFE_ERR_INVALID, "vocabulary_load_text: NULL argument");
+  if (!path || !out) return fail(ORBFE_ERR_INVALID, "vocabulary_load_text: NULL argument");
   *out = nullptr;
   FILE* fp = fopen(path, "rb");
-  if (!fp) return vfail(ORBFE_ERR_INVALID, std::string("vocabulary_load_text: cannot open ") + path);
+  if (!fp) return fail(ORBFE_ERR_INVALID, std::string("vocabulary_load_text: cannot open ") + path);
   std::string txt;  // ORBvoc.txt is 145 MB: one read, then pointer parsing (no stream per line)
   {
     char buf[1 << 16];
@@ -352,7 +351,7 @@ extern "C" int orbfe_vocabulary_load_text(const char* path, int device, orbfe_vo
   char* p = &txt[0];
   char* const end = p + txt.size();  // (*end is the string's own NUL)
   auto line_end = [&](char* q) { while (q < end && *q != '\n') q++; return q; };
-  if (p == end) return vfail(ORBFE_ERR_INVALID, "vocabulary_load_text: empty file");
+  if (p == end) return fail(ORBFE_ERR_INVALID, "vocabulary_load_text: empty file");
   int k = -1, L = -1, n1 = -1, n2 = -1;
   {
     const std::string head(p, line_end(p));
@@ -360,7 +359,7 @@ extern "C" int orbfe_vocabulary_load_text(const char* path, int device, orbfe_vo
     ss >> k >> L >> n1 >> n2;
   }
   if (k < 0 || k > 20 || L < 1 || L > 10 || n1 < 0 || n1 > 5 || n2 < 0 || n2 > 3)  // :1357-1361
-    return vfail(ORBFE_ERR_INVALID, "vocabulary_load_text: not a DBoW2 text vocabulary");
+    return fail(ORBFE_ERR_INVALID, "vocabulary_load_text: not a DBoW2 text vocabulary");
   std::vector<int32_t> parent(1, 0), wordId(1, -1);
   std::vector<uint8_t> desc(32, 0);
   std::vector<double> weight(1, 0.0);
@@ -392,7 +391,7 @@ extern "C" int orbfe_vocabulary_load_text(const char* path, int device, orbfe_vo
     p = le;
   }
   orbfe_vocabulary* v = new (std::nothrow) orbfe_vocabulary();
-  if (!v) return vfail(ORBFE_ERR_NOMEM, "out of memory");
+  if (!v) return fail(ORBFE_ERR_NOMEM, "out of memory");
   v->device = device; v->k = k; v->L = L; v->scoring = n1; v->weighting = n2;
   v->nNodes = (int)parent.size();
   v->nWords = nWords;
@@ -404,12 +403,12 @@ extern "C" int orbfe_vocabulary_load_text(const char* path, int device, orbfe_vo
 extern "C" int orbfe_vocabulary_create(int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
                                        const uint8_t* is_leaf, const uint8_t* descriptors, const double* weight,
                                        int device, orbfe_vocabulary** out) {
-  if (!out) return vfail(ORBFE_ERR_INVALID, "vocabulary_create: NULL argument");
+  if (!out) return fail(ORBFE_ERR_INVALID, "vocabulary_create: NULL argument");
   *out = nullptr;
   if (n_nodes < 0 || (n_nodes > 0 && (!parent || !is_leaf || !descriptors || !weight)))
-    return vfail(ORBFE_ERR_INVALID, "vocabulary_create: NULL argument");
+    return fail(ORBFE_ERR_INVALID, "vocabulary_create: NULL argument");
   if (k < 0 || k > 20 || L < 1 || L > 10 || scoring < 0 || scoring > 5 || weighting < 0 || weighting > 3)
-    return vfail(ORBFE_ERR_INVALID, "vocabulary_create: header values out of range (:1357-1361)");
+    return fail(ORBFE_ERR_INVALID, "vocabulary_create: header values out of range (:1357-1361)");
   const size_t n = (size_t)n_nodes + 1;
   std::vector<int32_t> par(n, 0), wordId(n, -1);
   std::vector<uint8_t> desc(n * 32, 0);
@@ -422,7 +421,7 @@ extern "C" int orbfe_vocabulary_create(int k, int L, int scoring, int weighting,
   }
   if (n_nodes) memcpy(desc.data() + 32, descriptors, (size_t)n_nodes * 32);
   orbfe_vocabulary* v = new (std::nothrow) orbfe_vocabulary();
-  if (!v) return vfail(ORBFE_ERR_NOMEM, "out of memory");
+  if (!v) return fail(ORBFE_ERR_NOMEM, "out of memory");
   v->device = device; v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting;
   v->nNodes = (int)n;
   v->nWords = nWords;
@@ -438,7 +437,7 @@ extern "C" void orbfe_vocabulary_destroy(orbfe_vocabulary* v) {
 }
 
 extern "C" int orbfe_vocabulary_info(const orbfe_vocabulary* v, int* k, int* L, int* n_nodes, int* n_words) {
-  if (!v) return vfail(ORBFE_ERR_INVALID, "NULL vocabulary");
+  if (!v) return fail(ORBFE_ERR_INVALID, "NULL vocabulary");
   if (k) *k = v->k;
   if (L) *L = v->L;
   if (n_nodes) *n_nodes = v->nNodes;
@@ -449,7 +448,7 @@ extern "C" int orbfe_vocabulary_info(const orbfe_vocabulary* v, int* k, int* L, 
 extern "C" int orbfe_vocabulary_transform(orbfe_vocabulary* v, const uint8_t* descriptors, int n, int levelsup,
                                           uint32_t* word_id, double* weight, uint32_t* node_id) {
   if (!v || n < 0 || (n > 0 && (!descriptors || !word_id || !weight || !node_id)))
-    return vfail(ORBFE_ERR_INVALID, "vocabulary_transform: bad argument");
+    return fail(ORBFE_ERR_INVALID, "vocabulary_transform: bad argument");
   if (n == 0) return 0;
   VHIP(hipSetDevice(v->device));
   if (n > v->scratchCap) {
@@ -505,10 +504,10 @@ extern "C" int orbfe_vocabulary_featvec_batch_device(orbfe_vocabulary* v, const 
                                                      double* d_weight) {
   if (!v || n_frames < 0 || capacity <= 0 || !d_descriptors || !d_n || !d_fv_nodes || !d_fv_offsets ||
       !d_fv_indices || !d_fv_count || ((d_word == nullptr) != (d_weight == nullptr)))
-    return vfail(ORBFE_ERR_INVALID, "vocabulary_featvec_batch_device: bad argument");
+    return fail(ORBFE_ERR_INVALID, "vocabulary_featvec_batch_device: bad argument");
   if (n_frames == 0) return ORBFE_OK;
   const int sortN = next_pow2(capacity);
-  if ((size_t)sortN * 8 > 96 * 1024) return vfail(ORBFE_ERR_INVALID, "vocabulary_featvec_batch_device: capacity > 8192");
+  if ((size_t)sortN * 8 > 96 * 1024) return fail(ORBFE_ERR_INVALID, "vocabulary_featvec_batch_device: capacity > 8192");
   VHIP(hipSetDevice(v->device));
   FeatVecBatch b = {};
   b.desc = d_descriptors; b.n = d_n; b.capacity = capacity; b.sortN = sortN;
@@ -539,12 +538,6 @@ extern "C" int orbfe_vocabulary_featvec_batch_device(orbfe_vocabulary* v, const 
 // Tracking::TrackReferenceKeyFrame-style matching over a device-resident batch: for t = 1..n-1,
 // ComputeBoW of both frames then SearchByBoW(KF = frame t-1 with a MapPoint on every feature,
 // F = frame t)  (src/Tracking.cc:836-843, src/ORBmatcher.cc:185-325).
-extern "C" int orbfe_extractor_consumer_begin_(orbfe_extractor* e, hipStream_t* s);
-extern "C" int orbfe_extractor_consumer_end_(orbfe_extractor* e);
-extern "C" int orbfe_extractor_split_(orbfe_extractor* e, int* S, int* per, int* frames, int* lanes, hipStream_t* streams,
-                                      hipEvent_t* chunkDone);
-extern "C" void orbfe_extractor_stage_mark_(orbfe_extractor* e, int stage, int sub, int isEnd, hipStream_t s, int frames);
-
 // e != NULL: enqueue on the extractor's stream, ordered behind every sub-batch of its last extract call, and
 // return without waiting (orbfe_extractor_synchronize() to wait); e == NULL: the vocabulary's own stream, waits.
 // step: frame t of the call is frame slot t*step of the arrays (2 = the left frames of an L,R-interleaved stereo batch)
@@ -554,10 +547,10 @@ static int bow_match_consecutive(orbfe_vocabulary* v, orbfe_extractor* e, int n_
                                  int check_orientation, int32_t* d_match, int32_t* d_nmatches, int step = 1) {
   if (!v || n_frames < 0 || capacity <= 0 || capacity > 65535 || !d_keypoints || !d_descriptors || !d_n || !d_match ||
       !d_nmatches)
-    return vfail(ORBFE_ERR_INVALID, "bow_match_consecutive_batch_device: bad argument");
+    return fail(ORBFE_ERR_INVALID, "bow_match_consecutive_batch_device: bad argument");
   if (n_frames < 2) return ORBFE_OK;
   const int sortN = next_pow2(capacity);
-  if ((size_t)sortN * 8 > 64 * 1024) return vfail(ORBFE_ERR_INVALID, "bow_match_consecutive_batch_device: capacity > 8192");
+  if ((size_t)sortN * 8 > 64 * 1024) return fail(ORBFE_ERR_INVALID, "bow_match_consecutive_batch_device: capacity > 8192");
   VHIP(hipSetDevice(v->device));
   int rc;
   if ((size_t)n_frames > v->wFrames || capacity > v->wCap || (v->lastMulti && v->lastMulti != e)) {
@@ -679,7 +672,7 @@ extern "C" int orbfe_bow_match_consecutive_batch_device_async(orbfe_vocabulary* 
                                                               int capacity, int levelsup, float nnratio,
                                                               int check_orientation, int32_t* d_match,
                                                               int32_t* d_nmatches) {
-  if (!e) return vfail(ORBFE_ERR_INVALID, "bow_match_consecutive_batch_device_async: NULL extractor");
+  if (!e) return fail(ORBFE_ERR_INVALID, "bow_match_consecutive_batch_device_async: NULL extractor");
   return bow_match_consecutive(v, e, n_frames, d_keypoints, d_descriptors, d_n, capacity, levelsup, nnratio,
                                check_orientation, d_match, d_nmatches);
 }
@@ -692,16 +685,7 @@ extern "C" int orbfe_bow_match_consecutive_stereo_batch_device_async(orbfe_vocab
                                                                      int capacity, int levelsup, float nnratio,
                                                                      int check_orientation, int32_t* d_match,
                                                                      int32_t* d_nmatches) {
-  if (!e) return vfail(ORBFE_ERR_INVALID, "bow_match_consecutive_stereo_batch_device_async: NULL extractor");
+  if (!e) return fail(ORBFE_ERR_INVALID, "bow_match_consecutive_stereo_batch_device_async: NULL extractor");
   return bow_match_consecutive(v, e, n_pairs, d_keypoints, d_descriptors, d_n, capacity, levelsup, nnratio,
                                check_orientation, d_match, d_nmatches, 2);
-}
-
-// internal: device view for the batched BoW path (extractor.hip)
-extern "C" int orbfe_vocabulary_device_(orbfe_vocabulary* v, VocabDevice* out, int* L, int* device) {
-  if (!v) return vfail(ORBFE_ERR_INVALID, "NULL vocabulary");
-  *out = v->d;
-  *L = v->L;
-  *device = v->device;
-  return ORBFE_OK;
 }
