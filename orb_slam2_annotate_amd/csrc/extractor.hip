@@ -27,12 +27,6 @@ int orbfe::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define HIPCHK(expr)                                                                   \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess)                                                              \
-      return fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-  } while (0)
 
 extern "C" const char* orbfe_last_error(void) { return g_err.c_str(); }
 extern "C" int orbfe_device_count(void) {
@@ -42,6 +36,12 @@ extern "C" int orbfe_device_count(void) {
 }
 
 static_assert(sizeof(orbfe_keypoint) == 28, "cv::KeyPoint layout");
+
+// one timed interval of a stage (between the handle's events evA .. evB of the same index): what was launched in it
+struct StageInterval {
+  bool used = false;  // closed and not yet read out (resolve_slot)
+  int launches = 0, frames = 0;
+};
 
 struct orbfe_extractor {
   ExtractorTables tab;
@@ -73,19 +73,32 @@ struct orbfe_extractor {
   bool readerPending = false;
   int chunksPending = 0;                     // sub-batch streams 1..chunksPending-1 carry an unrecorded-for-consumer event
   bool consumerPending = false;
-  int lastSplitFrames = -1, lastSplitStreams = -1;
-  int lastPer = 0, lastS = 1;     // frames per sub-batch and sub-batch count of the last run_pipeline call
-  bool lastLanes = false;
+  SubSplit last;                  // how the last run_pipeline call was split
   double stageFrames[ORBFE_STAGE_COUNT] = {};
   // stage timing: a ring of event pairs per stage so that asynchronous calls can stay in flight
   static constexpr int kEvRing = 8;
   static constexpr int kEvSubs = kMaxStreams;  // one event pair per (call slot, sub-batch stream, stage)
   hipEvent_t evA[kEvRing][kEvSubs][ORBFE_STAGE_COUNT] = {}, evB[kEvRing][kEvSubs][ORBFE_STAGE_COUNT] = {};
-  bool evUsed[kEvRing][kEvSubs][ORBFE_STAGE_COUNT] = {};
-  int evLaunches[kEvRing][kEvSubs][ORBFE_STAGE_COUNT] = {};
-  int evFrames[kEvRing][kEvSubs][ORBFE_STAGE_COUNT] = {};
+  StageInterval ev[kEvRing][kEvSubs][ORBFE_STAGE_COUNT];
   int evSlot = 0;
   unsigned stageMask = 0;
+  bool stage_on(int stage, int sub) const { return sub >= 0 && sub < kEvSubs && ((stageMask >> stage) & 1u); }
+  // opens the interval of (stage, sub-batch) in the current ring slot on stream s -- or, when this slot already holds
+  // one (a second matcher behind the same sub-batch: stereo, then BoW), counts the launches into it: one interval from
+  // the first one's start to the last one's end
+  void stage_open(int stage, int sub, hipStream_t s, int launches, int frames) {
+    if (!stage_on(stage, sub)) return;
+    StageInterval& iv = ev[evSlot][sub][stage];
+    if (iv.used) { iv.launches += launches; return; }
+    (void)hipEventRecord(evA[evSlot][sub][stage], s);
+    iv.launches = launches;
+    iv.frames = frames;
+  }
+  void stage_close(int stage, int sub, hipStream_t s) {
+    if (!stage_on(stage, sub)) return;
+    (void)hipEventRecord(evB[evSlot][sub][stage], s);
+    ev[evSlot][sub][stage].used = true;
+  }
   bool hostOctree = false;  // debug cross-check only (orbfe_extractor_debug_host_octree)
   // GaussianBlur inside the FAST kernel (k_fast_cells<.., true>) instead of the separate k_blur7 launch.  Measured
   // (r02, same box, 4096 VGA frames): fused 8.41 ms vs 5.28 + 3.26 ms for the two launches, pipeline 285.9 k vs
@@ -97,8 +110,8 @@ struct orbfe_extractor {
   int fastMode = 0;
   bool fastLowFirst = false;                 // current choice in auto mode
   static constexpr int kStatSlots = 64;       // counters per sub-batch (k_fast_cells spreads its sampled reports over them)
-  unsigned int* d_fastStat = nullptr;        // per sub-batch: sampled count of cells that needed minThFAST
-  unsigned int* h_fastStat = nullptr;        // pinned copy
+  DevBuf<unsigned int> d_fastStat;           // per sub-batch: sampled count of cells that needed minThFAST
+  PinBuf<unsigned int> h_fastStat;           // pinned copy
   hipEvent_t evStat[kMaxStreams] = {};
   bool statPending[kMaxStreams] = {};
   double statCells[kMaxStreams] = {};
@@ -111,58 +124,56 @@ struct orbfe_extractor {
   FrameGeom geom;
   int capFrames = 0;  // frames the workspace is sized for
   // constant device tables
-  float4* d_patternF = nullptr;
-  uint4* d_momentTab = nullptr;
-  uint8_t* d_hostIn = nullptr;      // input slab of the small host-batch path (frames at the caller's pitch)
+  DevBuf<float4> d_patternF;
+  DevBuf<uint4> d_momentTab;
+  DevBuf<uint8_t> d_hostIn;         // input slab of the small host-batch path (frames at the caller's pitch)
   size_t hostInBytes = 0;
-  DescTile* d_descTiles = nullptr;  // tile form of the orientation + descriptor stage (k_desc_tiles.hip)
+  DevBuf<DescTile> d_descTiles;     // tile form of the orientation + descriptor stage (k_desc_tiles.hip)
   int nDescTiles = 0;
   int knockoutChunks = 0;
   int descTilesMode = -1;           // -1: $ORBFE_DESC_TILES (default 0 = the per-keypoint form); 0 / 1 forced by orbfe_extractor_set_desc_tiles
-  int32_t* d_umax = nullptr;
-  CellDesc* d_cells = nullptr;
-  LevelGeom* d_lvgeom = nullptr;
-  int32_t* d_xofs[kMaxLevels] = {};
-  int16_t* d_alpha[kMaxLevels] = {};
-  int32_t* d_yofs[kMaxLevels] = {};
-  int16_t* d_beta[kMaxLevels] = {};
-  uint32_t* d_colrec[kMaxLevels] = {};
-  uint32_t* d_rowrec[kMaxLevels] = {};
-  ChainTile* d_chainTiles = nullptr;    // the one-launch pyramid of the single-frame form (k_pyramid_chain): tiles + what each needs
+  DevBuf<int32_t> d_umax;
+  DevBuf<CellDesc> d_cells;
+  DevBuf<LevelGeom> d_lvgeom;
+  DevBuf<int32_t> d_xofs[kMaxLevels];
+  DevBuf<int16_t> d_alpha[kMaxLevels];
+  DevBuf<int32_t> d_yofs[kMaxLevels];
+  DevBuf<int16_t> d_beta[kMaxLevels];
+  DevBuf<uint32_t> d_colrec[kMaxLevels];
+  DevBuf<uint32_t> d_rowrec[kMaxLevels];
+  DevBuf<ChainTile> d_chainTiles;       // the one-launch pyramid of the single-frame form (k_pyramid_chain): tiles + what each needs
   int nChainTiles = 0, chainBufA = 0, chainBufB = 0, chainMaxW = 0, chainMaxH = 0;
   bool chainOk = false;
   bool pyrChain = false;                // use it for calls of <= 8 frames ($ORBFE_PYR_CHAIN, orbfe_extractor_set_pyramid_chain): off,
                                         // it measured no faster than the seven launches
-  int32_t* d_tileGx[kMaxLevels] = {};   // ownership tables of the fused blur + resize kernel (ResizeTables::tileGx / tileDy)
-  int32_t* d_tileDy[kMaxLevels] = {};
+  DevBuf<int32_t> d_tileGx[kMaxLevels];  // ownership tables of the fused blur + resize kernel (ResizeTables::tileGx / tileDy)
+  DevBuf<int32_t> d_tileDy[kMaxLevels];
   bool pyrBlur = true;                  // blur level l and write level l+1 from the same staged tiles ($ORBFE_PYRBLUR,
                                         // orbfe_extractor_set_pyramid_blur)
   // per-batch workspace
-  uint8_t* d_pyr = nullptr;
-  uint8_t* d_blur = nullptr;
-  Candidate* d_slots = nullptr;
-  Candidate* d_cand = nullptr;
-  uint16_t* d_cellCount = nullptr;
-  int32_t* d_cellPrefix = nullptr;
-  int32_t* d_candCount = nullptr;
-  uint16_t* d_nodeOf = nullptr;
-  uint8_t* d_octreeWork = nullptr;  // node lists of k_octree_global (only when they do not fit in LDS)
+  DevBuf<uint8_t> d_pyr;
+  DevBuf<uint8_t> d_blur;
+  DevBuf<Candidate> d_slots;
+  DevBuf<Candidate> d_cand;
+  DevBuf<uint16_t> d_cellCount;
+  DevBuf<int32_t> d_cellPrefix;
+  DevBuf<int32_t> d_candCount;
+  DevBuf<uint16_t> d_nodeOf;
+  DevBuf<uint8_t> d_octreeWork;     // node lists of k_octree_global (only when they do not fit in LDS)
   size_t octreeWorkStride = 0;
-  float* d_scaleTab = nullptr;     // mvScaleFactor[16] + mvInvScaleFactor[16]
-  float* d_frameStereo = nullptr;  // orbfe_extract_stereo_frame: mvuRight | mvDepth | survivors of the pair
+  DevBuf<float> d_scaleTab;        // mvScaleFactor[16] + mvInvScaleFactor[16]
+  DevBuf<float> d_frameStereo;     // orbfe_extract_stereo_frame: mvuRight | mvDepth | survivors of the pair
   size_t frameStereoCap = 0;
-  int32_t* d_stereoSad = nullptr;  // scratch of the batched stereo matcher
-  int32_t* d_stereoRowStart = nullptr;
-  int32_t* d_stereoSorted = nullptr;
-  float4* d_stereoRec = nullptr;   // (uR, yR, octave, index) of the right keypoints in row order
+  DevBuf<int32_t> d_stereoSad;     // scratch of the batched stereo matcher
+  DevBuf<int32_t> d_stereoRowStart;
+  DevBuf<int32_t> d_stereoSorted;
+  DevBuf<float4> d_stereoRec;      // (uR, yR, octave, index) of the right keypoints in row order
   size_t stereoSadCap = 0, stereoRowCap = 0;
-  LevelKp* d_levelKp = nullptr;
-  int32_t* d_levelCount = nullptr;
-  // device-side outputs used by the host-buffer API
+  DevBuf<LevelKp> d_levelKp;
+  DevBuf<int32_t> d_levelCount;
   // outputs of the host-buffer API: ONE block [keypoints | descriptors | counts], so a small batch
   // comes back in a single D2H copy through the pinned staging buffer
-  uint8_t* d_outBlock = nullptr;
-  size_t outBlockBytes = 0;      // bytes from the block start to the end of the counts of the last call
+  DevBuf<uint8_t> d_outBlock;
   orbfe_keypoint* d_kpOut = nullptr;
   uint8_t* d_descOut = nullptr;
   int32_t* d_nOut = nullptr;
@@ -170,14 +181,14 @@ struct orbfe_extractor {
   // orbfe_extract_batch): orbfe_frame_from_extractor builds resident frames from it without the features travelling again
   int outLastFrames = 0, outLastCapacity = 0;
   std::vector<int32_t> outLastCount;
-  uint8_t* h_outStage = nullptr;  // pinned
+  PinBuf<uint8_t> h_outStage;
   size_t outStageBytes = 0;
   int outCap = 0;
   // pinned-host pipelined path (orbfe_extract_batch_pipelined): two input slabs + two output blocks in HBM,
   // one copy stream per direction, events per slot
   hipStream_t sH2D = nullptr, sD2H = nullptr;
-  uint8_t* d_pipeIn[2] = {nullptr, nullptr};
-  uint8_t* d_pipeOut[2] = {nullptr, nullptr};
+  DevBuf<uint8_t> d_pipeIn[2];
+  DevBuf<uint8_t> d_pipeOut[2];
   size_t pipeInBytes = 0, pipeOutBytes = 0;
   hipEvent_t evIn[2] = {}, evComp[2] = {}, evOutDone[2] = {};
   // host staging
@@ -187,25 +198,11 @@ struct orbfe_extractor {
   // description of the last call (for mvImagePyramid-style reads)
   PyramidViews lastPyr = {};
   PyramidViews lastBlur = {};
-  int lastFrames = 0;
   int lastFrameBase = 0;  // index, in the caller's batch, of the first frame the retained pyramid belongs to (pipelined host path: its LAST chunk)
   bool haveLast = false;
 };
 
 namespace {
-
-template <typename T>
-int dalloc(T** p, size_t n) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (n == 0) n = 1;
-  HIPCHK(hipMalloc((void**)p, n * sizeof(T)));
-  return ORBFE_OK;
-}
-template <typename T>
-void dfree(T** p) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-}
 
 // HIP streams of destroyed handles are kept and handed to the next handle that asks for the same role (sub-batch i, the
 // two copy streams).  Two reasons.  (1) hipStreamCreate / Destroy are not free, and a process that makes one handle per
@@ -285,19 +282,22 @@ int ensure_subs(orbfe_extractor* e, int n) {
 }
 
 void free_geometry(orbfe_extractor* e) {
-  dfree(&e->d_cells);
-  dfree(&e->d_lvgeom);
-  dfree(&e->d_descTiles);
+  e->d_cells.reset();
+  e->d_lvgeom.reset();
+  e->d_descTiles.reset();
   e->nDescTiles = 0;
-  dfree(&e->d_chainTiles);
+  e->d_chainTiles.reset();
   e->nChainTiles = 0;
   e->chainOk = false;
-  for (int l = 0; l < kMaxLevels; l++) { dfree(&e->d_xofs[l]); dfree(&e->d_alpha[l]); dfree(&e->d_yofs[l]); dfree(&e->d_beta[l]); dfree(&e->d_colrec[l]); dfree(&e->d_rowrec[l]); dfree(&e->d_tileGx[l]); dfree(&e->d_tileDy[l]); }
+  for (int l = 0; l < kMaxLevels; l++) {
+    e->d_xofs[l].reset(); e->d_alpha[l].reset(); e->d_yofs[l].reset(); e->d_beta[l].reset();
+    e->d_colrec[l].reset(); e->d_rowrec[l].reset(); e->d_tileGx[l].reset(); e->d_tileDy[l].reset();
+  }
 }
 void free_workspace(orbfe_extractor* e) {
-  dfree(&e->d_pyr); dfree(&e->d_blur); dfree(&e->d_slots); dfree(&e->d_cand);
-  dfree(&e->d_cellCount); dfree(&e->d_cellPrefix); dfree(&e->d_candCount); dfree(&e->d_nodeOf);
-  dfree(&e->d_levelKp); dfree(&e->d_levelCount); dfree(&e->d_octreeWork);
+  e->d_pyr.reset(); e->d_blur.reset(); e->d_slots.reset(); e->d_cand.reset();
+  e->d_cellCount.reset(); e->d_cellPrefix.reset(); e->d_candCount.reset(); e->d_nodeOf.reset();
+  e->d_levelKp.reset(); e->d_levelCount.reset(); e->d_octreeWork.reset();
   e->octreeWorkStride = 0;
   e->capFrames = 0;
 }
@@ -310,10 +310,54 @@ int reader_settle(orbfe_extractor* e) {
 }
 void free_outputs(orbfe_extractor* e) {
   (void)reader_settle(e);
-  dfree(&e->d_outBlock);
+  e->d_outBlock.reset();
   e->d_kpOut = nullptr; e->d_descOut = nullptr; e->d_nOut = nullptr;
   e->outCap = 0;
   e->outLastFrames = 0;
+}
+
+// k_pyramid_chain: 32 x 32 tiles of levels 1 .. n-1, each with the rectangles it needs of the levels below it
+// (walking the cv::resize tables back to level 0); usable (ok) while the two LDS rectangle buffers fit
+struct ChainPlan {
+  std::vector<ChainTile> tiles;
+  size_t bufA = 0, bufB = 0;
+  int maxW = 0, maxH = 0;
+  bool ok = false;
+};
+ChainPlan build_chain_tiles(const FrameGeom& g) {
+  ChainPlan c;
+  bool ok = g.nlevels > 1;
+  for (int l = g.nlevels - 1; l >= 1 && ok; l--) {  // the longest chains first
+    const int TS = l >= 4 ? 16 : 32;  // (deep levels: smaller tiles, i.e. smaller rectangles to recompute -- 16 measured best of 32 / 16 / 8)
+    for (int y0 = 0; y0 < g.lv[l].h && ok; y0 += TS)
+      for (int x0 = 0; x0 < g.lv[l].w; x0 += TS) {
+        ChainTile t = {};
+        t.level = l;
+        int rx0 = x0, ry0 = y0, rx1 = std::min(x0 + TS, g.lv[l].w) - 1, ry1 = std::min(y0 + TS, g.lv[l].h) - 1;  // inclusive
+        for (int k = l; k >= 0; k--) {
+          const int w = rx1 - rx0 + 1, h = ry1 - ry0 + 1;
+          if (w > 255 || h > 255) { ok = false; break; }
+          t.r[k] = ChainRect{(int16_t)rx0, (int16_t)ry0, (int16_t)w, (int16_t)h};
+          const size_t bytes = (size_t)((w + 3) & ~3) * h;
+          if (k & 1) c.bufB = std::max(c.bufB, bytes); else c.bufA = std::max(c.bufA, bytes);
+          if (k > 0) { c.maxW = std::max(c.maxW, w); c.maxH = std::max(c.maxH, h); }  // (table entries of the level-k output rectangle)
+          if (k == 0) break;
+          const ResizeTables& z = g.rz[k];
+          const int Wp = g.lv[k - 1].w, Hp = g.lv[k - 1].h;
+          auto clampr = [&](int v) { return v < 0 ? 0 : (v >= Hp ? Hp - 1 : v); };
+          const int sx0 = z.xofs[rx0], sx1 = std::min(z.xofs[rx1] + 1, Wp - 1);
+          const int sy0 = clampr(z.yofs[ry0]), sy1 = clampr(z.yofs[ry1] + 1);
+          rx0 = sx0; rx1 = std::max(sx1, sx0); ry0 = sy0; ry1 = std::max(sy1, sy0);
+        }
+        if (!ok) break;
+        c.tiles.push_back(t);
+      }
+  }
+  c.bufA = (c.bufA + 15) & ~(size_t)15;
+  c.bufB = (c.bufB + 15) & ~(size_t)15;
+  if (ok && c.bufA + c.bufB + (size_t)(c.maxW + c.maxH) * 8 > (size_t)60 * 1024) ok = false;
+  c.ok = ok && !c.tiles.empty();
+  return c;
 }
 
 int ensure_geometry(orbfe_extractor* e, int W, int H) {
@@ -340,85 +384,26 @@ int ensure_geometry(orbfe_extractor* e, int W, int H) {
     return fail(ORBFE_ERR_INVALID, "nfeatures too large: more than 65532 keypoints on one pyramid level");
   e->octreeMaxL = maxL;  // octree_lds_bytes(maxL) > kOctreeLdsLimit: node lists in global memory (ensure_workspace)
   int rc;
-  if ((rc = dalloc(&e->d_cells, g.cells.size()))) return rc;
-  if (!g.cells.empty()) HIPCHK(hipMemcpy(e->d_cells, g.cells.data(), g.cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
-  if ((rc = dalloc(&e->d_lvgeom, (size_t)kMaxLevels))) return rc;
-  HIPCHK(hipMemcpy(e->d_lvgeom, g.lv, sizeof(LevelGeom) * kMaxLevels, hipMemcpyHostToDevice));
-  {
-    const std::vector<DescTile> tiles = build_desc_tiles(g.lv, g.nlevels);
-    e->nDescTiles = (int)tiles.size();
-    if (!tiles.empty()) {
-      if ((rc = dalloc(&e->d_descTiles, tiles.size()))) return rc;
-      HIPCHK(hipMemcpy(e->d_descTiles, tiles.data(), tiles.size() * sizeof(DescTile), hipMemcpyHostToDevice));
-    }
-  }
-  {
-    // k_pyramid_chain: 32 x 32 tiles of levels 1 .. n-1, each with the rectangles it needs of the levels below it
-    // (walking the cv::resize tables back to level 0); usable while the two LDS rectangle buffers fit
-    std::vector<ChainTile> tiles;
-    size_t bufA = 0, bufB = 0;
-    int maxW = 0, maxH = 0;
-    bool ok = g.nlevels > 1;
-    for (int l = g.nlevels - 1; l >= 1 && ok; l--) {  // the longest chains first
-      const int TS = l >= 4 ? 16 : 32;  // (deep levels: smaller tiles, i.e. smaller rectangles to recompute -- 16 measured best of 32 / 16 / 8)
-      for (int y0 = 0; y0 < g.lv[l].h && ok; y0 += TS)
-        for (int x0 = 0; x0 < g.lv[l].w; x0 += TS) {
-          ChainTile t = {};
-          t.level = l;
-          int rx0 = x0, ry0 = y0, rx1 = std::min(x0 + TS, g.lv[l].w) - 1, ry1 = std::min(y0 + TS, g.lv[l].h) - 1;  // inclusive
-          for (int k = l; k >= 0; k--) {
-            const int w = rx1 - rx0 + 1, h = ry1 - ry0 + 1;
-            if (w > 255 || h > 255) { ok = false; break; }
-            t.r[k] = ChainRect{(int16_t)rx0, (int16_t)ry0, (int16_t)w, (int16_t)h};
-            const size_t bytes = (size_t)((w + 3) & ~3) * h;
-            if (k & 1) bufB = std::max(bufB, bytes); else bufA = std::max(bufA, bytes);
-            if (k > 0) { maxW = std::max(maxW, w); maxH = std::max(maxH, h); }  // (table entries of the level-k output rectangle)
-            if (k == 0) break;
-            const ResizeTables& z = g.rz[k];
-            const int Wp = g.lv[k - 1].w, Hp = g.lv[k - 1].h;
-            auto clampr = [&](int v) { return v < 0 ? 0 : (v >= Hp ? Hp - 1 : v); };
-            const int sx0 = z.xofs[rx0], sx1 = std::min(z.xofs[rx1] + 1, Wp - 1);
-            const int sy0 = clampr(z.yofs[ry0]), sy1 = clampr(z.yofs[ry1] + 1);
-            rx0 = sx0; rx1 = std::max(sx1, sx0); ry0 = sy0; ry1 = std::max(sy1, sy0);
-          }
-          if (!ok) break;
-          tiles.push_back(t);
-        }
-    }
-    bufA = (bufA + 15) & ~(size_t)15;
-    bufB = (bufB + 15) & ~(size_t)15;
-    if (ok && bufA + bufB + (size_t)(maxW + maxH) * 8 > (size_t)60 * 1024) ok = false;
-    e->chainOk = false;
-    if (ok && !tiles.empty()) {
-      if ((rc = dalloc(&e->d_chainTiles, tiles.size()))) return rc;
-      HIPCHK(hipMemcpy(e->d_chainTiles, tiles.data(), tiles.size() * sizeof(ChainTile), hipMemcpyHostToDevice));
-      e->nChainTiles = (int)tiles.size();
-      e->chainBufA = (int)bufA; e->chainBufB = (int)bufB; e->chainMaxW = maxW; e->chainMaxH = maxH;
-      e->chainOk = true;
-    }
+  if ((rc = e->d_cells.upload(g.cells))) return rc;
+  if ((rc = e->d_lvgeom.upload(g.lv, (size_t)kMaxLevels))) return rc;
+  const std::vector<DescTile> descTiles = build_desc_tiles(g.lv, g.nlevels);
+  e->nDescTiles = (int)descTiles.size();
+  if (!descTiles.empty() && (rc = e->d_descTiles.upload(descTiles))) return rc;
+  const ChainPlan chain = build_chain_tiles(g);
+  if (chain.ok) {
+    if ((rc = e->d_chainTiles.upload(chain.tiles))) return rc;
+    e->nChainTiles = (int)chain.tiles.size();
+    e->chainBufA = (int)chain.bufA; e->chainBufB = (int)chain.bufB; e->chainMaxW = chain.maxW; e->chainMaxH = chain.maxH;
+    e->chainOk = true;
   }
   for (int l = 1; l < g.nlevels; l++) {
     const ResizeTables& t = g.rz[l];
-    if ((rc = dalloc(&e->d_xofs[l], t.xofs.size()))) return rc;
-    if ((rc = dalloc(&e->d_alpha[l], t.alpha.size()))) return rc;
-    if ((rc = dalloc(&e->d_yofs[l], t.yofs.size()))) return rc;
-    if ((rc = dalloc(&e->d_beta[l], t.beta.size()))) return rc;
-    HIPCHK(hipMemcpy(e->d_xofs[l], t.xofs.data(), t.xofs.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_alpha[l], t.alpha.data(), t.alpha.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_yofs[l], t.yofs.data(), t.yofs.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_beta[l], t.beta.data(), t.beta.size() * 2, hipMemcpyHostToDevice));
-    if (!t.colrec.empty()) {
-      if ((rc = dalloc(&e->d_colrec[l], t.colrec.size()))) return rc;
-      if ((rc = dalloc(&e->d_rowrec[l], t.rowrec.size()))) return rc;
-      HIPCHK(hipMemcpy(e->d_colrec[l], t.colrec.data(), t.colrec.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_rowrec[l], t.rowrec.data(), t.rowrec.size() * 4, hipMemcpyHostToDevice));
-      if (!t.tileGx.empty()) {
-        if ((rc = dalloc(&e->d_tileGx[l], t.tileGx.size()))) return rc;
-        if ((rc = dalloc(&e->d_tileDy[l], t.tileDy.size()))) return rc;
-        HIPCHK(hipMemcpy(e->d_tileGx[l], t.tileGx.data(), t.tileGx.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_tileDy[l], t.tileDy.data(), t.tileDy.size() * 4, hipMemcpyHostToDevice));
-      }
-    }
+    if ((rc = e->d_xofs[l].upload(t.xofs)) || (rc = e->d_alpha[l].upload(t.alpha))) return rc;
+    if ((rc = e->d_yofs[l].upload(t.yofs)) || (rc = e->d_beta[l].upload(t.beta))) return rc;
+    if (t.colrec.empty()) continue;
+    if ((rc = e->d_colrec[l].upload(t.colrec)) || (rc = e->d_rowrec[l].upload(t.rowrec))) return rc;
+    if (t.tileGx.empty()) continue;
+    if ((rc = e->d_tileGx[l].upload(t.tileGx)) || (rc = e->d_tileDy[l].upload(t.tileDy))) return rc;
   }
   return ORBFE_OK;
 }
@@ -429,19 +414,19 @@ int ensure_workspace(orbfe_extractor* e, int nFrames) {
   const FrameGeom& g = e->geom;
   const size_t B = (size_t)nFrames;
   int rc;
-  if ((rc = dalloc(&e->d_pyr, B * g.pyrBytes))) return rc;
-  if ((rc = dalloc(&e->d_blur, B * g.pyrBytes))) return rc;
-  if ((rc = dalloc(&e->d_slots, B * (size_t)g.totalSlots))) return rc;
-  if ((rc = dalloc(&e->d_cand, B * (size_t)g.totalSlots))) return rc;
-  if ((rc = dalloc(&e->d_cellCount, B * g.cells.size()))) return rc;
-  if ((rc = dalloc(&e->d_cellPrefix, B * g.cells.size()))) return rc;
-  if ((rc = dalloc(&e->d_candCount, B * (size_t)g.nlevels))) return rc;
-  if ((rc = dalloc(&e->d_nodeOf, B * (size_t)g.totalSlots))) return rc;
-  if ((rc = dalloc(&e->d_levelKp, B * (size_t)g.totalKpCap))) return rc;
-  if ((rc = dalloc(&e->d_levelCount, B * (size_t)g.nlevels))) return rc;
+  if ((rc = e->d_pyr.alloc(B * g.pyrBytes))) return rc;
+  if ((rc = e->d_blur.alloc(B * g.pyrBytes))) return rc;
+  if ((rc = e->d_slots.alloc(B * (size_t)g.totalSlots))) return rc;
+  if ((rc = e->d_cand.alloc(B * (size_t)g.totalSlots))) return rc;
+  if ((rc = e->d_cellCount.alloc(B * g.cells.size()))) return rc;
+  if ((rc = e->d_cellPrefix.alloc(B * g.cells.size()))) return rc;
+  if ((rc = e->d_candCount.alloc(B * (size_t)g.nlevels))) return rc;
+  if ((rc = e->d_nodeOf.alloc(B * (size_t)g.totalSlots))) return rc;
+  if ((rc = e->d_levelKp.alloc(B * (size_t)g.totalKpCap))) return rc;
+  if ((rc = e->d_levelCount.alloc(B * (size_t)g.nlevels))) return rc;
   if (octree_lds_bytes(e->octreeMaxL) > kOctreeLdsLimit) {
     e->octreeWorkStride = (octree_lds_bytes(e->octreeMaxL) + 255) & ~(size_t)255;
-    if ((rc = dalloc(&e->d_octreeWork, B * (size_t)g.nlevels * e->octreeWorkStride))) return rc;
+    if ((rc = e->d_octreeWork.alloc(B * (size_t)g.nlevels * e->octreeWorkStride))) return rc;
   }
   e->capFrames = nFrames;
   return ORBFE_OK;
@@ -455,8 +440,8 @@ int ensure_outputs(orbfe_extractor* e, int nFrames, int capacity) {
   const size_t kpBytes = ((size_t)need * sizeof(orbfe_keypoint) + 255) & ~(size_t)255;
   const size_t descBytes = ((size_t)need * 32 + 255) & ~(size_t)255;
   const size_t cntBytes = (size_t)(nFrames > 4096 ? nFrames : 4096) * 4;
-  if ((rc = dalloc(&e->d_outBlock, kpBytes + descBytes + cntBytes))) return rc;
-  e->d_kpOut = reinterpret_cast<orbfe_keypoint*>(e->d_outBlock);
+  if ((rc = e->d_outBlock.alloc(kpBytes + descBytes + cntBytes))) return rc;
+  e->d_kpOut = reinterpret_cast<orbfe_keypoint*>(e->d_outBlock.p);
   e->d_descOut = e->d_outBlock + kpBytes;
   e->d_nOut = reinterpret_cast<int32_t*>(e->d_outBlock + kpBytes + descBytes);
   e->outCap = need;
@@ -470,40 +455,31 @@ struct StageTimer {
   orbfe_extractor* e;
   int stage, sub;
   hipStream_t s;
-  bool on;
   // sub = index of the sub-batch (its stream is s); every sub-batch of a call is timed on its own stream
-  StageTimer(orbfe_extractor* e_, int st, int n, int frames, int sub_, hipStream_t s_)
-      : e(e_), stage(st), sub(sub_), s(s_),
-        on(sub_ >= 0 && sub_ < orbfe_extractor::kEvSubs && ((e_->stageMask >> st) & 1u)) {
-    if (!on) return;
-    (void)hipEventRecord(e->evA[e->evSlot][sub][stage], s);
-    e->evLaunches[e->evSlot][sub][stage] = n;
-    e->evFrames[e->evSlot][sub][stage] = frames;
+  StageTimer(orbfe_extractor* e_, int st, int n, int frames, int sub_, hipStream_t s_) : e(e_), stage(st), sub(sub_), s(s_) {
+    e->stage_open(stage, sub, s, n, frames);
   }
-  ~StageTimer() {
-    if (!on) return;
-    (void)hipEventRecord(e->evB[e->evSlot][sub][stage], s);
-    e->evUsed[e->evSlot][sub][stage] = true;
-  }
+  ~StageTimer() { e->stage_close(stage, sub, s); }
 };
 void resolve_slot(orbfe_extractor* e, int slot) {
   for (int sub = 0; sub < orbfe_extractor::kEvSubs; sub++)
     for (int st = 0; st < ORBFE_STAGE_COUNT; st++) {
-      if (!e->evUsed[slot][sub][st]) continue;
-      e->evUsed[slot][sub][st] = false;
+      StageInterval& iv = e->ev[slot][sub][st];
+      if (!iv.used) continue;
+      iv.used = false;
       float ms = 0;
       if (hipEventSynchronize(e->evB[slot][sub][st]) == hipSuccess &&
           hipEventElapsedTime(&ms, e->evA[slot][sub][st], e->evB[slot][sub][st]) == hipSuccess) {
         e->stageMs[st] += ms;
-        e->stageLaunches[st] += e->evLaunches[slot][sub][st];
-        e->stageFrames[st] += e->evFrames[slot][sub][st];
+        e->stageLaunches[st] += iv.launches;
+        e->stageFrames[st] += iv.frames;
       }
     }
 }
 void resolve_stage_times(orbfe_extractor* e) {
   for (int slot = 0; slot < orbfe_extractor::kEvRing; slot++) resolve_slot(e, slot);
 }
-// advance to the next ring slot before a call records into it (waits for a 16-calls-old one)
+// advance to the next ring slot before a call records into it (waits for the call kEvRing calls back that used it)
 void next_event_slot(orbfe_extractor* e) {
   if (!e->stageMask) return;
   e->evSlot = (e->evSlot + 1) % orbfe_extractor::kEvRing;
@@ -612,6 +588,10 @@ int run_chunk(orbfe_extractor* e, hipStream_t s, int sub, LevelView level0, int 
     pyr.lv[0].base += F * own.frameStride;
   }
   if (pyrOut) { *pyrOut = pyr0; *blurOut = blur0; }
+  // level l of this sub-batch's slice of the handle's own pyramid / blurred slab, writable
+  auto mut = [&](const PyramidViews& v, int l) {
+    return LevelViewMut{const_cast<uint8_t*>(v.lv[l].base), g.pyrBytes, g.lv[l].pitch, g.lv[l].w, g.lv[l].h};
+  };
   Candidate* slots = e->d_slots + F * g.totalSlots;
   Candidate* cand = e->d_cand + F * g.totalSlots;
   uint16_t* cellCount = e->d_cellCount + F * nCells;
@@ -633,7 +613,7 @@ int run_chunk(orbfe_extractor* e, hipStream_t s, int sub, LevelView level0, int 
     ca.l0 = pyr.lv[0];
     for (int l = 0; l < g.nlevels; l++) { ca.w[l] = g.lv[l].w; ca.h[l] = g.lv[l].h; }
     for (int l = 1; l < g.nlevels; l++) {
-      ca.lv[l] = LevelViewMut{const_cast<uint8_t*>(pyr.lv[l].base), g.pyrBytes, g.lv[l].pitch, g.lv[l].w, g.lv[l].h};
+      ca.lv[l] = mut(pyr, l);
       ca.xofs[l] = e->d_xofs[l]; ca.alpha[l] = e->d_alpha[l]; ca.yofs[l] = e->d_yofs[l]; ca.beta[l] = e->d_beta[l];
     }
     ca.tiles = e->d_chainTiles;
@@ -644,18 +624,16 @@ int run_chunk(orbfe_extractor* e, hipStream_t s, int sub, LevelView level0, int 
     StageTimer t(e, ORBFE_STAGE_PYRAMID, pyrBlur ? g.nlevels : g.nlevels - 1, nFrames, sub, s);
     for (int l = 1; l <= g.nlevels && !(ko & 1); l++) {
       if (pyrBlur) {
-        LevelViewMut bdst{const_cast<uint8_t*>(blur.lv[l - 1].base), g.pyrBytes, g.lv[l - 1].pitch, g.lv[l - 1].w, g.lv[l - 1].h};
+        const LevelViewMut bdst = mut(blur, l - 1);
         if (l < g.nlevels && e->d_tileGx[l]) {
-          LevelViewMut next{const_cast<uint8_t*>(pyr.lv[l].base), g.pyrBytes, g.lv[l].pitch, g.lv[l].w, g.lv[l].h};
-          launch_blur7_resize(s, pyr.lv[l - 1], bdst, next, e->d_colrec[l], e->d_rowrec[l], e->d_tileGx[l], e->d_tileDy[l],
+          launch_blur7_resize(s, pyr.lv[l - 1], bdst, mut(pyr, l), e->d_colrec[l], e->d_rowrec[l], e->d_tileGx[l], e->d_tileDy[l],
                               nFrames, e->blurSpec);
           continue;
         }
         launch_blur7(s, pyr.lv[l - 1], bdst, nFrames, e->blurSpec);
       }
       if (l == g.nlevels) break;
-      LevelViewMut dst{const_cast<uint8_t*>(pyr.lv[l].base), g.pyrBytes, g.lv[l].pitch, g.lv[l].w, g.lv[l].h};
-      launch_resize(s, pyr.lv[l - 1], dst, e->d_xofs[l], e->d_alpha[l], e->d_yofs[l], e->d_beta[l], e->d_colrec[l],
+      launch_resize(s, pyr.lv[l - 1], mut(pyr, l), e->d_xofs[l], e->d_alpha[l], e->d_yofs[l], e->d_beta[l], e->d_colrec[l],
                     e->d_rowrec[l], nFrames);
     }
   }
@@ -670,7 +648,7 @@ int run_chunk(orbfe_extractor* e, hipStream_t s, int sub, LevelView level0, int 
     StageTimer t(e, ORBFE_STAGE_BLUR, 1, nFrames, sub, sV);
     LevelViewMut dsts[kMaxLevels];
     for (int l = 0; l < g.nlevels; l++)
-      dsts[l] = LevelViewMut{const_cast<uint8_t*>(blur.lv[l].base), g.pyrBytes, g.lv[l].pitch, g.lv[l].w, g.lv[l].h};
+      dsts[l] = mut(blur, l);
     launch_blur7_levels(sV, pyr.lv, dsts, g.nlevels, nFrames, e->blurSpec);
   };
   const bool blurFirst = !lanes && !fused && !pyrBlur && (sub & 1) != 0;  // measured +1.7 % frames/s (A/B on one box, 4 runs each)
@@ -775,10 +753,10 @@ int run_chunk(orbfe_extractor* e, hipStream_t s, int sub, LevelView level0, int 
     const int tilesMode = e->descTilesMode >= 0 ? e->descTilesMode : kTilesEnv;
     if (tilesMode && e->nDescTiles > 0)
       launch_orient_desc_tiles(sT, a, e->d_descTiles, e->nDescTiles, levelKp, levelCount, e->d_patternF, e->d_momentTab,
-                               e->d_umax, nFrames, d_kp + F * capacity, d_desc + F * (size_t)capacity * 32, d_nOut + F, e->lastS);
+                               e->d_umax, nFrames, d_kp + F * capacity, d_desc + F * (size_t)capacity * 32, d_nOut + F, e->last.S);
     else
       launch_orient_desc(sT, a, levelKp, levelCount, e->d_patternF, e->d_momentTab, e->d_umax, nFrames,
-                         d_kp + F * capacity, d_desc + F * (size_t)capacity * 32, d_nOut + F, e->lastS);
+                         d_kp + F * capacity, d_desc + F * (size_t)capacity * 32, d_nOut + F, e->last.S);
   }
   if (lanes) {
     HIPCHK(hipEventRecord(e->evTail[sub], sT));
@@ -799,26 +777,32 @@ struct PreChunk {
   void* ctx = nullptr;
 };
 
+// host wait for everything the handle has enqueued, and for the frame build that reads its output block
+int sync_all(orbfe_extractor* e) {
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (int i = 0; i < orbfe_extractor::kMaxStreams - 1; i++)
+    if (e->extra[i]) HIPCHK(hipStreamSynchronize(e->extra[i]));
+  return reader_settle(e);
+}
+
 int run_pipeline(orbfe_extractor* e, LevelView level0, int nFrames, orbfe_keypoint* d_kp,
                  uint8_t* d_desc, int capacity, int32_t* d_nOut, const hipEvent_t* waitFor = nullptr, int nWait = 0,
                  const PreChunk* pre = nullptr) {
-  int S = e->hostOctree ? 1 : e->nStreams;
-  if (S > nFrames) S = nFrames;
-  if (S < 1) S = 1;
-  if (e->lastSplitFrames != nFrames || e->lastSplitStreams != (e->laneMode ? -S : S)) {
+  SubSplit sp;
+  sp.frames = nFrames;
+  sp.S = e->hostOctree ? 1 : e->nStreams;
+  if (sp.S > nFrames) sp.S = nFrames;
+  if (sp.S < 1) sp.S = 1;
+  sp.per = (nFrames + sp.S - 1) / sp.S;
+  if ((nFrames & 1) == 0 && (sp.per & 1)) sp.per++;  // stereo batches (L0,R0,L1,R1,...): never split a pair across sub-batches
+  sp.lanes = e->laneMode && !e->hostOctree && sp.S >= 2;
+  e->haveLast = false;  // (until this call is enqueued in full)
+  if (!(sp == e->last)) {
     // a different split maps frames to different streams: drain everything first
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < orbfe_extractor::kMaxStreams - 1; i++)
-      if (e->extra[i]) HIPCHK(hipStreamSynchronize(e->extra[i]));
-    e->lastSplitFrames = nFrames;
-    e->lastSplitStreams = e->laneMode ? -S : S;
+    int rcs = sync_all(e);
+    if (rcs) return rcs;
+    e->last = sp;
   }
-  int per = (nFrames + S - 1) / S;
-  if ((nFrames & 1) == 0 && (per & 1)) per++;  // stereo batches (L0,R0,L1,R1,...): never split a pair across sub-batches
-  const bool lanes = e->laneMode && !e->hostOctree && S >= 2;
-  e->lastPer = per;
-  e->lastS = S;
-  e->lastLanes = lanes;
   // a frame build still reading the output block this call overwrites: every stream that writes the block waits for it
   // (stream 0 included -- the build runs on another thread's matcher stream)
   if (e->readerPending) {
@@ -826,68 +810,119 @@ int run_pipeline(orbfe_extractor* e, LevelView level0, int nFrames, orbfe_keypoi
     (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is not an error
   }
   const bool readerWait = e->readerPending && d_kp == e->d_kpOut;
-  if (lanes) {
-    hipStream_t sP = e->extra[0], sV = e->extra[1], sT = e->stream;
+  hipStream_t sP = nullptr, sV = nullptr, sT = nullptr;
+  if (sp.lanes) {
+    sP = e->extra[0]; sV = e->extra[1]; sT = e->stream;
     if (e->consumerPending) HIPCHK(hipStreamWaitEvent(sP, e->evConsumerDone, 0));  // a matcher still reads the last pyramid
     if (readerWait) HIPCHK(hipStreamWaitEvent(sP, e->evReaderDone, 0));  // (V and T start behind P's events)
     for (int k = 0; k < nWait; k++) {  // e.g. the H2D copy of this chunk (read by P, V and T), the D2H of its output block (T)
       HIPCHK(hipStreamWaitEvent(sP, waitFor[k], 0));
       HIPCHK(hipStreamWaitEvent(sT, waitFor[k], 0));
     }
-    for (int i = 0; i < S; i++) {
-      const int f0 = i * per;
-      const int n = f0 + per <= nFrames ? per : nFrames - f0;
-      if (n <= 0) break;
-      // slice i of the workspace is free once the previous call's tail lane has finished with it
-      if (e->tailPending[i]) HIPCHK(hipStreamWaitEvent(sP, e->evTail[i], 0));
-      if (pre && pre->fn) {  // (slice i's readers of the previous call: behind evTail[i] / evConsumerDone, waited for above)
-        StageTimer t(e, ORBFE_STAGE_H2D, 2, n, i, sP);  // "h2d" = the ingest stage of a call: here the rectification
-        int rcp = pre->fn(pre->ctx, sP, f0, n);
-        if (rcp) return rcp;
-      }
-      int rc = run_chunk(e, sP, i, level0, f0, n, d_kp, d_desc, capacity, d_nOut, i == 0 ? &e->lastPyr : nullptr,
-                         i == 0 ? &e->lastBlur : nullptr, sV, sT);
-      if (rc) return rc;
-    }
-    e->consumerPending = false;
-    e->chunksPending = 1;  // every sub-batch ends on `stream`: consumers there are ordered behind all of them
-    e->lastFrames = nFrames;
-    e->lastFrameBase = 0;
-    e->haveLast = true;
-    return ORBFE_OK;
+  } else {
+    for (int i = 0; i < orbfe_extractor::kMaxStreams; i++) e->tailPending[i] = false;  // (drained above if the mode changed)
   }
-  for (int i = 0; i < orbfe_extractor::kMaxStreams; i++) e->tailPending[i] = false;  // (drained above if the mode changed)
-  for (int i = 0; i < S; i++) {
-    const int f0 = i * per;
-    const int n = f0 + per <= nFrames ? per : nFrames - f0;
-    if (n <= 0) break;
-    hipStream_t s = i == 0 ? e->stream : e->extra[i - 1];
-    if (i > 0 && e->consumerPending) HIPCHK(hipStreamWaitEvent(s, e->evConsumerDone, 0));
-    if (readerWait) HIPCHK(hipStreamWaitEvent(s, e->evReaderDone, 0));
-    for (int k = 0; k < nWait; k++) HIPCHK(hipStreamWaitEvent(s, waitFor[k], 0));  // e.g. the H2D copy of this chunk
+  int f0, n;
+  for (int i = 0; sp.range(i, &f0, &n); i++) {
+    hipStream_t s = sp.lanes ? sP : (i == 0 ? e->stream : e->extra[i - 1]);  // the stream sub-batch i starts on
+    if (sp.lanes) {
+      // slice i of the workspace is free once the previous call's tail lane has finished with it
+      // (slice i's readers of the previous call: behind evTail[i] / evConsumerDone, waited for above)
+      if (e->tailPending[i]) HIPCHK(hipStreamWaitEvent(sP, e->evTail[i], 0));
+    } else {
+      if (i > 0 && e->consumerPending) HIPCHK(hipStreamWaitEvent(s, e->evConsumerDone, 0));
+      if (readerWait) HIPCHK(hipStreamWaitEvent(s, e->evReaderDone, 0));
+      for (int k = 0; k < nWait; k++) HIPCHK(hipStreamWaitEvent(s, waitFor[k], 0));  // e.g. the H2D copy of this chunk
+    }
     if (pre && pre->fn) {
       StageTimer t(e, ORBFE_STAGE_H2D, 2, n, i, s);  // "h2d" = the ingest stage of a call: here the rectification
       int rcp = pre->fn(pre->ctx, s, f0, n);
       if (rcp) return rcp;
     }
     int rc = run_chunk(e, s, i, level0, f0, n, d_kp, d_desc, capacity, d_nOut, i == 0 ? &e->lastPyr : nullptr,
-                       i == 0 ? &e->lastBlur : nullptr);
+                       i == 0 ? &e->lastBlur : nullptr, sV, sT);
     if (rc) return rc;
-    if (i > 0) HIPCHK(hipEventRecord(e->evChunkDone[i], s));
+    if (!sp.lanes && i > 0) HIPCHK(hipEventRecord(e->evChunkDone[i], s));
   }
-  e->consumerPending = false;  // stream 0 is ordered behind the consumer by itself
-  e->chunksPending = S;
-  e->lastFrames = nFrames;
+  // lanes: every sub-batch ends on `stream`, so consumers there are ordered behind all of them; otherwise stream 0 is
+  // ordered behind the consumer by itself and joins the others through evChunkDone
+  e->consumerPending = false;
+  e->chunksPending = sp.lanes ? 1 : sp.S;
   e->lastFrameBase = 0;
   e->haveLast = true;
   return ORBFE_OK;
 }
 
-int sync_all(orbfe_extractor* e) {
+// The prologue of every extract call: the output block is forgotten, geometry and a workspace for nFrames exist, the
+// stage timers have a ring slot.  drain: the call starts on an idle handle (the host-buffer calls); otherwise the handle
+// is only drained when the workspace is about to be re-allocated.
+int begin_call(orbfe_extractor* e, int W, int H, int nFrames, bool drain) {
+  HIPCHK(hipSetDevice(e->device));
+  int rc;
+  if (drain || e->geom.W != W || e->geom.H != H || nFrames > e->capFrames)
+    if ((rc = sync_all(e))) return rc;
+  e->outLastFrames = 0;  // "the frame this handle produced last" is no longer the one in its own output block
+  if ((rc = ensure_geometry(e, W, H))) return rc;
+  if ((rc = ensure_workspace(e, nFrames))) return rc;
+  next_event_slot(e);
+  return ORBFE_OK;
+}
+
+// the input slab of the host-buffer calls (frames at the caller's pitch)
+int ensure_host_in(orbfe_extractor* e, size_t bytes) {
+  if (bytes <= e->hostInBytes) return ORBFE_OK;
+  // alloc frees the old slab first: until the new one exists nothing may still point at it (the last result's
+  // level-0 view lives in it: get_pyramid_level / compute_stereo_matches of the PREVIOUS call would read freed memory)
+  e->hostInBytes = 0;
+  e->haveLast = false;
+  int rc = e->d_hostIn.alloc(bytes);
+  if (!rc) e->hostInBytes = bytes;
+  return rc;
+}
+// the pinned staging block of the host-buffer calls: at least 512 KiB, the largest block that comes back in one copy
+int ensure_out_stage(orbfe_extractor* e, size_t bytes) {
+  if (bytes <= e->outStageBytes) return ORBFE_OK;
+  if (bytes < (size_t)512 * 1024) bytes = (size_t)512 * 1024;
+  e->outStageBytes = 0;
+  int rc = e->h_outStage.alloc(bytes);
+  if (!rc) e->outStageBytes = bytes;
+  return rc;
+}
+
+// bytes from the start of the output block to the end of the counts of nFrames frames
+size_t out_block_bytes(const orbfe_extractor* e, int nFrames) {
+  return (size_t)(reinterpret_cast<uint8_t*>(e->d_nOut) - e->d_outBlock) + sizeof(int32_t) * (size_t)nFrames;
+}
+
+// The host-buffer result path: the output block of nFrames frames -- and tailBytes at d_tail behind it -- in ONE copy
+// sequence into pinned memory, one synchronisation, then scattered by the CPU: the records of frame f to kps[f] /
+// desc[f], its count, clamped to the capacity, to n[f].  The handle then holds the block for
+// orbfe_frame_from_extractor.  *h_tail: the staged tail.  ORBFE_ERR_CAPACITY comes after everything is filled.
+int fetch_outputs(orbfe_extractor* e, int nFrames, int capacity, orbfe_keypoint* const* kps, uint8_t* const* desc, int* n,
+                  const void* d_tail = nullptr, size_t tailBytes = 0, const uint8_t** h_tail = nullptr) {
+  const size_t blockBytes = out_block_bytes(e, nFrames);
+  int rc = ensure_out_stage(e, blockBytes + tailBytes);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(e->h_outStage, e->d_outBlock, blockBytes, hipMemcpyDeviceToHost, e->stream));
+  if (tailBytes) HIPCHK(hipMemcpyAsync(e->h_outStage + blockBytes, d_tail, tailBytes, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  for (int i = 0; i < orbfe_extractor::kMaxStreams - 1; i++)
-    if (e->extra[i]) HIPCHK(hipStreamSynchronize(e->extra[i]));
-  return reader_settle(e);
+  const uint8_t* hk = e->h_outStage;
+  const uint8_t* hd = e->h_outStage + (e->d_descOut - e->d_outBlock);
+  const int32_t* hc = reinterpret_cast<const int32_t*>(e->h_outStage + (blockBytes - sizeof(int32_t) * (size_t)nFrames));
+  bool overflow = false;
+  for (int f = 0; f < nFrames; f++) {
+    n[f] = hc[f];
+    if (n[f] > capacity) { overflow = true; n[f] = capacity; }
+    if (n[f] > 0) {
+      std::memcpy(kps[f], hk + (size_t)f * capacity * sizeof(orbfe_keypoint), sizeof(orbfe_keypoint) * (size_t)n[f]);
+      std::memcpy(desc[f], hd + (size_t)f * capacity * 32, (size_t)n[f] * 32);
+    }
+  }
+  if (h_tail) *h_tail = e->h_outStage + blockBytes;
+  e->outLastCount.assign(n, n + nFrames);
+  e->outLastCapacity = capacity;
+  e->outLastFrames = nFrames;
+  return overflow ? fail(ORBFE_ERR_CAPACITY, "keypoint capacity too small") : ORBFE_OK;
 }
 
 }  // namespace
@@ -906,15 +941,12 @@ extern "C" int orbfe_extractor_create(int nfeatures, float scaleFactor, int nlev
   if (!e) return fail(ORBFE_ERR_NOMEM, "out of memory");
   e->device = device;
   e->tab.init(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST);
-  hipError_t err = stream_get(device, 0, &e->stream);
+  // defaults from the environment (the setters override them)
   if (const char* env = getenv("ORBFE_COPY_UNALIGNED")) e->copyUnaligned = atoi(env) != 0;
   if (const char* env = getenv("ORBFE_FAST_MODE")) {
     const std::string v(env);
     e->fastMode = v == "high" ? 1 : (v == "low" ? 2 : 0);
   }
-  if (err == hipSuccess) err = hipMalloc((void**)&e->d_fastStat, sizeof(unsigned int) * orbfe_extractor::kMaxStreams * orbfe_extractor::kStatSlots);
-  if (err == hipSuccess)
-    err = hipHostMalloc((void**)&e->h_fastStat, sizeof(unsigned int) * orbfe_extractor::kMaxStreams * orbfe_extractor::kStatSlots, hipHostMallocDefault);
   if (const char* env = getenv("ORBFE_LANES")) e->laneMode = atoi(env) != 0;
   if (const char* env = getenv("ORBFE_FUSED")) e->fused = atoi(env) != 0;
   if (const char* env = getenv("ORBFE_PYRBLUR")) e->pyrBlur = atoi(env) != 0;
@@ -927,32 +959,31 @@ extern "C" int orbfe_extractor_create(int nfeatures, float scaleFactor, int nlev
     int v = atoi(env);
     if (v >= 1 && v <= orbfe_extractor::kMaxStreams) e->nStreams = v;
   }
-  if (err == hipSuccess) err = hipEventCreateWithFlags(&e->evConsumerDone, hipEventDisableTiming);
-  if (err == hipSuccess && ensure_subs(e, e->nStreams > 3 ? e->nStreams : 3) != ORBFE_OK) err = hipErrorUnknown;  // 3: the lane schedule's P / V / T
-  float patF[1024];
+  float4 patF[256];
   // test i = (x0, y0, x1, y1) in the table; uploaded as (x0, x1, y0, y1) so that k_orient_desc rotates the
   // two points of a test in one packed-fp32 operation per product
-  for (int i = 0; i < 256; i++) {
-    patF[4 * i + 0] = (float)kOrbBitPattern31[4 * i + 0];
-    patF[4 * i + 1] = (float)kOrbBitPattern31[4 * i + 2];
-    patF[4 * i + 2] = (float)kOrbBitPattern31[4 * i + 1];
-    patF[4 * i + 3] = (float)kOrbBitPattern31[4 * i + 3];
-  }
-  uint8_t momTab[1024];
-  build_moment_table(momTab);
-  if (err == hipSuccess) err = hipMalloc((void**)&e->d_patternF, sizeof(patF));
-  if (err == hipSuccess) err = hipMemcpy(e->d_patternF, patF, sizeof(patF), hipMemcpyHostToDevice);
+  for (int i = 0; i < 256; i++)
+    patF[i] = make_float4((float)kOrbBitPattern31[4 * i + 0], (float)kOrbBitPattern31[4 * i + 2],
+                          (float)kOrbBitPattern31[4 * i + 1], (float)kOrbBitPattern31[4 * i + 3]);
+  uint4 momTab[64];
+  build_moment_table(reinterpret_cast<uint8_t*>(momTab));
   float scTab[2 * kMaxLevels] = {};
   for (int i = 0; i < e->tab.nlevels; i++) { scTab[i] = e->tab.scale[i]; scTab[kMaxLevels + i] = e->tab.invScale[i]; }
-  if (err == hipSuccess) err = hipMalloc((void**)&e->d_scaleTab, sizeof(scTab));
-  if (err == hipSuccess) err = hipMemcpy(e->d_scaleTab, scTab, sizeof(scTab), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMalloc((void**)&e->d_momentTab, sizeof(momTab));
-  if (err == hipSuccess) err = hipMemcpy(e->d_momentTab, momTab, sizeof(momTab), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMalloc((void**)&e->d_umax, 16 * sizeof(int32_t));
-  if (err == hipSuccess) err = hipMemcpy(e->d_umax, e->tab.umax, 16 * sizeof(int32_t), hipMemcpyHostToDevice);
-  if (err != hipSuccess) {
+  const size_t nStat = (size_t)orbfe_extractor::kMaxStreams * orbfe_extractor::kStatSlots;
+  auto init = [&]() -> int {
+    int rc;
+    HIPCHK(stream_get(device, 0, &e->stream));
+    if ((rc = e->d_fastStat.alloc(nStat)) || (rc = e->h_fastStat.alloc(nStat))) return rc;
+    HIPCHK(hipEventCreateWithFlags(&e->evConsumerDone, hipEventDisableTiming));
+    if ((rc = ensure_subs(e, e->nStreams > 3 ? e->nStreams : 3))) return rc;  // 3: the lane schedule's P / V / T
+    if ((rc = e->d_patternF.upload(patF, 256)) || (rc = e->d_scaleTab.upload(scTab, 2 * kMaxLevels))) return rc;
+    if ((rc = e->d_momentTab.upload(momTab, 64))) return rc;
+    return e->d_umax.upload(e->tab.umax, 16);
+  };
+  if (int rc = init()) {
+    const std::string why = orbfe_last_error();
     orbfe_extractor_destroy(e);
-    return fail(ORBFE_ERR_HIP, std::string("extractor_create: ") + hipGetErrorString(err));
+    return fail(rc, "extractor_create: " + why);
   }
   *out = e;
   return ORBFE_OK;
@@ -964,48 +995,21 @@ extern "C" void orbfe_extractor_destroy(orbfe_extractor* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   for (int i = 0; i < orbfe_extractor::kMaxStreams - 1; i++)
     if (e->extra[i]) stream_put(e->device, i + 1, e->extra[i]);
-  free_geometry(e);
-  free_workspace(e);
-  free_outputs(e);
-  if (e->h_outStage) (void)hipHostFree(e->h_outStage);
-  if (e->h_fastStat) (void)hipHostFree(e->h_fastStat);
-  dfree(&e->d_fastStat);
-  for (int i = 0; i < orbfe_extractor::kMaxStreams; i++)
-    if (e->evStat[i]) (void)hipEventDestroy(e->evStat[i]);
-  for (int i = 0; i < 2; i++) {
-    dfree(&e->d_pipeIn[i]);
-    dfree(&e->d_pipeOut[i]);
-    if (e->evIn[i]) (void)hipEventDestroy(e->evIn[i]);
-    if (e->evComp[i]) (void)hipEventDestroy(e->evComp[i]);
-    if (e->evOutDone[i]) (void)hipEventDestroy(e->evOutDone[i]);
-  }
   stream_put(e->device, kRoleH2D, e->sH2D);
   stream_put(e->device, kRoleD2H, e->sD2H);
-  dfree(&e->d_patternF);
-  dfree(&e->d_frameStereo);
-  dfree(&e->d_stereoSad);
-  dfree(&e->d_scaleTab);
-  dfree(&e->d_stereoRowStart);
-  dfree(&e->d_stereoSorted);
-  dfree(&e->d_stereoRec);
-  dfree(&e->d_momentTab);
-  dfree(&e->d_hostIn);
-  dfree(&e->d_umax);
+  free_geometry(e);
+  free_workspace(e);
+  free_outputs(e);  // (settles the reader first; every other buffer goes with the handle below)
+  auto drop = [](hipEvent_t ev) { if (ev) (void)hipEventDestroy(ev); };
+  for (int i = 0; i < orbfe_extractor::kMaxStreams; i++) {
+    drop(e->evStat[i]); drop(e->evChunkDone[i]); drop(e->evPyr[i]); drop(e->evFast[i]); drop(e->evBlur[i]); drop(e->evTail[i]);
+  }
+  for (int i = 0; i < 2; i++) { drop(e->evIn[i]); drop(e->evComp[i]); drop(e->evOutDone[i]); }
   for (int r = 0; r < orbfe_extractor::kEvRing; r++)
     for (int u = 0; u < orbfe_extractor::kEvSubs; u++)
-      for (int i = 0; i < ORBFE_STAGE_COUNT; i++) {
-        if (e->evA[r][u][i]) (void)hipEventDestroy(e->evA[r][u][i]);
-        if (e->evB[r][u][i]) (void)hipEventDestroy(e->evB[r][u][i]);
-      }
-  for (int i = 0; i < orbfe_extractor::kMaxStreams; i++) {
-    if (e->evChunkDone[i]) (void)hipEventDestroy(e->evChunkDone[i]);
-    if (e->evPyr[i]) (void)hipEventDestroy(e->evPyr[i]);
-    if (e->evFast[i]) (void)hipEventDestroy(e->evFast[i]);
-    if (e->evBlur[i]) (void)hipEventDestroy(e->evBlur[i]);
-    if (e->evTail[i]) (void)hipEventDestroy(e->evTail[i]);
-  }
-  if (e->evConsumerDone) (void)hipEventDestroy(e->evConsumerDone);
-  if (e->evReaderDone) (void)hipEventDestroy(e->evReaderDone);
+      for (int i = 0; i < ORBFE_STAGE_COUNT; i++) { drop(e->evA[r][u][i]); drop(e->evB[r][u][i]); }
+  drop(e->evConsumerDone);
+  drop(e->evReaderDone);
   stream_put(e->device, 0, e->stream);
   delete e;
 }
@@ -1065,16 +1069,8 @@ extern "C" int orbfe_extract_batch_device_async(orbfe_extractor* e, const uint8_
     return fail(ORBFE_ERR_INVALID, "extract_batch_device: bad image");
   if (frame_stride < (size_t)stride * (size_t)height)  // rows are staged up to the PITCH (16-byte requests): see orbfe.h
     return fail(ORBFE_ERR_INVALID, "extract_batch_device: frame_stride < stride * height (every frame must be readable for stride * height bytes)");
-  HIPCHK(hipSetDevice(e->device));
-  int rc;
-  if (e->geom.W != width || e->geom.H != height || n_frames > e->capFrames) {
-    int rcs = sync_all(e);  // the workspace is about to be re-allocated
-    if (rcs) return rcs;
-  }
-  e->outLastFrames = 0;  // "the frame this handle produced last" is no longer the one in its own output block
-  if ((rc = ensure_geometry(e, width, height))) return rc;
-  if ((rc = ensure_workspace(e, n_frames))) return rc;
-  next_event_slot(e);
+  int rc = begin_call(e, width, height, n_frames, false);  // (the outputs are the caller's)
+  if (rc) return rc;
   LevelView l0{d_images, frame_stride, stride, width, height};
   return run_pipeline(e, l0, n_frames, d_keypoints, d_descriptors, capacity, d_n_out);
 }
@@ -1120,16 +1116,8 @@ extern "C" int orbfe_extract_stereo_rectified_batch_device_async(
   if ((rc = orbfe_remap_launch_(rect_right, nullptr, 0, 0, 0, 0, 0, nullptr, 0, 0, nullptr, &wr, &hr, &dr))) return rc;
   if (wl != wr || hl != hr || dl != e->device || dr != e->device)
     return fail(ORBFE_ERR_INVALID, "extract_stereo_rectified: the two rectifiers differ in size or device from each other / the extractor");
-  HIPCHK(hipSetDevice(e->device));
   const int n_frames = 2 * n_pairs;
-  if (e->geom.W != wl || e->geom.H != hl || n_frames > e->capFrames) {
-    int rcs = sync_all(e);  // the workspace is about to be re-allocated
-    if (rcs) return rcs;
-  }
-  e->outLastFrames = 0;  // (as orbfe_extract_batch_device_async: the outputs are the caller's)
-  if ((rc = ensure_geometry(e, wl, hl))) return rc;
-  if ((rc = ensure_workspace(e, n_frames))) return rc;
-  next_event_slot(e);
+  if ((rc = begin_call(e, wl, hl, n_frames, false))) return rc;  // (as orbfe_extract_batch_device_async: the outputs are the caller's)
   RectifyCtx ctx{rect_left, rect_right, d_raw_left, d_raw_right, src_width, src_height, src_stride, src_frame_stride,
                  d_rectified, wl, hl};
   PreChunk pre;
@@ -1180,15 +1168,10 @@ extern "C" int orbfe_extract_batch(orbfe_extractor* e, const uint8_t* images, in
     // 5-9 ms for 128 VGA frames) and only pays for very large batches; pinned ones (orbfe_host_alloc) always pay.
     return orbfe_extract_batch_pipelined(e, images, n_frames, width, height, stride, frame_stride, keypoints, descriptors,
                                          capacity, n_out, 0);
-  HIPCHK(hipSetDevice(e->device));
   int rc;
-  if ((rc = sync_all(e))) return rc;  // an earlier asynchronous call may still use the workspace
-  e->outLastFrames = 0;
-  if ((rc = ensure_geometry(e, width, height))) return rc;
-  if ((rc = ensure_workspace(e, n_frames))) return rc;
+  if ((rc = begin_call(e, width, height, n_frames, true))) return rc;  // an earlier asynchronous call may still use the workspace
   if ((rc = ensure_outputs(e, n_frames, capacity))) return rc;
   const FrameGeom& g = e->geom;
-  next_event_slot(e);
   LevelView l0{e->d_pyr + g.lv[0].off, g.pyrBytes, g.lv[0].pitch, width, height};
   const bool tight = frame_stride == (size_t)stride * height || n_frames == 1;
   {
@@ -1200,15 +1183,7 @@ extern "C" int orbfe_extract_batch(orbfe_extractor* e, const uint8_t* images, in
       // against 0.1 ms this way -- the live-camera latency of a KITTI frame was that copy.
       const size_t bytes = (size_t)(n_frames - 1) * frame_stride + (size_t)(height - 1) * stride + width;
       // the slab is readable for stride * height bytes per frame: the kernels stage rows up to the pitch, not the width
-      const size_t slab = (size_t)(n_frames - 1) * frame_stride + (size_t)stride * height + 64;
-      if (slab > e->hostInBytes) {
-        // dalloc frees the old slab first: until the new one exists nothing may still point at it (the last result's
-        // level-0 view lives in it: get_pyramid_level / compute_stereo_matches of the PREVIOUS call would read freed memory)
-        e->hostInBytes = 0;
-        e->haveLast = false;
-        if ((rc = dalloc(&e->d_hostIn, slab))) return rc;
-        e->hostInBytes = slab;
-      }
+      if ((rc = ensure_host_in(e, (size_t)(n_frames - 1) * frame_stride + (size_t)stride * height + 64))) return rc;
       HIPCHK(hipMemcpyAsync(e->d_hostIn, images, bytes, hipMemcpyHostToDevice, e->stream));
       l0 = LevelView{e->d_hostIn, frame_stride, stride, width, height};
     } else {
@@ -1227,33 +1202,18 @@ extern "C" int orbfe_extract_batch(orbfe_extractor* e, const uint8_t* images, in
   if ((rc = sync_all(e))) return rc;
   {
     StageTimer t(e, ORBFE_STAGE_D2H, 0, 0, 0, e->stream);
-    bool overflow = false;
-    const size_t blockBytes = (size_t)(reinterpret_cast<uint8_t*>(e->d_nOut) - e->d_outBlock) + sizeof(int32_t) * (size_t)n_frames;
-    if (blockBytes <= (size_t)512 * 1024) {
+    if (out_block_bytes(e, n_frames) <= (size_t)512 * 1024) {
       // small batch (the live-camera case): everything in ONE copy into pinned memory, then scattered
       // by the CPU -- one DMA + one synchronisation instead of 1 + 2*n_frames copies and two syncs
-      if (e->outStageBytes < blockBytes) {
-        if (e->h_outStage) (void)hipHostFree(e->h_outStage);
-        e->h_outStage = nullptr;
-        e->outStageBytes = 0;
-        HIPCHK(hipHostMalloc((void**)&e->h_outStage, (size_t)512 * 1024, hipHostMallocDefault));
-        e->outStageBytes = (size_t)512 * 1024;
-      }
-      HIPCHK(hipMemcpyAsync(e->h_outStage, e->d_outBlock, blockBytes, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      const uint8_t* hk = e->h_outStage;
-      const uint8_t* hd = e->h_outStage + (e->d_descOut - e->d_outBlock);
-      const int32_t* hc = reinterpret_cast<const int32_t*>(e->h_outStage + (reinterpret_cast<uint8_t*>(e->d_nOut) - e->d_outBlock));
-      for (int f = 0; f < n_frames; f++) {
-        int n = hc[f];
-        if (n > capacity) { overflow = true; n = capacity; }
-        n_out[f] = n;
-        if (n > 0) {
-          std::memcpy(keypoints + (size_t)f * capacity, hk + (size_t)f * capacity * sizeof(orbfe_keypoint), sizeof(orbfe_keypoint) * (size_t)n);
-          std::memcpy(descriptors + (size_t)f * capacity * 32, hd + (size_t)f * capacity * 32, (size_t)n * 32);
-        }
+      std::vector<orbfe_keypoint*> kk(n_frames);
+      std::vector<uint8_t*> dd(n_frames);
+      for (int f = 0; f < n_frames; f++) { kk[f] = keypoints + (size_t)f * capacity; dd[f] = descriptors + (size_t)f * capacity * 32; }
+      if ((rc = fetch_outputs(e, n_frames, capacity, kk.data(), dd.data(), n_out))) {
+        e->outLastFrames = 0;  // (an overflowing batch leaves no block to build frames from)
+        return rc;
       }
     } else {
+      bool overflow = false;
       std::vector<int32_t> cnt(n_frames);
       HIPCHK(hipMemcpyAsync(cnt.data(), e->d_nOut, sizeof(int32_t) * n_frames, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
@@ -1269,12 +1229,12 @@ extern "C" int orbfe_extract_batch(orbfe_extractor* e, const uint8_t* images, in
         }
       }
       HIPCHK(hipStreamSynchronize(e->stream));
+      if (overflow) return fail(ORBFE_ERR_CAPACITY, "keypoint capacity too small");
+      e->outLastCount.assign(n_out, n_out + n_frames);
+      e->outLastCapacity = capacity;
+      e->outLastFrames = n_frames;
     }
-    if (overflow) return fail(ORBFE_ERR_CAPACITY, "keypoint capacity too small");
   }
-  e->outLastCount.assign(n_out, n_out + n_frames);
-  e->outLastCapacity = capacity;
-  e->outLastFrames = n_frames;
   resolve_stage_times(e);
   return ORBFE_OK;
 }
@@ -1340,14 +1300,10 @@ extern "C" int orbfe_extract_batch_pipelined(orbfe_extractor* e, const uint8_t* 
   if (!images || width <= 0 || height <= 0) return ORBFE_OK;  // empty image: silent return (:1122)
   if (!keypoints || !descriptors || capacity <= 0 || stride < width || frame_stride < (size_t)stride * (height - 1) + width)
     return fail(ORBFE_ERR_INVALID, "extract_batch_pipelined: bad buffers");
-  HIPCHK(hipSetDevice(e->device));
-  int rc;
-  if ((rc = sync_all(e))) return rc;
-  e->outLastFrames = 0;  // (as orbfe_extract_batch_device_async: the outputs are the caller's)
-  if ((rc = ensure_geometry(e, width, height))) return rc;
   int C = chunk_frames > 0 ? chunk_frames : 256;
   if (C > n_frames) C = n_frames;
-  if ((rc = ensure_workspace(e, C))) return rc;
+  int rc = begin_call(e, width, height, C, true);  // (as orbfe_extract_batch_device_async: the outputs are the caller's)
+  if (rc) return rc;
   if (!e->sH2D) {
     HIPCHK(stream_get(e->device, kRoleH2D, &e->sH2D));
     HIPCHK(stream_get(e->device, kRoleD2H, &e->sD2H));
@@ -1372,8 +1328,8 @@ extern "C" int orbfe_extract_batch_pipelined(orbfe_extractor* e, const uint8_t* 
     HIPCHK(hipStreamSynchronize(e->sH2D));
     HIPCHK(hipStreamSynchronize(e->sD2H));
     for (int i = 0; i < 2; i++) {
-      if ((rc = dalloc(&e->d_pipeIn[i], inBytes))) return rc;
-      if ((rc = dalloc(&e->d_pipeOut[i], outBytes))) return rc;
+      if ((rc = e->d_pipeIn[i].alloc(inBytes))) return rc;
+      if ((rc = e->d_pipeOut[i].alloc(outBytes))) return rc;
     }
     e->pipeInBytes = inBytes;
     e->pipeOutBytes = outBytes;
@@ -1404,10 +1360,10 @@ extern "C" int orbfe_extract_batch_pipelined(orbfe_extractor* e, const uint8_t* 
     H(hipEventRecord(e->evIn[slot], e->sH2D));
     // kernels: wait for the upload, and for the D2H of chunk k-2 before its output block is overwritten
     hipEvent_t waits[2] = {e->evIn[slot], e->evOutDone[slot]};
-    orbfe_keypoint* d_kp = reinterpret_cast<orbfe_keypoint*>(e->d_pipeOut[slot]);
+    orbfe_keypoint* d_kp = reinterpret_cast<orbfe_keypoint*>(e->d_pipeOut[slot].p);
     uint8_t* d_de = e->d_pipeOut[slot] + kpB;
     int32_t* d_n = reinterpret_cast<int32_t*>(e->d_pipeOut[slot] + kpB + deB);
-    next_event_slot(e);
+    if (k > 0) next_event_slot(e);  // (chunk 0 records into the call's own slot)
     LevelView l0{e->d_pipeIn[slot], (size_t)pitch * height, pitch, width, height};
     if (status == ORBFE_OK) {
       rc = run_pipeline(e, l0, n, d_kp, d_de, capacity, d_n, waits, k >= 2 ? 2 : 1);
@@ -1455,10 +1411,10 @@ extern "C" int orbfe_extract(orbfe_extractor* e, const uint8_t* image, int width
 static int retained_frame(orbfe_extractor* e, int frame, int* local) {
   if (!e->haveLast) return fail(ORBFE_ERR_INVALID, "no extract call yet");
   const int f = frame - e->lastFrameBase;
-  if (frame < 0 || f >= e->lastFrames) return fail(ORBFE_ERR_INVALID, "frame out of range");
+  if (frame < 0 || f >= e->last.frames) return fail(ORBFE_ERR_INVALID, "frame out of range");
   if (f < 0)
     return fail(ORBFE_ERR_INVALID, "pyramid of frame " + std::to_string(frame) + " not retained: the pipelined host path keeps the last chunk only (frames " +
-                                       std::to_string(e->lastFrameBase) + ".." + std::to_string(e->lastFrameBase + e->lastFrames - 1) + ")");
+                                       std::to_string(e->lastFrameBase) + ".." + std::to_string(e->lastFrameBase + e->last.frames - 1) + ")");
   *local = f;
   return ORBFE_OK;
 }
@@ -1552,28 +1508,16 @@ extern "C" int orbfe_resize_linear(int device, const uint8_t* src, int sw, int s
   ResizeTables t;
   build_resize_tables(sw, sh, dw, dh, &t);
   const int sp = (sw + 63) & ~63, dp = (dw + 63) & ~63;
-  uint8_t *d_src = nullptr, *d_dst = nullptr;
-  int32_t *d_xofs = nullptr, *d_yofs = nullptr;
-  int16_t *d_alpha = nullptr, *d_beta = nullptr;
-  uint32_t *d_colrec = nullptr, *d_rowrec = nullptr;
-  int rc = ORBFE_OK;
-  auto cleanup = [&]() {
-    dfree(&d_src); dfree(&d_dst); dfree(&d_xofs); dfree(&d_yofs); dfree(&d_alpha); dfree(&d_beta);
-    dfree(&d_colrec); dfree(&d_rowrec);
-  };
-  if ((rc = dalloc(&d_src, (size_t)sp * sh)) || (rc = dalloc(&d_dst, (size_t)dp * dh)) ||
-      (rc = dalloc(&d_xofs, t.xofs.size())) || (rc = dalloc(&d_yofs, t.yofs.size())) ||
-      (rc = dalloc(&d_alpha, t.alpha.size())) || (rc = dalloc(&d_beta, t.beta.size()))) { cleanup(); return rc; }
+  DevBuf<uint8_t> d_src, d_dst;
+  DevBuf<int32_t> d_xofs, d_yofs;
+  DevBuf<int16_t> d_alpha, d_beta;
+  DevBuf<uint32_t> d_colrec, d_rowrec;
+  int rc;
+  if ((rc = d_src.alloc((size_t)sp * sh)) || (rc = d_dst.alloc((size_t)dp * dh))) return rc;
+  if ((rc = d_xofs.upload(t.xofs)) || (rc = d_yofs.upload(t.yofs)) || (rc = d_alpha.upload(t.alpha)) || (rc = d_beta.upload(t.beta)))
+    return rc;
+  if (!t.colrec.empty() && ((rc = d_colrec.upload(t.colrec)) || (rc = d_rowrec.upload(t.rowrec)))) return rc;
   hipError_t err = hipMemcpy2D(d_src, sp, src, sstride, sw, sh, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(d_xofs, t.xofs.data(), t.xofs.size() * 4, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(d_yofs, t.yofs.data(), t.yofs.size() * 4, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(d_alpha, t.alpha.data(), t.alpha.size() * 2, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(d_beta, t.beta.data(), t.beta.size() * 2, hipMemcpyHostToDevice);
-  if (err == hipSuccess && !t.colrec.empty()) {
-    if ((rc = dalloc(&d_colrec, t.colrec.size())) || (rc = dalloc(&d_rowrec, t.rowrec.size()))) { cleanup(); return rc; }
-    err = hipMemcpy(d_colrec, t.colrec.data(), t.colrec.size() * 4, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d_rowrec, t.rowrec.data(), t.rowrec.size() * 4, hipMemcpyHostToDevice);
-  }
   if (err == hipSuccess) {
     launch_resize(nullptr, LevelView{d_src, 0, sp, sw, sh}, LevelViewMut{d_dst, 0, dp, dw, dh}, d_xofs, d_alpha, d_yofs, d_beta,
                   d_colrec, d_rowrec, 1);
@@ -1581,7 +1525,6 @@ extern "C" int orbfe_resize_linear(int device, const uint8_t* src, int sw, int s
   }
   if (err == hipSuccess) err = hipDeviceSynchronize();
   if (err == hipSuccess) err = hipMemcpy2D(dst, dstride, d_dst, dp, dw, dh, hipMemcpyDeviceToHost);
-  cleanup();
   if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("resize: ") + hipGetErrorString(err));
   return ORBFE_OK;
 }
@@ -1593,10 +1536,9 @@ extern "C" int orbfe_gaussian_blur7_spec(int device, int spec, const uint8_t* sr
   if (!src || !dst || w <= 0 || h <= 0 || sstride < w || dstride < w || spec < 0 || spec > 2) return fail(ORBFE_ERR_INVALID, "blur: bad argument");
   HIPCHK(hipSetDevice(device));
   const int p = (w + 63) & ~63;
-  uint8_t *d_src = nullptr, *d_dst = nullptr;
+  DevBuf<uint8_t> d_src, d_dst;
   int rc;
-  if ((rc = dalloc(&d_src, (size_t)p * h))) return rc;
-  if ((rc = dalloc(&d_dst, (size_t)p * h))) { dfree(&d_src); return rc; }
+  if ((rc = d_src.alloc((size_t)p * h)) || (rc = d_dst.alloc((size_t)p * h))) return rc;
   hipError_t err = hipMemcpy2D(d_src, p, src, sstride, w, h, hipMemcpyHostToDevice);
   if (err == hipSuccess) {
     launch_blur7(nullptr, LevelView{d_src, 0, p, w, h}, LevelViewMut{d_dst, 0, p, w, h}, 1, spec);
@@ -1604,8 +1546,6 @@ extern "C" int orbfe_gaussian_blur7_spec(int device, int spec, const uint8_t* sr
   }
   if (err == hipSuccess) err = hipDeviceSynchronize();
   if (err == hipSuccess) err = hipMemcpy2D(dst, dstride, d_dst, p, w, h, hipMemcpyDeviceToHost);
-  dfree(&d_src);
-  dfree(&d_dst);
   if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("blur: ") + hipGetErrorString(err));
   return ORBFE_OK;
 }
@@ -1636,22 +1576,11 @@ extern "C" int orbfe_extractor_consumer_begin_(orbfe_extractor* e, hipStream_t* 
   HIPCHK(hipSetDevice(e->device));
   for (int i = 1; i < e->chunksPending; i++) HIPCHK(hipStreamWaitEvent(e->stream, e->evChunkDone[i], 0));
   *s = e->stream;
-  if ((e->stageMask >> ORBFE_STAGE_MATCH) & 1u) {  // same ring slot as the extract call it follows, sub-batch 0
-    if (e->evUsed[e->evSlot][0][ORBFE_STAGE_MATCH]) {  // a second matcher behind the same call: one interval for both
-      e->evLaunches[e->evSlot][0][ORBFE_STAGE_MATCH]++;
-    } else {
-      HIPCHK(hipEventRecord(e->evA[e->evSlot][0][ORBFE_STAGE_MATCH], e->stream));
-      e->evLaunches[e->evSlot][0][ORBFE_STAGE_MATCH] = 1;
-      e->evFrames[e->evSlot][0][ORBFE_STAGE_MATCH] = e->lastFrames;
-    }
-  }
+  e->stage_open(ORBFE_STAGE_MATCH, 0, e->stream, 1, e->last.frames);  // same ring slot as the extract call it follows, sub-batch 0
   return ORBFE_OK;
 }
 extern "C" int orbfe_extractor_consumer_end_(orbfe_extractor* e) {
-  if ((e->stageMask >> ORBFE_STAGE_MATCH) & 1u) {
-    HIPCHK(hipEventRecord(e->evB[e->evSlot][0][ORBFE_STAGE_MATCH], e->stream));
-    e->evUsed[e->evSlot][0][ORBFE_STAGE_MATCH] = true;
-  }
+  e->stage_close(ORBFE_STAGE_MATCH, 0, e->stream);
   HIPCHK(hipEventRecord(e->evConsumerDone, e->stream));
   e->consumerPending = true;
   return ORBFE_OK;
@@ -1673,14 +1602,11 @@ extern "C" int orbfe_extractor_reader_end_(orbfe_extractor* e, hipStream_t s) {
 
 // internal (vocabulary.hip): how the last extract call was split, so that a batched matcher can work per sub-batch on
 // the sub-batch's own stream.  streams / chunkDone: kMaxStreams entries.
-extern "C" int orbfe_extractor_split_(orbfe_extractor* e, int* S, int* per, int* frames, int* lanes, hipStream_t* streams,
-                                      hipEvent_t* chunkDone) {
+extern "C" int orbfe_extractor_split_(orbfe_extractor* e, SubSplit* split, hipStream_t* streams, hipEvent_t* chunkDone) {
   if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
   HIPCHK(hipSetDevice(e->device));
-  *S = e->haveLast ? e->lastS : 0;
-  *per = e->lastPer;
-  *frames = e->lastFrames;
-  *lanes = e->lastLanes ? 1 : 0;
+  *split = e->last;
+  if (!e->haveLast) split->S = 0;
   for (int i = 0; i < orbfe_extractor::kMaxStreams; i++) {
     streams[i] = i == 0 ? e->stream : e->extra[i - 1];
     chunkDone[i] = e->evChunkDone[i];
@@ -1689,18 +1615,9 @@ extern "C" int orbfe_extractor_split_(orbfe_extractor* e, int* S, int* per, int*
 }
 // internal: stage-timer marks for work another translation unit enqueues on a sub-batch stream
 extern "C" void orbfe_extractor_stage_mark_(orbfe_extractor* e, int stage, int sub, int isEnd, hipStream_t s, int frames) {
-  if (!e || sub < 0 || sub >= orbfe_extractor::kEvSubs || !((e->stageMask >> stage) & 1u)) return;
-  if (!isEnd) {
-    // a second matcher behind the same sub-batch on the same stream (stereo, then BoW): one interval from the first
-    // one's start to the last one's end
-    if (e->evUsed[e->evSlot][sub][stage]) { e->evLaunches[e->evSlot][sub][stage]++; return; }
-    (void)hipEventRecord(e->evA[e->evSlot][sub][stage], s);
-    e->evLaunches[e->evSlot][sub][stage] = 1;
-    e->evFrames[e->evSlot][sub][stage] = frames;
-  } else {
-    (void)hipEventRecord(e->evB[e->evSlot][sub][stage], s);
-    e->evUsed[e->evSlot][sub][stage] = true;
-  }
+  if (!e) return;
+  if (isEnd) e->stage_close(stage, sub, s);
+  else e->stage_open(stage, sub, s, 1, frames);
 }
 
 // Debug: route DistributeOctTree through the host implementation (cross-check of k_octree).
@@ -1710,58 +1627,40 @@ extern "C" int orbfe_extractor_debug_host_octree(orbfe_extractor* e, int enable)
   return ORBFE_OK;
 }
 
+// A setter of one field of an idle handle: `ok` checks the value, `assign` stores it once every stream is drained.
+#define SETTER(name, arg, ok, why, assign)                                   \
+  extern "C" int name(orbfe_extractor* e, int arg) {                         \
+    if (!e || !(ok)) return fail(ORBFE_ERR_INVALID, e ? why : "NULL handle"); \
+    HIPCHK(hipSetDevice(e->device));                                         \
+    int rc = sync_all(e);                                                    \
+    if (rc) return rc;                                                       \
+    assign;                                                                  \
+    return ORBFE_OK;                                                         \
+  }
 // FAST threshold order: 0 = auto, 1 = iniThFAST first with per-cell fallback, 2 = one attempt at the lower threshold.
-extern "C" int orbfe_extractor_set_fast_mode(orbfe_extractor* e, int mode) {
-  if (!e || mode < 0 || mode > 2) return fail(ORBFE_ERR_INVALID, "set_fast_mode: 0 (auto), 1 (high first) or 2 (low first)");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = sync_all(e);
-  if (rc) return rc;
+SETTER(orbfe_extractor_set_fast_mode, mode, mode >= 0 && mode <= 2, "set_fast_mode: 0 (auto), 1 (high first) or 2 (low first)", {
   e->fastMode = mode;
   for (int i = 0; i < orbfe_extractor::kMaxStreams; i++) e->statPending[i] = false;
-  return ORBFE_OK;
-}
-
+})
 // Which OpenCV's GaussianBlur arithmetic the extractor reproduces (include/orbfe.h, ORBFE_BLUR_*).
-extern "C" int orbfe_extractor_set_blur_spec(orbfe_extractor* e, int spec) {
-  if (!e || spec < 0 || spec > 2) return fail(ORBFE_ERR_INVALID, "set_blur_spec: 0 (OpenCV >= 3.4.1/4.x), 1 (2.4/3.x scalar) or 2 (2.4/3.x SSE2)");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = sync_all(e);
-  if (rc) return rc;
-  e->blurSpec = spec;
-  return ORBFE_OK;
-}
-
-// GaussianBlur inside the FAST kernel (default) or as the separate k_blur7 launch (A/B and cross-check).
-extern "C" int orbfe_extractor_set_fused(orbfe_extractor* e, int enable) {
-  if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = sync_all(e);
-  if (rc) return rc;
-  e->fused = enable != 0;
-  return ORBFE_OK;
-}
-
+SETTER(orbfe_extractor_set_blur_spec, spec, spec >= 0 && spec <= 2,
+       "set_blur_spec: 0 (OpenCV >= 3.4.1/4.x), 1 (2.4/3.x scalar) or 2 (2.4/3.x SSE2)", e->blurSpec = spec)
+// GaussianBlur inside the FAST kernel (1; $ORBFE_FUSED) or as the separate k_blur7 launch (0, the default).  Identical results.
+SETTER(orbfe_extractor_set_fused, enable, true, "", e->fused = enable != 0)
 // ComputePyramid and the per-level GaussianBlur as ONE kernel per level (1, the default; $ORBFE_PYRBLUR) or as the
 // separate resize and blur launches (0).  Identical results.
-extern "C" int orbfe_extractor_set_pyramid_blur(orbfe_extractor* e, int enable) {
-  if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = sync_all(e);
-  if (rc) return rc;
-  e->pyrBlur = enable != 0;
-  return ORBFE_OK;
-}
-
+SETTER(orbfe_extractor_set_pyramid_blur, enable, true, "", e->pyrBlur = enable != 0)
 // The pyramid of a call of <= 8 frames in ONE launch (k_pyramid_chain) instead of n-1 dependent resize launches.  Identical
 // results; off by default (measured: no faster).
-extern "C" int orbfe_extractor_set_pyramid_chain(orbfe_extractor* e, int enable) {
-  if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = sync_all(e);
-  if (rc) return rc;
-  e->pyrChain = enable != 0;
-  return ORBFE_OK;
-}
+SETTER(orbfe_extractor_set_pyramid_chain, enable, true, "", e->pyrChain = enable != 0)
+// Schedule of the sub-batches of a call: 0 = one independent stream per sub-batch, 1 = three lanes shared by all
+// sub-batches (pyramid | FAST + blur | gather + octree + orientation/descriptors) as a software pipeline.
+SETTER(orbfe_extractor_set_schedule, lanes, true, "", e->laneMode = lanes != 0)
+// Number of sub-batch streams one call is split over (1..32; default 1, or $ORBFE_STREAMS).
+SETTER(orbfe_extractor_set_streams, n, n >= 1 && n <= orbfe_extractor::kMaxStreams, "set_streams: 1..32", {
+  if ((rc = ensure_subs(e, n))) return rc;
+  e->nStreams = n;
+})
 
 // Order of the blur kernel's two passes (process-wide, k_blur.hip); the blurred bytes are the same either way.
 extern "C" int orbfe_set_blur_pass_order(int order) {
@@ -1769,31 +1668,11 @@ extern "C" int orbfe_set_blur_pass_order(int order) {
   return blur_pass_order();
 }
 
-// Schedule of the sub-batches of a call: 0 = one independent stream per sub-batch, 1 = three lanes shared by all
-// sub-batches (pyramid | FAST + blur | gather + octree + orientation/descriptors) as a software pipeline.
+// Orientation + descriptor stage in tile form (1), per-keypoint form (0) or as $ORBFE_DESC_TILES says (< 0, the default);
+// read per call, so no drain.
 extern "C" int orbfe_extractor_set_desc_tiles(orbfe_extractor* e, int enable) {
   if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
   e->descTilesMode = enable < 0 ? -1 : (enable ? 1 : 0);
-  return ORBFE_OK;
-}
-
-extern "C" int orbfe_extractor_set_schedule(orbfe_extractor* e, int lanes) {
-  if (!e) return fail(ORBFE_ERR_INVALID, "NULL handle");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = sync_all(e);
-  if (rc) return rc;
-  e->laneMode = lanes != 0;
-  return ORBFE_OK;
-}
-
-// Number of sub-batch streams one call is split over (1..32; default 1, or $ORBFE_STREAMS).
-extern "C" int orbfe_extractor_set_streams(orbfe_extractor* e, int n) {
-  if (!e || n < 1 || n > orbfe_extractor::kMaxStreams) return fail(ORBFE_ERR_INVALID, "set_streams: 1..32");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = sync_all(e);
-  if (rc) return rc;
-  if ((rc = ensure_subs(e, n))) return rc;
-  e->nStreams = n;
   return ORBFE_OK;
 }
 
@@ -1806,7 +1685,7 @@ extern "C" int orbfe_stereo_match_batch_device(orbfe_extractor* e, int n_pairs, 
       !d_n_stereo)
     return fail(ORBFE_ERR_INVALID, "stereo_match_batch_device: bad argument");
   if (n_pairs == 0) return ORBFE_OK;
-  if (!e->haveLast || e->lastFrames < 2 * n_pairs)
+  if (!e->haveLast || e->last.frames < 2 * n_pairs)
     return fail(ORBFE_ERR_INVALID, "stereo_match_batch_device: the last extract call holds fewer than 2*n_pairs frames");
   if (capacity >= (1 << 20)) return fail(ORBFE_ERR_INVALID, "stereo_match_batch_device: capacity too large");
   HIPCHK(hipSetDevice(e->device));
@@ -1816,11 +1695,10 @@ extern "C" int orbfe_stereo_match_batch_device(orbfe_extractor* e, int n_pairs, 
   if (need > e->stereoSadCap || needRows > e->stereoRowCap) {
     int rcs = sync_all(e);
     if (rcs) return rcs;
-    int rc = dalloc(&e->d_stereoSad, need);
-    if (!rc) rc = dalloc(&e->d_stereoSorted, need);
-    if (!rc) rc = dalloc(&e->d_stereoRec, need);
-    if (!rc) rc = dalloc(&e->d_stereoRowStart, needRows);
-    if (rc) return rc;
+    int rc;
+    if ((rc = e->d_stereoSad.alloc(need)) || (rc = e->d_stereoSorted.alloc(need)) || (rc = e->d_stereoRec.alloc(need)) ||
+        (rc = e->d_stereoRowStart.alloc(needRows)))
+      return rc;
     e->stereoSadCap = need;
     e->stereoRowCap = needRows;
   }
@@ -1845,7 +1723,8 @@ extern "C" int orbfe_stereo_match_batch_device(orbfe_extractor* e, int n_pairs, 
   b.uRight = d_uRight;
   b.depth = d_depth;
   b.sad = e->d_stereoSad;
-  // pairs [p0, p0+np) on stream st: every operand moved to the first pair by pointer arithmetic
+  // pairs [p0, p0+np) on stream st: every operand moved to the first pair by pointer arithmetic; timed as sub-batch
+  // `sub` (< 0: the caller times it)
   auto launch_range = [&](hipStream_t st, int p0, int np, int sub) {
     StereoArgs aa = a;
     StereoBatch bb = b;
@@ -1864,15 +1743,13 @@ extern "C" int orbfe_stereo_match_batch_device(orbfe_extractor* e, int n_pairs, 
     StageTimer t(e, ORBFE_STAGE_MATCH, 1, 2 * np, sub, st);
     launch_stereo_batch(st, aa, bb, np, d_n_stereo + p0);
   };
-  const int S = e->lastS, per = e->lastPer;
-  if (!e->lastLanes && S > 1 && (per & 1) == 0 && 2 * n_pairs == e->lastFrames) {
+  const SubSplit& sp = e->last;
+  if (!sp.lanes && sp.S > 1 && (sp.per & 1) == 0 && 2 * n_pairs == sp.frames) {
     // The pairs of a sub-batch are matched on that sub-batch's own stream, right behind its extraction: no join of
     // the sub-batch streams, and the (latency-bound) matcher of one sub-batch overlaps the kernels of the others.
     // The next extract call's sub-batch i is enqueued on the same stream, i.e. behind this matcher, by itself.
-    for (int i = 0; i < S; i++) {
-      const int f0 = i * per;
-      const int n = f0 + per <= e->lastFrames ? per : e->lastFrames - f0;
-      if (n <= 0) break;
+    int f0, n;
+    for (int i = 0; sp.range(i, &f0, &n); i++) {
       launch_range(i == 0 ? e->stream : e->extra[i - 1], f0 / 2, n / 2, i);
       if (i > 0) HIPCHK(hipEventRecord(e->evChunkDone[i], e->extra[i - 1]));  // "sub-batch i done" now includes its matcher
     }
@@ -1881,12 +1758,7 @@ extern "C" int orbfe_stereo_match_batch_device(orbfe_extractor* e, int n_pairs, 
   }
   // one launch on stream 0 behind all sub-batches (joined ON THE DEVICE, no host synchronisation)
   { hipStream_t s0; int rc = orbfe_extractor_consumer_begin_(e, &s0); if (rc) return rc; }
-  {
-    const unsigned keep = e->stageMask;
-    e->stageMask &= ~(1u << ORBFE_STAGE_MATCH);  // consumer_begin_/end_ time this form
-    launch_range(e->stream, 0, n_pairs, 0);
-    e->stageMask = keep;
-  }
+  launch_range(e->stream, 0, n_pairs, -1);  // (consumer_begin_/end_ time this form)
   HIPCHK(hipGetLastError());
   // the next extract call's sub-batch streams overwrite the pyramid slabs and the caller's keypoint /
   // descriptor / count buffers this matcher is still reading: they wait for this event (run_pipeline)
@@ -1908,28 +1780,18 @@ extern "C" int orbfe_extract_stereo_frame(orbfe_extractor* e, const uint8_t* lef
   if (!left || !right || width <= 0 || height <= 0) return ORBFE_OK;  // empty image: silent return (:1122)
   if (!kpL || !descL || !kpR || !descR || !uRight || !depth || capacity <= 0 || stride < width || capacity >= (1 << 20))
     return fail(ORBFE_ERR_INVALID, "extract_stereo_frame: bad output buffers");
-  HIPCHK(hipSetDevice(e->device));
   int rc;
-  e->outLastFrames = 0;
-  if ((rc = ensure_geometry(e, width, height))) return rc;
-  if ((rc = ensure_workspace(e, 2))) return rc;
+  if ((rc = begin_call(e, width, height, 2, false))) return rc;
   if ((rc = ensure_outputs(e, 2, capacity))) return rc;
   if (e->frameStereoCap < (size_t)capacity) {
     if ((rc = sync_all(e))) return rc;
     e->frameStereoCap = 0;
-    if ((rc = dalloc(&e->d_frameStereo, 2 * (size_t)capacity + 16))) return rc;
+    if ((rc = e->d_frameStereo.alloc(2 * (size_t)capacity + 16))) return rc;
     e->frameStereoCap = (size_t)capacity;
   }
-  next_event_slot(e);
   // both images into the input slab at the caller's pitch (the kernels read rows in place at any stride)
   const size_t frameStride = ((size_t)stride * height + 255) & ~(size_t)255;
-  const size_t slab = 2 * frameStride + 64;
-  if (slab > e->hostInBytes) {
-    e->hostInBytes = 0;
-    e->haveLast = false;
-    if ((rc = dalloc(&e->d_hostIn, slab))) return rc;
-    e->hostInBytes = slab;
-  }
+  if ((rc = ensure_host_in(e, 2 * frameStride + 64))) return rc;
   const size_t bytes = (size_t)(height - 1) * stride + width;
   {
     StageTimer t(e, ORBFE_STAGE_H2D, 0, 0, 0, e->stream);
@@ -1944,48 +1806,22 @@ extern "C" int orbfe_extract_stereo_frame(orbfe_extractor* e, const uint8_t* lef
   int32_t* d_ns = reinterpret_cast<int32_t*>(e->d_frameStereo + 2 * (size_t)capacity);
   if ((rc = orbfe_stereo_match_batch_device(e, 1, e->d_kpOut, e->d_descOut, e->d_nOut, capacity, mbf, mb, d_ur, d_dp, d_ns)))
     return rc;
-  if (e->lastS > 1 || e->lastLanes) { if ((rc = sync_all(e))) return rc; }  // (a pair is one sub-batch: everything is on e->stream)
+  if (e->last.S > 1 || e->last.lanes) { if ((rc = sync_all(e))) return rc; }  // (a pair is one sub-batch: everything is on e->stream)
   {
     StageTimer t(e, ORBFE_STAGE_D2H, 0, 0, 0, e->stream);
-    const size_t blockBytes = (size_t)(reinterpret_cast<uint8_t*>(e->d_nOut) - e->d_outBlock) + sizeof(int32_t) * 2;
-    const size_t stBytes = 2 * (size_t)capacity * sizeof(float);
-    const size_t need = blockBytes + stBytes;
-    if (e->outStageBytes < need) {
-      if (e->h_outStage) (void)hipHostFree(e->h_outStage);
-      e->h_outStage = nullptr;
-      e->outStageBytes = 0;
-      const size_t want = need > (size_t)512 * 1024 ? need : (size_t)512 * 1024;
-      HIPCHK(hipHostMalloc((void**)&e->h_outStage, want, hipHostMallocDefault));
-      e->outStageBytes = want;
-    }
-    HIPCHK(hipMemcpyAsync(e->h_outStage, e->d_outBlock, blockBytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(e->h_outStage + blockBytes, e->d_frameStereo, stBytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const uint8_t* hk = e->h_outStage;
-    const uint8_t* hd = e->h_outStage + (e->d_descOut - e->d_outBlock);
-    const int32_t* hc = reinterpret_cast<const int32_t*>(e->h_outStage + (reinterpret_cast<uint8_t*>(e->d_nOut) - e->d_outBlock));
-    bool overflow = false;
-    int n[2];
     orbfe_keypoint* kk[2] = {kpL, kpR};
     uint8_t* dd[2] = {descL, descR};
-    for (int f = 0; f < 2; f++) {
-      n[f] = hc[f];
-      if (n[f] > capacity) { overflow = true; n[f] = capacity; }
-      if (n[f] > 0) {
-        std::memcpy(kk[f], hk + (size_t)f * capacity * sizeof(orbfe_keypoint), sizeof(orbfe_keypoint) * (size_t)n[f]);
-        std::memcpy(dd[f], hd + (size_t)f * capacity * 32, (size_t)n[f] * 32);
-      }
-    }
+    int n[2] = {0, 0};
+    const uint8_t* h_st = nullptr;  // uRight | depth of the left keypoints, `capacity` floats each
+    rc = fetch_outputs(e, 2, capacity, kk, dd, n, e->d_frameStereo, 2 * (size_t)capacity * sizeof(float), &h_st);
+    if (rc && rc != ORBFE_ERR_CAPACITY) return rc;
     *nL = n[0];
     *nR = n[1];
     if (n[0] > 0) {
-      std::memcpy(uRight, e->h_outStage + blockBytes, sizeof(float) * (size_t)n[0]);
-      std::memcpy(depth, e->h_outStage + blockBytes + (size_t)capacity * sizeof(float), sizeof(float) * (size_t)n[0]);
+      std::memcpy(uRight, h_st, sizeof(float) * (size_t)n[0]);
+      std::memcpy(depth, h_st + (size_t)capacity * sizeof(float), sizeof(float) * (size_t)n[0]);
     }
-    e->outLastCount.assign(n, n + 2);
-    e->outLastCapacity = capacity;
-    e->outLastFrames = 2;
-    if (overflow) return fail(ORBFE_ERR_CAPACITY, "keypoint capacity too small");
+    if (rc) return rc;
   }
   resolve_stage_times(e);
   return ORBFE_OK;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/orbfe.h"
 #include "kernels.h"
@@ -15,15 +16,70 @@ namespace orbfe {
 int fail(int code, const std::string& msg);
 }  // namespace orbfe
 
+// in a function that returns an ORBFE_* status
+#define HIPCHK(expr)                                                                          \
+  do {                                                                                        \
+    hipError_t _e = (expr);                                                                   \
+    if (_e != hipSuccess)                                                                     \
+      return orbfe::fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
+  } while (0)
+
+namespace orbfe {
+// How a call of `frames` frames is cut into S sub-batches of `per` consecutive frames (the last one may be shorter,
+// and trailing ones empty): sub-batch i on its own stream, or -- lanes -- all of them on three shared lane streams.
+struct SubSplit {
+  int frames = 0, S = 0, per = 0;
+  bool lanes = false;
+  // frames [*f0, *f0 + *n) of sub-batch i; false behind the last sub-batch that has frames
+  bool range(int i, int* f0, int* n) const {
+    *f0 = i * per;
+    *n = frames - *f0 < per ? frames - *f0 : per;
+    return i < S && *n > 0;
+  }
+  bool operator==(const SubSplit& o) const { return frames == o.frames && S == o.S && per == o.per && lanes == o.lanes; }
+};
+
+// An owned array of T in device memory (kPinned: in page-locked host memory); converts to T* for launch sites.
+template <typename T, bool kPinned = false>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+  }
+  // frees what it holds first; at least one element
+  int alloc(size_t n) {
+    reset();
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    if (kPinned) HIPCHK(hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
+    else HIPCHK(hipMalloc((void**)&p, bytes));
+    return ORBFE_OK;
+  }
+  int upload(const T* src, size_t n) {
+    int rc = alloc(n);
+    if (rc) return rc;
+    if (n) HIPCHK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return ORBFE_OK;
+  }
+  int upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
+  operator T*() const { return p; }
+};
+template <typename T>
+using PinBuf = DevBuf<T, true>;
+}  // namespace orbfe
+
 extern "C" {
 // ---- extractor.hip (struct orbfe_extractor lives there) ----
 // a consumer of the last extract call's outputs on the handle's own stream: begin orders stream 0 behind every sub-batch
 // and returns it, end marks the consumer's last kernel for the next extract call to wait for
 int orbfe_extractor_consumer_begin_(orbfe_extractor* e, hipStream_t* s);
 int orbfe_extractor_consumer_end_(orbfe_extractor* e);
-// how the last extract call was split; streams / chunkDone: orbfe_extractor::kMaxStreams (32) entries
-int orbfe_extractor_split_(orbfe_extractor* e, int* S, int* per, int* frames, int* lanes, hipStream_t* streams,
-                           hipEvent_t* chunkDone);
+// how the last extract call was split (S = 0: no call yet); streams / chunkDone: orbfe_extractor::kMaxStreams (32) entries
+int orbfe_extractor_split_(orbfe_extractor* e, orbfe::SubSplit* split, hipStream_t* streams, hipEvent_t* chunkDone);
 // stage-timer marks for work another translation unit enqueues on a sub-batch stream
 void orbfe_extractor_stage_mark_(orbfe_extractor* e, int stage, int sub, int isEnd, hipStream_t s, int frames);
 // device pointers of frame `frame` of the handle's own output block (the host-buffer calls)

@@ -12,11 +12,6 @@
 #include "orb_spec.h"
 
 using orbfe::fail;
-#define IHIP(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) return fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 namespace {
 
@@ -88,10 +83,10 @@ extern "C" int orbfe_cvt_gray(int device, const uint8_t* src, int width, int hei
   if (!src || !dst || width <= 0 || height <= 0 || (channels != 3 && channels != 4) || stride < width * channels ||
       dst_stride < width)
     return fail(ORBFE_ERR_INVALID, "cvt_gray: bad argument");
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   uint8_t *ds = nullptr, *dd = nullptr;
   const size_t sb = (size_t)width * channels * height, db = (size_t)width * height;
-  IHIP(hipMalloc((void**)&ds, sb));
+  HIPCHK(hipMalloc((void**)&ds, sb));
   hipError_t err = hipMalloc((void**)&dd, db);
   if (err == hipSuccess) err = hipMemcpy2D(ds, (size_t)width * channels, src, stride, (size_t)width * channels, height, hipMemcpyHostToDevice);
   if (err == hipSuccess) {
@@ -114,11 +109,11 @@ extern "C" int orbfe_cvt_gray_batch_device(int device, const uint8_t* d_src, int
       stride < width * channels || dst_stride < width)
     return fail(ORBFE_ERR_INVALID, "cvt_gray_batch_device: bad argument");
   if (n_frames == 0) return ORBFE_OK;
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   hipLaunchKernelGGL(k_cvt_gray, dim3((width + 1023) / 1024, height, n_frames), dim3(256), 0, 0, d_src, width, height,
                      stride, frame_stride, channels, rgb_order, d_dst, dst_stride, dst_frame_stride);
-  IHIP(hipGetLastError());
-  IHIP(hipDeviceSynchronize());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
   return ORBFE_OK;
 }
 
@@ -132,9 +127,9 @@ extern "C" int orbfe_distinctive_descriptors(int device, const uint8_t* descript
       return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: bad offsets (or more than 65535 observations)");
   if (offsets[0] != 0) return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: offsets[0] != 0");
   const size_t total = (size_t)offsets[n_points];
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   uint8_t* dd = nullptr; int32_t *doff = nullptr, *dbest = nullptr;
-  IHIP(hipMalloc((void**)&dd, total * 32 + 32));
+  HIPCHK(hipMalloc((void**)&dd, total * 32 + 32));
   hipError_t err = hipMalloc((void**)&doff, ((size_t)n_points + 1) * 4);
   if (err == hipSuccess) err = hipMalloc((void**)&dbest, (size_t)n_points * 4);
   if (err == hipSuccess && total) err = hipMemcpy(dd, descriptors, total * 32, hipMemcpyHostToDevice);
@@ -241,7 +236,7 @@ int remap_launch(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw,
   const int tilesX = (r->width + 255) / 256, tilesY = (r->height + 3) / 4;
   hipLaunchKernelGGL(k_remap, dim3((unsigned)tilesX * tilesY * n_frames), dim3(256), 0, stream, r->xy, r->phase, r->pitch,
                      r->width, r->height, tilesX, n_frames, d_src, sw, sh, sstride, sFrame, d_dst, dstride, dFrame);
-  IHIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ORBFE_OK;
 }
 
@@ -263,7 +258,7 @@ extern "C" int orbfe_rectifier_create(int device, const float* map_x, const floa
                                   int map_stride, orbfe_rectifier** out) {
   if (!map_x || !map_y || !out || width <= 0 || height <= 0 || map_stride < width || width > 32767 || height > 32767)
     return fail(ORBFE_ERR_INVALID, "remap_create: bad argument");
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   orbfe_rectifier* r = new orbfe_rectifier();
   r->device = device; r->width = width; r->height = height; r->pitch = (width + 3) & ~3;
   float *dmx = nullptr, *dmy = nullptr;
@@ -304,9 +299,9 @@ extern "C" int orbfe_remap(orbfe_rectifier* r, const uint8_t* src, int src_width
                            uint8_t* dst, int dst_stride) {
   if (!r || !src || !dst || src_width <= 0 || src_height <= 0 || src_stride < src_width || dst_stride < r->width)
     return fail(ORBFE_ERR_INVALID, "remap: bad argument");
-  IHIP(hipSetDevice(r->device));
+  HIPCHK(hipSetDevice(r->device));
   uint8_t *ds = nullptr, *dd = nullptr;
-  IHIP(hipMalloc((void**)&ds, (size_t)src_width * src_height));
+  HIPCHK(hipMalloc((void**)&ds, (size_t)src_width * src_height));
   hipError_t err = hipMalloc((void**)&dd, (size_t)r->pitch * r->height);
   if (err == hipSuccess) err = hipMemcpy2D(ds, src_width, src, src_stride, src_width, src_height, hipMemcpyHostToDevice);
   int rc = ORBFE_OK;
@@ -326,11 +321,11 @@ extern "C" int orbfe_remap_batch_device(orbfe_rectifier* r, const uint8_t* d_src
       dst_stride < r->width)
     return fail(ORBFE_ERR_INVALID, "remap_batch_device: bad argument");
   if (n_frames == 0) return ORBFE_OK;
-  IHIP(hipSetDevice(r->device));
+  HIPCHK(hipSetDevice(r->device));
   const int rc = remap_launch(r, d_src, n_frames, src_width, src_height, src_stride, src_frame_stride, d_dst, dst_stride,
                               dst_frame_stride, 0);
   if (rc != ORBFE_OK) return rc;
-  IHIP(hipDeviceSynchronize());
+  HIPCHK(hipDeviceSynchronize());
   return ORBFE_OK;
 }
 
@@ -472,10 +467,10 @@ extern "C" int orbfe_init_undistort_rectify_map(int device, const double* K, con
   p.k1 = n_dist > 0 ? D[0] : 0; p.k2 = n_dist > 1 ? D[1] : 0; p.p1 = n_dist > 2 ? D[2] : 0; p.p2 = n_dist > 3 ? D[3] : 0;
   p.k3 = n_dist >= 5 ? D[4] : 0; p.k4 = n_dist >= 8 ? D[5] : 0; p.k5 = n_dist >= 8 ? D[6] : 0; p.k6 = n_dist >= 8 ? D[7] : 0;
   p.w = width; p.h = height;
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   float* dmap = nullptr;
   const size_t n = (size_t)width * height;
-  IHIP(hipMalloc((void**)&dmap, 2 * n * 4));
+  HIPCHK(hipMalloc((void**)&dmap, 2 * n * 4));
   hipLaunchKernelGGL(k_init_rectify_map, dim3((height + 63) / 64), dim3(64), 0, 0, p, dmap, dmap + n);
   hipError_t err = hipGetLastError();
   if (err == hipSuccess) err = hipMemcpy(map_x, dmap, n * 4, hipMemcpyDeviceToHost);
@@ -491,9 +486,9 @@ extern "C" int orbfe_undistort_points(int device, const float* xy, int n, const 
   if (n < 0 || (n > 0 && (!xy || !out_xy)) || !undistort_params(K4, dist, n_dist, &p))
     return fail(ORBFE_ERR_INVALID, "undistort_points: bad argument");
   if (n == 0) return ORBFE_OK;
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   float *din = nullptr, *dout = nullptr;
-  IHIP(hipMalloc((void**)&din, (size_t)n * 8));
+  HIPCHK(hipMalloc((void**)&din, (size_t)n * 8));
   hipError_t err = hipMalloc((void**)&dout, (size_t)n * 8);
   if (err == hipSuccess) err = hipMemcpy(din, xy, (size_t)n * 8, hipMemcpyHostToDevice);
   if (err == hipSuccess) {
@@ -515,11 +510,11 @@ extern "C" int orbfe_undistort_keypoints_batch_device(int device, const orbfe_ke
   if (!d_keypoints || !d_n || !d_keypoints_un || n_frames < 0 || capacity <= 0 || !undistort_params(K4, dist, n_dist, &p))
     return fail(ORBFE_ERR_INVALID, "undistort_keypoints_batch_device: bad argument");
   if (n_frames == 0) return ORBFE_OK;
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   hipLaunchKernelGGL(k_undistort_keypoints, dim3((capacity + 255) / 256, n_frames), dim3(256), 0, 0, p,
                      reinterpret_cast<const float*>(d_keypoints), d_n, capacity, reinterpret_cast<float*>(d_keypoints_un));
-  IHIP(hipGetLastError());
-  IHIP(hipDeviceSynchronize());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
   return ORBFE_OK;
 }
 
@@ -551,10 +546,10 @@ extern "C" int orbfe_stereo_from_rgbd(int device, const float* kx, const float* 
     if (!(kx[i] >= 0 && ky[i] >= 0 && (int)kx[i] < width && (int)ky[i] < height))
       return fail(ORBFE_ERR_INVALID, "stereo_from_rgbd: keypoint outside the depth image");
   if (n == 0) return ORBFE_OK;
-  IHIP(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   float* buf = nullptr;
   const size_t img = (size_t)width * height;
-  IHIP(hipMalloc((void**)&buf, (img + 5 * (size_t)n) * 4));
+  HIPCHK(hipMalloc((void**)&buf, (img + 5 * (size_t)n) * 4));
   float *dimg = buf, *dkx = buf + img, *dky = dkx + n, *dkux = dky + n, *dur = dkux + n, *ddp = dur + n;
   hipError_t err = hipMemcpy2D(dimg, (size_t)width * 4, depth_image, (size_t)stride_floats * 4, (size_t)width * 4, height, hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(dkx, kx, (size_t)n * 4, hipMemcpyHostToDevice);

@@ -230,11 +230,6 @@ bool featvec_ok(const orbfe_featvec* f, int n) {
 
 }  // namespace
 
-#define MHIP(expr)                                                                       \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) return fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 // (in a function that returns hipError_t)
 #define TRY(expr)                      \
   do {                                 \
@@ -246,16 +241,16 @@ extern "C" int orbfe_descriptor_distance(int device, const uint8_t* a, const uin
   if (n < 0 || (n > 0 && (!a || !b || !out))) return fail(ORBFE_ERR_INVALID, "descriptor_distance: bad argument");
   if (n == 0) return ORBFE_OK;
   Arena* ar;
-  MHIP(arena_begin(device, 2 * pad((size_t)n * 32) + pad((size_t)n * 4), &ar));
+  HIPCHK(arena_begin(device, 2 * pad((size_t)n * 32) + pad((size_t)n * 4), &ar));
   uint8_t *da, *db;
-  MHIP(up(ar, &da, a, (size_t)n * 32));
-  MHIP(up(ar, &db, b, (size_t)n * 32));
+  HIPCHK(up(ar, &da, a, (size_t)n * 32));
+  HIPCHK(up(ar, &db, b, (size_t)n * 32));
   int32_t* dout = carve<int32_t>(ar, n);
-  MHIP(flush(ar));
+  HIPCHK(flush(ar));
   launch_hamming_pairs(ar->stream, da, db, n, dout);
-  MHIP(hipGetLastError());
-  MHIP(hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, ar->stream));
-  MHIP(hipStreamSynchronize(ar->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, ar->stream));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   return ORBFE_OK;
 }
 
@@ -264,16 +259,16 @@ extern "C" int orbfe_hamming_matrix(int device, const uint8_t* d1, int n1, const
     return fail(ORBFE_ERR_INVALID, "hamming_matrix: bad argument");
   if (n1 == 0 || n2 == 0) return ORBFE_OK;
   Arena* ar;
-  MHIP(arena_begin(device, pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + pad((size_t)n1 * n2 * 4), &ar));
+  HIPCHK(arena_begin(device, pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + pad((size_t)n1 * n2 * 4), &ar));
   uint8_t *da, *db;
-  MHIP(up(ar, &da, d1, (size_t)n1 * 32));
-  MHIP(up(ar, &db, d2, (size_t)n2 * 32));
+  HIPCHK(up(ar, &da, d1, (size_t)n1 * 32));
+  HIPCHK(up(ar, &db, d2, (size_t)n2 * 32));
   int32_t* dout = carve<int32_t>(ar, (size_t)n1 * n2);
-  MHIP(flush(ar));
+  HIPCHK(flush(ar));
   launch_hamming_matrix(ar->stream, da, n1, db, n2, dout);
-  MHIP(hipGetLastError());
-  MHIP(hipMemcpyAsync(out, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost, ar->stream));
-  MHIP(hipStreamSynchronize(ar->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost, ar->stream));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   return ORBFE_OK;
 }
 
@@ -750,10 +745,10 @@ int bow_run(const char* who, int device, FvSide* one, const uint8_t* maskOne, in
     }
     return hipSuccess;
   };
-  MHIP(arena_stage(device, &ar, stage));
-  MHIP(frame_use(ar, one->frame));
-  for (int k = 0; k < K; k++) MHIP(frame_use(ar, many[k].frame));
-  MHIP(flush(ar));
+  HIPCHK(arena_stage(device, &ar, stage));
+  HIPCHK(frame_use(ar, one->frame));
+  for (int k = 0; k < K; k++) HIPCHK(frame_use(ar, many[k].frame));
+  HIPCHK(flush(ar));
   if (batch) {
     launch_search_by_bow_multi(ar->stream, dargs, dstart, (int)hargs.size(), total, maxCnt2);
     launch_rot_prune_batch(ar->stream, dmatch, dbin, nOut, K, check_ori, dcount);  // all K histograms in one launch
@@ -761,9 +756,9 @@ int bow_run(const char* who, int device, FvSide* one, const uint8_t* maskOne, in
     launch_search_by_bow(ar->stream, hargs[0], total, maxCnt2);
     launch_rot_prune(ar->stream, dmatch, dbin, nOut, check_ori, dcount);
   }
-  MHIP(hipGetLastError());
-  MHIP(down_range(ar, dmatch, dcount + K));
-  MHIP(hipStreamSynchronize(ar->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, dmatch, dcount + K));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   frames_settle();
   std::memcpy(match, mirror_of(ar, dmatch), (size_t)K * nOut * 4);
   std::memcpy(n_matches, mirror_of(ar, dcount), (size_t)K * 4);
@@ -846,17 +841,17 @@ int tri_run(const char* who, int device, FvSide* s1, const uint8_t* has_mp1, int
     }
     return hipSuccess;
   };
-  MHIP(arena_stage(device, &ar, stage));
-  MHIP(frame_use(ar, s1->frame));
-  for (int k = 0; k < K; k++) MHIP(frame_use(ar, many[k].frame));
-  MHIP(flush(ar));
+  HIPCHK(arena_stage(device, &ar, stage));
+  HIPCHK(frame_use(ar, s1->frame));
+  for (int k = 0; k < K; k++) HIPCHK(frame_use(ar, many[k].frame));
+  HIPCHK(flush(ar));
   if (targs.size() == 1) launch_search_triangulation(ar->stream, targs[0]);
   else if (!targs.empty()) launch_search_triangulation_multi(ar->stream, dargs, dstart, (int)targs.size(), totalBlocks);
   if (batch) launch_rot_prune_batch(ar->stream, dmatch, dbin, n1, K, check_ori, dcount);  // all K histograms in one launch
   else launch_rot_prune(ar->stream, dmatch, dbin, n1, check_ori, dcount);
-  MHIP(hipGetLastError());
-  MHIP(down_range(ar, dmatch, dcount + K));
-  MHIP(hipStreamSynchronize(ar->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, dmatch, dcount + K));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   frames_settle();
   std::memcpy(match12, mirror_of(ar, dmatch), (size_t)K * n1 * 4);
   std::memcpy(n_matches, mirror_of(ar, dcount), (size_t)K * 4);
@@ -1053,14 +1048,14 @@ extern "C" int orbfe_compute_stereo_matches(orbfe_extractor* left, int frameL, o
   }
   Arena* ar;
   const int rows = a.pyrL.lv[0].h;
-  MHIP(arena_begin(devL, pad((size_t)N * 60) + pad((size_t)Nr * 60) + 3 * pad((size_t)N * 4) + pad((size_t)Nr * 4) +
-                             pad((size_t)(rows + 1) * 4) + 4096, &ar));
+  HIPCHK(arena_begin(devL, pad((size_t)N * 60) + pad((size_t)Nr * 60) + 3 * pad((size_t)N * 4) + pad((size_t)Nr * 4) +
+                           pad((size_t)(rows + 1) * 4) + 4096, &ar));
   float *dkl, *dkr;
   uint8_t *ddl, *ddr;
-  MHIP(up(ar, &dkl, reinterpret_cast<const float*>(kpL), (size_t)N * 7));
-  MHIP(up(ar, &dkr, reinterpret_cast<const float*>(kpR), (size_t)Nr * 7));
-  MHIP(up(ar, &ddl, descL, (size_t)N * 32));
-  MHIP(up(ar, &ddr, descR, (size_t)Nr * 32));
+  HIPCHK(up(ar, &dkl, reinterpret_cast<const float*>(kpL), (size_t)N * 7));
+  HIPCHK(up(ar, &dkr, reinterpret_cast<const float*>(kpR), (size_t)Nr * 7));
+  HIPCHK(up(ar, &ddl, descL, (size_t)N * 32));
+  HIPCHK(up(ar, &ddr, descR, (size_t)Nr * 32));
   a.kpL = dkl; a.descL = ddl; a.N = N; a.kpR = dkr; a.descR = ddr; a.Nr = Nr;
   a.frameL = frameL; a.frameR = frameR;
   a.mbf = mbf;
@@ -1075,11 +1070,11 @@ extern "C" int orbfe_compute_stereo_matches(orbfe_extractor* left, int frameL, o
     a.rows = rows;
     a.bandR = (int)std::ceil(2.0f * scL[nlL - 1]) + 2;
   }
-  MHIP(flush(ar));
+  HIPCHK(flush(ar));
   launch_stereo(ar->stream, a, dcount);
-  MHIP(hipGetLastError());
-  MHIP(down_range(ar, a.uRight, dcount + 1));
-  MHIP(hipStreamSynchronize(ar->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, a.uRight, dcount + 1));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   std::memcpy(uRight, mirror_of(ar, a.uRight), (size_t)N * 4);
   std::memcpy(depth, mirror_of(ar, a.depth), (size_t)N * 4);
   return *mirror_of(ar, dcount);
@@ -1226,10 +1221,10 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
       }
       if (!lay[j].res && lay[j].frameOf == j) gridBytes += pad(n * 4) + pad(3073 * 4);
     }
-    MHIP(arena_begin(device, pad(inBytes) + gridBytes + outBytes + scrBytes + 2048, &ar));
+    HIPCHK(arena_begin(device, pad(inBytes) + gridBytes + outBytes + scrBytes + 2048, &ar));
     for (int j = 0; j < nJobs; j++)
-      if (lay[j].res) MHIP(frame_use(ar, jobs[j].f->resident));
-    MHIP(staging_reserve(inBytes > outBytes ? inBytes : outBytes));
+      if (lay[j].res) HIPCHK(frame_use(ar, jobs[j].f->resident));
+    HIPCHK(staging_reserve(inBytes > outBytes ? inBytes : outBytes));
     uint8_t* h = t_staging.h;
     for (int j = 0; j < nJobs; j++) {
       const WindowJob& J = jobs[j];
@@ -1359,25 +1354,25 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
       totalBlocks += (J.nq + 3) / 4;
     }
     if (nJobs > 1) std::memcpy(h + oWs, wsj.data(), (size_t)nJobs * sizeof(WindowSearchJob));
-    MHIP(hipMemcpyAsync(din, h, inBytes, hipMemcpyHostToDevice, ar->stream));
+    HIPCHK(hipMemcpyAsync(din, h, inBytes, hipMemcpyHostToDevice, ar->stream));
     for (int j = 0; j < nJobs; j++)
       if (buildsGrid[j]) {
         launch_grid_build(ar->stream, wsj[j].f, const_cast<uint32_t*>(wsj[j].sortedKey), const_cast<int32_t*>(wsj[j].cellOff));
-        MHIP(hipGetLastError());
+        HIPCHK(hipGetLastError());
       }
     if (nJobs > 1) {  // ONE launch for the window searches of all jobs
       launch_window_search_multi(ar->stream, reinterpret_cast<const WindowSearchJob*>(din + oWs), nJobs, totalBlocks);
     } else {
       launch_window_search(ar->stream, wsj[0].f, wsj[0].sortedKey, wsj[0].cellOff, wsj[0].q, wsj[0].count, wsj[0].cand);
     }
-    MHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     if (nClaim) {
       launch_window_claim(ar->stream, reinterpret_cast<const ClaimJob*>(din + oClaim), reinterpret_cast<const ClaimJob*>(h + oClaim), nClaim,
                           claimLds, claimInit);
-      MHIP(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    if (outBytes) MHIP(hipMemcpyAsync(h, dout, outBytes, hipMemcpyDeviceToHost, ar->stream));
-    MHIP(hipStreamSynchronize(ar->stream));
+    if (outBytes) HIPCHK(hipMemcpyAsync(h, dout, outBytes, hipMemcpyDeviceToHost, ar->stream));
+    HIPCHK(hipStreamSynchronize(ar->stream));
     frames_settle();
     int mx = 0;
     for (int j = 0; j < nJobs; j++) {

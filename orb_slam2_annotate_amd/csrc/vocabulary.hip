@@ -34,12 +34,6 @@
 
 using namespace orbfe;
 
-#define VHIP(expr)                                                                                   \
-  do {                                                                                               \
-    hipError_t _e = (expr);                                                                          \
-    if (_e != hipSuccess) return fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 struct orbfe_vocabulary {
   int device = 0;
   int k = 0, L = 0, scoring = 0, weighting = 0;
@@ -315,16 +309,16 @@ static int vocab_upload(orbfe_vocabulary* v, const int32_t* parent, const uint8_
     r.word = wordId[id];
     wpos[q] = weight[id];
   }
-  VHIP(hipSetDevice(v->device));
-  VHIP(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+  HIPCHK(hipSetDevice(v->device));
+  HIPCHK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
   VocabNode* dn; double* dwt;
-  VHIP(hipMalloc((void**)&dn, (size_t)n * sizeof(VocabNode)));
+  HIPCHK(hipMalloc((void**)&dn, (size_t)n * sizeof(VocabNode)));
   v->d.nodes = dn;
-  VHIP(hipMalloc((void**)&dwt, (size_t)n * 8));
+  HIPCHK(hipMalloc((void**)&dwt, (size_t)n * 8));
   v->d.weight = dwt;
   v->d.rootChildren = (uint32_t)(off[1] - off[0]);
-  VHIP(hipMemcpy(dn, rec.data(), (size_t)n * sizeof(VocabNode), hipMemcpyHostToDevice));
-  VHIP(hipMemcpy(dwt, wpos.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dn, rec.data(), (size_t)n * sizeof(VocabNode), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dwt, wpos.data(), (size_t)n * 8, hipMemcpyHostToDevice));
   return ORBFE_OK;
 }
 
@@ -450,27 +444,27 @@ extern "C" int orbfe_vocabulary_transform(orbfe_vocabulary* v, const uint8_t* de
   if (!v || n < 0 || (n > 0 && (!descriptors || !word_id || !weight || !node_id)))
     return fail(ORBFE_ERR_INVALID, "vocabulary_transform: bad argument");
   if (n == 0) return 0;
-  VHIP(hipSetDevice(v->device));
+  HIPCHK(hipSetDevice(v->device));
   if (n > v->scratchCap) {
-    VHIP(hipStreamSynchronize(v->stream));
+    HIPCHK(hipStreamSynchronize(v->stream));
     if (v->d_desc) { (void)hipFree(v->d_desc); (void)hipFree(v->d_word); (void)hipFree(v->d_node); (void)hipFree(v->d_weight); }
     v->d_desc = nullptr; v->d_word = nullptr; v->d_node = nullptr; v->d_weight = nullptr;
     v->scratchCap = 0;
     const int cap = n + n / 2 + 256;
-    VHIP(hipMalloc((void**)&v->d_desc, (size_t)cap * 32));
-    VHIP(hipMalloc((void**)&v->d_word, (size_t)cap * 4));
-    VHIP(hipMalloc((void**)&v->d_node, (size_t)cap * 4));
-    VHIP(hipMalloc((void**)&v->d_weight, (size_t)cap * 8));
+    HIPCHK(hipMalloc((void**)&v->d_desc, (size_t)cap * 32));
+    HIPCHK(hipMalloc((void**)&v->d_word, (size_t)cap * 4));
+    HIPCHK(hipMalloc((void**)&v->d_node, (size_t)cap * 4));
+    HIPCHK(hipMalloc((void**)&v->d_weight, (size_t)cap * 8));
     v->scratchCap = cap;
   }
-  VHIP(hipMemcpyAsync(v->d_desc, descriptors, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
+  HIPCHK(hipMemcpyAsync(v->d_desc, descriptors, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
   launch_vocab_transform(v->stream, v->d, v->d_desc, nullptr, n, n, 1, 1, v->L - levelsup, v->d_word, v->d_weight, v->d_node,
                          nullptr);
-  VHIP(hipGetLastError());
-  VHIP(hipMemcpyAsync(word_id, v->d_word, (size_t)n * 4, hipMemcpyDeviceToHost, v->stream));
-  VHIP(hipMemcpyAsync(weight, v->d_weight, (size_t)n * 8, hipMemcpyDeviceToHost, v->stream));
-  VHIP(hipMemcpyAsync(node_id, v->d_node, (size_t)n * 4, hipMemcpyDeviceToHost, v->stream));
-  VHIP(hipStreamSynchronize(v->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(word_id, v->d_word, (size_t)n * 4, hipMemcpyDeviceToHost, v->stream));
+  HIPCHK(hipMemcpyAsync(weight, v->d_weight, (size_t)n * 8, hipMemcpyDeviceToHost, v->stream));
+  HIPCHK(hipMemcpyAsync(node_id, v->d_node, (size_t)n * 4, hipMemcpyDeviceToHost, v->stream));
+  HIPCHK(hipStreamSynchronize(v->stream));
   int used = 0;
   for (int i = 0; i < n; i++) used += weight[i] > 0;
   return used;
@@ -478,17 +472,17 @@ extern "C" int orbfe_vocabulary_transform(orbfe_vocabulary* v, const uint8_t* de
 
 static int ensure_bow_workspace(orbfe_vocabulary* v, int nFrames, int capacity) {
   if ((size_t)nFrames <= v->wFrames && capacity <= v->wCap) return ORBFE_OK;
-  VHIP(hipStreamSynchronize(v->stream));
+  HIPCHK(hipStreamSynchronize(v->stream));
   if (v->w_nodes) { (void)hipFree(v->w_nodes); (void)hipFree(v->w_offsets); (void)hipFree(v->w_indices); (void)hipFree(v->w_count); (void)hipFree(v->w_bin); (void)hipFree(v->w_keys); }
   v->w_nodes = nullptr; v->w_offsets = nullptr; v->w_indices = nullptr; v->w_count = nullptr; v->w_bin = nullptr; v->w_keys = nullptr;
   v->wFrames = 0; v->wCap = 0;
   const size_t F = (size_t)nFrames, c = (size_t)capacity;
-  VHIP(hipMalloc((void**)&v->w_nodes, F * c * 4));
-  VHIP(hipMalloc((void**)&v->w_offsets, F * (c + 1) * 4));
-  VHIP(hipMalloc((void**)&v->w_indices, F * c * 4));
-  VHIP(hipMalloc((void**)&v->w_count, F * 4));
-  VHIP(hipMalloc((void**)&v->w_bin, F * c));
-  VHIP(hipMalloc((void**)&v->w_keys, F * c * 8));
+  HIPCHK(hipMalloc((void**)&v->w_nodes, F * c * 4));
+  HIPCHK(hipMalloc((void**)&v->w_offsets, F * (c + 1) * 4));
+  HIPCHK(hipMalloc((void**)&v->w_indices, F * c * 4));
+  HIPCHK(hipMalloc((void**)&v->w_count, F * 4));
+  HIPCHK(hipMalloc((void**)&v->w_bin, F * c));
+  HIPCHK(hipMalloc((void**)&v->w_keys, F * c * 8));
   v->wFrames = F;
   v->wCap = capacity;
   return ORBFE_OK;
@@ -508,30 +502,30 @@ extern "C" int orbfe_vocabulary_featvec_batch_device(orbfe_vocabulary* v, const 
   if (n_frames == 0) return ORBFE_OK;
   const int sortN = next_pow2(capacity);
   if ((size_t)sortN * 8 > 96 * 1024) return fail(ORBFE_ERR_INVALID, "vocabulary_featvec_batch_device: capacity > 8192");
-  VHIP(hipSetDevice(v->device));
+  HIPCHK(hipSetDevice(v->device));
   FeatVecBatch b = {};
   b.desc = d_descriptors; b.n = d_n; b.capacity = capacity; b.sortN = sortN;
   b.word = d_word; b.weight = d_weight;
   b.fvNodes = d_fv_nodes; b.fvOffsets = d_fv_offsets; b.fvIndices = d_fv_indices; b.fvCount = d_fv_count;
   const size_t need = (size_t)n_frames * capacity;
   if (need > v->fkCap) {
-    VHIP(hipStreamSynchronize(v->stream));
+    HIPCHK(hipStreamSynchronize(v->stream));
     if (v->fk_keys) (void)hipFree(v->fk_keys);
     v->fk_keys = nullptr; v->fkCap = 0;
-    VHIP(hipMalloc((void**)&v->fk_keys, need * 8));
+    HIPCHK(hipMalloc((void**)&v->fk_keys, need * 8));
     v->fkCap = need;
   }
   b.keys = v->fk_keys;
   if ((size_t)sortN * 8 > 64 * 1024) {
     static thread_local bool configured = false;
     if (!configured) {
-      VHIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_vocab_featvec), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_vocab_featvec), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
       configured = true;
     }
   }
   launch_vocab_featvec(v->stream, v->d, b, n_frames, v->L - levelsup);
-  VHIP(hipGetLastError());
-  VHIP(hipStreamSynchronize(v->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(v->stream));
   return ORBFE_OK;
 }
 
@@ -551,11 +545,11 @@ static int bow_match_consecutive(orbfe_vocabulary* v, orbfe_extractor* e, int n_
   if (n_frames < 2) return ORBFE_OK;
   const int sortN = next_pow2(capacity);
   if ((size_t)sortN * 8 > 64 * 1024) return fail(ORBFE_ERR_INVALID, "bow_match_consecutive_batch_device: capacity > 8192");
-  VHIP(hipSetDevice(v->device));
+  HIPCHK(hipSetDevice(v->device));
   int rc;
   if ((size_t)n_frames > v->wFrames || capacity > v->wCap || (v->lastMulti && v->lastMulti != e)) {
     // the workspace may still be in use on the streams of the previous call
-    if (v->lastStream) VHIP(hipStreamSynchronize(v->lastStream));
+    if (v->lastStream) HIPCHK(hipStreamSynchronize(v->lastStream));
     if (v->lastMulti && (rc = orbfe_extractor_synchronize(v->lastMulti))) return rc;
     v->lastMulti = nullptr;
   }
@@ -582,8 +576,8 @@ static int bow_match_consecutive(orbfe_vocabulary* v, orbfe_extractor* e, int n_
   };
   auto search_range = [&](hipStream_t st, int p0, int np) -> int {
     if (np <= 0) return ORBFE_OK;
-    VHIP(hipMemsetAsync(d_match + (size_t)p0 * c, 0xff, (size_t)np * c * 4, st));
-    VHIP(hipMemsetAsync(v->w_bin + (size_t)p0 * c, 0, (size_t)np * c, st));
+    HIPCHK(hipMemsetAsync(d_match + (size_t)p0 * c, 0xff, (size_t)np * c * 4, st));
+    HIPCHK(hipMemsetAsync(v->w_bin + (size_t)p0 * c, 0, (size_t)np * c, st));
     BowBatch r = bb;
     r.kp += (size_t)p0 * step * c * 7; r.desc += (size_t)p0 * step * c * 32;
     r.fvNodes += (size_t)p0 * c; r.fvOffsets += (size_t)p0 * (c + 1); r.fvIndices += (size_t)p0 * c; r.fvCount += p0;
@@ -592,47 +586,45 @@ static int bow_match_consecutive(orbfe_vocabulary* v, orbfe_extractor* e, int n_
     return ORBFE_OK;
   };
   if (e) {
-    int S = 0, per = 0, frames = 0, lanes = 0;
+    SubSplit ex;
     hipStream_t streams[32];  // orbfe_extractor::kMaxStreams
     hipEvent_t chunkDone[32];
-    if ((rc = orbfe_extractor_split_(e, &S, &per, &frames, &lanes, streams, chunkDone))) return rc;
-    if (!lanes && S > 1 && frames == n_frames * step && per % step == 0 && per / step >= 2) {
-      per /= step;  // frames of THIS call per sub-batch
+    if ((rc = orbfe_extractor_split_(e, &ex, streams, chunkDone))) return rc;
+    if (!ex.lanes && ex.S > 1 && ex.frames == n_frames * step && ex.per % step == 0 && ex.per / step >= 2) {
+      SubSplit sp = ex;  // in frames of THIS call
+      sp.frames = n_frames;
+      sp.per = ex.per / step;
       // Per sub-batch, on the sub-batch's own stream right behind its extraction (no join of the streams): the
       // FeatureVectors of its frames, then its consecutive pairs.  The pair that straddles two sub-batches
       // (last frame of i-1, first frame of i) runs on stream i behind an event of stream i-1's FeatureVectors, and
       // stream i-1 is made to wait for it before anything enqueued later (the next extract call) overwrites that frame.
-      if (v->lastStream) { VHIP(hipStreamSynchronize(v->lastStream)); v->lastStream = nullptr; }
+      if (v->lastStream) { HIPCHK(hipStreamSynchronize(v->lastStream)); v->lastStream = nullptr; }
       v->lastMulti = e;
       for (int i = 0; i < 32; i++)
         if (!v->evFv[i]) {
-          VHIP(hipEventCreateWithFlags(&v->evFv[i], hipEventDisableTiming));
-          VHIP(hipEventCreateWithFlags(&v->evBoundary[i], hipEventDisableTiming));
+          HIPCHK(hipEventCreateWithFlags(&v->evFv[i], hipEventDisableTiming));
+          HIPCHK(hipEventCreateWithFlags(&v->evBoundary[i], hipEventDisableTiming));
         }
-      int nSub = 0;
-      for (int i = 0; i < S; i++) {
-        const int f0 = i * per, n = f0 + per <= n_frames ? per : n_frames - f0;
-        if (n <= 0) break;
-        nSub = i + 1;
+      int f0, n;
+      for (int i = 0; sp.range(i, &f0, &n); i++) {
         orbfe_extractor_stage_mark_(e, ORBFE_STAGE_MATCH, i, 0, streams[i], n);
         featvec_range(streams[i], f0, n);
-        VHIP(hipEventRecord(v->evFv[i], streams[i]));
+        HIPCHK(hipEventRecord(v->evFv[i], streams[i]));
       }
-      for (int i = 0; i < nSub; i++) {
-        const int f0 = i * per, n = f0 + per <= n_frames ? per : n_frames - f0;
+      for (int i = 0; sp.range(i, &f0, &n); i++) {
         if (i > 0) {
           // the straddling pair first, on its own: the earlier stream is released as soon as this one launch is done
           // instead of after the whole sub-batch's pairs
-          VHIP(hipStreamWaitEvent(streams[i], v->evFv[i - 1], 0));
+          HIPCHK(hipStreamWaitEvent(streams[i], v->evFv[i - 1], 0));
           if ((rc = search_range(streams[i], f0 - 1, 1))) return rc;
-          VHIP(hipEventRecord(v->evBoundary[i], streams[i]));
-          VHIP(hipStreamWaitEvent(streams[i - 1], v->evBoundary[i], 0));
+          HIPCHK(hipEventRecord(v->evBoundary[i], streams[i]));
+          HIPCHK(hipStreamWaitEvent(streams[i - 1], v->evBoundary[i], 0));
         }
         if ((rc = search_range(streams[i], f0, n - 1))) return rc;
         orbfe_extractor_stage_mark_(e, ORBFE_STAGE_MATCH, i, 1, streams[i], n);
-        if (i > 0) VHIP(hipEventRecord(chunkDone[i], streams[i]));  // "sub-batch i done" now includes its matcher
+        if (i > 0) HIPCHK(hipEventRecord(chunkDone[i], streams[i]));  // "sub-batch i done" now includes its matcher
       }
-      VHIP(hipGetLastError());
+      HIPCHK(hipGetLastError());
       return ORBFE_OK;
     }
   }
@@ -643,16 +635,16 @@ static int bow_match_consecutive(orbfe_vocabulary* v, orbfe_extractor* e, int n_
   hipStream_t s = v->stream;
   if (e) {
     if ((rc = orbfe_extractor_consumer_begin_(e, &s))) return rc;
-    if (v->lastStream && v->lastStream != s) VHIP(hipStreamSynchronize(v->lastStream));
+    if (v->lastStream && v->lastStream != s) HIPCHK(hipStreamSynchronize(v->lastStream));
   } else if (v->lastStream && v->lastStream != s) {
-    VHIP(hipStreamSynchronize(v->lastStream));
+    HIPCHK(hipStreamSynchronize(v->lastStream));
   }
   v->lastStream = s;
   featvec_range(s, 0, n_frames);
   if ((rc = search_range(s, 0, n_frames - 1))) return rc;
-  VHIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (e) return orbfe_extractor_consumer_end_(e);
-  VHIP(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   return ORBFE_OK;
 }
 

@@ -707,3 +707,64 @@ def test_pyramid_in_one_launch_matches_the_level_by_level_form(amd, shape, cfg):
     assert np.array_equal(k2, kr) and np.array_equal(d2, dr)
     kf, df, _ = o.extract(np.ascontiguousarray(img[::-1]), want_pyramid=True)
     assert np.array_equal(k3, kf) and np.array_equal(d3, df)
+
+
+def test_stage_profile_counts_launches_and_frames_exactly(amd):
+    """orbfe_extractor_profile / _profile_get: per stage the launch and frame counts of the timed intervals are exactly
+    what each call enqueues (8 levels: 7 resize launches, or 8 fused blur + resize launches for sub-batches of more than 8
+    frames, which then have no separate blur launch; FAST 1; gather + octree 2; blur 1; orientation + descriptors 1; the
+    copy stages and the ingest count no kernel launch), summed over the sub-batches of a call and over calls (more calls
+    than the ring of event slots holds), and every stage that launched reports a positive, finite time."""
+    torch = pytest.importorskip("torch")
+    w, h, cfg = 640, 480, (1000, 1.2, 8, 20, 7)
+    imgs = np.stack(synth.render_sequence(900, 16, w, h, step=1.5))
+    e = amd.ORBextractor(*cfg)
+    e.set_schedule(False)
+    e.set_pyramid_blur(True)
+    e.set_pyramid_chain(False)
+    e.profile(False)
+    e(imgs[0])
+    assert all(v == (0.0, 0, 0.0) for v in e.profile_get().values())  # profiling off: nothing is recorded
+
+    def expect(what, **want):
+        got = e.profile_get()
+        print(what, got)
+        for stage, (ms, launches, frames) in got.items():
+            wl, wf = want.get(stage, (0, 0))
+            assert (launches, frames) == (wl, wf), (what, stage, launches, frames)
+            assert np.isfinite(ms) and ms >= 0, (what, stage, ms)
+            if wl > 0:
+                assert ms > 0, (what, stage, ms)
+
+    k = 11  # more calls than event slots in the ring
+    e.profile(True)
+    for i in range(k):
+        e(imgs[i])
+    expect("single frames", pyramid=(7 * k, k), fast=(k, k), octree=(2 * k, k), blur=(k, k), orient_desc=(k, k))
+
+    dev = torch.device("cuda", 0)
+    cap = e.max_keypoints(w, h)
+    d_img = torch.from_numpy(imgs).to(dev)
+    d_kp = torch.zeros((16, cap, 7), dtype=torch.float32, device=dev)
+    d_desc = torch.zeros((16, cap, 32), dtype=torch.uint8, device=dev)
+    d_n = torch.zeros((16,), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+
+    def batch():
+        e.extract_batch_device(d_img.data_ptr(), 16, w, h, w, w * h, d_kp.data_ptr(), d_desc.data_ptr(), cap, d_n.data_ptr())
+
+    e.profile(True)
+    batch()  # one launch chain over 16 frames: the fused blur + resize form, no separate blur
+    expect("16 frames, 1 stream", pyramid=(8, 16), fast=(1, 16), octree=(2, 16), orient_desc=(1, 16))
+    e.set_streams(4)
+    e.profile(True)
+    batch()  # four sub-batches of 4 frames, each with the launches of a few-frame call
+    expect("16 frames, 4 streams", pyramid=(28, 16), fast=(4, 16), octree=(8, 16), blur=(4, 16), orient_desc=(4, 16))
+    batch()  # counts add up over calls
+    expect("16 frames, 4 streams, twice", pyramid=(56, 32), fast=(8, 32), octree=(16, 32), blur=(8, 32), orient_desc=(8, 32))
+
+    e.set_streams(1)
+    left, right = synth.render_stereo(901, w, h, n_shapes=250, max_disp=40)
+    e.profile(True)
+    e.extract_stereo_frame(left, right, 400.0, 1.0)
+    expect("stereo frame", pyramid=(7, 2), fast=(1, 2), octree=(2, 2), blur=(1, 2), orient_desc=(1, 2), match=(1, 2))
