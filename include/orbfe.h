@@ -430,6 +430,60 @@ int orbfe_bow_match_consecutive_stereo_batch_device_async(orbfe_vocabulary *v, o
                                                           int check_orientation, int32_t *d_match,
                                                           int32_t *d_nmatches);
 
+/* The BowVector of transform(features, BowVector&, FeatureVector&, levelsup) (:1127-1194): addWeight in
+ * feature order for the features with weight > 0, then the L1 normalisation (sum of fabs in ascending word
+ * order, one division per entry; Thirdparty/DBoW2/DBoW2/BowVector.cpp:34-84).  word_ids ascend and are
+ * unique, *n_words of them; more than `capacity` returns ORBFE_ERR_CAPACITY with *n_words set.  Only
+ * L1_NORM / TF_IDF vocabularies (header "k L 0 0", what ORBvoc.txt is): others return ORBFE_ERR_INVALID. */
+int orbfe_vocabulary_transform_bow(orbfe_vocabulary *v, const uint8_t *descriptors, int n, int levelsup,
+                                   uint32_t *word_ids, double *values, int capacity, int *n_words);
+
+/* ------------------------------------------------------------------------- */
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc): BoW scores, loop / reloc sets  */
+/* ------------------------------------------------------------------------- */
+/* The BowVectors of the key frames, resident on the device, in the order of the reference's per-word lists
+ * (insertion order).  A handle serialises its own calls; creating one does not touch the device (the first
+ * call that uploads does), every later call needs it. */
+typedef struct orbfe_kfdb orbfe_kfdb;
+enum { ORBFE_KFDB_RELOC = 0, ORBFE_KFDB_LOOP = 1 };
+
+/* n_words: the vocabulary's word count (mvInvertedFile.resize(voc.size()), :36). */
+int orbfe_kfdb_create(int n_words, int device, orbfe_kfdb **out);
+void orbfe_kfdb_destroy(orbfe_kfdb *db);
+/* KeyFrameDatabase::add (:43-49) with pKF->mBowVec as n ascending unique word ids + values, checked on the
+ * host before anything is uploaded: ids that do not ascend strictly or reach n_words return ORBFE_ERR_INVALID.
+ * Deviation: an id already in the database returns ORBFE_ERR_INVALID (the reference would list it twice). */
+int orbfe_kfdb_add(orbfe_kfdb *db, int64_t kf_id, const uint32_t *word_ids, const double *values, int n);
+/* KeyFrameDatabase::erase (:51-70): the others keep their relative order, and a later add of the same id goes
+ * to the end.  Returns 1, or 0 when the id is not in the database; a negative status means nothing was erased. */
+int orbfe_kfdb_erase(orbfe_kfdb *db, int64_t kf_id);
+int orbfe_kfdb_clear(orbfe_kfdb *db);
+int orbfe_kfdb_size(const orbfe_kfdb *db);
+
+/* The scored set of DetectLoopCandidates (:106-160) / DetectRelocalizationCandidates (:236-288) for n_queries
+ * BowVectors in one call: query q is q_words / q_values [q_offsets[q], q_offsets[q+1]) (ascending unique ids),
+ * and the key frames excl_ids [excl_offsets[q], excl_offsets[q+1]) -- pKF->GetConnectedKeyFrames() of the loop
+ * form; excl_offsets NULL = none, ids the database does not hold are ignored -- take no part in it.  Per query:
+ * the key frames sharing more than (int)(maxCommonWords * 0.8f) words, in the order of the reference's
+ * lKFsSharingWords, as kf_id / n_common (mnLoopWords, mnRelocWords) / score ((float) of L1Scoring::score,
+ * Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68, query first) [q * capacity ..], count[q] of them.  A count
+ * above `capacity` fills `capacity` entries and returns ORBFE_ERR_CAPACITY (every count[] is still set).  At most
+ * 65535 queries per call (more returns ORBFE_ERR_INVALID). */
+int orbfe_kfdb_query(orbfe_kfdb *db, int n_queries, const int32_t *q_offsets, const uint32_t *q_words,
+                     const double *q_values, const int32_t *excl_offsets, const int64_t *excl_ids, int capacity,
+                     int64_t *kf_id, int32_t *n_common, float *score, int32_t *count);
+/* mpVoc->score(query, pKF->mBowVec) in double for n_ids named key frames (LoopClosing::DetectLoop's minScore,
+ * src/LoopClosing.cc:143-158); an id the database does not hold returns ORBFE_ERR_INVALID. */
+int orbfe_kfdb_score(orbfe_kfdb *db, const uint32_t *q_words, const double *q_values, int n, int n_ids,
+                     const int64_t *kf_ids, double *scores);
+/* The covisibility stage of both functions (:165-218 mode ORBFE_KFDB_LOOP, :293-346 ORBFE_KFDB_RELOC; min_score
+ * is read in loop mode only) over ONE query's scored set: entry i's GetBestCovisibilityKeyFrames(10) is
+ * neigh_ids [neigh_offsets[i], neigh_offsets[i+1]) in the caller's order.  Returns the candidate ids in group
+ * order, *n_out of them (ORBFE_ERR_CAPACITY when more than `capacity`).  Host code: needs no device. */
+int orbfe_kfdb_group_candidates(int mode, float min_score, int n, const int64_t *kf_id, const int32_t *n_common,
+                                const float *score, const int32_t *neigh_offsets, const int64_t *neigh_ids,
+                                int64_t *out_ids, int capacity, int *n_out);
+
 /* ------------------------------------------------------------------------- */
 /* Next to the path                                */
 /* ------------------------------------------------------------------------- */

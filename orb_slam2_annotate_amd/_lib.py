@@ -16,6 +16,7 @@ import os as _os
 # $ORBFE_LIB: an alternative build of the library (A/B runs of compile-time variants, tools/ab_build.sh); default in-tree
 LIB_PATH = Path(_os.environ["ORBFE_LIB"]) if _os.environ.get("ORBFE_LIB") else PKG_DIR / "liborbfe.so"
 
+KFDB_RELOC, KFDB_LOOP = 0, 1  # orbfe_kfdb_group_candidates modes
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 assert KP_DTYPE.itemsize == 28
@@ -66,6 +67,8 @@ EXPORTS = [
     "orbfe_undistort_points", "orbfe_undistort_keypoints_batch_device", "orbfe_compute_image_bounds",
     "orbfe_stereo_from_rgbd", "orbfe_frame_synchronize", "orbfe_debug_stall_extractor_stream", "orbfe_debug_extractor_stream_idle",
     "orbfe_debug_stall_thread_stream", "orbfe_debug_thread_stream_idle",
+    "orbfe_vocabulary_transform_bow", "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_erase",
+    "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_query", "orbfe_kfdb_score", "orbfe_kfdb_group_candidates",
 ]
 
 _lib = None
@@ -213,6 +216,18 @@ def load():
     L.orbfe_debug_geometry.argtypes = [ci, cf, ci, ci, ci, ci, ci, vp, vp, vp, ci]
     L.orbfe_debug_resize_tables.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp]
     L.orbfe_debug_resize_tiles.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    i64 = C.c_int64
+    L.orbfe_vocabulary_transform_bow.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp]
+    L.orbfe_kfdb_create.argtypes = [ci, ci, C.POINTER(C.c_void_p)]
+    L.orbfe_kfdb_destroy.argtypes = [vp]
+    L.orbfe_kfdb_destroy.restype = None
+    L.orbfe_kfdb_add.argtypes = [vp, i64, vp, vp, ci]
+    L.orbfe_kfdb_erase.argtypes = [vp, i64]
+    L.orbfe_kfdb_clear.argtypes = [vp]
+    L.orbfe_kfdb_size.argtypes = [vp]
+    L.orbfe_kfdb_query.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+    L.orbfe_kfdb_score.argtypes = [vp, vp, vp, ci, ci, vp, vp]
+    L.orbfe_kfdb_group_candidates.argtypes = [ci, cf, ci, vp, vp, vp, vp, vp, vp, ci, vp]
     _lib = L
     return L
 

@@ -19,6 +19,8 @@
 // the transform kernel, one bitonic sort per frame in LDS).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -468,6 +470,48 @@ extern "C" int orbfe_vocabulary_transform(orbfe_vocabulary* v, const uint8_t* de
   int used = 0;
   for (int i = 0; i < n; i++) used += weight[i] > 0;
   return used;
+}
+
+// The BowVector of transform(features, BowVector&, FeatureVector&, levelsup) (:1127-1194) for L1_NORM / TF_IDF:
+// addWeight(word, weight) in feature order for the features with weight > 0 (BowVector.cpp:34-46), then
+// normalize(L1): the sum of fabs over the map in ascending word order, and one division per entry (:62-84).
+extern "C" int orbfe_vocabulary_transform_bow(orbfe_vocabulary* v, const uint8_t* descriptors, int n, int levelsup,
+                                              uint32_t* word_ids, double* values, int capacity, int* n_words) {
+  if (!v || n < 0 || capacity < 0 || !n_words || (n > 0 && !descriptors) || (capacity > 0 && (!word_ids || !values)))
+    return fail(ORBFE_ERR_INVALID, "vocabulary_transform_bow: bad argument");
+  *n_words = 0;
+  if (v->scoring != 0 || v->weighting != 0)
+    return fail(ORBFE_ERR_INVALID, "vocabulary_transform_bow: only L1_NORM / TF_IDF vocabularies (header 'k L 0 0')");
+  const size_t m = (size_t)(n > 0 ? n : 1);
+  std::vector<uint32_t> word(m), node(m);
+  std::vector<double> weight(m);
+  const int rc = orbfe_vocabulary_transform(v, descriptors, n, levelsup, word.data(), weight.data(), node.data());
+  if (rc < 0) return rc;
+  std::vector<uint32_t> order;
+  order.reserve((size_t)rc);
+  for (int i = 0; i < n; i++)
+    if (weight[i] > 0) order.push_back((uint32_t)i);
+  // by word, feature order kept inside a word: the order each map entry received its additions in
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return word[a] < word[b]; });
+  std::vector<uint32_t> ids;
+  std::vector<double> vals;
+  for (size_t i = 0; i < order.size(); i++) {
+    const uint32_t f = order[i];
+    if (ids.empty() || ids.back() != word[f]) { ids.push_back(word[f]); vals.push_back(weight[f]); }
+    else vals.back() += weight[f];
+  }
+  double norm = 0.0;
+  for (double x : vals) norm += fabs(x);
+  if (norm > 0.0)
+    for (double& x : vals) x /= norm;
+  *n_words = (int)ids.size();
+  if (ids.size() > (size_t)capacity)
+    return fail(ORBFE_ERR_CAPACITY, "vocabulary_transform_bow: more words than `capacity` (see n_words)");
+  if (!ids.empty()) {
+    memcpy(word_ids, ids.data(), ids.size() * 4);
+    memcpy(values, vals.data(), vals.size() * 8);
+  }
+  return ORBFE_OK;
 }
 
 static int ensure_bow_workspace(orbfe_vocabulary* v, int nFrames, int capacity) {

@@ -84,6 +84,17 @@ class ORBVocabulary:
         fv = FeatureVector(ids, np.concatenate([[0], np.cumsum(counts)]), order)
         return bow, fv
 
+    def transform_bow(self, descriptors, levelsup: int = 4):
+        """The BowVector of transform(features, BowVector&, FeatureVector&, levelsup) through
+        orbfe_vocabulary_transform_bow: (ascending uint32 word ids, float64 values) -- the items of transform()'s dict."""
+        d = np.ascontiguousarray(descriptors, dtype=np.uint8).reshape(-1, 32)
+        cap = max(len(d), 1)
+        ids = np.zeros(cap, np.uint32)
+        values = np.zeros(cap, np.float64)
+        n = C.c_int(0)
+        check(self._L.orbfe_vocabulary_transform_bow(self._h, ptr(d), len(d), levelsup, ptr(ids), ptr(values), cap, C.byref(n)))
+        return ids[:n.value].copy(), values[:n.value].copy()
+
     def featvec_batch_device(self, d_desc, d_n, n_frames, capacity, d_nodes, d_offsets, d_indices, d_count,
                              levelsup: int = 4, d_word=0, d_weight=0):
         check(self._L.orbfe_vocabulary_featvec_batch_device(self._h, C.c_void_p(d_desc), C.c_void_p(d_n), n_frames,
