@@ -1338,8 +1338,8 @@ extern "C" int orbfe_extract_batch_pipelined(orbfe_extractor* e, const uint8_t* 
   pinIn.pin(images, frame_stride * (size_t)(n_frames - 1) + (size_t)stride * (height - 1) + width);
   pinKp.pin(keypoints, (size_t)n_frames * capacity * sizeof(orbfe_keypoint));
   pinDesc.pin(descriptors, (size_t)n_frames * capacity * 32);
-  int32_t* h_cnt = nullptr;  // counts come back through a small pinned block of their own
-  HIPCHK(hipHostMalloc((void**)&h_cnt, sizeof(int32_t) * (size_t)n_frames, hipHostMallocDefault));
+  PinBuf<int32_t> h_cnt;  // counts come back through a small pinned block of their own
+  if ((rc = h_cnt.alloc((size_t)n_frames))) return rc;
   const int nChunks = (n_frames + C - 1) / C;
   int status = ORBFE_OK;
   for (int k = 0; k < nChunks && status == ORBFE_OK; k++) {
@@ -1389,7 +1389,6 @@ extern "C" int orbfe_extract_batch_pipelined(orbfe_extractor* e, const uint8_t* 
       if (n > capacity) { overflow = true; n = capacity; }
       n_out[f] = n;
     }
-  (void)hipHostFree(h_cnt);
   resolve_stage_times(e);
   if (status != ORBFE_OK) return status;
   if (e1 != hipSuccess) return fail(ORBFE_ERR_HIP, hipGetErrorString(e1));

@@ -14,6 +14,8 @@
 namespace orbfe {
 // extractor.hip: sets the text orbfe_last_error() returns on the calling thread; returns `code`
 int fail(int code, const std::string& msg);
+// the one status rule: out of memory answers ORBFE_ERR_NOMEM, every other HIP error ORBFE_ERR_HIP
+inline int hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP; }
 }  // namespace orbfe
 
 // in a function that returns an ORBFE_* status
@@ -21,7 +23,7 @@ int fail(int code, const std::string& msg);
   do {                                                                                        \
     hipError_t _e = (expr);                                                                   \
     if (_e != hipSuccess)                                                                     \
-      return orbfe::fail(ORBFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
+      return orbfe::fail(orbfe::hip_status(_e), std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
 namespace orbfe {
@@ -43,22 +45,35 @@ struct SubSplit {
 template <typename T, bool kPinned = false>
 struct DevBuf {
   T* p = nullptr;
+  size_t cap = 0;  // elements asked for by the alloc() that made p
   DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    return *this;
+  }
   ~DevBuf() { reset(); }
   void reset() {
     if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
     p = nullptr;
+    cap = 0;
   }
-  // frees what it holds first; at least one element
-  int alloc(size_t n) {
+  // frees what it holds first; at least one element.  try_alloc: for helpers that pass the HIP error on
+  hipError_t try_alloc(size_t n) {
     reset();
     const size_t bytes = (n ? n : 1) * sizeof(T);
-    if (kPinned) HIPCHK(hipHostMalloc((void**)&p, bytes, hipHostMallocDefault));
-    else HIPCHK(hipMalloc((void**)&p, bytes));
+    const hipError_t e = kPinned ? hipHostMalloc((void**)&p, bytes, hipHostMallocDefault) : hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess) cap = n;
+    else p = nullptr;
+    return e;
+  }
+  int alloc(size_t n) {
+    HIPCHK(try_alloc(n));
     return ORBFE_OK;
   }
+  // grow-only: room for `need` elements, or a fresh array of `grown` (the caller's growth policy); the old contents are
+  // dropped, so whatever may still read them must have finished
+  int reserve(size_t need, size_t grown) { return need <= cap ? ORBFE_OK : alloc(grown); }
   int upload(const T* src, size_t n) {
     int rc = alloc(n);
     if (rc) return rc;
@@ -70,6 +85,17 @@ struct DevBuf {
 };
 template <typename T>
 using PinBuf = DevBuf<T, true>;
+
+// matcher.hip: device slabs of released frames / key-frame databases, kept for the next one -- hipMalloc / hipFree cost
+// tens of microseconds and hipFree waits for the whole device.  slab_get: the smallest kept slab of `device` with
+// bytes <= cap <= 4 * bytes + 64 KiB, else a new one of the next 64 KiB class; slab_put: back to the pool (p = NULL after)
+struct Slab {
+  void* p = nullptr;
+  size_t cap = 0;  // bytes
+  int device = 0;
+};
+hipError_t slab_get(int device, size_t bytes, Slab* out);
+void slab_put(Slab* s);
 }  // namespace orbfe
 
 extern "C" {

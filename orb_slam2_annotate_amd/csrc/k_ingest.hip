@@ -3,6 +3,7 @@
 // src/Tracking.cc:176-262) and MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:269-333).
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -11,6 +12,7 @@
 #include "kernels.h"
 #include "orb_spec.h"
 
+using orbfe::DevBuf;
 using orbfe::fail;
 
 namespace {
@@ -84,21 +86,15 @@ extern "C" int orbfe_cvt_gray(int device, const uint8_t* src, int width, int hei
       dst_stride < width)
     return fail(ORBFE_ERR_INVALID, "cvt_gray: bad argument");
   HIPCHK(hipSetDevice(device));
-  uint8_t *ds = nullptr, *dd = nullptr;
-  const size_t sb = (size_t)width * channels * height, db = (size_t)width * height;
-  HIPCHK(hipMalloc((void**)&ds, sb));
-  hipError_t err = hipMalloc((void**)&dd, db);
-  if (err == hipSuccess) err = hipMemcpy2D(ds, (size_t)width * channels, src, stride, (size_t)width * channels, height, hipMemcpyHostToDevice);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(k_cvt_gray, dim3((width + 1023) / 1024, height, 1), dim3(256), 0, 0, ds, width, height,
-                       width * channels, 0, channels, rgb_order, dd, width, 0);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (err == hipSuccess) err = hipMemcpy2D(dst, dst_stride, dd, width, width, height, hipMemcpyDeviceToHost);
-  (void)hipFree(ds);
-  if (dd) (void)hipFree(dd);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("cvt_gray: ") + hipGetErrorString(err));
+  DevBuf<uint8_t> ds, dd;
+  int rc;
+  if ((rc = ds.alloc((size_t)width * channels * height)) || (rc = dd.alloc((size_t)width * height))) return rc;
+  HIPCHK(hipMemcpy2D(ds, (size_t)width * channels, src, stride, (size_t)width * channels, height, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_cvt_gray, dim3((width + 1023) / 1024, height, 1), dim3(256), 0, 0, ds.p, width, height,
+                     width * channels, 0, channels, rgb_order, dd.p, width, 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy2D(dst, dst_stride, dd, width, width, height, hipMemcpyDeviceToHost));
   return ORBFE_OK;
 }
 
@@ -128,21 +124,15 @@ extern "C" int orbfe_distinctive_descriptors(int device, const uint8_t* descript
   if (offsets[0] != 0) return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: offsets[0] != 0");
   const size_t total = (size_t)offsets[n_points];
   HIPCHK(hipSetDevice(device));
-  uint8_t* dd = nullptr; int32_t *doff = nullptr, *dbest = nullptr;
-  HIPCHK(hipMalloc((void**)&dd, total * 32 + 32));
-  hipError_t err = hipMalloc((void**)&doff, ((size_t)n_points + 1) * 4);
-  if (err == hipSuccess) err = hipMalloc((void**)&dbest, (size_t)n_points * 4);
-  if (err == hipSuccess && total) err = hipMemcpy(dd, descriptors, total * 32, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(doff, offsets, ((size_t)n_points + 1) * 4, hipMemcpyHostToDevice);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(k_distinctive, dim3(n_points), dim3(256), 0, 0, dd, doff, dbest);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipMemcpy(best_index, dbest, (size_t)n_points * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(dd);
-  if (doff) (void)hipFree(doff);
-  if (dbest) (void)hipFree(dbest);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("distinctive_descriptors: ") + hipGetErrorString(err));
+  DevBuf<uint8_t> dd;
+  DevBuf<int32_t> doff, dbest;
+  int rc;
+  if ((rc = dd.alloc(total * 32 + 32)) || (rc = doff.alloc((size_t)n_points + 1)) || (rc = dbest.alloc((size_t)n_points))) return rc;
+  if (total) HIPCHK(hipMemcpy(dd, descriptors, total * 32, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(doff, offsets, ((size_t)n_points + 1) * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_distinctive, dim3(n_points), dim3(256), 0, 0, dd.p, doff.p, dbest.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(best_index, dbest, (size_t)n_points * 4, hipMemcpyDeviceToHost));
   return ORBFE_OK;
 }
 
@@ -158,8 +148,8 @@ extern "C" int orbfe_distinctive_descriptors(int device, const uint8_t* descript
 struct orbfe_rectifier {
   int device = 0;
   int width = 0, height = 0;  // destination size = map size
-  uint32_t* xy = nullptr;     // [height][pitch]
-  uint16_t* phase = nullptr;  // [height][pitch]
+  DevBuf<uint32_t> xy;        // [height][pitch]
+  DevBuf<uint16_t> phase;     // [height][pitch]
   int pitch = 0;              // multiple of 4
 };
 
@@ -234,7 +224,7 @@ __global__ __launch_bounds__(256) void k_remap(const uint32_t* __restrict__ xy, 
 int remap_launch(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride, size_t sFrame,
                  uint8_t* d_dst, int dstride, size_t dFrame, hipStream_t stream) {
   const int tilesX = (r->width + 255) / 256, tilesY = (r->height + 3) / 4;
-  hipLaunchKernelGGL(k_remap, dim3((unsigned)tilesX * tilesY * n_frames), dim3(256), 0, stream, r->xy, r->phase, r->pitch,
+  hipLaunchKernelGGL(k_remap, dim3((unsigned)tilesX * tilesY * n_frames), dim3(256), 0, stream, r->xy.p, r->phase.p, r->pitch,
                      r->width, r->height, tilesX, n_frames, d_src, sw, sh, sstride, sFrame, d_dst, dstride, dFrame);
   HIPCHK(hipGetLastError());
   return ORBFE_OK;
@@ -259,39 +249,25 @@ extern "C" int orbfe_rectifier_create(int device, const float* map_x, const floa
   if (!map_x || !map_y || !out || width <= 0 || height <= 0 || map_stride < width || width > 32767 || height > 32767)
     return fail(ORBFE_ERR_INVALID, "remap_create: bad argument");
   HIPCHK(hipSetDevice(device));
-  orbfe_rectifier* r = new orbfe_rectifier();
+  std::unique_ptr<orbfe_rectifier> r(new orbfe_rectifier());
   r->device = device; r->width = width; r->height = height; r->pitch = (width + 3) & ~3;
-  float *dmx = nullptr, *dmy = nullptr;
-  const size_t mb = (size_t)width * height * 4, n = (size_t)r->pitch * height;
-  hipError_t err = hipMalloc((void**)&r->xy, n * 4);
-  if (err == hipSuccess) err = hipMalloc((void**)&r->phase, n * 2);
-  if (err == hipSuccess) err = hipMalloc((void**)&dmx, mb);
-  if (err == hipSuccess) err = hipMalloc((void**)&dmy, mb);
-  if (err == hipSuccess) err = hipMemcpy2D(dmx, (size_t)width * 4, map_x, (size_t)map_stride * 4, (size_t)width * 4, height, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy2D(dmy, (size_t)width * 4, map_y, (size_t)map_stride * 4, (size_t)width * 4, height, hipMemcpyHostToDevice);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(k_remap_convert, dim3((r->pitch + 255) / 256, height), dim3(256), 0, 0, dmx, dmy, width, width,
-                       height, r->pitch, r->xy, r->phase);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (dmx) (void)hipFree(dmx);
-  if (dmy) (void)hipFree(dmy);
-  if (err != hipSuccess) {
-    if (r->xy) (void)hipFree(r->xy);
-    if (r->phase) (void)hipFree(r->phase);
-    delete r;
-    return fail(err == hipErrorOutOfMemory ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP, std::string("remap_create: ") + hipGetErrorString(err));
-  }
-  *out = r;
+  DevBuf<float> dmx, dmy;
+  const size_t m = (size_t)width * height, n = (size_t)r->pitch * height;
+  int rc;
+  if ((rc = r->xy.alloc(n)) || (rc = r->phase.alloc(n)) || (rc = dmx.alloc(m)) || (rc = dmy.alloc(m))) return rc;
+  HIPCHK(hipMemcpy2D(dmx, (size_t)width * 4, map_x, (size_t)map_stride * 4, (size_t)width * 4, height, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy2D(dmy, (size_t)width * 4, map_y, (size_t)map_stride * 4, (size_t)width * 4, height, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_remap_convert, dim3((r->pitch + 255) / 256, height), dim3(256), 0, 0, dmx.p, dmy.p, width, width,
+                     height, r->pitch, r->xy.p, r->phase.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  *out = r.release();
   return ORBFE_OK;
 }
 
 extern "C" void orbfe_rectifier_destroy(orbfe_rectifier* r) {
   if (!r) return;
   (void)hipSetDevice(r->device);
-  (void)hipFree(r->xy);
-  (void)hipFree(r->phase);
   delete r;
 }
 
@@ -300,18 +276,14 @@ extern "C" int orbfe_remap(orbfe_rectifier* r, const uint8_t* src, int src_width
   if (!r || !src || !dst || src_width <= 0 || src_height <= 0 || src_stride < src_width || dst_stride < r->width)
     return fail(ORBFE_ERR_INVALID, "remap: bad argument");
   HIPCHK(hipSetDevice(r->device));
-  uint8_t *ds = nullptr, *dd = nullptr;
-  HIPCHK(hipMalloc((void**)&ds, (size_t)src_width * src_height));
-  hipError_t err = hipMalloc((void**)&dd, (size_t)r->pitch * r->height);
-  if (err == hipSuccess) err = hipMemcpy2D(ds, src_width, src, src_stride, src_width, src_height, hipMemcpyHostToDevice);
-  int rc = ORBFE_OK;
-  if (err == hipSuccess) rc = remap_launch(r, ds, 1, src_width, src_height, src_width, 0, dd, r->pitch, 0, 0);
-  if (err == hipSuccess && rc == ORBFE_OK) err = hipDeviceSynchronize();
-  if (err == hipSuccess && rc == ORBFE_OK) err = hipMemcpy2D(dst, dst_stride, dd, r->pitch, r->width, r->height, hipMemcpyDeviceToHost);
-  (void)hipFree(ds);
-  if (dd) (void)hipFree(dd);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("remap: ") + hipGetErrorString(err));
-  return rc;
+  DevBuf<uint8_t> ds, dd;
+  int rc;
+  if ((rc = ds.alloc((size_t)src_width * src_height)) || (rc = dd.alloc((size_t)r->pitch * r->height))) return rc;
+  HIPCHK(hipMemcpy2D(ds, src_width, src, src_stride, src_width, src_height, hipMemcpyHostToDevice));
+  if ((rc = remap_launch(r, ds, 1, src_width, src_height, src_width, 0, dd, r->pitch, 0, 0))) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy2D(dst, dst_stride, dd, r->pitch, r->width, r->height, hipMemcpyDeviceToHost));
+  return ORBFE_OK;
 }
 
 extern "C" int orbfe_remap_batch_device(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int src_width,
@@ -468,15 +440,14 @@ extern "C" int orbfe_init_undistort_rectify_map(int device, const double* K, con
   p.k3 = n_dist >= 5 ? D[4] : 0; p.k4 = n_dist >= 8 ? D[5] : 0; p.k5 = n_dist >= 8 ? D[6] : 0; p.k6 = n_dist >= 8 ? D[7] : 0;
   p.w = width; p.h = height;
   HIPCHK(hipSetDevice(device));
-  float* dmap = nullptr;
+  DevBuf<float> dmap;
   const size_t n = (size_t)width * height;
-  HIPCHK(hipMalloc((void**)&dmap, 2 * n * 4));
-  hipLaunchKernelGGL(k_init_rectify_map, dim3((height + 63) / 64), dim3(64), 0, 0, p, dmap, dmap + n);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipMemcpy(map_x, dmap, n * 4, hipMemcpyDeviceToHost);
-  if (err == hipSuccess) err = hipMemcpy(map_y, dmap + n, n * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(dmap);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("init_undistort_rectify_map: ") + hipGetErrorString(err));
+  const int rc = dmap.alloc(2 * n);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_init_rectify_map, dim3((height + 63) / 64), dim3(64), 0, 0, p, dmap.p, dmap.p + n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(map_x, dmap, n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(map_y, dmap + n, n * 4, hipMemcpyDeviceToHost));
   return ORBFE_OK;
 }
 
@@ -487,18 +458,13 @@ extern "C" int orbfe_undistort_points(int device, const float* xy, int n, const 
     return fail(ORBFE_ERR_INVALID, "undistort_points: bad argument");
   if (n == 0) return ORBFE_OK;
   HIPCHK(hipSetDevice(device));
-  float *din = nullptr, *dout = nullptr;
-  HIPCHK(hipMalloc((void**)&din, (size_t)n * 8));
-  hipError_t err = hipMalloc((void**)&dout, (size_t)n * 8);
-  if (err == hipSuccess) err = hipMemcpy(din, xy, (size_t)n * 8, hipMemcpyHostToDevice);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, 0, p, din, n, dout);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipMemcpy(out_xy, dout, (size_t)n * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(din);
-  if (dout) (void)hipFree(dout);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("undistort_points: ") + hipGetErrorString(err));
+  DevBuf<float> din, dout;
+  int rc;
+  if ((rc = din.alloc((size_t)n * 2)) || (rc = dout.alloc((size_t)n * 2))) return rc;
+  HIPCHK(hipMemcpy(din, xy, (size_t)n * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, 0, p, din.p, n, dout.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out_xy, dout, (size_t)n * 8, hipMemcpyDeviceToHost));
   return ORBFE_OK;
 }
 
@@ -547,21 +513,18 @@ extern "C" int orbfe_stereo_from_rgbd(int device, const float* kx, const float* 
       return fail(ORBFE_ERR_INVALID, "stereo_from_rgbd: keypoint outside the depth image");
   if (n == 0) return ORBFE_OK;
   HIPCHK(hipSetDevice(device));
-  float* buf = nullptr;
+  DevBuf<float> buf;
   const size_t img = (size_t)width * height;
-  HIPCHK(hipMalloc((void**)&buf, (img + 5 * (size_t)n) * 4));
+  const int rc = buf.alloc(img + 5 * (size_t)n);
+  if (rc) return rc;
   float *dimg = buf, *dkx = buf + img, *dky = dkx + n, *dkux = dky + n, *dur = dkux + n, *ddp = dur + n;
-  hipError_t err = hipMemcpy2D(dimg, (size_t)width * 4, depth_image, (size_t)stride_floats * 4, (size_t)width * 4, height, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dkx, kx, (size_t)n * 4, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dky, ky, (size_t)n * 4, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dkux, kux, (size_t)n * 4, hipMemcpyHostToDevice);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(k_stereo_from_rgbd, dim3((n + 255) / 256), dim3(256), 0, 0, dkx, dky, dkux, n, dimg, width, mbf, dur, ddp);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipMemcpy(u_right, dur, (size_t)n * 4, hipMemcpyDeviceToHost);
-  if (err == hipSuccess) err = hipMemcpy(depth, ddp, (size_t)n * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(buf);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("stereo_from_rgbd: ") + hipGetErrorString(err));
+  HIPCHK(hipMemcpy2D(dimg, (size_t)width * 4, depth_image, (size_t)stride_floats * 4, (size_t)width * 4, height, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dkx, kx, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dky, ky, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dkux, kux, (size_t)n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_stereo_from_rgbd, dim3((n + 255) / 256), dim3(256), 0, 0, dkx, dky, dkux, n, dimg, width, mbf, dur, ddp);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(u_right, dur, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(depth, ddp, (size_t)n * 4, hipMemcpyDeviceToHost));
   return ORBFE_OK;
 }

@@ -24,52 +24,6 @@
 using namespace orbfe;
 
 namespace {
-// Released slabs are kept for the next database / the next doubling (the frame slabs of matcher.hip work the same way)
-struct Slab {
-  void* p = nullptr;
-  size_t cap = 0;  // bytes
-  int device = 0;
-};
-
-struct KfdbPool {
-  std::mutex m;
-  std::vector<Slab> slabs;
-  static constexpr size_t kKeep = 16;
-  ~KfdbPool() {}  // (process exit: the runtime reclaims device memory; no HIP calls from static destructors)
-};
-KfdbPool g_kfdbPool;
-
-hipError_t slab_get(int device, size_t bytes, Slab* out) {
-  {
-    std::lock_guard<std::mutex> lk(g_kfdbPool.m);
-    auto& v = g_kfdbPool.slabs;
-    int best = -1;
-    for (size_t i = 0; i < v.size(); i++)
-      if (v[i].device == device && v[i].cap >= bytes && v[i].cap <= 4 * bytes + (1u << 16) && (best < 0 || v[i].cap < v[(size_t)best].cap))
-        best = (int)i;
-    if (best >= 0) {
-      *out = v[(size_t)best];
-      v.erase(v.begin() + best);
-      return hipSuccess;
-    }
-  }
-  const size_t want = (bytes + (1u << 16) - 1) & ~(size_t)((1u << 16) - 1);
-  hipError_t e = hipMalloc(&out->p, want);
-  if (e == hipSuccess) { out->cap = want; out->device = device; } else out->p = nullptr;
-  return e;
-}
-
-void slab_put(int device, Slab* s) {
-  if (!s->p) return;
-  bool kept = false;
-  {
-    std::lock_guard<std::mutex> lk(g_kfdbPool.m);
-    if (g_kfdbPool.slabs.size() < KfdbPool::kKeep) { g_kfdbPool.slabs.push_back({s->p, s->cap, device}); kept = true; }
-  }
-  if (!kept) (void)hipFree(s->p);
-  s->p = nullptr; s->cap = 0;
-}
-
 struct HostSlot {
   int64_t id;  // the slot's index is its insertion sequence number (compaction renumbers, order kept)
   uint32_t off, n;
@@ -89,11 +43,12 @@ struct orbfe_kfdb {
   std::unordered_map<int64_t, int> slotOf;  // live ids
   int nLive = 0;
   bool stale = false;  // a compaction failed half-way: the device arrays must be rewritten before they are read again
-  // device CSR
+  // device CSR: slabs of the pool that the resident frames use (host_internal.h), so a released database's arrays serve
+  // the next database / the next doubling
   Slab dWords, dValues, dSlots;
   // grow-only workspace of the queries + pinned staging in both directions
-  DevBuf<uint8_t> work; size_t workCap = 0;
-  PinBuf<uint8_t> pin; size_t pinCap = 0;
+  DevBuf<uint8_t> work;
+  PinBuf<uint8_t> pin;
 };
 
 namespace {
@@ -107,40 +62,31 @@ int kfdb_device(orbfe_kfdb* db) {
   return ORBFE_OK;
 }
 
+// `have` (or `first` when there is nothing yet), doubled until it holds `need`
+size_t doubled(size_t have, size_t first, size_t need) {
+  size_t want = have ? have : first;
+  while (want < need) want *= 2;
+  return want;
+}
+
 // room for `need` bytes in *s, contents [0, used) kept: a doubled slab from the pool, one device-to-device copy
 int slab_reserve(orbfe_kfdb* db, Slab* s, size_t need, size_t used) {
   if (need <= s->cap) return ORBFE_OK;
-  size_t want = s->cap ? s->cap : (size_t)1 << 16;
-  while (want < need) want *= 2;
   Slab n;
-  HIPCHK(slab_get(db->device, want, &n));
+  HIPCHK(slab_get(db->device, doubled(s->cap, (size_t)1 << 16, need), &n));
   if (used) {
     hipError_t e = hipMemcpyAsync(n.p, s->p, used, hipMemcpyDeviceToDevice, db->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
-    if (e != hipSuccess) { slab_put(db->device, &n); HIPCHK(e); }
+    if (e != hipSuccess) { slab_put(&n); HIPCHK(e); }
   }
-  slab_put(db->device, s);
+  slab_put(s);
   *s = n;
   return ORBFE_OK;
 }
 
 int ensure_work(orbfe_kfdb* db, size_t devBytes, size_t pinBytes) {
-  int rc;
-  if (devBytes > db->workCap) {
-    size_t want = db->workCap ? db->workCap : (size_t)1 << 20;
-    while (want < devBytes) want *= 2;
-    db->workCap = 0;
-    if ((rc = db->work.alloc(want))) return rc;
-    db->workCap = want;
-  }
-  if (pinBytes > db->pinCap) {
-    size_t want = db->pinCap ? db->pinCap : (size_t)1 << 16;
-    while (want < pinBytes) want *= 2;
-    db->pinCap = 0;
-    if ((rc = db->pin.alloc(want))) return rc;
-    db->pinCap = want;
-  }
-  return ORBFE_OK;
+  const int rc = db->work.reserve(devBytes, doubled(db->work.cap, (size_t)1 << 20, devBytes));
+  return rc ? rc : db->pin.reserve(pinBytes, doubled(db->pin.cap, (size_t)1 << 16, pinBytes));
 }
 
 KfdbStore store_of(const orbfe_kfdb* db) {
@@ -210,9 +156,9 @@ extern "C" void orbfe_kfdb_destroy(orbfe_kfdb* db) {
   if (db->ready) {
     (void)hipSetDevice(db->device);
     (void)hipStreamSynchronize(db->stream);
-    slab_put(db->device, &db->dWords);
-    slab_put(db->device, &db->dValues);
-    slab_put(db->device, &db->dSlots);
+    slab_put(&db->dWords);
+    slab_put(&db->dValues);
+    slab_put(&db->dSlots);
     (void)hipStreamDestroy(db->stream);
   }
   delete db;

@@ -25,18 +25,16 @@ namespace {
 struct Arena {
   int device = -1;
   hipStream_t stream = nullptr;
-  uint8_t* base = nullptr;
-  size_t cap = 0, used = 0;
+  DevBuf<uint8_t> base;
+  size_t used = 0;
   // pinned mirror of the uploaded part of the arena: up() only copies into it, flush() sends the whole
   // dirty range in ONE host-to-device copy before the first kernel of the call
-  uint8_t* hmirror = nullptr;
-  size_t hcap = 0, dirtyLo = 0, dirtyHi = 0;
+  PinBuf<uint8_t> hmirror;
+  size_t dirtyLo = 0, dirtyHi = 0;
   bool sizing = false;  // arena_stage()'s first pass: carve() only advances `used`, up() / up_fill() copy nothing
-  ~Arena() {
+  ~Arena() {  // (thread exit; the buffers free themselves behind this, on the device set here)
     if (device >= 0) {
       (void)hipSetDevice(device);
-      if (hmirror) (void)hipHostFree(hmirror);
-      if (base) (void)hipFree(base);
       if (stream) (void)hipStreamDestroy(stream);
     }
   }
@@ -53,14 +51,9 @@ hipError_t arena_begin(int device, size_t bytes, Arena** out) {
     err = hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking);
     if (err != hipSuccess) { a.device = -1; return err; }
   }
-  if (bytes > a.cap) {
-    if (a.base) (void)hipFree(a.base);
-    a.base = nullptr;
-    a.cap = 0;
-    size_t want = bytes + bytes / 2 + (1u << 20);
-    err = hipMalloc((void**)&a.base, want);
+  if (bytes > a.base.cap) {
+    err = a.base.try_alloc(bytes + bytes / 2 + (1u << 20));
     if (err != hipSuccess) return err;
-    a.cap = want;
   }
   a.used = 0;
   a.dirtyLo = a.dirtyHi = 0;
@@ -71,23 +64,18 @@ template <typename T>
 T* carve(Arena* a, size_t n) {
   size_t off = (a->used + 255) & ~(size_t)255;
   a->used = off + n * sizeof(T);
-  return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(a->base) + off);
+  return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(a->base.p) + off);
 }
 inline size_t pad(size_t bytes) { return ((bytes + 255) & ~(size_t)255) + 256; }
 
 // the pinned mirror covers arena offsets [0, upto); what earlier up() calls of this call staged is kept
 hipError_t grow_mirror(Arena* a, size_t upto) {
-  if (upto <= a->hcap) return hipSuccess;
-  const size_t want = upto + upto / 2 + (1u << 16);
-  uint8_t* nh = nullptr;
-  hipError_t e = hipHostMalloc((void**)&nh, want, hipHostMallocDefault);
+  if (upto <= a->hmirror.cap) return hipSuccess;
+  PinBuf<uint8_t> nh;
+  hipError_t e = nh.try_alloc(upto + upto / 2 + (1u << 16));
   if (e != hipSuccess) return e;
-  if (a->hmirror) {
-    if (a->dirtyHi > a->dirtyLo) std::memcpy(nh + a->dirtyLo, a->hmirror + a->dirtyLo, a->dirtyHi - a->dirtyLo);
-    (void)hipHostFree(a->hmirror);
-  }
-  a->hmirror = nh;
-  a->hcap = want;
+  if (a->hmirror && a->dirtyHi > a->dirtyLo) std::memcpy(nh + a->dirtyLo, a->hmirror + a->dirtyLo, a->dirtyHi - a->dirtyLo);
+  a->hmirror = std::move(nh);
   return hipSuccess;
 }
 inline void mark_dirty(Arena* a, size_t off, size_t bytes) {
@@ -160,12 +148,10 @@ hipError_t arena_stage(int device, Arena** out, F&& stage) {
 // ONE host-to-device copy, counts + candidate lists come back in ONE copy (13 + 2 small transfers of
 // ~7 us each were most of a call before).
 struct Staging {
-  uint8_t* h = nullptr;
-  size_t cap = 0;
+  PinBuf<uint8_t> h;
   hipEvent_t pending = nullptr;  // an asynchronous copy OUT of the buffer that nobody waited for (orbfe_frame_upload): the
   bool isPending = false;        // next use of the buffer waits for it first
   ~Staging() {
-    if (h) (void)hipHostFree(h);
     if (pending) (void)hipEventDestroy(pending);
   }
 };
@@ -177,14 +163,7 @@ hipError_t staging_reserve(size_t bytes) {
     if (e != hipSuccess) return e;
     t_staging.isPending = false;
   }
-  if (bytes <= t_staging.cap) return hipSuccess;
-  if (t_staging.h) (void)hipHostFree(t_staging.h);
-  t_staging.h = nullptr;
-  t_staging.cap = 0;
-  const size_t want = bytes + bytes / 2 + (1u << 16);
-  hipError_t e = hipHostMalloc((void**)&t_staging.h, want, hipHostMallocDefault);
-  if (e == hipSuccess) t_staging.cap = want;
-  return e;
+  return bytes <= t_staging.h.cap ? hipSuccess : t_staging.h.try_alloc(bytes + bytes / 2 + (1u << 16));
 }
 // an asynchronous copy out of the staging buffer was enqueued on `s` and nobody waits for it: the next staging_reserve() does
 hipError_t staging_mark_pending(hipStream_t s) {
@@ -290,8 +269,7 @@ struct orbfe_frame {
   std::vector<uint32_t> hindices;
   orbfe_featvec fv = {};
   bool haveFv = false;
-  uint8_t* slab = nullptr;                  // one device allocation (from the slab pool)
-  size_t slabCap = 0;
+  Slab slab;                                // one device allocation (from the slab pool)
   hipEvent_t ready = nullptr;               // recorded behind the upload + grid build; consumers on other streams wait for it
   mutable std::atomic<bool> settled{false}; // a consumer has synchronised behind `ready`: no further waits needed
   float *dx = nullptr, *dy = nullptr, *dangle = nullptr, *dur = nullptr;
@@ -308,19 +286,21 @@ inline const orbfe_frame_view* canon(const orbfe_frame_view* f) { return (f && f
 }
 
 namespace {
-// Slabs and events of released frames are kept for the next upload: hipMalloc / hipFree cost tens of microseconds and
-// hipFree waits for the whole device -- in a live system every key-frame insertion would stall the extractor's streams.
+// Slabs (host_internal.h: frames here, the key-frame database's arrays in kfdb.hip) and events of released frames are kept
+// for the next upload: hipMalloc / hipFree cost tens of microseconds and hipFree waits for the whole device -- in a live
+// system every key-frame insertion would stall the extractor's streams.
 struct FramePool {
   std::mutex m;
-  struct Slab { int device; uint8_t* p; size_t cap; };
   std::vector<Slab> slabs;
   std::vector<std::pair<int, hipEvent_t>> events;
-  static constexpr size_t kKeep = 64;
+  static constexpr size_t kKeepSlabs = 80, kKeepEvents = 256;
   ~FramePool() {}  // (process exit: the runtime reclaims device memory; no HIP calls from static destructors)
 };
 FramePool g_framePool;
+}  // namespace
 
-hipError_t slab_get(int device, size_t bytes, uint8_t** p, size_t* cap) {
+namespace orbfe {
+hipError_t slab_get(int device, size_t bytes, Slab* out) {
   {
     std::lock_guard<std::mutex> lk(g_framePool.m);
     auto& v = g_framePool.slabs;
@@ -329,24 +309,30 @@ hipError_t slab_get(int device, size_t bytes, uint8_t** p, size_t* cap) {
       if (v[i].device == device && v[i].cap >= bytes && v[i].cap <= 4 * bytes + (1u << 16) && (best < 0 || v[i].cap < v[(size_t)best].cap))
         best = (int)i;
     if (best >= 0) {
-      *p = v[(size_t)best].p; *cap = v[(size_t)best].cap;
+      *out = v[(size_t)best];
       v.erase(v.begin() + best);
       return hipSuccess;
     }
   }
-  const size_t want = (bytes + (1u << 16) - 1) & ~(size_t)((1u << 16) - 1);  // 64 KB classes: frames of similar size share slabs
-  hipError_t e = hipMalloc((void**)p, want);
-  if (e == hipSuccess) *cap = want;
+  const size_t want = (bytes + (1u << 16) - 1) & ~(size_t)((1u << 16) - 1);  // 64 KB classes: users of similar size share slabs
+  *out = Slab{};
+  hipError_t e = hipMalloc(&out->p, want);
+  if (e == hipSuccess) { out->cap = want; out->device = device; } else out->p = nullptr;
   return e;
 }
-void slab_put(int device, uint8_t* p, size_t cap) {
-  if (!p) return;
+void slab_put(Slab* s) {
+  if (!s->p) return;
+  bool kept = false;
   {
     std::lock_guard<std::mutex> lk(g_framePool.m);
-    if (g_framePool.slabs.size() < FramePool::kKeep) { g_framePool.slabs.push_back({device, p, cap}); return; }
+    if (g_framePool.slabs.size() < FramePool::kKeepSlabs) { g_framePool.slabs.push_back(*s); kept = true; }
   }
-  (void)hipFree(p);
+  if (!kept) (void)hipFree(s->p);
+  *s = Slab{};
 }
+}  // namespace orbfe
+
+namespace {
 hipError_t event_get(int device, hipEvent_t* e) {
   {
     std::lock_guard<std::mutex> lk(g_framePool.m);
@@ -360,7 +346,7 @@ void event_put(int device, hipEvent_t e) {
   if (!e) return;
   {
     std::lock_guard<std::mutex> lk(g_framePool.m);
-    if (g_framePool.events.size() < 4 * FramePool::kKeep) { g_framePool.events.push_back({device, e}); return; }
+    if (g_framePool.events.size() < FramePool::kKeepEvents) { g_framePool.events.push_back({device, e}); return; }
   }
   (void)hipEventDestroy(e);
 }
@@ -395,7 +381,7 @@ extern "C" void orbfe_frame_release(orbfe_frame* f) {
   if (f->ready && !f->settled.load(std::memory_order_acquire)) (void)hipEventSynchronize(f->ready);
   for (size_t i = 0; i < t_unsettled.size();)
     if (t_unsettled[i] == f) t_unsettled.erase(t_unsettled.begin() + (long)i); else i++;
-  slab_put(f->device, f->slab, f->slabCap);
+  slab_put(&f->slab);
   event_put(f->device, f->ready);
   delete f;
 }
@@ -454,15 +440,14 @@ int frame_host_init(const char* who, int device, const orbfe_frame_view* v, cons
   L->oA = place(N * 4); L->oO = place(N * 4); L->oD = place(N * 32); L->oK = place(N * 4); L->oC = place(3073 * 4);
   L->total = off;
   hipError_t err = hipSetDevice(device);
-  if (err == hipSuccess) err = slab_get(device, off, &f->slab, &f->slabCap);
+  if (err == hipSuccess) err = slab_get(device, off, &f->slab);
   if (err == hipSuccess) err = event_get(device, &f->ready);
   if (err != hipSuccess) {
-    const int code = err == hipErrorOutOfMemory ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP;
     orbfe_frame_release(f);
-    return fail(code, std::string(who) + ": " + hipGetErrorString(err));
+    return fail(hip_status(err), std::string(who) + ": " + hipGetErrorString(err));
   }
   f->settled.store(false);
-  uint8_t* b = f->slab;
+  uint8_t* b = (uint8_t*)f->slab.p;
   f->dx = (float*)(b + L->oX); f->dy = (float*)(b + L->oY); f->dangle = (float*)(b + L->oA); f->dur = (float*)(b + L->oU);
   f->doct = (int32_t*)(b + L->oO); f->dkey = (uint32_t*)(b + L->oK); f->dcell = (int32_t*)(b + L->oC); f->dindices = (uint32_t*)(b + L->oI);
   f->ddesc = b + L->oD; f->dstereo = b + L->oS;
@@ -512,11 +497,11 @@ extern "C" int orbfe_frame_upload(int device, const orbfe_frame_view* v, const o
     }
     if (nIdx) std::memcpy(h + L.oI, f->hindices.data(), nIdx * 4);
     // ONE copy (every further hipMemcpyAsync costs the host ~5 us)
-    err = hipMemcpyAsync(f->slab, h, upBytes, hipMemcpyHostToDevice, ar->stream);
+    err = hipMemcpyAsync(f->slab.p, h, upBytes, hipMemcpyHostToDevice, ar->stream);
     if (err == hipSuccess) err = staging_mark_pending(ar->stream);  // the next use of the staging buffer waits for these copies
   }
   if (err == hipSuccess) err = frame_finish(ar, f, v);
-  if (err != hipSuccess) { orbfe_frame_release(f); return fail(ORBFE_ERR_HIP, std::string("frame_upload: ") + hipGetErrorString(err)); }
+  if (err != hipSuccess) { orbfe_frame_release(f); return fail(hip_status(err), std::string("frame_upload: ") + hipGetErrorString(err)); }
   *out = f;
   return ORBFE_OK;
 }
@@ -552,7 +537,7 @@ extern "C" int orbfe_frame_from_device(int device, const orbfe_keypoint* d_keypo
     else { std::memset(h + L.oU, 0, (size_t)n * 4); std::memset(h + L.oS, 0, (size_t)n); }
     if (nIdx) std::memcpy(h + L.oI, f->hindices.data(), nIdx * 4);
     if (xyFromView) { std::memcpy(h + L.oX, f->hx.data(), (size_t)n * 4); std::memcpy(h + L.oY, f->hy.data(), (size_t)n * 4); }
-    err = hipMemcpyAsync(f->slab, h, hostBytes, hipMemcpyHostToDevice, ar->stream);
+    err = hipMemcpyAsync(f->slab.p, h, hostBytes, hipMemcpyHostToDevice, ar->stream);
     if (err == hipSuccess) err = staging_mark_pending(ar->stream);
   }
   if (err == hipSuccess && n) {
@@ -561,7 +546,7 @@ extern "C" int orbfe_frame_from_device(int device, const orbfe_keypoint* d_keypo
     err = hipGetLastError();
   }
   if (err == hipSuccess) err = frame_finish(ar, f, view);
-  if (err != hipSuccess) { orbfe_frame_release(f); return fail(ORBFE_ERR_HIP, std::string("frame_from_device: ") + hipGetErrorString(err)); }
+  if (err != hipSuccess) { orbfe_frame_release(f); return fail(hip_status(err), std::string("frame_from_device: ") + hipGetErrorString(err)); }
   *out = f;
   return ORBFE_OK;
 }
@@ -614,7 +599,7 @@ extern "C" int orbfe_frame_set_featvec(orbfe_frame* f, const orbfe_featvec* fv) 
     err = hipMemcpyAsync(f->dindices, t_staging.h, nIdx * 4, hipMemcpyHostToDevice, ar->stream);
   }
   if (err == hipSuccess) err = hipStreamSynchronize(ar->stream);  // (the handle may be in use on other streams afterwards)
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("frame_set_featvec: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(hip_status(err), std::string("frame_set_featvec: ") + hipGetErrorString(err));
   frames_settle();
   return ORBFE_OK;
 }
@@ -624,7 +609,7 @@ extern "C" int orbfe_frame_synchronize(const orbfe_frame* f) {
   if (f->settled.load(std::memory_order_acquire)) return ORBFE_OK;
   hipError_t err = hipSetDevice(f->device);
   if (err == hipSuccess) err = hipEventSynchronize(f->ready);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("frame_synchronize: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(hip_status(err), std::string("frame_synchronize: ") + hipGetErrorString(err));
   f->settled.store(true, std::memory_order_release);
   return ORBFE_OK;
 }
@@ -634,14 +619,14 @@ extern "C" int orbfe_debug_stall_thread_stream(int device, int usec) {
   if (usec < 0 || usec > 1000000) return fail(ORBFE_ERR_INVALID, "debug_stall: usec must be 0 .. 1000000");
   Arena* ar;
   hipError_t err = arena_begin(device, 0, &ar);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("debug_stall: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(hip_status(err), std::string("debug_stall: ") + hipGetErrorString(err));
   return orbfe_debug_stall_launch_(ar->stream, usec);
 }
 
 extern "C" int orbfe_debug_thread_stream_idle(int device) {
   Arena* ar;
   hipError_t err = arena_begin(device, 0, &ar);
-  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("debug_stream_idle: ") + hipGetErrorString(err));
+  if (err != hipSuccess) return fail(hip_status(err), std::string("debug_stream_idle: ") + hipGetErrorString(err));
   return orbfe_debug_stream_idle_(ar->stream);
 }
 

@@ -41,15 +41,15 @@ struct orbfe_vocabulary {
   int k = 0, L = 0, scoring = 0, weighting = 0;
   int nNodes = 0, nWords = 0;
   hipStream_t stream = nullptr;
+  DevBuf<VocabNode> nodes; DevBuf<double> weight;  // the tree; `d` is what the kernels take of it
   VocabDevice d = {};
   // grow-only scratch of the host-array entry point
-  uint8_t* d_desc = nullptr; uint32_t* d_word = nullptr; uint32_t* d_node = nullptr; double* d_weight = nullptr;
-  int scratchCap = 0;
+  DevBuf<uint8_t> d_desc; DevBuf<uint32_t> d_word, d_node; DevBuf<double> d_weight;
   // grow-only workspace of the batched device path
-  uint32_t* w_nodes = nullptr; int32_t* w_offsets = nullptr; uint32_t* w_indices = nullptr; int32_t* w_count = nullptr;
-  int8_t* w_bin = nullptr; unsigned long long* w_keys = nullptr;
-  unsigned long long* fk_keys = nullptr; size_t fkCap = 0;  // key scratch of orbfe_vocabulary_featvec_batch_device
+  DevBuf<uint32_t> w_nodes, w_indices; DevBuf<int32_t> w_offsets, w_count;
+  DevBuf<int8_t> w_bin; DevBuf<unsigned long long> w_keys;
   size_t wFrames = 0; int wCap = 0;
+  DevBuf<unsigned long long> fk_keys;  // key scratch of orbfe_vocabulary_featvec_batch_device
   hipStream_t lastStream = nullptr;  // stream of the last batched call (its workspace may still be in use there)
   hipEvent_t evFv[32] = {}, evBoundary[32] = {};  // per sub-batch: FeatureVectors built / boundary pair searched
   orbfe_extractor* lastMulti = nullptr;  // extractor whose sub-batch streams ran the last per-sub-batch call
@@ -250,20 +250,8 @@ void launch_vocab_featvec(hipStream_t s, const VocabDevice& v, const FeatVecBatc
 }
 }  // namespace orbfe
 
-static void vocab_free_device(orbfe_vocabulary* v) {
-  if (v->d.nodes) (void)hipFree((void*)v->d.nodes);
-  if (v->d.weight) (void)hipFree((void*)v->d.weight);
-  if (v->d_desc) (void)hipFree(v->d_desc);
-  if (v->d_word) (void)hipFree(v->d_word);
-  if (v->d_node) (void)hipFree(v->d_node);
-  if (v->d_weight) (void)hipFree(v->d_weight);
-  if (v->w_nodes) (void)hipFree(v->w_nodes);
-  if (v->w_offsets) (void)hipFree(v->w_offsets);
-  if (v->w_indices) (void)hipFree(v->w_indices);
-  if (v->w_count) (void)hipFree(v->w_count);
-  if (v->w_bin) (void)hipFree(v->w_bin);
-  if (v->w_keys) (void)hipFree(v->w_keys);
-  if (v->fk_keys) (void)hipFree(v->fk_keys);
+// the events and the stream of the handle (its buffers free themselves when it is deleted)
+static void vocab_destroy_sync_objects(orbfe_vocabulary* v) {
   for (int i = 0; i < 32; i++) {
     if (v->evFv[i]) (void)hipEventDestroy(v->evFv[i]);
     if (v->evBoundary[i]) (void)hipEventDestroy(v->evBoundary[i]);
@@ -313,21 +301,19 @@ static int vocab_upload(orbfe_vocabulary* v, const int32_t* parent, const uint8_
   }
   HIPCHK(hipSetDevice(v->device));
   HIPCHK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
-  VocabNode* dn; double* dwt;
-  HIPCHK(hipMalloc((void**)&dn, (size_t)n * sizeof(VocabNode)));
-  v->d.nodes = dn;
-  HIPCHK(hipMalloc((void**)&dwt, (size_t)n * 8));
-  v->d.weight = dwt;
+  int rc;
+  if ((rc = v->nodes.alloc((size_t)n)) || (rc = v->weight.alloc((size_t)n))) return rc;
+  v->d.nodes = v->nodes; v->d.weight = v->weight;
   v->d.rootChildren = (uint32_t)(off[1] - off[0]);
-  HIPCHK(hipMemcpy(dn, rec.data(), (size_t)n * sizeof(VocabNode), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dwt, wpos.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(v->nodes, rec.data(), (size_t)n * sizeof(VocabNode), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(v->weight, wpos.data(), (size_t)n * 8, hipMemcpyHostToDevice));
   return ORBFE_OK;
 }
 
 static int vocab_finish(orbfe_vocabulary* v, const std::vector<int32_t>& parent, const std::vector<uint8_t>& desc,
                         const std::vector<double>& weight, const std::vector<int32_t>& wordId, orbfe_vocabulary** out) {
   int rc = vocab_upload(v, parent.data(), desc.data(), weight.data(), wordId.data());
-  if (rc) { vocab_free_device(v); delete v; return rc; }
+  if (rc) { vocab_destroy_sync_objects(v); delete v; return rc; }
   *out = v;
   return ORBFE_OK;
 }
@@ -428,7 +414,7 @@ extern "C" void orbfe_vocabulary_destroy(orbfe_vocabulary* v) {
   if (!v) return;
   (void)hipSetDevice(v->device);
   if (v->stream) (void)hipStreamSynchronize(v->stream);
-  vocab_free_device(v);
+  vocab_destroy_sync_objects(v);
   delete v;
 }
 
@@ -447,17 +433,13 @@ extern "C" int orbfe_vocabulary_transform(orbfe_vocabulary* v, const uint8_t* de
     return fail(ORBFE_ERR_INVALID, "vocabulary_transform: bad argument");
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(v->device));
-  if (n > v->scratchCap) {
+  const size_t N = (size_t)n, grown = N + N / 2 + 256;
+  if (N * 32 > v->d_desc.cap || N > v->d_word.cap || N > v->d_node.cap || N > v->d_weight.cap) {
     HIPCHK(hipStreamSynchronize(v->stream));
-    if (v->d_desc) { (void)hipFree(v->d_desc); (void)hipFree(v->d_word); (void)hipFree(v->d_node); (void)hipFree(v->d_weight); }
-    v->d_desc = nullptr; v->d_word = nullptr; v->d_node = nullptr; v->d_weight = nullptr;
-    v->scratchCap = 0;
-    const int cap = n + n / 2 + 256;
-    HIPCHK(hipMalloc((void**)&v->d_desc, (size_t)cap * 32));
-    HIPCHK(hipMalloc((void**)&v->d_word, (size_t)cap * 4));
-    HIPCHK(hipMalloc((void**)&v->d_node, (size_t)cap * 4));
-    HIPCHK(hipMalloc((void**)&v->d_weight, (size_t)cap * 8));
-    v->scratchCap = cap;
+    int rc;
+    if ((rc = v->d_desc.reserve(N * 32, grown * 32)) || (rc = v->d_word.reserve(N, grown)) ||
+        (rc = v->d_node.reserve(N, grown)) || (rc = v->d_weight.reserve(N, grown)))
+      return rc;
   }
   HIPCHK(hipMemcpyAsync(v->d_desc, descriptors, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
   launch_vocab_transform(v->stream, v->d, v->d_desc, nullptr, n, n, 1, 1, v->L - levelsup, v->d_word, v->d_weight, v->d_node,
@@ -514,19 +496,16 @@ extern "C" int orbfe_vocabulary_transform_bow(orbfe_vocabulary* v, const uint8_t
   return ORBFE_OK;
 }
 
+// the six workspace arrays hold wFrames frames of wCap features; a call that exceeds either gets arrays of exactly its size
 static int ensure_bow_workspace(orbfe_vocabulary* v, int nFrames, int capacity) {
   if ((size_t)nFrames <= v->wFrames && capacity <= v->wCap) return ORBFE_OK;
   HIPCHK(hipStreamSynchronize(v->stream));
-  if (v->w_nodes) { (void)hipFree(v->w_nodes); (void)hipFree(v->w_offsets); (void)hipFree(v->w_indices); (void)hipFree(v->w_count); (void)hipFree(v->w_bin); (void)hipFree(v->w_keys); }
-  v->w_nodes = nullptr; v->w_offsets = nullptr; v->w_indices = nullptr; v->w_count = nullptr; v->w_bin = nullptr; v->w_keys = nullptr;
   v->wFrames = 0; v->wCap = 0;
   const size_t F = (size_t)nFrames, c = (size_t)capacity;
-  HIPCHK(hipMalloc((void**)&v->w_nodes, F * c * 4));
-  HIPCHK(hipMalloc((void**)&v->w_offsets, F * (c + 1) * 4));
-  HIPCHK(hipMalloc((void**)&v->w_indices, F * c * 4));
-  HIPCHK(hipMalloc((void**)&v->w_count, F * 4));
-  HIPCHK(hipMalloc((void**)&v->w_bin, F * c));
-  HIPCHK(hipMalloc((void**)&v->w_keys, F * c * 8));
+  int rc;
+  if ((rc = v->w_nodes.alloc(F * c)) || (rc = v->w_offsets.alloc(F * (c + 1))) || (rc = v->w_indices.alloc(F * c)) ||
+      (rc = v->w_count.alloc(F)) || (rc = v->w_bin.alloc(F * c)) || (rc = v->w_keys.alloc(F * c)))
+    return rc;
   v->wFrames = F;
   v->wCap = capacity;
   return ORBFE_OK;
@@ -552,12 +531,10 @@ extern "C" int orbfe_vocabulary_featvec_batch_device(orbfe_vocabulary* v, const 
   b.word = d_word; b.weight = d_weight;
   b.fvNodes = d_fv_nodes; b.fvOffsets = d_fv_offsets; b.fvIndices = d_fv_indices; b.fvCount = d_fv_count;
   const size_t need = (size_t)n_frames * capacity;
-  if (need > v->fkCap) {
+  if (need > v->fk_keys.cap) {
     HIPCHK(hipStreamSynchronize(v->stream));
-    if (v->fk_keys) (void)hipFree(v->fk_keys);
-    v->fk_keys = nullptr; v->fkCap = 0;
-    HIPCHK(hipMalloc((void**)&v->fk_keys, need * 8));
-    v->fkCap = need;
+    int rc;
+    if ((rc = v->fk_keys.reserve(need, need))) return rc;
   }
   b.keys = v->fk_keys;
   if ((size_t)sortN * 8 > 64 * 1024) {

@@ -400,3 +400,49 @@ def test_loop_candidates_through_the_wrapper(amd, world):
         assert not set(got) & set(con)
         some += len(got) > 0
     assert some
+
+
+def test_a_slab_that_changes_owner_carries_nothing_with_it(amd):
+    """The database's arrays and the resident frames' slabs come from ONE pool: a destroyed database's slabs (doubled past
+    64 KiB: 100 key frames x ~200 words) go to the next frame uploads, the released frames' slabs to the next database, and
+    neither sees what the other left in them."""
+    bows = [b for b in kw.random_bows(5, 200, max_words=400) if len(b[0]) >= 100][:100]
+    assert len(bows) == 100 and sum(len(w) for w, _ in bows) * 8 > 2 * 65536
+    ids = [7 * i + 3 for i in range(len(bows))]
+    queries = [b for b in kw.random_bows(6, 16, max_words=400) if len(b[0])]
+
+    def build_and_query():
+        db, rdb = _fill(amd, 10 ** 6, ids, bows)
+        got = db.query(queries)
+        for g, q in zip(got, queries):
+            _same(g, rdb.scored(q, ())[0])
+        del db  # orbfe_kfdb_destroy: its slabs go back to the pool
+        return got
+
+    A = build_and_query()
+    assert max(len(g[0]) for g in A) > 10
+    rng = np.random.default_rng(21)
+    base = rng.integers(0, 256, size=(500, 32), dtype=np.uint8)
+    views, fvs, frames = [], [], []
+    for f in range(8):
+        n = 500 - 7 * f
+        desc = (base ^ (rng.integers(0, 256, base.shape, dtype=np.uint8) & rng.integers(0, 256, base.shape, dtype=np.uint8)
+                        & rng.integers(0, 256, base.shape, dtype=np.uint8) & rng.integers(0, 256, base.shape, dtype=np.uint8)))[:n]
+        x, y = rng.uniform(1, 639, n).astype(np.float32), rng.uniform(1, 479, n).astype(np.float32)
+        angle = (np.linspace(5, 355, 500)[:n] + rng.uniform(-2, 2, n)).astype(np.float32)
+        views.append((desc, angle, amd.FrameView(x, y, rng.integers(0, 8, n).astype(np.int32), desc, (0.0, 640.0, 0.0, 480.0), angle=angle)))
+        fvs.append(amd.FeatureVector.from_node_of_feature((base[:n, 0].astype(np.uint32) % 40) * 5 + 1))
+        frames.append(views[-1][2].upload(fvs[-1]))
+    m = amd.ORBmatcher(0.7, True)
+    for f in range(8):
+        g = (f + 1) % 8
+        has = np.ones(len(views[f][0]), np.uint8)
+        rn, r = m.SearchByBoW(views[f][0], has, views[f][1], fvs[f], views[g][0], views[g][1], fvs[g])
+        gn, got = m.SearchByBoWResident(frames[f], has, frames[g])
+        assert gn == rn and np.array_equal(got, r), f
+        assert rn > 50
+    for fr in frames:
+        fr.close()
+    B = build_and_query()
+    for a, b in zip(A, B):
+        assert a[0].tolist() == b[0].tolist() and a[1].tolist() == b[1].tolist() and _bits32(a[2]) == _bits32(b[2])

@@ -340,3 +340,75 @@ def test_gpu_vocabulary_short_lines_do_not_shift_later_nodes(tmp_path):
         word, weight, node = voc.transform_features(desc, levelsup)
         _, w_ref, wt_ref, n_ref = va.transform(desc, levelsup)
         assert np.array_equal(word, w_ref) and np.array_equal(weight, wt_ref) and np.array_equal(node, n_ref)
+
+
+@pytest.mark.gpu
+def test_gpu_one_handle_regrows_its_buffers_like_fresh_handles(tmp_path):
+    """The grow-only buffers of a handle -- transform scratch (40 + 20 + 256 elements first, so 700 replaces it), the key
+    scratch of featvec_batch_device, the workspace of bow_match_consecutive_batch_device -- are replaced by larger calls
+    and reused by smaller ones: every call on ONE handle equals the same call on a fresh handle, element for element."""
+    torch = pytest.importorskip("torch")
+    import orb_slam2_annotate_amd as amd
+    path = tmp_path / "voc.txt"
+    write_synthetic_vocabulary(path, k=4, L=3, seed=6)
+    vo = orc.Vocabulary(path)
+
+    def handle():
+        v = amd.ORBVocabulary()
+        assert v.loadFromTextFile(path)
+        return v
+
+    one = handle()
+    rng = np.random.default_rng(12)
+    dev = torch.device("cuda", 0)
+
+    for n in (40, 700, 40):
+        desc = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+        got, fresh = one.transform_features(desc, 1), handle().transform_features(desc, 1)
+        assert all(np.array_equal(a, b) for a, b in zip(got, fresh)), n
+        if n == 700:
+            _, w_ref, wt_ref, n_ref = vo.transform(desc, 1)
+            assert np.array_equal(got[0], w_ref) and np.array_equal(got[1], wt_ref) and np.array_equal(got[2], n_ref)
+
+    def batch(F, cap):
+        """F frames that resemble their predecessor (so consecutive frames match), counts below, at and near the capacity"""
+        desc = np.zeros((F, cap, 32), np.uint8)
+        desc[0] = rng.integers(0, 256, size=(cap, 32), dtype=np.uint8)
+        for f in range(1, F):
+            flip = np.full((cap, 32), 255, np.uint8)
+            for _ in range(5):  # about 8 of the 256 bits change
+                flip &= rng.integers(0, 256, (cap, 32), dtype=np.uint8)
+            desc[f] = desc[f - 1] ^ flip
+        kp = np.zeros((F, cap, 7), np.float32)
+        kp[..., 3] = rng.uniform(5, 355, size=(1, cap)) + rng.uniform(-3, 3, size=(F, cap))
+        n = rng.integers(cap // 2, cap + 1, size=F).astype(np.int32)
+        n[0] = cap
+        return torch.from_numpy(desc).to(dev), torch.from_numpy(kp).to(dev), torch.from_numpy(n).to(dev)
+
+    def featvec(v, d_desc, d_n, F, cap):
+        out = [torch.zeros((F, cap), dtype=torch.int32, device=dev), torch.zeros((F, cap + 1), dtype=torch.int32, device=dev),
+               torch.zeros((F, cap), dtype=torch.int32, device=dev), torch.zeros((F,), dtype=torch.int32, device=dev)]
+        torch.cuda.synchronize()
+        v.featvec_batch_device(d_desc.data_ptr(), d_n.data_ptr(), F, cap, *[t.data_ptr() for t in out], levelsup=1)
+        return [t.cpu().numpy() for t in out]
+
+    for F, cap in ((2, 64), (5, 128)):
+        d_desc, _, d_n = batch(F, cap)
+        got, fresh = featvec(one, d_desc, d_n, F, cap), featvec(handle(), d_desc, d_n, F, cap)
+        assert all(np.array_equal(a, b) for a, b in zip(got, fresh)), (F, cap)
+        assert got[3].min() > 0
+
+    def match(v, d_desc, d_kp, d_n, F, cap):
+        d_match = torch.zeros((F - 1, cap), dtype=torch.int32, device=dev)
+        d_nm = torch.zeros((F - 1,), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        v.bow_match_consecutive_batch_device(F, d_kp.data_ptr(), d_desc.data_ptr(), d_n.data_ptr(), cap, d_match.data_ptr(),
+                                             d_nm.data_ptr(), nnratio=0.7, check_orientation=True, levelsup=1)
+        return d_match.cpu().numpy(), d_nm.cpu().numpy()
+
+    # (the last two: more frames at a smaller capacity replaces the workspace too, and the one after reuses it)
+    for F, cap in ((3, 128), (6, 256), (3, 128), (8, 64), (6, 64)):
+        d_desc, d_kp, d_n = batch(F, cap)
+        got, fresh = match(one, d_desc, d_kp, d_n, F, cap), match(handle(), d_desc, d_kp, d_n, F, cap)
+        assert np.array_equal(got[0], fresh[0]) and np.array_equal(got[1], fresh[1]), (F, cap)
+        assert got[1].min() > 0, got[1]  # (the pairs do match: the comparison is not of two empty results)
