@@ -6,8 +6,10 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg as the CHECKER.
  * Nothing under orb_slam2_annotate_amd/ may include, link or call this.
  *
- * PARITY UNPINNED: the reference ships no tests, no golden vectors and cannot be
- * built here (OpenCV/Eigen absent, version unpinned; see DESIGN.md "Oracle").
+ * PARITY UNPINNED at the OpenCV boundary: the reference ships no tests and no golden
+ * vectors, and OpenCV/Eigen are absent (version unpinned; see DESIGN.md "Oracle").
+ * src/ORBextractor.cc itself is built against an OpenCV double and compared with
+ * this file bit for bit (orbextractor_ref_shim.cpp, tests/test_orbextractor_ref.py).
  * The pixel primitives that live in OpenCV (resize, FAST, GaussianBlur,
  * fastAtan2, cvRound) are restated from their published algorithm as the
  * "canonical spec" frozen in SURVEY.md section 8(c); cos/sin is this project's

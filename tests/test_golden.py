@@ -1,5 +1,6 @@
 """Golden-vector tests.  tests/golden/*.npz are regression pins produced by tools/gen_golden.py
-from the CPU oracle (the reference has no vectors of its own and is unbuildable here): the CPU
+from the CPU oracle (the reference has no vectors of its own; what its own extractor source returns is pinned
+separately, tests/test_orbextractor_ref.py): the CPU
 tests re-run the oracle against them, the GPU tests run the HIP path through the C-ABI."""
 from pathlib import Path
 

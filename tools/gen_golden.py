@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.npz -- small input/output vectors of the hot path.
 
-The reference ships no tests/golden vectors and cannot be built here (OpenCV/Eigen absent), so
-these vectors are produced by the CPU oracle (oracle/orb_oracle.c) and act as REGRESSION PINS of
+The reference ships no tests/golden vectors and OpenCV/Eigen are absent (tools/gen_ref_golden.py records what its
+extractor source returns over an OpenCV double), so these vectors are produced by the CPU oracle (oracle/orb_oracle.c) and act as REGRESSION PINS of
 the frozen canonical spec, not as reference-derived truth ("parity unpinned").  The
 fixtures hold data only: input images (synthetic, seeded) and expected outputs.
 """

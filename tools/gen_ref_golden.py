@@ -3,13 +3,17 @@
 
   tests/golden/dbow2_ref.npz              what the reference's DBoW2 FeatureVector / BowVector return for every input
                                           tests/test_dbow2_ref.py hands them (tests/ref_lib.py looks results up by input)
+  tests/golden/orbextractor_ref.npz       what the reference's src/ORBextractor.cc (built untouched against the OpenCV
+                                          double oracle/ref_cv/) returns for ref_lib.CASES and ref_lib.octree_sets():
+                                          records and descriptors up to ~300 keypoints, else per-level counts and
+                                          SHA-256 digests; digests of the pyramid levels and of every input; the tables
   tests/golden/orbmatcher_ref_methods.json the public methods of the reference's include/ORBmatcher.h, as
                                           tests/test_dropin_headers.py normalises them
 
     python tools/gen_ref_golden.py <reference tree>
 
-The two DBoW2 sources are compiled in place into oracle/_ref/libdbow2_ref.so (`make -C oracle ref`); nothing of the
-tree is copied.  The GPU test's inputs are the oracle's (bit-identical to the device extractor and vocabulary)."""
+The DBoW2 sources and the extractor are compiled in place into oracle/_ref/ (`make -C oracle ref`); nothing of the
+tree is copied, and the recordings hold results only.  The GPU test's inputs are the oracle's (bit-identical to the device extractor and vocabulary)."""
 import json
 import subprocess
 import sys
@@ -45,8 +49,20 @@ def gpu_test_inputs(tmp):
         ref_lib.featvec(vo.transform(desc, 1)[3])
 
 
+def record_extractor():
+    """The reference build on every case (ref_lib refuses a case outside the reference's domain) and candidate set."""
+    rec = {}
+    for name in ref_lib.CASE_NAMES:
+        kps, desc, levels, _ = ref_lib.ref_extract(name)
+        rec.update(ref_lib.case_record(name, kps, desc, levels, ref_lib.ref_tables(ref_lib.case(name)[5])))
+    rec.update(ref_lib.octree_record([ref_lib.ref_octree(*s[1:]) for s in ref_lib.octree_sets()]))
+    np.savez_compressed(ref_lib.GOLDEN_X, **rec)
+    print(ref_lib.GOLDEN_X, len(rec), "arrays", ref_lib.GOLDEN_X.stat().st_size, "bytes")
+
+
 def main():
     ref = Path(sys.argv[1]).resolve()
+    ref_lib.REF_TREE = ref
     subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref", f"REF={ref}"], check=True)
     ref_lib.recording = {}
     with tempfile.TemporaryDirectory() as d:
@@ -57,6 +73,7 @@ def main():
         gpu_test_inputs(tmp)
     np.savez_compressed(ref_lib.GOLDEN, **ref_lib.recording)
     print(ref_lib.GOLDEN, len(ref_lib.recording), "arrays")
+    record_extractor()
     methods = sorted(test_dropin_headers._methods((ref / "include" / "ORBmatcher.h").read_text(errors="replace")))
     test_dropin_headers.REF_METHODS.write_text(json.dumps(methods, indent=1) + "\n")
     print(test_dropin_headers.REF_METHODS, len(methods), "methods")
