@@ -603,6 +603,68 @@ int orbfe_search_by_projection(int device, const orbfe_frame_view *F, const floa
                                const uint8_t *mp_obs_positive, float th, float nnratio,
                                int32_t *match, int32_t *n_matches);
 
+/* ------------------------------------------------------------------------- */
+/* Device-resident map points: Frame::isInFrustum + Tracking::SearchLocalPoints */
+/* ------------------------------------------------------------------------- */
+/* What isInFrustum and SearchByProjection read of a MapPoint (mWorldPos, mNormalVector, mfMinDistance, mfMaxDistance,
+ * mDescriptor, isBad(), Observations() > 0), resident on the device and indexed by SLOT: the caller keeps the
+ * MapPoint* <-> slot map, as it keeps the ids of the key-frame database.  The local map hardly changes between
+ * consecutive frames, so per frame only a slot list, the masks and the pose travel.  Creating a table does not touch
+ * the device (the first update or use does); a slot that was never updated counts as bad.  A handle serialises its own
+ * calls. */
+typedef struct orbfe_mappoints orbfe_mappoints;
+#define ORBFE_MP_BAD 1          /* flags bit 0: MapPoint::isBad() */
+#define ORBFE_MP_OBSERVED 2     /* flags bit 1: MapPoint::Observations() > 0 */
+int orbfe_mappoints_create(int device, int capacity, orbfe_mappoints **out);
+void orbfe_mappoints_destroy(orbfe_mappoints *mp);
+int orbfe_mappoints_capacity(const orbfe_mappoints *mp);
+/* Writes n slots: pos = GetWorldPos(), normal = GetNormal() (3 floats each), min_dist / max_dist the RAW mfMinDistance /
+ * mfMaxDistance (the 0.8f / 1.2f of GetMinDistanceInvariance / GetMaxDistanceInvariance, src/MapPoint.cc, are applied
+ * on the device), desc = GetDescriptor() (32 bytes each; NULL keeps the descriptors the slots hold), flags as above.
+ * Slots outside [0, capacity), n < 0 and NULL arrays return ORBFE_ERR_INVALID before anything is enqueued; a slot named
+ * twice in one call takes either entry.  Enqueued on the calling thread's matcher stream and complete on return, so
+ * the table may be used from any thread afterwards. */
+int orbfe_mappoints_update(orbfe_mappoints *mp, int n, const int32_t *slot, const float *pos, const float *normal,
+                           const float *min_dist, const float *max_dist, const uint8_t *desc, const uint8_t *flags);
+
+/* The fields of the Frame isInFrustum reads (src/Frame.cc:292-353): mRcw (row-major), mtcw, mOw, fx, fy, cx, cy, mbf,
+ * mnMinX .. mnMaxY, mfLogScaleFactor, mnScaleLevels. */
+typedef struct orbfe_camera_pose {
+  float Rcw[9], tcw[3], Ow[3];
+  float fx, fy, cx, cy, mbf;
+  float min_x, max_x, min_y, max_y;
+  float log_scale_factor;
+  int32_t n_levels;
+} orbfe_camera_pose;
+
+/* Frame::isInFrustum(pMP, viewingCosLimit) (src/Frame.cc:292-353) with MapPoint::PredictScale for the n map points in
+ * slot[]; skip[i] != 0 (NULL = none) leaves point i out, as the points already matched in the frame are
+ * (mnLastFrameSeen, src/Tracking.cc SearchLocalPoints).  in_view[i] = !skip && !bad && every test passes; where it is
+ * set, level / view_cos / proj_x / proj_y / proj_xr are mnTrackScaleLevel / mTrackViewCos / mTrackProjX / Y / XR and
+ * inv_z / dist the 1/z and the distance to the camera centre behind them; elsewhere they are 0.  IEEE binary32, no
+ * contraction, sums left to right:
+ *   xc = ((R00*X + R01*Y) + R02*Z) + t0 (yc, zc likewise); reject zc < 0; invz = 1/zc; u = (fx*xc)*invz + cx;
+ *   v = (fy*yc)*invz + cy; reject u < min_x || u > max_x || v < min_y || v > max_y; PO = P - Ow;
+ *   dist = (float)sqrt(sum (double)PO_i^2); reject dist < 0.8f*min || dist > 1.2f*max;
+ *   view_cos = (float)(sum (double)PO_i*(double)Pn_i / (double)dist); reject view_cos < limit;
+ *   level = clamp(ceil(log((double)(max/dist)) / (double)log_scale_factor), 0, n_levels-1); proj_xr = u - mbf*invz.
+ * Only the slot list, the mask and the pose go up.  Any output may be NULL. */
+int orbfe_project_in_frustum(orbfe_mappoints *mp, int n, const int32_t *slot, const uint8_t *skip,
+                             const orbfe_camera_pose *pose, float viewing_cos_limit, uint8_t *in_view, int32_t *level,
+                             float *view_cos, float *proj_x, float *proj_y, float *proj_xr, float *inv_z, float *dist);
+
+/* Tracking::SearchLocalPoints (src/Tracking.cc) as ONE call: the projection above writes the query windows of
+ * orbfe_search_by_projection (RadiusByViewingCos(view_cos) * th * scale_factors[level], levels [level-1, level], the
+ * points' descriptors gathered from the table) directly in device memory, and the window search and the claim loop run
+ * behind it on the same stream.  match[idx] = position in slot[] of the point assigned to frame feature idx, or -1;
+ * *n_matches as the reference counts them; in_view (optional, n bytes) for IncreaseVisible.  Equal to
+ * orbfe_search_by_projection fed with orbfe_project_in_frustum's outputs, the table's descriptors and
+ * mp_obs_positive = flags bit 1.  pose->n_levels must not exceed n_levels. */
+int orbfe_search_local_points(orbfe_mappoints *mp, int n, const int32_t *slot, const uint8_t *skip,
+                              const orbfe_camera_pose *pose, float viewing_cos_limit, const orbfe_frame_view *F,
+                              const float *scale_factors, int n_levels, const uint8_t *blocked, float th, float nnratio,
+                              int32_t *match, int32_t *n_matches, uint8_t *in_view);
+
 /* The FeatureVector searches on resident frames (uploaded WITH their FeatureVector and angles): per call only the
  * shared-node list, the MapPoint masks and the result travel.  Semantics and outputs of orbfe_search_by_bow /
  * orbfe_search_by_bow_kf. */

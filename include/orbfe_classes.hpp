@@ -549,6 +549,69 @@ class ORBmatcher {
   int device_;
 };
 
+// The map points Tracking::SearchLocalPoints reads, resident on the device (orbfe_mappoints): slot <-> MapPoint* is the
+// caller's map, as the key-frame ids of the KeyFrameDatabase are.
+class MapPointTable {
+ public:
+  // what Frame::isInFrustum leaves on the MapPoints, as arrays over the slot list
+  struct Projection {
+    std::vector<uint8_t> mbTrackInView;
+    std::vector<int32_t> mnTrackScaleLevel;
+    std::vector<float> mTrackViewCos, mTrackProjX, mTrackProjY, mTrackProjXR, invZ, dist;
+  };
+  explicit MapPointTable(int capacity, int device = 0) { check(orbfe_mappoints_create(device, capacity, &h_), "MapPointTable"); }
+  ~MapPointTable() { orbfe_mappoints_destroy(h_); }
+  MapPointTable(const MapPointTable&) = delete;
+  MapPointTable& operator=(const MapPointTable&) = delete;
+  int capacity() const { return orbfe_mappoints_capacity(h_); }
+  // pos / normal: 3 floats per slot; desc: 32 bytes per slot, or empty to keep the descriptors; flags: ORBFE_MP_BAD | ORBFE_MP_OBSERVED
+  void update(const std::vector<int32_t>& slot, const std::vector<float>& pos, const std::vector<float>& normal,
+              const std::vector<float>& minDist, const std::vector<float>& maxDist, const std::vector<uint8_t>& desc,
+              const std::vector<uint8_t>& flags) {
+    const size_t n = slot.size();
+    if (pos.size() != 3 * n || normal.size() != 3 * n || minDist.size() != n || maxDist.size() != n || flags.size() != n ||
+        (!desc.empty() && desc.size() != 32 * n))
+      throw std::invalid_argument("MapPointTable::update: one entry per slot");
+    check(orbfe_mappoints_update(h_, (int)n, slot.data(), pos.data(), normal.data(), minDist.data(), maxDist.data(),
+                                 desc.empty() ? nullptr : desc.data(), flags.data()), "MapPointTable::update");
+  }
+  // Frame::isInFrustum(pMP, viewingCosLimit) for every slot; skip: empty, or one byte per slot
+  Projection ProjectInFrustum(const std::vector<int32_t>& slot, const orbfe_camera_pose& pose, float viewingCosLimit = 0.5f,
+                              const std::vector<uint8_t>& skip = {}) const {
+    const size_t n = slot.size();
+    if (!skip.empty() && skip.size() != n) throw std::invalid_argument("MapPointTable::ProjectInFrustum: one skip entry per slot");
+    Projection p;
+    p.mbTrackInView.assign(n, 0); p.mnTrackScaleLevel.assign(n, 0);
+    p.mTrackViewCos.assign(n, 0); p.mTrackProjX.assign(n, 0); p.mTrackProjY.assign(n, 0); p.mTrackProjXR.assign(n, 0);
+    p.invZ.assign(n, 0); p.dist.assign(n, 0);
+    check(orbfe_project_in_frustum(h_, (int)n, slot.data(), skip.empty() ? nullptr : skip.data(), &pose, viewingCosLimit,
+                                   p.mbTrackInView.data(), p.mnTrackScaleLevel.data(), p.mTrackViewCos.data(), p.mTrackProjX.data(),
+                                   p.mTrackProjY.data(), p.mTrackProjXR.data(), p.invZ.data(), p.dist.data()), "ProjectInFrustum");
+    return p;
+  }
+  // Tracking::SearchLocalPoints: isInFrustum + SearchByProjection(F, points, th) in one call.  match[idx] = position in `slot`
+  // of the point given to keypoint idx, or -1; inView (may be NULL) for IncreaseVisible.  Returns nmatches.
+  int SearchLocalPoints(const FrameArrays& F, const std::vector<int32_t>& slot, const orbfe_camera_pose& pose,
+                        const std::vector<float>& mvScaleFactors, float th, float nnratio, std::vector<int32_t>& match,
+                        std::vector<uint8_t>* inView = nullptr, float viewingCosLimit = 0.5f, const std::vector<uint8_t>& skip = {},
+                        const std::vector<uint8_t>& blocked = {}) const {
+    const size_t n = slot.size();
+    if (!skip.empty() && skip.size() != n) throw std::invalid_argument("MapPointTable::SearchLocalPoints: one skip entry per slot");
+    if (!blocked.empty() && blocked.size() != (size_t)F.c.n) throw std::invalid_argument("MapPointTable::SearchLocalPoints: one blocked entry per keypoint");
+    match.assign((size_t)F.c.n, -1);
+    if (inView) inView->assign(n, 0);
+    int32_t nmatches = 0;
+    check(orbfe_search_local_points(h_, (int)n, slot.data(), skip.empty() ? nullptr : skip.data(), &pose, viewingCosLimit, &F.c,
+                                    mvScaleFactors.data(), (int)mvScaleFactors.size(), blocked.empty() ? nullptr : blocked.data(), th,
+                                    nnratio, match.data(), &nmatches, inView ? inView->data() : nullptr), "SearchLocalPoints");
+    return nmatches;
+  }
+  orbfe_mappoints* handle() const { return h_; }
+
+ private:
+  orbfe_mappoints* h_ = nullptr;
+};
+
 // void Frame::ComputeStereoMatches(): fills mvuRight / mvDepth
 inline int ComputeStereoMatches(ORBextractor& left, ORBextractor& right, const std::vector<KeyPoint>& kL,
                                 const std::vector<uint8_t>& dL, const std::vector<KeyPoint>& kR,

@@ -39,6 +39,14 @@ class FrameViewC(C.Structure):
                 ("resident", C.c_void_p)]
 
 
+class CameraPoseC(C.Structure):
+    """orbfe_camera_pose: what Frame::isInFrustum reads of the Frame (src/Frame.cc:292-353)."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mbf", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
+
+
 class FeatVecC(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_ids", C.c_void_p), ("offsets", C.c_void_p),
                 ("indices", C.c_void_p)]
@@ -69,6 +77,8 @@ EXPORTS = [
     "orbfe_debug_stall_thread_stream", "orbfe_debug_thread_stream_idle",
     "orbfe_vocabulary_transform_bow", "orbfe_kfdb_create", "orbfe_kfdb_destroy", "orbfe_kfdb_add", "orbfe_kfdb_erase",
     "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_query", "orbfe_kfdb_score", "orbfe_kfdb_group_candidates",
+    "orbfe_mappoints_create", "orbfe_mappoints_destroy", "orbfe_mappoints_capacity", "orbfe_mappoints_update",
+    "orbfe_project_in_frustum", "orbfe_search_local_points",
 ]
 
 _lib = None
@@ -228,6 +238,14 @@ def load():
     L.orbfe_kfdb_query.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
     L.orbfe_kfdb_score.argtypes = [vp, vp, vp, ci, ci, vp, vp]
     L.orbfe_kfdb_group_candidates.argtypes = [ci, cf, ci, vp, vp, vp, vp, vp, vp, ci, vp]
+    cpp = C.POINTER(CameraPoseC)
+    L.orbfe_mappoints_create.argtypes = [ci, ci, C.POINTER(C.c_void_p)]
+    L.orbfe_mappoints_destroy.argtypes = [vp]
+    L.orbfe_mappoints_destroy.restype = None
+    L.orbfe_mappoints_capacity.argtypes = [vp]
+    L.orbfe_mappoints_update.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_project_in_frustum.argtypes = [vp, ci, vp, vp, cpp, cf, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_search_local_points.argtypes = [vp, ci, vp, vp, cpp, cf, fwp, vp, ci, vp, cf, cf, vp, vp, vp]
     _lib = L
     return L
 

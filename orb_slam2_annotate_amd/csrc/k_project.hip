@@ -1,0 +1,129 @@
+// k_project.hip -- the pose arithmetic in front of Tracking::SearchLocalPoints on the device-resident map points:
+// Frame::isInFrustum (src/Frame.cc:292-353) with MapPoint::PredictScale, and the scatter that keeps the table up to date.
+// Both kernels are bandwidth-trivial (64 bytes of table per point, a few thousand points): one lane per point, the table
+// records as 16-byte loads, the descriptor rows moved by the whole workgroup as 16-byte pieces.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "match_kernels.h"
+
+namespace orbfe {
+
+namespace {
+
+constexpr int kProjectThreads = 256;
+
+// Every operation is written with the round-to-nearest intrinsics, in the order include/orbfe.h states: no contraction, no
+// reassociation, whatever flags the file is built with.
+__global__ __launch_bounds__(kProjectThreads) void k_project_frustum(const ProjectArgs a) {
+  const int base = blockIdx.x * kProjectThreads;
+  const int i = base + (int)threadIdx.x;
+  if (i < a.n) {
+    const int s = a.slot[i];
+    const float4 r0 = a.table.rec[2 * (size_t)s], r1 = a.table.rec[2 * (size_t)s + 1];
+    const uint8_t fl = a.table.flags[s];
+    const orbfe_camera_pose& c = a.cam;
+    const float X = r0.x, Y = r0.y, Z = r0.z, minD = r0.w, maxD = r1.w;
+    bool ok = !(fl & ORBFE_MP_BAD) && !(a.skip && a.skip[i]);
+    // 3D in camera coordinates (:305-309); the depth must be positive (:311-313)
+    const float xc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[0], X), __fmul_rn(c.Rcw[1], Y)), __fmul_rn(c.Rcw[2], Z)), c.tcw[0]);
+    const float yc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[3], X), __fmul_rn(c.Rcw[4], Y)), __fmul_rn(c.Rcw[5], Z)), c.tcw[1]);
+    const float zc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[6], X), __fmul_rn(c.Rcw[7], Y)), __fmul_rn(c.Rcw[8], Z)), c.tcw[2]);
+    if (zc < 0.0f) ok = false;
+    // projection inside the image (:315-323)
+    const float invz = __fdiv_rn(1.0f, zc);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, xc), invz), c.cx);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, yc), invz), c.cy);
+    if (u < c.min_x || u > c.max_x) ok = false;
+    if (v < c.min_y || v > c.max_y) ok = false;
+    // distance inside the scale invariance region of the point (:325-332): cv::norm accumulates in double
+    const float px = __fsub_rn(X, c.Ow[0]), py = __fsub_rn(Y, c.Ow[1]), pz = __fsub_rn(Z, c.Ow[2]);
+    const double dpx = (double)px, dpy = (double)py, dpz = (double)pz;
+    const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dpx, dpx), __dmul_rn(dpy, dpy)), __dmul_rn(dpz, dpz));
+    const float dist = (float)__dsqrt_rn(d2);
+    if (dist < __fmul_rn(0.8f, minD) || dist > __fmul_rn(1.2f, maxD)) ok = false;
+    // viewing angle (:334-340): Mat::dot accumulates in double
+    const double dot = __dadd_rn(__dadd_rn(__dmul_rn(dpx, (double)r1.x), __dmul_rn(dpy, (double)r1.y)), __dmul_rn(dpz, (double)r1.z));
+    const float viewCos = (float)__ddiv_rn(dot, (double)dist);
+    if (viewCos < a.limit) ok = false;
+    // MapPoint::PredictScale (:342-343)
+    int lv = 0;
+    if (ok) {
+      const float ratio = __fdiv_rn(maxD, dist);
+      const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
+      const int top = c.n_levels - 1;
+      lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
+    }
+    const float xr = __fsub_rn(u, __fmul_rn(c.mbf, invz));
+    if (a.inView) a.inView[i] = ok;
+    if (a.level) a.level[i] = lv;
+    if (a.viewCos) a.viewCos[i] = ok ? viewCos : 0.0f;
+    if (a.projX) a.projX[i] = ok ? u : 0.0f;
+    if (a.projY) a.projY[i] = ok ? v : 0.0f;
+    if (a.projXr) a.projXr[i] = ok ? xr : 0.0f;
+    if (a.invZ) a.invZ[i] = ok ? invz : 0.0f;
+    if (a.dist) a.dist[i] = ok ? dist : 0.0f;
+    if (a.qx) {
+      // the windows of SearchByProjection(Frame&, vector<MapPoint*>&, th): RadiusByViewingCos (src/ORBmatcher.cc:140-146,
+      // the compare in double), r *= th when th != 1.0 (:68-69), r * mvScaleFactors[level], levels [level - 1, level] (:71-73)
+      float r = (double)(ok ? viewCos : 0.0f) > 0.998 ? 2.5f : 4.0f;
+      if ((double)a.th != 1.0) r = __fmul_rn(r, a.th);
+      a.qx[i] = ok ? u : 0.0f;
+      a.qy[i] = ok ? v : 0.0f;
+      a.qr[i] = __fmul_rn(r, a.scale[lv]);
+      a.qmin[i] = lv - 1;
+      a.qmax[i] = lv;
+      a.qactive[i] = ok;
+      a.qobs[i] = (fl & ORBFE_MP_OBSERVED) ? 1 : 0;
+      if (a.qur) a.qur[i] = ok ? xr : 0.0f;
+      if (a.inViewCopy) a.inViewCopy[i] = ok;
+    }
+  }
+  if (a.qdesc) {  // (workgroup-uniform) the points' descriptors, gathered from the table: piece p = half (p & 1) of point base + p / 2
+    const int cnt = a.n - base < kProjectThreads ? a.n - base : kProjectThreads;
+    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
+    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
+    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
+      const int q = base + (p >> 1);
+      dst[2 * (size_t)q + (p & 1)] = src[2 * (size_t)a.slot[q] + (p & 1)];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kProjectThreads) void k_mappoints_scatter(const MapPointsDevice t, int n, const int32_t* __restrict__ slot,
+                                                                       const float4* __restrict__ rec, const uint8_t* __restrict__ flags,
+                                                                       const uint8_t* __restrict__ desc) {
+  const int base = blockIdx.x * kProjectThreads;
+  const int i = base + (int)threadIdx.x;
+  if (i < n) {
+    const int s = slot[i];
+    t.rec[2 * (size_t)s] = rec[2 * (size_t)i];
+    t.rec[2 * (size_t)s + 1] = rec[2 * (size_t)i + 1];
+    t.flags[s] = flags[i];
+  }
+  if (desc) {  // (uniform)
+    const int cnt = n - base < kProjectThreads ? n - base : kProjectThreads;
+    const uint4* src = reinterpret_cast<const uint4*>(desc);
+    uint4* dst = reinterpret_cast<uint4*>(t.desc);
+    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
+      const int q = base + (p >> 1);
+      dst[2 * (size_t)slot[q] + (p & 1)] = src[2 * (size_t)q + (p & 1)];
+    }
+  }
+}
+
+}  // namespace
+
+void launch_project_frustum(hipStream_t s, const ProjectArgs& a) {
+  if (a.n <= 0) return;
+  hipLaunchKernelGGL(k_project_frustum, dim3((a.n + kProjectThreads - 1) / kProjectThreads), dim3(kProjectThreads), 0, s, a);
+}
+
+void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,
+                              const uint8_t* flags, const uint8_t* desc) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_mappoints_scatter, dim3((n + kProjectThreads - 1) / kProjectThreads), dim3(kProjectThreads), 0, s, t, n, slot, rec,
+                     flags, desc);
+}
+
+}  // namespace orbfe

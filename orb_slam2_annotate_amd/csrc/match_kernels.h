@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/orbfe.h"
 #include "kernels.h"
 
 namespace orbfe {
@@ -145,6 +146,29 @@ struct WindowSearchJob {  // one job of k_window_search_multi; blockStart = firs
 void launch_window_search_multi(hipStream_t s, const WindowSearchJob* d_jobs, int nJobs, int totalBlocks);
 void launch_window_search(hipStream_t s, const GridFrame& f, const uint32_t* sortedKey, const int32_t* cellOff,
                           const WindowQueries& q, int32_t* count, uint32_t* cand);
+
+// Device map-point table (k_project.hip).  Slot s of the table: rec[2 s] = (X, Y, Z, mfMinDistance), rec[2 s + 1] = (nx, ny, nz,
+// mfMaxDistance), desc[32 s ..], flags[s] (ORBFE_MP_BAD | ORBFE_MP_OBSERVED).
+struct MapPointsDevice { float4* rec; uint8_t* desc; uint8_t* flags; };
+// k_project_frustum: Frame::isInFrustum + MapPoint::PredictScale (src/Frame.cc:292-353) for the n points slot[0 .. n), one
+// lane per point.  Two sets of outputs, either may be absent: the fields isInFrustum leaves on the MapPoint (every pointer may
+// be NULL), and -- qx != NULL -- the query windows of SearchByProjection(Frame&, vector<MapPoint*>&, th) exactly as
+// orbfe_search_by_projection builds them on the host (src/ORBmatcher.cc:51-76), with the points' descriptors gathered from
+// the table, so that k_window_search / k_window_claim run behind it without a host step.
+struct ProjectArgs {
+  MapPointsDevice table;
+  const int32_t* slot; const uint8_t* skip /* NULL: none */; int n;
+  orbfe_camera_pose cam; float limit;
+  uint8_t* inView; int32_t* level; float* viewCos; float* projX; float* projY; float* projXr; float* invZ; float* dist;
+  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive; float* qur /* NULL: monocular frame */;
+  uint8_t* qdesc; uint8_t* qobs /* Observations() > 0: does the point's match hide its feature */;
+  uint8_t* inViewCopy /* NULL, or a second copy of qactive next to the results that travel back */;
+  const float* scale; float th;
+};
+void launch_project_frustum(hipStream_t s, const ProjectArgs& a);
+// orbfe_mappoints_update: n staged entries (slot, the two records, flags, descriptors or NULL = keep) into their slots
+void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,
+                              const uint8_t* flags, const uint8_t* desc);
 
 void launch_search_by_bow(hipStream_t s, const BowArgs& a, int nPairs, int maxCnt2);
 void launch_search_by_bow_multi(hipStream_t s, const BowArgs* d_args, const int32_t* d_pairStart, int K, int nPairsTotal, int maxCnt2);

@@ -16,6 +16,7 @@
 #include "../../include/orbfe.h"
 #include "host_internal.h"
 #include "kernels.h"
+#include "mappoints_host.h"
 #include "match_kernels.h"
 
 using namespace orbfe;
@@ -1107,6 +1108,19 @@ struct WindowJob {
   // them (match_kernels.h: ClaimJob); the match array, the count and -- SearchForInitialization -- the updated previous
   // positions come back
   struct ClaimSpec* claim = nullptr;
+  // PRODUCER (claim jobs only): the query arrays above are NULL -- k_project_frustum writes them on the device, behind the
+  // call's one upload, from the map-point table; only the slot list, the skip mask and the scale factors travel
+  struct FrustumProducer* producer = nullptr;
+};
+struct FrustumProducer {
+  MapPointsDevice table;
+  const int32_t* slot;      // [nq]
+  const uint8_t* skip;      // [nq] or NULL
+  orbfe_camera_pose pose;
+  float limit = 0.0f, th = 1.0f;
+  const float* scale = nullptr;  // [nLevels] mvScaleFactors
+  int nLevels = 0;
+  uint8_t* inViewOut = nullptr;  // out [nq] or NULL
 };
 struct ClaimSpec {
   int mode = CLAIM_BEST, maxDist = 100, checkOri = 0;
@@ -1128,22 +1142,28 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
   UnsettledScope unsettledScope;
   t_lastClaimRounds = 0;
   int K = ((K0 < 8 ? 8 : K0) + 7) & ~7;  // (k_window_claim reads the lists eight entries at a time)
-  struct Lay { size_t oX, oY, oOct, oUr, oDesc, oQx, oQy, oQr, oQmin, oQmax, oQact, oQur, oQdesc, oOut, oGur, oSig, oAng, oBlk, oBval, oQang, oScr;
+  struct Lay { size_t oX, oY, oOct, oUr, oDesc, oQx, oQy, oQr, oQmin, oQmax, oQact, oQur, oQdesc, oOut, oGur, oSig, oAng, oBlk, oBval, oQang, oScr, oSlot, oSkip, oScale;
                bool withDesc, withUr, res; int frameOf; };
   std::vector<Lay> lay((size_t)nJobs);
-  size_t off = 0;
+  size_t off = 0, prodOff = 0;  // prodOff: the query arrays a producer writes, in a region of their own that is never uploaded
   int nClaim = 0;
   bool claimInit = false;
   auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  auto qplace = [&](bool produced, size_t bytes) {
+    if (!produced) return place(bytes);
+    const size_t o = prodOff; prodOff += (bytes + 255) & ~(size_t)255; return o;
+  };
   for (int j = 0; j < nJobs; j++) {
     const WindowJob& J = jobs[j];
     Lay& L = lay[j];
     const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
     L.res = J.f->resident != nullptr;
     if (L.res && J.f->resident->device != device) return fail(ORBFE_ERR_INVALID, "resident frame lives on another device");
-    L.withDesc = J.f->desc && J.qdesc;
-    L.withUr = J.qur && J.f->u_right;
-    L.oX = L.oY = L.oOct = L.oUr = L.oDesc = L.oAng = L.oBlk = L.oBval = L.oQang = L.oScr = 0;
+    const bool prod = J.producer != nullptr;
+    if (prod && (!J.claim || J.claim->mode != CLAIM_RATIO)) return fail(ORBFE_ERR_INVALID, "a producer needs a CLAIM_RATIO job");
+    L.withDesc = J.f->desc && (J.qdesc || prod);
+    L.withUr = (J.qur || prod) && J.f->u_right;
+    L.oX = L.oY = L.oOct = L.oUr = L.oDesc = L.oAng = L.oBlk = L.oBval = L.oQang = L.oScr = L.oSlot = L.oSkip = L.oScale = 0;
     L.frameOf = j;  // several jobs on the SAME host-array frame (one frame against K candidates): one upload, one grid
     if (!L.res)
       for (int k = 0; k < j; k++)
@@ -1156,17 +1176,23 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
       L.oUr = J.f->u_right ? place(n * 4) : 0;
       L.oDesc = L.withDesc ? place(n * 32) : 0;
     }
-    L.oQx = place(q * 4); L.oQy = place(q * 4); L.oQr = place(q * 4); L.oQmin = place(q * 4); L.oQmax = place(q * 4);
-    L.oQact = J.qactive ? place(q) : 0;
-    L.oQur = L.withUr ? place(q * 4) : 0;
+    L.oQx = qplace(prod, q * 4); L.oQy = qplace(prod, q * 4); L.oQr = qplace(prod, q * 4); L.oQmin = qplace(prod, q * 4);
+    L.oQmax = qplace(prod, q * 4);
+    L.oQact = (J.qactive || prod) ? qplace(prod, q) : 0;
+    L.oQur = L.withUr ? qplace(prod, q * 4) : 0;
+    if (prod) {
+      L.oSlot = place(q * 4);
+      L.oSkip = J.producer->skip ? place(q) : 0;
+      L.oScale = place((size_t)J.producer->nLevels * 4);
+    }
     L.oGur = (J.bestOut && J.gate && J.gur) ? place(q * 4) : 0;
     L.oSig = (J.bestOut && J.gate) ? place((size_t)J.nLevels * 4) : 0;
     L.oQdesc = 0;
     if (L.withDesc) {
       int shared = -1;
       for (int k = 0; k < j; k++)
-        if (lay[k].withDesc && jobs[k].qdesc == J.qdesc && jobs[k].nq == J.nq) { shared = k; break; }
-      L.oQdesc = shared >= 0 ? lay[shared].oQdesc : place(q * 32);
+        if (!prod && !jobs[k].producer && lay[k].withDesc && jobs[k].qdesc == J.qdesc && jobs[k].nq == J.nq) { shared = k; break; }
+      L.oQdesc = shared >= 0 ? lay[shared].oQdesc : qplace(prod, q * 32);
     }
     if (J.claim) {
       if (J.nq > 0x1fffff) return fail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
@@ -1175,7 +1201,7 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
       nClaim++;
       if (J.claim->checkOri && !L.res) L.oAng = place(n * 4);  // (a resident frame has its angles on the device)
       if (J.claim->blocked) L.oBlk = place(n);
-      if (J.claim->blockVal) L.oBval = place(q);
+      if (J.claim->blockVal || prod) L.oBval = qplace(prod, q);
       if (J.claim->checkOri) L.oQang = place(q * 4);
     }
   }
@@ -1193,6 +1219,7 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
         // comes back: header | match | (INIT: previous positions).  Stays: counts | lists | choice | link | (owner)
         const bool ini = jobs[j].claim->mode == CLAIM_INIT;
         outBytes += pad(16 + (ini ? q : n) * 4 + (ini ? 2 * q * 4 : 0));
+        if (jobs[j].producer && jobs[j].producer->inViewOut) outBytes += pad(q);  // in_view, behind the match array
         lay[j].oScr = scrBytes;
         // the claim kernel's dynamic LDS: the per-feature owner array(s) -- in HBM when they do not fit -- + the features'
         // octave bytes (RATIO)
@@ -1206,7 +1233,7 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
       }
       if (!lay[j].res && lay[j].frameOf == j) gridBytes += pad(n * 4) + pad(3073 * 4);
     }
-    HIPCHK(arena_begin(device, pad(inBytes) + gridBytes + outBytes + scrBytes + 2048, &ar));
+    HIPCHK(arena_begin(device, pad(inBytes) + gridBytes + outBytes + scrBytes + (prodOff ? pad(prodOff) : 0) + 2048, &ar));
     for (int j = 0; j < nJobs; j++)
       if (lay[j].res) HIPCHK(frame_use(ar, jobs[j].f->resident));
     HIPCHK(staging_reserve(inBytes > outBytes ? inBytes : outBytes));
@@ -1220,7 +1247,11 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
         if (J.f->u_right) std::memcpy(h + L.oUr, J.f->u_right, n * 4);
         if (L.withDesc) std::memcpy(h + L.oDesc, J.f->desc, n * 32);
       }
-      if (q) {
+      if (J.producer) {
+        if (q) std::memcpy(h + L.oSlot, J.producer->slot, q * 4);
+        if (q && J.producer->skip) std::memcpy(h + L.oSkip, J.producer->skip, q);
+        std::memcpy(h + L.oScale, J.producer->scale, (size_t)J.producer->nLevels * 4);
+      } else if (q) {
         std::memcpy(h + L.oQx, J.qx, q * 4); std::memcpy(h + L.oQy, J.qy, q * 4); std::memcpy(h + L.oQr, J.qr, q * 4);
         std::memcpy(h + L.oQmin, J.qmin, q * 4); std::memcpy(h + L.oQmax, J.qmax, q * 4);
         if (J.qactive) std::memcpy(h + L.oQact, J.qactive, q);
@@ -1240,6 +1271,7 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
     uint8_t* dgrid = carve<uint8_t>(ar, gridBytes ? gridBytes : 1);
     uint8_t* dout = carve<uint8_t>(ar, outBytes ? outBytes : 1);
     uint8_t* dscr = carve<uint8_t>(ar, scrBytes ? scrBytes : 1);
+    uint8_t* dprod = prodOff ? carve<uint8_t>(ar, prodOff) : nullptr;
     // the claim jobs' argument blocks travel with the inputs (their device addresses are known once the arena is carved)
     for (int j = 0, c = 0; j < nJobs; j++) {
       const WindowJob& J = jobs[j];
@@ -1256,16 +1288,17 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
       const size_t ownBytes = (ini ? 1 : 2) * n * 4, octBytes = J.claim->mode == CLAIM_RATIO ? n : 0;
       cj.owner = ownBytes + octBytes > kOwnerLds ? reinterpret_cast<int32_t*>(sc) : nullptr;
       cj.K = K; cj.nq = J.nq; cj.n = J.f->n;
-      cj.active = J.qactive ? din + L.oQact : nullptr;
+      uint8_t* qb = J.producer ? dprod : din;  // where the job's query arrays are
+      cj.active = (J.qactive || J.producer) ? qb + L.oQact : nullptr;
       cj.blocked = J.claim->blocked ? din + L.oBlk : nullptr;
-      cj.blockVal = J.claim->blockVal ? din + L.oBval : nullptr;
+      cj.blockVal = (J.claim->blockVal || J.producer) ? qb + L.oBval : nullptr;
       const orbfe_frame* R = L.res ? J.f->resident : nullptr;
       cj.octave = R ? R->doct : reinterpret_cast<const int32_t*>(din + L.oOct);
       cj.qAngle = J.claim->checkOri ? reinterpret_cast<const float*>(din + L.oQang) : nullptr;
       cj.fAngle = J.claim->checkOri ? (R ? R->dangle : reinterpret_cast<const float*>(din + L.oAng)) : nullptr;
       cj.fx = R ? R->dx : reinterpret_cast<const float*>(din + L.oX);
       cj.fy = R ? R->dy : reinterpret_cast<const float*>(din + L.oY);
-      cj.qx = reinterpret_cast<const float*>(din + L.oQx); cj.qy = reinterpret_cast<const float*>(din + L.oQy);
+      cj.qx = reinterpret_cast<const float*>(qb + L.oQx); cj.qy = reinterpret_cast<const float*>(qb + L.oQy);
       cj.mode = J.claim->mode; cj.maxDist = J.claim->maxDist; cj.checkOri = J.claim->checkOri; cj.nnratio = J.claim->nnratio;
       cj.header = reinterpret_cast<int32_t*>(dout + L.oOut);
       cj.match = cj.header + 4;
@@ -1315,12 +1348,13 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
         keyOf[j] = k; cellOf[j] = c;
       }
       WindowQueries wq{};
-      wq.x = reinterpret_cast<const float*>(din + L.oQx); wq.y = reinterpret_cast<const float*>(din + L.oQy);
-      wq.r = reinterpret_cast<const float*>(din + L.oQr);
-      wq.minLevel = reinterpret_cast<const int32_t*>(din + L.oQmin); wq.maxLevel = reinterpret_cast<const int32_t*>(din + L.oQmax);
-      wq.active = J.qactive ? din + L.oQact : nullptr;
-      wq.ur = L.withUr ? reinterpret_cast<const float*>(din + L.oQur) : nullptr;
-      wq.desc = L.withDesc ? din + L.oQdesc : nullptr;
+      uint8_t* qb = J.producer ? dprod : din;  // where the job's query arrays are
+      wq.x = reinterpret_cast<const float*>(qb + L.oQx); wq.y = reinterpret_cast<const float*>(qb + L.oQy);
+      wq.r = reinterpret_cast<const float*>(qb + L.oQr);
+      wq.minLevel = reinterpret_cast<const int32_t*>(qb + L.oQmin); wq.maxLevel = reinterpret_cast<const int32_t*>(qb + L.oQmax);
+      wq.active = (J.qactive || J.producer) ? qb + L.oQact : nullptr;
+      wq.ur = L.withUr ? reinterpret_cast<const float*>(qb + L.oQur) : nullptr;
+      wq.desc = L.withDesc ? qb + L.oQdesc : nullptr;
       wq.n = J.nq; wq.K = K;
       if (J.bestOut) {
         wq.best = reinterpret_cast<int32_t*>(dout + L.oOut);  // (the job's output block holds the nq keypoint indices)
@@ -1340,6 +1374,29 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
     }
     if (nJobs > 1) std::memcpy(h + oWs, wsj.data(), (size_t)nJobs * sizeof(WindowSearchJob));
     HIPCHK(hipMemcpyAsync(din, h, inBytes, hipMemcpyHostToDevice, ar->stream));
+    for (int j = 0; j < nJobs; j++)
+      if (jobs[j].producer) {  // the job's query arrays, written where the searches below read them
+        const FrustumProducer& P = *jobs[j].producer;
+        const Lay& L = lay[j];
+        const size_t n = (size_t)jobs[j].f->n;
+        ProjectArgs pa{};
+        pa.table = P.table;
+        pa.slot = reinterpret_cast<const int32_t*>(din + L.oSlot);
+        pa.skip = P.skip ? din + L.oSkip : nullptr;
+        pa.n = jobs[j].nq;
+        pa.cam = P.pose; pa.limit = P.limit;
+        pa.qx = reinterpret_cast<float*>(dprod + L.oQx); pa.qy = reinterpret_cast<float*>(dprod + L.oQy);
+        pa.qr = reinterpret_cast<float*>(dprod + L.oQr);
+        pa.qmin = reinterpret_cast<int32_t*>(dprod + L.oQmin); pa.qmax = reinterpret_cast<int32_t*>(dprod + L.oQmax);
+        pa.qactive = dprod + L.oQact;
+        pa.qur = L.withUr ? reinterpret_cast<float*>(dprod + L.oQur) : nullptr;
+        pa.qdesc = L.withDesc ? dprod + L.oQdesc : nullptr;
+        pa.qobs = dprod + L.oBval;
+        pa.inViewCopy = P.inViewOut ? dout + L.oOut + pad(16 + n * 4) : nullptr;
+        pa.scale = reinterpret_cast<const float*>(din + L.oScale); pa.th = P.th;
+        launch_project_frustum(ar->stream, pa);
+        HIPCHK(hipGetLastError());
+      }
     for (int j = 0; j < nJobs; j++)
       if (buildsGrid[j]) {
         launch_grid_build(ar->stream, wsj[j].f, const_cast<uint32_t*>(wsj[j].sortedKey), const_cast<int32_t*>(wsj[j].cellOff));
@@ -1374,6 +1431,8 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
         const bool ini = C->mode == CLAIM_INIT;
         const size_t nOut = ini ? q : (size_t)jobs[j].f->n;
         if (nOut) std::memcpy(C->match, hd + 4, nOut * 4);
+        if (jobs[j].producer && jobs[j].producer->inViewOut && q)
+          std::memcpy(jobs[j].producer->inViewOut, h + lay[j].oOut + pad(16 + nOut * 4), q);
         *C->nMatches = hd[1];
         C->rounds = hd[2];
         t_lastClaimRounds = hd[2] + 1 > t_lastClaimRounds ? hd[2] + 1 : t_lastClaimRounds;
@@ -1465,6 +1524,162 @@ extern "C" int orbfe_search_by_projection(int device, const orbfe_frame_view* F,
   WindowJob job{F, n_mp, proj_x, proj_y, qr.data(), qmin.data(), qmax.data(), in_view, proj_xr, mp_desc, nullptr};
   job.claim = &C;
   return window_search_multi(device, &job, 1, 32);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident map points (include/orbfe.h: orbfe_mappoints).  One slab from the pool holds the table; an update is one
+// staged copy and one scatter launch on the calling thread's stream, complete on return.  The argument checks and the
+// layouts are mappoints_host.h (no device needed: tests/cpp/mappoints_host_san.cpp runs them under the sanitizers).
+// ---------------------------------------------------------------------------------------------
+struct orbfe_mappoints {
+  int device = 0, capacity = 0;
+  std::mutex m;  // a handle serialises its own calls
+  Slab slab;     // empty until the first call that needs the device
+  MapPointsDevice d{};
+};
+
+namespace {
+// the table's slab, every slot bad until it is updated; enqueued on the arena's stream
+hipError_t mappoints_ready(orbfe_mappoints* mp, Arena* ar) {
+  if (mp->slab.p) return hipSuccess;
+  const MapPointsLayout L = mappoints_layout(mp->capacity);
+  TRY(slab_get(mp->device, L.total, &mp->slab));
+  uint8_t* b = static_cast<uint8_t*>(mp->slab.p);
+  mp->d.rec = reinterpret_cast<float4*>(b + L.oRec); mp->d.desc = b + L.oDesc; mp->d.flags = b + L.oFlags;
+  hipError_t e = hipMemsetAsync(b, 0, L.oFlags, ar->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(mp->d.flags, ORBFE_MP_BAD, (size_t)mp->capacity, ar->stream);
+  // complete before the handle counts as ready: another thread's stream may be the next to read the table
+  if (e == hipSuccess) e = hipStreamSynchronize(ar->stream);
+  if (e != hipSuccess) { slab_put(&mp->slab); mp->d = MapPointsDevice{}; }
+  return e;
+}
+bool pose_ok(const orbfe_camera_pose* p) { return p && p->n_levels >= 1 && p->n_levels <= ORBFE_MAX_LEVELS * 4; }
+
+// k_project_frustum with the isInFrustum outputs (n > 0, arguments checked, the handle locked): slot list and mask up, one
+// launch, the eight arrays back in one copy
+int project_run(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip, const orbfe_camera_pose* pose, float limit,
+                uint8_t* in_view, int32_t* level, float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z,
+                float* dist) {
+  const size_t q = (size_t)n;
+  Arena* ar;
+  HIPCHK(arena_begin(mp->device, 10 * pad(q * 4) + 1024, &ar));
+  HIPCHK(mappoints_ready(mp, ar));
+  ProjectArgs pa{};
+  int32_t* dslot;
+  uint8_t* dskip = nullptr;
+  HIPCHK(up(ar, &dslot, slot, q));
+  if (skip) HIPCHK(up(ar, &dskip, skip, q));
+  // the outputs adjacent: one copy back
+  pa.level = carve<int32_t>(ar, q); pa.viewCos = carve<float>(ar, q); pa.projX = carve<float>(ar, q); pa.projY = carve<float>(ar, q);
+  pa.projXr = carve<float>(ar, q); pa.invZ = carve<float>(ar, q); pa.dist = carve<float>(ar, q); pa.inView = carve<uint8_t>(ar, q);
+  pa.table = mp->d; pa.slot = dslot; pa.skip = dskip; pa.n = n; pa.cam = *pose; pa.limit = limit;
+  HIPCHK(flush(ar));
+  launch_project_frustum(ar->stream, pa);
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, pa.level, pa.inView + q));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  if (level) std::memcpy(level, mirror_of(ar, pa.level), q * 4);
+  if (view_cos) std::memcpy(view_cos, mirror_of(ar, pa.viewCos), q * 4);
+  if (proj_x) std::memcpy(proj_x, mirror_of(ar, pa.projX), q * 4);
+  if (proj_y) std::memcpy(proj_y, mirror_of(ar, pa.projY), q * 4);
+  if (proj_xr) std::memcpy(proj_xr, mirror_of(ar, pa.projXr), q * 4);
+  if (inv_z) std::memcpy(inv_z, mirror_of(ar, pa.invZ), q * 4);
+  if (dist) std::memcpy(dist, mirror_of(ar, pa.dist), q * 4);
+  if (in_view) std::memcpy(in_view, mirror_of(ar, pa.inView), q);
+  return ORBFE_OK;
+}
+}  // namespace
+
+extern "C" int orbfe_mappoints_create(int device, int capacity, orbfe_mappoints** out) {
+  if (const char* e = mappoints_check_create(capacity, out)) return fail(ORBFE_ERR_INVALID, std::string("mappoints_create: ") + e);
+  *out = nullptr;
+  if (device < 0) return fail(ORBFE_ERR_INVALID, "mappoints_create: negative device");
+  orbfe_mappoints* mp = new (std::nothrow) orbfe_mappoints();
+  if (!mp) return fail(ORBFE_ERR_NOMEM, "out of memory");
+  mp->device = device; mp->capacity = capacity;
+  *out = mp;
+  return ORBFE_OK;
+}
+
+extern "C" void orbfe_mappoints_destroy(orbfe_mappoints* mp) {
+  if (!mp) return;
+  if (mp->slab.p) {  // (every call on the table has completed on return: nothing can still read the slab)
+    (void)hipSetDevice(mp->device);
+    slab_put(&mp->slab);
+  }
+  delete mp;
+}
+
+extern "C" int orbfe_mappoints_capacity(const orbfe_mappoints* mp) { return mp ? mp->capacity : fail(ORBFE_ERR_INVALID, "mappoints_capacity: NULL table"); }
+
+extern "C" int orbfe_mappoints_update(orbfe_mappoints* mp, int n, const int32_t* slot, const float* pos, const float* normal,
+                                      const float* min_dist, const float* max_dist, const uint8_t* desc, const uint8_t* flags) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "mappoints_update: NULL table");
+  if (const char* e = mappoints_check_update(mp->capacity, n, slot, pos, normal, min_dist, max_dist, flags))
+    return fail(ORBFE_ERR_INVALID, std::string("mappoints_update: ") + e);
+  if (n == 0) return ORBFE_OK;
+  std::lock_guard<std::mutex> lk(mp->m);
+  const MapPointsStage S = mappoints_stage_layout(n, desc != nullptr);
+  Arena* ar;
+  HIPCHK(arena_begin(mp->device, S.total, &ar));
+  HIPCHK(mappoints_ready(mp, ar));
+  HIPCHK(staging_reserve(S.total));
+  uint8_t* h = t_staging.h;
+  mappoints_pack(h, S, n, slot, pos, normal, min_dist, max_dist, desc, flags);
+  uint8_t* din = carve<uint8_t>(ar, S.total);
+  HIPCHK(hipMemcpyAsync(din, h, S.total, hipMemcpyHostToDevice, ar->stream));
+  launch_mappoints_scatter(ar->stream, mp->d, n, reinterpret_cast<const int32_t*>(din + S.oSlot), reinterpret_cast<const float4*>(din + S.oRec),
+                           din + S.oFlags, desc ? din + S.oDesc : nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_project_in_frustum(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
+                                        const orbfe_camera_pose* pose, float viewing_cos_limit, uint8_t* in_view, int32_t* level,
+                                        float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z, float* dist) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "project_in_frustum: NULL table");
+  if (const char* e = mappoints_check_slots(mp->capacity, n, slot)) return fail(ORBFE_ERR_INVALID, std::string("project_in_frustum: ") + e);
+  if (!pose_ok(pose)) return fail(ORBFE_ERR_INVALID, "project_in_frustum: bad pose (n_levels must be 1 .. 64)");
+  if (n == 0) return ORBFE_OK;
+  std::lock_guard<std::mutex> lk(mp->m);
+  return project_run(mp, n, slot, skip, pose, viewing_cos_limit, in_view, level, view_cos, proj_x, proj_y, proj_xr, inv_z, dist);
+}
+
+extern "C" int orbfe_search_local_points(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
+                                         const orbfe_camera_pose* pose, float viewing_cos_limit, const orbfe_frame_view* F,
+                                         const float* scale_factors, int n_levels, const uint8_t* blocked, float th, float nnratio,
+                                         int32_t* match, int32_t* n_matches, uint8_t* in_view) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "search_local_points: NULL table");
+  if (const char* e = mappoints_check_slots(mp->capacity, n, slot)) return fail(ORBFE_ERR_INVALID, std::string("search_local_points: ") + e);
+  F = canon(F);
+  if (!frame_ok(F) || !scale_factors || n_levels <= 0 || !pose_ok(pose) || pose->n_levels > n_levels || !n_matches ||
+      (F->n > 0 && (!match || !F->desc)))
+    return fail(ORBFE_ERR_INVALID, "search_local_points: bad argument");
+  for (int i = 0; i < F->n; i++) match[i] = -1;
+  *n_matches = 0;
+  if (n == 0) return ORBFE_OK;
+  std::lock_guard<std::mutex> lk(mp->m);
+  if (F->n == 0) {  // nothing to search: the flags alone
+    return in_view ? project_run(mp, n, slot, skip, pose, viewing_cos_limit, in_view, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
+                   : ORBFE_OK;
+  }
+  {
+    Arena* ar;
+    HIPCHK(arena_begin(mp->device, 0, &ar));
+    HIPCHK(mappoints_ready(mp, ar));
+  }
+  FrustumProducer P;
+  P.table = mp->d; P.slot = slot; P.skip = skip; P.pose = *pose; P.limit = viewing_cos_limit; P.th = th;
+  P.scale = scale_factors; P.nLevels = n_levels; P.inViewOut = in_view;
+  ClaimSpec C;
+  C.mode = CLAIM_RATIO; C.maxDist = 100 /* TH_HIGH */; C.nnratio = nnratio;
+  C.blocked = blocked;
+  C.match = match; C.nMatches = n_matches;
+  WindowJob job{F, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  job.claim = &C;
+  job.producer = &P;
+  return window_search_multi(mp->device, &job, 1, 32);
 }
 
 extern "C" int orbfe_search_by_projection_last_frame(int device, const orbfe_frame_view* Cur, const float* scale_factors,

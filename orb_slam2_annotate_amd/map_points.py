@@ -1,0 +1,116 @@
+"""Device-resident map points (include/orbfe.h: orbfe_mappoints): what ``Frame::isInFrustum`` (src/Frame.cc:292-353) and
+``SearchByProjection(Frame&, vector<MapPoint*>&, th)`` read of a MapPoint, kept in HBM and indexed by slot, and
+``Tracking::SearchLocalPoints`` on top of it.  The caller keeps the MapPoint <-> slot map."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import CameraPoseC, check, ptr
+
+MP_BAD, MP_OBSERVED = 1, 2  # flags: MapPoint::isBad(), MapPoint::Observations() > 0
+
+
+def camera_pose(Rcw, tcw, K4, mbf, bounds, scale_factor: float, n_levels: int, Ow=None) -> CameraPoseC:
+    """orbfe_camera_pose from mRcw (3 x 3), mtcw, (fx, fy, cx, cy), mbf, (mnMinX, mnMaxX, mnMinY, mnMaxY) and the pyramid.
+    Ow defaults to -Rcw^T tcw in float32 as Frame::UpdatePoseMatrices computes it (src/Frame.cc:277-283); a caller that
+    holds mOw passes it.  log_scale_factor = (float)log(scaleFactor) (mfLogScaleFactor, src/Frame.cc:72)."""
+    R = np.asarray(Rcw, dtype=np.float32).reshape(3, 3)
+    t = np.asarray(tcw, dtype=np.float32).reshape(3)
+    if Ow is None:
+        Ow = -(R.T @ t)
+    Ow = np.asarray(Ow, dtype=np.float32).reshape(3)
+    p = CameraPoseC()
+    p.Rcw[:] = [float(v) for v in R.reshape(9)]
+    p.tcw[:] = [float(v) for v in t]
+    p.Ow[:] = [float(v) for v in Ow]
+    p.fx, p.fy, p.cx, p.cy = [float(np.float32(v)) for v in K4]
+    p.mbf = float(np.float32(mbf))
+    p.min_x, p.max_x, p.min_y, p.max_y = [float(np.float32(v)) for v in bounds]
+    p.log_scale_factor = float(np.float32(np.log(np.float32(scale_factor))))
+    p.n_levels = int(n_levels)
+    return p
+
+
+class MapPoints:
+    """A table of `capacity` map-point slots on the device.  After close() every method raises, as ResidentFrame does."""
+
+    def __init__(self, capacity: int, device: int = 0):
+        self._L = _lib.load()
+        self._handle = C.c_void_p()
+        check(self._L.orbfe_mappoints_create(int(device), int(capacity), C.byref(self._handle)))
+        self.capacity, self.device = int(capacity), int(device)
+
+    @property
+    def _h(self):
+        if self._handle is None:
+            raise ValueError("MapPoints is closed")
+        return self._handle
+
+    @property
+    def closed(self):
+        return self._handle is None
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._L.orbfe_mappoints_destroy(self._handle)
+        self._handle = None
+
+    __del__ = close
+
+    def update(self, slot, pos, normal, min_dist, max_dist, desc, flags):
+        """orbfe_mappoints_update: GetWorldPos / GetNormal ([n, 3]), the raw mfMinDistance / mfMaxDistance, GetDescriptor
+        ([n, 32] uint8, or None to keep what the slots hold) and flags (MP_BAD | MP_OBSERVED) into slot[n]."""
+        h = self._h
+        s = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        n = len(s)
+        p = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+        nv = np.ascontiguousarray(normal, dtype=np.float32).reshape(-1, 3)
+        lo = np.ascontiguousarray(min_dist, dtype=np.float32).reshape(-1)
+        hi = np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+        d = None if desc is None else np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        if not (len(p) == len(nv) == len(lo) == len(hi) == len(fl) == n and (d is None or len(d) == n)):
+            raise ValueError("MapPoints.update: the arrays must hold one entry per slot")
+        check(self._L.orbfe_mappoints_update(h, n, ptr(s), ptr(p), ptr(nv), ptr(lo), ptr(hi), ptr(d), ptr(fl)))
+
+    @staticmethod
+    def _slots(slot, skip):
+        s = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        k = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+        if k is not None and len(k) != len(s):
+            raise ValueError("skip must hold one entry per slot")
+        return s, k
+
+    def ProjectInFrustum(self, slot, pose: CameraPoseC, viewing_cos_limit: float = 0.5, skip=None):
+        """Frame::isInFrustum(pMP, viewingCosLimit) for the points in slot[] -> dict of in_view (uint8), level (int32),
+        view_cos, proj_x, proj_y, proj_xr, inv_z, dist (float32); the fields are 0 where in_view is."""
+        h = self._h
+        s, k = self._slots(slot, skip)
+        n = len(s)
+        out = {"in_view": np.zeros(n, np.uint8), "level": np.zeros(n, np.int32)}
+        for name in ("view_cos", "proj_x", "proj_y", "proj_xr", "inv_z", "dist"):
+            out[name] = np.zeros(n, np.float32)
+        check(self._L.orbfe_project_in_frustum(h, n, ptr(s), ptr(k), C.byref(pose), float(viewing_cos_limit),
+                                               *[ptr(out[f]) for f in ("in_view", "level", "view_cos", "proj_x", "proj_y",
+                                                                       "proj_xr", "inv_z", "dist")]))
+        return out
+
+    def SearchLocalPoints(self, F, slot, pose: CameraPoseC, scale_factors, th: float = 1.0, nnratio: float = 0.8,
+                          viewing_cos_limit: float = 0.5, skip=None, blocked=None):
+        """Tracking::SearchLocalPoints: isInFrustum for slot[] and SearchByProjection(F, points, th) in one call ->
+        (nmatches, match[F.N], in_view[n]); match[idx] = position in slot[] of the point given to feature idx, or -1."""
+        h = self._h
+        s, k = self._slots(slot, skip)
+        n = len(s)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
+        blk = None if blocked is None else np.ascontiguousarray(blocked, dtype=np.uint8)
+        match = np.full(max(F.N, 1), -1, dtype=np.int32)
+        in_view = np.zeros(max(n, 1), np.uint8)
+        nm = C.c_int32(0)
+        check(self._L.orbfe_search_local_points(h, n, ptr(s), ptr(k), C.byref(pose), float(viewing_cos_limit), C.byref(F.c),
+                                                ptr(sf), len(sf), ptr(blk), float(th), float(nnratio), ptr(match),
+                                                C.byref(nm), ptr(in_view)))
+        return nm.value, match[:F.N], in_view[:n]

@@ -176,6 +176,37 @@ def measure(reps=30, verbose=True):
         lambda: orc.search_by_projection_sim3(Fo, SF, valid, u, v, lv, md, None, th))
     row("Fuse, resident", lambda: M.FuseSearch(FR, SF, valid, u, v, lv, md, th=th, inv_level_sigma2=inv_s2, ur=pxr),
         lambda: orc.fuse_search(Fo, SF, inv_s2, valid, u, v, pxr, lv, md, th, True))
+    # --- Tracking::SearchLocalPoints: 2000 local map points (tests/frustum_ref.py's scene), the KITTI frame resident.
+    # One call on the device table against today's path: the host projection, then SearchByProjection with uploaded operands.
+    import frustum_ref
+    from orb_slam2_annotate_amd.map_points import MapPoints, camera_pose
+    sc = frustum_ref.scene(0, 2000)
+    slots = np.random.default_rng(7).permutation(4096)[:2000].astype(np.int32)
+    table = MapPoints(4096)
+    table.update(slots, sc["pos"], sc["normal"], sc["min_dist"], sc["max_dist"], sc["desc"], sc["flags"])
+    pose = camera_pose(sc["Rcw"], sc["tcw"], (frustum_ref.FX, frustum_ref.FY, frustum_ref.CX, frustum_ref.CY), frustum_ref.MBF,
+                       frustum_ref.BOUNDS, frustum_ref.SCALE, frustum_ref.LEVELS, Ow=sc["Ow"])
+    obs = ((sc["flags"] >> 1) & 1).astype(np.uint8)
+
+    def two_step():
+        p = frustum_ref.spec32(sc, sc["skip"])
+        return M.SearchByProjection(FR, SF, p["in_view"], p["level"], p["view_cos"], p["proj_x"], p["proj_y"], sc["desc"], th=th,
+                                    proj_xr=p["proj_xr"], mp_obs_positive=obs)
+
+    def cpu_local():
+        p = frustum_ref.spec32(sc, sc["skip"])
+        return orc.search_by_projection_mappoints(Fo, SF, None, p["in_view"], p["level"], p["view_cos"], p["proj_x"], p["proj_y"],
+                                                  p["proj_xr"], sc["desc"], obs, th, 0.7)
+    row("SearchLocalPoints: ONE call, 2000 points in the device table (resident)",
+        lambda: table.SearchLocalPoints(FR, slots, pose, SF, th=th, nnratio=0.7, skip=sc["skip"]), cpu_local)
+    row("SearchLocalPoints today: host isInFrustum (numpy) + SearchByProjection, uploaded operands (resident)", two_step, cpu_local)
+    p0 = frustum_ref.spec32(sc, sc["skip"])
+    row("  of which SearchByProjection alone (2000 points, operands uploaded)",
+        lambda: M.SearchByProjection(FR, SF, p0["in_view"], p0["level"], p0["view_cos"], p0["proj_x"], p0["proj_y"], sc["desc"], th=th,
+                                     proj_xr=p0["proj_xr"], mp_obs_positive=obs), cpu_local)
+    row("ProjectInFrustum alone (2000 points)", lambda: table.ProjectInFrustum(slots, pose, 0.5, skip=sc["skip"]),
+        lambda: frustum_ref.spec32(sc, sc["skip"]))
+    table.close()
     NK = 10  # SearchInNeighbors: the current key frame's map points fused into every neighbour (src/LocalMapping.cc:542-549)
     st = lambda a_: np.stack([a_] * NK)  # noqa: E731
     row(f"Fuse into {NK} neighbours, ONE call (resident)",
