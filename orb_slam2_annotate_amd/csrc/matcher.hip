@@ -47,6 +47,7 @@ hipError_t arena_begin(int device, size_t bytes, Arena** out) {
   hipError_t err = hipSetDevice(device);
   if (err != hipSuccess) return err;
   Arena& a = t_arenas[device];
+  bytes = (bytes + 255) & ~(size_t)255;
   if (a.device < 0) {
     a.device = device;
     err = hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking);
@@ -86,16 +87,22 @@ inline void mark_dirty(Arena* a, size_t off, size_t bytes) {
     if (off + bytes > a->dirtyHi) a->dirtyHi = off + bytes;
   }
 }
+// host data for an array carved earlier in this call: for blocks of device addresses, which are known only once everything
+// is carved but must lie among the uploads
 template <typename T>
-hipError_t up(Arena* a, T** d, const T* h, size_t n) {
-  *d = carve<T>(a, n ? n : 1);
+hipError_t put(Arena* a, T* d, const T* h, size_t n) {
   if (n == 0 || a->sizing) return hipSuccess;
-  const size_t off = (size_t)(reinterpret_cast<uint8_t*>(*d) - a->base), bytes = n * sizeof(T);
+  const size_t off = (size_t)(reinterpret_cast<uint8_t*>(d) - a->base), bytes = n * sizeof(T);
   hipError_t e = grow_mirror(a, off + bytes);
   if (e != hipSuccess) return e;
   std::memcpy(a->hmirror + off, h, bytes);
   mark_dirty(a, off, bytes);
   return hipSuccess;
+}
+template <typename T>
+hipError_t up(Arena* a, T** d, const T* h, size_t n) {
+  *d = carve<T>(a, n ? n : 1);
+  return put(a, *d, h, n);
 }
 // a device array of n elements whose bytes all start as `byteValue`: filled in the mirror, so it travels with the one
 // host-to-device copy of the call instead of costing a fill kernel of its own
@@ -123,11 +130,14 @@ template <typename T>
 const T* mirror_of(Arena* a, const T* d) {
   return reinterpret_cast<const T*>(a->hmirror + (reinterpret_cast<const uint8_t*>(d) - a->base));
 }
-// one H2D copy for everything up() staged since arena_begin(); call before the first kernel launch
+// one H2D copy for everything up() staged since arena_begin(); call before the first kernel launch.  Whole 256-byte lines
+// travel (a copy that ends inside a line costs a microsecond more): carve() starts every array on a line and arena_begin()
+// reserves whole lines, so the tail of the last line belongs to no array
 hipError_t flush(Arena* a) {
   if (a->dirtyHi == a->dirtyLo) return hipSuccess;
-  hipError_t e = hipMemcpyAsync(a->base + a->dirtyLo, a->hmirror + a->dirtyLo, a->dirtyHi - a->dirtyLo,
-                                hipMemcpyHostToDevice, a->stream);
+  const size_t hi = (a->dirtyHi + 255) & ~(size_t)255;
+  hipError_t e = grow_mirror(a, hi);
+  if (e == hipSuccess) e = hipMemcpyAsync(a->base + a->dirtyLo, a->hmirror + a->dirtyLo, hi - a->dirtyLo, hipMemcpyHostToDevice, a->stream);
   a->dirtyLo = a->dirtyHi = 0;
   return e;
 }
@@ -145,9 +155,9 @@ hipError_t arena_stage(int device, Arena** out, F&& stage) {
   return e;
 }
 
-// Pinned staging of the calling thread: every input array of a call is packed into it and travels in
-// ONE host-to-device copy, counts + candidate lists come back in ONE copy (13 + 2 small transfers of
-// ~7 us each were most of a call before).
+// Pinned staging of the calling thread for copies whose destination is a slab, not the arena (frame builds,
+// orbfe_frame_set_featvec, orbfe_mappoints_update): the call packs what travels in the slab's own layout and sends it in ONE
+// host-to-device copy.  Everything else stages through the arena (up() / flush() / down_range()).
 struct Staging {
   PinBuf<uint8_t> h;
   hipEvent_t pending = nullptr;  // an asynchronous copy OUT of the buffer that nobody waited for (orbfe_frame_upload): the
@@ -1090,14 +1100,15 @@ bool frame_ok(const orbfe_frame_view* f) {
 // One window search = one frame + one set of query windows.  Several jobs of a call (Fuse against K neighbour key frames,
 // the two directions of SearchBySim3) share ONE upload, one group of launches, one download and one synchronisation.
 struct WindowJob {
-  const orbfe_frame_view* f;
-  int nq;
-  const float *qx, *qy, *qr;
-  const int32_t *qmin, *qmax;
-  const uint8_t* qactive;
-  const float* qur;
-  const uint8_t* qdesc;  // jobs that pass the SAME pointer share one device copy
-  WindowResult* res;
+  const orbfe_frame_view* f = nullptr;
+  int nq = 0;
+  const float *qx = nullptr, *qy = nullptr, *qr = nullptr;
+  const int32_t *qmin = nullptr, *qmax = nullptr;
+  const uint8_t* qactive = nullptr;
+  const float* qur = nullptr;
+  const uint8_t* qdesc = nullptr;  // jobs that pass the SAME pointer share one device copy
+  // list mode (res != NULL): the counts and candidate lists come back
+  WindowResult* res = nullptr;
   // BEST mode (bestOut != NULL): no candidate lists come back -- the device keeps the first minimum of every window, behind
   // Fuse's chi-square gate when gate != 0 (gur / invSigma2), and writes the keypoint or -1 (WindowQueries::best)
   int32_t* bestOut = nullptr;
@@ -1135,330 +1146,303 @@ struct ClaimSpec {
   int rounds = 0;                     // out: rounds the fixed point took
 };
 
-// Upload frames (unless resident: keypoint arrays, descriptors and grid are on the device already) + queries, build the
-// grids, search every window; grows K until every list fits.
-thread_local int t_lastClaimRounds = 0;
-int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
-  UnsettledScope unsettledScope;
-  t_lastClaimRounds = 0;
-  int K = ((K0 < 8 ? 8 : K0) + 7) & ~7;  // (k_window_claim reads the lists eight entries at a time)
-  struct Lay { size_t oX, oY, oOct, oUr, oDesc, oQx, oQy, oQr, oQmin, oQmax, oQact, oQur, oQdesc, oOut, oGur, oSig, oAng, oBlk, oBval, oQang, oScr, oSlot, oSkip, oScale;
-               bool withDesc, withUr, res; int frameOf; };
-  std::vector<Lay> lay((size_t)nJobs);
-  size_t off = 0, prodOff = 0;  // prodOff: the query arrays a producer writes, in a region of their own that is never uploaded
-  int nClaim = 0;
-  bool claimInit = false;
-  auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  auto qplace = [&](bool produced, size_t bytes) {
-    if (!produced) return place(bytes);
-    const size_t o = prodOff; prodOff += (bytes + 255) & ~(size_t)255; return o;
-  };
-  for (int j = 0; j < nJobs; j++) {
-    const WindowJob& J = jobs[j];
-    Lay& L = lay[j];
-    const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
-    L.res = J.f->resident != nullptr;
-    if (L.res && J.f->resident->device != device) return fail(ORBFE_ERR_INVALID, "resident frame lives on another device");
-    const bool prod = J.producer != nullptr;
-    if (prod && (!J.claim || J.claim->mode != CLAIM_RATIO)) return fail(ORBFE_ERR_INVALID, "a producer needs a CLAIM_RATIO job");
-    L.withDesc = J.f->desc && (J.qdesc || prod);
-    L.withUr = (J.qur || prod) && J.f->u_right;
-    L.oX = L.oY = L.oOct = L.oUr = L.oDesc = L.oAng = L.oBlk = L.oBval = L.oQang = L.oScr = L.oSlot = L.oSkip = L.oScale = 0;
-    L.frameOf = j;  // several jobs on the SAME host-array frame (one frame against K candidates): one upload, one grid
-    if (!L.res)
-      for (int k = 0; k < j; k++)
-        if (!lay[k].res && jobs[k].f == J.f && lay[k].withDesc == L.withDesc) { L.frameOf = lay[k].frameOf; break; }
-    if (!L.res && L.frameOf != j) {
-      const Lay& F = lay[L.frameOf];
-      L.oX = F.oX; L.oY = F.oY; L.oOct = F.oOct; L.oUr = F.oUr; L.oDesc = F.oDesc;
-    } else if (!L.res) {
-      L.oX = place(n * 4); L.oY = place(n * 4); L.oOct = place(n * 4);
-      L.oUr = J.f->u_right ? place(n * 4) : 0;
-      L.oDesc = L.withDesc ? place(n * 32) : 0;
-    }
-    L.oQx = qplace(prod, q * 4); L.oQy = qplace(prod, q * 4); L.oQr = qplace(prod, q * 4); L.oQmin = qplace(prod, q * 4);
-    L.oQmax = qplace(prod, q * 4);
-    L.oQact = (J.qactive || prod) ? qplace(prod, q) : 0;
-    L.oQur = L.withUr ? qplace(prod, q * 4) : 0;
-    if (prod) {
-      L.oSlot = place(q * 4);
-      L.oSkip = J.producer->skip ? place(q) : 0;
-      L.oScale = place((size_t)J.producer->nLevels * 4);
-    }
-    L.oGur = (J.bestOut && J.gate && J.gur) ? place(q * 4) : 0;
-    L.oSig = (J.bestOut && J.gate) ? place((size_t)J.nLevels * 4) : 0;
-    L.oQdesc = 0;
-    if (L.withDesc) {
-      int shared = -1;
-      for (int k = 0; k < j; k++)
-        if (!prod && !jobs[k].producer && lay[k].withDesc && jobs[k].qdesc == J.qdesc && jobs[k].nq == J.nq) { shared = k; break; }
-      L.oQdesc = shared >= 0 ? lay[shared].oQdesc : qplace(prod, q * 32);
-    }
-    if (J.claim) {
-      if (J.nq > 0x1fffff) return fail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
-      if (nClaim && claimInit != (J.claim->mode == CLAIM_INIT)) return fail(ORBFE_ERR_INVALID, "mixed claim forms in one call");
-      claimInit = J.claim->mode == CLAIM_INIT;
-      nClaim++;
-      if (J.claim->checkOri && !L.res) L.oAng = place(n * 4);  // (a resident frame has its angles on the device)
-      if (J.claim->blocked) L.oBlk = place(n);
-      if (J.claim->blockVal || prod) L.oBval = qplace(prod, q);
-      if (J.claim->checkOri) L.oQang = place(q * 4);
+// Where a job's arrays are on the device: carved from the call's arena by the three stage_* helpers below, or a resident
+// frame's own.  NULL where the job has no such array.
+struct JobDev {
+  bool withDesc = false, withUr = false;  // the search takes descriptor distances / runs the stereo check
+  int frameOf = -1;  // the job whose uploaded frame arrays and grid this one uses (itself: it uploads and builds); -1: resident
+  float *x = nullptr, *y = nullptr, *ur = nullptr, *angle = nullptr;  // frame
+  int32_t *oct = nullptr, *cell = nullptr;
+  uint8_t* desc = nullptr;
+  uint32_t* key = nullptr;
+  float *qx = nullptr, *qy = nullptr, *qr = nullptr, *qur = nullptr;  // queries: uploaded, or written by k_project_frustum ...
+  int32_t *qmin = nullptr, *qmax = nullptr, *slot = nullptr;          // ... from slot / skip / scale
+  uint8_t *qactive = nullptr, *qdesc = nullptr, *skip = nullptr;
+  float *scale = nullptr, *gateUr = nullptr, *invSigma2 = nullptr;    // (BEST mode behind Fuse's gate)
+  uint8_t *blocked = nullptr, *blockVal = nullptr;  // CLAIM mode: inputs, scratch, the dynamic LDS the job's workgroup needs
+  float* qAngle = nullptr;
+  int32_t *choice = nullptr, *link = nullptr, *owner = nullptr;
+  size_t claimLds = 0;
+  int32_t* count = nullptr;  // the lists: a result in list mode, the claim kernel's input in CLAIM mode
+  uint32_t* cand = nullptr;
+  int32_t *best = nullptr, *header = nullptr, *match = nullptr;  // results of BEST / CLAIM mode
+  float *prevX = nullptr, *prevY = nullptr;
+  uint8_t* inView = nullptr;
+};
+
+// Region 1 of a call's arena, job j's part: everything that travels up.  Only up() between the first and the last of these,
+// so that flush()'s dirty range is exactly the uploads: one host-to-device copy.
+hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev) {
+  const WindowJob& J = jobs[j];
+  JobDev& D = dev[j];
+  const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
+  D = JobDev{};
+  D.withDesc = J.f->desc && (J.qdesc || J.producer);
+  D.withUr = (J.qur || J.producer) && J.f->u_right;
+  if (const orbfe_frame* R = J.f->resident) {
+    D.x = R->dx; D.y = R->dy; D.oct = R->doct; D.ur = J.f->u_right ? R->dur : nullptr; D.desc = D.withDesc ? R->ddesc : nullptr;
+    D.angle = R->dangle; D.key = R->dkey; D.cell = R->dcell;
+  } else {
+    D.frameOf = j;  // several jobs on the SAME host-array frame (one frame against K candidates): one upload, one grid
+    for (int k = 0; k < j && D.frameOf == j; k++)
+      if (dev[k].frameOf == k && jobs[k].f == J.f && dev[k].withDesc == D.withDesc) D.frameOf = k;
+    if (D.frameOf != j) {
+      const JobDev& S = dev[D.frameOf];
+      D.x = S.x; D.y = S.y; D.oct = S.oct; D.ur = S.ur; D.desc = S.desc;
+    } else {
+      TRY(up(a, &D.x, J.f->x, n)); TRY(up(a, &D.y, J.f->y, n)); TRY(up(a, &D.oct, J.f->octave, n));
+      if (J.f->u_right) TRY(up(a, &D.ur, J.f->u_right, n));
+      if (D.withDesc) TRY(up(a, &D.desc, J.f->desc, n * 32));
     }
   }
-  const size_t oClaim = nClaim ? place((size_t)nClaim * sizeof(ClaimJob)) : 0;
-  const size_t oWs = nJobs > 1 ? place((size_t)nJobs * sizeof(WindowSearchJob)) : 0;
-  const size_t inBytes = off ? off : 256;
-  constexpr size_t kOwnerLds = 60 * 1024;  // the claim kernel's per-feature arrays live in its LDS up to this size (~6800 features)
-  for (;;) {
-    Arena* ar;
-    size_t outBytes = 0, gridBytes = 0, scrBytes = 0, claimLds = 0;
-    for (int j = 0; j < nJobs; j++) {
-      lay[j].oOut = outBytes;
-      const size_t q = (size_t)jobs[j].nq, n = (size_t)jobs[j].f->n;
-      if (jobs[j].claim) {
-        // comes back: header | match | (INIT: previous positions).  Stays: counts | lists | choice | link | (owner)
-        const bool ini = jobs[j].claim->mode == CLAIM_INIT;
-        outBytes += pad(16 + (ini ? q : n) * 4 + (ini ? 2 * q * 4 : 0));
-        if (jobs[j].producer && jobs[j].producer->inViewOut) outBytes += pad(q);  // in_view, behind the match array
-        lay[j].oScr = scrBytes;
-        // the claim kernel's dynamic LDS: the per-feature owner array(s) -- in HBM when they do not fit -- + the features'
-        // octave bytes (RATIO)
-        const size_t ownBytes = (ini ? 1 : 2) * n * 4, octBytes = jobs[j].claim->mode == CLAIM_RATIO ? n : 0;
-        const bool ownInLds = ownBytes + octBytes <= kOwnerLds;
-        scrBytes += pad(q * 4) + pad(q * (size_t)K * 4) + 2 * pad(q * 4) + (ownInLds ? 0 : pad(ownBytes));
-        const size_t lds = (ownInLds ? ownBytes : 0) + octBytes;
-        if (lds > claimLds) claimLds = lds;
-      } else {
-        outBytes += pad(q * 4) + (jobs[j].bestOut ? 0 : pad(q * (size_t)K * 4));
-      }
-      if (!lay[j].res && lay[j].frameOf == j) gridBytes += pad(n * 4) + pad(3073 * 4);
+  if (const FrustumProducer* P = J.producer) {
+    TRY(up(a, &D.slot, P->slot, q));
+    if (P->skip) TRY(up(a, &D.skip, P->skip, q));
+    TRY(up(a, &D.scale, P->scale, (size_t)P->nLevels));
+  } else {
+    TRY(up(a, &D.qx, J.qx, q)); TRY(up(a, &D.qy, J.qy, q)); TRY(up(a, &D.qr, J.qr, q));
+    TRY(up(a, &D.qmin, J.qmin, q)); TRY(up(a, &D.qmax, J.qmax, q));
+    if (J.qactive) TRY(up(a, &D.qactive, J.qactive, q));
+    if (D.withUr) TRY(up(a, &D.qur, J.qur, q));
+    if (D.withDesc) {  // the same descriptors for several jobs (Fuse: one set of map points into K key frames): one copy
+      int shared = -1;
+      for (int k = 0; k < j && shared < 0; k++)
+        if (!jobs[k].producer && dev[k].withDesc && jobs[k].qdesc == J.qdesc && jobs[k].nq == J.nq) shared = k;
+      if (shared >= 0) D.qdesc = dev[shared].qdesc; else TRY(up(a, &D.qdesc, J.qdesc, q * 32));
     }
-    HIPCHK(arena_begin(device, pad(inBytes) + gridBytes + outBytes + scrBytes + (prodOff ? pad(prodOff) : 0) + 2048, &ar));
-    for (int j = 0; j < nJobs; j++)
-      if (lay[j].res) HIPCHK(frame_use(ar, jobs[j].f->resident));
-    HIPCHK(staging_reserve(inBytes > outBytes ? inBytes : outBytes));
-    uint8_t* h = t_staging.h;
-    for (int j = 0; j < nJobs; j++) {
-      const WindowJob& J = jobs[j];
-      const Lay& L = lay[j];
-      const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
-      if (!L.res && L.frameOf == j && n) {
-        std::memcpy(h + L.oX, J.f->x, n * 4); std::memcpy(h + L.oY, J.f->y, n * 4); std::memcpy(h + L.oOct, J.f->octave, n * 4);
-        if (J.f->u_right) std::memcpy(h + L.oUr, J.f->u_right, n * 4);
-        if (L.withDesc) std::memcpy(h + L.oDesc, J.f->desc, n * 32);
-      }
-      if (J.producer) {
-        if (q) std::memcpy(h + L.oSlot, J.producer->slot, q * 4);
-        if (q && J.producer->skip) std::memcpy(h + L.oSkip, J.producer->skip, q);
-        std::memcpy(h + L.oScale, J.producer->scale, (size_t)J.producer->nLevels * 4);
-      } else if (q) {
-        std::memcpy(h + L.oQx, J.qx, q * 4); std::memcpy(h + L.oQy, J.qy, q * 4); std::memcpy(h + L.oQr, J.qr, q * 4);
-        std::memcpy(h + L.oQmin, J.qmin, q * 4); std::memcpy(h + L.oQmax, J.qmax, q * 4);
-        if (J.qactive) std::memcpy(h + L.oQact, J.qactive, q);
-        if (L.withUr) std::memcpy(h + L.oQur, J.qur, q * 4);
-        if (L.withDesc) std::memcpy(h + L.oQdesc, J.qdesc, q * 32);
-        if (J.bestOut && J.gate && J.gur) std::memcpy(h + L.oGur, J.gur, q * 4);
-        if (J.bestOut && J.gate) std::memcpy(h + L.oSig, J.invSigma2, (size_t)J.nLevels * 4);
-      }
-      if (J.claim) {
-        if (L.oAng && n) std::memcpy(h + L.oAng, J.f->angle, n * 4);
-        if (J.claim->blocked && n) std::memcpy(h + L.oBlk, J.claim->blocked, n);
-        if (J.claim->blockVal && q) std::memcpy(h + L.oBval, J.claim->blockVal, q);
-        if (J.claim->checkOri && q) std::memcpy(h + L.oQang, J.claim->qAngle, q * 4);
-      }
-    }
-    uint8_t* din = carve<uint8_t>(ar, inBytes);
-    uint8_t* dgrid = carve<uint8_t>(ar, gridBytes ? gridBytes : 1);
-    uint8_t* dout = carve<uint8_t>(ar, outBytes ? outBytes : 1);
-    uint8_t* dscr = carve<uint8_t>(ar, scrBytes ? scrBytes : 1);
-    uint8_t* dprod = prodOff ? carve<uint8_t>(ar, prodOff) : nullptr;
-    // the claim jobs' argument blocks travel with the inputs (their device addresses are known once the arena is carved)
-    for (int j = 0, c = 0; j < nJobs; j++) {
-      const WindowJob& J = jobs[j];
-      if (!J.claim) continue;
-      const Lay& L = lay[j];
-      const size_t q = (size_t)J.nq, n = (size_t)J.f->n;
-      const bool ini = J.claim->mode == CLAIM_INIT;
-      ClaimJob cj{};
-      uint8_t* sc = dscr + L.oScr;
-      cj.count = reinterpret_cast<const int32_t*>(sc); sc += pad(q * 4);
-      cj.cand = reinterpret_cast<const uint32_t*>(sc); sc += pad(q * (size_t)K * 4);
-      cj.choice = reinterpret_cast<int32_t*>(sc); sc += pad(q * 4);
-      cj.link = reinterpret_cast<int32_t*>(sc); sc += pad(q * 4);
-      const size_t ownBytes = (ini ? 1 : 2) * n * 4, octBytes = J.claim->mode == CLAIM_RATIO ? n : 0;
-      cj.owner = ownBytes + octBytes > kOwnerLds ? reinterpret_cast<int32_t*>(sc) : nullptr;
-      cj.K = K; cj.nq = J.nq; cj.n = J.f->n;
-      uint8_t* qb = J.producer ? dprod : din;  // where the job's query arrays are
-      cj.active = (J.qactive || J.producer) ? qb + L.oQact : nullptr;
-      cj.blocked = J.claim->blocked ? din + L.oBlk : nullptr;
-      cj.blockVal = (J.claim->blockVal || J.producer) ? qb + L.oBval : nullptr;
-      const orbfe_frame* R = L.res ? J.f->resident : nullptr;
-      cj.octave = R ? R->doct : reinterpret_cast<const int32_t*>(din + L.oOct);
-      cj.qAngle = J.claim->checkOri ? reinterpret_cast<const float*>(din + L.oQang) : nullptr;
-      cj.fAngle = J.claim->checkOri ? (R ? R->dangle : reinterpret_cast<const float*>(din + L.oAng)) : nullptr;
-      cj.fx = R ? R->dx : reinterpret_cast<const float*>(din + L.oX);
-      cj.fy = R ? R->dy : reinterpret_cast<const float*>(din + L.oY);
-      cj.qx = reinterpret_cast<const float*>(qb + L.oQx); cj.qy = reinterpret_cast<const float*>(qb + L.oQy);
-      cj.mode = J.claim->mode; cj.maxDist = J.claim->maxDist; cj.checkOri = J.claim->checkOri; cj.nnratio = J.claim->nnratio;
-      cj.header = reinterpret_cast<int32_t*>(dout + L.oOut);
-      cj.match = cj.header + 4;
-      cj.prevX = ini ? reinterpret_cast<float*>(cj.match + q) : nullptr;
-      cj.prevY = ini ? cj.prevX + q : nullptr;
-      std::memcpy(h + oClaim + (size_t)c * sizeof(ClaimJob), &cj, sizeof(ClaimJob));
-      c++;
-    }
-    // the search jobs: every device address is known once the arena is carved, so the job blocks travel with the inputs too
-    size_t goff = 0;
-    std::vector<const uint32_t*> keyOf((size_t)nJobs, nullptr);
-    std::vector<const int32_t*> cellOf((size_t)nJobs, nullptr);
-    std::vector<WindowSearchJob> wsj((size_t)nJobs);
-    std::vector<char> buildsGrid((size_t)nJobs, 0);
-    int totalBlocks = 0;
-    for (int j = 0; j < nJobs; j++) {
-      const WindowJob& J = jobs[j];
-      const Lay& L = lay[j];
-      const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
-      GridFrame g{};
-      const uint32_t* dkey;
-      const int32_t* dcell;
-      if (L.res) {
-        const orbfe_frame* R = J.f->resident;
-        g.x = R->dx; g.y = R->dy; g.octave = R->doct; g.uRight = J.f->u_right ? R->dur : nullptr;
-        g.desc = L.withDesc ? R->ddesc : nullptr;
-        dkey = R->dkey; dcell = R->dcell;
-      } else {
-        g.x = reinterpret_cast<const float*>(din + L.oX); g.y = reinterpret_cast<const float*>(din + L.oY);
-        g.octave = reinterpret_cast<const int32_t*>(din + L.oOct);
-        g.uRight = J.f->u_right ? reinterpret_cast<const float*>(din + L.oUr) : nullptr;
-        g.desc = L.withDesc ? din + L.oDesc : nullptr;
-      }
-      g.n = J.f->n;
-      g.minX = J.f->min_x; g.minY = J.f->min_y;
-      g.wInv = 64.0f / (J.f->max_x - J.f->min_x);  // src/Frame.cc:109-110 (FRAME_GRID_COLS / ROWS)
-      g.hInv = 48.0f / (J.f->max_y - J.f->min_y);
-      if (!L.res && L.frameOf != j) {
-        dkey = keyOf[L.frameOf]; dcell = cellOf[L.frameOf];
-      } else if (!L.res) {
-        uint32_t* k = reinterpret_cast<uint32_t*>(dgrid + goff);
-        goff += pad(n * 4);
-        int32_t* c = reinterpret_cast<int32_t*>(dgrid + goff);
-        goff += pad(3073 * 4);
-        buildsGrid[j] = 1;
-        dkey = k; dcell = c;
-        keyOf[j] = k; cellOf[j] = c;
-      }
-      WindowQueries wq{};
-      uint8_t* qb = J.producer ? dprod : din;  // where the job's query arrays are
-      wq.x = reinterpret_cast<const float*>(qb + L.oQx); wq.y = reinterpret_cast<const float*>(qb + L.oQy);
-      wq.r = reinterpret_cast<const float*>(qb + L.oQr);
-      wq.minLevel = reinterpret_cast<const int32_t*>(qb + L.oQmin); wq.maxLevel = reinterpret_cast<const int32_t*>(qb + L.oQmax);
-      wq.active = (J.qactive || J.producer) ? qb + L.oQact : nullptr;
-      wq.ur = L.withUr ? reinterpret_cast<const float*>(qb + L.oQur) : nullptr;
-      wq.desc = L.withDesc ? qb + L.oQdesc : nullptr;
-      wq.n = J.nq; wq.K = K;
-      if (J.bestOut) {
-        wq.best = reinterpret_cast<int32_t*>(dout + L.oOut);  // (the job's output block holds the nq keypoint indices)
-        wq.gate = J.gate; wq.maxDist = J.maxDist;
-        wq.gateUr = (J.gate && J.gur) ? reinterpret_cast<const float*>(din + L.oGur) : nullptr;
-        wq.invSigma2 = J.gate ? reinterpret_cast<const float*>(din + L.oSig) : nullptr;
-      }
-      // counts and candidate lists of a job are adjacent, the jobs' blocks too: one copy back
-      int32_t* dcount = reinterpret_cast<int32_t*>(dout + L.oOut);
-      uint32_t* dcand = reinterpret_cast<uint32_t*>(dout + L.oOut + pad(q * 4));
-      if (J.claim) {  // the lists of a claim job stay in the scratch area
-        dcount = reinterpret_cast<int32_t*>(dscr + L.oScr);
-        dcand = reinterpret_cast<uint32_t*>(dscr + L.oScr + pad(q * 4));
-      }
-      wsj[j] = WindowSearchJob{g, dkey, dcell, wq, dcount, dcand, totalBlocks};
-      totalBlocks += (J.nq + 3) / 4;
-    }
-    if (nJobs > 1) std::memcpy(h + oWs, wsj.data(), (size_t)nJobs * sizeof(WindowSearchJob));
-    HIPCHK(hipMemcpyAsync(din, h, inBytes, hipMemcpyHostToDevice, ar->stream));
-    for (int j = 0; j < nJobs; j++)
-      if (jobs[j].producer) {  // the job's query arrays, written where the searches below read them
-        const FrustumProducer& P = *jobs[j].producer;
-        const Lay& L = lay[j];
-        const size_t n = (size_t)jobs[j].f->n;
-        ProjectArgs pa{};
-        pa.table = P.table;
-        pa.slot = reinterpret_cast<const int32_t*>(din + L.oSlot);
-        pa.skip = P.skip ? din + L.oSkip : nullptr;
-        pa.n = jobs[j].nq;
-        pa.cam = P.pose; pa.limit = P.limit;
-        pa.qx = reinterpret_cast<float*>(dprod + L.oQx); pa.qy = reinterpret_cast<float*>(dprod + L.oQy);
-        pa.qr = reinterpret_cast<float*>(dprod + L.oQr);
-        pa.qmin = reinterpret_cast<int32_t*>(dprod + L.oQmin); pa.qmax = reinterpret_cast<int32_t*>(dprod + L.oQmax);
-        pa.qactive = dprod + L.oQact;
-        pa.qur = L.withUr ? reinterpret_cast<float*>(dprod + L.oQur) : nullptr;
-        pa.qdesc = L.withDesc ? dprod + L.oQdesc : nullptr;
-        pa.qobs = dprod + L.oBval;
-        pa.inViewCopy = P.inViewOut ? dout + L.oOut + pad(16 + n * 4) : nullptr;
-        pa.scale = reinterpret_cast<const float*>(din + L.oScale); pa.th = P.th;
-        launch_project_frustum(ar->stream, pa);
-        HIPCHK(hipGetLastError());
-      }
-    for (int j = 0; j < nJobs; j++)
-      if (buildsGrid[j]) {
-        launch_grid_build(ar->stream, wsj[j].f, const_cast<uint32_t*>(wsj[j].sortedKey), const_cast<int32_t*>(wsj[j].cellOff));
-        HIPCHK(hipGetLastError());
-      }
-    if (nJobs > 1) {  // ONE launch for the window searches of all jobs
-      launch_window_search_multi(ar->stream, reinterpret_cast<const WindowSearchJob*>(din + oWs), nJobs, totalBlocks);
-    } else {
-      launch_window_search(ar->stream, wsj[0].f, wsj[0].sortedKey, wsj[0].cellOff, wsj[0].q, wsj[0].count, wsj[0].cand);
-    }
-    HIPCHK(hipGetLastError());
-    if (nClaim) {
-      launch_window_claim(ar->stream, reinterpret_cast<const ClaimJob*>(din + oClaim), reinterpret_cast<const ClaimJob*>(h + oClaim), nClaim,
-                          claimLds, claimInit);
-      HIPCHK(hipGetLastError());
-    }
-    if (outBytes) HIPCHK(hipMemcpyAsync(h, dout, outBytes, hipMemcpyDeviceToHost, ar->stream));
-    HIPCHK(hipStreamSynchronize(ar->stream));
-    frames_settle();
-    int mx = 0;
-    for (int j = 0; j < nJobs; j++) {
-      const size_t q = (size_t)jobs[j].nq;
-      if (jobs[j].bestOut) {
-        if (q) std::memcpy(jobs[j].bestOut, h + lay[j].oOut, q * 4);
-        continue;
-      }
-      if (jobs[j].claim) {
-        ClaimSpec* C = jobs[j].claim;
-        const int32_t* hd = reinterpret_cast<const int32_t*>(h + lay[j].oOut);
-        mx = hd[0] > mx ? hd[0] : mx;
-        if (hd[0] > K) continue;  // truncated lists: the call searches again with room for the largest
-        const bool ini = C->mode == CLAIM_INIT;
-        const size_t nOut = ini ? q : (size_t)jobs[j].f->n;
-        if (nOut) std::memcpy(C->match, hd + 4, nOut * 4);
-        if (jobs[j].producer && jobs[j].producer->inViewOut && q)
-          std::memcpy(jobs[j].producer->inViewOut, h + lay[j].oOut + pad(16 + nOut * 4), q);
-        *C->nMatches = hd[1];
-        C->rounds = hd[2];
-        t_lastClaimRounds = hd[2] + 1 > t_lastClaimRounds ? hd[2] + 1 : t_lastClaimRounds;
-        if (ini && q) { std::memcpy(C->prevX, hd + 4 + q, q * 4); std::memcpy(C->prevY, hd + 4 + 2 * q, q * 4); }
-        continue;
-      }
-      WindowResult* res = jobs[j].res;
-      res->count.assign(q, 0);
-      res->cand.resize(q * (size_t)K);
-      res->K = K;
-      if (q) {
-        std::memcpy(res->count.data(), h + lay[j].oOut, q * 4);
-        std::memcpy(res->cand.data(), h + lay[j].oOut + pad(q * 4), q * (size_t)K * 4);
-      }
-      for (size_t i = 0; i < q; i++) mx = res->count[i] > mx ? res->count[i] : mx;
-    }
-    if (mx <= K) return ORBFE_OK;
-    K = (mx + 7) & ~7;  // a window held more features than the list: search again with room for the largest
+    if (J.bestOut && J.gate && J.gur) TRY(up(a, &D.gateUr, J.gur, q));
+    if (J.bestOut && J.gate) TRY(up(a, &D.invSigma2, J.invSigma2, (size_t)J.nLevels));
+  }
+  if (const ClaimSpec* C = J.claim) {
+    if (C->checkOri && !J.f->resident) TRY(up(a, &D.angle, J.f->angle, n));  // (a resident frame has its angles on the device)
+    if (C->blocked) TRY(up(a, &D.blocked, C->blocked, n));
+    if (C->blockVal && !J.producer) TRY(up(a, &D.blockVal, C->blockVal, q));  // (a producer writes it: Observations() > 0)
+    if (C->checkOri) TRY(up(a, &D.qAngle, C->qAngle, q));
+  }
+  return hipSuccess;
+}
+
+// Region 2, a job's part: what comes back, fetched with the other jobs' by ONE down_range().  No kernel wants these adjacent
+// (k_window_claim takes header, match and the previous positions as separate pointers) or reads past the end of one.
+void stage_outputs(Arena* a, const WindowJob& J, int K, JobDev* D) {
+  const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
+  if (J.bestOut) {
+    D->best = carve<int32_t>(a, q);
+  } else if (!J.claim) {
+    D->count = carve<int32_t>(a, q);
+    D->cand = carve<uint32_t>(a, q * (size_t)K);
+  } else {
+    const bool ini = J.claim->mode == CLAIM_INIT;
+    D->header = carve<int32_t>(a, 4);
+    D->match = carve<int32_t>(a, ini ? q : n);
+    if (ini) { D->prevX = carve<float>(a, q); D->prevY = carve<float>(a, q); }
+    if (J.producer && J.producer->inViewOut) D->inView = carve<uint8_t>(a, q);
   }
 }
 
-int window_search(int device, const orbfe_frame_view* f, int nq, const float* qx, const float* qy, const float* qr,
-                  const int32_t* qmin, const int32_t* qmax, const uint8_t* qactive, const float* qur,
-                  const uint8_t* qdesc, int K0, WindowResult* res) {
-  WindowJob j{f, nq, qx, qy, qr, qmin, qmax, qactive, qur, qdesc, res};
-  return window_search_multi(device, &j, 1, K0);
+// k_window_claim keeps its per-feature owner stamps ([2 n], CLAIM_INIT [n]) in dynamic LDS, with the features' octave bytes
+// (RATIO) behind them.  A frame too large for that (~6800 features) gets the stamps in HBM; the octave bytes stay in LDS.
+struct OwnerPlace { size_t ints, ldsBytes; bool inLds; };
+OwnerPlace owner_place(const WindowJob& J) {
+  constexpr size_t kOwnerLds = 60 * 1024;
+  const size_t n = (size_t)J.f->n, ints = (J.claim->mode == CLAIM_INIT ? 1 : 2) * n, octBytes = J.claim->mode == CLAIM_RATIO ? n : 0;
+  const bool inLds = ints * 4 + octBytes <= kOwnerLds;
+  return OwnerPlace{ints, (inLds ? ints * 4 : 0) + octBytes, inLds};
+}
+
+// Region 3, job j's part: what never leaves the device -- the grid of an uploaded frame, the query arrays a producer
+// writes, the claim kernel's lists and scratch
+void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev) {
+  const WindowJob& J = jobs[j];
+  JobDev& D = dev[j];
+  const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
+  if (D.frameOf == j) { D.key = carve<uint32_t>(a, n); D.cell = carve<int32_t>(a, 3073); }
+  else if (D.frameOf >= 0) { D.key = dev[D.frameOf].key; D.cell = dev[D.frameOf].cell; }
+  if (J.producer) {
+    D.qx = carve<float>(a, q); D.qy = carve<float>(a, q); D.qr = carve<float>(a, q);
+    D.qmin = carve<int32_t>(a, q); D.qmax = carve<int32_t>(a, q);
+    D.qactive = carve<uint8_t>(a, q); D.blockVal = carve<uint8_t>(a, q);
+    if (D.withUr) D.qur = carve<float>(a, q);
+    if (D.withDesc) D.qdesc = carve<uint8_t>(a, q * 32);
+  }
+  if (J.claim) {
+    // k_window_claim reads a list as pairs of 16-byte requests, eight entries at a time and never past entry K: K is a
+    // multiple of 8 and carve() aligns the first list
+    D.count = carve<int32_t>(a, q); D.cand = carve<uint32_t>(a, q * (size_t)K);
+    D.choice = carve<int32_t>(a, q); D.link = carve<int32_t>(a, q);
+    const OwnerPlace o = owner_place(J);
+    if (!o.inLds) D.owner = carve<int32_t>(a, o.ints);
+    D.claimLds = o.ldsBytes;
+  }
+}
+
+ClaimJob claim_job(const WindowJob& J, const JobDev& D, int K) {
+  const ClaimSpec& C = *J.claim;
+  ClaimJob c{};
+  c.count = D.count; c.cand = D.cand; c.K = K; c.nq = J.nq; c.n = J.f->n;
+  c.active = D.qactive; c.blocked = D.blocked; c.blockVal = D.blockVal;
+  c.octave = D.oct; c.qAngle = D.qAngle; c.fAngle = C.checkOri ? D.angle : nullptr;
+  c.fx = D.x; c.fy = D.y; c.qx = D.qx; c.qy = D.qy; c.prevX = D.prevX; c.prevY = D.prevY;
+  c.mode = C.mode; c.maxDist = C.maxDist; c.checkOri = C.checkOri; c.nnratio = C.nnratio;
+  c.choice = D.choice; c.link = D.link; c.owner = D.owner; c.match = D.match; c.header = D.header;
+  return c;
+}
+
+WindowSearchJob search_job(const WindowJob& J, const JobDev& D, int K, int blockStart) {
+  GridFrame g{};
+  g.x = D.x; g.y = D.y; g.octave = D.oct; g.uRight = D.ur; g.desc = D.desc; g.n = J.f->n;
+  g.minX = J.f->min_x; g.minY = J.f->min_y;
+  g.wInv = 64.0f / (J.f->max_x - J.f->min_x);  // src/Frame.cc:109-110 (FRAME_GRID_COLS / ROWS)
+  g.hInv = 48.0f / (J.f->max_y - J.f->min_y);
+  WindowQueries w{};
+  w.x = D.qx; w.y = D.qy; w.r = D.qr; w.minLevel = D.qmin; w.maxLevel = D.qmax; w.active = D.qactive; w.ur = D.qur; w.desc = D.qdesc;
+  w.n = J.nq; w.K = K;
+  if (J.bestOut) { w.best = D.best; w.gateUr = D.gateUr; w.invSigma2 = D.invSigma2; w.gate = J.gate; w.maxDist = J.maxDist; }
+  return WindowSearchJob{g, D.key, D.cell, w, D.count, D.cand, blockStart};
+}
+
+// a producer job's k_project_frustum: the query arrays, written where the searches read them
+ProjectArgs project_args(const WindowJob& J, const JobDev& D) {
+  const FrustumProducer& P = *J.producer;
+  ProjectArgs pa{};
+  pa.table = P.table; pa.slot = D.slot; pa.skip = D.skip; pa.n = J.nq; pa.cam = P.pose; pa.limit = P.limit;
+  pa.qx = D.qx; pa.qy = D.qy; pa.qr = D.qr; pa.qmin = D.qmin; pa.qmax = D.qmax; pa.qactive = D.qactive; pa.qur = D.qur;
+  pa.qdesc = D.qdesc; pa.qobs = D.blockVal; pa.inViewCopy = D.inView;
+  pa.scale = D.scale; pa.th = P.th;
+  return pa;
+}
+
+// What arena_stage() leaves of a call: every job's pointers, the kernels' argument blocks and where they and the results are
+struct WindowCall {
+  std::vector<JobDev> dev;
+  std::vector<ClaimJob> claims;
+  std::vector<WindowSearchJob> searches;
+  ClaimJob* dClaims = nullptr;
+  WindowSearchJob* dSearches = nullptr;  // (a single job travels as kernel arguments)
+  uint8_t *outLo = nullptr, *outHi = nullptr;
+  size_t claimLds = 0;
+  int totalBlocks = 0;
+};
+
+// The arena of a call, in the order that keeps it at one copy each way: uploads | results | what stays on the device.  The
+// argument blocks hold device addresses, known once everything is carved: they get their room behind the other uploads
+// and are put() there at the end.
+hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, int K, WindowCall* c) {
+  *c = WindowCall{};
+  c->dev.resize((size_t)nJobs);
+  for (int j = 0; j < nJobs; j++) TRY(stage_inputs(a, jobs, j, c->dev.data()));
+  c->dClaims = carve<ClaimJob>(a, (size_t)nClaim);
+  c->dSearches = carve<WindowSearchJob>(a, nJobs > 1 ? (size_t)nJobs : 0);
+  c->outLo = carve<uint8_t>(a, 0);
+  for (int j = 0; j < nJobs; j++) stage_outputs(a, jobs[j], K, &c->dev[j]);
+  c->outHi = carve<uint8_t>(a, 0);
+  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data());
+  for (int j = 0; j < nJobs; j++) {
+    if (jobs[j].claim) {
+      c->claims.push_back(claim_job(jobs[j], c->dev[j], K));
+      if (c->dev[j].claimLds > c->claimLds) c->claimLds = c->dev[j].claimLds;
+    }
+    c->searches.push_back(search_job(jobs[j], c->dev[j], K, c->totalBlocks));
+    c->totalBlocks += (jobs[j].nq + 3) / 4;
+  }
+  TRY(put(a, c->dClaims, c->claims.data(), c->claims.size()));
+  if (nJobs > 1) TRY(put(a, c->dSearches, c->searches.data(), c->searches.size()));
+  return hipSuccess;
+}
+
+// The call on the thread's stream: one copy up, the producers, one grid build per uploaded frame, ONE window-search launch
+// for all jobs, one claim launch, one copy down
+hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCall& c, bool claimInit) {
+  for (int j = 0; j < nJobs; j++) TRY(frame_use(ar, jobs[j].f->resident));
+  TRY(flush(ar));
+  for (int j = 0; j < nJobs; j++)
+    if (jobs[j].producer) {
+      launch_project_frustum(ar->stream, project_args(jobs[j], c.dev[j]));
+      TRY(hipGetLastError());
+    }
+  for (int j = 0; j < nJobs; j++)
+    if (c.dev[j].frameOf == j) {
+      launch_grid_build(ar->stream, c.searches[j].f, c.dev[j].key, c.dev[j].cell);
+      TRY(hipGetLastError());
+    }
+  if (nJobs > 1) {
+    launch_window_search_multi(ar->stream, c.dSearches, nJobs, c.totalBlocks);
+  } else {
+    const WindowSearchJob& s = c.searches[0];
+    launch_window_search(ar->stream, s.f, s.sortedKey, s.cellOff, s.q, s.count, s.cand);
+  }
+  TRY(hipGetLastError());
+  if (!c.claims.empty()) {
+    launch_window_claim(ar->stream, c.dClaims, mirror_of(ar, c.dClaims), (int)c.claims.size(), c.claimLds, claimInit);
+    TRY(hipGetLastError());
+  }
+  return down_range(ar, c.outLo, c.outHi);
+}
+
+// Behind the synchronisation: every job's results out of the mirror, by mode.  Returns the longest list of the call; one
+// longer than K was truncated, and a claim job that saw one has no result yet.
+thread_local int t_lastClaimRounds = 0;
+int collect_results(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCall& c, int K) {
+  int mx = 0;
+  for (int j = 0; j < nJobs; j++) {
+    const WindowJob& J = jobs[j];
+    const JobDev& D = c.dev[j];
+    const size_t q = (size_t)J.nq;
+    if (J.bestOut) {
+      if (q) std::memcpy(J.bestOut, mirror_of(ar, D.best), q * 4);
+    } else if (ClaimSpec* C = J.claim) {
+      const int32_t* hd = mirror_of(ar, D.header);  // largest list length, matches, rounds
+      mx = hd[0] > mx ? hd[0] : mx;
+      if (hd[0] > K) continue;
+      const bool ini = C->mode == CLAIM_INIT;
+      const size_t nOut = ini ? q : (size_t)J.f->n;
+      if (nOut) std::memcpy(C->match, mirror_of(ar, D.match), nOut * 4);
+      if (D.inView && q) std::memcpy(J.producer->inViewOut, mirror_of(ar, D.inView), q);
+      *C->nMatches = hd[1];
+      C->rounds = hd[2];
+      t_lastClaimRounds = hd[2] + 1 > t_lastClaimRounds ? hd[2] + 1 : t_lastClaimRounds;
+      if (ini && q) { std::memcpy(C->prevX, mirror_of(ar, D.prevX), q * 4); std::memcpy(C->prevY, mirror_of(ar, D.prevY), q * 4); }
+    } else {
+      const int32_t* cnt = mirror_of(ar, D.count);
+      const uint32_t* cand = mirror_of(ar, D.cand);
+      J.res->count.assign(cnt, cnt + q);
+      J.res->cand.assign(cand, cand + q * (size_t)K);
+      J.res->K = K;
+      for (size_t i = 0; i < q; i++) mx = cnt[i] > mx ? cnt[i] : mx;
+    }
+  }
+  return mx;
+}
+
+// Upload frames (unless resident: keypoint arrays, descriptors and grid are on the device already) + queries, build the
+// grids, search every window; grows K until every list fits.
+int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
+  UnsettledScope unsettledScope;
+  t_lastClaimRounds = 0;
+  int nClaim = 0;
+  bool claimInit = false;
+  for (int j = 0; j < nJobs; j++) {
+    const WindowJob& J = jobs[j];
+    if (J.f->resident && J.f->resident->device != device) return fail(ORBFE_ERR_INVALID, "resident frame lives on another device");
+    if (J.producer && (!J.claim || J.claim->mode != CLAIM_RATIO)) return fail(ORBFE_ERR_INVALID, "a producer needs a CLAIM_RATIO job");
+    if (!J.claim) continue;
+    if (J.nq > 0x1fffff) return fail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
+    if (nClaim && claimInit != (J.claim->mode == CLAIM_INIT)) return fail(ORBFE_ERR_INVALID, "mixed claim forms in one call");
+    claimInit = J.claim->mode == CLAIM_INIT;
+    nClaim++;
+  }
+  WindowCall call;
+  for (int K = ((K0 < 8 ? 8 : K0) + 7) & ~7;;) {  // (k_window_claim reads the lists eight entries at a time)
+    Arena* ar;
+    auto stage = [&](Arena* a) { return stage_call(a, jobs, nJobs, nClaim, K, &call); };
+    HIPCHK(arena_stage(device, &ar, stage));
+    HIPCHK(enqueue_call(ar, jobs, nJobs, call, claimInit));
+    HIPCHK(hipStreamSynchronize(ar->stream));
+    frames_settle();
+    const int mx = collect_results(ar, jobs, nJobs, call, K);
+    if (mx <= K) return ORBFE_OK;
+    K = (mx + 7) & ~7;  // a window held more features than the list: search again with room for the largest
+  }
 }
 
 }  // namespace
@@ -1474,8 +1458,10 @@ extern "C" int orbfe_features_in_area(int device, const orbfe_frame_view* frame,
     return fail(ORBFE_ERR_INVALID, "features_in_area: bad argument");
   if (n_queries == 0) return ORBFE_OK;
   WindowResult res;
-  const int rc = window_search(device, frame, n_queries, x, y, r, min_level, max_level, nullptr, nullptr, nullptr,
-                               capacity, &res);
+  WindowJob job;
+  job.f = frame; job.nq = n_queries; job.qx = x; job.qy = y; job.qr = r; job.qmin = min_level; job.qmax = max_level;
+  job.res = &res;
+  const int rc = window_search_multi(device, &job, 1, capacity);
   if (rc != ORBFE_OK) return rc;
   bool over = false;
   for (int i = 0; i < n_queries; i++) {
@@ -1521,7 +1507,9 @@ extern "C" int orbfe_search_by_projection(int device, const orbfe_frame_view* F,
   C.mode = CLAIM_RATIO; C.maxDist = 100 /* TH_HIGH */; C.nnratio = nnratio;
   C.blocked = blocked; C.blockVal = mp_obs_positive;
   C.match = match; C.nMatches = n_matches;
-  WindowJob job{F, n_mp, proj_x, proj_y, qr.data(), qmin.data(), qmax.data(), in_view, proj_xr, mp_desc, nullptr};
+  WindowJob job;
+  job.f = F; job.nq = n_mp; job.qx = proj_x; job.qy = proj_y; job.qr = qr.data(); job.qmin = qmin.data(); job.qmax = qmax.data();
+  job.qactive = in_view; job.qur = proj_xr; job.qdesc = mp_desc;
   job.claim = &C;
   return window_search_multi(device, &job, 1, 32);
 }
@@ -1676,7 +1664,8 @@ extern "C" int orbfe_search_local_points(orbfe_mappoints* mp, int n, const int32
   C.mode = CLAIM_RATIO; C.maxDist = 100 /* TH_HIGH */; C.nnratio = nnratio;
   C.blocked = blocked;
   C.match = match; C.nMatches = n_matches;
-  WindowJob job{F, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  WindowJob job;
+  job.f = F; job.nq = n;
   job.claim = &C;
   job.producer = &P;
   return window_search_multi(mp->device, &job, 1, 32);
@@ -1720,7 +1709,9 @@ extern "C" int orbfe_search_by_projection_last_frame(int device, const orbfe_fra
   C.blockVal = obs_positive;
   C.qAngle = last_angle;
   C.match = match_cur; C.nMatches = n_matches;
-  WindowJob job{Cur, n_last, u, v, qr.data(), qmin.data(), qmax.data(), valid, Cur->u_right ? qur.data() : nullptr, mp_desc, nullptr};
+  WindowJob job;
+  job.f = Cur; job.nq = n_last; job.qx = u; job.qy = v; job.qr = qr.data(); job.qmin = qmin.data(); job.qmax = qmax.data();
+  job.qactive = valid; job.qur = Cur->u_right ? qur.data() : nullptr; job.qdesc = mp_desc;
   job.claim = &C;
   return window_search_multi(device, &job, 1, 32);
 }
@@ -1771,7 +1762,9 @@ extern "C" int orbfe_search_by_projection_keyframe(int device, const orbfe_frame
   C.mode = CLAIM_BEST; C.maxDist = orb_dist; C.checkOri = check_orientation ? 1 : 0;
   C.blocked = blocked; C.qAngle = kf_angle;
   C.match = match_cur; C.nMatches = n_matches;
-  WindowJob job{Cur, n, u, v, qr.data(), qmin.data(), qmax.data(), valid, nullptr, mp_desc, nullptr};
+  WindowJob job;
+  job.f = Cur; job.nq = n; job.qx = u; job.qy = v; job.qr = qr.data(); job.qmin = qmin.data(); job.qmax = qmax.data();
+  job.qactive = valid; job.qdesc = mp_desc;
   job.claim = &C;
   return window_search_multi(device, &job, 1, 32);
 }
@@ -1813,7 +1806,9 @@ extern "C" int orbfe_search_by_projection_keyframe_multi(int device, const orbfe
     C.blocked = blocked ? blocked[k] : nullptr;
     C.qAngle = check_orientation ? kf_angle[k] : nullptr;
     C.match = match_cur + (size_t)k * Cur->n; C.nMatches = &n_matches[k];
-    WindowJob job{Cur, n[k], u[k], v[k], qr[k].data(), qmin[k].data(), qmax[k].data(), valid[k], nullptr, mp_desc[k], nullptr};
+    WindowJob job;
+    job.f = Cur; job.nq = n[k]; job.qx = u[k]; job.qy = v[k]; job.qr = qr[k].data(); job.qmin = qmin[k].data(); job.qmax = qmax[k].data();
+    job.qactive = valid[k]; job.qdesc = mp_desc[k];
     job.claim = &C;
     wj.push_back(job);
   }
@@ -1844,7 +1839,9 @@ extern "C" int orbfe_search_by_projection_sim3(int device, const orbfe_frame_vie
   C.mode = CLAIM_BEST; C.maxDist = 50 /* TH_LOW */;
   C.blocked = matched;
   C.match = match; C.nMatches = n_matches;
-  WindowJob job{KF, n, u, v, qr.data(), qmin.data(), qmax.data(), valid, nullptr, mp_desc, nullptr};
+  WindowJob job;
+  job.f = KF; job.nq = n; job.qx = u; job.qy = v; job.qr = qr.data(); job.qmin = qmin.data(); job.qmax = qmax.data();
+  job.qactive = valid; job.qdesc = mp_desc;
   job.claim = &C;
   return window_search_multi(device, &job, 1, 32);
 }
@@ -1874,7 +1871,9 @@ extern "C" int orbfe_search_for_initialization(int device, const orbfe_frame_vie
   C.qAngle = F1->angle;
   C.match = match12; C.nMatches = n_matches;
   C.prevX = prev_x; C.prevY = prev_y;
-  WindowJob job{F2, n1, prev_x, prev_y, qr.data(), qlv.data(), qlv.data(), active.data(), nullptr, F1->desc, nullptr};
+  WindowJob job;
+  job.f = F2; job.nq = n1; job.qx = prev_x; job.qy = prev_y; job.qr = qr.data(); job.qmin = qlv.data(); job.qmax = qlv.data();
+  job.qactive = active.data(); job.qdesc = F1->desc;
   job.claim = &C;
   return window_search_multi(device, &job, 1, 128);
 }
@@ -1903,7 +1902,9 @@ int window_best_multi(const char* who, int device, BestJob* jobs, int nJobs, int
     // The whole inner search runs on the device (round 4): the window scan, the octave filter, Fuse's chi-square gate
     // (src/ORBmatcher.cc:1036-1058) and the first minimum with its distance bound -- a point's best keypoint depends on no
     // other point, so there is no claim loop to replay: 4 bytes per point come back instead of a 32-entry candidate list
-    WindowJob w{J.KF, J.n, J.u, J.v, qr[j].data(), qmin[j].data(), qmax[j].data(), J.valid, nullptr, J.desc, nullptr};
+    WindowJob w;
+    w.f = J.KF; w.nq = J.n; w.qx = J.u; w.qy = J.v; w.qr = qr[j].data(); w.qmin = qmin[j].data(); w.qmax = qmax[j].data();
+    w.qactive = J.valid; w.qdesc = J.desc;
     w.bestOut = J.best;
     w.gate = gate ? 1 : 0;
     w.gur = (gate && J.KF->u_right) ? J.ur : nullptr;
@@ -1914,13 +1915,6 @@ int window_best_multi(const char* who, int device, BestJob* jobs, int nJobs, int
   }
   if (wj.empty()) return ORBFE_OK;
   return window_search_multi(device, wj.data(), (int)wj.size(), 8);
-}
-int window_best(const char* who, int device, const orbfe_frame_view* KF, const float* sf, int n_levels,
-                const float* inv_level_sigma2, int n, const uint8_t* valid, const float* u, const float* v,
-                const float* ur, const int32_t* level, const uint8_t* desc, float th, bool gate, int max_dist,
-                int32_t* best) {
-  BestJob j{KF, sf, inv_level_sigma2, n, valid, u, v, ur, level, desc, best};
-  return window_best_multi(who, device, &j, 1, n_levels, th, gate, max_dist);
 }
 }  // namespace
 
@@ -1963,8 +1957,8 @@ extern "C" int orbfe_fuse_search(int device, const orbfe_frame_view* KF, const f
   for (int i = 0; i < KF->n; i++)
     if (chi2_gate && (KF->octave[i] < 0 || KF->octave[i] >= n_levels))
       return fail(ORBFE_ERR_INVALID, "fuse_search: keypoint octave outside the pyramid");
-  return window_best("fuse_search", device, KF, scale_factors, n_levels, inv_level_sigma2, n, valid, u, v, ur, level,
-                     mp_desc, th, chi2_gate != 0, 50 /* TH_LOW */, best_idx);
+  BestJob job{KF, scale_factors, inv_level_sigma2, n, valid, u, v, ur, level, mp_desc, best_idx};
+  return window_best_multi("fuse_search", device, &job, 1, n_levels, th, chi2_gate != 0, 50 /* TH_LOW */);
 }
 
 extern "C" int orbfe_search_by_sim3(int device, const orbfe_frame_view* KF1, const orbfe_frame_view* KF2,

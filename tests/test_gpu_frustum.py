@@ -210,3 +210,51 @@ def test_search_local_points_equals_the_two_step_form_and_the_oracle(local_map, 
     R.close()
     print(f"stereo={stereo} th={th}: {nm} matches of {int(s32['in_view'].sum())} points in view")
     assert nm > 100
+
+
+def _crowd_on_a_point(sc, s32, n_crowd, seed):
+    """_frame_for's monocular / stereo frame with n_crowd more key points inside 3 px of one visible map point's projection, at
+    its predicted level: that point's window holds more than the 32 entries the search's lists start with.
+    -> (FrameView, oracle Frame, index of the point)"""
+    import oracle_lib as O
+    from orb_slam2_annotate_amd import FrameView
+    rng = np.random.default_rng(seed)
+    F, _ = _frame_for(sc, s32, True, seed)
+    inside = (s32["in_view"] != 0) & (s32["proj_x"] > 20) & (s32["proj_x"] < 1220) & (s32["proj_y"] > 20) & (s32["proj_y"] < 355) & \
+        (s32["level"] >= 1)
+    p = int(np.flatnonzero(inside)[0])
+    x, y, octv, desc, ang, ur = F.x.copy(), F.y.copy(), F.octave.copy(), F.desc.copy(), F.angle.copy(), F.u_right.copy()
+    kp = rng.choice(F.N, n_crowd, replace=False)
+    x[kp] = (s32["proj_x"][p] + rng.uniform(-3, 3, n_crowd)).astype(np.float32)
+    y[kp] = (s32["proj_y"][p] + rng.uniform(-3, 3, n_crowd)).astype(np.float32)
+    octv[kp] = s32["level"][p] - rng.integers(0, 2, n_crowd)
+    desc[kp] = sc["desc"][p] ^ (rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8) & rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8) &
+                                rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8))
+    ur[kp] = -1.0  # (no stereo check on the crowd)
+    return (FrameView(x, y, octv, desc, fr.BOUNDS, angle=ang, u_right=ur), O.Frame(x, y, octv, desc, fr.BOUNDS, angle=ang, u_right=ur), p)
+
+
+@pytest.mark.parametrize("n_crowd", [40, 65])
+def test_search_local_points_grows_its_lists(local_map, oracle_mod, n_crowd):
+    """A map point whose window holds more key points than a list has entries: the one-call form (k_project_frustum writes
+    the queries on the device) searches again with longer lists and still equals the two-step form and the oracle."""
+    from orb_slam2_annotate_amd import ORBmatcher
+    sc, slot, mp, s32 = local_map
+    pose = _pose(sc)
+    F, Fo, p = _crowd_on_a_point(sc, s32, n_crowd, seed=21)
+    lv = int(s32["level"][p])
+    # the oracle's own window of that point, at the smaller of the two radii (RadiusByViewingCos): more than 32 candidates
+    assert Fo.features_in_area(s32["proj_x"][p], s32["proj_y"][p], 2.5 * 3.0 * SF[lv], lv - 1, lv).size >= n_crowd > 32
+    obs = ((sc["flags"] >> 1) & 1).astype(np.uint8)
+    n_orc, m_orc = oracle_mod.search_by_projection_mappoints(Fo, SF, None, s32["in_view"], s32["level"], s32["view_cos"], s32["proj_x"],
+                                                             s32["proj_y"], s32["proj_xr"], sc["desc"], obs, 3.0, 0.8)
+    q = mp.ProjectInFrustum(slot, pose, fr.LIMIT, skip=sc["skip"])
+    n_two, m_two = ORBmatcher(0.8).SearchByProjection(F, SF, q["in_view"], q["level"], q["view_cos"], q["proj_x"], q["proj_y"], sc["desc"],
+                                                      th=3.0, proj_xr=q["proj_xr"], mp_obs_positive=obs)
+    R = F.upload()
+    for frame in (R, F):  # resident, host arrays
+        nm, match, iv = mp.SearchLocalPoints(frame, slot, pose, SF, th=3.0, nnratio=0.8, viewing_cos_limit=fr.LIMIT, skip=sc["skip"])
+        assert np.array_equal(iv, s32["in_view"]) and np.array_equal(iv, q["in_view"])
+        assert nm == n_two == n_orc and np.array_equal(match, m_two) and np.array_equal(match, m_orc)
+    R.close()
+    assert nm > 100

@@ -536,3 +536,152 @@ def test_grid_with_a_crowded_cell(amd, n_crowd):
     for q in range(len(qx)):
         assert got[q].tolist() == Fo.features_in_area(qx[q], qy[q], r[q], lo[q], hi[q]).tolist(), q
     assert len(got[1]) > n_crowd // 3
+
+
+# ---- the window searches' staging: list regrowth in claim mode, shared uploads, arena reuse, empty edges ----
+
+def _crowded_case(n_crowd, seed=300):
+    """A frame of 300 spread-out key points plus n_crowd of octave 2 inside a 6-px disc around (320, 240), and 100 projected
+    points of which point 0 sits on the crowd: its window holds the whole crowd in every projection search."""
+    rng = np.random.default_rng(seed + n_crowd)
+    base = rng.integers(0, 256, 32, dtype=np.uint8)
+    cx, cy, co, ca, cd = _cluster(rng, n_crowd, base, 2, 20)
+    rx, ry, ro, ra, rd, _ = _random_frame(rng, 300, spread=0.0)
+    perm = rng.permutation(n_crowd + 300)
+    x, y, octv, ang = (np.concatenate(p)[perm] for p in ((cx, rx), (cy, ry), (co, ro), (ca, ra)))
+    desc = np.concatenate([cd, rd])[perm]
+    src, u, v, md, level, valid, qa = _projected(rng, x, y, octv, ang, desc, 100)
+    u[0], v[0], level[0], valid[0], md[0] = 320.0, 240.0, 2, 1, base
+    return (x, y, octv, ang, desc), (u, v, md, level, valid, qa)
+
+
+@pytest.mark.parametrize("n_crowd", [40, 65])
+def test_claim_searches_grow_their_lists(amd, n_crowd):
+    """A window with more key points than the 32 entries a claim search starts with: the call searches again with longer
+    lists (CLAIM_BEST: the key-frame form, CLAIM_RATIO: the map-point form) and still equals the oracle."""
+    frame, (u, v, md, level, valid, qa) = _crowded_case(n_crowd)
+    F, Fo = _both(amd, *frame, None)
+    # the oracle's own windows of point 0 hold more than 32 candidates: no pass without regrowing
+    assert Fo.features_in_area(320.0, 240.0, 10.0 * SF[2], 1, 3).size >= n_crowd > 32
+    assert Fo.features_in_area(320.0, 240.0, 4.0 * 3.0 * SF[2], 1, 2).size >= n_crowd
+    n_ref, ref = orc.search_by_projection_reloc(Fo, SF, valid, u, v, level, qa, md, None, 10.0, 100, True)
+    n_got, got = amd.ORBmatcher(0.9, True).SearchByProjectionKeyFrame(F, SF, valid, u, v, level, qa, md, 10.0, 100)
+    assert (n_got, got.tolist()) == (n_ref, ref.tolist()) and n_ref > 20
+    view_cos = np.full(len(u), 0.9, np.float32)
+    obs = (np.arange(len(u)) % 3 > 0).astype(np.uint8)
+    n_ref, ref = orc.search_by_projection_mappoints(Fo, SF, None, valid, level, view_cos, u, v, None, md, obs, 3.0, 0.8)
+    n_got, got = amd.ORBmatcher(0.8).SearchByProjection(F, SF, valid, level, view_cos, u, v, md, th=3.0, mp_obs_positive=obs)
+    assert (n_got, got.tolist()) == (n_ref, ref.tolist()) and n_ref > 20
+
+
+def test_fuse_search_multi_shares_uploads(amd):
+    """Three key-frame views of which two are the SAME host-array frame object (one upload, one grid) and one is resident,
+    the shared mp_desc, chi-square gate and stereo: equal to three single calls and to the oracle."""
+    rng = np.random.default_rng(310)
+    n = 250
+    inv_sigma2 = (1.0 / (SF * SF)).astype(np.float32)
+    md = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    frames = []
+    for nk in (300, 350):
+        x, y, octv, ang, desc, ur = _random_frame(rng, nk, True, spread=0.0)
+        near = rng.choice(nk, n // 2, replace=False)  # key points whose descriptors are a few bits from the first map points'
+        desc[near] = md[: n // 2] ^ (rng.integers(0, 256, (n // 2, 32), dtype=np.uint8) & rng.integers(0, 256, (n // 2, 32), dtype=np.uint8) &
+                                     rng.integers(0, 256, (n // 2, 32), dtype=np.uint8))
+        frames.append((x, y, octv, ang, desc, np.where(ur > 0, ur, -1.0).astype(np.float32), near))
+    view = lambda f: amd.FrameView(f[0], f[1], f[2], f[4], BOUNDS, angle=f[3], u_right=f[5])  # noqa: E731
+    A, B = view(frames[0]), view(frames[1]).upload()
+    views, m = [A, B, A], amd.ORBmatcher(0.6)
+    U, V, UR, LV, VA, refs = [], [], [], [], [], []
+    for w in (0, 1, 0):
+        x, y, octv, ang, desc, ur, near = frames[w]
+        src = np.concatenate([near, rng.integers(0, len(x), n - n // 2)])
+        U.append((x[src] + rng.normal(0, 1.2, n)).astype(np.float32))
+        V.append((y[src] + rng.normal(0, 1.2, n)).astype(np.float32))
+        UR.append(np.where(ur[src] >= 0, ur[src] + rng.normal(0, 1.0, n), U[-1] - 10).astype(np.float32))
+        LV.append(np.clip(octv[src] + rng.integers(0, 2, n), 0, 7).astype(np.int32))
+        VA.append((rng.random(n) < 0.85).astype(np.uint8))
+        refs.append(orc.fuse_search(orc.Frame(x, y, octv, desc, BOUNDS, angle=ang, u_right=ur), SF, inv_sigma2, VA[-1], U[-1], V[-1],
+                                    UR[-1], LV[-1], md, 3.0, True))
+    got = m.FuseSearchMulti(views, SF, np.stack(VA), np.stack(U), np.stack(V), np.stack(LV), md, th=3.0,
+                            inv_level_sigma2=inv_sigma2, ur=np.stack(UR))
+    for k in range(3):
+        single = m.FuseSearch(views[k], SF, VA[k], U[k], V[k], LV[k], md, th=3.0, inv_level_sigma2=inv_sigma2, ur=UR[k])
+        assert got[k].tolist() == refs[k].tolist() == single.tolist(), k
+    assert min(int((r >= 0).sum()) for r in refs) > 30
+    B.close()
+
+
+def test_arena_and_mirror_reuse_on_one_thread(amd):
+    """Calls of very different sizes and modes one after the other on one thread (one arena, one pinned mirror): a large
+    CLAIM_RATIO call, one query, a list-mode call, a CLAIM_INIT call, the large call again -- each equal to the oracle, the
+    first and the last identical.  Stale mirror bytes or a dirty range that spans a carved region would show here."""
+    rng = np.random.default_rng(320)
+    x, y, octv, ang, desc, _ = _random_frame(rng, 400, spread=0.0)
+    octv[rng.random(400) < 0.5] = 0
+    F, Fo = _both(amd, x, y, octv, ang, desc, None)
+    n_mp = 2000
+    src, px, py, md = _map_points(rng, x, y, octv, desc, n_mp, 1.5)
+    level = np.clip(octv[src] + rng.integers(0, 2, n_mp), 0, 7).astype(np.int32)
+    in_view = (rng.random(n_mp) < 0.85).astype(np.uint8)
+    view_cos = rng.uniform(0.99, 1.0, n_mp).astype(np.float32)
+    blocked = (rng.random(400) < 0.1).astype(np.uint8)
+    m = amd.ORBmatcher(0.8, True)
+    large_ref = orc.search_by_projection_mappoints(Fo, SF, blocked, in_view, level, view_cos, px, py, None, md, None, 3.0, 0.8)
+
+    def large():
+        n_got, got = m.SearchByProjection(F, SF, in_view, level, view_cos, px, py, md, th=3.0, blocked=blocked)
+        assert (n_got, got.tolist()) == (large_ref[0], large_ref[1].tolist())
+        return n_got, got.copy()
+    first = large()
+    assert first[0] > 100
+    one = slice(5, 6)  # one query
+    n_ref, ref = orc.search_by_projection_reloc(Fo, SF, np.ones(1, np.uint8), px[one], py[one], level[one], ang[src][one], md[one], None, 10.0, 100, True)
+    n_got, got = amd.ORBmatcher(0.9, True).SearchByProjectionKeyFrame(F, SF, np.ones(1, np.uint8), px[one], py[one], level[one],
+                                                                       ang[src][one], md[one], 10.0, 100)
+    assert (n_got, got.tolist()) == (n_ref, ref.tolist())
+    qx, qy = px[:50].copy(), py[:50].copy()
+    r = rng.choice(np.array([3.0, 15.0, 64.0], np.float32), 50)
+    lists = F.GetFeaturesInArea(qx, qy, r, -1, -1, capacity=16)
+    for q in range(50):
+        assert lists[q].tolist() == Fo.features_in_area(qx[q], qy[q], r[q], -1, -1).tolist(), q
+    # SearchForInitialization: 300 level-0 key points that are noisy copies of the frame's
+    s1 = rng.integers(0, 400, 300)
+    x1 = (x[s1] + rng.normal(0, 2.0, 300)).astype(np.float32)
+    y1 = (y[s1] + rng.normal(0, 2.0, 300)).astype(np.float32)
+    o1 = np.where(rng.random(300) < 0.9, 0, 1).astype(np.int32)
+    d1 = desc[s1] ^ (rng.integers(0, 256, (300, 32), dtype=np.uint8) & rng.integers(0, 256, (300, 32), dtype=np.uint8) &
+                     rng.integers(0, 256, (300, 32), dtype=np.uint8))
+    F1, O1 = _both(amd, x1, y1, o1, ang[s1], d1, None)
+    prev = np.stack([x1, y1], axis=1).astype(np.float32)
+    n_ref, ref, prev_ref = orc.search_for_initialization(O1, Fo, prev.copy(), 30, 0.9, True)
+    prev_got = prev.copy()
+    n_got, got = amd.ORBmatcher(0.9, True).SearchForInitialization(F1, F, prev_got, 30)
+    assert (n_got, got.tolist()) == (n_ref, ref.tolist()) and np.array_equal(prev_got, prev_ref) and n_ref > 20
+    last = large()
+    assert first[0] == last[0] and np.array_equal(first[1], last[1])
+
+
+def test_empty_frames_and_a_monocular_frame_with_right_coordinates(amd):
+    """The entry points that return early on a frame without key points, and a frame without mvuRight searched with and
+    without projected right coordinates (the stereo check does not run: both equal the monocular oracle)."""
+    rng = np.random.default_rng(330)
+    x, y, octv, ang, desc, _ = _random_frame(rng, 300, spread=0.0)
+    src, u, v, md, level, valid, qa = _projected(rng, x, y, octv, ang, desc, 120)
+    z = np.zeros(0, np.float32)
+    E, _ = _both(amd, z, z, np.zeros(0, np.int32), z, np.zeros((0, 32), np.uint8), None)
+    vc = np.full(120, 0.9, np.float32)
+    m = amd.ORBmatcher(0.8, True)
+    for n_got, got in (m.SearchByProjection(E, SF, valid, level, vc, u, v, md, th=3.0),
+                       m.SearchByProjectionLastFrame(E, SF, valid, u, v, level, qa, md, 15.0),
+                       m.SearchByProjectionKeyFrame(E, SF, valid, u, v, level, qa, md, 10.0, 100),
+                       m.SearchByProjectionSim3(E, SF, valid, u, v, level, md, 10.0)):
+        assert n_got == 0 and got.size == 0
+    assert (m.FuseSearch(E, SF, valid, u, v, level, md, th=3.0) == -1).all()
+    cnt, got = m.SearchByProjectionKeyFrameMulti(E, SF, [dict(valid=valid, u=u, v=v, level=level, kf_angle=qa, mp_desc=md, th=10.0, ORBdist=100)])
+    assert cnt.tolist() == [0] and got.size == 0
+    F, Fo = _both(amd, x, y, octv, ang, desc, None)
+    n_ref, ref = orc.search_by_projection_mappoints(Fo, SF, None, valid, level, vc, u, v, None, md, None, 3.0, 0.8)
+    pxr = (u - 10.0).astype(np.float32)
+    for xr in (None, pxr):
+        n_got, got = m.SearchByProjection(F, SF, valid, level, vc, u, v, md, th=3.0, proj_xr=xr)
+        assert (n_got, got.tolist()) == (n_ref, ref.tolist()) and n_ref > 20
