@@ -856,6 +856,20 @@ int64_t orc_distance_calls(void) { return g_distance_calls; }
    distance count): row-bucket entries scanned (src/Frame.cc:573-595), SAD refinements entered (:598-652) */
 static __thread int64_t g_stereo_scanned = 0, g_stereo_sad = 0;
 void orc_stereo_counters(int64_t *out) { out[0] = g_stereo_scanned; out[1] = g_stereo_sad; }
+/* one counter per exit of the per-keypoint loop of the last orc_compute_stereo_matches call of this thread (the order
+   is ORC_SB_* below and in orb_oracle.h); the tests use them to show that a case reaches the branch it was built for.
+   They change no result. */
+enum { ORC_SB_INVALID_RECORD, ORC_SB_ROW_OUT_OF_RANGE, ORC_SB_EMPTY_ROW, ORC_SB_MAXU_NEGATIVE, ORC_SB_NO_CANDIDATE,
+       ORC_SB_HAMMING_ABOVE_TH, ORC_SB_INIU_NEGATIVE, ORC_SB_ENDU_PAST_COLS, ORC_SB_GUARD_CY_LOW, ORC_SB_GUARD_CY_HIGH,
+       ORC_SB_GUARD_CXL_LOW, ORC_SB_GUARD_CXL_HIGH, ORC_SB_GUARD_CXR_LOW, ORC_SB_BESTINC_LOW_END,
+       ORC_SB_BESTINC_HIGH_END, ORC_SB_DELTA_OUT_OF_RANGE, ORC_SB_DELTA_NAN_PASSED, ORC_SB_DISPARITY_OUT_OF_RANGE,
+       ORC_SB_DISPARITY_CLAMPED, ORC_SB_ACCEPTED, ORC_SB_MEDIAN_REMOVED, ORC_SB_COUNT };
+static __thread int64_t g_stereo_branch[ORC_SB_COUNT];
+int orc_stereo_branch_counts(int64_t *out, int n) {
+  for (int i = 0; i < n && i < ORC_SB_COUNT; i++) out[i] = g_stereo_branch[i];
+  return ORC_SB_COUNT;
+}
+#define SB(k) (g_stereo_branch[ORC_SB_##k]++)
 
 int orc_descriptor_distance(const uint8_t *a, const uint8_t *b) { /* :1828-1844 */
   int dist = 0;
@@ -1060,6 +1074,10 @@ int orc_search_for_triangulation(const uint8_t *desc1, const uint8_t *has_mp1, c
 /* ------------------------------------------------------------------ */
 /* Frame::ComputeStereoMatches: src/Frame.cc:512-686                   */
 /* ------------------------------------------------------------------ */
+/* the parabola fit of :648, as the stereo function below takes it (exported so a test can compare it with a double evaluation) */
+float orc_stereo_delta_r(float dist1, float dist2, float dist3) {
+  return (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
+}
 typedef struct { int d, i; } distidx;
 static int distidx_cmp(const void *a, const void *b) {
   const distidx *A = (const distidx *)a, *B = (const distidx *)b;
@@ -1103,19 +1121,20 @@ int orc_compute_stereo_matches(const orc_extractor *e, int W, int H, const orc_k
   int nDist = 0;
   g_stereo_scanned = 0;
   g_stereo_sad = 0;
+  memset(g_stereo_branch, 0, sizeof(g_stereo_branch));
   for (int iL = 0; iL < N; iL++) {
     const orc_keypoint *kl = &kpL[iL];
     const int levelL = kl->octave;
     const float vL = kl->y, uL = kl->x;
     /* records no extractor writes: the reference indexes its tables out of range with them; here "no stereo" */
-    if (levelL < 0 || levelL >= e->nlevels || !(fabsf(uL) < 3.0e38f) || !(fabsf(vL) < 3.0e38f)) continue;
+    if (levelL < 0 || levelL >= e->nlevels || !(fabsf(uL) < 3.0e38f) || !(fabsf(vL) < 3.0e38f)) { SB(INVALID_RECORD); continue; }
     const int row = (int)vL;
-    if (row < 0 || row >= nRows) continue;
-    if (rowCnt[row] == 0) continue;
+    if (row < 0 || row >= nRows) { SB(ROW_OUT_OF_RANGE); continue; }
+    if (rowCnt[row] == 0) { SB(EMPTY_ROW); continue; }
     const float minU = uL - maxD, maxU = uL - minD;
-    if (maxU < 0) continue;
+    if (maxU < 0) { SB(MAXU_NEGATIVE); continue; }
     int bestDist = TH_HIGH;
-    int bestIdxR = 0;
+    int bestIdxR = 0, nInRange = 0;
     const uint8_t *dL = descL + (size_t)iL * 32;
     g_stereo_scanned += rowCnt[row];
     for (int iC = 0; iC < rowCnt[row]; iC++) {
@@ -1124,6 +1143,7 @@ int orc_compute_stereo_matches(const orc_extractor *e, int W, int H, const orc_k
       if (kr->octave < levelL - 1 || kr->octave > levelL + 1) continue;
       const float uR = kr->x;
       if (uR >= minU && uR <= maxU) {
+        nInRange++;
         const int dist = orc_descriptor_distance(dL, descR + (size_t)iR * 32);
         if (dist < bestDist) { bestDist = dist; bestIdxR = iR; }
       }
@@ -1143,10 +1163,15 @@ int orc_compute_stereo_matches(const orc_extractor *e, int W, int H, const orc_k
       float vDists[11];
       const float iniu = scaleduR0 + L - w;
       const float endu = scaleduR0 + L + w + 1;
-      if (iniu < 0 || endu >= (float)lw[lv]) continue;
+      if (iniu < 0) { SB(INIU_NEGATIVE); continue; }
+      if (endu >= (float)lw[lv]) { SB(ENDU_PAST_COLS); continue; }
       /* rowRange / colRange (:609-610, :626) assert 0 <= start <= end <= size: a patch that leaves the level throws in
          the reference; "no stereo" here */
-      if (cy < w || cy + w >= lh[lv] || cxL < w || cxL + w >= lw[lv] || (int)scaleduR0 < L + w) continue;
+      if (cy < w) { SB(GUARD_CY_LOW); continue; }
+      if (cy + w >= lh[lv]) { SB(GUARD_CY_HIGH); continue; }
+      if (cxL < w) { SB(GUARD_CXL_LOW); continue; }
+      if (cxL + w >= lw[lv]) { SB(GUARD_CXL_HIGH); continue; }
+      if ((int)scaleduR0 < L + w) { SB(GUARD_CXR_LOW); continue; }
       g_stereo_sad++;
       const int cL = IL[(size_t)cy * st + cxL];
       for (int incR = -L; incR <= +L; incR++) {
@@ -1163,23 +1188,27 @@ int orc_compute_stereo_matches(const orc_extractor *e, int W, int H, const orc_k
         if (dist < (float)bestD) { bestD = (int)dist; bestincR = incR; }
         vDists[L + incR] = dist;
       }
-      if (bestincR == -L || bestincR == L) continue;
+      if (bestincR == -L) { SB(BESTINC_LOW_END); continue; }
+      if (bestincR == L) { SB(BESTINC_HIGH_END); continue; }
       const float dist1 = vDists[L + bestincR - 1];
       const float dist2 = vDists[L + bestincR];
       const float dist3 = vDists[L + bestincR + 1];
-      const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
-      if (deltaR < -1 || deltaR > 1) continue;
+      const float deltaR = orc_stereo_delta_r(dist1, dist2, dist3);
+      if (deltaR < -1 || deltaR > 1) { SB(DELTA_OUT_OF_RANGE); continue; }
+      if (deltaR != deltaR) SB(DELTA_NAN_PASSED);
       float bestuR = e->mvScaleFactor[kl->octave] * ((float)scaleduR0 + (float)bestincR + deltaR);
       float disparity = (uL - bestuR);
       if (disparity >= minD && disparity < maxD) {
-        if (disparity <= 0) { disparity = 0.01f; bestuR = (float)((double)uL - 0.01); }
+        if (disparity <= 0) { SB(DISPARITY_CLAMPED); disparity = 0.01f; bestuR = (float)((double)uL - 0.01); }
         depth[iL] = mbf / disparity;
         uRight[iL] = bestuR;
         vDistIdx[nDist].d = bestD;
         vDistIdx[nDist].i = iL;
         nDist++;
-      }
-    }
+        SB(ACCEPTED);
+      } else SB(DISPARITY_OUT_OF_RANGE);
+    } else if (nInRange == 0) SB(NO_CANDIDATE);
+    else SB(HAMMING_ABOVE_TH);
   }
   if (nDist > 0) { /* :672-685; empty case is UB in the reference -- guarded */
     qsort(vDistIdx, nDist, sizeof(distidx), distidx_cmp);
@@ -1187,6 +1216,7 @@ int orc_compute_stereo_matches(const orc_extractor *e, int W, int H, const orc_k
     const float thDist = 1.5f * 1.4f * median;
     for (int i = nDist - 1; i >= 0; i--) {
       if ((float)vDistIdx[i].d < thDist) break;
+      SB(MEDIAN_REMOVED);
       uRight[vDistIdx[i].i] = -1;
       depth[vDistIdx[i].i] = -1;
     }

@@ -104,6 +104,13 @@ int orc_descriptor_distance(const uint8_t *a, const uint8_t *b); /* :1828-1844 *
 void orc_distance_calls_reset(void);
 int64_t orc_distance_calls(void);
 void orc_stereo_counters(int64_t *out); /* [bucket entries scanned, SAD refinements] of this thread's last stereo call */
+/* one counter per exit of the per-keypoint loop of this thread's last stereo call, in the order: invalid record, row out
+   of range, empty row, maxU < 0, no candidate in range, bestDist >= thOrbDist, iniu < 0, endu >= cols, patch guards (cy low,
+   cy high, cxL low, cxL high, cxR low), bestincR == -L, bestincR == +L, deltaR out of range, deltaR NaN and passed on,
+   disparity out of range, disparity clamped, accepted (clamped ones included), removed by the median cut.  Writes
+   min(n, count) entries, returns the count. */
+int orc_stereo_branch_counts(int64_t *out, int n);
+float orc_stereo_delta_r(float dist1, float dist2, float dist3); /* src/Frame.cc:648 */
 void orc_three_maxima(const int *histo_sizes, int L, int *ind1, int *ind2, int *ind3); /* :1777-1821 */
 
 /* A DBoW2::FeatureVector flattened: node_ids ascending, CSR offsets into indices. */

@@ -73,6 +73,29 @@ def stereo_counters():
     return int(out[0]), int(out[1])
 
 
+STEREO_BRANCHES = ("invalid_record", "row_out_of_range", "empty_row", "maxu_negative", "no_candidate", "hamming_above_th",
+                   "iniu_negative", "endu_past_cols", "guard_cy_low", "guard_cy_high", "guard_cxl_low", "guard_cxl_high",
+                   "guard_cxr_low", "bestinc_low_end", "bestinc_high_end", "delta_out_of_range", "delta_nan_passed",
+                   "disparity_out_of_range", "disparity_clamped", "accepted", "median_removed")
+
+
+def stereo_branch_counts() -> dict:
+    """exit of the per-keypoint loop -> how many left keypoints of this thread's last Oracle.stereo call took it
+    ("accepted" includes the clamped ones; "median_removed" counts accepted ones the median cut took back)"""
+    out = (C.c_int64 * len(STEREO_BRANCHES))()
+    n = lib().orc_stereo_branch_counts(out, len(STEREO_BRANCHES))
+    assert n == len(STEREO_BRANCHES)
+    return dict(zip(STEREO_BRANCHES, (int(v) for v in out)))
+
+
+def stereo_delta_r(dist1, dist2, dist3) -> np.float32:
+    """the oracle's parabola fit (src/Frame.cc:648)"""
+    L = lib()
+    L.orc_stereo_delta_r.restype = C.c_float
+    L.orc_stereo_delta_r.argtypes = [C.c_float] * 3
+    return np.float32(L.orc_stereo_delta_r(float(dist1), float(dist2), float(dist3)))
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
