@@ -665,6 +665,52 @@ int orbfe_search_local_points(orbfe_mappoints *mp, int n, const int32_t *slot, c
                               const float *scale_factors, int n_levels, const uint8_t *blocked, float th, float nnratio,
                               int32_t *match, int32_t *n_matches, uint8_t *in_view);
 
+/* ------------------------------------------------------------------------- */
+/* Optimizer::PoseOptimization (src/Optimizer.cc:256-473)                     */
+/* ------------------------------------------------------------------------- */
+/* The pose-only optimisation Tracking runs between its searches, as ONE kernel launch: the four rounds of up to ten
+ * Levenberg iterations with up to ten lambda trials each, on the one graph PoseOptimization builds (one free SE3 vertex,
+ * unary mono / stereo reprojection edges, Huber kernel, dense 6 x 6 system).  Not a g2o port: the other Optimizer functions
+ * are not covered.  Arithmetic is binary64 as in g2o; inputs are widened from float.  Edge i: xw = GetWorldPos(), (u, v) =
+ * mvKeysUn[i].pt, u_right = mvuRight[i] (< 0: a monocular edge), inv_sigma2 = mvInvLevelSigma2[octave]; K5 = fx fy cx cy mbf;
+ * Tcw_in = mTcw (row-major 4 x 4).  Outputs: Tcw_out = the pose Frame::SetPose receives, outlier[i] = mvbOutlier,
+ * *n_inliers = the return value nInitialCorrespondences - nBad.  With fewer than 3 edges *n_inliers = 0, Tcw_out = Tcw_in
+ * and outlier[] is not written (the reference has cleared those mvbOutlier entries by then, :310 / :344; here the caller's
+ * array is left alone).  stats (may be NULL): rounds run, and per round the iterations, the lambda trials, the last lambda
+ * and the robust chi2 of the estimate.  edge_chi2 (may be NULL): the chi2 each edge was classified with in the last round
+ * -- for an inlier that of the last evaluated trial, as g2o leaves it in _error.
+ * Sums over edges run in a fixed order that depends on the edge count alone, so equal inputs give equal bits; against g2o
+ * they differ by reordering and by the last place of sin / cos.  The 6 x 6 solve is an unpivoted LDL^T.
+ * n < 0, n > 16384 (per problem), NULL arrays and offsets that descend return ORBFE_ERR_INVALID before anything is
+ * enqueued.  Runs on the calling thread's matcher stream and is complete on return. */
+typedef struct orbfe_poseopt_stats {
+  int32_t rounds, iterations[4], trials[4];
+  double lambda[4], chi2[4];
+} orbfe_poseopt_stats;
+int orbfe_pose_optimization(int device, int n, const float *xw /*[n,3]*/, const float *u, const float *v,
+                            const float *u_right, const float *inv_sigma2, const float K5[5], const float Tcw_in[16],
+                            float Tcw_out[16], uint8_t *outlier, int32_t *n_inliers, orbfe_poseopt_stats *stats,
+                            double *edge_chi2);
+/* n_problems independent problems (one per Relocalization candidate) in one launch, one workgroup each: problem p owns
+ * edges [offsets[p], offsets[p+1]) of the edge arrays, K5[5p ..], Tcw_in / Tcw_out[16p ..], n_inliers[p], stats[p].
+ * Equal to n_problems single calls, bit for bit. */
+int orbfe_pose_optimization_batch(int device, int n_problems, const int32_t *offsets /*[n_problems+1]*/, const float *xw,
+                                  const float *u, const float *v, const float *u_right, const float *inv_sigma2,
+                                  const float *K5, const float *Tcw_in, float *Tcw_out, uint8_t *outlier,
+                                  int32_t *n_inliers, orbfe_poseopt_stats *stats, double *edge_chi2);
+/* The same on the resident map-point table, fed with what orbfe_search_local_points returned: feature i of F has an edge
+ * when match[i] >= 0 (a position in slot[]) and that slot is not ORBFE_MP_BAD (src/Optimizer.cc:303) -- such a feature is
+ * not counted and keeps its flag, as one without a match does.  World positions are gathered from the table on the
+ * device; inv_level_sigma2[n_levels] = mvInvLevelSigma2, indexed by F->octave.  The slot list, match[], the frame's
+ * keypoint arrays (x, y, octave, u_right; F->u_right NULL: every edge monocular), the level table and the pose go up.
+ * outlier / edge_chi2 hold F->n entries.  Equal to orbfe_pose_optimization on the same edges, bit for bit.  Under the
+ * handle's serialisation, as the other orbfe_mappoints calls.  A slot outside the table, a match outside slot[] and an
+ * octave outside the level table return ORBFE_ERR_INVALID before anything is enqueued. */
+int orbfe_pose_optimization_mappoints(orbfe_mappoints *mp, int n_slots, const int32_t *slot, const orbfe_frame_view *F,
+                                      const int32_t *match, const float *inv_level_sigma2, int n_levels,
+                                      const float K5[5], const float Tcw_in[16], float Tcw_out[16], uint8_t *outlier,
+                                      int32_t *n_inliers, orbfe_poseopt_stats *stats, double *edge_chi2);
+
 /* The FeatureVector searches on resident frames (uploaded WITH their FeatureVector and angles): per call only the
  * shared-node list, the MapPoint masks and the result travel.  Semantics and outputs of orbfe_search_by_bow /
  * orbfe_search_by_bow_kf. */

@@ -612,6 +612,44 @@ class MapPointTable {
   orbfe_mappoints* h_ = nullptr;
 };
 
+// Optimizer::PoseOptimization (src/Optimizer.cc:256-473) on the device; the other Optimizer functions are not covered.
+// Both forms return nInitialCorrespondences - nBad, write the pose Frame::SetPose receives into Tcw (row-major 4 x 4) and
+// mvbOutlier of every edge; with fewer than 3 edges they return 0 and leave both alone.
+class Optimizer {
+ public:
+  // one edge per entry: Xw 3 floats each, (u, v) = mvKeysUn[i].pt, uRight = mvuRight[i] (< 0: monocular), invSigma2 =
+  // mvInvLevelSigma2[octave]; K5 = fx fy cx cy mbf
+  static int PoseOptimization(const std::vector<float>& Xw, const std::vector<float>& u, const std::vector<float>& v,
+                              const std::vector<float>& uRight, const std::vector<float>& invSigma2, const float K5[5], float Tcw[16],
+                              std::vector<uint8_t>& mvbOutlier, orbfe_poseopt_stats* stats = nullptr, int device = 0) {
+    const size_t n = u.size();
+    if (Xw.size() != 3 * n || v.size() != n || uRight.size() != n || invSigma2.size() != n)
+      throw std::invalid_argument("Optimizer::PoseOptimization: one entry per edge");
+    mvbOutlier.resize(n, 0);
+    float out[16];
+    int32_t nInliers = 0;
+    check(orbfe_pose_optimization(device, (int)n, Xw.data(), u.data(), v.data(), uRight.data(), invSigma2.data(), K5, Tcw, out,
+                                  mvbOutlier.data(), &nInliers, stats, nullptr), "PoseOptimization");
+    for (int k = 0; k < 16; k++) Tcw[k] = out[k];
+    return nInliers;
+  }
+  // on the resident table, with the match[] MapPointTable::SearchLocalPoints returned for F and slot: keypoints without an
+  // edge (no match, or a bad slot) keep their mvbOutlier entry
+  static int PoseOptimization(const MapPointTable& table, const std::vector<int32_t>& slot, const FrameArrays& F,
+                              const std::vector<int32_t>& match, const std::vector<float>& mvInvLevelSigma2, const float K5[5],
+                              float Tcw[16], std::vector<uint8_t>& mvbOutlier, orbfe_poseopt_stats* stats = nullptr) {
+    if (match.size() != (size_t)F.c.n) throw std::invalid_argument("Optimizer::PoseOptimization: one match entry per keypoint");
+    mvbOutlier.resize((size_t)F.c.n, 0);
+    float out[16];
+    int32_t nInliers = 0;
+    check(orbfe_pose_optimization_mappoints(table.handle(), (int)slot.size(), slot.data(), &F.c, match.data(), mvInvLevelSigma2.data(),
+                                            (int)mvInvLevelSigma2.size(), K5, Tcw, out, mvbOutlier.data(), &nInliers, stats, nullptr),
+          "PoseOptimization");
+    for (int k = 0; k < 16; k++) Tcw[k] = out[k];
+    return nInliers;
+  }
+};
+
 // void Frame::ComputeStereoMatches(): fills mvuRight / mvDepth
 inline int ComputeStereoMatches(ORBextractor& left, ORBextractor& right, const std::vector<KeyPoint>& kL,
                                 const std::vector<uint8_t>& dL, const std::vector<KeyPoint>& kR,

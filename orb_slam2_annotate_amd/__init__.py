@@ -7,6 +7,7 @@ from .extractor import ORBextractor, gaussian_blur7, resize_linear, set_blur_pas
 from .matcher import ComputeStereoMatches, FeatureVector, FrameView, ORBmatcher, ResidentFrame  # noqa: F401
 from .vocabulary import ORBVocabulary, synthetic_vocabulary_arrays, write_synthetic_vocabulary, write_vocabulary_text  # noqa: F401
 from .map_points import MapPoints, camera_pose  # noqa: F401
+from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401
 from .keyframe_database import KeyFrameDatabase, bow_arrays, group_candidates  # noqa: F401
 from .ingest import (ComputeDistinctiveDescriptors, ComputeImageBounds, ComputeStereoFromRGBD,  # noqa: F401
                      Rectifier, UndistortKeyPoints, cvtColorToGray, initUndistortRectifyMap, undistortPoints)  # noqa: F401

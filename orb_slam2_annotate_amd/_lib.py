@@ -47,6 +47,12 @@ class CameraPoseC(C.Structure):
                 ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
 
 
+class PoseOptStatsC(C.Structure):
+    """orbfe_poseopt_stats."""
+    _fields_ = [("rounds", C.c_int32), ("iterations", C.c_int32 * 4), ("trials", C.c_int32 * 4),
+                ("lam", C.c_double * 4), ("chi2", C.c_double * 4)]
+
+
 class FeatVecC(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_ids", C.c_void_p), ("offsets", C.c_void_p),
                 ("indices", C.c_void_p)]
@@ -79,6 +85,7 @@ EXPORTS = [
     "orbfe_kfdb_clear", "orbfe_kfdb_size", "orbfe_kfdb_query", "orbfe_kfdb_score", "orbfe_kfdb_group_candidates",
     "orbfe_mappoints_create", "orbfe_mappoints_destroy", "orbfe_mappoints_capacity", "orbfe_mappoints_update",
     "orbfe_project_in_frustum", "orbfe_search_local_points",
+    "orbfe_pose_optimization", "orbfe_pose_optimization_batch", "orbfe_pose_optimization_mappoints",
 ]
 
 _lib = None
@@ -246,6 +253,9 @@ def load():
     L.orbfe_mappoints_update.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_project_in_frustum.argtypes = [vp, ci, vp, vp, cpp, cf, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_search_local_points.argtypes = [vp, ci, vp, vp, cpp, cf, fwp, vp, ci, vp, cf, cf, vp, vp, vp]
+    L.orbfe_pose_optimization.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_pose_optimization_batch.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_pose_optimization_mappoints.argtypes = [vp, ci, vp, fwp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

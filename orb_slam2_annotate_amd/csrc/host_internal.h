@@ -119,6 +119,14 @@ int orbfe_stereo_views_(orbfe_extractor* e, int frame, orbfe::PyramidViews* pv, 
 // test hooks: hold back / query a stream
 int orbfe_debug_stall_launch_(hipStream_t s, int usec);
 int orbfe_debug_stream_idle_(hipStream_t s);
+// ---- matcher.hip (the thread arenas and struct orbfe_mappoints live there) ----
+// the calling thread's arena on `device`, begun with `bytes` of device memory (*d) and as much of its pinned mirror (*h), and
+// the arena's stream: the caller fills *h, copies, launches and copies back on *s, and synchronises before it returns
+int orbfe_thread_scratch_(int device, size_t bytes, uint8_t** d, uint8_t** h, hipStream_t* s);
+// takes the handle's serialisation and makes the table ready on the device; every success is paired with an unlock once the
+// caller's work on the table has completed
+int orbfe_mappoints_lock_(orbfe_mappoints* mp, const float4** rec, const uint8_t** flags, int* device);
+void orbfe_mappoints_unlock_(orbfe_mappoints* mp);
 // ---- k_ingest.hip (struct orbfe_rectifier lives there) ----
 // the rectification of a sub-batch on that sub-batch's own stream; d_src == NULL only queries w / h / device
 int orbfe_remap_launch_(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride,

@@ -1623,6 +1623,34 @@ extern "C" int orbfe_mappoints_update(orbfe_mappoints* mp, int n, const int32_t*
   return ORBFE_OK;
 }
 
+// ---- back doors for poseopt.hip (host_internal.h) ----
+// the calling thread's arena on `device`, begun with `bytes` of device memory and as much of its pinned mirror, and its stream
+extern "C" int orbfe_thread_scratch_(int device, size_t bytes, uint8_t** d, uint8_t** h, hipStream_t* s) {
+  Arena* ar;
+  HIPCHK(arena_begin(device, bytes, &ar));
+  HIPCHK(grow_mirror(ar, bytes));
+  *d = ar->base;
+  *h = ar->hmirror;
+  *s = ar->stream;
+  return ORBFE_OK;
+}
+// holds the handle's serialisation until orbfe_mappoints_unlock_, with the table on the device
+extern "C" int orbfe_mappoints_lock_(orbfe_mappoints* mp, const float4** rec, const uint8_t** flags, int* device) {
+  mp->m.lock();
+  Arena* ar;
+  hipError_t e = arena_begin(mp->device, 0, &ar);
+  if (e == hipSuccess) e = mappoints_ready(mp, ar);
+  if (e != hipSuccess) {
+    mp->m.unlock();
+    return fail(hip_status(e), std::string("mappoints: ") + hipGetErrorString(e));
+  }
+  *rec = mp->d.rec;
+  *flags = mp->d.flags;
+  *device = mp->device;
+  return ORBFE_OK;
+}
+extern "C" void orbfe_mappoints_unlock_(orbfe_mappoints* mp) { mp->m.unlock(); }
+
 extern "C" int orbfe_project_in_frustum(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
                                         const orbfe_camera_pose* pose, float viewing_cos_limit, uint8_t* in_view, int32_t* level,
                                         float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z, float* dist) {

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CameraPoseC, check, ptr
+from ._lib import CameraPoseC, PoseOptStatsC, check, ptr
 
 MP_BAD, MP_OBSERVED = 1, 2  # flags: MapPoint::isBad(), MapPoint::Observations() > 0
 
@@ -114,3 +114,25 @@ class MapPoints:
                                                 ptr(sf), len(sf), ptr(blk), float(th), float(nnratio), ptr(match),
                                                 C.byref(nm), ptr(in_view)))
         return nm.value, match[:F.N], in_view[:n]
+
+    def pose_optimization(self, frame, slot, match, pose, K5, inv_level_sigma2, outlier=None):
+        """Optimizer::PoseOptimization on the table (orbfe_pose_optimization_mappoints): `match` is what SearchLocalPoints
+        returned for `frame` and `slot`, `pose` the 4 x 4 mTcw, inv_level_sigma2 = mvInvLevelSigma2 -> (n_inliers, Tcw_out
+        [4, 4], outlier [frame.N], stats dict, edge_chi2 [frame.N]).  Features without an edge (no match, or a bad slot)
+        keep the flag `outlier` gave them and a chi2 of 0."""
+        from .optimizer import _flags, stats_dict
+        h = self._h
+        s = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        m = np.ascontiguousarray(match, dtype=np.int32).reshape(-1)
+        if len(m) != frame.N:
+            raise ValueError("MapPoints.pose_optimization: match must hold one entry per feature of the frame")
+        lv = np.ascontiguousarray(inv_level_sigma2, dtype=np.float32).reshape(-1)
+        k = np.ascontiguousarray(K5, dtype=np.float32).reshape(5)
+        T = np.ascontiguousarray(pose, dtype=np.float32).reshape(16)
+        out = np.zeros(16, np.float32)
+        flags = _flags(outlier, frame.N, "MapPoints.pose_optimization")
+        chi2 = np.zeros(max(frame.N, 1), np.float64)
+        ni, st = C.c_int32(0), PoseOptStatsC()
+        check(self._L.orbfe_pose_optimization_mappoints(h, len(s), ptr(s), C.byref(frame.c), ptr(m), ptr(lv), len(lv), ptr(k), ptr(T),
+                                                        ptr(out), ptr(flags), C.byref(ni), C.byref(st), ptr(chi2)))
+        return ni.value, out.reshape(4, 4), flags[:frame.N], stats_dict(st), chi2[:frame.N]
