@@ -1239,7 +1239,7 @@ extern "C" int orbfe_extract_batch(orbfe_extractor* e, const uint8_t* images, in
   return ORBFE_OK;
 }
 
-// internal (matcher.hip, orbfe_frame_from_extractor): device records of frame `frame` of the last host-buffer call
+// internal (frames.hip, orbfe_frame_from_extractor): device records of frame `frame` of the last host-buffer call
 extern "C" int orbfe_extractor_output_device_(orbfe_extractor* e, int frame, const orbfe_keypoint** d_kp, const uint8_t** d_desc,
                                               int* n, int* device) {
   if (!e || !d_kp || !d_desc || !n || !device) return fail(ORBFE_ERR_INVALID, "frame_from_extractor: NULL argument");
@@ -1585,7 +1585,7 @@ extern "C" int orbfe_extractor_consumer_end_(orbfe_extractor* e) {
   return ORBFE_OK;
 }
 
-// internal (matcher.hip, orbfe_frame_from_extractor): a frame build that reads the output block was enqueued on `s`;
+// internal (frames.hip, orbfe_frame_from_extractor): a frame build that reads the output block was enqueued on `s`;
 // the next call that writes the block waits for it on the device.  Builds on one stream are ordered by that stream, so
 // one event covers them; a build on another thread's stream first settles the one before it (rare: one handle, two threads)
 extern "C" int orbfe_extractor_reader_end_(orbfe_extractor* e, hipStream_t s) {
@@ -1920,7 +1920,7 @@ __global__ void __launch_bounds__(64) k_debug_stall(long long ticks) {
 }
 }  // namespace
 
-// internal (matcher.hip): the stall on any stream; usec = 0 is a marker that completes at once
+// internal (arena.hip): the stall on any stream; usec = 0 is a marker that completes at once
 extern "C" int orbfe_debug_stall_launch_(hipStream_t s, int usec) {
   if (usec < 0 || usec > 1000000) return fail(ORBFE_ERR_INVALID, "debug_stall: usec must be 0 .. 1000000");
   hipLaunchKernelGGL(k_debug_stall, dim3(1), dim3(64), 0, s, (long long)usec * 100);

@@ -86,8 +86,8 @@ struct DevBuf {
 template <typename T>
 using PinBuf = DevBuf<T, true>;
 
-// matcher.hip: device slabs of released frames / key-frame databases, kept for the next one -- hipMalloc / hipFree cost
-// tens of microseconds and hipFree waits for the whole device.  slab_get: the smallest kept slab of `device` with
+// arena.hip: device slabs of released frames / map-point tables / key-frame databases, kept for the next one -- hipMalloc /
+// hipFree cost tens of microseconds and hipFree waits for the whole device.  slab_get: the smallest kept slab of `device` with
 // bytes <= cap <= 4 * bytes + 64 KiB, else a new one of the next 64 KiB class; slab_put: back to the pool (p = NULL after)
 struct Slab {
   void* p = nullptr;
@@ -96,6 +96,24 @@ struct Slab {
 };
 hipError_t slab_get(int device, size_t bytes, Slab* out);
 void slab_put(Slab* s);
+
+// ---- mappoints.hip (struct orbfe_mappoints lives there) ----
+bool pose_ok(const orbfe_camera_pose* p);
+// The one way another host file reaches a table: takes the handle's serialisation and makes the table ready on the device,
+// for the scope.  rc != ORBFE_OK: nothing is held and the error text is set.  The holder's work on the table has completed
+// (its stream is synchronised) before the scope ends.
+struct MapPointsDevice;  // match_kernels.h
+struct MapPointsLock {
+  MapPointsLock(orbfe_mappoints* mp);
+  ~MapPointsLock();
+  MapPointsLock(const MapPointsLock&) = delete;
+  MapPointsLock& operator=(const MapPointsLock&) = delete;
+  int rc = ORBFE_OK, device = 0;
+  const MapPointsDevice* table = nullptr;
+
+ private:
+  orbfe_mappoints* held = nullptr;
+};
 }  // namespace orbfe
 
 extern "C" {
@@ -119,14 +137,6 @@ int orbfe_stereo_views_(orbfe_extractor* e, int frame, orbfe::PyramidViews* pv, 
 // test hooks: hold back / query a stream
 int orbfe_debug_stall_launch_(hipStream_t s, int usec);
 int orbfe_debug_stream_idle_(hipStream_t s);
-// ---- matcher.hip (the thread arenas and struct orbfe_mappoints live there) ----
-// the calling thread's arena on `device`, begun with `bytes` of device memory (*d) and as much of its pinned mirror (*h), and
-// the arena's stream: the caller fills *h, copies, launches and copies back on *s, and synchronises before it returns
-int orbfe_thread_scratch_(int device, size_t bytes, uint8_t** d, uint8_t** h, hipStream_t* s);
-// takes the handle's serialisation and makes the table ready on the device; every success is paired with an unlock once the
-// caller's work on the table has completed
-int orbfe_mappoints_lock_(orbfe_mappoints* mp, const float4** rec, const uint8_t** flags, int* device);
-void orbfe_mappoints_unlock_(orbfe_mappoints* mp);
 // ---- k_ingest.hip (struct orbfe_rectifier lives there) ----
 // the rectification of a sub-batch on that sub-batch's own stream; d_src == NULL only queries w / h / device
 int orbfe_remap_launch_(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride,

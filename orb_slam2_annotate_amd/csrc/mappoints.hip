@@ -1,0 +1,159 @@
+// mappoints.hip -- C-ABI entry points of the device map-point table (include/orbfe.h: orbfe_mappoints_*,
+// orbfe_project_in_frustum) and MapPointsLock (host_internal.h), the one way another host file reaches the table.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <string>
+
+#include "../../include/orbfe.h"
+#include "arena.h"
+#include "host_internal.h"
+#include "mappoints_host.h"
+#include "match_kernels.h"
+
+using namespace orbfe;
+
+// ---------------------------------------------------------------------------------------------
+// Device-resident map points (include/orbfe.h: orbfe_mappoints).  One slab from the pool holds the table; an update is one
+// staged copy and one scatter launch on the calling thread's stream, complete on return.  The argument checks and the
+// layouts are mappoints_host.h (no device needed: tests/cpp/mappoints_host_san.cpp runs them under the sanitizers).
+// ---------------------------------------------------------------------------------------------
+struct orbfe_mappoints {
+  int device = 0, capacity = 0;
+  std::mutex m;  // a handle serialises its own calls
+  Slab slab;     // empty until the first call that needs the device
+  MapPointsDevice d{};
+};
+
+namespace {
+// the table's slab, every slot bad until it is updated; enqueued on the arena's stream
+hipError_t mappoints_ready(orbfe_mappoints* mp, Arena* ar) {
+  if (mp->slab.p) return hipSuccess;
+  const MapPointsLayout L = mappoints_layout(mp->capacity);
+  TRY(slab_get(mp->device, L.total, &mp->slab));
+  uint8_t* b = static_cast<uint8_t*>(mp->slab.p);
+  mp->d.rec = reinterpret_cast<float4*>(b + L.oRec); mp->d.desc = b + L.oDesc; mp->d.flags = b + L.oFlags;
+  hipError_t e = hipMemsetAsync(b, 0, L.oFlags, ar->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(mp->d.flags, ORBFE_MP_BAD, (size_t)mp->capacity, ar->stream);
+  // complete before the handle counts as ready: another thread's stream may be the next to read the table
+  if (e == hipSuccess) e = hipStreamSynchronize(ar->stream);
+  if (e != hipSuccess) { slab_put(&mp->slab); mp->d = MapPointsDevice{}; }
+  return e;
+}
+
+// k_project_frustum with the isInFrustum outputs (n > 0, arguments checked, the handle locked): slot list and mask up, one
+// launch, the eight arrays back in one copy
+int project_run(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip, const orbfe_camera_pose* pose, float limit,
+                uint8_t* in_view, int32_t* level, float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z,
+                float* dist) {
+  const size_t q = (size_t)n;
+  Arena* ar;
+  ProjectArgs pa{};
+  int32_t* dslot;
+  uint8_t* dskip = nullptr;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dslot, slot, q));
+    if (skip) TRY(up(a, &dskip, skip, q));
+    // the outputs adjacent: one copy back
+    pa.level = carve<int32_t>(a, q); pa.viewCos = carve<float>(a, q); pa.projX = carve<float>(a, q); pa.projY = carve<float>(a, q);
+    pa.projXr = carve<float>(a, q); pa.invZ = carve<float>(a, q); pa.dist = carve<float>(a, q); pa.inView = carve<uint8_t>(a, q);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(mp->device, &ar, stage));
+  HIPCHK(mappoints_ready(mp, ar));
+  pa.table = mp->d; pa.slot = dslot; pa.skip = dskip; pa.n = n; pa.cam = *pose; pa.limit = limit;
+  HIPCHK(flush(ar));
+  launch_project_frustum(ar->stream, pa);
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, pa.level, pa.inView + q));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  if (level) std::memcpy(level, mirror_of(ar, pa.level), q * 4);
+  if (view_cos) std::memcpy(view_cos, mirror_of(ar, pa.viewCos), q * 4);
+  if (proj_x) std::memcpy(proj_x, mirror_of(ar, pa.projX), q * 4);
+  if (proj_y) std::memcpy(proj_y, mirror_of(ar, pa.projY), q * 4);
+  if (proj_xr) std::memcpy(proj_xr, mirror_of(ar, pa.projXr), q * 4);
+  if (inv_z) std::memcpy(inv_z, mirror_of(ar, pa.invZ), q * 4);
+  if (dist) std::memcpy(dist, mirror_of(ar, pa.dist), q * 4);
+  if (in_view) std::memcpy(in_view, mirror_of(ar, pa.inView), q);
+  return ORBFE_OK;
+}
+}  // namespace
+
+extern "C" int orbfe_mappoints_create(int device, int capacity, orbfe_mappoints** out) {
+  if (const char* e = mappoints_check_create(capacity, out)) return fail(ORBFE_ERR_INVALID, std::string("mappoints_create: ") + e);
+  *out = nullptr;
+  if (device < 0) return fail(ORBFE_ERR_INVALID, "mappoints_create: negative device");
+  orbfe_mappoints* mp = new (std::nothrow) orbfe_mappoints();
+  if (!mp) return fail(ORBFE_ERR_NOMEM, "out of memory");
+  mp->device = device; mp->capacity = capacity;
+  *out = mp;
+  return ORBFE_OK;
+}
+
+extern "C" void orbfe_mappoints_destroy(orbfe_mappoints* mp) {
+  if (!mp) return;
+  if (mp->slab.p) {  // (every call on the table has completed on return: nothing can still read the slab)
+    (void)hipSetDevice(mp->device);
+    slab_put(&mp->slab);
+  }
+  delete mp;
+}
+
+extern "C" int orbfe_mappoints_capacity(const orbfe_mappoints* mp) { return mp ? mp->capacity : fail(ORBFE_ERR_INVALID, "mappoints_capacity: NULL table"); }
+
+extern "C" int orbfe_mappoints_update(orbfe_mappoints* mp, int n, const int32_t* slot, const float* pos, const float* normal,
+                                      const float* min_dist, const float* max_dist, const uint8_t* desc, const uint8_t* flags) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "mappoints_update: NULL table");
+  if (const char* e = mappoints_check_update(mp->capacity, n, slot, pos, normal, min_dist, max_dist, flags))
+    return fail(ORBFE_ERR_INVALID, std::string("mappoints_update: ") + e);
+  if (n == 0) return ORBFE_OK;
+  std::lock_guard<std::mutex> lk(mp->m);
+  const MapPointsStage S = mappoints_stage_layout(n, desc != nullptr);
+  Arena* ar;
+  HIPCHK(arena_scratch(mp->device, S.total, &ar));
+  HIPCHK(mappoints_ready(mp, ar));
+  mappoints_pack(ar->hmirror, S, n, slot, pos, normal, min_dist, max_dist, desc, flags);
+  uint8_t* din = ar->base;
+  HIPCHK(hipMemcpyAsync(din, ar->hmirror, S.total, hipMemcpyHostToDevice, ar->stream));
+  launch_mappoints_scatter(ar->stream, mp->d, n, reinterpret_cast<const int32_t*>(din + S.oSlot), reinterpret_cast<const float4*>(din + S.oRec),
+                           din + S.oFlags, desc ? din + S.oDesc : nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  return ORBFE_OK;
+}
+
+namespace orbfe {
+bool pose_ok(const orbfe_camera_pose* p) { return p && p->n_levels >= 1 && p->n_levels <= ORBFE_MAX_LEVELS * 4; }
+
+// host_internal.h: holds the handle's serialisation for a scope, with the table on the device
+MapPointsLock::MapPointsLock(orbfe_mappoints* mp) {
+  mp->m.lock();
+  Arena* ar;
+  hipError_t e = arena_stream(mp->device, &ar);
+  if (e == hipSuccess) e = mappoints_ready(mp, ar);
+  if (e != hipSuccess) {
+    mp->m.unlock();
+    rc = fail(hip_status(e), std::string("mappoints: ") + hipGetErrorString(e));
+    return;
+  }
+  held = mp;
+  table = &mp->d;
+  device = mp->device;
+}
+MapPointsLock::~MapPointsLock() {
+  if (held) held->m.unlock();
+}
+}  // namespace orbfe
+
+extern "C" int orbfe_project_in_frustum(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
+                                        const orbfe_camera_pose* pose, float viewing_cos_limit, uint8_t* in_view, int32_t* level,
+                                        float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z, float* dist) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "project_in_frustum: NULL table");
+  if (const char* e = mappoints_check_slots(mp->capacity, n, slot)) return fail(ORBFE_ERR_INVALID, std::string("project_in_frustum: ") + e);
+  if (!pose_ok(pose)) return fail(ORBFE_ERR_INVALID, "project_in_frustum: bad pose (n_levels must be 1 .. 64)");
+  if (n == 0) return ORBFE_OK;
+  std::lock_guard<std::mutex> lk(mp->m);
+  return project_run(mp, n, slot, skip, pose, viewing_cos_limit, in_view, level, view_cos, proj_x, proj_y, proj_xr, inv_z, dist);
+}

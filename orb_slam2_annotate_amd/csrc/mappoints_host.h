@@ -1,4 +1,4 @@
-// mappoints_host.h -- the host side of the device map-point table (matcher.hip: orbfe_mappoints_*) that needs no device:
+// mappoints_host.h -- the host side of the device map-point table (mappoints.hip: orbfe_mappoints_*) that needs no device:
 // argument checks, the table's slab layout and the packing of an update into the staging buffer.  Plain C++ without a HIP
 // include, so tests/cpp/mappoints_host_san.cpp runs exactly this code under the address and undefined-behaviour sanitizers.
 #pragma once

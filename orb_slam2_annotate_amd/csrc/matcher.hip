@@ -1,19 +1,18 @@
-// matcher.hip -- C-ABI entry points of the Hamming matchers and the stereo matcher
-// (include/orbfe.h, "Matcher").  Stateless and re-entrant: every thread owns a private
-// device arena + stream per device (the reference constructs stack-local ORBmatcher objects
-// on three threads concurrently, src/LocalMapping.cc:261, src/LoopClosing.cc:294).
+// matcher.hip -- C-ABI entry points of the searches (include/orbfe.h, "Matcher"): the Hamming utilities, the FeatureVector
+// searches (SearchByBoW, SearchForTriangulation), the stereo matcher, and the window searches (GetFeaturesInArea, the
+// projection searches, Fuse, SearchBySim3).  Stateless and re-entrant: every call runs on the calling thread's own arena and
+// stream (arena.h); resident frames are frame.h / frames.hip, the map-point table mappoints.hip.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "arena.h"
+#include "frame.h"
 #include "host_internal.h"
 #include "kernels.h"
 #include "mappoints_host.h"
@@ -22,170 +21,6 @@
 using namespace orbfe;
 
 namespace {
-
-struct Arena {
-  int device = -1;
-  hipStream_t stream = nullptr;
-  DevBuf<uint8_t> base;
-  size_t used = 0;
-  // pinned mirror of the uploaded part of the arena: up() only copies into it, flush() sends the whole
-  // dirty range in ONE host-to-device copy before the first kernel of the call
-  PinBuf<uint8_t> hmirror;
-  size_t dirtyLo = 0, dirtyHi = 0;
-  bool sizing = false;  // arena_stage()'s first pass: carve() only advances `used`, up() / up_fill() copy nothing
-  ~Arena() {  // (thread exit; the buffers free themselves behind this, on the device set here)
-    if (device >= 0) {
-      (void)hipSetDevice(device);
-      if (stream) (void)hipStreamDestroy(stream);
-    }
-  }
-};
-thread_local std::map<int, Arena> t_arenas;
-
-// Reserve `bytes` up front (sum of all buffers of a call), then carve.
-hipError_t arena_begin(int device, size_t bytes, Arena** out) {
-  hipError_t err = hipSetDevice(device);
-  if (err != hipSuccess) return err;
-  Arena& a = t_arenas[device];
-  bytes = (bytes + 255) & ~(size_t)255;
-  if (a.device < 0) {
-    a.device = device;
-    err = hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking);
-    if (err != hipSuccess) { a.device = -1; return err; }
-  }
-  if (bytes > a.base.cap) {
-    err = a.base.try_alloc(bytes + bytes / 2 + (1u << 20));
-    if (err != hipSuccess) return err;
-  }
-  a.used = 0;
-  a.dirtyLo = a.dirtyHi = 0;
-  *out = &a;
-  return hipSuccess;
-}
-template <typename T>
-T* carve(Arena* a, size_t n) {
-  size_t off = (a->used + 255) & ~(size_t)255;
-  a->used = off + n * sizeof(T);
-  return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(a->base.p) + off);
-}
-inline size_t pad(size_t bytes) { return ((bytes + 255) & ~(size_t)255) + 256; }
-
-// the pinned mirror covers arena offsets [0, upto); what earlier up() calls of this call staged is kept
-hipError_t grow_mirror(Arena* a, size_t upto) {
-  if (upto <= a->hmirror.cap) return hipSuccess;
-  PinBuf<uint8_t> nh;
-  hipError_t e = nh.try_alloc(upto + upto / 2 + (1u << 16));
-  if (e != hipSuccess) return e;
-  if (a->hmirror && a->dirtyHi > a->dirtyLo) std::memcpy(nh + a->dirtyLo, a->hmirror + a->dirtyLo, a->dirtyHi - a->dirtyLo);
-  a->hmirror = std::move(nh);
-  return hipSuccess;
-}
-inline void mark_dirty(Arena* a, size_t off, size_t bytes) {
-  if (a->dirtyHi == a->dirtyLo) { a->dirtyLo = off; a->dirtyHi = off + bytes; }
-  else {
-    if (off < a->dirtyLo) a->dirtyLo = off;
-    if (off + bytes > a->dirtyHi) a->dirtyHi = off + bytes;
-  }
-}
-// host data for an array carved earlier in this call: for blocks of device addresses, which are known only once everything
-// is carved but must lie among the uploads
-template <typename T>
-hipError_t put(Arena* a, T* d, const T* h, size_t n) {
-  if (n == 0 || a->sizing) return hipSuccess;
-  const size_t off = (size_t)(reinterpret_cast<uint8_t*>(d) - a->base), bytes = n * sizeof(T);
-  hipError_t e = grow_mirror(a, off + bytes);
-  if (e != hipSuccess) return e;
-  std::memcpy(a->hmirror + off, h, bytes);
-  mark_dirty(a, off, bytes);
-  return hipSuccess;
-}
-template <typename T>
-hipError_t up(Arena* a, T** d, const T* h, size_t n) {
-  *d = carve<T>(a, n ? n : 1);
-  return put(a, *d, h, n);
-}
-// a device array of n elements whose bytes all start as `byteValue`: filled in the mirror, so it travels with the one
-// host-to-device copy of the call instead of costing a fill kernel of its own
-template <typename T>
-hipError_t up_fill(Arena* a, T** d, size_t n, int byteValue) {
-  *d = carve<T>(a, n ? n : 1);
-  if (a->sizing) return hipSuccess;
-  const size_t off = (size_t)(reinterpret_cast<uint8_t*>(*d) - a->base), bytes = (n ? n : 1) * sizeof(T);
-  hipError_t e = grow_mirror(a, off + bytes);
-  if (e != hipSuccess) return e;
-  std::memset(a->hmirror + off, byteValue, bytes);
-  mark_dirty(a, off, bytes);
-  return hipSuccess;
-}
-// results: ONE device-to-host copy of the arena range [first, last) into the pinned mirror (same offsets), to be read
-// through mirror_of() after the stream is synchronised -- instead of one pageable copy per output array
-hipError_t down_range(Arena* a, const void* first, const void* last) {
-  const size_t lo = (size_t)(reinterpret_cast<const uint8_t*>(first) - a->base);
-  const size_t hi = (size_t)(reinterpret_cast<const uint8_t*>(last) - a->base);
-  hipError_t e = grow_mirror(a, hi);
-  if (e != hipSuccess) return e;
-  return hipMemcpyAsync(a->hmirror + lo, a->base + lo, hi - lo, hipMemcpyDeviceToHost, a->stream);
-}
-template <typename T>
-const T* mirror_of(Arena* a, const T* d) {
-  return reinterpret_cast<const T*>(a->hmirror + (reinterpret_cast<const uint8_t*>(d) - a->base));
-}
-// one H2D copy for everything up() staged since arena_begin(); call before the first kernel launch.  Whole 256-byte lines
-// travel (a copy that ends inside a line costs a microsecond more): carve() starts every array on a line and arena_begin()
-// reserves whole lines, so the tail of the last line belongs to no array
-hipError_t flush(Arena* a) {
-  if (a->dirtyHi == a->dirtyLo) return hipSuccess;
-  const size_t hi = (a->dirtyHi + 255) & ~(size_t)255;
-  hipError_t e = grow_mirror(a, hi);
-  if (e == hipSuccess) e = hipMemcpyAsync(a->base + a->dirtyLo, a->hmirror + a->dirtyLo, hi - a->dirtyLo, hipMemcpyHostToDevice, a->stream);
-  a->dirtyLo = a->dirtyHi = 0;
-  return e;
-}
-
-// Stages a call: runs `stage` -- the up() / up_fill() / carve() calls of the call -- twice, first on a sizing arena that
-// only counts, then on the calling thread's arena of `device`, begun with exactly what the first pass carved: the size
-// cannot drift from the carving.  `stage` must compute the same sizes in both passes.
-template <typename F>
-hipError_t arena_stage(int device, Arena** out, F&& stage) {
-  Arena sizing;
-  sizing.sizing = true;
-  hipError_t e = stage(&sizing);
-  if (e == hipSuccess) e = arena_begin(device, sizing.used, out);
-  if (e == hipSuccess) e = stage(*out);
-  return e;
-}
-
-// Pinned staging of the calling thread for copies whose destination is a slab, not the arena (frame builds,
-// orbfe_frame_set_featvec, orbfe_mappoints_update): the call packs what travels in the slab's own layout and sends it in ONE
-// host-to-device copy.  Everything else stages through the arena (up() / flush() / down_range()).
-struct Staging {
-  PinBuf<uint8_t> h;
-  hipEvent_t pending = nullptr;  // an asynchronous copy OUT of the buffer that nobody waited for (orbfe_frame_upload): the
-  bool isPending = false;        // next use of the buffer waits for it first
-  ~Staging() {
-    if (pending) (void)hipEventDestroy(pending);
-  }
-};
-thread_local Staging t_staging;
-
-hipError_t staging_reserve(size_t bytes) {
-  if (t_staging.isPending) {  // (normally long done: the copy took microseconds, the caller's next call comes later)
-    hipError_t e = hipEventSynchronize(t_staging.pending);
-    if (e != hipSuccess) return e;
-    t_staging.isPending = false;
-  }
-  return bytes <= t_staging.h.cap ? hipSuccess : t_staging.h.try_alloc(bytes + bytes / 2 + (1u << 16));
-}
-// an asynchronous copy out of the staging buffer was enqueued on `s` and nobody waits for it: the next staging_reserve() does
-hipError_t staging_mark_pending(hipStream_t s) {
-  if (!t_staging.pending) {
-    hipError_t e = hipEventCreateWithFlags(&t_staging.pending, hipEventDisableTiming);
-    if (e != hipSuccess) return e;
-  }
-  hipError_t e = hipEventRecord(t_staging.pending, s);
-  if (e == hipSuccess) t_staging.isPending = true;
-  return e;
-}
 
 // merge-walk of the two ascending node-id lists (the std::map iteration + lower_bound of
 // src/ORBmatcher.cc:211-300)
@@ -203,39 +38,21 @@ void shared_nodes(const orbfe_featvec* f1, const orbfe_featvec* f2, std::vector<
   }
 }
 
-bool featvec_ok(const orbfe_featvec* f, int n) {
-  if (!f || f->n_nodes < 0) return false;
-  if (f->n_nodes == 0) return true;
-  if (!f->node_ids || !f->offsets || !f->indices) return false;
-  if (f->offsets[0] != 0) return false;
-  for (int i = 0; i < f->n_nodes; i++) {
-    if (f->offsets[i + 1] < f->offsets[i]) return false;
-    if (i > 0 && f->node_ids[i] <= f->node_ids[i - 1]) return false;
-  }
-  const int tot = f->offsets[f->n_nodes];
-  for (int i = 0; i < tot; i++)
-    if (f->indices[i] >= (uint32_t)n) return false;
-  return true;
-}
-
 }  // namespace
-
-// (in a function that returns hipError_t)
-#define TRY(expr)                      \
-  do {                                 \
-    hipError_t _e = (expr);            \
-    if (_e != hipSuccess) return _e;   \
-  } while (0)
 
 extern "C" int orbfe_descriptor_distance(int device, const uint8_t* a, const uint8_t* b, int n, int32_t* out) {
   if (n < 0 || (n > 0 && (!a || !b || !out))) return fail(ORBFE_ERR_INVALID, "descriptor_distance: bad argument");
   if (n == 0) return ORBFE_OK;
   Arena* ar;
-  HIPCHK(arena_begin(device, 2 * pad((size_t)n * 32) + pad((size_t)n * 4), &ar));
   uint8_t *da, *db;
-  HIPCHK(up(ar, &da, a, (size_t)n * 32));
-  HIPCHK(up(ar, &db, b, (size_t)n * 32));
-  int32_t* dout = carve<int32_t>(ar, n);
+  int32_t* dout;
+  auto stage = [&](Arena* s) -> hipError_t {
+    TRY(up(s, &da, a, (size_t)n * 32));
+    TRY(up(s, &db, b, (size_t)n * 32));
+    dout = carve<int32_t>(s, n);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(device, &ar, stage));
   HIPCHK(flush(ar));
   launch_hamming_pairs(ar->stream, da, db, n, dout);
   HIPCHK(hipGetLastError());
@@ -249,396 +66,21 @@ extern "C" int orbfe_hamming_matrix(int device, const uint8_t* d1, int n1, const
     return fail(ORBFE_ERR_INVALID, "hamming_matrix: bad argument");
   if (n1 == 0 || n2 == 0) return ORBFE_OK;
   Arena* ar;
-  HIPCHK(arena_begin(device, pad((size_t)n1 * 32) + pad((size_t)n2 * 32) + pad((size_t)n1 * n2 * 4), &ar));
   uint8_t *da, *db;
-  HIPCHK(up(ar, &da, d1, (size_t)n1 * 32));
-  HIPCHK(up(ar, &db, d2, (size_t)n2 * 32));
-  int32_t* dout = carve<int32_t>(ar, (size_t)n1 * n2);
+  int32_t* dout;
+  auto stage = [&](Arena* s) -> hipError_t {
+    TRY(up(s, &da, d1, (size_t)n1 * 32));
+    TRY(up(s, &db, d2, (size_t)n2 * 32));
+    dout = carve<int32_t>(s, (size_t)n1 * n2);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(device, &ar, stage));
   HIPCHK(flush(ar));
   launch_hamming_matrix(ar->stream, da, n1, db, n2, dout);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, dout, (size_t)n1 * n2 * 4, hipMemcpyDeviceToHost, ar->stream));
   HIPCHK(hipStreamSynchronize(ar->stream));
   return ORBFE_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Device-resident Frame / KeyFrame operands (round 3).  The live system matches one key frame against 10-20
-// neighbours (LocalMapping::CreateNewMapPoints / SearchInNeighbors, src/LocalMapping.cc:256-315, 517-573) and one
-// frame against several candidates (Tracking::Relocalization, src/Tracking.cc:1478-1498): with host-pointer operands
-// every call uploaded both frames' descriptors again.  orbfe_frame_upload moves what a frame contributes to ANY search
-// -- keypoint arrays, descriptors, the 64 x 48 grid (built once), the FeatureVector's index list -- to the device once;
-// the handle is immutable afterwards, so any thread may use it concurrently.
-// ---------------------------------------------------------------------------------------------
-struct orbfe_frame {
-  int device = 0, n = 0;
-  std::vector<float> hx, hy, hangle, hur;   // host copies: the claim loops and chi-square gates read them
-  std::vector<int32_t> hoct;
-  std::vector<uint8_t> hstereo;             // mvuRight[i] >= 0
-  std::vector<uint32_t> nodeIds;            // FeatureVector (host side of the merge-walk)
-  std::vector<int32_t> offsets;
-  std::vector<uint32_t> hindices;
-  orbfe_featvec fv = {};
-  bool haveFv = false;
-  Slab slab;                                // one device allocation (from the slab pool)
-  hipEvent_t ready = nullptr;               // recorded behind the upload + grid build; consumers on other streams wait for it
-  mutable std::atomic<bool> settled{false}; // a consumer has synchronised behind `ready`: no further waits needed
-  float *dx = nullptr, *dy = nullptr, *dangle = nullptr, *dur = nullptr;
-  int32_t* doct = nullptr;
-  uint8_t *ddesc = nullptr, *dstereo = nullptr;
-  uint32_t *dkey = nullptr, *dindices = nullptr;
-  int32_t* dcell = nullptr;
-  std::vector<uint8_t> hdesc;               // (the host-pointer fallbacks of a view need it)
-  orbfe_frame_view view = {};               // canonical view: host copies + resident = this
-};
-
-namespace {
-inline const orbfe_frame_view* canon(const orbfe_frame_view* f) { return (f && f->resident) ? &f->resident->view : f; }
-}
-
-namespace {
-// Slabs (host_internal.h: frames here, the key-frame database's arrays in kfdb.hip) and events of released frames are kept
-// for the next upload: hipMalloc / hipFree cost tens of microseconds and hipFree waits for the whole device -- in a live
-// system every key-frame insertion would stall the extractor's streams.
-struct FramePool {
-  std::mutex m;
-  std::vector<Slab> slabs;
-  std::vector<std::pair<int, hipEvent_t>> events;
-  static constexpr size_t kKeepSlabs = 80, kKeepEvents = 256;
-  ~FramePool() {}  // (process exit: the runtime reclaims device memory; no HIP calls from static destructors)
-};
-FramePool g_framePool;
-}  // namespace
-
-namespace orbfe {
-hipError_t slab_get(int device, size_t bytes, Slab* out) {
-  {
-    std::lock_guard<std::mutex> lk(g_framePool.m);
-    auto& v = g_framePool.slabs;
-    int best = -1;
-    for (size_t i = 0; i < v.size(); i++)
-      if (v[i].device == device && v[i].cap >= bytes && v[i].cap <= 4 * bytes + (1u << 16) && (best < 0 || v[i].cap < v[(size_t)best].cap))
-        best = (int)i;
-    if (best >= 0) {
-      *out = v[(size_t)best];
-      v.erase(v.begin() + best);
-      return hipSuccess;
-    }
-  }
-  const size_t want = (bytes + (1u << 16) - 1) & ~(size_t)((1u << 16) - 1);  // 64 KB classes: users of similar size share slabs
-  *out = Slab{};
-  hipError_t e = hipMalloc(&out->p, want);
-  if (e == hipSuccess) { out->cap = want; out->device = device; } else out->p = nullptr;
-  return e;
-}
-void slab_put(Slab* s) {
-  if (!s->p) return;
-  bool kept = false;
-  {
-    std::lock_guard<std::mutex> lk(g_framePool.m);
-    if (g_framePool.slabs.size() < FramePool::kKeepSlabs) { g_framePool.slabs.push_back(*s); kept = true; }
-  }
-  if (!kept) (void)hipFree(s->p);
-  *s = Slab{};
-}
-}  // namespace orbfe
-
-namespace {
-hipError_t event_get(int device, hipEvent_t* e) {
-  {
-    std::lock_guard<std::mutex> lk(g_framePool.m);
-    auto& v = g_framePool.events;
-    for (size_t i = 0; i < v.size(); i++)
-      if (v[i].first == device) { *e = v[i].second; v.erase(v.begin() + (long)i); return hipSuccess; }
-  }
-  return hipEventCreateWithFlags(e, hipEventDisableTiming);
-}
-void event_put(int device, hipEvent_t e) {
-  if (!e) return;
-  {
-    std::lock_guard<std::mutex> lk(g_framePool.m);
-    if (g_framePool.events.size() < FramePool::kKeepEvents) { g_framePool.events.push_back({device, e}); return; }
-  }
-  (void)hipEventDestroy(e);
-}
-
-// A search that reads a resident frame on ITS stream: ordered behind the frame's upload + grid build (which ran on the
-// uploading thread's stream) by the frame's event -- the upload itself does not wait for the device.  Once any consumer
-// has synchronised behind the event the frame is settled and nothing waits any more.
-thread_local std::vector<const orbfe_frame*> t_unsettled;
-hipError_t frame_use(Arena* ar, const orbfe_frame* f) {
-  if (!f || f->settled.load(std::memory_order_acquire)) return hipSuccess;
-  hipError_t e = hipStreamWaitEvent(ar->stream, f->ready, 0);
-  if (e == hipSuccess) t_unsettled.push_back(f);
-  return e;
-}
-void frames_settle() {  // call after the stream of the call has been synchronised
-  for (const orbfe_frame* f : t_unsettled) f->settled.store(true, std::memory_order_release);
-  t_unsettled.clear();
-}
-// an entry point that returns early (a HIP error between frame_use and its synchronisation) must not leave frames on the
-// list: they could be released before this thread's next call settles -- and writes to -- them
-struct UnsettledScope {
-  UnsettledScope() { t_unsettled.clear(); }
-  ~UnsettledScope() { t_unsettled.clear(); }
-};
-}  // namespace
-
-extern "C" void orbfe_frame_release(orbfe_frame* f) {
-  if (!f) return;
-  (void)hipSetDevice(f->device);
-  // a frame whose own upload may still be in flight (released before any search used it): its slab must not be handed
-  // to the next upload until then
-  if (f->ready && !f->settled.load(std::memory_order_acquire)) (void)hipEventSynchronize(f->ready);
-  for (size_t i = 0; i < t_unsettled.size();)
-    if (t_unsettled[i] == f) t_unsettled.erase(t_unsettled.begin() + (long)i); else i++;
-  slab_put(&f->slab);
-  event_put(f->device, f->ready);
-  delete f;
-}
-
-extern "C" const orbfe_frame_view* orbfe_frame_get_view(const orbfe_frame* f) { return f ? &f->view : nullptr; }
-
-namespace {
-// host side of a resident frame: copies of what the claim loops / gates read, the canonical view, the slab layout
-struct FrameLayout { size_t oX, oY, oA, oU, oO, oK, oC, oI, oD, oS, total; };
-int frame_host_init(const char* who, int device, const orbfe_frame_view* v, const orbfe_featvec* fv, orbfe_frame** outF,
-                    FrameLayout* L, size_t* nIdxOut) {
-  if (!v || v->n < 0 || v->n > GRID_MAX_FEATURES || !(v->max_x > v->min_x) || !(v->max_y > v->min_y) ||
-      (v->n > 0 && (!v->x || !v->y || !v->octave || !v->desc)))
-    return fail(ORBFE_ERR_INVALID, std::string(who) + ": bad frame view (x, y, octave, desc and the image bounds are required)");
-  const int n = v->n;
-  if (fv && !featvec_ok(fv, n)) return fail(ORBFE_ERR_INVALID, std::string(who) + ": malformed FeatureVector");
-  orbfe_frame* f = new (std::nothrow) orbfe_frame();
-  if (!f) return fail(ORBFE_ERR_NOMEM, "out of memory");
-  f->device = device; f->n = n;
-  f->hx.assign(v->x, v->x + n); f->hy.assign(v->y, v->y + n); f->hoct.assign(v->octave, v->octave + n);
-  f->hdesc.assign(v->desc, v->desc + (size_t)n * 32);
-  if (v->angle) f->hangle.assign(v->angle, v->angle + n);
-  if (v->u_right) f->hur.assign(v->u_right, v->u_right + n);
-  f->hstereo.assign((size_t)n, 0);
-  if (v->u_right) for (int i = 0; i < n; i++) f->hstereo[i] = v->u_right[i] >= 0 ? 1 : 0;
-  size_t nIdx = 0;
-  if (fv) {
-    f->haveFv = true;
-    if (fv->n_nodes > 0) {  // (an EMPTY FeatureVector may come with NULL arrays: nothing is read from them)
-      f->nodeIds.assign(fv->node_ids, fv->node_ids + fv->n_nodes);
-      f->offsets.assign(fv->offsets, fv->offsets + fv->n_nodes + 1);
-      nIdx = (size_t)fv->offsets[fv->n_nodes];
-      f->hindices.assign(fv->indices, fv->indices + nIdx);
-    } else {
-      f->offsets.assign(1, 0);
-    }
-    f->fv.n_nodes = fv->n_nodes; f->fv.node_ids = f->nodeIds.data(); f->fv.offsets = f->offsets.data(); f->fv.indices = f->hindices.data();
-  }
-  orbfe_frame_view& c = f->view;
-  c.n = n; c.x = f->hx.data(); c.y = f->hy.data(); c.octave = f->hoct.data();
-  c.angle = v->angle ? f->hangle.data() : nullptr;
-  c.u_right = v->u_right ? f->hur.data() : nullptr;
-  c.desc = f->hdesc.data();
-  c.min_x = v->min_x; c.max_x = v->max_x; c.min_y = v->min_y; c.max_y = v->max_y;
-  c.resident = f;
-  // one slab: x y angle u_right | octave | key | cell | indices | desc | stereo.  The index list gets room for one index per
-  // feature even when no FeatureVector comes with the upload: orbfe_frame_set_featvec may attach it later (Frame::ComputeBoW
-  // runs after the constructor, src/Tracking.cc:836-843)
-  const size_t N = (size_t)(n ? n : 1);
-  size_t off = 0;
-  auto place = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  // what always comes from the host first (mvuRight, stereo flags, index list, then the positions), what the device can
-  // supply behind it (angles, octaves, descriptors), what the grid build writes last: an upload is ONE copy of [0, oK), a
-  // frame built from the extractor's records ONE copy of [0, oX) (or [0, oA) with caller-undistorted positions)
-  L->oU = place(N * 4); L->oS = place(N); L->oI = place((nIdx > N ? nIdx : N) * 4); L->oX = place(N * 4); L->oY = place(N * 4);
-  L->oA = place(N * 4); L->oO = place(N * 4); L->oD = place(N * 32); L->oK = place(N * 4); L->oC = place(3073 * 4);
-  L->total = off;
-  hipError_t err = hipSetDevice(device);
-  if (err == hipSuccess) err = slab_get(device, off, &f->slab);
-  if (err == hipSuccess) err = event_get(device, &f->ready);
-  if (err != hipSuccess) {
-    orbfe_frame_release(f);
-    return fail(hip_status(err), std::string(who) + ": " + hipGetErrorString(err));
-  }
-  f->settled.store(false);
-  uint8_t* b = (uint8_t*)f->slab.p;
-  f->dx = (float*)(b + L->oX); f->dy = (float*)(b + L->oY); f->dangle = (float*)(b + L->oA); f->dur = (float*)(b + L->oU);
-  f->doct = (int32_t*)(b + L->oO); f->dkey = (uint32_t*)(b + L->oK); f->dcell = (int32_t*)(b + L->oC); f->dindices = (uint32_t*)(b + L->oI);
-  f->ddesc = b + L->oD; f->dstereo = b + L->oS;
-  *outF = f;
-  *nIdxOut = nIdx;
-  return ORBFE_OK;
-}
-
-// grid build behind whatever filled the slab, then the ready event: NO host wait (frame_use orders the consumers)
-hipError_t frame_finish(Arena* ar, orbfe_frame* f, const orbfe_frame_view* v) {
-  GridFrame g{};
-  g.x = f->dx; g.y = f->dy; g.octave = f->doct; g.uRight = v->u_right ? f->dur : nullptr; g.desc = f->ddesc; g.n = f->n;
-  g.minX = v->min_x; g.minY = v->min_y;
-  g.wInv = 64.0f / (v->max_x - v->min_x);
-  g.hInv = 48.0f / (v->max_y - v->min_y);
-  launch_grid_build(ar->stream, g, f->dkey, f->dcell);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventRecord(f->ready, ar->stream);
-  return err;
-}
-}  // namespace
-
-extern "C" int orbfe_frame_upload(int device, const orbfe_frame_view* v, const orbfe_featvec* fv, orbfe_frame** out) {
-  if (!out) return fail(ORBFE_ERR_INVALID, "frame_upload: NULL argument");
-  *out = nullptr;
-  orbfe_frame* f = nullptr;
-  FrameLayout L;
-  size_t nIdx = 0;
-  int rc = frame_host_init("frame_upload", device, v, fv, &f, &L, &nIdx);
-  if (rc != ORBFE_OK) return rc;
-  const int n = f->n;
-  // only what the searches read goes up: the key / cell arrays behind it are written by the grid build
-  const size_t upBytes = L.oK;
-  Arena* ar;
-  // staged through the thread's pinned mirror: one copy up, then the grid build (Frame::AssignFeaturesToGrid, once)
-  hipError_t err = arena_begin(device, 1024, &ar);
-  if (err == hipSuccess) err = staging_reserve(upBytes);
-  if (err == hipSuccess) {
-    uint8_t* h = t_staging.h;
-    if (n) {
-      std::memcpy(h + L.oX, f->hx.data(), (size_t)n * 4); std::memcpy(h + L.oY, f->hy.data(), (size_t)n * 4);
-      if (v->angle) std::memcpy(h + L.oA, f->hangle.data(), (size_t)n * 4); else std::memset(h + L.oA, 0, (size_t)n * 4);
-      if (v->u_right) std::memcpy(h + L.oU, f->hur.data(), (size_t)n * 4); else std::memset(h + L.oU, 0, (size_t)n * 4);
-      std::memcpy(h + L.oO, f->hoct.data(), (size_t)n * 4);
-      std::memcpy(h + L.oD, f->hdesc.data(), (size_t)n * 32);
-      std::memcpy(h + L.oS, f->hstereo.data(), (size_t)n);
-    }
-    if (nIdx) std::memcpy(h + L.oI, f->hindices.data(), nIdx * 4);
-    // ONE copy (every further hipMemcpyAsync costs the host ~5 us)
-    err = hipMemcpyAsync(f->slab.p, h, upBytes, hipMemcpyHostToDevice, ar->stream);
-    if (err == hipSuccess) err = staging_mark_pending(ar->stream);  // the next use of the staging buffer waits for these copies
-  }
-  if (err == hipSuccess) err = frame_finish(ar, f, v);
-  if (err != hipSuccess) { orbfe_frame_release(f); return fail(hip_status(err), std::string("frame_upload: ") + hipGetErrorString(err)); }
-  *out = f;
-  return ORBFE_OK;
-}
-
-// Frame::Frame (src/Frame.cc:61-117) is extract -> undistort -> stereo -> grid: the keypoint records and descriptors the
-// extractor produced are still in HBM when the Frame is built.  orbfe_frame_from_device makes the resident operands from
-// THOSE (28-byte records -> x / y / angle / octave arrays, descriptors device to device, grid built on the device): of
-// the frame's 60 bytes per keypoint only mvuRight (and, with ORBFE_FRAME_XY_FROM_VIEW, the undistorted positions) travel
-// over PCIe.  `view` holds the host arrays the claim loops read (what orbfe_extract returned to the caller, after its own
-// UndistortKeyPoints); view->n records are taken.
-extern "C" int orbfe_frame_from_device(int device, const orbfe_keypoint* d_keypoints, const uint8_t* d_descriptors,
-                                       const orbfe_frame_view* view, const orbfe_featvec* fv, int flags, orbfe_frame** out) {
-  if (!out) return fail(ORBFE_ERR_INVALID, "frame_from_device: NULL argument");
-  *out = nullptr;
-  if (view && view->n > 0 && (!d_keypoints || !d_descriptors)) return fail(ORBFE_ERR_INVALID, "frame_from_device: NULL device arrays");
-  orbfe_frame* f = nullptr;
-  FrameLayout L;
-  size_t nIdx = 0;
-  int rc = frame_host_init("frame_from_device", device, view, fv, &f, &L, &nIdx);
-  if (rc != ORBFE_OK) return rc;
-  const int n = f->n;
-  const bool xyFromView = (flags & ORBFE_FRAME_XY_FROM_VIEW) != 0;
-  Arena* ar;
-  hipError_t err = arena_begin(device, 1024, &ar);
-  // host part: mvuRight + stereo flags + the FeatureVector's index list (+ positions), adjacent at the head of the slab:
-  // ONE copy through the pinned staging
-  const size_t hostBytes = xyFromView ? L.oA : L.oX;
-  const bool anyHost = view->u_right || nIdx || xyFromView;
-  if (err == hipSuccess && anyHost) err = staging_reserve(hostBytes);
-  if (err == hipSuccess && n && anyHost) {
-    uint8_t* h = t_staging.h;
-    if (view->u_right) { std::memcpy(h + L.oU, f->hur.data(), (size_t)n * 4); std::memcpy(h + L.oS, f->hstereo.data(), (size_t)n); }
-    else { std::memset(h + L.oU, 0, (size_t)n * 4); std::memset(h + L.oS, 0, (size_t)n); }
-    if (nIdx) std::memcpy(h + L.oI, f->hindices.data(), nIdx * 4);
-    if (xyFromView) { std::memcpy(h + L.oX, f->hx.data(), (size_t)n * 4); std::memcpy(h + L.oY, f->hy.data(), (size_t)n * 4); }
-    err = hipMemcpyAsync(f->slab.p, h, hostBytes, hipMemcpyHostToDevice, ar->stream);
-    if (err == hipSuccess) err = staging_mark_pending(ar->stream);
-  }
-  if (err == hipSuccess && n) {
-    launch_frame_from_records(ar->stream, reinterpret_cast<const float*>(d_keypoints), d_descriptors, n, xyFromView ? nullptr : f->dx,
-                              xyFromView ? nullptr : f->dy, f->dangle, f->doct, f->ddesc, anyHost ? nullptr : f->dstereo);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = frame_finish(ar, f, view);
-  if (err != hipSuccess) { orbfe_frame_release(f); return fail(hip_status(err), std::string("frame_from_device: ") + hipGetErrorString(err)); }
-  *out = f;
-  return ORBFE_OK;
-}
-
-extern "C" int orbfe_frame_from_extractor(orbfe_extractor* e, int frame, const orbfe_frame_view* view, const orbfe_featvec* fv,
-                                          int flags, orbfe_frame** out) {
-  if (!out) return fail(ORBFE_ERR_INVALID, "frame_from_extractor: NULL argument");
-  *out = nullptr;
-  const orbfe_keypoint* dkp = nullptr;
-  const uint8_t* ddesc = nullptr;
-  int n = 0, device = 0;
-  int rc = orbfe_extractor_output_device_(e, frame, &dkp, &ddesc, &n, &device);
-  if (rc != ORBFE_OK) return rc;
-  if (!view || view->n > n) return fail(ORBFE_ERR_INVALID, "frame_from_extractor: the view holds more keypoints than the extractor produced for this frame");
-  rc = orbfe_frame_from_device(device, dkp, ddesc, view, fv, flags, out);
-  if (rc != ORBFE_OK) return rc;
-  // the build reads the handle's output block on this thread's stream without a host wait: the handle's next call that
-  // rewrites the block waits for it
-  rc = orbfe_extractor_reader_end_(e, t_arenas[device].stream);
-  if (rc != ORBFE_OK) { orbfe_frame_release(*out); *out = nullptr; }
-  return rc;
-}
-
-// Frame::ComputeBoW runs after the constructor (src/Tracking.cc:836-843, src/Frame.cc:433-440): attach the FeatureVector
-// to a frame that was made resident without one.  Call it before any search uses the frame (it rewrites the index list);
-// the calling thread may differ from the building one (LocalMapping's KeyFrame::ComputeBoW): frame_use orders the copy.
-extern "C" int orbfe_frame_set_featvec(orbfe_frame* f, const orbfe_featvec* fv) {
-  UnsettledScope unsettledScope;
-  if (!f || !fv) return fail(ORBFE_ERR_INVALID, "frame_set_featvec: NULL argument");
-  if (!featvec_ok(fv, f->n)) return fail(ORBFE_ERR_INVALID, "frame_set_featvec: malformed FeatureVector");
-  const size_t nIdx = fv->n_nodes > 0 ? (size_t)fv->offsets[fv->n_nodes] : 0;
-  if (nIdx > (size_t)(f->n ? f->n : 1)) return fail(ORBFE_ERR_INVALID, "frame_set_featvec: more indices than features");
-  if (fv->n_nodes > 0) {
-    f->nodeIds.assign(fv->node_ids, fv->node_ids + fv->n_nodes);
-    f->offsets.assign(fv->offsets, fv->offsets + fv->n_nodes + 1);
-    f->hindices.assign(fv->indices, fv->indices + nIdx);
-  } else {
-    f->nodeIds.clear(); f->hindices.clear(); f->offsets.assign(1, 0);
-  }
-  f->fv.n_nodes = fv->n_nodes; f->fv.node_ids = f->nodeIds.data(); f->fv.offsets = f->offsets.data(); f->fv.indices = f->hindices.data();
-  f->haveFv = true;
-  if (nIdx == 0) return ORBFE_OK;
-  Arena* ar;
-  hipError_t err = arena_begin(f->device, 1024, &ar);
-  if (err == hipSuccess) err = staging_reserve(nIdx * 4);
-  // the frame's own build copy covers the index region and may still be queued on the building thread's stream
-  if (err == hipSuccess) err = frame_use(ar, f);
-  if (err == hipSuccess) {
-    std::memcpy(t_staging.h, f->hindices.data(), nIdx * 4);
-    err = hipMemcpyAsync(f->dindices, t_staging.h, nIdx * 4, hipMemcpyHostToDevice, ar->stream);
-  }
-  if (err == hipSuccess) err = hipStreamSynchronize(ar->stream);  // (the handle may be in use on other streams afterwards)
-  if (err != hipSuccess) return fail(hip_status(err), std::string("frame_set_featvec: ") + hipGetErrorString(err));
-  frames_settle();
-  return ORBFE_OK;
-}
-
-extern "C" int orbfe_frame_synchronize(const orbfe_frame* f) {
-  if (!f) return fail(ORBFE_ERR_INVALID, "frame_synchronize: NULL frame");
-  if (f->settled.load(std::memory_order_acquire)) return ORBFE_OK;
-  hipError_t err = hipSetDevice(f->device);
-  if (err == hipSuccess) err = hipEventSynchronize(f->ready);
-  if (err != hipSuccess) return fail(hip_status(err), std::string("frame_synchronize: ") + hipGetErrorString(err));
-  f->settled.store(true, std::memory_order_release);
-  return ORBFE_OK;
-}
-
-// ---- test hook (tests/stream_order.py): hold back / query the calling thread's matcher stream on `device` ----
-extern "C" int orbfe_debug_stall_thread_stream(int device, int usec) {
-  if (usec < 0 || usec > 1000000) return fail(ORBFE_ERR_INVALID, "debug_stall: usec must be 0 .. 1000000");
-  Arena* ar;
-  hipError_t err = arena_begin(device, 0, &ar);
-  if (err != hipSuccess) return fail(hip_status(err), std::string("debug_stall: ") + hipGetErrorString(err));
-  return orbfe_debug_stall_launch_(ar->stream, usec);
-}
-
-extern "C" int orbfe_debug_thread_stream_idle(int device) {
-  Arena* ar;
-  hipError_t err = arena_begin(device, 0, &ar);
-  if (err != hipSuccess) return fail(hip_status(err), std::string("debug_stream_idle: ") + hipGetErrorString(err));
-  return orbfe_debug_stream_idle_(ar->stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1044,28 +486,32 @@ extern "C" int orbfe_compute_stereo_matches(orbfe_extractor* left, int frameL, o
   }
   Arena* ar;
   const int rows = a.pyrL.lv[0].h;
-  HIPCHK(arena_begin(devL, pad((size_t)N * 60) + pad((size_t)Nr * 60) + 3 * pad((size_t)N * 4) + pad((size_t)Nr * 4) +
-                           pad((size_t)(rows + 1) * 4) + 4096, &ar));
-  float *dkl, *dkr;
-  uint8_t *ddl, *ddr;
-  HIPCHK(up(ar, &dkl, reinterpret_cast<const float*>(kpL), (size_t)N * 7));
-  HIPCHK(up(ar, &dkr, reinterpret_cast<const float*>(kpR), (size_t)Nr * 7));
-  HIPCHK(up(ar, &ddl, descL, (size_t)N * 32));
-  HIPCHK(up(ar, &ddr, descR, (size_t)Nr * 32));
-  a.kpL = dkl; a.descL = ddl; a.N = N; a.kpR = dkr; a.descR = ddr; a.Nr = Nr;
+  a.N = N; a.Nr = Nr;
   a.frameL = frameL; a.frameR = frameR;
   a.mbf = mbf;
   a.maxD = mbf / mb;  // minZ = mb, maxD = mbf/minZ (:542-544)
-  a.uRight = carve<float>(ar, N);
-  a.depth = carve<float>(ar, N);
-  int32_t* dcount = carve<int32_t>(ar, 1);  // (right behind the two outputs: one copy brings all three back)
-  a.sad = carve<int32_t>(ar, N);
-  if (rows + 1 <= 8192) {  // row index of the right keypoints (k_stereo_bucket)
-    a.rowStart = carve<int32_t>(ar, (size_t)rows + 1);
-    a.sortedIdx = carve<int32_t>(ar, (size_t)Nr);
-    a.rows = rows;
-    a.bandR = (int)std::ceil(2.0f * scL[nlL - 1]) + 2;
-  }
+  int32_t* dcount = nullptr;
+  auto stage = [&](Arena* s) -> hipError_t {
+    float *dkl, *dkr;
+    uint8_t *ddl, *ddr;
+    TRY(up(s, &dkl, reinterpret_cast<const float*>(kpL), (size_t)N * 7));
+    TRY(up(s, &dkr, reinterpret_cast<const float*>(kpR), (size_t)Nr * 7));
+    TRY(up(s, &ddl, descL, (size_t)N * 32));
+    TRY(up(s, &ddr, descR, (size_t)Nr * 32));
+    a.kpL = dkl; a.descL = ddl; a.kpR = dkr; a.descR = ddr;
+    a.uRight = carve<float>(s, N);
+    a.depth = carve<float>(s, N);
+    dcount = carve<int32_t>(s, 1);  // (right behind the two outputs: one copy brings all three back)
+    a.sad = carve<int32_t>(s, N);
+    if (rows + 1 <= 8192) {  // row index of the right keypoints (k_stereo_bucket)
+      a.rowStart = carve<int32_t>(s, (size_t)rows + 1);
+      a.sortedIdx = carve<int32_t>(s, (size_t)Nr);
+      a.rows = rows;
+      a.bandR = (int)std::ceil(2.0f * scL[nlL - 1]) + 2;
+    }
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(devL, &ar, stage));
   HIPCHK(flush(ar));
   launch_stereo(ar->stream, a, dcount);
   HIPCHK(hipGetLastError());
@@ -1514,160 +960,12 @@ extern "C" int orbfe_search_by_projection(int device, const orbfe_frame_view* F,
   return window_search_multi(device, &job, 1, 32);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Device-resident map points (include/orbfe.h: orbfe_mappoints).  One slab from the pool holds the table; an update is one
-// staged copy and one scatter launch on the calling thread's stream, complete on return.  The argument checks and the
-// layouts are mappoints_host.h (no device needed: tests/cpp/mappoints_host_san.cpp runs them under the sanitizers).
-// ---------------------------------------------------------------------------------------------
-struct orbfe_mappoints {
-  int device = 0, capacity = 0;
-  std::mutex m;  // a handle serialises its own calls
-  Slab slab;     // empty until the first call that needs the device
-  MapPointsDevice d{};
-};
-
-namespace {
-// the table's slab, every slot bad until it is updated; enqueued on the arena's stream
-hipError_t mappoints_ready(orbfe_mappoints* mp, Arena* ar) {
-  if (mp->slab.p) return hipSuccess;
-  const MapPointsLayout L = mappoints_layout(mp->capacity);
-  TRY(slab_get(mp->device, L.total, &mp->slab));
-  uint8_t* b = static_cast<uint8_t*>(mp->slab.p);
-  mp->d.rec = reinterpret_cast<float4*>(b + L.oRec); mp->d.desc = b + L.oDesc; mp->d.flags = b + L.oFlags;
-  hipError_t e = hipMemsetAsync(b, 0, L.oFlags, ar->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(mp->d.flags, ORBFE_MP_BAD, (size_t)mp->capacity, ar->stream);
-  // complete before the handle counts as ready: another thread's stream may be the next to read the table
-  if (e == hipSuccess) e = hipStreamSynchronize(ar->stream);
-  if (e != hipSuccess) { slab_put(&mp->slab); mp->d = MapPointsDevice{}; }
-  return e;
-}
-bool pose_ok(const orbfe_camera_pose* p) { return p && p->n_levels >= 1 && p->n_levels <= ORBFE_MAX_LEVELS * 4; }
-
-// k_project_frustum with the isInFrustum outputs (n > 0, arguments checked, the handle locked): slot list and mask up, one
-// launch, the eight arrays back in one copy
-int project_run(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip, const orbfe_camera_pose* pose, float limit,
-                uint8_t* in_view, int32_t* level, float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z,
-                float* dist) {
-  const size_t q = (size_t)n;
-  Arena* ar;
-  HIPCHK(arena_begin(mp->device, 10 * pad(q * 4) + 1024, &ar));
-  HIPCHK(mappoints_ready(mp, ar));
-  ProjectArgs pa{};
-  int32_t* dslot;
-  uint8_t* dskip = nullptr;
-  HIPCHK(up(ar, &dslot, slot, q));
-  if (skip) HIPCHK(up(ar, &dskip, skip, q));
-  // the outputs adjacent: one copy back
-  pa.level = carve<int32_t>(ar, q); pa.viewCos = carve<float>(ar, q); pa.projX = carve<float>(ar, q); pa.projY = carve<float>(ar, q);
-  pa.projXr = carve<float>(ar, q); pa.invZ = carve<float>(ar, q); pa.dist = carve<float>(ar, q); pa.inView = carve<uint8_t>(ar, q);
-  pa.table = mp->d; pa.slot = dslot; pa.skip = dskip; pa.n = n; pa.cam = *pose; pa.limit = limit;
-  HIPCHK(flush(ar));
-  launch_project_frustum(ar->stream, pa);
-  HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, pa.level, pa.inView + q));
-  HIPCHK(hipStreamSynchronize(ar->stream));
-  if (level) std::memcpy(level, mirror_of(ar, pa.level), q * 4);
-  if (view_cos) std::memcpy(view_cos, mirror_of(ar, pa.viewCos), q * 4);
-  if (proj_x) std::memcpy(proj_x, mirror_of(ar, pa.projX), q * 4);
-  if (proj_y) std::memcpy(proj_y, mirror_of(ar, pa.projY), q * 4);
-  if (proj_xr) std::memcpy(proj_xr, mirror_of(ar, pa.projXr), q * 4);
-  if (inv_z) std::memcpy(inv_z, mirror_of(ar, pa.invZ), q * 4);
-  if (dist) std::memcpy(dist, mirror_of(ar, pa.dist), q * 4);
-  if (in_view) std::memcpy(in_view, mirror_of(ar, pa.inView), q);
-  return ORBFE_OK;
-}
-}  // namespace
-
-extern "C" int orbfe_mappoints_create(int device, int capacity, orbfe_mappoints** out) {
-  if (const char* e = mappoints_check_create(capacity, out)) return fail(ORBFE_ERR_INVALID, std::string("mappoints_create: ") + e);
-  *out = nullptr;
-  if (device < 0) return fail(ORBFE_ERR_INVALID, "mappoints_create: negative device");
-  orbfe_mappoints* mp = new (std::nothrow) orbfe_mappoints();
-  if (!mp) return fail(ORBFE_ERR_NOMEM, "out of memory");
-  mp->device = device; mp->capacity = capacity;
-  *out = mp;
-  return ORBFE_OK;
-}
-
-extern "C" void orbfe_mappoints_destroy(orbfe_mappoints* mp) {
-  if (!mp) return;
-  if (mp->slab.p) {  // (every call on the table has completed on return: nothing can still read the slab)
-    (void)hipSetDevice(mp->device);
-    slab_put(&mp->slab);
-  }
-  delete mp;
-}
-
-extern "C" int orbfe_mappoints_capacity(const orbfe_mappoints* mp) { return mp ? mp->capacity : fail(ORBFE_ERR_INVALID, "mappoints_capacity: NULL table"); }
-
-extern "C" int orbfe_mappoints_update(orbfe_mappoints* mp, int n, const int32_t* slot, const float* pos, const float* normal,
-                                      const float* min_dist, const float* max_dist, const uint8_t* desc, const uint8_t* flags) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "mappoints_update: NULL table");
-  if (const char* e = mappoints_check_update(mp->capacity, n, slot, pos, normal, min_dist, max_dist, flags))
-    return fail(ORBFE_ERR_INVALID, std::string("mappoints_update: ") + e);
-  if (n == 0) return ORBFE_OK;
-  std::lock_guard<std::mutex> lk(mp->m);
-  const MapPointsStage S = mappoints_stage_layout(n, desc != nullptr);
-  Arena* ar;
-  HIPCHK(arena_begin(mp->device, S.total, &ar));
-  HIPCHK(mappoints_ready(mp, ar));
-  HIPCHK(staging_reserve(S.total));
-  uint8_t* h = t_staging.h;
-  mappoints_pack(h, S, n, slot, pos, normal, min_dist, max_dist, desc, flags);
-  uint8_t* din = carve<uint8_t>(ar, S.total);
-  HIPCHK(hipMemcpyAsync(din, h, S.total, hipMemcpyHostToDevice, ar->stream));
-  launch_mappoints_scatter(ar->stream, mp->d, n, reinterpret_cast<const int32_t*>(din + S.oSlot), reinterpret_cast<const float4*>(din + S.oRec),
-                           din + S.oFlags, desc ? din + S.oDesc : nullptr);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ar->stream));
-  return ORBFE_OK;
-}
-
-// ---- back doors for poseopt.hip (host_internal.h) ----
-// the calling thread's arena on `device`, begun with `bytes` of device memory and as much of its pinned mirror, and its stream
-extern "C" int orbfe_thread_scratch_(int device, size_t bytes, uint8_t** d, uint8_t** h, hipStream_t* s) {
-  Arena* ar;
-  HIPCHK(arena_begin(device, bytes, &ar));
-  HIPCHK(grow_mirror(ar, bytes));
-  *d = ar->base;
-  *h = ar->hmirror;
-  *s = ar->stream;
-  return ORBFE_OK;
-}
-// holds the handle's serialisation until orbfe_mappoints_unlock_, with the table on the device
-extern "C" int orbfe_mappoints_lock_(orbfe_mappoints* mp, const float4** rec, const uint8_t** flags, int* device) {
-  mp->m.lock();
-  Arena* ar;
-  hipError_t e = arena_begin(mp->device, 0, &ar);
-  if (e == hipSuccess) e = mappoints_ready(mp, ar);
-  if (e != hipSuccess) {
-    mp->m.unlock();
-    return fail(hip_status(e), std::string("mappoints: ") + hipGetErrorString(e));
-  }
-  *rec = mp->d.rec;
-  *flags = mp->d.flags;
-  *device = mp->device;
-  return ORBFE_OK;
-}
-extern "C" void orbfe_mappoints_unlock_(orbfe_mappoints* mp) { mp->m.unlock(); }
-
-extern "C" int orbfe_project_in_frustum(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
-                                        const orbfe_camera_pose* pose, float viewing_cos_limit, uint8_t* in_view, int32_t* level,
-                                        float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z, float* dist) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "project_in_frustum: NULL table");
-  if (const char* e = mappoints_check_slots(mp->capacity, n, slot)) return fail(ORBFE_ERR_INVALID, std::string("project_in_frustum: ") + e);
-  if (!pose_ok(pose)) return fail(ORBFE_ERR_INVALID, "project_in_frustum: bad pose (n_levels must be 1 .. 64)");
-  if (n == 0) return ORBFE_OK;
-  std::lock_guard<std::mutex> lk(mp->m);
-  return project_run(mp, n, slot, skip, pose, viewing_cos_limit, in_view, level, view_cos, proj_x, proj_y, proj_xr, inv_z, dist);
-}
-
 extern "C" int orbfe_search_local_points(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
                                          const orbfe_camera_pose* pose, float viewing_cos_limit, const orbfe_frame_view* F,
                                          const float* scale_factors, int n_levels, const uint8_t* blocked, float th, float nnratio,
                                          int32_t* match, int32_t* n_matches, uint8_t* in_view) {
   if (!mp) return fail(ORBFE_ERR_INVALID, "search_local_points: NULL table");
-  if (const char* e = mappoints_check_slots(mp->capacity, n, slot)) return fail(ORBFE_ERR_INVALID, std::string("search_local_points: ") + e);
+  if (const char* e = mappoints_check_slots(orbfe_mappoints_capacity(mp), n, slot)) return fail(ORBFE_ERR_INVALID, std::string("search_local_points: ") + e);
   F = canon(F);
   if (!frame_ok(F) || !scale_factors || n_levels <= 0 || !pose_ok(pose) || pose->n_levels > n_levels || !n_matches ||
       (F->n > 0 && (!match || !F->desc)))
@@ -1675,18 +973,15 @@ extern "C" int orbfe_search_local_points(orbfe_mappoints* mp, int n, const int32
   for (int i = 0; i < F->n; i++) match[i] = -1;
   *n_matches = 0;
   if (n == 0) return ORBFE_OK;
-  std::lock_guard<std::mutex> lk(mp->m);
   if (F->n == 0) {  // nothing to search: the flags alone
-    return in_view ? project_run(mp, n, slot, skip, pose, viewing_cos_limit, in_view, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
+    return in_view ? orbfe_project_in_frustum(mp, n, slot, skip, pose, viewing_cos_limit, in_view, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr)
                    : ORBFE_OK;
   }
-  {
-    Arena* ar;
-    HIPCHK(arena_begin(mp->device, 0, &ar));
-    HIPCHK(mappoints_ready(mp, ar));
-  }
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
   FrustumProducer P;
-  P.table = mp->d; P.slot = slot; P.skip = skip; P.pose = *pose; P.limit = viewing_cos_limit; P.th = th;
+  P.table = *lock.table; P.slot = slot; P.skip = skip; P.pose = *pose; P.limit = viewing_cos_limit; P.th = th;
   P.scale = scale_factors; P.nLevels = n_levels; P.inViewOut = in_view;
   ClaimSpec C;
   C.mode = CLAIM_RATIO; C.maxDist = 100 /* TH_HIGH */; C.nnratio = nnratio;
@@ -1696,7 +991,7 @@ extern "C" int orbfe_search_local_points(orbfe_mappoints* mp, int n, const int32
   job.f = F; job.nq = n;
   job.claim = &C;
   job.producer = &P;
-  return window_search_multi(mp->device, &job, 1, 32);
+  return window_search_multi(lock.device, &job, 1, 32);
 }
 
 extern "C" int orbfe_search_by_projection_last_frame(int device, const orbfe_frame_view* Cur, const float* scale_factors,

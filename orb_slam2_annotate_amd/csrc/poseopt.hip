@@ -1,6 +1,7 @@
 // poseopt.hip -- C-ABI entry points of the pose-only optimisation (include/orbfe.h, "Optimizer::PoseOptimization").  A call
 // is one staged copy up, ONE launch of k_pose_optimize (k_poseopt.hip) and one copy back on the calling thread's matcher
-// stream, complete on return.  The argument checks and the arena layout are poseopt_host.h (no device needed).
+// stream (arena.h: arena_scratch), complete on return.  The argument checks and the arena layout are poseopt_host.h (no device
+// needed).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -8,6 +9,7 @@
 #include <string>
 
 #include "../../include/orbfe.h"
+#include "arena.h"
 #include "host_internal.h"
 #include "poseopt_host.h"
 #include "poseopt_kernels.h"
@@ -36,8 +38,9 @@ struct Staged {
 
 int stage_begin(int device, const PoseOptLayout& L, Staged* S) {
   S->L = L;
-  int rc = orbfe_thread_scratch_(device, L.total, &S->d, &S->h, &S->s);
-  if (rc) return rc;
+  Arena* ar;
+  HIPCHK(arena_scratch(device, L.total, &ar));
+  S->d = ar->base; S->h = ar->hmirror; S->s = ar->stream;
   PoseOptArgs& a = S->a;
   uint8_t* d = S->d;
   a.prob = reinterpret_cast<const PoseOptProblem*>(d + L.oProb);
@@ -139,18 +142,11 @@ extern "C" int orbfe_pose_optimization_mappoints(orbfe_mappoints* mp, int n_slot
                                           inv_level_sigma2, n_levels, K5, Tcw_in, Tcw_out, outlier, n_inliers))
     return fail(ORBFE_ERR_INVALID, std::string("pose_optimization_mappoints: ") + e);
   const int nf = F->n;
-  const float4* rec;
-  const uint8_t* flags;
-  int device = 0;
-  int rc = orbfe_mappoints_lock_(mp, &rec, &flags, &device);
-  if (rc) return rc;
-  struct Unlock {
-    orbfe_mappoints* mp;
-    ~Unlock() { orbfe_mappoints_unlock_(mp); }
-  } unlock{mp};
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
   Staged S;
-  rc = stage_begin(device, poseopt_layout(1, nf, true, F->u_right != nullptr, n_slots, n_levels, sizeof(PoseOptProblem),
-                                          sizeof(PoseOptResult)), &S);
+  int rc = stage_begin(lock.device, poseopt_layout(1, nf, true, F->u_right != nullptr, n_slots, n_levels, sizeof(PoseOptProblem),
+                                                   sizeof(PoseOptResult)), &S);
   if (rc) return rc;
   const PoseOptLayout& L = S.L;
   PoseOptProblem* hp = reinterpret_cast<PoseOptProblem*>(S.h + L.oProb);
@@ -168,7 +164,7 @@ extern "C" int orbfe_pose_optimization_mappoints(orbfe_mappoints* mp, int n_slot
   std::memcpy(S.h + L.oLevelTab, inv_level_sigma2, (size_t)n_levels * 4);
   PoseOptArgs& a = S.a;
   a.gather = 1;
-  a.table.rec = const_cast<float4*>(rec); a.table.desc = nullptr; a.table.flags = const_cast<uint8_t*>(flags);
+  a.table = *lock.table;
   a.slot = reinterpret_cast<const int32_t*>(S.d + L.oSlot);
   a.match = reinterpret_cast<const int32_t*>(S.d + L.oMatch);
   a.featX = reinterpret_cast<const float*>(S.d + L.oFeatX);

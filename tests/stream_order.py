@@ -710,13 +710,13 @@ CASES = {
     "stale_output_block": Case(stale_output_block, pins=[],
                                bug="a stale output block served after a pipelined or rectified call"),
     "frame_synchronize": Case(frame_synchronize, pins=[
-        "matcher.hip:orbfe_frame_synchronize:hipEventSynchronize(f->ready)",
+        "frames.hip:orbfe_frame_synchronize:hipEventSynchronize(f->ready)",
     ]),
     "frame_ready_cross_thread": Case(frame_ready_cross_thread, pins=[
-        "matcher.hip:frame_use:hipStreamWaitEvent(ar->stream, f->ready)",
+        "frames.hip:frame_use:hipStreamWaitEvent(ar->stream, f->ready)",
     ]),
     "staging_reuse": Case(staging_reuse, pins=[
-        "matcher.hip:staging_reserve:hipEventSynchronize(t_staging.pending)",
+        "arena.hip:staging_reserve:hipEventSynchronize(t_staging.pending)",
     ]),
     "consumer_vs_extract_subbatch": Case(consumer_vs_extract_subbatch, pins=[
         "extractor.hip:run_pipeline:hipStreamWaitEvent(s, e->evConsumerDone)",
@@ -755,7 +755,7 @@ NOT_CASED = {
     "extractor.hip:orbfe_extract_batch_pipelined:hipStreamWaitEvent(e->stream, e->evChunkDone[i])":
         "the call drains stream 0 and extra[] first and all sub-batches of a chunk wait on the same copy events, so no "
         "stall holds one sub-batch back against stream 0",
-    "matcher.hip:orbfe_frame_release:hipEventSynchronize(f->ready)":
+    "frames.hip:orbfe_frame_release:hipEventSynchronize(f->ready)":
         "teardown: a frame released before its build finished; the wait guards the slab's return to the pool",
 }
 

@@ -1,0 +1,79 @@
+"""CPU drift guard of csrc/arena.h, csrc/frame.h and csrc/mappoints.hip: the thread arena, the resident frames and the
+map-point table are each owned by one file and reached through one interface.  A host file that begins the arena by a
+hand-written size, names the thread-local state, or looks into a table handle would bring the second way back."""
+import re
+from pathlib import Path
+
+from test_host_internal_header import _DEFN, _code
+
+CSRC = Path(__file__).resolve().parent.parent / "orb_slam2_annotate_amd" / "csrc"
+ARENA = {"arena.h", "arena.hip"}
+# what only the arena's own files may name: the begin behind arena_stage / arena_scratch / arena_stream and the hand sum's
+# helper; what only arena.hip may name: the thread-local state
+ARENA_ONLY = re.compile(r"\b(arena_begin|pad)\s*\(")
+STATE_ONLY = re.compile(r"\b(t_arenas|t_staging)\b")
+TABLE_ONLY = re.compile(r"\bmappoints_ready\b|\bmp\s*->\s*(?:slab|m|d)\b")
+
+
+def files(root=CSRC):
+    return {p.name: _code(p.read_text()) for p in sorted(root.iterdir()) if p.suffix in (".hip", ".cpp", ".h", ".inc")}
+
+
+def named_outside(rx, owners, root=CSRC):
+    """(file, name) of every match of rx in a file of csrc/ that is not one of `owners`."""
+    return sorted({(n, m.group(0).split("(")[0].strip()) for n, t in files(root).items() if n not in owners
+                   for m in rx.finditer(t)})
+
+
+def defining(fn, root=CSRC):
+    return [n for n, t in files(root).items() if any(m.group(2).split("::")[-1] == fn for m in _DEFN.finditer(t))]
+
+
+def test_the_scan_reads_the_owners():
+    f = files()
+    assert ARENA_ONLY.search(f["arena.hip"]) and ARENA_ONLY.search(f["arena.h"])  # arena_begin: defined / behind arena_stage
+    assert {m.group(1) for m in STATE_ONLY.finditer(f["arena.hip"])} == {"t_arenas", "t_staging"}
+    assert TABLE_ONLY.search(f["mappoints.hip"])
+    for way in ("arena_stage", "arena_scratch", "arena_stream"):
+        users = [n for n, t in f.items() if n not in ARENA and re.search(r"\b" + way + r"\s*\(", t)]
+        assert users, f"{way} (csrc/arena.h) is used by no other file"
+
+
+def test_only_the_arena_begins_the_arena_and_nothing_sums_by_hand():
+    assert not named_outside(ARENA_ONLY, ARENA), "carve inside arena_stage(), or take arena_scratch() / arena_stream()"
+
+
+def test_the_thread_local_state_is_named_only_in_arena_hip():
+    assert not named_outside(STATE_ONLY, {"arena.hip"})
+
+
+def test_the_raw_pointer_back_door_is_gone():
+    assert not [n for n, t in files().items() if "orbfe_thread_scratch_" in t]
+
+
+def test_one_file_defines_each_pool_and_the_frame_ordering():
+    assert defining("slab_get") == ["arena.hip"]
+    assert defining("event_get") == ["arena.hip"]
+    assert defining("frame_use") == ["frames.hip"]
+
+
+def test_the_table_handle_is_private_to_mappoints_hip():
+    owners = [n for n, t in files().items() if re.search(r"^struct\s+orbfe_mappoints\s*\{", t, re.M)]
+    assert owners == ["mappoints.hip"], owners
+    assert not named_outside(TABLE_ONLY, {"mappoints.hip"}), "reach the table through MapPointsLock (csrc/host_internal.h)"
+
+
+def test_the_guard_notices_a_hand_summed_begin(tmp_path):
+    """A scratch copy of csrc/ whose matcher.hip begins the arena by a size of its own again, and one that looks into the
+    table handle."""
+    for p in CSRC.iterdir():
+        if p.suffix in (".hip", ".h", ".cpp", ".inc"):
+            (tmp_path / p.name).write_text(p.read_text())
+    assert not named_outside(ARENA_ONLY, ARENA, tmp_path) and not named_outside(TABLE_ONLY, {"mappoints.hip"}, tmp_path)
+    m = tmp_path / "matcher.hip"
+    text = m.read_text()
+    assert text.count("  HIPCHK(arena_stage(device, &ar, stage));\n") >= 1
+    m.write_text(text.replace("  HIPCHK(arena_stage(device, &ar, stage));\n", "  HIPCHK(arena_begin(device, 2 * n, &ar));\n", 1))
+    assert named_outside(ARENA_ONLY, ARENA, tmp_path) == [("matcher.hip", "arena_begin")]
+    m.write_text(text.replace("  MapPointsLock lock(mp);\n", "  std::lock_guard<std::mutex> lk(mp->m);\n", 1))
+    assert named_outside(TABLE_ONLY, {"mappoints.hip"}, tmp_path) == [("matcher.hip", "mp->m")]

@@ -12,8 +12,8 @@ CALLS = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\s*\(")
 # closing brace in column 0
 ALLOWED = {
     "host_internal.h:DevBuf": "DevBuf / PinBuf: the owning buffer every other site holds",
-    "matcher.hip:slab_get": "the slab pool hands out a kept slab or allocates one of the next size class",
-    "matcher.hip:slab_put": "the slab pool frees a slab it has no room to keep",
+    "arena.hip:slab_get": "the slab pool hands out a kept slab or allocates one of the next size class",
+    "arena.hip:slab_put": "the slab pool frees a slab it has no room to keep",
     "extractor.hip:orbfe_host_alloc": "public raw allocator of pinned host memory (include/orbfe.h)",
     "extractor.hip:orbfe_host_free": "frees what orbfe_host_alloc returned",
 }
@@ -46,7 +46,7 @@ def strays(root=CSRC):
 
 def test_the_scan_finds_the_owners():
     where = {w for w, _ in raw_calls()}
-    assert {"matcher.hip:slab_get", "matcher.hip:slab_put", "extractor.hip:orbfe_host_alloc",
+    assert {"arena.hip:slab_get", "arena.hip:slab_put", "extractor.hip:orbfe_host_alloc",
             "extractor.hip:orbfe_host_free"} <= where, where
     assert {c for w, c in raw_calls() if w == "host_internal.h:DevBuf"} == {"hipMalloc", "hipFree", "hipHostMalloc",
                                                                             "hipHostFree"}
@@ -66,7 +66,7 @@ def test_every_allowed_site_exists_and_has_a_reason():
 def test_one_source_file_defines_the_slab_pool():
     defining = [p.name for p in sorted(CSRC.iterdir()) if p.suffix in (".hip", ".cpp", ".h")
                 and any(m.group(2).split("::")[-1] == "slab_get" for m in _DEFN.finditer(_code(p.read_text())))]
-    assert defining == ["matcher.hip"], defining
+    assert defining == ["arena.hip"], defining
 
 
 def test_the_guard_notices_a_hand_made_allocation(tmp_path):
@@ -87,10 +87,10 @@ def test_the_guard_bounds_a_function_by_its_closing_brace(tmp_path):
     for p in CSRC.iterdir():
         if p.suffix in (".hip", ".h", ".cpp"):
             (tmp_path / p.name).write_text(p.read_text())
-    m = tmp_path / "matcher.hip"
+    m = tmp_path / "arena.hip"
     text = m.read_text()
     at = text.index("\n}\n", text.index("\nvoid slab_put(")) + 3
     m.write_text(text[:at] + "  inline void drop(void* q) { (void)hipFree(q); }\n" + text[at:])
     h = tmp_path / "host_internal.h"
     h.write_text(h.read_text().replace("struct Slab {", "inline void drop_pinned(void* q) { (void)hipHostFree(q); }\nstruct Slab {", 1))
-    assert strays(tmp_path) == [("host_internal.h:drop_pinned", "hipHostFree"), ("matcher.hip:?", "hipFree")]
+    assert strays(tmp_path) == [("arena.hip:?", "hipFree"), ("host_internal.h:drop_pinned", "hipHostFree")]

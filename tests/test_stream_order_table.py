@@ -79,7 +79,7 @@ def test_the_scan_finds_the_known_waits():
     s = sites()
     assert sum(s.values()) >= 20, s
     assert "extractor.hip:run_pipeline:hipStreamWaitEvent(s, e->evConsumerDone)" in s
-    assert "matcher.hip:frame_use:hipStreamWaitEvent(ar->stream, f->ready)" in s
+    assert "frames.hip:frame_use:hipStreamWaitEvent(ar->stream, f->ready)" in s
 
 
 def test_every_wait_is_cased_or_listed_exactly_once():
