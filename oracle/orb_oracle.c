@@ -870,6 +870,25 @@ int orc_stereo_branch_counts(int64_t *out, int n) {
   return ORC_SB_COUNT;
 }
 #define SB(k) (g_stereo_branch[ORC_SB_##k]++)
+/* one counter per exit / decision of the grid window and of the searches built on it (Frame::GetFeaturesInArea and the
+   projection searches, SearchForInitialization, Fuse, SearchBySim3, ComputeThreeMaxima) taken by this thread's last
+   search call; the order is ORC_WB_* below and in orb_oracle.h.  Reset when a search call starts; they change no result. */
+enum { ORC_WB_EMPTY_MINX_PAST, ORC_WB_EMPTY_MAXX_NEG, ORC_WB_EMPTY_MINY_PAST, ORC_WB_EMPTY_MAXY_NEG, ORC_WB_CLAMP_MINX,
+       ORC_WB_CLAMP_MAXX, ORC_WB_CLAMP_MINY, ORC_WB_CLAMP_MAXY, ORC_WB_LEVEL_REJECT_LOW, ORC_WB_LEVEL_REJECT_HIGH,
+       ORC_WB_RADIUS_REJECT, ORC_WB_AREA_ACCEPT, ORC_WB_BLOCKED, ORC_WB_STEREO_REJECT, ORC_WB_STEREO_PASS,
+       ORC_WB_STEREO_SKIPPED, ORC_WB_CHI2_MONO_PASS, ORC_WB_CHI2_MONO_REJECT, ORC_WB_CHI2_STEREO_PASS,
+       ORC_WB_CHI2_STEREO_REJECT, ORC_WB_BETTER_BEST, ORC_WB_BETTER_SECOND, ORC_WB_TIE_IGNORED, ORC_WB_NO_CANDIDATE,
+       ORC_WB_THRESHOLD_REJECT, ORC_WB_RATIO_REJECT, ORC_WB_RATIO_PASS_LEVELS_DIFFER, ORC_WB_ACCEPTED,
+       ORC_WB_INIT_OVERWRITE, ORC_WB_INIT_REFUSED, ORC_WB_HIST_PRUNED, ORC_WB_HIST_PRUNE_ALREADY_UNMATCHED,
+       ORC_WB_MAX2_BELOW_TENTH, ORC_WB_MAX3_BELOW_TENTH, ORC_WB_MAXIMA_ALL_KEPT, ORC_WB_SIM3_MUTUAL,
+       ORC_WB_SIM3_ONE_WAY_ONLY, ORC_WB_COUNT };
+static __thread int64_t g_window_branch[ORC_WB_COUNT];
+int orc_window_branch_counts(int64_t *out, int n) {
+  for (int i = 0; i < n && i < ORC_WB_COUNT; i++) out[i] = g_window_branch[i];
+  return ORC_WB_COUNT;
+}
+#define WB(k) (g_window_branch[ORC_WB_##k]++)
+#define WB_RESET() memset(g_window_branch, 0, sizeof(g_window_branch))
 
 int orc_descriptor_distance(const uint8_t *a, const uint8_t *b) { /* :1828-1844 */
   int dist = 0;
@@ -886,7 +905,7 @@ int orc_descriptor_distance(const uint8_t *a, const uint8_t *b) { /* :1828-1844 
   return dist;
 }
 
-void orc_three_maxima(const int *hs, int L, int *ind1, int *ind2, int *ind3) { /* :1777-1821 */
+static void three_maxima(const int *hs, int L, int *ind1, int *ind2, int *ind3) { /* :1777-1821 */
   int max1 = 0, max2 = 0, max3 = 0;
   for (int i = 0; i < L; i++) {
     const int s = hs[i];
@@ -894,8 +913,13 @@ void orc_three_maxima(const int *hs, int L, int *ind1, int *ind2, int *ind3) { /
     else if (s > max2) { max3 = max2; max2 = s; *ind3 = *ind2; *ind2 = i; }
     else if (s > max3) { max3 = s; *ind3 = i; }
   }
-  if (max2 < 0.1f * (float)max1) { *ind2 = -1; *ind3 = -1; }
-  else if (max3 < 0.1f * (float)max1) { *ind3 = -1; }
+  if (max2 < 0.1f * (float)max1) { *ind2 = -1; *ind3 = -1; WB(MAX2_BELOW_TENTH); }
+  else if (max3 < 0.1f * (float)max1) { *ind3 = -1; WB(MAX3_BELOW_TENTH); }
+  else WB(MAXIMA_ALL_KEPT);
+}
+void orc_three_maxima(const int *hs, int L, int *ind1, int *ind2, int *ind3) {
+  WB_RESET();
+  three_maxima(hs, L, ind1, ind2, ind3);
 }
 
 #define HISTO_LENGTH 30
@@ -915,10 +939,10 @@ static void rh_push(rothist *h, float a1, float a2, int idx) { /* :272-281 */
 }
 static int rh_prune(rothist *h, int32_t *arr) { /* :303-322; returns removed count */
   int i1 = -1, i2 = -1, i3 = -1, removed = 0;
-  orc_three_maxima(h->n, HISTO_LENGTH, &i1, &i2, &i3);
+  three_maxima(h->n, HISTO_LENGTH, &i1, &i2, &i3);
   for (int i = 0; i < HISTO_LENGTH; i++) {
     if (i == i1 || i == i2 || i == i3) continue;
-    for (int j = 0; j < h->n[i]; j++) { arr[h->v[i][j]] = -1; removed++; }
+    for (int j = 0; j < h->n[i]; j++) { arr[h->v[i][j]] = -1; removed++; WB(HIST_PRUNED); }
   }
   return removed;
 }
@@ -1423,22 +1447,22 @@ void orc_frame_build_grid(orc_frame *f) {
 }
 void orc_frame_free_grid(orc_frame *f) { free(f->cell_off); free(f->cell_idx); f->cell_off = NULL; f->cell_idx = NULL; }
 
-int orc_features_in_area(const orc_frame *f, float x, float y, float r, int minLevel, int maxLevel, int32_t *out, int cap) {
+static int features_in_area(const orc_frame *f, float x, float y, float r, int minLevel, int maxLevel, int32_t *out, int cap) {
   const float wInv = (float)ORC_GRID_COLS / (f->mnMaxX - f->mnMinX);
   const float hInv = (float)ORC_GRID_ROWS / (f->mnMaxY - f->mnMinY);
   int n = 0;
   int nMinCellX = (int)floorf((x - f->mnMinX - r) * wInv);
-  if (nMinCellX < 0) nMinCellX = 0;
-  if (nMinCellX >= ORC_GRID_COLS) return 0;
+  if (nMinCellX < 0) { nMinCellX = 0; WB(CLAMP_MINX); }
+  if (nMinCellX >= ORC_GRID_COLS) { WB(EMPTY_MINX_PAST); return 0; }
   int nMaxCellX = (int)ceilf((x - f->mnMinX + r) * wInv);
-  if (nMaxCellX > ORC_GRID_COLS - 1) nMaxCellX = ORC_GRID_COLS - 1;
-  if (nMaxCellX < 0) return 0;
+  if (nMaxCellX > ORC_GRID_COLS - 1) { nMaxCellX = ORC_GRID_COLS - 1; WB(CLAMP_MAXX); }
+  if (nMaxCellX < 0) { WB(EMPTY_MAXX_NEG); return 0; }
   int nMinCellY = (int)floorf((y - f->mnMinY - r) * hInv);
-  if (nMinCellY < 0) nMinCellY = 0;
-  if (nMinCellY >= ORC_GRID_ROWS) return 0;
+  if (nMinCellY < 0) { nMinCellY = 0; WB(CLAMP_MINY); }
+  if (nMinCellY >= ORC_GRID_ROWS) { WB(EMPTY_MINY_PAST); return 0; }
   int nMaxCellY = (int)ceilf((y - f->mnMinY + r) * hInv);
-  if (nMaxCellY > ORC_GRID_ROWS - 1) nMaxCellY = ORC_GRID_ROWS - 1;
-  if (nMaxCellY < 0) return 0;
+  if (nMaxCellY > ORC_GRID_ROWS - 1) { nMaxCellY = ORC_GRID_ROWS - 1; WB(CLAMP_MAXY); }
+  if (nMaxCellY < 0) { WB(EMPTY_MAXY_NEG); return 0; }
   const int bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
   for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
     for (int iy = nMinCellY; iy <= nMaxCellY; iy++) {
@@ -1446,14 +1470,19 @@ int orc_features_in_area(const orc_frame *f, float x, float y, float r, int minL
       for (int j = f->cell_off[c]; j < f->cell_off[c + 1]; j++) {
         const int id = f->cell_idx[j];
         if (bCheckLevels) {
-          if (f->octave[id] < minLevel) continue;
-          if (maxLevel >= 0 && f->octave[id] > maxLevel) continue;
+          if (f->octave[id] < minLevel) { WB(LEVEL_REJECT_LOW); continue; }
+          if (maxLevel >= 0 && f->octave[id] > maxLevel) { WB(LEVEL_REJECT_HIGH); continue; }
         }
         const float distx = f->x[id] - x, disty = f->y[id] - y;
-        if (fabsf(distx) < r && fabsf(disty) < r) { if (n < cap) out[n] = id; n++; }
+        if (fabsf(distx) < r && fabsf(disty) < r) { if (n < cap) out[n] = id; n++; WB(AREA_ACCEPT); }
+        else WB(RADIUS_REJECT);
       }
     }
   return n;
+}
+int orc_features_in_area(const orc_frame *f, float x, float y, float r, int minLevel, int maxLevel, int32_t *out, int cap) {
+  WB_RESET();
+  return features_in_area(f, x, y, r, minLevel, maxLevel, out, cap);
 }
 
 /* src/ORBmatcher.cc:140-150 */
@@ -1465,6 +1494,7 @@ int orc_search_by_projection_mappoints(orc_frame *F, const float *sf, const uint
                                        const uint8_t *mp_desc, const uint8_t *mp_obs_positive, float th, float nnratio,
                                        int32_t *match) {
   int nmatches = 0;
+  WB_RESET();
   const int bFactor = th != 1.0;
   uint8_t *blocked = (uint8_t *)malloc((size_t)(F->N > 0 ? F->N : 1));
   memcpy(blocked, blocked0, (size_t)F->N);
@@ -1475,28 +1505,35 @@ int orc_search_by_projection_mappoints(orc_frame *F, const float *sf, const uint
     const int nPredictedLevel = level[iMP];
     float r = radius_by_viewing_cos(view_cos[iMP]);
     if (bFactor) r *= th;
-    const int nc = orc_features_in_area(F, proj_x[iMP], proj_y[iMP], r * sf[nPredictedLevel], nPredictedLevel - 1,
+    const int nc = features_in_area(F, proj_x[iMP], proj_y[iMP], r * sf[nPredictedLevel], nPredictedLevel - 1,
                                         nPredictedLevel, vIdx, F->N);
     if (nc == 0) continue;
     const uint8_t *d0 = mp_desc + (size_t)iMP * 32;
     int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
     for (int c = 0; c < nc; c++) {
       const int idx = vIdx[c];
-      if (blocked[idx]) continue;
+      if (blocked[idx]) { WB(BLOCKED); continue; }
       if (F->uRight && F->uRight[idx] > 0) {
         const float er = fabsf(proj_xr[iMP] - F->uRight[idx]);
-        if (er > r * sf[nPredictedLevel]) continue;
-      }
+        if (er > r * sf[nPredictedLevel]) { WB(STEREO_REJECT); continue; }
+        WB(STEREO_PASS);
+      } else if (F->uRight) WB(STEREO_SKIPPED);
       const int dist = orc_descriptor_distance(d0, F->desc + (size_t)idx * 32);
-      if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = F->octave[idx]; bestIdx = idx; }
-      else if (dist < bestDist2) { bestLevel2 = F->octave[idx]; bestDist2 = dist; }
+      if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = F->octave[idx]; bestIdx = idx; WB(BETTER_BEST); }
+      else {
+        if (dist == bestDist) WB(TIE_IGNORED);
+        if (dist < bestDist2) { bestLevel2 = F->octave[idx]; bestDist2 = dist; WB(BETTER_SECOND); }
+      }
     }
     if (bestDist <= TH_HIGH) {
-      if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
+      if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) { WB(RATIO_REJECT); continue; }
+      if ((float)bestDist > nnratio * (float)bestDist2) WB(RATIO_PASS_LEVELS_DIFFER);
       match[bestIdx] = iMP;
       blocked[bestIdx] = mp_obs_positive ? mp_obs_positive[iMP] : 1;
       nmatches++;
-    }
+      WB(ACCEPTED);
+    } else if (bestIdx < 0) WB(NO_CANDIDATE);
+    else WB(THRESHOLD_REJECT);
   }
   free(vIdx);
   free(blocked);
@@ -1509,6 +1546,7 @@ int orc_search_by_projection_lastframe(orc_frame *Cur, const float *sf, float mb
                                        const uint8_t *blocked_at_entry, int mode, float th, int check_ori,
                                        int32_t *match_cur) {
   int nmatches = 0;
+  WB_RESET();
   rothist rh;
   rh_init(&rh, nLast > Cur->N ? nLast : Cur->N);
   for (int i = 0; i < Cur->N; i++) match_cur[i] = -1;
@@ -1520,29 +1558,33 @@ int orc_search_by_projection_lastframe(orc_frame *Cur, const float *sf, float mb
     const int nLastOctave = last_octave[i];
     const float radius = th * sf[nLastOctave];
     int nc;
-    if (mode == 1) nc = orc_features_in_area(Cur, u[i], v[i], radius, nLastOctave, -1, vIdx, Cur->N);
-    else if (mode == 2) nc = orc_features_in_area(Cur, u[i], v[i], radius, 0, nLastOctave, vIdx, Cur->N);
-    else nc = orc_features_in_area(Cur, u[i], v[i], radius, nLastOctave - 1, nLastOctave + 1, vIdx, Cur->N);
+    if (mode == 1) nc = features_in_area(Cur, u[i], v[i], radius, nLastOctave, -1, vIdx, Cur->N);
+    else if (mode == 2) nc = features_in_area(Cur, u[i], v[i], radius, 0, nLastOctave, vIdx, Cur->N);
+    else nc = features_in_area(Cur, u[i], v[i], radius, nLastOctave - 1, nLastOctave + 1, vIdx, Cur->N);
     if (nc == 0) continue;
     const uint8_t *dMP = mp_desc + (size_t)i * 32;
     int bestDist = 256, bestIdx2 = -1;
     for (int c = 0; c < nc; c++) {
       const int i2 = vIdx[c];
-      if (blocked[i2]) continue; /* mvpMapPoints[i2] set with Observations()>0 */
+      if (blocked[i2]) { WB(BLOCKED); continue; } /* mvpMapPoints[i2] set with Observations()>0 */
       if (Cur->uRight && Cur->uRight[i2] > 0) {
         const float ur = u[i] - mbf * invzc[i];
         const float er = fabsf(ur - Cur->uRight[i2]);
-        if (er > radius) continue;
-      }
+        if (er > radius) { WB(STEREO_REJECT); continue; }
+        WB(STEREO_PASS);
+      } else if (Cur->uRight) WB(STEREO_SKIPPED);
       const int dist = orc_descriptor_distance(dMP, Cur->desc + (size_t)i2 * 32);
-      if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
+      if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; WB(BETTER_BEST); }
+      else if (dist == bestDist) WB(TIE_IGNORED);
     }
     if (bestDist <= TH_HIGH) {
       match_cur[bestIdx2] = i;
       blocked[bestIdx2] = obs_positive ? obs_positive[i] : 1;
       nmatches++;
+      WB(ACCEPTED);
       if (check_ori) rh_push(&rh, last_angle[i], Cur->angle[bestIdx2], bestIdx2);
-    }
+    } else if (bestIdx2 < 0) WB(NO_CANDIDATE);
+    else WB(THRESHOLD_REJECT);
   }
   if (check_ori) nmatches -= rh_prune(&rh, match_cur);
   rh_free(&rh);
@@ -1556,6 +1598,7 @@ int orc_search_by_projection_reloc(orc_frame *Cur, const float *sf, int n, const
                                    const uint8_t *mp_desc, const uint8_t *blocked0, float th, int orb_dist,
                                    int check_ori, int32_t *match_cur) {
   int nmatches = 0;
+  WB_RESET();
   rothist rh;
   rh_init(&rh, n);
   for (int i = 0; i < Cur->N; i++) match_cur[i] = -1;
@@ -1566,22 +1609,25 @@ int orc_search_by_projection_reloc(orc_frame *Cur, const float *sf, int n, const
     if (!valid[i]) continue;
     const int nPredictedLevel = level[i];
     const float radius = th * sf[nPredictedLevel];
-    const int nc = orc_features_in_area(Cur, u[i], v[i], radius, nPredictedLevel - 1, nPredictedLevel + 1, vIdx, Cur->N);
+    const int nc = features_in_area(Cur, u[i], v[i], radius, nPredictedLevel - 1, nPredictedLevel + 1, vIdx, Cur->N);
     if (nc == 0) continue;
     const uint8_t *dMP = mp_desc + (size_t)i * 32;
     int bestDist = 256, bestIdx2 = -1;
     for (int c = 0; c < nc; c++) {
       const int i2 = vIdx[c];
-      if (blocked[i2]) continue; /* CurrentFrame.mvpMapPoints[i2] != NULL */
+      if (blocked[i2]) { WB(BLOCKED); continue; } /* CurrentFrame.mvpMapPoints[i2] != NULL */
       const int dist = orc_descriptor_distance(dMP, Cur->desc + (size_t)i2 * 32);
-      if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
+      if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; WB(BETTER_BEST); }
+      else if (dist == bestDist) WB(TIE_IGNORED);
     }
     if (bestDist <= orb_dist) {
       match_cur[bestIdx2] = i;
       blocked[bestIdx2] = 1;
       nmatches++;
+      WB(ACCEPTED);
       if (check_ori) rh_push(&rh, kf_angle[i], Cur->angle[bestIdx2], bestIdx2);
-    }
+    } else if (bestIdx2 < 0) WB(NO_CANDIDATE);
+    else WB(THRESHOLD_REJECT);
   }
   if (check_ori) nmatches -= rh_prune(&rh, match_cur);
   rh_free(&rh);
@@ -1594,6 +1640,7 @@ int orc_search_by_projection_sim3(orc_frame *KF, const float *sf, int n, const u
                                   const float *v, const int32_t *level, const uint8_t *mp_desc,
                                   const uint8_t *matched0, float th, int32_t *match) {
   int nmatches = 0;
+  WB_RESET();
   for (int i = 0; i < KF->N; i++) match[i] = -1;
   uint8_t *matched = (uint8_t *)calloc((size_t)(KF->N > 0 ? KF->N : 1), 1);
   if (matched0) memcpy(matched, matched0, (size_t)KF->N);
@@ -1602,19 +1649,23 @@ int orc_search_by_projection_sim3(orc_frame *KF, const float *sf, int n, const u
     if (!valid[i]) continue;
     const int nPredictedLevel = level[i];
     const float radius = th * sf[nPredictedLevel];
-    const int nc = orc_features_in_area(KF, u[i], v[i], radius, -1, -1, vIdx, KF->N); /* KeyFrame::GetFeaturesInArea */
+    const int nc = features_in_area(KF, u[i], v[i], radius, -1, -1, vIdx, KF->N); /* KeyFrame::GetFeaturesInArea */
     if (nc == 0) continue;
     const uint8_t *dMP = mp_desc + (size_t)i * 32;
     int bestDist = 256, bestIdx = -1;
     for (int c = 0; c < nc; c++) {
       const int idx = vIdx[c];
-      if (matched[idx]) continue;
+      if (matched[idx]) { WB(BLOCKED); continue; }
       const int kpLevel = KF->octave[idx];
-      if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
+      if (kpLevel < nPredictedLevel - 1) { WB(LEVEL_REJECT_LOW); continue; }
+      if (kpLevel > nPredictedLevel) { WB(LEVEL_REJECT_HIGH); continue; }
       const int dist = orc_descriptor_distance(dMP, KF->desc + (size_t)idx * 32);
-      if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
+      if (dist < bestDist) { bestDist = dist; bestIdx = idx; WB(BETTER_BEST); }
+      else if (dist == bestDist) WB(TIE_IGNORED);
     }
-    if (bestDist <= TH_LOW) { match[bestIdx] = i; matched[bestIdx] = 1; nmatches++; }
+    if (bestDist <= TH_LOW) { match[bestIdx] = i; matched[bestIdx] = 1; nmatches++; WB(ACCEPTED); }
+    else if (bestIdx < 0) WB(NO_CANDIDATE);
+    else WB(THRESHOLD_REJECT);
   }
   free(vIdx);
   free(matched);
@@ -1624,6 +1675,7 @@ int orc_search_by_projection_sim3(orc_frame *KF, const float *sf, int n, const u
 int orc_search_for_initialization(const orc_frame *F1, orc_frame *F2, float *prev_x, float *prev_y, int window,
                                   float nnratio, int check_ori, int32_t *match12) {
   int nmatches = 0;
+  WB_RESET();
   for (int i = 0; i < F1->N; i++) match12[i] = -1;
   rothist rh;
   rh_init(&rh, F1->N);
@@ -1635,36 +1687,42 @@ int orc_search_for_initialization(const orc_frame *F1, orc_frame *F2, float *pre
   for (int i1 = 0; i1 < F1->N; i1++) {
     const int level1 = F1->octave[i1];
     if (level1 > 0) continue;
-    const int nc = orc_features_in_area(F2, prev_x[i1], prev_y[i1], (float)window, level1, level1, vIdx, F2->N);
+    const int nc = features_in_area(F2, prev_x[i1], prev_y[i1], (float)window, level1, level1, vIdx, F2->N);
     if (nc == 0) continue;
     const uint8_t *d1 = F1->desc + (size_t)i1 * 32;
     int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx2 = -1;
     for (int c = 0; c < nc; c++) {
       const int i2 = vIdx[c];
       const int dist = orc_descriptor_distance(d1, F2->desc + (size_t)i2 * 32);
-      if (vMatchedDistance[i2] <= dist) continue;
-      if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx2 = i2; }
-      else if (dist < bestDist2) bestDist2 = dist;
+      if (vMatchedDistance[i2] <= dist) { WB(INIT_REFUSED); continue; }
+      if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx2 = i2; WB(BETTER_BEST); }
+      else {
+        if (dist == bestDist) WB(TIE_IGNORED);
+        if (dist < bestDist2) { bestDist2 = dist; WB(BETTER_SECOND); }
+      }
     }
     if (bestDist <= TH_LOW) {
       if ((float)bestDist < (float)bestDist2 * nnratio) {
-        if (vnMatches21[bestIdx2] >= 0) { match12[vnMatches21[bestIdx2]] = -1; nmatches--; }
+        if (vnMatches21[bestIdx2] >= 0) { match12[vnMatches21[bestIdx2]] = -1; nmatches--; WB(INIT_OVERWRITE); }
         match12[i1] = bestIdx2;
         vnMatches21[bestIdx2] = i1;
         vMatchedDistance[bestIdx2] = bestDist;
         nmatches++;
+        WB(ACCEPTED);
         if (check_ori) rh_push(&rh, F1->angle[i1], F2->angle[bestIdx2], i1);
-      }
-    }
+      } else WB(RATIO_REJECT);
+    } else if (bestIdx2 < 0) WB(NO_CANDIDATE);
+    else WB(THRESHOLD_REJECT);
   }
   if (check_ori) { /* :568-592: only entries still matched are cleared and counted */
     int i1 = -1, i2 = -1, i3 = -1;
-    orc_three_maxima(rh.n, HISTO_LENGTH, &i1, &i2, &i3);
+    three_maxima(rh.n, HISTO_LENGTH, &i1, &i2, &i3);
     for (int i = 0; i < HISTO_LENGTH; i++) {
       if (i == i1 || i == i2 || i == i3) continue;
       for (int j = 0; j < rh.n[i]; j++) {
         const int idx1 = rh.v[i][j];
-        if (match12[idx1] >= 0) { match12[idx1] = -1; nmatches--; }
+        if (match12[idx1] >= 0) { match12[idx1] = -1; nmatches--; WB(HIST_PRUNED); }
+        else WB(HIST_PRUNE_ALREADY_UNMATCHED);
       }
     }
   }
@@ -1681,35 +1739,42 @@ void orc_fuse_search(orc_frame *KF, const float *sf, const float *inv_level_sigm
                      const float *u, const float *v, const float *ur, const int32_t *level, const uint8_t *mp_desc,
                      float th, int chi2, int32_t *best_idx) {
   int32_t *vIdx = (int32_t *)malloc(sizeof(int32_t) * (size_t)(KF->N > 0 ? KF->N : 1));
+  WB_RESET();
   for (int i = 0; i < n; i++) {
     best_idx[i] = -1;
     if (!valid[i]) continue;
     const int nPredictedLevel = level[i];
     const float radius = th * sf[nPredictedLevel];
-    const int nc = orc_features_in_area(KF, u[i], v[i], radius, -1, -1, vIdx, KF->N);
+    const int nc = features_in_area(KF, u[i], v[i], radius, -1, -1, vIdx, KF->N);
     const uint8_t *dMP = mp_desc + (size_t)i * 32;
     int bestDist = 256, bestIdx = -1;
     for (int c = 0; c < nc; c++) {
       const int idx = vIdx[c];
       const int kpLevel = KF->octave[idx];
-      if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
+      if (kpLevel < nPredictedLevel - 1) { WB(LEVEL_REJECT_LOW); continue; }
+      if (kpLevel > nPredictedLevel) { WB(LEVEL_REJECT_HIGH); continue; }
       if (chi2) {
         const float kpx = KF->x[idx], kpy = KF->y[idx];
         if (KF->uRight && KF->uRight[idx] >= 0) {
           const float kpr = KF->uRight[idx];
           const float ex = u[i] - kpx, ey = v[i] - kpy, er = ur[i] - kpr;
           const float e2 = ex * ex + ey * ey + er * er;
-          if (e2 * inv_level_sigma2[kpLevel] > 7.8) continue;
+          if (e2 * inv_level_sigma2[kpLevel] > 7.8) { WB(CHI2_STEREO_REJECT); continue; }
+          WB(CHI2_STEREO_PASS);
         } else {
           const float ex = u[i] - kpx, ey = v[i] - kpy;
           const float e2 = ex * ex + ey * ey;
-          if (e2 * inv_level_sigma2[kpLevel] > 5.99) continue;
+          if (e2 * inv_level_sigma2[kpLevel] > 5.99) { WB(CHI2_MONO_REJECT); continue; }
+          WB(CHI2_MONO_PASS);
         }
       }
       const int dist = orc_descriptor_distance(dMP, KF->desc + (size_t)idx * 32);
-      if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
+      if (dist < bestDist) { bestDist = dist; bestIdx = idx; WB(BETTER_BEST); }
+      else if (dist == bestDist) WB(TIE_IGNORED);
     }
-    if (bestDist <= TH_LOW) best_idx[i] = bestIdx;
+    if (bestDist <= TH_LOW) { best_idx[i] = bestIdx; WB(ACCEPTED); }
+    else if (bestIdx < 0) WB(NO_CANDIDATE);
+    else WB(THRESHOLD_REJECT);
   }
   free(vIdx);
 }
@@ -1722,16 +1787,20 @@ static void sim3_one_way(orc_frame *KF, const float *sf, int n, const uint8_t *v
     if (!valid[i]) continue;
     const int nPredictedLevel = level[i];
     const float radius = th * sf[nPredictedLevel];
-    const int nc = orc_features_in_area(KF, u[i], v[i], radius, -1, -1, vIdx, KF->N);
+    const int nc = features_in_area(KF, u[i], v[i], radius, -1, -1, vIdx, KF->N);
     const uint8_t *dMP = desc + (size_t)i * 32;
     int bestDist = INT_MAX, bestIdx = -1;
     for (int c = 0; c < nc; c++) {
       const int idx = vIdx[c];
-      if (KF->octave[idx] < nPredictedLevel - 1 || KF->octave[idx] > nPredictedLevel) continue;
+      if (KF->octave[idx] < nPredictedLevel - 1) { WB(LEVEL_REJECT_LOW); continue; }
+      if (KF->octave[idx] > nPredictedLevel) { WB(LEVEL_REJECT_HIGH); continue; }
       const int dist = orc_descriptor_distance(dMP, KF->desc + (size_t)idx * 32);
-      if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
+      if (dist < bestDist) { bestDist = dist; bestIdx = idx; WB(BETTER_BEST); }
+      else if (dist == bestDist) WB(TIE_IGNORED);
     }
-    if (bestDist <= TH_HIGH) vnMatch[i] = bestIdx;
+    if (bestDist <= TH_HIGH) { vnMatch[i] = bestIdx; WB(ACCEPTED); }
+    else if (bestIdx < 0) WB(NO_CANDIDATE);
+    else WB(THRESHOLD_REJECT);
   }
   free(vIdx);
 }
@@ -1740,6 +1809,7 @@ int orc_search_by_sim3(orc_frame *KF1, orc_frame *KF2, const float *sf1, const f
                        const float *u1, const float *v1, const int32_t *level1, const uint8_t *desc1,
                        const uint8_t *valid2, const float *u2, const float *v2, const int32_t *level2,
                        const uint8_t *desc2, float th, int32_t *match12) {
+  WB_RESET();
   int *vnMatch1 = (int *)malloc(sizeof(int) * (size_t)(KF1->N > 0 ? KF1->N : 1));
   int *vnMatch2 = (int *)malloc(sizeof(int) * (size_t)(KF2->N > 0 ? KF2->N : 1));
   sim3_one_way(KF2, sf2, KF1->N, valid1, u1, v1, level1, desc1, th, vnMatch1); /* KF1 points searched in KF2 */
@@ -1748,7 +1818,8 @@ int orc_search_by_sim3(orc_frame *KF1, orc_frame *KF2, const float *sf1, const f
   for (int i1 = 0; i1 < KF1->N; i1++) {
     match12[i1] = -1;
     const int idx2 = vnMatch1[i1];
-    if (idx2 >= 0 && vnMatch2[idx2] == i1) { match12[i1] = idx2; nFound++; }
+    if (idx2 >= 0 && vnMatch2[idx2] == i1) { match12[i1] = idx2; nFound++; WB(SIM3_MUTUAL); }
+    else if (idx2 >= 0) WB(SIM3_ONE_WAY_ONLY);
   }
   free(vnMatch1);
   free(vnMatch2);

@@ -110,6 +110,27 @@ void orc_stereo_counters(int64_t *out); /* [bucket entries scanned, SAD refineme
    disparity out of range, disparity clamped, accepted (clamped ones included), removed by the median cut.  Writes
    min(n, count) entries, returns the count. */
 int orc_stereo_branch_counts(int64_t *out, int n);
+/* one counter per exit / decision of the grid window (Frame::GetFeaturesInArea, src/Frame.cc:358-415) and of the searches
+   built on it, taken during this thread's last search call (orc_features_in_area, orc_search_by_projection_*,
+   orc_search_for_initialization, orc_fuse_search, orc_search_by_sim3, orc_three_maxima; each resets them when it starts).
+   They change no result.  Order:
+     0 window right of the grid (nMinCellX >= 64), 1 left of it (nMaxCellX < 0), 2 below it (nMinCellY >= 48), 3 above it
+       (nMaxCellY < 0): the four empty returns;
+     4 nMinCellX clamped to 0, 5 nMaxCellX clamped to 63, 6 nMinCellY clamped to 0, 7 nMaxCellY clamped to 47;
+     8 octave below minLevel (or below level-1 in the loops that filter themselves), 9 octave above maxLevel,
+    10 |dx| or |dy| not < r, 11 feature returned by the window;
+    12 feature blocked / already matched, 13 stereo reject (er > radius), 14 stereo check passed, 15 stereo check skipped
+       (the frame has mvuRight and this one is not > 0);
+    16 chi-square monocular pass, 17 reject (> 5.99), 18 stereo pass, 19 reject (> 7.8);
+    20 dist < bestDist, 21 dist < bestDist2, 22 dist == bestDist on a later candidate (the first one keeps the place),
+    23 window not empty but no candidate left (best stays 256 / INT_MAX), 24 bestDist above the threshold,
+    25 ratio test failed, 26 ratio condition true but the two levels differ (map-point form: accepted), 27 accepted,
+    28 SearchForInitialization: an earlier match of the feature replaced, 29 candidate refused by vMatchedDistance <= dist,
+    30 entry of a pruned histogram bin cleared, 31 the same for an entry that was already unmatched (initialisation only),
+    32 ComputeThreeMaxima: max2 < 0.1f * max1, 33 max3 < 0.1f * max1, 34 all three kept,
+    35 SearchBySim3: pair agreed in both directions, 36 forward match without the backward one.
+   Writes min(n, count) entries, returns the count. */
+int orc_window_branch_counts(int64_t *out, int n);
 float orc_stereo_delta_r(float dist1, float dist2, float dist3); /* src/Frame.cc:648 */
 void orc_three_maxima(const int *histo_sizes, int L, int *ind1, int *ind2, int *ind3); /* :1777-1821 */
 

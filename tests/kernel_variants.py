@@ -416,11 +416,31 @@ def _pad(run):
     pad_cases(run)
 
 
+def grid_edge_cases(run: Run):
+    """The engineered grid and window cases of tests/window_edges.py (key points on half cells, on the bounds, at -0.0f;
+    windows on cell boundaries, clamped, outside the grid; |dx| == r) in the sparse, crowded-cell and n > 8192 frame forms,
+    on host-array and resident frames."""
+    import orb_slam2_annotate_amd as amd
+    import window_edges as we
+    for c in we.area_cases():
+        ref = we.run_oracle(c)[0]
+        for form in ("sparse", "crowded", "large"):
+            for resident in (False, True):
+                got = we.run_gpu(amd, we.padded_case(c, form), resident)
+                if got != ref:
+                    q = next(i for i, (g, r) in enumerate(zip(got[0], ref[0])) if g != r)
+                    _fail(f"{c.name}_{form}_{'resident' if resident else 'host_arrays'}", 0, "indices", q,
+                          f"gpu {got[0][q][:8]} vs oracle {ref[0][q][:8]}")
+                run.frames += 1
+
+
 @variant("grid_sort1", {"ORBFE_GRID_SORT": "1"})
 def _grid_sort(run):
     """launch_grid_build: k_grid_build (the bitonic sort) for every frame instead of k_grid_build_count, which otherwise
-    runs for every n <= 8192 -- all of n = 1, 1000, 2300 and the 1500-keypoint projection frame."""
+    runs for every n <= 8192 -- all of n = 1, 1000, 2300 and the 1500-keypoint projection frame, and the grid-edge frames
+    of tests/window_edges.py (21 key points; 91 with a crowded cell)."""
     grid_cases(run)
+    grid_edge_cases(run)
 
 
 def run_variant(name: str) -> int:

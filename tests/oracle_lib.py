@@ -88,6 +88,24 @@ def stereo_branch_counts() -> dict:
     return dict(zip(STEREO_BRANCHES, (int(v) for v in out)))
 
 
+WINDOW_BRANCHES = ("empty_minx_past", "empty_maxx_neg", "empty_miny_past", "empty_maxy_neg", "clamp_minx", "clamp_maxx",
+                   "clamp_miny", "clamp_maxy", "level_reject_low", "level_reject_high", "radius_reject", "area_accept",
+                   "blocked", "stereo_reject", "stereo_pass", "stereo_skipped", "chi2_mono_pass", "chi2_mono_reject",
+                   "chi2_stereo_pass", "chi2_stereo_reject", "better_best", "better_second", "tie_ignored", "no_candidate",
+                   "threshold_reject", "ratio_reject", "ratio_pass_levels_differ", "accepted", "init_overwrite",
+                   "init_refused", "hist_pruned", "hist_prune_already_unmatched", "max2_below_tenth", "max3_below_tenth",
+                   "maxima_all_kept", "sim3_mutual", "sim3_one_way_only")
+
+
+def window_branch_counts() -> dict:
+    """exit / decision of the grid window and the searches on it -> how often this thread's last search call took it
+    (orc_window_branch_counts; the order is documented in oracle/orb_oracle.h)"""
+    out = (C.c_int64 * len(WINDOW_BRANCHES))()
+    n = lib().orc_window_branch_counts(out, len(WINDOW_BRANCHES))
+    assert n == len(WINDOW_BRANCHES)
+    return dict(zip(WINDOW_BRANCHES, (int(v) for v in out)))
+
+
 def stereo_delta_r(dist1, dist2, dist3) -> np.float32:
     """the oracle's parabola fit (src/Frame.cc:648)"""
     L = lib()

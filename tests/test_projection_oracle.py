@@ -1,61 +1,11 @@
 """CPU tests of the oracle's Frame grid / projection searches (oracle/orb_oracle.c, restating
 src/Frame.cc:246-267,358-427 and src/ORBmatcher.cc:51-138,1484-1633) against a literal
 pure-Python transcription of the same loops on small inputs."""
-import math
-
 import numpy as np
 import pytest
 
 import oracle_lib as O
-
-
-def c_round(v):  # C round(): half away from zero
-    return int(math.floor(abs(v) + 0.5)) * (1 if v >= 0 else -1)
-
-
-def py_grid(x, y, bounds):
-    minx, maxx, miny, maxy = bounds
-    f32 = np.float32
-    winv = f32(64.0) / (f32(maxx) - f32(minx))
-    hinv = f32(48.0) / (f32(maxy) - f32(miny))
-    grid = [[[] for _ in range(48)] for _ in range(64)]
-    for i in range(len(x)):
-        px = c_round(float((f32(x[i]) - f32(minx)) * winv))
-        py = c_round(float((f32(y[i]) - f32(miny)) * hinv))
-        if 0 <= px < 64 and 0 <= py < 48:
-            grid[px][py].append(i)
-    return grid, winv, hinv
-
-
-def py_area(grid, winv, hinv, X, Y, octv, bounds, x, y, r, lo, hi):
-    f32 = np.float32
-    minx, _, miny, _ = [f32(b) for b in bounds]
-    x, y, r = f32(x), f32(y), f32(r)
-    out = []
-    a = max(0, int(math.floor(float((x - minx - r) * winv))))
-    if a >= 64:
-        return out
-    b = min(63, int(math.ceil(float((x - minx + r) * winv))))
-    if b < 0:
-        return out
-    c = max(0, int(math.floor(float((y - miny - r) * hinv))))
-    if c >= 48:
-        return out
-    d = min(47, int(math.ceil(float((y - miny + r) * hinv))))
-    if d < 0:
-        return out
-    chk = lo > 0 or hi >= 0
-    for ix in range(a, b + 1):
-        for iy in range(c, d + 1):
-            for i in grid[ix][iy]:
-                if chk:
-                    if octv[i] < lo:
-                        continue
-                    if hi >= 0 and octv[i] > hi:
-                        continue
-                if abs(f32(X[i]) - x) < r and abs(f32(Y[i]) - y) < r:
-                    out.append(i)
-    return out
+from window_edges import c_round, py_area, py_grid  # (moved there: one restatement of the grid)
 
 
 def random_frame(rng, n, w=640, h=480, stereo=False):
