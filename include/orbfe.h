@@ -752,6 +752,60 @@ int orbfe_fuse_search_multi(int device, int n_keyframes, const orbfe_frame_view 
                             const int32_t *level, const uint8_t *mp_desc, float th, int chi2_gate,
                             int32_t *best_idx);
 
+/* LocalMapping::CreateNewMapPoints, the per-pair loop between the two calls above (src/LocalMapping.cc:331-501): the
+ * parallax test, the 4 x 4 linear triangulation or KeyFrame::UnprojectStereo, the positive-depth test in both cameras, the
+ * two reprojection gates and the scale-consistency test, for every matched pair of ONE key frame against n_neighbours key
+ * frames as ONE kernel launch, one lane per pair.  match12 [k*n1 + i1] is what orbfe_search_for_triangulation_multi
+ * returned (feature of neighbour k or -1); cam1 / cam2[k] hold what the loop reads of the key frames besides their
+ * keypoints; scale_factors / level_sigma2 [n_levels] = mvScaleFactors / mvLevelSigma2 (shared by all key frames, as the
+ * reference's are); ratio_factor = 1.5f * mfScaleFactor (:278).
+ * Arithmetic is binary64 on inputs widened from float, in a fixed order, so equal inputs give equal bits.  The null vector of
+ * the 4 x 4 system comes from a one-sided Jacobi SVD (fixed pair order, at most 30 sweeps, a rotation skipped when
+ * |a_p.a_q| <= DBL_EPSILON sqrt(|a_p|^2 |a_q|^2)).  The reference computes in CV_32F with cv::SVD: results agree with it to
+ * float rounding and are NOT bit-identical to it; a pair within float rounding of a gate may fall on the other side.  Kept
+ * as the reference has them: the `else if` of :358-361 (key frame 2's stereo parallax only when keypoint 1 is monocular),
+ * the double literals 0.9998 / 5.991 / 7.8, key frame 1's mbf in the SECOND reprojection gate (:455), the raw keypoint
+ * position in UnprojectStereo (src/KeyFrame.cc:663-664).
+ * Outputs, [k*n1 + i1] as match12: status = ORBFE_TRI_NO_MATCH where match12 is -1, else ORBFE_TRI_CREATED or the
+ * `continue` the pair left the loop by; x3d [3 * slot ..] = the new point (binary64 result rounded once) where status is
+ * CREATED, zeros elsewhere; n_created[k] = CREATED pairs of neighbour k; winner[i1] = the smallest k whose pair for keypoint
+ * i1 is CREATED, or -1.
+ * What winner is for: the reference gives keypoint i1 its MapPoint at the FIRST neighbour that succeeds (AddMapPoint, :489)
+ * and no longer searches i1 for later neighbours (src/ORBmatcher.cc:800-803).  With the multi search every neighbour was
+ * searched with the mask of entry, so the caller replays the neighbours in order and keeps, for each i1, only the pair with
+ * k == winner[i1].  What remains different: in the reference, masking i1 could free its idx2 for another keypoint of the
+ * same neighbour; that is a deviation of orbfe_search_for_triangulation_multi, not of this call.
+ * Views with `resident` set upload nothing of the frame, host views upload x / y / octave / u_right; per call the pair
+ * records, the K + 1 cameras and the level tables go up and the four outputs come back in one copy.  n_neighbours outside
+ * [0, 64], more than 16384 keypoints, a match outside [-1, n2), a matched keypoint's octave outside [0, n_levels), n_levels
+ * outside (0, ORBFE_MAX_LEVELS], a matched stereo keypoint (u_right >= 0) without `depth` or with a depth <= 0 (the reference
+ * would dereference an empty matrix there) and NULL arrays return ORBFE_ERR_INVALID before anything is enqueued.
+ * n_neighbours = 0, or no pair at all, returns ORBFE_OK with the outputs initialised and no launch.  Runs on the calling
+ * thread's matcher stream and is complete on return. */
+typedef struct orbfe_keyframe_camera {   /* a key frame as CreateNewMapPoints reads it */
+  float Tcw[12];                         /* [Rcw | tcw], row-major 3 x 4 (GetRotation / GetTranslation) */
+  float Ow[3];                           /* GetCameraCenter() */
+  float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+  const float *depth;                    /* mvDepth [n], NULL: no stereo keypoints are unprojected (monocular) */
+  const float *x_raw, *y_raw;            /* mvKeys[i].pt for UnprojectStereo, NULL: the view's x / y (mvKeys == mvKeysUn:
+                                            every camera without distortion, src/Frame.cc:445-449) */
+} orbfe_keyframe_camera;
+
+enum { ORBFE_TRI_NO_MATCH = 0, ORBFE_TRI_CREATED = 1, ORBFE_TRI_LOW_PARALLAX, ORBFE_TRI_W_ZERO, ORBFE_TRI_BEHIND_1,
+       ORBFE_TRI_BEHIND_2, ORBFE_TRI_REPROJ_1, ORBFE_TRI_REPROJ_2, ORBFE_TRI_DIST_ZERO, ORBFE_TRI_SCALE };
+
+int orbfe_triangulate_matches_multi(int device, const orbfe_frame_view *KF1, const orbfe_keyframe_camera *cam1,
+                                    int n_neighbours, const orbfe_frame_view *const *KF2,
+                                    const orbfe_keyframe_camera *cam2 /*[K]*/, const int32_t *match12 /*[K*n1]*/,
+                                    const float *scale_factors, const float *level_sigma2, int n_levels,
+                                    float ratio_factor, float *x3d /*[K*n1*3]*/, uint8_t *status /*[K*n1]*/,
+                                    int32_t *n_created /*[K]*/, int32_t *winner /*[n1]*/);
+/* One neighbour (match12 [n1], n_created [1]); equal to the multi form with n_neighbours = 1, without winner. */
+int orbfe_triangulate_matches(int device, const orbfe_frame_view *KF1, const orbfe_keyframe_camera *cam1,
+                              const orbfe_frame_view *KF2, const orbfe_keyframe_camera *cam2, const int32_t *match12,
+                              const float *scale_factors, const float *level_sigma2, int n_levels, float ratio_factor,
+                              float *x3d, uint8_t *status, int32_t *n_created);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th,
  * const bool bMono) (src/ORBmatcher.cc:1484-1633) after the caller's pose arithmetic: last-frame
  * point i is valid when it has a non-outlier map point with invzc >= 0 projecting to (u, v) inside

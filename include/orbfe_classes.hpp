@@ -10,6 +10,7 @@
 // src/ORBmatcher_orbfe.cc (matcher) of this repo wrap these classes once more with the reference's exact
 // signatures for a build that has OpenCV and the reference's own headers; those two are not compiled here.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -228,6 +229,32 @@ class FrameArrays {
   orbfe_frame* resident_ = nullptr;
 };
 
+// What LocalMapping::CreateNewMapPoints reads of a key frame besides its keypoints (orbfe_keyframe_camera); owns the arrays.
+// Tcw: the 3 x 4 [Rcw | tcw] (GetRotation / GetTranslation), row-major; Ow = GetCameraCenter(); mvDepth empty: monocular;
+// mvKeysX / mvKeysY (the raw positions UnprojectStereo reads, src/KeyFrame.cc:663-664) empty: the frame's own mvKeysUn.
+struct KeyFrameCamera {
+  KeyFrameCamera(const float Tcw[12], const float Ow[3], float fx, float fy, float cx, float cy, float invfx, float invfy,
+                 float mb, float mbf, const std::vector<float>& mvDepth = std::vector<float>(),
+                 const std::vector<float>& mvKeysX = std::vector<float>(), const std::vector<float>& mvKeysY = std::vector<float>())
+      : depth(mvDepth), xRaw(mvKeysX), yRaw(mvKeysY) {
+    std::memcpy(c_.Tcw, Tcw, sizeof c_.Tcw);
+    std::memcpy(c_.Ow, Ow, sizeof c_.Ow);
+    c_.fx = fx; c_.fy = fy; c_.cx = cx; c_.cy = cy; c_.invfx = invfx; c_.invfy = invfy; c_.mb = mb; c_.mbf = mbf;
+  }
+  // (pointers are taken at the call: the object may have been copied or moved since it was made)
+  orbfe_keyframe_camera c() const {
+    orbfe_keyframe_camera r = c_;
+    r.depth = depth.empty() ? nullptr : depth.data();
+    r.x_raw = xRaw.empty() ? nullptr : xRaw.data();
+    r.y_raw = yRaw.empty() ? nullptr : yRaw.data();
+    return r;
+  }
+  std::vector<float> depth, xRaw, yRaw;
+
+ private:
+  orbfe_keyframe_camera c_ = {};
+};
+
 class ORBmatcher {
  public:
   static const int TH_LOW = 50;
@@ -369,6 +396,50 @@ class ORBmatcher {
     for (int k = 0; k < K; k++)
       for (int i = 0; i < n1; i++)
         if (match[(size_t)k * n1 + i] >= 0) vMatchedPairs[k].push_back(std::make_pair((size_t)i, (size_t)match[(size_t)k * n1 + i]));
+  }
+
+  // The per-pair loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:331-501) for every pair
+  // SearchForTriangulationMulti matched, in ONE call (orbfe_triangulate_matches_multi): match12[k * n1 + i1] = keypoint of
+  // neighbour k or -1; x3d [3 per slot], status (ORBFE_TRI_*) and winner as include/orbfe.h describes them; nCreated[k].
+  // Replay the neighbours in order and keep, for keypoint i1, only the pair with status CREATED and winner[i1] == k.
+  // Frames may be resident or not.
+  void TriangulateMatchesMulti(const FrameArrays& KF1, const KeyFrameCamera& cam1, const std::vector<const FrameArrays*>& neighbours,
+                               const std::vector<const KeyFrameCamera*>& cams, const std::vector<int32_t>& match12,
+                               const std::vector<float>& mvScaleFactors, const std::vector<float>& mvLevelSigma2, float ratioFactor,
+                               std::vector<float>& x3d, std::vector<uint8_t>& status, std::vector<int32_t>& nCreated,
+                               std::vector<int32_t>& winner) {
+    const int K = (int)neighbours.size(), n1 = KF1.N();
+    std::vector<const orbfe_frame_view*> views(K > 0 ? K : 1, nullptr);
+    std::vector<orbfe_keyframe_camera> cc(K > 0 ? K : 1);
+    for (int k = 0; k < K; k++) { views[k] = &neighbours[k]->c; cc[k] = cams[k]->c(); }
+    const orbfe_keyframe_camera c1 = cam1.c();
+    const size_t slots = (size_t)K * n1;
+    x3d.assign(slots * 3, 0.0f); status.assign(slots, 0); nCreated.assign(K, 0); winner.assign(n1, -1);
+    std::vector<float> xb(slots * 3 + 1);
+    std::vector<uint8_t> sb(slots + 1);
+    std::vector<int32_t> nb((size_t)K + 1), wb((size_t)n1 + 1);
+    check(orbfe_triangulate_matches_multi(device_, &KF1.c, &c1, K, views.data(), cc.data(), match12.data(), mvScaleFactors.data(),
+                                          mvLevelSigma2.data(), (int)mvScaleFactors.size(), ratioFactor, xb.data(), sb.data(),
+                                          nb.data(), wb.data()),
+          "TriangulateMatchesMulti");
+    std::copy(xb.begin(), xb.begin() + slots * 3, x3d.begin()); std::copy(sb.begin(), sb.begin() + slots, status.begin());
+    std::copy(nb.begin(), nb.begin() + K, nCreated.begin()); std::copy(wb.begin(), wb.begin() + n1, winner.begin());
+  }
+  // one neighbour: match12 [n1]; returns the number of points created
+  int TriangulateMatches(const FrameArrays& KF1, const KeyFrameCamera& cam1, const FrameArrays& KF2, const KeyFrameCamera& cam2,
+                         const std::vector<int32_t>& match12, const std::vector<float>& mvScaleFactors,
+                         const std::vector<float>& mvLevelSigma2, float ratioFactor, std::vector<float>& x3d,
+                         std::vector<uint8_t>& status) {
+    const int n1 = KF1.N();
+    const orbfe_keyframe_camera c1 = cam1.c(), c2 = cam2.c();
+    std::vector<float> xb((size_t)n1 * 3 + 1);
+    std::vector<uint8_t> sb((size_t)n1 + 1);
+    int32_t created = 0;
+    check(orbfe_triangulate_matches(device_, &KF1.c, &c1, &KF2.c, &c2, match12.data(), mvScaleFactors.data(), mvLevelSigma2.data(),
+                                    (int)mvScaleFactors.size(), ratioFactor, xb.data(), sb.data(), &created),
+          "TriangulateMatches");
+    x3d.assign(xb.begin(), xb.begin() + (size_t)n1 * 3); status.assign(sb.begin(), sb.begin() + n1);
+    return created;
   }
 
   // The loop of Tracking::Relocalization (src/Tracking.cc:1478-1498) in ONE call: SearchByBoW(pKF_k, mCurrentFrame,

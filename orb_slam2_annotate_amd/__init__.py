@@ -8,6 +8,7 @@ from .matcher import ComputeStereoMatches, FeatureVector, FrameView, ORBmatcher,
 from .vocabulary import ORBVocabulary, synthetic_vocabulary_arrays, write_synthetic_vocabulary, write_vocabulary_text  # noqa: F401
 from .map_points import MapPoints, camera_pose  # noqa: F401
 from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401
+from .local_mapping import KeyFrameCamera, triangulate_matches, triangulate_matches_multi  # noqa: F401
 from .keyframe_database import KeyFrameDatabase, bow_arrays, group_candidates  # noqa: F401
 from .ingest import (ComputeDistinctiveDescriptors, ComputeImageBounds, ComputeStereoFromRGBD,  # noqa: F401
                      Rectifier, UndistortKeyPoints, cvtColorToGray, initUndistortRectifyMap, undistortPoints)  # noqa: F401

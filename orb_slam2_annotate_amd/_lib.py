@@ -53,6 +53,14 @@ class PoseOptStatsC(C.Structure):
                 ("lam", C.c_double * 4), ("chi2", C.c_double * 4)]
 
 
+class KeyFrameCameraC(C.Structure):
+    """orbfe_keyframe_camera: what LocalMapping::CreateNewMapPoints reads of a key frame besides its keypoints."""
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("invfx", C.c_float), ("invfy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float),
+                ("depth", C.c_void_p), ("x_raw", C.c_void_p), ("y_raw", C.c_void_p)]
+
+
 class FeatVecC(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_ids", C.c_void_p), ("offsets", C.c_void_p),
                 ("indices", C.c_void_p)]
@@ -86,6 +94,7 @@ EXPORTS = [
     "orbfe_mappoints_create", "orbfe_mappoints_destroy", "orbfe_mappoints_capacity", "orbfe_mappoints_update",
     "orbfe_project_in_frustum", "orbfe_search_local_points",
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch", "orbfe_pose_optimization_mappoints",
+    "orbfe_triangulate_matches", "orbfe_triangulate_matches_multi",
 ]
 
 _lib = None
@@ -256,6 +265,9 @@ def load():
     L.orbfe_pose_optimization.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_pose_optimization_batch.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_pose_optimization_mappoints.argtypes = [vp, ci, vp, fwp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    kcp = C.POINTER(KeyFrameCameraC)
+    L.orbfe_triangulate_matches_multi.argtypes = [ci, fwp, kcp, ci, vp, kcp, vp, vp, vp, ci, cf, vp, vp, vp, vp]
+    L.orbfe_triangulate_matches.argtypes = [ci, fwp, kcp, fwp, kcp, vp, vp, vp, ci, cf, vp, vp, vp]
     _lib = L
     return L
 
