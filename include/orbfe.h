@@ -806,6 +806,58 @@ int orbfe_triangulate_matches(int device, const orbfe_frame_view *KF1, const orb
                               const float *scale_factors, const float *level_sigma2, int n_levels, float ratio_factor,
                               float *x3d, uint8_t *status, int32_t *n_created);
 
+/* Sim3Solver (src/Sim3Solver.cc), the RANSAC between SearchByBoW and SearchBySim3 in LoopClosing::ComputeSim3
+ * (src/LoopClosing.cc:286-404): EVERY hypothesis of EVERY candidate's solver in ONE kernel launch, one wave per hypothesis.
+ * A hypothesis is Sim3Solver::ComputeSim3 (:254-370, Horn's closed form) on three matched pairs followed by CheckInliers
+ * (:374-398) over all pairs of its candidate.  Hypotheses are independent; the order-dependent part of iterate() (:150-220:
+ * best on >=, return on > minInliers) is a scan over n_inliers that the caller replays on the host (C++
+ * orbfe_cpp::Sim3Solver, Python Sim3Solver).
+ * Candidate k owns pairs [pair_off[k], pair_off[k+1]) of x3dc1 / x3dc2 (mvX3Dc1 / mvX3Dc2, :95-98: the matched MapPoints in
+ * the cameras of key frames 1 and 2) and of max_err1 / max_err2 (mvnMaxError1 / 2 = 9.210 * sigma2, :87-88), the cameras
+ * cam1[k] / cam2[k] = fx fy cx cy of mK1 / mK2, and hypotheses [hyp_off[k], hyp_off[k+1]); triples[3 h ..] are the three
+ * pairs of hypothesis h as indices LOCAL to its candidate's pairs (what :176-187 draws).  fix_scale = mbFixScale.
+ * Arithmetic is binary64 on inputs widened from float, in a fixed order, so equal inputs give equal bytes.  The eigenvector
+ * of N comes from a cyclic Jacobi iteration (fixed pair order, at most 30 sweeps, a rotation skipped when
+ * |a_pq| <= DBL_EPSILON sqrt(|a_pp a_qq|)), the rotation from it the reference's way (angle-axis, cv::Rodrigues' formula).
+ * The reference computes in CV_32F with cv::eigen / cv::Rodrigues: results agree with it to float rounding and are NOT
+ * bit-identical to it; a pair within float rounding of its max_err may fall on the other side.  Kept as the reference has
+ * them: no depth test in Project (:436), strict < in :390, and the division by |vec| = 0 of :310 for two identical triples,
+ * after which everything is NaN and no pair is an inlier.
+ * Outputs per hypothesis h: n_inliers[h]; status[h] = ORBFE_SIM3_OK, or ORBFE_SIM3_NONFINITE when any of R, t, s is not finite
+ * (n_inliers 0 and all mask words 0 then; R, t, s stored as they came out); sim3[13 h ..] = R12 row-major, t12, s12 (binary64
+ * results rounded once); its ceil(n_k / 32) mask words at mask_words[word_off[k] + (h - hyp_off[k]) * ceil(n_k / 32)], pair i
+ * of the candidate at bit i & 31 of word i >> 5.  word_off [K + 1] is written by the call; mask_words must hold
+ * sum_k H_k * ceil(n_k / 32) words.
+ * Returns ORBFE_ERR_INVALID before anything is enqueued, leaving the thread usable, for: NULL arrays, offsets that do not
+ * start at 0, decrease, or do not end at n_pairs / n_hypotheses, a triple index outside [0, n_k), a triple that repeats an
+ * index, a camera entry that is not finite, a candidate with n_k < 3 that has hypotheses, n_candidates outside [0, 4096].
+ * A candidate without hypotheses is legal; a call without any returns ORBFE_OK with word_off written and no launch.  Runs on
+ * the calling thread's matcher stream and is complete on return. */
+enum { ORBFE_SIM3_OK = 0, ORBFE_SIM3_NONFINITE = 1 };
+
+int orbfe_sim3_ransac_multi(int device, int n_candidates, int n_pairs, int n_hypotheses, const int32_t *pair_off /*[K+1]*/,
+                            const float *x3dc1 /*[N*3]*/, const float *x3dc2 /*[N*3]*/, const float *max_err1 /*[N]*/,
+                            const float *max_err2 /*[N]*/, const float *cam1 /*[K*4]*/, const float *cam2 /*[K*4]*/,
+                            int fix_scale, const int32_t *hyp_off /*[K+1]*/, const int32_t *triples /*[H*3]*/,
+                            int32_t *n_inliers /*[H]*/, uint8_t *status /*[H]*/, float *sim3 /*[H*13]*/,
+                            uint32_t *mask_words, int32_t *word_off /*[K+1]*/);
+/* One candidate; equal to the multi form with n_candidates = 1.  mask_words [H * ceil(n / 32)]. */
+int orbfe_sim3_ransac(int device, int n_pairs, const float *x3dc1, const float *x3dc2, const float *max_err1,
+                      const float *max_err2, const float *cam1, const float *cam2, int fix_scale, int n_hypotheses,
+                      const int32_t *triples, int32_t *n_inliers, uint8_t *status, float *sim3, uint32_t *mask_words);
+/* The selection without replacement of Sim3Solver::iterate (:173-187), no device involved: draws[3 h + i] is the value
+ * RandomInt(0, vAvailableIndices.size() - 1) returned for pick i of hypothesis h, in [0, n - 1 - i] -- an index INTO the list
+ * of still available pairs, which starts as 0 .. n-1 for every hypothesis and loses the pair taken by swap-with-back and pop
+ * -> triples[3 h + i] the pair taken.  A caller who feeds the reference's DUtils::Random::RandomInt stream gets the
+ * reference's triples; the library does not restate rand().  n < 3 with hypotheses, NULL arrays or a draw outside its range
+ * return ORBFE_ERR_INVALID. */
+int orbfe_sim3_triples_from_draws(int n, int n_hypotheses, const int32_t *draws /*[H*3]*/, int32_t *triples /*[H*3]*/);
+/* What Sim3Solver::SetRansacParameters (:118-142) leaves in mRansacMaxIts for n correspondences: the reference's float
+ * epsilon = minInliers / n, ceil(log(1 - prob) / log(1 - pow(epsilon, 3))), max(1, min(., max_its)), 1 when
+ * min_inliers == n.  n < min_inliers returns 1 without the formula (the reference's expression is NaN there and iterate()
+ * never reads the result). */
+int orbfe_sim3_max_iterations(int n, double prob, int min_inliers, int max_its);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th,
  * const bool bMono) (src/ORBmatcher.cc:1484-1633) after the caller's pose arithmetic: last-frame
  * point i is valid when it has a non-outlier map point with invzc >= 0 projecting to (u, v) inside

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "orbfe.h"
+#include "orbfe_sim3_replay.hpp"
 
 namespace orbfe_cpp {
 
@@ -718,6 +719,145 @@ class Optimizer {
           "PoseOptimization");
     for (int k = 0; k < 16; k++) Tcw[k] = out[k];
     return nInliers;
+  }
+};
+
+// Sim3Solver (src/Sim3Solver.cc) without the map graph: the caller walks vpMatched12 as the reference's constructor does
+// (:62-103) and hands in, for the n pairs it keeps, mvnIndices1 (:92), mvX3Dc1 / mvX3Dc2 (3 floats per pair, :95-98), the
+// sigma2 of the two keypoints' levels (:84-85), fx fy cx cy of mK1 / mK2, N1 = vpMatched12.size() and bFixScale.  The class
+// computes maxErr = (float)(9.210 * sigma2) (:87-88) and calls SetRansacParameters() with the reference's defaults (:111).
+// Sim3Solver::evaluate_all evaluates every solver's mRansacMaxIts hypotheses in ONE orbfe_sim3_ransac_multi call; iterate()
+// then behaves as the reference's (:150-220) over the results (Sim3Replay, orbfe_sim3_replay.hpp).  The caller's round-robin
+// loop (src/LoopClosing.cc:342-404) stays as it is.
+class Sim3Solver {
+ public:
+  Sim3Solver(const std::vector<int32_t>& indices1, const std::vector<float>& x3dc1, const std::vector<float>& x3dc2,
+             const std::vector<float>& sigma2_1, const std::vector<float>& sigma2_2, const float cam1[4], const float cam2[4],
+             int N1, bool bFixScale)
+      : indices1_(indices1), x1_(x3dc1), x2_(x3dc2), fixScale_(bFixScale) {
+    const size_t n = indices1.size();
+    if (x3dc1.size() != 3 * n || x3dc2.size() != 3 * n || sigma2_1.size() != n || sigma2_2.size() != n)
+      throw std::invalid_argument("Sim3Solver: one entry per pair in every array");
+    for (int32_t i : indices1)
+      if (i < 0 || i >= N1) throw std::invalid_argument("Sim3Solver: indices1 outside [0, N1)");
+    e1_.resize(n); e2_.resize(n);
+    for (size_t i = 0; i < n; i++) { e1_[i] = (float)(9.210 * sigma2_1[i]); e2_[i] = (float)(9.210 * sigma2_2[i]); }  // :87-88
+    std::memcpy(cam1_, cam1, sizeof cam1_); std::memcpy(cam2_, cam2, sizeof cam2_);
+    st_.N = (int)n; st_.mN1 = N1;
+    SetRansacParameters();
+  }
+  // :118-142; what an earlier evaluate_all left is dropped (the number of hypotheses may have changed)
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    st_.mRansacMinInliers = minInliers;
+    st_.mRansacMaxIts = orbfe_sim3_max_iterations(st_.N, probability, minInliers, maxIterations);
+    st_.mnIterations = 0;
+    evaluated_ = false;
+  }
+  int N() const { return st_.N; }
+  int maxIterations() const { return st_.mRansacMaxIts; }
+  // what evaluate_all evaluates for this solver: nothing when iterate() would return at :156
+  int nHypotheses() const { return st_.N < st_.mRansacMinInliers ? 0 : st_.mRansacMaxIts; }
+
+  // triples[k]: 3 * nHypotheses() pair indices of solver k (e.g. orbfe_sim3_triples_from_draws of the reference's stream)
+  static void evaluate_all(const std::vector<Sim3Solver*>& solvers, const std::vector<std::vector<int32_t>>& triples, int device = 0) {
+    const int K = (int)solvers.size();
+    if ((int)triples.size() != K) throw std::invalid_argument("Sim3Solver::evaluate_all: one array of triples per solver");
+    std::vector<int32_t> pairOff(1, 0), hypOff(1, 0), tr, wordOff((size_t)K + 1, 0);
+    std::vector<float> x1, x2, e1, e2, c1, c2;
+    size_t W = 0;
+    for (int k = 0; k < K; k++) {
+      const Sim3Solver& s = *solvers[k];
+      if (s.fixScale_ != solvers[0]->fixScale_) throw std::invalid_argument("Sim3Solver::evaluate_all: the solvers of one call share bFixScale");
+      if (triples[k].size() != 3 * (size_t)s.nHypotheses()) throw std::invalid_argument("Sim3Solver::evaluate_all: 3 * nHypotheses() indices per solver");
+      pairOff.push_back(pairOff.back() + s.st_.N);
+      hypOff.push_back(hypOff.back() + s.nHypotheses());
+      x1.insert(x1.end(), s.x1_.begin(), s.x1_.end()); x2.insert(x2.end(), s.x2_.begin(), s.x2_.end());
+      e1.insert(e1.end(), s.e1_.begin(), s.e1_.end()); e2.insert(e2.end(), s.e2_.begin(), s.e2_.end());
+      c1.insert(c1.end(), s.cam1_, s.cam1_ + 4); c2.insert(c2.end(), s.cam2_, s.cam2_ + 4);
+      tr.insert(tr.end(), triples[k].begin(), triples[k].end());
+      W += (size_t)s.nHypotheses() * (size_t)((s.st_.N + 31) / 32);
+    }
+    const int H = hypOff.back();
+    std::vector<int32_t> nInl((size_t)H + 1);
+    std::vector<uint8_t> status((size_t)H + 1);
+    std::vector<float> sim3((size_t)H * 13 + 1);
+    std::vector<uint32_t> words(W + 1);
+    x1.push_back(0.0f); x2.push_back(0.0f); e1.push_back(0.0f); e2.push_back(0.0f); c1.push_back(0.0f); c2.push_back(0.0f); tr.push_back(0);
+    check(orbfe_sim3_ransac_multi(device, K, pairOff.back(), H, pairOff.data(), x1.data(), x2.data(), e1.data(), e2.data(), c1.data(),
+                                  c2.data(), K > 0 && solvers[0]->fixScale_ ? 1 : 0, hypOff.data(), tr.data(), nInl.data(),
+                                  status.data(), sim3.data(), words.data(), wordOff.data()),
+          "Sim3Solver::evaluate_all");
+    for (int k = 0; k < K; k++) {
+      Sim3Solver& s = *solvers[k];
+      const size_t h0 = (size_t)hypOff[k], h1 = (size_t)hypOff[k + 1];
+      s.nInliers_.assign(nInl.begin() + h0, nInl.begin() + h1);
+      s.status_.assign(status.begin() + h0, status.begin() + h1);
+      s.sim3_.assign(sim3.begin() + 13 * h0, sim3.begin() + 13 * h1);
+      s.words_.assign(words.begin() + wordOff[k], words.begin() + wordOff[k + 1]);
+      s.evaluated_ = true;
+    }
+  }
+  // the triples drawn by the documented generator sim3_seeded_draw through orbfe_sim3_triples_from_draws
+  static void evaluate_all(const std::vector<Sim3Solver*>& solvers, uint64_t seed, int device = 0) {
+    std::vector<std::vector<int32_t>> triples(solvers.size());
+    uint64_t c = 0;
+    for (size_t k = 0; k < solvers.size(); k++) {
+      const int H = solvers[k]->nHypotheses(), n = solvers[k]->st_.N;
+      std::vector<int32_t> draws(3 * (size_t)H);
+      for (size_t j = 0; j < draws.size(); j++, c++) draws[j] = sim3_seeded_draw(seed, c, n - (int)(j % 3));
+      triples[k].resize(draws.size());
+      if (H) check(orbfe_sim3_triples_from_draws(n, H, draws.data(), triples[k].data()), "Sim3Solver::evaluate_all");
+    }
+    evaluate_all(solvers, triples, device);
+  }
+
+  // :150-220 -> true and T12 (row-major 4 x 4) when a hypothesis with more than minInliers inliers came up
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float T12[16]) {
+    if (!evaluated_) throw std::logic_error("Sim3Solver::iterate: call Sim3Solver::evaluate_all first");
+    const Sim3Replay::Step r = st_.iterate(nIterations, nInliers_.data(), words_.data(), indices1_.data(), vbInliers);
+    bNoMore = r.bNoMore;
+    nInliers = r.nInliers;
+    if (r.best >= 0) {  // :197-202: a copy, so that the estimate outlives the next SetRansacParameters / evaluate_all
+      std::memcpy(best_, &sim3_[13 * (size_t)r.best], sizeof best_);
+      hasBest_ = true;
+    }
+    if (r.accepted < 0) return false;
+    const float* v = &sim3_[13 * (size_t)r.accepted];
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) T12[4 * i + j] = v[12] * v[3 * i + j];  // :356
+      T12[4 * i + 3] = v[9 + i];
+    }
+    T12[12] = T12[13] = T12[14] = 0.0f; T12[15] = 1.0f;
+    return true;
+  }
+  bool find(std::vector<bool>& vbInliers12, int& nInliers, float T12[16]) {  // :222-226
+    bool bFlag;
+    return iterate(st_.mRansacMaxIts, bFlag, vbInliers12, nInliers, T12);
+  }
+  // of the best hypothesis so far (:401-414), which SetRansacParameters and evaluate_all leave alone as the reference leaves
+  // mBestRotation; std::logic_error before any hypothesis was taken (the reference returns empty matrices there)
+  void GetEstimatedRotation(float R[9]) const { std::memcpy(R, best(), 9 * sizeof(float)); }
+  void GetEstimatedTranslation(float t[3]) const { std::memcpy(t, best() + 9, 3 * sizeof(float)); }
+  float GetEstimatedScale() const { return best()[12]; }
+  int iterations() const { return st_.mnIterations; }
+  int bestInliers() const { return st_.mnBestInliers; }
+
+ private:
+  std::vector<int32_t> indices1_;
+  std::vector<float> x1_, x2_, e1_, e2_;
+  float cam1_[4], cam2_[4];
+  bool fixScale_;
+  Sim3Replay st_;
+  bool evaluated_ = false;
+  std::vector<int32_t> nInliers_;
+  std::vector<uint8_t> status_;
+  std::vector<float> sim3_;
+  std::vector<uint32_t> words_;
+  float best_[13] = {};
+  bool hasBest_ = false;
+  const float* best() const {
+    if (!hasBest_) throw std::logic_error("Sim3Solver: no hypothesis has been taken yet");
+    return best_;
   }
 };
 

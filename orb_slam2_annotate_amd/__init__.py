@@ -9,6 +9,8 @@ from .vocabulary import ORBVocabulary, synthetic_vocabulary_arrays, write_synthe
 from .map_points import MapPoints, camera_pose  # noqa: F401
 from .optimizer import pose_optimization, pose_optimization_batch  # noqa: F401
 from .local_mapping import KeyFrameCamera, triangulate_matches, triangulate_matches_multi  # noqa: F401
+from .loop_closing import (Sim3Solver, sim3_max_iterations, sim3_ransac, sim3_ransac_multi,  # noqa: F401
+                           sim3_triples_from_draws)
 from .keyframe_database import KeyFrameDatabase, bow_arrays, group_candidates  # noqa: F401
 from .ingest import (ComputeDistinctiveDescriptors, ComputeImageBounds, ComputeStereoFromRGBD,  # noqa: F401
                      Rectifier, UndistortKeyPoints, cvtColorToGray, initUndistortRectifyMap, undistortPoints)  # noqa: F401

@@ -95,6 +95,7 @@ EXPORTS = [
     "orbfe_project_in_frustum", "orbfe_search_local_points",
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch", "orbfe_pose_optimization_mappoints",
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_multi",
+    "orbfe_sim3_ransac", "orbfe_sim3_ransac_multi", "orbfe_sim3_triples_from_draws", "orbfe_sim3_max_iterations",
 ]
 
 _lib = None
@@ -268,6 +269,10 @@ def load():
     kcp = C.POINTER(KeyFrameCameraC)
     L.orbfe_triangulate_matches_multi.argtypes = [ci, fwp, kcp, ci, vp, kcp, vp, vp, vp, ci, cf, vp, vp, vp, vp]
     L.orbfe_triangulate_matches.argtypes = [ci, fwp, kcp, fwp, kcp, vp, vp, vp, ci, cf, vp, vp, vp]
+    L.orbfe_sim3_ransac_multi.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_sim3_ransac.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+    L.orbfe_sim3_triples_from_draws.argtypes = [ci, ci, vp, vp]
+    L.orbfe_sim3_max_iterations.argtypes = [ci, C.c_double, ci, ci]
     _lib = L
     return L
 
