@@ -3,10 +3,9 @@
 // arena + stream per device (the reference constructs stack-local ORBmatcher objects on three threads concurrently,
 // src/LocalMapping.cc:261, src/LoopClosing.cc:294), so the entry points built on it are stateless and re-entrant.
 //
-// Three ways in, each of which begins the arena anew (what an earlier call of the thread left in it is gone):
-//   arena_stage(device, &ar, stage)    a call that carves: up() / up_fill() / carve() inside `stage`, then flush(), the
-//                                      launches, down_range(), a synchronisation, mirror_of()
-//   arena_scratch(device, bytes, &ar)  one block [0, bytes) of ar->base with ar->hmirror grown to match, laid out by the caller
+// Two ways in, each of which begins the arena anew (what an earlier call of the thread left in it is gone):
+//   arena_stage(device, &ar, stage)    a call that carves: up() / up_pack() / up_fill() / carve() inside `stage`, then
+//                                      flush(), the launches, down_range(), a synchronisation, mirror_of()
 //   arena_stream(device, &ar)          ar->stream alone
 // State and the non-templates: arena.hip.
 #pragma once
@@ -35,7 +34,7 @@ struct Arena {
   // dirty range in ONE host-to-device copy before the first kernel of the call
   PinBuf<uint8_t> hmirror;
   size_t dirtyLo = 0, dirtyHi = 0;
-  bool sizing = false;  // arena_stage()'s first pass: carve() only advances `used`, up() / up_fill() copy nothing
+  bool sizing = false;  // arena_stage()'s first pass: carve() only advances `used`, the up*() calls write nothing
   ~Arena() {  // (thread exit; the buffers free themselves behind this, on the device set here)
     if (device >= 0) {
       (void)hipSetDevice(device);
@@ -44,7 +43,7 @@ struct Arena {
   }
 };
 
-// begins the arena with room for `bytes`: behind arena_stage / arena_scratch / arena_stream, which are what callers use
+// begins the arena with room for `bytes`: behind arena_stage / arena_stream, which are what callers use
 hipError_t arena_begin(int device, size_t bytes, Arena** out);
 
 template <typename T>
@@ -57,41 +56,46 @@ T* carve(Arena* a, size_t n) {
 // the pinned mirror covers arena offsets [0, upto); what earlier up() calls of this call staged is kept
 hipError_t grow_mirror(Arena* a, size_t upto);
 inline void mark_dirty(Arena* a, size_t off, size_t bytes) {
-  if (a->dirtyHi == a->dirtyLo) { a->dirtyLo = off; a->dirtyHi = off + bytes; }
-  else {
-    if (off < a->dirtyLo) a->dirtyLo = off;
-    if (off + bytes > a->dirtyHi) a->dirtyHi = off + bytes;
-  }
+  const bool none = a->dirtyHi == a->dirtyLo;
+  if (none || off < a->dirtyLo) a->dirtyLo = off;
+  if (none || off + bytes > a->dirtyHi) a->dirtyHi = off + bytes;
+}
+// the one body of staging: fill(h) writes the `bytes` of the array carved at `d` at their place h in the mirror.  Not in the
+// sizing pass and not for an empty array; h is good inside `fill` only, the next grow_mirror() may move the mirror
+template <typename Fill>
+hipError_t stage_bytes(Arena* a, const void* d, size_t bytes, Fill&& fill) {
+  if (bytes == 0 || a->sizing) return hipSuccess;
+  const size_t off = (size_t)(static_cast<const uint8_t*>(d) - a->base);
+  TRY(grow_mirror(a, off + bytes));
+  fill(a->hmirror + off);
+  mark_dirty(a, off, bytes);
+  return hipSuccess;
 }
 // host data for an array carved earlier in this call: for blocks of device addresses, which are known only once everything
 // is carved but must lie among the uploads
 template <typename T>
 hipError_t put(Arena* a, T* d, const T* h, size_t n) {
-  if (n == 0 || a->sizing) return hipSuccess;
-  const size_t off = (size_t)(reinterpret_cast<uint8_t*>(d) - a->base), bytes = n * sizeof(T);
-  hipError_t e = grow_mirror(a, off + bytes);
-  if (e != hipSuccess) return e;
-  std::memcpy(a->hmirror + off, h, bytes);
-  mark_dirty(a, off, bytes);
-  return hipSuccess;
+  return stage_bytes(a, d, n * sizeof(T), [&](uint8_t* m) { std::memcpy(m, h, n * sizeof(T)); });
 }
 template <typename T>
 hipError_t up(Arena* a, T** d, const T* h, size_t n) {
   *d = carve<T>(a, n ? n : 1);
   return put(a, *d, h, n);
 }
+// a device array of n elements that the call packs in place: fill(T* h) writes the n elements in the mirror, which saves
+// the host copy a finished array handed to up() would cost
+template <typename T, typename Fill>
+hipError_t up_pack(Arena* a, T** d, size_t n, Fill&& fill) {
+  *d = carve<T>(a, n ? n : 1);
+  return stage_bytes(a, *d, n * sizeof(T), [&](uint8_t* m) { fill(reinterpret_cast<T*>(m)); });
+}
 // a device array of n elements whose bytes all start as `byteValue`: filled in the mirror, so it travels with the one
 // host-to-device copy of the call instead of costing a fill kernel of its own
 template <typename T>
 hipError_t up_fill(Arena* a, T** d, size_t n, int byteValue) {
+  const size_t bytes = (n ? n : 1) * sizeof(T);
   *d = carve<T>(a, n ? n : 1);
-  if (a->sizing) return hipSuccess;
-  const size_t off = (size_t)(reinterpret_cast<uint8_t*>(*d) - a->base), bytes = (n ? n : 1) * sizeof(T);
-  hipError_t e = grow_mirror(a, off + bytes);
-  if (e != hipSuccess) return e;
-  std::memset(a->hmirror + off, byteValue, bytes);
-  mark_dirty(a, off, bytes);
-  return hipSuccess;
+  return stage_bytes(a, *d, bytes, [&](uint8_t* m) { std::memset(m, byteValue, bytes); });
 }
 // results: ONE device-to-host copy of the arena range [first, last) into the pinned mirror (same offsets), to be read
 // through mirror_of() after the stream is synchronised -- instead of one pageable copy per output array
@@ -100,12 +104,12 @@ template <typename T>
 const T* mirror_of(Arena* a, const T* d) {
   return reinterpret_cast<const T*>(a->hmirror + (reinterpret_cast<const uint8_t*>(d) - a->base));
 }
-// one H2D copy for everything up() staged since arena_begin(); call before the first kernel launch.  Whole 256-byte lines
+// one H2D copy for everything staged since arena_begin(); call before the first kernel launch.  Whole 256-byte lines
 // travel (a copy that ends inside a line costs a microsecond more): carve() starts every array on a line and arena_begin()
 // reserves whole lines, so the tail of the last line belongs to no array
 hipError_t flush(Arena* a);
 
-// Stages a call: runs `stage` -- the up() / up_fill() / carve() calls of the call -- twice, first on a sizing arena that
+// Stages a call: runs `stage` -- the up*() / carve() calls of the call -- twice, first on a sizing arena that
 // only counts, then on the calling thread's arena of `device`, begun with exactly what the first pass carved: the size
 // cannot drift from the carving.  `stage` must carve the same sizes in both passes: one that does not fails the call
 // with hipErrorInvalidValue before anything is enqueued.
@@ -119,10 +123,6 @@ hipError_t arena_stage(int device, Arena** out, F&& stage) {
   if (e == hipSuccess && (*out)->used != sizing.used) e = hipErrorInvalidValue;
   return e;
 }
-// one block [0, bytes) of the calling thread's arena on `device`, (*out)->base, and as much of its pinned mirror,
-// (*out)->hmirror: the caller fills the mirror, copies, launches and copies back on (*out)->stream, and synchronises before
-// it returns
-hipError_t arena_scratch(int device, size_t bytes, Arena** out);
 // the calling thread's stream on `device`, (*out)->stream, for a call that carves nothing
 hipError_t arena_stream(int device, Arena** out);
 

@@ -41,10 +41,6 @@ hipError_t arena_begin(int device, size_t bytes, Arena** out) {
   return hipSuccess;
 }
 
-hipError_t arena_scratch(int device, size_t bytes, Arena** out) {
-  TRY(arena_begin(device, bytes, out));
-  return grow_mirror(*out, bytes);
-}
 hipError_t arena_stream(int device, Arena** out) { return arena_begin(device, 0, out); }
 
 hipError_t grow_mirror(Arena* a, size_t upto) {

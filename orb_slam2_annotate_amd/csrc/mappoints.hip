@@ -17,8 +17,9 @@ using namespace orbfe;
 
 // ---------------------------------------------------------------------------------------------
 // Device-resident map points (include/orbfe.h: orbfe_mappoints).  One slab from the pool holds the table; an update is one
-// staged copy and one scatter launch on the calling thread's stream, complete on return.  The argument checks and the
-// layouts are mappoints_host.h (no device needed: tests/cpp/mappoints_host_san.cpp runs them under the sanitizers).
+// staged copy (arena.h: arena_stage) and one scatter launch on the calling thread's stream, complete on return.  The
+// argument checks, the slab layout and the interleaving of an update's records are mappoints_host.h (no device needed:
+// tests/cpp/mappoints_host_san.cpp runs them under the sanitizers).
 // ---------------------------------------------------------------------------------------------
 struct orbfe_mappoints {
   int device = 0, capacity = 0;
@@ -110,15 +111,21 @@ extern "C" int orbfe_mappoints_update(orbfe_mappoints* mp, int n, const int32_t*
     return fail(ORBFE_ERR_INVALID, std::string("mappoints_update: ") + e);
   if (n == 0) return ORBFE_OK;
   std::lock_guard<std::mutex> lk(mp->m);
-  const MapPointsStage S = mappoints_stage_layout(n, desc != nullptr);
   Arena* ar;
-  HIPCHK(arena_scratch(mp->device, S.total, &ar));
+  int32_t* dslot;
+  float4* drec;
+  uint8_t *dflags, *ddesc = nullptr;
+  auto stage = [&](Arena* a) -> hipError_t {  // in the order the scatter kernel reads: slots | records | flags | descriptors
+    TRY(up(a, &dslot, slot, (size_t)n));
+    TRY(up_pack(a, &drec, 2 * (size_t)n, [&](float4* h) { mappoints_pack_records(&h->x, n, pos, normal, min_dist, max_dist); }));
+    TRY(up(a, &dflags, flags, (size_t)n));
+    if (desc) TRY(up(a, &ddesc, desc, 32 * (size_t)n));
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(mp->device, &ar, stage));
   HIPCHK(mappoints_ready(mp, ar));
-  mappoints_pack(ar->hmirror, S, n, slot, pos, normal, min_dist, max_dist, desc, flags);
-  uint8_t* din = ar->base;
-  HIPCHK(hipMemcpyAsync(din, ar->hmirror, S.total, hipMemcpyHostToDevice, ar->stream));
-  launch_mappoints_scatter(ar->stream, mp->d, n, reinterpret_cast<const int32_t*>(din + S.oSlot), reinterpret_cast<const float4*>(din + S.oRec),
-                           din + S.oFlags, desc ? din + S.oDesc : nullptr);
+  HIPCHK(flush(ar));
+  launch_mappoints_scatter(ar->stream, mp->d, n, dslot, drec, dflags, ddesc);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ar->stream));
   return ORBFE_OK;

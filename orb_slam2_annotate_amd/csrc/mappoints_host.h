@@ -1,11 +1,9 @@
 // mappoints_host.h -- the host side of the device map-point table (mappoints.hip: orbfe_mappoints_*) that needs no device:
-// argument checks, the table's slab layout and the packing of an update into the staging buffer.  Plain C++ without a HIP
+// argument checks, the table's slab layout and the interleaving of an update's records.  Plain C++ without a HIP
 // include, so tests/cpp/mappoints_host_san.cpp runs exactly this code under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-
-#include <cstring>
 
 namespace orbfe {
 
@@ -24,19 +22,6 @@ inline MapPointsLayout mappoints_layout(int capacity) {
   L.oFlags = L.oDesc + mp_align(c * 32);
   L.total = L.oFlags + mp_align(c);
   return L;
-}
-
-// one update in the staging buffer, in the order the scatter kernel reads it: slots | records | flags | descriptors
-struct MapPointsStage { size_t oSlot, oRec, oFlags, oDesc, total; };
-inline MapPointsStage mappoints_stage_layout(int n, bool withDesc) {
-  const size_t c = (size_t)(n > 0 ? n : 1);
-  MapPointsStage S;
-  S.oSlot = 0;
-  S.oRec = mp_align(c * 4);
-  S.oFlags = S.oRec + mp_align(c * 32);
-  S.oDesc = S.oFlags + mp_align(c);
-  S.total = S.oDesc + (withDesc ? mp_align(c * 32) : 0);
-  return S;
 }
 
 inline const char* mappoints_check_create(int capacity, const void* out) {
@@ -61,19 +46,15 @@ inline const char* mappoints_check_update(int capacity, int n, const int32_t* sl
   return nullptr;
 }
 
-// h: S.total bytes
-inline void mappoints_pack(uint8_t* h, const MapPointsStage& S, int n, const int32_t* slot, const float* pos, const float* normal,
-                           const float* min_dist, const float* max_dist, const uint8_t* desc, const uint8_t* flags) {
-  if (n <= 0) return;
-  std::memcpy(h + S.oSlot, slot, (size_t)n * 4);
-  float* rec = reinterpret_cast<float*>(h + S.oRec);
+// the two 16-byte records of each of the n points of an update, as the scatter kernel reads them: rec[8 i ..] =
+// (X, Y, Z, min_dist, nx, ny, nz, max_dist), 8 n floats
+inline void mappoints_pack_records(float* rec, int n, const float* pos, const float* normal, const float* min_dist,
+                                   const float* max_dist) {
   for (int i = 0; i < n; i++) {
     float* r = rec + (size_t)i * 8;
     r[0] = pos[3 * i]; r[1] = pos[3 * i + 1]; r[2] = pos[3 * i + 2]; r[3] = min_dist[i];
     r[4] = normal[3 * i]; r[5] = normal[3 * i + 1]; r[6] = normal[3 * i + 2]; r[7] = max_dist[i];
   }
-  std::memcpy(h + S.oFlags, flags, (size_t)n);
-  if (desc) std::memcpy(h + S.oDesc, desc, (size_t)n * 32);
 }
 
 }  // namespace orbfe

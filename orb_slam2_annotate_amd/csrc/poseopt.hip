@@ -1,9 +1,10 @@
 // poseopt.hip -- C-ABI entry points of the pose-only optimisation (include/orbfe.h, "Optimizer::PoseOptimization").  A call
 // is one staged copy up, ONE launch of k_pose_optimize (k_poseopt.hip) and one copy back on the calling thread's matcher
-// stream (arena.h: arena_scratch), complete on return.  The argument checks and the arena layout are poseopt_host.h (no device
-// needed).
+// stream (arena.h: arena_stage), complete on return.  The argument checks and the interleaving of the edges are
+// poseopt_host.h (no device needed).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -28,41 +29,26 @@ void fill_stats(const PoseOptResult& r, orbfe_poseopt_stats* st) {
   }
 }
 
-// what a call leaves in the arena
-struct Staged {
-  uint8_t *d = nullptr, *h = nullptr;
-  hipStream_t s = nullptr;
-  PoseOptLayout L{};
+PoseOptArgs args_begin() {
   PoseOptArgs a{};
-};
-
-int stage_begin(int device, const PoseOptLayout& L, Staged* S) {
-  S->L = L;
-  Arena* ar;
-  HIPCHK(arena_scratch(device, L.total, &ar));
-  S->d = ar->base; S->h = ar->hmirror; S->s = ar->stream;
-  PoseOptArgs& a = S->a;
-  uint8_t* d = S->d;
-  a.prob = reinterpret_cast<const PoseOptProblem*>(d + L.oProb);
-  a.res = reinterpret_cast<PoseOptResult*>(d + L.oRes);
-  a.edgeA = reinterpret_cast<float4*>(d + L.oEdgeA);
-  a.edgeB = reinterpret_cast<float4*>(d + L.oEdgeB);
-  a.level = d + L.oLevel;
-  a.chi2 = reinterpret_cast<double*>(d + L.oChi2);
   a.deltaMono = (float)std::sqrt(5.991);    // const float deltaMono = sqrt(5.991) (src/Optimizer.cc:291)
   a.deltaStereo = (float)std::sqrt(7.815);  // :292
-  return ORBFE_OK;
+  return a;
 }
 
-// one copy up, the launch, one copy back; the results are in the pinned mirror on return
-int stage_run(Staged* S, int Q, bool lds) {
-  const PoseOptLayout& L = S->L;
-  HIPCHK(hipMemcpyAsync(S->d, S->h, L.upEnd, hipMemcpyHostToDevice, S->s));
-  launch_pose_optimize(S->s, S->a, Q, lds);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(S->h + L.downBegin, S->d + L.downBegin, L.total - L.downBegin, hipMemcpyDeviceToHost, S->s));
-  HIPCHK(hipStreamSynchronize(S->s));
-  return ORBFE_OK;
+hipError_t up_problems(Arena* ar, PoseOptArgs* a, int Q, const int32_t* offsets, const float* K5, const float* Tcw_in) {
+  PoseOptProblem* dp;
+  TRY(up_pack(ar, &dp, (size_t)Q, [&](PoseOptProblem* hp) {
+    for (int p = 0; p < Q; p++) {
+      hp[p].off = offsets[p];
+      hp[p].n = offsets[p + 1] - offsets[p];
+      std::memcpy(hp[p].K5, K5 + 5 * (size_t)p, sizeof hp[p].K5);
+      std::memcpy(hp[p].Tcw, Tcw_in + 16 * (size_t)p, sizeof hp[p].Tcw);
+      hp[p].pad = 0.0f;
+    }
+  }));
+  a->prob = dp;
+  return hipSuccess;
 }
 
 int run_batch(int device, int Q, const int32_t* offsets, const float* xw, const float* u, const float* v, const float* u_right,
@@ -70,37 +56,34 @@ int run_batch(int device, int Q, const int32_t* offsets, const float* xw, const 
               int32_t* n_inliers, orbfe_poseopt_stats* stats, double* edge_chi2) {
   if (Q == 0) return ORBFE_OK;
   const int N = offsets[Q];
-  Staged S;
-  int rc = stage_begin(device, poseopt_layout(Q, N, false, false, 0, 0, sizeof(PoseOptProblem), sizeof(PoseOptResult)), &S);
-  if (rc) return rc;
-  const PoseOptLayout& L = S.L;
-  PoseOptProblem* hp = reinterpret_cast<PoseOptProblem*>(S.h + L.oProb);
+  const size_t n1 = (size_t)(N ? N : 1);
   int maxN = 0;
-  for (int p = 0; p < Q; p++) {
-    hp[p].off = offsets[p];
-    hp[p].n = offsets[p + 1] - offsets[p];
-    if (hp[p].n > maxN) maxN = hp[p].n;
-    std::memcpy(hp[p].K5, K5 + 5 * (size_t)p, sizeof hp[p].K5);
-    std::memcpy(hp[p].Tcw, Tcw_in + 16 * (size_t)p, sizeof hp[p].Tcw);
-    hp[p].pad = 0.0f;
-  }
-  float* hA = reinterpret_cast<float*>(S.h + L.oEdgeA);
-  float* hB = reinterpret_cast<float*>(S.h + L.oEdgeB);
-  for (int i = 0; i < N; i++) {
-    hA[4 * i] = xw[3 * i]; hA[4 * i + 1] = xw[3 * i + 1]; hA[4 * i + 2] = xw[3 * i + 2]; hA[4 * i + 3] = inv_sigma2[i];
-    hB[4 * i] = u[i]; hB[4 * i + 1] = v[i]; hB[4 * i + 2] = u_right[i]; hB[4 * i + 3] = 0.0f;
-  }
-  S.a.gather = 0;
-  rc = stage_run(&S, Q, maxN <= kPoseOptLdsEdges);
-  if (rc) return rc;
-  const PoseOptResult* hr = reinterpret_cast<const PoseOptResult*>(S.h + L.oRes);
-  const uint8_t* hl = S.h + L.oLevel;
-  const double* hc = reinterpret_cast<const double*>(S.h + L.oChi2);
+  for (int p = 0; p < Q; p++) maxN = std::max(maxN, offsets[p + 1] - offsets[p]);
+  PoseOptArgs A = args_begin();
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up_problems(a, &A, Q, offsets, K5, Tcw_in));
+    TRY(up_pack(a, &A.edgeA, (size_t)N, [&](float4* h) { poseopt_pack_edges_a(&h->x, N, xw, inv_sigma2); }));
+    TRY(up_pack(a, &A.edgeB, (size_t)N, [&](float4* h) { poseopt_pack_edges_b(&h->x, N, u, v, u_right); }));
+    A.res = carve<PoseOptResult>(a, (size_t)Q);  // the three outputs adjacent: one copy back
+    A.level = carve<uint8_t>(a, n1);
+    A.chi2 = carve<double>(a, n1);
+    return a->sizing ? hipSuccess : grow_mirror(a, a->used);  // the mirror reaches the outputs before flush() reads from it
+  };
+  HIPCHK(arena_stage(device, &ar, stage));
+  HIPCHK(flush(ar));
+  launch_pose_optimize(ar->stream, A, Q, maxN <= kPoseOptLdsEdges);
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, A.res, A.chi2 + n1));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  const PoseOptResult* hr = mirror_of(ar, A.res);
+  const uint8_t* hl = mirror_of(ar, A.level);
+  const double* hc = mirror_of(ar, A.chi2);
   for (int p = 0; p < Q; p++) {
     std::memcpy(Tcw_out + 16 * (size_t)p, hr[p].Tcw, 16 * sizeof(float));
     n_inliers[p] = hr[p].nInliers;
     if (stats) fill_stats(hr[p], stats + p);
-    const int n = hp[p].n, off = hp[p].off;
+    const int off = offsets[p], n = offsets[p + 1] - off;
     if (n < 3) continue;  // pose and flags untouched (src/Optimizer.cc:385)
     std::memcpy(outlier + off, hl + off, (size_t)n);
     if (edge_chi2) std::memcpy(edge_chi2 + off, hc + off, (size_t)n * sizeof(double));
@@ -144,45 +127,46 @@ extern "C" int orbfe_pose_optimization_mappoints(orbfe_mappoints* mp, int n_slot
   const int nf = F->n;
   MapPointsLock lock(mp);
   if (lock.rc) return lock.rc;
-  Staged S;
-  int rc = stage_begin(lock.device, poseopt_layout(1, nf, true, F->u_right != nullptr, n_slots, n_levels, sizeof(PoseOptProblem),
-                                                   sizeof(PoseOptResult)), &S);
-  if (rc) return rc;
-  const PoseOptLayout& L = S.L;
-  PoseOptProblem* hp = reinterpret_cast<PoseOptProblem*>(S.h + L.oProb);
-  hp->off = 0; hp->n = nf; hp->pad = 0.0f;
-  std::memcpy(hp->K5, K5, sizeof hp->K5);
-  std::memcpy(hp->Tcw, Tcw_in, sizeof hp->Tcw);
-  if (n_slots) std::memcpy(S.h + L.oSlot, slot, (size_t)n_slots * 4);
-  if (nf) {
-    std::memcpy(S.h + L.oMatch, match, (size_t)nf * 4);
-    std::memcpy(S.h + L.oFeatX, F->x, (size_t)nf * 4);
-    std::memcpy(S.h + L.oFeatY, F->y, (size_t)nf * 4);
-    if (F->u_right) std::memcpy(S.h + L.oFeatUr, F->u_right, (size_t)nf * 4);
-    std::memcpy(S.h + L.oFeatOct, F->octave, (size_t)nf * 4);
-  }
-  std::memcpy(S.h + L.oLevelTab, inv_level_sigma2, (size_t)n_levels * 4);
-  PoseOptArgs& a = S.a;
-  a.gather = 1;
-  a.table = *lock.table;
-  a.slot = reinterpret_cast<const int32_t*>(S.d + L.oSlot);
-  a.match = reinterpret_cast<const int32_t*>(S.d + L.oMatch);
-  a.featX = reinterpret_cast<const float*>(S.d + L.oFeatX);
-  a.featY = reinterpret_cast<const float*>(S.d + L.oFeatY);
-  a.featUr = F->u_right ? reinterpret_cast<const float*>(S.d + L.oFeatUr) : nullptr;
-  a.featOctave = reinterpret_cast<const int32_t*>(S.d + L.oFeatOct);
-  a.invLevelSigma2 = reinterpret_cast<const float*>(S.d + L.oLevelTab);
-  a.edgeFeat = reinterpret_cast<int32_t*>(S.d + L.oEdgeFeat);
-  rc = stage_run(&S, 1, nf <= kPoseOptLdsEdges);
-  if (rc) return rc;
-  const PoseOptResult* hr = reinterpret_cast<const PoseOptResult*>(S.h + L.oRes);
+  const size_t n1 = (size_t)(nf ? nf : 1);
+  const int32_t offsets[2] = {0, nf};
+  PoseOptArgs A = args_begin();
+  A.gather = 1;
+  A.table = *lock.table;
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up_problems(a, &A, 1, offsets, K5, Tcw_in));
+    int32_t *ds, *dm, *doct;
+    float *dx, *dy, *dur = nullptr, *dlv;  // dur NULL: a monocular frame
+    TRY(up(a, &ds, slot, (size_t)n_slots));
+    TRY(up(a, &dm, match, (size_t)nf));
+    TRY(up(a, &dx, F->x, (size_t)nf));
+    TRY(up(a, &dy, F->y, (size_t)nf));
+    if (F->u_right) TRY(up(a, &dur, F->u_right, (size_t)nf));
+    TRY(up(a, &doct, F->octave, (size_t)nf));
+    TRY(up(a, &dlv, inv_level_sigma2, (size_t)n_levels));
+    A.edgeA = carve<float4>(a, n1);  // the kernel writes the edges itself: they never travel
+    A.edgeB = carve<float4>(a, n1);
+    A.res = carve<PoseOptResult>(a, 1);  // the four outputs adjacent: one copy back
+    A.level = carve<uint8_t>(a, n1);
+    A.chi2 = carve<double>(a, n1);
+    A.edgeFeat = carve<int32_t>(a, n1);
+    A.slot = ds; A.match = dm; A.featX = dx; A.featY = dy; A.featUr = dur; A.featOctave = doct; A.invLevelSigma2 = dlv;
+    return a->sizing ? hipSuccess : grow_mirror(a, a->used);  // the mirror reaches the outputs before flush() reads from it
+  };
+  HIPCHK(arena_stage(lock.device, &ar, stage));
+  HIPCHK(flush(ar));
+  launch_pose_optimize(ar->stream, A, 1, nf <= kPoseOptLdsEdges);
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, A.res, A.edgeFeat + n1));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  const PoseOptResult* hr = mirror_of(ar, A.res);
   std::memcpy(Tcw_out, hr->Tcw, 16 * sizeof(float));
   *n_inliers = hr->nInliers;
   if (stats) fill_stats(*hr, stats);
   if (hr->nEdges < 3) return ORBFE_OK;
-  const uint8_t* hl = S.h + L.oLevel;
-  const double* hc = reinterpret_cast<const double*>(S.h + L.oChi2);
-  const int32_t* hf = reinterpret_cast<const int32_t*>(S.h + L.oEdgeFeat);
+  const uint8_t* hl = mirror_of(ar, A.level);
+  const double* hc = mirror_of(ar, A.chi2);
+  const int32_t* hf = mirror_of(ar, A.edgeFeat);
   for (int e = 0; e < hr->nEdges; e++) {  // features without an edge keep their flag (src/Optimizer.cc:301-304)
     outlier[hf[e]] = hl[e];
     if (edge_chi2) edge_chi2[hf[e]] = hc[e];

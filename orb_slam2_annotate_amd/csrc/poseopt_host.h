@@ -1,6 +1,6 @@
 // poseopt_host.h -- the host side of orbfe_pose_optimization* (poseopt.hip) that needs no device: argument checks and the
-// layout of a call in the calling thread's arena.  Plain C++ without a HIP include, so tests/cpp/poseopt_host_san.cpp runs
-// exactly this code under the address and undefined-behaviour sanitizers.
+// interleaving of the edge arrays into the kernel's float4 records.  Plain C++ without a HIP include, so
+// tests/cpp/poseopt_host_san.cpp runs exactly this code under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -10,45 +10,17 @@ namespace orbfe {
 constexpr int kPoseOptHostMaxEdges = 16384;      // the frame limit of include/orbfe.h
 constexpr int kPoseOptHostMaxProblems = 1 << 20;
 
-inline size_t po_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// A call in the arena: everything below `upEnd` travels up in one copy, [downBegin, total) comes back in one copy.
-struct PoseOptLayout {
-  size_t oProb, oEdgeA, oEdgeB, oSlot, oMatch, oFeatX, oFeatY, oFeatUr, oFeatOct, oLevelTab, upEnd;
-  size_t downBegin, oRes, oLevel, oChi2, oEdgeFeat, total;
-};
-// Q problems of N edges in all; table form: N = features of the frame, nSlots entries of slot[], nLevels of the level table.
-// sizeofProblem / sizeofResult: of the kernel's records (poseopt_kernels.h)
-inline PoseOptLayout poseopt_layout(int Q, int N, bool table, bool stereoFrame, int nSlots, int nLevels, size_t sizeofProblem,
-                                    size_t sizeofResult) {
-  const size_t q = (size_t)(Q > 0 ? Q : 1), n = (size_t)(N > 0 ? N : 1);
-  PoseOptLayout L{};
-  size_t o = 0;
-  L.oProb = o; o += po_align(q * sizeofProblem);
-  if (!table) {  // the edges travel
-    L.oEdgeA = o; o += po_align(n * 16);
-    L.oEdgeB = o; o += po_align(n * 16);
-  } else {
-    L.oSlot = o; o += po_align((size_t)(nSlots > 0 ? nSlots : 1) * 4);
-    L.oMatch = o; o += po_align(n * 4);
-    L.oFeatX = o; o += po_align(n * 4);
-    L.oFeatY = o; o += po_align(n * 4);
-    L.oFeatUr = o; o += stereoFrame ? po_align(n * 4) : 0;
-    L.oFeatOct = o; o += po_align(n * 4);
-    L.oLevelTab = o; o += po_align((size_t)(nLevels > 0 ? nLevels : 1) * 4);
+// The n edges of a call as the kernel reads them (poseopt_kernels.h: PoseOptArgs): A[4 i ..] = (Xw.x, Xw.y, Xw.z, inv_sigma2)
+// and B[4 i ..] = (u, v, u_right, 0), 4 n floats each.  One function per destination: each array is staged on its own
+inline void poseopt_pack_edges_a(float* A, int n, const float* xw, const float* inv_sigma2) {
+  for (int i = 0; i < n; i++) {
+    A[4 * i] = xw[3 * i]; A[4 * i + 1] = xw[3 * i + 1]; A[4 * i + 2] = xw[3 * i + 2]; A[4 * i + 3] = inv_sigma2[i];
   }
-  L.upEnd = o;
-  if (table) {  // the kernel writes the edges itself
-    L.oEdgeA = o; o += po_align(n * 16);
-    L.oEdgeB = o; o += po_align(n * 16);
+}
+inline void poseopt_pack_edges_b(float* B, int n, const float* u, const float* v, const float* u_right) {
+  for (int i = 0; i < n; i++) {
+    B[4 * i] = u[i]; B[4 * i + 1] = v[i]; B[4 * i + 2] = u_right[i]; B[4 * i + 3] = 0.0f;
   }
-  L.downBegin = o;
-  L.oRes = o; o += po_align(q * sizeofResult);
-  L.oLevel = o; o += po_align(n);
-  L.oChi2 = o; o += po_align(n * 8);
-  L.oEdgeFeat = o; o += table ? po_align(n * 4) : 0;
-  L.total = o;
-  return L;
 }
 
 // NULL when the arguments of the array forms are fine, else what is wrong with them.  offsets: Q + 1 ascending entries from 0

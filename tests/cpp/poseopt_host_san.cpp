@@ -1,5 +1,5 @@
-// Stand-alone program: the host side of orbfe_pose_optimization* (csrc/poseopt_host.h: argument checks and the arena layout)
-// on exactly-sized heap buffers, up to where the entry points would make their first device call.  Built with
+// Stand-alone program: the host side of orbfe_pose_optimization* (csrc/poseopt_host.h: argument checks and the interleaving
+// of the edge arrays) on exactly-sized heap buffers, up to where the entry points would make their first device call.  Built with
 // -fsanitize=address,undefined and run on the CPU (tests/test_poseopt_host_san.py); nothing of it is loaded into Python.
 // Prints "ok" and returns 0.
 #include <cstdio>
@@ -80,19 +80,22 @@ int main() {
     EXPECT(poseopt_check_table(cap, ns, slot.get(), kPoseOptHostMaxEdges + 1, match.get(), oct.get(), x.get(), x.get(), lv.get(), nl, K5.get(), T.get(), T.get(), fl.get(), &ni));
     EXPECT(poseopt_check_table(cap, ns, slot.get(), nf, match.get(), oct.get(), x.get(), x.get(), lv.get(), 0, K5.get(), T.get(), T.get(), fl.get(), &ni));
   }
-  // layout: ascending, aligned, every array inside the total
-  for (int table = 0; table < 2; table++)
-    for (int N : {0, 1, 255, 2049, kPoseOptHostMaxEdges})
-      for (int Q : {1, 512}) {
-        if (table && Q != 1) continue;
-        const PoseOptLayout L = poseopt_layout(Q, N, table != 0, true, 1000, 8, 96, 152);
-        const size_t n = (size_t)(N ? N : 1);
-        EXPECT(L.upEnd <= L.downBegin && L.downBegin == L.oRes && L.total % 256 == 0 && L.upEnd % 256 == 0);
-        EXPECT(L.oEdgeA + n * 16 <= L.oEdgeB && L.oRes + (size_t)Q * 152 <= L.oLevel && L.oLevel + n <= L.oChi2 && L.oChi2 + n * 8 <= L.total);
-        if (table) EXPECT(L.oSlot + 4000 <= L.oMatch && L.oFeatOct + n * 4 <= L.oLevelTab && L.oLevelTab + 32 <= L.upEnd &&
-                          L.oEdgeA >= L.upEnd && L.oEdgeB + n * 16 <= L.downBegin && L.oEdgeFeat + n * 4 <= L.total);
-        else EXPECT(L.oEdgeB + n * 16 <= L.upEnd);
-      }
+  // the edge interleave: every source and destination array exactly as long as n says, every output element against its source
+  for (int n : {0, 1, 15, 16, 17, 2049, kPoseOptHostMaxEdges}) {
+    auto xw = exact<float>(3 * (size_t)n), u = exact<float>(n), v = exact<float>(n), ur = exact<float>(n), w = exact<float>(n);
+    for (int i = 0; i < n; i++) {
+      for (int k = 0; k < 3; k++) xw[3 * i + k] = (float)(3 * i + k) + 0.25f;
+      u[i] = (float)i + 0.5f; v[i] = -(float)i - 1.0f; ur[i] = i % 2 ? -1.0f : (float)i - 0.125f; w[i] = 1.0f / (float)(i + 1);
+    }
+    auto A = exact<float>(4 * (size_t)n), B = exact<float>(4 * (size_t)n);
+    for (size_t k = 0; k < 4 * (size_t)n; k++) A[k] = B[k] = -7.0f;  // (no packed value is -7)
+    poseopt_pack_edges_a(A.get(), n, xw.get(), w.get());
+    poseopt_pack_edges_b(B.get(), n, u.get(), v.get(), ur.get());
+    for (int i = 0; i < n; i++) {
+      EXPECT(A[4 * i] == xw[3 * i] && A[4 * i + 1] == xw[3 * i + 1] && A[4 * i + 2] == xw[3 * i + 2] && A[4 * i + 3] == w[i]);
+      EXPECT(B[4 * i] == u[i] && B[4 * i + 1] == v[i] && B[4 * i + 2] == ur[i] && B[4 * i + 3] == 0.0f);
+    }
+  }
   std::printf("ok\n");
   return 0;
 }

@@ -8,9 +8,10 @@ from test_host_internal_header import _DEFN, _code
 
 CSRC = Path(__file__).resolve().parent.parent / "orb_slam2_annotate_amd" / "csrc"
 ARENA = {"arena.h", "arena.hip"}
-# what only the arena's own files may name: the begin behind arena_stage / arena_scratch / arena_stream and the hand sum's
-# helper; what only arena.hip may name: the thread-local state
-ARENA_ONLY = re.compile(r"\b(arena_begin|pad)\s*\(")
+# what only the arena's own files may name: the begin behind arena_stage / arena_stream, the hand sum's helper and the
+# pinned mirror (a call reads it through mirror_of() and writes it through up() / up_pack() / up_fill() / put()); what
+# only arena.hip may name: the thread-local state
+ARENA_ONLY = re.compile(r"\b(arena_begin|pad)\s*\(|\bhmirror\b")
 STATE_ONLY = re.compile(r"\b(t_arenas|t_staging)\b")
 TABLE_ONLY = re.compile(r"\bmappoints_ready\b|\bmp\s*->\s*(?:slab|m|d)\b")
 
@@ -34,13 +35,17 @@ def test_the_scan_reads_the_owners():
     assert ARENA_ONLY.search(f["arena.hip"]) and ARENA_ONLY.search(f["arena.h"])  # arena_begin: defined / behind arena_stage
     assert {m.group(1) for m in STATE_ONLY.finditer(f["arena.hip"])} == {"t_arenas", "t_staging"}
     assert TABLE_ONLY.search(f["mappoints.hip"])
-    for way in ("arena_stage", "arena_scratch", "arena_stream"):
+    for way in ("arena_stage", "arena_stream"):
         users = [n for n, t in f.items() if n not in ARENA and re.search(r"\b" + way + r"\s*\(", t)]
         assert users, f"{way} (csrc/arena.h) is used by no other file"
 
 
+def test_the_caller_laid_block_is_gone():
+    assert not [p.name for p in sorted(CSRC.iterdir()) if p.is_file() and "arena_scratch" in p.read_text(errors="replace")]
+
+
 def test_only_the_arena_begins_the_arena_and_nothing_sums_by_hand():
-    assert not named_outside(ARENA_ONLY, ARENA), "carve inside arena_stage(), or take arena_scratch() / arena_stream()"
+    assert not named_outside(ARENA_ONLY, ARENA), "carve inside arena_stage(), or take arena_stream(); reach the mirror through up*() / mirror_of()"
 
 
 def test_the_thread_local_state_is_named_only_in_arena_hip():
@@ -64,8 +69,8 @@ def test_the_table_handle_is_private_to_mappoints_hip():
 
 
 def test_the_guard_notices_a_hand_summed_begin(tmp_path):
-    """A scratch copy of csrc/ whose matcher.hip begins the arena by a size of its own again, and one that looks into the
-    table handle."""
+    """A scratch copy of csrc/ whose matcher.hip begins the arena by a size of its own again, one that writes the pinned
+    mirror by hand, and one that looks into the table handle."""
     for p in CSRC.iterdir():
         if p.suffix in (".hip", ".h", ".cpp", ".inc"):
             (tmp_path / p.name).write_text(p.read_text())
@@ -75,5 +80,7 @@ def test_the_guard_notices_a_hand_summed_begin(tmp_path):
     assert text.count("  HIPCHK(arena_stage(device, &ar, stage));\n") >= 1
     m.write_text(text.replace("  HIPCHK(arena_stage(device, &ar, stage));\n", "  HIPCHK(arena_begin(device, 2 * n, &ar));\n", 1))
     assert named_outside(ARENA_ONLY, ARENA, tmp_path) == [("matcher.hip", "arena_begin")]
+    m.write_text(text.replace("  HIPCHK(flush(ar));\n", "  std::memset(ar->hmirror, 0, 256);\n  HIPCHK(flush(ar));\n", 1))
+    assert named_outside(ARENA_ONLY, ARENA, tmp_path) == [("matcher.hip", "hmirror")]
     m.write_text(text.replace("  MapPointsLock lock(mp);\n", "  std::lock_guard<std::mutex> lk(mp->m);\n", 1))
     assert named_outside(TABLE_ONLY, {"mappoints.hip"}, tmp_path) == [("matcher.hip", "mp->m")]

@@ -100,6 +100,28 @@ def test_batch_equals_single_calls_bit_for_bit():
     assert ni[1] == 0 and st[1]["rounds"] == 0 and np.array_equal(T[1], scs[1]["Tcw"])
 
 
+def test_batch_whose_problems_end_around_a_256_byte_line():
+    """Per-problem edge counts 15, 16, 17, 3, 0 and 2: sixteen float4 edges are exactly one 256-byte line, so the edge, flag and
+    chi2 arrays of the call end just before, on and just after a line, and 53 edges in all end inside one.  An array carved
+    a line short would be overwritten by its neighbour."""
+    import orb_slam2_annotate_amd as amd
+    scs = [pr.scene(40 + p, n, 0.5, 0.2) for p, n in enumerate((15, 16, 17, 3, 0, 2))]
+    assert all((s["u_right"] >= 0).any() and (s["u_right"] < 0).any() for s in scs[:3])  # mixed mono / stereo
+    off = np.cumsum([0] + [len(s["u"]) for s in scs]).astype(np.int32)
+    cat = lambda k: np.concatenate([s[k] for s in scs])
+    ni, T, flags, st, chi2 = amd.pose_optimization_batch(off, cat("xw"), cat("u"), cat("v"), cat("u_right"), cat("inv_sigma2"),
+                                                         np.stack([s["K5"] for s in scs]), np.stack([s["Tcw"] for s in scs]),
+                                                         outlier=np.full(off[-1], 7, np.uint8))
+    for p, s in enumerate(scs):
+        lo, hi = off[p], off[p + 1]
+        one = run_gpu(s, outlier=np.full(hi - lo, 7, np.uint8))
+        assert _same(one, (int(ni[p]), T[p], flags[lo:hi], st[p], chi2[lo:hi])), p
+        if hi - lo < 3:  # pose and flags untouched
+            assert (flags[lo:hi] == 7).all() and ni[p] == 0 and st[p]["rounds"] == 0 and np.array_equal(T[p], s["Tcw"]), p
+        else:
+            assert (flags[lo:hi] <= 1).all() and st[p]["rounds"] > 0, p
+
+
 def test_batch_across_the_lds_bound_equals_single_calls():
     """One problem above kPoseOptLdsEdges = 2048 sends the whole batch to the global-memory form of the kernel; the single
     call of the small problem takes the LDS form.  Both read the same floats and sum in the same order."""
@@ -160,6 +182,39 @@ def test_table_form_equals_array_form_and_leaves_bad_slots_alone():
     has = pos_of >= 0
     assert _same(one, (ni, T, flags[has], st, chi2[has]))
     assert (flags[~has] == 9).all() and (~has).sum() == 2
+    mp.close()
+
+
+@pytest.mark.parametrize("stereo", [False, True], ids=["mono", "stereo"])
+@pytest.mark.parametrize("nf", [64, 65])
+@pytest.mark.parametrize("n_slots", [63, 64, 65])
+def test_table_form_whose_arrays_end_around_a_256_byte_line(n_slots, nf, stereo):
+    """64 int32 / float entries are exactly one 256-byte line: slot[] and the frame's arrays end just before, on and just after
+    one, a monocular frame stages no u_right at all.  min(nf, n_slots) edges; the other features have no match, the other
+    slots no feature.  Equal to the array form on the same edges bit for bit."""
+    import orb_slam2_annotate_amd as amd
+    ne = min(nf, n_slots)
+    kind = "stereo" if stereo else "mono"
+    sc = pr.scene(pr.SEEDS.get((ne, kind, 0.2), 0), ne, pr.KINDS[kind], 0.2)  # (the scene of test_against_the_reference)
+    rng = np.random.default_rng(100 * n_slots + nf)
+    pos_of = np.full(nf, -1)  # feature -> edge of the scene, -1: a feature without a match
+    pos_of[np.sort(rng.permutation(nf)[:ne])] = np.arange(ne)
+    has = pos_of >= 0
+    edge = np.where(has, pos_of, 0)
+    cap = 70
+    slots = rng.permutation(cap)[:n_slots].astype(np.int32)
+    at = rng.permutation(n_slots)[:ne]  # slot[] position of edge k
+    mp = amd.MapPoints(cap)
+    z = np.zeros(ne, np.float32)
+    mp.update(slots[at], sc["xw"], np.zeros((ne, 3), np.float32), z, z + 1, np.zeros((ne, 32), np.uint8), np.full(ne, 2, np.uint8))
+    match = np.where(has, at[edge], -1).astype(np.int32)
+    assert (sc["u_right"] >= 0).all() if stereo else (sc["u_right"] < 0).all()
+    F = amd.FrameView(sc["u"][edge], sc["v"][edge], np.where(has, sc["octave"][edge], 0), np.zeros((nf, 32), np.uint8), fr.BOUNDS,
+                      u_right=sc["u_right"][edge] if stereo else None)
+    ni, T, flags, st, chi2 = mp.pose_optimization(F, slots, match, sc["Tcw"], sc["K5"], pr.INV_LEVEL_SIGMA2,
+                                                  outlier=np.full(nf, 9, np.uint8))
+    assert _same(run_gpu(sc), (ni, T, flags[has], st, chi2[has]))
+    assert (flags[~has] == 9).all() and (chi2[~has] == 0).all() and (~has).sum() == nf - ne
     mp.close()
 
 
