@@ -889,6 +889,25 @@ int orc_window_branch_counts(int64_t *out, int n) {
 }
 #define WB(k) (g_window_branch[ORC_WB_##k]++)
 #define WB_RESET() memset(g_window_branch, 0, sizeof(g_window_branch))
+/* one counter per exit / decision of the FeatureVector searches (SearchByBoW in both forms, SearchForTriangulation) taken
+   by this thread's last call of one of the three; the order is ORC_BB_* below and in orb_oracle.h.  Reset when such a call
+   starts, together with the window counters above: the histogram decisions of three_maxima / rh_prune (HIST_PRUNED,
+   MAX2_BELOW_TENTH, MAX3_BELOW_TENTH, MAXIMA_ALL_KEPT) stay WB() counts and are read through orc_window_branch_counts
+   after the call.  They change no result. */
+enum { ORC_BB_NODE_SHARED, ORC_BB_NODE_ONLY_IN_1, ORC_BB_NODE_ONLY_IN_2, ORC_BB_QUERY_MASKED, ORC_BB_CAND_CLAIMED,
+       ORC_BB_CAND_MASKED, ORC_BB_BETTER_BEST, ORC_BB_BETTER_SECOND, ORC_BB_EQUAL_BEST_BECOMES_SECOND, ORC_BB_NOT_BETTER,
+       ORC_BB_NO_CANDIDATE, ORC_BB_THRESHOLD_REJECT, ORC_BB_THRESHOLD_PASS_AT_50, ORC_BB_RATIO_REJECT,
+       ORC_BB_RATIO_SECOND_IS_256, ORC_BB_ACCEPTED, ORC_BB_TRI_QUERY_HAS_MP, ORC_BB_TRI_QUERY_MONO_ONLY_STEREO,
+       ORC_BB_TRI_CAND_HAS_MP, ORC_BB_TRI_CAND_MONO_ONLY_STEREO, ORC_BB_TRI_DIST_ABOVE_TH, ORC_BB_TRI_DIST_ABOVE_BEST,
+       ORC_BB_TRI_EPIPOLE_REJECT, ORC_BB_TRI_EPIPOLE_SKIPPED_STEREO, ORC_BB_TRI_DEN_ZERO, ORC_BB_TRI_EPIPOLAR_REJECT,
+       ORC_BB_TRI_REPLACED_EQUAL, ORC_BB_TRI_REPLACED_SMALLER, ORC_BB_TRI_FIRST_ACCEPT, ORC_BB_TRI_NO_MATCH, ORC_BB_COUNT };
+static __thread int64_t g_bow_branch[ORC_BB_COUNT];
+int orc_bow_branch_counts(int64_t *out, int n) {
+  for (int i = 0; i < n && i < ORC_BB_COUNT; i++) out[i] = g_bow_branch[i];
+  return ORC_BB_COUNT;
+}
+#define BB(k) (g_bow_branch[ORC_BB_##k]++)
+#define BB_RESET() do { memset(g_bow_branch, 0, sizeof(g_bow_branch)); WB_RESET(); } while (0)
 
 int orc_descriptor_distance(const uint8_t *a, const uint8_t *b) { /* :1828-1844 */
   int dist = 0;
@@ -951,19 +970,27 @@ static int rh_prune(rothist *h, int32_t *arr) { /* :303-322; returns removed cou
 #define FV_WALK_BEGIN(fv1, fv2) \
   { int a_ = 0, b_ = 0; \
     while (a_ < (fv1)->n_nodes && b_ < (fv2)->n_nodes) { \
-      if ((fv1)->node_ids[a_] == (fv2)->node_ids[b_]) {
+      if ((fv1)->node_ids[a_] == (fv2)->node_ids[b_]) { \
+        BB(NODE_SHARED);
 #define FV_WALK_END(fv1, fv2) \
         a_++; b_++; \
       } else if ((fv1)->node_ids[a_] < (fv2)->node_ids[b_]) { \
-        while (a_ < (fv1)->n_nodes && (fv1)->node_ids[a_] < (fv2)->node_ids[b_]) a_++; \
+        while (a_ < (fv1)->n_nodes && (fv1)->node_ids[a_] < (fv2)->node_ids[b_]) { a_++; BB(NODE_ONLY_IN_1); } \
       } else { \
-        while (b_ < (fv2)->n_nodes && (fv2)->node_ids[b_] < (fv1)->node_ids[a_]) b_++; \
+        while (b_ < (fv2)->n_nodes && (fv2)->node_ids[b_] < (fv1)->node_ids[a_]) { b_++; BB(NODE_ONLY_IN_2); } \
       } } }
+
+/* the two-smallest bookkeeping of :251-260 / :674-683 and the decisions of :263-285 / :686-706, counted */
+#define BOW_TWO_SMALLEST(dist, idx) \
+  if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdx = (int)(idx); BB(BETTER_BEST); } \
+  else if (dist < bestDist2) { if (dist == bestDist1) BB(EQUAL_BEST_BECOMES_SECOND); else BB(BETTER_SECOND); bestDist2 = dist; } \
+  else BB(NOT_BETTER);
 
 int orc_search_by_bow(const uint8_t *desc1, const uint8_t *has_mp1, const float *ang1, int n1,
                       const orc_featvec *fv1, const uint8_t *desc2, const float *ang2, int n2,
                       const orc_featvec *fv2, float nnratio, int check_ori, int32_t *match_f) {
   (void)n1;
+  BB_RESET();
   for (int i = 0; i < n2; i++) match_f[i] = -1;
   int nmatches = 0;
   rothist rh;
@@ -971,23 +998,27 @@ int orc_search_by_bow(const uint8_t *desc1, const uint8_t *has_mp1, const float 
   FV_WALK_BEGIN(fv1, fv2)
     for (int iKF = fv1->offsets[a_]; iKF < fv1->offsets[a_ + 1]; iKF++) {
       const unsigned realIdxKF = fv1->indices[iKF];
-      if (!has_mp1[realIdxKF]) continue;
+      if (!has_mp1[realIdxKF]) { BB(QUERY_MASKED); continue; }
       const uint8_t *dKF = desc1 + (size_t)realIdxKF * 32;
-      int bestDist1 = 256, bestIdxF = -1, bestDist2 = 256;
+      int bestDist1 = 256, bestIdx = -1, bestDist2 = 256;
       for (int iF = fv2->offsets[b_]; iF < fv2->offsets[b_ + 1]; iF++) {
         const unsigned realIdxF = fv2->indices[iF];
-        if (match_f[realIdxF] >= 0) continue;
+        if (match_f[realIdxF] >= 0) { BB(CAND_CLAIMED); continue; }
         const int dist = orc_descriptor_distance(dKF, desc2 + (size_t)realIdxF * 32);
-        if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdxF = (int)realIdxF; }
-        else if (dist < bestDist2) bestDist2 = dist;
+        BOW_TWO_SMALLEST(dist, realIdxF)
       }
+      const int bestIdxF = bestIdx;
       if (bestDist1 <= TH_LOW) {
         if ((float)bestDist1 < nnratio * (float)bestDist2) {
           match_f[bestIdxF] = (int32_t)realIdxKF;
           if (check_ori) rh_push(&rh, ang1[realIdxKF], ang2[bestIdxF], bestIdxF);
           nmatches++;
-        }
-      }
+          BB(ACCEPTED);
+          if (bestDist1 == TH_LOW) BB(THRESHOLD_PASS_AT_50);
+          if (bestDist2 == 256) BB(RATIO_SECOND_IS_256);
+        } else BB(RATIO_REJECT);
+      } else if (bestIdx < 0) BB(NO_CANDIDATE);
+      else BB(THRESHOLD_REJECT);
     }
   FV_WALK_END(fv1, fv2)
   if (check_ori) nmatches -= rh_prune(&rh, match_f);
@@ -999,6 +1030,7 @@ int orc_search_by_bow_kf(const uint8_t *desc1, const uint8_t *has_mp1, const flo
                          const orc_featvec *fv1, const uint8_t *desc2, const uint8_t *has_mp2,
                          const float *ang2, int n2, const orc_featvec *fv2, float nnratio,
                          int check_ori, int32_t *match12) {
+  BB_RESET();
   for (int i = 0; i < n1; i++) match12[i] = -1;
   uint8_t *matched2 = (uint8_t *)calloc(n2 > 0 ? n2 : 1, 1);
   int nmatches = 0;
@@ -1007,24 +1039,28 @@ int orc_search_by_bow_kf(const uint8_t *desc1, const uint8_t *has_mp1, const flo
   FV_WALK_BEGIN(fv1, fv2)
     for (int i1 = fv1->offsets[a_]; i1 < fv1->offsets[a_ + 1]; i1++) {
       const unsigned idx1 = fv1->indices[i1];
-      if (!has_mp1[idx1]) continue;
+      if (!has_mp1[idx1]) { BB(QUERY_MASKED); continue; }
       const uint8_t *d1 = desc1 + (size_t)idx1 * 32;
-      int bestDist1 = 256, bestIdx2 = -1, bestDist2 = 256;
+      int bestDist1 = 256, bestIdx = -1, bestDist2 = 256;
       for (int i2 = fv2->offsets[b_]; i2 < fv2->offsets[b_ + 1]; i2++) {
         const unsigned idx2 = fv2->indices[i2];
-        if (matched2[idx2] || !has_mp2[idx2]) continue;
+        if (matched2[idx2]) { BB(CAND_CLAIMED); continue; }
+        if (!has_mp2[idx2]) { BB(CAND_MASKED); continue; }
         int dist = orc_descriptor_distance(d1, desc2 + (size_t)idx2 * 32);
-        if (dist < bestDist1) { bestDist2 = bestDist1; bestDist1 = dist; bestIdx2 = (int)idx2; }
-        else if (dist < bestDist2) bestDist2 = dist;
+        BOW_TWO_SMALLEST(dist, idx2)
       }
+      const int bestIdx2 = bestIdx;
       if (bestDist1 < TH_LOW) {
         if ((float)bestDist1 < nnratio * (float)bestDist2) {
           match12[idx1] = bestIdx2;
           matched2[bestIdx2] = 1;
           if (check_ori) rh_push(&rh, ang1[idx1], ang2[bestIdx2], (int)idx1);
           nmatches++;
-        }
-      }
+          BB(ACCEPTED);
+          if (bestDist2 == 256) BB(RATIO_SECOND_IS_256);
+        } else BB(RATIO_REJECT);
+      } else if (bestIdx < 0) BB(NO_CANDIDATE);
+      else BB(THRESHOLD_REJECT);
     }
   FV_WALK_END(fv1, fv2)
   if (check_ori) nmatches -= rh_prune(&rh, match12);
@@ -1040,9 +1076,11 @@ static int check_epipolar(float x1, float y1, float x2, float y2, const float *F
   const float c = x1 * F[2] + y1 * F[5] + F[8];
   const float num = a * x2 + b * y2 + c;
   const float den = a * a + b * b;
-  if (den == 0) return 0;
+  if (den == 0) { BB(TRI_DEN_ZERO); return 0; }
   const float dsqr = num * num / den;
-  return (double)dsqr < 3.84 * (double)sigma2;
+  if ((double)dsqr < 3.84 * (double)sigma2) return 1;
+  BB(TRI_EPIPOLAR_REJECT);
+  return 0;
 }
 
 int orc_search_for_triangulation(const uint8_t *desc1, const uint8_t *has_mp1, const float *x1,
@@ -1054,6 +1092,7 @@ int orc_search_for_triangulation(const uint8_t *desc1, const uint8_t *has_mp1, c
                                  float ey, const float *scale_factors2, const float *level_sigma2_2,
                                  int only_stereo, int check_ori, int32_t *match12) {
   (void)n2;
+  BB_RESET();
   for (int i = 0; i < n1; i++) match12[i] = -1;
   int nmatches = 0;
   rothist rh;
@@ -1061,24 +1100,28 @@ int orc_search_for_triangulation(const uint8_t *desc1, const uint8_t *has_mp1, c
   FV_WALK_BEGIN(fv1, fv2)
     for (int i1 = fv1->offsets[a_]; i1 < fv1->offsets[a_ + 1]; i1++) {
       const unsigned idx1 = fv1->indices[i1];
-      if (has_mp1[idx1]) continue;
+      if (has_mp1[idx1]) { BB(TRI_QUERY_HAS_MP); continue; }
       const int bStereo1 = stereo1[idx1];
-      if (only_stereo && !bStereo1) continue;
+      if (only_stereo && !bStereo1) { BB(TRI_QUERY_MONO_ONLY_STEREO); continue; }
       const uint8_t *d1 = desc1 + (size_t)idx1 * 32;
       int bestDist = TH_LOW, bestIdx2 = -1;
       for (int i2 = fv2->offsets[b_]; i2 < fv2->offsets[b_ + 1]; i2++) {
         const unsigned idx2 = fv2->indices[i2];
-        if (has_mp2[idx2]) continue; /* vbMatched2 is never set (:774,827) */
+        if (has_mp2[idx2]) { BB(TRI_CAND_HAS_MP); continue; } /* vbMatched2 is never set (:774,827) */
         const int bStereo2 = stereo2[idx2];
-        if (only_stereo && !bStereo2) continue;
+        if (only_stereo && !bStereo2) { BB(TRI_CAND_MONO_ONLY_STEREO); continue; }
         const int dist = orc_descriptor_distance(d1, desc2 + (size_t)idx2 * 32);
-        if (dist > TH_LOW || dist > bestDist) continue;
+        if (dist > TH_LOW) { BB(TRI_DIST_ABOVE_TH); continue; }
+        if (dist > bestDist) { BB(TRI_DIST_ABOVE_BEST); continue; }
         if (!bStereo1 && !bStereo2) {
           const float distex = ex - x2[idx2];
           const float distey = ey - y2[idx2];
-          if (distex * distex + distey * distey < 100 * scale_factors2[oct2[idx2]]) continue;
-        }
+          if (distex * distex + distey * distey < 100 * scale_factors2[oct2[idx2]]) { BB(TRI_EPIPOLE_REJECT); continue; }
+        } else BB(TRI_EPIPOLE_SKIPPED_STEREO);
         if (check_epipolar(x1[idx1], y1[idx1], x2[idx2], y2[idx2], F12, level_sigma2_2[oct2[idx2]])) {
+          if (bestIdx2 < 0) BB(TRI_FIRST_ACCEPT);
+          else if (dist == bestDist) BB(TRI_REPLACED_EQUAL);
+          else BB(TRI_REPLACED_SMALLER);
           bestIdx2 = (int)idx2;
           bestDist = dist;
         }
@@ -1086,8 +1129,9 @@ int orc_search_for_triangulation(const uint8_t *desc1, const uint8_t *has_mp1, c
       if (bestIdx2 >= 0) {
         match12[idx1] = bestIdx2;
         nmatches++;
+        BB(ACCEPTED);
         if (check_ori) rh_push(&rh, ang1[idx1], ang2[bestIdx2], (int)idx1);
-      }
+      } else BB(TRI_NO_MATCH);
     }
   FV_WALK_END(fv1, fv2)
   if (check_ori) nmatches -= rh_prune(&rh, match12);

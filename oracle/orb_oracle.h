@@ -131,6 +131,28 @@ int orc_stereo_branch_counts(int64_t *out, int n);
     35 SearchBySim3: pair agreed in both directions, 36 forward match without the backward one.
    Writes min(n, count) entries, returns the count. */
 int orc_window_branch_counts(int64_t *out, int n);
+/* one counter per exit / decision of the FeatureVector searches, taken during this thread's last call of
+   orc_search_by_bow, orc_search_by_bow_kf or orc_search_for_triangulation (each resets them when it starts).  The same
+   three entry points also RESET the window counters above: the histogram decisions of their ComputeThreeMaxima / pruning
+   step are not mirrored here, they are read as entries 30 and 32..34 of orc_window_branch_counts after the call.
+   They change no result.  Order:
+     0 node id in both FeatureVectors, 1 node of the first passed over by lower_bound, 2 node of the second passed over
+       (nodes left when either map ends are not visited and not counted);
+     3 query without a map point skipped (:225, :647), 4 candidate already matched (:242, :664), 5 candidate without a map
+       point (KF, KF form, :664);
+     6 dist < bestDist1, 7 bestDist1 < dist < bestDist2, 8 dist == bestDist1 < bestDist2 (an equal distance becomes the
+       second best), 9 neither;
+    10 no candidate left (bestDist1 stays 256), 11 bestDist1 above the threshold (> 50 for (KF, Frame), >= 50 for (KF, KF)),
+    12 accepted with bestDist1 == 50 ((KF, Frame) only), 13 ratio test failed, 14 accepted with bestDist2 still 256,
+    15 accepted (all three searches: a match written, before the histogram pruning);
+    SearchForTriangulation: 16 query has a map point (:802), 17 monocular query under bOnlyStereo (:807), 18 candidate has a
+    map point (:827), 19 monocular candidate under bOnlyStereo (:832), 20 dist > TH_LOW, 21 dist > bestDist (:840),
+    22 closer to the epipole than 100 * scaleFactor (:852), 23 that test skipped because either side is stereo,
+    24 CheckDistEpipolarLine: den == 0, 25 dsqr not below 3.84 * sigma2, 26 passed at dist == bestDist over an earlier
+    candidate, 27 passed at a smaller dist over an earlier candidate, 28 passed as the first candidate, 29 query ends
+    without a match.
+   Writes min(n, count) entries, returns the count. */
+int orc_bow_branch_counts(int64_t *out, int n);
 float orc_stereo_delta_r(float dist1, float dist2, float dist3); /* src/Frame.cc:648 */
 void orc_three_maxima(const int *histo_sizes, int L, int *ind1, int *ind2, int *ind3); /* :1777-1821 */
 

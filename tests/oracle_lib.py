@@ -106,6 +106,24 @@ def window_branch_counts() -> dict:
     return dict(zip(WINDOW_BRANCHES, (int(v) for v in out)))
 
 
+BOW_BRANCHES = ("node_shared", "node_only_in_1", "node_only_in_2", "query_masked", "cand_claimed", "cand_masked", "better_best",
+                "better_second", "equal_best_becomes_second", "not_better", "no_candidate", "threshold_reject",
+                "threshold_pass_at_50", "ratio_reject", "ratio_second_is_256", "accepted", "tri_query_has_mp",
+                "tri_query_mono_only_stereo", "tri_cand_has_mp", "tri_cand_mono_only_stereo", "tri_dist_above_th",
+                "tri_dist_above_best", "tri_epipole_reject", "tri_epipole_skipped_stereo", "tri_den_zero", "tri_epipolar_reject",
+                "tri_replaced_equal", "tri_replaced_smaller", "tri_first_accept", "tri_no_match")
+
+
+def bow_branch_counts() -> dict:
+    """exit / decision of SearchByBoW (both forms) and SearchForTriangulation -> how often this thread's last call of one of
+    them took it (orc_bow_branch_counts; the order is documented in oracle/orb_oracle.h).  The histogram decisions of the
+    same call are in window_branch_counts(): those entry points reset both sets."""
+    out = (C.c_int64 * len(BOW_BRANCHES))()
+    n = lib().orc_bow_branch_counts(out, len(BOW_BRANCHES))
+    assert n == len(BOW_BRANCHES)
+    return dict(zip(BOW_BRANCHES, (int(v) for v in out)))
+
+
 def stereo_delta_r(dist1, dist2, dist3) -> np.float32:
     """the oracle's parabola fit (src/Frame.cc:648)"""
     L = lib()
