@@ -858,6 +858,40 @@ int orbfe_sim3_triples_from_draws(int n, int n_hypotheses, const int32_t *draws 
  * never reads the result). */
 int orbfe_sim3_max_iterations(int n, double prob, int min_inliers, int max_its);
 
+/* -------------------------------------------------------------------------- */
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:1116-1323)                        */
+/* -------------------------------------------------------------------------- */
+/* The Sim3 refinement LoopClosing::ComputeSim3 runs on every candidate that survives Sim3Solver and SearchBySim3
+ * (src/LoopClosing.cc:387-388), ONE kernel launch per call: both rounds (optimize(5), erase, optimize(5 or 10), erase), their
+ * Levenberg iterations with up to ten lambda trials each, and the "fewer than 10 pairs left" exit, on the one graph
+ * OptimizeSim3 builds (one free Sim3 vertex S12, per pair an EdgeSim3ProjectXYZ and an EdgeInverseSim3ProjectXYZ with
+ * information invSigma2 I and a Huber kernel of delta = sqrt(th2), a dense 7 x 7 system).  Arithmetic is binary64 on inputs
+ * widened from float.  g2o differentiates the two edges numerically; the call uses the analytic Jacobian of the same left
+ * update, so it agrees with g2o to the accuracy of g2o's difference quotient and is not bit-identical to it.
+ * As in the reference, a classification reads the error of the LAST evaluated Levenberg trial, accepted or not.
+ * K problems; pair_off[K+1]; per pair: X1 = R1w*P1w+t1w, X2 likewise (float, as cv::Mat holds them), obs1 = mvKeysUn1[i].pt,
+ * obs2 = mvKeysUn2[i2].pt, the two mvInvLevelSigma2[octave]; per problem: cam1/cam2 = fx fy cx cy, sim3_in[13] = R row-major, t, s
+ * (the layout orbfe_sim3_ransac_multi writes), th2, fix_scale.  sim3_out[8] = qx qy qz qw tx ty tz s: g2o::Sim3's own members.
+ * Outputs per problem: n_in (the return value of OptimizeSim3); sim3_out -- the incoming S12 converted as
+ * Sim3(Matrix3d, Vector3d, double) does whenever n_in comes from the early return (fewer than 10 pairs left after round
+ * one, or no pair at all), the optimised S12 otherwise; bad[i] = 0 kept, 1 erased after round one, 2 erased after round two
+ * (the caller sets vpMatches1[idx] = NULL for every bad[i] != 0, also after the early return); chi2_12 / chi2_21 (both may
+ * be NULL) the chi2 the last classification of the pair read.  stats may be NULL.
+ * Limits: 16384 pairs per problem, 1048576 problems.  Returns ORBFE_ERR_INVALID before anything is enqueued, leaving the
+ * thread usable, for: NULL arrays, pair_off that does not start at 0 or descends, a problem above the limit, a th2 that is
+ * not positive and finite.  Runs on the calling thread's matcher stream and is complete on return. */
+typedef struct orbfe_optsim3_stats { int32_t rounds, n_bad; int32_t iterations[2], trials[2]; double lambda[2], chi2[2]; } orbfe_optsim3_stats;
+int orbfe_optimize_sim3_multi(int device, int n_problems, const int32_t *pair_off, const float *x3dc1, const float *x3dc2,
+                              const float *obs1, const float *obs2, const float *inv_sigma2_1, const float *inv_sigma2_2,
+                              const float *cam1, const float *cam2, const float *sim3_in, const float *th2, const uint8_t *fix_scale,
+                              double *sim3_out, uint8_t *bad, int32_t *n_in, orbfe_optsim3_stats *stats,
+                              double *chi2_12, double *chi2_21 /* both may be NULL */);
+/* One problem; bit-equal to the multi form with n_problems = 1. */
+int orbfe_optimize_sim3(int device, int n, const float *x3dc1, const float *x3dc2, const float *obs1, const float *obs2,
+                        const float *inv_sigma2_1, const float *inv_sigma2_2, const float cam1[4], const float cam2[4],
+                        const float sim3_in[13], float th2, int fix_scale, double sim3_out[8], uint8_t *bad, int32_t *n_in,
+                        orbfe_optsim3_stats *stats, double *chi2_12, double *chi2_21);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th,
  * const bool bMono) (src/ORBmatcher.cc:1484-1633) after the caller's pose arithmetic: last-frame
  * point i is valid when it has a non-outlier map point with invzc >= 0 projecting to (u, v) inside

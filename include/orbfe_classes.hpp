@@ -684,7 +684,8 @@ class MapPointTable {
   orbfe_mappoints* h_ = nullptr;
 };
 
-// Optimizer::PoseOptimization (src/Optimizer.cc:256-473) on the device; the other Optimizer functions are not covered.
+// Optimizer::PoseOptimization (src/Optimizer.cc:256-473) and Optimizer::OptimizeSim3 (:1116-1323) on the device; the other
+// Optimizer functions are not covered.
 // Both forms return nInitialCorrespondences - nBad, write the pose Frame::SetPose receives into Tcw (row-major 4 x 4) and
 // mvbOutlier of every edge; with fewer than 3 edges they return 0 and leave both alone.
 class Optimizer {
@@ -719,6 +720,95 @@ class Optimizer {
           "PoseOptimization");
     for (int k = 0; k < 16; k++) Tcw[k] = out[k];
     return nInliers;
+  }
+
+  // OptimizeSim3 without the map graph.  The caller walks vpMatches1 as the reference does (:1173-1259) and hands in, for the
+  // pairs it adds edges for: idx1 (vnIndexEdge: the index i into vpMatches1), X1 / X2 3 floats each (P3D1c = R1w * P3D1w +
+  // t1w, P3D2c likewise), obs1 / obs2 2 floats each (mvKeysUn[i].pt of key frame 1, mvKeysUn[i2].pt of key frame 2), the
+  // two mvInvLevelSigma2[octave], K1 / K2 = fx fy cx cy.  vpMatches1 holds whatever the caller keeps per keypoint of key
+  // frame 1 (here an index, -1 = no match): every erased pair gets vpMatches1[idx1[i]] = -1, also when the call returns 0
+  // early.  S12 = g2o::Sim3's members qx qy qz qw tx ty tz s, in and out; it is left untouched when the reference would
+  // leave g2oS12 untouched (fewer than 10 pairs left after round one, or no pair).  Returns nIn.
+  static int OptimizeSim3(const std::vector<int32_t>& idx1, const std::vector<float>& X1, const std::vector<float>& X2,
+                          const std::vector<float>& obs1, const std::vector<float>& obs2, const std::vector<float>& invSigma2_1,
+                          const std::vector<float>& invSigma2_2, const float K1[4], const float K2[4], std::vector<int32_t>& vpMatches1,
+                          double S12[8], float th2, bool bFixScale, orbfe_optsim3_stats* stats = nullptr, int device = 0) {
+    const size_t n = idx1.size();
+    if (X1.size() != 3 * n || X2.size() != 3 * n || obs1.size() != 2 * n || obs2.size() != 2 * n || invSigma2_1.size() != n ||
+        invSigma2_2.size() != n)
+      throw std::invalid_argument("Optimizer::OptimizeSim3: one entry per pair");
+    for (int32_t i : idx1)
+      if (i < 0 || (size_t)i >= vpMatches1.size()) throw std::invalid_argument("Optimizer::OptimizeSim3: idx1 outside vpMatches1");
+    float rec[13];
+    sim3_record(S12, rec);
+    std::vector<uint8_t> bad(n ? n : 1, 0);
+    double out[8];
+    int32_t nIn = 0;
+    orbfe_optsim3_stats st;
+    check(orbfe_optimize_sim3(device, (int)n, X1.data(), X2.data(), obs1.data(), obs2.data(), invSigma2_1.data(), invSigma2_2.data(),
+                              K1, K2, rec, th2, bFixScale ? 1 : 0, out, bad.data(), &nIn, &st, nullptr, nullptr), "OptimizeSim3");
+    for (size_t i = 0; i < n; i++)
+      if (bad[i]) vpMatches1[(size_t)idx1[i]] = -1;
+    if (st.rounds == 2)
+      for (int k = 0; k < 8; k++) S12[k] = out[k];
+    if (stats) *stats = st;
+    return nIn;
+  }
+  // K candidates in one launch: pairOff [K + 1], K1 / K2 4 K floats, S12 8 K doubles, th2 and bFixScale one entry each; idx1
+  // indexes the candidate's own vpMatches1[k].  Returns nIn of every candidate
+  static std::vector<int> OptimizeSim3Multi(const std::vector<int32_t>& pairOff, const std::vector<int32_t>& idx1,
+                                            const std::vector<float>& X1, const std::vector<float>& X2, const std::vector<float>& obs1,
+                                            const std::vector<float>& obs2, const std::vector<float>& invSigma2_1,
+                                            const std::vector<float>& invSigma2_2, const std::vector<float>& K1,
+                                            const std::vector<float>& K2, std::vector<std::vector<int32_t>>& vpMatches1,
+                                            std::vector<double>& S12, const std::vector<float>& th2,
+                                            const std::vector<uint8_t>& bFixScale, std::vector<orbfe_optsim3_stats>* stats = nullptr,
+                                            int device = 0) {
+    if (pairOff.empty() || pairOff[0] != 0) throw std::invalid_argument("Optimizer::OptimizeSim3Multi: pairOff holds K + 1 entries from 0");
+    const size_t K = pairOff.size() - 1, n = idx1.size();
+    if ((size_t)pairOff[K] != n || X1.size() != 3 * n || X2.size() != 3 * n || obs1.size() != 2 * n || obs2.size() != 2 * n ||
+        invSigma2_1.size() != n || invSigma2_2.size() != n)
+      throw std::invalid_argument("Optimizer::OptimizeSim3Multi: one entry per pair");
+    if (K1.size() != 4 * K || K2.size() != 4 * K || S12.size() != 8 * K || th2.size() != K || bFixScale.size() != K ||
+        vpMatches1.size() != K)
+      throw std::invalid_argument("Optimizer::OptimizeSim3Multi: one entry per candidate");
+    for (size_t k = 0; k < K; k++) {
+      if (pairOff[k + 1] < pairOff[k]) throw std::invalid_argument("Optimizer::OptimizeSim3Multi: pairOff must not descend");
+      for (int32_t p = pairOff[k]; p < pairOff[k + 1]; p++)
+        if (idx1[(size_t)p] < 0 || (size_t)idx1[(size_t)p] >= vpMatches1[k].size())
+          throw std::invalid_argument("Optimizer::OptimizeSim3Multi: idx1 outside vpMatches1");
+    }
+    std::vector<float> rec(13 * K + 1);
+    for (size_t k = 0; k < K; k++) sim3_record(S12.data() + 8 * k, rec.data() + 13 * k);
+    std::vector<uint8_t> bad(n ? n : 1, 0);
+    std::vector<double> out(8 * K + 1);
+    std::vector<int32_t> nIn(K + 1, 0);
+    std::vector<orbfe_optsim3_stats> st(K + 1);
+    check(orbfe_optimize_sim3_multi(device, (int)K, pairOff.data(), X1.data(), X2.data(), obs1.data(), obs2.data(), invSigma2_1.data(),
+                                    invSigma2_2.data(), K1.data(), K2.data(), rec.data(), th2.data(), bFixScale.data(), out.data(),
+                                    bad.data(), nIn.data(), st.data(), nullptr, nullptr), "OptimizeSim3Multi");
+    std::vector<int> ret(K);
+    for (size_t k = 0; k < K; k++) {
+      for (int32_t p = pairOff[k]; p < pairOff[k + 1]; p++)
+        if (bad[(size_t)p]) vpMatches1[k][(size_t)idx1[(size_t)p]] = -1;
+      if (st[k].rounds == 2)
+        for (int j = 0; j < 8; j++) S12[8 * k + j] = out[8 * k + j];
+      ret[k] = nIn[k];
+    }
+    if (stats) stats->assign(st.begin(), st.begin() + (std::ptrdiff_t)K);
+    return ret;
+  }
+  // g2o::Sim3's members -> the sim3[13] record the C-ABI takes (R = r.toRotationMatrix() row-major, t, s; rounded to float
+  // as the reference's cv::Mat hand-over is): the C-ABI rebuilds Sim3(Matrix3d, Vector3d, double) from it
+  static void sim3_record(const double S[8], float rec[13]) {
+    const double x = S[0], y = S[1], z = S[2], w = S[3];
+    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x;
+    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    const double R[9] = {1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz), tyz - twx,
+                         txz - twy, tyz + twx, 1.0 - (txx + tyy)};
+    for (int k = 0; k < 9; k++) rec[k] = (float)R[k];
+    rec[9] = (float)S[4]; rec[10] = (float)S[5]; rec[11] = (float)S[6]; rec[12] = (float)S[7];
   }
 };
 

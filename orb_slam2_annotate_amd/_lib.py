@@ -53,6 +53,12 @@ class PoseOptStatsC(C.Structure):
                 ("lam", C.c_double * 4), ("chi2", C.c_double * 4)]
 
 
+class OptSim3StatsC(C.Structure):
+    """orbfe_optsim3_stats."""
+    _fields_ = [("rounds", C.c_int32), ("n_bad", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2),
+                ("lam", C.c_double * 2), ("chi2", C.c_double * 2)]
+
+
 class KeyFrameCameraC(C.Structure):
     """orbfe_keyframe_camera: what LocalMapping::CreateNewMapPoints reads of a key frame besides its keypoints."""
     _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3),
@@ -96,6 +102,7 @@ EXPORTS = [
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch", "orbfe_pose_optimization_mappoints",
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_multi",
     "orbfe_sim3_ransac", "orbfe_sim3_ransac_multi", "orbfe_sim3_triples_from_draws", "orbfe_sim3_max_iterations",
+    "orbfe_optimize_sim3", "orbfe_optimize_sim3_multi",
 ]
 
 _lib = None
@@ -270,6 +277,8 @@ def load():
     L.orbfe_triangulate_matches_multi.argtypes = [ci, fwp, kcp, ci, vp, kcp, vp, vp, vp, ci, cf, vp, vp, vp, vp]
     L.orbfe_triangulate_matches.argtypes = [ci, fwp, kcp, fwp, kcp, vp, vp, vp, ci, cf, vp, vp, vp]
     L.orbfe_sim3_ransac_multi.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_optimize_sim3_multi.argtypes = [ci, ci] + [vp] * 18
+    L.orbfe_optimize_sim3.argtypes = [ci, ci] + [vp] * 9 + [C.c_float, ci] + [vp] * 6
     L.orbfe_sim3_ransac.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     L.orbfe_sim3_triples_from_draws.argtypes = [ci, ci, vp, vp]
     L.orbfe_sim3_max_iterations.argtypes = [ci, C.c_double, ci, ci]

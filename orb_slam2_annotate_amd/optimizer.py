@@ -1,6 +1,10 @@
 """Optimizer::PoseOptimization (src/Optimizer.cc:256-473) on the device (include/orbfe.h: orbfe_pose_optimization*): the
-pose-only optimisation Tracking runs between its searches, one kernel launch per call.  The other Optimizer functions are
-not covered.  The map-point table form is ``MapPoints.pose_optimization``."""
+pose-only optimisation Tracking runs between its searches, one kernel launch per call.  The map-point table form is
+``MapPoints.pose_optimization``.
+
+Optimizer::OptimizeSim3 (src/Optimizer.cc:1116-1323; orbfe_optimize_sim3*): the Sim3 refinement LoopClosing::ComputeSim3
+runs on a loop candidate after Sim3Solver and SearchBySim3, one kernel launch for all candidates of a call.  The other
+Optimizer functions are not covered."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import PoseOptStatsC, check, ptr
+from ._lib import OptSim3StatsC, PoseOptStatsC, check, ptr
 
 
 def stats_dict(st: PoseOptStatsC) -> dict:
@@ -73,3 +77,86 @@ def pose_optimization_batch(offsets, xw, u, v, u_right, inv_sigma2, K5, Tcw, out
     check(_lib.load().orbfe_pose_optimization_batch(int(device), Q, ptr(off), ptr(xw), ptr(u), ptr(v), ptr(ur), ptr(w), ptr(k),
                                                     ptr(T), ptr(out), ptr(flags), ptr(ni), C.cast(st, C.c_void_p), ptr(chi2)))
     return ni[:Q], out[:16 * Q].reshape(Q, 4, 4), flags[:n], [stats_dict(st[p]) for p in range(Q)], chi2[:n]
+
+
+def optsim3_stats_dict(st: OptSim3StatsC) -> dict:
+    r = st.rounds
+    return dict(rounds=r, n_bad=st.n_bad, iterations=list(st.iterations)[:r], trials=list(st.trials)[:r], lam=list(st.lam)[:r],
+                chi2=list(st.chi2)[:r])
+
+
+def sim3_to_Rts(sim3_out):
+    """sim3_out = (qx, qy, qz, qw, tx, ty, tz, s), g2o::Sim3's own members -> (R [3, 3], t [3], s) in float64: the
+    rotation().toRotationMatrix(), translation() and scale() that LoopClosing reads of g2oS12 (src/LoopClosing.cc:393-396)
+    and that SearchByProjection / Sim3Solver users hold.  The quaternion is used as it is, as Eigen does (not normalised)."""
+    x, y, z, w, tx, ty, tz, s = [float(c) for c in np.asarray(sim3_out, np.float64).reshape(8)]
+    t2x, t2y, t2z = 2.0 * x, 2.0 * y, 2.0 * z
+    twx, twy, twz = t2x * w, t2y * w, t2z * w
+    txx, txy, txz = t2x * x, t2y * x, t2z * x
+    tyy, tyz, tzz = t2y * y, t2z * y, t2z * z
+    R = np.array([[1.0 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1.0 - (txx + tzz), tyz - twx],
+                  [txz - twy, tyz + twx, 1.0 - (txx + tyy)]])
+    return R, np.array([tx, ty, tz]), s
+
+
+def _pairs(x3dc1, x3dc2, obs1, obs2, inv_sigma2_1, inv_sigma2_2):
+    x1 = np.ascontiguousarray(x3dc1, dtype=np.float32).reshape(-1, 3)
+    n = len(x1)
+    out = [x1]
+    for a, k in ((x3dc2, 3), (obs1, 2), (obs2, 2), (inv_sigma2_1, 1), (inv_sigma2_2, 1)):
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        if len(a) != k * n:
+            raise ValueError("optimize_sim3: the arrays must hold one entry per pair")
+        out.append(a)
+    return out
+
+
+def optimize_sim3(x3dc1, x3dc2, obs1, obs2, inv_sigma2_1, inv_sigma2_2, cam1, cam2, sim3_in, th2=10.0, fix_scale=False,
+                  device: int = 0):
+    """One loop candidate: x3dc1 / x3dc2 [n, 3] (the matched map points in camera 1 / camera 2), obs1 / obs2 [n, 2], the two
+    inv_sigma2 [n], cam1 / cam2 = (fx, fy, cx, cy), sim3_in [13] = R row-major, t, s (what Sim3Solver hands over) ->
+    (n_in, sim3_out [8] float64 = qx qy qz qw tx ty tz s, bad [n] uint8 (0 kept, 1 / 2 erased after round one / two), stats
+    dict, chi2_12 [n], chi2_21 [n] float64).  n_in = 0 with rounds < 2 is the reference's early return: sim3_out is the
+    incoming S12 and the erasures of round one stay."""
+    x1, x2, o1, o2, w1, w2 = _pairs(x3dc1, x3dc2, obs1, obs2, inv_sigma2_1, inv_sigma2_2)
+    n = len(x1)
+    k1 = np.ascontiguousarray(cam1, dtype=np.float32).reshape(4)
+    k2 = np.ascontiguousarray(cam2, dtype=np.float32).reshape(4)
+    s_in = np.ascontiguousarray(sim3_in, dtype=np.float32).reshape(13)
+    out = np.zeros(8, np.float64)
+    bad = np.zeros(max(n, 1), np.uint8)
+    c12, c21 = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+    ni, st = C.c_int32(0), OptSim3StatsC()
+    check(_lib.load().orbfe_optimize_sim3(int(device), n, ptr(x1), ptr(x2), ptr(o1), ptr(o2), ptr(w1), ptr(w2), ptr(k1), ptr(k2),
+                                          ptr(s_in), float(th2), int(bool(fix_scale)), ptr(out), ptr(bad), C.byref(ni),
+                                          C.byref(st), ptr(c12), ptr(c21)))
+    return ni.value, out, bad[:n], optsim3_stats_dict(st), c12[:n], c21[:n]
+
+
+def optimize_sim3_multi(pair_off, x3dc1, x3dc2, obs1, obs2, inv_sigma2_1, inv_sigma2_2, cam1, cam2, sim3_in, th2, fix_scale,
+                        device: int = 0):
+    """K candidates in one launch: candidate p owns pairs [pair_off[p], pair_off[p + 1]); cam1 / cam2 [K, 4], sim3_in [K, 13],
+    th2 [K], fix_scale [K] -> (n_in [K], sim3_out [K, 8], bad [N], list of stats dicts, chi2_12 [N], chi2_21 [N]).  Equal to K
+    single calls, bit for bit."""
+    off = np.ascontiguousarray(pair_off, dtype=np.int32).reshape(-1)
+    K = len(off) - 1
+    x1, x2, o1, o2, w1, w2 = _pairs(x3dc1, x3dc2, obs1, obs2, inv_sigma2_1, inv_sigma2_2)
+    n = len(x1)
+    if K < 0 or off[-1] != n:
+        raise ValueError("optimize_sim3_multi: pair_off must end at the pair count")
+    k1 = np.ascontiguousarray(cam1, dtype=np.float32).reshape(-1)
+    k2 = np.ascontiguousarray(cam2, dtype=np.float32).reshape(-1)
+    s_in = np.ascontiguousarray(sim3_in, dtype=np.float32).reshape(-1)
+    t2 = np.ascontiguousarray(th2, dtype=np.float32).reshape(-1)
+    fix = np.ascontiguousarray(np.asarray(fix_scale).astype(bool), dtype=np.uint8).reshape(-1)
+    if len(k1) != 4 * K or len(k2) != 4 * K or len(s_in) != 13 * K or len(t2) != K or len(fix) != K:
+        raise ValueError("optimize_sim3_multi: cam1 / cam2 / sim3_in / th2 / fix_scale must hold one entry per problem")
+    out = np.zeros(max(8 * K, 1), np.float64)
+    bad = np.zeros(max(n, 1), np.uint8)
+    c12, c21 = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+    ni = np.zeros(max(K, 1), np.int32)
+    st = (OptSim3StatsC * max(K, 1))()
+    check(_lib.load().orbfe_optimize_sim3_multi(int(device), K, ptr(off), ptr(x1), ptr(x2), ptr(o1), ptr(o2), ptr(w1), ptr(w2),
+                                                ptr(k1), ptr(k2), ptr(s_in), ptr(t2), ptr(fix), ptr(out), ptr(bad), ptr(ni),
+                                                C.cast(st, C.c_void_p), ptr(c12), ptr(c21)))
+    return ni[:K], out[:8 * K].reshape(K, 8), bad[:n], [optsim3_stats_dict(st[p]) for p in range(K)], c12[:n], c21[:n]
