@@ -859,6 +859,62 @@ int orbfe_sim3_triples_from_draws(int n, int n_hypotheses, const int32_t *draws 
 int orbfe_sim3_max_iterations(int n, double prob, int min_inliers, int max_its);
 
 /* -------------------------------------------------------------------------- */
+/* Initializer::FindHomography / FindFundamental (src/Initializer.cc:141-255)  */
+/* -------------------------------------------------------------------------- */
+/* The RANSAC of monocular map initialisation, the step after SearchForInitialization in Tracking::MonocularInitialization:
+ * EVERY hypothesis of BOTH models of EVERY problem in ONE kernel launch, one wave per (set, model).  A hypothesis is the
+ * normalised 8-point DLT of ComputeH21 (:260-305) or ComputeF21 (:307-345, with the rank-2 step) on the 8 pairs of a set,
+ * un-normalised (:187-188, :244), followed by CheckHomography (:350-436) or CheckFundamental (:444-526) over all pairs of its
+ * problem.  Hypotheses are independent; the order-dependent part (`currentScore > score`, :192, :248) is a scan over the
+ * scores that the caller replays on the host (include/orbfe_initializer_replay.hpp, C++ orbfe_cpp::Initializer, Python
+ * Initializer).
+ * Problem k owns pairs [pair_off[k], pair_off[k+1]) of pairs[4 i ..] = u1 v1 u2 v2 (mvKeys1[mvMatches12[i].first].pt,
+ * mvKeys2[mvMatches12[i].second].pt), T1[4 k ..] / T2[4 k ..] = sX sY meanX meanY of Normalize over ALL keys of frame 1 / 2
+ * (orbfe_initializer_normalize), sigma[k] = mSigma and sets [hyp_off[k], hyp_off[k+1]); sets[8 h ..] are the 8 pairs of set h
+ * (mvSets[h]) as indices LOCAL to its problem's pairs.  Both models use the same sets.
+ * Arithmetic is binary64 on inputs widened from float, in a fixed order, so equal inputs give equal bytes.  The null vector
+ * of the 16 x 9 / 8 x 9 matrix comes from a one-sided (Hestenes) Jacobi iteration on its columns (pair order (0,1) ... (7,8),
+ * at most 30 sweeps, a rotation skipped when |a_p . a_q| <= DBL_EPSILON |a_p| |a_q|); it is the column of V under the column
+ * of the smallest norm.  The reference computes in CV_32F with cv::SVDecomp: results agree with it to float rounding and are
+ * NOT bit-identical to it; a pair within float rounding of a threshold may fall on the other side.  Kept as the reference
+ * has them: cv::Mat::inv() of a singular H21 is the zero matrix, every chi-square is then NaN, takes the else branch of
+ * `if (chi > th)` and makes the score NaN.
+ * Outputs per (set h, model m), m = ORBFE_INIT_MODEL_H or _F, at index g = 2 h + m: score[g] (the float score of the
+ * reference, in binary64); status[g] = ORBFE_INIT_OK, or ORBFE_INIT_NONFINITE when the score or an entry of the model (or of
+ * H12) is not finite (n_inliers 0 and all mask words 0 then; score and model stored as they came out: `score > best` is false
+ * for it); n_inliers[g]; model[9 g ..] = H21 or F21 row-major; h12[9 h ..] = H12 of set h; its ceil(n_k / 32) mask words at
+ * mask_words[word_off[k] + (2 (h - hyp_off[k]) + m) * ceil(n_k / 32)], pair i of the problem at bit i & 31 of word i >> 5.
+ * word_off [K + 1] is written by the call; mask_words must hold sum_k 2 H_k ceil(n_k / 32) words.
+ * Returns ORBFE_ERR_INVALID before anything is enqueued, leaving the thread usable, for: NULL arrays, offsets that do not
+ * start at 0, decrease, or do not end at n_pairs / n_sets, a set index outside [0, n_k), a set that repeats an index, a
+ * problem with n_k < 8 that has sets, an entry of T1 / T2 or a sigma that is not finite, sigma <= 0, n_problems outside
+ * [0, 4096], more than 2^24 sets.  A problem without pairs and sets is legal; a call without any set returns ORBFE_OK with
+ * word_off written and no launch.  Runs on the calling thread's matcher stream and is complete on return. */
+enum { ORBFE_INIT_OK = 0, ORBFE_INIT_NONFINITE = 1 };
+enum { ORBFE_INIT_MODEL_H = 0, ORBFE_INIT_MODEL_F = 1 };
+
+int orbfe_initializer_ransac_multi(int device, int n_problems, int n_pairs, int n_sets, const int32_t *pair_off /*[K+1]*/,
+                                   const float *pairs /*[N*4]*/, const double *T1 /*[K*4]*/, const double *T2 /*[K*4]*/,
+                                   const float *sigma /*[K]*/, const int32_t *hyp_off /*[K+1]*/, const int32_t *sets /*[H*8]*/,
+                                   double *score /*[H*2]*/, uint8_t *status /*[H*2]*/, int32_t *n_inliers /*[H*2]*/,
+                                   double *model /*[H*2*9]*/, double *h12 /*[H*9]*/, uint32_t *mask_words,
+                                   int32_t *word_off /*[K+1]*/);
+/* One problem; equal to the multi form with n_problems = 1.  mask_words [H * 2 * ceil(n / 32)]. */
+int orbfe_initializer_ransac(int device, int n_pairs, const float *pairs, const double *T1 /*[4]*/, const double *T2 /*[4]*/,
+                             float sigma, int n_sets, const int32_t *sets, double *score, uint8_t *status, int32_t *n_inliers,
+                             double *model, double *h12, uint32_t *mask_words);
+/* Initializer::Normalize (:852-904) over ALL n_keys undistorted keys of a frame (keys_xy = x y interleaved), as :149-150
+ * call it -- not only the matched ones -> T = sX sY meanX meanY.  Host code, binary64, sequential sums in index order (the
+ * reference sums in float).  n_keys <= 0 or a NULL array return ORBFE_ERR_INVALID. */
+int orbfe_initializer_normalize(int n_keys, const float *keys_xy /*[n*2]*/, double *T /*[4]*/);
+/* The selection without replacement of Initializer::Initialize (:93-108), no device involved: draws[8 h + j] is the value
+ * RandomInt(0, vAvailableIndices.size() - 1) returned for pick j of set h, in [0, n - j) -- an index INTO the list of still
+ * available pairs, which starts as 0 .. n-1 for every set and loses the pair taken by swap-with-back and pop -> sets[8 h + j]
+ * the pair taken.  A caller who feeds the reference's DUtils::Random::RandomInt stream gets the reference's mvSets; the
+ * library does not restate rand().  n < 8 with sets, NULL arrays or a draw outside its range return ORBFE_ERR_INVALID. */
+int orbfe_initializer_sets_from_draws(int n, int n_sets, const int32_t *draws /*[H*8]*/, int32_t *sets /*[H*8]*/);
+
+/* -------------------------------------------------------------------------- */
 /* Optimizer::OptimizeSim3 (src/Optimizer.cc:1116-1323)                        */
 /* -------------------------------------------------------------------------- */
 /* The Sim3 refinement LoopClosing::ComputeSim3 runs on every candidate that survives Sim3Solver and SearchBySim3

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "orbfe.h"
+#include "orbfe_initializer_replay.hpp"
 #include "orbfe_sim3_replay.hpp"
 
 namespace orbfe_cpp {
@@ -949,6 +950,78 @@ class Sim3Solver {
     if (!hasBest_) throw std::logic_error("Sim3Solver: no hypothesis has been taken yet");
     return best_;
   }
+};
+
+// Initializer (src/Initializer.cc) up to the choice of the model.  keys1 = the reference frame's mvKeysUn points (x y
+// interleaved), sigma and iterations as the reference's constructor takes them (:36-43).  FindModels does what Initialize does
+// from :57 to :127: compacts vMatches12 into mvMatches12 (:64-73), builds mvSets from the caller's RandomInt values (draws
+// [iterations * 8], draws[8 h + j] in [0, N - j); :93-108), evaluates every hypothesis of both models in ONE device call
+// (orbfe_initializer_ransac) and replays the two scans (InitializerReplay, orbfe_initializer_replay.hpp).  The caller then
+// runs its own unchanged ReconstructH / ReconstructF on H21 / vbMatchesInliersH or F21 / vbMatchesInliersF.
+class Initializer {
+ public:
+  struct Models {
+    double H21[9] = {}, F21[9] = {};   // row-major; meaningful when bestH / bestF >= 0
+    int bestH = -1, bestF = -1;        // the hypothesis each scan took, -1: none scored above 0 (an empty cv::Mat)
+    double SH = 0.0, SF = 0.0, RH = 0.0;
+    bool chooseH = false;              // RH > 0.40 (:127)
+    std::vector<bool> vbMatchesInliersH, vbMatchesInliersF;  // indexed like mvMatches12
+    std::vector<std::pair<int, int>> mvMatches12;
+    std::vector<int32_t> mvSets;       // [iterations * 8]
+    // per (set, model), the layout of orbfe_initializer_ransac
+    std::vector<double> score, model, h12;
+    std::vector<uint8_t> status;
+    std::vector<int32_t> nInliers;
+    std::vector<uint32_t> words;
+  };
+
+  Initializer(const std::vector<float>& keys1, float sigma = 1.0f, int iterations = 200, int device = 0)
+      : keys1_(keys1), sigma_(sigma), iterations_(iterations), device_(device) {
+    if (keys1.size() % 2) throw std::invalid_argument("Initializer: keys1 holds x y pairs");
+    if (!keys1.empty()) check(orbfe_initializer_normalize((int)(keys1.size() / 2), keys1.data(), T1_), "Initializer");
+  }
+
+  Models FindModels(const std::vector<float>& keys2, const std::vector<int>& vMatches12, const std::vector<int32_t>& draws) const {
+    if (keys2.size() % 2 || vMatches12.size() != keys1_.size() / 2)
+      throw std::invalid_argument("Initializer::FindModels: keys2 holds x y pairs, vMatches12 one entry per reference key");
+    if (draws.size() != (size_t)iterations_ * 8) throw std::invalid_argument("Initializer::FindModels: draws holds iterations * 8 values");
+    Models m;
+    std::vector<float> pairs;
+    for (size_t i = 0; i < vMatches12.size(); i++)  // :64-73
+      if (vMatches12[i] >= 0) {
+        if ((size_t)vMatches12[i] >= keys2.size() / 2) throw std::invalid_argument("Initializer::FindModels: a match outside keys2");
+        m.mvMatches12.emplace_back((int)i, vMatches12[i]);
+        pairs.insert(pairs.end(), {keys1_[2 * i], keys1_[2 * i + 1], keys2[2 * (size_t)vMatches12[i]], keys2[2 * (size_t)vMatches12[i] + 1]});
+      }
+    const int N = (int)m.mvMatches12.size(), H = iterations_;
+    m.mvSets.assign((size_t)H * 8, 0);
+    check(orbfe_initializer_sets_from_draws(N, H, draws.data(), m.mvSets.data()), "Initializer::FindModels");
+    double T2[4];
+    check(orbfe_initializer_normalize((int)(keys2.size() / 2), keys2.data(), T2), "Initializer::FindModels");  // :150: all keys
+    const size_t w = (size_t)((N + 31) / 32);
+    m.score.assign((size_t)H * 2, 0.0); m.model.assign((size_t)H * 18, 0.0); m.h12.assign((size_t)H * 9, 0.0);
+    m.status.assign((size_t)H * 2, 0); m.nInliers.assign((size_t)H * 2, 0); m.words.assign((size_t)H * 2 * w + 1, 0u);
+    check(orbfe_initializer_ransac(device_, N, pairs.data(), T1_, T2, sigma_, H, m.mvSets.data(), m.score.data(), m.status.data(),
+                                   m.nInliers.data(), m.model.data(), m.h12.data(), m.words.data()),
+          "Initializer::FindModels");
+    m.words.resize((size_t)H * 2 * w);
+    const InitializerReplay::Pick pH = InitializerReplay::scan(H, ORBFE_INIT_MODEL_H, m.score.data());
+    const InitializerReplay::Pick pF = InitializerReplay::scan(H, ORBFE_INIT_MODEL_F, m.score.data());
+    m.bestH = pH.best; m.SH = pH.score; m.bestF = pF.best; m.SF = pF.score;
+    if (pH.best >= 0) std::memcpy(m.H21, &m.model[9 * (2 * (size_t)pH.best + ORBFE_INIT_MODEL_H)], sizeof m.H21);
+    if (pF.best >= 0) std::memcpy(m.F21, &m.model[9 * (2 * (size_t)pF.best + ORBFE_INIT_MODEL_F)], sizeof m.F21);
+    InitializerReplay::inliers(N, pH.best, ORBFE_INIT_MODEL_H, m.words.data(), m.vbMatchesInliersH);
+    InitializerReplay::inliers(N, pF.best, ORBFE_INIT_MODEL_F, m.words.data(), m.vbMatchesInliersF);
+    m.RH = InitializerReplay::ratio(m.SH, m.SF);  // :124
+    m.chooseH = InitializerReplay::choose_h(m.RH);
+    return m;
+  }
+
+ private:
+  std::vector<float> keys1_;
+  float sigma_;
+  int iterations_, device_;
+  double T1_[4] = {1.0, 1.0, 0.0, 0.0};
 };
 
 // void Frame::ComputeStereoMatches(): fills mvuRight / mvDepth

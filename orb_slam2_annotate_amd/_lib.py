@@ -103,6 +103,7 @@ EXPORTS = [
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_multi",
     "orbfe_sim3_ransac", "orbfe_sim3_ransac_multi", "orbfe_sim3_triples_from_draws", "orbfe_sim3_max_iterations",
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_multi",
+    "orbfe_initializer_ransac", "orbfe_initializer_ransac_multi", "orbfe_initializer_normalize", "orbfe_initializer_sets_from_draws",
 ]
 
 _lib = None
@@ -282,6 +283,10 @@ def load():
     L.orbfe_sim3_ransac.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     L.orbfe_sim3_triples_from_draws.argtypes = [ci, ci, vp, vp]
     L.orbfe_sim3_max_iterations.argtypes = [ci, C.c_double, ci, ci]
+    L.orbfe_initializer_ransac_multi.argtypes = [ci, ci, ci, ci] + [vp] * 14
+    L.orbfe_initializer_ransac.argtypes = [ci, ci, vp, vp, vp, C.c_float, ci] + [vp] * 7
+    L.orbfe_initializer_normalize.argtypes = [ci, vp, vp]
+    L.orbfe_initializer_sets_from_draws.argtypes = [ci, ci, vp, vp]
     _lib = L
     return L
 

@@ -1,0 +1,128 @@
+// initializer_host.h -- the host side of orbfe_initializer_ransac* (initializer.hip) that needs no device: the argument
+// checks, the layout of a call (problem records, the problem of every set, the mask-word offsets) and the two pure host
+// functions orbfe_initializer_normalize / orbfe_initializer_sets_from_draws.  Plain C++ without a HIP include, so
+// tests/cpp/initializer_host_san.cpp runs exactly this code under the address and undefined-behaviour sanitizers.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "initializer_math.h"
+
+namespace orbfe {
+
+constexpr int kInitHostMaxProblems = 4096;
+constexpr int kInitHostMaxSets = 1 << 24;  // 2 waves per set: the launch stays far below 2^31 waves
+
+inline bool init_offsets_ok(const int32_t* off, int K, int total) {
+  if (off[0] != 0 || off[K] != total) return false;
+  for (int k = 0; k < K; k++)
+    if (off[k + 1] < off[k]) return false;
+  return true;
+}
+
+// NULL when the arguments are fine, else what is wrong with them.  N pairs and H sets in all.
+inline const char* init_check(int K, int N, int H, const int32_t* pair_off, const float* pairs, const double* T1, const double* T2,
+                              const float* sigma, const int32_t* hyp_off, const int32_t* sets, const double* score,
+                              const uint8_t* status, const int32_t* n_inliers, const double* model, const double* h12,
+                              const uint32_t* mask_words, const int32_t* word_off) {
+  if (K < 0 || K > kInitHostMaxProblems) return "n_problems outside [0, 4096]";
+  if (N < 0 || H < 0) return "negative count";
+  if (H > kInitHostMaxSets) return "more than 2^24 sets";
+  if (!pair_off || !hyp_off || !word_off) return "NULL offsets";
+  if (K > 0 && (!T1 || !T2 || !sigma)) return "NULL T1 / T2 / sigma";
+  if (N > 0 && !pairs) return "NULL pair array";
+  if (H > 0 && (!sets || !score || !status || !n_inliers || !model || !h12 || !mask_words)) return "NULL set or output array";
+  if (!init_offsets_ok(pair_off, K, N)) return "pair_off is not monotone from 0 to n_pairs";
+  if (!init_offsets_ok(hyp_off, K, H)) return "hyp_off is not monotone from 0 to n_sets";
+  size_t words = 0;
+  for (int k = 0; k < K; k++) {
+    for (int i = 0; i < 4; i++)
+      if (!isfinite(T1[4 * k + i]) || !isfinite(T2[4 * k + i])) return "T1 / T2 entry is not finite";
+    if (!isfinite(sigma[k]) || !(sigma[k] > 0.0f)) return "sigma is not positive and finite";
+    const int n = pair_off[k + 1] - pair_off[k], h0 = hyp_off[k], h1 = hyp_off[k + 1];
+    if (h1 > h0 && n < 8) return "a problem with fewer than 8 pairs has sets";
+    for (int h = h0; h < h1; h++) {
+      const int32_t* s = sets + 8 * (size_t)h;
+      for (int j = 0; j < 8; j++) {
+        if (s[j] < 0 || s[j] >= n) return "set index outside [0, n_k)";
+        for (int i = 0; i < j; i++)
+          if (s[i] == s[j]) return "set repeats an index";
+      }
+    }
+    words += 2 * (size_t)(h1 - h0) * (size_t)((n + 31) / 32);
+    if (words > (size_t)INT32_MAX) return "more than 2^31 - 1 mask words";
+  }
+  return nullptr;
+}
+
+// the arguments have passed init_check: word_off [K + 1], the problem records and the problem of every set
+inline void init_layout(int K, const int32_t* pair_off, const int32_t* hyp_off, const double* T1, const double* T2,
+                        const float* sigma, int32_t* word_off, std::vector<InitProblem>* probs, std::vector<int32_t>* hypProb) {
+  probs->clear();
+  hypProb->clear();
+  word_off[0] = 0;
+  for (int k = 0; k < K; k++) {
+    InitProblem p = {};
+    p.pair0 = pair_off[k]; p.nPairs = pair_off[k + 1] - pair_off[k];
+    p.hyp0 = hyp_off[k];
+    p.word0 = word_off[k]; p.words = (p.nPairs + 31) / 32;
+    p.sigma = sigma[k];
+    for (int i = 0; i < 4; i++) { p.T1[i] = T1[4 * k + i]; p.T2[i] = T2[4 * k + i]; }
+    probs->push_back(p);
+    const int h = hyp_off[k + 1] - hyp_off[k];
+    hypProb->insert(hypProb->end(), (size_t)h, k);
+    word_off[k + 1] = word_off[k] + 2 * h * p.words;
+  }
+}
+
+// Initializer::Normalize (src/Initializer.cc:852-904) over n keys (x y interleaved) -> T = sX sY meanX meanY, in binary64
+// with sequential sums in index order (the reference sums in float).  false: n <= 0 or a NULL array.
+inline bool init_normalize(int n, const float* xy, double T[4]) {
+  if (n <= 0 || !xy || !T) return false;
+  double meanX = 0.0, meanY = 0.0;
+  for (int i = 0; i < n; i++) { meanX += (double)xy[2 * (size_t)i]; meanY += (double)xy[2 * (size_t)i + 1]; }  // :861-865
+  meanX = meanX / n; meanY = meanY / n;  // :867-868
+  double meanDevX = 0.0, meanDevY = 0.0;
+  for (int i = 0; i < n; i++) {  // :876-883
+    meanDevX += fabs((double)xy[2 * (size_t)i] - meanX);
+    meanDevY += fabs((double)xy[2 * (size_t)i + 1] - meanY);
+  }
+  meanDevX = meanDevX / n; meanDevY = meanDevY / n;  // :885-886
+  T[0] = 1.0 / meanDevX; T[1] = 1.0 / meanDevY;       // :889-890
+  T[2] = meanX; T[3] = meanY;
+  return true;
+}
+
+// The selection without replacement of Initializer::Initialize (:93-108) for H sets over n pairs: draws[8 h + j] is the value
+// RandomInt(0, vAvailableIndices.size() - 1) returned (:100) with size = n - j, the index INTO the list of still available
+// pairs; the pair taken leaves the list by swap-with-back and pop (:105-106).  The list starts as 0 .. n-1 for every set (:95).
+// The random stream itself is the caller's.  false: n < 8 with sets, a NULL array or a draw outside [0, n - j); sets is then
+// unspecified.
+inline bool init_sets_from_draws(int n, int H, const int32_t* draws, int32_t* sets) {
+  if (H == 0) return n >= 0;
+  if (n < 8 || H < 0 || !draws || !sets) return false;
+  std::vector<int32_t> avail((size_t)n);
+  for (int i = 0; i < n; i++) avail[i] = i;
+  for (int h = 0; h < H; h++) {
+    int32_t at[8], was[8];
+    int size = n, done = 0;
+    bool ok = true;
+    for (int j = 0; j < 8; j++) {
+      const int32_t r = draws[8 * (size_t)h + j];
+      ok = r >= 0 && r < size;
+      if (!ok) break;
+      sets[8 * (size_t)h + j] = avail[r];  // :101-103
+      at[done] = r; was[done] = avail[r]; done++;
+      avail[r] = avail[size - 1];          // :105
+      size--;                              // :106
+    }
+    for (int i = done - 1; i >= 0; i--) avail[at[i]] = was[i];  // the list of the next set is whole again (:95)
+    if (!ok) return false;
+  }
+  return true;
+}
+
+}  // namespace orbfe
