@@ -948,6 +948,71 @@ int orbfe_optimize_sim3(int device, int n, const float *x3dc1, const float *x3dc
                         const float sim3_in[13], float th2, int fix_scale, double sim3_out[8], uint8_t *bad, int32_t *n_in,
                         orbfe_optsim3_stats *stats, double *chi2_12, double *chi2_21);
 
+/* -------------------------------------------------------------------------- */
+/* Optimizer::LocalBundleAdjustment (src/Optimizer.cc:483-814), BundleAdjustment (:54-253) */
+/* -------------------------------------------------------------------------- */
+/* The bundle adjustment LocalMapping runs per key frame, from :538 on: the caller walks the map graph (:485-536) and hands
+ * over the key-frame poses -- the n_local local ones first (optimised unless local_is_fixed[j], i.e. mnId == 0), then the
+ * n_fixed ones that only observe local points --, their fx fy cx cy bf, the local points and one edge per observation
+ * (u, v = mvKeysUn[idx].pt, u_right = mvuRight[idx] (< 0: a monocular EdgeSE3ProjectXYZ, information inv_sigma2 I2, Huber
+ * delta sqrt(5.991); else an EdgeStereoSE3ProjectXYZ, inv_sigma2 I3, sqrt(7.815)), inv_sigma2 = mvInvLevelSigma2[octave]).
+ * Edges are grouped by point (edge_point non-decreasing), in the order the reference adds them.  The call runs optimize(5)
+ * with the Huber kernels, the first classification (chi2 > 5.991 / 7.815 or depth not positive: level 1; every kernel off),
+ * optimize(10) on the level-0 edges and the final classification; g2o's Levenberg loop runs on the host and reads one small
+ * record per linearisation and per trial, the passes (linearisation, Schur complement of the points, dense Cholesky of the
+ * reduced camera system, back-substitution, errors) are kernels.  Arithmetic is binary64 on inputs widened from float; every
+ * sum has a fixed order, so two calls return the same bits.  As in the reference a classification reads the chi2
+ * of the last pass the edge was active in -- the last Levenberg trial, accepted or not; for a level-1 edge its round-one
+ * value -- while isDepthPositive() is evaluated at the final estimates.
+ * Outputs: Tcw_out = SE3Quat::to_homogeneous_matrix of every local pose (a local_is_fixed one: its input through
+ * Converter::toSE3Quat); xw_out; erase[e] = 0 kept, 1 in vToErase and level 1 after round one, 2 in vToErase by the final
+ * test only (nonzero <=> the reference puts the pair into vToErase; an edge that was level 1 but passes the final test --
+ * possible only when its depth turned positive -- is 0); level1[e] (may be NULL) = at level 1 after round one;
+ * edge_chi2[e] (may be NULL) what the final test read.  EraseMapPointMatch / EraseObservation, SetPose, SetWorldPos,
+ * UpdateNormalAndDepth and the map mutex stay with the caller.
+ * stop_flag (may be NULL) is pbStopFlag, polled where the reference polls it: up at entry, the call returns with
+ * stats->stopped = 1 and the outputs equal to the converted inputs, erase[] zero; up later, the running optimize() ends
+ * and, when up at :698, round two and the first classification are skipped.
+ * stats (may be NULL): per round iterations, trials, the final lambda, the robust chi2 of the estimate and why optimize()
+ * ended (0 never ran / no active edge, 1 iteration count, 2 ten trials, 3 rho == 0, 4 the nBad >= 3 rule, 5 stop flag).
+ * Returns ORBFE_ERR_INVALID before anything is enqueued for: NULL arrays, n_local < 1, more than 256 local key frames, an
+ * index out of range, free poses x points above 16777216, edges not grouped by point, a non-finite input, a point or a free pose without any edge, two edges
+ * between the same pose and point.  Runs on the calling thread's matcher stream and is complete on return. */
+typedef struct orbfe_lba_stats {
+  int32_t rounds, stopped, host_syncs, n_level1;
+  int32_t iterations[2], trials[2], termination[2];
+  double lambda[2], chi2[2];
+} orbfe_lba_stats;
+int orbfe_local_bundle_adjustment(int device, int n_local, int n_fixed, const float *Tcw /*[n_local+n_fixed,16], local first*/,
+                                  const uint8_t *local_is_fixed /*[n_local]; may be NULL*/,
+                                  const float *cam /*[n_local+n_fixed,5]: fx fy cx cy bf*/, int n_points, const float *xw /*[n_points,3]*/,
+                                  int n_edges, const int32_t *edge_pose, const int32_t *edge_point /*non-decreasing*/,
+                                  const float *u, const float *v, const float *u_right /*<0: monocular*/, const float *inv_sigma2,
+                                  const volatile int *stop_flag /*may be NULL*/, double *Tcw_out /*[n_local,16]*/,
+                                  double *xw_out /*[n_points,3]*/, uint8_t *erase /*[n_edges]*/, uint8_t *level1 /*[n_edges]; may be NULL*/,
+                                  orbfe_lba_stats *stats, double *edge_chi2 /*[n_edges]; may be NULL*/);
+/* Optimizer::BundleAdjustment (:54-253) on the same operands (every key frame is local, fixed when mnId == 0; fixed ones may
+ * still be appended): ONE optimize(n_iterations), Huber kernels when robust != 0, no classification, so there is no
+ * erase[].  stop_flag is polled before every iteration and inside the trial loop.  stats->...[1] stay 0. */
+int orbfe_bundle_adjustment(int device, int n_local, int n_fixed, const float *Tcw, const uint8_t *local_is_fixed, const float *cam,
+                            int n_points, const float *xw, int n_edges, const int32_t *edge_pose, const int32_t *edge_point,
+                            const float *u, const float *v, const float *u_right, const float *inv_sigma2, int n_iterations,
+                            int robust, const volatile int *stop_flag, double *Tcw_out, double *xw_out, orbfe_lba_stats *stats,
+                            double *edge_chi2 /*may be NULL*/);
+/* orbfe_local_bundle_adjustment with the points in a resident table: point p is slot[p] (distinct slots); its position is
+ * gathered from the table on the device and the optimised position written back to the same slot as a float (SetWorldPos),
+ * so only poses, slots, edges and flags travel.  Normal and distance range are the caller's UpdateNormalAndDepth, written
+ * through orbfe_mappoints_update.  xw_out may be NULL.  Every output is bit-equal to the array form on the table's floats.
+ * When the flag is up at entry the table is left as it is and xw_out is not written.  The table's lock is held for the whole
+ * call (every Levenberg trial synchronises with the host), so other calls on the same table wait for it.  Slots named twice
+ * are refused. */
+int orbfe_local_bundle_adjustment_mappoints(orbfe_mappoints *mp, int n_points, const int32_t *slot, int n_local, int n_fixed,
+                                            const float *Tcw, const uint8_t *local_is_fixed, const float *cam, int n_edges,
+                                            const int32_t *edge_pose, const int32_t *edge_point, const float *u, const float *v,
+                                            const float *u_right, const float *inv_sigma2, const volatile int *stop_flag,
+                                            double *Tcw_out, double *xw_out /*may be NULL*/, uint8_t *erase, uint8_t *level1,
+                                            orbfe_lba_stats *stats, double *edge_chi2);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th,
  * const bool bMono) (src/ORBmatcher.cc:1484-1633) after the caller's pose arithmetic: last-frame
  * point i is valid when it has a non-outlier map point with invzc >= 0 projecting to (u, v) inside

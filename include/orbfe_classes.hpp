@@ -685,8 +685,8 @@ class MapPointTable {
   orbfe_mappoints* h_ = nullptr;
 };
 
-// Optimizer::PoseOptimization (src/Optimizer.cc:256-473) and Optimizer::OptimizeSim3 (:1116-1323) on the device; the other
-// Optimizer functions are not covered.
+// Optimizer::PoseOptimization (src/Optimizer.cc:256-473), Optimizer::OptimizeSim3 (:1116-1323), Optimizer::LocalBundleAdjustment
+// (:483-814) and Optimizer::BundleAdjustment (:54-253) on the device; OptimizeEssentialGraph is not covered.
 // Both forms return nInitialCorrespondences - nBad, write the pose Frame::SetPose receives into Tcw (row-major 4 x 4) and
 // mvbOutlier of every edge; with fewer than 3 edges they return 0 and leave both alone.
 class Optimizer {
@@ -754,6 +754,59 @@ class Optimizer {
       for (int k = 0; k < 8; k++) S12[k] = out[k];
     if (stats) *stats = st;
     return nIn;
+  }
+  // What the map-graph walk of LocalBundleAdjustment (:485-536) or BundleAdjustment (:62-140) found, flattened: the nLocal
+  // local key frames first, then the fixed ones (Tcw row-major 4 x 4 floats, cam = fx fy cx cy mbf each); localIsFixed[j] =
+  // (mnId == 0), empty = none; the points; one edge per observation, grouped by point in the order the reference adds them
+  // (u, v = mvKeysUn[idx].pt, uRight = mvuRight[idx] (< 0: monocular), invSigma2 = mvInvLevelSigma2[octave])
+  struct BundleGraph {
+    int nLocal = 0;
+    std::vector<float> Tcw, cam;
+    std::vector<uint8_t> localIsFixed;
+    std::vector<float> Xw;
+    std::vector<int32_t> edgePose, edgePoint;
+    std::vector<float> u, v, uRight, invSigma2;
+    void validate(const char* who) const {
+      const size_t nT = Tcw.size() / 16, nE = edgePose.size();
+      if (nLocal < 0 || Tcw.size() != 16 * nT || (size_t)nLocal > nT || cam.size() != 5 * nT || Xw.size() % 3 != 0 ||
+          (!localIsFixed.empty() && localIsFixed.size() != (size_t)nLocal))
+        throw std::invalid_argument(std::string(who) + ": one Tcw and cam per key frame, one localIsFixed per local one");
+      if (edgePoint.size() != nE || u.size() != nE || v.size() != nE || uRight.size() != nE || invSigma2.size() != nE)
+        throw std::invalid_argument(std::string(who) + ": one entry per edge");
+    }
+  };
+  // LocalBundleAdjustment from :538 on.  Returns per edge whether the reference puts the pair into vToErase (the caller runs
+  // EraseMapPointMatch / EraseObservation under its map mutex); TcwOut [nLocal * 16] is what SetPose receives, XwOut
+  // [nPoints * 3] what SetWorldPos receives, both in double.  stats->stopped && stats->rounds == 0: the early return of :689
+  static std::vector<uint8_t> LocalBundleAdjustment(const BundleGraph& g, std::vector<double>& TcwOut, std::vector<double>& XwOut,
+                                                    const volatile int* pbStopFlag = nullptr, orbfe_lba_stats* stats = nullptr,
+                                                    int device = 0) {
+    g.validate("Optimizer::LocalBundleAdjustment");
+    const size_t nE = g.edgePose.size();
+    TcwOut.assign(16 * (size_t)g.nLocal + 1, 0.0);
+    XwOut.assign(g.Xw.size() + 1, 0.0);
+    std::vector<uint8_t> erase(nE ? nE : 1, 0);
+    check(orbfe_local_bundle_adjustment(device, g.nLocal, (int)(g.Tcw.size() / 16) - g.nLocal, g.Tcw.data(),
+                                        g.localIsFixed.empty() ? nullptr : g.localIsFixed.data(), g.cam.data(), (int)(g.Xw.size() / 3),
+                                        g.Xw.data(), (int)nE, g.edgePose.data(), g.edgePoint.data(), g.u.data(), g.v.data(),
+                                        g.uRight.data(), g.invSigma2.data(), pbStopFlag, TcwOut.data(), XwOut.data(), erase.data(),
+                                        nullptr, stats, nullptr), "LocalBundleAdjustment");
+    TcwOut.resize(16 * (size_t)g.nLocal); XwOut.resize(g.Xw.size()); erase.resize(nE);
+    return erase;
+  }
+  // BundleAdjustment: one optimize(nIterations), Huber kernels with bRobust, no classification
+  static void BundleAdjustment(const BundleGraph& g, std::vector<double>& TcwOut, std::vector<double>& XwOut, int nIterations = 5,
+                               const volatile int* pbStopFlag = nullptr, bool bRobust = true, orbfe_lba_stats* stats = nullptr,
+                               int device = 0) {
+    g.validate("Optimizer::BundleAdjustment");
+    TcwOut.assign(16 * (size_t)g.nLocal + 1, 0.0);
+    XwOut.assign(g.Xw.size() + 1, 0.0);
+    check(orbfe_bundle_adjustment(device, g.nLocal, (int)(g.Tcw.size() / 16) - g.nLocal, g.Tcw.data(),
+                                  g.localIsFixed.empty() ? nullptr : g.localIsFixed.data(), g.cam.data(), (int)(g.Xw.size() / 3), g.Xw.data(),
+                                  (int)g.edgePose.size(), g.edgePose.data(), g.edgePoint.data(), g.u.data(), g.v.data(), g.uRight.data(),
+                                  g.invSigma2.data(), nIterations, bRobust ? 1 : 0, pbStopFlag, TcwOut.data(), XwOut.data(), stats, nullptr),
+          "BundleAdjustment");
+    TcwOut.resize(16 * (size_t)g.nLocal); XwOut.resize(g.Xw.size());
   }
   // K candidates in one launch: pairOff [K + 1], K1 / K2 4 K floats, S12 8 K doubles, th2 and bFixScale one entry each; idx1
   // indexes the candidate's own vpMatches1[k].  Returns nIn of every candidate

@@ -53,6 +53,13 @@ class PoseOptStatsC(C.Structure):
                 ("lam", C.c_double * 4), ("chi2", C.c_double * 4)]
 
 
+class LbaStatsC(C.Structure):
+    """orbfe_lba_stats."""
+    _fields_ = [("rounds", C.c_int32), ("stopped", C.c_int32), ("host_syncs", C.c_int32), ("n_level1", C.c_int32),
+                ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("termination", C.c_int32 * 2),
+                ("lam", C.c_double * 2), ("chi2", C.c_double * 2)]
+
+
 class OptSim3StatsC(C.Structure):
     """orbfe_optsim3_stats."""
     _fields_ = [("rounds", C.c_int32), ("n_bad", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2),
@@ -103,6 +110,7 @@ EXPORTS = [
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_multi",
     "orbfe_sim3_ransac", "orbfe_sim3_ransac_multi", "orbfe_sim3_triples_from_draws", "orbfe_sim3_max_iterations",
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_multi",
+    "orbfe_local_bundle_adjustment", "orbfe_bundle_adjustment", "orbfe_local_bundle_adjustment_mappoints",
     "orbfe_initializer_ransac", "orbfe_initializer_ransac_multi", "orbfe_initializer_normalize", "orbfe_initializer_sets_from_draws",
 ]
 
@@ -279,6 +287,9 @@ def load():
     L.orbfe_triangulate_matches.argtypes = [ci, fwp, kcp, fwp, kcp, vp, vp, vp, ci, cf, vp, vp, vp]
     L.orbfe_sim3_ransac_multi.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_optimize_sim3_multi.argtypes = [ci, ci] + [vp] * 18
+    L.orbfe_local_bundle_adjustment.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, ci] + [vp] * 13
+    L.orbfe_bundle_adjustment.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, ci] + [vp] * 6 + [ci, ci] + [vp] * 5
+    L.orbfe_local_bundle_adjustment_mappoints.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci] + [vp] * 13
     L.orbfe_optimize_sim3.argtypes = [ci, ci] + [vp] * 9 + [C.c_float, ci] + [vp] * 6
     L.orbfe_sim3_ransac.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     L.orbfe_sim3_triples_from_draws.argtypes = [ci, ci, vp, vp]

@@ -136,3 +136,18 @@ class MapPoints:
         check(self._L.orbfe_pose_optimization_mappoints(h, len(s), ptr(s), C.byref(frame.c), ptr(m), ptr(lv), len(lv), ptr(k), ptr(T),
                                                         ptr(out), ptr(flags), C.byref(ni), C.byref(st), ptr(chi2)))
         return ni.value, out.reshape(4, 4), flags[:frame.N], stats_dict(st), chi2[:frame.N]
+
+    def local_bundle_adjustment(self, slot, n_local, Tcw, cam, edge_pose, edge_point, u, v, u_right, inv_sigma2,
+                                local_is_fixed=None, stop_flag=None):
+        """Optimizer::LocalBundleAdjustment with the local points in the table (orbfe_local_bundle_adjustment_mappoints):
+        point p of the edges is slot[p]; positions are read from and written back to the table on the device -> what
+        optimizer.local_bundle_adjustment returns, bit for bit.  Normal and distance range remain the caller's
+        UpdateNormalAndDepth, written through update()."""
+        from .optimizer import LbaOperands, _stop_ptr
+        s = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        o = LbaOperands(n_local, Tcw, cam, None, edge_pose, edge_point, u, v, u_right, inv_sigma2, local_is_fixed, n_points=len(s))
+        check(self._L.orbfe_local_bundle_adjustment_mappoints(self._h, len(s), ptr(s), o.n_local, o.n_fixed, ptr(o.T), o.fixed_ptr(),
+                                                              ptr(o.cam), *o.edges(), _stop_ptr(stop_flag), ptr(o.Tout), ptr(o.xout),
+                                                              ptr(o.erase), ptr(o.level1), C.cast(C.byref(o.st), C.c_void_p),
+                                                              ptr(o.chi2)))
+        return o.result()

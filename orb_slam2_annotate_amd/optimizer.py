@@ -3,8 +3,10 @@ pose-only optimisation Tracking runs between its searches, one kernel launch per
 ``MapPoints.pose_optimization``.
 
 Optimizer::OptimizeSim3 (src/Optimizer.cc:1116-1323; orbfe_optimize_sim3*): the Sim3 refinement LoopClosing::ComputeSim3
-runs on a loop candidate after Sim3Solver and SearchBySim3, one kernel launch for all candidates of a call.  The other
-Optimizer functions are not covered."""
+runs on a loop candidate after Sim3Solver and SearchBySim3, one kernel launch for all candidates of a call.
+Optimizer::LocalBundleAdjustment (:483-814; orbfe_local_bundle_adjustment*) and Optimizer::BundleAdjustment (:54-253;
+orbfe_bundle_adjustment): g2o's Levenberg loop on the host over kernels for the linearisation, the Schur complement of the
+points, the dense solve of the reduced camera system and the back-substitution.  OptimizeEssentialGraph is not covered."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import OptSim3StatsC, PoseOptStatsC, check, ptr
+from ._lib import LbaStatsC, OptSim3StatsC, PoseOptStatsC, check, ptr
 
 
 def stats_dict(st: PoseOptStatsC) -> dict:
@@ -160,3 +162,83 @@ def optimize_sim3_multi(pair_off, x3dc1, x3dc2, obs1, obs2, inv_sigma2_1, inv_si
                                                 ptr(k1), ptr(k2), ptr(s_in), ptr(t2), ptr(fix), ptr(out), ptr(bad), ptr(ni),
                                                 C.cast(st, C.c_void_p), ptr(c12), ptr(c21)))
     return ni[:K], out[:8 * K].reshape(K, 8), bad[:n], [optsim3_stats_dict(st[p]) for p in range(K)], c12[:n], c21[:n]
+
+
+LBA_TERMINATION = ("none", "iterations", "trials", "rho_zero", "no_progress", "stop")
+
+
+def lba_stats_dict(st: LbaStatsC) -> dict:
+    return dict(rounds=st.rounds, stopped=st.stopped, host_syncs=st.host_syncs, n_level1=st.n_level1,
+                iterations=list(st.iterations), trials=list(st.trials), termination=list(st.termination), lam=list(st.lam),
+                chi2=list(st.chi2))
+
+
+class LbaOperands:
+    """The operands of the bundle-adjustment calls as contiguous arrays of the C types: Tcw [n_local + n_fixed, 4, 4] (local
+    key frames first), cam [.., 5] = fx fy cx cy bf, xw [n_points, 3] (None in the table form), the edges grouped by point."""
+
+    def __init__(self, n_local, Tcw, cam, xw, edge_pose, edge_point, u, v, u_right, inv_sigma2, local_is_fixed, n_points=None):
+        self.T = np.ascontiguousarray(Tcw, dtype=np.float32).reshape(-1, 16)
+        self.n_local, self.n_fixed = int(n_local), len(self.T) - int(n_local)
+        self.cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(-1)
+        if self.n_fixed < 0 or len(self.cam) != 5 * len(self.T):
+            raise ValueError("bundle adjustment: Tcw and cam must hold one entry per key frame, n_local of them local")
+        self.xw = None if xw is None else np.ascontiguousarray(xw, dtype=np.float32).reshape(-1, 3)
+        self.n_points = len(self.xw) if n_points is None else int(n_points)
+        self.ep = np.ascontiguousarray(edge_pose, dtype=np.int32).reshape(-1)
+        self.n_edges = len(self.ep)
+        self.ept = np.ascontiguousarray(edge_point, dtype=np.int32).reshape(-1)
+        self.obs = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (u, v, u_right, inv_sigma2)]
+        if any(len(a) != self.n_edges for a in [self.ept] + self.obs):
+            raise ValueError("bundle adjustment: the edge arrays must hold one entry per edge")
+        self.fixed = None
+        if local_is_fixed is not None:
+            self.fixed = np.ascontiguousarray(np.asarray(local_is_fixed).astype(bool), dtype=np.uint8).reshape(-1)
+            if len(self.fixed) != self.n_local:
+                raise ValueError("bundle adjustment: local_is_fixed must hold one entry per local key frame")
+        self.Tout = np.zeros((max(self.n_local, 1), 4, 4), np.float64)
+        self.xout = np.zeros((max(self.n_points, 1), 3), np.float64)
+        self.erase = np.zeros(max(self.n_edges, 1), np.uint8)
+        self.level1 = np.zeros(max(self.n_edges, 1), np.uint8)
+        self.chi2 = np.zeros(max(self.n_edges, 1), np.float64)
+        self.st = LbaStatsC()
+
+    def edges(self):
+        return [self.n_edges, ptr(self.ep), ptr(self.ept)] + [ptr(a) for a in self.obs]
+
+    def fixed_ptr(self):
+        return None if self.fixed is None else ptr(self.fixed)
+
+    def result(self, with_flags=True):
+        out = [self.Tout[:self.n_local], self.xout[:self.n_points]]
+        if with_flags:
+            out += [self.erase[:self.n_edges], self.level1[:self.n_edges]]
+        return tuple(out + [lba_stats_dict(self.st), self.chi2[:self.n_edges]])
+
+
+def _stop_ptr(stop_flag):
+    """stop_flag: None, or a ctypes c_int the caller may raise from another thread (pbStopFlag)."""
+    return None if stop_flag is None else C.cast(C.byref(stop_flag), C.c_void_p)
+
+
+def local_bundle_adjustment(n_local, Tcw, cam, xw, edge_pose, edge_point, u, v, u_right, inv_sigma2, local_is_fixed=None,
+                            stop_flag=None, device: int = 0):
+    """Optimizer::LocalBundleAdjustment from the graph on (src/Optimizer.cc:538-777) -> (Tcw_out [n_local, 4, 4] float64,
+    xw_out [n_points, 3] float64, erase [n_edges] uint8 (nonzero: the pair goes into vToErase; 1 level 1 after round one, 2 by
+    the final test only), level1 [n_edges] uint8, stats dict, edge_chi2 [n_edges] float64: what the final test read)."""
+    o = LbaOperands(n_local, Tcw, cam, xw, edge_pose, edge_point, u, v, u_right, inv_sigma2, local_is_fixed)
+    check(_lib.load().orbfe_local_bundle_adjustment(int(device), o.n_local, o.n_fixed, ptr(o.T), o.fixed_ptr(), ptr(o.cam), o.n_points,
+                                                    ptr(o.xw), *o.edges(), _stop_ptr(stop_flag), ptr(o.Tout), ptr(o.xout),
+                                                    ptr(o.erase), ptr(o.level1), C.cast(C.byref(o.st), C.c_void_p), ptr(o.chi2)))
+    return o.result()
+
+
+def bundle_adjustment(n_local, Tcw, cam, xw, edge_pose, edge_point, u, v, u_right, inv_sigma2, n_iterations=5, robust=True,
+                      local_is_fixed=None, stop_flag=None, device: int = 0):
+    """Optimizer::BundleAdjustment (src/Optimizer.cc:54-253): one optimize(n_iterations) -> (Tcw_out, xw_out, stats dict,
+    edge_chi2)."""
+    o = LbaOperands(n_local, Tcw, cam, xw, edge_pose, edge_point, u, v, u_right, inv_sigma2, local_is_fixed)
+    check(_lib.load().orbfe_bundle_adjustment(int(device), o.n_local, o.n_fixed, ptr(o.T), o.fixed_ptr(), ptr(o.cam), o.n_points,
+                                              ptr(o.xw), *o.edges(), int(n_iterations), int(bool(robust)), _stop_ptr(stop_flag),
+                                              ptr(o.Tout), ptr(o.xout), C.cast(C.byref(o.st), C.c_void_p), ptr(o.chi2)))
+    return o.result(with_flags=False)
