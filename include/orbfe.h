@@ -1013,6 +1013,62 @@ int orbfe_local_bundle_adjustment_mappoints(orbfe_mappoints *mp, int n_points, c
                                             double *Tcw_out, double *xw_out /*may be NULL*/, uint8_t *erase, uint8_t *level1,
                                             orbfe_lba_stats *stats, double *edge_chi2);
 
+/* Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:833-1104) from the graph on: the 7-DoF pose graph over every key frame
+ * of the map that LoopClosing::CorrectLoop runs after a loop is closed.  Vertex v is a VertexSim3Expmap with estimate sim3[v]
+ * (vScw: CorrectedSim3[pKF] if present, else Sim3(Rcw, tcw, 1); the record of orbfe_optimize_sim3: qx qy qz qw tx ty tz s),
+ * fixed when is_fixed[v] (pKF == pLoopKF; NULL: none).  Edge e is an EdgeSim3 with identity information and no robust
+ * kernel, vertex 0 = edge_i[e], vertex 1 = edge_j[e]; its measurement Sji = S[j] * S[i]^-1 is computed by the library from
+ * sim3_meas (Snc: NonCorrectedSim3[k] if present, else vScw[k]; NULL: the same as sim3) when edge_kind[e] == 0 -- spanning
+ * tree, old loop and covisibility edges (:939-1040) -- and from sim3 when edge_kind[e] == 1 -- the new LoopConnections
+ * (:907-936); edge_kind NULL: all 0.  Which edges exist, and their de-duplication, is the caller's (two edges between one
+ * pair are legal).  Levenberg with lambda_init = 1e-16 and optimize(n_iterations) (20 in the reference): the loop runs on the
+ * host and reads one small record per linearisation and per trial; the linearisation (analytic Jacobians), the
+ * assembly of the block-sparse normal equations, the block-sparse Cholesky factorisation (7 x 7 blocks, the caller's vertex
+ * order, symbolic part on the host) with its substitutions, and the errors are kernels.  Arithmetic is binary64 and every sum
+ * has a fixed order, so two calls return the same bits.  A failed factorisation is a zero step and a rejected trial.
+ * Outputs: sim3_out[v] the optimised Siw; Tiw_out[v] = [R | t / s] as floats (:1059-1067); edge_chi2 (may be NULL) the chi2
+ * of the last evaluation of the edge (the last Levenberg trial, accepted or not).  An edge between two fixed vertices is not
+ * active: its edge_chi2 is that of the inputs and it takes no part in stats->chi2.  A free vertex without edges is legal (its
+ * step is zero).  With no free vertex, no active edge or n_iterations == 0 nothing is optimised and the outputs are the
+ * inputs.  stats (may be NULL): termination as in orbfe_lba_stats; host_syncs = iterations + trials + 1; n_free, blocks_A and
+ * blocks_L the free vertices and the blocks of the lower triangle, diagonal included, of H and of its factor; solve_failures
+ * the trials whose factorisation met a pivot that was not positive; lambda, chi2_initial and chi2.
+ * Returns ORBFE_ERR_INVALID before anything is enqueued for: NULL arrays, an edge with i == j, an edge index out of range,
+ * an edge_kind above 1, a non-finite input, a scale <= 0, n_iterations < 0; ORBFE_ERR_CAPACITY when the factor has more than
+ * 262144 blocks or the factorisation more than 4194304 block updates.  Runs on the calling thread's matcher stream and is
+ * complete on return.  SetPose, SetWorldPos, UpdateNormalAndDepth and the map mutex stay with the caller. */
+typedef struct orbfe_essgraph_stats {
+  int32_t iterations, trials, termination, stopped, host_syncs;
+  int32_t n_free, blocks_A, blocks_L;
+  int32_t solve_failures;
+  double lambda, chi2_initial, chi2;
+} orbfe_essgraph_stats;
+int orbfe_optimize_essential_graph(int device, int n_vertices, const double *sim3 /*[n_vertices,8]*/,
+                                   const double *sim3_meas /*[n_vertices,8]; may be NULL*/, const uint8_t *is_fixed /*[n_vertices]; may be NULL*/,
+                                   int n_edges, const int32_t *edge_i, const int32_t *edge_j, const uint8_t *edge_kind /*may be NULL*/,
+                                   int fix_scale, int n_iterations, double *sim3_out /*[n_vertices,8]*/, float *Tiw_out /*[n_vertices,16]*/,
+                                   double *edge_chi2 /*[n_edges]; may be NULL*/, orbfe_essgraph_stats *stats);
+/* The tail of OptimizeEssentialGraph (:1070-1103): P <- Sout[r]^-1 .map( S[r] .map(P) ) for every point, r = ref_vertex[p] its
+ * reference key frame (mnCorrectedReference where mnCorrectedByKF is the current key frame); sim3 is the vScw the
+ * optimisation was given, sim3_out what it returned.  In double, stored as float; ref_vertex[p] == -1 copies the point
+ * through (a bad map point). */
+int orbfe_essential_graph_correct_points(int device, int n_vertices, const double *sim3, const double *sim3_out, int n_points,
+                                         const float *xw /*[n_points,3]*/, const int32_t *ref_vertex, float *xw_out /*[n_points,3]*/);
+/* The same on a resident table: the positions of slot[0 .. n_slots) (distinct slots) are rewritten in place, bit-equal to the
+ * array form.  Normal and distance range are the caller's UpdateNormalAndDepth, written through orbfe_mappoints_update. */
+int orbfe_essential_graph_correct_mappoints(orbfe_mappoints *table, int n_vertices, const double *sim3, const double *sim3_out,
+                                            int n_slots, const int32_t *slot, const int32_t *ref_vertex);
+/* GetWorldPos of slot[0 .. n_slots) as the table holds it: what orbfe_essential_graph_correct_mappoints (or the table form of
+ * the local bundle adjustment) left there, for the caller's SetWorldPos. */
+int orbfe_mappoints_positions(orbfe_mappoints *table, int n_slots, const int32_t *slot, float *xw_out /*[n_slots,3]*/);
+/* The linear solver of orbfe_optimize_essential_graph on its own (diagnostic and test surface; the optimiser uses the very
+ * same kernels): A x = rhs for a symmetric positive definite A of 7 x 7 blocks given by its block lower triangle in
+ * block-CSC -- column c holds blocks [colptr[c], colptr[c + 1]), the first of them the diagonal block (its lower triangle is
+ * read), rows ascending -- blocks[k] row-major.  *ok = 0 and x = 0 when a pivot is not positive; *blocks_L (may be NULL) the
+ * blocks of the factor. */
+int orbfe_block_sparse_solve7(int device, int n_block_cols, const int32_t *colptr, const int32_t *rowidx, const double *blocks /*[.,49]*/,
+                              const double *rhs /*[7 n_block_cols]*/, double *x, int32_t *ok, int32_t *blocks_L);
+
 /* ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, const float th,
  * const bool bMono) (src/ORBmatcher.cc:1484-1633) after the caller's pose arithmetic: last-frame
  * point i is valid when it has a non-outlier map point with invzc >= 0 projecting to (u, v) inside

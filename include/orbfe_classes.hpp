@@ -680,13 +680,29 @@ class MapPointTable {
     return nmatches;
   }
   orbfe_mappoints* handle() const { return h_; }
+  // the tail of Optimizer::OptimizeEssentialGraph (:1070-1103) on the table: the position of slot[p] becomes
+  // Sout[r]^-1 .map(Scw[r] .map(P)), r = refVertex[p] (-1: left alone); Scw / SiwOut 8 doubles per vertex
+  void EssentialGraphCorrect(const std::vector<int32_t>& slot, const std::vector<double>& Scw, const std::vector<double>& SiwOut,
+                             const std::vector<int32_t>& refVertex) {
+    if (Scw.size() != SiwOut.size() || Scw.size() % 8 || slot.size() != refVertex.size())
+      throw std::invalid_argument("MapPointTable::EssentialGraphCorrect: the lists disagree in length");
+    check(orbfe_essential_graph_correct_mappoints(h_, (int)(Scw.size() / 8), Scw.data(), SiwOut.data(), (int)slot.size(), slot.data(),
+                                                  refVertex.data()), "MapPointTable::EssentialGraphCorrect");
+  }
+  // GetWorldPos of slot[] as the table holds it (3 floats each)
+  std::vector<float> Positions(const std::vector<int32_t>& slot) const {
+    std::vector<float> out(3 * slot.size() + 1);
+    check(orbfe_mappoints_positions(h_, (int)slot.size(), slot.data(), out.data()), "MapPointTable::Positions");
+    out.resize(3 * slot.size());
+    return out;
+  }
 
  private:
   orbfe_mappoints* h_ = nullptr;
 };
 
 // Optimizer::PoseOptimization (src/Optimizer.cc:256-473), Optimizer::OptimizeSim3 (:1116-1323), Optimizer::LocalBundleAdjustment
-// (:483-814) and Optimizer::BundleAdjustment (:54-253) on the device; OptimizeEssentialGraph is not covered.
+// (:483-814), Optimizer::BundleAdjustment (:54-253) and Optimizer::OptimizeEssentialGraph (:833-1104) on the device.
 // Both forms return nInitialCorrespondences - nBad, write the pose Frame::SetPose receives into Tcw (row-major 4 x 4) and
 // mvbOutlier of every edge; with fewer than 3 edges they return 0 and leave both alone.
 class Optimizer {
@@ -807,6 +823,46 @@ class Optimizer {
                                   g.invSigma2.data(), nIterations, bRobust ? 1 : 0, pbStopFlag, TcwOut.data(), XwOut.data(), stats, nullptr),
           "BundleAdjustment");
     TcwOut.resize(16 * (size_t)g.nLocal); XwOut.resize(g.Xw.size());
+  }
+  // OptimizeEssentialGraph (:833-1104) from the graph on.  The caller flattens its key frames into vertices (vScw: the
+  // CorrectedSim3 entry or Sim3(Rcw, tcw, 1); Snc: the NonCorrectedSim3 entry or vScw; qx qy qz qw tx ty tz s) and its four
+  // edge loops into (edgeI, edgeJ, edgeKind): kind 1 for the new LoopConnections (:907-936, measured from vScw), kind 0 for
+  // spanning tree, old loops and covisibility (:939-1040, measured from Snc).  The de-duplication rules stay the caller's.
+  struct EssentialGraph {
+    std::vector<double> Scw, Snc;  // 8 per vertex; Snc empty: the same as Scw
+    std::vector<uint8_t> isFixed;  // per vertex (pKF == pLoopKF); empty: none
+    std::vector<int32_t> edgeI, edgeJ;
+    std::vector<uint8_t> edgeKind;  // per edge; empty: all 0
+    void validate(const char* what) const {
+      const size_t n = Scw.size() / 8;
+      if (Scw.empty() || Scw.size() % 8 || (!Snc.empty() && Snc.size() != Scw.size()) || (!isFixed.empty() && isFixed.size() != n) ||
+          edgeJ.size() != edgeI.size() || (!edgeKind.empty() && edgeKind.size() != edgeI.size()))
+        throw std::invalid_argument(std::string(what) + ": the flattened lists disagree in length");
+    }
+  };
+  // -> CorrectedSiw per vertex in SiwOut (8 doubles each) and the pose SetPose receives in TiwOut (row-major 4 x 4 floats)
+  static void OptimizeEssentialGraph(const EssentialGraph& g, std::vector<double>& SiwOut, std::vector<float>& TiwOut, bool bFixScale,
+                                     int nIterations = 20, orbfe_essgraph_stats* stats = nullptr, int device = 0) {
+    g.validate("Optimizer::OptimizeEssentialGraph");
+    const size_t n = g.Scw.size() / 8;
+    SiwOut.assign(8 * n, 0.0);
+    TiwOut.assign(16 * n, 0.0f);
+    check(orbfe_optimize_essential_graph(device, (int)n, g.Scw.data(), g.Snc.empty() ? nullptr : g.Snc.data(),
+                                         g.isFixed.empty() ? nullptr : g.isFixed.data(), (int)g.edgeI.size(), g.edgeI.data(), g.edgeJ.data(),
+                                         g.edgeKind.empty() ? nullptr : g.edgeKind.data(), bFixScale ? 1 : 0, nIterations, SiwOut.data(),
+                                         TiwOut.data(), nullptr, stats),
+          "OptimizeEssentialGraph");
+  }
+  // the point correction of its tail (:1070-1103) on arrays: refVertex[p] = the vertex of the point's reference key frame, -1 bad
+  static std::vector<float> EssentialGraphCorrectPoints(const EssentialGraph& g, const std::vector<double>& SiwOut, const std::vector<float>& Xw,
+                                                        const std::vector<int32_t>& refVertex, int device = 0) {
+    if (SiwOut.size() != g.Scw.size() || Xw.size() != 3 * refVertex.size())
+      throw std::invalid_argument("Optimizer::EssentialGraphCorrectPoints: the lists disagree in length");
+    std::vector<float> out(Xw.size() + 1);
+    check(orbfe_essential_graph_correct_points(device, (int)(g.Scw.size() / 8), g.Scw.data(), SiwOut.data(), (int)refVertex.size(), Xw.data(),
+                                               refVertex.data(), out.data()), "EssentialGraphCorrectPoints");
+    out.resize(Xw.size());
+    return out;
   }
   // K candidates in one launch: pairOff [K + 1], K1 / K2 4 K floats, S12 8 K doubles, th2 and bFixScale one entry each; idx1
   // indexes the candidate's own vpMatches1[k].  Returns nIn of every candidate

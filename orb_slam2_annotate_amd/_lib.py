@@ -60,6 +60,13 @@ class LbaStatsC(C.Structure):
                 ("lam", C.c_double * 2), ("chi2", C.c_double * 2)]
 
 
+class EssGraphStatsC(C.Structure):
+    """orbfe_essgraph_stats."""
+    _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("termination", C.c_int32), ("stopped", C.c_int32),
+                ("host_syncs", C.c_int32), ("n_free", C.c_int32), ("blocks_A", C.c_int32), ("blocks_L", C.c_int32),
+                ("solve_failures", C.c_int32), ("lam", C.c_double), ("chi2_initial", C.c_double), ("chi2", C.c_double)]
+
+
 class OptSim3StatsC(C.Structure):
     """orbfe_optsim3_stats."""
     _fields_ = [("rounds", C.c_int32), ("n_bad", C.c_int32), ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2),
@@ -111,6 +118,8 @@ EXPORTS = [
     "orbfe_sim3_ransac", "orbfe_sim3_ransac_multi", "orbfe_sim3_triples_from_draws", "orbfe_sim3_max_iterations",
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_multi",
     "orbfe_local_bundle_adjustment", "orbfe_bundle_adjustment", "orbfe_local_bundle_adjustment_mappoints",
+    "orbfe_optimize_essential_graph", "orbfe_essential_graph_correct_points", "orbfe_essential_graph_correct_mappoints",
+    "orbfe_block_sparse_solve7", "orbfe_mappoints_positions",
     "orbfe_initializer_ransac", "orbfe_initializer_ransac_multi", "orbfe_initializer_normalize", "orbfe_initializer_sets_from_draws",
 ]
 
@@ -290,6 +299,11 @@ def load():
     L.orbfe_local_bundle_adjustment.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, ci] + [vp] * 13
     L.orbfe_bundle_adjustment.argtypes = [ci, ci, ci, vp, vp, vp, ci, vp, ci] + [vp] * 6 + [ci, ci] + [vp] * 5
     L.orbfe_local_bundle_adjustment_mappoints.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci] + [vp] * 13
+    L.orbfe_optimize_essential_graph.argtypes = [ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp]
+    L.orbfe_essential_graph_correct_points.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp]
+    L.orbfe_essential_graph_correct_mappoints.argtypes = [vp, ci, vp, vp, ci, vp, vp]
+    L.orbfe_block_sparse_solve7.argtypes = [ci, ci] + [vp] * 7
+    L.orbfe_mappoints_positions.argtypes = [vp, ci, vp, vp]
     L.orbfe_optimize_sim3.argtypes = [ci, ci] + [vp] * 9 + [C.c_float, ci] + [vp] * 6
     L.orbfe_sim3_ransac.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     L.orbfe_sim3_triples_from_draws.argtypes = [ci, ci, vp, vp]

@@ -151,3 +151,21 @@ class MapPoints:
                                                               ptr(o.erase), ptr(o.level1), C.cast(C.byref(o.st), C.c_void_p),
                                                               ptr(o.chi2)))
         return o.result()
+
+    def essential_graph_correct(self, slot, sim3, sim3_out, ref_vertex):
+        """The tail of Optimizer::OptimizeEssentialGraph on the table (orbfe_essential_graph_correct_mappoints): the position
+        of slot[p] becomes Sout[r]^-1 .map(S[r] .map(P)), r = ref_vertex[p] (-1: left as it is), in place and bit-equal to
+        optimizer.essential_graph_correct_points.  Normal and distance range remain the caller's UpdateNormalAndDepth."""
+        from .optimizer import _correction
+        s, so, r = _correction(sim3, sim3_out, ref_vertex)
+        sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        if len(r) != len(sl):
+            raise ValueError("MapPoints.essential_graph_correct: ref_vertex must hold one entry per slot")
+        check(self._L.orbfe_essential_graph_correct_mappoints(self._h, len(s), ptr(s), ptr(so), len(sl), ptr(sl), ptr(r)))
+
+    def positions(self, slot):
+        """orbfe_mappoints_positions: the world positions the table holds for slot[] -> [n, 3] float32."""
+        sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        out = np.zeros((max(len(sl), 1), 3), np.float32)
+        check(self._L.orbfe_mappoints_positions(self._h, len(sl), ptr(sl), ptr(out)))
+        return out[:len(sl)]

@@ -6,7 +6,10 @@ Optimizer::OptimizeSim3 (src/Optimizer.cc:1116-1323; orbfe_optimize_sim3*): the 
 runs on a loop candidate after Sim3Solver and SearchBySim3, one kernel launch for all candidates of a call.
 Optimizer::LocalBundleAdjustment (:483-814; orbfe_local_bundle_adjustment*) and Optimizer::BundleAdjustment (:54-253;
 orbfe_bundle_adjustment): g2o's Levenberg loop on the host over kernels for the linearisation, the Schur complement of the
-points, the dense solve of the reduced camera system and the back-substitution.  OptimizeEssentialGraph is not covered."""
+points, the dense solve of the reduced camera system and the back-substitution.
+Optimizer::OptimizeEssentialGraph (:833-1104; orbfe_optimize_essential_graph, orbfe_essential_graph_correct_*): the same
+loop over kernels for the linearisation of the EdgeSim3 pose graph, a block-sparse Cholesky factorisation of its normal
+equations and the correction of the map points; ``block_sparse_solve7`` is that solver on its own."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LbaStatsC, OptSim3StatsC, PoseOptStatsC, check, ptr
+from ._lib import EssGraphStatsC, LbaStatsC, OptSim3StatsC, PoseOptStatsC, check, ptr
 
 
 def stats_dict(st: PoseOptStatsC) -> dict:
@@ -242,3 +245,78 @@ def bundle_adjustment(n_local, Tcw, cam, xw, edge_pose, edge_point, u, v, u_righ
                                               ptr(o.xw), *o.edges(), int(n_iterations), int(bool(robust)), _stop_ptr(stop_flag),
                                               ptr(o.Tout), ptr(o.xout), C.cast(C.byref(o.st), C.c_void_p), ptr(o.chi2)))
     return o.result(with_flags=False)
+
+
+def essgraph_stats_dict(st: EssGraphStatsC) -> dict:
+    return dict(iterations=st.iterations, trials=st.trials, termination=st.termination, stopped=st.stopped, host_syncs=st.host_syncs,
+                n_free=st.n_free, blocks_A=st.blocks_A, blocks_L=st.blocks_L, solve_failures=st.solve_failures, lam=st.lam,
+                chi2_initial=st.chi2_initial, chi2=st.chi2)
+
+
+def _sim3_records(a, n, what):
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 8)
+    if n is not None and len(a) != n:
+        raise ValueError(f"{what} must hold one (qx qy qz qw tx ty tz s) record per vertex")
+    return a
+
+
+def optimize_essential_graph(sim3, edge_i, edge_j, sim3_meas=None, is_fixed=None, edge_kind=None, fix_scale=False,
+                             n_iterations=20, device: int = 0):
+    """Optimizer::OptimizeEssentialGraph from the graph on (src/Optimizer.cc:862-1067): sim3 [n, 8] = vScw as
+    (qx qy qz qw tx ty tz s), sim3_meas [n, 8] = Snc (None: sim3), is_fixed [n] (the loop key frame), the edges (i, j) with
+    edge_kind 0 (measurement from sim3_meas: spanning tree, old loops, covisibility) or 1 (from sim3: the new loop
+    connections) -> (sim3_out [n, 8] float64, Tiw_out [n, 4, 4] float32 = [R | t / s], stats dict, edge_chi2 [n_edges])."""
+    s = _sim3_records(sim3, None, "sim3")
+    n = len(s)
+    m = None if sim3_meas is None else _sim3_records(sim3_meas, n, "sim3_meas")
+    ei = np.ascontiguousarray(edge_i, dtype=np.int32).reshape(-1)
+    ej = np.ascontiguousarray(edge_j, dtype=np.int32).reshape(-1)
+    ne = len(ei)
+    if len(ej) != ne:
+        raise ValueError("optimize_essential_graph: edge_i and edge_j must hold one entry per edge")
+    kind = None if edge_kind is None else np.ascontiguousarray(edge_kind, dtype=np.uint8).reshape(-1)
+    fixed = None if is_fixed is None else np.ascontiguousarray(np.asarray(is_fixed).astype(bool), dtype=np.uint8).reshape(-1)
+    if (kind is not None and len(kind) != ne) or (fixed is not None and len(fixed) != n):
+        raise ValueError("optimize_essential_graph: edge_kind / is_fixed must hold one entry per edge / vertex")
+    out = np.zeros((max(n, 1), 8), np.float64)
+    Tiw = np.zeros((max(n, 1), 4, 4), np.float32)
+    chi2 = np.zeros(max(ne, 1), np.float64)
+    st = EssGraphStatsC()
+    check(_lib.load().orbfe_optimize_essential_graph(int(device), n, ptr(s), ptr(m), ptr(fixed), ne, ptr(ei), ptr(ej), ptr(kind),
+                                                     int(bool(fix_scale)), int(n_iterations), ptr(out), ptr(Tiw), ptr(chi2),
+                                                     C.cast(C.byref(st), C.c_void_p)))
+    return out[:n], Tiw[:n], essgraph_stats_dict(st), chi2[:ne]
+
+
+def _correction(sim3, sim3_out, ref_vertex):
+    s = _sim3_records(sim3, None, "sim3")
+    so = _sim3_records(sim3_out, len(s), "sim3_out")
+    return s, so, np.ascontiguousarray(ref_vertex, dtype=np.int32).reshape(-1)
+
+
+def essential_graph_correct_points(sim3, sim3_out, xw, ref_vertex, device: int = 0):
+    """The tail of OptimizeEssentialGraph (:1070-1103): xw [n, 3] float32, ref_vertex [n] (the reference key frame's vertex,
+    -1: copied through) -> xw_out [n, 3] float32 = Sout[r]^-1 .map(S[r] .map(P))."""
+    s, so, r = _correction(sim3, sim3_out, ref_vertex)
+    x = np.ascontiguousarray(xw, dtype=np.float32).reshape(-1, 3)
+    if len(r) != len(x):
+        raise ValueError("essential_graph_correct_points: ref_vertex must hold one entry per point")
+    out = np.zeros((max(len(x), 1), 3), np.float32)
+    check(_lib.load().orbfe_essential_graph_correct_points(int(device), len(s), ptr(s), ptr(so), len(x), ptr(x), ptr(r), ptr(out)))
+    return out[:len(x)]
+
+
+def block_sparse_solve7(colptr, rowidx, blocks, rhs, device: int = 0):
+    """orbfe_block_sparse_solve7: the block lower triangle of a symmetric positive definite matrix in block-CSC (7 x 7 blocks
+    [k, 7, 7], every column beginning with its diagonal block, rows ascending) and rhs [7 n] -> (x [7 n], ok, blocks_L)."""
+    cp = np.ascontiguousarray(colptr, dtype=np.int32).reshape(-1)
+    ri = np.ascontiguousarray(rowidx, dtype=np.int32).reshape(-1)
+    n = len(cp) - 1
+    bl = np.ascontiguousarray(blocks, dtype=np.float64).reshape(-1, 49)
+    b = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
+    if n < 1 or cp[-1] != len(ri) or len(bl) != len(ri) or len(b) != 7 * n:
+        raise ValueError("block_sparse_solve7: colptr must end at the block count; one block per row index; 7 entries of rhs per column")
+    x = np.zeros(7 * n, np.float64)
+    ok, nl = C.c_int32(0), C.c_int32(0)
+    check(_lib.load().orbfe_block_sparse_solve7(int(device), n, ptr(cp), ptr(ri), ptr(bl), ptr(b), ptr(x), C.byref(ok), C.byref(nl)))
+    return x, ok.value, nl.value
