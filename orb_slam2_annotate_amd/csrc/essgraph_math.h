@@ -26,7 +26,7 @@
 #include <stdint.h>
 
 #include "lba_math.h"      // LbaRecord, LbaLM and the Levenberg rules, unmodified
-#include "optsim3_math.h"  // OptSim3, optsim3_exp / _mul / _inverse / _map / _quat_to_R, unmodified
+#include "optsim3_math.h"  // OptSim3, optsim3_exp / _mul / _inverse / _map, unmodified; g2o_quat_to_R through it
 
 namespace orbfe {
 
@@ -144,7 +144,7 @@ struct EssLogBranch {
 ORBFE_HD inline void essgraph_log_ex(const OptSim3& S, double out[7], EssLogBranch& br) {
   const double sigma = log(S.s);
   double R[9];
-  optsim3_quat_to_R(S.q, R);
+  g2o_quat_to_R(S.q, R);
   const double d = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
   const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};  // deltaR (se3_ops.hpp)
   const double eps = 0.00001;
@@ -333,7 +333,7 @@ ORBFE_HD inline double ess_linearise_edge(const OptSim3& C, const OptSim3& Si, c
   optsim3_inverse(Si, &Siinv);
   optsim3_mul(Sj, Siinv, &T);
   double R[9], tx[9], txR[9], PR[9], QR[9], StxR[9], SR[9], St[3];
-  optsim3_quat_to_R(T.q, R);
+  g2o_quat_to_R(T.q, R);
   ess_skew(T.t, tx);
   ess_mul3(tx, R, txR);
   ess_mul3(P, R, PR);
@@ -583,7 +583,7 @@ ORBFE_HD inline void ess_Tiw(const double* rec8, float* T) {
   OptSim3 S;
   ess_load(rec8, &S);
   double R[9];
-  optsim3_quat_to_R(S.q, R);
+  g2o_quat_to_R(S.q, R);
   const double k = 1.0 / S.s;
 #pragma unroll
   for (int r = 0; r < 3; r++) {

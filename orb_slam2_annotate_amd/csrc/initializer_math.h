@@ -25,11 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define ORBFE_HD __host__ __device__
-#else
-#define ORBFE_HD
-#endif
+#include "g2o_math.h"  // ORBFE_HD
 
 namespace orbfe {
 

@@ -1,7 +1,7 @@
 // k_optsim3.hip -- Optimizer::OptimizeSim3 (src/Optimizer.cc:1116-1323) as ONE launch: both rounds, their Levenberg
 // iterations, the lambda trials of every iteration, both classifications and the "fewer than 10 left" exit run inside
-// k_optimize_sim3, one problem (loop candidate) per 64-lane workgroup, i.e. per wave.  The arithmetic is optsim3_math.h:
-// binary64, and the build has -ffp-contract=off, so every product and sum rounds where it is written.
+// k_optimize_sim3, one problem (loop candidate) per 64-lane workgroup, i.e. per wave.  The arithmetic is optsim3_math.h on
+// g2o_math.h: binary64, and the build has -ffp-contract=off, so every product and sum rounds where it is written.
 //
 // Layout.  No LDS and no barrier.  Lane l owns pairs l, l + 64, ...: it alone reads and writes their `bad` byte and their two
 // stored chi2.  A pass evaluates the pairs that are not erased at one transform -- a FULL pass at the estimate (errors,
@@ -53,9 +53,10 @@ __global__ __launch_bounds__(kOptSim3Threads) void k_optimize_sim3(OptSim3Args a
   const float th2 = pr.th2;
   const bool fixScale = pr.fixScale != 0;
 
-  OptSim3LM lm;
-  lm.fixScale = fixScale;
-  optsim3_from_record(pr.sim3, &lm.est);
+  G2oLM<7> lm;
+  OptSim3Vertex vx;
+  vx.fixScale = fixScale;
+  optsim3_from_record(pr.sim3, &vx.est);
 
   int rounds = 0, nBad = 0, nIn = 0, maxIt = 5;  // optimizer.optimize(5) (:1263)
   bool early = true;                             // the call returns 0 and g2oS12 stays what came in
@@ -68,14 +69,14 @@ __global__ __launch_bounds__(kOptSim3Threads) void k_optimize_sim3(OptSim3Args a
     for (int i = first + lane; i < last; i += kOptSim3Threads) a.bad[i] = 0;
 #pragma unroll 1
     for (int rnd = 0; rnd < 2; rnd++) {
-      optsim3_lm_begin(&lm, maxIt);
-      int cmd = kOptSim3Full;
+      g2o_lm_begin(&lm, maxIt);
+      int cmd = kG2oLMFull;
 #pragma unroll 1
-      while (cmd != kOptSim3Done) {
+      while (cmd != kG2oLMDone) {
         OptSim3Eval E;
-        if (cmd == kOptSim3Full) {
+        if (cmd == kG2oLMFull) {
           // computeActiveErrors + activeRobustChi2 + buildSystem (optimization_algorithm_levenberg.cpp:75-87)
-          optsim3_eval_at(lm.est, &E);
+          optsim3_eval_at(vx.est, &E);
           double acc[kOptSim3Sums];
 #pragma unroll
           for (int k = 0; k < kOptSim3Sums; k++) acc[k] = 0.0;
@@ -92,11 +93,11 @@ __global__ __launch_bounds__(kOptSim3Threads) void k_optimize_sim3(OptSim3Args a
           wave_sum<kOptSim3Sums>(acc);
 #pragma unroll
           for (int k = 0; k < kOptSim3Sums; k++) lm.S[k] = acc[k];
-          optsim3_lm_after_full(&lm);
-          cmd = kOptSim3Trial;
+          cmd = g2o_lm_after_full(&lm);
+          optsim3_lm_propose(&lm, &vx);
         } else {
           // computeActiveErrors + activeRobustChi2 at the trial (:123-124)
-          optsim3_eval_at(lm.trial, &E);
+          optsim3_eval_at(vx.trial, &E);
           double sum[1] = {0.0};
 #pragma unroll 1
           for (int i = first + lane; i < last; i += kOptSim3Threads) {
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(kOptSim3Threads) void k_optimize_sim3(OptSim3Args a
             a.chi21[i] = c21;
           }
           wave_sum<1>(sum);
-          cmd = optsim3_lm_after_trial(&lm, sum[0]);
+          cmd = g2o_lm_after_trial(&lm, sum[0], &vx.est, vx.trial, [&] { optsim3_lm_propose(&lm, &vx); });
           // the counters are the same in every lane: kept in scalar registers, they leave the vector file to the sums
           cmd = __builtin_amdgcn_readfirstlane(cmd);
           lm.it = __builtin_amdgcn_readfirstlane(lm.it); lm.q = __builtin_amdgcn_readfirstlane(lm.q);
@@ -143,12 +144,12 @@ __global__ __launch_bounds__(kOptSim3Threads) void k_optimize_sim3(OptSim3Args a
   }
 
   if (lane == 0) {
-    if (early) optsim3_from_record(pr.sim3, &lm.est);  // (converted again: kept, it would hold 16 registers throughout)
+    if (early) optsim3_from_record(pr.sim3, &vx.est);  // (converted again: kept, it would hold 16 registers throughout)
 #pragma unroll
-    for (int k = 0; k < 4; k++) res->sim3[k] = lm.est.q[k];
+    for (int k = 0; k < 4; k++) res->sim3[k] = vx.est.q[k];
 #pragma unroll
-    for (int k = 0; k < 3; k++) res->sim3[4 + k] = lm.est.t[k];
-    res->sim3[7] = lm.est.s;
+    for (int k = 0; k < 3; k++) res->sim3[4 + k] = vx.est.t[k];
+    res->sim3[7] = vx.est.s;
     res->nIn = nIn; res->nBad = nBad; res->rounds = rounds; res->pad = 0;
   }
 }

@@ -17,17 +17,7 @@
 // are 64 lane-strided partial sums combined by the __shfl_down tree 32 .. 1; the CPU program combines the same partial sums
 // in the same tree, so both give the same bits.
 #pragma once
-#include <float.h>
-#include <math.h>
-#include <stdint.h>
-
-#ifndef ORBFE_HD
-#if defined(__HIPCC__)
-#define ORBFE_HD __host__ __device__
-#else
-#define ORBFE_HD
-#endif
-#endif
+#include "g2o_math.h"
 
 namespace orbfe {
 
@@ -85,67 +75,20 @@ struct LbaArgs {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
-// SE3Quat
-ORBFE_HD inline void lba_quat_from_R(const double m[9], double q[4]) {  // Eigen::Quaterniond(Matrix3d); m row-major
-  double t = m[0] + m[4] + m[8];
-  if (t > 0.0) {
-    t = sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (m[7] - m[5]) * t; q[1] = (m[2] - m[6]) * t; q[2] = (m[3] - m[1]) * t;
-  } else {
-    int i = 0;
-    if (m[4] > m[0]) i = 1;
-    if (m[8] > (i == 0 ? m[0] : m[4])) i = 2;
-    if (i == 0) {
-      t = sqrt(m[0] - m[4] - m[8] + 1.0);
-      q[0] = 0.5 * t; t = 0.5 / t;
-      q[3] = (m[7] - m[5]) * t; q[1] = (m[3] + m[1]) * t; q[2] = (m[6] + m[2]) * t;
-    } else if (i == 1) {
-      t = sqrt(m[4] - m[8] - m[0] + 1.0);
-      q[1] = 0.5 * t; t = 0.5 / t;
-      q[3] = (m[2] - m[6]) * t; q[2] = (m[7] + m[5]) * t; q[0] = (m[1] + m[3]) * t;
-    } else {
-      t = sqrt(m[8] - m[0] - m[4] + 1.0);
-      q[2] = 0.5 * t; t = 0.5 / t;
-      q[3] = (m[3] - m[1]) * t; q[0] = (m[2] + m[6]) * t; q[1] = (m[5] + m[7]) * t;
-    }
-  }
-}
-ORBFE_HD inline void lba_normalize(double q[4]) {  // se3quat.h:280-285
-  if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n;
-}
-ORBFE_HD inline void lba_rotate(const double q[4], double X, double Y, double Z, double r[3]) {  // Eigen _transformVector
-  double uvx = q[1] * Z - q[2] * Y, uvy = q[2] * X - q[0] * Z, uvz = q[0] * Y - q[1] * X;
-  uvx = uvx + uvx; uvy = uvy + uvy; uvz = uvz + uvz;
-  r[0] = (X + q[3] * uvx) + (q[1] * uvz - q[2] * uvy);
-  r[1] = (Y + q[3] * uvy) + (q[2] * uvx - q[0] * uvz);
-  r[2] = (Z + q[3] * uvz) + (q[0] * uvy - q[1] * uvx);
-}
-ORBFE_HD inline void lba_quat_to_R(const double q[4], double R[9]) {  // Eigen toRotationMatrix, row-major
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y,
-               tzz = tz * z;
-  R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-  R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-}
+// SE3Quat (the quaternion arithmetic is g2o_math.h)
 // Converter::toSE3Quat (src/Converter.cc:37-47) of a row-major 4 x 4 float pose into the 8 doubles of LbaArgs::pose
 ORBFE_HD inline void lba_pose_from_Tcw(const float* T, double* P) {
   double R[9];
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) R[3 * r + c] = (double)T[4 * r + c];
-  lba_quat_from_R(R, P);
-  lba_normalize(P);
+  g2o_quat_from_R(R, P);
+  g2o_normalize_rotation(P);
   P[4] = (double)T[3]; P[5] = (double)T[7]; P[6] = (double)T[11]; P[7] = 0.0;
 }
 // SE3Quat::to_homogeneous_matrix, row-major 4 x 4
 ORBFE_HD inline void lba_pose_to_Tcw(const double* P, double* T) {
   double R[9];
-  lba_quat_to_R(P, R);
+  g2o_quat_to_R(P, R);
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) T[4 * r + c] = R[3 * r + c];
     T[4 * r + 3] = P[4 + r];
@@ -154,35 +97,8 @@ ORBFE_HD inline void lba_pose_to_Tcw(const double* P, double* T) {
 }
 // VertexSE3Expmap::oplusImpl: out = SE3Quat::exp(x) * est; x = (omega, upsilon)
 ORBFE_HD inline void lba_pose_oplus(const double* est, const double x[6], double* out) {
-  const double wx = x[0], wy = x[1], wz = x[2];
-  const double theta = sqrt(wx * wx + wy * wy + wz * wz);
-  const double Om[9] = {0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0};
-  double Om2[9], R[9], V[9];
-  for (int r = 0; r < 3; r++)
-    for (int c = 0; c < 3; c++) Om2[3 * r + c] = (Om[3 * r] * Om[c] + Om[3 * r + 1] * Om[3 + c]) + Om[3 * r + 2] * Om[6 + c];
-  if (theta < 0.00001) {
-    for (int k = 0; k < 9; k++) { R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + Om[k]) + Om2[k]; V[k] = R[k]; }
-  } else {
-    const double a = sin(theta) / theta, b = (1.0 - cos(theta)) / (theta * theta), c3 = (theta - sin(theta)) / (theta * theta * theta);
-    for (int k = 0; k < 9; k++) {
-      const double I = k % 4 == 0 ? 1.0 : 0.0;
-      R[k] = (I + a * Om[k]) + b * Om2[k];
-      V[k] = (I + b * Om[k]) + c3 * Om2[k];
-    }
-  }
-  double qe[4], te[3];
-  lba_quat_from_R(R, qe);
-  lba_normalize(qe);
-  for (int r = 0; r < 3; r++) te[r] = (V[3 * r] * x[3] + V[3 * r + 1] * x[4]) + V[3 * r + 2] * x[5];
-  // SE3Quat::operator*: t = a.t + a.r * b.t; r = a.r * b.r; normalizeRotation
-  double rt[3];
-  lba_rotate(qe, est[4], est[5], est[6], rt);
-  const double ax = qe[0], ay = qe[1], az = qe[2], aw = qe[3], bx = est[0], by = est[1], bz = est[2], bw = est[3];
-  double q[4] = {aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz, aw * bz + az * bw + ax * by - ay * bx,
-                 aw * bw - ax * bx - ay * by - az * bz};
-  lba_normalize(q);
-  out[0] = q[0]; out[1] = q[1]; out[2] = q[2]; out[3] = q[3];
-  out[4] = te[0] + rt[0]; out[5] = te[1] + rt[1]; out[6] = te[2] + rt[2]; out[7] = 0.0;
+  g2o_se3_oplus(x, est, out);
+  out[7] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -194,43 +110,21 @@ struct LbaEdge {
 };
 // computeError (types_six_dof_expmap.h:94-104, :126-136) with cam_project (.cpp:141-157); z is what isDepthPositive tests
 ORBFE_HD inline void lba_edge_error(const double* P, const float* cam, const double* X, const float* obs, LbaEdge* E) {
-  double c[3];
-  lba_rotate(P, X[0], X[1], X[2], c);
-  const double x = c[0] + P[4], y = c[1] + P[5], z = c[2] + P[6];
-  const double fx = (double)cam[0], fy = (double)cam[1], cx = (double)cam[2], cy = (double)cam[3], bf = (double)cam[4];
-  const double u = (double)obs[0], v = (double)obs[1], ur = (double)obs[2], w = (double)obs[3];
+  const double K[5] = {(double)cam[0], (double)cam[1], (double)cam[2], (double)cam[3], (double)cam[4]};
+  double xyz[3];
   E->stereo = !(obs[2] < 0.0f);  // mvuRight < 0: monocular (src/Optimizer.cc:627)
-  if (E->stereo) {
-    const double invz = (double)(float)(1.0 / z);  // const float invz = 1.0f / trans_xyz[2]
-    const double p0 = (x * invz) * fx + cx;
-    E->e[0] = u - p0;
-    E->e[1] = v - ((y * invz) * fy + cy);
-    E->e[2] = ur - (p0 - bf * invz);
-  } else {
-    E->e[0] = u - ((x / z) * fx + cx);
-    E->e[1] = v - ((y / z) * fy + cy);
-    E->e[2] = 0.0;
-  }
-  E->chi2 = (E->e[0] * (w * E->e[0]) + E->e[1] * (w * E->e[1])) + E->e[2] * (w * E->e[2]);
-  E->w = w; E->x = x; E->y = y; E->z = z;
+  E->w = (double)obs[3];
+  E->chi2 = g2o_se3_project_error(P, K, X, (double)obs[0], (double)obs[1], (double)obs[2], E->w, E->e, xyz);
+  E->x = xyz[0]; E->y = xyz[1]; E->z = xyz[2];
 }
-// RobustKernelHuber::robustify: rho[0], rho[1]; with robust off the identity
-ORBFE_HD inline void lba_huber(double chi2, double delta, bool robust, double* rho0, double* rho1) {
-  const double dsqr = delta * delta;
-  if (!robust || chi2 <= dsqr) {
-    *rho0 = chi2; *rho1 = 1.0;
-  } else {
-    const double sq = sqrt(chi2);
-    *rho0 = 2 * sq * delta - dsqr;
-    *rho1 = delta / sq;
-  }
-}
-// linearizeOplus (.cpp:103-139, :188-234): Jp = _jacobianOplusXj [3][6], Jl = _jacobianOplusXi [3][3]
+// linearizeOplus (.cpp:103-139, :188-234): Jp = _jacobianOplusXj [3][6], Jl = _jacobianOplusXi [3][3].  These blocks DIVIDE by
+// z and z_2; the pose-only edges of poseopt_math.h multiply by invz and invz_2 (.cpp:266-288, :335-364) and round differently:
+// the two Jacobians are not copies and stay apart
 ORBFE_HD inline void lba_edge_jacobians(const double* P, const float* cam, const LbaEdge& E, double Jp[18], double Jl[9]) {
   const double fx = (double)cam[0], fy = (double)cam[1], bf = (double)cam[4];
   const double x = E.x, y = E.y, z = E.z, z_2 = z * z;
   double R[9];
-  lba_quat_to_R(P, R);
+  g2o_quat_to_R(P, R);
   Jp[0] = x * y / z_2 * fx; Jp[1] = -(1 + (x * x / z_2)) * fx; Jp[2] = y / z * fx; Jp[3] = -1. / z * fx; Jp[4] = 0.0; Jp[5] = x / z_2 * fx;
   Jp[6] = (1 + y * y / z_2) * fy; Jp[7] = -x * y / z_2 * fy; Jp[8] = -x / z * fy; Jp[9] = 0.0; Jp[10] = -1. / z * fy; Jp[11] = y / z_2 * fy;
   if (E.stereo) {
@@ -290,7 +184,7 @@ ORBFE_HD inline void lba_linearise_point(const LbaArgs& a, int p, int cur, bool 
     lba_edge_error(P, a.cam + 8 * (size_t)j, X, a.edgeObs + 4 * (size_t)e, &E);
     a.chi2[e] = E.chi2;
     double rho0, rho1;
-    lba_huber(E.chi2, lba_delta(E), robust, &rho0, &rho1);
+    g2o_huber(E.chi2, lba_delta(E), robust, &rho0, &rho1);
     rho = rho + rho0;
     double Jp[18], Jl[9];
     lba_edge_jacobians(P, a.cam + 8 * (size_t)j, E, Jp, Jl);
@@ -473,7 +367,7 @@ ORBFE_HD inline void lba_trial_point(const LbaArgs& a, int p, int cur, double la
     lba_edge_error(lba_pose_at(a, 1 - cur, j), a.cam + 8 * (size_t)j, Xt, a.edgeObs + 4 * (size_t)e, &E);
     a.chi2[e] = E.chi2;
     double rho0, rho1;
-    lba_huber(E.chi2, lba_delta(E), robust, &rho0, &rho1);
+    g2o_huber(E.chi2, lba_delta(E), robust, &rho0, &rho1);
     rho = rho + rho0;
   }
   a.ptRho[p] = rho;
@@ -509,7 +403,7 @@ ORBFE_HD inline bool lba_edge_bad(const LbaArgs& a, int e, int cur) {
   const double* P = lba_pose_at(a, cur, j);
   const double* X = lba_pt_at(a, cur, a.edgePoint[e]);
   double c[3];
-  lba_rotate(P, X[0], X[1], X[2], c);
+  g2o_quat_rotate(P, X[0], X[1], X[2], c);
   const double z = c[2] + P[6];
   const double thr = a.edgeObs[4 * (size_t)e + 2] < 0.0f ? kLbaChi2Mono : kLbaChi2Stereo;
   return a.chi2[e] > thr || !(z > 0.0);

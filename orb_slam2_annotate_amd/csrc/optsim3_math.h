@@ -5,7 +5,7 @@
 //
 // * Thirdparty/g2o/g2o/types/sim3.h (Sim3(Vector7d) :70-142, map :144-146, inverse :233-236, operator* :266-272),
 // * Thirdparty/g2o/g2o/types/types_seven_dof_expmap.h (oplusImpl :60-69, cam_map1/2 :74-88, computeError :138-145, :160-167),
-// * Thirdparty/g2o/g2o/core/base_binary_edge.hpp:54-120 (constructQuadraticForm), robust_kernel_impl.cpp:78-91 (Huber),
+// * Thirdparty/g2o/g2o/core/base_binary_edge.hpp:54-120 (constructQuadraticForm), robust_kernel_impl.cpp:78-91 (Huber; g2o_math.h),
 // * Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-189 and Eigen's Quaternion <-> matrix conversions.
 //
 // Arithmetic is binary64 on inputs widened from float (build with -ffp-contract=off).  g2o differentiates these two edges
@@ -14,17 +14,7 @@
 // NOT bit-identical to it.  Everything is written on compile-time indices, fully unrolled, so that the
 // 7 x 7 system and the 36 running sums stay in registers on the device.
 #pragma once
-#include <float.h>
-#include <math.h>
-#include <stdint.h>
-
-#ifndef ORBFE_HD
-#if defined(__HIPCC__)
-#define ORBFE_HD __host__ __device__
-#else
-#define ORBFE_HD
-#endif
-#endif
+#include "g2o_math.h"
 
 namespace orbfe {
 
@@ -71,77 +61,12 @@ ORBFE_HD inline void optsim3_unpack(const float A[4], const float B[4], const fl
   p->o1[0] = (double)C[0]; p->o1[1] = (double)C[1]; p->o2[0] = (double)C[2]; p->o2[1] = (double)C[3];
 }
 
-// Eigen::Quaterniond(Matrix3d) (Eigen/src/Geometry/Quaternion.h: quaternionbase_assign_impl<Other, 3, 3>); m row-major
-ORBFE_HD inline void optsim3_quat_from_R(const double m[9], double q[4]) {
-  double t = m[0] + m[4] + m[8];
-  if (t > 0.0) {
-    t = sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (m[7] - m[5]) * t;
-    q[1] = (m[2] - m[6]) * t;
-    q[2] = (m[3] - m[1]) * t;
-  } else {
-    int i = 0;
-    if (m[4] > m[0]) i = 1;
-    if (m[8] > (i == 0 ? m[0] : m[4])) i = 2;
-    // j = (i + 1) % 3, k = (j + 1) % 3, written out so that every index is a constant
-    if (i == 0) {
-      t = sqrt(m[0] - m[4] - m[8] + 1.0);
-      q[0] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[7] - m[5]) * t;
-      q[1] = (m[3] + m[1]) * t;
-      q[2] = (m[6] + m[2]) * t;
-    } else if (i == 1) {
-      t = sqrt(m[4] - m[8] - m[0] + 1.0);
-      q[1] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[2] - m[6]) * t;
-      q[2] = (m[7] + m[5]) * t;
-      q[0] = (m[1] + m[3]) * t;
-    } else {
-      t = sqrt(m[8] - m[0] - m[4] + 1.0);
-      q[2] = 0.5 * t;
-      t = 0.5 / t;
-      q[3] = (m[3] - m[1]) * t;
-      q[0] = (m[2] + m[6]) * t;
-      q[1] = (m[5] + m[7]) * t;
-    }
-  }
-}
-
-// Eigen QuaternionBase::_transformVector: uv = 2 (q.vec x v); v + w uv + q.vec x uv
-ORBFE_HD inline void optsim3_rotate(const double q[4], double X, double Y, double Z, double r[3]) {
-  double uvx = q[1] * Z - q[2] * Y;
-  double uvy = q[2] * X - q[0] * Z;
-  double uvz = q[0] * Y - q[1] * X;
-  uvx = uvx + uvx;
-  uvy = uvy + uvy;
-  uvz = uvz + uvz;
-  r[0] = (X + q[3] * uvx) + (q[1] * uvz - q[2] * uvy);
-  r[1] = (Y + q[3] * uvy) + (q[2] * uvx - q[0] * uvz);
-  r[2] = (Z + q[3] * uvz) + (q[0] * uvy - q[1] * uvx);
-}
-
-// Eigen QuaternionBase::toRotationMatrix, row-major
-ORBFE_HD inline void optsim3_quat_to_R(const double q[4], double R[9]) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-  R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
-}
-
 // the sim3[13] record of orbfe_sim3_ransac_multi (R row-major, t, s; floats) as the reference converts it:
 // Converter::toMatrix3d / toVector3d widen, then Sim3(Matrix3d, Vector3d, double) (sim3.h:64-67; src/LoopClosing.cc:381)
 ORBFE_HD inline void optsim3_from_record(const float rec[13], OptSim3* S) {
   const double R[9] = {(double)rec[0], (double)rec[1], (double)rec[2], (double)rec[3], (double)rec[4],
                        (double)rec[5], (double)rec[6], (double)rec[7], (double)rec[8]};
-  optsim3_quat_from_R(R, S->q);
+  g2o_quat_from_R(R, S->q);
   S->t[0] = (double)rec[9]; S->t[1] = (double)rec[10]; S->t[2] = (double)rec[11];
   S->s = (double)rec[12];
 }
@@ -199,7 +124,7 @@ ORBFE_HD inline void optsim3_exp(const double u[7], OptSim3* out) {
 #pragma unroll
     for (int k = 0; k < 9; k++) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + ra * Om[k]) + rb * Om2[k];
   }
-  optsim3_quat_from_R(R, out->q);
+  g2o_quat_from_R(R, out->q);
   double W[9];
 #pragma unroll
   for (int k = 0; k < 9; k++) W[k] = (A * Om[k] + B * Om2[k]) + C * (k % 4 == 0 ? 1.0 : 0.0);
@@ -210,14 +135,9 @@ ORBFE_HD inline void optsim3_exp(const double u[7], OptSim3* out) {
 
 // Sim3::operator* (sim3.h:266-272): r = a.r * b.r (Eigen quat_product, no normalisation); t = a.s (a.r * b.t) + a.t
 ORBFE_HD inline void optsim3_mul(const OptSim3& a, const OptSim3& b, OptSim3* out) {
-  const double ax = a.q[0], ay = a.q[1], az = a.q[2], aw = a.q[3];
-  const double bx = b.q[0], by = b.q[1], bz = b.q[2], bw = b.q[3];
   double r[3];
-  optsim3_rotate(a.q, b.t[0], b.t[1], b.t[2], r);
-  out->q[0] = aw * bx + ax * bw + ay * bz - az * by;
-  out->q[1] = aw * by + ay * bw + az * bx - ax * bz;
-  out->q[2] = aw * bz + az * bw + ax * by - ay * bx;
-  out->q[3] = aw * bw - ax * bx - ay * by - az * bz;
+  g2o_quat_rotate(a.q, b.t[0], b.t[1], b.t[2], r);
+  g2o_quat_mul(a.q, b.q, out->q);
   out->t[0] = a.s * r[0] + a.t[0]; out->t[1] = a.s * r[1] + a.t[1]; out->t[2] = a.s * r[2] + a.t[2];
   out->s = a.s * b.s;
 }
@@ -225,7 +145,7 @@ ORBFE_HD inline void optsim3_mul(const OptSim3& a, const OptSim3& b, OptSim3* ou
 // Sim3::map (sim3.h:144-146): s (r * xyz) + t
 ORBFE_HD inline void optsim3_map(const OptSim3& S, const double X[3], double P[3]) {
   double r[3];
-  optsim3_rotate(S.q, X[0], X[1], X[2], r);
+  g2o_quat_rotate(S.q, X[0], X[1], X[2], r);
   P[0] = S.s * r[0] + S.t[0]; P[1] = S.s * r[1] + S.t[1]; P[2] = S.s * r[2] + S.t[2];
 }
 
@@ -233,7 +153,7 @@ ORBFE_HD inline void optsim3_map(const OptSim3& S, const double X[3], double P[3
 ORBFE_HD inline void optsim3_inverse(const OptSim3& S, OptSim3* out) {
   out->q[0] = -S.q[0]; out->q[1] = -S.q[1]; out->q[2] = -S.q[2]; out->q[3] = S.q[3];
   const double k = -1.0 / S.s;
-  optsim3_rotate(out->q, k * S.t[0], k * S.t[1], k * S.t[2], out->t);
+  g2o_quat_rotate(out->q, k * S.t[0], k * S.t[1], k * S.t[2], out->t);
   out->s = 1.0 / S.s;
 }
 
@@ -241,7 +161,7 @@ ORBFE_HD inline void optsim3_eval_at(const OptSim3& S, OptSim3Eval* E) {
   E->S = S;
   optsim3_inverse(S, &E->Sinv);
   double R[9];
-  optsim3_quat_to_R(E->Sinv.q, R);
+  g2o_quat_to_R(E->Sinv.q, R);
 #pragma unroll
   for (int k = 0; k < 9; k++) E->M[k] = E->Sinv.s * R[k];
 }
@@ -314,18 +234,6 @@ ORBFE_HD inline void optsim3_jac21(const OptSim3Eval& E, const OptSim3Cam& K2, c
   }
 }
 
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho and its first derivative
-ORBFE_HD inline void optsim3_huber(double chi2, double delta, double* rho0, double* rho1) {
-  const double dsqr = delta * delta;
-  *rho0 = chi2;
-  *rho1 = 1.0;
-  if (chi2 > dsqr) {
-    const double sq = sqrt(chi2);
-    *rho0 = 2 * sq * delta - dsqr;
-    *rho1 = delta / sq;
-  }
-}
-
 // constructQuadraticForm (base_binary_edge.hpp:91-113) of one edge into the running sums: H += J^T (rho1 w I) J,
 // b += rho1 J^T w e (negated once, after the sum), chi2 += rho0
 ORBFE_HD inline void optsim3_accumulate(double (&acc)[kOptSim3Sums], const double J0[7], const double J1[7], const double e[2],
@@ -350,11 +258,11 @@ ORBFE_HD inline void optsim3_pair_full(const OptSim3Eval& E, const OptSim3Cam& K
                                        double delta, bool fixScale, double (&acc)[kOptSim3Sums], double* chi12, double* chi21) {
   double e[2], P[3], J0[7], J1[7], rho0, rho1;
   const double c12 = optsim3_edge12(E, K1, p, e, P);
-  optsim3_huber(c12, delta, &rho0, &rho1);
+  g2o_huber(c12, delta, true, &rho0, &rho1);
   optsim3_jac12(K1, P, J0, J1);
   optsim3_accumulate(acc, J0, J1, e, p.w1, rho0, rho1);
   const double c21 = optsim3_edge21(E, K2, p, e, P);
-  optsim3_huber(c21, delta, &rho0, &rho1);
+  g2o_huber(c21, delta, true, &rho0, &rho1);
   optsim3_jac21(E, K2, p.X1, P, fixScale, J0, J1);
   optsim3_accumulate(acc, J0, J1, e, p.w2, rho0, rho1);
   *chi12 = c12;
@@ -366,143 +274,29 @@ ORBFE_HD inline void optsim3_pair_trial(const OptSim3Eval& E, const OptSim3Cam& 
                                         double delta, double* sum, double* chi12, double* chi21) {
   double e[2], P[3], rho0, rho1;
   const double c12 = optsim3_edge12(E, K1, p, e, P);
-  optsim3_huber(c12, delta, &rho0, &rho1);
+  g2o_huber(c12, delta, true, &rho0, &rho1);
   *sum = *sum + rho0;
   const double c21 = optsim3_edge21(E, K2, p, e, P);
-  optsim3_huber(c21, delta, &rho0, &rho1);
+  g2o_huber(c21, delta, true, &rho0, &rho1);
   *sum = *sum + rho0;
   *chi12 = c12;
   *chi21 = c21;
 }
 
-// (H + lam I) x = b by unpivoted LDL^T; Hs: the 28 upper-triangle entries, row-major.  false on a pivot that is not positive
-ORBFE_HD inline bool optsim3_solve7(const double* Hs, double lam, const double* b, double x[7]) {
-  double A[7][7], L[7][7], D[7], y[7];
-  int k = 0;
-#pragma unroll
-  for (int r = 0; r < 7; r++)
-#pragma unroll
-    for (int c = r; c < 7; c++) { A[r][c] = Hs[k]; A[c][r] = Hs[k]; k++; }
-#pragma unroll
-  for (int j = 0; j < 7; j++) A[j][j] = A[j][j] + lam;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 7; j++) {
-    double d = A[j][j];
-#pragma unroll
-    for (int m = 0; m < j; m++) d = d - (L[j][m] * L[j][m]) * D[m];
-    if (!(d > 0.0)) ok = false;
-    D[j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 7; i++) {
-      double s = A[j][i];
-#pragma unroll
-      for (int m = 0; m < j; m++) s = s - (L[i][m] * L[j][m]) * D[m];
-      L[i][j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 7; i++) {
-    double s = b[i];
-#pragma unroll
-    for (int m = 0; m < i; m++) s = s - L[i][m] * y[m];
-    y[i] = s;
-  }
-#pragma unroll
-  for (int i = 6; i >= 0; i--) {
-    double s = y[i] / D[i];
-#pragma unroll
-    for (int m = i + 1; m < 7; m++) s = s - L[m][i] * x[m];
-    x[i] = s;
-  }
-  if (!ok) {  // a failed factorisation: the update is zero and the trial counts as DBL_MAX (levenberg.cpp:126-127)
-#pragma unroll
-    for (int i = 0; i < 7; i++) x[i] = 0.0;
-  }
-  return ok;
-}
-
-// OptimizationAlgorithmLevenberg::solve (optimization_algorithm_levenberg.cpp:61-189) as two steps around the passes over
-// the pairs: lm_after_full() consumes the 36 sums of a FULL pass at the estimate and gives the first trial; lm_after_trial()
-// consumes the robust chi2 of a TRIAL pass and gives the next command.
-enum OptSim3Cmd { kOptSim3Done = 0, kOptSim3Full = 1, kOptSim3Trial = 2 };
-
-struct OptSim3LM {
+// The vertex's side of the Levenberg step (g2o_math.h: G2oLM<7>): the estimate and the trial
+struct OptSim3Vertex {
   OptSim3 est, trial;
-  double S[kOptSim3Sums];  // H, b (negated), robust chi2 of the last FULL pass
-  double x[7];
-  double lam, ni, cur, ini;
-  int nBadLM, q, it, trials, maxIt;
-  bool ok, fixScale;
+  bool fixScale;
 };
-
-// optimize(maxIt) starts: iteration 0 re-initialises lambda (:77-81)
-ORBFE_HD inline void optsim3_lm_begin(OptSim3LM* s, int maxIt) {
-  s->lam = 0.0; s->ni = 2.0; s->cur = 0.0; s->ini = 0.0;
-  s->nBadLM = 0; s->q = 0; s->it = 0; s->trials = 0; s->maxIt = maxIt;
-  s->ok = true;
-}
 
 // solve (H + lam I) x = b and form the trial Sim3(x) * est (VertexSim3Expmap::oplusImpl: x[6] = 0 with _fix_scale, written
 // into the solver's own x, which computeScale reads afterwards)
-ORBFE_HD inline void optsim3_lm_propose(OptSim3LM* s) {
-  s->ok = optsim3_solve7(s->S, s->lam, s->S + 28, s->x);
-  if (s->fixScale) s->x[6] = 0.0;
+ORBFE_HD inline void optsim3_lm_propose(G2oLM<7>* s, OptSim3Vertex* v) {
+  s->ok = g2o_solve_ldlt<7>(s->S, s->lam, s->S + 28, s->x);
+  if (v->fixScale) s->x[6] = 0.0;
   OptSim3 up;
   optsim3_exp(s->x, &up);
-  optsim3_mul(up, s->est, &s->trial);
-}
-
-ORBFE_HD inline void optsim3_lm_after_full(OptSim3LM* s) {
-#pragma unroll
-  for (int j = 0; j < 7; j++) s->S[28 + j] = -s->S[28 + j];
-  s->cur = s->ini = s->S[35];
-  if (s->it == 0) {  // computeLambdaInit: tau * max |H_jj| (:166-180)
-    double mx = 0.0;
-    mx = fmax(fabs(s->S[0]), mx); mx = fmax(fabs(s->S[7]), mx); mx = fmax(fabs(s->S[13]), mx); mx = fmax(fabs(s->S[18]), mx);
-    mx = fmax(fabs(s->S[22]), mx); mx = fmax(fabs(s->S[25]), mx); mx = fmax(fabs(s->S[27]), mx);
-    s->lam = 1e-5 * mx;
-    s->ni = 2.0;
-    s->nBadLM = 0;
-  }
-  s->q = 0;
-  optsim3_lm_propose(s);
-}
-
-// temp: the robust chi2 at s->trial.  Returns what runs next; on kOptSim3Trial s->trial is the next trial
-ORBFE_HD inline int optsim3_lm_after_trial(OptSim3LM* s, double temp) {
-  if (!s->ok) temp = DBL_MAX;  // (:126-127)
-  const double* b = s->S + 28;
-  double scale = 0.0;  // computeScale (:182-189)
-#pragma unroll
-  for (int j = 0; j < 7; j++) scale = scale + s->x[j] * (s->lam * s->x[j] + b[j]);
-  scale = scale + 1e-3;
-  const double rho = (s->cur - temp) / scale;
-  s->trials++;
-  if (rho > 0 && isfinite(temp)) {  // (:134-147)
-    const double tt = 2 * rho - 1;
-    const double alpha = fmin(1.0 - tt * tt * tt, 2.0 / 3.0);
-    s->lam = s->lam * fmax(1.0 / 3.0, alpha);
-    s->ni = 2.0;
-    s->cur = temp;
-    s->est = s->trial;
-  } else {
-    s->lam = s->lam * s->ni;
-    s->ni = s->ni * 2;
-  }
-  s->q++;
-  if (rho < 0 && s->q < 10) {  // (:149)
-    optsim3_lm_propose(s);
-    return kOptSim3Trial;
-  }
-  s->it++;
-  bool stop = (s->q == 10 || rho == 0);  // (:151-152)
-  if (!stop) {
-    if ((s->ini - s->cur) * 1e3 < s->ini) s->nBadLM++;  // Stop criterium (Raul) (:154-161)
-    else s->nBadLM = 0;
-    stop = s->nBadLM >= 3;
-  }
-  return (stop || s->it == s->maxIt) ? kOptSim3Done : kOptSim3Full;
+  optsim3_mul(up, v->est, &v->trial);
 }
 
 // a pair is erased when e12->chi2() > th2 || e21->chi2() > th2 (src/Optimizer.cc:1274, :1309): double against the float

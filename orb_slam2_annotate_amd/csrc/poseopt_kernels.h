@@ -4,32 +4,9 @@
 #include <stdint.h>
 
 #include "match_kernels.h"
+#include "poseopt_math.h"  // PoseOptProblem, PoseOptResult, the constants
 
 namespace orbfe {
-
-constexpr int kPoseOptThreads = 256;   // T: lane t of the workgroup owns edges t, t + T, t + 2T, ...
-constexpr int kPoseOptMaxEdges = 16384;  // the frame limit of include/orbfe.h
-// Edge constants (Xw, obs, invSigma2: 7 floats = 28 bytes) are staged in LDS for problems of up to this many edges and re-read
-// from global memory above it.  A CU has 160 KiB of LDS, of which one workgroup may declare 64 KiB statically: 2048 edges
-// take 56 KiB, the reduction scratch and the pose broadcast 2 KiB more, and two problems still share a CU.  ORB-SLAM2 asks
-// for at most 2000 features per frame.
-constexpr int kPoseOptLdsEdges = 2048;
-
-// One problem of a call.  Array form: edges [off, off + n) of the edge arrays.  Table form: n = features of the frame, the
-// kernel makes the edges itself.
-struct PoseOptProblem {
-  int32_t off, n;
-  float K5[5];    // fx fy cx cy bf
-  float Tcw[16];  // the start pose (row-major 4 x 4)
-  float pad;
-};
-
-struct PoseOptResult {
-  int32_t nInliers, nEdges, rounds, pad;
-  int32_t iterations[4], trials[4];
-  double lambda[4], chi2[4];
-  float Tcw[16];
-};
 
 struct PoseOptArgs {
   const PoseOptProblem* prob;

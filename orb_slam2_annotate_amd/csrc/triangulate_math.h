@@ -7,11 +7,7 @@
 #include <float.h>
 #include <math.h>
 
-#if defined(__HIPCC__)
-#define ORBFE_HD __host__ __device__
-#else
-#define ORBFE_HD
-#endif
+#include "g2o_math.h"  // ORBFE_HD
 // the sweep loop of tri_null_vector ends when no lane of the wave rotated anything (a lane that is done rotates nothing in
 // further sweeps, so its result does not depend on its neighbours); on the host the "wave" is the one pair
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -36,21 +36,22 @@ void solve(const OptSim3Problem& pr, const float* A, const float* B, const float
   const OptSim3Cam K2 = {(double)pr.cam2[0], (double)pr.cam2[1], (double)pr.cam2[2], (double)pr.cam2[3]};
   const double delta = (double)pr.delta;
   const bool fixScale = pr.fixScale != 0;
-  OptSim3LM lm;
-  lm.fixScale = fixScale;
-  optsim3_from_record(pr.sim3, &lm.est);
+  G2oLM<7> lm;
+  OptSim3Vertex vx;
+  vx.fixScale = fixScale;
+  optsim3_from_record(pr.sim3, &vx.est);
   int rounds = 0, nBad = 0, nIn = 0, maxIt = 5;
   bool early = true;
   for (int r = 0; r < 2; r++) { res->iterations[r] = 0; res->trials[r] = 0; res->lambda[r] = 0.0; res->chi2[r] = 0.0; }
   if (n > 0) {
     for (int i = 0; i < n; i++) bad[i] = 0;
     for (int rnd = 0; rnd < 2; rnd++) {
-      optsim3_lm_begin(&lm, maxIt);
-      int cmd = kOptSim3Full;
-      while (cmd != kOptSim3Done) {
+      g2o_lm_begin(&lm, maxIt);
+      int cmd = kG2oLMFull;
+      while (cmd != kG2oLMDone) {
         OptSim3Eval E;
-        if (cmd == kOptSim3Full) {
-          optsim3_eval_at(lm.est, &E);
+        if (cmd == kG2oLMFull) {
+          optsim3_eval_at(vx.est, &E);
           static double part[kOptSim3Sums][kLanes];
           for (int lane = 0; lane < kLanes; lane++) {
             double acc[kOptSim3Sums];
@@ -64,10 +65,10 @@ void solve(const OptSim3Problem& pr, const float* A, const float* B, const float
             for (int k = 0; k < kOptSim3Sums; k++) part[k][lane] = acc[k];
           }
           for (int k = 0; k < kOptSim3Sums; k++) lm.S[k] = tree(part[k]);
-          optsim3_lm_after_full(&lm);
-          cmd = kOptSim3Trial;
+          cmd = g2o_lm_after_full(&lm);
+          optsim3_lm_propose(&lm, &vx);
         } else {
-          optsim3_eval_at(lm.trial, &E);
+          optsim3_eval_at(vx.trial, &E);
           double part[kLanes];
           for (int lane = 0; lane < kLanes; lane++) {
             double sum = 0.0;
@@ -79,7 +80,7 @@ void solve(const OptSim3Problem& pr, const float* A, const float* B, const float
             }
             part[lane] = sum;
           }
-          cmd = optsim3_lm_after_trial(&lm, tree(part));
+          cmd = g2o_lm_after_trial(&lm, tree(part), &vx.est, vx.trial, [&] { optsim3_lm_propose(&lm, &vx); });
         }
       }
       int erased = 0, kept = 0;
@@ -100,10 +101,10 @@ void solve(const OptSim3Problem& pr, const float* A, const float* B, const float
       }
     }
   }
-  if (early) optsim3_from_record(pr.sim3, &lm.est);
-  for (int k = 0; k < 4; k++) res->sim3[k] = lm.est.q[k];
-  for (int k = 0; k < 3; k++) res->sim3[4 + k] = lm.est.t[k];
-  res->sim3[7] = lm.est.s;
+  if (early) optsim3_from_record(pr.sim3, &vx.est);
+  for (int k = 0; k < 4; k++) res->sim3[k] = vx.est.q[k];
+  for (int k = 0; k < 3; k++) res->sim3[4 + k] = vx.est.t[k];
+  res->sim3[7] = vx.est.s;
   res->nIn = nIn; res->nBad = nBad; res->rounds = rounds; res->pad = 0;
 }
 
