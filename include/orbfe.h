@@ -914,6 +914,62 @@ int orbfe_initializer_normalize(int n_keys, const float *keys_xy /*[n*2]*/, doub
  * library does not restate rand().  n < 8 with sets, NULL arrays or a draw outside its range return ORBFE_ERR_INVALID. */
 int orbfe_initializer_sets_from_draws(int n, int n_sets, const int32_t *draws /*[H*8]*/, int32_t *sets /*[H*8]*/);
 
+/* Initializer::ReconstructH (:653-824) / ReconstructF (:536-642) up to their order-dependent tails: what Initialize does with
+ * the chosen model.  ONE kernel launch, one workgroup of 256 lanes per (problem, hypothesis): the 8 motion hypotheses of an H
+ * problem (Faugeras, :667-775, in the reference's index order: 0-3 the case d' = d2, 4-7 the case d' = -d2) or the 4 of an F
+ * problem ((R1,t) (R2,t) (R1,-t) (R2,-t) of DecomposeE, :546-566, :1034-1057), and for each of them CheckRT (:913-1029) over
+ * the problem's inlier pairs.  The tails (:568-641, :778-823) are replayed on the host from n_good and cos_sel
+ * (include/orbfe_initializer_replay.hpp, C++ orbfe_cpp::Initializer::Reconstruct / Initialize, Python Initializer).
+ * Problem k owns pairs [pair_off[k], pair_off[k+1]) (u1 v1 u2 v2 as for orbfe_initializer_ransac*), model_kind[k] =
+ * ORBFE_INIT_MODEL_H or _F, model[9 k ..] = H21 or F21 row-major, K4[4 k ..] = fx fy cx cy, sigma[k] = mSigma and the
+ * ceil(n_k / 32) words inlier_words[in_word_off[k] ..] = vbMatchesInliers in the mask format of orbfe_initializer_ransac*
+ * (pair i at bit i & 31 of word i >> 5; bits past n_k are ignored).  in_word_off[k+1] - in_word_off[k] must be ceil(n_k / 32).
+ * Arithmetic is binary64 on inputs widened from float, in a fixed order: equal inputs give equal bytes, and the multi form
+ * equals the single calls byte for byte.  K.inv() is its closed form.  The 3 x 3 SVD (of K^-1 H21 K, :673; of K^T F21 K,
+ * :1037) is a one-sided Jacobi iteration on the columns (pair order (0,1) (0,2) (1,2), a rotation skipped when
+ * |a_p . a_q| <= DBL_EPSILON |a_p| |a_q|, at most 30 sweeps), singular values descending, u_i = A v_i / w_i for i = 0, 1 and
+ * u_2 = +-(u_0 x u_1) with the sign of (u_0 x u_1) . (A v_2), + when that is 0 -- E21 has rank 2, a normalised A v_2 would be
+ * noise.  The signs of the singular vectors are free as in any SVD and permute the hypotheses among themselves (H: 0 <-> 2,
+ * 1 <-> 3 within each group of four; F: t <-> -t, R1 <-> R2).  The 4 x 4 null vector of Triangulate (:829-842) is the Jacobi
+ * routine of orbfe_triangulate_new_points.  The reference computes in CV_32F with cv::SVD: results agree with it to float
+ * rounding and are NOT bit-identical to the CV_32F cv::SVD path; a pair within float rounding of a threshold may fall on the
+ * other side.  Every comparison is written as the reference writes it (`!isfinite`, `z <= 0 && cos < 0.99998` twice,
+ * `squareError > th2` twice with th2 = 4 sigma^2), so NaN takes the reference's branches.
+ * An H problem whose singular values meet `d1/d2 < 1.00001 || d2/d3 < 1.00001` (:684, as written: a NaN or inf ratio does not)
+ * has problem_status ORBFE_RECON_DEGENERATE: its 8 slots stay, with R, t, the points and the flags zero and every n_good 0.
+ * Written by the call: hyp_off [K+1] (8 per H problem, 4 per F problem) and slot_off [K+1] (slot_off[k+1] - slot_off[k] =
+ * hypotheses of k times n_k).  With G = hyp_off[K] and S = slot_off[K], per hypothesis g: R[9 g ..] row-major, t[3 g ..]
+ * (unit), n_good[g] = CheckRT's return value (an integer sum in a fixed tree; no floating-point atomics anywhere), cos_sel[g]
+ * = the element at index min(50, n_sel - 1) of the ascending order of the finite cosines of the counted pairs (:1018-1023;
+ * found exactly, by bisection on an order-preserving 64-bit key; 0.0 when there is none; the device takes no acos: parallax =
+ * acos(cos_sel) 180 / pi belongs to the replay), hyp_status[g] = ORBFE_RECON_OK, or ORBFE_RECON_NONFINITE when a counted pair's
+ * cosine is not finite (it counts in n_good and is left out of the selection: the reference sorts a NaN there, which is
+ * undefined).  Per (hypothesis g of problem k, pair i of k) at slot s = slot_off[k] + (g - hyp_off[k]) n_k + i: x3d[3 s ..] =
+ * the triangulated point in camera 1 as it came out, pair_flags[s] bit 0 = the pair added 1 to n_good, bit 1 = vbGood (bit 0
+ * and cos < 0.99998); zero for a pair whose inlier bit is clear.  Per problem: problem_status[k], n_inliers[k] = N of :540-543.
+ * Returns ORBFE_ERR_INVALID before anything is enqueued, leaving the thread usable, for: NULL arrays (x3d and pair_flags
+ * included, even when S = 0), offsets that do not start at 0, decrease, or do not end at n_pairs / n_words, a problem whose
+ * word count is not ceil(n_k / 32), a model kind other than the two, a non-finite entry of model or K4, fx or fy equal to 0, a
+ * sigma that is not finite or <= 0, n_problems outside [0, 4096], more than 2^31 - 1 slots.  A problem without pairs or with an
+ * all-zero mask is legal (every n_good 0, cos_sel 0.0); a call without problems returns ORBFE_OK without a launch.  Runs on the
+ * calling thread's matcher stream and is complete on return. */
+enum { ORBFE_RECON_OK = 0, ORBFE_RECON_NONFINITE = 1 };
+enum { ORBFE_RECON_PROBLEM_OK = 0, ORBFE_RECON_DEGENERATE = 1 };
+
+int orbfe_initializer_reconstruct_multi(int device, int n_problems, int n_pairs, int n_words, const int32_t *pair_off /*[K+1]*/,
+                                        const float *pairs /*[N*4]*/, const int32_t *model_kind /*[K]*/,
+                                        const double *model /*[K*9]*/, const float *K4 /*[K*4]*/, const float *sigma /*[K]*/,
+                                        const uint32_t *inlier_words /*[W]*/, const int32_t *in_word_off /*[K+1]*/,
+                                        int32_t *hyp_off /*[K+1]*/, int32_t *slot_off /*[K+1]*/, double *R /*[G*9]*/,
+                                        double *t /*[G*3]*/, int32_t *n_good /*[G]*/, double *cos_sel /*[G]*/,
+                                        uint8_t *hyp_status /*[G]*/, double *x3d /*[S*3]*/, uint8_t *pair_flags /*[S]*/,
+                                        uint8_t *problem_status /*[K]*/, int32_t *n_inliers /*[K]*/);
+/* One problem; equal to the multi form with n_problems = 1.  G = 8 or 4, S = G n_pairs, inlier_words [ceil(n / 32)]. */
+int orbfe_initializer_reconstruct(int device, int n_pairs, const float *pairs, int model_kind, const double *model /*[9]*/,
+                                  const float *K4 /*[4]*/, float sigma, const uint32_t *inlier_words, double *R, double *t,
+                                  int32_t *n_good, double *cos_sel, uint8_t *hyp_status, double *x3d, uint8_t *pair_flags,
+                                  uint8_t *problem_status, int32_t *n_inliers);
+
 /* -------------------------------------------------------------------------- */
 /* Optimizer::OptimizeSim3 (src/Optimizer.cc:1116-1323)                        */
 /* -------------------------------------------------------------------------- */

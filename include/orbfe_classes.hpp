@@ -1061,12 +1061,13 @@ class Sim3Solver {
   }
 };
 
-// Initializer (src/Initializer.cc) up to the choice of the model.  keys1 = the reference frame's mvKeysUn points (x y
+// Initializer (src/Initializer.cc).  keys1 = the reference frame's mvKeysUn points (x y
 // interleaved), sigma and iterations as the reference's constructor takes them (:36-43).  FindModels does what Initialize does
 // from :57 to :127: compacts vMatches12 into mvMatches12 (:64-73), builds mvSets from the caller's RandomInt values (draws
 // [iterations * 8], draws[8 h + j] in [0, N - j); :93-108), evaluates every hypothesis of both models in ONE device call
-// (orbfe_initializer_ransac) and replays the two scans (InitializerReplay, orbfe_initializer_replay.hpp).  The caller then
-// runs its own unchanged ReconstructH / ReconstructF on H21 / vbMatchesInliersH or F21 / vbMatchesInliersF.
+// (orbfe_initializer_ransac) and replays the two scans (InitializerReplay, orbfe_initializer_replay.hpp).  Reconstruct runs
+// ReconstructH / ReconstructF on the chosen model (a second device call and the replay of the tail), and Initialize is both:
+// it returns what the reference's Initialize returns, with no reference or OpenCV code on the path.
 class Initializer {
  public:
   struct Models {
@@ -1077,6 +1078,7 @@ class Initializer {
     std::vector<bool> vbMatchesInliersH, vbMatchesInliersF;  // indexed like mvMatches12
     std::vector<std::pair<int, int>> mvMatches12;
     std::vector<int32_t> mvSets;       // [iterations * 8]
+    std::vector<float> pairs;          // [N * 4] u1 v1 u2 v2 of mvMatches12
     // per (set, model), the layout of orbfe_initializer_ransac
     std::vector<double> score, model, h12;
     std::vector<uint8_t> status;
@@ -1123,7 +1125,75 @@ class Initializer {
     InitializerReplay::inliers(N, pF.best, ORBFE_INIT_MODEL_F, m.words.data(), m.vbMatchesInliersF);
     m.RH = InitializerReplay::ratio(m.SH, m.SF);  // :124
     m.chooseH = InitializerReplay::choose_h(m.RH);
+    m.pairs = std::move(pairs);
     return m;
+  }
+
+  // What Initialize returns (:52-53), and the device's per-hypothesis results of orbfe_initializer_reconstruct.
+  struct Reconstruction {
+    bool success = false;
+    double R21[9] = {}, t21[3] = {};    // row-major / unit; meaningful when success
+    std::vector<float> vP3D;            // [n1 * 3], indexed by the reference key (vMatches12[i].first)
+    std::vector<bool> vbTriangulated;   // [n1]
+    double parallax = 0.0;              // of the hypothesis taken, degrees
+    int modelKind = ORBFE_INIT_MODEL_F, best = -1;
+    int nHyp = 0, nInliers = 0;
+    uint8_t problemStatus = ORBFE_RECON_PROBLEM_OK;
+    std::vector<double> R, t, cosSel, x3d;
+    std::vector<int32_t> nGood;
+    std::vector<uint8_t> hypStatus, pairFlags;
+  };
+
+  // ReconstructH or ReconstructF (:129-131) on the model FindModels chose: ONE device call for the 8 or 4 hypotheses
+  // (orbfe_initializer_reconstruct), then the replay of the tail (InitializerReplay::reconstruct_h / _f).  K4 = fx fy cx cy.
+  Reconstruction Reconstruct(const Models& m, const float K4[4], double minParallax = 1.0, int minTriangulated = 50) const {
+    Reconstruction r;
+    const size_t n1 = keys1_.size() / 2, N = m.mvMatches12.size();
+    r.vP3D.assign(n1 * 3, 0.0f);
+    r.vbTriangulated.assign(n1, false);
+    r.modelKind = m.chooseH ? ORBFE_INIT_MODEL_H : ORBFE_INIT_MODEL_F;
+    if ((m.chooseH ? m.bestH : m.bestF) < 0) return r;  // an empty model: nothing to reconstruct
+    r.nHyp = m.chooseH ? 8 : 4;
+    const size_t G = (size_t)r.nHyp;
+    std::vector<uint32_t> words;
+    InitializerReplay::pack(m.chooseH ? m.vbMatchesInliersH : m.vbMatchesInliersF, words);
+    words.push_back(0u);  // (never empty)
+    r.R.assign(G * 9, 0.0); r.t.assign(G * 3, 0.0); r.cosSel.assign(G, 0.0); r.nGood.assign(G, 0); r.hypStatus.assign(G, 0);
+    r.x3d.assign(G * N * 3 + 1, 0.0); r.pairFlags.assign(G * N + 1, 0);
+    int32_t nInl = 0;
+    check(orbfe_initializer_reconstruct(device_, (int)N, m.pairs.data(), r.modelKind, m.chooseH ? m.H21 : m.F21, K4, sigma_, words.data(),
+                                        r.R.data(), r.t.data(), r.nGood.data(), r.cosSel.data(), r.hypStatus.data(), r.x3d.data(),
+                                        r.pairFlags.data(), &r.problemStatus, &nInl),
+          "Initializer::Reconstruct");
+    r.x3d.resize(G * N * 3); r.pairFlags.resize(G * N);
+    r.nInliers = nInl;
+    if (r.problemStatus == ORBFE_RECON_DEGENERATE) return r;  // :684-687
+    double par[8];
+    for (size_t g = 0; g < G; g++) par[g] = InitializerReplay::parallax_degrees(r.nGood[g], r.cosSel[g]);
+    const InitializerReplay::Outcome o = m.chooseH ? InitializerReplay::reconstruct_h(nInl, r.nGood.data(), par, minParallax, minTriangulated)
+                                                   : InitializerReplay::reconstruct_f(nInl, r.nGood.data(), par, minParallax, minTriangulated);
+    if (!o.success) return r;
+    r.success = true; r.best = o.best; r.parallax = par[o.best];
+    std::memcpy(r.R21, &r.R[9 * (size_t)o.best], sizeof r.R21);
+    std::memcpy(r.t21, &r.t[3 * (size_t)o.best], sizeof r.t21);
+    for (size_t i = 0; i < N; i++) {
+      const size_t s = (size_t)o.best * N + i, first = (size_t)m.mvMatches12[i].first;
+      if (r.pairFlags[s] & 1)  // :1011
+        for (int c = 0; c < 3; c++) r.vP3D[3 * first + (size_t)c] = (float)r.x3d[3 * s + (size_t)c];
+      r.vbTriangulated[first] = (r.pairFlags[s] & 2) != 0;  // :1014-1015
+    }
+    return r;
+  }
+
+  // Initializer::Initialize (:52-135): FindModels + Reconstruct on the chosen model
+  bool Initialize(const std::vector<float>& keys2, const std::vector<int>& vMatches12, const std::vector<int32_t>& draws,
+                  const float K4[4], double R21[9], double t21[3], std::vector<float>& vP3D, std::vector<bool>& vbTriangulated) const {
+    const Reconstruction r = Reconstruct(FindModels(keys2, vMatches12, draws), K4);
+    std::memcpy(R21, r.R21, sizeof r.R21);
+    std::memcpy(t21, r.t21, sizeof r.t21);
+    vP3D = r.vP3D;
+    vbTriangulated = r.vbTriangulated;
+    return r.success;
   }
 
  private:

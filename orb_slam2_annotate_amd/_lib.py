@@ -121,6 +121,7 @@ EXPORTS = [
     "orbfe_optimize_essential_graph", "orbfe_essential_graph_correct_points", "orbfe_essential_graph_correct_mappoints",
     "orbfe_block_sparse_solve7", "orbfe_mappoints_positions",
     "orbfe_initializer_ransac", "orbfe_initializer_ransac_multi", "orbfe_initializer_normalize", "orbfe_initializer_sets_from_draws",
+    "orbfe_initializer_reconstruct", "orbfe_initializer_reconstruct_multi",
 ]
 
 _lib = None
@@ -312,6 +313,8 @@ def load():
     L.orbfe_initializer_ransac.argtypes = [ci, ci, vp, vp, vp, C.c_float, ci] + [vp] * 7
     L.orbfe_initializer_normalize.argtypes = [ci, vp, vp]
     L.orbfe_initializer_sets_from_draws.argtypes = [ci, ci, vp, vp]
+    L.orbfe_initializer_reconstruct_multi.argtypes = [ci, ci, ci, ci] + [vp] * 19
+    L.orbfe_initializer_reconstruct.argtypes = [ci, ci, vp, ci, vp, vp, C.c_float, vp] + [vp] * 9
     _lib = L
     return L
 

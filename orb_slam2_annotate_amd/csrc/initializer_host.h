@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "initializer_math.h"
+#include "initializer_reconstruct_math.h"
 
 namespace orbfe {
 
@@ -75,6 +76,66 @@ inline void init_layout(int K, const int32_t* pair_off, const int32_t* hyp_off, 
     const int h = hyp_off[k + 1] - hyp_off[k];
     hypProb->insert(hypProb->end(), (size_t)h, k);
     word_off[k + 1] = word_off[k] + 2 * h * p.words;
+  }
+}
+
+// orbfe_initializer_reconstruct*: NULL when the arguments are fine, else what is wrong with them.  N pairs and W inlier words
+// in all; G / slots receive the totals of hypotheses and of per-(hypothesis, pair) records when the offsets are fine.
+inline const char* recon_check(int K, int N, int W, const int32_t* pair_off, const float* pairs, const int32_t* model_kind,
+                               const double* model, const float* K4, const float* sigma, const uint32_t* inlier_words,
+                               const int32_t* in_word_off, const int32_t* hyp_off, const int32_t* slot_off, const double* R,
+                               const double* t, const int32_t* n_good, const double* cos_sel, const uint8_t* hyp_status,
+                               const double* x3d, const uint8_t* pair_flags, const uint8_t* problem_status,
+                               const int32_t* n_inliers) {
+  if (K < 0 || K > kInitHostMaxProblems) return "n_problems outside [0, 4096]";
+  if (N < 0 || W < 0 || N > INT32_MAX - 31) return "count negative or above 2^31 - 32";
+  if (!pair_off || !in_word_off || !hyp_off || !slot_off) return "NULL offsets";
+  if (K > 0 && (!model_kind || !model || !K4 || !sigma || !R || !t || !n_good || !cos_sel || !hyp_status || !problem_status ||
+                !n_inliers || !x3d || !pair_flags))
+    return "NULL problem or output array";
+  if (N > 0 && !pairs) return "NULL pair array";
+  if (W > 0 && !inlier_words) return "NULL inlier words";
+  if (!init_offsets_ok(pair_off, K, N)) return "pair_off is not monotone from 0 to n_pairs";
+  if (!init_offsets_ok(in_word_off, K, W)) return "in_word_off is not monotone from 0 to n_words";
+  size_t slots = 0;
+  for (int k = 0; k < K; k++) {
+    if (model_kind[k] != kInitH && model_kind[k] != kInitF) return "model_kind is neither ORBFE_INIT_MODEL_H nor _F";
+    for (int i = 0; i < 9; i++)
+      if (!isfinite(model[9 * (size_t)k + i])) return "model entry is not finite";
+    for (int i = 0; i < 4; i++)
+      if (!isfinite(K4[4 * (size_t)k + i])) return "K4 entry is not finite";
+    if (K4[4 * (size_t)k] == 0.0f || K4[4 * (size_t)k + 1] == 0.0f) return "fx or fy is 0";
+    if (!isfinite(sigma[k]) || !(sigma[k] > 0.0f)) return "sigma is not positive and finite";
+    const int n = pair_off[k + 1] - pair_off[k];
+    if (in_word_off[k + 1] - in_word_off[k] != (n + 31) / 32) return "a problem does not have ceil(n_k / 32) inlier words";
+    slots += (size_t)recon_hyps(model_kind[k]) * (size_t)n;
+    if (slots > (size_t)INT32_MAX) return "more than 2^31 - 1 (hypothesis, pair) records";
+  }
+  return nullptr;
+}
+
+// the arguments have passed recon_check: hyp_off / slot_off [K + 1], the problem records and the problem of every hypothesis
+inline void recon_layout(int K, const int32_t* pair_off, const int32_t* model_kind, const double* model, const float* K4,
+                         const float* sigma, const int32_t* in_word_off, int32_t* hyp_off, int32_t* slot_off,
+                         std::vector<ReconProblem>* probs, std::vector<int32_t>* hypProb) {
+  probs->clear();
+  hypProb->clear();
+  hyp_off[0] = 0;
+  slot_off[0] = 0;
+  for (int k = 0; k < K; k++) {
+    ReconProblem p = {};
+    p.pair0 = pair_off[k]; p.nPairs = pair_off[k + 1] - pair_off[k];
+    p.word0 = in_word_off[k];
+    p.hyp0 = hyp_off[k]; p.nHyp = recon_hyps(model_kind[k]);
+    p.slot0 = slot_off[k];
+    p.kind = model_kind[k];
+    p.sigma = sigma[k];
+    for (int i = 0; i < 4; i++) p.K[i] = K4[4 * (size_t)k + i];
+    for (int i = 0; i < 9; i++) p.model[i] = model[9 * (size_t)k + i];
+    probs->push_back(p);
+    hypProb->insert(hypProb->end(), (size_t)p.nHyp, k);
+    hyp_off[k + 1] = hyp_off[k] + p.nHyp;
+    slot_off[k + 1] = slot_off[k] + p.nHyp * p.nPairs;
   }
 }
 
