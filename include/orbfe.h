@@ -1273,6 +1273,136 @@ int orbfe_stereo_from_rgbd(int device, const float *kx, const float *ky, const f
                            const float *depth_image, int width, int height, int stride_floats,
                            float mbf, float *u_right, float *depth);
 
+/* ------------------------------------------------------------------------- */
+/* Observation graph: MapPoint::mObservations resident on the device, and the */
+/* four loops over it (covisibility votes, key-frame culling, normal / depth)  */
+/* ------------------------------------------------------------------------- */
+/* The table map point -> the key frames that see it, indexed by point SLOT (the slot space of an orbfe_mappoints table:
+ * one slot list serves both) and by KF SLOT (the caller keeps the KeyFrame* <-> kf slot map and gives each key frame
+ * its mnId).  One row of row_width entries per point slot (a power of two in 8 .. 256, fixed at create; an entry is the
+ * 8-byte orbfe_observation), and per point slot the live entry count, nObs (a stereo observation weighs 2, as
+ * MapPoint::AddObservation / EraseObservation count, src/MapPoint.cc:101-145), a bad flag and the kf slot of mpRefKF;
+ * per kf slot mnId, the camera centre Ow and a bad flag.  A slot that was never set counts as bad.
+ *
+ * Deviation (row order): the reference iterates std::map<KeyFrame*, size_t> in POINTER order, which differs from run
+ * to run.  This table keeps every row in ascending mnId of the observing key frame -- one of the orders the reference
+ * can take, and the one every result below is defined by.  It matters for the float sum of update_normal_depth and for
+ * which key frame becomes the reference after an erase ("mObservations.begin()": here the lowest remaining mnId).
+ *
+ * The host keeps a mirror of everything; the mutations below change the mirror alone -- they need no device and touch
+ * none -- and mark the rows they changed.  A call that reads the table on the device (votes, culling_counts,
+ * update_normal_depth*, get_row from the device) first rewrites the marked rows, each as a whole (at most 2 KB), then
+ * runs on the handle's one stream and is complete on return.  Every operand is checked on the host before anything is
+ * enqueued: slots out of range, NULL arrays and n < 0 return ORBFE_ERR_INVALID.  A handle serialises its own calls;
+ * creating one does not touch the device.  Without a device the reading calls return ORBFE_ERR_HIP: no CPU fallback.
+ * Limits: point_capacity <= 2^24, kf_capacity <= 2^20, point_capacity * row_width <= 2^28. */
+typedef struct orbfe_obsgraph orbfe_obsgraph;
+typedef struct orbfe_observation {
+  int32_t kf_slot;
+  uint16_t idx;   /* mObservations[pKF] */
+  uint8_t octave; /* pKF->mvKeysUn[idx].octave */
+  uint8_t flags;  /* bit 0: pKF->mvuRight[idx] >= 0 */
+} orbfe_observation;
+
+int orbfe_obsgraph_create(int device, int point_capacity, int kf_capacity, int row_width, orbfe_obsgraph **out);
+void orbfe_obsgraph_destroy(orbfe_obsgraph *g);
+/* Back to the state after create (the device memory stays with the handle). */
+int orbfe_obsgraph_clear(orbfe_obsgraph *g);
+/* kf_slot[i] holds key frame kf_id[i] (mnId >= 0) with camera centre Ow[3 i ..] (GetCameraCenter()) and isBad() = bad[i].
+ * Two kf slots never hold one id, and the id of a kf slot that rows still name cannot change (the rows are ordered by
+ * it): both return ORBFE_ERR_INVALID with nothing applied. */
+int orbfe_obsgraph_set_keyframes(orbfe_obsgraph *g, int n, const int32_t *kf_slot, const int64_t *kf_id, const float *Ow,
+                                 const uint8_t *bad);
+/* isBad() and mpRefKF (a kf slot, -1 = none) of n point slots.  The rows stay as they are: the kernels skip a bad point. */
+int orbfe_obsgraph_set_points(orbfe_obsgraph *g, int n, const int32_t *slot, const uint8_t *bad, const int32_t *ref_kf_slot);
+/* MapPoint::AddObservation(pKF, idx) (:101-114) n times, in order: a (slot, kf_slot) pair already present is ignored, as
+ * the count(pKF) early return does; nObs += stereo[i] ? 2 : 1.  The kf slot must have been set.  A full row returns
+ * ORBFE_ERR_CAPACITY with NOTHING of the call applied. */
+int orbfe_obsgraph_add_observations(orbfe_obsgraph *g, int n, const int32_t *slot, const int32_t *kf_slot, const uint16_t *idx,
+                                    const uint8_t *octave, const uint8_t *stereo);
+/* MapPoint::EraseObservation(pKF) (:119-145) n times, in order: an absent pair is ignored; nObs drops by 1 or 2; if the
+ * erased key frame was the reference, the reference moves to the row's first remaining entry; nObs <= 2 marks the point
+ * bad and clears its row (SetBadFlag, :164-182; nObs keeps its value) -- became_bad[i] = 1 (may be NULL).  Deviation: the
+ * reference of a row that empties becomes -1 (the reference dereferences begin() of an empty map). */
+int orbfe_obsgraph_erase_observations(orbfe_obsgraph *g, int n, const int32_t *slot, const int32_t *kf_slot, uint8_t *became_bad);
+/* The map-point part of KeyFrame::SetBadFlag (src/KeyFrame.cc:488 ff.): EraseObservation(kf) on every point that lists
+ * the key frame, the key frame marked bad; out_slots = the points that became bad, ascending, *n_out of them.  More than
+ * `capacity` returns ORBFE_ERR_CAPACITY with *n_out set and nothing applied.  The covisibility edges and the spanning
+ * tree stay with the caller. */
+int orbfe_obsgraph_erase_keyframe(orbfe_obsgraph *g, int kf_slot, int32_t *out_slots, int capacity, int *n_out);
+/* Test read-back of one point slot: from the host mirror (from_device = 0; needs no device) or from the device table
+ * (from_device != 0, after the pending rows were written).  entries holds row_width records, the live ones first, the
+ * rest zero. */
+int orbfe_obsgraph_get_row(orbfe_obsgraph *g, int from_device, int slot, orbfe_observation *entries, int32_t *n_entries,
+                           int32_t *n_obs, uint8_t *bad, int32_t *ref_kf_slot);
+
+/* The counting loop of KeyFrame::UpdateConnections (src/KeyFrame.cc:326-344) and of Tracking::UpdateLocalKeyFrames
+ * (src/Tracking.cc:1346-1362) for n_queries point lists in one launch: query q is q_slots [q_offsets[q], q_offsets[q+1])
+ * -- a key frame's (a frame's) non-NULL mvpMapPoints.  Bad points are skipped; every entry of every other point's row
+ * adds 1 to its key frame's counter, except entries of self_kf_slot[q] (-1: none; the mnId == mnId test of :340).  A slot
+ * named twice votes twice.  Per query: the kf slots with a non-zero counter in ASCENDING KF-SLOT order and their
+ * counters, [q * capacity ..], count[q] of them; equal inputs give equal arrays.  A count above `capacity` fills
+ * `capacity` entries and returns ORBFE_ERR_CAPACITY (every count[] is still set).  At most 65535 queries per call.
+ * The counters are int32 in the workgroup's LDS for kf_capacity <= 8192, above that in a workspace of
+ * n_queries * kf_capacity int32. */
+int orbfe_obsgraph_votes(orbfe_obsgraph *g, int n_queries, const int32_t *q_offsets, const int32_t *q_slots,
+                         const int32_t *self_kf_slot, int capacity, int32_t *kf_slot_out, int32_t *weight_out, int32_t *count);
+/* The counting of LocalMapping::KeyFrameCulling (src/LocalMapping.cc:729-769) for n_kf candidates in one launch.
+ * Candidate c is kf_slot[c]; its features slot / octave [offsets[c], offsets[c+1]) are the ones that pass the host-side
+ * tests of :732-740 (a map point, and for stereo / RGB-D 0 <= mvDepth <= mThDepth), each with mvKeysUn[i].octave.  Per
+ * listed feature: a bad point is skipped; n_mps[c]++; if nObs > 3, the row's entries with kf_slot != kf_slot[c] and
+ * octave_i <= octave + 1 are counted, and 3 or more give n_redundant[c]++ (the reference's early break does not change
+ * ">= 3").  The counts describe the table as it stands at entry; the caller culls when n_redundant > 0.9 * n_mps. */
+int orbfe_obsgraph_culling_counts(orbfe_obsgraph *g, int n_kf, const int32_t *kf_slot, const int32_t *offsets, const int32_t *slot,
+                                  const uint8_t *octave, int32_t *n_mps, int32_t *n_redundant);
+/* MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:360-404) for n point slots at the positions pos[3 i ..]
+ * (scale_factors = mvScaleFactors, n_levels = mnScaleLevels, 1 .. 256).  A restatement of :378-402 as OpenCV's
+ * Mat / double and Mat + MatExpr evaluate them, in IEEE binary32 with no contraction, over the row left to right
+ * (ascending mnId); it equals the reference up to the observer order and the last place:
+ *   per entry k: d = P - Ow_k (per component); nrm = sqrt(sum (double)d_i^2); a = (float)(1.0 / nrm);
+ *                normal_i = normal_i + d_i * a;
+ *   at the end:  normal_i = normal_i * (float)(1.0 / n), n = the row's entry count;
+ *   PC = P - Ow_ref; dist = (float)sqrt(sum (double)PC_i^2); max_dist = dist * scale_factors[level], level = the octave of
+ *   the reference key frame's entry; min_dist = max_dist / scale_factors[n_levels - 1].
+ * The sum over a row is sequential by definition: lanes compute the terms, one chain adds them in row order.
+ * valid[i] = 0 -- and normal / min_dist / max_dist [i] are NOT written -- for a bad point, an empty row, and a reference
+ * key frame that is not in the row (deviation: the reference's observations[pRefKF] would silently insert index 0).  A
+ * reference entry whose octave is not below n_levels returns ORBFE_ERR_INVALID before anything is enqueued. */
+int orbfe_obsgraph_update_normal_depth(orbfe_obsgraph *g, int n, const int32_t *slot, const float *pos, const float *scale_factors,
+                                       int n_levels, float *normal, float *min_dist, float *max_dist, uint8_t *valid);
+/* The same on a resident map-point table: pos is read from mp's slot and normal / min_dist / max_dist are written into
+ * it, bit-equal to the array form; only the slot list travels.  Slots with valid = 0 keep what they hold.  Both handles
+ * must be on one device and g's point_capacity must not exceed mp's capacity, and no slot may be named twice
+ * (ORBFE_ERR_INVALID).  Takes g's serialisation, then mp's. */
+int orbfe_obsgraph_update_normal_depth_mappoints(orbfe_obsgraph *g, orbfe_mappoints *mp, int n, const int32_t *slot,
+                                                 const float *scale_factors, int n_levels, uint8_t *valid);
+
+/* KeyFrame::UpdateConnections :347-393 over ONE query's votes, KFcounter = (kf_id, weight)[n] (mnIds, any order, weights
+ * positive).  th = 15; when nobody reaches it the maximum alone is connected.  ordered_id / ordered_weight:
+ * mvpOrderedConnectedKeyFrames / mvOrderedWeights; connect_id / connect_weight: who receives AddConnection(this, weight),
+ * in ascending id; *parent_id: mvpOrderedConnectedKeyFrames.front() (for mbFirstConnection; -1 when n = 0, where the
+ * reference returns early and every count is 0).  mConnectedKeyFrameWeights is the input itself.  Every output array
+ * holds n entries.  Deviation: ties break by mnId where the reference breaks them by pointer -- sort() of
+ * pair<int, KeyFrame*> ascends, so after push_front equal weights come out in DESCENDING id, and the strict > of the nmax
+ * scan keeps the LOWEST id.  Host code: needs no device. */
+int orbfe_obsgraph_update_connections(int n, const int64_t *kf_id, const int32_t *weight, int64_t *ordered_id,
+                                      int32_t *ordered_weight, int *n_ordered, int64_t *connect_id, int32_t *connect_weight,
+                                      int *n_connect, int64_t *parent_id);
+/* Tracking::UpdateLocalKeyFrames :1364-1454 over ONE frame's votes, keyframeCounter = (kf_id, weight, bad = isBad())[n].
+ * K1: the voted key frames in ascending id, bad ones skipped, pKFmax under strict >.  K2: for each K1 key frame, in
+ * order, the first eligible (not bad, not yet local) of its best 10 covisibles, the first eligible child, and its
+ * parent when not yet local -- the reference's break after a parent is added leaves the WHOLE loop, and the loop stops
+ * once more than 80 key frames are local.  The loop's end iterator is taken before anything is appended, so it visits
+ * the K1 entries while the vector grows.  Record i carries what the walk reads of key frame i:
+ * GetBestCovisibilityKeyFrames as neigh_ids / neigh_bad [neigh_offsets[i], neigh_offsets[i+1]) (a longer list may be
+ * given: 10 are read), GetChilds() likewise (give them in ascending id), GetParent() as parent_id[i] (-1: none).
+ * out_ids: mvpLocalKeyFrames, *n_out of them (more than `capacity`: ORBFE_ERR_CAPACITY, *n_out set); *ref_id: pKFmax
+ * (-1: none, mpReferenceKF unchanged).  Host code: needs no device. */
+int orbfe_obsgraph_local_keyframes(int n, const int64_t *kf_id, const int32_t *weight, const uint8_t *bad,
+                                   const int32_t *neigh_offsets, const int64_t *neigh_ids, const uint8_t *neigh_bad,
+                                   const int32_t *child_offsets, const int64_t *child_ids, const uint8_t *child_bad,
+                                   const int64_t *parent_id, int64_t *out_ids, int capacity, int *n_out, int64_t *ref_id);
+
 #ifdef __cplusplus
 }
 #endif

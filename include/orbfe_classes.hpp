@@ -622,6 +622,114 @@ class ORBmatcher {
   int device_;
 };
 
+// MapPoint::mObservations resident on the device (orbfe_obsgraph): point slots are the MapPointTable's, kf slot <-> KeyFrame* is
+// the caller's map, as are the spanning tree, mvpMapPoints and the map mutex.  Mutations change the host mirror alone; the
+// calls that read the table on the device write the changed rows first.
+class ObservationGraph {
+ public:
+  struct Votes { std::vector<int32_t> kfSlot, weight; };  // ascending kf slot
+  struct Connections {  // KeyFrame::UpdateConnections: ids are mnIds
+    std::vector<int64_t> orderedId, connectId;
+    std::vector<int32_t> orderedWeight, connectWeight;
+    int64_t parentId = -1;
+  };
+  struct NormalDepth { std::vector<float> normal, minDist, maxDist; std::vector<uint8_t> valid; };
+  ObservationGraph(int pointCapacity, int kfCapacity, int rowWidth = 64, int device = 0) : kfCap_(kfCapacity) {
+    check(orbfe_obsgraph_create(device, pointCapacity, kfCapacity, rowWidth, &h_), "ObservationGraph");
+  }
+  ~ObservationGraph() { orbfe_obsgraph_destroy(h_); }
+  ObservationGraph(const ObservationGraph&) = delete;
+  ObservationGraph& operator=(const ObservationGraph&) = delete;
+  orbfe_obsgraph* handle() const { return h_; }
+  void SetKeyFrames(const std::vector<int32_t>& kfSlot, const std::vector<int64_t>& mnId, const std::vector<float>& Ow,
+                    const std::vector<uint8_t>& bad) {
+    const size_t n = kfSlot.size();
+    if (mnId.size() != n || Ow.size() != 3 * n || bad.size() != n) throw std::invalid_argument("ObservationGraph::SetKeyFrames: one entry per kf slot");
+    check(orbfe_obsgraph_set_keyframes(h_, (int)n, kfSlot.data(), mnId.data(), Ow.data(), bad.data()), "ObservationGraph::SetKeyFrames");
+  }
+  void SetPoints(const std::vector<int32_t>& slot, const std::vector<uint8_t>& bad, const std::vector<int32_t>& refKfSlot) {
+    if (bad.size() != slot.size() || refKfSlot.size() != slot.size()) throw std::invalid_argument("ObservationGraph::SetPoints: one entry per slot");
+    check(orbfe_obsgraph_set_points(h_, (int)slot.size(), slot.data(), bad.data(), refKfSlot.data()), "ObservationGraph::SetPoints");
+  }
+  // MapPoint::AddObservation per entry
+  void AddObservations(const std::vector<int32_t>& slot, const std::vector<int32_t>& kfSlot, const std::vector<uint16_t>& idx,
+                       const std::vector<uint8_t>& octave, const std::vector<uint8_t>& stereo) {
+    const size_t n = slot.size();
+    if (kfSlot.size() != n || idx.size() != n || octave.size() != n || stereo.size() != n)
+      throw std::invalid_argument("ObservationGraph::AddObservations: one entry per observation");
+    check(orbfe_obsgraph_add_observations(h_, (int)n, slot.data(), kfSlot.data(), idx.data(), octave.data(), stereo.data()),
+          "ObservationGraph::AddObservations");
+  }
+  // MapPoint::EraseObservation per entry; returns became-bad flags
+  std::vector<uint8_t> EraseObservations(const std::vector<int32_t>& slot, const std::vector<int32_t>& kfSlot) {
+    if (kfSlot.size() != slot.size()) throw std::invalid_argument("ObservationGraph::EraseObservations: one kf slot per slot");
+    std::vector<uint8_t> bad(slot.size() + 1, 0);
+    check(orbfe_obsgraph_erase_observations(h_, (int)slot.size(), slot.data(), kfSlot.data(), bad.data()), "ObservationGraph::EraseObservations");
+    bad.resize(slot.size());
+    return bad;
+  }
+  // the map-point part of KeyFrame::SetBadFlag; returns the slots of the points that became bad
+  std::vector<int32_t> EraseKeyFrame(int kfSlot) {
+    int n = 0;
+    std::vector<int32_t> out;
+    int rc = orbfe_obsgraph_erase_keyframe(h_, kfSlot, nullptr, 0, &n);
+    if (rc == ORBFE_ERR_CAPACITY) {
+      out.resize((size_t)n);
+      rc = orbfe_obsgraph_erase_keyframe(h_, kfSlot, out.data(), n, &n);
+    }
+    check(rc, "ObservationGraph::EraseKeyFrame");
+    out.resize((size_t)n);
+    return out;
+  }
+  // the votes of one point-slot list (a key frame's: self = its kf slot; a frame's: self = -1)
+  Votes VotesOf(const std::vector<int32_t>& pointSlots, int selfKfSlot = -1) const {
+    const int32_t off[2] = {0, (int32_t)pointSlots.size()}, self = selfKfSlot;
+    Votes v;
+    v.kfSlot.assign((size_t)kfCap_, 0); v.weight.assign((size_t)kfCap_, 0);
+    int32_t count = 0;
+    check(orbfe_obsgraph_votes(h_, 1, off, pointSlots.data(), &self, kfCap_, v.kfSlot.data(), v.weight.data(), &count), "ObservationGraph::VotesOf");
+    v.kfSlot.resize((size_t)count); v.weight.resize((size_t)count);
+    return v;
+  }
+  // KeyFrame::UpdateConnections :347-393 on a key frame's votes; mnIdOfSlot: kf slot -> mnId
+  static Connections UpdateConnections(const Votes& v, const std::vector<int64_t>& mnIdOfSlot) {
+    const size_t n = v.kfSlot.size();
+    std::vector<int64_t> id(n + 1);
+    for (size_t i = 0; i < n; i++) id[i] = mnIdOfSlot.at((size_t)v.kfSlot[i]);
+    Connections c;
+    c.orderedId.assign(n + 1, 0); c.orderedWeight.assign(n + 1, 0); c.connectId.assign(n + 1, 0); c.connectWeight.assign(n + 1, 0);
+    int no = 0, nc = 0;
+    check(orbfe_obsgraph_update_connections((int)n, id.data(), v.weight.data(), c.orderedId.data(), c.orderedWeight.data(), &no,
+                                            c.connectId.data(), c.connectWeight.data(), &nc, &c.parentId), "ObservationGraph::UpdateConnections");
+    c.orderedId.resize((size_t)no); c.orderedWeight.resize((size_t)no); c.connectId.resize((size_t)nc); c.connectWeight.resize((size_t)nc);
+    return c;
+  }
+  // LocalMapping::KeyFrameCulling's counts: candidate c = kfSlot[c] with features slot / octave [offsets[c], offsets[c+1])
+  void CullingCounts(const std::vector<int32_t>& kfSlot, const std::vector<int32_t>& offsets, const std::vector<int32_t>& slot,
+                     const std::vector<uint8_t>& octave, std::vector<int32_t>& nMPs, std::vector<int32_t>& nRedundant) const {
+    if (offsets.size() != kfSlot.size() + 1 || slot.size() != octave.size() || (size_t)offsets.back() != slot.size())
+      throw std::invalid_argument("ObservationGraph::CullingCounts: the lists disagree in length");
+    nMPs.assign(kfSlot.size(), 0); nRedundant.assign(kfSlot.size(), 0);
+    check(orbfe_obsgraph_culling_counts(h_, (int)kfSlot.size(), kfSlot.data(), offsets.data(), slot.data(), octave.data(), nMPs.data(),
+                                        nRedundant.data()), "ObservationGraph::CullingCounts");
+  }
+  // MapPoint::UpdateNormalAndDepth at the given positions (3 floats per slot)
+  NormalDepth UpdateNormalAndDepth(const std::vector<int32_t>& slot, const std::vector<float>& pos, const std::vector<float>& mvScaleFactors) const {
+    const size_t n = slot.size();
+    if (pos.size() != 3 * n) throw std::invalid_argument("ObservationGraph::UpdateNormalAndDepth: one position per slot");
+    NormalDepth r;
+    r.normal.assign(3 * n + 1, 0); r.minDist.assign(n + 1, 0); r.maxDist.assign(n + 1, 0); r.valid.assign(n + 1, 0);
+    check(orbfe_obsgraph_update_normal_depth(h_, (int)n, slot.data(), pos.data(), mvScaleFactors.data(), (int)mvScaleFactors.size(),
+                                             r.normal.data(), r.minDist.data(), r.maxDist.data(), r.valid.data()), "ObservationGraph::UpdateNormalAndDepth");
+    r.normal.resize(3 * n); r.minDist.resize(n); r.maxDist.resize(n); r.valid.resize(n);
+    return r;
+  }
+
+ private:
+  orbfe_obsgraph* h_ = nullptr;
+  int kfCap_ = 0;
+};
+
 // The map points Tracking::SearchLocalPoints reads, resident on the device (orbfe_mappoints): slot <-> MapPoint* is the
 // caller's map, as the key-frame ids of the KeyFrameDatabase are.
 class MapPointTable {
@@ -695,6 +803,15 @@ class MapPointTable {
     check(orbfe_mappoints_positions(h_, (int)slot.size(), slot.data(), out.data()), "MapPointTable::Positions");
     out.resize(3 * slot.size());
     return out;
+  }
+
+  // MapPoint::UpdateNormalAndDepth for slot[] on the device: positions from this table, normal / min / max into it; returns valid[]
+  std::vector<uint8_t> UpdateNormalAndDepth(const ObservationGraph& graph, const std::vector<int32_t>& slot, const std::vector<float>& mvScaleFactors) {
+    std::vector<uint8_t> valid(slot.size() + 1, 0);
+    check(orbfe_obsgraph_update_normal_depth_mappoints(graph.handle(), h_, (int)slot.size(), slot.data(), mvScaleFactors.data(),
+                                                       (int)mvScaleFactors.size(), valid.data()), "MapPointTable::UpdateNormalAndDepth");
+    valid.resize(slot.size());
+    return valid;
   }
 
  private:

@@ -15,5 +15,6 @@ from .loop_closing import (Sim3Solver, sim3_max_iterations, sim3_ransac, sim3_ra
 from .initializer import (Initializer, initializer_normalize, initializer_ransac, initializer_ransac_multi,  # noqa: F401
                           initializer_reconstruct, initializer_reconstruct_multi, initializer_sets_from_draws)
 from .keyframe_database import KeyFrameDatabase, bow_arrays, group_candidates  # noqa: F401
+from .observation_graph import ObservationGraph  # noqa: F401
 from .ingest import (ComputeDistinctiveDescriptors, ComputeImageBounds, ComputeStereoFromRGBD,  # noqa: F401
                      Rectifier, UndistortKeyPoints, cvtColorToGray, initUndistortRectifyMap, undistortPoints)  # noqa: F401

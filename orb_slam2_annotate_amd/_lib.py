@@ -122,6 +122,11 @@ EXPORTS = [
     "orbfe_block_sparse_solve7", "orbfe_mappoints_positions",
     "orbfe_initializer_ransac", "orbfe_initializer_ransac_multi", "orbfe_initializer_normalize", "orbfe_initializer_sets_from_draws",
     "orbfe_initializer_reconstruct", "orbfe_initializer_reconstruct_multi",
+    "orbfe_obsgraph_create", "orbfe_obsgraph_destroy", "orbfe_obsgraph_clear", "orbfe_obsgraph_set_keyframes",
+    "orbfe_obsgraph_set_points", "orbfe_obsgraph_add_observations", "orbfe_obsgraph_erase_observations",
+    "orbfe_obsgraph_erase_keyframe", "orbfe_obsgraph_get_row", "orbfe_obsgraph_votes", "orbfe_obsgraph_culling_counts",
+    "orbfe_obsgraph_update_normal_depth", "orbfe_obsgraph_update_normal_depth_mappoints",
+    "orbfe_obsgraph_update_connections", "orbfe_obsgraph_local_keyframes",
 ]
 
 _lib = None
@@ -315,6 +320,22 @@ def load():
     L.orbfe_initializer_sets_from_draws.argtypes = [ci, ci, vp, vp]
     L.orbfe_initializer_reconstruct_multi.argtypes = [ci, ci, ci, ci] + [vp] * 19
     L.orbfe_initializer_reconstruct.argtypes = [ci, ci, vp, ci, vp, vp, C.c_float, vp] + [vp] * 9
+    L.orbfe_obsgraph_create.argtypes = [ci, ci, ci, ci, C.POINTER(C.c_void_p)]
+    L.orbfe_obsgraph_destroy.argtypes = [vp]
+    L.orbfe_obsgraph_destroy.restype = None
+    L.orbfe_obsgraph_clear.argtypes = [vp]
+    L.orbfe_obsgraph_set_keyframes.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.orbfe_obsgraph_set_points.argtypes = [vp, ci, vp, vp, vp]
+    L.orbfe_obsgraph_add_observations.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_obsgraph_erase_observations.argtypes = [vp, ci, vp, vp, vp]
+    L.orbfe_obsgraph_erase_keyframe.argtypes = [vp, ci, vp, ci, vp]
+    L.orbfe_obsgraph_get_row.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+    L.orbfe_obsgraph_votes.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp]
+    L.orbfe_obsgraph_culling_counts.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_obsgraph_update_normal_depth.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp]
+    L.orbfe_obsgraph_update_normal_depth_mappoints.argtypes = [vp, vp, ci, vp, vp, ci, vp]
+    L.orbfe_obsgraph_update_connections.argtypes = [ci] + [vp] * 9
+    L.orbfe_obsgraph_local_keyframes.argtypes = [ci] + [vp] * 10 + [vp, ci, vp, vp]
     _lib = L
     return L
 

@@ -99,6 +99,8 @@ void slab_put(Slab* s);
 
 // ---- mappoints.hip (struct orbfe_mappoints lives there) ----
 bool pose_ok(const orbfe_camera_pose* p);
+// the device a table was created for (fixed at create: no lock, no device call)
+int mappoints_device(const orbfe_mappoints* mp);
 // The one way another host file reaches a table: takes the handle's serialisation and makes the table ready on the device,
 // for the scope.  rc != ORBFE_OK: nothing is held and the error text is set.  The holder's work on the table has completed
 // (its stream is synchronised) before the scope ends.

@@ -133,6 +133,7 @@ extern "C" int orbfe_mappoints_update(orbfe_mappoints* mp, int n, const int32_t*
 
 namespace orbfe {
 bool pose_ok(const orbfe_camera_pose* p) { return p && p->n_levels >= 1 && p->n_levels <= ORBFE_MAX_LEVELS * 4; }
+int mappoints_device(const orbfe_mappoints* mp) { return mp->device; }
 
 // host_internal.h: holds the handle's serialisation for a scope, with the table on the device
 MapPointsLock::MapPointsLock(orbfe_mappoints* mp) {
