@@ -1403,6 +1403,53 @@ int orbfe_obsgraph_local_keyframes(int n, const int64_t *kf_id, const int32_t *w
                                    const int32_t *child_offsets, const int64_t *child_ids, const uint8_t *child_bad,
                                    const int64_t *parent_id, int64_t *out_ids, int capacity, int *n_out, int64_t *ref_id);
 
+/* ---- The opposite direction: KeyFrame::mvpMapPoints, key frame -> its points, in the same handle ----
+ * One row of kf_row_width point slots per kf slot, entry idx = mvpMapPoints[idx] (-1: NULL), with the row's length N.
+ * The discipline is the one above: the host mirror is the truth, the three mutations change the mirror alone and mark
+ * the rows they touched, the device rows live in a slab of their own that is taken at the first device call after
+ * enable, and a reading call (keyframe_points_union, tracked_points, get_keyframe_points from the device) first rewrites
+ * the marked rows, each as a whole.  A handle that never calls enable behaves as before and allocates nothing more.
+ * Every function below except enable returns ORBFE_ERR_INVALID on a handle that is not enabled.
+ * orbfe_obsgraph_clear also empties these rows and keeps the width.  orbfe_obsgraph_erase_keyframe leaves the erased key
+ * frame's row as it is: KeyFrame::SetBadFlag (src/KeyFrame.cc:488 ff.) does not clear mvpMapPoints either. */
+
+/* Gives the handle rows of kf_row_width entries: a multiple of 64 in 64 .. 16384 (at least the largest N), with
+ * kf_capacity * kf_row_width <= 2^28.  Once per handle: a second call with the same width is a no-op, with another width
+ * ORBFE_ERR_INVALID.  Does not touch the device. */
+int orbfe_obsgraph_enable_keyframe_points(orbfe_obsgraph *g, int kf_row_width);
+/* The whole mvpMapPoints of the key frame in kf_slot, as the KeyFrame constructor copies it from the Frame
+ * (src/KeyFrame.cc:42): n = N <= kf_row_width entries, slot[i] in [-1, point_capacity).  The kf slot must have been
+ * given to set_keyframes.  The row's length becomes n. */
+int orbfe_obsgraph_set_keyframe_points(orbfe_obsgraph *g, int kf_slot, int n, const int32_t *slot);
+/* KeyFrame::AddMapPoint(pMP, idx) and ReplaceMapPointMatch(idx, pMP) (src/KeyFrame.cc:220-224, 240-243: both are
+ * mvpMapPoints[idx] = pMP) and EraseMapPointMatch(idx) (:226-230; slot[i] = -1), n assignments applied in order.  idx[i]
+ * must be below the length of row kf_slot[i] (so a row that was never set takes none).  The call applies as a whole or,
+ * with ORBFE_ERR_INVALID, not at all.  EraseMapPointMatch(pMP) (:232-237) is the caller's GetIndexInKeyFrame, then this. */
+int orbfe_obsgraph_assign_keyframe_points(orbfe_obsgraph *g, int n, const int32_t *kf_slot, const uint16_t *idx, const int32_t *slot);
+/* Test read-back of one row: from the host mirror (from_device = 0; needs no device) or from the device (from_device != 0,
+ * after the marked rows were written).  slots holds kf_row_width entries, the row's *n first, the rest -1. */
+int orbfe_obsgraph_get_keyframe_points(orbfe_obsgraph *g, int from_device, int kf_slot, int32_t *slots, int32_t *n);
+/* The ordered union of key frames' map points, for n_queries key-frame lists in one call: Tracking::UpdateLocalPoints
+ * (src/Tracking.cc:1315-1333; query = mvpLocalKeyFrames), and the same loop of LocalMapping::SearchInNeighbors
+ * (src/LocalMapping.cc:552-571; vpTargetKFs -> vpFuseCandidates), LoopClosing::ComputeSim3 (src/LoopClosing.cc:417-436;
+ * vpLoopConnectedKFs -> mvpLoopMapPoints) and lLocalMapPoints of Optimizer::LocalBundleAdjustment.  Query q is the kf slots
+ * q_kf_slots [q_offsets[q], q_offsets[q+1]) in the caller's order.  The key frames are visited in list order and the
+ * entries of a row in idx order; -1 is skipped, a point whose record is bad or was never set (set_points) is skipped, a
+ * point already emitted for this query is skipped, the others are emitted: slot_out [q * capacity ..] holds the point
+ * slots in exactly that order, count[q] of them -- unchanged the slot[] argument of orbfe_search_local_points.  A kf
+ * slot named twice contributes nothing the second time; a key frame's own bad flag is not read (none of the four loops
+ * reads it).  Equal inputs give equal arrays: the order is fixed by position k * kf_row_width + idx (k: the key frame's
+ * place in the query), never by arrival.  A count above `capacity` fills `capacity` entries and returns
+ * ORBFE_ERR_CAPACITY (every count[] is still set).  ORBFE_ERR_INVALID: a kf slot out of range or never set, more than
+ * 65535 queries, offsets that do not start at 0 or descend, a query with key frames * kf_row_width >= 2^31.  The
+ * workspace is point_capacity int32 per query, at most 2^26 int32 at a time: more queries run in several groups. */
+int orbfe_obsgraph_keyframe_points_union(orbfe_obsgraph *g, int n_queries, const int32_t *q_offsets, const int32_t *q_kf_slots,
+                                         int capacity, int32_t *slot_out, int32_t *count);
+/* KeyFrame::TrackedMapPoints(minObs) (src/KeyFrame.cc:264-289) for n_kf key frames in one launch: count[i] = the entries
+ * of row kf_slot[i] that are not NULL and not bad and, when min_obs > 0, have nObs >= min_obs (nObs as the point's record
+ * holds it: a stereo observation weighs 2).  A kf slot out of range or never set returns ORBFE_ERR_INVALID. */
+int orbfe_obsgraph_tracked_points(orbfe_obsgraph *g, int n_kf, const int32_t *kf_slot, int min_obs, int32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

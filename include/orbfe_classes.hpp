@@ -725,9 +725,65 @@ class ObservationGraph {
     return r;
   }
 
+  // ---- KeyFrame::mvpMapPoints: key frame -> its points (rows of kfRowWidth point slots, -1 = NULL) ----
+  void EnableKeyFramePoints(int kfRowWidth) {
+    check(orbfe_obsgraph_enable_keyframe_points(h_, kfRowWidth), "ObservationGraph::EnableKeyFramePoints");
+    kfRowWidth_ = kfRowWidth;
+  }
+  // the whole mvpMapPoints of a key frame, as at the KeyFrame constructor
+  void SetKeyFramePoints(int kfSlot, const std::vector<int32_t>& slot) {
+    check(orbfe_obsgraph_set_keyframe_points(h_, kfSlot, (int)slot.size(), slot.data()), "ObservationGraph::SetKeyFramePoints");
+  }
+  // KeyFrame::AddMapPoint / ReplaceMapPointMatch (slot) and EraseMapPointMatch(idx) (slot -1) per entry, all or nothing
+  void AssignKeyFramePoints(const std::vector<int32_t>& kfSlot, const std::vector<uint16_t>& idx, const std::vector<int32_t>& slot) {
+    if (idx.size() != kfSlot.size() || slot.size() != kfSlot.size())
+      throw std::invalid_argument("ObservationGraph::AssignKeyFramePoints: one entry per assignment");
+    check(orbfe_obsgraph_assign_keyframe_points(h_, (int)kfSlot.size(), kfSlot.data(), idx.data(), slot.data()),
+          "ObservationGraph::AssignKeyFramePoints");
+  }
+  std::vector<int32_t> GetKeyFramePoints(int kfSlot, bool fromDevice = false) const {
+    std::vector<int32_t> out((size_t)std::max(kfRowWidth_, 1), -1);
+    int32_t n = 0;
+    check(orbfe_obsgraph_get_keyframe_points(h_, fromDevice ? 1 : 0, kfSlot, out.data(), &n), "ObservationGraph::GetKeyFramePoints");
+    out.resize((size_t)n);
+    return out;
+  }
+  // the ordered union of the key frames' map points per query (query q: kfSlots [offsets[q], offsets[q+1])); a first call
+  // sized by `capacity` (<= 0: 4096) is repeated once with the largest count when a list does not fit
+  std::vector<std::vector<int32_t>> KeyFramePointsUnion(const std::vector<int32_t>& offsets, const std::vector<int32_t>& kfSlots,
+                                                        int capacity = 0) const {
+    if (offsets.empty() || (size_t)offsets.back() != kfSlots.size())
+      throw std::invalid_argument("ObservationGraph::KeyFramePointsUnion: the lists disagree in length");
+    const size_t Q = offsets.size() - 1;
+    size_t cap = capacity > 0 ? (size_t)capacity : 4096;
+    std::vector<int32_t> out(Q * cap + 1), count(Q + 1, 0);
+    int rc = orbfe_obsgraph_keyframe_points_union(h_, (int)Q, offsets.data(), kfSlots.data(), (int)cap, out.data(), count.data());
+    if (rc == ORBFE_ERR_CAPACITY) {
+      cap = (size_t)*std::max_element(count.begin(), count.end());
+      out.assign(Q * cap + 1, 0);
+      rc = orbfe_obsgraph_keyframe_points_union(h_, (int)Q, offsets.data(), kfSlots.data(), (int)cap, out.data(), count.data());
+    }
+    check(rc, "ObservationGraph::KeyFramePointsUnion");
+    std::vector<std::vector<int32_t>> lists(Q);
+    for (size_t q = 0; q < Q; q++) lists[q].assign(out.begin() + (ptrdiff_t)(q * cap), out.begin() + (ptrdiff_t)(q * cap + (size_t)count[q]));
+    return lists;
+  }
+  // Tracking::UpdateLocalPoints: mvpLocalKeyFrames as kf slots -> mvpLocalMapPoints as point slots, the slot list of
+  // MapPointTable::SearchLocalPoints
+  std::vector<int32_t> UpdateLocalPoints(const std::vector<int32_t>& localKfSlots, int capacity = 0) const {
+    return KeyFramePointsUnion({0, (int32_t)localKfSlots.size()}, localKfSlots, capacity)[0];
+  }
+  // KeyFrame::TrackedMapPoints(minObs) per kf slot
+  std::vector<int32_t> TrackedMapPoints(const std::vector<int32_t>& kfSlot, int minObs) const {
+    std::vector<int32_t> count(kfSlot.size() + 1, 0);
+    check(orbfe_obsgraph_tracked_points(h_, (int)kfSlot.size(), kfSlot.data(), minObs, count.data()), "ObservationGraph::TrackedMapPoints");
+    count.resize(kfSlot.size());
+    return count;
+  }
+
  private:
   orbfe_obsgraph* h_ = nullptr;
-  int kfCap_ = 0;
+  int kfCap_ = 0, kfRowWidth_ = 0;
 };
 
 // The map points Tracking::SearchLocalPoints reads, resident on the device (orbfe_mappoints): slot <-> MapPoint* is the

@@ -127,6 +127,8 @@ EXPORTS = [
     "orbfe_obsgraph_erase_keyframe", "orbfe_obsgraph_get_row", "orbfe_obsgraph_votes", "orbfe_obsgraph_culling_counts",
     "orbfe_obsgraph_update_normal_depth", "orbfe_obsgraph_update_normal_depth_mappoints",
     "orbfe_obsgraph_update_connections", "orbfe_obsgraph_local_keyframes",
+    "orbfe_obsgraph_enable_keyframe_points", "orbfe_obsgraph_set_keyframe_points", "orbfe_obsgraph_assign_keyframe_points",
+    "orbfe_obsgraph_get_keyframe_points", "orbfe_obsgraph_keyframe_points_union", "orbfe_obsgraph_tracked_points",
 ]
 
 _lib = None
@@ -336,6 +338,12 @@ def load():
     L.orbfe_obsgraph_update_normal_depth_mappoints.argtypes = [vp, vp, ci, vp, vp, ci, vp]
     L.orbfe_obsgraph_update_connections.argtypes = [ci] + [vp] * 9
     L.orbfe_obsgraph_local_keyframes.argtypes = [ci] + [vp] * 10 + [vp, ci, vp, vp]
+    L.orbfe_obsgraph_enable_keyframe_points.argtypes = [vp, ci]
+    L.orbfe_obsgraph_set_keyframe_points.argtypes = [vp, ci, ci, vp]
+    L.orbfe_obsgraph_assign_keyframe_points.argtypes = [vp, ci, vp, vp, vp]
+    L.orbfe_obsgraph_get_keyframe_points.argtypes = [vp, ci, ci, vp, vp]
+    L.orbfe_obsgraph_keyframe_points_union.argtypes = [vp, ci, vp, vp, ci, vp, vp]
+    L.orbfe_obsgraph_tracked_points.argtypes = [vp, ci, vp, ci, vp]
     _lib = L
     return L
 

@@ -21,6 +21,7 @@
 #include "../../include/orbfe.h"
 #include "host_internal.h"
 #include "match_kernels.h"
+#include "obsgraph_handle.h"
 #include "obsgraph_host.h"
 #include "obsgraph_kernels.h"
 
@@ -28,24 +29,11 @@ using namespace orbfe;
 
 static_assert(sizeof(orbfe_observation) == sizeof(ObsEntry), "orbfe_observation is the table's entry");
 
-struct orbfe_obsgraph {
-  int device = 0;
-  std::mutex m;  // a handle serialises its own calls
-  bool ready = false;  // stream created
-  hipStream_t stream = nullptr;
-  ObsGraphMirror h;
-  Slab table;  // empty until the first call that needs the device
-  ObsGraphDevice d{};
-  // grow-only workspace + pinned staging in both directions
-  DevBuf<uint8_t> work;
-  PinBuf<uint8_t> pin;
-};
-
 namespace {
 
-constexpr size_t kFlushChunkBytes = (size_t)8 << 20;
+constexpr size_t kFlushChunkBytes = kObsFlushChunkBytes;
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+size_t al(size_t x) { return obs_al(x); }
 
 size_t grown(size_t have, size_t first, size_t need) {
   size_t want = have ? have : first;
@@ -53,10 +41,7 @@ size_t grown(size_t have, size_t first, size_t need) {
   return want;
 }
 
-int ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes) {
-  const int rc = g->work.reserve(devBytes, grown(g->work.cap, (size_t)1 << 20, devBytes));
-  return rc ? rc : g->pin.reserve(pinBytes, grown(g->pin.cap, (size_t)1 << 16, pinBytes));
-}
+int ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes) { return obs_ensure_work(g, devBytes, pinBytes); }
 
 // the marked rows and key frames onto the device; the marks are dropped only when everything has arrived
 int obs_flush(orbfe_obsgraph* g) {
@@ -104,8 +89,17 @@ int obs_flush(orbfe_obsgraph* g) {
   return ORBFE_OK;
 }
 
+}  // namespace
+
+int orbfe::obs_ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes) {
+  const int rc = g->work.reserve(devBytes, grown(g->work.cap, (size_t)1 << 20, devBytes));
+  return rc ? rc : g->pin.reserve(pinBytes, grown(g->pin.cap, (size_t)1 << 16, pinBytes));
+}
+
+int orbfe::obs_invalid(const char* fn, const char* what) { return fail(ORBFE_ERR_INVALID, std::string(fn) + ": " + what); }
+
 // what every call that reads the table on the device starts with (the handle locked)
-int obs_ready(orbfe_obsgraph* g) {
+int orbfe::obs_ready(orbfe_obsgraph* g) {
   HIPCHK(hipSetDevice(g->device));
   if (!g->ready) {
     HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
@@ -135,7 +129,9 @@ int obs_ready(orbfe_obsgraph* g) {
   return obs_flush(g);
 }
 
-int invalid(const char* fn, const char* what) { return fail(ORBFE_ERR_INVALID, std::string(fn) + ": " + what); }
+namespace {
+
+int invalid(const char* fn, const char* what) { return obs_invalid(fn, what); }
 
 // pos == NULL: the table form (positions from and results into *table)
 int normal_depth_run(orbfe_obsgraph* g, int n, const int32_t* slot, const float* pos, const float* scale, int n_levels, float* normal,
@@ -202,6 +198,7 @@ extern "C" void orbfe_obsgraph_destroy(orbfe_obsgraph* g) {
     (void)hipSetDevice(g->device);
     (void)hipStreamSynchronize(g->stream);
     slab_put(&g->table);
+    slab_put(&g->kfTable);
     (void)hipStreamDestroy(g->stream);
   }
   delete g;

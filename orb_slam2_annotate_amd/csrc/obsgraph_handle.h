@@ -1,0 +1,40 @@
+// obsgraph_handle.h -- struct orbfe_obsgraph and what its two host files share (obsgraph.hip: the observation rows;
+// kfpoints.hip: the key-frame rows).  Everything here is called with the handle locked.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <string>
+
+#include "../../include/orbfe.h"
+#include "host_internal.h"
+#include "obsgraph_host.h"
+#include "obsgraph_kernels.h"
+
+struct orbfe_obsgraph {
+  int device = 0;
+  std::mutex m;  // a handle serialises its own calls
+  bool ready = false;  // stream created
+  hipStream_t stream = nullptr;
+  orbfe::ObsGraphMirror h;
+  orbfe::Slab table;  // empty until the first call that needs the device
+  orbfe::ObsGraphDevice d{};
+  // KeyFrame::mvpMapPoints: a slab of its own, empty until the first device call after enable_keyframe_points
+  orbfe::Slab kfTable;
+  orbfe::KfPointsDevice kd{};
+  // grow-only workspace + pinned staging in both directions
+  orbfe::DevBuf<uint8_t> work;
+  orbfe::PinBuf<uint8_t> pin;
+};
+
+namespace orbfe {
+
+constexpr size_t kObsFlushChunkBytes = (size_t)8 << 20;
+
+inline size_t obs_al(size_t x) { return (x + 255) & ~(size_t)255; }
+int obs_ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes);
+// what every call that reads the table on the device starts with: device, stream, the slab, the marked rows written
+int obs_ready(orbfe_obsgraph* g);
+int obs_invalid(const char* fn, const char* what);
+
+}  // namespace orbfe

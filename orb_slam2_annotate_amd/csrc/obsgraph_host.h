@@ -7,6 +7,12 @@
 // The mirror is the truth: a mutation changes the mirror alone and marks the rows it touched; the next call that reads
 // the table on the device rewrites those rows, each as a whole.  Rows are kept in ascending mnId of the observing key
 // frame (ties cannot occur: two live kf slots never share an id).
+//
+// The opposite direction, KeyFrame::mvpMapPoints (key frame -> its points, by keypoint index), lives here too once
+// enable_keyframe_points() gave it a width: one row of point slots per kf slot (-1: NULL), under the same discipline.  A
+// mirror that never enables it holds nothing more than before.  kfpoints_union_flat() below is the reference's ordered
+// union (src/Tracking.cc:1315-1333) over flat arrays: the sanitizer program's check and the CPU yardstick of
+// tools/kfpoints_latency.py -- never a fallback, the library does not call it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -20,6 +26,8 @@ namespace orbfe {
 
 constexpr int kObsMaxPoints = 1 << 24, kObsMaxKeyFrames = 1 << 20;
 constexpr int64_t kObsMaxEntries = (int64_t)1 << 28;  // point_capacity * row_width: a 2 GiB table at the most
+constexpr int kKfRowMinWidth = 64, kKfRowMaxWidth = 16384;  // kf_row_width: a multiple of 64 (one wave never spans two rows)
+constexpr int64_t kKfRowMaxEntries = (int64_t)1 << 28;      // kf_capacity * kf_row_width: a 1 GiB table at the most
 
 // one observation: 8 bytes, what a lane of the kernels reads
 struct ObsEntry {
@@ -60,6 +68,11 @@ struct ObsGraphMirror {
   std::vector<uint8_t> rowDirty;
   std::vector<int32_t> dirtyRows;
   int kfDirtyLo = 0, kfDirtyHi = 0;  // [lo, hi)
+  // KeyFrame::mvpMapPoints per kf slot; kfRowWidth = 0: not enabled, and nothing below is allocated
+  int kfRowWidth = 0;
+  std::vector<std::vector<int32_t>> kfRows;
+  std::vector<uint8_t> kfRowDirty;
+  std::vector<int32_t> dirtyKfRows;
 
   void init(int points, int keyframes, int width) {
     pointCap = points; kfCap = keyframes; rowWidth = width;
@@ -77,6 +90,10 @@ struct ObsGraphMirror {
   void clear() {
     init(pointCap, kfCap, rowWidth);
     for (int s = 0; s < pointCap; s++) touch(s);
+    if (kfRowWidth) {  // the rows are emptied, the width stays
+      kfRows.assign((size_t)kfCap, {});
+      for (int k = 0; k < kfCap; k++) touch_kf_row(k);
+    }
   }
   void touch(int slot) {
     if (!rowDirty[(size_t)slot]) { rowDirty[(size_t)slot] = 1; dirtyRows.push_back(slot); }
@@ -277,6 +294,85 @@ struct ObsGraphMirror {
     }
     return nullptr;
   }
+
+  // ---- KeyFrame::mvpMapPoints (src/KeyFrame.cc:220-243) ----
+
+  void touch_kf_row(int k) {
+    if (!kfRowDirty[(size_t)k]) { kfRowDirty[(size_t)k] = 1; dirtyKfRows.push_back(k); }
+  }
+  void kf_rows_flushed() {
+    for (int32_t k : dirtyKfRows) kfRowDirty[(size_t)k] = 0;
+    dirtyKfRows.clear();
+  }
+  // what a slab of rows that was just allocated needs: the rows that hold something (the lengths travel as one block)
+  void mark_kf_rows_held() {
+    kf_rows_flushed();
+    for (int k = 0; k < kfCap; k++)
+      if (!kfRows[(size_t)k].empty()) touch_kf_row(k);
+  }
+
+  const char* enable_keyframe_points(int width) {
+    if (width < kKfRowMinWidth || width > kKfRowMaxWidth || width % 64) return "kf_row_width must be a multiple of 64 in 64 .. 16384";
+    if ((int64_t)kfCap * width > kKfRowMaxEntries) return "kf_capacity * kf_row_width must not exceed 2^28";
+    if (kfRowWidth) return kfRowWidth == width ? nullptr : "key-frame rows are enabled with another width";
+    kfRows.assign((size_t)kfCap, {});
+    kfRowDirty.assign((size_t)kfCap, 0);
+    dirtyKfRows.clear();
+    kfRowWidth = width;
+    return nullptr;
+  }
+
+  // the whole mvpMapPoints of a key frame, as at the KeyFrame constructor (N = n entries, -1: NULL)
+  const char* set_keyframe_points(int k, int n, const int32_t* slot) {
+    if (!kfRowWidth) return "key-frame rows are not enabled (orbfe_obsgraph_enable_keyframe_points)";
+    if (k < 0 || k >= kfCap) return "kf slot outside [0, kf_capacity)";
+    if (kfs[(size_t)k].id < 0) return "kf slot was never set (orbfe_obsgraph_set_keyframes)";
+    if (n < 0 || n > kfRowWidth) return "n outside [0, kf_row_width]";
+    if (n > 0 && !slot) return "NULL array";
+    for (int i = 0; i < n; i++)
+      if (slot[i] < -1 || slot[i] >= pointCap) return "slot outside [-1, point_capacity)";
+    kfRows[(size_t)k].assign(slot, slot + n);
+    touch_kf_row(k);
+    return nullptr;
+  }
+
+  // AddMapPoint / ReplaceMapPointMatch (mvpMapPoints[idx] = pMP) and EraseMapPointMatch(idx) (slot -1), n times in order;
+  // everything is checked before the first entry changes
+  const char* assign_keyframe_points(int n, const int32_t* kf, const uint16_t* idx, const int32_t* slot) {
+    if (!kfRowWidth) return "key-frame rows are not enabled (orbfe_obsgraph_enable_keyframe_points)";
+    if (n < 0) return "negative count";
+    if (n == 0) return nullptr;
+    if (!kf || !idx || !slot) return "NULL array";
+    if (!kf_slots_ok(n, kf)) return "kf slot outside [0, kf_capacity)";
+    for (int i = 0; i < n; i++) {
+      if ((size_t)idx[i] >= kfRows[(size_t)kf[i]].size()) return "idx is not below the row's length";
+      if (slot[i] < -1 || slot[i] >= pointCap) return "slot outside [-1, point_capacity)";
+    }
+    for (int i = 0; i < n; i++) {
+      kfRows[(size_t)kf[i]][idx[i]] = slot[i];
+      touch_kf_row(kf[i]);
+    }
+    return nullptr;
+  }
+
+  // the key-frame lists of n_queries union queries (offsets as in orbfe_obsgraph_votes): NULL when they may be enqueued
+  const char* check_kf_queries(int nQueries, const int32_t* off, const int32_t* kf) const {
+    if (!kfRowWidth) return "key-frame rows are not enabled (orbfe_obsgraph_enable_keyframe_points)";
+    if (off[0] != 0) return "q_offsets[0] must be 0";
+    for (int q = 0; q < nQueries; q++) {
+      if (off[q + 1] < off[q]) return "q_offsets must not descend";
+      if ((int64_t)(off[q + 1] - off[q]) * kfRowWidth >= ((int64_t)1 << 31)) return "a query's key frames * kf_row_width must stay below 2^31";
+    }
+    if (off[nQueries] > 0 && !kf) return "NULL q_kf_slots";
+    return check_kf_list(off[nQueries], kf);
+  }
+  const char* check_kf_list(int n, const int32_t* kf) const {
+    if (!kfRowWidth) return "key-frame rows are not enabled (orbfe_obsgraph_enable_keyframe_points)";
+    if (!kf_slots_ok(n, kf)) return "kf slot outside [0, kf_capacity)";
+    for (int i = 0; i < n; i++)
+      if (kfs[(size_t)kf[i]].id < 0) return "kf slot was never set (orbfe_obsgraph_set_keyframes)";
+    return nullptr;
+  }
 };
 
 // ---- host replays over one query's votes ----
@@ -396,6 +492,44 @@ inline const char* obsgraph_local_keyframes(int n, const int64_t* kf_id, const i
   for (size_t i = 0; i < m; i++) out_id[i] = local[i];
   if (local.size() > (size_t)capacity) { *over = true; return "more local key frames than `capacity` (see n_out)"; }
   return nullptr;
+}
+
+// ---- the loops over mvpMapPoints on flat arrays: rows [kf][width] of point slots, len [kf], meta [point] ----
+
+// The ordered union of Tracking::UpdateLocalPoints (src/Tracking.cc:1315-1333; the same loop as
+// LocalMapping::SearchInNeighbors src/LocalMapping.cc:555-571, LoopClosing::ComputeSim3 src/LoopClosing.cc:420-436 and
+// lLocalMapPoints of Optimizer::LocalBundleAdjustment): key frames in list order, entries in idx order, NULL (-1) skipped,
+// a point stamped for this query skipped (mnTrackReferenceForFrame == mCurrentFrame.mnId), bad points skipped, the rest
+// emitted and stamped.  stamp: one int32 per point slot, every entry different from `mark` on entry (the caller raises
+// mark from query to query, as the reference raises the frame id).  Returns the count; out receives the first `capacity`.
+inline int kfpoints_union_flat(const int32_t* rows, const int32_t* len, int width, const ObsPointMeta* meta, int nKf,
+                               const int32_t* kf, int32_t* stamp, int32_t mark, int32_t* out, int capacity) {
+  int n = 0;
+  for (int k = 0; k < nKf; k++) {
+    const int32_t* r = rows + (size_t)kf[k] * (size_t)width;
+    const int m = len[kf[k]];
+    for (int i = 0; i < m; i++) {
+      const int32_t s = r[i];
+      if (s < 0) continue;               // !pMP
+      if (stamp[s] == mark) continue;    // already a local point of this query
+      if (meta[s].bad) continue;         // isBad() (a slot that was never set counts as bad)
+      if (n < capacity) out[n] = s;
+      n++;
+      stamp[s] = mark;
+    }
+  }
+  return n;
+}
+
+// KeyFrame::TrackedMapPoints (src/KeyFrame.cc:264-289) of one row
+inline int kfpoints_tracked_flat(const int32_t* row, int len, const ObsPointMeta* meta, int minObs) {
+  int n = 0;
+  for (int i = 0; i < len; i++) {
+    const int32_t s = row[i];
+    if (s < 0 || meta[s].bad) continue;
+    if (minObs > 0 ? meta[s].nObs >= minObs : true) n++;
+  }
+  return n;
 }
 
 }  // namespace orbfe

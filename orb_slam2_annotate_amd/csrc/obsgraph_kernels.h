@@ -40,4 +40,38 @@ void launch_obs_normal_depth(hipStream_t s, const ObsGraphDevice& g, int n, cons
                              const float* scale, int nLevels, float* normal, float* minDist, float* maxDist, uint8_t* valid,
                              const MapPointsDevice* table);
 
+// ---- k_kfpoints.hip: KeyFrame::mvpMapPoints, the rows of point slots per kf slot ----
+
+// the unit of the union's grid: 1024 consecutive positions p = k * width + idx of one query (k: the key frame's place in
+// the query), as 16 wave-sized chunks.  width is a multiple of 64, so a chunk never spans two rows.
+constexpr int kKfBlockEntries = 1024, kKfChunksPerBlock = kKfBlockEntries / 64;
+
+struct KfPointsDevice {
+  int32_t* rows;  // [kf_capacity][width], -1: NULL; entries at and past len[kf] are never read
+  int32_t* len;   // [kf_capacity]: N of the key frame
+  int width;
+};
+
+// rewrites n rows from a staged block: kf[n], len[n], rowOf[n] (index of the row's `width` entries in `rows`, -1: the
+// row is empty and only its length is written)
+void launch_kf_scatter(hipStream_t s, const KfPointsDevice& t, int n, const int32_t* kf, const int32_t* len, const int32_t* rowOf,
+                       const int32_t* rows);
+
+// One group of queries of orbfe_obsgraph_keyframe_points_union.  Query q: the kf slots qKf [qOff[q], qOff[q+1]); its
+// blocks are blkOff[q] .. blkOff[q+1] of a flat grid of nBlocks = blkOff[nQueries].  Workspaces, none of which needs
+// clearing: first [nQueries][point_capacity], keepMask [nBlocks][16], blockCount [nBlocks] (holds each block's exclusive
+// prefix within its query afterwards).  out [nQueries][capacity], count [nQueries].  Five launches on s.
+struct KfUnionArgs {
+  int nQueries, nBlocks, capacity;
+  const int32_t *qOff, *qKf, *blkOff;
+  int32_t* first;
+  unsigned long long* keepMask;
+  int32_t *blockCount, *out, *count;
+};
+void launch_kf_union(hipStream_t s, const ObsGraphDevice& g, const KfPointsDevice& t, const KfUnionArgs& a);
+
+// KeyFrame::TrackedMapPoints for kf[n] in one launch, a wave per key frame
+void launch_kf_tracked(hipStream_t s, const ObsGraphDevice& g, const KfPointsDevice& t, int n, const int32_t* kf, int minObs,
+                       int32_t* count);
+
 }  // namespace orbfe

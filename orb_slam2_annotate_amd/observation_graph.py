@@ -3,7 +3,9 @@ frames that see it -- kept in HBM, and the four loops over it: the votes of ``Ke
 (src/KeyFrame.cc:311-403) and ``Tracking::UpdateLocalKeyFrames`` (src/Tracking.cc:1339-1455), the counts of
 ``LocalMapping::KeyFrameCulling`` (src/LocalMapping.cc:710-774) and ``MapPoint::UpdateNormalAndDepth``
 (src/MapPoint.cc:360-404).  Points are addressed by the slots of a ``MapPoints`` table, key frames by kf slot; the caller
-keeps both maps, the spanning tree, ``mvpMapPoints`` and the map mutex."""
+keeps both maps, the spanning tree and the map mutex.  Once ``enable_keyframe_points`` gave it a width the graph also holds
+the opposite direction, ``KeyFrame::mvpMapPoints``, and runs the ordered union of ``Tracking::UpdateLocalPoints``
+(src/Tracking.cc:1311-1334) and ``KeyFrame::TrackedMapPoints`` (src/KeyFrame.cc:264-289) over it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -85,6 +87,7 @@ class ObservationGraph:
         check(self._L.orbfe_obsgraph_create(int(device), int(point_capacity), int(kf_capacity), int(row_width), C.byref(self._handle)))
         self.point_capacity, self.kf_capacity, self.row_width, self.device = int(point_capacity), int(kf_capacity), int(row_width), int(device)
         self._kf_id = {}  # kf slot -> mnId, for the replays
+        self._kf_len = {}  # kf slot -> length of its mvpMapPoints row, to size the union's output
 
     @property
     def _h(self):
@@ -102,6 +105,7 @@ class ObservationGraph:
     def clear(self):
         check(self._L.orbfe_obsgraph_clear(self._h))
         self._kf_id.clear()
+        self._kf_len.clear()
 
     def set_keyframes(self, kf_slot, kf_id, Ow, bad=None):
         k = _i32(kf_slot)
@@ -222,6 +226,70 @@ class ObservationGraph:
             bad_points.extend(self.erase_keyframe(cand[start + hit]).tolist())
             start += hit + 1
         return culled, bad_points
+
+    # ---- KeyFrame::mvpMapPoints: key frame -> its points ----
+
+    def enable_keyframe_points(self, kf_row_width: int):
+        """Rows of `kf_row_width` point slots per kf slot (a multiple of 64 in 64 .. 16384); once per graph."""
+        check(self._L.orbfe_obsgraph_enable_keyframe_points(self._h, int(kf_row_width)))
+        self.kf_row_width = int(kf_row_width)
+
+    def set_keyframe_points(self, kf_slot: int, slots):
+        """The whole mvpMapPoints of a key frame (-1: NULL), as at the KeyFrame constructor."""
+        s = _i32(slots)
+        check(self._L.orbfe_obsgraph_set_keyframe_points(self._h, int(kf_slot), len(s), ptr(s)))
+        self._kf_len[int(kf_slot)] = len(s)
+
+    def assign_keyframe_points(self, kf_slot, idx, slot):
+        """KeyFrame::AddMapPoint / ReplaceMapPointMatch (mvpMapPoints[idx] = slot) and EraseMapPointMatch(idx) (slot -1) per
+        entry, in order; an invalid entry raises OrbfeError(ERR_INVALID) with nothing applied."""
+        k, s = _i32(kf_slot), _i32(slot)
+        i = np.ascontiguousarray(idx, dtype=np.uint16).reshape(-1)
+        if not (len(i) == len(s) == len(k)):
+            raise ValueError("ObservationGraph.assign_keyframe_points: one entry per assignment")
+        check(self._L.orbfe_obsgraph_assign_keyframe_points(self._h, len(k), ptr(k), ptr(i), ptr(s)))
+
+    def get_keyframe_points(self, kf_slot: int, from_device: bool = False):
+        """-> the row's point slots (its length N; -1: NULL), from the mirror or from the device."""
+        w = getattr(self, "kf_row_width", 0)
+        out = np.full(max(w, 1), -1, np.int32)
+        n = C.c_int32(0)
+        check(self._L.orbfe_obsgraph_get_keyframe_points(self._h, int(bool(from_device)), int(kf_slot), ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def keyframe_points_union(self, queries, capacity=None):
+        """The ordered union of the key frames' map points for len(queries) kf-slot lists in one call (Tracking::
+        UpdateLocalPoints and its three siblings) -> list of point-slot arrays, each in visiting order with first occurrence
+        kept.  capacity defaults to what the lists' row lengths allow; below a query's count it raises
+        OrbfeError(ERR_CAPACITY) with .count and .partial set."""
+        Q = len(queries)
+        off, flat = _csr(queries, np.int32)
+        if capacity is None:
+            cap = max([min(sum(self._kf_len.get(int(k), 0) for k in q), self.point_capacity) for q in queries] + [1])
+        else:
+            cap = int(capacity)
+        out = np.zeros(max(Q * cap, 1), np.int32)
+        cnt = np.zeros(max(Q, 1), np.int32)
+        try:
+            check(self._L.orbfe_obsgraph_keyframe_points_union(self._h, Q, ptr(off), ptr(flat), cap, ptr(out), ptr(cnt)))
+        except _lib.OrbfeError as e:
+            if e.code == _lib.ERR_CAPACITY:
+                e.count = cnt[:Q].copy()
+                e.partial = [out[q * cap:q * cap + min(cnt[q], cap)].copy() for q in range(Q)]
+            raise
+        return [out[q * cap:q * cap + cnt[q]].copy() for q in range(Q)]
+
+    def local_points(self, kf_slots):
+        """Tracking::UpdateLocalPoints for mvpLocalKeyFrames = kf_slots -> mvpLocalMapPoints as point slots: the slot list
+        MapPoints.search_local_points takes."""
+        return self.keyframe_points_union([kf_slots])[0]
+
+    def tracked_points(self, kf_slot, min_obs: int = 0):
+        """KeyFrame::TrackedMapPoints(min_obs) for each kf slot in one launch -> counts (int32)."""
+        k = _i32(kf_slot)
+        cnt = np.zeros(max(len(k), 1), np.int32)
+        check(self._L.orbfe_obsgraph_tracked_points(self._h, len(k), ptr(k), int(min_obs), ptr(cnt)))
+        return cnt[:len(k)]
 
     def update_normal_depth(self, slot, scale_factors, pos=None, mp=None):
         """MapPoint::UpdateNormalAndDepth for slot[].  pos ([n, 3]): the array form -> (normal [n, 3], min_dist, max_dist,
