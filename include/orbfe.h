@@ -169,6 +169,28 @@ int orbfe_extractor_debug_blurred_level(orbfe_extractor *e, int frame, int level
 int orbfe_debug_octree_host(const uint16_t *xs, const uint16_t *ys, const uint8_t *resp, int n, int minX, int maxX,
                             int minY, int maxY, int N, uint16_t *out_x, uint16_t *out_y, uint8_t *out_resp,
                             int cap);
+/* debug_octree_device: DistributeOctTree of one DEVICE form on n_frames candidate sets of one distribution area -- the
+ * operands of debug_octree_host (x, y relative to the area, 8-bit response, minX, maxX, minY, maxY, N), the sets
+ * concatenated in xs / ys / resp with n_per_frame[f] candidates each.  The sets run as the (frame, level) items of ONE
+ * launch of a one-level geometry; the candidates are handed over gathered (no in-kernel gather).  The host octree is
+ * never called.
+ *   form: 0 = the form the extractor's launch picks for n_frames frames, 1 = k_octree (throughput form), 2 = k_octree_reg,
+ *         3 = k_octree_reg1024, 4 = k_octree_global.
+ *   info6 (always written): nIni, kpCap (keypoint slots per frame), node capacity maxL, octree_lds_bytes(maxL), the LDS
+ *         limit beyond which the node list lives in global memory, and the form that 0 stands for.  With out_x == NULL
+ *         the call returns after writing it and needs no GPU.
+ *   outputs, `cap` >= kpCap slots per frame (frame f at f * cap): every slot of the kernel's output array in the kernel's
+ *         order -- spatial: 128-pixel column strip, then row, then column of the LEVEL coordinate x + 16, y + 16 -- with
+ *         out_rank = the keypoint's position in the reference's list order; out_x / out_y are level coordinates
+ *         (+ minX / + minY, as debug_octree_host).  out_count[f] keypoints are valid.  All scratch and output arrays are
+ *         filled with 0xFF bytes before the launch and the kernels write nothing past a frame's count: the slots from
+ *         out_count[f] to kpCap come back as 0xFFFF in all four arrays.
+ * ORBFE_ERR_INVALID: form 1, 2 or 3 with a node list beyond the LDS limit (form 0 is then form 4).  Form 4 is accepted
+ * at every size: k_octree_global needs nothing but its slab, which this entry allocates whenever form 4 runs. */
+int orbfe_debug_octree_device(int device, int form, int n_frames, const uint16_t *xs, const uint16_t *ys,
+                              const uint8_t *resp, const int32_t *n_per_frame, int minX, int maxX, int minY, int maxY,
+                              int N, uint16_t *out_x, uint16_t *out_y, uint16_t *out_resp, uint16_t *out_rank,
+                              int32_t *out_count, int cap, int32_t *info6);
 int orbfe_debug_geometry(int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST, int width,
                          int height, int32_t *levels9, float *tables4 /* scale, invScale, sigma2, invSigma2 per level; may be NULL */,
                          int16_t *cells5, int cell_cap);

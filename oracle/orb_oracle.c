@@ -518,6 +518,21 @@ int orc_grid_candidates(const orc_extractor *e, const uint8_t *img, int cols, in
 /* reference's (count, pointer) sort key becomes (count, creation order)*/
 /* -- documented deviation, SURVEY.md 7 hard part 4.                    */
 /* ------------------------------------------------------------------ */
+/* one counter per decision of the last orc_distribute_octtree call of this thread (the order is ORC_OB_* below and in
+   orb_oracle.h); the tests use them to show that a candidate set reaches the branch it was built for.  Reset when the
+   call starts; they change no result. */
+enum { ORC_OB_ROOTS, ORC_OB_ROOT_EMPTY_DROPPED, ORC_OB_CHILD_EMPTY_DROPPED, ORC_OB_CLOSED_ONE_POINT, ORC_OB_PHASE1_END_N_REACHED,
+       ORC_OB_PHASE1_END_EXACTLY_N, ORC_OB_PHASE1_END_NONE_EXPANDABLE, ORC_OB_PHASE1_END_NO_GROWTH, ORC_OB_LARGEST_FIRST_ENTERED,
+       ORC_OB_LARGEST_FIRST_PASS, ORC_OB_EARLY_BREAK, ORC_OB_BREAK_AT_LAST_NODE, ORC_OB_EQUAL_COUNTS_COMPARED,
+       ORC_OB_LARGEST_FIRST_END_N_REACHED, ORC_OB_LARGEST_FIRST_END_NO_GROWTH, ORC_OB_RESPONSE_TIE_FIRST_WINS, ORC_OB_OVERSHOOT,
+       ORC_OB_COUNT };
+static __thread int64_t g_octree_branch[ORC_OB_COUNT];
+int orc_octree_branch_counts(int64_t *out, int n) {
+  for (int i = 0; i < n && i < ORC_OB_COUNT; i++) out[i] = g_octree_branch[i];
+  return ORC_OB_COUNT;
+}
+#define OB(k) (g_octree_branch[ORC_OB_##k]++)
+
 typedef struct {
   int ULx, ULy, URx, URy, BLx, BLy, BRx, BRy;
   int *keys; /* indices into the input arrays */
@@ -597,14 +612,17 @@ static void divide_node(olist *L, int pi, const float *xs, const float *ys, int 
     else t = n4;
     t->keys[t->nkeys++] = id;
   }
-  for (int k = 0; k < 4; k++)
-    if (L->pool[c[k]].nkeys == 1) L->pool[c[k]].noMore = 1;
+  for (int k = 0; k < 4; k++) {
+    if (L->pool[c[k]].nkeys == 1) { L->pool[c[k]].noMore = 1; OB(CLOSED_ONE_POINT); }
+    if (L->pool[c[k]].nkeys == 0) OB(CHILD_EMPTY_DROPPED);
+  }
 }
 
 typedef struct { int count, seq; } szptr;
 static int szptr_cmp(const void *a, const void *b) {
   const szptr *A = (const szptr *)a, *B = (const szptr *)b;
   if (A->count != B->count) return A->count < B->count ? -1 : 1;
+  OB(EQUAL_COUNTS_COMPARED);
   return A->seq < B->seq ? -1 : (A->seq > B->seq ? 1 : 0);
 }
 
@@ -615,6 +633,7 @@ int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, 
   olist L;
   memset(&L, 0, sizeof(L));
   L.head = L.tail = -1;
+  memset(g_octree_branch, 0, sizeof(g_octree_branch));
   if (nIni <= 0) return 0; /* reference assumes width>height (:560) */
   int *ini = (int *)malloc(sizeof(int) * nIni);
   for (int i = 0; i < nIni; i++) {
@@ -628,6 +647,7 @@ int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, 
     nd->nkeys = 0;
     ol_push_back(&L, ni);
     ini[i] = ni;
+    OB(ROOTS);
   }
   for (int i = 0; i < n; i++) {
     int b = (int)(xs[i] / hX);
@@ -636,8 +656,8 @@ int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, 
     nd->keys[nd->nkeys++] = i;
   }
   for (int lit = L.head; lit >= 0;) { /* :608-619 */
-    if (L.pool[lit].nkeys == 1) { L.pool[lit].noMore = 1; lit = L.pool[lit].next; }
-    else if (L.pool[lit].nkeys == 0) lit = ol_erase(&L, lit);
+    if (L.pool[lit].nkeys == 1) { L.pool[lit].noMore = 1; lit = L.pool[lit].next; OB(CLOSED_ONE_POINT); }
+    else if (L.pool[lit].nkeys == 0) { lit = ol_erase(&L, lit); OB(ROOT_EMPTY_DROPPED); }
     else lit = L.pool[lit].next;
   }
   int bFinish = 0;
@@ -648,12 +668,13 @@ int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, 
   while (!bFinish) {
     int prevSize = L.size;
     int lit = L.head;
-    int nToExpand = 0;
+    int nToExpand = 0, nDivided = 0;
     nSize = 0;
     while (lit >= 0) {
       if (L.pool[lit].noMore) { lit = L.pool[lit].next; continue; }
       int c[4];
       divide_node(&L, lit, xs, ys, c);
+      nDivided++;
       for (int k = 0; k < 4; k++) {
         if (L.pool[c[k]].nkeys > 0) {
           ol_push_front(&L, c[k]);
@@ -664,8 +685,13 @@ int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, 
     }
     if (L.size >= N || L.size == prevSize) {
       bFinish = 1;
+      if (L.size >= N) { OB(PHASE1_END_N_REACHED); if (L.size == N) OB(PHASE1_END_EXACTLY_N); }
+      else if (nDivided == 0) OB(PHASE1_END_NONE_EXPANDABLE);
+      else OB(PHASE1_END_NO_GROWTH);
     } else if (L.size + nToExpand * 3 > N) {
+      OB(LARGEST_FIRST_ENTERED);
       while (!bFinish) {
+        OB(LARGEST_FIRST_PASS);
         prevSize = L.size;
         int nPrev = nSize;
         szptr *vPrev = (szptr *)malloc(sizeof(szptr) * (nPrev > 0 ? nPrev : 1));
@@ -683,10 +709,16 @@ int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, 
             }
           }
           ol_erase(&L, pi);
-          if (L.size >= N) break;
+          if (L.size >= N) {
+            if (j > 0) OB(EARLY_BREAK); else OB(BREAK_AT_LAST_NODE);
+            break;
+          }
         }
         free(vPrev);
-        if (L.size >= N || L.size == prevSize) bFinish = 1;
+        if (L.size >= N || L.size == prevSize) {
+          bFinish = 1;
+          if (L.size >= N) OB(LARGEST_FIRST_END_N_REACHED); else OB(LARGEST_FIRST_END_NO_GROWTH);
+        }
       }
     }
   }
@@ -698,9 +730,12 @@ int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, 
     float maxR = resp[best];
     for (int k = 1; k < nd->nkeys; k++)
       if (resp[nd->keys[k]] > maxR) { best = nd->keys[k]; maxR = resp[best]; }
+    for (int k = 0; k < nd->nkeys; k++)
+      if (nd->keys[k] != best && resp[nd->keys[k]] == maxR) { OB(RESPONSE_TIE_FIRST_WINS); break; }
     if (nout < cap) out_idx[nout] = best;
     nout++;
   }
+  if (nout > N) OB(OVERSHOOT);
   for (int i = 0; i < L.npool; i++) free(L.pool[i].keys);
   free(L.pool);
   free(vSize);

@@ -87,6 +87,22 @@ int orc_grid_candidates(const orc_extractor *e, const uint8_t *img, int w, int h
  * returns number selected; out_idx receives indices into the input in list order. */
 int orc_distribute_octtree(const float *xs, const float *ys, const float *resp, int n, int minX,
                            int maxX, int minY, int maxY, int N, int *out_idx, int cap);
+/* one counter per decision of this thread's last orc_distribute_octtree call (reset when it starts; they change no
+   result).  Order:
+     0 root nodes created (nIni), 1 root without a point erased (:608-619), 2 child without a point not linked (:637-692),
+     3 node closed with one point (bNoMore; roots and children),
+     4 split-everything loop ended because the list reached N (:707), 5 ... and holds exactly N nodes,
+     6 ... ended by a pass in which no node was expandable (every node closed; size == prevSize),
+     7 ... ended because the list did not grow although nodes were divided (coincident points),
+     8 largest-first loop entered (:714), 9 its passes,
+    10 early break: the list reached N with nodes of the pass still unsplit (:774), 11 the list reached N at the last node of
+       a pass,
+    12 two expandable nodes with equal counts compared by the sort (creation order decides),
+    13 largest-first loop ended because the list reached N, 14 ... because the list did not grow,
+    15 returned node whose largest response occurs more than once (the first index wins, :787-805),
+    16 result longer than N.
+   Writes min(n, count) entries, returns the count. */
+int orc_octree_branch_counts(int64_t *out, int n);
 float orc_ic_angle(const uint8_t *img, int stride, int x, int y, const int *umax);
 void orc_descriptor(const uint8_t *blur, int stride, int x, int y, float angle_deg,
                     uint8_t desc[32]);

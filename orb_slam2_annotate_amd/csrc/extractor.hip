@@ -373,15 +373,9 @@ int ensure_geometry(orbfe_extractor* e, int W, int H) {
     if (c.w > 60 || c.h > 60) return fail(ORBFE_ERR_INVALID, "FAST grid cell larger than 60 px");
   for (int l = 0; l < g.nlevels; l++)
     if (g.lv[l].w < 1 || g.lv[l].h < 1) return fail(ORBFE_ERR_INVALID, "image too small for the pyramid");
-  int maxL = 4;
-  for (int l = 0; l < g.nlevels; l++) {
-    if (g.lv[l].kpCap > maxL) maxL = g.lv[l].kpCap;
-    if (g.lv[l].nIni > maxL) maxL = g.lv[l].nIni;
-    if (g.lv[l].slotCount >= (1 << 24)) return fail(ORBFE_ERR_INVALID, "level too large for the octree kernel");
-  }
-  maxL = (maxL + 3) & ~3;
-  if (maxL > 65532)  // 16-bit node positions (nodeOf, order, rank)
-    return fail(ORBFE_ERR_INVALID, "nfeatures too large: more than 65532 keypoints on one pyramid level");
+  const int maxL = octree_node_capacity(g.lv, g.nlevels);
+  if (maxL == 0) return fail(ORBFE_ERR_INVALID, "level too large for the octree kernel");
+  if (maxL < 0) return fail(ORBFE_ERR_INVALID, "nfeatures too large: more than 65532 keypoints on one pyramid level");
   e->octreeMaxL = maxL;  // octree_lds_bytes(maxL) > kOctreeLdsLimit: node lists in global memory (ensure_workspace)
   int rc;
   if ((rc = e->d_cells.upload(g.cells))) return rc;
@@ -425,7 +419,7 @@ int ensure_workspace(orbfe_extractor* e, int nFrames) {
   if ((rc = e->d_levelKp.alloc(B * (size_t)g.totalKpCap))) return rc;
   if ((rc = e->d_levelCount.alloc(B * (size_t)g.nlevels))) return rc;
   if (octree_lds_bytes(e->octreeMaxL) > kOctreeLdsLimit) {
-    e->octreeWorkStride = (octree_lds_bytes(e->octreeMaxL) + 255) & ~(size_t)255;
+    e->octreeWorkStride = octree_work_stride(e->octreeMaxL);
     if ((rc = e->d_octreeWork.alloc(B * (size_t)g.nlevels * e->octreeWorkStride))) return rc;
   }
   e->capFrames = nFrames;
@@ -1842,6 +1836,104 @@ extern "C" int orbfe_debug_octree_host(const uint16_t* xs, const uint16_t* ys, c
   const int k = distribute_octree_host(cand.data(), n, minX, maxX, minY, maxY, N, out.data(), cap);
   for (int i = 0; i < k && i < cap; i++) { out_x[i] = out[i].x; out_y[i] = out[i].y; out_resp[i] = (uint8_t)out[i].score; }
   return k;
+}
+
+// DistributeOctTree of a chosen DEVICE form (k_octree.hip) on n_frames pre-gathered candidate sets of one distribution
+// area: one level, the sets are the frames of one launch.  Never runs the host octree.  See include/orbfe.h.
+extern "C" int orbfe_debug_octree_device(int device, int form, int n_frames, const uint16_t* xs, const uint16_t* ys,
+                                         const uint8_t* resp, const int32_t* n_per_frame, int minX, int maxX, int minY,
+                                         int maxY, int N, uint16_t* out_x, uint16_t* out_y, uint16_t* out_resp,
+                                         uint16_t* out_rank, int32_t* out_count, int cap, int32_t* info6) {
+  const int bw = maxX - minX, bh = maxY - minY;
+  if (form < 0 || form > 4 || n_frames < 1 || N < 0 || N > 65532 || minX < 0 || minY < 0 || bw <= 0 || bh <= 0 ||
+      maxX > 32767 - kMinBorder || maxY > 32767 - kMinBorder || !info6)
+    return fail(ORBFE_ERR_INVALID, "debug_octree_device: bad argument");
+  LevelGeom lg;
+  std::memset(&lg, 0, sizeof(lg));
+  lg.w = bw + 2 * kMinBorder;  // the kernels take the area from the level size and add kMinBorder to what they select
+  lg.h = bh + 2 * kMinBorder;
+  lg.quota = N;
+  octree_level_caps(&lg);
+  int maxN = 0;
+  size_t total = 0;
+  if (n_per_frame)
+    for (int f = 0; f < n_frames; f++) {
+      if (n_per_frame[f] < 0) return fail(ORBFE_ERR_INVALID, "debug_octree_device: negative candidate count");
+      if (n_per_frame[f] > maxN) maxN = n_per_frame[f];
+      total += (size_t)n_per_frame[f];
+    }
+  lg.slotCount = maxN > 0 ? maxN : 1;
+  const int maxL = octree_node_capacity(&lg, 1);
+  if (maxL <= 0) return fail(ORBFE_ERR_INVALID, "debug_octree_device: set or quota too large for the octree kernels");
+  const OctreeForm chosen = octree_choose_form(maxL, n_frames);
+  info6[0] = lg.nIni; info6[1] = lg.kpCap; info6[2] = maxL; info6[3] = (int32_t)octree_lds_bytes(maxL);
+  info6[4] = (int32_t)kOctreeLdsLimit; info6[5] = (int32_t)chosen;
+  if (!out_x) return ORBFE_OK;  // sizes only: no device needed
+  if (!n_per_frame || !out_y || !out_resp || !out_rank || !out_count || cap < lg.kpCap || (total > 0 && (!xs || !ys || !resp)))
+    return fail(ORBFE_ERR_INVALID, "debug_octree_device: bad buffers (cap must hold kpCap slots per frame)");
+  const OctreeForm run = form == 0 ? chosen : (OctreeForm)form;
+  if (run != kOctreeGlobal && octree_lds_bytes(maxL) > kOctreeLdsLimit)
+    return fail(ORBFE_ERR_INVALID, "debug_octree_device: the node list of this quota does not fit the LDS forms");
+  HIPCHK(hipSetDevice(device));
+  const size_t F = (size_t)n_frames, slots = (size_t)lg.slotCount, kpCap = (size_t)lg.kpCap;
+  std::vector<Candidate> h_cand(F * slots);
+  std::memset(h_cand.data(), 0xFF, h_cand.size() * sizeof(Candidate));  // (slots past a frame's count are never read)
+  std::vector<int32_t> h_count(F);
+  size_t at = 0;
+  for (size_t f = 0; f < F; f++) {
+    h_count[f] = n_per_frame[f];
+    for (int i = 0; i < n_per_frame[f]; i++, at++) {
+      h_cand[f * slots + i].xy = (uint32_t)xs[at] | ((uint32_t)ys[at] << 16);
+      h_cand[f * slots + i].score = resp[at];
+    }
+  }
+  DevBuf<Candidate> d_cand;
+  DevBuf<int32_t> d_candCount, d_levelCount;
+  DevBuf<LevelGeom> d_lvg;
+  DevBuf<uint16_t> d_nodeOf;
+  DevBuf<LevelKp> d_levelKp;
+  DevBuf<uint8_t> d_work;
+  int rc;
+  if ((rc = d_cand.upload(h_cand)) || (rc = d_candCount.upload(h_count)) || (rc = d_lvg.upload(&lg, 1))) return rc;
+  if ((rc = d_nodeOf.alloc(F * slots)) || (rc = d_levelKp.alloc(F * kpCap)) || (rc = d_levelCount.alloc(F))) return rc;
+  const size_t workStride = run == kOctreeGlobal ? octree_work_stride(maxL) : 0;
+  if (workStride && (rc = d_work.alloc(F * workStride))) return rc;
+  // every scratch and output array starts as 0xFF bytes: a slot the kernel does not write shows
+  HIPCHK(hipMemset(d_nodeOf, 0xFF, F * slots * sizeof(uint16_t)));
+  HIPCHK(hipMemset(d_levelKp, 0xFF, F * kpCap * sizeof(LevelKp)));
+  HIPCHK(hipMemset(d_levelCount, 0xFF, F * sizeof(int32_t)));
+  if (workStride) HIPCHK(hipMemset(d_work, 0xFF, F * workStride));
+  OctreeArgs oa = {};
+  oa.cand = d_cand;
+  oa.slotsPerFrame = lg.slotCount;
+  oa.candCount = d_candCount;
+  oa.lvg = d_lvg;
+  oa.nlevels = 1;
+  oa.nodeOf = d_nodeOf;
+  oa.levelKp = d_levelKp;
+  oa.levelCount = d_levelCount;
+  oa.kpSlotsPerFrame = lg.kpCap;
+  oa.maxL = maxL;
+  oa.work = workStride ? d_work.p : nullptr;
+  oa.workStride = workStride;
+  hipError_t err = launch_octree_form(nullptr, oa, 1, n_frames, run);
+  if (err == hipErrorInvalidValue) return fail(ORBFE_ERR_INVALID, "debug_octree_device: the form refused these arguments");
+  if (err == hipSuccess) err = hipGetLastError();
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  std::vector<LevelKp> h_kp(F * kpCap);
+  if (err == hipSuccess) err = hipMemcpy(h_kp.data(), d_levelKp, h_kp.size() * sizeof(LevelKp), hipMemcpyDeviceToHost);
+  if (err == hipSuccess) err = hipMemcpy(out_count, d_levelCount, F * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (err != hipSuccess) return fail(ORBFE_ERR_HIP, std::string("debug_octree_device: ") + hipGetErrorString(err));
+  for (size_t f = 0; f < F; f++)
+    for (size_t i = 0; i < kpCap; i++) {
+      const LevelKp k = h_kp[f * kpCap + i];
+      const bool written = out_count[f] >= 0 && (int32_t)i < out_count[f];  // the kernel's + kMinBorder becomes + minX / + minY
+      out_x[f * cap + i] = written ? (uint16_t)(k.x - kMinBorder + minX) : k.x;
+      out_y[f * cap + i] = written ? (uint16_t)(k.y - kMinBorder + minY) : k.y;
+      out_resp[f * cap + i] = k.score;
+      out_rank[f * cap + i] = k.rank;
+    }
+  return ORBFE_OK;
 }
 
 // Geometry tables the pipeline derives on the host for a WxH input: per level (w, h, nCols, nRows,

@@ -677,23 +677,49 @@ bool octree_gathers(int nFrames, int maxL) {
   return !off && nFrames > 0 && nFrames <= 8 && octree_lds_bytes(maxL) <= kOctreeLdsLimit && octree_latency_threads() == 1024;
 }
 
+int octree_node_capacity(const LevelGeom* lv, int nlevels) {
+  int maxL = 4;
+  for (int l = 0; l < nlevels; l++) {
+    if (lv[l].kpCap > maxL) maxL = lv[l].kpCap;
+    if (lv[l].nIni > maxL) maxL = lv[l].nIni;
+    if (lv[l].slotCount >= (1 << 24)) return 0;
+  }
+  maxL = (maxL + 3) & ~3;
+  return maxL > 65532 ? -1 : maxL;  // 16-bit node positions (nodeOf, order, rank)
+}
+
+size_t octree_work_stride(int maxL) { return (octree_lds_bytes(maxL) + 255) & ~(size_t)255; }
+
+OctreeForm octree_choose_form(int maxL, int nFrames) {
+  if (octree_lds_bytes(maxL) > kOctreeLdsLimit) return kOctreeGlobal;  // node list in global memory
+  const bool latencyForm = nFrames <= 8;  // too few workgroups to fill the GPU anyway
+  // (the 1024-thread form for whole batches, measured once: octree stage 0.63 -> 1.81 ms per 1024 KITTI frames, 1.19 -> 3.52 per
+  // 4096 VGA frames, pipelines -17 % -- sixteen waves per problem leave room for two problems per CU instead of six)
+  if (latencyForm) return octree_latency_threads() == 1024 ? kOctreeReg1024 : kOctreeReg;
+  return kOctreeThroughput;
+}
+
 hipError_t launch_octree(hipStream_t s, const OctreeArgs& args, int nlevels, int nFrames) {
+  if (nFrames <= 0) return hipSuccess;
+  return launch_octree_form(s, args, nlevels, nFrames, octree_choose_form(args.maxL, nFrames));
+}
+
+hipError_t launch_octree_form(hipStream_t s, const OctreeArgs& args, int nlevels, int nFrames, OctreeForm form) {
   if (nFrames <= 0) return hipSuccess;
   OctreeArgs a = args;
   a.nFrames = nFrames;
   size_t lds = octree_lds_bytes(a.maxL);
-  if (lds > kOctreeLdsLimit) {  // node list in global memory
+  if (form == kOctreeGlobal) {
     if (!a.work || a.workStride < lds) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_octree_global, dim3(nFrames, nlevels), dim3(256), 0, s, a);
     return hipSuccess;
   }
-  const bool latencyForm = nFrames <= 8;  // too few workgroups to fill the GPU anyway
+  if (lds > kOctreeLdsLimit) return hipErrorInvalidValue;
+  const bool wide = form == kOctreeReg1024, latencyForm = wide || form == kOctreeReg;
+  if (!latencyForm && form != kOctreeThroughput) return hipErrorInvalidValue;
   static const size_t pad = occupancy_pad_bytes("OCTREE", 0);
   if (!latencyForm && lds + pad <= 64 * 1024) lds += pad;
   static thread_local size_t configured[3] = {0, 0, 0};
-  // (the 1024-thread form for whole batches, measured once: octree stage 0.63 -> 1.81 ms per 1024 KITTI frames, 1.19 -> 3.52 per
-  // 4096 VGA frames, pipelines -17 % -- sixteen waves per problem leave room for two problems per CU instead of six)
-  const bool wide = latencyForm && octree_latency_threads() == 1024;
   if (a.gCells && !wide) return hipErrorInvalidValue;  // (only the wide single-frame form gathers)
   const void* fn = wide ? reinterpret_cast<const void*>(k_octree_reg1024)
                         : (latencyForm ? reinterpret_cast<const void*>(k_octree_reg) : reinterpret_cast<const void*>(k_octree));

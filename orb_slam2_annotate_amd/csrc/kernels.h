@@ -195,6 +195,16 @@ struct OctreeArgs {
 bool octree_gathers(int nFrames, int maxL);  // launch_octree(..., nFrames) will run the form that gathers: fill the g* fields, skip launch_gather_candidates
 constexpr size_t kOctreeLdsLimit = 150 * 1024;  // beyond it the node list lives in global memory (k_octree_global)
 size_t octree_lds_bytes(int maxL);
+// node capacity of a geometry: the largest kpCap / nIni of its levels, at least 4, rounded up to a multiple of 4.
+// 0: a level has 2^24 or more candidate slots (24-bit candidate indices); -1: more than 65532 nodes (16-bit node positions)
+int octree_node_capacity(const LevelGeom* lv, int nlevels);
+size_t octree_work_stride(int maxL);  // bytes of one (frame, level) slab of k_octree_global
+// the four kernels; launch_octree = launch_octree_form(..., octree_choose_form(...))
+enum OctreeForm { kOctreeThroughput = 1, kOctreeReg = 2, kOctreeReg1024 = 3, kOctreeGlobal = 4 };
+OctreeForm octree_choose_form(int maxL, int nFrames);
+// launches `form` as launch_octree would: hipErrorInvalidValue when the form cannot run these arguments (an LDS form whose
+// node list exceeds kOctreeLdsLimit, the global form without a slab, gCells on a form that does not gather)
+hipError_t launch_octree_form(hipStream_t s, const OctreeArgs& a, int nlevels, int nFrames, OctreeForm form);
 hipError_t launch_octree(hipStream_t s, const OctreeArgs& a, int nlevels, int nFrames);
 
 // ---- blur (GaussianBlur 7x7 sigma 2 reflect-101, :1169-1175) ----

@@ -137,6 +137,19 @@ void build_resize_tables(int sw, int sh, int dw, int dh, ResizeTables* t) {
   }
 }
 
+void octree_level_caps(LevelGeom* lv) {
+  LevelGeom& g = *lv;
+  // DistributeOctTree roots, :570
+  const int bw = g.w - 2 * kMinBorder, bh = g.h - 2 * kMinBorder;  // maxBorder - minBorder
+  g.nIni = (bw > 0 && bh > 0) ? (int)std::round((float)bw / (float)bh) : 0;
+  if (g.nIni < 0) g.nIni = 0;
+  // per-level output bound: phase 2 stops at >= quota after adding at most 3 per split;
+  // the first split pass can create 4*nIni leaves regardless of the quota (Appendix A3).
+  int cap = g.quota + 3;
+  if (cap < 4 * g.nIni) cap = 4 * g.nIni;
+  g.kpCap = cap;
+}
+
 void FrameGeom::build(const ExtractorTables& t, int W_, int H_) {
   W = W_;
   H = H_;
@@ -202,17 +215,9 @@ void FrameGeom::build(const ExtractorTables& t, int W_, int H_) {
     }
     g.nCells = (int)cells.size() - g.cellStart;
     g.slotCount = slots - g.slotStart;
-    // DistributeOctTree roots, :570
-    const int bw = maxBX - minBX, bh = maxBY - minBY;
-    g.nIni = (bw > 0 && bh > 0) ? (int)std::round((float)bw / (float)bh) : 0;
-    if (g.nIni < 0) g.nIni = 0;
-    // per-level output bound: phase 2 stops at >= quota after adding at most 3 per split;
-    // the first split pass can create 4*nIni leaves regardless of the quota (Appendix A3).
-    int cap = g.quota + 3;
-    if (cap < 4 * g.nIni) cap = 4 * g.nIni;
+    octree_level_caps(&g);
     g.kpStart = kps;
-    g.kpCap = cap;
-    kps += cap;
+    kps += g.kpCap;
     if (l > 0) build_resize_tables(lv[l - 1].w, lv[l - 1].h, g.w, g.h, &rz[l]);
   }
   pyrBytes = off;

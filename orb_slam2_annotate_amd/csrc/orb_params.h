@@ -74,6 +74,9 @@ struct FrameGeom {
   void build(const ExtractorTables& t, int W, int H);
 };
 
+// nIni and kpCap of a level from its w, h and quota (the octree's share of FrameGeom::build)
+void octree_level_caps(LevelGeom* lv);
+
 void build_resize_tables(int sw, int sh, int dw, int dh, ResizeTables* out);
 
 }  // namespace orbfe

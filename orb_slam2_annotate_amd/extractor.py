@@ -302,6 +302,36 @@ class ORBextractor:
         check(self._L.orbfe_extractor_set_fused(self._h, int(bool(enable))))
 
 
+OCTREE_FORMS = {0: "auto", 1: "k_octree", 2: "k_octree_reg", 3: "k_octree_reg1024", 4: "k_octree_global"}
+
+
+def debug_octree_limits(minX: int, maxX: int, minY: int, maxY: int, N: int, n_frames: int = 1, max_n: int = 0) -> dict:
+    """The octree stage's sizes for one distribution area and quota (no GPU needed): nIni, kpCap, the node capacity maxL,
+    its LDS bytes, the LDS limit and the form a launch of n_frames frames takes (1-4, see OCTREE_FORMS)."""
+    info = np.zeros(6, np.int32)
+    npf = np.full(max(n_frames, 1), max_n, np.int32)
+    check(_lib.load().orbfe_debug_octree_device(0, 0, n_frames, None, None, None, ptr(npf), minX, maxX, minY, maxY, N,
+                                                None, None, None, None, None, 0, ptr(info)))
+    return dict(zip(("nIni", "kpCap", "maxL", "lds_bytes", "lds_limit", "form"), (int(v) for v in info)))
+
+
+def debug_octree_device(sets, minX: int, maxX: int, minY: int, maxY: int, N: int, form: int = 0, device: int = 0):
+    """DistributeOctTree of one device form (OCTREE_FORMS) on the candidate sets [(xs, ys, responses), ...] of one area, as
+    the frames of one launch.  Returns one dict per set: count, and x / y / resp / rank of ALL kpCap slots of the kernel's
+    output array in the kernel's (spatial) order -- the first `count` are keypoints, rank is their position in the
+    reference's list order, the rest is the 0xFF fill."""
+    sets = [tuple(np.ascontiguousarray(a, dt) for a, dt in zip(s, (np.uint16, np.uint16, np.uint8))) for s in sets]
+    npf = np.array([len(s[0]) for s in sets], np.int32)
+    xs, ys, rs = (np.ascontiguousarray(np.concatenate([s[i] for s in sets])) for i in range(3))
+    cap = debug_octree_limits(minX, maxX, minY, maxY, N, len(sets), int(npf.max()))["kpCap"]
+    F = len(sets)
+    ox, oy, orr, ork = (np.zeros((F, cap), np.uint16) for _ in range(4))
+    cnt, info = np.zeros(F, np.int32), np.zeros(6, np.int32)
+    check(_lib.load().orbfe_debug_octree_device(device, int(form), F, ptr(xs), ptr(ys), ptr(rs), ptr(npf), minX, maxX, minY,
+                                                maxY, N, ptr(ox), ptr(oy), ptr(orr), ptr(ork), ptr(cnt), cap, ptr(info)))
+    return [{"count": int(cnt[f]), "x": ox[f], "y": oy[f], "resp": orr[f], "rank": ork[f]} for f in range(F)]
+
+
 def resize_linear(src: np.ndarray, dw: int, dh: int, device: int = 0) -> np.ndarray:
     src = np.ascontiguousarray(src, dtype=np.uint8)
     sh, sw = src.shape

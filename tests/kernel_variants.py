@@ -334,6 +334,33 @@ def variant(name, env, setup=None):
     return deco
 
 
+def octree_item_cases(run: Run, count=300):
+    """`count` small candidate sets of tests/octree_edges.py as the frames of ONE k_octree launch (form 1 of
+    orbfe_debug_octree_device), each frame against the oracle's DistributeOctTree in the reference's list order."""
+    import octree_edges as oe
+    import oracle_lib as orc
+    from orb_slam2_annotate_amd.extractor import debug_octree_device
+    items = oe.small_items(count)
+    minX, _, minY, _ = oe.AREA
+    got = debug_octree_device(items, *oe.AREA, oe.NEIGHBOUR_N, form=1)
+    answers = {}
+    for f, ((xs, ys, rs), res) in enumerate(zip(items, got)):
+        key = (xs.tobytes(), ys.tobytes(), rs.tobytes())
+        if key not in answers:
+            answers[key] = orc.distribute_octtree(xs, ys, rs, *oe.AREA, oe.NEIGHBOUR_N)
+        idx = answers[key]
+        if res["count"] != len(idx):
+            _fail("octree_items", f, "count", min(res["count"], len(idx)), f"gpu {res['count']} vs oracle {len(idx)}")
+        o = np.argsort(res["rank"][:len(idx)], kind="stable")
+        for name, a, b in (("x", xs[idx] + minX, res["x"][:len(idx)][o]), ("y", ys[idx] + minY, res["y"][:len(idx)][o]),
+                           ("response", rs[idx], res["resp"][:len(idx)][o])):
+            i = _first_diff(np.asarray(a, np.int64), np.asarray(b, np.int64))
+            if i >= 0:
+                _fail("octree_items", f, name, i, f"gpu {b[i]} vs oracle {a[i]}")
+        run.frames += 1
+        run.keypoints += len(idx)
+
+
 @variant("octree_t256", {"ORBFE_OCTREE_T": "256"})
 def _octree_t256(run):
     """launch_octree: a launch of <= 8 frames is the latency form, and with 256 threads it is k_octree_reg
@@ -356,8 +383,10 @@ def _octree_grid1(run):
     """k_octree's persistent loop: 1 workgroup per CU = a grid of 256.  mixed40_1stream launches 40 frames x 8 levels =
     320 (frame, level) items > 256 workgroups, so workgroups 0..63 take a second item (it = blockIdx.x + 256).  The other
     throughput launches (9 x 8 = 72 items, 10 x 8 per sub-batch of the 8-stream call, 12 x 1) stay below the grid:
-    one item each."""
+    one item each.  octree_item_cases adds ONE launch of form 1 (k_octree) over 300 small candidate sets = 300 one-level
+    (frame, level) items > 256: workgroups 0..43 take a second item, each next to other sets than in the launch above."""
     throughput_cases(run)
+    octree_item_cases(run)
 
 
 @variant("orient_kpb128", {"ORBFE_ORIENT_KPB": "128"})

@@ -124,6 +124,21 @@ def bow_branch_counts() -> dict:
     return dict(zip(BOW_BRANCHES, (int(v) for v in out)))
 
 
+OCTREE_BRANCHES = ("roots", "root_empty_dropped", "child_empty_dropped", "closed_one_point", "phase1_end_n_reached",
+                   "phase1_end_exactly_n", "phase1_end_none_expandable", "phase1_end_no_growth", "largest_first_entered",
+                   "largest_first_pass", "early_break", "break_at_last_node", "equal_counts_compared",
+                   "largest_first_end_n_reached", "largest_first_end_no_growth", "response_tie_first_wins", "overshoot")
+
+
+def octree_branch_counts() -> dict:
+    """decision of DistributeOctTree -> how often this thread's last distribute_octtree call took it
+    (orc_octree_branch_counts; the order is documented in oracle/orb_oracle.h)"""
+    out = (C.c_int64 * len(OCTREE_BRANCHES))()
+    n = lib().orc_octree_branch_counts(out, len(OCTREE_BRANCHES))
+    assert n == len(OCTREE_BRANCHES)
+    return dict(zip(OCTREE_BRANCHES, (int(v) for v in out)))
+
+
 def stereo_delta_r(dist1, dist2, dist3) -> np.float32:
     """the oracle's parabola fit (src/Frame.cc:648)"""
     L = lib()

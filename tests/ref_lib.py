@@ -384,3 +384,41 @@ def recorded_octree():
         "the candidate-set generator drifted from the recording"
     ends = np.cumsum(g["octree/count"])
     return [g["octree/idx"][e - c:e].astype(np.int32) for c, e in zip(g["octree/count"], ends)]
+
+
+# ---- the engineered sets of tests/octree_edges.py: recorded next to the sets above, under keys of their own ----
+_edge_sets = None
+
+
+def octree_edge_sets():
+    """octree_edges.edge_sets() at the node-list seam of the built library (its own LDS figures; needs no GPU)"""
+    global _edge_sets
+    if _edge_sets is None:
+        import octree_edges as oe
+        from orb_slam2_annotate_amd.extractor import debug_octree_limits
+        _edge_sets = oe.edge_sets(oe.largest_lds_quota(lambda N: debug_octree_limits(*oe.AREA, N)))
+    return _edge_sets
+
+
+def octree_edge_sets_in_domain():
+    import octree_edges as oe
+    return [s for s in octree_edge_sets() if s[0] not in oe.OUT_OF_DOMAIN]
+
+
+def octree_edges_record(results):
+    """{key: array} for the index lists `results` of octree_edge_sets_in_domain(), in its order"""
+    sets = octree_edge_sets_in_domain()
+    assert len(results) == len(sets)
+    return {"octree_edges/inputs_sha": np.stack([octree_inputs_sha(s) for s in sets]),
+            "octree_edges/count": np.array([len(r) for r in results], np.int32),
+            "octree_edges/idx": np.concatenate(results).astype(np.uint16)}
+
+
+def recorded_octree_edges():
+    """{name: recorded index list} of octree_edge_sets_in_domain(), after checking that the sets are the recorded ones"""
+    g = golden_x()
+    sets = octree_edge_sets_in_domain()
+    assert np.array_equal(g["octree_edges/inputs_sha"], np.stack([octree_inputs_sha(s) for s in sets])), \
+        "the engineered sets (or the library's node-list limit) drifted from the recording"
+    ends = np.cumsum(g["octree_edges/count"])
+    return {s[0]: g["octree_edges/idx"][e - c:e].astype(np.int32) for s, c, e in zip(sets, g["octree_edges/count"], ends)}

@@ -56,6 +56,13 @@ def record_extractor():
         kps, desc, levels, _ = ref_lib.ref_extract(name)
         rec.update(ref_lib.case_record(name, kps, desc, levels, ref_lib.ref_tables(ref_lib.case(name)[5])))
     rec.update(ref_lib.octree_record([ref_lib.ref_octree(*s[1:]) for s in ref_lib.octree_sets()]))
+    rec.update(ref_lib.octree_edges_record([ref_lib.ref_octree(*s[1:]) for s in ref_lib.octree_edge_sets_in_domain()]))
+    if ref_lib.GOLDEN_X.is_file():  # a recording that is already there keeps every record it holds, byte for byte
+        with np.load(ref_lib.GOLDEN_X) as z:
+            for k in z.files:
+                assert k in rec and rec[k].dtype == z[k].dtype and rec[k].shape == z[k].shape and \
+                    rec[k].tobytes() == z[k].tobytes(), f"record {k} changed"
+            print(len(z.files), "earlier records unchanged")
     np.savez_compressed(ref_lib.GOLDEN_X, **rec)
     print(ref_lib.GOLDEN_X, len(rec), "arrays", ref_lib.GOLDEN_X.stat().st_size, "bytes")
 
