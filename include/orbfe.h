@@ -174,7 +174,8 @@ int orbfe_debug_octree_host(const uint16_t *xs, const uint16_t *ys, const uint8_
  * concatenated in xs / ys / resp with n_per_frame[f] candidates each.  The sets run as the (frame, level) items of ONE
  * launch of a one-level geometry; the candidates are handed over gathered (no in-kernel gather).  The host octree is
  * never called.
- *   form: 0 = the form the extractor's launch picks for n_frames frames, 1 = k_octree (throughput form), 2 = k_octree_reg,
+ *   form: 0 = the form the extractor's launch picks for n_frames frames, 1 = k_octree (throughput form: 16-bit counts, and
+ *         k_octree_wide behind it for the sets of more than 65535 candidates), 2 = k_octree_reg,
  *         3 = k_octree_reg1024, 4 = k_octree_global.
  *   info6 (always written): nIni, kpCap (keypoint slots per frame), node capacity maxL, octree_lds_bytes(maxL), the LDS
  *         limit beyond which the node list lives in global memory, and the form that 0 stands for.  With out_x == NULL
@@ -191,6 +192,11 @@ int orbfe_debug_octree_device(int device, int form, int n_frames, const uint16_t
                               const uint8_t *resp, const int32_t *n_per_frame, int minX, int maxX, int minY, int maxY,
                               int N, uint16_t *out_x, uint16_t *out_y, uint16_t *out_resp, uint16_t *out_rank,
                               int32_t *out_count, int cap, int32_t *info6);
+/* debug_octree_carve (no GPU needed): how the octree kernels lay out the node arrays of one (frame, level) item of node
+ * capacity maxL, with 16-bit counts (narrow != 0: k_octree) or 32-bit counts (every other kernel).
+ *   out11: the byte offsets of rect[0], rect[1], cnt[0], cnt[1], child, scanA, scanB, order, inS; the end of the carve;
+ *          and octree_lds_bytes(maxL, narrow), the LDS a launch asks for. */
+int orbfe_debug_octree_carve(int maxL, int narrow, int64_t *out11);
 int orbfe_debug_geometry(int nfeatures, float scaleFactor, int nlevels, int iniThFAST, int minThFAST, int width,
                          int height, int32_t *levels9, float *tables4 /* scale, invScale, sigma2, invSigma2 per level; may be NULL */,
                          int16_t *cells5, int cell_cap);

@@ -713,6 +713,7 @@ int run_chunk(orbfe_extractor* e, hipStream_t s, int sub, LevelView level0, int 
     oa.levelCount = levelCount;
     oa.kpSlotsPerFrame = g.totalKpCap;
     oa.maxL = e->octreeMaxL;
+    oa.narrowLevels = octree_narrow_levels(g.lv, g.nlevels);
     oa.work = e->d_octreeWork ? e->d_octreeWork + F * (size_t)g.nlevels * e->octreeWorkStride : nullptr;
     oa.workStride = e->octreeWorkStride;
     HIPCHK(launch_octree(sT, oa, g.nlevels, nFrames));
@@ -1914,6 +1915,7 @@ extern "C" int orbfe_debug_octree_device(int device, int form, int n_frames, con
   oa.levelCount = d_levelCount;
   oa.kpSlotsPerFrame = lg.kpCap;
   oa.maxL = maxL;
+  oa.narrowLevels = octree_narrow_levels(&lg, 1);
   oa.work = workStride ? d_work.p : nullptr;
   oa.workStride = workStride;
   hipError_t err = launch_octree_form(nullptr, oa, 1, n_frames, run);
@@ -1933,6 +1935,16 @@ extern "C" int orbfe_debug_octree_device(int device, int form, int n_frames, con
       out_resp[f * cap + i] = k.score;
       out_rank[f * cap + i] = k.rank;
     }
+  return ORBFE_OK;
+}
+
+// The node-array layout of the octree kernels (octree_carve, kernels.h) and the LDS bytes a launch asks for.
+extern "C" int orbfe_debug_octree_carve(int maxL, int narrow, int64_t* out11) {
+  if (maxL < 4 || maxL > 65532 || (maxL & 3) || !out11) return fail(ORBFE_ERR_INVALID, "debug_octree_carve: bad argument");
+  const OctreeCarve c = octree_carve(maxL, narrow ? 2 : 4);
+  const uint32_t v[10] = {c.rect0, c.rect1, c.cnt0, c.cnt1, c.child, c.scanA, c.scanB, c.order, c.inS, c.end};
+  for (int i = 0; i < 10; i++) out11[i] = v[i];
+  out11[10] = (int64_t)octree_lds_bytes(maxL, narrow != 0);
   return ORBFE_OK;
 }
 

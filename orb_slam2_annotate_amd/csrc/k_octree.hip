@@ -41,8 +41,8 @@ __device__ __forceinline__ int octree_wave_incl_scan(int v, int lane) {
   }
   return x;
 }
-template <int T, bool kDpp>
-__device__ int block_scan_excl(int* a, int len, int* waveTot) {
+template <int T, bool kDpp, typename CT>
+__device__ int block_scan_excl(CT* a, int len, int* waveTot) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int run = 0;
   for (int base = 0; base < len; base += T) {
@@ -51,7 +51,7 @@ __device__ int block_scan_excl(int* a, int len, int* waveTot) {
     const int x = octree_wave_incl_scan<kDpp>(v, lane);
     if (T == 64) {  // one wavefront: the running total lives in a register
       const int tot = __builtin_amdgcn_readlane(x, 63);
-      if (i < len) a[i] = run + x - v;
+      if (i < len) a[i] = (CT)(run + x - v);
       run += tot;
     } else {
       if (lane == 63) waveTot[wave] = x;
@@ -60,7 +60,7 @@ __device__ int block_scan_excl(int* a, int len, int* waveTot) {
       for (int w = 0; w < wave; w++) b += waveTot[w];
 #pragma unroll
       for (int w = 0; w < T / 64; w++) run += waveTot[w];
-      if (i < len) a[i] = b + x - v;
+      if (i < len) a[i] = (CT)(b + x - v);
       __syncthreads();
     }
   }
@@ -76,18 +76,27 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // exclusive scan of a[0..len) in place by ONE wavefront (lane = 0..63); returns the total to every lane
-template <bool kDpp>
-__device__ __forceinline__ int wave_scan_excl(int* a, int len, int lane) {
+template <bool kDpp, typename CT>
+__device__ __forceinline__ int wave_scan_excl(CT* a, int len, int lane) {
   int run = 0;
   for (int base = 0; base < len; base += 64) {
     const int i = base + lane;
     const int v = i < len ? a[i] : 0;
     const int x = octree_wave_incl_scan<kDpp>(v, lane);
-    if (i < len) a[i] = run + x - v;
+    if (i < len) a[i] = (CT)(run + x - v);
     run += __builtin_amdgcn_readlane(x, 63);
   }
   wave_sync();
   return run;
+}
+
+// a[i] += v on a count array.  16-bit counts are added as one half of their aligned 32-bit word (LDS and global atomics are 32
+// bits wide): every count of a level is at most its candidate count n <= kOctreeNarrowMaxN = 65535, so the low half never
+// carries into the high one.  The array starts on a 4-byte boundary (octree_carve).
+template <typename CT>
+__device__ __forceinline__ void count_add(CT* a, int i, int v) {
+  if constexpr (sizeof(CT) == 4) atomicAdd(&a[i], v);
+  else atomicAdd(reinterpret_cast<unsigned int*>(a) + (i >> 1), (unsigned int)v << ((i & 1) * 16));
 }
 
 __device__ __forceinline__ int quadrant(const Rect r, int x, int y) {
@@ -115,25 +124,40 @@ __device__ __forceinline__ Rect child_rect(const Rect r, int q) {
 // take the global-memory form of the same loops.
 constexpr int kRegCand = 16;
 
-template <bool REG, int T, bool HYB = false, int RC = kRegCand>
+// CT: element type of the count arrays.  What they hold, from the passes below:
+//   cnt    keys of a node                                        <= n
+//   child  keys of a child, then (pass E) its list position      <= n, < maxL
+//   scanA  0/1 flags and their scan (<= maxL); in the largest-first passes the list growth of the splits walked so far, at
+//          most 3 per split (<= 3 * maxL)
+//   scanB  keys of a root (<= n), then 0/1 flags, their scan and list positions (<= maxL)
+// so uint16_t holds all of them when n <= kOctreeNarrowMaxN and 3 * maxL <= 65535 (every LDS form: static_assert below); node
+// positions are 16-bit anyway.  A level of more candidates (noise images, slotCount goes up to 2^24) takes CT = int.
+static_assert(3 * (kOctreeLdsLimit / 53) <= 65535, "scanA of the 16-bit form holds up to 3 * maxL");
+template <bool REG, int T, bool HYB = false, int RC = kRegCand, typename CT = int>
 __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, int* waveTot, int* sh, const int l, const int f) {
   const int tid = threadIdx.x;
   constexpr bool kDpp = REG || T == 1024;  // the single-frame forms (see octree_wave_incl_scan)
   const LevelGeom g = a.lvg[l];
   const int M = a.maxL;
-  // LDS carve (M entries each)
+  // LDS carve (M entries each; octree_carve, kernels.h, is also what octree_lds_bytes adds up)
+  const OctreeCarve cv = octree_carve(M, (int)sizeof(CT));
   Rect* rect[2];
-  int* cnt[2];
-  rect[0] = reinterpret_cast<Rect*>(smem);
-  rect[1] = rect[0] + M;
-  cnt[0] = reinterpret_cast<int*>(rect[1] + M);
-  cnt[1] = cnt[0] + M;
-  int* child = cnt[1] + M;        // [4*M] child key counts, later child list positions
-  int* scanA = child + 4 * M;     // [M] scans over processing order
-  int* scanB = scanA + M;         // [M] scans over list order
-  uint16_t* order = reinterpret_cast<uint16_t*>(scanB + M);  // [M] processing order -> list position
-  uint16_t* rankOf = order + M;   // [M] list position -> processing rank (valid where inS)
-  uint8_t* inS = reinterpret_cast<uint8_t*>(rankOf + M);      // [M]
+  CT* cnt[2];
+  rect[0] = reinterpret_cast<Rect*>(smem + cv.rect0);
+  rect[1] = reinterpret_cast<Rect*>(smem + cv.rect1);
+  cnt[0] = reinterpret_cast<CT*>(smem + cv.cnt0);
+  cnt[1] = reinterpret_cast<CT*>(smem + cv.cnt1);
+  CT* child = reinterpret_cast<CT*>(smem + cv.child);  // [4*M] child key counts, later child list positions
+  CT* scanA = reinterpret_cast<CT*>(smem + cv.scanA);  // [M] scans over processing order
+  CT* scanB = reinterpret_cast<CT*>(smem + cv.scanB);  // [M] scans over list order
+  uint16_t* order = reinterpret_cast<uint16_t*>(smem + cv.order);  // [M] processing order -> list position
+  uint8_t* inS = smem + cv.inS;                                     // [M]
+  // Shared storage: the two 32-bit arrays of the output phase, best[M] and skey[M], lie over child (4 * M counts) and over
+  // cnt[0] ++ cnt[1] (2 * M counts, adjacent), at least 4 * M bytes each for either CT.  The split loop is the only reader of
+  // cnt and child, its last read is pass F of the last pass, and the __syncthreads() that ends every pass stands between
+  // that read and the first store to best; nothing after the loop reads a node's count or child.
+  int* best = reinterpret_cast<int*>(smem + cv.child);
+  uint32_t* skey = reinterpret_cast<uint32_t*>(smem + cv.cnt0);
 
   const int n = a.candCount[(size_t)f * a.nlevels + l];
   const Candidate* cand = a.cand + (size_t)f * a.slotsPerFrame + g.slotStart;
@@ -167,7 +191,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
       // root counts: one LDS atomic per wave and root instead of one per candidate on 1-3 addresses
       for (int b = 0; b < nIni; b++) {
         const unsigned long long m = __ballot(k < n && knode[j] == (uint32_t)b);
-        if ((tid & 63) == 0 && m) atomicAdd(&scanB[b], __popcll(m));
+        if ((tid & 63) == 0 && m) count_add(scanB, b, __popcll(m));
       }
     }
   } else {
@@ -182,7 +206,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
         int b = (int)__fdiv_rn((float)(xy4[u] & 0xffffu), hX);
         if (b >= nIni) b = nIni - 1;
         nodeOf[k] = (uint16_t)b;
-        atomicAdd(&scanB[b], 1);
+        count_add(scanB, b, 1);
       }
     }
   }
@@ -215,7 +239,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
   for (;;) {
     const int prevSize = L;
     Rect* rc = rect[cur];
-    int* cn = cnt[cur];
+    CT* cn = cnt[cur];
     // A. candidates of this pass
     for (int p = tid; p < L; p += T) {
       const bool c = phase2 ? (p < C && cn[p] > 1) : (cn[p] > 1);
@@ -245,7 +269,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
           int bin = -1;
           if (j * T + tid < n && in4[u]) bin = 4 * p + quadrant(r4[u], (int)(kxy[j] & 0xffffu), (int)(kxy[j] >> 16));
           kbin[j] = bin;
-          if (bin >= 0) atomicAdd(&child[bin], 1);
+          if (bin >= 0) count_add(child, bin, 1);
         }
       }
     } else {
@@ -264,13 +288,13 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
 #pragma unroll
         for (int u = 0; u < 4; u++)
           if (k0 + u * T < n && inS[p4[u]])
-            atomicAdd(&child[4 * p4[u] + quadrant(rc[p4[u]], (int)(xy4[u] & 0xffffu), (int)(xy4[u] >> 16))], 1);
+            count_add(child, 4 * p4[u] + quadrant(rc[p4[u]], (int)(xy4[u] & 0xffffu), (int)(xy4[u] >> 16)), 1);
       }
     }
     __syncthreads();
     int Cn, nSurv;
     Rect* rn = rect[cur ^ 1];
-    int* cnn = cnt[cur ^ 1];
+    CT* cnn = cnt[cur ^ 1];
     if constexpr (HYB) {
       // C-E on the node list belong to wave 0 alone: ~20 short dependent LDS steps that cost a workgroup barrier each
       // when 256 threads share them (a barrier is ~1 us with 8 workgroups of 4 waves on the CU) and only a compiler
@@ -288,7 +312,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
             if (p2 < C && inS[p2]) { const int c2 = cn[p2]; before = (c2 > c) || (c2 == c && p2 < p); }
             r += __popcll(__ballot(before));
           }
-          if (lane == 0) { order[r] = (uint16_t)p; rankOf[p] = (uint16_t)r; }
+          if (lane == 0) order[r] = (uint16_t)p;
         }
         __syncthreads();
       }
@@ -304,7 +328,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
           wave_sync();
           m = wave_scan_excl<kDpp>(scanA, L, lane);
           for (int p = lane; p < L; p += 64)
-            if (inS[p]) { order[scanA[p]] = (uint16_t)p; rankOf[p] = (uint16_t)scanA[p]; }
+            if (inS[p]) order[scanA[p]] = (uint16_t)p;
           wave_sync();
         } else {
           int E = 0;  // candidates of this pass (all have p < C)
@@ -343,8 +367,8 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
             if (c > 0) {
               const int np = cn0 - 1 - ci;
               rn[np] = child_rect(r, q);
-              cnn[np] = c;
-              child[4 * p + q] = np;
+              cnn[np] = (CT)c;
+              child[4 * p + q] = (CT)np;
               expand += (c > 1);
               ci++;
             }
@@ -355,7 +379,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
             const int np = cn0 + scanB[p];
             rn[np] = rc[p];
             cnn[np] = cn[p];
-            scanB[p] = np;
+            scanB[p] = (CT)np;
           }
         if constexpr (kDpp) expand = wave_sum_dpp(expand);
         else {
@@ -375,7 +399,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
         __syncthreads();
         m = block_scan_excl<T, kDpp>(scanA, L, waveTot);
         for (int p = tid; p < L; p += T)
-          if (inS[p]) { order[scanA[p]] = (uint16_t)p; rankOf[p] = (uint16_t)scanA[p]; }
+          if (inS[p]) order[scanA[p]] = (uint16_t)p;
         __syncthreads();
       } else {
         // rank by (count desc, list position asc) among the candidates (all have p < C)
@@ -394,7 +418,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
               if (p2 < C && inS[p2]) { const int c2 = cn[p2]; before = (c2 > c) || (c2 == c && p2 < p); }
               r += __popcll(__ballot(before));
             }
-            if (lane == 0) { order[r] = (uint16_t)p; rankOf[p] = (uint16_t)r; nE++; }
+            if (lane == 0) { order[r] = (uint16_t)p; nE++; }
           }
         }
         if (tid == 0) sh[0] = 0;
@@ -444,8 +468,8 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
           if (c > 0) {
             const int np = Cn - 1 - ci;
             rn[np] = child_rect(r, q);
-            cnn[np] = c;
-            child[4 * p + q] = np;
+            cnn[np] = (CT)c;
+            child[4 * p + q] = (CT)np;
             expand += (c > 1);
             ci++;
           }
@@ -456,7 +480,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
           const int np = Cn + scanB[p];
           rn[np] = rc[p];
           cnn[np] = cn[p];
-          scanB[p] = np;
+          scanB[p] = (CT)np;
         }
       if (expand) atomicAdd(&sh[2], expand);
       __syncthreads();
@@ -474,7 +498,7 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
 #pragma unroll
         for (int u = 0; u < 4; u++) {
           const int j = j0 + u;
-          const int* srcp = (in4[u] && kbin[j] >= 0) ? &child[kbin[j]] : &scanB[knode[j]];
+          const CT* srcp = (in4[u] && kbin[j] >= 0) ? &child[kbin[j]] : &scanB[knode[j]];
           v4[u] = *srcp;
         }
 #pragma unroll
@@ -512,7 +536,6 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
   }
 
   // ---- best response per node, first key wins ties (:787-805) ----
-  int* best = scanA;
   for (int p = tid; p < L; p += T) best[p] = 0;
   __syncthreads();
   if constexpr (REG) {
@@ -543,7 +566,6 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
   // what one k_orient_desc workgroup processes, and neighbours in memory share the cache lines of
   // their patches.  `rank` keeps the reference's list position, which decides the output row.
   const int nKp = L < g.kpCap ? L : g.kpCap;
-  uint32_t* skey = reinterpret_cast<uint32_t*>(scanB);
   for (int p = tid; p < nKp; p += T) {
     const Candidate c = cand[0xffffffu - ((unsigned)best[p] & 0xffffffu)];
     const uint32_t x = (c.xy & 0xffffu) + kMinBorder, y = (c.xy >> 16) + kMinBorder;  // :909-910
@@ -570,10 +592,20 @@ __device__ __forceinline__ void octree_body(const OctreeArgs& a, uint8_t* smem, 
 // workgroups per CU as LDS allows -- the throughput form for large batches), k_octree_reg keeps them
 // in registers when a level has at most 256 * kRegCand candidates (~100 VGPRs, 4 workgroups per CU,
 // but a 20 % shorter critical path -- the latency form for the live-camera case of a few frames).
-__global__ __launch_bounds__(256) void k_octree(OctreeArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ int waveTot[4];
-  __shared__ int sh[4];
+//
+// The throughput form is a set of dependent LDS chains and its rate is the number of chains in flight, which the LDS node
+// lists bound: with the 53-byte node records of 32-bit counts (a rank array that nothing read among them) 6 items per CU at 2000 features
+// (maxL ~ 440, 23.4 KB each).  k_octree therefore keeps the counts in 16 bits -- 35 bytes per node, 15.5 KB, 10 items per CU
+// by LDS -- and takes the items of at most kOctreeNarrowMaxN candidates, which is every item of a camera frame.  The slot
+// capacity of a level is a worst case far above that (104 k for level 0 of a 1241 x 376 frame that lists ~5000), so the
+// choice is made per item from its n, and the items above the bound are k_octree_wide's (below).
+//
+// Wave slots are the next bound: 8 waves per SIMD, 8 workgroups per CU, need at most 64 VGPRs.  The body alone takes 60; the
+// persistent loop around it -- only $ORBFE_OCTREE_GRID asks for it -- keeps enough scalar state alive across the body to
+// spill SGPRs into 78-81 VGPRs (5-6 workgroups per CU), so the default launch of one workgroup per item is a kernel of its
+// own without the loop (k_octree) and the capped grid keeps the loop (k_octree_capped).
+template <bool kLoop>
+__device__ __forceinline__ void octree_throughput(const OctreeArgs& a, uint8_t* smem, int* waveTot, int* sh) {
   // Throughput form: a 1-D grid of gridDim.x workgroups walks the (level, frame) items LEVEL-MAJOR: all frames of level
   // 0 first, so the long items start first and consecutive workgroups -- which go to consecutive XCDs -- hold equal
   // work.  Round 1 launched a (level, frame) grid: level l of every frame ran on XCD l (8 levels, 8 XCDs) and the XCD
@@ -582,16 +614,56 @@ __global__ __launch_bounds__(256) void k_octree(OctreeArgs a) {
   // grid size, not the LDS, bounds the workgroups in flight, and the rest of each CU stays free for the other streams.
   ORBFE_LATENCY_KERNEL_PRIO();
   const int nItems = a.nlevels * a.nFrames;
-  for (int it = blockIdx.x; it < nItems; it += gridDim.x) {
+  if constexpr (!kLoop) {
+    const int it = blockIdx.x;
+    if (it >= nItems) return;
     const int l = it / a.nFrames, f = it - l * a.nFrames;
-    octree_body<false, 256, true>(a, smem, waveTot, sh, l, f);
-    __syncthreads();  // the next item reuses the LDS arrays
+    const int n = a.candCount[(size_t)f * a.nlevels + l];  // block-uniform
+    if (n > kOctreeNarrowMaxN) return;                     // k_octree_wide's item
+    octree_body<false, 256, true, kRegCand, uint16_t>(a, smem, waveTot, sh, l, f);
+  } else {
+    for (int it = blockIdx.x; it < nItems; it += gridDim.x) {
+      const int l = it / a.nFrames, f = it - l * a.nFrames;
+      const int n = a.candCount[(size_t)f * a.nlevels + l];  // block-uniform
+      if (n > kOctreeNarrowMaxN) continue;                   // k_octree_wide's item
+      octree_body<false, 256, true, kRegCand, uint16_t>(a, smem, waveTot, sh, l, f);
+      __syncthreads();  // the next item reuses the LDS arrays
+    }
   }
+}
+__global__ __launch_bounds__(256) void k_octree(OctreeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ int waveTot[4];
+  __shared__ int sh[4];
+  octree_throughput<false>(a, smem, waveTot, sh);
+}
+__global__ __launch_bounds__(256) void k_octree_capped(OctreeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ int waveTot[4];
+  __shared__ int sh[4];
+  octree_throughput<true>(a, smem, waveTot, sh);
+}
+
+// The items that k_octree leaves: more than kOctreeNarrowMaxN candidates (noise images, engineered sets), 32-bit counts.
+// Launched behind k_octree over the levels whose slot capacity admits such an item (blockIdx.y counts the levels whose
+// bit in narrowLevels is clear), one workgroup per (frame, level); a workgroup whose item was k_octree's returns at once.
+__global__ __launch_bounds__(256) void k_octree_wide(OctreeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  __shared__ int waveTot[4];
+  __shared__ int sh[4];
+  int l = -1;
+  for (int k = 0, seen = 0; k < a.nlevels && l < 0; k++)
+    if (!((a.narrowLevels >> k) & 1u) && seen++ == (int)blockIdx.y) l = k;
+  const int f = blockIdx.x;
+  if (l < 0) return;
+  const int n = a.candCount[(size_t)f * a.nlevels + l];  // block-uniform
+  if (n <= kOctreeNarrowMaxN) return;
+  octree_body<false, 256, true>(a, smem, waveTot, sh, l, f);
 }
 
 // Measured and dropped (round 2): octree_body<false, 64>, ONE wavefront per (frame, level) with no barrier at all.  The
-// number of resident (frame, level) problems is set by their LDS node lists (6 per CU at 2000 features), not by wave
-// slots, so a problem that is worked on by one wave instead of four just takes longer: stage 1.15 -> 2.97 ms per 1024
+// number of resident (frame, level) problems is set by their LDS node lists (6 per CU at 2000 features with the 32-bit
+// counts of that round), not by wave slots, so a problem that is worked on by one wave instead of four just takes longer: stage 1.15 -> 2.97 ms per 1024
 // KITTI frames, 2.05 -> 2.84 ms per 4096 VGA frames, pipeline -17 % / -7 %.  The body stays a template on the size.
 __global__ __launch_bounds__(256) void k_octree_reg(OctreeArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -661,9 +733,17 @@ __global__ __launch_bounds__(256) void k_octree_global(OctreeArgs a) {
   octree_body<false, 256>(a, slab, waveTot, sh, l, f);
 }
 
-size_t octree_lds_bytes(int maxL) {
-  // 2 rect (8) + 2 cnt (4) + child (16) + scanA (4) + scanB (4) + order (2) + rankOf (2) + inS (1)
-  return (size_t)maxL * (2 * 8 + 2 * 4 + 16 + 4 + 4 + 2 + 2 + 1) + 64;
+size_t octree_lds_bytes(int maxL, bool narrow) {
+  // per node, counts of c = 4 (2: narrow) bytes: 2 rect (8) + 2 cnt (c) + child (4 c) + scanA (c) + scanB (c) + order (2) +
+  // inS (1) = 51 (35), + 2 unused for c = 4 (octree_carve); best and skey of the output phase lie over child and cnt
+  return (size_t)octree_carve(maxL, narrow ? 2 : 4).end + 64;
+}
+
+uint32_t octree_narrow_levels(const LevelGeom* lv, int nlevels) {
+  uint32_t m = 0;
+  for (int l = 0; l < nlevels && l < 32; l++)
+    if (lv[l].slotCount <= kOctreeNarrowMaxN) m |= 1u << l;
+  return m;
 }
 
 namespace {
@@ -717,15 +797,19 @@ hipError_t launch_octree_form(hipStream_t s, const OctreeArgs& args, int nlevels
   if (lds > kOctreeLdsLimit) return hipErrorInvalidValue;
   const bool wide = form == kOctreeReg1024, latencyForm = wide || form == kOctreeReg;
   if (!latencyForm && form != kOctreeThroughput) return hipErrorInvalidValue;
+  const size_t ldsWide = lds;
+  if (!latencyForm) lds = octree_lds_bytes(a.maxL, true);  // k_octree: 16-bit counts
   static const size_t pad = occupancy_pad_bytes("OCTREE", 0);
   if (!latencyForm && lds + pad <= 64 * 1024) lds += pad;
-  static thread_local size_t configured[3] = {0, 0, 0};
+  static thread_local size_t configured[4] = {0, 0, 0, 0};
   if (a.gCells && !wide) return hipErrorInvalidValue;  // (only the wide single-frame form gathers)
   const void* fn = wide ? reinterpret_cast<const void*>(k_octree_reg1024)
                         : (latencyForm ? reinterpret_cast<const void*>(k_octree_reg) : reinterpret_cast<const void*>(k_octree));
   const int which = wide ? 2 : (latencyForm ? 1 : 0);
   if (lds > 64 * 1024 && lds > configured[which]) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess && which == 0)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_octree_capped), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     configured[which] = lds;
   }
@@ -738,8 +822,21 @@ hipError_t launch_octree_form(hipStream_t s, const OctreeArgs& args, int nlevels
     // (0.62 vs 0.81 ms per 1024 KITTI frames): no cap by default
     static const int perCu = getenv("ORBFE_OCTREE_GRID") ? atoi(getenv("ORBFE_OCTREE_GRID")) : 0;
     unsigned grid = (unsigned)nlevels * (unsigned)nFrames;
-    if (perCu > 0 && (unsigned)perCu * 256u < grid) grid = (unsigned)perCu * 256u;
-    hipLaunchKernelGGL(k_octree, dim3(grid), dim3(256), lds, s, a);
+    const bool capped = perCu > 0 && (unsigned)perCu * 256u < grid;
+    if (capped) grid = (unsigned)perCu * 256u;
+    if (capped) hipLaunchKernelGGL(k_octree_capped, dim3(grid), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL(k_octree, dim3(grid), dim3(256), lds, s, a);
+    // the levels that can list more than kOctreeNarrowMaxN candidates: their items above the bound
+    int nWide = 0;
+    for (int l = 0; l < nlevels; l++) nWide += !((a.narrowLevels >> l) & 1u);
+    if (nWide) {
+      if (ldsWide > 64 * 1024 && ldsWide > configured[3]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_octree_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsWide);
+        if (e != hipSuccess) return e;
+        configured[3] = ldsWide;
+      }
+      hipLaunchKernelGGL(k_octree_wide, dim3(nFrames, nWide), dim3(256), ldsWide, s, a);
+    }
   }
   return hipSuccess;
 }

@@ -185,6 +185,7 @@ struct OctreeArgs {
   int32_t* levelCount;        // out, [frame][level]
   int kpSlotsPerFrame;
   int maxL;                   // node capacity (>= every level's kpCap and nIni, multiple of 4)
+  uint32_t narrowLevels;      // bit l: level l never lists more than kOctreeNarrowMaxN candidates (octree_narrow_levels); 0 is safe
   uint8_t* work;              // global-memory node lists, one slab of workStride bytes per (frame, level);
   size_t workStride;          //   only read when octree_lds_bytes(maxL) > kOctreeLdsLimit
   // the single-frame form gathers the level's candidates itself (octree_gathers(): k_gather_candidates's work at the head of
@@ -194,7 +195,34 @@ struct OctreeArgs {
 };
 bool octree_gathers(int nFrames, int maxL);  // launch_octree(..., nFrames) will run the form that gathers: fill the g* fields, skip launch_gather_candidates
 constexpr size_t kOctreeLdsLimit = 150 * 1024;  // beyond it the node list lives in global memory (k_octree_global)
-size_t octree_lds_bytes(int maxL);
+// The throughput form keeps the counts of a (frame, level) item in 16 bits when the item lists at most this many candidates
+constexpr int kOctreeNarrowMaxN = 65535;
+// Byte offsets of the node arrays of one (frame, level) item (maxL entries each, child 4 * maxL) for counts of countBytes = 2
+// or 4 bytes; maxL is a multiple of 4, so every array starts on an 8-byte boundary and child on a 16-byte one.  The kernels
+// carve their LDS (or slab) with it and octree_lds_bytes is its end: the two cannot drift apart.
+struct OctreeCarve { uint32_t rect0, rect1, cnt0, cnt1, child, scanA, scanB, order, inS, end; };
+__host__ __device__ inline OctreeCarve octree_carve(int maxL, int countBytes) {
+  const uint32_t M = (uint32_t)maxL, c = (uint32_t)countBytes;
+  OctreeCarve v;
+  v.rect0 = 0;                   // 4 x int16 per node, current list
+  v.rect1 = v.rect0 + 8 * M;     //                     next list
+  v.cnt0 = v.rect1 + 8 * M;      // counts: keys per node, current / next list (adjacent: skey lies over both, k_octree.hip)
+  v.cnt1 = v.cnt0 + c * M;
+  v.child = v.cnt1 + c * M;      // counts x 4
+  v.scanA = v.child + 4 * c * M; // counts
+  v.scanB = v.scanA + c * M;     // counts
+  v.order = v.scanB + c * M;     // uint16
+  v.inS = v.order + 2 * M;       // uint8
+  v.end = v.inS + M;
+  // 32-bit counts: two more bytes per node, unused since the rank array that nothing read went.  octree_lds_bytes(maxL) is
+  // where the forms move from LDS to global memory, and the recorded expectations of the tests pin that seam.
+  if (c == 4) v.end += 2 * M;
+  return v;
+}
+// LDS (or slab) bytes of one item: 53 per node with 32-bit counts (51 in use), 35 with 16-bit counts (narrow), + 64
+size_t octree_lds_bytes(int maxL, bool narrow = false);
+// levels whose candidate slots (the worst case of a level's candidate count) number at most kOctreeNarrowMaxN, as a bit mask
+uint32_t octree_narrow_levels(const LevelGeom* lv, int nlevels);
 // node capacity of a geometry: the largest kpCap / nIni of its levels, at least 4, rounded up to a multiple of 4.
 // 0: a level has 2^24 or more candidate slots (24-bit candidate indices); -1: more than 65532 nodes (16-bit node positions)
 int octree_node_capacity(const LevelGeom* lv, int nlevels);

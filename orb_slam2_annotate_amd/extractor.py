@@ -315,6 +315,15 @@ def debug_octree_limits(minX: int, maxX: int, minY: int, maxY: int, N: int, n_fr
     return dict(zip(("nIni", "kpCap", "maxL", "lds_bytes", "lds_limit", "form"), (int(v) for v in info)))
 
 
+def debug_octree_carve(maxL: int, narrow: bool) -> dict:
+    """Byte offsets of the node arrays the octree kernels carve for one (frame, level) item of node capacity maxL, with 16-bit
+    (narrow: k_octree) or 32-bit counts, the end of the carve, and the LDS bytes a launch asks for (no GPU needed)."""
+    out = np.zeros(11, np.int64)
+    check(_lib.load().orbfe_debug_octree_carve(int(maxL), int(bool(narrow)), ptr(out)))
+    return dict(zip(("rect0", "rect1", "cnt0", "cnt1", "child", "scanA", "scanB", "order", "inS", "end", "lds_bytes"),
+                    (int(v) for v in out)))
+
+
 def debug_octree_device(sets, minX: int, maxX: int, minY: int, maxY: int, N: int, form: int = 0, device: int = 0):
     """DistributeOctTree of one device form (OCTREE_FORMS) on the candidate sets [(xs, ys, responses), ...] of one area, as
     the frames of one launch.  Returns one dict per set: count, and x / y / resp / rank of ALL kpCap slots of the kernel's
