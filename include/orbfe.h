@@ -886,6 +886,75 @@ int orbfe_sim3_triples_from_draws(int n, int n_hypotheses, const int32_t *draws 
  * never reads the result). */
 int orbfe_sim3_max_iterations(int n, double prob, int min_inliers, int max_its);
 
+/* PnPsolver (src/PnPsolver.cc), the RANSAC of Tracking::Relocalization (src/Tracking.cc:1487-1560) between SearchByBoW and
+ * PoseOptimization: EVERY hypothesis of EVERY candidate's solver in ONE kernel launch, one wave per hypothesis, and every
+ * Refine() problem of every candidate in a second one, one workgroup per problem.  A hypothesis is compute_pose (:544-598,
+ * EPnP) on four correspondences followed by CheckInliers (:323-354) over all correspondences of its candidate.  Refine()
+ * (:275-320) is compute_pose on the correspondences of a best inlier set, then CheckInliers.  It is a pure function of that
+ * set, and the set changes only where a hypothesis has n_inliers >= minInliers and more inliers than every earlier such
+ * hypothesis: those hypotheses are the Refine records of a solver.  The order-dependent rest of iterate() (:178-271) is a
+ * scan over the two result sets that the caller replays on the host (C++ orbfe_cpp::PnPsolver, Python PnPsolver).
+ * Candidate k owns correspondences [point_off[k], point_off[k+1]) of p3d (mvP3Dw), p2d (mvP2D) and max_err2 (mvMaxError =
+ * sigma2 * th2, :163), the camera cam[k] = fu fv uc vc, and hypotheses [hyp_off[k], hyp_off[k+1]); sets[4 h ..] are the four
+ * correspondences of hypothesis h as indices LOCAL to its candidate (what :204-214 draws).
+ * Arithmetic is binary64 on inputs widened from float, in a fixed order, so equal inputs give equal bytes; CheckInliers has
+ * the reference's own float / double mix and strict <.  Two DEVIATIONS from the reference, whose decompositions are
+ * OpenCV's and so depend on the OpenCV build:
+ *   - the decompositions are Jacobi iterations (3 x 3 SVDs, the least squares of find_betas_approx_*, the eigenvectors of
+ *     the 12 x 12 M^T M: fixed pair order, at most 30 sweeps, a rotation skipped when |a_pq| <= DBL_EPSILON sqrt(|a_pp a_qq|));
+ *     the rows of UCt in choose_control_points are signed so that their largest component is positive.  Results agree with
+ *     cv::SVD to rounding and are NOT bit-identical to it;
+ *   - for FOUR correspondences M is 8 x 12 and EPnP takes four vectors of a null space of dimension >= 4, inside which an
+ *     eigen-solver's basis is rounding noise.  The basis is canonical here: Householder QR of M^T, reflector k mapping its
+ *     column to -sign(alpha) |x| e_1 with sign(0) = +1, ut rows 8 .. 11 = Q e_8 .. Q e_11.  It spans the same subspace as the
+ *     reference's four vectors and is a continuous function of M wherever M has rank 8.
+ * Outputs per hypothesis or record h: n_inliers[h]; status[h] = ORBFE_PNP_OK, or ORBFE_PNP_NONFINITE when any entry of R or
+ * t is not finite (n_inliers 0 and all mask words 0 then); pose[12 h ..] = R row-major, then t (binary64 results rounded
+ * once: what mBestTcw / mRefinedTcw hold); its ceil(n_k / 32) mask words at
+ * mask_words[word_off[k] + (h - hyp_off[k]) * ceil(n_k / 32)], correspondence i at bit i & 31 of word i >> 5.  word_off
+ * [K + 1] is written by the call; mask_words must hold sum_k H_k * ceil(n_k / 32) words.
+ * Returns ORBFE_ERR_INVALID before anything is enqueued, leaving the thread usable, for: NULL arrays, offsets that do not
+ * start at 0, decrease, or do not end at the totals, a set index outside [0, n_k) or repeated within a set, a camera entry
+ * that is not finite, a candidate with n_k < 4 that has hypotheses or records, a record mask with fewer than 4 bits or with
+ * bits at or beyond n_k, n_candidates outside [0, 4096].  A candidate without hypotheses is legal; a call without any returns
+ * ORBFE_OK with word_off written and no launch.  Runs on the calling thread's matcher stream and is complete on return. */
+enum { ORBFE_PNP_OK = 0, ORBFE_PNP_NONFINITE = 1 };
+
+int orbfe_pnp_ransac_multi(int device, int n_candidates, int n_points, int n_hypotheses, const int32_t *point_off /*[K+1]*/,
+                           const float *p3d /*[N*3]*/, const float *p2d /*[N*2]*/, const float *max_err2 /*[N]*/,
+                           const float *cam /*[K*4]*/, const int32_t *hyp_off /*[K+1]*/, const int32_t *sets /*[H*4]*/,
+                           int32_t *n_inliers /*[H]*/, uint8_t *status /*[H]*/, float *pose /*[H*12]*/,
+                           int32_t *word_off /*[K+1]*/, uint32_t *mask_words);
+/* One candidate; equal to the multi form with n_candidates = 1.  mask_words [H * ceil(n / 32)]. */
+int orbfe_pnp_ransac(int device, int n_points, const float *p3d, const float *p2d, const float *max_err2, const float *cam,
+                     int n_hypotheses, const int32_t *sets, int32_t *n_inliers, uint8_t *status, float *pose,
+                     uint32_t *mask_words);
+/* The Refine() problems: candidate k owns records [rec_off[k], rec_off[k+1]); rec_masks holds ceil(n_k / 32) words per
+ * record, candidate after candidate (the layout mask_words has): the correspondences EPnP runs on, in index order.  Outputs
+ * as above, per record. */
+int orbfe_pnp_refine_multi(int device, int n_candidates, int n_points, int n_records, const int32_t *point_off /*[K+1]*/,
+                           const float *p3d, const float *p2d, const float *max_err2, const float *cam,
+                           const int32_t *rec_off /*[K+1]*/, const uint32_t *rec_masks, int32_t *n_inliers /*[R]*/,
+                           uint8_t *status /*[R]*/, float *pose /*[R*12]*/, int32_t *word_off /*[K+1]*/, uint32_t *mask_words);
+/* Both launches and the record scan between them: the hypotheses as orbfe_pnp_ransac_multi, then for candidate k with
+ * min_inliers[k] (mRansacMinInliers after SetRansacParameters, >= 4) the records rec_hyp[rec_off[k] .. rec_off[k+1]) = the
+ * hypotheses (indices into the call's H) whose n_inliers is >= min_inliers[k] and above every earlier such count, and the
+ * results of Refine() on their masks.  The rec_* arrays must hold what H records need (rec_mask_words as many words as
+ * mask_words). */
+int orbfe_pnp_solve_multi(int device, int n_candidates, int n_points, int n_hypotheses, const int32_t *point_off,
+                          const float *p3d, const float *p2d, const float *max_err2, const float *cam, const int32_t *hyp_off,
+                          const int32_t *sets, const int32_t *min_inliers /*[K]*/, int32_t *n_inliers, uint8_t *status,
+                          float *pose, int32_t *word_off, uint32_t *mask_words, int32_t *rec_off /*[K+1]*/,
+                          int32_t *rec_hyp, int32_t *rec_n_inliers, uint8_t *rec_status, float *rec_pose,
+                          int32_t *rec_word_off /*[K+1]*/, uint32_t *rec_mask_words);
+/* The selection without replacement of PnPsolver::iterate (:201-214), no device involved: draws[4 h + i] is the value
+ * RandomInt(0, vAvailableIndices.size() - 1) returned for pick i of hypothesis h, in [0, n - 1 - i] -- an index INTO the list
+ * of still available correspondences, which starts as 0 .. n-1 for every hypothesis and loses the entry taken by
+ * swap-with-back and pop -> sets[4 h + i] the correspondence taken.  A caller who feeds the reference's
+ * DUtils::Random::RandomInt stream gets the reference's sets; the library does not restate rand().  n < 4 with hypotheses,
+ * NULL arrays or a draw outside its range return ORBFE_ERR_INVALID. */
+int orbfe_pnp_sets_from_draws(int n, int n_hypotheses, const int32_t *draws /*[H*4]*/, int32_t *sets /*[H*4]*/);
+
 /* -------------------------------------------------------------------------- */
 /* Initializer::FindHomography / FindFundamental (src/Initializer.cc:141-255)  */
 /* -------------------------------------------------------------------------- */

@@ -21,6 +21,7 @@
 
 #include "orbfe.h"
 #include "orbfe_initializer_replay.hpp"
+#include "orbfe_pnp_replay.hpp"
 #include "orbfe_sim3_replay.hpp"
 
 namespace orbfe_cpp {
@@ -1232,6 +1233,158 @@ class Sim3Solver {
     if (!hasBest_) throw std::logic_error("Sim3Solver: no hypothesis has been taken yet");
     return best_;
   }
+};
+
+// PnPsolver (src/PnPsolver.cc) without the map graph: the caller walks vpMapPointMatches as the reference's constructor does
+// (:79-101) and hands in, for the n correspondences it keeps, mvP3Dw (3 floats each), mvP2D (mvKeysUn[i].pt, 2 floats each),
+// mvSigma2 (mvLevelSigma2 of the key point's octave), mvKeyPointIndices, fx fy cx cy and
+// nKeyPoints = vpMapPointMatches.size().  The constructor calls SetRansacParameters() with the reference's defaults (:109).
+// PnPsolver::solve_all runs every hypothesis and every Refine() of ALL solvers in ONE orbfe_pnp_solve_multi call (two
+// launches); the multi-candidate constructor does that on construction.  iterate() then behaves as the reference's
+// (:178-271) over the results (PnPReplay, orbfe_pnp_replay.hpp), so the loop of src/Tracking.cc:1503-1560 stays as it is.
+// sets[k]: 4 * nHypotheses() indices, the 4-sets of solver k's hypotheses in order (orbfe_pnp_sets_from_draws of the
+// reference's RandomInt stream gives the reference's).  iterate() throws std::out_of_range when it needs more.
+class PnPsolver {
+ public:
+  PnPsolver(const std::vector<float>& p3d, const std::vector<float>& p2d, const std::vector<float>& sigma2,
+            const std::vector<int32_t>& keyPointIndices, const float cam[4], int nKeyPoints)
+      : p3d_(p3d), p2d_(p2d), sigma2_(sigma2), kp_(keyPointIndices) {
+    const size_t n = sigma2.size();
+    if (p3d.size() != 3 * n || p2d.size() != 2 * n || keyPointIndices.size() != n)
+      throw std::invalid_argument("PnPsolver: one entry per correspondence in every array");
+    for (int32_t i : keyPointIndices)
+      if (i < 0 || i >= nKeyPoints) throw std::invalid_argument("PnPsolver: keyPointIndices outside [0, nKeyPoints)");
+    std::memcpy(cam_, cam, sizeof cam_);
+    st_.N = (int)n; st_.nKeyPoints = nKeyPoints;
+    SetRansacParameters();
+  }
+  // :127-164; what an earlier solve_all left is dropped
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4,
+                           float epsilon = 0.4f, float th2 = 5.991f) {
+    if (minSet != 4) throw std::invalid_argument("PnPsolver: the minimal set is 4");
+    st_.SetRansacParameters(probability, minInliers, maxIterations, minSet, epsilon);
+    st_.mnIterations = 0;
+    maxErr_.resize(sigma2_.size());
+    for (size_t i = 0; i < sigma2_.size(); i++) maxErr_[i] = sigma2_[i] * th2;  // :163
+    solved_ = false;
+  }
+  int N() const { return st_.N; }
+  int minInliers() const { return st_.mRansacMinInliers; }
+  int maxIterations() const { return st_.mRansacMaxIts; }
+  int iterations() const { return st_.mnIterations; }
+  // true: iterate() returns at :186 and the solver takes no part in solve_all
+  bool tooFew() const { return st_.N < st_.mRansacMinInliers; }
+
+  static void solve_all(const std::vector<PnPsolver*>& solvers, const std::vector<std::vector<int32_t>>& sets, int device = 0) {
+    const int K = (int)solvers.size();
+    if ((int)sets.size() != K) throw std::invalid_argument("PnPsolver::solve_all: one array of sets per solver");
+    std::vector<int32_t> pointOff(1, 0), hypOff(1, 0), all, minInl, live;
+    std::vector<float> p3, p2, me, cam;
+    size_t W = 0;
+    for (int k = 0; k < K; k++) {
+      PnPsolver& s = *solvers[k];
+      if (sets[k].size() % 4) throw std::invalid_argument("PnPsolver::solve_all: four indices per hypothesis");
+      s.nHyp_ = 0; s.nRec_ = 0; s.solved_ = true;
+      if (s.tooFew()) continue;
+      live.push_back(k);
+      const int H = (int)(sets[k].size() / 4);
+      pointOff.push_back(pointOff.back() + s.st_.N);
+      hypOff.push_back(hypOff.back() + H);
+      p3.insert(p3.end(), s.p3d_.begin(), s.p3d_.end()); p2.insert(p2.end(), s.p2d_.begin(), s.p2d_.end());
+      me.insert(me.end(), s.maxErr_.begin(), s.maxErr_.end());
+      cam.insert(cam.end(), s.cam_, s.cam_ + 4);
+      minInl.push_back(s.st_.mRansacMinInliers);
+      all.insert(all.end(), sets[k].begin(), sets[k].end());
+      W += (size_t)H * (size_t)((s.st_.N + 31) / 32);
+    }
+    const int L = (int)live.size(), H = hypOff.back();
+    std::vector<int32_t> nInl((size_t)H + 1), wordOff((size_t)L + 1, 0), recOff((size_t)L + 1, 0), recHyp((size_t)H + 1),
+        recInl((size_t)H + 1), recWordOff((size_t)L + 1, 0);
+    std::vector<uint8_t> status((size_t)H + 1), recStatus((size_t)H + 1);
+    std::vector<float> pose((size_t)H * 12 + 1), recPose((size_t)H * 12 + 1);
+    std::vector<uint32_t> words(W + 1), recWords(W + 1);
+    p3.push_back(0.0f); p2.push_back(0.0f); me.push_back(0.0f); cam.push_back(0.0f); all.push_back(0); minInl.push_back(4);
+    check(orbfe_pnp_solve_multi(device, L, pointOff.back(), H, pointOff.data(), p3.data(), p2.data(), me.data(), cam.data(),
+                                hypOff.data(), all.data(), minInl.data(), nInl.data(), status.data(), pose.data(), wordOff.data(),
+                                words.data(), recOff.data(), recHyp.data(), recInl.data(), recStatus.data(), recPose.data(),
+                                recWordOff.data(), recWords.data()),
+          "PnPsolver::solve_all");
+    for (int j = 0; j < L; j++) {
+      PnPsolver& s = *solvers[(size_t)live[j]];
+      const size_t h0 = (size_t)hypOff[j], h1 = (size_t)hypOff[j + 1], r0 = (size_t)recOff[j], r1 = (size_t)recOff[j + 1];
+      s.nHyp_ = (int)(h1 - h0); s.nRec_ = (int)(r1 - r0);
+      s.nInliers_.assign(nInl.begin() + h0, nInl.begin() + h1);
+      s.pose_.assign(pose.begin() + 12 * h0, pose.begin() + 12 * h1);
+      s.words_.assign(words.begin() + wordOff[j], words.begin() + wordOff[j + 1]);
+      s.recHyp_.assign(recHyp.begin() + r0, recHyp.begin() + r1);
+      for (int32_t& h : s.recHyp_) h -= (int32_t)h0;  // local to the solver
+      s.recInliers_.assign(recInl.begin() + r0, recInl.begin() + r1);
+      s.recPose_.assign(recPose.begin() + 12 * r0, recPose.begin() + 12 * r1);
+      s.recWords_.assign(recWords.begin() + recWordOff[j], recWords.begin() + recWordOff[j + 1]);
+      s.nInliers_.push_back(0); s.words_.push_back(0); s.recHyp_.push_back(0); s.recInliers_.push_back(0); s.recWords_.push_back(0);
+    }
+  }
+  // the multi-candidate form: K solvers built from flattened arrays (candidate k owns correspondences
+  // [pointOff[k], pointOff[k + 1]), cam[4 k ..], nKeyPoints[k], sets[k]), parameterised alike and solved in one call
+  static std::vector<PnPsolver> make_all(const std::vector<int32_t>& pointOff, const std::vector<float>& p3d,
+                                         const std::vector<float>& p2d, const std::vector<float>& sigma2,
+                                         const std::vector<int32_t>& keyPointIndices, const std::vector<float>& cam,
+                                         const std::vector<int32_t>& nKeyPoints, const std::vector<std::vector<int32_t>>& sets,
+                                         double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4,
+                                         float epsilon = 0.4f, float th2 = 5.991f, int device = 0) {
+    if (pointOff.empty() || pointOff[0] != 0) throw std::invalid_argument("PnPsolver::make_all: pointOff holds K + 1 entries from 0");
+    const size_t K = pointOff.size() - 1;
+    if (cam.size() != 4 * K || nKeyPoints.size() != K || sets.size() != K || (size_t)pointOff[K] != sigma2.size() ||
+        p3d.size() != 3 * sigma2.size() || p2d.size() != 2 * sigma2.size() || keyPointIndices.size() != sigma2.size())
+      throw std::invalid_argument("PnPsolver::make_all: the arrays disagree in length");
+    std::vector<PnPsolver> out;
+    out.reserve(K);
+    for (size_t k = 0; k < K; k++) {
+      if (pointOff[k + 1] < pointOff[k]) throw std::invalid_argument("PnPsolver::make_all: pointOff must not descend");
+      const size_t a = (size_t)pointOff[k], b = (size_t)pointOff[k + 1];
+      out.emplace_back(std::vector<float>(p3d.begin() + 3 * a, p3d.begin() + 3 * b), std::vector<float>(p2d.begin() + 2 * a, p2d.begin() + 2 * b),
+                       std::vector<float>(sigma2.begin() + a, sigma2.begin() + b),
+                       std::vector<int32_t>(keyPointIndices.begin() + a, keyPointIndices.begin() + b), &cam[4 * k], nKeyPoints[k]);
+      out.back().SetRansacParameters(probability, minInliers, maxIterations, minSet, epsilon, th2);
+    }
+    std::vector<PnPsolver*> ptrs;
+    for (PnPsolver& s : out) ptrs.push_back(&s);
+    solve_all(ptrs, sets, device);
+    return out;
+  }
+
+  // :178-271 -> true and Tcw (row-major 4 x 4) when the reference returns a pose: mRefinedTcw of a Refine() with more than
+  // minInliers inliers (bNoMore false), or mBestTcw at the mnIterations >= mRansacMaxIts tail (bNoMore true)
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, float Tcw[16]) {
+    if (!solved_ && !tooFew()) throw std::logic_error("PnPsolver::iterate: call PnPsolver::solve_all first");
+    const PnPReplay::Step r = st_.iterate(nIterations, nHyp_, nInliers_.data(), words_.data(), nRec_, recHyp_.data(),
+                                          recInliers_.data(), recWords_.data(), kp_.data(), vbInliers);
+    bNoMore = r.bNoMore;
+    nInliers = r.nInliers;
+    const float* v = r.refined >= 0 ? &recPose_[12 * (size_t)r.refined] : (r.best >= 0 ? &pose_[12 * (size_t)r.best] : nullptr);
+    if (!v) return false;
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) Tcw[4 * i + j] = v[3 * i + j];
+      Tcw[4 * i + 3] = v[9 + i];
+    }
+    Tcw[12] = Tcw[13] = Tcw[14] = 0.0f; Tcw[15] = 1.0f;
+    return true;
+  }
+  bool find(std::vector<bool>& vbInliers, int& nInliers, float Tcw[16]) {  // :166-170
+    bool bFlag;
+    return iterate(st_.mRansacMaxIts, bFlag, vbInliers, nInliers, Tcw);
+  }
+
+ private:
+  std::vector<float> p3d_, p2d_, sigma2_, maxErr_;
+  std::vector<int32_t> kp_;
+  float cam_[4];
+  PnPReplay st_;
+  bool solved_ = false;
+  int nHyp_ = 0, nRec_ = 0;
+  std::vector<int32_t> nInliers_ = {0}, recHyp_ = {0}, recInliers_ = {0};
+  std::vector<float> pose_, recPose_;
+  std::vector<uint32_t> words_ = {0}, recWords_ = {0};
 };
 
 // Initializer (src/Initializer.cc).  keys1 = the reference frame's mvKeysUn points (x y

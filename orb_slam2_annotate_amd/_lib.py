@@ -116,6 +116,7 @@ EXPORTS = [
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch", "orbfe_pose_optimization_mappoints",
     "orbfe_triangulate_matches", "orbfe_triangulate_matches_multi",
     "orbfe_sim3_ransac", "orbfe_sim3_ransac_multi", "orbfe_sim3_triples_from_draws", "orbfe_sim3_max_iterations",
+    "orbfe_pnp_ransac", "orbfe_pnp_ransac_multi", "orbfe_pnp_refine_multi", "orbfe_pnp_solve_multi", "orbfe_pnp_sets_from_draws",
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_multi",
     "orbfe_local_bundle_adjustment", "orbfe_bundle_adjustment", "orbfe_local_bundle_adjustment_mappoints",
     "orbfe_optimize_essential_graph", "orbfe_essential_graph_correct_points", "orbfe_essential_graph_correct_mappoints",
@@ -317,6 +318,11 @@ def load():
     L.orbfe_optimize_sim3.argtypes = [ci, ci] + [vp] * 9 + [C.c_float, ci] + [vp] * 6
     L.orbfe_sim3_ransac.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     L.orbfe_sim3_triples_from_draws.argtypes = [ci, ci, vp, vp]
+    L.orbfe_pnp_ransac_multi.argtypes = [ci, ci, ci, ci] + [vp] * 12
+    L.orbfe_pnp_ransac.argtypes = [ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_pnp_refine_multi.argtypes = [ci, ci, ci, ci] + [vp] * 12
+    L.orbfe_pnp_solve_multi.argtypes = [ci, ci, ci, ci] + [vp] * 20
+    L.orbfe_pnp_sets_from_draws.argtypes = [ci, ci, vp, vp]
     L.orbfe_sim3_max_iterations.argtypes = [ci, C.c_double, ci, ci]
     L.orbfe_initializer_ransac_multi.argtypes = [ci, ci, ci, ci] + [vp] * 14
     L.orbfe_initializer_ransac.argtypes = [ci, ci, vp, vp, vp, C.c_float, ci] + [vp] * 7
