@@ -1214,6 +1214,9 @@ int orbfe_essential_graph_correct_mappoints(orbfe_mappoints *table, int n_vertic
 /* GetWorldPos of slot[0 .. n_slots) as the table holds it: what orbfe_essential_graph_correct_mappoints (or the table form of
  * the local bundle adjustment) left there, for the caller's SetWorldPos. */
 int orbfe_mappoints_positions(orbfe_mappoints *table, int n_slots, const int32_t *slot, float *xw_out /*[n_slots,3]*/);
+/* GetDescriptor of slot[0 .. n_slots) as the table holds it: what orbfe_mappoints_update or
+ * orbfe_obsgraph_distinctive_descriptors_mappoints wrote (a slot that was never written holds zeros). */
+int orbfe_mappoints_descriptors(orbfe_mappoints *table, int n_slots, const int32_t *slot, uint8_t *desc_out /*[n_slots,32]*/);
 /* The linear solver of orbfe_optimize_essential_graph on its own (diagnostic and test surface; the optimiser uses the very
  * same kernels): A x = rhs for a symmetric positive definite A of 7 x 7 blocks given by its block lower triangle in
  * block-CSC -- column c holds blocks [colptr[c], colptr[c + 1]), the first of them the diagonal block (its lower triangle is
@@ -1546,6 +1549,56 @@ int orbfe_obsgraph_keyframe_points_union(orbfe_obsgraph *g, int n_queries, const
  * of row kf_slot[i] that are not NULL and not bad and, when min_obs > 0, have nObs >= min_obs (nObs as the point's record
  * holds it: a stereo observation weighs 2).  A kf slot out of range or never set returns ORBFE_ERR_INVALID. */
 int orbfe_obsgraph_tracked_points(orbfe_obsgraph *g, int n_kf, const int32_t *kf_slot, int min_obs, int32_t *count);
+
+/* ---- KeyFrame::mDescriptors in the same handle, and MapPoint::ComputeDistinctiveDescriptors over the rows ----
+ * With the key frames' descriptors next to the rows, the second call LocalMapping makes on every map point a new key
+ * frame touched (src/MapPoint.cc:269-333) needs only a slot list, as update_normal_depth_mappoints does for the first:
+ * no walk over mObservations, no descriptor list, no index read back.  The store is independent of
+ * enable_keyframe_points.  A handle that never enables it allocates nothing and behaves as before; every function below
+ * except enable returns ORBFE_ERR_INVALID on such a handle.
+ *
+ * A key frame's descriptors never change in the reference, so -- unlike everything else in the handle -- the host keeps
+ * NO mirror of the bytes, only the number of rows each kf slot received (0: never set).  The two set calls therefore are
+ * the handle's only mutations that TOUCH THE DEVICE: they copy into the store on the handle's stream, are complete on
+ * return, and without a device return ORBFE_ERR_HIP.  orbfe_obsgraph_clear resets every count to 0 and keeps the device
+ * memory; orbfe_obsgraph_erase_keyframe leaves the descriptors in place (a bad key frame is skipped by its flag). */
+
+/* Gives the handle a store of kf_desc_width descriptors per kf slot: a multiple of 64 in 64 .. 16384 (at least the largest
+ * N), with kf_capacity * kf_desc_width <= 2^26 (2 GiB).  Once per handle: the same width again is a no-op, another width
+ * ORBFE_ERR_INVALID.  Does not touch the device: uint8 [kf_capacity][kf_desc_width][32] is taken at the first set. */
+int orbfe_obsgraph_enable_keyframe_descriptors(orbfe_obsgraph *g, int kf_desc_width);
+/* mDescriptors of the key frame in kf_slot: n <= kf_desc_width rows of 32 bytes from the host.  The kf slot must have
+ * been given to set_keyframes. */
+int orbfe_obsgraph_set_keyframe_descriptors(orbfe_obsgraph *g, int kf_slot, int n, const uint8_t *desc /*[n,32]*/);
+/* The same, device to device, from a resident frame's descriptors (all f's features): the copy runs on the handle's
+ * stream, ordered behind the frame's build.  The frame must be on the handle's device and may be released after the
+ * call. */
+int orbfe_obsgraph_set_keyframe_descriptors_frame(orbfe_obsgraph *g, int kf_slot, const orbfe_frame *f);
+/* Test read-back from the device: the *n_out rows the kf slot holds into desc_out (room for kf_desc_width rows). */
+int orbfe_obsgraph_get_keyframe_descriptors(orbfe_obsgraph *g, int kf_slot, uint8_t *desc_out, int32_t *n_out);
+
+/* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:269-333) for n point slots in one call.  Per listed slot:
+ *   valid[i] = 0 -- and NOTHING else of entry i is written -- for a bad or never-set point (mbBad, :278), an empty row
+ *   (:283), and a row of which no entry remains once the entries of bad key frames are skipped (:292, :296);
+ *   the row is read left to right, in ascending mnId (the handle's order; the reference's is pointer order), the
+ *   entries whose key frame has the bad flag are skipped (:292); N entries remain, descriptor i = the row idx_i of key
+ *   frame kf_i's descriptors;
+ *   d[i][j] = the 256-bit Hamming distance (:303-312); the median of row i is the (size_t)(0.5 * (N - 1))-th smallest of
+ *   its N distances, the self-distance 0 included (:319-321); the winner is the first i under strict < (:323);
+ *   best_kf_slot[i] / best_idx[i] = the winner's entry, desc[32 i ..] = its 32 bytes (:332; desc may be NULL).
+ * Integers only: equal inputs give equal bytes.  Checked on the host, from the mirror, before anything is enqueued
+ * (ORBFE_ERR_INVALID): the store is not enabled; a slot out of range; a listed point that is not bad has an entry whose
+ * key frame received no descriptors, or whose idx is not below that key frame's row count -- whether or not that key
+ * frame is bad.  One wave per point; rows of more than 64 entries run with four descriptors per lane. */
+int orbfe_obsgraph_distinctive_descriptors(orbfe_obsgraph *g, int n, const int32_t *slot, int32_t *best_kf_slot, int32_t *best_idx,
+                                           uint8_t *desc /*[n,32], may be NULL*/, uint8_t *valid);
+/* The same on a resident map-point table: the winner's 32 bytes are written into mp's descriptor of the slot and nothing
+ * else of the slot changes; slots with valid = 0 keep what they hold.  Only the slot list travels.  Both handles must be
+ * on one device, g's point_capacity must not exceed mp's capacity, and no slot may be named twice (ORBFE_ERR_INVALID).
+ * After a call that returns ORBFE_ERR_INVALID the table is unchanged.  Takes g's serialisation, then mp's. */
+int orbfe_obsgraph_distinctive_descriptors_mappoints(orbfe_obsgraph *g, orbfe_mappoints *mp, int n, const int32_t *slot,
+                                                     int32_t *best_kf_slot /*may be NULL*/, int32_t *best_idx /*may be NULL*/,
+                                                     uint8_t *valid);
 
 #ifdef __cplusplus
 }

@@ -782,9 +782,45 @@ class ObservationGraph {
     return count;
   }
 
+  // ---- KeyFrame::mDescriptors per kf slot, and MapPoint::ComputeDistinctiveDescriptors over the rows ----
+  void EnableKeyFrameDescriptors(int kfDescWidth) {
+    check(orbfe_obsgraph_enable_keyframe_descriptors(h_, kfDescWidth), "ObservationGraph::EnableKeyFrameDescriptors");
+    kfDescWidth_ = kfDescWidth;
+  }
+  // mDescriptors of a key frame, 32 bytes per row, from the host; unlike the other mutations this touches the device
+  void SetKeyFrameDescriptors(int kfSlot, const std::vector<uint8_t>& desc) {
+    if (desc.size() % 32) throw std::invalid_argument("ObservationGraph::SetKeyFrameDescriptors: 32 bytes per descriptor");
+    check(orbfe_obsgraph_set_keyframe_descriptors(h_, kfSlot, (int)(desc.size() / 32), desc.data()), "ObservationGraph::SetKeyFrameDescriptors");
+  }
+  // ... or from a resident frame (FrameArrays::resident()), device to device; the frame may be released afterwards
+  void SetKeyFrameDescriptors(int kfSlot, const orbfe_frame* frame) {
+    check(orbfe_obsgraph_set_keyframe_descriptors_frame(h_, kfSlot, frame), "ObservationGraph::SetKeyFrameDescriptors");
+  }
+  std::vector<uint8_t> GetKeyFrameDescriptors(int kfSlot) const {
+    std::vector<uint8_t> out((size_t)std::max(kfDescWidth_, 1) * 32, 0);
+    int32_t n = 0;
+    check(orbfe_obsgraph_get_keyframe_descriptors(h_, kfSlot, out.data(), &n), "ObservationGraph::GetKeyFrameDescriptors");
+    out.resize((size_t)n * 32);
+    return out;
+  }
+  // per slot the winner's (kf slot, idx) and its 32 bytes; -1 / -1 / zeros where valid is 0
+  struct Distinctive {
+    std::vector<int32_t> kfSlot, idx;
+    std::vector<uint8_t> desc, valid;
+  };
+  Distinctive ComputeDistinctiveDescriptors(const std::vector<int32_t>& slot) const {
+    const size_t n = slot.size();
+    Distinctive r;
+    r.kfSlot.assign(n + 1, -1); r.idx.assign(n + 1, -1); r.desc.assign(32 * n + 1, 0); r.valid.assign(n + 1, 0);
+    check(orbfe_obsgraph_distinctive_descriptors(h_, (int)n, slot.data(), r.kfSlot.data(), r.idx.data(), r.desc.data(), r.valid.data()),
+          "ObservationGraph::ComputeDistinctiveDescriptors");
+    r.kfSlot.resize(n); r.idx.resize(n); r.desc.resize(32 * n); r.valid.resize(n);
+    return r;
+  }
+
  private:
   orbfe_obsgraph* h_ = nullptr;
-  int kfCap_ = 0, kfRowWidth_ = 0;
+  int kfCap_ = 0, kfRowWidth_ = 0, kfDescWidth_ = 0;
 };
 
 // The map points Tracking::SearchLocalPoints reads, resident on the device (orbfe_mappoints): slot <-> MapPoint* is the
@@ -869,6 +905,29 @@ class MapPointTable {
                                                        (int)mvScaleFactors.size(), valid.data()), "MapPointTable::UpdateNormalAndDepth");
     valid.resize(slot.size());
     return valid;
+  }
+  // MapPoint::ComputeDistinctiveDescriptors for slot[] on the device: the rows and the key frames' descriptors from `graph`,
+  // the winners' bytes into this table's descriptors; returns valid[] (winners: the winning (kf slot, idx) per slot, -1 where
+  // valid is 0)
+  std::vector<uint8_t> ComputeDistinctiveDescriptors(const ObservationGraph& graph, const std::vector<int32_t>& slot,
+                                                     std::vector<int32_t>* winnerKfSlot = nullptr, std::vector<int32_t>* winnerIdx = nullptr) {
+    std::vector<uint8_t> valid(slot.size() + 1, 0);
+    if (winnerKfSlot) winnerKfSlot->assign(slot.size() + 1, -1);
+    if (winnerIdx) winnerIdx->assign(slot.size() + 1, -1);
+    check(orbfe_obsgraph_distinctive_descriptors_mappoints(graph.handle(), h_, (int)slot.size(), slot.data(),
+                                                           winnerKfSlot ? winnerKfSlot->data() : nullptr, winnerIdx ? winnerIdx->data() : nullptr,
+                                                           valid.data()), "MapPointTable::ComputeDistinctiveDescriptors");
+    valid.resize(slot.size());
+    if (winnerKfSlot) winnerKfSlot->resize(slot.size());
+    if (winnerIdx) winnerIdx->resize(slot.size());
+    return valid;
+  }
+  // GetDescriptor of slot[] as the table holds it (32 bytes each)
+  std::vector<uint8_t> Descriptors(const std::vector<int32_t>& slot) const {
+    std::vector<uint8_t> out(32 * slot.size() + 1);
+    check(orbfe_mappoints_descriptors(h_, (int)slot.size(), slot.data(), out.data()), "MapPointTable::Descriptors");
+    out.resize(32 * slot.size());
+    return out;
   }
 
  private:

@@ -130,6 +130,9 @@ EXPORTS = [
     "orbfe_obsgraph_update_connections", "orbfe_obsgraph_local_keyframes",
     "orbfe_obsgraph_enable_keyframe_points", "orbfe_obsgraph_set_keyframe_points", "orbfe_obsgraph_assign_keyframe_points",
     "orbfe_obsgraph_get_keyframe_points", "orbfe_obsgraph_keyframe_points_union", "orbfe_obsgraph_tracked_points",
+    "orbfe_obsgraph_enable_keyframe_descriptors", "orbfe_obsgraph_set_keyframe_descriptors",
+    "orbfe_obsgraph_set_keyframe_descriptors_frame", "orbfe_obsgraph_get_keyframe_descriptors",
+    "orbfe_obsgraph_distinctive_descriptors", "orbfe_obsgraph_distinctive_descriptors_mappoints", "orbfe_mappoints_descriptors",
 ]
 
 _lib = None
@@ -352,6 +355,13 @@ def load():
     L.orbfe_obsgraph_get_keyframe_points.argtypes = [vp, ci, ci, vp, vp]
     L.orbfe_obsgraph_keyframe_points_union.argtypes = [vp, ci, vp, vp, ci, vp, vp]
     L.orbfe_obsgraph_tracked_points.argtypes = [vp, ci, vp, ci, vp]
+    L.orbfe_obsgraph_enable_keyframe_descriptors.argtypes = [vp, ci]
+    L.orbfe_obsgraph_set_keyframe_descriptors.argtypes = [vp, ci, ci, vp]
+    L.orbfe_obsgraph_set_keyframe_descriptors_frame.argtypes = [vp, ci, vp]
+    L.orbfe_obsgraph_get_keyframe_descriptors.argtypes = [vp, ci, vp, vp]
+    L.orbfe_obsgraph_distinctive_descriptors.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_obsgraph_distinctive_descriptors_mappoints.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    L.orbfe_mappoints_descriptors.argtypes = [vp, ci, vp, vp]
     _lib = L
     return L
 

@@ -112,6 +112,14 @@ __global__ __launch_bounds__(kProjectThreads) void k_mappoints_scatter(const Map
   }
 }
 
+// the descriptors of slot[0 .. n), moved by the whole workgroup as 16-byte pieces: piece p = half (p & 1) of point p / 2
+__global__ __launch_bounds__(kProjectThreads) void k_mappoints_read_descriptors(const MapPointsDevice t, int n, const int32_t* __restrict__ slot,
+                                                                                uint8_t* __restrict__ desc) {
+  const size_t p = (size_t)blockIdx.x * kProjectThreads + threadIdx.x;
+  if (p >= 2 * (size_t)n) return;
+  reinterpret_cast<uint4*>(desc)[p] = reinterpret_cast<const uint4*>(t.desc)[2 * (size_t)slot[p >> 1] + (p & 1)];
+}
+
 }  // namespace
 
 void launch_project_frustum(hipStream_t s, const ProjectArgs& a) {
@@ -124,6 +132,12 @@ void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, co
   if (n <= 0) return;
   hipLaunchKernelGGL(k_mappoints_scatter, dim3((n + kProjectThreads - 1) / kProjectThreads), dim3(kProjectThreads), 0, s, t, n, slot, rec,
                      flags, desc);
+}
+
+void launch_mappoints_read_descriptors(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, uint8_t* desc) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_mappoints_read_descriptors, dim3((unsigned)((2 * (size_t)n + kProjectThreads - 1) / kProjectThreads)),
+                     dim3(kProjectThreads), 0, s, t, n, slot, desc);
 }
 
 }  // namespace orbfe

@@ -131,6 +131,32 @@ extern "C" int orbfe_mappoints_update(orbfe_mappoints* mp, int n, const int32_t*
   return ORBFE_OK;
 }
 
+extern "C" int orbfe_mappoints_descriptors(orbfe_mappoints* mp, int n_slots, const int32_t* slot, uint8_t* desc_out) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "mappoints_descriptors: NULL table");
+  if (const char* e = mappoints_check_slots(mp->capacity, n_slots, slot)) return fail(ORBFE_ERR_INVALID, std::string("mappoints_descriptors: ") + e);
+  if (n_slots > 0 && !desc_out) return fail(ORBFE_ERR_INVALID, "mappoints_descriptors: NULL output");
+  if (n_slots == 0) return ORBFE_OK;
+  const size_t q = (size_t)n_slots;
+  std::lock_guard<std::mutex> lk(mp->m);
+  Arena* ar;
+  int32_t* dslot;
+  uint8_t* dout = nullptr;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dslot, slot, q));
+    dout = carve<uint8_t>(a, 32 * q);
+    return a->sizing ? hipSuccess : grow_mirror(a, (size_t)(dout + 32 * q - a->base.p));
+  };
+  HIPCHK(arena_stage(mp->device, &ar, stage));
+  HIPCHK(mappoints_ready(mp, ar));
+  HIPCHK(flush(ar));
+  launch_mappoints_read_descriptors(ar->stream, mp->d, n_slots, dslot, dout);
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, dout, dout + 32 * q));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  std::memcpy(desc_out, mirror_of(ar, dout), 32 * q);
+  return ORBFE_OK;
+}
+
 namespace orbfe {
 bool pose_ok(const orbfe_camera_pose* p) { return p && p->n_levels >= 1 && p->n_levels <= ORBFE_MAX_LEVELS * 4; }
 int mappoints_device(const orbfe_mappoints* mp) { return mp->device; }

@@ -169,6 +169,8 @@ void launch_project_frustum(hipStream_t s, const ProjectArgs& a);
 // orbfe_mappoints_update: n staged entries (slot, the two records, flags, descriptors or NULL = keep) into their slots
 void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,
                               const uint8_t* flags, const uint8_t* desc);
+// the descriptors of slot[0 .. n) of a table into desc[n][32] (orbfe_mappoints_descriptors)
+void launch_mappoints_read_descriptors(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, uint8_t* desc);
 
 void launch_search_by_bow(hipStream_t s, const BowArgs& a, int nPairs, int maxCnt2);
 void launch_search_by_bow_multi(hipStream_t s, const BowArgs* d_args, const int32_t* d_pairStart, int K, int nPairsTotal, int maxCnt2);

@@ -98,13 +98,18 @@ int orbfe::obs_ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes) 
 
 int orbfe::obs_invalid(const char* fn, const char* what) { return fail(ORBFE_ERR_INVALID, std::string(fn) + ": " + what); }
 
-// what every call that reads the table on the device starts with (the handle locked)
-int orbfe::obs_ready(orbfe_obsgraph* g) {
+int orbfe::obs_stream(orbfe_obsgraph* g) {
   HIPCHK(hipSetDevice(g->device));
   if (!g->ready) {
     HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     g->ready = true;
   }
+  return ORBFE_OK;
+}
+
+// what every call that reads the table on the device starts with (the handle locked)
+int orbfe::obs_ready(orbfe_obsgraph* g) {
+  if (int rc = obs_stream(g)) return rc;
   ObsGraphMirror& h = g->h;
   if (!g->table.p) {
     const size_t oMeta = al((size_t)h.pointCap * h.rowWidth * sizeof(ObsEntry)), oKf = oMeta + al((size_t)h.pointCap * sizeof(ObsPointMeta)),
@@ -199,6 +204,7 @@ extern "C" void orbfe_obsgraph_destroy(orbfe_obsgraph* g) {
     (void)hipStreamSynchronize(g->stream);
     slab_put(&g->table);
     slab_put(&g->kfTable);
+    slab_put(&g->descTable);
     (void)hipStreamDestroy(g->stream);
   }
   delete g;

@@ -1,5 +1,6 @@
-// obsgraph_handle.h -- struct orbfe_obsgraph and what its two host files share (obsgraph.hip: the observation rows;
-// kfpoints.hip: the key-frame rows).  Everything here is called with the handle locked.
+// obsgraph_handle.h -- struct orbfe_obsgraph and what its three host files share (obsgraph.hip: the observation rows;
+// kfpoints.hip: the key-frame rows; obsdesc.hip: the key frames' descriptors).  Everything here is called with the handle
+// locked.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +23,9 @@ struct orbfe_obsgraph {
   // KeyFrame::mvpMapPoints: a slab of its own, empty until the first device call after enable_keyframe_points
   orbfe::Slab kfTable;
   orbfe::KfPointsDevice kd{};
+  // KeyFrame::mDescriptors: a slab of its own, empty until the first set_keyframe_descriptors*; no host copy of the bytes
+  orbfe::Slab descTable;
+  orbfe::KfDescDevice dd{};
   // grow-only workspace + pinned staging in both directions
   orbfe::DevBuf<uint8_t> work;
   orbfe::PinBuf<uint8_t> pin;
@@ -33,6 +37,9 @@ constexpr size_t kObsFlushChunkBytes = (size_t)8 << 20;
 
 inline size_t obs_al(size_t x) { return (x + 255) & ~(size_t)255; }
 int obs_ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes);
+// the handle's device made current and its stream created: the first step of obs_ready, and all a call needs that
+// touches the device but not the table
+int obs_stream(orbfe_obsgraph* g);
 // what every call that reads the table on the device starts with: device, stream, the slab, the marked rows written
 int obs_ready(orbfe_obsgraph* g);
 int obs_invalid(const char* fn, const char* what);

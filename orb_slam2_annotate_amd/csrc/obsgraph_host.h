@@ -13,6 +13,10 @@
 // mirror that never enables it holds nothing more than before.  kfpoints_union_flat() below is the reference's ordered
 // union (src/Tracking.cc:1315-1333) over flat arrays: the sanitizer program's check and the CPU yardstick of
 // tools/kfpoints_latency.py -- never a fallback, the library does not call it.
+//
+// The key frames' descriptors (KeyFrame::mDescriptors) are the one thing the handle holds WITHOUT a host copy: they never
+// change in the reference, so enable_keyframe_descriptors() gives the store a width and the mirror keeps only descN, the
+// number of rows each kf slot received (0: never set).  That is all the checks of the distinctive-descriptor loop need.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -28,6 +32,8 @@ constexpr int kObsMaxPoints = 1 << 24, kObsMaxKeyFrames = 1 << 20;
 constexpr int64_t kObsMaxEntries = (int64_t)1 << 28;  // point_capacity * row_width: a 2 GiB table at the most
 constexpr int kKfRowMinWidth = 64, kKfRowMaxWidth = 16384;  // kf_row_width: a multiple of 64 (one wave never spans two rows)
 constexpr int64_t kKfRowMaxEntries = (int64_t)1 << 28;      // kf_capacity * kf_row_width: a 1 GiB table at the most
+constexpr int kKfDescMinWidth = 64, kKfDescMaxWidth = 16384;  // kf_desc_width: a multiple of 64
+constexpr int64_t kKfDescMaxRows = (int64_t)1 << 26;          // kf_capacity * kf_desc_width: 2 GiB of 32-byte descriptors at the most
 
 // one observation: 8 bytes, what a lane of the kernels reads
 struct ObsEntry {
@@ -73,6 +79,9 @@ struct ObsGraphMirror {
   std::vector<std::vector<int32_t>> kfRows;
   std::vector<uint8_t> kfRowDirty;
   std::vector<int32_t> dirtyKfRows;
+  // KeyFrame::mDescriptors per kf slot: the bytes are on the device alone; kfDescWidth = 0: not enabled
+  int kfDescWidth = 0;
+  std::vector<int32_t> descN;  // rows the kf slot received (0: never set)
 
   void init(int points, int keyframes, int width) {
     pointCap = points; kfCap = keyframes; rowWidth = width;
@@ -94,6 +103,7 @@ struct ObsGraphMirror {
       kfRows.assign((size_t)kfCap, {});
       for (int k = 0; k < kfCap; k++) touch_kf_row(k);
     }
+    if (kfDescWidth) descN.assign((size_t)kfCap, 0);  // the width and the device slab stay
   }
   void touch(int slot) {
     if (!rowDirty[(size_t)slot]) { rowDirty[(size_t)slot] = 1; dirtyRows.push_back(slot); }
@@ -373,6 +383,44 @@ struct ObsGraphMirror {
       if (kfs[(size_t)kf[i]].id < 0) return "kf slot was never set (orbfe_obsgraph_set_keyframes)";
     return nullptr;
   }
+
+  // ---- KeyFrame::mDescriptors and MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:269-333) ----
+
+  const char* enable_keyframe_descriptors(int width) {
+    if (width < kKfDescMinWidth || width > kKfDescMaxWidth || width % 64) return "kf_desc_width must be a multiple of 64 in 64 .. 16384";
+    if ((int64_t)kfCap * width > kKfDescMaxRows) return "kf_capacity * kf_desc_width must not exceed 2^26";
+    if (kfDescWidth) return kfDescWidth == width ? nullptr : "key-frame descriptors are enabled with another width";
+    descN.assign((size_t)kfCap, 0);
+    kfDescWidth = width;
+    return nullptr;
+  }
+
+  // what either set_keyframe_descriptors call checks before it touches the device (have: the source is there)
+  const char* check_set_keyframe_descriptors(int k, int n, bool have) const {
+    if (!kfDescWidth) return "key-frame descriptors are not enabled (orbfe_obsgraph_enable_keyframe_descriptors)";
+    if (k < 0 || k >= kfCap) return "kf slot outside [0, kf_capacity)";
+    if (kfs[(size_t)k].id < 0) return "kf slot was never set (orbfe_obsgraph_set_keyframes)";
+    if (n < 0 || n > kfDescWidth) return "n outside [0, kf_desc_width]";
+    if (n > 0 && !have) return "NULL descriptors";
+    return nullptr;
+  }
+
+  // what the distinctive-descriptor loop needs to know before it may launch: every entry the kernel can gather -- the
+  // entries of a listed point that is not bad, whether or not the entry's key frame is bad -- names a descriptor row
+  // that was set.  A bad point's row is never read on the device, so it is not looked at here either.
+  const char* check_distinctive(int n, const int32_t* slot) const {
+    if (!kfDescWidth) return "key-frame descriptors are not enabled (orbfe_obsgraph_enable_keyframe_descriptors)";
+    if (!slots_ok(n, slot)) return "slot outside [0, point_capacity)";
+    for (int i = 0; i < n; i++) {
+      if (meta[(size_t)slot[i]].bad) continue;
+      for (const ObsEntry& e : rows[(size_t)slot[i]]) {
+        const int32_t have = descN[(size_t)e.kf];
+        if (have == 0) return "an observing key frame's descriptors were never set (orbfe_obsgraph_set_keyframe_descriptors)";
+        if ((int32_t)e.idx >= have) return "an observation's idx is not below its key frame's descriptor count";
+      }
+    }
+    return nullptr;
+  }
 };
 
 // ---- host replays over one query's votes ----
@@ -519,6 +567,31 @@ inline int kfpoints_union_flat(const int32_t* rows, const int32_t* len, int widt
     }
   }
   return n;
+}
+
+// MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:288-328) of one row on flat arrays: entries [count] in the
+// table's order, kfBad [kf], desc [kf][width][32].  Returns the row position of the winner, -1 when no entry remains.  The
+// sanitizer program's check and a CPU yardstick -- never a fallback, the library does not call it.
+inline int obsdesc_distinctive_flat(const ObsEntry* entries, int count, const ObsKeyFrame* kf, const uint8_t* desc, int width) {
+  std::vector<int> live;
+  for (int e = 0; e < count; e++)
+    if (!kf[entries[e].kf].bad) live.push_back(e);  // !pKF->isBad() (:292)
+  const int N = (int)live.size();
+  if (N == 0) return -1;  // vDescriptors.empty(): return (:296)
+  auto row = [&](int e) { return desc + ((size_t)entries[e].kf * (size_t)width + entries[e].idx) * 32; };
+  int bestMedian = 1 << 30, best = -1;
+  std::vector<int> d((size_t)N);
+  for (int i = 0; i < N; i++) {
+    for (int j = 0; j < N; j++) {
+      int s = 0;
+      for (int b = 0; b < 32; b++) s += __builtin_popcount((unsigned)(row(live[(size_t)i])[b] ^ row(live[(size_t)j])[b]));
+      d[(size_t)j] = s;
+    }
+    std::sort(d.begin(), d.end());
+    const int median = d[(size_t)(0.5 * (N - 1))];  // (:321)
+    if (median < bestMedian) { bestMedian = median; best = live[(size_t)i]; }  // strict <: the first row wins (:323)
+  }
+  return best;
 }
 
 // KeyFrame::TrackedMapPoints (src/KeyFrame.cc:264-289) of one row

@@ -74,4 +74,20 @@ void launch_kf_union(hipStream_t s, const ObsGraphDevice& g, const KfPointsDevic
 void launch_kf_tracked(hipStream_t s, const ObsGraphDevice& g, const KfPointsDevice& t, int n, const int32_t* kf, int minObs,
                        int32_t* count);
 
+// ---- k_obsdesc.hip: KeyFrame::mDescriptors per kf slot and MapPoint::ComputeDistinctiveDescriptors over the rows ----
+
+struct KfDescDevice {
+  const uint8_t* desc;  // [kf_capacity][width][32]; rows at and past a key frame's count are never read.  NULL: nothing set yet
+  int width;
+};
+
+// a row whose entry count is above this runs in the form whose lanes hold four descriptors each
+constexpr int kObsDescOneChunk = 64;
+
+// MapPoint::ComputeDistinctiveDescriptors for slot[n], a wave per point.  valid[n]; where valid: bestKf / bestIdx [n] and
+// the winner's 32 bytes -- into outDesc[n][32] (table == NULL) or into the table's descriptor of the slot.  maxCount: the
+// largest entry count among the listed rows (from the mirror); above kObsDescOneChunk a second launch takes the long rows.
+void launch_obs_distinctive(hipStream_t s, const ObsGraphDevice& g, const KfDescDevice& kd, int n, const int32_t* slot, int maxCount,
+                            int32_t* bestKf, int32_t* bestIdx, uint8_t* outDesc, uint8_t* valid, const MapPointsDevice* table);
+
 }  // namespace orbfe

@@ -169,3 +169,16 @@ class MapPoints:
         out = np.zeros((max(len(sl), 1), 3), np.float32)
         check(self._L.orbfe_mappoints_positions(self._h, len(sl), ptr(sl), ptr(out)))
         return out[:len(sl)]
+
+    def descriptors(self, slot):
+        """orbfe_mappoints_descriptors: GetDescriptor as the table holds it for slot[] -> [n, 32] uint8."""
+        sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        out = np.zeros((max(len(sl), 1), 32), np.uint8)
+        check(self._L.orbfe_mappoints_descriptors(self._h, len(sl), ptr(sl), ptr(out)))
+        return out[:len(sl)]
+
+    def compute_distinctive_descriptors(self, graph, slot):
+        """MapPoint::ComputeDistinctiveDescriptors for slot[] on the device (orbfe_obsgraph_distinctive_descriptors_mappoints):
+        `graph` is the ObservationGraph that holds the rows and the key frames' descriptors; the winners' bytes land in this
+        table's descriptors -> (best_kf_slot, best_idx, valid); slots with valid = 0 keep what they hold."""
+        return graph.distinctive_descriptors(slot, mp=self)

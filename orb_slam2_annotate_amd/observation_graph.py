@@ -291,6 +291,44 @@ class ObservationGraph:
         check(self._L.orbfe_obsgraph_tracked_points(self._h, len(k), ptr(k), int(min_obs), ptr(cnt)))
         return cnt[:len(k)]
 
+    # ---- KeyFrame::mDescriptors and MapPoint::ComputeDistinctiveDescriptors ----
+
+    def enable_keyframe_descriptors(self, kf_desc_width: int):
+        """A store of `kf_desc_width` descriptors per kf slot (a multiple of 64 in 64 .. 16384); once per graph."""
+        check(self._L.orbfe_obsgraph_enable_keyframe_descriptors(self._h, int(kf_desc_width)))
+        self.kf_desc_width = int(kf_desc_width)
+
+    def set_keyframe_descriptors(self, kf_slot: int, desc):
+        """mDescriptors of a key frame: an [n, 32] uint8 array from the host, or a ResidentFrame, whose descriptors are
+        copied on the device (the frame may be closed afterwards).  Unlike the other mutations this touches the device."""
+        if hasattr(desc, "_h") and hasattr(desc, "c"):  # a resident frame
+            check(self._L.orbfe_obsgraph_set_keyframe_descriptors_frame(self._h, int(kf_slot), desc._h))
+            return
+        d = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+        check(self._L.orbfe_obsgraph_set_keyframe_descriptors(self._h, int(kf_slot), len(d), ptr(d)))
+
+    def get_keyframe_descriptors(self, kf_slot: int):
+        """-> the [n, 32] descriptors the kf slot holds, read back from the device."""
+        out = np.zeros((max(getattr(self, "kf_desc_width", 0), 1), 32), np.uint8)
+        n = C.c_int32(0)
+        check(self._L.orbfe_obsgraph_get_keyframe_descriptors(self._h, int(kf_slot), ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def distinctive_descriptors(self, slot, mp=None):
+        """MapPoint::ComputeDistinctiveDescriptors for slot[] over the rows and the stored key-frame descriptors.  Without mp:
+        -> (best_kf_slot, best_idx, desc [n, 32], valid); entries with valid = 0 hold -1 / -1 / zeros.  mp (a MapPoints table):
+        the winners' bytes are written into the table's descriptors on the device -> (best_kf_slot, best_idx, valid)."""
+        s = _i32(slot)
+        n = len(s)
+        kf, idx = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32)
+        valid = np.zeros(max(n, 1), np.uint8)
+        if mp is not None:
+            check(self._L.orbfe_obsgraph_distinctive_descriptors_mappoints(self._h, mp._h, n, ptr(s), ptr(kf), ptr(idx), ptr(valid)))
+            return kf[:n], idx[:n], valid[:n]
+        desc = np.zeros((max(n, 1), 32), np.uint8)
+        check(self._L.orbfe_obsgraph_distinctive_descriptors(self._h, n, ptr(s), ptr(kf), ptr(idx), ptr(desc), ptr(valid)))
+        return kf[:n], idx[:n], desc[:n], valid[:n]
+
     def update_normal_depth(self, slot, scale_factors, pos=None, mp=None):
         """MapPoint::UpdateNormalAndDepth for slot[].  pos ([n, 3]): the array form -> (normal [n, 3], min_dist, max_dist,
         valid); rows with valid = 0 hold zeros.  mp (a MapPoints table): positions are read from and the results written into
