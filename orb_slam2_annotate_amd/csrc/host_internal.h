@@ -12,7 +12,7 @@
 #include "kernels.h"
 
 namespace orbfe {
-// extractor.hip: sets the text orbfe_last_error() returns on the calling thread; returns `code`
+// runtime.hip: sets the text orbfe_last_error() returns on the calling thread; returns `code`
 int fail(int code, const std::string& msg);
 // the one status rule: out of memory answers ORBFE_ERR_NOMEM, every other HIP error ORBFE_ERR_HIP
 inline int hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? ORBFE_ERR_NOMEM : ORBFE_ERR_HIP; }
@@ -119,7 +119,7 @@ struct MapPointsLock {
 }  // namespace orbfe
 
 extern "C" {
-// ---- extractor.hip (struct orbfe_extractor lives there) ----
+// ---- extractor_handle.hip (struct orbfe_extractor: extractor_handle.h, for the extractor's own files only) ----
 // a consumer of the last extract call's outputs on the handle's own stream: begin orders stream 0 behind every sub-batch
 // and returns it, end marks the consumer's last kernel for the next extract call to wait for
 int orbfe_extractor_consumer_begin_(orbfe_extractor* e, hipStream_t* s);
@@ -133,10 +133,10 @@ int orbfe_extractor_output_device_(orbfe_extractor* e, int frame, const orbfe_ke
                                    int* n, int* device);
 // a frame build that reads the output block was enqueued on `s`: the next call that writes the block waits for it
 int orbfe_extractor_reader_end_(orbfe_extractor* e, hipStream_t s);
-// pyramid views + scale tables of the last extract call
+// stereo_batch.hip: pyramid views + scale tables of the last extract call
 int orbfe_stereo_views_(orbfe_extractor* e, int frame, orbfe::PyramidViews* pv, float* scale, float* invScale,
                         int* nlevels, int* device, const float** d_scaleTab);
-// test hooks: hold back / query a stream
+// extractor_debug.hip: test hooks that hold back / query a stream
 int orbfe_debug_stall_launch_(hipStream_t s, int usec);
 int orbfe_debug_stream_idle_(hipStream_t s);
 // ---- k_ingest.hip (struct orbfe_rectifier lives there) ----

@@ -701,9 +701,9 @@ def lane_stages():
 # ---- the table --------------------------------------------------------------------------------------------------------
 CASES = {
     "frame_build_vs_next_extract": Case(frame_build_vs_next_extract, pins=[
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(s, e->evReaderDone)",
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(sP, e->evReaderDone)",
-        "extractor.hip:reader_settle:hipEventSynchronize(e->evReaderDone)",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(s, e->evReaderDone)",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(sP, e->evReaderDone)",
+        "extractor_handle.hip:reader_settle:hipEventSynchronize(e->evReaderDone)",
     ], bug="resident frame built from the output block vs. the next extract (write after read)"),
     "set_featvec_cross_thread": Case(set_featvec_cross_thread, pins=[],
                                      bug="orbfe_frame_set_featvec vs. the frame's own build copy (frame_use)"),
@@ -719,21 +719,21 @@ CASES = {
         "arena.hip:staging_reserve:hipEventSynchronize(t_staging.pending)",
     ]),
     "consumer_vs_extract_subbatch": Case(consumer_vs_extract_subbatch, pins=[
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(s, e->evConsumerDone)",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(s, e->evConsumerDone)",
     ]),
     "consumer_vs_extract_lanes": Case(consumer_vs_extract_lanes, pins=[
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(sP, e->evConsumerDone)",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(sP, e->evConsumerDone)",
     ]),
     "tail_lane_vs_next_call": Case(tail_lane_vs_next_call, pins=[
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(sP, e->evTail[i])",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(sP, e->evTail[i])",
     ]),
     "subbatch_join_vs_consumer": Case(subbatch_join_vs_consumer, pins=[
-        "extractor.hip:orbfe_extractor_consumer_begin_:hipStreamWaitEvent(e->stream, e->evChunkDone[i])",
+        "extractor_handle.hip:orbfe_extractor_consumer_begin_:hipStreamWaitEvent(e->stream, e->evChunkDone[i])",
     ]),
     "pipelined_slots": Case(pipelined_slots, pins=[
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(s, waitFor[k])",
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(sP, waitFor[k])",
-        "extractor.hip:run_pipeline:hipStreamWaitEvent(sT, waitFor[k])",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(s, waitFor[k])",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(sP, waitFor[k])",
+        "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(sT, waitFor[k])",
         "extractor.hip:orbfe_extract_batch_pipelined:hipStreamWaitEvent(e->sH2D, e->evComp[slot])",
         "extractor.hip:orbfe_extract_batch_pipelined:hipStreamWaitEvent(e->sD2H, e->evComp[slot])",
     ]),
@@ -742,15 +742,15 @@ CASES = {
         "vocabulary.hip:bow_match_consecutive:hipStreamWaitEvent(streams[i - 1], v->evBoundary[i])",
     ]),
     "lane_stages": Case(lane_stages, pins=[
-        "extractor.hip:run_chunk:hipStreamWaitEvent(sV, e->evPyr[sub])",
-        "extractor.hip:run_chunk:hipStreamWaitEvent(sT, e->evFast[sub])",
-        "extractor.hip:run_chunk:hipStreamWaitEvent(sT, e->evBlur[sub])",
+        "extractor_pipeline.hip:run_chunk:hipStreamWaitEvent(sV, e->evPyr[sub])",
+        "extractor_pipeline.hip:run_chunk:hipStreamWaitEvent(sT, e->evFast[sub])",
+        "extractor_pipeline.hip:run_chunk:hipStreamWaitEvent(sT, e->evBlur[sub])",
     ]),
 }
 
 # wait sites no case pins, each with the reason
 NOT_CASED = {
-    "extractor.hip:resolve_slot:hipEventSynchronize(e->evB[slot][sub][st])":
+    "extractor_handle.hip:resolve_slot:hipEventSynchronize(e->evB[slot][sub][st])":
         "stage-timer readout after the call's own synchronisation: orders no data",
     "extractor.hip:orbfe_extract_batch_pipelined:hipStreamWaitEvent(e->stream, e->evChunkDone[i])":
         "the call drains stream 0 and extra[] first and all sub-batches of a chunk wait on the same copy events, so no "

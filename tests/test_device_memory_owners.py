@@ -14,8 +14,8 @@ ALLOWED = {
     "host_internal.h:DevBuf": "DevBuf / PinBuf: the owning buffer every other site holds",
     "arena.hip:slab_get": "the slab pool hands out a kept slab or allocates one of the next size class",
     "arena.hip:slab_put": "the slab pool frees a slab it has no room to keep",
-    "extractor.hip:orbfe_host_alloc": "public raw allocator of pinned host memory (include/orbfe.h)",
-    "extractor.hip:orbfe_host_free": "frees what orbfe_host_alloc returned",
+    "runtime.hip:orbfe_host_alloc": "public raw allocator of pinned host memory (include/orbfe.h)",
+    "runtime.hip:orbfe_host_free": "frees what orbfe_host_alloc returned",
 }
 _STRUCT = re.compile(r"^(?:struct|class)\s+(\w+)[^;{}()]*\{", re.M)
 _CLOSE = re.compile(r"^\}", re.M)
@@ -46,8 +46,8 @@ def strays(root=CSRC):
 
 def test_the_scan_finds_the_owners():
     where = {w for w, _ in raw_calls()}
-    assert {"arena.hip:slab_get", "arena.hip:slab_put", "extractor.hip:orbfe_host_alloc",
-            "extractor.hip:orbfe_host_free"} <= where, where
+    assert {"arena.hip:slab_get", "arena.hip:slab_put", "runtime.hip:orbfe_host_alloc",
+            "runtime.hip:orbfe_host_free"} <= where, where
     assert {c for w, c in raw_calls() if w == "host_internal.h:DevBuf"} == {"hipMalloc", "hipFree", "hipHostMalloc",
                                                                             "hipHostFree"}
 

@@ -1,11 +1,14 @@
-"""CPU drift guard of csrc/host_internal.h: what one host source of csrc/ defines for another is declared there, once, and
-both sides include it -- so a signature that drifts does not compile.  A prototype re-typed in a source file would bring
-the silent mismatch back (the functions are extern "C"), and an entry nobody uses would only look like an interface."""
+"""CPU drift guard of csrc/host_internal.h and csrc/extractor_handle.h: what one host source of csrc/ defines for another
+is declared there, once, and both sides include it -- so a signature that drifts does not compile.  A prototype re-typed in
+a source file would bring the silent mismatch back (the back doors are extern "C"; a re-declared orbfe:: helper with other
+parameters is an overload nothing defines), and an entry nobody uses would only look like an interface."""
 import re
 from pathlib import Path
 
+import pytest
+
 CSRC = Path(__file__).resolve().parent.parent / "orb_slam2_annotate_amd" / "csrc"
-HEADER = "host_internal.h"
+HEADERS = ("host_internal.h", "extractor_handle.h")  # the back doors of every host file; the extractor's own files
 BACK_DOOR = re.compile(r"orbfe_[a-z0-9_]+_$")  # the internal cross-file functions end in '_'
 _NOT_A_TYPE = {"return", "else", "delete", "new", "throw", "goto", "case", "typedef", "using", "co_return"}
 # "<type words> name(<arguments>)": arguments may nest one level of parentheses (function pointers, casts in defaults)
@@ -53,38 +56,53 @@ def stray_prototypes(root=CSRC):
     return sorted(set(out))
 
 
-def header_names(root=CSRC):
-    return sorted(set(_matches(_DECL, _code((root / HEADER).read_text()))))
+def header_names(header, root=CSRC):
+    return sorted(set(_matches(_DECL, _code((root / header).read_text()))))
 
 
 def test_the_scan_reads_the_header_and_the_sources():
-    names = header_names()
+    names = header_names("host_internal.h")
     assert {"fail", "orbfe_extractor_consumer_begin_", "orbfe_remap_launch_", "orbfe_stereo_views_"} <= set(names), names
+    names = header_names("extractor_handle.h")
+    assert {"run_pipeline", "begin_call", "sync_all", "fetch_outputs"} <= set(names), names
+    assert not {"stage_on", "stage_open", "stage_close", "StageTimer"} & set(names), names  # defined in the header itself
     defs = defined(sources())
     assert defs["orbfe_extract"] == {"extractor.hip"} and defs["orbfe_search_by_bow"] == {"matcher.hip"}
-    assert defs["launch_search_by_bow"] == {"k_match.hip"}
+    assert defs["launch_search_by_bow"] == {"k_match.hip"} and defs["run_pipeline"] == {"extractor_pipeline.hip"}
 
 
 def test_no_source_file_declares_another_files_function():
     assert not stray_prototypes(), "prototypes belong in a header (csrc/host_internal.h for the host back doors)"
 
 
-def test_every_header_entry_is_defined_once_and_used_elsewhere():
+@pytest.mark.parametrize("header", HEADERS)
+def test_every_header_entry_is_defined_once_and_used_elsewhere(header):
     srcs = sources()
     defs = defined(srcs)
-    for fn in header_names():
+    names = header_names(header)
+    assert names, f"the scan finds no declaration in csrc/{header}"
+    for fn in names:
         where = defs.get(fn, set())
-        assert len(where) == 1, f"{fn} (csrc/{HEADER}) is defined in {sorted(where) or 'no source file'}"
+        assert len(where) == 1, f"{fn} (csrc/{header}) is defined in {sorted(where) or 'no source file'}"
         users = [n for n, t in srcs.items() if n not in where and re.search(r"\b" + fn + r"\s*\(", t)]
-        assert users, f"{fn} (csrc/{HEADER}) is used by no other source file: delete it, or make it static"
+        assert users, f"{fn} (csrc/{header}) is used by no other source file: delete it, or make it static"
 
 
-def test_every_user_and_definer_includes_the_header():
+@pytest.mark.parametrize("header", HEADERS)
+def test_every_user_and_definer_includes_the_header(header):
     srcs = sources()
-    for fn in header_names():
+    for fn in header_names(header):
         for n, t in srcs.items():
             if re.search(r"\b" + fn + r"\s*\(", t):
-                assert f'#include "{HEADER}"' in (CSRC / n).read_text(), f"{n} uses {fn} without including {HEADER}"
+                assert f'#include "{header}"' in (CSRC / n).read_text(), f"{n} uses {fn} without including {header}"
+
+
+def test_only_the_extractors_own_files_see_the_handle():
+    """struct orbfe_extractor has one definition, and the matcher side keeps to the back doors of host_internal.h."""
+    own = {"extractor_handle.hip", "extractor_pipeline.hip", "extractor.hip", "stereo_batch.hip", "extractor_debug.hip"}
+    texts = {p.name: p.read_text() for p in CSRC.iterdir() if p.suffix in (".hip", ".h", ".cpp")}
+    assert [n for n, t in texts.items() if "struct orbfe_extractor {" in t] == ["extractor_handle.h"]
+    assert {n for n, t in texts.items() if '#include "extractor_handle.h"' in t} == own
 
 
 def test_the_guard_notices_a_hand_copied_prototype(tmp_path):
@@ -102,3 +120,10 @@ def test_the_guard_notices_a_hand_copied_prototype(tmp_path):
     m = tmp_path / "matcher.hip"
     m.write_text(m.read_text().replace("  GridFrame g{};", "  extern int orbfe_device_count(void);\n  GridFrame g{};", 1))
     assert ("matcher.hip", "orbfe_device_count") in stray_prototypes(tmp_path)
+    # ... and a helper of extractor_handle.h, re-declared by one of the extractor's own files
+    s = tmp_path / "stereo_batch.hip"
+    s.write_text(s.read_text().replace(
+        "using namespace orbfe;\n",
+        "using namespace orbfe;\nnamespace orbfe {\nint run_pipeline(orbfe_extractor* e, LevelView level0, int nFrames, "
+        "orbfe_keypoint* d_kp, uint8_t* d_desc, int capacity, int32_t* d_nOut);\n}\n", 1))
+    assert ("stereo_batch.hip", "run_pipeline") in stray_prototypes(tmp_path)

@@ -78,7 +78,7 @@ def sites():
 def test_the_scan_finds_the_known_waits():
     s = sites()
     assert sum(s.values()) >= 20, s
-    assert "extractor.hip:run_pipeline:hipStreamWaitEvent(s, e->evConsumerDone)" in s
+    assert "extractor_pipeline.hip:run_pipeline:hipStreamWaitEvent(s, e->evConsumerDone)" in s
     assert "frames.hip:frame_use:hipStreamWaitEvent(ar->stream, f->ready)" in s
 
 
