@@ -1600,6 +1600,57 @@ int orbfe_obsgraph_distinctive_descriptors_mappoints(orbfe_obsgraph *g, orbfe_ma
                                                      int32_t *best_kf_slot /*may be NULL*/, int32_t *best_idx /*may be NULL*/,
                                                      uint8_t *valid);
 
+/* ------------------------------------------------------------------------- */
+/* ORBmatcher::Fuse on the resident map points                                 */
+/* ------------------------------------------------------------------------- */
+/* The prologue of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:960-1006; the Sim3 overload :1135-1184 with the
+ * caller's decomposition of Scw in pose[k]) for the n map points in slot[] against n_keyframes (<= 64) key-frame poses, as ONE
+ * kernel launch.  pose[k] holds what Fuse reads of key frame k: GetRotation / GetTranslation / GetCameraCenter, fx fy cx cy mbf,
+ * mnMinX .. mnMaxY, mfLogScaleFactor, mnScaleLevels.  Outputs are [k*n + i]; any may be NULL.  valid[k*n+i] = the point passes
+ * every test for key frame k; where it is set, u / v / ur / level / dist are the projection, u - mbf/z, PredictScale and
+ * dist3D; elsewhere they are 0.  IEEE binary32 (binary64 where stated), no contraction, sums left to right, in this order:
+ *   reject flags & ORBFE_MP_BAD; reject skip[k*n+i] (NULL = none); with a graph, reject a point whose observation row names
+ *   kf_slot[k] among its live entries (MapPoint::IsInKeyFrame, :965; a slot at or past g's point_capacity has no row);
+ *   xc = ((R00*X + R01*Y) + R02*Z) + t0 (yc, zc likewise); reject zc < 0; invz = 1/zc; x = xc*invz; y = yc*invz;
+ *   u = fx*x + cx; v = fy*y + cy (NOT isInFrustum's (fx*xc)*invz; the Sim3 overload's 1.0/z in double, rounded to float, is the
+ *   same float quotient: 53 >= 2*24 + 2);
+ *   KeyFrame::IsInImage (src/KeyFrame.cc:653-656): reject unless u >= min_x && u < max_x && v >= min_y && v < max_y -- the
+ *   upper bounds are strict, unlike isInFrustum's;
+ *   ur = u - mbf*invz; PO = P - Ow; dist = (float)sqrt(sum (double)PO_i^2); reject dist < 0.8f*min || dist > 1.2f*max;
+ *   reject sum (double)PO_i*(double)Pn_i < 0.5 * (double)dist (a compare in double, nothing is divided, :1000);
+ *   level = clamp(ceil(log((double)(max/dist)) / (double)log_scale_factor), 0, n_levels-1).
+ * Only the slot list, the mask, the poses and kf_slot[] go up.  Slots outside the table, kf slots outside the graph,
+ * n_keyframes > 64, a pose whose n_levels is not 1 .. 64, NULL slot / pose / kf_slot (with g) arrays and handles on
+ * different devices return ORBFE_ERR_INVALID before anything is enqueued; n == 0 or n_keyframes == 0 is ORBFE_OK with
+ * nothing touched.  Takes g's serialisation, then mp's. */
+int orbfe_project_fuse(orbfe_mappoints *mp, orbfe_obsgraph *g /* NULL: no IsInKeyFrame test */, int n, const int32_t *slot,
+                       int n_keyframes, const int32_t *kf_slot /* [K], read only with g */,
+                       const orbfe_camera_pose *pose /* [K] */, const uint8_t *skip /* [K*n] or NULL */,
+                       uint8_t *valid, float *u, float *v, float *ur, int32_t *level, float *dist);
+
+/* ORBmatcher::Fuse (chi2_gate != 0: src/ORBmatcher.cc:940-1099; == 0: the Sim3 overload :1112-1237 with the caller's
+ * decomposition of Scw in pose[k]) for the SAME slots against K key frames as ONE call: the projection above writes the
+ * query windows (centre (u, v), radius th * scale_factors[level], octaves [level-1, level], ur for the chi-square gate of
+ * :1030-1054; without the gate ur is not read, :1197-1214) where the window search reads them, the points' descriptors are
+ * gathered from the table once for all K key frames, and the one window-search launch of orbfe_fuse_search_multi runs
+ * behind it.  One upload (slot list, mask, poses, kf_slot, level tables), one download.  best_idx[k*n+i] = the keypoint of
+ * KF[k] Fuse would take for point i (bestDist <= TH_LOW) or -1; projected[k*n+i] (optional) = the point passed the prologue.
+ * best_idx equals orbfe_fuse_search_multi fed with orbfe_project_fuse's outputs and the table's descriptors, bit for bit.
+ * Beyond orbfe_project_fuse's checks: pose[k].n_levels > n_levels, NULL KF / scale_factors / best_idx (inv_level_sigma2 when
+ * gated), a bad key-frame view and -- gated -- a keypoint octave outside the pyramid return ORBFE_ERR_INVALID before
+ * anything is enqueued.
+ * What stays with the caller: Replace / AddObservation / AddMapPoint (:1069-1090), the pMPinKF comparison of observation
+ * counts, and the Sim3 overload's vpReplacePoint.  Results are computed against the state AT ENTRY: a caller that replays
+ * the key frames in order ignores the hits of a point that an earlier key frame's replay made bad, and the hits of a point
+ * that the replay placed in that key frame.  One thing the multi form cannot reproduce: MapPoint::Replace ends in
+ * ComputeDistinctiveDescriptors, so a survivor's descriptor may change between two key frames of the reference's loop.  A
+ * caller who needs that exact sequence calls with K = 1 per key frame and refreshes the table in between with
+ * orbfe_obsgraph_distinctive_descriptors_mappoints (orbfe_fuse_search_multi has the same property). */
+int orbfe_fuse_mappoints(orbfe_mappoints *mp, orbfe_obsgraph *g, int n, const int32_t *slot, int n_keyframes,
+                         const orbfe_frame_view *const *KF, const int32_t *kf_slot, const orbfe_camera_pose *pose,
+                         const uint8_t *skip, const float *scale_factors, const float *inv_level_sigma2, int n_levels,
+                         float th, int chi2_gate, int32_t *best_idx /* [K*n] */, uint8_t *projected /* [K*n] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

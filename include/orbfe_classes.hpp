@@ -880,6 +880,34 @@ class MapPointTable {
                                     nnratio, match.data(), &nmatches, inView ? inView->data() : nullptr), "SearchLocalPoints");
     return nmatches;
   }
+  // ORBmatcher::Fuse for slot[] against K key frames in one call (orbfe_fuse_mappoints): bestIdx[k * n + i] = the keypoint of
+  // KFs[k] Fuse would take for point i, or -1.  chi2Gate: Fuse(pKF, vpMapPoints, th), needs mvInvLevelSigma2; otherwise the
+  // Sim3 overload with the caller's decomposition of Scw in pose[k].  graph (may be NULL) + kfSlot: IsInKeyFrame from the
+  // observation rows; skip: empty, or K * n bytes; projected (may be NULL): the points that passed the prologue.  Replace /
+  // AddObservation / AddMapPoint stay with the caller; the results are those of the state at entry (include/orbfe.h).
+  std::vector<int32_t> Fuse(const std::vector<const FrameArrays*>& KFs, const std::vector<orbfe_camera_pose>& pose,
+                            const std::vector<int32_t>& slot, const std::vector<float>& mvScaleFactors,
+                            const std::vector<float>& mvInvLevelSigma2, float th = 3.0f, bool chi2Gate = true,
+                            const ObservationGraph* graph = nullptr, const std::vector<int32_t>& kfSlot = {},
+                            const std::vector<uint8_t>& skip = {}, std::vector<uint8_t>* projected = nullptr) const {
+    const size_t n = slot.size(), K = KFs.size();
+    if (pose.size() != K) throw std::invalid_argument("MapPointTable::Fuse: one pose per key frame");
+    if (graph && kfSlot.size() != K) throw std::invalid_argument("MapPointTable::Fuse: one kf slot per key frame");
+    if (!skip.empty() && skip.size() != K * n) throw std::invalid_argument("MapPointTable::Fuse: K * n skip entries");
+    if (chi2Gate && mvInvLevelSigma2.size() != mvScaleFactors.size())
+      throw std::invalid_argument("MapPointTable::Fuse: one mvInvLevelSigma2 entry per level");
+    std::vector<const orbfe_frame_view*> views;
+    for (const FrameArrays* f : KFs) views.push_back(&f->c);
+    std::vector<int32_t> best(K * n + 1, -1);
+    if (projected) projected->assign(K * n + 1, 0);
+    check(orbfe_fuse_mappoints(h_, graph ? graph->handle() : nullptr, (int)n, slot.data(), (int)K, views.data(),
+                               graph ? kfSlot.data() : nullptr, pose.data(), skip.empty() ? nullptr : skip.data(), mvScaleFactors.data(),
+                               chi2Gate ? mvInvLevelSigma2.data() : nullptr, (int)mvScaleFactors.size(), th, chi2Gate ? 1 : 0, best.data(),
+                               projected ? projected->data() : nullptr), "MapPointTable::Fuse");
+    best.resize(K * n);
+    if (projected) projected->resize(K * n);
+    return best;
+  }
   orbfe_mappoints* handle() const { return h_; }
   // the tail of Optimizer::OptimizeEssentialGraph (:1070-1103) on the table: the position of slot[p] becomes
   // Sout[r]^-1 .map(Scw[r] .map(P)), r = refVertex[p] (-1: left alone); Scw / SiwOut 8 doubles per vertex

@@ -133,6 +133,7 @@ EXPORTS = [
     "orbfe_obsgraph_enable_keyframe_descriptors", "orbfe_obsgraph_set_keyframe_descriptors",
     "orbfe_obsgraph_set_keyframe_descriptors_frame", "orbfe_obsgraph_get_keyframe_descriptors",
     "orbfe_obsgraph_distinctive_descriptors", "orbfe_obsgraph_distinctive_descriptors_mappoints", "orbfe_mappoints_descriptors",
+    "orbfe_project_fuse", "orbfe_fuse_mappoints",
 ]
 
 _lib = None
@@ -362,6 +363,8 @@ def load():
     L.orbfe_obsgraph_distinctive_descriptors.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.orbfe_obsgraph_distinctive_descriptors_mappoints.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     L.orbfe_mappoints_descriptors.argtypes = [vp, ci, vp, vp]
+    L.orbfe_project_fuse.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_fuse_mappoints.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, cf, ci, vp, vp]
     _lib = L
     return L
 

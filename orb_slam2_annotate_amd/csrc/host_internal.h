@@ -116,6 +116,25 @@ struct MapPointsLock {
  private:
   orbfe_mappoints* held = nullptr;
 };
+
+// ---- obsgraph.hip (struct orbfe_obsgraph: obsgraph_handle.h, for the graph's own files only) ----
+// How another host file reads a graph's rows on the device, by the route orbfe_obsgraph_update_normal_depth_mappoints takes:
+// the constructor takes the handle's serialisation (g == NULL: holds nothing, and table_ready() is a no-op that leaves
+// `graph` NULL); the caller then takes its MapPointsLock, and table_ready() writes the marked rows -- complete on return, so
+// any stream may read them for the scope.  The capacities and the device are fixed at create.
+struct ObsGraphDevice;  // obsgraph_kernels.h
+struct ObsGraphLock {
+  ObsGraphLock(orbfe_obsgraph* g);
+  ~ObsGraphLock();
+  ObsGraphLock(const ObsGraphLock&) = delete;
+  ObsGraphLock& operator=(const ObsGraphLock&) = delete;
+  int table_ready();
+  int device = 0, pointCap = 0, kfCap = 0;
+  const ObsGraphDevice* graph = nullptr;
+
+ private:
+  orbfe_obsgraph* held = nullptr;
+};
 }  // namespace orbfe
 
 extern "C" {

@@ -1,11 +1,13 @@
 // k_project.hip -- the pose arithmetic in front of Tracking::SearchLocalPoints on the device-resident map points:
-// Frame::isInFrustum (src/Frame.cc:292-353) with MapPoint::PredictScale, and the scatter that keeps the table up to date.
-// Both kernels are bandwidth-trivial (64 bytes of table per point, a few thousand points): one lane per point, the table
+// Frame::isInFrustum (src/Frame.cc:292-353) with MapPoint::PredictScale, the prologue of ORBmatcher::Fuse for K key frames
+// (k_project_fuse), and the scatter that keeps the table up to date.
+// The kernels are bandwidth-trivial (64 bytes of table per point, a few thousand points): one lane per point, the table
 // records as 16-byte loads, the descriptor rows moved by the whole workgroup as 16-byte pieces.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
 #include "match_kernels.h"
+#include "obsgraph_host.h"
 
 namespace orbfe {
 
@@ -90,6 +92,106 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_frustum(const Proje
   }
 }
 
+// The prologue of ORBmatcher::Fuse (src/ORBmatcher.cc:960-1006) for 256 consecutive points x K key-frame poses: the two table
+// records and the flag byte of a point are read once, the poses and kf slots wait in LDS (K x 104 bytes), and every result array
+// is [k * n + i], so that a wave's stores of one k are consecutive.  The arithmetic is include/orbfe.h's (orbfe_project_fuse),
+// operation by operation.  The Sim3 overload (:1135-1184) computes 1.0 / z in double and rounds the quotient to float: that
+// is the float division below, since a double quotient of two floats rounded to float is correctly rounded (53 >= 2 * 24 + 2).
+__global__ __launch_bounds__(kProjectThreads) void k_project_fuse(const FuseArgs a) {
+  __shared__ orbfe_camera_pose sPose[kFuseMaxKeyFrames];
+  __shared__ int32_t sKf[kFuseMaxKeyFrames];
+  {
+    constexpr int kWords = (int)(sizeof(orbfe_camera_pose) / 4);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.pose);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(sPose);
+    for (int w = (int)threadIdx.x; w < a.K * kWords; w += kProjectThreads) dst[w] = src[w];
+    if ((int)threadIdx.x < a.K) sKf[threadIdx.x] = a.rows ? a.kfSlot[threadIdx.x] : -1;
+  }
+  __syncthreads();
+  const int base = blockIdx.x * kProjectThreads;
+  const int i = base + (int)threadIdx.x;
+  if (i < a.n) {
+    const int s = a.slot[i];
+    const float4 r0 = a.table.rec[2 * (size_t)s], r1 = a.table.rec[2 * (size_t)s + 1];
+    const uint8_t fl = a.table.flags[s];
+    const float X = r0.x, Y = r0.y, Z = r0.z, minD = r0.w, maxD = r1.w;
+    // MapPoint::IsInKeyFrame (:965) for all K key frames from one walk over the row: bit k = the row names kfSlot[k]
+    unsigned long long inKf = 0;
+    if (a.rows && s < a.pointCap) {
+      int cnt = a.meta[s].count;
+      cnt = cnt < a.rowWidth ? cnt : a.rowWidth;
+      const ObsEntry* row = a.rows + (size_t)s * a.rowWidth;
+      for (int e = 0; e < cnt; e++) {
+        const int32_t kf = row[e].kf;
+        for (int k = 0; k < a.K; k++)
+          if (sKf[k] == kf) inKf |= 1ull << k;
+      }
+    }
+    const float lo = __fmul_rn(0.8f, minD), hi = __fmul_rn(1.2f, maxD);
+    const double nx = (double)r1.x, ny = (double)r1.y, nz = (double)r1.z;
+    for (int k = 0; k < a.K; k++) {
+      const orbfe_camera_pose& c = sPose[k];
+      const size_t o = (size_t)k * a.n + i;
+      bool ok = !(fl & ORBFE_MP_BAD) && !(a.skip && a.skip[o]) && !((inKf >> k) & 1);
+      // 3D in camera coordinates (:969); the depth must be positive (:972)
+      const float xc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[0], X), __fmul_rn(c.Rcw[1], Y)), __fmul_rn(c.Rcw[2], Z)), c.tcw[0]);
+      const float yc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[3], X), __fmul_rn(c.Rcw[4], Y)), __fmul_rn(c.Rcw[5], Z)), c.tcw[1]);
+      const float zc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[6], X), __fmul_rn(c.Rcw[7], Y)), __fmul_rn(c.Rcw[8], Z)), c.tcw[2]);
+      if (zc < 0.0f) ok = false;
+      // normalised coordinates first (:975-980) -- not isInFrustum's (fx * xc) * invz
+      const float invz = __fdiv_rn(1.0f, zc);
+      const float x = __fmul_rn(xc, invz), y = __fmul_rn(yc, invz);
+      const float u = __fadd_rn(__fmul_rn(c.fx, x), c.cx);
+      const float v = __fadd_rn(__fmul_rn(c.fy, y), c.cy);
+      // KeyFrame::IsInImage (src/KeyFrame.cc:653-656): the upper bounds are strict
+      if (!(u >= c.min_x && u < c.max_x && v >= c.min_y && v < c.max_y)) ok = false;
+      const float ur = __fsub_rn(u, __fmul_rn(c.mbf, invz));
+      // distance inside the scale invariance region (:990-995): cv::norm accumulates in double
+      const float px = __fsub_rn(X, c.Ow[0]), py = __fsub_rn(Y, c.Ow[1]), pz = __fsub_rn(Z, c.Ow[2]);
+      const double dpx = (double)px, dpy = (double)py, dpz = (double)pz;
+      const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dpx, dpx), __dmul_rn(dpy, dpy)), __dmul_rn(dpz, dpz));
+      const float dist = (float)__dsqrt_rn(d2);
+      if (dist < lo || dist > hi) ok = false;
+      // viewing angle below 60 degrees (:1000): Mat::dot accumulates in double, the compare is in double, nothing is divided
+      const double dot = __dadd_rn(__dadd_rn(__dmul_rn(dpx, nx), __dmul_rn(dpy, ny)), __dmul_rn(dpz, nz));
+      if (dot < __dmul_rn(0.5, (double)dist)) ok = false;
+      // MapPoint::PredictScale (:1003)
+      int lv = 0;
+      if (ok) {
+        const float ratio = __fdiv_rn(maxD, dist);
+        const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
+        const int top = c.n_levels - 1;
+        lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
+      }
+      if (a.valid) a.valid[o] = ok;
+      if (a.u) a.u[o] = ok ? u : 0.0f;
+      if (a.v) a.v[o] = ok ? v : 0.0f;
+      if (a.ur) a.ur[o] = ok ? ur : 0.0f;
+      if (a.level) a.level[o] = lv;
+      if (a.dist) a.dist[o] = ok ? dist : 0.0f;
+      if (a.qx) {  // the windows of :1006-1028 as orbfe_fuse_search_multi builds them from the arrays above
+        a.qx[o] = ok ? u : 0.0f;
+        a.qy[o] = ok ? v : 0.0f;
+        a.qr[o] = __fmul_rn(a.th, a.scale[lv]);
+        a.qmin[o] = lv - 1;
+        a.qmax[o] = lv;
+        a.qactive[o] = ok;
+        if (a.qur) a.qur[o] = ok ? ur : 0.0f;
+        if (a.validCopy) a.validCopy[o] = ok;
+      }
+    }
+  }
+  if (a.qdesc) {  // (workgroup-uniform) the descriptors, gathered once for all K jobs: piece p = half (p & 1) of point base + p / 2
+    const int cnt = a.n - base < kProjectThreads ? a.n - base : kProjectThreads;
+    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
+    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
+    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
+      const int q = base + (p >> 1);
+      dst[2 * (size_t)q + (p & 1)] = src[2 * (size_t)a.slot[q] + (p & 1)];
+    }
+  }
+}
+
 __global__ __launch_bounds__(kProjectThreads) void k_mappoints_scatter(const MapPointsDevice t, int n, const int32_t* __restrict__ slot,
                                                                        const float4* __restrict__ rec, const uint8_t* __restrict__ flags,
                                                                        const uint8_t* __restrict__ desc) {
@@ -125,6 +227,11 @@ __global__ __launch_bounds__(kProjectThreads) void k_mappoints_read_descriptors(
 void launch_project_frustum(hipStream_t s, const ProjectArgs& a) {
   if (a.n <= 0) return;
   hipLaunchKernelGGL(k_project_frustum, dim3((a.n + kProjectThreads - 1) / kProjectThreads), dim3(kProjectThreads), 0, s, a);
+}
+
+void launch_project_fuse(hipStream_t s, const FuseArgs& a) {
+  if (a.n <= 0 || a.K <= 0 || a.K > kFuseMaxKeyFrames) return;
+  hipLaunchKernelGGL(k_project_fuse, dim3((a.n + kProjectThreads - 1) / kProjectThreads), dim3(kProjectThreads), 0, s, a);
 }
 
 void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/orbfe.h"
+
 namespace orbfe {
 
 constexpr int kMapPointsMaxCapacity = 1 << 24;
@@ -55,6 +57,26 @@ inline void mappoints_pack_records(float* rec, int n, const float* pos, const fl
     r[0] = pos[3 * i]; r[1] = pos[3 * i + 1]; r[2] = pos[3 * i + 2]; r[3] = min_dist[i];
     r[4] = normal[3 * i]; r[5] = normal[3 * i + 1]; r[6] = normal[3 * i + 2]; r[7] = max_dist[i];
   }
+}
+
+
+// The operands of orbfe_project_fuse / orbfe_fuse_mappoints that need neither handle: the slot list of a table of `capacity`
+// slots, K poses (at most kFuseMaxPoses, the kernel's LDS holds them) and -- with_graph -- the K kf slots of a graph of
+// kf_capacity key frames.  n_levels > 0: the caller's level tables hold that many entries, and no pose may predict past them.
+constexpr int kFuseMaxPoses = 64, kFuseMaxPoseLevels = 64;
+inline const char* fuse_check_operands(int capacity, int n, const int32_t* slot, int K, const int32_t* kf_slot, bool with_graph,
+                                       int kf_capacity, const orbfe_camera_pose* pose, int n_levels) {
+  if (K < 0) return "negative number of key frames";
+  if (K > kFuseMaxPoses) return "more than 64 key frames in one call";
+  if (const char* e = mappoints_check_slots(capacity, n, slot)) return e;
+  if (K > 0 && !pose) return "NULL pose array";
+  if (K > 0 && with_graph && !kf_slot) return "NULL kf_slot array";
+  for (int k = 0; k < K; k++) {
+    if (pose[k].n_levels < 1 || pose[k].n_levels > kFuseMaxPoseLevels) return "bad pose (n_levels must be 1 .. 64)";
+    if (n_levels > 0 && pose[k].n_levels > n_levels) return "a pose predicts more levels than the level tables hold";
+    if (with_graph && (kf_slot[k] < 0 || kf_slot[k] >= kf_capacity)) return "kf slot outside [0, kf_capacity)";
+  }
+  return nullptr;
 }
 
 }  // namespace orbfe

@@ -166,6 +166,29 @@ struct ProjectArgs {
   const float* scale; float th;
 };
 void launch_project_frustum(hipStream_t s, const ProjectArgs& a);
+// k_project_fuse: the prologue of ORBmatcher::Fuse (src/ORBmatcher.cc:960-1006; the Sim3 overload :1135-1184) for the n points
+// slot[0 .. n) against K key-frame poses in ONE launch.  A workgroup owns 256 consecutive points, reads each point's two
+// records and flag byte once and walks the K poses, which it holds in LDS.  Arrays of results are [k * n + i].  Two sets of
+// outputs, either may be absent: the projection itself (every pointer may be NULL), and -- qx != NULL -- the query windows of
+// orbfe_fuse_search_multi exactly as it builds them on the host (centre (u, v), radius th * scale[level], octaves
+// [level - 1, level]), with the points' descriptors gathered once for all K jobs, so that k_window_search runs behind it
+// without a host step.  rows != NULL: IsInKeyFrame (:965) from the observation graph -- a point whose row names kfSlot[k]
+// among its meta.count live entries is rejected for pose k; a slot at or past pointCap has no row.
+constexpr int kFuseMaxKeyFrames = 64;
+struct ObsEntry;      // obsgraph_host.h
+struct ObsPointMeta;
+struct FuseArgs {
+  MapPointsDevice table;
+  const int32_t* slot; const uint8_t* skip /* [K * n], NULL: none */; int n, K;
+  const orbfe_camera_pose* pose /* [K] */; const int32_t* kfSlot /* [K], read only with rows */;
+  const ObsEntry* rows; const ObsPointMeta* meta; int rowWidth, pointCap;
+  uint8_t* valid; float* u; float* v; float* ur; int32_t* level; float* dist;
+  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive;
+  float* qur /* NULL: no chi-square gate reads it */; uint8_t* qdesc /* [n * 32] */;
+  uint8_t* validCopy /* NULL, or a second copy of qactive among the results that travel back */;
+  const float* scale; float th;
+};
+void launch_project_fuse(hipStream_t s, const FuseArgs& a);
 // orbfe_mappoints_update: n staged entries (slot, the two records, flags, descriptors or NULL = keep) into their slots
 void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,
                               const uint8_t* flags, const uint8_t* desc);

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "mappoints_host.h"
 #include "match_kernels.h"
+#include "obsgraph_kernels.h"
 
 using namespace orbfe;
 
@@ -568,6 +569,36 @@ struct WindowJob {
   // PRODUCER (claim jobs only): the query arrays above are NULL -- k_project_frustum writes them on the device, behind the
   // call's one upload, from the map-point table; only the slot list, the skip mask and the scale factors travel
   struct FrustumProducer* producer = nullptr;
+  // FUSE PRODUCER (BEST jobs only): the K jobs of a call name ONE FuseProducer and their place k in it; the query arrays above
+  // are NULL -- ONE k_project_fuse launch writes the windows of all K jobs from the map-point table, and the descriptors once
+  struct FuseProducer* fuse = nullptr;
+  int fuseK = 0;
+};
+struct FuseProducer {
+  MapPointsDevice table;
+  const ObsGraphDevice* graph = nullptr;  // NULL: no IsInKeyFrame test
+  const int32_t* slot = nullptr;          // [n]
+  const uint8_t* skip = nullptr;          // [K * n] or NULL
+  const orbfe_camera_pose* pose = nullptr;  // [K]
+  const int32_t* kfSlot = nullptr;          // [K] (with graph)
+  int n = 0, K = 0;
+  const float* scale = nullptr;      // [nLevels] mvScaleFactors
+  const float* invSigma2 = nullptr;  // [nLevels] mvInvLevelSigma2 (gate)
+  int nLevels = 0;
+  float th = 3.0f;
+  bool gate = false;
+  uint8_t* projectedOut = nullptr;  // out [K * n] or NULL
+};
+// where a call's FuseProducer has its arrays on the device: uploads | the one result | what k_project_fuse writes for the search
+struct FuseDev {
+  int32_t *slot = nullptr, *kfSlot = nullptr;
+  uint8_t* skip = nullptr;
+  orbfe_camera_pose* pose = nullptr;
+  float *scale = nullptr, *invSigma2 = nullptr;
+  uint8_t* projected = nullptr;
+  float *qx = nullptr, *qy = nullptr, *qr = nullptr, *qur = nullptr;
+  int32_t *qmin = nullptr, *qmax = nullptr;
+  uint8_t *qactive = nullptr, *qdesc = nullptr;
 };
 struct FrustumProducer {
   MapPointsDevice table;
@@ -618,12 +649,40 @@ struct JobDev {
 
 // Region 1 of a call's arena, job j's part: everything that travels up.  Only up() between the first and the last of these,
 // so that flush()'s dirty range is exactly the uploads: one host-to-device copy.
-hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev) {
+hipError_t stage_fuse_inputs(Arena* a, const FuseProducer& P, FuseDev* F) {
+  const size_t q = (size_t)P.K * P.n;
+  TRY(up(a, &F->slot, P.slot, (size_t)P.n));
+  if (P.skip) TRY(up(a, &F->skip, P.skip, q));
+  TRY(up(a, &F->pose, P.pose, (size_t)P.K));
+  if (P.graph) TRY(up(a, &F->kfSlot, P.kfSlot, (size_t)P.K));
+  if (P.scale) TRY(up(a, &F->scale, P.scale, (size_t)P.nLevels));
+  if (P.gate) TRY(up(a, &F->invSigma2, P.invSigma2, (size_t)P.nLevels));
+  return hipSuccess;
+}
+void stage_fuse_scratch(Arena* a, const FuseProducer& P, FuseDev* F) {
+  const size_t q = (size_t)P.K * P.n;
+  F->qx = carve<float>(a, q); F->qy = carve<float>(a, q); F->qr = carve<float>(a, q);
+  F->qmin = carve<int32_t>(a, q); F->qmax = carve<int32_t>(a, q);
+  F->qactive = carve<uint8_t>(a, q);
+  if (P.gate) F->qur = carve<float>(a, q);
+  F->qdesc = carve<uint8_t>(a, (size_t)P.n * 32);
+}
+FuseArgs fuse_args(const FuseProducer& P, const FuseDev& F) {
+  FuseArgs fa{};
+  fa.table = P.table; fa.slot = F.slot; fa.skip = F.skip; fa.n = P.n; fa.K = P.K; fa.pose = F.pose; fa.kfSlot = F.kfSlot;
+  if (P.graph) { fa.rows = P.graph->rows; fa.meta = P.graph->meta; fa.rowWidth = P.graph->rowWidth; fa.pointCap = P.graph->pointCap; }
+  fa.qx = F.qx; fa.qy = F.qy; fa.qr = F.qr; fa.qmin = F.qmin; fa.qmax = F.qmax; fa.qactive = F.qactive; fa.qur = F.qur;
+  fa.qdesc = F.qdesc; fa.validCopy = F.projected;
+  fa.scale = F.scale; fa.th = P.th;
+  return fa;
+}
+
+hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, const FuseDev& fuse) {
   const WindowJob& J = jobs[j];
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
   D = JobDev{};
-  D.withDesc = J.f->desc && (J.qdesc || J.producer);
+  D.withDesc = J.f->desc && (J.qdesc || J.producer || J.fuse);
   D.withUr = (J.qur || J.producer) && J.f->u_right;
   if (const orbfe_frame* R = J.f->resident) {
     D.x = R->dx; D.y = R->dy; D.oct = R->doct; D.ur = J.f->u_right ? R->dur : nullptr; D.desc = D.withDesc ? R->ddesc : nullptr;
@@ -645,6 +704,8 @@ hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev) {
     TRY(up(a, &D.slot, P->slot, q));
     if (P->skip) TRY(up(a, &D.skip, P->skip, q));
     TRY(up(a, &D.scale, P->scale, (size_t)P->nLevels));
+  } else if (J.fuse) {  // (the call's one FuseProducer has uploaded everything: stage_fuse_inputs)
+    if (J.fuse->gate) D.invSigma2 = fuse.invSigma2;
   } else {
     TRY(up(a, &D.qx, J.qx, q)); TRY(up(a, &D.qy, J.qy, q)); TRY(up(a, &D.qr, J.qr, q));
     TRY(up(a, &D.qmin, J.qmin, q)); TRY(up(a, &D.qmax, J.qmax, q));
@@ -698,10 +759,16 @@ OwnerPlace owner_place(const WindowJob& J) {
 
 // Region 3, job j's part: what never leaves the device -- the grid of an uploaded frame, the query arrays a producer
 // writes, the claim kernel's lists and scratch
-void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev) {
+void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev, const FuseDev& fuse) {
   const WindowJob& J = jobs[j];
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
+  if (J.fuse) {  // job k's part of what the one k_project_fuse launch writes
+    const size_t o = (size_t)J.fuseK * q;
+    D.qx = fuse.qx + o; D.qy = fuse.qy + o; D.qr = fuse.qr + o; D.qmin = fuse.qmin + o; D.qmax = fuse.qmax + o;
+    D.qactive = fuse.qactive + o; D.qdesc = fuse.qdesc;
+    if (J.fuse->gate && J.f->u_right) D.gateUr = fuse.qur + o;
+  }
   if (D.frameOf == j) { D.key = carve<uint32_t>(a, n); D.cell = carve<int32_t>(a, 3073); }
   else if (D.frameOf >= 0) { D.key = dev[D.frameOf].key; D.cell = dev[D.frameOf].cell; }
   if (J.producer) {
@@ -766,6 +833,8 @@ struct WindowCall {
   ClaimJob* dClaims = nullptr;
   WindowSearchJob* dSearches = nullptr;  // (a single job travels as kernel arguments)
   uint8_t *outLo = nullptr, *outHi = nullptr;
+  const FuseProducer* fuseProducer = nullptr;  // the one FuseProducer of the call's jobs, and where it is on the device
+  FuseDev fuse;
   size_t claimLds = 0;
   int totalBlocks = 0;
 };
@@ -776,13 +845,17 @@ struct WindowCall {
 hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, int K, WindowCall* c) {
   *c = WindowCall{};
   c->dev.resize((size_t)nJobs);
-  for (int j = 0; j < nJobs; j++) TRY(stage_inputs(a, jobs, j, c->dev.data()));
+  for (int j = 0; j < nJobs && !c->fuseProducer; j++) c->fuseProducer = jobs[j].fuse;
+  if (c->fuseProducer) TRY(stage_fuse_inputs(a, *c->fuseProducer, &c->fuse));
+  for (int j = 0; j < nJobs; j++) TRY(stage_inputs(a, jobs, j, c->dev.data(), c->fuse));
   c->dClaims = carve<ClaimJob>(a, (size_t)nClaim);
   c->dSearches = carve<WindowSearchJob>(a, nJobs > 1 ? (size_t)nJobs : 0);
   c->outLo = carve<uint8_t>(a, 0);
   for (int j = 0; j < nJobs; j++) stage_outputs(a, jobs[j], K, &c->dev[j]);
+  if (c->fuseProducer && c->fuseProducer->projectedOut) c->fuse.projected = carve<uint8_t>(a, (size_t)c->fuseProducer->K * c->fuseProducer->n);
   c->outHi = carve<uint8_t>(a, 0);
-  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data());
+  if (c->fuseProducer) stage_fuse_scratch(a, *c->fuseProducer, &c->fuse);
+  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data(), c->fuse);
   for (int j = 0; j < nJobs; j++) {
     if (jobs[j].claim) {
       c->claims.push_back(claim_job(jobs[j], c->dev[j], K));
@@ -801,6 +874,10 @@ hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, in
 hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCall& c, bool claimInit) {
   for (int j = 0; j < nJobs; j++) TRY(frame_use(ar, jobs[j].f->resident));
   TRY(flush(ar));
+  if (c.fuseProducer) {  // ONE launch for the windows of all its jobs
+    launch_project_fuse(ar->stream, fuse_args(*c.fuseProducer, c.fuse));
+    TRY(hipGetLastError());
+  }
   for (int j = 0; j < nJobs; j++)
     if (jobs[j].producer) {
       launch_project_frustum(ar->stream, project_args(jobs[j], c.dev[j]));
@@ -830,6 +907,8 @@ hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, const Windo
 thread_local int t_lastClaimRounds = 0;
 int collect_results(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCall& c, int K) {
   int mx = 0;
+  if (const FuseProducer* P = c.fuseProducer)
+    if (P->projectedOut) std::memcpy(P->projectedOut, mirror_of(ar, c.fuse.projected), (size_t)P->K * P->n);
   for (int j = 0; j < nJobs; j++) {
     const WindowJob& J = jobs[j];
     const JobDev& D = c.dev[j];
@@ -871,6 +950,9 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
     const WindowJob& J = jobs[j];
     if (J.f->resident && J.f->resident->device != device) return fail(ORBFE_ERR_INVALID, "resident frame lives on another device");
     if (J.producer && (!J.claim || J.claim->mode != CLAIM_RATIO)) return fail(ORBFE_ERR_INVALID, "a producer needs a CLAIM_RATIO job");
+    if (J.fuse && (!J.bestOut || J.fuse != jobs[0].fuse || J.nq != J.fuse->n || J.fuseK < 0 || J.fuseK >= J.fuse->K))
+      return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST jobs that all name it");
+    if (!J.fuse && jobs[0].fuse) return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST jobs that all name it");
     if (!J.claim) continue;
     if (J.nq > 0x1fffff) return fail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
     if (nClaim && claimInit != (J.claim->mode == CLAIM_INIT)) return fail(ORBFE_ERR_INVALID, "mixed claim forms in one call");
@@ -1282,6 +1364,105 @@ extern "C" int orbfe_fuse_search(int device, const orbfe_frame_view* KF, const f
       return fail(ORBFE_ERR_INVALID, "fuse_search: keypoint octave outside the pyramid");
   BestJob job{KF, scale_factors, inv_level_sigma2, n, valid, u, v, ur, level, mp_desc, best_idx};
   return window_best_multi("fuse_search", device, &job, 1, n_levels, th, chi2_gate != 0, 50 /* TH_LOW */);
+}
+
+namespace {
+// k_project_fuse alone (n > 0, K > 0, arguments checked, both handles held): slot list, mask, poses and kf slots up, one launch,
+// the six arrays back in one copy
+int project_fuse_run(int device, const MapPointsDevice& table, const ObsGraphDevice* graph, int n, const int32_t* slot, int K,
+                     const int32_t* kf_slot, const orbfe_camera_pose* pose, const uint8_t* skip, uint8_t* valid, float* u, float* v,
+                     float* ur, int32_t* level, float* dist) {
+  const size_t q = (size_t)K * n;
+  FuseProducer P;
+  P.table = table; P.graph = graph; P.slot = slot; P.skip = skip; P.pose = pose; P.kfSlot = kf_slot; P.n = n; P.K = K;
+  FuseDev F;
+  FuseArgs fa{};
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    F = FuseDev{};
+    TRY(stage_fuse_inputs(a, P, &F));
+    fa = fuse_args(P, F);
+    // the outputs adjacent: one copy back
+    fa.level = carve<int32_t>(a, q); fa.u = carve<float>(a, q); fa.v = carve<float>(a, q); fa.ur = carve<float>(a, q);
+    fa.dist = carve<float>(a, q); fa.valid = carve<uint8_t>(a, q);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(device, &ar, stage));
+  HIPCHK(flush(ar));
+  launch_project_fuse(ar->stream, fa);
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_range(ar, fa.level, fa.valid + q));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  if (level) std::memcpy(level, mirror_of(ar, fa.level), q * 4);
+  if (u) std::memcpy(u, mirror_of(ar, fa.u), q * 4);
+  if (v) std::memcpy(v, mirror_of(ar, fa.v), q * 4);
+  if (ur) std::memcpy(ur, mirror_of(ar, fa.ur), q * 4);
+  if (dist) std::memcpy(dist, mirror_of(ar, fa.dist), q * 4);
+  if (valid) std::memcpy(valid, mirror_of(ar, fa.valid), q);
+  return ORBFE_OK;
+}
+}  // namespace
+
+extern "C" int orbfe_project_fuse(orbfe_mappoints* mp, orbfe_obsgraph* g, int n, const int32_t* slot, int n_keyframes,
+                                  const int32_t* kf_slot, const orbfe_camera_pose* pose, const uint8_t* skip, uint8_t* valid, float* u,
+                                  float* v, float* ur, int32_t* level, float* dist) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "project_fuse: NULL table");
+  ObsGraphLock glock(g);  // the graph's serialisation first, then the table's: the order of orbfe_obsgraph_*_mappoints
+  if (g && mappoints_device(mp) != glock.device) return fail(ORBFE_ERR_INVALID, "project_fuse: the graph and the map-point table are on different devices");
+  if (const char* e = fuse_check_operands(orbfe_mappoints_capacity(mp), n, slot, n_keyframes, kf_slot, g != nullptr, glock.kfCap, pose, 0))
+    return fail(ORBFE_ERR_INVALID, std::string("project_fuse: ") + e);
+  if (n == 0 || n_keyframes == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  if (int rc = glock.table_ready()) return rc;
+  return project_fuse_run(lock.device, *lock.table, glock.graph, n, slot, n_keyframes, kf_slot, pose, skip, valid, u, v, ur, level, dist);
+}
+
+extern "C" int orbfe_fuse_mappoints(orbfe_mappoints* mp, orbfe_obsgraph* g, int n, const int32_t* slot, int n_keyframes,
+                                    const orbfe_frame_view* const* KF, const int32_t* kf_slot, const orbfe_camera_pose* pose,
+                                    const uint8_t* skip, const float* scale_factors, const float* inv_level_sigma2, int n_levels,
+                                    float th, int chi2_gate, int32_t* best_idx, uint8_t* projected) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "fuse_mappoints: NULL table");
+  if (!scale_factors || n_levels <= 0 || (chi2_gate && !inv_level_sigma2) || (n_keyframes > 0 && !KF) ||
+      (n_keyframes > 0 && n > 0 && !best_idx))
+    return fail(ORBFE_ERR_INVALID, "fuse_mappoints: bad argument");
+  ObsGraphLock glock(g);  // the graph's serialisation first, then the table's: the order of orbfe_obsgraph_*_mappoints
+  if (g && mappoints_device(mp) != glock.device) return fail(ORBFE_ERR_INVALID, "fuse_mappoints: the graph and the map-point table are on different devices");
+  if (const char* e = fuse_check_operands(orbfe_mappoints_capacity(mp), n, slot, n_keyframes, kf_slot, g != nullptr, glock.kfCap, pose, n_levels))
+    return fail(ORBFE_ERR_INVALID, std::string("fuse_mappoints: ") + e);
+  std::vector<const orbfe_frame_view*> views;
+  for (int k = 0; k < n_keyframes; k++) {  // (orbfe_fuse_search_multi's checks of its key frames)
+    const orbfe_frame_view* f = canon(KF[k]);
+    if (!frame_ok(f) || (f->n > 0 && !f->desc)) return fail(ORBFE_ERR_INVALID, "fuse_mappoints: bad key frame view");
+    for (int i = 0; i < f->n; i++)
+      if (chi2_gate && (f->octave[i] < 0 || f->octave[i] >= n_levels))
+        return fail(ORBFE_ERR_INVALID, "fuse_mappoints: keypoint octave outside the pyramid");
+    views.push_back(f);
+  }
+  if (n == 0 || n_keyframes == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  if (int rc = glock.table_ready()) return rc;
+  for (size_t i = 0; i < (size_t)n_keyframes * n; i++) best_idx[i] = -1;
+  FuseProducer P;
+  P.table = *lock.table; P.graph = glock.graph; P.slot = slot; P.skip = skip; P.pose = pose; P.kfSlot = kf_slot; P.n = n; P.K = n_keyframes;
+  P.scale = scale_factors; P.invSigma2 = inv_level_sigma2; P.nLevels = n_levels; P.th = th; P.gate = chi2_gate != 0;
+  P.projectedOut = projected;
+  std::vector<WindowJob> wj;
+  for (int k = 0; k < n_keyframes; k++) {
+    if (views[(size_t)k]->n == 0) continue;  // nothing to search: every best_idx of the key frame stays -1
+    WindowJob w;
+    w.f = views[(size_t)k]; w.nq = n;
+    w.bestOut = best_idx + (size_t)k * n;
+    w.gate = P.gate ? 1 : 0; w.nLevels = n_levels; w.maxDist = 50 /* TH_LOW */;
+    w.fuse = &P; w.fuseK = k;
+    wj.push_back(w);
+  }
+  if (wj.empty())  // K empty key frames: the prologue alone, if the caller asked for it
+    return projected ? project_fuse_run(lock.device, *lock.table, glock.graph, n, slot, n_keyframes, kf_slot, pose, skip, projected, nullptr,
+                                        nullptr, nullptr, nullptr, nullptr)
+                     : ORBFE_OK;
+  return window_search_multi(lock.device, wj.data(), (int)wj.size(), 8);
 }
 
 extern "C" int orbfe_search_by_sim3(int device, const orbfe_frame_view* KF1, const orbfe_frame_view* KF2,

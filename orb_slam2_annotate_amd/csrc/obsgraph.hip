@@ -134,6 +134,23 @@ int orbfe::obs_ready(orbfe_obsgraph* g) {
   return obs_flush(g);
 }
 
+// host_internal.h: the handle's serialisation for a scope, for a host file that reads the rows on the device
+orbfe::ObsGraphLock::ObsGraphLock(orbfe_obsgraph* g) {
+  if (!g) return;
+  g->m.lock();
+  held = g;
+  device = g->device; pointCap = g->h.pointCap; kfCap = g->h.kfCap;
+}
+orbfe::ObsGraphLock::~ObsGraphLock() {
+  if (held) held->m.unlock();
+}
+int orbfe::ObsGraphLock::table_ready() {
+  if (!held) return ORBFE_OK;
+  if (int rc = obs_ready(held)) return rc;
+  graph = &held->d;
+  return ORBFE_OK;
+}
+
 namespace {
 
 int invalid(const char* fn, const char* what) { return obs_invalid(fn, what); }

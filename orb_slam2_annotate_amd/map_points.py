@@ -115,6 +115,71 @@ class MapPoints:
                                                 C.byref(nm), ptr(in_view)))
         return nm.value, match[:F.N], in_view[:n]
 
+    def _fuse_operands(self, poses, slot, graph, kf_slot, skip):
+        """(K, n, slots, pose array, graph handle, kf slots, mask) of project_fuse / fuse."""
+        s = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        poses = list(poses)
+        K, n = len(poses), len(s)
+        pa = (CameraPoseC * max(K, 1))(*poses)
+        kf = None
+        if graph is not None:
+            if kf_slot is None:
+                raise ValueError("a graph needs the kf slots of the key frames")
+            kf = np.ascontiguousarray(kf_slot, dtype=np.int32).reshape(-1)
+            if len(kf) != K:
+                raise ValueError("kf_slot must hold one entry per pose")
+        k = None
+        if skip is not None:
+            k = np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+            if len(k) != K * n:
+                raise ValueError("skip must hold K * n entries")
+        return K, n, s, pa, (graph._h if graph is not None else None), kf, k
+
+    def project_fuse(self, poses, slot, graph=None, kf_slot=None, skip=None):
+        """The prologue of ORBmatcher::Fuse (src/ORBmatcher.cc:960-1006) for slot[] against the K key-frame poses
+        (orbfe_project_fuse) -> dict of valid (uint8), u, v, ur, dist (float32), level (int32), each [K, n]; the fields are
+        0 where valid is.  With `graph` a point that observes kf_slot[k] is rejected for pose k (IsInKeyFrame)."""
+        h = self._h
+        K, n, s, pa, gh, kf, k = self._fuse_operands(poses, slot, graph, kf_slot, skip)
+        q = max(K * n, 1)
+        flat = {"valid": np.zeros(q, np.uint8), "level": np.zeros(q, np.int32)}
+        for name in ("u", "v", "ur", "dist"):
+            flat[name] = np.zeros(q, np.float32)
+        check(self._L.orbfe_project_fuse(h, gh, n, ptr(s), K, ptr(kf), pa, ptr(k),
+                                         *[ptr(flat[f]) for f in ("valid", "u", "v", "ur", "level", "dist")]))
+        return {name: a[:K * n].reshape(K, n) for name, a in flat.items()}
+
+    def fuse(self, frames, poses, slot, graph=None, kf_slot=None, skip=None, th: float = 3.0, chi2_gate: bool = True,
+             scale_factors=None, inv_level_sigma2=None, return_projected: bool = False):
+        """ORBmatcher::Fuse for slot[] against K key frames (views or resident frames) in one call (orbfe_fuse_mappoints):
+        the projection, the windows and the search all on the device -> best_idx [K, n] (keypoint of key frame k for point
+        i, or -1); scale_factors = mvScaleFactors; with return_projected also the [K, n] mask of the points that passed the prologue.  chi2_gate=True is
+        Fuse(pKF, vpMapPoints, th) and needs inv_level_sigma2 = mvInvLevelSigma2; False is the Sim3 overload with the
+        caller's decomposition of Scw in the poses.  Replace / AddObservation / AddMapPoint stay with the caller, and the
+        results are those of the state at entry (include/orbfe.h)."""
+        h = self._h
+        frames = list(frames)
+        K, n, s, pa, gh, kf, k = self._fuse_operands(poses, slot, graph, kf_slot, skip)
+        if len(frames) != K:
+            raise ValueError("MapPoints.fuse: one pose per key frame")
+        if scale_factors is None:
+            raise ValueError("MapPoints.fuse: scale_factors (mvScaleFactors) is needed")
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        isg = None
+        if chi2_gate:
+            if inv_level_sigma2 is None:
+                raise ValueError("MapPoints.fuse: the chi-square gate needs inv_level_sigma2")
+            isg = np.ascontiguousarray(inv_level_sigma2, dtype=np.float32).reshape(-1)
+            if len(isg) != len(sf):
+                raise ValueError("MapPoints.fuse: inv_level_sigma2 must hold one entry per level")
+        views = (C.POINTER(_lib.FrameViewC) * max(K, 1))(*[C.pointer(f.c) for f in frames])
+        best = np.full(max(K * n, 1), -1, dtype=np.int32)
+        proj = np.zeros(max(K * n, 1), np.uint8) if return_projected else None
+        check(self._L.orbfe_fuse_mappoints(h, gh, n, ptr(s), K, views, ptr(kf), pa, ptr(k), ptr(sf), ptr(isg), len(sf), float(th),
+                                           int(bool(chi2_gate)), ptr(best), ptr(proj)))
+        best = best[:K * n].reshape(K, n)
+        return (best, proj[:K * n].reshape(K, n)) if return_projected else best
+
     def pose_optimization(self, frame, slot, match, pose, K5, inv_level_sigma2, outlier=None):
         """Optimizer::PoseOptimization on the table (orbfe_pose_optimization_mappoints): `match` is what SearchLocalPoints
         returned for `frame` and `slot`, `pose` the 4 x 4 mTcw, inv_level_sigma2 = mvInvLevelSigma2 -> (n_inliers, Tcw_out
