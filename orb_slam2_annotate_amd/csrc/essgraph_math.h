@@ -78,12 +78,6 @@ ORBFE_HD inline void ess_store(const OptSim3& S, double* rec8) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 3 x 3 helpers, row-major, every sum in index order
-ORBFE_HD inline void ess_mul3(const double A[9], const double B[9], double C[9]) {
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) C[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
-}
 ORBFE_HD inline void ess_mulv3(const double A[9], const double v[3], double o[3]) {
 #pragma unroll
   for (int r = 0; r < 3; r++) o[r] = (A[3 * r] * v[0] + A[3 * r + 1] * v[1]) + A[3 * r + 2] * v[2];
@@ -186,7 +180,7 @@ ORBFE_HD inline void essgraph_log_ex(const OptSim3& S, double out[7], EssLogBran
   ess_skew(w, Om);
 #pragma unroll
   for (int k = 0; k < 9; k++) BOm[k] = B * Om[k];
-  ess_mul3(BOm, Om, Om2);
+  g2o_mul3(BOm, Om, Om2);
 #pragma unroll
   for (int k = 0; k < 9; k++) W[k] = (A * Om[k] + Om2[k]) + C * (k % 4 == 0 ? 1.0 : 0.0);
   double u[3] = {S.t[0], S.t[1], S.t[2]};
@@ -249,7 +243,7 @@ ORBFE_HD inline void ess_log_jacobian(const OptSim3& E, const double e[7], const
   const double A = br.A, B = br.B;
   double Om[9], Om2[9], ux[9];
   ess_skew(w, Om);
-  ess_mul3(Om, Om, Om2);
+  g2o_mul3(Om, Om, Om2);
   ess_skew(u, ux);
   if (br.smallTheta) {
     const double tr = (br.R[0] + br.R[4]) + br.R[8];
@@ -285,7 +279,7 @@ ORBFE_HD inline void ess_log_jacobian(const OptSim3& E, const double e[7], const
   ess_mulv3(Om, u, ou);
   ess_mulv3(Om, ou, o2u);
   ess_skew(ou, oux);
-  ess_mul3(Om, ux, Oux);
+  g2o_mul3(Om, ux, Oux);
 #pragma unroll
   for (int i = 0; i < 9; i++) K[i] = -A * ux[i] - B * (oux[i] + Oux[i]);
   if (!br.smallTheta) {
@@ -294,7 +288,7 @@ ORBFE_HD inline void ess_log_jacobian(const OptSim3& E, const double e[7], const
 #pragma unroll
       for (int cc = 0; cc < 3; cc++) K[3 * rr + cc] = K[3 * rr + cc] + ((At * ou[rr] + Bt * o2u[rr]) * w[cc]) / theta;
   }
-  ess_mul3(K, P, KP);
+  g2o_mul3(K, P, KP);
   // W^-1 [ -K P | s R | -(A_s Omega u + B_s Omega^2 u + C_s u) ]
   double X[21];
 #pragma unroll
@@ -335,11 +329,11 @@ ORBFE_HD inline double ess_linearise_edge(const OptSim3& C, const OptSim3& Si, c
   double R[9], tx[9], txR[9], PR[9], QR[9], StxR[9], SR[9], St[3];
   g2o_quat_to_R(T.q, R);
   ess_skew(T.t, tx);
-  ess_mul3(tx, R, txR);
-  ess_mul3(P, R, PR);
-  ess_mul3(Q, R, QR);
-  ess_mul3(S, txR, StxR);
-  ess_mul3(S, R, SR);
+  g2o_mul3(tx, R, txR);
+  g2o_mul3(P, R, PR);
+  g2o_mul3(Q, R, QR);
+  g2o_mul3(S, txR, StxR);
+  g2o_mul3(S, R, SR);
   ess_mulv3(S, T.t, St);
   const double k6 = fixScale ? 0.0 : 1.0;
 #pragma unroll

@@ -21,6 +21,20 @@
 
 namespace orbfe {
 
+// 3 x 3, row-major.  C = A B with every entry summed left to right, as Eigen's product and cv's gemm do; T = M^T
+ORBFE_HD inline void g2o_mul3(const double A[9], const double B[9], double C[9]) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+}
+ORBFE_HD inline void g2o_transpose3(const double M[9], double T[9]) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) T[3 * i + j] = M[3 * j + i];
+}
+
 // Eigen::Quaterniond(Matrix3d) (Eigen/src/Geometry/Quaternion.h: quaternionbase_assign_impl<Other, 3, 3>); m row-major
 ORBFE_HD inline void g2o_quat_from_R(const double m[9], double q[4]) {
   double t = m[0] + m[4] + m[8];

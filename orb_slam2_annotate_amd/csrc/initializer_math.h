@@ -6,15 +6,12 @@
 // takes its null vector from cv::SVDecomp, so results agree with it to float rounding and are NOT bit-identical to it: a pair
 // within float rounding of a threshold may fall on the other side, and a score differs in its last float digits.
 //
-// The null vector comes from a one-sided (Hestenes) Jacobi iteration on the columns of the stacked matrix [A; V], which is what
-// cv::SVDecomp's JacobiSVDImpl_ does and which does not square the condition number as an eigen-solve of A^T A would.  The
-// matrix is held BY ROWS, one row of 9 doubles per owner: the device gives every lane of a wave one row (lanes 0-15 the rows
-// of A, lanes 16-24 the rows of V), the host programs hold all 25.  `Lanes` says who owns what and how a sum over the rows of
-// A and a broadcast are made; the arithmetic, the order of the additions included (a fixed xor butterfly), is the same.
+// The null vector comes from the one-sided Jacobi iteration of jacobi_math.h on the stacked matrix [A; V].  The matrix is held
+// BY ROWS, one row of 9 doubles per owner: the device gives every lane of a wave one row (lanes 0-15 the rows of A, lanes
+// 16-24 the rows of V), the host programs hold all 25.  `Lanes` says who owns what and how a sum over the rows of A and a
+// broadcast are made; the arithmetic, the order of the additions included (a fixed xor butterfly), is the same.
 //   * A has 16 rows.  For F only 8 are data and the other 8 are zero, which adds +0.0 to every sum: one code path, two models.
-//   * pair order of a sweep: (0,1) (0,2) ... (0,8) (1,2) ... (7,8), the 36 pairs with compile-time indices;
-//   * a pair is skipped -- its columns count as orthogonal -- when |a_p . a_q| <= DBL_EPSILON sqrt(|a_p|^2 |a_q|^2);
-//   * at most kInitMaxSweeps sweeps, until a sweep rotates nothing;
+//   * the 36 pairs of a sweep are unrolled, so every column index is a compile-time constant;
 //   * the null vector is the column of V under the column of A with the smallest squared norm (the first of equal ones).
 //
 // IEEE semantics the reference relies on are kept.  cv::Mat::inv() of a singular 3 x 3 matrix (determinant == 0) is the zero
@@ -25,14 +22,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "g2o_math.h"  // ORBFE_HD
+#include "jacobi_math.h"  // the one-sided iteration; g2o_mul3, g2o_transpose3, ORBFE_HD of g2o_math.h
 
 namespace orbfe {
 
 enum InitStatus { kInitOk = 0, kInitNonfinite = 1 };  // ORBFE_INIT_* of include/orbfe.h
 enum InitModel { kInitH = 0, kInitF = 1 };            // ORBFE_INIT_MODEL_*
 
-constexpr int kInitMaxSweeps = 30;
 constexpr int kInitARows = 16;   // rows of A (lanes 0-15)
 constexpr int kInitRows = 25;    // rows of [A; V] (V: lanes 16-24)
 constexpr double kInitThH = 5.991;       // :378
@@ -105,71 +101,27 @@ ORBFE_HD inline void init_fill_row(int model, int id, const float p[4], const do
   }
 }
 
-// one Hestenes rotation of the columns P, Q of every owned row
-#define ORBFE_INIT_ROTATE(P, Q)                                                                      \
-  {                                                                                                  \
-    double pa[L::kOwned], pb[L::kOwned], pg[L::kOwned];                                              \
-    _Pragma("unroll") for (int r = 0; r < L::kOwned; r++) {                                          \
-      pa[r] = m[r][P] * m[r][P]; pb[r] = m[r][Q] * m[r][Q]; pg[r] = m[r][P] * m[r][Q];               \
-    }                                                                                                \
-    const double al = ln.sum_a(pa), be = ln.sum_a(pb), ga = ln.sum_a(pg);                            \
-    if (fabs(ga) > DBL_EPSILON * sqrt(al * be)) {                                                    \
-      const double zeta = (be - al) / (2.0 * ga);                                                    \
-      const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));          \
-      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;                                           \
-      _Pragma("unroll") for (int r = 0; r < L::kOwned; r++) {                                        \
-        const double mp = m[r][P], mq = m[r][Q];                                                     \
-        m[r][P] = c * mp - s * mq;                                                                   \
-        m[r][Q] = s * mp + c * mq;                                                                   \
-      }                                                                                              \
-      rotated = 1;                                                                                   \
-    }                                                                                                \
-  }
-#define ORBFE_INIT_NORM(J)                                                                           \
-  {                                                                                                  \
-    double pa[L::kOwned], col[L::kOwned];                                                            \
-    _Pragma("unroll") for (int r = 0; r < L::kOwned; r++) { pa[r] = m[r][J] * m[r][J]; col[r] = m[r][J]; } \
-    const double n2 = ln.sum_a(pa);                                                                  \
-    if (J == 0 || n2 < best) {                                                                       \
-      best = n2;                                                                                     \
-      _Pragma("unroll") for (int i = 0; i < 9; i++) nv[i] = ln.pick(col, kInitARows + i);            \
-    }                                                                                                \
-  }
-
 // The right singular vector of the smallest singular value of A (the rows of m owned by rows 0-15; rows 16-24 hold V = I on
 // entry; m is destroyed): stands where the reference has vt.row(8) of cv::SVDecomp (:301-304, :334-336).  The sign is free:
 // it scales H (which cancels in the projections) and F (which cancels in num^2 / (a^2 + b^2)).  Every owner runs the same
-// control flow: the sums and hence c, s and `rotated` are the same for all.
+// control flow: the sums and hence c, s and whether a pair rotates are the same for all.
 template <class L>
 ORBFE_HD inline void init_null_vector(const L& ln, double (*m)[9], double nv[9]) {
-  for (int sweep = 0; sweep < kInitMaxSweeps; sweep++) {
-    int rotated = 0;
-    ORBFE_INIT_ROTATE(0, 1) ORBFE_INIT_ROTATE(0, 2) ORBFE_INIT_ROTATE(0, 3) ORBFE_INIT_ROTATE(0, 4)
-    ORBFE_INIT_ROTATE(0, 5) ORBFE_INIT_ROTATE(0, 6) ORBFE_INIT_ROTATE(0, 7) ORBFE_INIT_ROTATE(0, 8)
-    ORBFE_INIT_ROTATE(1, 2) ORBFE_INIT_ROTATE(1, 3) ORBFE_INIT_ROTATE(1, 4) ORBFE_INIT_ROTATE(1, 5)
-    ORBFE_INIT_ROTATE(1, 6) ORBFE_INIT_ROTATE(1, 7) ORBFE_INIT_ROTATE(1, 8)
-    ORBFE_INIT_ROTATE(2, 3) ORBFE_INIT_ROTATE(2, 4) ORBFE_INIT_ROTATE(2, 5) ORBFE_INIT_ROTATE(2, 6)
-    ORBFE_INIT_ROTATE(2, 7) ORBFE_INIT_ROTATE(2, 8)
-    ORBFE_INIT_ROTATE(3, 4) ORBFE_INIT_ROTATE(3, 5) ORBFE_INIT_ROTATE(3, 6) ORBFE_INIT_ROTATE(3, 7) ORBFE_INIT_ROTATE(3, 8)
-    ORBFE_INIT_ROTATE(4, 5) ORBFE_INIT_ROTATE(4, 6) ORBFE_INIT_ROTATE(4, 7) ORBFE_INIT_ROTATE(4, 8)
-    ORBFE_INIT_ROTATE(5, 6) ORBFE_INIT_ROTATE(5, 7) ORBFE_INIT_ROTATE(5, 8)
-    ORBFE_INIT_ROTATE(6, 7) ORBFE_INIT_ROTATE(6, 8)
-    ORBFE_INIT_ROTATE(7, 8)
-    if (!rotated) break;
-  }
+  const JacobiLaneRows<L, 9> rows = {ln, m};
+  jacobi_sweeps_unrolled<9>([&](int p, int q) { return jacobi_cols_pair(rows, p, q); }, JacobiOwnDone());
   double best = 0.0;
-  ORBFE_INIT_NORM(0) ORBFE_INIT_NORM(1) ORBFE_INIT_NORM(2) ORBFE_INIT_NORM(3) ORBFE_INIT_NORM(4)
-  ORBFE_INIT_NORM(5) ORBFE_INIT_NORM(6) ORBFE_INIT_NORM(7) ORBFE_INIT_NORM(8)
-}
-#undef ORBFE_INIT_ROTATE
-#undef ORBFE_INIT_NORM
-
-// C = A B, 3 x 3 row-major, each entry summed left to right as cv's gemm does
-ORBFE_HD inline void init_mul3(const double A[9], const double B[9], double C[9]) {
 #pragma unroll
-  for (int i = 0; i < 3; i++)
+  for (int j = 0; j < 9; j++) {
+    double col[L::kOwned];
 #pragma unroll
-    for (int j = 0; j < 3; j++) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
+    for (int r = 0; r < L::kOwned; r++) col[r] = m[r][j];
+    const double n2 = rows.dot(j, j);
+    if (j == 0 || n2 < best) {
+      best = n2;
+#pragma unroll
+      for (int i = 0; i < 9; i++) nv[i] = ln.pick(col, kInitARows + i);
+    }
+  }
 }
 
 // T of Normalize (:899-903)
@@ -202,43 +154,21 @@ ORBFE_HD inline void init_model_h(const double nv[9], const double t1[4], const 
   T2i[0] = 1.0 / t2[0]; T2i[1] = 0.0;         T2i[2] = t2[2];
   T2i[3] = 0.0;         T2i[4] = 1.0 / t2[1]; T2i[5] = t2[3];
   T2i[6] = 0.0;         T2i[7] = 0.0;         T2i[8] = 1.0;
-  init_mul3(T2i, nv, tmp);
-  init_mul3(tmp, T1, H21);
+  g2o_mul3(T2i, nv, tmp);
+  g2o_mul3(tmp, T1, H21);
   init_inv3(H21, H12);
 }
 
-#define ORBFE_INIT_ROT3(P, Q)                                                                        \
-  {                                                                                                  \
-    const double al = a[P] * a[P] + a[3 + P] * a[3 + P] + a[6 + P] * a[6 + P];                       \
-    const double be = a[Q] * a[Q] + a[3 + Q] * a[3 + Q] + a[6 + Q] * a[6 + Q];                       \
-    const double ga = a[P] * a[Q] + a[3 + P] * a[3 + Q] + a[6 + P] * a[6 + Q];                       \
-    if (fabs(ga) > DBL_EPSILON * sqrt(al * be)) {                                                    \
-      const double zeta = (be - al) / (2.0 * ga);                                                    \
-      const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));          \
-      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;                                           \
-      _Pragma("unroll") for (int r = 0; r < 3; r++) {                                                \
-        const double ap = a[3 * r + P], aq = a[3 * r + Q], vp = v[3 * r + P], vq = v[3 * r + Q];     \
-        a[3 * r + P] = c * ap - s * aq; a[3 * r + Q] = s * ap + c * aq;                              \
-        v[3 * r + P] = c * vp - s * vq; v[3 * r + Q] = s * vp + c * vq;                              \
-      }                                                                                              \
-      rotated = 1;                                                                                   \
-    }                                                                                                \
-  }
-
-// :339-344: the SVD of Fpre, the smallest singular value set to zero, recomposed.  One-sided Jacobi on the columns of a = Fpre
-// (pair order (0,1) (0,2) (1,2), the skip rule and the sweep cap above) leaves a = U diag(w), v = V, so that
-// Fpre = sum_j a_j v_j^T; the sum without the column of the smallest norm (the first of equal ones) is u diag(w') vt.
+// :339-344: the SVD of Fpre, the smallest singular value set to zero, recomposed.  The one-sided iteration on the columns of
+// a = Fpre leaves a = U diag(w), v = V, so that Fpre = sum_j a_j v_j^T; the sum without the column of the smallest norm (the
+// first of equal ones) is u diag(w') vt.
 ORBFE_HD inline void init_rank2(const double Fpre[9], double Fn[9]) {
   double a[9], v[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
 #pragma unroll
   for (int i = 0; i < 9; i++) a[i] = Fpre[i];
-  for (int sweep = 0; sweep < kInitMaxSweeps; sweep++) {
-    int rotated = 0;
-    ORBFE_INIT_ROT3(0, 1) ORBFE_INIT_ROT3(0, 2) ORBFE_INIT_ROT3(1, 2)
-    if (!rotated) break;
-  }
-  const double n0 = a[0] * a[0] + a[3] * a[3] + a[6] * a[6], n1 = a[1] * a[1] + a[4] * a[4] + a[7] * a[7];
-  const double n2 = a[2] * a[2] + a[5] * a[5] + a[8] * a[8];
+  jacobi_cols_fixed<3, 3>(a, v, JacobiOwnDone());
+  const JacobiCols<3> m = {a, v, 3};
+  const double n0 = m.dot(0, 0), n1 = m.dot(1, 1), n2 = m.dot(2, 2);
   int drop = 0;
   double best = n0;
   if (n1 < best) { best = n1; drop = 1; }
@@ -255,20 +185,16 @@ ORBFE_HD inline void init_rank2(const double Fpre[9], double Fn[9]) {
       Fn[3 * i + j] = f;
     }
 }
-#undef ORBFE_INIT_ROT3
 
 // :244: F21 = T2^T Fn T1 with Fn the rank-2 matrix of the null vector
 ORBFE_HD inline void init_model_f(const double nv[9], const double t1[4], const double t2[4], double F21[9]) {
   double T1[9], T2[9], T2t[9], Fn[9], tmp[9];
   init_T(t1, T1);
   init_T(t2, T2);
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) T2t[3 * i + j] = T2[3 * j + i];
+  g2o_transpose3(T2, T2t);
   init_rank2(nv, Fn);
-  init_mul3(T2t, Fn, tmp);
-  init_mul3(tmp, T1, F21);
+  g2o_mul3(T2t, Fn, tmp);
+  g2o_mul3(tmp, T1, F21);
 }
 
 // CheckHomography for one pair (:384-432): true = vbMatchesInliers[i]; *score receives the pair's terms in the reference's order

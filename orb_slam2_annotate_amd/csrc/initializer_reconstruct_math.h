@@ -6,27 +6,19 @@
 // operation after the lines cited.  The reference computes in CV_32F with cv::SVD: results agree with it to float rounding and
 // are NOT bit-identical to the CV_32F cv::SVD path.
 //
-// The 3 x 3 SVD A = U diag(w) V^T with full, proper U and V (recon_svd3):
-//   * one-sided (Hestenes) Jacobi on the columns of a = A V, pair order (0,1) (0,2) (1,2), a pair skipped when
-//     |a_p . a_q| <= DBL_EPSILON sqrt(|a_p|^2 |a_q|^2), at most kInitMaxSweeps sweeps, until a sweep rotates nothing (the rules
-//     of initializer_math.h);
-//   * the columns sorted by descending norm (a stable bubble of three compares: equal norms keep their order);
-//   * w_i = |a_i|, u_i = a_i / w_i for i = 0, 1;
-//   * u_2 = +-(u_0 x u_1), the sign that of (u_0 x u_1) . a_2 (a_2 = A v_2), + when that is 0.  E21 is rank 2 by construction:
-//     a_2 is rounding noise there and a_2 / |a_2| would be garbage; with this rule U is orthonormal, A = U diag(w) V^T holds
-//     and det(U) det(V) is that of a valid SVD.
-// The signs of (u_i, v_i) are free, as in any SVD; they permute the hypotheses (H: 0 <-> 2 and 1 <-> 3 within each group of
-// four; F: t <-> -t, R1 <-> R2) and leave the set unchanged.
+// The 3 x 3 SVD A = U diag(w) V^T with full, proper U and V is jacobi_svd3 of jacobi_math.h, which says how U is completed
+// for the rank-2 E21.  The signs of (u_i, v_i) are free, as in any SVD; they permute the hypotheses (H: 0 <-> 2 and 1 <-> 3
+// within each group of four; F: t <-> -t, R1 <-> R2) and leave the set unchanged.
 //
-// The 4 x 4 null vector of Triangulate (:829-842) is tri_null_vector of triangulate_math.h.  Every comparison of CheckRT is
-// written as the reference writes it, so that NaN falls through the same branches.
+// The 4 x 4 null vector of Triangulate (:829-842) is jacobi_null4 of jacobi_math.h, the very routine of the triangulation of
+// LocalMapping.  Every comparison of CheckRT is written as the reference writes it, so that NaN falls through the same branches.
 #pragma once
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
 
-#include "initializer_math.h"   // init_mul3, kInitMaxSweeps, kInitH / kInitF
-#include "triangulate_math.h"   // tri_null_vector
+#include "initializer_math.h"  // kInitH / kInitF
+#include "jacobi_math.h"       // jacobi_svd3, jacobi_null4; g2o_mul3, g2o_transpose3 of g2o_math.h
 
 namespace orbfe {
 
@@ -57,70 +49,8 @@ ORBFE_HD inline double recon_det3(const double M[9]) {
   return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
 }
 
-#define ORBFE_RECON_ROT3(P, Q)                                                                       \
-  {                                                                                                  \
-    const double al = a[P] * a[P] + a[3 + P] * a[3 + P] + a[6 + P] * a[6 + P];                       \
-    const double be = a[Q] * a[Q] + a[3 + Q] * a[3 + Q] + a[6 + Q] * a[6 + Q];                       \
-    const double ga = a[P] * a[Q] + a[3 + P] * a[3 + Q] + a[6 + P] * a[6 + Q];                       \
-    if (fabs(ga) > DBL_EPSILON * sqrt(al * be)) {                                                    \
-      const double zeta = (be - al) / (2.0 * ga);                                                    \
-      const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));          \
-      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;                                           \
-      _Pragma("unroll") for (int r = 0; r < 3; r++) {                                                \
-        const double ap = a[3 * r + P], aq = a[3 * r + Q], vp = v[3 * r + P], vq = v[3 * r + Q];     \
-        a[3 * r + P] = c * ap - s * aq; a[3 * r + Q] = s * ap + c * aq;                              \
-        v[3 * r + P] = c * vp - s * vq; v[3 * r + Q] = s * vp + c * vq;                              \
-      }                                                                                              \
-      rotated = 1;                                                                                   \
-    }                                                                                                \
-  }
-// columns P < Q of a and v change places when column P has the strictly smaller norm
-#define ORBFE_RECON_SORT(P, Q)                                                                       \
-  if (n[P] < n[Q]) {                                                                                 \
-    const double tn = n[P]; n[P] = n[Q]; n[Q] = tn;                                                  \
-    _Pragma("unroll") for (int r = 0; r < 3; r++) {                                                  \
-      const double ta = a[3 * r + P]; a[3 * r + P] = a[3 * r + Q]; a[3 * r + Q] = ta;                \
-      const double tv = v[3 * r + P]; v[3 * r + P] = v[3 * r + Q]; v[3 * r + Q] = tv;                \
-    }                                                                                                \
-  }
-
-// A = U diag(w) V^T (all row-major), w descending; see the head of the file.  Stands where the reference has
-// cv::SVD::compute(A, w, U, Vt, FULL_UV) (:673) and cv::SVD::compute(E, w, u, vt) (:1037).
-ORBFE_HD inline void recon_svd3(const double A[9], double U[9], double w[3], double V[9]) {
-  double a[9], v[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-#pragma unroll
-  for (int i = 0; i < 9; i++) a[i] = A[i];
-  for (int sweep = 0; sweep < kInitMaxSweeps; sweep++) {
-    int rotated = 0;
-    ORBFE_RECON_ROT3(0, 1) ORBFE_RECON_ROT3(0, 2) ORBFE_RECON_ROT3(1, 2)
-    if (!rotated) break;
-  }
-  double n[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) n[j] = a[j] * a[j] + a[3 + j] * a[3 + j] + a[6 + j] * a[6 + j];
-  ORBFE_RECON_SORT(0, 1) ORBFE_RECON_SORT(1, 2) ORBFE_RECON_SORT(0, 1)
-#pragma unroll
-  for (int j = 0; j < 3; j++) w[j] = sqrt(n[j]);
-  const double u0x = a[0] / w[0], u0y = a[3] / w[0], u0z = a[6] / w[0];
-  const double u1x = a[1] / w[1], u1y = a[4] / w[1], u1z = a[7] / w[1];
-  const double cx = u0y * u1z - u0z * u1y, cy = u0z * u1x - u0x * u1z, cz = u0x * u1y - u0y * u1x;
-  const double dot = cx * a[2] + cy * a[5] + cz * a[8];
-  const double sg = dot < 0.0 ? -1.0 : 1.0;
-  U[0] = u0x; U[1] = u1x; U[2] = sg * cx;
-  U[3] = u0y; U[4] = u1y; U[5] = sg * cy;
-  U[6] = u0z; U[7] = u1z; U[8] = sg * cz;
-#pragma unroll
-  for (int i = 0; i < 9; i++) V[i] = v[i];
-}
-#undef ORBFE_RECON_ROT3
-#undef ORBFE_RECON_SORT
-
-ORBFE_HD inline void recon_transpose3(const double M[9], double T[9]) {
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) T[3 * i + j] = M[3 * j + i];
-}
+// Stands where the reference has cv::SVD::compute(A, w, U, Vt, FULL_UV) (:673) and cv::SVD::compute(E, w, u, vt) (:1037)
+ORBFE_HD inline void recon_svd3(const double A[9], double U[9], double w[3], double V[9]) { jacobi_svd3(A, U, w, V); }
 
 // Hypothesis `hi` of ReconstructH (:667-775): 0-3 the case d' = d2, 4-7 the case d' = -d2, in the reference's index order
 // (x1 = {+,+,-,-} aux1, x3 = {+,-,+,-} aux3, stheta / sphi = {+,-,-,+} aux).  vn is never read by the reference and is not
@@ -131,10 +61,10 @@ ORBFE_HD inline bool recon_motion_h(const double H21[9], const float K4[4], int 
   const double K[9] = {fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0};
   const double invK[9] = {1.0 / fx, 0.0, -cx / fx, 0.0, 1.0 / fy, -cy / fy, 0.0, 0.0, 1.0};  // K.inv() in closed form (:667)
   double tmp[9], A[9], U[9], V[9], Vt[9], w[3];
-  init_mul3(invK, H21, tmp);
-  init_mul3(tmp, K, A);  // :668
+  g2o_mul3(invK, H21, tmp);
+  g2o_mul3(tmp, K, A);  // :668
   recon_svd3(A, U, w, V);
-  recon_transpose3(V, Vt);
+  g2o_transpose3(V, Vt);
   const double s = recon_det3(U) * recon_det3(V);  // :677
   const double d1 = w[0], d2 = w[1], d3 = w[2];
   if (d1 / d2 < kReconSvTh || d2 / d3 < kReconSvTh) return true;  // :684
@@ -158,8 +88,8 @@ ORBFE_HD inline bool recon_motion_h(const double H21[9], const float K4[4], int 
     tp[0] = x1 * (d1 + d3); tp[1] = 0.0 * (d1 + d3); tp[2] = x3 * (d1 + d3);  // :758-761
   }
   double URp[9], URpVt[9];
-  init_mul3(U, Rp, URp);
-  init_mul3(URp, Vt, URpVt);
+  g2o_mul3(U, Rp, URp);
+  g2o_mul3(URp, Vt, URpVt);
 #pragma unroll
   for (int k = 0; k < 9; k++) R[k] = s * URpVt[k];  // :716, :754
   const double tx = U[0] * tp[0] + U[1] * tp[1] + U[2] * tp[2];  // :725, :763
@@ -176,10 +106,10 @@ ORBFE_HD inline void recon_motion_f(const double F21[9], const float K4[4], int 
   const double K[9] = {fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0};
   const double Kt[9] = {fx, 0.0, 0.0, 0.0, fy, 0.0, cx, cy, 1.0};
   double tmp[9], E[9], U[9], V[9], Vt[9], w[3];
-  init_mul3(Kt, F21, tmp);
-  init_mul3(tmp, K, E);  // :546
+  g2o_mul3(Kt, F21, tmp);
+  g2o_mul3(tmp, K, E);  // :546
   recon_svd3(E, U, w, V);
-  recon_transpose3(V, Vt);
+  g2o_transpose3(V, Vt);
   const double nt = sqrt(U[2] * U[2] + U[5] * U[5] + U[8] * U[8]);  // :1040-1041
   const double sg = (hi & 2) ? -1.0 : 1.0;                          // :554-555
   t[0] = sg * (U[2] / nt); t[1] = sg * (U[5] / nt); t[2] = sg * (U[8] / nt);
@@ -187,8 +117,8 @@ ORBFE_HD inline void recon_motion_f(const double F21[9], const float K4[4], int 
   const double m = (hi & 1) ? -1.0 : 1.0;
   const double W[9] = {0.0, -m, 0.0, m, 0.0, 0.0, 0.0, 0.0, 1.0};
   double UW[9];
-  init_mul3(U, W, UW);
-  init_mul3(UW, Vt, R);  // :1048, :1054
+  g2o_mul3(U, W, UW);
+  g2o_mul3(UW, Vt, R);  // :1048, :1054
   if (recon_det3(R) < 0.0) {  // :1051-1052, :1055-1056
 #pragma unroll
     for (int k = 0; k < 9; k++) R[k] = -R[k];
@@ -249,7 +179,7 @@ ORBFE_HD inline int recon_pair(const ReconCam& c, const float p[4], double X[3],
     a[12 + j] = v2 * c.P2[8 + j] - c.P2[4 + j];
   }
   double h[4];
-  tri_null_vector(a, h);  // :840-841
+  jacobi_null4(a, h, JacobiWaveDone());  // :840-841 (sweeps end with the wave, as in k_triangulate)
   X[0] = h[0] / h[3]; X[1] = h[1] / h[3]; X[2] = h[2] / h[3];  // :842
   *cosParallax = 0.0;
   if (!isfinite(X[0]) || !isfinite(X[1]) || !isfinite(X[2])) return 0;  // :958-962

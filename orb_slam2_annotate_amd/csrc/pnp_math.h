@@ -11,17 +11,15 @@
 // places in LDS: nothing of it goes to scratch.
 //
 // The OpenCV calls have no arithmetic of their own here (the reference accepts any OpenCV >= 2.4.3).  They are restated:
-//   * cvSVD of the symmetric 3 x 3 PW0^T PW0 (:436) and of ABt (:689): recon_svd3 of initializer_reconstruct_math.h
-//     (one-sided cyclic Jacobi, singular values descending).  The sign of a singular-vector pair is free in any SVD, but
-//     the control points depend on it, so :436 gets a rule: every row of UCt has its component of largest magnitude (the
-//     first of equal ones) positive.
-//   * cvInvert(CV_SVD) of the 3 x 3 control-point matrix (:473): the pseudo-inverse V diag(1 / w) U^T from recon_svd3 with
+//   * cvSVD of the symmetric 3 x 3 PW0^T PW0 (:436) and of ABt (:689): jacobi_svd3 of jacobi_math.h (singular values
+//     descending).  The sign of a singular-vector pair is free in any SVD, but the control points depend on it, so :436
+//     gets a rule: every row of UCt has its component of largest magnitude (the first of equal ones) positive.
+//   * cvInvert(CV_SVD) of the 3 x 3 control-point matrix (:473): the pseudo-inverse V diag(1 / w) U^T from jacobi_svd3 with
 //     1 / w_i = 0 where w_i <= kPnpSvCut (w_0 + w_1 + w_2), kPnpSvCut = 2 DBL_EPSILON.
-//   * cvSolve(CV_SVD) of the 6 x 4, 6 x 3 and 6 x 5 systems (:781, :812, :846): least squares by one-sided Jacobi on the
-//     columns of [A; V] (pair order (p, q), p < q, row-major; the skip rule and sweep limit of initializer_math.h), then
-//     x = sum_j v_j (a_j . b) / |a_j|^2 over the columns with |a_j| > kPnpSvCut sum_k |a_k|.
-//   * cvSVD of the 12 x 12 M^T M for n >= 5 (:561): cyclic two-sided Jacobi, pair order (p, q), p < q, row-major, at most
-//     kPnpMaxSweeps sweeps, a pair skipped when |a_pq| <= DBL_EPSILON sqrt(|a_pp a_qq|); eigenvalues descending, ties by
+//   * cvSolve(CV_SVD) of the 6 x 4, 6 x 3 and 6 x 5 systems (:781, :812, :846): least squares by jacobi_math.h's one-sided
+//     iteration on the columns of [A; V], then x = sum_j v_j (a_j . b) / |a_j|^2 over the columns with
+//     |a_j| > kPnpSvCut sum_k |a_k|.
+//   * cvSVD of the 12 x 12 M^T M for n >= 5 (:561): jacobi_math.h's two-sided iteration; eigenvalues descending, ties by
 //     index; ut row 11 is the eigenvector of the smallest one.  NOT bit-identical to cv::SVD.
 //   * cvSVD of M^T M for n = 4 (the RANSAC minimal set): M is 8 x 12 and its null space has dimension >= 4, inside which an
 //     eigen-solver's basis is rounding noise.  DEVIATION: the basis is canonical instead -- Householder QR of M^T (12 x 8),
@@ -35,13 +33,12 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "initializer_reconstruct_math.h"  // recon_svd3, kInitMaxSweeps; ORBFE_HD
+#include "jacobi_math.h"  // jacobi_svd3 and both iterations; ORBFE_HD
 
 namespace orbfe {
 
 enum PnpStatus { kPnpOk = 0, kPnpNonfinite = 1 };  // ORBFE_PNP_* of include/orbfe.h
 
-constexpr int kPnpMaxSweeps = 30;
 constexpr double kPnpSvCut = 2.0 * DBL_EPSILON;
 
 // fu fv uc vc
@@ -80,7 +77,7 @@ ORBFE_HD inline double pnp_dist2(const double* p1, const double* p2) {  // :612
 // choose_control_points (:401-445) after its two sums: c0 = the centroid (sum / n, :410), cov = PW0^T PW0 row-major
 ORBFE_HD inline void pnp_control_points(const double c0[3], const double cov[9], int n, double cws[4][3]) {
   double U[9], w[3], V[9];
-  recon_svd3(cov, U, w, V);  // :436: dc = w, uct = U^T
+  jacobi_svd3(cov, U, w, V);  // :436: dc = w, uct = U^T
 #pragma unroll
   for (int j = 0; j < 3; j++) cws[0][j] = c0[j];
 #pragma unroll
@@ -102,7 +99,7 @@ ORBFE_HD inline void pnp_cc_inv(const double cws[4][3], double ci[9]) {
   for (int i = 0; i < 3; i++)
 #pragma unroll
     for (int j = 1; j < 4; j++) cc[3 * i + j - 1] = cws[j][i] - cws[0][i];  // :471
-  recon_svd3(cc, U, w, V);
+  jacobi_svd3(cc, U, w, V);
   const double cut = kPnpSvCut * (w[0] + w[1] + w[2]);
   double iw[3];
 #pragma unroll
@@ -136,34 +133,8 @@ ORBFE_HD inline void pnp_fill_M(const double as[4], double u, double v, const Pn
 ORBFE_HD inline void pnp_eig12(PnpWork* W) {
   double* a = W->a;
   double* v = W->v;
-  for (int i = 0; i < 144; i++) v[i] = 0.0;
-  for (int i = 0; i < 12; i++) v[13 * i] = 1.0;
-  for (int sweep = 0; sweep < kPnpMaxSweeps; sweep++) {
-    int rotated = 0;
-    for (int p = 0; p < 11; p++)
-      for (int q = p + 1; q < 12; q++) {
-        const double apq = a[12 * p + q], app = a[13 * p], aqq = a[13 * q];
-        if (!(fabs(apq) > DBL_EPSILON * sqrt(fabs(app * aqq)))) continue;
-        const double zeta = (aqq - app) / (2.0 * apq);
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        a[13 * p] = app - t * apq;
-        a[13 * q] = aqq + t * apq;
-        a[12 * p + q] = a[12 * q + p] = 0.0;
-        for (int r = 0; r < 12; r++) {
-          if (r != p && r != q) {
-            const double rp = a[12 * r + p], rq = a[12 * r + q];
-            a[12 * r + p] = a[12 * p + r] = c * rp - s * rq;
-            a[12 * r + q] = a[12 * q + r] = s * rp + c * rq;
-          }
-          const double vp = v[12 * r + p], vq = v[12 * r + q];
-          v[12 * r + p] = c * vp - s * vq;
-          v[12 * r + q] = s * vp + c * vq;
-        }
-        rotated = 1;
-      }
-    if (!rotated) break;
-  }
+  jacobi_identity(v, 12);
+  jacobi_sweeps(12, [&](int p, int q) { return jacobi_sym_pair(a, v, 12, p, q); });
   for (int i = 0; i < 12; i++) W->d[i] = a[13 * i];
   // descending, ties by index: the last row is the smallest eigenvalue, of equal ones the one with the highest index
   for (int k = 0; k < 4; k++) {
@@ -240,39 +211,13 @@ ORBFE_HD inline void pnp_L_and_rho(PnpWork* W) {
 ORBFE_HD inline void pnp_ls6(PnpWork* W, int m) {
   double* a = W->la;
   double* v = W->lv;
-  for (int i = 0; i < m * m; i++) v[i] = 0.0;
-  for (int i = 0; i < m; i++) v[(m + 1) * i] = 1.0;
-  for (int sweep = 0; sweep < kInitMaxSweeps; sweep++) {
-    int rotated = 0;
-    for (int p = 0; p < m - 1; p++)
-      for (int q = p + 1; q < m; q++) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-        for (int r = 0; r < 6; r++) {
-          al += a[m * r + p] * a[m * r + p];
-          be += a[m * r + q] * a[m * r + q];
-          ga += a[m * r + p] * a[m * r + q];
-        }
-        if (!(fabs(ga) > DBL_EPSILON * sqrt(al * be))) continue;
-        const double zeta = (be - al) / (2.0 * ga);
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-        for (int r = 0; r < 6; r++) {
-          const double ap = a[m * r + p], aq = a[m * r + q];
-          a[m * r + p] = c * ap - s * aq; a[m * r + q] = s * ap + c * aq;
-        }
-        for (int r = 0; r < m; r++) {
-          const double vp = v[m * r + p], vq = v[m * r + q];
-          v[m * r + p] = c * vp - s * vq; v[m * r + q] = s * vp + c * vq;
-        }
-        rotated = 1;
-      }
-    if (!rotated) break;
-  }
+  const JacobiCols<6> cols = {a, v, m};
+  jacobi_identity(v, m);
+  jacobi_sweeps(m, [&](int p, int q) { return jacobi_cols_pair(cols, p, q); });
   double* n2 = W->d;  // (free here: pnp_eig12 / pnp_null4 are done with it)
   double sumw = 0.0;
   for (int j = 0; j < m; j++) {
-    double s2 = 0.0;
-    for (int r = 0; r < 6; r++) s2 += a[m * r + j] * a[m * r + j];
+    const double s2 = cols.dot(j, j);
     n2[j] = s2;
     sumw += sqrt(s2);
   }
@@ -418,7 +363,7 @@ ORBFE_HD inline void pnp_solve_for_sign(PnpWork* W, const double pc_first[3]) {
 // estimate_R_and_t (:648-710) after its sums: pc0, pw0 the centroids (sums / n), abt row-major
 ORBFE_HD inline void pnp_estimate_R_and_t(const double pc0[3], const double pw0[3], const double abt[9], double R[9], double t[3]) {
   double U[9], w[3], V[9];
-  recon_svd3(abt, U, w, V);
+  jacobi_svd3(abt, U, w, V);
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll

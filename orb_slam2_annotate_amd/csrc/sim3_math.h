@@ -3,8 +3,8 @@
 // device, tests/cpp/sim3_cpu.cpp and tests/cpp/sim3_host_san.cpp for the host.  Plain C++ without a HIP include.  Arithmetic
 // is binary64 on inputs widened from float (build with -ffp-contract=off).  The reference computes in CV_32F with cv::eigen
 // and cv::Rodrigues, so results agree with it to float rounding and are NOT bit-identical to it; a pair within float rounding
-// of its maxErr may fall on the other side.  Everything is written with compile-time indices so that the 4 x 4 matrices stay
-// in registers on the device.
+// of its maxErr may fall on the other side.  Every index is a compile-time constant (after unrolling, in jacobi_math.h's
+// iteration) so that the 4 x 4 matrices stay in registers on the device.
 //
 // IEEE semantics the reference relies on are kept: two identical point sets make row 0 of N (0 off the diagonal), the
 // eigenvector is (+-1, 0, 0, 0), |vec| = 0, the reference divides by it (:310) and everything downstream is NaN, so that
@@ -16,13 +16,11 @@
 #include <float.h>
 #include <math.h>
 
-#include "g2o_math.h"  // ORBFE_HD
+#include "jacobi_math.h"  // jacobi_sym_pair; ORBFE_HD
 
 namespace orbfe {
 
 enum Sim3Status { kSim3Ok = 0, kSim3Nonfinite = 1 };  // ORBFE_SIM3_* of include/orbfe.h
-
-constexpr int kSim3MaxSweeps = 30;
 
 // what one hypothesis yields: R12 row-major, t12, s12 and the two transforms the inlier test reads
 struct Sim3Transform {
@@ -44,58 +42,19 @@ struct Sim3Candidate {
   Sim3Camera K1, K2;
 };
 
-#define ORBFE_SIM3_ROT1(m, I, J) { const double mp = m[I], mq = m[J]; m[I] = c * mp - s * mq; m[J] = s * mp + c * mq; }
-// the entries a[R][P], a[R][Q] of a row R that is neither P nor Q, and their mirror images
-#define ORBFE_SIM3_SIDE(P, Q, R)                                              \
-  {                                                                           \
-    const double rp = a[4 * R + P], rq = a[4 * R + Q];                        \
-    a[4 * R + P] = a[4 * P + R] = c * rp - s * rq;                            \
-    a[4 * R + Q] = a[4 * Q + R] = s * rp + c * rq;                            \
-  }
-// one Jacobi rotation of the symmetric 4 x 4 `a` (row-major, both triangles kept) in the plane (P, Q) -- R, S are the other
-// two indices -- and of the columns P, Q of `v`; skipped -- the entry counts as zero -- when
-// |a_pq| <= DBL_EPSILON sqrt(|a_pp a_qq|)
-#define ORBFE_SIM3_ROTATE(P, Q, R, S)                                                                     \
-  do {                                                                                                    \
-    const double apq = a[4 * P + Q], app = a[5 * P], aqq = a[5 * Q];                                      \
-    if (fabs(apq) > DBL_EPSILON * sqrt(fabs(app * aqq))) {                                                \
-      const double zeta = (aqq - app) / (2.0 * apq);                                                      \
-      const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));               \
-      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;                                                \
-      a[5 * P] = app - t * apq;                                                                           \
-      a[5 * Q] = aqq + t * apq;                                                                           \
-      a[4 * P + Q] = a[4 * Q + P] = 0.0;                                                                  \
-      ORBFE_SIM3_SIDE(P, Q, R) ORBFE_SIM3_SIDE(P, Q, S)                                                   \
-      ORBFE_SIM3_ROT1(v, P, Q) ORBFE_SIM3_ROT1(v, 4 + P, 4 + Q) ORBFE_SIM3_ROT1(v, 8 + P, 8 + Q) ORBFE_SIM3_ROT1(v, 12 + P, 12 + Q) \
-      rotated = 1;                                                                                        \
-    }                                                                                                     \
-  } while (0)
-
-// The eigenvector of the largest eigenvalue of the symmetric 4 x 4 `a` (row-major; destroyed): cyclic Jacobi, pair order
-// (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), at most kSim3MaxSweeps sweeps, until a sweep rotates nothing.  The vector is the
-// column of V under the largest diagonal entry (the first of equal ones).  Stands where the reference has evec.row(0) of
-// cv::eigen (:300); the sign is free and cancels in sim3_rotation.
+// The eigenvector of the largest eigenvalue of the symmetric 4 x 4 `a` (row-major; destroyed): the column of V under the
+// largest diagonal entry (the first of equal ones) after jacobi_math.h's two-sided iteration.  Stands where the reference has
+// evec.row(0) of cv::eigen (:300); the sign is free and cancels in sim3_rotation.
 ORBFE_HD inline void sim3_top_eigenvector(double a[16], double q[4]) {
-  double v[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-  for (int sweep = 0; sweep < kSim3MaxSweeps; sweep++) {
-    int rotated = 0;
-    ORBFE_SIM3_ROTATE(0, 1, 2, 3);
-    ORBFE_SIM3_ROTATE(0, 2, 1, 3);
-    ORBFE_SIM3_ROTATE(0, 3, 1, 2);
-    ORBFE_SIM3_ROTATE(1, 2, 0, 3);
-    ORBFE_SIM3_ROTATE(1, 3, 0, 2);
-    ORBFE_SIM3_ROTATE(2, 3, 0, 1);
-    if (!rotated) break;
-  }
+  double v[16];
+  jacobi_identity(v, 4);
+  jacobi_sweeps_unrolled<4>([&](int p, int k) { return jacobi_sym_pair(a, v, 4, p, k); }, JacobiOwnDone());
   double best = a[0];
   q[0] = v[0]; q[1] = v[4]; q[2] = v[8]; q[3] = v[12];
   if (a[5] > best) { best = a[5]; q[0] = v[1]; q[1] = v[5]; q[2] = v[9]; q[3] = v[13]; }
   if (a[10] > best) { best = a[10]; q[0] = v[2]; q[1] = v[6]; q[2] = v[10]; q[3] = v[14]; }
   if (a[15] > best) { best = a[15]; q[0] = v[3]; q[1] = v[7]; q[2] = v[11]; q[3] = v[15]; }
 }
-#undef ORBFE_SIM3_ROTATE
-#undef ORBFE_SIM3_SIDE
-#undef ORBFE_SIM3_ROT1
 
 // :302-314: the rotation from the quaternion the reference's way -- angle-axis, then cv::Rodrigues' formula
 // R = cos(theta) I + (1 - cos(theta)) r r^T + sin(theta) [r]x -- so that q and -q give the same R (atan2 sees the sign of

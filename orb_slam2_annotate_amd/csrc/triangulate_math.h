@@ -1,20 +1,13 @@
 // triangulate_math.h -- the per-pair arithmetic of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:338-481), written
 // once: k_triangulate.hip compiles it for the device, tests/cpp/triangulate_cpu.cpp for the host.  Plain C++ without a HIP
 // include.  Arithmetic is binary64 on inputs widened from float (build with -ffp-contract=off); the reference computes in
-// CV_32F with cv::SVD, so results agree with it to float rounding, not bit for bit.  Everything is written with compile-time
-// indices so that the 4 x 4 matrices stay in registers on the device.
+// CV_32F with cv::SVD, so results agree with it to float rounding, not bit for bit.  Every index is a compile-time
+// constant (after unrolling, in jacobi_math.h's 4 x 4 form) so that the 4 x 4 matrices stay in registers on the device.
 #pragma once
 #include <float.h>
 #include <math.h>
 
-#include "g2o_math.h"  // ORBFE_HD
-// the sweep loop of tri_null_vector ends when no lane of the wave rotated anything (a lane that is done rotates nothing in
-// further sweeps, so its result does not depend on its neighbours); on the host the "wave" is the one pair
-#if defined(__HIP_DEVICE_COMPILE__)
-#define ORBFE_TRI_ALL(x) __all(x)
-#else
-#define ORBFE_TRI_ALL(x) (x)
-#endif
+#include "jacobi_math.h"  // jacobi_null4; ORBFE_HD
 
 namespace orbfe {
 
@@ -48,54 +41,10 @@ struct TriangulatePair {
   float xraw1, yraw1, xraw2, yraw2;  // mvKeys[i].pt
 };
 
-constexpr int kTriMaxSweeps = 30;
-
-// one Hestenes rotation of columns P, Q of the 4 x 4 `a` (row-major) and of `v`; skipped -- the columns count as orthogonal
-// -- when |a_p . a_q| <= DBL_EPSILON sqrt(|a_p|^2 |a_q|^2)
-#define ORBFE_TRI_ROTATE(P, Q)                                                                                   \
-  do {                                                                                                           \
-    const double al = a[P] * a[P] + a[4 + P] * a[4 + P] + a[8 + P] * a[8 + P] + a[12 + P] * a[12 + P];           \
-    const double be = a[Q] * a[Q] + a[4 + Q] * a[4 + Q] + a[8 + Q] * a[8 + Q] + a[12 + Q] * a[12 + Q];           \
-    const double ga = a[P] * a[Q] + a[4 + P] * a[4 + Q] + a[8 + P] * a[8 + Q] + a[12 + P] * a[12 + Q];           \
-    if (fabs(ga) > DBL_EPSILON * sqrt(al * be)) {                                                                \
-      const double zeta = (be - al) / (2.0 * ga);                                                                \
-      const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));                      \
-      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;                                                       \
-      ORBFE_TRI_ROT1(a, P, Q) ORBFE_TRI_ROT1(a, 4 + P, 4 + Q) ORBFE_TRI_ROT1(a, 8 + P, 8 + Q) ORBFE_TRI_ROT1(a, 12 + P, 12 + Q) \
-      ORBFE_TRI_ROT1(v, P, Q) ORBFE_TRI_ROT1(v, 4 + P, 4 + Q) ORBFE_TRI_ROT1(v, 8 + P, 8 + Q) ORBFE_TRI_ROT1(v, 12 + P, 12 + Q) \
-      rotated = 1;                                                                                               \
-    }                                                                                                            \
-  } while (0)
-#define ORBFE_TRI_ROT1(m, I, J) { const double mp = m[I], mq = m[J]; m[I] = c * mp - s * mq; m[J] = s * mp + c * mq; }
-
-// The right singular vector of the smallest singular value of the 4 x 4 `a` (row-major; destroyed): one-sided Jacobi, pair
-// order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), at most kTriMaxSweeps sweeps, until a sweep rotates nothing.  The vector is
-// the column of V under the column of A V with the smallest norm (the first of equal ones).  Stands where the reference has
-// vt.row(3) of cv::SVD::compute (:378-380); the sign is free and cancels in x / w.
-ORBFE_HD inline void tri_null_vector(double a[16], double x[4]) {
-  double v[16] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-  for (int sweep = 0; sweep < kTriMaxSweeps; sweep++) {
-    int rotated = 0;
-    ORBFE_TRI_ROTATE(0, 1);
-    ORBFE_TRI_ROTATE(0, 2);
-    ORBFE_TRI_ROTATE(0, 3);
-    ORBFE_TRI_ROTATE(1, 2);
-    ORBFE_TRI_ROTATE(1, 3);
-    ORBFE_TRI_ROTATE(2, 3);
-    if (ORBFE_TRI_ALL(!rotated)) break;
-  }
-  const double n0 = a[0] * a[0] + a[4] * a[4] + a[8] * a[8] + a[12] * a[12];
-  const double n1 = a[1] * a[1] + a[5] * a[5] + a[9] * a[9] + a[13] * a[13];
-  const double n2 = a[2] * a[2] + a[6] * a[6] + a[10] * a[10] + a[14] * a[14];
-  const double n3 = a[3] * a[3] + a[7] * a[7] + a[11] * a[11] + a[15] * a[15];
-  double best = n0;
-  x[0] = v[0]; x[1] = v[4]; x[2] = v[8]; x[3] = v[12];
-  if (n1 < best) { best = n1; x[0] = v[1]; x[1] = v[5]; x[2] = v[9]; x[3] = v[13]; }
-  if (n2 < best) { best = n2; x[0] = v[2]; x[1] = v[6]; x[2] = v[10]; x[3] = v[14]; }
-  if (n3 < best) { best = n3; x[0] = v[3]; x[1] = v[7]; x[2] = v[11]; x[3] = v[15]; }
-}
-#undef ORBFE_TRI_ROTATE
-#undef ORBFE_TRI_ROT1
+// The right singular vector of the smallest singular value of the 4 x 4 `a` (row-major; destroyed): stands where the
+// reference has vt.row(3) of cv::SVD::compute (:378-380); the sign is free and cancels in x / w.  The iteration is
+// jacobi_math.h's; its sweep loop ends with the wave (JacobiWaveDone).
+ORBFE_HD inline void tri_null_vector(double a[16], double x[4]) { jacobi_null4(a, x, JacobiWaveDone()); }
 
 // KeyFrame::UnprojectStereo (src/KeyFrame.cc:658-674): reads the RAW keypoint position (mvKeys); Twc = [Rcw^T | Ow].  The
 // callers hand in a depth > 0 (the host checks refuse others: the reference would return an empty matrix there)

@@ -75,14 +75,14 @@ Call make(int n) {
   const double Kd[9] = {512.0, 0.0, 256.0, 0.0, 512.0, 256.0, 0.0, 0.0, 1.0};
   const double Ki[9] = {1.0 / 512.0, 0.0, -0.5, 0.0, 1.0 / 512.0, -0.5, 0.0, 0.0, 1.0};
   double Kit[9], E[9], a[9], F[9], Hc[9], H[9];
-  recon_transpose3(Ki, Kit);
-  init_mul3(Tx, R, E);
-  init_mul3(Kit, E, a);
-  init_mul3(a, Ki, F);
+  g2o_transpose3(Ki, Kit);
+  g2o_mul3(Tx, R, E);
+  g2o_mul3(Kit, E, a);
+  g2o_mul3(a, Ki, F);
   for (int i = 0; i < 9; i++) Hc[i] = R[i];
   Hc[2] += tx / 4.0;  // R + t n^T / d, n = (0, 0, 1), d = 4
-  init_mul3(Kd, Hc, a);
-  init_mul3(a, Ki, H);
+  g2o_mul3(Kd, Hc, a);
+  g2o_mul3(a, Ki, H);
   c.model.insert(c.model.end(), F, F + 9);
   c.model.insert(c.model.end(), H, H + 9);
   c.model.insert(c.model.end(), F, F + 9);
