@@ -5,7 +5,7 @@
 //
 // Two ways in, each of which begins the arena anew (what an earlier call of the thread left in it is gone):
 //   arena_stage(device, &ar, stage)    a call that carves: up() / up_pack() / up_fill() / carve() inside `stage`, then
-//                                      flush(), the launches, down_range(), a synchronisation, mirror_of()
+//                                      flush(), the launches, down_span() / down_range(), a synchronisation, mirror_of()
 //   arena_stream(device, &ar)          ar->stream alone
 // State and the non-templates: arena.hip.
 #pragma once
@@ -35,6 +35,9 @@ struct Arena {
   PinBuf<uint8_t> hmirror;
   size_t dirtyLo = 0, dirtyHi = 0;
   bool sizing = false;  // arena_stage()'s first pass: carve() only advances `used`, the up*() calls write nothing
+  struct OutSpan {
+    size_t lo = 0, hi = 0;  // arena offsets: the start of the first output, the end of the last (not rounded up)
+  } out;                    // open_span() / close_span() / down_span()
   ~Arena() {  // (thread exit; the buffers free themselves behind this, on the device set here)
     if (device >= 0) {
       (void)hipSetDevice(device);
@@ -100,6 +103,15 @@ hipError_t up_fill(Arena* a, T** d, size_t n, int byteValue) {
 // results: ONE device-to-host copy of the arena range [first, last) into the pinned mirror (same offsets), to be read
 // through mirror_of() after the stream is synchronised -- instead of one pageable copy per output array
 hipError_t down_range(Arena* a, const void* first, const void* last);
+// The outputs of a call, carved next to each other: `stage` opens the arena's span before its first output carve and closes
+// it after its last, down_span() is then the one copy back.  The span is what was carved, so an output added inside it
+// travels without anyone restating where the range ends.
+inline void open_span(Arena* a) { a->out.lo = (a->used + 255) & ~(size_t)255; }  // where carve() puts the next array
+inline hipError_t close_span(Arena* a) {
+  a->out.hi = a->used;
+  return a->sizing ? hipSuccess : grow_mirror(a, a->out.hi);  // the mirror reaches the outputs before flush() reads from it
+}
+inline hipError_t down_span(Arena* a) { return down_range(a, a->base + a->out.lo, a->base + a->out.hi); }
 template <typename T>
 const T* mirror_of(Arena* a, const T* d) {
   return reinterpret_cast<const T*>(a->hmirror + (reinterpret_cast<const uint8_t*>(d) - a->base));

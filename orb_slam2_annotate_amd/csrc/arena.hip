@@ -37,6 +37,7 @@ hipError_t arena_begin(int device, size_t bytes, Arena** out) {
   }
   a.used = 0;
   a.dirtyLo = a.dirtyHi = 0;
+  a.out = {};
   *out = &a;
   return hipSuccess;
 }

@@ -42,13 +42,14 @@ int run(const char* who, int device, int K, int N, int H, const int32_t* pair_of
     TRY(up(a, &dh, hypProb.data(), hypProb.size()));
     TRY(up(a, &ds, sets, (size_t)H * 8));
     TRY(up(a, &dx, pairs, (size_t)N * 4));
-    A.score = carve<double>(a, (size_t)H * 2);  // the outputs adjacent: one copy back; the kernel writes every element
+    open_span(a);  // the outputs adjacent: one copy back; the kernel writes every element
+    A.score = carve<double>(a, (size_t)H * 2);
     A.model = carve<double>(a, (size_t)H * 18);
     A.h12 = carve<double>(a, (size_t)H * 9);
     A.nInliers = carve<int32_t>(a, (size_t)H * 2);
     A.words = carve<uint32_t>(a, words ? words : 1);
     A.status = carve<uint8_t>(a, (size_t)H * 2);
-    if (!a->sizing) TRY(grow_mirror(a, a->used));  // the mirror reaches the outputs before flush() reads from it
+    TRY(close_span(a));
     A.nHyp = H;
     A.probs = dp; A.hypProb = dh; A.sets = ds; A.pairs = dx;
     return hipSuccess;
@@ -57,7 +58,7 @@ int run(const char* who, int device, int K, int N, int H, const int32_t* pair_of
   HIPCHK(flush(ar));
   launch_initializer(ar->stream, A);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.score, A.status + 2 * (size_t)H));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   std::memcpy(score, mirror_of(ar, A.score), (size_t)H * 2 * sizeof(double));
   std::memcpy(model, mirror_of(ar, A.model), (size_t)H * 18 * sizeof(double));
@@ -96,7 +97,8 @@ int run_reconstruct(const char* who, int device, int K, int N, int W, const int3
     TRY(up(a, &dx, pairs, (size_t)N * 4));
     TRY(up(a, &dw, inlier_words, (size_t)W));
     A.keys = carve<uint64_t>(a, slots ? slots : 1);
-    A.R = carve<double>(a, G * 9);  // the outputs adjacent: one copy back; the kernel writes every element
+    open_span(a);  // the outputs adjacent: one copy back; the kernel writes every element
+    A.R = carve<double>(a, G * 9);
     A.t = carve<double>(a, G * 3);
     A.cosSel = carve<double>(a, G);
     A.x3d = carve<double>(a, slots ? slots * 3 : 1);
@@ -105,7 +107,7 @@ int run_reconstruct(const char* who, int device, int K, int N, int W, const int3
     A.hypStatus = carve<uint8_t>(a, G);
     A.pairFlags = carve<uint8_t>(a, slots ? slots : 1);
     A.problemStatus = carve<uint8_t>(a, (size_t)K);
-    if (!a->sizing) TRY(grow_mirror(a, a->used));  // the mirror reaches the outputs before flush() reads from it
+    TRY(close_span(a));
     A.nHyp = (int)G;
     A.probs = dp; A.hypProb = dh; A.pairs = dx; A.words = dw;
     return hipSuccess;
@@ -114,7 +116,7 @@ int run_reconstruct(const char* who, int device, int K, int N, int W, const int3
   HIPCHK(flush(ar));
   launch_init_reconstruct(ar->stream, A);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.R, A.problemStatus + (size_t)K));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   std::memcpy(R, mirror_of(ar, A.R), G * 9 * sizeof(double));
   std::memcpy(t, mirror_of(ar, A.t), G * 3 * sizeof(double));

@@ -1,6 +1,8 @@
-// initializer_host.h -- the host side of orbfe_initializer_ransac* (initializer.hip) that needs no device: the argument
-// checks, the layout of a call (problem records, the problem of every set, the mask-word offsets) and the two pure host
-// functions orbfe_initializer_normalize / orbfe_initializer_sets_from_draws.  Plain C++ without a HIP include, so
+// initializer_host.h -- the host side of orbfe_initializer_ransac* and orbfe_initializer_reconstruct* (initializer.hip) that
+// needs no device: the argument checks, the problem records of the layouts and the two pure host functions
+// orbfe_initializer_normalize / orbfe_initializer_sets_from_draws.  What the three RANSAC solvers share (offsets check, set
+// predicate, layout walk, selection without replacement) is ransac_host.h; recon_layout keeps its own loop, because there
+// the item counts are not given but follow from model_kind and hyp_off is an output.  Plain C++ without a HIP include, so
 // tests/cpp/initializer_host_san.cpp runs exactly this code under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <math.h>
@@ -11,33 +13,26 @@
 
 #include "initializer_math.h"
 #include "initializer_reconstruct_math.h"
+#include "ransac_host.h"
 
 namespace orbfe {
 
-constexpr int kInitHostMaxProblems = 4096;
 constexpr int kInitHostMaxSets = 1 << 24;  // 2 waves per set: the launch stays far below 2^31 waves
-
-inline bool init_offsets_ok(const int32_t* off, int K, int total) {
-  if (off[0] != 0 || off[K] != total) return false;
-  for (int k = 0; k < K; k++)
-    if (off[k + 1] < off[k]) return false;
-  return true;
-}
 
 // NULL when the arguments are fine, else what is wrong with them.  N pairs and H sets in all.
 inline const char* init_check(int K, int N, int H, const int32_t* pair_off, const float* pairs, const double* T1, const double* T2,
                               const float* sigma, const int32_t* hyp_off, const int32_t* sets, const double* score,
                               const uint8_t* status, const int32_t* n_inliers, const double* model, const double* h12,
                               const uint32_t* mask_words, const int32_t* word_off) {
-  if (K < 0 || K > kInitHostMaxProblems) return "n_problems outside [0, 4096]";
+  if (K < 0 || K > kRansacMaxOwners) return "n_problems outside [0, 4096]";
   if (N < 0 || H < 0) return "negative count";
   if (H > kInitHostMaxSets) return "more than 2^24 sets";
   if (!pair_off || !hyp_off || !word_off) return "NULL offsets";
   if (K > 0 && (!T1 || !T2 || !sigma)) return "NULL T1 / T2 / sigma";
   if (N > 0 && !pairs) return "NULL pair array";
   if (H > 0 && (!sets || !score || !status || !n_inliers || !model || !h12 || !mask_words)) return "NULL set or output array";
-  if (!init_offsets_ok(pair_off, K, N)) return "pair_off is not monotone from 0 to n_pairs";
-  if (!init_offsets_ok(hyp_off, K, H)) return "hyp_off is not monotone from 0 to n_sets";
+  if (!offsets_ok(pair_off, K, N)) return "pair_off is not monotone from 0 to n_pairs";
+  if (!offsets_ok(hyp_off, K, H)) return "hyp_off is not monotone from 0 to n_sets";
   size_t words = 0;
   for (int k = 0; k < K; k++) {
     for (int i = 0; i < 4; i++)
@@ -48,13 +43,11 @@ inline const char* init_check(int K, int N, int H, const int32_t* pair_off, cons
     for (int h = h0; h < h1; h++) {
       const int32_t* s = sets + 8 * (size_t)h;
       for (int j = 0; j < 8; j++) {
-        if (s[j] < 0 || s[j] >= n) return "set index outside [0, n_k)";
-        for (int i = 0; i < j; i++)
-          if (s[i] == s[j]) return "set repeats an index";
+        if (set_index_outside(s, j, n)) return "set index outside [0, n_k)";
+        if (set_index_repeats(s, j)) return "set repeats an index";
       }
     }
-    words += 2 * (size_t)(h1 - h0) * (size_t)((n + 31) / 32);
-    if (words > (size_t)INT32_MAX) return "more than 2^31 - 1 mask words";
+    if (!add_mask_words(&words, 2, h1 - h0, n)) return kTooManyMaskWords;  // an H and an F mask per set
   }
   return nullptr;
 }
@@ -63,20 +56,15 @@ inline const char* init_check(int K, int N, int H, const int32_t* pair_off, cons
 inline void init_layout(int K, const int32_t* pair_off, const int32_t* hyp_off, const double* T1, const double* T2,
                         const float* sigma, int32_t* word_off, std::vector<InitProblem>* probs, std::vector<int32_t>* hypProb) {
   probs->clear();
-  hypProb->clear();
-  word_off[0] = 0;
-  for (int k = 0; k < K; k++) {
+  layout_walk(K, pair_off, hyp_off, 2, word_off, hypProb, [&](int k, int n, int words) {  // an H and an F mask per set
     InitProblem p = {};
-    p.pair0 = pair_off[k]; p.nPairs = pair_off[k + 1] - pair_off[k];
+    p.pair0 = pair_off[k]; p.nPairs = n;
     p.hyp0 = hyp_off[k];
-    p.word0 = word_off[k]; p.words = (p.nPairs + 31) / 32;
+    p.word0 = word_off[k]; p.words = words;
     p.sigma = sigma[k];
     for (int i = 0; i < 4; i++) { p.T1[i] = T1[4 * k + i]; p.T2[i] = T2[4 * k + i]; }
     probs->push_back(p);
-    const int h = hyp_off[k + 1] - hyp_off[k];
-    hypProb->insert(hypProb->end(), (size_t)h, k);
-    word_off[k + 1] = word_off[k] + 2 * h * p.words;
-  }
+  });
 }
 
 // orbfe_initializer_reconstruct*: NULL when the arguments are fine, else what is wrong with them.  N pairs and W inlier words
@@ -87,7 +75,7 @@ inline const char* recon_check(int K, int N, int W, const int32_t* pair_off, con
                                const double* t, const int32_t* n_good, const double* cos_sel, const uint8_t* hyp_status,
                                const double* x3d, const uint8_t* pair_flags, const uint8_t* problem_status,
                                const int32_t* n_inliers) {
-  if (K < 0 || K > kInitHostMaxProblems) return "n_problems outside [0, 4096]";
+  if (K < 0 || K > kRansacMaxOwners) return "n_problems outside [0, 4096]";
   if (N < 0 || W < 0 || N > INT32_MAX - 31) return "count negative or above 2^31 - 32";
   if (!pair_off || !in_word_off || !hyp_off || !slot_off) return "NULL offsets";
   if (K > 0 && (!model_kind || !model || !K4 || !sigma || !R || !t || !n_good || !cos_sel || !hyp_status || !problem_status ||
@@ -95,8 +83,8 @@ inline const char* recon_check(int K, int N, int W, const int32_t* pair_off, con
     return "NULL problem or output array";
   if (N > 0 && !pairs) return "NULL pair array";
   if (W > 0 && !inlier_words) return "NULL inlier words";
-  if (!init_offsets_ok(pair_off, K, N)) return "pair_off is not monotone from 0 to n_pairs";
-  if (!init_offsets_ok(in_word_off, K, W)) return "in_word_off is not monotone from 0 to n_words";
+  if (!offsets_ok(pair_off, K, N)) return "pair_off is not monotone from 0 to n_pairs";
+  if (!offsets_ok(in_word_off, K, W)) return "in_word_off is not monotone from 0 to n_words";
   size_t slots = 0;
   for (int k = 0; k < K; k++) {
     if (model_kind[k] != kInitH && model_kind[k] != kInitF) return "model_kind is neither ORBFE_INIT_MODEL_H nor _F";
@@ -157,33 +145,8 @@ inline bool init_normalize(int n, const float* xy, double T[4]) {
   return true;
 }
 
-// The selection without replacement of Initializer::Initialize (:93-108) for H sets over n pairs: draws[8 h + j] is the value
-// RandomInt(0, vAvailableIndices.size() - 1) returned (:100) with size = n - j, the index INTO the list of still available
-// pairs; the pair taken leaves the list by swap-with-back and pop (:105-106).  The list starts as 0 .. n-1 for every set (:95).
-// The random stream itself is the caller's.  false: n < 8 with sets, a NULL array or a draw outside [0, n - j); sets is then
-// unspecified.
-inline bool init_sets_from_draws(int n, int H, const int32_t* draws, int32_t* sets) {
-  if (H == 0) return n >= 0;
-  if (n < 8 || H < 0 || !draws || !sets) return false;
-  std::vector<int32_t> avail((size_t)n);
-  for (int i = 0; i < n; i++) avail[i] = i;
-  for (int h = 0; h < H; h++) {
-    int32_t at[8], was[8];
-    int size = n, done = 0;
-    bool ok = true;
-    for (int j = 0; j < 8; j++) {
-      const int32_t r = draws[8 * (size_t)h + j];
-      ok = r >= 0 && r < size;
-      if (!ok) break;
-      sets[8 * (size_t)h + j] = avail[r];  // :101-103
-      at[done] = r; was[done] = avail[r]; done++;
-      avail[r] = avail[size - 1];          // :105
-      size--;                              // :106
-    }
-    for (int i = done - 1; i >= 0; i--) avail[at[i]] = was[i];  // the list of the next set is whole again (:95)
-    if (!ok) return false;
-  }
-  return true;
-}
+// Initializer::Initialize's selection without replacement (ransac_host.h, S = 8); false: n < 8 with sets, a NULL array or a
+// draw outside [0, n - j)
+inline bool init_sets_from_draws(int n, int H, const int32_t* draws, int32_t* sets) { return sets_from_draws<8>(n, H, draws, sets); }
 
 }  // namespace orbfe

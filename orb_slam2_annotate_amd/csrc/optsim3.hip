@@ -35,17 +35,18 @@ int run_multi(int device, int K, const int32_t* pair_off, const float* x3dc1, co
     TRY(up_pack(a, &dB, (size_t)N, [&](float4* h) { optsim3_pack_pairs_b(&h->x, N, x3dc2, w2); }));
     TRY(up_pack(a, &dC, (size_t)N, [&](float4* h) { optsim3_pack_pairs_c(&h->x, N, obs1, obs2); }));
     A.prob = dp; A.pairA = dA; A.pairB = dB; A.pairC = dC;
-    A.res = carve<OptSim3Result>(a, (size_t)K);  // the four outputs adjacent: one copy back
+    open_span(a);  // the four outputs adjacent: one copy back
+    A.res = carve<OptSim3Result>(a, (size_t)K);
     A.bad = carve<uint8_t>(a, n1);
     A.chi12 = carve<double>(a, n1);
     A.chi21 = carve<double>(a, n1);
-    return a->sizing ? hipSuccess : grow_mirror(a, a->used);  // the mirror reaches the outputs before flush() reads from it
+    return close_span(a);
   };
   HIPCHK(arena_stage(device, &ar, stage));
   HIPCHK(flush(ar));
   launch_optimize_sim3(ar->stream, A, K);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.res, A.chi21 + n1));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   const OptSim3Result* hr = mirror_of(ar, A.res);
   const uint8_t* hb = mirror_of(ar, A.bad);

@@ -57,11 +57,12 @@ int round_trip(int device, const Points& P, int I, const int32_t* item_off, cons
     TRY(up(a, &d3, P.p3d, (size_t)P.N * 3));
     TRY(up(a, &d2, P.p2d, (size_t)P.N * 2));
     TRY(up(a, &de, P.max_err2, (size_t)P.N));
-    A.nInliers = carve<int32_t>(a, (size_t)I);  // the four outputs adjacent: one copy back; the kernel writes every element
+    open_span(a);  // the four outputs adjacent: one copy back; the kernel writes every element
+    A.nInliers = carve<int32_t>(a, (size_t)I);
     A.pose = carve<float>(a, (size_t)I * 12);
     A.words = carve<uint32_t>(a, words ? words : 1);
     A.status = carve<uint8_t>(a, (size_t)I);
-    if (!a->sizing) TRY(grow_mirror(a, a->used));  // the mirror reaches the outputs before flush() reads from it
+    TRY(close_span(a));
     A.nItems = I;
     A.cands = dc; A.itemCand = dh; A.sets = ds; A.idxOff = dio; A.idx = di;
     A.p3d = d3; A.p2d = d2; A.maxErr2 = de;
@@ -72,7 +73,7 @@ int round_trip(int device, const Points& P, int I, const int32_t* item_off, cons
   if (sets) launch_pnp_ransac(ar->stream, A);
   else launch_pnp_refine(ar->stream, A);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.nInliers, A.status + I));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   std::memcpy(O.n_inliers, mirror_of(ar, A.nInliers), (size_t)I * 4);
   std::memcpy(O.pose, mirror_of(ar, A.pose), (size_t)I * 12 * sizeof(float));

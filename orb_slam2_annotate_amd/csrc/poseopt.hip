@@ -65,16 +65,17 @@ int run_batch(int device, int Q, const int32_t* offsets, const float* xw, const 
     TRY(up_problems(a, &A, Q, offsets, K5, Tcw_in));
     TRY(up_pack(a, &A.edgeA, (size_t)N, [&](float4* h) { poseopt_pack_edges_a(&h->x, N, xw, inv_sigma2); }));
     TRY(up_pack(a, &A.edgeB, (size_t)N, [&](float4* h) { poseopt_pack_edges_b(&h->x, N, u, v, u_right); }));
-    A.res = carve<PoseOptResult>(a, (size_t)Q);  // the three outputs adjacent: one copy back
+    open_span(a);  // the three outputs adjacent: one copy back
+    A.res = carve<PoseOptResult>(a, (size_t)Q);
     A.level = carve<uint8_t>(a, n1);
     A.chi2 = carve<double>(a, n1);
-    return a->sizing ? hipSuccess : grow_mirror(a, a->used);  // the mirror reaches the outputs before flush() reads from it
+    return close_span(a);
   };
   HIPCHK(arena_stage(device, &ar, stage));
   HIPCHK(flush(ar));
   launch_pose_optimize(ar->stream, A, Q, maxN <= kPoseOptLdsEdges);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.res, A.chi2 + n1));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   const PoseOptResult* hr = mirror_of(ar, A.res);
   const uint8_t* hl = mirror_of(ar, A.level);
@@ -146,18 +147,19 @@ extern "C" int orbfe_pose_optimization_mappoints(orbfe_mappoints* mp, int n_slot
     TRY(up(a, &dlv, inv_level_sigma2, (size_t)n_levels));
     A.edgeA = carve<float4>(a, n1);  // the kernel writes the edges itself: they never travel
     A.edgeB = carve<float4>(a, n1);
-    A.res = carve<PoseOptResult>(a, 1);  // the four outputs adjacent: one copy back
+    open_span(a);  // the four outputs adjacent: one copy back
+    A.res = carve<PoseOptResult>(a, 1);
     A.level = carve<uint8_t>(a, n1);
     A.chi2 = carve<double>(a, n1);
     A.edgeFeat = carve<int32_t>(a, n1);
     A.slot = ds; A.match = dm; A.featX = dx; A.featY = dy; A.featUr = dur; A.featOctave = doct; A.invLevelSigma2 = dlv;
-    return a->sizing ? hipSuccess : grow_mirror(a, a->used);  // the mirror reaches the outputs before flush() reads from it
+    return close_span(a);
   };
   HIPCHK(arena_stage(lock.device, &ar, stage));
   HIPCHK(flush(ar));
   launch_pose_optimize(ar->stream, A, 1, nf <= kPoseOptLdsEdges);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.res, A.edgeFeat + n1));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   const PoseOptResult* hr = mirror_of(ar, A.res);
   std::memcpy(Tcw_out, hr->Tcw, 16 * sizeof(float));

@@ -44,11 +44,12 @@ int run(const char* who, int device, int K, int N, int H, const int32_t* pair_of
     TRY(up(a, &d2, x3dc2, (size_t)N * 3));
     TRY(up(a, &e1, max_err1, (size_t)N));
     TRY(up(a, &e2, max_err2, (size_t)N));
-    A.nInliers = carve<int32_t>(a, (size_t)H);  // the four outputs adjacent: one copy back; the kernel writes every element
+    open_span(a);  // the four outputs adjacent: one copy back; the kernel writes every element
+    A.nInliers = carve<int32_t>(a, (size_t)H);
     A.sim3 = carve<float>(a, (size_t)H * 13);
     A.words = carve<uint32_t>(a, words ? words : 1);
     A.status = carve<uint8_t>(a, (size_t)H);
-    if (!a->sizing) TRY(grow_mirror(a, a->used));  // the mirror reaches the outputs before flush() reads from it
+    TRY(close_span(a));
     A.nHyp = H; A.fixScale = fix_scale ? 1 : 0;
     A.cands = dc; A.hypCand = dh; A.triples = dt;
     A.x3dc1 = d1; A.x3dc2 = d2; A.maxErr1 = e1; A.maxErr2 = e2;
@@ -58,7 +59,7 @@ int run(const char* who, int device, int K, int N, int H, const int32_t* pair_of
   HIPCHK(flush(ar));
   launch_sim3(ar->stream, A);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.nInliers, A.status + H));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   std::memcpy(n_inliers, mirror_of(ar, A.nInliers), (size_t)H * 4);
   std::memcpy(sim3, mirror_of(ar, A.sim3), (size_t)H * 13 * sizeof(float));

@@ -79,10 +79,12 @@ int run(const char* who, int device, const orbfe_frame_view* KF1, const orbfe_ke
     TRY(up(a, &dsg, level_sigma2, (size_t)n_levels));
     TriangulateFrame* dframes = carve<TriangulateFrame>(a, frames.size());  // (device addresses: known once the frames are carved)
     TRY(put(a, dframes, frames.data(), frames.size()));
-    TRY(up_fill(a, &A.x3d, slots * 3, 0));  // the four outputs adjacent: one copy back
+    open_span(a);  // the four outputs adjacent: one copy back
+    TRY(up_fill(a, &A.x3d, slots * 3, 0));
     TRY(up_fill(a, &A.status, slots, 0));
     TRY(up_fill(a, &A.nCreated, (size_t)K, 0));
     TRY(up_fill(a, &A.winner, (size_t)n1, 0x7f));
+    TRY(close_span(a));
     A.pairs = dpairs; A.nPairs = (int)pairs.size(); A.n1 = n1;
     A.frames = dframes; A.cams = dcams; A.scaleFactors = dsf; A.levelSigma2 = dsg; A.ratioFactor = ratio_factor;
     return hipSuccess;
@@ -93,7 +95,7 @@ int run(const char* who, int device, const orbfe_frame_view* KF1, const orbfe_ke
   HIPCHK(flush(ar));
   launch_triangulate(ar->stream, A);
   HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, A.x3d, A.winner + n1));
+  HIPCHK(down_span(ar));
   HIPCHK(hipStreamSynchronize(ar->stream));
   frames_settle();
   std::memcpy(x3d, mirror_of(ar, A.x3d), slots * 3 * sizeof(float));
