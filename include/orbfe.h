@@ -693,6 +693,77 @@ int orbfe_search_local_points(orbfe_mappoints *mp, int n, const int32_t *slot, c
                               const float *scale_factors, int n_levels, const uint8_t *blocked, float th, float nnratio,
                               int32_t *match, int32_t *n_matches, uint8_t *in_view);
 
+/* The prologue of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1516-1550), the search
+ * Tracking::TrackWithMotionModel runs on every frame, for a COMPACT list: slot[i] / last_octave[i] / skip[i] name only the
+ * last-frame features that hold a non-outlier map point (:1510-1514), in ascending feature order -- the claim loop depends on
+ * that order.  pose = the current frame's (motion-model) pose.  Outputs hold n entries; any may be NULL.  valid[i] = the point
+ * passes every test; where it is set, u / v / inv_z / ur / radius are the projection, 1/zc, u - mbf/zc and the window radius;
+ * elsewhere they are 0.  IEEE binary32, no contraction, sums left to right, in this order:
+ *   reject skip[i] (NULL = none); flags & ORBFE_MP_BAD is NOT tested -- the reference asks pMP and mvbOutlier[i] only;
+ *   xc = ((R00*X + R01*Y) + R02*Z) + t0 (yc, zc likewise); invz = 1/zc (the reference's 1.0/z in double, rounded to float, is
+ *   the same float quotient: 53 >= 2*24 + 2); reject invz < 0; u = (fx*xc)*invz + cx; v = (fy*yc)*invz + cy;
+ *   keep only u >= min_x && u <= max_x && v >= min_y && v <= max_y -- the bounds are inclusive.  This differs from the
+ *   reference's four rejects (u < min_x || u > max_x, v likewise) only for a NaN coordinate (zc == 0 with xc == 0), which is
+ *   rejected here; the reference would pass it on to GetFeaturesInArea, whose float-to-int conversions are then undefined;
+ *   ur = u - mbf*invz; radius = th * scale_factors[last_octave].
+ * mode selects the levels searched, as for orbfe_search_by_projection_last_frame: 0 [octave-1, octave+1], 1 (bForward)
+ * >= octave, 2 (bBackward) <= octave; the caller computes it from tlc (:1497-1506).  Only the slot list, the mask, the
+ * octaves, the pose and the level table go up.  A slot outside the table (-1 included), an octave outside [0, n_levels),
+ * pose->n_levels outside 1 .. min(64, n_levels), n < 0, a mode other than 0 / 1 / 2 and NULL slot / last_octave / pose /
+ * scale_factors return ORBFE_ERR_INVALID before anything is enqueued; n == 0 is ORBFE_OK with nothing touched. */
+int orbfe_project_last_frame(orbfe_mappoints *mp, int n, const int32_t *slot, const uint8_t *skip /* [n] or NULL */,
+                             const int32_t *last_octave, const orbfe_camera_pose *pose, const float *scale_factors, int n_levels,
+                             float th, int mode, uint8_t *valid, float *u, float *v, float *inv_z, float *ur, float *radius);
+
+/* SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1484-1633) as ONE call: the projection above
+ * writes the query windows of orbfe_search_by_projection_last_frame (centre (u, v), radius, the level range of `mode`, ur for
+ * the stereo check of :1567-1573 when Cur has u_right), gathers the points' descriptors from the table and takes
+ * obs_positive from flags bit ORBFE_MP_OBSERVED; the window search and the claim loop (TH_HIGH, the rotation histogram with
+ * last_angle[i] = LastFrame.mvKeysUn[.].angle) run behind it on the same stream.  One upload (slot list, mask, octaves,
+ * angles, pose, level table, blocked), one download.  match_cur[i2] = POSITION IN slot[] of the point given to feature i2 of
+ * Cur, or -1 -- what orbfe_pose_optimization_mappoints takes with the same slot[], so the two chain without repacking;
+ * *n_matches as the reference counts them; valid_out (optional, n bytes) = the points that were searched.  Cur may be a
+ * host view or a resident frame.  blocked as for orbfe_search_by_projection_last_frame (NULL = none).  Equal to
+ * orbfe_search_by_projection_last_frame fed with orbfe_project_last_frame's outputs, the table's descriptors and
+ * obs_positive = flags bit 1, bit for bit.  Beyond orbfe_project_last_frame's checks: a bad Cur, NULL match_cur / n_matches
+ * and -- with check_orientation -- NULL angles return ORBFE_ERR_INVALID before anything is enqueued.
+ * What stays with the caller: mode from tlc, the retry with 2*th when fewer than 20 matches come back
+ * (src/Tracking.cc:969-973), and everything behind the pose optimisation (:985-1010). */
+int orbfe_search_last_frame_mappoints(orbfe_mappoints *mp, int n, const int32_t *slot, const uint8_t *skip,
+                                      const int32_t *last_octave, const float *last_angle, const orbfe_camera_pose *pose,
+                                      const orbfe_frame_view *Cur, const float *scale_factors, int n_levels,
+                                      const uint8_t *blocked, int mode, float th, int check_orientation, int32_t *match_cur,
+                                      int32_t *n_matches, uint8_t *valid_out /* [n] or NULL */);
+
+/* The prologue of ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1665-1699,
+ * Tracking::Relocalization) for n_candidates (<= 64) jobs in ONE kernel launch.  Job k owns entries [offsets[k],
+ * offsets[k+1]) of the concatenated slot[] / skip[] -- pKF_k's non-null map points in feature order, skip = sAlreadyFound --
+ * and pose[k], the current frame's pose for that candidate.  offsets[0] = 0; offsets never descend; a job may be empty.
+ * Outputs hold offsets[n_candidates] entries; any may be NULL; where valid is 0 the others are 0.  In this order:
+ *   reject flags & ORBFE_MP_BAD; reject skip[i] (NULL = none); xc, yc, zc, invz, u, v and the inclusive image test as for
+ *   orbfe_project_last_frame -- there is NO depth-sign test, the reference has none; PO = P - Ow;
+ *   dist = (float)sqrt(sum (double)PO_i^2); reject dist < 0.8f*min || dist > 1.2f*max; no viewing-angle test;
+ *   level = clamp(ceil(log((double)(max/dist)) / (double)log_scale_factor), 0, n_levels-1) (MapPoint::PredictScale).
+ * A slot outside the table, n_candidates outside 0 .. 64, offsets that do not start at 0 or descend, a pose whose n_levels is
+ * not 1 .. 64 and NULL offsets / slot / pose return ORBFE_ERR_INVALID before anything is enqueued; n_candidates == 0 or no
+ * point at all is ORBFE_OK with nothing touched. */
+int orbfe_project_keyframe(orbfe_mappoints *mp, int n_candidates, const int32_t *offsets /* [n_candidates + 1] */,
+                           const int32_t *slot, const uint8_t *skip, const orbfe_camera_pose *pose /* [n_candidates] */,
+                           uint8_t *valid, float *u, float *v, float *inv_z, int32_t *level, float *dist);
+
+/* The relocalisation search for K candidates as ONE call: the projection above writes the windows of
+ * orbfe_search_by_projection_keyframe_multi (radius th[k] * scale_factors[level], levels [level-1, level+1]) and gathers the
+ * descriptors; the K window searches and claim loops (bound orb_dist[k], blocked[k] = Cur.mvpMapPoints[i2] != NULL at entry,
+ * blocked or blocked[k] may be NULL, kf_angle[i] = pKF_k->mvKeysUn[.].angle over the concatenated list) follow in one launch
+ * each.  match_cur[k*Cur->n + i2] = position in job k's part of slot[] (0 = offsets[k]) or -1; n_matches[k].  Equal to K
+ * calls of orbfe_search_by_projection_keyframe fed with orbfe_project_keyframe's outputs and the table's descriptors, bit for
+ * bit.  pose[k].n_levels must not exceed n_levels. */
+int orbfe_search_keyframe_mappoints_multi(orbfe_mappoints *mp, const orbfe_frame_view *Cur, const float *scale_factors,
+                                          int n_levels, int n_candidates, const int32_t *offsets, const int32_t *slot,
+                                          const uint8_t *skip, const float *kf_angle, const orbfe_camera_pose *pose,
+                                          const uint8_t *const *blocked, const float *th, const int32_t *orb_dist,
+                                          int check_orientation, int32_t *match_cur, int32_t *n_matches);
+
 /* ------------------------------------------------------------------------- */
 /* Optimizer::PoseOptimization (src/Optimizer.cc:256-473)                     */
 /* ------------------------------------------------------------------------- */

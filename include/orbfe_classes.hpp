@@ -908,6 +908,102 @@ class MapPointTable {
     if (projected) projected->resize(K * n);
     return best;
   }
+  // the prologue of SearchByProjection(CurrentFrame, LastFrame, th, bMono) for the compact list slot[] / lastOctave[]
+  // (orbfe_project_last_frame); the fields are 0 where valid is
+  struct LastFrameProjection {
+    std::vector<uint8_t> valid;
+    std::vector<float> u, v, invZ, ur, radius;
+  };
+  LastFrameProjection ProjectLastFrame(const std::vector<int32_t>& slot, const std::vector<int32_t>& lastOctave,
+                                       const orbfe_camera_pose& pose, const std::vector<float>& mvScaleFactors, float th, int mode = 0,
+                                       const std::vector<uint8_t>& skip = {}) const {
+    const size_t n = slot.size();
+    if (lastOctave.size() != n || (!skip.empty() && skip.size() != n))
+      throw std::invalid_argument("MapPointTable::ProjectLastFrame: one octave (and skip entry) per slot");
+    LastFrameProjection p;
+    p.valid.assign(n + 1, 0);
+    for (std::vector<float>* a : {&p.u, &p.v, &p.invZ, &p.ur, &p.radius}) a->assign(n + 1, 0.0f);
+    check(orbfe_project_last_frame(h_, (int)n, slot.data(), skip.empty() ? nullptr : skip.data(), lastOctave.data(), &pose,
+                                   mvScaleFactors.data(), (int)mvScaleFactors.size(), th, mode, p.valid.data(), p.u.data(), p.v.data(),
+                                   p.invZ.data(), p.ur.data(), p.radius.data()), "MapPointTable::ProjectLastFrame");
+    p.valid.resize(n);
+    for (std::vector<float>* a : {&p.u, &p.v, &p.invZ, &p.ur, &p.radius}) a->resize(n);
+    return p;
+  }
+  // SearchByProjection(CurrentFrame, LastFrame, th, bMono) in one call (orbfe_search_last_frame_mappoints): slot[] names the
+  // last frame's features with a non-outlier map point in ascending order, lastOctave / lastAngle their mvKeysUn; mode from
+  // tlc (0 / 1 bForward / 2 bBackward).  match[i2] = position in slot[] of the point given to keypoint i2 of Cur, or -1 -- the
+  // `match` of PoseOptimization below.  Returns nmatches; the 2 * th retry and the bookkeeping behind stay with the caller.
+  int SearchByProjectionLastFrame(const FrameArrays& Cur, const std::vector<int32_t>& slot, const std::vector<int32_t>& lastOctave,
+                                  const std::vector<float>& lastAngle, const orbfe_camera_pose& pose,
+                                  const std::vector<float>& mvScaleFactors, float th, int mode, std::vector<int32_t>& match,
+                                  bool checkOrientation = true, const std::vector<uint8_t>& skip = {},
+                                  const std::vector<uint8_t>& blocked = {}, std::vector<uint8_t>* valid = nullptr) const {
+    const size_t n = slot.size();
+    if (lastOctave.size() != n || (checkOrientation && lastAngle.size() != n) || (!skip.empty() && skip.size() != n))
+      throw std::invalid_argument("MapPointTable::SearchByProjectionLastFrame: one octave, angle (and skip entry) per slot");
+    if (!blocked.empty() && blocked.size() != (size_t)Cur.c.n)
+      throw std::invalid_argument("MapPointTable::SearchByProjectionLastFrame: one blocked entry per keypoint");
+    match.assign((size_t)Cur.c.n + 1, -1);
+    if (valid) valid->assign(n + 1, 0);
+    int32_t nmatches = 0;
+    check(orbfe_search_last_frame_mappoints(h_, (int)n, slot.data(), skip.empty() ? nullptr : skip.data(), lastOctave.data(),
+                                            checkOrientation ? lastAngle.data() : nullptr, &pose, &Cur.c, mvScaleFactors.data(),
+                                            (int)mvScaleFactors.size(), blocked.empty() ? nullptr : blocked.data(), mode, th,
+                                            checkOrientation ? 1 : 0, match.data(), &nmatches, valid ? valid->data() : nullptr),
+          "MapPointTable::SearchByProjectionLastFrame");
+    match.resize((size_t)Cur.c.n);
+    if (valid) valid->resize(n);
+    return nmatches;
+  }
+  // the prologue of SearchByProjection(CurrentFrame, pKF_k, sAlreadyFound, th, ORBdist) for K candidates in one launch
+  // (orbfe_project_keyframe): candidate k owns entries [offsets[k], offsets[k + 1]) of slot / skip and pose[k]
+  struct KeyFrameProjection {
+    std::vector<uint8_t> valid;
+    std::vector<float> u, v, invZ, dist;
+    std::vector<int32_t> level;
+  };
+  KeyFrameProjection ProjectKeyFrames(const std::vector<int32_t>& offsets, const std::vector<int32_t>& slot,
+                                      const std::vector<orbfe_camera_pose>& pose, const std::vector<uint8_t>& skip = {}) const {
+    const size_t K = pose.size(), n = slot.size();
+    if (offsets.size() != K + 1 || (size_t)offsets.back() != n || (!skip.empty() && skip.size() != n))
+      throw std::invalid_argument("MapPointTable::ProjectKeyFrames: K + 1 offsets that end at the number of slots");
+    KeyFrameProjection p;
+    p.valid.assign(n + 1, 0); p.level.assign(n + 1, 0);
+    for (std::vector<float>* a : {&p.u, &p.v, &p.invZ, &p.dist}) a->assign(n + 1, 0.0f);
+    check(orbfe_project_keyframe(h_, (int)K, offsets.data(), slot.data(), skip.empty() ? nullptr : skip.data(), pose.data(),
+                                 p.valid.data(), p.u.data(), p.v.data(), p.invZ.data(), p.level.data(), p.dist.data()),
+          "MapPointTable::ProjectKeyFrames");
+    p.valid.resize(n); p.level.resize(n);
+    for (std::vector<float>* a : {&p.u, &p.v, &p.invZ, &p.dist}) a->resize(n);
+    return p;
+  }
+  // Tracking::Relocalization's SearchByProjection for K candidates in one call (orbfe_search_keyframe_mappoints_multi):
+  // match[k * Cur.n + i2] = position in candidate k's part of slot[] or -1; nMatches[k].  kfAngle: pKF_k->mvKeysUn[.].angle
+  // over the concatenated list; blocked: empty, or K * Cur.n bytes (Cur.mvpMapPoints[i2] != NULL at the entry of call k).
+  std::vector<int32_t> SearchByProjectionKeyFrames(const FrameArrays& Cur, const std::vector<int32_t>& offsets,
+                                                   const std::vector<int32_t>& slot, const std::vector<float>& kfAngle,
+                                                   const std::vector<orbfe_camera_pose>& pose, const std::vector<float>& mvScaleFactors,
+                                                   const std::vector<float>& th, const std::vector<int32_t>& ORBdist,
+                                                   std::vector<int32_t>& match, bool checkOrientation = true,
+                                                   const std::vector<uint8_t>& skip = {}, const std::vector<uint8_t>& blocked = {}) const {
+    const size_t K = pose.size(), n = slot.size(), nc = (size_t)Cur.c.n;
+    if (offsets.size() != K + 1 || (size_t)offsets.back() != n || th.size() != K || ORBdist.size() != K ||
+        (checkOrientation && kfAngle.size() != n) || (!skip.empty() && skip.size() != n) || (!blocked.empty() && blocked.size() != K * nc))
+      throw std::invalid_argument("MapPointTable::SearchByProjectionKeyFrames: the lists disagree in length");
+    std::vector<const uint8_t*> blk;
+    for (size_t k = 0; k < K && !blocked.empty(); k++) blk.push_back(blocked.data() + k * nc);
+    match.assign(K * nc + 1, -1);
+    std::vector<int32_t> nMatches(K + 1, 0);
+    check(orbfe_search_keyframe_mappoints_multi(h_, &Cur.c, mvScaleFactors.data(), (int)mvScaleFactors.size(), (int)K, offsets.data(),
+                                                slot.data(), skip.empty() ? nullptr : skip.data(),
+                                                checkOrientation ? kfAngle.data() : nullptr, pose.data(), blk.empty() ? nullptr : blk.data(),
+                                                th.data(), ORBdist.data(), checkOrientation ? 1 : 0, match.data(), nMatches.data()),
+          "MapPointTable::SearchByProjectionKeyFrames");
+    match.resize(K * nc);
+    nMatches.resize(K);
+    return nMatches;
+  }
   orbfe_mappoints* handle() const { return h_; }
   // the tail of Optimizer::OptimizeEssentialGraph (:1070-1103) on the table: the position of slot[p] becomes
   // Sout[r]^-1 .map(Scw[r] .map(P)), r = refVertex[p] (-1: left alone); Scw / SiwOut 8 doubles per vertex

@@ -6,7 +6,7 @@ from ._lib import KP_DTYPE, OrbfeError, LIB_PATH  # noqa: F401
 from .extractor import ORBextractor, gaussian_blur7, resize_linear, set_blur_pass_order  # noqa: F401
 from .matcher import ComputeStereoMatches, FeatureVector, FrameView, ORBmatcher, ResidentFrame  # noqa: F401
 from .vocabulary import ORBVocabulary, synthetic_vocabulary_arrays, write_synthetic_vocabulary, write_vocabulary_text  # noqa: F401
-from .map_points import MapPoints, camera_pose  # noqa: F401
+from .map_points import MapPoints, camera_pose, motion_model_mode, track_with_motion_model  # noqa: F401
 from .optimizer import (bundle_adjustment, local_bundle_adjustment, optimize_sim3, optimize_sim3_multi,  # noqa: F401
                         pose_optimization, pose_optimization_batch, sim3_to_Rts)
 from .local_mapping import KeyFrameCamera, triangulate_matches, triangulate_matches_multi  # noqa: F401

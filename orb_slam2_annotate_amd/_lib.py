@@ -134,6 +134,8 @@ EXPORTS = [
     "orbfe_obsgraph_set_keyframe_descriptors_frame", "orbfe_obsgraph_get_keyframe_descriptors",
     "orbfe_obsgraph_distinctive_descriptors", "orbfe_obsgraph_distinctive_descriptors_mappoints", "orbfe_mappoints_descriptors",
     "orbfe_project_fuse", "orbfe_fuse_mappoints",
+    "orbfe_project_last_frame", "orbfe_search_last_frame_mappoints", "orbfe_project_keyframe",
+    "orbfe_search_keyframe_mappoints_multi",
 ]
 
 _lib = None
@@ -365,6 +367,10 @@ def load():
     L.orbfe_mappoints_descriptors.argtypes = [vp, ci, vp, vp]
     L.orbfe_project_fuse.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_fuse_mappoints.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, cf, ci, vp, vp]
+    L.orbfe_project_last_frame.argtypes = [vp, ci, vp, vp, vp, cpp, vp, ci, cf, ci, vp, vp, vp, vp, vp, vp]
+    L.orbfe_search_last_frame_mappoints.argtypes = [vp, ci, vp, vp, vp, vp, cpp, fwp, vp, ci, vp, ci, cf, ci, vp, vp, vp]
+    L.orbfe_project_keyframe.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_search_keyframe_mappoints_multi.argtypes = [vp, fwp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp]
     _lib = L
     return L
 

@@ -1,6 +1,7 @@
 // k_project.hip -- the pose arithmetic in front of Tracking::SearchLocalPoints on the device-resident map points:
 // Frame::isInFrustum (src/Frame.cc:292-353) with MapPoint::PredictScale, the prologue of ORBmatcher::Fuse for K key frames
-// (k_project_fuse), and the scatter that keeps the table up to date.
+// (k_project_fuse), the prologues of the last-frame and key-frame SearchByProjection (k_project_track), and the scatter that
+// keeps the table up to date.
 // The kernels are bandwidth-trivial (64 bytes of table per point, a few thousand points): one lane per point, the table
 // records as 16-byte loads, the descriptor rows moved by the whole workgroup as 16-byte pieces.
 #include <hip/hip_runtime.h>
@@ -192,6 +193,99 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_fuse(const FuseArgs
   }
 }
 
+// The prologues of SearchByProjection(CurrentFrame, LastFrame, th, bMono) (kForm 0, src/ORBmatcher.cc:1516-1550) and of
+// SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (kForm 1, :1665-1699) for K jobs over concatenated lists:
+// blockIdx.y is the job, a workgroup owns 256 consecutive points of it, and a job shorter than the longest leaves its spare
+// workgroups at once.  The pose and th of the job are uniform reads.  The arithmetic is include/orbfe.h's
+// (orbfe_project_last_frame / orbfe_project_keyframe), operation by operation.  The reference's 1.0 / z in double, rounded to
+// float, is the float division below: a double quotient of two floats rounded to float is correctly rounded (53 >= 2 * 24 + 2).
+template <int kForm>
+__global__ __launch_bounds__(kProjectThreads) void k_project_track(const TrackArgs a) {
+  const int k = (int)blockIdx.y;
+  const int off = a.offsets[k], nk = a.offsets[k + 1] - off;
+  const int base = blockIdx.x * kProjectThreads;
+  if (base >= nk) return;  // (workgroup-uniform)
+  const int i = base + (int)threadIdx.x;
+  if (i < nk) {
+    const size_t o = (size_t)off + i;
+    const int s = a.slot[o];
+    const float4 r0 = a.table.rec[2 * (size_t)s], r1 = a.table.rec[2 * (size_t)s + 1];
+    const uint8_t fl = a.table.flags[s];
+    const orbfe_camera_pose& c = a.pose[k];
+    const float th = a.th ? a.th[k] : 0.0f;
+    const float X = r0.x, Y = r0.y, Z = r0.z, minD = r0.w, maxD = r1.w;
+    // pMP && !mvbOutlier[i] is the caller's list (:1510-1514: isBad is NOT asked); !isBad() && !sAlreadyFound.count(pMP) (:1663)
+    bool ok = !(a.skip && a.skip[o]);
+    if (kForm == 1 && (fl & ORBFE_MP_BAD)) ok = false;
+    const float xc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[0], X), __fmul_rn(c.Rcw[1], Y)), __fmul_rn(c.Rcw[2], Z)), c.tcw[0]);
+    const float yc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[3], X), __fmul_rn(c.Rcw[4], Y)), __fmul_rn(c.Rcw[5], Z)), c.tcw[1]);
+    const float zc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[6], X), __fmul_rn(c.Rcw[7], Y)), __fmul_rn(c.Rcw[8], Z)), c.tcw[2]);
+    const float invz = __fdiv_rn(1.0f, zc);
+    if (kForm == 0 && invz < 0.0f) ok = false;  // (:1524; the key-frame form has no depth test)
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, xc), invz), c.cx);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, yc), invz), c.cy);
+    // inside the image, bounds included (:1533-1536, :1676-1679); a NaN coordinate is rejected here
+    if (!(u >= c.min_x && u <= c.max_x && v >= c.min_y && v <= c.max_y)) ok = false;
+    int lv = 0, lo = 0, hi = 0;
+    float dist = 0.0f;
+    const float ur = __fsub_rn(u, __fmul_rn(c.mbf, invz));
+    if (kForm == 0) {
+      lv = ok ? a.lastOctave[o] : 0;
+      if (a.mode == 1) { lo = lv; hi = -1; }       // bForward:  GetFeaturesInArea(u, v, radius, nLastOctave)
+      else if (a.mode == 2) { lo = 0; hi = lv; }   // bBackward: (u, v, radius, 0, nLastOctave)
+      else { lo = lv - 1; hi = lv + 1; }
+    } else {
+      // distance inside the scale invariance region of the point (:1682-1691): cv::norm accumulates in double
+      const float px = __fsub_rn(X, c.Ow[0]), py = __fsub_rn(Y, c.Ow[1]), pz = __fsub_rn(Z, c.Ow[2]);
+      const double dpx = (double)px, dpy = (double)py, dpz = (double)pz;
+      const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dpx, dpx), __dmul_rn(dpy, dpy)), __dmul_rn(dpz, dpz));
+      dist = (float)__dsqrt_rn(d2);
+      if (dist < __fmul_rn(0.8f, minD) || dist > __fmul_rn(1.2f, maxD)) ok = false;
+      if (ok) {  // MapPoint::PredictScale (:1694)
+        const float ratio = __fdiv_rn(maxD, dist);
+        const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
+        const int top = c.n_levels - 1;
+        lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
+      }
+      lo = lv - 1; hi = lv + 1;
+    }
+    const float r = a.scale ? __fmul_rn(th, a.scale[lv]) : 0.0f;  // (:1541, :1697)
+    if (a.valid) a.valid[o] = ok;
+    if (a.u) a.u[o] = ok ? u : 0.0f;
+    if (a.v) a.v[o] = ok ? v : 0.0f;
+    if (a.invZ) a.invZ[o] = ok ? invz : 0.0f;
+    if (kForm == 0) {
+      if (a.ur) a.ur[o] = ok ? ur : 0.0f;
+      if (a.radius) a.radius[o] = ok ? r : 0.0f;
+    } else {
+      if (a.level) a.level[o] = lv;
+      if (a.dist) a.dist[o] = ok ? dist : 0.0f;
+    }
+    if (a.qx) {  // the windows as the host-array calls build them from the arrays above
+      a.qx[o] = ok ? u : 0.0f;
+      a.qy[o] = ok ? v : 0.0f;
+      a.qr[o] = r;
+      a.qmin[o] = lo;
+      a.qmax[o] = hi;
+      a.qactive[o] = ok;
+      if (kForm == 0) {
+        a.qobs[o] = (fl & ORBFE_MP_OBSERVED) ? 1 : 0;
+        if (a.qur) a.qur[o] = ok ? ur : 0.0f;
+      }
+      if (a.validCopy) a.validCopy[o] = ok;
+    }
+  }
+  if (a.qdesc) {  // (workgroup-uniform) the points' descriptors: piece p = half (p & 1) of point off + base + p / 2
+    const int cnt = nk - base < kProjectThreads ? nk - base : kProjectThreads;
+    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
+    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
+    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
+      const size_t q = (size_t)off + base + (p >> 1);
+      dst[2 * q + (p & 1)] = src[2 * (size_t)a.slot[q] + (p & 1)];
+    }
+  }
+}
+
 __global__ __launch_bounds__(kProjectThreads) void k_mappoints_scatter(const MapPointsDevice t, int n, const int32_t* __restrict__ slot,
                                                                        const float4* __restrict__ rec, const uint8_t* __restrict__ flags,
                                                                        const uint8_t* __restrict__ desc) {
@@ -232,6 +326,13 @@ void launch_project_frustum(hipStream_t s, const ProjectArgs& a) {
 void launch_project_fuse(hipStream_t s, const FuseArgs& a) {
   if (a.n <= 0 || a.K <= 0 || a.K > kFuseMaxKeyFrames) return;
   hipLaunchKernelGGL(k_project_fuse, dim3((a.n + kProjectThreads - 1) / kProjectThreads), dim3(kProjectThreads), 0, s, a);
+}
+
+void launch_project_track(hipStream_t s, const TrackArgs& a, int maxN) {
+  if (maxN <= 0 || a.K <= 0 || a.K > kTrackMaxJobs) return;
+  const dim3 grid((maxN + kProjectThreads - 1) / kProjectThreads, a.K);
+  if (a.form == 0) hipLaunchKernelGGL(k_project_track<0>, grid, dim3(kProjectThreads), 0, s, a);
+  else hipLaunchKernelGGL(k_project_track<1>, grid, dim3(kProjectThreads), 0, s, a);
 }
 
 void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,

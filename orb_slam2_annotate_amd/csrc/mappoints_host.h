@@ -79,4 +79,34 @@ inline const char* fuse_check_operands(int capacity, int n, const int32_t* slot,
   return nullptr;
 }
 
+// The operands of orbfe_project_last_frame / orbfe_search_last_frame_mappoints (K = 1, offsets = {0, n}, with_octave) and of
+// orbfe_project_keyframe / orbfe_search_keyframe_mappoints_multi that need no handle: K jobs (at most kTrackMaxJobPoses) over
+// concatenated lists -- offsets[K + 1] starts at 0 and never descends --, the slots of a table of `capacity` slots, one pose per
+// job and -- with_octave -- the last frame's octaves.  n_levels > 0: the caller's level table holds that many entries; no
+// octave and no pose may point past it.  Nothing is read past what K and offsets[K] say.
+constexpr int kTrackMaxJobPoses = 64;
+inline const char* track_check_operands(int capacity, int K, const int32_t* offsets, const int32_t* slot, bool with_octave,
+                                        const int32_t* last_octave, const orbfe_camera_pose* pose, int n_levels) {
+  if (K < 0) return "negative number of jobs";
+  if (K > kTrackMaxJobPoses) return "more than 64 jobs in one call";
+  if (K == 0) return nullptr;
+  if (!offsets) return "NULL offsets";
+  if (offsets[0] != 0) return "offsets must start at 0";
+  for (int k = 0; k < K; k++)
+    if (offsets[k + 1] < offsets[k]) return offsets[k + 1] < 0 ? "negative count" : "offsets descend";
+  const int total = offsets[K];
+  if (const char* e = mappoints_check_slots(capacity, total, slot)) return e;
+  if (!pose) return "NULL pose array";
+  for (int k = 0; k < K; k++) {
+    if (pose[k].n_levels < 1 || pose[k].n_levels > kFuseMaxPoseLevels) return "bad pose (n_levels must be 1 .. 64)";
+    if (n_levels > 0 && pose[k].n_levels > n_levels) return "a pose predicts more levels than the level table holds";
+  }
+  if (with_octave) {
+    if (total > 0 && !last_octave) return "NULL octave array";
+    for (int i = 0; i < total; i++)
+      if (last_octave[i] < 0 || (n_levels > 0 && last_octave[i] >= n_levels)) return "octave outside the level table";
+  }
+  return nullptr;
+}
+
 }  // namespace orbfe

@@ -189,6 +189,30 @@ struct FuseArgs {
   const float* scale; float th;
 };
 void launch_project_fuse(hipStream_t s, const FuseArgs& a);
+// k_project_track: the prologues of the two tracking-thread searches that walk a frame's own map points, for K jobs over
+// concatenated lists in ONE launch (blockIdx.y = job k, points [offsets[k], offsets[k + 1]), pose[k], th[k]); one lane per point.
+//   form 0, SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1516-1550): no isBad test, invz < 0
+//   rejected, radius th * scale[lastOctave], the level range of `mode` (0 / 1 bForward / 2 bBackward), qobs = Observations() > 0;
+//   form 1, SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (:1665-1699): isBad and skip rejected, no depth
+//   sign test, the distance range, PredictScale, radius th * scale[level], levels [level - 1, level + 1].
+// Two sets of outputs, either may be absent: the projection itself (every pointer may be NULL; entries of a rejected point
+// are 0) and -- qx != NULL -- the query windows exactly as orbfe_search_by_projection_last_frame / _keyframe build them on the
+// host, with the points' descriptors gathered from the table, so that k_window_search / k_window_claim run behind it without
+// a host step.  Every array is indexed by the position in the concatenated list.
+constexpr int kTrackMaxJobs = 64;
+struct TrackArgs {
+  MapPointsDevice table;
+  int form, K, mode;
+  const int32_t* offsets /* [K + 1] */; const int32_t* slot; const uint8_t* skip /* NULL: none */;
+  const int32_t* lastOctave /* form 0 */; const orbfe_camera_pose* pose /* [K] */; const float* th /* [K] */;
+  uint8_t* valid; float* u; float* v; float* invZ; float* ur /* form 0 */; float* radius /* form 0 */;
+  int32_t* level /* form 1 */; float* dist /* form 1 */;
+  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive;
+  float* qur /* form 0, NULL: monocular frame */; uint8_t* qdesc; uint8_t* qobs /* form 0 */;
+  uint8_t* validCopy /* NULL, or a second copy of qactive among the results that travel back */;
+  const float* scale;
+};
+void launch_project_track(hipStream_t s, const TrackArgs& a, int maxN /* the longest list of the K jobs */);
 // orbfe_mappoints_update: n staged entries (slot, the two records, flags, descriptors or NULL = keep) into their slots
 void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,
                               const uint8_t* flags, const uint8_t* desc);

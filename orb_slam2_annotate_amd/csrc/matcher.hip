@@ -573,6 +573,42 @@ struct WindowJob {
   // are NULL -- ONE k_project_fuse launch writes the windows of all K jobs from the map-point table, and the descriptors once
   struct FuseProducer* fuse = nullptr;
   int fuseK = 0;
+  // TRACK PRODUCER (CLAIM_BEST jobs only): the jobs of a call name ONE TrackProducer and their place k in it; the query arrays
+  // above are NULL -- ONE k_project_track launch writes the windows of all its jobs from the map-point table, each job's
+  // descriptors and, in the last-frame form, blockVal (Observations() > 0)
+  struct TrackProducer* track = nullptr;
+  int trackK = 0;
+};
+// The prologue of the last-frame (form 0) or key-frame (form 1) SearchByProjection for K jobs over concatenated lists
+struct TrackProducer {
+  MapPointsDevice table;
+  int form = 0, K = 0, mode = 0;
+  const int32_t* offsets = nullptr;     // [K + 1]
+  const int32_t* slot = nullptr;        // [offsets[K]]
+  const uint8_t* skip = nullptr;        // [offsets[K]] or NULL
+  const int32_t* lastOctave = nullptr;  // [offsets[K]] (form 0)
+  const orbfe_camera_pose* pose = nullptr;  // [K]
+  const float* th = nullptr;                // [K]
+  const float* scale = nullptr;             // [nLevels] mvScaleFactors
+  int nLevels = 0;
+  uint8_t* validOut = nullptr;  // out [offsets[K]] or NULL
+  int total() const { return offsets[K]; }
+  int longest() const {
+    int m = 0;
+    for (int k = 0; k < K; k++) m = offsets[k + 1] - offsets[k] > m ? offsets[k + 1] - offsets[k] : m;
+    return m;
+  }
+};
+// where a call's TrackProducer has its arrays on the device: uploads | the one result | what k_project_track writes for the search
+struct TrackDev {
+  int32_t *offsets = nullptr, *slot = nullptr, *lastOctave = nullptr;
+  uint8_t* skip = nullptr;
+  orbfe_camera_pose* pose = nullptr;
+  float *th = nullptr, *scale = nullptr;
+  uint8_t* valid = nullptr;
+  float *qx = nullptr, *qy = nullptr, *qr = nullptr, *qur = nullptr;
+  int32_t *qmin = nullptr, *qmax = nullptr;
+  uint8_t *qactive = nullptr, *qdesc = nullptr, *qobs = nullptr;
 };
 struct FuseProducer {
   MapPointsDevice table;
@@ -677,13 +713,43 @@ FuseArgs fuse_args(const FuseProducer& P, const FuseDev& F) {
   return fa;
 }
 
+hipError_t stage_track_inputs(Arena* a, const TrackProducer& P, TrackDev* T) {
+  const size_t q = (size_t)P.total();
+  TRY(up(a, &T->offsets, P.offsets, (size_t)P.K + 1));
+  TRY(up(a, &T->slot, P.slot, q));
+  if (P.skip) TRY(up(a, &T->skip, P.skip, q));
+  if (P.form == 0) TRY(up(a, &T->lastOctave, P.lastOctave, q));
+  TRY(up(a, &T->pose, P.pose, (size_t)P.K));
+  if (P.th) TRY(up(a, &T->th, P.th, (size_t)P.K));
+  if (P.scale) TRY(up(a, &T->scale, P.scale, (size_t)P.nLevels));
+  return hipSuccess;
+}
+void stage_track_scratch(Arena* a, const TrackProducer& P, bool withUr, TrackDev* T) {
+  const size_t q = (size_t)P.total();
+  T->qx = carve<float>(a, q); T->qy = carve<float>(a, q); T->qr = carve<float>(a, q);
+  T->qmin = carve<int32_t>(a, q); T->qmax = carve<int32_t>(a, q);
+  T->qactive = carve<uint8_t>(a, q);
+  if (P.form == 0) T->qobs = carve<uint8_t>(a, q);
+  if (withUr) T->qur = carve<float>(a, q);
+  T->qdesc = carve<uint8_t>(a, q * 32);
+}
+TrackArgs track_args(const TrackProducer& P, const TrackDev& T) {
+  TrackArgs ta{};
+  ta.table = P.table; ta.form = P.form; ta.K = P.K; ta.mode = P.mode;
+  ta.offsets = T.offsets; ta.slot = T.slot; ta.skip = T.skip; ta.lastOctave = T.lastOctave; ta.pose = T.pose; ta.th = T.th;
+  ta.qx = T.qx; ta.qy = T.qy; ta.qr = T.qr; ta.qmin = T.qmin; ta.qmax = T.qmax; ta.qactive = T.qactive; ta.qur = T.qur;
+  ta.qdesc = T.qdesc; ta.qobs = T.qobs; ta.validCopy = T.valid;
+  ta.scale = T.scale;
+  return ta;
+}
+
 hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, const FuseDev& fuse) {
   const WindowJob& J = jobs[j];
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
   D = JobDev{};
-  D.withDesc = J.f->desc && (J.qdesc || J.producer || J.fuse);
-  D.withUr = (J.qur || J.producer) && J.f->u_right;
+  D.withDesc = J.f->desc && (J.qdesc || J.producer || J.fuse || J.track);
+  D.withUr = (J.qur || J.producer || (J.track && J.track->form == 0)) && J.f->u_right;
   if (const orbfe_frame* R = J.f->resident) {
     D.x = R->dx; D.y = R->dy; D.oct = R->doct; D.ur = J.f->u_right ? R->dur : nullptr; D.desc = D.withDesc ? R->ddesc : nullptr;
     D.angle = R->dangle; D.key = R->dkey; D.cell = R->dcell;
@@ -706,6 +772,7 @@ hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, con
     TRY(up(a, &D.scale, P->scale, (size_t)P->nLevels));
   } else if (J.fuse) {  // (the call's one FuseProducer has uploaded everything: stage_fuse_inputs)
     if (J.fuse->gate) D.invSigma2 = fuse.invSigma2;
+  } else if (J.track) {  // (the call's one TrackProducer has uploaded everything: stage_track_inputs)
   } else {
     TRY(up(a, &D.qx, J.qx, q)); TRY(up(a, &D.qy, J.qy, q)); TRY(up(a, &D.qr, J.qr, q));
     TRY(up(a, &D.qmin, J.qmin, q)); TRY(up(a, &D.qmax, J.qmax, q));
@@ -759,10 +826,17 @@ OwnerPlace owner_place(const WindowJob& J) {
 
 // Region 3, job j's part: what never leaves the device -- the grid of an uploaded frame, the query arrays a producer
 // writes, the claim kernel's lists and scratch
-void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev, const FuseDev& fuse) {
+void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev, const FuseDev& fuse, const TrackDev& track) {
   const WindowJob& J = jobs[j];
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
+  if (J.track) {  // job k's part of what the one k_project_track launch writes
+    const size_t o = (size_t)J.track->offsets[J.trackK];
+    D.qx = track.qx + o; D.qy = track.qy + o; D.qr = track.qr + o; D.qmin = track.qmin + o; D.qmax = track.qmax + o;
+    D.qactive = track.qactive + o; D.qdesc = track.qdesc + o * 32;
+    if (track.qobs) D.blockVal = track.qobs + o;
+    if (D.withUr) D.qur = track.qur + o;
+  }
   if (J.fuse) {  // job k's part of what the one k_project_fuse launch writes
     const size_t o = (size_t)J.fuseK * q;
     D.qx = fuse.qx + o; D.qy = fuse.qy + o; D.qr = fuse.qr + o; D.qmin = fuse.qmin + o; D.qmax = fuse.qmax + o;
@@ -835,6 +909,8 @@ struct WindowCall {
   uint8_t *outLo = nullptr, *outHi = nullptr;
   const FuseProducer* fuseProducer = nullptr;  // the one FuseProducer of the call's jobs, and where it is on the device
   FuseDev fuse;
+  const TrackProducer* trackProducer = nullptr;  // likewise the one TrackProducer
+  TrackDev track;
   size_t claimLds = 0;
   int totalBlocks = 0;
 };
@@ -847,15 +923,23 @@ hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, in
   c->dev.resize((size_t)nJobs);
   for (int j = 0; j < nJobs && !c->fuseProducer; j++) c->fuseProducer = jobs[j].fuse;
   if (c->fuseProducer) TRY(stage_fuse_inputs(a, *c->fuseProducer, &c->fuse));
+  for (int j = 0; j < nJobs && !c->trackProducer; j++) c->trackProducer = jobs[j].track;
+  if (c->trackProducer) TRY(stage_track_inputs(a, *c->trackProducer, &c->track));
   for (int j = 0; j < nJobs; j++) TRY(stage_inputs(a, jobs, j, c->dev.data(), c->fuse));
   c->dClaims = carve<ClaimJob>(a, (size_t)nClaim);
   c->dSearches = carve<WindowSearchJob>(a, nJobs > 1 ? (size_t)nJobs : 0);
   c->outLo = carve<uint8_t>(a, 0);
   for (int j = 0; j < nJobs; j++) stage_outputs(a, jobs[j], K, &c->dev[j]);
   if (c->fuseProducer && c->fuseProducer->projectedOut) c->fuse.projected = carve<uint8_t>(a, (size_t)c->fuseProducer->K * c->fuseProducer->n);
+  if (c->trackProducer && c->trackProducer->validOut) c->track.valid = carve<uint8_t>(a, (size_t)c->trackProducer->total());
   c->outHi = carve<uint8_t>(a, 0);
   if (c->fuseProducer) stage_fuse_scratch(a, *c->fuseProducer, &c->fuse);
-  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data(), c->fuse);
+  if (c->trackProducer) {
+    bool withUr = false;
+    for (int j = 0; j < nJobs; j++) withUr = withUr || c->dev[j].withUr;
+    stage_track_scratch(a, *c->trackProducer, withUr, &c->track);
+  }
+  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data(), c->fuse, c->track);
   for (int j = 0; j < nJobs; j++) {
     if (jobs[j].claim) {
       c->claims.push_back(claim_job(jobs[j], c->dev[j], K));
@@ -876,6 +960,10 @@ hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, const Windo
   TRY(flush(ar));
   if (c.fuseProducer) {  // ONE launch for the windows of all its jobs
     launch_project_fuse(ar->stream, fuse_args(*c.fuseProducer, c.fuse));
+    TRY(hipGetLastError());
+  }
+  if (c.trackProducer) {  // likewise
+    launch_project_track(ar->stream, track_args(*c.trackProducer, c.track), c.trackProducer->longest());
     TRY(hipGetLastError());
   }
   for (int j = 0; j < nJobs; j++)
@@ -909,6 +997,8 @@ int collect_results(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCal
   int mx = 0;
   if (const FuseProducer* P = c.fuseProducer)
     if (P->projectedOut) std::memcpy(P->projectedOut, mirror_of(ar, c.fuse.projected), (size_t)P->K * P->n);
+  if (const TrackProducer* P = c.trackProducer)
+    if (P->validOut && P->total()) std::memcpy(P->validOut, mirror_of(ar, c.track.valid), (size_t)P->total());
   for (int j = 0; j < nJobs; j++) {
     const WindowJob& J = jobs[j];
     const JobDev& D = c.dev[j];
@@ -953,6 +1043,10 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
     if (J.fuse && (!J.bestOut || J.fuse != jobs[0].fuse || J.nq != J.fuse->n || J.fuseK < 0 || J.fuseK >= J.fuse->K))
       return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST jobs that all name it");
     if (!J.fuse && jobs[0].fuse) return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST jobs that all name it");
+    if (J.track != jobs[0].track ||
+        (J.track && (!J.claim || J.claim->mode != CLAIM_BEST || J.trackK < 0 || J.trackK >= J.track->K ||
+                     J.nq != J.track->offsets[J.trackK + 1] - J.track->offsets[J.trackK])))
+      return fail(ORBFE_ERR_INVALID, "a track producer needs CLAIM_BEST jobs that all name it");
     if (!J.claim) continue;
     if (J.nq > 0x1fffff) return fail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
     if (nClaim && claimInit != (J.claim->mode == CLAIM_INIT)) return fail(ORBFE_ERR_INVALID, "mixed claim forms in one call");
@@ -976,6 +1070,31 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
 }  // namespace
 
 extern "C" int orbfe_debug_last_claim_rounds(void) { return t_lastClaimRounds; }
+
+namespace {
+// The claim loops of the two searches that walk a frame's own map points, on the device (k_window_claim); shared by the
+// host-array calls and the calls on the resident map points.
+// SearchByProjection(CurrentFrame, LastFrame, th, bMono): claim loop :1572-1612 + rotation histogram :1614-1628
+ClaimSpec last_frame_claim(const uint8_t* blocked, const uint8_t* obs_positive, const float* last_angle, int check_orientation,
+                           int32_t* match_cur, int32_t* n_matches) {
+  ClaimSpec C;
+  C.mode = CLAIM_BEST; C.maxDist = 100 /* TH_HIGH */; C.checkOri = check_orientation ? 1 : 0;
+  C.blocked = blocked;        // mvpMapPoints[i2] set with Observations() > 0 at entry (:1572-1574)
+  C.blockVal = obs_positive;  // (a track producer writes it from the table's flags)
+  C.qAngle = last_angle;
+  C.match = match_cur; C.nMatches = n_matches;
+  return C;
+}
+// SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist): claim loop :1726-1760
+ClaimSpec keyframe_claim(const uint8_t* blocked, const float* kf_angle, int orb_dist, int check_orientation, int32_t* match_cur,
+                         int32_t* n_matches) {
+  ClaimSpec C;
+  C.mode = CLAIM_BEST; C.maxDist = orb_dist; C.checkOri = check_orientation ? 1 : 0;
+  C.blocked = blocked; C.qAngle = kf_angle;
+  C.match = match_cur; C.nMatches = n_matches;
+  return C;
+}
+}  // namespace
 
 extern "C" int orbfe_features_in_area(int device, const orbfe_frame_view* frame, int n_queries, const float* x,
                                       const float* y, const float* r, const int32_t* min_level,
@@ -1107,13 +1226,7 @@ extern "C" int orbfe_search_by_projection_last_frame(int device, const orbfe_fra
     else { qmin[i] = o - 1; qmax[i] = o + 1; }
     if (Cur->u_right) qur[i] = u[i] - mbf * invzc[i];        // :1562
   }
-  // claim loop :1572-1612 + rotation histogram :1614-1628 on the device (k_window_claim)
-  ClaimSpec C;
-  C.mode = CLAIM_BEST; C.maxDist = 100 /* TH_HIGH */; C.checkOri = check_orientation ? 1 : 0;
-  C.blocked = blocked;        // mvpMapPoints[i2] set with Observations() > 0 at entry (:1572-1574)
-  C.blockVal = obs_positive;
-  C.qAngle = last_angle;
-  C.match = match_cur; C.nMatches = n_matches;
+  ClaimSpec C = last_frame_claim(blocked, obs_positive, last_angle, check_orientation, match_cur, n_matches);
   WindowJob job;
   job.f = Cur; job.nq = n_last; job.qx = u; job.qy = v; job.qr = qr.data(); job.qmin = qmin.data(); job.qmax = qmax.data();
   job.qactive = valid; job.qur = Cur->u_right ? qur.data() : nullptr; job.qdesc = mp_desc;
@@ -1163,10 +1276,7 @@ extern "C" int orbfe_search_by_projection_keyframe(int device, const orbfe_frame
   for (int i = 0; i < Cur->n; i++) match_cur[i] = -1;
   *n_matches = 0;
   if (n == 0 || Cur->n == 0) return ORBFE_OK;
-  ClaimSpec C;  // claim loop :1726-1760 on the device
-  C.mode = CLAIM_BEST; C.maxDist = orb_dist; C.checkOri = check_orientation ? 1 : 0;
-  C.blocked = blocked; C.qAngle = kf_angle;
-  C.match = match_cur; C.nMatches = n_matches;
+  ClaimSpec C = keyframe_claim(blocked, kf_angle, orb_dist, check_orientation, match_cur, n_matches);
   WindowJob job;
   job.f = Cur; job.nq = n; job.qx = u; job.qy = v; job.qr = qr.data(); job.qmin = qmin.data(); job.qmax = qmax.data();
   job.qactive = valid; job.qdesc = mp_desc;
@@ -1207,10 +1317,8 @@ extern "C" int orbfe_search_by_projection_keyframe_multi(int device, const orbfe
     n_matches[k] = 0;
     if (n[k] == 0 || Cur->n == 0) continue;
     ClaimSpec& C = claims[k];
-    C.mode = CLAIM_BEST; C.maxDist = orb_dist[k]; C.checkOri = check_orientation ? 1 : 0;
-    C.blocked = blocked ? blocked[k] : nullptr;
-    C.qAngle = check_orientation ? kf_angle[k] : nullptr;
-    C.match = match_cur + (size_t)k * Cur->n; C.nMatches = &n_matches[k];
+    C = keyframe_claim(blocked ? blocked[k] : nullptr, check_orientation ? kf_angle[k] : nullptr, orb_dist[k], check_orientation,
+                       match_cur + (size_t)k * Cur->n, &n_matches[k]);
     WindowJob job;
     job.f = Cur; job.nq = n[k]; job.qx = u[k]; job.qy = v[k]; job.qr = qr[k].data(); job.qmin = qmin[k].data(); job.qmax = qmax[k].data();
     job.qactive = valid[k]; job.qdesc = mp_desc[k];
@@ -1220,6 +1328,151 @@ extern "C" int orbfe_search_by_projection_keyframe_multi(int device, const orbfe
   if (wj.empty()) return ORBFE_OK;
   // one claim workgroup per candidate behind the K window searches: one upload, one launch group, one download
   return window_search_multi(device, wj.data(), (int)wj.size(), 32);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same two searches on the resident map points: k_project_track writes the windows the host-array calls above build from
+// the caller's projection (TrackProducer), and the same window search and claim launches follow.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// k_project_track alone (a point to project, arguments checked, the table held): lists, masks, octaves and poses up, one
+// launch, the requested arrays back in one copy.  aux0 / aux1: form 0 ur / radius (float), form 1 level (int32) / dist
+int project_track_run(int device, const TrackProducer& P, uint8_t* valid, float* u, float* v, float* inv_z, void* aux0, float* aux1) {
+  const size_t q = (size_t)P.total();
+  TrackDev T;
+  TrackArgs ta{};
+  float* daux0 = nullptr;
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    T = TrackDev{};
+    TRY(stage_track_inputs(a, P, &T));
+    ta = track_args(P, T);
+    open_span(a);
+    ta.u = carve<float>(a, q); ta.v = carve<float>(a, q); ta.invZ = carve<float>(a, q);
+    daux0 = carve<float>(a, q);
+    float* daux1 = carve<float>(a, q);
+    ta.valid = carve<uint8_t>(a, q);
+    if (P.form == 0) { ta.ur = daux0; ta.radius = daux1; }
+    else { ta.level = reinterpret_cast<int32_t*>(daux0); ta.dist = daux1; }
+    return close_span(a);
+  };
+  HIPCHK(arena_stage(device, &ar, stage));
+  HIPCHK(flush(ar));
+  launch_project_track(ar->stream, ta, P.longest());
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  if (u) std::memcpy(u, mirror_of(ar, ta.u), q * 4);
+  if (v) std::memcpy(v, mirror_of(ar, ta.v), q * 4);
+  if (inv_z) std::memcpy(inv_z, mirror_of(ar, ta.invZ), q * 4);
+  if (aux0) std::memcpy(aux0, mirror_of(ar, daux0), q * 4);
+  if (aux1) std::memcpy(aux1, mirror_of(ar, P.form == 0 ? ta.radius : ta.dist), q * 4);
+  if (valid) std::memcpy(valid, mirror_of(ar, ta.valid), q);
+  return ORBFE_OK;
+}
+}  // namespace
+
+extern "C" int orbfe_project_last_frame(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
+                                        const int32_t* last_octave, const orbfe_camera_pose* pose, const float* scale_factors,
+                                        int n_levels, float th, int mode, uint8_t* valid, float* u, float* v, float* inv_z, float* ur,
+                                        float* radius) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "project_last_frame: NULL table");
+  if (!scale_factors || n_levels <= 0 || mode < 0 || mode > 2) return fail(ORBFE_ERR_INVALID, "project_last_frame: bad argument");
+  const int32_t offsets[2] = {0, n};
+  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), 1, offsets, slot, true, last_octave, pose, n_levels))
+    return fail(ORBFE_ERR_INVALID, std::string("project_last_frame: ") + e);
+  if (n == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  TrackProducer P;
+  P.table = *lock.table; P.form = 0; P.K = 1; P.mode = mode; P.offsets = offsets; P.slot = slot; P.skip = skip;
+  P.lastOctave = last_octave; P.pose = pose; P.th = &th; P.scale = scale_factors; P.nLevels = n_levels;
+  return project_track_run(lock.device, P, valid, u, v, inv_z, ur, radius);
+}
+
+extern "C" int orbfe_search_last_frame_mappoints(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
+                                                 const int32_t* last_octave, const float* last_angle, const orbfe_camera_pose* pose,
+                                                 const orbfe_frame_view* Cur, const float* scale_factors, int n_levels,
+                                                 const uint8_t* blocked, int mode, float th, int check_orientation,
+                                                 int32_t* match_cur, int32_t* n_matches, uint8_t* valid_out) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "search_last_frame_mappoints: NULL table");
+  const int32_t offsets[2] = {0, n};
+  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), 1, offsets, slot, true, last_octave, pose, n_levels))
+    return fail(ORBFE_ERR_INVALID, std::string("search_last_frame_mappoints: ") + e);
+  Cur = canon(Cur);
+  if (!frame_ok(Cur) || !scale_factors || n_levels <= 0 || !n_matches || mode < 0 || mode > 2 ||
+      (Cur->n > 0 && (!match_cur || !Cur->desc)) || (check_orientation && Cur->n > 0 && !Cur->angle) ||
+      (check_orientation && n > 0 && !last_angle))
+    return fail(ORBFE_ERR_INVALID, "search_last_frame_mappoints: bad argument");
+  for (int i = 0; i < Cur->n; i++) match_cur[i] = -1;
+  *n_matches = 0;
+  if (n == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  TrackProducer P;
+  P.table = *lock.table; P.form = 0; P.K = 1; P.mode = mode; P.offsets = offsets; P.slot = slot; P.skip = skip;
+  P.lastOctave = last_octave; P.pose = pose; P.th = &th; P.scale = scale_factors; P.nLevels = n_levels; P.validOut = valid_out;
+  if (Cur->n == 0)  // nothing to search: the flags alone
+    return valid_out ? project_track_run(lock.device, P, valid_out, nullptr, nullptr, nullptr, nullptr, nullptr) : ORBFE_OK;
+  ClaimSpec C = last_frame_claim(blocked, nullptr, last_angle, check_orientation, match_cur, n_matches);
+  WindowJob job;
+  job.f = Cur; job.nq = n;
+  job.claim = &C;
+  job.track = &P; job.trackK = 0;
+  return window_search_multi(lock.device, &job, 1, 32);
+}
+
+extern "C" int orbfe_project_keyframe(orbfe_mappoints* mp, int n_candidates, const int32_t* offsets, const int32_t* slot,
+                                      const uint8_t* skip, const orbfe_camera_pose* pose, uint8_t* valid, float* u, float* v,
+                                      float* inv_z, int32_t* level, float* dist) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "project_keyframe: NULL table");
+  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), n_candidates, offsets, slot, false, nullptr, pose, 0))
+    return fail(ORBFE_ERR_INVALID, std::string("project_keyframe: ") + e);
+  if (n_candidates == 0 || offsets[n_candidates] == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  TrackProducer P;
+  P.table = *lock.table; P.form = 1; P.K = n_candidates; P.offsets = offsets; P.slot = slot; P.skip = skip; P.pose = pose;
+  return project_track_run(lock.device, P, valid, u, v, inv_z, level, dist);
+}
+
+extern "C" int orbfe_search_keyframe_mappoints_multi(orbfe_mappoints* mp, const orbfe_frame_view* Cur, const float* scale_factors,
+                                                     int n_levels, int n_candidates, const int32_t* offsets, const int32_t* slot,
+                                                     const uint8_t* skip, const float* kf_angle, const orbfe_camera_pose* pose,
+                                                     const uint8_t* const* blocked, const float* th, const int32_t* orb_dist,
+                                                     int check_orientation, int32_t* match_cur, int32_t* n_matches) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "search_keyframe_mappoints_multi: NULL table");
+  const int K = n_candidates;
+  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), K, offsets, slot, false, nullptr, pose, n_levels))
+    return fail(ORBFE_ERR_INVALID, std::string("search_keyframe_mappoints_multi: ") + e);
+  Cur = canon(Cur);
+  if (!frame_ok(Cur) || !scale_factors || n_levels <= 0 || (K > 0 && (!th || !orb_dist || !n_matches)) ||
+      (Cur->n > 0 && K > 0 && (!match_cur || !Cur->desc)) || (check_orientation && Cur->n > 0 && !Cur->angle) ||
+      (check_orientation && K > 0 && offsets[K] > 0 && !kf_angle))
+    return fail(ORBFE_ERR_INVALID, "search_keyframe_mappoints_multi: bad argument");
+  if (K == 0) return ORBFE_OK;
+  for (size_t i = 0; i < (size_t)K * Cur->n; i++) match_cur[i] = -1;
+  for (int k = 0; k < K; k++) n_matches[k] = 0;
+  if (offsets[K] == 0 || Cur->n == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  TrackProducer P;
+  P.table = *lock.table; P.form = 1; P.K = K; P.offsets = offsets; P.slot = slot; P.skip = skip; P.pose = pose; P.th = th;
+  P.scale = scale_factors; P.nLevels = n_levels;
+  std::vector<ClaimSpec> claims((size_t)K);
+  std::vector<WindowJob> wj;
+  for (int k = 0; k < K; k++) {
+    if (offsets[k + 1] == offsets[k]) continue;  // an empty candidate: its matches stay -1
+    claims[k] = keyframe_claim(blocked ? blocked[k] : nullptr, check_orientation ? kf_angle + offsets[k] : nullptr, orb_dist[k],
+                               check_orientation, match_cur + (size_t)k * Cur->n, &n_matches[k]);
+    WindowJob job;
+    job.f = Cur; job.nq = offsets[k + 1] - offsets[k];
+    job.claim = &claims[k];
+    job.track = &P; job.trackK = k;
+    wj.push_back(job);
+  }
+  // one claim workgroup per candidate behind the K window searches: one upload, one launch group, one download
+  return window_search_multi(lock.device, wj.data(), (int)wj.size(), 32);
 }
 
 extern "C" int orbfe_search_by_projection_sim3(int device, const orbfe_frame_view* KF, const float* scale_factors,

@@ -180,6 +180,128 @@ class MapPoints:
         best = best[:K * n].reshape(K, n)
         return (best, proj[:K * n].reshape(K, n)) if return_projected else best
 
+    @staticmethod
+    def _last_frame_operands(slot, last_octave, skip):
+        s = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        o = np.ascontiguousarray(last_octave, dtype=np.int32).reshape(-1)
+        k = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+        if len(o) != len(s) or (k is not None and len(k) != len(s)):
+            raise ValueError("last_octave (and skip) must hold one entry per slot")
+        return s, o, k
+
+    def project_last_frame(self, slot, last_octave, pose: CameraPoseC, scale_factors, th: float, mode: int = 0, skip=None):
+        """The prologue of SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1516-1550) for the compact
+        list slot[] / last_octave[] (orbfe_project_last_frame) -> dict of valid (uint8), u, v, inv_z, ur, radius (float32);
+        the fields are 0 where valid is."""
+        h = self._h
+        s, o, k = self._last_frame_operands(slot, last_octave, skip)
+        n = len(s)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        out = {"valid": np.zeros(max(n, 1), np.uint8)}
+        for name in ("u", "v", "inv_z", "ur", "radius"):
+            out[name] = np.zeros(max(n, 1), np.float32)
+        check(self._L.orbfe_project_last_frame(h, n, ptr(s), ptr(k), ptr(o), C.byref(pose), ptr(sf), len(sf), float(th), int(mode),
+                                               *[ptr(out[f]) for f in ("valid", "u", "v", "inv_z", "ur", "radius")]))
+        return {name: a[:n] for name, a in out.items()}
+
+    def SearchByProjectionLastFrame(self, Cur, slot, last_octave, last_angle, pose: CameraPoseC, scale_factors, th: float,
+                                    mode: int = 0, skip=None, blocked=None, check_orientation: bool = True,
+                                    return_valid: bool = False):
+        """SearchByProjection(CurrentFrame, LastFrame, th, bMono) in one call (orbfe_search_last_frame_mappoints): slot[] names
+        the last frame's features that hold a non-outlier map point, in ascending feature order; last_octave / last_angle are
+        their mvKeysUn -> (nmatches, match_cur[Cur.N]) with match_cur[i2] = position in slot[] or -1 (what pose_optimization
+        takes), and with return_valid the points that were searched."""
+        h = self._h
+        s, o, k = self._last_frame_operands(slot, last_octave, skip)
+        n = len(s)
+        la = None
+        if check_orientation:
+            la = np.ascontiguousarray(last_angle, dtype=np.float32).reshape(-1)
+            if len(la) != n:
+                raise ValueError("last_angle must hold one entry per slot")
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        blk = None if blocked is None else np.ascontiguousarray(blocked, dtype=np.uint8).reshape(-1)
+        if blk is not None and len(blk) != Cur.N:
+            raise ValueError("blocked must hold one entry per feature of the frame")
+        match = np.full(max(Cur.N, 1), -1, dtype=np.int32)
+        valid = np.zeros(max(n, 1), np.uint8) if return_valid else None
+        nm = C.c_int32(0)
+        check(self._L.orbfe_search_last_frame_mappoints(h, n, ptr(s), ptr(k), ptr(o), ptr(la), C.byref(pose), C.byref(Cur.c), ptr(sf),
+                                                        len(sf), ptr(blk), int(mode), float(th), int(bool(check_orientation)),
+                                                        ptr(match), C.byref(nm), ptr(valid)))
+        return (nm.value, match[:Cur.N], valid[:n]) if return_valid else (nm.value, match[:Cur.N])
+
+    @staticmethod
+    def _keyframe_operands(poses, slots, skips):
+        """(K, offsets [K + 1], concatenated slots, pose array, concatenated mask) of project_keyframes / SearchByProjectionKeyFrames"""
+        poses = list(poses)
+        lists = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in slots]
+        K = len(poses)
+        if len(lists) != K:
+            raise ValueError("one slot list per pose")
+        off = np.zeros(K + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in lists])
+        s = np.concatenate(lists + [np.zeros(0, np.int32)]).astype(np.int32)
+        k = None
+        if skips is not None:
+            masks = [np.ascontiguousarray(m, dtype=np.uint8).reshape(-1) for m in skips]
+            if [len(m) for m in masks] != [len(x) for x in lists]:
+                raise ValueError("one skip entry per slot")
+            k = np.concatenate(masks + [np.zeros(0, np.uint8)]).astype(np.uint8)
+        return K, off, s, (CameraPoseC * max(K, 1))(*poses), k
+
+    def project_keyframes(self, poses, slots, skips=None):
+        """The prologue of SearchByProjection(CurrentFrame, pKF_k, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1665-1699) for K
+        candidates in one launch (orbfe_project_keyframe): slots[k] names pKF_k's non-null map points in feature order,
+        skips[k] = sAlreadyFound -> list of K dicts of valid (uint8), u, v, inv_z, dist (float32), level (int32)."""
+        h = self._h
+        K, off, s, pa, k = self._keyframe_operands(poses, slots, skips)
+        q = max(len(s), 1)
+        flat = {"valid": np.zeros(q, np.uint8), "level": np.zeros(q, np.int32)}
+        for name in ("u", "v", "inv_z", "dist"):
+            flat[name] = np.zeros(q, np.float32)
+        check(self._L.orbfe_project_keyframe(h, K, ptr(off), ptr(s), ptr(k), pa,
+                                             *[ptr(flat[f]) for f in ("valid", "u", "v", "inv_z", "level", "dist")]))
+        return [{name: a[off[j]:off[j + 1]] for name, a in flat.items()} for j in range(K)]
+
+    def SearchByProjectionKeyFrames(self, Cur, poses, slots, kf_angles, scale_factors, th, ORBdist, skips=None, blocked=None,
+                                    check_orientation: bool = True):
+        """Tracking::Relocalization's SearchByProjection for K candidates in one call (orbfe_search_keyframe_mappoints_multi):
+        th[k] / ORBdist[k] per candidate (scalars apply to all), kf_angles[k] = pKF_k->mvKeysUn[.].angle of slots[k], blocked[k]
+        (or None) = Cur.mvpMapPoints[i2] != NULL -> (n_matches[K], match_cur[K, Cur.N]) with match_cur[k, i2] = position in
+        slots[k] or -1."""
+        h = self._h
+        K, off, s, pa, k = self._keyframe_operands(poses, slots, skips)
+        ka = None
+        if check_orientation:
+            ka = np.concatenate([np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in kf_angles] +
+                                [np.zeros(0, np.float32)]).astype(np.float32)
+            if len(ka) != len(s):
+                raise ValueError("kf_angles must hold one entry per slot")
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        tha = np.ascontiguousarray(np.broadcast_to(np.asarray(th, np.float32), (K,)) if K else np.zeros(1, np.float32))
+        od = np.ascontiguousarray(np.broadcast_to(np.asarray(ORBdist, np.int32), (K,)) if K else np.zeros(1, np.int32))
+        keep, bp = [], None
+        if blocked is not None:
+            addr = []
+            for b in blocked:
+                if b is None:
+                    addr.append(None)
+                    continue
+                b = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1)
+                if len(b) != Cur.N:
+                    raise ValueError("blocked[k] must hold one entry per feature of the frame")
+                keep.append(b)
+                addr.append(b.ctypes.data)
+            if len(addr) != K:
+                raise ValueError("one blocked entry (or None) per candidate")
+            bp = (C.c_void_p * max(K, 1))(*addr)
+        match = np.full((max(K, 1), max(Cur.N, 1)), -1, dtype=np.int32)
+        cnt = np.zeros(max(K, 1), dtype=np.int32)
+        check(self._L.orbfe_search_keyframe_mappoints_multi(h, C.byref(Cur.c), ptr(sf), len(sf), K, ptr(off), ptr(s), ptr(k), ptr(ka), pa,
+                                                            bp, ptr(tha), ptr(od), int(bool(check_orientation)), ptr(match), ptr(cnt)))
+        return cnt[:K], match[:K, :Cur.N]
+
     def pose_optimization(self, frame, slot, match, pose, K5, inv_level_sigma2, outlier=None):
         """Optimizer::PoseOptimization on the table (orbfe_pose_optimization_mappoints): `match` is what SearchLocalPoints
         returned for `frame` and `slot`, `pose` the 4 x 4 mTcw, inv_level_sigma2 = mvInvLevelSigma2 -> (n_inliers, Tcw_out
@@ -247,3 +369,47 @@ class MapPoints:
         `graph` is the ObservationGraph that holds the rows and the key frames' descriptors; the winners' bytes land in this
         table's descriptors -> (best_kf_slot, best_idx, valid); slots with valid = 0 keep what they hold."""
         return graph.distinctive_descriptors(slot, mp=self)
+
+
+def motion_model_mode(Tcw_cur, Tlw, mb: float, mono: bool) -> int:
+    """The `mode` of SearchByProjectionLastFrame from the two poses (src/ORBmatcher.cc:1494-1506): tlc = Rlw * twc + tlw with
+    twc = -Rcw^T tcw, in float32; 1 (bForward) when tlc.z > mb, 2 (bBackward) when -tlc.z > mb, never for a monocular frame."""
+    Tc = np.asarray(Tcw_cur, dtype=np.float32).reshape(4, 4)
+    Tl = np.asarray(Tlw, dtype=np.float32).reshape(4, 4)
+    twc = -(Tc[:3, :3].T @ Tc[:3, 3])
+    tlc = Tl[:3, :3] @ twc + Tl[:3, 3]
+    if mono:
+        return 0
+    return 1 if tlc[2] > np.float32(mb) else (2 if -tlc[2] > np.float32(mb) else 0)
+
+
+def track_with_motion_model(mp: MapPoints, cur, slot, last_octave, last_angle, Tcw_cur, Tlw, mb: float, mono: bool, K5, bounds,
+                            scale_factor: float, scale_factors, inv_level_sigma2, skip=None, blocked=None,
+                            check_orientation: bool = True, outlier=None):
+    """The device part of Tracking::TrackWithMotionModel (src/Tracking.cc:958-1010) on the resident map points, with no
+    per-point host work: `mode` from tlc, SearchByProjection(mCurrentFrame, mLastFrame, th, mono) with th = 15 for a monocular
+    sensor and 7 otherwise, once more with 2 * th when fewer than 20 matches came back (:969-973), then
+    Optimizer::PoseOptimization on the same slot[].  Tcw_cur = mVelocity * mLastFrame.mTcw, Tlw = mLastFrame.mTcw, K5 = fx fy
+    cx cy mbf, bounds = mnMinX mnMaxX mnMinY mnMaxY -> dict of nmatches, match [cur.N] (positions in slot[], -1 none), th (the
+    one that was used), mode, n_inliers, Tcw [4, 4], outlier [cur.N].  With fewer than 20 matches after the retry the
+    reference returns false before the optimisation: n_inliers is then 0, Tcw is Tcw_cur and no flag is set.  Everything
+    behind (discarding the outliers' map points, mnLastFrameSeen, nmatchesMap and the decision, :988-1010) stays with the caller."""
+    Tc = np.ascontiguousarray(Tcw_cur, dtype=np.float32).reshape(4, 4)
+    k5 = np.ascontiguousarray(K5, dtype=np.float32).reshape(5)
+    sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+    pose = camera_pose(Tc[:3, :3], Tc[:3, 3], k5[:4], k5[4], bounds, scale_factor, len(sf))
+    mode = motion_model_mode(Tc, Tlw, mb, mono)
+    th = 15.0 if mono else 7.0
+    args = (cur, slot, last_octave, last_angle, pose, sf)
+    kw = dict(mode=mode, skip=skip, blocked=blocked, check_orientation=check_orientation)
+    nmatches, match = mp.SearchByProjectionLastFrame(*args, th, **kw)
+    if nmatches < 20:
+        th = 2.0 * th
+        nmatches, match = mp.SearchByProjectionLastFrame(*args, th, **kw)
+    out = dict(nmatches=nmatches, match=match, th=th, mode=mode, n_inliers=0, Tcw=Tc.copy(),
+               outlier=np.zeros(cur.N, np.uint8) if outlier is None else np.asarray(outlier, np.uint8).copy())
+    if nmatches < 20:
+        return out
+    ni, Tout, flags, _, _ = mp.pose_optimization(cur, slot, match, Tc, k5, inv_level_sigma2, outlier=outlier)
+    out.update(n_inliers=ni, Tcw=Tout, outlier=flags)
+    return out
