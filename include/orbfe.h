@@ -1722,6 +1722,88 @@ int orbfe_fuse_mappoints(orbfe_mappoints *mp, orbfe_obsgraph *g, int n, const in
                          const uint8_t *skip, const float *scale_factors, const float *inv_level_sigma2, int n_levels,
                          float th, int chi2_gate, int32_t *best_idx /* [K*n] */, uint8_t *projected /* [K*n] or NULL */);
 
+/* ------------------------------------------------------------------------- */
+/* LoopClosing::ComputeSim3's two searches on the resident map points         */
+/* ------------------------------------------------------------------------- */
+/* One LEG of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1251-1477): one direction of one candidate, the source key frame's
+ * map points projected into the target key frame.  Rw / tw = the SOURCE key frame's GetRotation (row-major) / GetTranslation;
+ * sR / t = source camera to target camera, i.e. sR21, t21 for the leg KF1 -> KF2 and sR12, t12 for KF2 -> KF1 (:1268-1270);
+ * the rest is what the leg reads of the TARGET: fx fy cx cy, mnMinX .. mnMaxY, mfLogScaleFactor, mnScaleLevels.  The CALLER
+ * composes the 12 floats of sR / t per direction: s12*R12, (1.0/s12)*R12.t() and -sR21*t12 go through OpenCV's scaled-matrix
+ * and product routines, whose rounding depends on the OpenCV version and build, and have no place in a kernel. */
+typedef struct orbfe_sim3_leg {
+  float Rw[9], tw[3];
+  float sR[9], t[3];
+  float fx, fy, cx, cy;
+  float min_x, max_x, min_y, max_y;
+  float log_scale_factor;
+  int32_t n_levels;
+} orbfe_sim3_leg;
+
+/* The prologue of SearchBySim3 (:1298-1340, :1379-1420) for n_legs (<= 128) legs in ONE kernel launch.  Leg l owns entries
+ * [offsets[l], offsets[l+1]) of the concatenated slot[] / skip[] -- the source key frame's GetMapPointMatches() in slot space,
+ * as orbfe_obsgraph_get_keyframe_points returns it: slot -1 = no map point; skip = vbAlreadyMatched.  offsets[0] = 0; offsets
+ * never descend; a leg may be empty.  Outputs hold offsets[n_legs] entries; any may be NULL; valid = the point passes every
+ * test; where it is 0, u / v / dist / level are 0.  IEEE binary32 (binary64 where stated), no contraction, sums left to right,
+ * in this order:
+ *   reject slot -1; reject skip[i] (NULL = none); reject flags & ORBFE_MP_BAD;
+ *   c1 = ((Rw00*X + Rw01*Y) + Rw02*Z) + tw0 (rows 1, 2 likewise); c2 = ((sR00*c1x + sR01*c1y) + sR02*c1z) + t0 (likewise);
+ *   reject c2z < 0; invz = 1/c2z (the reference's 1.0/z in double, rounded to float, is the same float quotient:
+ *   53 >= 2*24 + 2); x = c2x*invz; y = c2y*invz; u = fx*x + cx; v = fy*y + cy;
+ *   KeyFrame::IsInImage (src/KeyFrame.cc:653-656): keep only u >= min_x && u < max_x && v >= min_y && v < max_y -- the upper
+ *   bounds are strict, and a NaN coordinate (c2 == 0) is rejected;
+ *   dist = (float)sqrt(sum (double)c2_i^2) -- the norm of the camera-frame vector, NOT of P - Ow;
+ *   reject dist < 0.8f*min || dist > 1.2f*max; there is no viewing-angle test;
+ *   level = clamp(ceil(log((double)(max/dist)) / (double)log_scale_factor), 0, n_levels-1) with the target's values.
+ * Only offsets, the slot list, the mask and the legs go up.  A slot below -1 or at or past the capacity, n_legs outside
+ * 0 .. 128, offsets that do not start at 0 or descend, a leg whose n_levels is not 1 .. 64 and NULL offsets / slot / legs return
+ * ORBFE_ERR_INVALID before anything is enqueued; n_legs == 0 or no point at all is ORBFE_OK with nothing touched. */
+int orbfe_project_sim3(orbfe_mappoints *mp, int n_legs, const int32_t *offsets /* [n_legs + 1] */, const int32_t *slot,
+                       const uint8_t *skip, const orbfe_sim3_leg *legs /* [n_legs] */, uint8_t *valid, float *u, float *v,
+                       int32_t *level, float *dist);
+
+/* SearchBySim3(pKF1, pKF2_k, vpMatches12_k, s12_k, R12_k, t12_k, th) for K (<= 64) candidates of ONE key frame KF1 as ONE call:
+ * both directions of all K candidates are 2K legs of one orbfe_project_sim3 launch, which writes the query windows (centre
+ * (u, v), radius th * scale_factors[level] of the leg's target, octaves [level-1, level]) where the window search reads them
+ * and gathers KF1's descriptors once for all K; the 2K best-keypoint searches (bound TH_HIGH) follow in one launch; the
+ * agreement check of :1461-1474 runs on the host over the one download.
+ *   slot1[N1] = KF1's GetMapPointMatches() in slot space (-1 = none), N1 = KF1->n; candidate k owns [offsets2[k], offsets2[k+1])
+ *   of slot2[], N2_k = KF2[k]->n entries; legs12[k] is the leg KF1 -> KF2_k (sR21, t21, KF2_k's intrinsics), legs21[k] the leg
+ *   KF2_k -> KF1.  scale_factors1 / scale_factors2 are KF1's / the candidates' mvScaleFactors, n_levels entries each.
+ *   matched12_in[k*N1 + i1] = the slot of vpMatches12_k[i1] at entry or -1 (NULL = none): vbAlreadyMatched1.
+ *   vbAlreadyMatched2 is the union of already2 (by the position in slot2[], NULL = none) and -- when g and kf2_slot are given --
+ *   GetIndexInKeyFrame from the observation rows on the device (:1288-1290): for every matched slot, the live entry whose
+ *   kf == kf2_slot[k] marks its idx if idx < N2_k; a matched slot at or past g's point_capacity has no row.
+ *   match12[k*N1 + i1] = i2 for mutually consistent pairs, else -1; n_found[k] = the return value.  What the caller does with
+ *   a pair (vpMatches12[i1] = vpMapPoints2[i2]) stays with the caller.
+ * With K = 1 the result equals orbfe_search_by_sim3 fed with orbfe_project_sim3's outputs and the table's descriptors, bit for
+ * bit.  Beyond orbfe_project_sim3's checks: K outside 0 .. 64, N2_k != KF2[k]->n, a matched slot below -1 or at or past the
+ * capacity, a kf2_slot outside the graph, a leg's n_levels above n_levels, bad views, NULL required arrays and handles on
+ * different devices return ORBFE_ERR_INVALID before anything is enqueued; K == 0 is ORBFE_OK.  Takes g's serialisation, then
+ * mp's. */
+int orbfe_search_by_sim3_mappoints_multi(orbfe_mappoints *mp, orbfe_obsgraph *g /* or NULL */, const orbfe_frame_view *KF1,
+                                         const int32_t *slot1 /* [N1] */, int n_candidates,
+                                         const orbfe_frame_view *const *KF2 /* [K] */, const int32_t *offsets2 /* [K + 1] */,
+                                         const int32_t *slot2, const orbfe_sim3_leg *legs12 /* [K] */,
+                                         const orbfe_sim3_leg *legs21 /* [K] */, const int32_t *matched12_in /* [K*N1] or NULL */,
+                                         const int32_t *kf2_slot /* [K], with g */, const uint8_t *already2 /* or NULL */,
+                                         const float *scale_factors1, const float *scale_factors2, int n_levels, float th,
+                                         int32_t *match12 /* [K*N1] */, int32_t *n_found /* [K] */);
+
+/* ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:335-451, LoopClosing::ComputeSim3 over
+ * mvpLoopMapPoints) as ONE call.  Its prologue (:366-405) is the Sim3 Fuse prologue term by term, so orbfe_project_fuse's
+ * kernel runs it at K = 1 without a graph (pose = the caller's decomposition of Scw, as for orbfe_fuse_mappoints), writes the
+ * windows and gathers the descriptors; the window search and the claim loop of :418-446 (TH_LOW) run behind it on the same
+ * stream.  slot[] = vpPoints in slot space (no -1: the reference dereferences every entry); skip[i] = spAlreadyFound.count(pMP)
+ * (NULL = none); matched[idx] = vpMatched[idx] != NULL at entry (NULL = none).  match[idx] = the POSITION IN slot[] of the point
+ * newly given to keypoint idx of KF, or -1; *n_matches = the return value; projected[i] (optional) = the point passed the
+ * prologue.  Equal to orbfe_search_by_projection_sim3 fed with orbfe_project_fuse's outputs and the table's descriptors, bit
+ * for bit.  Argument errors as for orbfe_fuse_mappoints; n == 0 is ORBFE_OK with match cleared. */
+int orbfe_search_by_projection_sim3_mappoints(orbfe_mappoints *mp, int n, const int32_t *slot, const uint8_t *skip,
+                                              const orbfe_camera_pose *pose, const orbfe_frame_view *KF,
+                                              const float *scale_factors, int n_levels, const uint8_t *matched, float th,
+                                              int32_t *match, int32_t *n_matches, uint8_t *projected /* [n] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

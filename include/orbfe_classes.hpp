@@ -1004,6 +1004,61 @@ class MapPointTable {
     nMatches.resize(K);
     return nMatches;
   }
+  // ORBmatcher::SearchBySim3 for K candidates of KF1 in one call (orbfe_search_by_sim3_mappoints_multi): slot1 = KF1's
+  // GetMapPointMatches() in slot space (-1 = none, one entry per keypoint), candidate k owns [offsets2[k], offsets2[k + 1]) of
+  // slot2 (one entry per keypoint of KF2s[k]); legs12[k] / legs21[k] are the two directions, composed by the caller
+  // (include/orbfe.h: orbfe_sim3_leg).  matched12In: empty, or K * N1 slots of vpMatches12_k at entry (-1 = NULL).
+  // vbAlreadyMatched2: already2 (empty, or one byte per entry of slot2) and / or, with graph and kf2Slot, GetIndexInKeyFrame from
+  // the observation rows.  match12[k * N1 + i1] = i2 or -1; returns nFound per candidate.
+  std::vector<int32_t> SearchBySim3(const FrameArrays& KF1, const std::vector<int32_t>& slot1, const std::vector<const FrameArrays*>& KF2s,
+                                    const std::vector<int32_t>& offsets2, const std::vector<int32_t>& slot2,
+                                    const std::vector<orbfe_sim3_leg>& legs12, const std::vector<orbfe_sim3_leg>& legs21,
+                                    const std::vector<float>& mvScaleFactors1, const std::vector<float>& mvScaleFactors2, float th,
+                                    std::vector<int32_t>& match12, const std::vector<int32_t>& matched12In = {},
+                                    const ObservationGraph* graph = nullptr, const std::vector<int32_t>& kf2Slot = {},
+                                    const std::vector<uint8_t>& already2 = {}) const {
+    const size_t K = KF2s.size(), n1 = slot1.size();
+    if (offsets2.size() != K + 1 || (size_t)offsets2.back() != slot2.size() || legs12.size() != K || legs21.size() != K ||
+        n1 != (size_t)KF1.c.n || (!matched12In.empty() && matched12In.size() != K * n1) || (graph && kf2Slot.size() != K) ||
+        (!already2.empty() && already2.size() != slot2.size()) || mvScaleFactors1.size() != mvScaleFactors2.size())
+      throw std::invalid_argument("MapPointTable::SearchBySim3: the lists disagree in length");
+    std::vector<const orbfe_frame_view*> views;
+    for (const FrameArrays* f : KF2s) views.push_back(&f->c);
+    match12.assign(K * n1 + 1, -1);
+    std::vector<int32_t> nFound(K + 1, 0);
+    check(orbfe_search_by_sim3_mappoints_multi(h_, graph ? graph->handle() : nullptr, &KF1.c, slot1.data(), (int)K, views.data(),
+                                               offsets2.data(), slot2.data(), legs12.data(), legs21.data(),
+                                               matched12In.empty() ? nullptr : matched12In.data(), graph ? kf2Slot.data() : nullptr,
+                                               already2.empty() ? nullptr : already2.data(), mvScaleFactors1.data(), mvScaleFactors2.data(),
+                                               (int)mvScaleFactors1.size(), th, match12.data(), nFound.data()),
+          "MapPointTable::SearchBySim3");
+    match12.resize(K * n1);
+    nFound.resize(K);
+    return nFound;
+  }
+  // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) in one call (orbfe_search_by_projection_sim3_mappoints): slot[] =
+  // vpPoints in slot space, pose = the caller's decomposition of Scw (as for Fuse's Sim3 overload); matched: empty, or one byte
+  // per keypoint (vpMatched[idx] != NULL); skip: empty, or one byte per slot (spAlreadyFound).  match[idx] = position in slot[] of
+  // the point newly given to keypoint idx, or -1.  Returns nmatches.
+  int SearchByProjection(const FrameArrays& KF, const orbfe_camera_pose& pose, const std::vector<int32_t>& slot,
+                         const std::vector<float>& mvScaleFactors, float th, std::vector<int32_t>& match,
+                         const std::vector<uint8_t>& matched = {}, const std::vector<uint8_t>& skip = {},
+                         std::vector<uint8_t>* projected = nullptr) const {
+    const size_t n = slot.size();
+    if ((!skip.empty() && skip.size() != n) || (!matched.empty() && matched.size() != (size_t)KF.c.n))
+      throw std::invalid_argument("MapPointTable::SearchByProjection: one skip entry per slot, one matched entry per keypoint");
+    match.assign((size_t)KF.c.n + 1, -1);
+    if (projected) projected->assign(n + 1, 0);
+    int32_t nmatches = 0;
+    check(orbfe_search_by_projection_sim3_mappoints(h_, (int)n, slot.data(), skip.empty() ? nullptr : skip.data(), &pose, &KF.c,
+                                                    mvScaleFactors.data(), (int)mvScaleFactors.size(),
+                                                    matched.empty() ? nullptr : matched.data(), th, match.data(), &nmatches,
+                                                    projected ? projected->data() : nullptr),
+          "MapPointTable::SearchByProjection");
+    match.resize((size_t)KF.c.n);
+    if (projected) projected->resize(n);
+    return nmatches;
+  }
   orbfe_mappoints* handle() const { return h_; }
   // the tail of Optimizer::OptimizeEssentialGraph (:1070-1103) on the table: the position of slot[p] becomes
   // Sout[r]^-1 .map(Scw[r] .map(P)), r = refVertex[p] (-1: left alone); Scw / SiwOut 8 doubles per vertex

@@ -39,6 +39,14 @@ class FrameViewC(C.Structure):
                 ("resident", C.c_void_p)]
 
 
+class Sim3LegC(C.Structure):
+    """orbfe_sim3_leg: one direction of one SearchBySim3 candidate (src/ORBmatcher.cc:1251-1477)."""
+    _fields_ = [("Rw", C.c_float * 9), ("tw", C.c_float * 3), ("sR", C.c_float * 9), ("t", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
+
+
 class CameraPoseC(C.Structure):
     """orbfe_camera_pose: what Frame::isInFrustum reads of the Frame (src/Frame.cc:292-353)."""
     _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3),
@@ -136,6 +144,7 @@ EXPORTS = [
     "orbfe_project_fuse", "orbfe_fuse_mappoints",
     "orbfe_project_last_frame", "orbfe_search_last_frame_mappoints", "orbfe_project_keyframe",
     "orbfe_search_keyframe_mappoints_multi",
+    "orbfe_project_sim3", "orbfe_search_by_sim3_mappoints_multi", "orbfe_search_by_projection_sim3_mappoints",
 ]
 
 _lib = None
@@ -371,6 +380,9 @@ def load():
     L.orbfe_search_last_frame_mappoints.argtypes = [vp, ci, vp, vp, vp, vp, cpp, fwp, vp, ci, vp, ci, cf, ci, vp, vp, vp]
     L.orbfe_project_keyframe.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_search_keyframe_mappoints_multi.argtypes = [vp, fwp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp]
+    L.orbfe_project_sim3.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbfe_search_by_sim3_mappoints_multi.argtypes = [vp, vp, fwp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
+    L.orbfe_search_by_projection_sim3_mappoints.argtypes = [vp, ci, vp, vp, cpp, fwp, vp, ci, vp, cf, vp, vp, vp]
     _lib = L
     return L
 

@@ -1,7 +1,7 @@
 // k_project.hip -- the pose arithmetic in front of Tracking::SearchLocalPoints on the device-resident map points:
 // Frame::isInFrustum (src/Frame.cc:292-353) with MapPoint::PredictScale, the prologue of ORBmatcher::Fuse for K key frames
-// (k_project_fuse), the prologues of the last-frame and key-frame SearchByProjection (k_project_track), and the scatter that
-// keeps the table up to date.
+// (k_project_fuse), the prologues of the last-frame and key-frame SearchByProjection (k_project_track), the prologue of
+// SearchBySim3 for many legs (k_project_sim3), and the scatter that keeps the table up to date.
 // The kernels are bandwidth-trivial (64 bytes of table per point, a few thousand points): one lane per point, the table
 // records as 16-byte loads, the descriptor rows moved by the whole workgroup as 16-byte pieces.
 #include <hip/hip_runtime.h>
@@ -286,6 +286,100 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_track(const TrackAr
   }
 }
 
+// The prologue of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1298-1340, :1379-1420) for many legs: blockIdx.y is the leg (one
+// direction of one candidate), a workgroup owns 256 consecutive points of it, and a leg shorter than the longest leaves its
+// spare workgroups at once.  The leg record and its span are uniform reads.  The arithmetic is include/orbfe.h's
+// (orbfe_project_sim3), operation by operation.  The reference's 1.0 / z in double, rounded to float, is the float division
+// below: a double quotient of two floats rounded to float is correctly rounded (53 >= 2 * 24 + 2).
+__global__ __launch_bounds__(kProjectThreads) void k_project_sim3(const Sim3Args a) {
+  const Sim3Span sp = a.span[blockIdx.y];
+  const int base = blockIdx.x * kProjectThreads;
+  if (base >= sp.n) return;  // (workgroup-uniform)
+  const int i = base + (int)threadIdx.x;
+  if (i < sp.n) {
+    const orbfe_sim3_leg& c = a.leg[blockIdx.y];
+    const size_t o = (size_t)sp.outOff + i;
+    const int s = a.slot[(size_t)sp.slotOff + i];
+    // pMP && !vbAlreadyMatched[i] && !pMP->isBad() (:1300-1306): slot -1 is "no map point" and reads nothing of the table
+    float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+    uint8_t fl = ORBFE_MP_BAD;
+    if (s >= 0) { r0 = a.table.rec[2 * (size_t)s]; r1 = a.table.rec[2 * (size_t)s + 1]; fl = a.table.flags[s]; }
+    bool ok = s >= 0 && !(a.skip && a.skip[o]) && !(fl & ORBFE_MP_BAD);
+    const float X = r0.x, Y = r0.y, Z = r0.z, minD = r0.w, maxD = r1.w;
+    // source camera (:1309), then target camera (:1310)
+    const float x1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rw[0], X), __fmul_rn(c.Rw[1], Y)), __fmul_rn(c.Rw[2], Z)), c.tw[0]);
+    const float y1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rw[3], X), __fmul_rn(c.Rw[4], Y)), __fmul_rn(c.Rw[5], Z)), c.tw[1]);
+    const float z1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rw[6], X), __fmul_rn(c.Rw[7], Y)), __fmul_rn(c.Rw[8], Z)), c.tw[2]);
+    const float x2 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.sR[0], x1), __fmul_rn(c.sR[1], y1)), __fmul_rn(c.sR[2], z1)), c.t[0]);
+    const float y2 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.sR[3], x1), __fmul_rn(c.sR[4], y1)), __fmul_rn(c.sR[5], z1)), c.t[1]);
+    const float z2 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.sR[6], x1), __fmul_rn(c.sR[7], y1)), __fmul_rn(c.sR[8], z1)), c.t[2]);
+    if (z2 < 0.0f) ok = false;  // (:1313)
+    const float invz = __fdiv_rn(1.0f, z2);
+    const float x = __fmul_rn(x2, invz), y = __fmul_rn(y2, invz);
+    const float u = __fadd_rn(__fmul_rn(c.fx, x), c.cx);
+    const float v = __fadd_rn(__fmul_rn(c.fy, y), c.cy);
+    // KeyFrame::IsInImage (src/KeyFrame.cc:653-656): the upper bounds are strict; a NaN coordinate is rejected here
+    if (!(u >= c.min_x && u < c.max_x && v >= c.min_y && v < c.max_y)) ok = false;
+    // cv::norm(p3Dc2) (:1330) accumulates in double: the camera-frame vector, not P - Ow
+    const double dx = (double)x2, dy = (double)y2, dz = (double)z2;
+    const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+    const float dist = (float)__dsqrt_rn(d2);
+    if (dist < __fmul_rn(0.8f, minD) || dist > __fmul_rn(1.2f, maxD)) ok = false;
+    int lv = 0;
+    if (ok) {  // MapPoint::PredictScale (:1337)
+      const float ratio = __fdiv_rn(maxD, dist);
+      const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
+      const int top = c.n_levels - 1;
+      lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
+    }
+    if (a.valid) a.valid[o] = ok;
+    if (a.u) a.u[o] = ok ? u : 0.0f;
+    if (a.v) a.v[o] = ok ? v : 0.0f;
+    if (a.level) a.level[o] = lv;
+    if (a.dist) a.dist[o] = ok ? dist : 0.0f;
+    if (a.qx) {  // the windows of :1340-1359 as orbfe_search_by_sim3 builds them from the arrays above
+      const float* scale = a.scale + ((sp.flags & 2) ? a.nLevels : 0);
+      a.qx[o] = ok ? u : 0.0f;
+      a.qy[o] = ok ? v : 0.0f;
+      a.qr[o] = __fmul_rn(a.th, scale[lv]);
+      a.qmin[o] = lv - 1;
+      a.qmax[o] = lv;
+      a.qactive[o] = ok;
+    }
+  }
+  if (a.qdesc && (sp.flags & 1)) {  // (workgroup-uniform) the leg's descriptors; a point without a slot gets zeros, nothing reads them
+    const int cnt = sp.n - base < kProjectThreads ? sp.n - base : kProjectThreads;
+    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
+    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
+    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
+      const size_t q = (size_t)sp.slotOff + base + (p >> 1);
+      const int s = a.slot[q];
+      dst[2 * q + (p & 1)] = s >= 0 ? src[2 * (size_t)s + (p & 1)] : make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
+
+// vbAlreadyMatched2 (:1282-1292) from the observation rows: one lane per (candidate, keypoint of KF1)
+__global__ __launch_bounds__(kProjectThreads) void k_sim3_already(const ObsEntry* __restrict__ rows, const ObsPointMeta* __restrict__ meta,
+                                                                  int rowWidth, int pointCap, int n1, const int32_t* __restrict__ matched,
+                                                                  const int32_t* __restrict__ kfSlot, const int32_t* __restrict__ offsets2,
+                                                                  uint8_t* __restrict__ already2) {
+  const int k = (int)blockIdx.y;
+  const int i = blockIdx.x * kProjectThreads + (int)threadIdx.x;
+  if (i >= n1) return;
+  const int s = matched[(size_t)k * n1 + i];
+  if (s < 0 || s >= pointCap) return;
+  const int off = offsets2[k], n2 = offsets2[k + 1] - off, kf = kfSlot[k];
+  int cnt = meta[s].count;
+  cnt = cnt < rowWidth ? cnt : rowWidth;
+  const ObsEntry* row = rows + (size_t)s * rowWidth;
+  for (int e = 0; e < cnt; e++)
+    if (row[e].kf == kf) {
+      const int idx = (int)row[e].idx;
+      if (idx < n2) already2[(size_t)off + idx] = 1;
+    }
+}
+
 __global__ __launch_bounds__(kProjectThreads) void k_mappoints_scatter(const MapPointsDevice t, int n, const int32_t* __restrict__ slot,
                                                                        const float4* __restrict__ rec, const uint8_t* __restrict__ flags,
                                                                        const uint8_t* __restrict__ desc) {
@@ -333,6 +427,18 @@ void launch_project_track(hipStream_t s, const TrackArgs& a, int maxN) {
   const dim3 grid((maxN + kProjectThreads - 1) / kProjectThreads, a.K);
   if (a.form == 0) hipLaunchKernelGGL(k_project_track<0>, grid, dim3(kProjectThreads), 0, s, a);
   else hipLaunchKernelGGL(k_project_track<1>, grid, dim3(kProjectThreads), 0, s, a);
+}
+
+void launch_project_sim3(hipStream_t s, const Sim3Args& a, int maxN) {
+  if (maxN <= 0 || a.nLegs <= 0 || a.nLegs > kSim3MaxLegs) return;
+  hipLaunchKernelGGL(k_project_sim3, dim3((maxN + kProjectThreads - 1) / kProjectThreads, a.nLegs), dim3(kProjectThreads), 0, s, a);
+}
+
+void launch_sim3_already(hipStream_t s, const ObsEntry* rows, const ObsPointMeta* meta, int rowWidth, int pointCap, int K, int n1,
+                         const int32_t* matched, const int32_t* kfSlot, const int32_t* offsets2, uint8_t* already2) {
+  if (K <= 0 || n1 <= 0) return;
+  hipLaunchKernelGGL(k_sim3_already, dim3((n1 + kProjectThreads - 1) / kProjectThreads, K), dim3(kProjectThreads), 0, s, rows, meta, rowWidth,
+                     pointCap, n1, matched, kfSlot, offsets2, already2);
 }
 
 void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,

@@ -109,4 +109,67 @@ inline const char* track_check_operands(int capacity, int K, const int32_t* offs
   return nullptr;
 }
 
+// The operands of orbfe_project_sim3 that need no handle: n_legs legs (at most kSim3MaxLegRecords) over concatenated lists --
+// offsets[n_legs + 1] starts at 0 and never descends --, slots of a table of `capacity` slots or -1 (no map point), one leg
+// record each.  n_levels > 0: the caller's level tables hold that many entries and no leg may predict past them.  Nothing is
+// read past what n_legs and offsets[n_legs] say.
+constexpr int kSim3MaxCandidates = 64, kSim3MaxLegRecords = 2 * kSim3MaxCandidates;
+inline const char* sim3_check_slots(int capacity, int n, const int32_t* slot) {
+  if (n < 0) return "negative count";
+  if (n > 0 && !slot) return "NULL slot list";
+  for (int i = 0; i < n; i++)
+    if (slot[i] < -1 || slot[i] >= capacity) return "slot outside [-1, capacity)";
+  return nullptr;
+}
+inline const char* sim3_check_offsets(int K, const int32_t* offsets) {
+  if (!offsets) return "NULL offsets";
+  if (offsets[0] != 0) return "offsets must start at 0";
+  for (int k = 0; k < K; k++)
+    if (offsets[k + 1] < offsets[k]) return offsets[k + 1] < 0 ? "negative count" : "offsets descend";
+  return nullptr;
+}
+inline const char* sim3_check_leg_records(int n, const orbfe_sim3_leg* legs, int n_levels) {
+  if (n > 0 && !legs) return "NULL leg array";
+  for (int l = 0; l < n; l++) {
+    if (legs[l].n_levels < 1 || legs[l].n_levels > kFuseMaxPoseLevels) return "bad leg (n_levels must be 1 .. 64)";
+    if (n_levels > 0 && legs[l].n_levels > n_levels) return "a leg predicts more levels than the level table holds";
+  }
+  return nullptr;
+}
+inline const char* sim3_check_legs(int capacity, int n_legs, const int32_t* offsets, const int32_t* slot, const orbfe_sim3_leg* legs,
+                                   int n_levels) {
+  if (n_legs < 0) return "negative number of legs";
+  if (n_legs > kSim3MaxLegRecords) return "more than 128 legs in one call";
+  if (n_legs == 0) return nullptr;
+  if (const char* e = sim3_check_offsets(n_legs, offsets)) return e;
+  if (const char* e = sim3_check_slots(capacity, offsets[n_legs], slot)) return e;
+  return sim3_check_leg_records(n_legs, legs, n_levels);
+}
+
+// The operands of orbfe_search_by_sim3_mappoints_multi that need no handle and no view: KF1's n1 slots, K candidates (at most
+// kSim3MaxCandidates) over the concatenated slot2[] (offsets2[K + 1]), the two leg arrays, the matched slots ([K * n1], NULL:
+// none; -1 or a slot of the table) and -- with_graph -- the K kf slots of a graph of kf_capacity key frames.
+inline const char* sim3_check_search(int capacity, int n1, const int32_t* slot1, int K, const int32_t* offsets2, const int32_t* slot2,
+                                     const orbfe_sim3_leg* legs12, const orbfe_sim3_leg* legs21, const int32_t* matched12_in,
+                                     const int32_t* kf2_slot, bool with_graph, int kf_capacity, int n_levels) {
+  if (K < 0) return "negative number of candidates";
+  if (K > kSim3MaxCandidates) return "more than 64 candidates in one call";
+  if (n_levels < 1 || n_levels > kFuseMaxPoseLevels) return "n_levels must be 1 .. 64";
+  if (const char* e = sim3_check_slots(capacity, n1, slot1)) return e;
+  if (K == 0) return nullptr;
+  if (const char* e = sim3_check_offsets(K, offsets2)) return e;
+  if (const char* e = sim3_check_slots(capacity, offsets2[K], slot2)) return e;
+  if (const char* e = sim3_check_leg_records(K, legs12, n_levels)) return e;
+  if (const char* e = sim3_check_leg_records(K, legs21, n_levels)) return e;
+  if (matched12_in)
+    for (size_t i = 0; i < (size_t)K * (size_t)n1; i++)
+      if (matched12_in[i] < -1 || matched12_in[i] >= capacity) return "matched slot outside [-1, capacity)";
+  if (with_graph) {
+    if (!kf2_slot) return "NULL kf2_slot array";
+    for (int k = 0; k < K; k++)
+      if (kf2_slot[k] < 0 || kf2_slot[k] >= kf_capacity) return "kf slot outside [0, kf_capacity)";
+  }
+  return nullptr;
+}
+
 }  // namespace orbfe

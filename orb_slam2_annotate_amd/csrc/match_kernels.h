@@ -213,6 +213,30 @@ struct TrackArgs {
   const float* scale;
 };
 void launch_project_track(hipStream_t s, const TrackArgs& a, int maxN /* the longest list of the K jobs */);
+// k_project_sim3: the prologue of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1298-1340 and :1379-1420) for nLegs legs in ONE
+// launch; a leg is one direction of one candidate (blockIdx.y = leg, one lane per point, a workgroup owns 256 consecutive
+// points of its leg).  Leg l reads slot[span.slotOff + i] (-1: no map point) and writes every array at [span.outOff + i], so
+// the K "1 -> 2" legs of a call share ONE copy of KF1's slot list and -- span.flags & 1 on the first of them only -- one gather
+// of its descriptors into qdesc[(span.slotOff + i) * 32].  span.flags & 2: the leg's target uses the second level table
+// (scale + nLevels).  Two sets of outputs, either may be absent, as for k_project_fuse; the arithmetic is include/orbfe.h's
+// (orbfe_project_sim3), operation by operation.
+constexpr int kSim3MaxLegs = 128;
+struct Sim3Span { int32_t slotOff, n, outOff, flags; };
+struct Sim3Args {
+  MapPointsDevice table;
+  int nLegs, nLevels;
+  const Sim3Span* span /* [nLegs] */; const orbfe_sim3_leg* leg /* [nLegs] */;
+  const int32_t* slot; const uint8_t* skip /* by output position, NULL: none */;
+  uint8_t* valid; float* u; float* v; int32_t* level; float* dist;
+  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive; uint8_t* qdesc;
+  const float* scale /* [nLevels] or [2 * nLevels] */; float th;
+};
+void launch_project_sim3(hipStream_t s, const Sim3Args& a, int maxN /* the longest leg */);
+// vbAlreadyMatched2 of SearchBySim3 (:1282-1292) from the observation rows: for candidate k and keypoint i1 of KF1 with
+// matched[k * n1 + i1] = slot s >= 0, the live entry of s's row whose kf == kfSlot[k] marks already2[offsets2[k] + idx] when
+// idx < offsets2[k + 1] - offsets2[k] (MapPoint::GetIndexInKeyFrame); a slot at or past pointCap has no row.  Byte stores of 1.
+void launch_sim3_already(hipStream_t s, const ObsEntry* rows, const ObsPointMeta* meta, int rowWidth, int pointCap, int K, int n1,
+                         const int32_t* matched, const int32_t* kfSlot, const int32_t* offsets2, uint8_t* already2);
 // orbfe_mappoints_update: n staged entries (slot, the two records, flags, descriptors or NULL = keep) into their slots
 void launch_mappoints_scatter(hipStream_t s, const MapPointsDevice& t, int n, const int32_t* slot, const float4* rec,
                               const uint8_t* flags, const uint8_t* desc);

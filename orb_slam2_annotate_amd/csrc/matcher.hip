@@ -578,6 +578,44 @@ struct WindowJob {
   // descriptors and, in the last-frame form, blockVal (Observations() > 0)
   struct TrackProducer* track = nullptr;
   int trackK = 0;
+  // SIM3 PRODUCER (BEST jobs only): the jobs of a call name ONE Sim3Producer and the leg they search for; the query arrays above
+  // are NULL -- ONE k_project_sim3 launch writes the windows of all legs from the map-point table, and KF1's descriptors once
+  struct Sim3Producer* sim3 = nullptr;
+  int sim3Leg = 0;
+};
+// The prologue of SearchBySim3 for nLegs legs.  slot[] holds every source list once (KF1's, then the candidates'); the outputs
+// and skip[] are by OUTPUT position (a leg's span says where both start), so K legs may read one list.
+static_assert(kSim3MaxLegs == kSim3MaxLegRecords, "the kernel's leg limit is the one sim3_check_legs enforces");
+struct Sim3Producer {
+  MapPointsDevice table;
+  int nLegs = 0;
+  const Sim3Span* span = nullptr;        // [nLegs]
+  const orbfe_sim3_leg* leg = nullptr;   // [nLegs]
+  const int32_t* slot = nullptr; size_t nSlot = 0;
+  const uint8_t* skip = nullptr; size_t nOut = 0;  // [nOut] or NULL
+  const float* scale = nullptr;          // [nScale] level table(s)
+  int nScale = 0, nLevels = 0;
+  float th = 0.0f;
+  // vbAlreadyMatched2 from the observation rows (graph != NULL): a scatter into skip[already2Off ..] ahead of the prologue
+  const ObsGraphDevice* graph = nullptr;
+  const int32_t *matched = nullptr, *kfSlot = nullptr, *offsets2 = nullptr;
+  int K = 0, n1 = 0;
+  size_t already2Off = 0;
+  int longest() const {
+    int m = 0;
+    for (int l = 0; l < nLegs; l++) m = span[l].n > m ? span[l].n : m;
+    return m;
+  }
+};
+struct Sim3Dev {
+  Sim3Span* span = nullptr;
+  orbfe_sim3_leg* leg = nullptr;
+  int32_t *slot = nullptr, *matched = nullptr, *kfSlot = nullptr, *offsets2 = nullptr;
+  uint8_t* skip = nullptr;
+  float* scale = nullptr;
+  float *qx = nullptr, *qy = nullptr, *qr = nullptr;
+  int32_t *qmin = nullptr, *qmax = nullptr;
+  uint8_t *qactive = nullptr, *qdesc = nullptr;
 };
 // The prologue of the last-frame (form 0) or key-frame (form 1) SearchByProjection for K jobs over concatenated lists
 struct TrackProducer {
@@ -743,12 +781,46 @@ TrackArgs track_args(const TrackProducer& P, const TrackDev& T) {
   return ta;
 }
 
+hipError_t stage_sim3_inputs(Arena* a, const Sim3Producer& P, Sim3Dev* S) {
+  TRY(up(a, &S->span, P.span, (size_t)P.nLegs));
+  TRY(up(a, &S->leg, P.leg, (size_t)P.nLegs));
+  TRY(up(a, &S->slot, P.slot, P.nSlot));
+  if (P.skip) TRY(up(a, &S->skip, P.skip, P.nOut));
+  if (P.scale) TRY(up(a, &S->scale, P.scale, (size_t)P.nScale));
+  if (P.graph) {
+    TRY(up(a, &S->matched, P.matched, (size_t)P.K * P.n1));
+    TRY(up(a, &S->kfSlot, P.kfSlot, (size_t)P.K));
+    TRY(up(a, &S->offsets2, P.offsets2, (size_t)P.K + 1));
+  }
+  return hipSuccess;
+}
+void stage_sim3_scratch(Arena* a, const Sim3Producer& P, Sim3Dev* S) {
+  const size_t q = P.nOut;
+  S->qx = carve<float>(a, q); S->qy = carve<float>(a, q); S->qr = carve<float>(a, q);
+  S->qmin = carve<int32_t>(a, q); S->qmax = carve<int32_t>(a, q);
+  S->qactive = carve<uint8_t>(a, q);
+  S->qdesc = carve<uint8_t>(a, P.nSlot * 32);
+}
+Sim3Args sim3_args(const Sim3Producer& P, const Sim3Dev& S) {
+  Sim3Args sa{};
+  sa.table = P.table; sa.nLegs = P.nLegs; sa.nLevels = P.nLevels; sa.span = S.span; sa.leg = S.leg; sa.slot = S.slot; sa.skip = S.skip;
+  sa.qx = S.qx; sa.qy = S.qy; sa.qr = S.qr; sa.qmin = S.qmin; sa.qmax = S.qmax; sa.qactive = S.qactive; sa.qdesc = S.qdesc;
+  sa.scale = S.scale; sa.th = P.th;
+  return sa;
+}
+// the scatter of vbAlreadyMatched2 from the observation rows, ahead of the prologue on the same stream
+void sim3_already(hipStream_t s, const Sim3Producer& P, const Sim3Dev& S) {
+  if (!P.graph) return;
+  launch_sim3_already(s, P.graph->rows, P.graph->meta, P.graph->rowWidth, P.graph->pointCap, P.K, P.n1, S.matched, S.kfSlot, S.offsets2,
+                      S.skip + P.already2Off);
+}
+
 hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, const FuseDev& fuse) {
   const WindowJob& J = jobs[j];
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
   D = JobDev{};
-  D.withDesc = J.f->desc && (J.qdesc || J.producer || J.fuse || J.track);
+  D.withDesc = J.f->desc && (J.qdesc || J.producer || J.fuse || J.track || J.sim3);
   D.withUr = (J.qur || J.producer || (J.track && J.track->form == 0)) && J.f->u_right;
   if (const orbfe_frame* R = J.f->resident) {
     D.x = R->dx; D.y = R->dy; D.oct = R->doct; D.ur = J.f->u_right ? R->dur : nullptr; D.desc = D.withDesc ? R->ddesc : nullptr;
@@ -773,6 +845,7 @@ hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, con
   } else if (J.fuse) {  // (the call's one FuseProducer has uploaded everything: stage_fuse_inputs)
     if (J.fuse->gate) D.invSigma2 = fuse.invSigma2;
   } else if (J.track) {  // (the call's one TrackProducer has uploaded everything: stage_track_inputs)
+  } else if (J.sim3) {   // (likewise the call's one Sim3Producer: stage_sim3_inputs)
   } else {
     TRY(up(a, &D.qx, J.qx, q)); TRY(up(a, &D.qy, J.qy, q)); TRY(up(a, &D.qr, J.qr, q));
     TRY(up(a, &D.qmin, J.qmin, q)); TRY(up(a, &D.qmax, J.qmax, q));
@@ -826,10 +899,17 @@ OwnerPlace owner_place(const WindowJob& J) {
 
 // Region 3, job j's part: what never leaves the device -- the grid of an uploaded frame, the query arrays a producer
 // writes, the claim kernel's lists and scratch
-void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev, const FuseDev& fuse, const TrackDev& track) {
+void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev, const FuseDev& fuse, const TrackDev& track,
+                   const Sim3Dev& sim3) {
   const WindowJob& J = jobs[j];
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
+  if (J.sim3) {  // the leg's part of what the one k_project_sim3 launch writes; its descriptors lie where its slot list does
+    const Sim3Span& sp = J.sim3->span[J.sim3Leg];
+    const size_t o = (size_t)sp.outOff;
+    D.qx = sim3.qx + o; D.qy = sim3.qy + o; D.qr = sim3.qr + o; D.qmin = sim3.qmin + o; D.qmax = sim3.qmax + o;
+    D.qactive = sim3.qactive + o; D.qdesc = sim3.qdesc + (size_t)sp.slotOff * 32;
+  }
   if (J.track) {  // job k's part of what the one k_project_track launch writes
     const size_t o = (size_t)J.track->offsets[J.trackK];
     D.qx = track.qx + o; D.qy = track.qy + o; D.qr = track.qr + o; D.qmin = track.qmin + o; D.qmax = track.qmax + o;
@@ -911,6 +991,8 @@ struct WindowCall {
   FuseDev fuse;
   const TrackProducer* trackProducer = nullptr;  // likewise the one TrackProducer
   TrackDev track;
+  const Sim3Producer* sim3Producer = nullptr;  // likewise the one Sim3Producer
+  Sim3Dev sim3;
   size_t claimLds = 0;
   int totalBlocks = 0;
 };
@@ -925,6 +1007,8 @@ hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, in
   if (c->fuseProducer) TRY(stage_fuse_inputs(a, *c->fuseProducer, &c->fuse));
   for (int j = 0; j < nJobs && !c->trackProducer; j++) c->trackProducer = jobs[j].track;
   if (c->trackProducer) TRY(stage_track_inputs(a, *c->trackProducer, &c->track));
+  for (int j = 0; j < nJobs && !c->sim3Producer; j++) c->sim3Producer = jobs[j].sim3;
+  if (c->sim3Producer) TRY(stage_sim3_inputs(a, *c->sim3Producer, &c->sim3));
   for (int j = 0; j < nJobs; j++) TRY(stage_inputs(a, jobs, j, c->dev.data(), c->fuse));
   c->dClaims = carve<ClaimJob>(a, (size_t)nClaim);
   c->dSearches = carve<WindowSearchJob>(a, nJobs > 1 ? (size_t)nJobs : 0);
@@ -939,7 +1023,8 @@ hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, in
     for (int j = 0; j < nJobs; j++) withUr = withUr || c->dev[j].withUr;
     stage_track_scratch(a, *c->trackProducer, withUr, &c->track);
   }
-  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data(), c->fuse, c->track);
+  if (c->sim3Producer) stage_sim3_scratch(a, *c->sim3Producer, &c->sim3);
+  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data(), c->fuse, c->track, c->sim3);
   for (int j = 0; j < nJobs; j++) {
     if (jobs[j].claim) {
       c->claims.push_back(claim_job(jobs[j], c->dev[j], K));
@@ -964,6 +1049,12 @@ hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, const Windo
   }
   if (c.trackProducer) {  // likewise
     launch_project_track(ar->stream, track_args(*c.trackProducer, c.track), c.trackProducer->longest());
+    TRY(hipGetLastError());
+  }
+  if (c.sim3Producer) {  // likewise, behind the scatter of vbAlreadyMatched2 when the graph supplies it
+    sim3_already(ar->stream, *c.sim3Producer, c.sim3);
+    TRY(hipGetLastError());
+    launch_project_sim3(ar->stream, sim3_args(*c.sim3Producer, c.sim3), c.sim3Producer->longest());
     TRY(hipGetLastError());
   }
   for (int j = 0; j < nJobs; j++)
@@ -1040,9 +1131,14 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
     const WindowJob& J = jobs[j];
     if (J.f->resident && J.f->resident->device != device) return fail(ORBFE_ERR_INVALID, "resident frame lives on another device");
     if (J.producer && (!J.claim || J.claim->mode != CLAIM_RATIO)) return fail(ORBFE_ERR_INVALID, "a producer needs a CLAIM_RATIO job");
-    if (J.fuse && (!J.bestOut || J.fuse != jobs[0].fuse || J.nq != J.fuse->n || J.fuseK < 0 || J.fuseK >= J.fuse->K))
-      return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST jobs that all name it");
-    if (!J.fuse && jobs[0].fuse) return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST jobs that all name it");
+    // (a fuse producer feeds BEST jobs -- Fuse -- or CLAIM_BEST jobs: the Sim3 SearchByProjection, whose prologue is Fuse's)
+    if (J.fuse && ((!J.bestOut && !(J.claim && J.claim->mode == CLAIM_BEST)) || J.fuse != jobs[0].fuse || J.nq != J.fuse->n ||
+                   J.fuseK < 0 || J.fuseK >= J.fuse->K))
+      return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST or CLAIM_BEST jobs that all name it");
+    if (!J.fuse && jobs[0].fuse) return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST or CLAIM_BEST jobs that all name it");
+    if (J.sim3 != jobs[0].sim3 || (J.sim3 && (!J.bestOut || J.sim3Leg < 0 || J.sim3Leg >= J.sim3->nLegs ||
+                                              J.nq != J.sim3->span[J.sim3Leg].n)))
+      return fail(ORBFE_ERR_INVALID, "a sim3 producer needs BEST jobs that all name it");
     if (J.track != jobs[0].track ||
         (J.track && (!J.claim || J.claim->mode != CLAIM_BEST || J.trackK < 0 || J.trackK >= J.track->K ||
                      J.nq != J.track->offsets[J.trackK + 1] - J.track->offsets[J.trackK])))
@@ -1744,4 +1840,178 @@ extern "C" int orbfe_search_by_sim3(int device, const orbfe_frame_view* KF1, con
   }
   *n_found = nFound;
   return ORBFE_OK;
+}
+
+namespace {
+// k_project_sim3 alone (a point to project, arguments checked, the table held): spans, legs, slots and the mask up, one
+// launch, the five arrays back in one copy
+int project_sim3_run(int device, const Sim3Producer& P, uint8_t* valid, float* u, float* v, int32_t* level, float* dist) {
+  const size_t q = P.nOut;
+  Sim3Dev S;
+  Sim3Args sa{};
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    S = Sim3Dev{};
+    TRY(stage_sim3_inputs(a, P, &S));
+    sa = sim3_args(P, S);
+    open_span(a);
+    sa.level = carve<int32_t>(a, q); sa.u = carve<float>(a, q); sa.v = carve<float>(a, q); sa.dist = carve<float>(a, q);
+    sa.valid = carve<uint8_t>(a, q);
+    return close_span(a);
+  };
+  HIPCHK(arena_stage(device, &ar, stage));
+  HIPCHK(flush(ar));
+  launch_project_sim3(ar->stream, sa, P.longest());
+  HIPCHK(hipGetLastError());
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  if (level) std::memcpy(level, mirror_of(ar, sa.level), q * 4);
+  if (u) std::memcpy(u, mirror_of(ar, sa.u), q * 4);
+  if (v) std::memcpy(v, mirror_of(ar, sa.v), q * 4);
+  if (dist) std::memcpy(dist, mirror_of(ar, sa.dist), q * 4);
+  if (valid) std::memcpy(valid, mirror_of(ar, sa.valid), q);
+  return ORBFE_OK;
+}
+}  // namespace
+
+extern "C" int orbfe_project_sim3(orbfe_mappoints* mp, int n_legs, const int32_t* offsets, const int32_t* slot, const uint8_t* skip,
+                                  const orbfe_sim3_leg* legs, uint8_t* valid, float* u, float* v, int32_t* level, float* dist) {
+  if (!mp) return fail(ORBFE_ERR_INVALID, "project_sim3: NULL table");
+  if (const char* e = sim3_check_legs(orbfe_mappoints_capacity(mp), n_legs, offsets, slot, legs, 0))
+    return fail(ORBFE_ERR_INVALID, std::string("project_sim3: ") + e);
+  if (n_legs == 0 || offsets[n_legs] == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  std::vector<Sim3Span> span((size_t)n_legs);
+  for (int l = 0; l < n_legs; l++) span[(size_t)l] = Sim3Span{offsets[l], offsets[l + 1] - offsets[l], offsets[l], 0};
+  Sim3Producer P;
+  P.table = *lock.table; P.nLegs = n_legs; P.span = span.data(); P.leg = legs; P.slot = slot; P.nSlot = (size_t)offsets[n_legs];
+  P.skip = skip; P.nOut = P.nSlot;
+  return project_sim3_run(lock.device, P, valid, u, v, level, dist);
+}
+
+// SearchBySim3 for K candidates of one key frame: legs 2k (KF1 -> KF2_k) and 2k + 1 (KF2_k -> KF1) of ONE prologue launch, 2K
+// BEST window jobs of one search launch, the agreement check (:1461-1474) over the one download
+extern "C" int orbfe_search_by_sim3_mappoints_multi(orbfe_mappoints* mp, orbfe_obsgraph* g, const orbfe_frame_view* KF1,
+                                                    const int32_t* slot1, int n_candidates, const orbfe_frame_view* const* KF2,
+                                                    const int32_t* offsets2, const int32_t* slot2, const orbfe_sim3_leg* legs12,
+                                                    const orbfe_sim3_leg* legs21, const int32_t* matched12_in, const int32_t* kf2_slot,
+                                                    const uint8_t* already2, const float* scale_factors1, const float* scale_factors2,
+                                                    int n_levels, float th, int32_t* match12, int32_t* n_found) {
+  const char* who = "search_by_sim3_mappoints_multi: ";
+  if (!mp) return fail(ORBFE_ERR_INVALID, std::string(who) + "NULL table");
+  const int K = n_candidates;
+  KF1 = canon(KF1);
+  if (!frame_ok(KF1) || (KF1->n > 0 && !KF1->desc)) return fail(ORBFE_ERR_INVALID, std::string(who) + "bad key frame view");
+  const int N1 = KF1->n;
+  const bool withGraph = g != nullptr && kf2_slot != nullptr;
+  ObsGraphLock glock(withGraph ? g : nullptr);  // the graph's serialisation first, then the table's
+  if (withGraph && mappoints_device(mp) != glock.device)
+    return fail(ORBFE_ERR_INVALID, std::string(who) + "the graph and the map-point table are on different devices");
+  if (const char* e = sim3_check_search(orbfe_mappoints_capacity(mp), N1, slot1, K, offsets2, slot2, legs12, legs21, matched12_in, kf2_slot,
+                                        withGraph, glock.kfCap, n_levels))
+    return fail(ORBFE_ERR_INVALID, std::string(who) + e);
+  if (K == 0) return ORBFE_OK;
+  if (!KF2 || !scale_factors1 || !scale_factors2 || !n_found || (N1 > 0 && !match12))
+    return fail(ORBFE_ERR_INVALID, std::string(who) + "NULL argument");
+  std::vector<const orbfe_frame_view*> views((size_t)K);
+  for (int k = 0; k < K; k++) {
+    const orbfe_frame_view* f = canon(KF2[k]);
+    if (!frame_ok(f) || (f->n > 0 && !f->desc)) return fail(ORBFE_ERR_INVALID, std::string(who) + "bad key frame view");
+    if (f->n != offsets2[k + 1] - offsets2[k]) return fail(ORBFE_ERR_INVALID, std::string(who) + "slot2 does not hold KF2->n entries per candidate");
+    views[(size_t)k] = f;
+  }
+  for (size_t i = 0; i < (size_t)K * N1; i++) match12[i] = -1;
+  for (int k = 0; k < K; k++) n_found[k] = 0;
+  const size_t total2 = (size_t)offsets2[K], out2 = (size_t)K * N1;
+  if (N1 == 0 || total2 == 0) return ORBFE_OK;  // (a direction without a point finds nothing, so no pair can agree)
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  if (int rc = glock.table_ready()) return rc;
+  // what travels: KF1's list once, then the candidates'; the masks by output position (K x N1, then the candidates')
+  std::vector<int32_t> slot((size_t)N1 + total2);
+  std::memcpy(slot.data(), slot1, (size_t)N1 * 4);
+  std::memcpy(slot.data() + N1, slot2, total2 * 4);
+  std::vector<uint8_t> skip(out2 + total2, 0);
+  if (matched12_in)
+    for (size_t i = 0; i < out2; i++) skip[i] = matched12_in[i] >= 0;
+  if (already2)
+    for (size_t i = 0; i < total2; i++) skip[out2 + i] = already2[i] != 0;
+  std::vector<Sim3Span> span((size_t)2 * K);
+  std::vector<orbfe_sim3_leg> leg((size_t)2 * K);
+  for (int k = 0; k < K; k++) {
+    span[2 * (size_t)k] = Sim3Span{0, N1, (int32_t)((size_t)k * N1), (k == 0 ? 1 : 0) | 2};  // KF2_k's level table is the second
+    span[2 * (size_t)k + 1] = Sim3Span{N1 + offsets2[k], offsets2[k + 1] - offsets2[k], (int32_t)(out2 + (size_t)offsets2[k]), 1};
+    leg[2 * (size_t)k] = legs12[k];
+    leg[2 * (size_t)k + 1] = legs21[k];
+  }
+  std::vector<float> scale((size_t)2 * n_levels);
+  std::memcpy(scale.data(), scale_factors1, (size_t)n_levels * 4);
+  std::memcpy(scale.data() + n_levels, scale_factors2, (size_t)n_levels * 4);
+  Sim3Producer P;
+  P.table = *lock.table; P.nLegs = 2 * K; P.span = span.data(); P.leg = leg.data(); P.slot = slot.data(); P.nSlot = slot.size();
+  P.skip = skip.data(); P.nOut = skip.size(); P.scale = scale.data(); P.nScale = 2 * n_levels; P.nLevels = n_levels; P.th = th;
+  if (withGraph && matched12_in) {
+    P.graph = glock.graph; P.matched = matched12_in; P.kfSlot = kf2_slot; P.offsets2 = offsets2; P.K = K; P.n1 = N1; P.already2Off = out2;
+  }
+  std::vector<int32_t> m2(total2, -1);  // vnMatch2 of every candidate; match12 holds vnMatch1 until the agreement check
+  std::vector<WindowJob> wj;
+  for (int k = 0; k < K; k++) {
+    const int n2 = views[(size_t)k]->n;
+    if (n2 == 0) continue;  // nothing to search in either direction
+    WindowJob a, b;
+    a.f = views[(size_t)k]; a.nq = N1; a.bestOut = match12 + (size_t)k * N1; a.maxDist = 100 /* TH_HIGH */; a.nLevels = n_levels;
+    a.sim3 = &P; a.sim3Leg = 2 * k;
+    b.f = KF1; b.nq = n2; b.bestOut = m2.data() + offsets2[k]; b.maxDist = 100; b.nLevels = n_levels;
+    b.sim3 = &P; b.sim3Leg = 2 * k + 1;
+    wj.push_back(a);
+    wj.push_back(b);
+  }
+  if (int rc = window_search_multi(lock.device, wj.data(), (int)wj.size(), 8)) return rc;
+  for (int k = 0; k < K; k++) {
+    int32_t* m1 = match12 + (size_t)k * N1;
+    const int32_t* mk = m2.data() + offsets2[k];
+    int nFound = 0;
+    for (int i1 = 0; i1 < N1; i1++) {
+      const int idx2 = m1[i1];
+      if (idx2 >= 0 && mk[idx2] == i1) nFound++; else m1[i1] = -1;
+    }
+    n_found[k] = nFound;
+  }
+  return ORBFE_OK;
+}
+
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): k_project_fuse at K = 1 without a graph in front of the claim loop
+extern "C" int orbfe_search_by_projection_sim3_mappoints(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
+                                                         const orbfe_camera_pose* pose, const orbfe_frame_view* KF,
+                                                         const float* scale_factors, int n_levels, const uint8_t* matched, float th,
+                                                         int32_t* match, int32_t* n_matches, uint8_t* projected) {
+  const char* who = "search_by_projection_sim3_mappoints: ";
+  if (!mp) return fail(ORBFE_ERR_INVALID, std::string(who) + "NULL table");
+  KF = canon(KF);
+  if (!frame_ok(KF) || !scale_factors || n_levels <= 0 || !n_matches || (KF->n > 0 && (!match || !KF->desc)))
+    return fail(ORBFE_ERR_INVALID, std::string(who) + "bad argument");
+  if (const char* e = fuse_check_operands(orbfe_mappoints_capacity(mp), n, slot, 1, nullptr, false, 0, pose, n_levels))
+    return fail(ORBFE_ERR_INVALID, std::string(who) + e);
+  for (int i = 0; i < KF->n; i++) match[i] = -1;
+  *n_matches = 0;
+  if (n == 0) return ORBFE_OK;
+  MapPointsLock lock(mp);
+  if (lock.rc) return lock.rc;
+  if (KF->n == 0)  // nothing to search: the flags alone
+    return projected ? project_fuse_run(lock.device, *lock.table, nullptr, n, slot, 1, nullptr, pose, skip, projected, nullptr, nullptr,
+                                        nullptr, nullptr, nullptr)
+                     : ORBFE_OK;
+  FuseProducer P;
+  P.table = *lock.table; P.slot = slot; P.skip = skip; P.pose = pose; P.n = n; P.K = 1;
+  P.scale = scale_factors; P.nLevels = n_levels; P.th = th; P.projectedOut = projected;
+  ClaimSpec C;  // claim loop :418-446 on the device
+  C.mode = CLAIM_BEST; C.maxDist = 50 /* TH_LOW */;
+  C.blocked = matched;
+  C.match = match; C.nMatches = n_matches;
+  WindowJob job;
+  job.f = KF; job.nq = n;
+  job.claim = &C;
+  job.fuse = &P; job.fuseK = 0;
+  return window_search_multi(lock.device, &job, 1, 32);
 }

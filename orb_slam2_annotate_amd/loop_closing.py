@@ -20,6 +20,36 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def sim3_legs(R1w, t1w, R2w, t2w, s12, R12, t12, K4_1, bounds1, scale_factor1, n_levels1, K4_2=None, bounds2=None,
+              scale_factor2=None, n_levels2=None):
+    """The two legs of ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1260-1270) for
+    MapPoints.SearchBySim3 -> (leg12, leg21): leg12 projects KF1's points into KF2 (R1w, t1w, then sR21, t21, KF2's camera),
+    leg21 KF2's points into KF1 (R2w, t2w, then sR12, t12, KF1's camera).  The camera of KF2 defaults to KF1's.
+
+    The rounding of the 24 composed floats is fixed HERE, not in the kernel, because the reference leaves it to OpenCV's
+    matrix expressions, whose arithmetic depends on the OpenCV version and build:
+      sR12 = float32(s12) * R12 entry by entry, one binary32 product each;
+      sR21 = (1.0 / s12) * R12^T: the reciprocal in binary64, each entry the binary64 product rounded to binary32 once;
+      t21  = -(sR21 t12): per row ((a0*b0 + a1*b1) + a2*b2) in binary32, products and sums rounded one by one, then negated;
+      t12 unchanged.
+    A caller that must match one particular OpenCV build bit for bit composes the 24 floats itself and calls
+    map_points.sim3_leg."""
+    from .map_points import sim3_leg
+
+    s = np.float32(s12)
+    R = np.asarray(R12, dtype=np.float32).reshape(3, 3)
+    t = np.asarray(t12, dtype=np.float32).reshape(3)
+    sR12 = (s * R).astype(np.float32)
+    sR21 = ((1.0 / np.float64(s)) * R.T.astype(np.float64)).astype(np.float32)
+    p = (sR21 * t[None, :]).astype(np.float32)
+    t21 = -((p[:, 0] + p[:, 1]).astype(np.float32) + p[:, 2]).astype(np.float32)
+    if K4_2 is None:
+        K4_2, bounds2, scale_factor2, n_levels2 = K4_1, bounds1, scale_factor1, n_levels1
+    leg12 = sim3_leg(R1w, t1w, sR21, t21, K4_2, bounds2, scale_factor2, n_levels2)
+    leg21 = sim3_leg(R2w, t2w, sR12, t, K4_1, bounds1, scale_factor1, n_levels1)
+    return leg12, leg21
+
+
 def sim3_max_iterations(n: int, prob: float = 0.99, min_inliers: int = 6, max_its: int = 300) -> int:
     """What SetRansacParameters (:118-142) leaves in mRansacMaxIts (orbfe_sim3_max_iterations)."""
     return int(_lib.load().orbfe_sim3_max_iterations(int(n), float(prob), int(min_inliers), int(max_its)))

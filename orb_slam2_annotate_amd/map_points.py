@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CameraPoseC, PoseOptStatsC, check, ptr
+from ._lib import CameraPoseC, PoseOptStatsC, Sim3LegC, check, ptr
 
 MP_BAD, MP_OBSERVED = 1, 2  # flags: MapPoint::isBad(), MapPoint::Observations() > 0
 
@@ -32,6 +32,22 @@ def camera_pose(Rcw, tcw, K4, mbf, bounds, scale_factor: float, n_levels: int, O
     p.log_scale_factor = float(np.float32(np.log(np.float32(scale_factor))))
     p.n_levels = int(n_levels)
     return p
+
+
+def sim3_leg(Rw, tw, sR, t, K4, bounds, scale_factor: float, n_levels: int) -> Sim3LegC:
+    """orbfe_sim3_leg: the SOURCE key frame's GetRotation (3 x 3) / GetTranslation, the 12 floats sR / t that take its camera
+    frame to the target's (sR21, t21 or sR12, t12 -- composed by the caller, see loop_closing.sim3_legs), and the TARGET's
+    (fx, fy, cx, cy), (mnMinX, mnMaxX, mnMinY, mnMaxY) and pyramid.  Every value is rounded to float32 once, here."""
+    leg = Sim3LegC()
+    leg.Rw[:] = [float(v) for v in np.asarray(Rw, dtype=np.float32).reshape(9)]
+    leg.tw[:] = [float(v) for v in np.asarray(tw, dtype=np.float32).reshape(3)]
+    leg.sR[:] = [float(v) for v in np.asarray(sR, dtype=np.float32).reshape(9)]
+    leg.t[:] = [float(v) for v in np.asarray(t, dtype=np.float32).reshape(3)]
+    leg.fx, leg.fy, leg.cx, leg.cy = [float(np.float32(v)) for v in K4]
+    leg.min_x, leg.max_x, leg.min_y, leg.max_y = [float(np.float32(v)) for v in bounds]
+    leg.log_scale_factor = float(np.float32(np.log(np.float32(scale_factor))))
+    leg.n_levels = int(n_levels)
+    return leg
 
 
 class MapPoints:
@@ -301,6 +317,108 @@ class MapPoints:
         check(self._L.orbfe_search_keyframe_mappoints_multi(h, C.byref(Cur.c), ptr(sf), len(sf), K, ptr(off), ptr(s), ptr(k), ptr(ka), pa,
                                                             bp, ptr(tha), ptr(od), int(bool(check_orientation)), ptr(match), ptr(cnt)))
         return cnt[:K], match[:K, :Cur.N]
+
+    def project_sim3(self, legs, slots, skips=None):
+        """The prologue of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1298-1340, :1379-1420) for many legs in one launch
+        (orbfe_project_sim3): slots[l] = the source key frame's GetMapPointMatches() in slot space (-1 = none), skips[l] =
+        vbAlreadyMatched -> list of dicts of valid (uint8), u, v, dist (float32), level (int32), one per leg."""
+        h = self._h
+        legs = list(legs)
+        lists = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in slots]
+        n = len(legs)
+        if len(lists) != n:
+            raise ValueError("one slot list per leg")
+        off = np.zeros(n + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in lists])
+        s = np.concatenate(lists + [np.zeros(0, np.int32)]).astype(np.int32)
+        k = None
+        if skips is not None:
+            masks = [np.zeros(len(x), np.uint8) if m is None else np.ascontiguousarray(m, dtype=np.uint8).reshape(-1)
+                     for m, x in zip(skips, lists)]
+            if [len(m) for m in masks] != [len(x) for x in lists]:
+                raise ValueError("one skip entry per slot")
+            k = np.concatenate(masks + [np.zeros(0, np.uint8)]).astype(np.uint8)
+        la = (Sim3LegC * max(n, 1))(*legs)
+        q = max(len(s), 1)
+        flat = {"valid": np.zeros(q, np.uint8), "level": np.zeros(q, np.int32)}
+        for name in ("u", "v", "dist"):
+            flat[name] = np.zeros(q, np.float32)
+        check(self._L.orbfe_project_sim3(h, n, ptr(off), ptr(s), ptr(k), la,
+                                         *[ptr(flat[f]) for f in ("valid", "u", "v", "level", "dist")]))
+        return [{name: a[off[j]:off[j + 1]] for name, a in flat.items()} for j in range(n)]
+
+    def SearchBySim3(self, KF1, slot1, KF2s, slot2s, legs12, legs21, scale_factors1, scale_factors2, th: float,
+                     matched12=None, graph=None, kf2_slot=None, already2=None):
+        """ORBmatcher::SearchBySim3 for K candidates of KF1 in one call (orbfe_search_by_sim3_mappoints_multi).  slot1 /
+        slot2s[k] = GetMapPointMatches() of KF1 / KF2_k in slot space (-1 = none); legs12[k] / legs21[k] from
+        loop_closing.sim3_legs; matched12 [K, N1] = the slots of vpMatches12_k at entry (-1 = NULL).  vbAlreadyMatched2 comes
+        from already2[k] (masks over KF2_k's keypoints) and / or, with graph and kf2_slot, from the observation rows on the
+        device -> (n_found[K], match12[K, N1]) with match12[k, i1] = i2 or -1."""
+        h = self._h
+        KF2s, legs12, legs21 = list(KF2s), list(legs12), list(legs21)
+        K = len(KF2s)
+        s1 = np.ascontiguousarray(slot1, dtype=np.int32).reshape(-1)
+        lists = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in slot2s]
+        if not (len(lists) == len(legs12) == len(legs21) == K):
+            raise ValueError("MapPoints.SearchBySim3: one slot list and two legs per candidate")
+        if len(s1) != KF1.N:
+            raise ValueError("MapPoints.SearchBySim3: slot1 must hold one entry per keypoint of KF1")
+        N1 = len(s1)
+        off = np.zeros(K + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in lists])
+        s2 = np.concatenate(lists + [np.zeros(0, np.int32)]).astype(np.int32)
+        m_in = None
+        if matched12 is not None:
+            m_in = np.ascontiguousarray(matched12, dtype=np.int32).reshape(-1)
+            if len(m_in) != K * N1:
+                raise ValueError("MapPoints.SearchBySim3: matched12 must be [K, N1]")
+        a2 = None
+        if already2 is not None:
+            masks = [np.zeros(len(x), np.uint8) if m is None else np.ascontiguousarray(m, dtype=np.uint8).reshape(-1)
+                     for m, x in zip(already2, lists)]
+            if [len(m) for m in masks] != [len(x) for x in lists]:
+                raise ValueError("MapPoints.SearchBySim3: already2[k] must hold one entry per keypoint of KF2_k")
+            a2 = np.concatenate(masks + [np.zeros(0, np.uint8)]).astype(np.uint8)
+        kf = None
+        if graph is not None:
+            if kf2_slot is None:
+                raise ValueError("a graph needs the kf slots of the candidates")
+            kf = np.ascontiguousarray(kf2_slot, dtype=np.int32).reshape(-1)
+            if len(kf) != K:
+                raise ValueError("kf2_slot must hold one entry per candidate")
+        sf1 = np.ascontiguousarray(scale_factors1, dtype=np.float32).reshape(-1)
+        sf2 = np.ascontiguousarray(scale_factors2, dtype=np.float32).reshape(-1)
+        if len(sf1) != len(sf2):
+            raise ValueError("MapPoints.SearchBySim3: the two level tables must hold the same number of levels")
+        views = (C.POINTER(_lib.FrameViewC) * max(K, 1))(*[C.pointer(f.c) for f in KF2s])
+        l12 = (Sim3LegC * max(K, 1))(*legs12)
+        l21 = (Sim3LegC * max(K, 1))(*legs21)
+        match = np.full(max(K * N1, 1), -1, dtype=np.int32)
+        cnt = np.zeros(max(K, 1), dtype=np.int32)
+        check(self._L.orbfe_search_by_sim3_mappoints_multi(h, graph._h if graph is not None else None, C.byref(KF1.c), ptr(s1), K,
+                                                           views, ptr(off), ptr(s2), l12, l21, ptr(m_in), ptr(kf), ptr(a2),
+                                                           ptr(sf1), ptr(sf2), len(sf1), float(th), ptr(match), ptr(cnt)))
+        return cnt[:K], match[:K * N1].reshape(K, N1)
+
+    def SearchByProjectionSim3(self, KF, slot, pose: CameraPoseC, scale_factors, th: float, matched=None, skip=None,
+                               return_projected: bool = False):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:335-451) in one call
+        (orbfe_search_by_projection_sim3_mappoints): slot[] = vpPoints in slot space, pose = the decomposition of Scw (as for
+        fuse), matched[idx] = vpMatched[idx] != NULL, skip[i] = the point is in spAlreadyFound -> (nmatches, match[KF.N]) with
+        match[idx] = position in slot[] or -1, and with return_projected the points that passed the prologue."""
+        h = self._h
+        s, k = self._slots(slot, skip)
+        n = len(s)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        blk = None if matched is None else np.ascontiguousarray(matched, dtype=np.uint8).reshape(-1)
+        if blk is not None and len(blk) != KF.N:
+            raise ValueError("matched must hold one entry per keypoint of the key frame")
+        match = np.full(max(KF.N, 1), -1, dtype=np.int32)
+        proj = np.zeros(max(n, 1), np.uint8) if return_projected else None
+        nm = C.c_int32(0)
+        check(self._L.orbfe_search_by_projection_sim3_mappoints(h, n, ptr(s), ptr(k), C.byref(pose), C.byref(KF.c), ptr(sf), len(sf),
+                                                                ptr(blk), float(th), ptr(match), C.byref(nm), ptr(proj)))
+        return (nm.value, match[:KF.N], proj[:n]) if return_projected else (nm.value, match[:KF.N])
 
     def pose_optimization(self, frame, slot, match, pose, K5, inv_level_sigma2, outlier=None):
         """Optimizer::PoseOptimization on the table (orbfe_pose_optimization_mappoints): `match` is what SearchLocalPoints
