@@ -17,7 +17,58 @@ namespace {
 constexpr int kProjectThreads = 256;
 
 // Every operation is written with the round-to-nearest intrinsics, in the order include/orbfe.h states: no contraction, no
-// reassociation, whatever flags the file is built with.
+// reassociation, whatever flags the file is built with.  The steps the prologues share stand here once; they inline.
+
+struct Vec3 { float x, y, z; };
+// R (3 x 3, row-major) * (X, Y, Z) + t: a point into a camera's coordinates
+__device__ __forceinline__ Vec3 transform(const float* R, const float* t, float X, float Y, float Z) {
+  Vec3 p;
+  p.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[0], X), __fmul_rn(R[1], Y)), __fmul_rn(R[2], Z)), t[0]);
+  p.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[3], X), __fmul_rn(R[4], Y)), __fmul_rn(R[5], Z)), t[1]);
+  p.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[6], X), __fmul_rn(R[7], Y)), __fmul_rn(R[8], Z)), t[2]);
+  return p;
+}
+// cv::norm and Mat::dot of three floats accumulate in double
+__device__ __forceinline__ double dot3(Vec3 a, float bx, float by, float bz) {
+  return __dadd_rn(__dadd_rn(__dmul_rn((double)a.x, (double)bx), __dmul_rn((double)a.y, (double)by)), __dmul_rn((double)a.z, (double)bz));
+}
+__device__ __forceinline__ float norm3(Vec3 a) { return (float)__dsqrt_rn(dot3(a, a.x, a.y, a.z)); }
+// MapPoint::PredictScale: ceil(log(maxD / dist) / log_scale_factor), clamped to the pyramid; a NaN quotient -> 0
+__device__ __forceinline__ int predict_scale(float maxD, float dist, float logScaleFactor, int nLevels) {
+  const float ratio = __fdiv_rn(maxD, dist);
+  const double cl = ceil(__ddiv_rn(log((double)ratio), (double)logScaleFactor));
+  const int top = nLevels - 1;
+  return cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;
+}
+// the window of point o as the host-array searches build it: centre (u, v) or 0 when rejected, radius r, octaves [lo, hi],
+// and the optional arrays (match_kernels.h: QueryOut) the call asked for
+__device__ __forceinline__ void store_window(const QueryOut& q, size_t o, bool ok, float u, float v, float r, int lo, int hi, float ur,
+                                             uint8_t fl) {
+  q.x[o] = ok ? u : 0.0f;
+  q.y[o] = ok ? v : 0.0f;
+  q.r[o] = r;
+  q.minLevel[o] = lo;
+  q.maxLevel[o] = hi;
+  q.active[o] = ok;
+  if (q.obs) q.obs[o] = (fl & ORBFE_MP_OBSERVED) ? 1 : 0;
+  if (q.ur) q.ur[o] = ok ? ur : 0.0f;
+  if (q.validCopy) q.validCopy[o] = ok;
+}
+// (workgroup-uniform) the descriptors of the workgroup's points -- positions off + base .. of slot[], n points in the list --
+// gathered from the table into out[] at the same positions: piece p = half (p & 1) of point off + base + p / 2.  sparse
+// (k_project_sim3): slot -1 is "no map point" and gets zeros, nothing reads them
+__device__ __forceinline__ void gather_desc(const MapPointsDevice& t, const int32_t* slot, uint8_t* out, size_t off, int n, int base,
+                                            bool sparse) {
+  const int cnt = n - base < kProjectThreads ? n - base : kProjectThreads;
+  const uint4* src = reinterpret_cast<const uint4*>(t.desc);
+  uint4* dst = reinterpret_cast<uint4*>(out);
+  for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
+    const size_t q = off + base + (p >> 1);
+    const int s = slot[q];
+    dst[2 * q + (p & 1)] = sparse && s < 0 ? make_uint4(0u, 0u, 0u, 0u) : src[2 * (size_t)s + (p & 1)];
+  }
+}
+
 __global__ __launch_bounds__(kProjectThreads) void k_project_frustum(const ProjectArgs a) {
   const int base = blockIdx.x * kProjectThreads;
   const int i = base + (int)threadIdx.x;
@@ -29,34 +80,23 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_frustum(const Proje
     const float X = r0.x, Y = r0.y, Z = r0.z, minD = r0.w, maxD = r1.w;
     bool ok = !(fl & ORBFE_MP_BAD) && !(a.skip && a.skip[i]);
     // 3D in camera coordinates (:305-309); the depth must be positive (:311-313)
-    const float xc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[0], X), __fmul_rn(c.Rcw[1], Y)), __fmul_rn(c.Rcw[2], Z)), c.tcw[0]);
-    const float yc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[3], X), __fmul_rn(c.Rcw[4], Y)), __fmul_rn(c.Rcw[5], Z)), c.tcw[1]);
-    const float zc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[6], X), __fmul_rn(c.Rcw[7], Y)), __fmul_rn(c.Rcw[8], Z)), c.tcw[2]);
-    if (zc < 0.0f) ok = false;
+    const Vec3 pc = transform(c.Rcw, c.tcw, X, Y, Z);
+    if (pc.z < 0.0f) ok = false;
     // projection inside the image (:315-323)
-    const float invz = __fdiv_rn(1.0f, zc);
-    const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, xc), invz), c.cx);
-    const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, yc), invz), c.cy);
+    const float invz = __fdiv_rn(1.0f, pc.z);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, pc.x), invz), c.cx);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, pc.y), invz), c.cy);
     if (u < c.min_x || u > c.max_x) ok = false;
     if (v < c.min_y || v > c.max_y) ok = false;
-    // distance inside the scale invariance region of the point (:325-332): cv::norm accumulates in double
-    const float px = __fsub_rn(X, c.Ow[0]), py = __fsub_rn(Y, c.Ow[1]), pz = __fsub_rn(Z, c.Ow[2]);
-    const double dpx = (double)px, dpy = (double)py, dpz = (double)pz;
-    const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dpx, dpx), __dmul_rn(dpy, dpy)), __dmul_rn(dpz, dpz));
-    const float dist = (float)__dsqrt_rn(d2);
+    // distance inside the scale invariance region of the point (:325-332)
+    const Vec3 po = {__fsub_rn(X, c.Ow[0]), __fsub_rn(Y, c.Ow[1]), __fsub_rn(Z, c.Ow[2])};
+    const float dist = norm3(po);
     if (dist < __fmul_rn(0.8f, minD) || dist > __fmul_rn(1.2f, maxD)) ok = false;
-    // viewing angle (:334-340): Mat::dot accumulates in double
-    const double dot = __dadd_rn(__dadd_rn(__dmul_rn(dpx, (double)r1.x), __dmul_rn(dpy, (double)r1.y)), __dmul_rn(dpz, (double)r1.z));
-    const float viewCos = (float)__ddiv_rn(dot, (double)dist);
+    // viewing angle (:334-340)
+    const float viewCos = (float)__ddiv_rn(dot3(po, r1.x, r1.y, r1.z), (double)dist);
     if (viewCos < a.limit) ok = false;
-    // MapPoint::PredictScale (:342-343)
     int lv = 0;
-    if (ok) {
-      const float ratio = __fdiv_rn(maxD, dist);
-      const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
-      const int top = c.n_levels - 1;
-      lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
-    }
+    if (ok) lv = predict_scale(maxD, dist, c.log_scale_factor, c.n_levels);  // (:342-343)
     const float xr = __fsub_rn(u, __fmul_rn(c.mbf, invz));
     if (a.inView) a.inView[i] = ok;
     if (a.level) a.level[i] = lv;
@@ -66,31 +106,15 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_frustum(const Proje
     if (a.projXr) a.projXr[i] = ok ? xr : 0.0f;
     if (a.invZ) a.invZ[i] = ok ? invz : 0.0f;
     if (a.dist) a.dist[i] = ok ? dist : 0.0f;
-    if (a.qx) {
+    if (a.q.x) {
       // the windows of SearchByProjection(Frame&, vector<MapPoint*>&, th): RadiusByViewingCos (src/ORBmatcher.cc:140-146,
       // the compare in double), r *= th when th != 1.0 (:68-69), r * mvScaleFactors[level], levels [level - 1, level] (:71-73)
       float r = (double)(ok ? viewCos : 0.0f) > 0.998 ? 2.5f : 4.0f;
       if ((double)a.th != 1.0) r = __fmul_rn(r, a.th);
-      a.qx[i] = ok ? u : 0.0f;
-      a.qy[i] = ok ? v : 0.0f;
-      a.qr[i] = __fmul_rn(r, a.scale[lv]);
-      a.qmin[i] = lv - 1;
-      a.qmax[i] = lv;
-      a.qactive[i] = ok;
-      a.qobs[i] = (fl & ORBFE_MP_OBSERVED) ? 1 : 0;
-      if (a.qur) a.qur[i] = ok ? xr : 0.0f;
-      if (a.inViewCopy) a.inViewCopy[i] = ok;
+      store_window(a.q, (size_t)i, ok, u, v, __fmul_rn(r, a.scale[lv]), lv - 1, lv, xr, fl);
     }
   }
-  if (a.qdesc) {  // (workgroup-uniform) the points' descriptors, gathered from the table: piece p = half (p & 1) of point base + p / 2
-    const int cnt = a.n - base < kProjectThreads ? a.n - base : kProjectThreads;
-    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
-    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
-    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
-      const int q = base + (p >> 1);
-      dst[2 * (size_t)q + (p & 1)] = src[2 * (size_t)a.slot[q] + (p & 1)];
-    }
-  }
+  if (a.q.desc) gather_desc(a.table, a.slot, a.q.desc, 0, a.n, base, false);
 }
 
 // The prologue of ORBmatcher::Fuse (src/ORBmatcher.cc:960-1006) for 256 consecutive points x K key-frame poses: the two table
@@ -129,68 +153,40 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_fuse(const FuseArgs
       }
     }
     const float lo = __fmul_rn(0.8f, minD), hi = __fmul_rn(1.2f, maxD);
-    const double nx = (double)r1.x, ny = (double)r1.y, nz = (double)r1.z;
     for (int k = 0; k < a.K; k++) {
       const orbfe_camera_pose& c = sPose[k];
       const size_t o = (size_t)k * a.n + i;
       bool ok = !(fl & ORBFE_MP_BAD) && !(a.skip && a.skip[o]) && !((inKf >> k) & 1);
       // 3D in camera coordinates (:969); the depth must be positive (:972)
-      const float xc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[0], X), __fmul_rn(c.Rcw[1], Y)), __fmul_rn(c.Rcw[2], Z)), c.tcw[0]);
-      const float yc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[3], X), __fmul_rn(c.Rcw[4], Y)), __fmul_rn(c.Rcw[5], Z)), c.tcw[1]);
-      const float zc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[6], X), __fmul_rn(c.Rcw[7], Y)), __fmul_rn(c.Rcw[8], Z)), c.tcw[2]);
-      if (zc < 0.0f) ok = false;
+      const Vec3 pc = transform(c.Rcw, c.tcw, X, Y, Z);
+      if (pc.z < 0.0f) ok = false;
       // normalised coordinates first (:975-980) -- not isInFrustum's (fx * xc) * invz
-      const float invz = __fdiv_rn(1.0f, zc);
-      const float x = __fmul_rn(xc, invz), y = __fmul_rn(yc, invz);
+      const float invz = __fdiv_rn(1.0f, pc.z);
+      const float x = __fmul_rn(pc.x, invz), y = __fmul_rn(pc.y, invz);
       const float u = __fadd_rn(__fmul_rn(c.fx, x), c.cx);
       const float v = __fadd_rn(__fmul_rn(c.fy, y), c.cy);
       // KeyFrame::IsInImage (src/KeyFrame.cc:653-656): the upper bounds are strict
       if (!(u >= c.min_x && u < c.max_x && v >= c.min_y && v < c.max_y)) ok = false;
       const float ur = __fsub_rn(u, __fmul_rn(c.mbf, invz));
-      // distance inside the scale invariance region (:990-995): cv::norm accumulates in double
-      const float px = __fsub_rn(X, c.Ow[0]), py = __fsub_rn(Y, c.Ow[1]), pz = __fsub_rn(Z, c.Ow[2]);
-      const double dpx = (double)px, dpy = (double)py, dpz = (double)pz;
-      const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dpx, dpx), __dmul_rn(dpy, dpy)), __dmul_rn(dpz, dpz));
-      const float dist = (float)__dsqrt_rn(d2);
+      // distance inside the scale invariance region (:990-995)
+      const Vec3 po = {__fsub_rn(X, c.Ow[0]), __fsub_rn(Y, c.Ow[1]), __fsub_rn(Z, c.Ow[2])};
+      const float dist = norm3(po);
       if (dist < lo || dist > hi) ok = false;
-      // viewing angle below 60 degrees (:1000): Mat::dot accumulates in double, the compare is in double, nothing is divided
-      const double dot = __dadd_rn(__dadd_rn(__dmul_rn(dpx, nx), __dmul_rn(dpy, ny)), __dmul_rn(dpz, nz));
-      if (dot < __dmul_rn(0.5, (double)dist)) ok = false;
-      // MapPoint::PredictScale (:1003)
+      // viewing angle below 60 degrees (:1000): the compare is in double, nothing is divided
+      if (dot3(po, r1.x, r1.y, r1.z) < __dmul_rn(0.5, (double)dist)) ok = false;
       int lv = 0;
-      if (ok) {
-        const float ratio = __fdiv_rn(maxD, dist);
-        const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
-        const int top = c.n_levels - 1;
-        lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
-      }
+      if (ok) lv = predict_scale(maxD, dist, c.log_scale_factor, c.n_levels);  // (:1003)
       if (a.valid) a.valid[o] = ok;
       if (a.u) a.u[o] = ok ? u : 0.0f;
       if (a.v) a.v[o] = ok ? v : 0.0f;
       if (a.ur) a.ur[o] = ok ? ur : 0.0f;
       if (a.level) a.level[o] = lv;
       if (a.dist) a.dist[o] = ok ? dist : 0.0f;
-      if (a.qx) {  // the windows of :1006-1028 as orbfe_fuse_search_multi builds them from the arrays above
-        a.qx[o] = ok ? u : 0.0f;
-        a.qy[o] = ok ? v : 0.0f;
-        a.qr[o] = __fmul_rn(a.th, a.scale[lv]);
-        a.qmin[o] = lv - 1;
-        a.qmax[o] = lv;
-        a.qactive[o] = ok;
-        if (a.qur) a.qur[o] = ok ? ur : 0.0f;
-        if (a.validCopy) a.validCopy[o] = ok;
-      }
+      // the windows of :1006-1028 as orbfe_fuse_search_multi builds them from the arrays above
+      if (a.q.x) store_window(a.q, o, ok, u, v, __fmul_rn(a.th, a.scale[lv]), lv - 1, lv, ur, fl);
     }
   }
-  if (a.qdesc) {  // (workgroup-uniform) the descriptors, gathered once for all K jobs: piece p = half (p & 1) of point base + p / 2
-    const int cnt = a.n - base < kProjectThreads ? a.n - base : kProjectThreads;
-    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
-    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
-    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
-      const int q = base + (p >> 1);
-      dst[2 * (size_t)q + (p & 1)] = src[2 * (size_t)a.slot[q] + (p & 1)];
-    }
-  }
+  if (a.q.desc) gather_desc(a.table, a.slot, a.q.desc, 0, a.n, base, false);  // once for all K jobs
 }
 
 // The prologues of SearchByProjection(CurrentFrame, LastFrame, th, bMono) (kForm 0, src/ORBmatcher.cc:1516-1550) and of
@@ -217,13 +213,11 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_track(const TrackAr
     // pMP && !mvbOutlier[i] is the caller's list (:1510-1514: isBad is NOT asked); !isBad() && !sAlreadyFound.count(pMP) (:1663)
     bool ok = !(a.skip && a.skip[o]);
     if (kForm == 1 && (fl & ORBFE_MP_BAD)) ok = false;
-    const float xc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[0], X), __fmul_rn(c.Rcw[1], Y)), __fmul_rn(c.Rcw[2], Z)), c.tcw[0]);
-    const float yc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[3], X), __fmul_rn(c.Rcw[4], Y)), __fmul_rn(c.Rcw[5], Z)), c.tcw[1]);
-    const float zc = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rcw[6], X), __fmul_rn(c.Rcw[7], Y)), __fmul_rn(c.Rcw[8], Z)), c.tcw[2]);
-    const float invz = __fdiv_rn(1.0f, zc);
+    const Vec3 pc = transform(c.Rcw, c.tcw, X, Y, Z);
+    const float invz = __fdiv_rn(1.0f, pc.z);
     if (kForm == 0 && invz < 0.0f) ok = false;  // (:1524; the key-frame form has no depth test)
-    const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, xc), invz), c.cx);
-    const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, yc), invz), c.cy);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(c.fx, pc.x), invz), c.cx);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(c.fy, pc.y), invz), c.cy);
     // inside the image, bounds included (:1533-1536, :1676-1679); a NaN coordinate is rejected here
     if (!(u >= c.min_x && u <= c.max_x && v >= c.min_y && v <= c.max_y)) ok = false;
     int lv = 0, lo = 0, hi = 0;
@@ -235,18 +229,11 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_track(const TrackAr
       else if (a.mode == 2) { lo = 0; hi = lv; }   // bBackward: (u, v, radius, 0, nLastOctave)
       else { lo = lv - 1; hi = lv + 1; }
     } else {
-      // distance inside the scale invariance region of the point (:1682-1691): cv::norm accumulates in double
-      const float px = __fsub_rn(X, c.Ow[0]), py = __fsub_rn(Y, c.Ow[1]), pz = __fsub_rn(Z, c.Ow[2]);
-      const double dpx = (double)px, dpy = (double)py, dpz = (double)pz;
-      const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dpx, dpx), __dmul_rn(dpy, dpy)), __dmul_rn(dpz, dpz));
-      dist = (float)__dsqrt_rn(d2);
+      // distance inside the scale invariance region of the point (:1682-1691)
+      const Vec3 po = {__fsub_rn(X, c.Ow[0]), __fsub_rn(Y, c.Ow[1]), __fsub_rn(Z, c.Ow[2])};
+      dist = norm3(po);
       if (dist < __fmul_rn(0.8f, minD) || dist > __fmul_rn(1.2f, maxD)) ok = false;
-      if (ok) {  // MapPoint::PredictScale (:1694)
-        const float ratio = __fdiv_rn(maxD, dist);
-        const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
-        const int top = c.n_levels - 1;
-        lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
-      }
+      if (ok) lv = predict_scale(maxD, dist, c.log_scale_factor, c.n_levels);  // (:1694)
       lo = lv - 1; hi = lv + 1;
     }
     const float r = a.scale ? __fmul_rn(th, a.scale[lv]) : 0.0f;  // (:1541, :1697)
@@ -261,29 +248,10 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_track(const TrackAr
       if (a.level) a.level[o] = lv;
       if (a.dist) a.dist[o] = ok ? dist : 0.0f;
     }
-    if (a.qx) {  // the windows as the host-array calls build them from the arrays above
-      a.qx[o] = ok ? u : 0.0f;
-      a.qy[o] = ok ? v : 0.0f;
-      a.qr[o] = r;
-      a.qmin[o] = lo;
-      a.qmax[o] = hi;
-      a.qactive[o] = ok;
-      if (kForm == 0) {
-        a.qobs[o] = (fl & ORBFE_MP_OBSERVED) ? 1 : 0;
-        if (a.qur) a.qur[o] = ok ? ur : 0.0f;
-      }
-      if (a.validCopy) a.validCopy[o] = ok;
-    }
+    // the windows as the host-array calls build them from the arrays above (q.obs and q.ur: the last-frame form alone)
+    if (a.q.x) store_window(a.q, o, ok, u, v, r, lo, hi, ur, fl);
   }
-  if (a.qdesc) {  // (workgroup-uniform) the points' descriptors: piece p = half (p & 1) of point off + base + p / 2
-    const int cnt = nk - base < kProjectThreads ? nk - base : kProjectThreads;
-    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
-    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
-    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
-      const size_t q = (size_t)off + base + (p >> 1);
-      dst[2 * q + (p & 1)] = src[2 * (size_t)a.slot[q] + (p & 1)];
-    }
-  }
+  if (a.q.desc) gather_desc(a.table, a.slot, a.q.desc, (size_t)off, nk, base, false);
 }
 
 // The prologue of ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1298-1340, :1379-1420) for many legs: blockIdx.y is the leg (one
@@ -305,58 +273,33 @@ __global__ __launch_bounds__(kProjectThreads) void k_project_sim3(const Sim3Args
     uint8_t fl = ORBFE_MP_BAD;
     if (s >= 0) { r0 = a.table.rec[2 * (size_t)s]; r1 = a.table.rec[2 * (size_t)s + 1]; fl = a.table.flags[s]; }
     bool ok = s >= 0 && !(a.skip && a.skip[o]) && !(fl & ORBFE_MP_BAD);
-    const float X = r0.x, Y = r0.y, Z = r0.z, minD = r0.w, maxD = r1.w;
+    const float minD = r0.w, maxD = r1.w;
     // source camera (:1309), then target camera (:1310)
-    const float x1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rw[0], X), __fmul_rn(c.Rw[1], Y)), __fmul_rn(c.Rw[2], Z)), c.tw[0]);
-    const float y1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rw[3], X), __fmul_rn(c.Rw[4], Y)), __fmul_rn(c.Rw[5], Z)), c.tw[1]);
-    const float z1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.Rw[6], X), __fmul_rn(c.Rw[7], Y)), __fmul_rn(c.Rw[8], Z)), c.tw[2]);
-    const float x2 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.sR[0], x1), __fmul_rn(c.sR[1], y1)), __fmul_rn(c.sR[2], z1)), c.t[0]);
-    const float y2 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.sR[3], x1), __fmul_rn(c.sR[4], y1)), __fmul_rn(c.sR[5], z1)), c.t[1]);
-    const float z2 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c.sR[6], x1), __fmul_rn(c.sR[7], y1)), __fmul_rn(c.sR[8], z1)), c.t[2]);
-    if (z2 < 0.0f) ok = false;  // (:1313)
-    const float invz = __fdiv_rn(1.0f, z2);
-    const float x = __fmul_rn(x2, invz), y = __fmul_rn(y2, invz);
+    const Vec3 p1 = transform(c.Rw, c.tw, r0.x, r0.y, r0.z);
+    const Vec3 p2 = transform(c.sR, c.t, p1.x, p1.y, p1.z);
+    if (p2.z < 0.0f) ok = false;  // (:1313)
+    const float invz = __fdiv_rn(1.0f, p2.z);
+    const float x = __fmul_rn(p2.x, invz), y = __fmul_rn(p2.y, invz);
     const float u = __fadd_rn(__fmul_rn(c.fx, x), c.cx);
     const float v = __fadd_rn(__fmul_rn(c.fy, y), c.cy);
     // KeyFrame::IsInImage (src/KeyFrame.cc:653-656): the upper bounds are strict; a NaN coordinate is rejected here
     if (!(u >= c.min_x && u < c.max_x && v >= c.min_y && v < c.max_y)) ok = false;
-    // cv::norm(p3Dc2) (:1330) accumulates in double: the camera-frame vector, not P - Ow
-    const double dx = (double)x2, dy = (double)y2, dz = (double)z2;
-    const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-    const float dist = (float)__dsqrt_rn(d2);
+    const float dist = norm3(p2);  // cv::norm(p3Dc2) (:1330): the camera-frame vector, not P - Ow
     if (dist < __fmul_rn(0.8f, minD) || dist > __fmul_rn(1.2f, maxD)) ok = false;
     int lv = 0;
-    if (ok) {  // MapPoint::PredictScale (:1337)
-      const float ratio = __fdiv_rn(maxD, dist);
-      const double cl = ceil(__ddiv_rn(log((double)ratio), (double)c.log_scale_factor));
-      const int top = c.n_levels - 1;
-      lv = cl > 0.0 ? (cl > (double)top ? top : (int)cl) : 0;  // (a NaN quotient -> 0)
-    }
+    if (ok) lv = predict_scale(maxD, dist, c.log_scale_factor, c.n_levels);  // (:1337)
     if (a.valid) a.valid[o] = ok;
     if (a.u) a.u[o] = ok ? u : 0.0f;
     if (a.v) a.v[o] = ok ? v : 0.0f;
     if (a.level) a.level[o] = lv;
     if (a.dist) a.dist[o] = ok ? dist : 0.0f;
-    if (a.qx) {  // the windows of :1340-1359 as orbfe_search_by_sim3 builds them from the arrays above
+    if (a.q.x) {  // the windows of :1340-1359 as orbfe_search_by_sim3 builds them from the arrays above
       const float* scale = a.scale + ((sp.flags & 2) ? a.nLevels : 0);
-      a.qx[o] = ok ? u : 0.0f;
-      a.qy[o] = ok ? v : 0.0f;
-      a.qr[o] = __fmul_rn(a.th, scale[lv]);
-      a.qmin[o] = lv - 1;
-      a.qmax[o] = lv;
-      a.qactive[o] = ok;
+      store_window(a.q, o, ok, u, v, __fmul_rn(a.th, scale[lv]), lv - 1, lv, 0.0f, fl);
     }
   }
-  if (a.qdesc && (sp.flags & 1)) {  // (workgroup-uniform) the leg's descriptors; a point without a slot gets zeros, nothing reads them
-    const int cnt = sp.n - base < kProjectThreads ? sp.n - base : kProjectThreads;
-    const uint4* src = reinterpret_cast<const uint4*>(a.table.desc);
-    uint4* dst = reinterpret_cast<uint4*>(a.qdesc);
-    for (int p = (int)threadIdx.x; p < 2 * cnt; p += kProjectThreads) {
-      const size_t q = (size_t)sp.slotOff + base + (p >> 1);
-      const int s = a.slot[q];
-      dst[2 * q + (p & 1)] = s >= 0 ? src[2 * (size_t)s + (p & 1)] : make_uint4(0u, 0u, 0u, 0u);
-    }
-  }
+  // the leg's descriptors lie where its slots do, so the K legs that read one list share one gather (flags & 1)
+  if (a.q.desc && (sp.flags & 1)) gather_desc(a.table, a.slot, a.q.desc, (size_t)sp.slotOff, sp.n, base, true);
 }
 
 // vbAlreadyMatched2 (:1282-1292) from the observation rows: one lane per (candidate, keypoint of KF1)

@@ -1,5 +1,6 @@
-// mappoints.hip -- C-ABI entry points of the device map-point table (include/orbfe.h: orbfe_mappoints_*,
-// orbfe_project_in_frustum) and MapPointsLock (host_internal.h), the one way another host file reaches the table.
+// mappoints.hip -- C-ABI entry points of the device map-point table (include/orbfe.h: orbfe_mappoints_*) and MapPointsLock
+// (host_internal.h), the one way another host file reaches the table.  What projects or searches the points is
+// mappoints_search.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -42,43 +43,6 @@ hipError_t mappoints_ready(orbfe_mappoints* mp, Arena* ar) {
   if (e == hipSuccess) e = hipStreamSynchronize(ar->stream);
   if (e != hipSuccess) { slab_put(&mp->slab); mp->d = MapPointsDevice{}; }
   return e;
-}
-
-// k_project_frustum with the isInFrustum outputs (n > 0, arguments checked, the handle locked): slot list and mask up, one
-// launch, the eight arrays back in one copy
-int project_run(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip, const orbfe_camera_pose* pose, float limit,
-                uint8_t* in_view, int32_t* level, float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z,
-                float* dist) {
-  const size_t q = (size_t)n;
-  Arena* ar;
-  ProjectArgs pa{};
-  int32_t* dslot;
-  uint8_t* dskip = nullptr;
-  auto stage = [&](Arena* a) -> hipError_t {
-    TRY(up(a, &dslot, slot, q));
-    if (skip) TRY(up(a, &dskip, skip, q));
-    // the outputs adjacent: one copy back
-    pa.level = carve<int32_t>(a, q); pa.viewCos = carve<float>(a, q); pa.projX = carve<float>(a, q); pa.projY = carve<float>(a, q);
-    pa.projXr = carve<float>(a, q); pa.invZ = carve<float>(a, q); pa.dist = carve<float>(a, q); pa.inView = carve<uint8_t>(a, q);
-    return hipSuccess;
-  };
-  HIPCHK(arena_stage(mp->device, &ar, stage));
-  HIPCHK(mappoints_ready(mp, ar));
-  pa.table = mp->d; pa.slot = dslot; pa.skip = dskip; pa.n = n; pa.cam = *pose; pa.limit = limit;
-  HIPCHK(flush(ar));
-  launch_project_frustum(ar->stream, pa);
-  HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, pa.level, pa.inView + q));
-  HIPCHK(hipStreamSynchronize(ar->stream));
-  if (level) std::memcpy(level, mirror_of(ar, pa.level), q * 4);
-  if (view_cos) std::memcpy(view_cos, mirror_of(ar, pa.viewCos), q * 4);
-  if (proj_x) std::memcpy(proj_x, mirror_of(ar, pa.projX), q * 4);
-  if (proj_y) std::memcpy(proj_y, mirror_of(ar, pa.projY), q * 4);
-  if (proj_xr) std::memcpy(proj_xr, mirror_of(ar, pa.projXr), q * 4);
-  if (inv_z) std::memcpy(inv_z, mirror_of(ar, pa.invZ), q * 4);
-  if (dist) std::memcpy(dist, mirror_of(ar, pa.dist), q * 4);
-  if (in_view) std::memcpy(in_view, mirror_of(ar, pa.inView), q);
-  return ORBFE_OK;
 }
 }  // namespace
 
@@ -180,14 +144,3 @@ MapPointsLock::~MapPointsLock() {
   if (held) held->m.unlock();
 }
 }  // namespace orbfe
-
-extern "C" int orbfe_project_in_frustum(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
-                                        const orbfe_camera_pose* pose, float viewing_cos_limit, uint8_t* in_view, int32_t* level,
-                                        float* view_cos, float* proj_x, float* proj_y, float* proj_xr, float* inv_z, float* dist) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "project_in_frustum: NULL table");
-  if (const char* e = mappoints_check_slots(mp->capacity, n, slot)) return fail(ORBFE_ERR_INVALID, std::string("project_in_frustum: ") + e);
-  if (!pose_ok(pose)) return fail(ORBFE_ERR_INVALID, "project_in_frustum: bad pose (n_levels must be 1 .. 64)");
-  if (n == 0) return ORBFE_OK;
-  std::lock_guard<std::mutex> lk(mp->m);
-  return project_run(mp, n, slot, skip, pose, viewing_cos_limit, in_view, level, view_cos, proj_x, proj_y, proj_xr, inv_z, dist);
-}

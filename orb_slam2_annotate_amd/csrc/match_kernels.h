@@ -150,9 +150,17 @@ void launch_window_search(hipStream_t s, const GridFrame& f, const uint32_t* sor
 // Device map-point table (k_project.hip).  Slot s of the table: rec[2 s] = (X, Y, Z, mfMinDistance), rec[2 s + 1] = (nx, ny, nz,
 // mfMaxDistance), desc[32 s ..], flags[s] (ORBFE_MP_BAD | ORBFE_MP_OBSERVED).
 struct MapPointsDevice { float4* rec; uint8_t* desc; uint8_t* flags; };
+// Where a prologue writes the queries of the window search (k_window.hip: WindowQueries), and what the host holds of a job's
+// queries.  x == NULL: the launch writes no windows.  Optional, each NULL when nobody reads it: ur (the projected right
+// coordinate: the stereo check, or Fuse's chi-square gate), obs (Observations() > 0: does the point's match hide its feature),
+// validCopy (a second copy of `active` among the results that travel back).  desc rows are 32 bytes.
+struct QueryOut {
+  float* x; float* y; float* r; int32_t* minLevel; int32_t* maxLevel; uint8_t* active;
+  float* ur; uint8_t* desc; uint8_t* obs; uint8_t* validCopy;
+};
 // k_project_frustum: Frame::isInFrustum + MapPoint::PredictScale (src/Frame.cc:292-353) for the n points slot[0 .. n), one
 // lane per point.  Two sets of outputs, either may be absent: the fields isInFrustum leaves on the MapPoint (every pointer may
-// be NULL), and -- qx != NULL -- the query windows of SearchByProjection(Frame&, vector<MapPoint*>&, th) exactly as
+// be NULL), and -- q.x != NULL -- the query windows of SearchByProjection(Frame&, vector<MapPoint*>&, th) exactly as
 // orbfe_search_by_projection builds them on the host (src/ORBmatcher.cc:51-76), with the points' descriptors gathered from
 // the table, so that k_window_search / k_window_claim run behind it without a host step.
 struct ProjectArgs {
@@ -160,16 +168,14 @@ struct ProjectArgs {
   const int32_t* slot; const uint8_t* skip /* NULL: none */; int n;
   orbfe_camera_pose cam; float limit;
   uint8_t* inView; int32_t* level; float* viewCos; float* projX; float* projY; float* projXr; float* invZ; float* dist;
-  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive; float* qur /* NULL: monocular frame */;
-  uint8_t* qdesc; uint8_t* qobs /* Observations() > 0: does the point's match hide its feature */;
-  uint8_t* inViewCopy /* NULL, or a second copy of qactive next to the results that travel back */;
+  QueryOut q;
   const float* scale; float th;
 };
 void launch_project_frustum(hipStream_t s, const ProjectArgs& a);
 // k_project_fuse: the prologue of ORBmatcher::Fuse (src/ORBmatcher.cc:960-1006; the Sim3 overload :1135-1184) for the n points
 // slot[0 .. n) against K key-frame poses in ONE launch.  A workgroup owns 256 consecutive points, reads each point's two
 // records and flag byte once and walks the K poses, which it holds in LDS.  Arrays of results are [k * n + i].  Two sets of
-// outputs, either may be absent: the projection itself (every pointer may be NULL), and -- qx != NULL -- the query windows of
+// outputs, either may be absent: the projection itself (every pointer may be NULL), and -- q.x != NULL -- the query windows of
 // orbfe_fuse_search_multi exactly as it builds them on the host (centre (u, v), radius th * scale[level], octaves
 // [level - 1, level]), with the points' descriptors gathered once for all K jobs, so that k_window_search runs behind it
 // without a host step.  rows != NULL: IsInKeyFrame (:965) from the observation graph -- a point whose row names kfSlot[k]
@@ -183,20 +189,18 @@ struct FuseArgs {
   const orbfe_camera_pose* pose /* [K] */; const int32_t* kfSlot /* [K], read only with rows */;
   const ObsEntry* rows; const ObsPointMeta* meta; int rowWidth, pointCap;
   uint8_t* valid; float* u; float* v; float* ur; int32_t* level; float* dist;
-  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive;
-  float* qur /* NULL: no chi-square gate reads it */; uint8_t* qdesc /* [n * 32] */;
-  uint8_t* validCopy /* NULL, or a second copy of qactive among the results that travel back */;
+  QueryOut q;  // (desc: [n * 32], once for all K)
   const float* scale; float th;
 };
 void launch_project_fuse(hipStream_t s, const FuseArgs& a);
 // k_project_track: the prologues of the two tracking-thread searches that walk a frame's own map points, for K jobs over
 // concatenated lists in ONE launch (blockIdx.y = job k, points [offsets[k], offsets[k + 1]), pose[k], th[k]); one lane per point.
 //   form 0, SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1516-1550): no isBad test, invz < 0
-//   rejected, radius th * scale[lastOctave], the level range of `mode` (0 / 1 bForward / 2 bBackward), qobs = Observations() > 0;
+//   rejected, radius th * scale[lastOctave], the level range of `mode` (0 / 1 bForward / 2 bBackward), q.obs = Observations() > 0;
 //   form 1, SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (:1665-1699): isBad and skip rejected, no depth
 //   sign test, the distance range, PredictScale, radius th * scale[level], levels [level - 1, level + 1].
 // Two sets of outputs, either may be absent: the projection itself (every pointer may be NULL; entries of a rejected point
-// are 0) and -- qx != NULL -- the query windows exactly as orbfe_search_by_projection_last_frame / _keyframe build them on the
+// are 0) and -- q.x != NULL -- the query windows exactly as orbfe_search_by_projection_last_frame / _keyframe build them on the
 // host, with the points' descriptors gathered from the table, so that k_window_search / k_window_claim run behind it without
 // a host step.  Every array is indexed by the position in the concatenated list.
 constexpr int kTrackMaxJobs = 64;
@@ -207,9 +211,7 @@ struct TrackArgs {
   const int32_t* lastOctave /* form 0 */; const orbfe_camera_pose* pose /* [K] */; const float* th /* [K] */;
   uint8_t* valid; float* u; float* v; float* invZ; float* ur /* form 0 */; float* radius /* form 0 */;
   int32_t* level /* form 1 */; float* dist /* form 1 */;
-  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive;
-  float* qur /* form 0, NULL: monocular frame */; uint8_t* qdesc; uint8_t* qobs /* form 0 */;
-  uint8_t* validCopy /* NULL, or a second copy of qactive among the results that travel back */;
+  QueryOut q;  // (ur, obs: form 0)
   const float* scale;
 };
 void launch_project_track(hipStream_t s, const TrackArgs& a, int maxN /* the longest list of the K jobs */);
@@ -217,7 +219,7 @@ void launch_project_track(hipStream_t s, const TrackArgs& a, int maxN /* the lon
 // launch; a leg is one direction of one candidate (blockIdx.y = leg, one lane per point, a workgroup owns 256 consecutive
 // points of its leg).  Leg l reads slot[span.slotOff + i] (-1: no map point) and writes every array at [span.outOff + i], so
 // the K "1 -> 2" legs of a call share ONE copy of KF1's slot list and -- span.flags & 1 on the first of them only -- one gather
-// of its descriptors into qdesc[(span.slotOff + i) * 32].  span.flags & 2: the leg's target uses the second level table
+// of its descriptors into q.desc[(span.slotOff + i) * 32].  span.flags & 2: the leg's target uses the second level table
 // (scale + nLevels).  Two sets of outputs, either may be absent, as for k_project_fuse; the arithmetic is include/orbfe.h's
 // (orbfe_project_sim3), operation by operation.
 constexpr int kSim3MaxLegs = 128;
@@ -228,7 +230,7 @@ struct Sim3Args {
   const Sim3Span* span /* [nLegs] */; const orbfe_sim3_leg* leg /* [nLegs] */;
   const int32_t* slot; const uint8_t* skip /* by output position, NULL: none */;
   uint8_t* valid; float* u; float* v; int32_t* level; float* dist;
-  float* qx; float* qy; float* qr; int32_t* qmin; int32_t* qmax; uint8_t* qactive; uint8_t* qdesc;
+  QueryOut q;  // (no ur, obs or validCopy; desc by slot position)
   const float* scale /* [nLevels] or [2 * nLevels] */; float th;
 };
 void launch_project_sim3(hipStream_t s, const Sim3Args& a, int maxN /* the longest leg */);

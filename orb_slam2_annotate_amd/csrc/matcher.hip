@@ -1,7 +1,8 @@
 // matcher.hip -- C-ABI entry points of the searches (include/orbfe.h, "Matcher"): the Hamming utilities, the FeatureVector
 // searches (SearchByBoW, SearchForTriangulation), the stereo matcher, and the window searches (GetFeaturesInArea, the
-// projection searches, Fuse, SearchBySim3).  Stateless and re-entrant: every call runs on the calling thread's own arena and
-// stream (arena.h); resident frames are frame.h / frames.hip, the map-point table mappoints.hip.
+// projection searches, Fuse, SearchBySim3) on host arrays, with the machinery of a window-search call (window_call.h).
+// Stateless and re-entrant: every call runs on the calling thread's own arena and stream (arena.h); resident frames are
+// frame.h / frames.hip, the searches on the resident map points mappoints_search.hip.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -15,9 +16,8 @@
 #include "frame.h"
 #include "host_internal.h"
 #include "kernels.h"
-#include "mappoints_host.h"
 #include "match_kernels.h"
-#include "obsgraph_kernels.h"
+#include "window_call.h"
 
 using namespace orbfe;
 
@@ -524,181 +524,24 @@ extern "C" int orbfe_compute_stereo_matches(orbfe_extractor* left, int frameL, o
 }
 
 // ---------------------------------------------------------------------------------------------
-// Frame grid, GetFeaturesInArea and the two tracking-thread projection searches
-// (SURVEY.md 8(f) rank 1).  The device gathers every window and takes the Hamming distances
-// (k_window.hip); the claim logic below is the reference's sequential loop over the compact
-// per-query candidate lists -- it depends on the order of the map points and stays on the host.
+// Frame grid, GetFeaturesInArea and the projection searches: the machinery of one window-search
+// call (window_call.h).  The device gathers every window and takes the Hamming distances (k_window.hip); the claim loops
+// run behind it on the device (k_window_claim), so the candidate lists never leave it.  A call's queries travel with it as
+// host arrays, or a producer (window_call.h: Producer; mappoints_search.hip) writes them on the device.
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-struct WindowResult {
-  std::vector<int32_t> count;
-  std::vector<uint32_t> cand;  // [nq * K] (dist << 16 | feature index) in scan order
-  int K = 0;
-};
-
+namespace orbfe {
 bool frame_ok(const orbfe_frame_view* f) {
   if (!f || f->n < 0 || f->n > GRID_MAX_FEATURES) return false;
   if (!(f->max_x > f->min_x) || !(f->max_y > f->min_y)) return false;
   if (f->n > 0 && (!f->x || !f->y || !f->octave)) return false;
   return true;
 }
+}  // namespace orbfe
 
-// One window search = one frame + one set of query windows.  Several jobs of a call (Fuse against K neighbour key frames,
-// the two directions of SearchBySim3) share ONE upload, one group of launches, one download and one synchronisation.
-struct WindowJob {
-  const orbfe_frame_view* f = nullptr;
-  int nq = 0;
-  const float *qx = nullptr, *qy = nullptr, *qr = nullptr;
-  const int32_t *qmin = nullptr, *qmax = nullptr;
-  const uint8_t* qactive = nullptr;
-  const float* qur = nullptr;
-  const uint8_t* qdesc = nullptr;  // jobs that pass the SAME pointer share one device copy
-  // list mode (res != NULL): the counts and candidate lists come back
-  WindowResult* res = nullptr;
-  // BEST mode (bestOut != NULL): no candidate lists come back -- the device keeps the first minimum of every window, behind
-  // Fuse's chi-square gate when gate != 0 (gur / invSigma2), and writes the keypoint or -1 (WindowQueries::best)
-  int32_t* bestOut = nullptr;
-  const float* gur = nullptr;
-  const float* invSigma2 = nullptr;
-  int nLevels = 0, gate = 0, maxDist = 256;
-  // CLAIM mode (claim != NULL): the lists stay on the device and k_window_claim replays the reference's claim loop over
-  // them (match_kernels.h: ClaimJob); the match array, the count and -- SearchForInitialization -- the updated previous
-  // positions come back
-  struct ClaimSpec* claim = nullptr;
-  // PRODUCER (claim jobs only): the query arrays above are NULL -- k_project_frustum writes them on the device, behind the
-  // call's one upload, from the map-point table; only the slot list, the skip mask and the scale factors travel
-  struct FrustumProducer* producer = nullptr;
-  // FUSE PRODUCER (BEST jobs only): the K jobs of a call name ONE FuseProducer and their place k in it; the query arrays above
-  // are NULL -- ONE k_project_fuse launch writes the windows of all K jobs from the map-point table, and the descriptors once
-  struct FuseProducer* fuse = nullptr;
-  int fuseK = 0;
-  // TRACK PRODUCER (CLAIM_BEST jobs only): the jobs of a call name ONE TrackProducer and their place k in it; the query arrays
-  // above are NULL -- ONE k_project_track launch writes the windows of all its jobs from the map-point table, each job's
-  // descriptors and, in the last-frame form, blockVal (Observations() > 0)
-  struct TrackProducer* track = nullptr;
-  int trackK = 0;
-  // SIM3 PRODUCER (BEST jobs only): the jobs of a call name ONE Sim3Producer and the leg they search for; the query arrays above
-  // are NULL -- ONE k_project_sim3 launch writes the windows of all legs from the map-point table, and KF1's descriptors once
-  struct Sim3Producer* sim3 = nullptr;
-  int sim3Leg = 0;
-};
-// The prologue of SearchBySim3 for nLegs legs.  slot[] holds every source list once (KF1's, then the candidates'); the outputs
-// and skip[] are by OUTPUT position (a leg's span says where both start), so K legs may read one list.
-static_assert(kSim3MaxLegs == kSim3MaxLegRecords, "the kernel's leg limit is the one sim3_check_legs enforces");
-struct Sim3Producer {
-  MapPointsDevice table;
-  int nLegs = 0;
-  const Sim3Span* span = nullptr;        // [nLegs]
-  const orbfe_sim3_leg* leg = nullptr;   // [nLegs]
-  const int32_t* slot = nullptr; size_t nSlot = 0;
-  const uint8_t* skip = nullptr; size_t nOut = 0;  // [nOut] or NULL
-  const float* scale = nullptr;          // [nScale] level table(s)
-  int nScale = 0, nLevels = 0;
-  float th = 0.0f;
-  // vbAlreadyMatched2 from the observation rows (graph != NULL): a scatter into skip[already2Off ..] ahead of the prologue
-  const ObsGraphDevice* graph = nullptr;
-  const int32_t *matched = nullptr, *kfSlot = nullptr, *offsets2 = nullptr;
-  int K = 0, n1 = 0;
-  size_t already2Off = 0;
-  int longest() const {
-    int m = 0;
-    for (int l = 0; l < nLegs; l++) m = span[l].n > m ? span[l].n : m;
-    return m;
-  }
-};
-struct Sim3Dev {
-  Sim3Span* span = nullptr;
-  orbfe_sim3_leg* leg = nullptr;
-  int32_t *slot = nullptr, *matched = nullptr, *kfSlot = nullptr, *offsets2 = nullptr;
-  uint8_t* skip = nullptr;
-  float* scale = nullptr;
-  float *qx = nullptr, *qy = nullptr, *qr = nullptr;
-  int32_t *qmin = nullptr, *qmax = nullptr;
-  uint8_t *qactive = nullptr, *qdesc = nullptr;
-};
-// The prologue of the last-frame (form 0) or key-frame (form 1) SearchByProjection for K jobs over concatenated lists
-struct TrackProducer {
-  MapPointsDevice table;
-  int form = 0, K = 0, mode = 0;
-  const int32_t* offsets = nullptr;     // [K + 1]
-  const int32_t* slot = nullptr;        // [offsets[K]]
-  const uint8_t* skip = nullptr;        // [offsets[K]] or NULL
-  const int32_t* lastOctave = nullptr;  // [offsets[K]] (form 0)
-  const orbfe_camera_pose* pose = nullptr;  // [K]
-  const float* th = nullptr;                // [K]
-  const float* scale = nullptr;             // [nLevels] mvScaleFactors
-  int nLevels = 0;
-  uint8_t* validOut = nullptr;  // out [offsets[K]] or NULL
-  int total() const { return offsets[K]; }
-  int longest() const {
-    int m = 0;
-    for (int k = 0; k < K; k++) m = offsets[k + 1] - offsets[k] > m ? offsets[k + 1] - offsets[k] : m;
-    return m;
-  }
-};
-// where a call's TrackProducer has its arrays on the device: uploads | the one result | what k_project_track writes for the search
-struct TrackDev {
-  int32_t *offsets = nullptr, *slot = nullptr, *lastOctave = nullptr;
-  uint8_t* skip = nullptr;
-  orbfe_camera_pose* pose = nullptr;
-  float *th = nullptr, *scale = nullptr;
-  uint8_t* valid = nullptr;
-  float *qx = nullptr, *qy = nullptr, *qr = nullptr, *qur = nullptr;
-  int32_t *qmin = nullptr, *qmax = nullptr;
-  uint8_t *qactive = nullptr, *qdesc = nullptr, *qobs = nullptr;
-};
-struct FuseProducer {
-  MapPointsDevice table;
-  const ObsGraphDevice* graph = nullptr;  // NULL: no IsInKeyFrame test
-  const int32_t* slot = nullptr;          // [n]
-  const uint8_t* skip = nullptr;          // [K * n] or NULL
-  const orbfe_camera_pose* pose = nullptr;  // [K]
-  const int32_t* kfSlot = nullptr;          // [K] (with graph)
-  int n = 0, K = 0;
-  const float* scale = nullptr;      // [nLevels] mvScaleFactors
-  const float* invSigma2 = nullptr;  // [nLevels] mvInvLevelSigma2 (gate)
-  int nLevels = 0;
-  float th = 3.0f;
-  bool gate = false;
-  uint8_t* projectedOut = nullptr;  // out [K * n] or NULL
-};
-// where a call's FuseProducer has its arrays on the device: uploads | the one result | what k_project_fuse writes for the search
-struct FuseDev {
-  int32_t *slot = nullptr, *kfSlot = nullptr;
-  uint8_t* skip = nullptr;
-  orbfe_camera_pose* pose = nullptr;
-  float *scale = nullptr, *invSigma2 = nullptr;
-  uint8_t* projected = nullptr;
-  float *qx = nullptr, *qy = nullptr, *qr = nullptr, *qur = nullptr;
-  int32_t *qmin = nullptr, *qmax = nullptr;
-  uint8_t *qactive = nullptr, *qdesc = nullptr;
-};
-struct FrustumProducer {
-  MapPointsDevice table;
-  const int32_t* slot;      // [nq]
-  const uint8_t* skip;      // [nq] or NULL
-  orbfe_camera_pose pose;
-  float limit = 0.0f, th = 1.0f;
-  const float* scale = nullptr;  // [nLevels] mvScaleFactors
-  int nLevels = 0;
-  uint8_t* inViewOut = nullptr;  // out [nq] or NULL
-};
-struct ClaimSpec {
-  int mode = CLAIM_BEST, maxDist = 100, checkOri = 0;
-  float nnratio = 0.0f;
-  const uint8_t* blocked = nullptr;   // [f->n] features taken at entry (NULL: none)
-  const uint8_t* blockVal = nullptr;  // [nq] does query i's match hide its feature (NULL: always)
-  const float* qAngle = nullptr;      // [nq] (checkOri)
-  int32_t* match = nullptr;           // out: [f->n] (BEST / RATIO) or [nq] (INIT)
-  int32_t* nMatches = nullptr;        // out
-  float* prevX = nullptr;             // INIT, out [nq]: the matched feature's position, else the query's own
-  float* prevY = nullptr;
-  int rounds = 0;                     // out: rounds the fixed point took
-};
+namespace {
 
-// Where a job's arrays are on the device: carved from the call's arena by the three stage_* helpers below, or a resident
-// frame's own.  NULL where the job has no such array.
+// Where a job's arrays are on the device: carved from the call's arena by the three stage_* helpers below, a slice of what
+// the call's producer writes, or a resident frame's own.  NULL where the job has no such array.
 struct JobDev {
   bool withDesc = false, withUr = false;  // the search takes descriptor distances / runs the stereo check
   int frameOf = -1;  // the job whose uploaded frame arrays and grid this one uses (itself: it uploads and builds); -1: resident
@@ -706,10 +549,10 @@ struct JobDev {
   int32_t *oct = nullptr, *cell = nullptr;
   uint8_t* desc = nullptr;
   uint32_t* key = nullptr;
-  float *qx = nullptr, *qy = nullptr, *qr = nullptr, *qur = nullptr;  // queries: uploaded, or written by k_project_frustum ...
-  int32_t *qmin = nullptr, *qmax = nullptr, *slot = nullptr;          // ... from slot / skip / scale
-  uint8_t *qactive = nullptr, *qdesc = nullptr, *skip = nullptr;
-  float *scale = nullptr, *gateUr = nullptr, *invSigma2 = nullptr;    // (BEST mode behind Fuse's gate)
+  float *qx = nullptr, *qy = nullptr, *qr = nullptr, *qur = nullptr;  // queries: uploaded, or the producer's
+  int32_t *qmin = nullptr, *qmax = nullptr;
+  uint8_t *qactive = nullptr, *qdesc = nullptr;
+  float *gateUr = nullptr, *invSigma2 = nullptr;  // (BEST mode behind Fuse's gate)
   uint8_t *blocked = nullptr, *blockVal = nullptr;  // CLAIM mode: inputs, scratch, the dynamic LDS the job's workgroup needs
   float* qAngle = nullptr;
   int32_t *choice = nullptr, *link = nullptr, *owner = nullptr;
@@ -718,110 +561,18 @@ struct JobDev {
   uint32_t* cand = nullptr;
   int32_t *best = nullptr, *header = nullptr, *match = nullptr;  // results of BEST / CLAIM mode
   float *prevX = nullptr, *prevY = nullptr;
-  uint8_t* inView = nullptr;
 };
 
 // Region 1 of a call's arena, job j's part: everything that travels up.  Only up() between the first and the last of these,
 // so that flush()'s dirty range is exactly the uploads: one host-to-device copy.
-hipError_t stage_fuse_inputs(Arena* a, const FuseProducer& P, FuseDev* F) {
-  const size_t q = (size_t)P.K * P.n;
-  TRY(up(a, &F->slot, P.slot, (size_t)P.n));
-  if (P.skip) TRY(up(a, &F->skip, P.skip, q));
-  TRY(up(a, &F->pose, P.pose, (size_t)P.K));
-  if (P.graph) TRY(up(a, &F->kfSlot, P.kfSlot, (size_t)P.K));
-  if (P.scale) TRY(up(a, &F->scale, P.scale, (size_t)P.nLevels));
-  if (P.gate) TRY(up(a, &F->invSigma2, P.invSigma2, (size_t)P.nLevels));
-  return hipSuccess;
-}
-void stage_fuse_scratch(Arena* a, const FuseProducer& P, FuseDev* F) {
-  const size_t q = (size_t)P.K * P.n;
-  F->qx = carve<float>(a, q); F->qy = carve<float>(a, q); F->qr = carve<float>(a, q);
-  F->qmin = carve<int32_t>(a, q); F->qmax = carve<int32_t>(a, q);
-  F->qactive = carve<uint8_t>(a, q);
-  if (P.gate) F->qur = carve<float>(a, q);
-  F->qdesc = carve<uint8_t>(a, (size_t)P.n * 32);
-}
-FuseArgs fuse_args(const FuseProducer& P, const FuseDev& F) {
-  FuseArgs fa{};
-  fa.table = P.table; fa.slot = F.slot; fa.skip = F.skip; fa.n = P.n; fa.K = P.K; fa.pose = F.pose; fa.kfSlot = F.kfSlot;
-  if (P.graph) { fa.rows = P.graph->rows; fa.meta = P.graph->meta; fa.rowWidth = P.graph->rowWidth; fa.pointCap = P.graph->pointCap; }
-  fa.qx = F.qx; fa.qy = F.qy; fa.qr = F.qr; fa.qmin = F.qmin; fa.qmax = F.qmax; fa.qactive = F.qactive; fa.qur = F.qur;
-  fa.qdesc = F.qdesc; fa.validCopy = F.projected;
-  fa.scale = F.scale; fa.th = P.th;
-  return fa;
-}
-
-hipError_t stage_track_inputs(Arena* a, const TrackProducer& P, TrackDev* T) {
-  const size_t q = (size_t)P.total();
-  TRY(up(a, &T->offsets, P.offsets, (size_t)P.K + 1));
-  TRY(up(a, &T->slot, P.slot, q));
-  if (P.skip) TRY(up(a, &T->skip, P.skip, q));
-  if (P.form == 0) TRY(up(a, &T->lastOctave, P.lastOctave, q));
-  TRY(up(a, &T->pose, P.pose, (size_t)P.K));
-  if (P.th) TRY(up(a, &T->th, P.th, (size_t)P.K));
-  if (P.scale) TRY(up(a, &T->scale, P.scale, (size_t)P.nLevels));
-  return hipSuccess;
-}
-void stage_track_scratch(Arena* a, const TrackProducer& P, bool withUr, TrackDev* T) {
-  const size_t q = (size_t)P.total();
-  T->qx = carve<float>(a, q); T->qy = carve<float>(a, q); T->qr = carve<float>(a, q);
-  T->qmin = carve<int32_t>(a, q); T->qmax = carve<int32_t>(a, q);
-  T->qactive = carve<uint8_t>(a, q);
-  if (P.form == 0) T->qobs = carve<uint8_t>(a, q);
-  if (withUr) T->qur = carve<float>(a, q);
-  T->qdesc = carve<uint8_t>(a, q * 32);
-}
-TrackArgs track_args(const TrackProducer& P, const TrackDev& T) {
-  TrackArgs ta{};
-  ta.table = P.table; ta.form = P.form; ta.K = P.K; ta.mode = P.mode;
-  ta.offsets = T.offsets; ta.slot = T.slot; ta.skip = T.skip; ta.lastOctave = T.lastOctave; ta.pose = T.pose; ta.th = T.th;
-  ta.qx = T.qx; ta.qy = T.qy; ta.qr = T.qr; ta.qmin = T.qmin; ta.qmax = T.qmax; ta.qactive = T.qactive; ta.qur = T.qur;
-  ta.qdesc = T.qdesc; ta.qobs = T.qobs; ta.validCopy = T.valid;
-  ta.scale = T.scale;
-  return ta;
-}
-
-hipError_t stage_sim3_inputs(Arena* a, const Sim3Producer& P, Sim3Dev* S) {
-  TRY(up(a, &S->span, P.span, (size_t)P.nLegs));
-  TRY(up(a, &S->leg, P.leg, (size_t)P.nLegs));
-  TRY(up(a, &S->slot, P.slot, P.nSlot));
-  if (P.skip) TRY(up(a, &S->skip, P.skip, P.nOut));
-  if (P.scale) TRY(up(a, &S->scale, P.scale, (size_t)P.nScale));
-  if (P.graph) {
-    TRY(up(a, &S->matched, P.matched, (size_t)P.K * P.n1));
-    TRY(up(a, &S->kfSlot, P.kfSlot, (size_t)P.K));
-    TRY(up(a, &S->offsets2, P.offsets2, (size_t)P.K + 1));
-  }
-  return hipSuccess;
-}
-void stage_sim3_scratch(Arena* a, const Sim3Producer& P, Sim3Dev* S) {
-  const size_t q = P.nOut;
-  S->qx = carve<float>(a, q); S->qy = carve<float>(a, q); S->qr = carve<float>(a, q);
-  S->qmin = carve<int32_t>(a, q); S->qmax = carve<int32_t>(a, q);
-  S->qactive = carve<uint8_t>(a, q);
-  S->qdesc = carve<uint8_t>(a, P.nSlot * 32);
-}
-Sim3Args sim3_args(const Sim3Producer& P, const Sim3Dev& S) {
-  Sim3Args sa{};
-  sa.table = P.table; sa.nLegs = P.nLegs; sa.nLevels = P.nLevels; sa.span = S.span; sa.leg = S.leg; sa.slot = S.slot; sa.skip = S.skip;
-  sa.qx = S.qx; sa.qy = S.qy; sa.qr = S.qr; sa.qmin = S.qmin; sa.qmax = S.qmax; sa.qactive = S.qactive; sa.qdesc = S.qdesc;
-  sa.scale = S.scale; sa.th = P.th;
-  return sa;
-}
-// the scatter of vbAlreadyMatched2 from the observation rows, ahead of the prologue on the same stream
-void sim3_already(hipStream_t s, const Sim3Producer& P, const Sim3Dev& S) {
-  if (!P.graph) return;
-  launch_sim3_already(s, P.graph->rows, P.graph->meta, P.graph->rowWidth, P.graph->pointCap, P.K, P.n1, S.matched, S.kfSlot, S.offsets2,
-                      S.skip + P.already2Off);
-}
-
-hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, const FuseDev& fuse) {
+hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev) {
   const WindowJob& J = jobs[j];
+  const Producer* P = J.producer;
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
   D = JobDev{};
-  D.withDesc = J.f->desc && (J.qdesc || J.producer || J.fuse || J.track || J.sim3);
-  D.withUr = (J.qur || J.producer || (J.track && J.track->form == 0)) && J.f->u_right;
+  D.withDesc = J.f->desc && (J.qdesc || P);
+  D.withUr = J.f->u_right && (P ? !J.bestOut && P->with_ur(true) : J.qur != nullptr);
   if (const orbfe_frame* R = J.f->resident) {
     D.x = R->dx; D.y = R->dy; D.oct = R->doct; D.ur = J.f->u_right ? R->dur : nullptr; D.desc = D.withDesc ? R->ddesc : nullptr;
     D.angle = R->dangle; D.key = R->dkey; D.cell = R->dcell;
@@ -838,14 +589,8 @@ hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, con
       if (D.withDesc) TRY(up(a, &D.desc, J.f->desc, n * 32));
     }
   }
-  if (const FrustumProducer* P = J.producer) {
-    TRY(up(a, &D.slot, P->slot, q));
-    if (P->skip) TRY(up(a, &D.skip, P->skip, q));
-    TRY(up(a, &D.scale, P->scale, (size_t)P->nLevels));
-  } else if (J.fuse) {  // (the call's one FuseProducer has uploaded everything: stage_fuse_inputs)
-    if (J.fuse->gate) D.invSigma2 = fuse.invSigma2;
-  } else if (J.track) {  // (the call's one TrackProducer has uploaded everything: stage_track_inputs)
-  } else if (J.sim3) {   // (likewise the call's one Sim3Producer: stage_sim3_inputs)
+  if (P) {  // (the call's producer has uploaded everything: Producer::upload)
+    if (J.bestOut && J.gate) D.invSigma2 = P->invSigma2;
   } else {
     TRY(up(a, &D.qx, J.qx, q)); TRY(up(a, &D.qy, J.qy, q)); TRY(up(a, &D.qr, J.qr, q));
     TRY(up(a, &D.qmin, J.qmin, q)); TRY(up(a, &D.qmax, J.qmax, q));
@@ -854,7 +599,7 @@ hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, con
     if (D.withDesc) {  // the same descriptors for several jobs (Fuse: one set of map points into K key frames): one copy
       int shared = -1;
       for (int k = 0; k < j && shared < 0; k++)
-        if (!jobs[k].producer && dev[k].withDesc && jobs[k].qdesc == J.qdesc && jobs[k].nq == J.nq) shared = k;
+        if (dev[k].withDesc && jobs[k].qdesc == J.qdesc && jobs[k].nq == J.nq) shared = k;
       if (shared >= 0) D.qdesc = dev[shared].qdesc; else TRY(up(a, &D.qdesc, J.qdesc, q * 32));
     }
     if (J.bestOut && J.gate && J.gur) TRY(up(a, &D.gateUr, J.gur, q));
@@ -863,7 +608,7 @@ hipError_t stage_inputs(Arena* a, const WindowJob* jobs, int j, JobDev* dev, con
   if (const ClaimSpec* C = J.claim) {
     if (C->checkOri && !J.f->resident) TRY(up(a, &D.angle, J.f->angle, n));  // (a resident frame has its angles on the device)
     if (C->blocked) TRY(up(a, &D.blocked, C->blocked, n));
-    if (C->blockVal && !J.producer) TRY(up(a, &D.blockVal, C->blockVal, q));  // (a producer writes it: Observations() > 0)
+    if (C->blockVal && !P) TRY(up(a, &D.blockVal, C->blockVal, q));  // (a producer writes it: Observations() > 0)
     if (C->checkOri) TRY(up(a, &D.qAngle, C->qAngle, q));
   }
   return hipSuccess;
@@ -883,7 +628,6 @@ void stage_outputs(Arena* a, const WindowJob& J, int K, JobDev* D) {
     D->header = carve<int32_t>(a, 4);
     D->match = carve<int32_t>(a, ini ? q : n);
     if (ini) { D->prevX = carve<float>(a, q); D->prevY = carve<float>(a, q); }
-    if (J.producer && J.producer->inViewOut) D->inView = carve<uint8_t>(a, q);
   }
 }
 
@@ -897,41 +641,36 @@ OwnerPlace owner_place(const WindowJob& J) {
   return OwnerPlace{ints, (inLds ? ints * 4 : 0) + octBytes, inLds};
 }
 
-// Region 3, job j's part: what never leaves the device -- the grid of an uploaded frame, the query arrays a producer
-// writes, the claim kernel's lists and scratch
-void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev, const FuseDev& fuse, const TrackDev& track,
-                   const Sim3Dev& sim3) {
+// Region 3, the producer's part: the query arrays its launch writes, for all its parts -- the one carve of them
+void carve_queries(Arena* a, Producer* P, const WindowJob* jobs, int nJobs) {
+  const size_t n = P->total();
+  bool ur = false;
+  for (int j = 0; j < nJobs; j++) ur = ur || P->with_ur(jobs[j].f->u_right != nullptr);
+  QueryOut& q = P->q;
+  q.x = carve<float>(a, n); q.y = carve<float>(a, n); q.r = carve<float>(a, n);
+  q.minLevel = carve<int32_t>(a, n); q.maxLevel = carve<int32_t>(a, n);
+  q.active = carve<uint8_t>(a, n);
+  if (P->with_obs()) q.obs = carve<uint8_t>(a, n);
+  if (ur) q.ur = carve<float>(a, n);
+  q.desc = carve<uint8_t>(a, P->desc_rows() * 32);
+}
+
+// Region 3, job j's part: what never leaves the device -- the grid of an uploaded frame, its slice of the producer's query
+// arrays, the claim kernel's lists and scratch
+void stage_scratch(Arena* a, const WindowJob* jobs, int j, int K, JobDev* dev) {
   const WindowJob& J = jobs[j];
   JobDev& D = dev[j];
   const size_t n = (size_t)J.f->n, q = (size_t)J.nq;
-  if (J.sim3) {  // the leg's part of what the one k_project_sim3 launch writes; its descriptors lie where its slot list does
-    const Sim3Span& sp = J.sim3->span[J.sim3Leg];
-    const size_t o = (size_t)sp.outOff;
-    D.qx = sim3.qx + o; D.qy = sim3.qy + o; D.qr = sim3.qr + o; D.qmin = sim3.qmin + o; D.qmax = sim3.qmax + o;
-    D.qactive = sim3.qactive + o; D.qdesc = sim3.qdesc + (size_t)sp.slotOff * 32;
-  }
-  if (J.track) {  // job k's part of what the one k_project_track launch writes
-    const size_t o = (size_t)J.track->offsets[J.trackK];
-    D.qx = track.qx + o; D.qy = track.qy + o; D.qr = track.qr + o; D.qmin = track.qmin + o; D.qmax = track.qmax + o;
-    D.qactive = track.qactive + o; D.qdesc = track.qdesc + o * 32;
-    if (track.qobs) D.blockVal = track.qobs + o;
-    if (D.withUr) D.qur = track.qur + o;
-  }
-  if (J.fuse) {  // job k's part of what the one k_project_fuse launch writes
-    const size_t o = (size_t)J.fuseK * q;
-    D.qx = fuse.qx + o; D.qy = fuse.qy + o; D.qr = fuse.qr + o; D.qmin = fuse.qmin + o; D.qmax = fuse.qmax + o;
-    D.qactive = fuse.qactive + o; D.qdesc = fuse.qdesc;
-    if (J.fuse->gate && J.f->u_right) D.gateUr = fuse.qur + o;
+  if (J.producer) {
+    const QueryOut pq = J.producer->part_queries(J.part);
+    D.qx = pq.x; D.qy = pq.y; D.qr = pq.r; D.qmin = pq.minLevel; D.qmax = pq.maxLevel; D.qactive = pq.active;
+    D.qdesc = D.withDesc ? pq.desc : nullptr;
+    if (pq.obs) D.blockVal = pq.obs;
+    if (D.withUr) D.qur = pq.ur;
+    if (J.bestOut && J.gate && J.f->u_right) D.gateUr = pq.ur;
   }
   if (D.frameOf == j) { D.key = carve<uint32_t>(a, n); D.cell = carve<int32_t>(a, 3073); }
   else if (D.frameOf >= 0) { D.key = dev[D.frameOf].key; D.cell = dev[D.frameOf].cell; }
-  if (J.producer) {
-    D.qx = carve<float>(a, q); D.qy = carve<float>(a, q); D.qr = carve<float>(a, q);
-    D.qmin = carve<int32_t>(a, q); D.qmax = carve<int32_t>(a, q);
-    D.qactive = carve<uint8_t>(a, q); D.blockVal = carve<uint8_t>(a, q);
-    if (D.withUr) D.qur = carve<float>(a, q);
-    if (D.withDesc) D.qdesc = carve<uint8_t>(a, q * 32);
-  }
   if (J.claim) {
     // k_window_claim reads a list as pairs of 16-byte requests, eight entries at a time and never past entry K: K is a
     // multiple of 8 and carve() aligns the first list
@@ -968,17 +707,6 @@ WindowSearchJob search_job(const WindowJob& J, const JobDev& D, int K, int block
   return WindowSearchJob{g, D.key, D.cell, w, D.count, D.cand, blockStart};
 }
 
-// a producer job's k_project_frustum: the query arrays, written where the searches read them
-ProjectArgs project_args(const WindowJob& J, const JobDev& D) {
-  const FrustumProducer& P = *J.producer;
-  ProjectArgs pa{};
-  pa.table = P.table; pa.slot = D.slot; pa.skip = D.skip; pa.n = J.nq; pa.cam = P.pose; pa.limit = P.limit;
-  pa.qx = D.qx; pa.qy = D.qy; pa.qr = D.qr; pa.qmin = D.qmin; pa.qmax = D.qmax; pa.qactive = D.qactive; pa.qur = D.qur;
-  pa.qdesc = D.qdesc; pa.qobs = D.blockVal; pa.inViewCopy = D.inView;
-  pa.scale = D.scale; pa.th = P.th;
-  return pa;
-}
-
 // What arena_stage() leaves of a call: every job's pointers, the kernels' argument blocks and where they and the results are
 struct WindowCall {
   std::vector<JobDev> dev;
@@ -987,44 +715,29 @@ struct WindowCall {
   ClaimJob* dClaims = nullptr;
   WindowSearchJob* dSearches = nullptr;  // (a single job travels as kernel arguments)
   uint8_t *outLo = nullptr, *outHi = nullptr;
-  const FuseProducer* fuseProducer = nullptr;  // the one FuseProducer of the call's jobs, and where it is on the device
-  FuseDev fuse;
-  const TrackProducer* trackProducer = nullptr;  // likewise the one TrackProducer
-  TrackDev track;
-  const Sim3Producer* sim3Producer = nullptr;  // likewise the one Sim3Producer
-  Sim3Dev sim3;
   size_t claimLds = 0;
   int totalBlocks = 0;
 };
 
 // The arena of a call, in the order that keeps it at one copy each way: uploads | results | what stays on the device.  The
 // argument blocks hold device addresses, known once everything is carved: they get their room behind the other uploads
-// and are put() there at the end.
-hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, int K, WindowCall* c) {
+// and are put() there at the end.  P: the call's producer or NULL; every pass leaves its device pointers anew.
+hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, Producer* P, int nClaim, int K, WindowCall* c) {
   *c = WindowCall{};
   c->dev.resize((size_t)nJobs);
-  for (int j = 0; j < nJobs && !c->fuseProducer; j++) c->fuseProducer = jobs[j].fuse;
-  if (c->fuseProducer) TRY(stage_fuse_inputs(a, *c->fuseProducer, &c->fuse));
-  for (int j = 0; j < nJobs && !c->trackProducer; j++) c->trackProducer = jobs[j].track;
-  if (c->trackProducer) TRY(stage_track_inputs(a, *c->trackProducer, &c->track));
-  for (int j = 0; j < nJobs && !c->sim3Producer; j++) c->sim3Producer = jobs[j].sim3;
-  if (c->sim3Producer) TRY(stage_sim3_inputs(a, *c->sim3Producer, &c->sim3));
-  for (int j = 0; j < nJobs; j++) TRY(stage_inputs(a, jobs, j, c->dev.data(), c->fuse));
+  if (P) {
+    P->q = QueryOut{};
+    TRY(P->upload(a));
+  }
+  for (int j = 0; j < nJobs; j++) TRY(stage_inputs(a, jobs, j, c->dev.data()));
   c->dClaims = carve<ClaimJob>(a, (size_t)nClaim);
   c->dSearches = carve<WindowSearchJob>(a, nJobs > 1 ? (size_t)nJobs : 0);
   c->outLo = carve<uint8_t>(a, 0);
   for (int j = 0; j < nJobs; j++) stage_outputs(a, jobs[j], K, &c->dev[j]);
-  if (c->fuseProducer && c->fuseProducer->projectedOut) c->fuse.projected = carve<uint8_t>(a, (size_t)c->fuseProducer->K * c->fuseProducer->n);
-  if (c->trackProducer && c->trackProducer->validOut) c->track.valid = carve<uint8_t>(a, (size_t)c->trackProducer->total());
+  if (P && P->flagsOut) P->q.validCopy = carve<uint8_t>(a, P->total());
   c->outHi = carve<uint8_t>(a, 0);
-  if (c->fuseProducer) stage_fuse_scratch(a, *c->fuseProducer, &c->fuse);
-  if (c->trackProducer) {
-    bool withUr = false;
-    for (int j = 0; j < nJobs; j++) withUr = withUr || c->dev[j].withUr;
-    stage_track_scratch(a, *c->trackProducer, withUr, &c->track);
-  }
-  if (c->sim3Producer) stage_sim3_scratch(a, *c->sim3Producer, &c->sim3);
-  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data(), c->fuse, c->track, c->sim3);
+  if (P) carve_queries(a, P, jobs, nJobs);
+  for (int j = 0; j < nJobs; j++) stage_scratch(a, jobs, j, K, c->dev.data());
   for (int j = 0; j < nJobs; j++) {
     if (jobs[j].claim) {
       c->claims.push_back(claim_job(jobs[j], c->dev[j], K));
@@ -1038,30 +751,12 @@ hipError_t stage_call(Arena* a, const WindowJob* jobs, int nJobs, int nClaim, in
   return hipSuccess;
 }
 
-// The call on the thread's stream: one copy up, the producers, one grid build per uploaded frame, ONE window-search launch
-// for all jobs, one claim launch, one copy down
-hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCall& c, bool claimInit) {
+// The call on the thread's stream: one copy up, the producer's launch, one grid build per uploaded frame, ONE window-search
+// launch for all jobs, one claim launch, one copy down
+hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, Producer* P, const WindowCall& c, bool claimInit) {
   for (int j = 0; j < nJobs; j++) TRY(frame_use(ar, jobs[j].f->resident));
   TRY(flush(ar));
-  if (c.fuseProducer) {  // ONE launch for the windows of all its jobs
-    launch_project_fuse(ar->stream, fuse_args(*c.fuseProducer, c.fuse));
-    TRY(hipGetLastError());
-  }
-  if (c.trackProducer) {  // likewise
-    launch_project_track(ar->stream, track_args(*c.trackProducer, c.track), c.trackProducer->longest());
-    TRY(hipGetLastError());
-  }
-  if (c.sim3Producer) {  // likewise, behind the scatter of vbAlreadyMatched2 when the graph supplies it
-    sim3_already(ar->stream, *c.sim3Producer, c.sim3);
-    TRY(hipGetLastError());
-    launch_project_sim3(ar->stream, sim3_args(*c.sim3Producer, c.sim3), c.sim3Producer->longest());
-    TRY(hipGetLastError());
-  }
-  for (int j = 0; j < nJobs; j++)
-    if (jobs[j].producer) {
-      launch_project_frustum(ar->stream, project_args(jobs[j], c.dev[j]));
-      TRY(hipGetLastError());
-    }
+  if (P) TRY(P->launch(ar->stream));  // the windows of all its parts
   for (int j = 0; j < nJobs; j++)
     if (c.dev[j].frameOf == j) {
       launch_grid_build(ar->stream, c.searches[j].f, c.dev[j].key, c.dev[j].cell);
@@ -1081,15 +776,12 @@ hipError_t enqueue_call(Arena* ar, const WindowJob* jobs, int nJobs, const Windo
   return down_range(ar, c.outLo, c.outHi);
 }
 
-// Behind the synchronisation: every job's results out of the mirror, by mode.  Returns the longest list of the call; one
-// longer than K was truncated, and a claim job that saw one has no result yet.
+// Behind the synchronisation: the producer's flags and every job's results out of the mirror, by mode.  Returns the longest
+// list of the call; one longer than K was truncated, and a claim job that saw one has no result yet.
 thread_local int t_lastClaimRounds = 0;
-int collect_results(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCall& c, int K) {
+int collect_results(Arena* ar, const WindowJob* jobs, int nJobs, const Producer* P, const WindowCall& c, int K) {
   int mx = 0;
-  if (const FuseProducer* P = c.fuseProducer)
-    if (P->projectedOut) std::memcpy(P->projectedOut, mirror_of(ar, c.fuse.projected), (size_t)P->K * P->n);
-  if (const TrackProducer* P = c.trackProducer)
-    if (P->validOut && P->total()) std::memcpy(P->validOut, mirror_of(ar, c.track.valid), (size_t)P->total());
+  if (P && P->flagsOut && P->total()) std::memcpy(P->flagsOut, mirror_of(ar, P->q.validCopy), P->total());
   for (int j = 0; j < nJobs; j++) {
     const WindowJob& J = jobs[j];
     const JobDev& D = c.dev[j];
@@ -1103,7 +795,6 @@ int collect_results(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCal
       const bool ini = C->mode == CLAIM_INIT;
       const size_t nOut = ini ? q : (size_t)J.f->n;
       if (nOut) std::memcpy(C->match, mirror_of(ar, D.match), nOut * 4);
-      if (D.inView && q) std::memcpy(J.producer->inViewOut, mirror_of(ar, D.inView), q);
       *C->nMatches = hd[1];
       C->rounds = hd[2];
       t_lastClaimRounds = hd[2] + 1 > t_lastClaimRounds ? hd[2] + 1 : t_lastClaimRounds;
@@ -1120,29 +811,25 @@ int collect_results(Arena* ar, const WindowJob* jobs, int nJobs, const WindowCal
   return mx;
 }
 
-// Upload frames (unless resident: keypoint arrays, descriptors and grid are on the device already) + queries, build the
-// grids, search every window; grows K until every list fits.
+}  // namespace
+
+namespace orbfe {
+
 int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
   UnsettledScope unsettledScope;
   t_lastClaimRounds = 0;
   int nClaim = 0;
   bool claimInit = false;
+  Producer* P = nJobs > 0 ? jobs[0].producer : nullptr;
   for (int j = 0; j < nJobs; j++) {
     const WindowJob& J = jobs[j];
     if (J.f->resident && J.f->resident->device != device) return fail(ORBFE_ERR_INVALID, "resident frame lives on another device");
-    if (J.producer && (!J.claim || J.claim->mode != CLAIM_RATIO)) return fail(ORBFE_ERR_INVALID, "a producer needs a CLAIM_RATIO job");
-    // (a fuse producer feeds BEST jobs -- Fuse -- or CLAIM_BEST jobs: the Sim3 SearchByProjection, whose prologue is Fuse's)
-    if (J.fuse && ((!J.bestOut && !(J.claim && J.claim->mode == CLAIM_BEST)) || J.fuse != jobs[0].fuse || J.nq != J.fuse->n ||
-                   J.fuseK < 0 || J.fuseK >= J.fuse->K))
-      return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST or CLAIM_BEST jobs that all name it");
-    if (!J.fuse && jobs[0].fuse) return fail(ORBFE_ERR_INVALID, "a fuse producer needs BEST or CLAIM_BEST jobs that all name it");
-    if (J.sim3 != jobs[0].sim3 || (J.sim3 && (!J.bestOut || J.sim3Leg < 0 || J.sim3Leg >= J.sim3->nLegs ||
-                                              J.nq != J.sim3->span[J.sim3Leg].n)))
-      return fail(ORBFE_ERR_INVALID, "a sim3 producer needs BEST jobs that all name it");
-    if (J.track != jobs[0].track ||
-        (J.track && (!J.claim || J.claim->mode != CLAIM_BEST || J.trackK < 0 || J.trackK >= J.track->K ||
-                     J.nq != J.track->offsets[J.trackK + 1] - J.track->offsets[J.trackK])))
-      return fail(ORBFE_ERR_INVALID, "a track producer needs CLAIM_BEST jobs that all name it");
+    if (J.producer != P) return fail(ORBFE_ERR_INVALID, "the jobs of a call name one producer, or none does");
+    if (P) {
+      if (J.part < 0 || J.part >= P->parts() || J.nq != P->queries(J.part))
+        return fail(ORBFE_ERR_INVALID, "a job behind a producer searches one of its parts, with that part's queries");
+      if (const char* e = P->accepts(J.bestOut != nullptr, J.claim ? J.claim->mode : -1)) return fail(ORBFE_ERR_INVALID, e);
+    }
     if (!J.claim) continue;
     if (J.nq > 0x1fffff) return fail(ORBFE_ERR_INVALID, "more than 2097151 points in one projection search");
     if (nClaim && claimInit != (J.claim->mode == CLAIM_INIT)) return fail(ORBFE_ERR_INVALID, "mixed claim forms in one call");
@@ -1152,25 +839,42 @@ int window_search_multi(int device, WindowJob* jobs, int nJobs, int K0) {
   WindowCall call;
   for (int K = ((K0 < 8 ? 8 : K0) + 7) & ~7;;) {  // (k_window_claim reads the lists eight entries at a time)
     Arena* ar;
-    auto stage = [&](Arena* a) { return stage_call(a, jobs, nJobs, nClaim, K, &call); };
+    auto stage = [&](Arena* a) { return stage_call(a, jobs, nJobs, P, nClaim, K, &call); };
     HIPCHK(arena_stage(device, &ar, stage));
-    HIPCHK(enqueue_call(ar, jobs, nJobs, call, claimInit));
+    HIPCHK(enqueue_call(ar, jobs, nJobs, P, call, claimInit));
     HIPCHK(hipStreamSynchronize(ar->stream));
     frames_settle();
-    const int mx = collect_results(ar, jobs, nJobs, call, K);
+    const int mx = collect_results(ar, jobs, nJobs, P, call, K);
     if (mx <= K) return ORBFE_OK;
     K = (mx + 7) & ~7;  // a window held more features than the list: search again with room for the largest
   }
 }
 
-}  // namespace
+int producer_run(int device, Producer& P, int n4, void* const* out4, uint8_t* flags) {
+  const size_t q = P.total();
+  void* d4[8] = {};
+  uint8_t* dflags = nullptr;
+  Arena* ar;
+  auto stage = [&](Arena* a) -> hipError_t {
+    P.q = QueryOut{};  // no windows: the projection alone
+    TRY(P.upload(a));
+    open_span(a);  // the outputs adjacent: one copy back
+    for (int i = 0; i < n4; i++) d4[i] = carve<float>(a, q);
+    dflags = carve<uint8_t>(a, q);
+    P.project_to(d4, dflags);
+    return close_span(a);
+  };
+  HIPCHK(arena_stage(device, &ar, stage));
+  HIPCHK(flush(ar));
+  HIPCHK(P.launch(ar->stream));
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  for (int i = 0; i < n4; i++)
+    if (out4[i]) std::memcpy(out4[i], mirror_of(ar, static_cast<const uint8_t*>(d4[i])), q * 4);
+  if (flags) std::memcpy(flags, mirror_of(ar, dflags), q);
+  return ORBFE_OK;
+}
 
-extern "C" int orbfe_debug_last_claim_rounds(void) { return t_lastClaimRounds; }
-
-namespace {
-// The claim loops of the two searches that walk a frame's own map points, on the device (k_window_claim); shared by the
-// host-array calls and the calls on the resident map points.
-// SearchByProjection(CurrentFrame, LastFrame, th, bMono): claim loop :1572-1612 + rotation histogram :1614-1628
 ClaimSpec last_frame_claim(const uint8_t* blocked, const uint8_t* obs_positive, const float* last_angle, int check_orientation,
                            int32_t* match_cur, int32_t* n_matches) {
   ClaimSpec C;
@@ -1181,7 +885,6 @@ ClaimSpec last_frame_claim(const uint8_t* blocked, const uint8_t* obs_positive, 
   C.match = match_cur; C.nMatches = n_matches;
   return C;
 }
-// SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist): claim loop :1726-1760
 ClaimSpec keyframe_claim(const uint8_t* blocked, const float* kf_angle, int orb_dist, int check_orientation, int32_t* match_cur,
                          int32_t* n_matches) {
   ClaimSpec C;
@@ -1190,7 +893,26 @@ ClaimSpec keyframe_claim(const uint8_t* blocked, const float* kf_angle, int orb_
   C.match = match_cur; C.nMatches = n_matches;
   return C;
 }
-}  // namespace
+
+int level_queries(const char* who, int n, const uint8_t* valid, const int32_t* level, const float* sf, int n_levels, float th, int lo,
+                  int hi, bool no_filter, std::vector<float>* qr, std::vector<int32_t>* qmin, std::vector<int32_t>* qmax) {
+  qr->resize(n); qmin->resize(n); qmax->resize(n);
+  for (int i = 0; i < n; i++) {
+    int lv = 0;
+    if (valid[i]) {
+      lv = level[i];
+      if (lv < 0 || lv >= n_levels) return fail(ORBFE_ERR_INVALID, std::string(who) + ": level outside the pyramid");
+    }
+    (*qr)[i] = th * sf[lv];
+    (*qmin)[i] = no_filter ? -1 : lv + lo;
+    (*qmax)[i] = no_filter ? -1 : lv + hi;
+  }
+  return ORBFE_OK;
+}
+
+}  // namespace orbfe
+
+extern "C" int orbfe_debug_last_claim_rounds(void) { return t_lastClaimRounds; }
 
 extern "C" int orbfe_features_in_area(int device, const orbfe_frame_view* frame, int n_queries, const float* x,
                                       const float* y, const float* r, const int32_t* min_level,
@@ -1257,40 +979,6 @@ extern "C" int orbfe_search_by_projection(int device, const orbfe_frame_view* F,
   return window_search_multi(device, &job, 1, 32);
 }
 
-extern "C" int orbfe_search_local_points(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
-                                         const orbfe_camera_pose* pose, float viewing_cos_limit, const orbfe_frame_view* F,
-                                         const float* scale_factors, int n_levels, const uint8_t* blocked, float th, float nnratio,
-                                         int32_t* match, int32_t* n_matches, uint8_t* in_view) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "search_local_points: NULL table");
-  if (const char* e = mappoints_check_slots(orbfe_mappoints_capacity(mp), n, slot)) return fail(ORBFE_ERR_INVALID, std::string("search_local_points: ") + e);
-  F = canon(F);
-  if (!frame_ok(F) || !scale_factors || n_levels <= 0 || !pose_ok(pose) || pose->n_levels > n_levels || !n_matches ||
-      (F->n > 0 && (!match || !F->desc)))
-    return fail(ORBFE_ERR_INVALID, "search_local_points: bad argument");
-  for (int i = 0; i < F->n; i++) match[i] = -1;
-  *n_matches = 0;
-  if (n == 0) return ORBFE_OK;
-  if (F->n == 0) {  // nothing to search: the flags alone
-    return in_view ? orbfe_project_in_frustum(mp, n, slot, skip, pose, viewing_cos_limit, in_view, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                              nullptr, nullptr)
-                   : ORBFE_OK;
-  }
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  FrustumProducer P;
-  P.table = *lock.table; P.slot = slot; P.skip = skip; P.pose = *pose; P.limit = viewing_cos_limit; P.th = th;
-  P.scale = scale_factors; P.nLevels = n_levels; P.inViewOut = in_view;
-  ClaimSpec C;
-  C.mode = CLAIM_RATIO; C.maxDist = 100 /* TH_HIGH */; C.nnratio = nnratio;
-  C.blocked = blocked;
-  C.match = match; C.nMatches = n_matches;
-  WindowJob job;
-  job.f = F; job.nq = n;
-  job.claim = &C;
-  job.producer = &P;
-  return window_search_multi(lock.device, &job, 1, 32);
-}
-
 extern "C" int orbfe_search_by_projection_last_frame(int device, const orbfe_frame_view* Cur, const float* scale_factors,
                                                      int n_levels, float mbf, int n_last, const uint8_t* valid,
                                                      const float* u, const float* v, const float* invzc,
@@ -1329,29 +1017,6 @@ extern "C" int orbfe_search_by_projection_last_frame(int device, const orbfe_fra
   job.claim = &C;
   return window_search_multi(device, &job, 1, 32);
 }
-
-namespace {
-
-// radius = th * scale_factors[level] and the level window [level + lo, level + hi] of each query
-// (hi_open: no level filter at all, KeyFrame::GetFeaturesInArea, src/KeyFrame.cc:611-650)
-int level_queries(const char* who, int n, const uint8_t* valid, const int32_t* level, const float* sf, int n_levels,
-                  float th, int lo, int hi, bool no_filter, std::vector<float>* qr, std::vector<int32_t>* qmin,
-                  std::vector<int32_t>* qmax) {
-  qr->resize(n); qmin->resize(n); qmax->resize(n);
-  for (int i = 0; i < n; i++) {
-    int lv = 0;
-    if (valid[i]) {
-      lv = level[i];
-      if (lv < 0 || lv >= n_levels) return fail(ORBFE_ERR_INVALID, std::string(who) + ": level outside the pyramid");
-    }
-    (*qr)[i] = th * sf[lv];
-    (*qmin)[i] = no_filter ? -1 : lv + lo;
-    (*qmax)[i] = no_filter ? -1 : lv + hi;
-  }
-  return ORBFE_OK;
-}
-
-}  // namespace
 
 extern "C" int orbfe_search_by_projection_keyframe(int device, const orbfe_frame_view* Cur, const float* scale_factors,
                                                    int n_levels, const uint8_t* blocked, int n, const uint8_t* valid,
@@ -1424,151 +1089,6 @@ extern "C" int orbfe_search_by_projection_keyframe_multi(int device, const orbfe
   if (wj.empty()) return ORBFE_OK;
   // one claim workgroup per candidate behind the K window searches: one upload, one launch group, one download
   return window_search_multi(device, wj.data(), (int)wj.size(), 32);
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same two searches on the resident map points: k_project_track writes the windows the host-array calls above build from
-// the caller's projection (TrackProducer), and the same window search and claim launches follow.
-// ---------------------------------------------------------------------------------------------
-namespace {
-// k_project_track alone (a point to project, arguments checked, the table held): lists, masks, octaves and poses up, one
-// launch, the requested arrays back in one copy.  aux0 / aux1: form 0 ur / radius (float), form 1 level (int32) / dist
-int project_track_run(int device, const TrackProducer& P, uint8_t* valid, float* u, float* v, float* inv_z, void* aux0, float* aux1) {
-  const size_t q = (size_t)P.total();
-  TrackDev T;
-  TrackArgs ta{};
-  float* daux0 = nullptr;
-  Arena* ar;
-  auto stage = [&](Arena* a) -> hipError_t {
-    T = TrackDev{};
-    TRY(stage_track_inputs(a, P, &T));
-    ta = track_args(P, T);
-    open_span(a);
-    ta.u = carve<float>(a, q); ta.v = carve<float>(a, q); ta.invZ = carve<float>(a, q);
-    daux0 = carve<float>(a, q);
-    float* daux1 = carve<float>(a, q);
-    ta.valid = carve<uint8_t>(a, q);
-    if (P.form == 0) { ta.ur = daux0; ta.radius = daux1; }
-    else { ta.level = reinterpret_cast<int32_t*>(daux0); ta.dist = daux1; }
-    return close_span(a);
-  };
-  HIPCHK(arena_stage(device, &ar, stage));
-  HIPCHK(flush(ar));
-  launch_project_track(ar->stream, ta, P.longest());
-  HIPCHK(hipGetLastError());
-  HIPCHK(down_span(ar));
-  HIPCHK(hipStreamSynchronize(ar->stream));
-  if (u) std::memcpy(u, mirror_of(ar, ta.u), q * 4);
-  if (v) std::memcpy(v, mirror_of(ar, ta.v), q * 4);
-  if (inv_z) std::memcpy(inv_z, mirror_of(ar, ta.invZ), q * 4);
-  if (aux0) std::memcpy(aux0, mirror_of(ar, daux0), q * 4);
-  if (aux1) std::memcpy(aux1, mirror_of(ar, P.form == 0 ? ta.radius : ta.dist), q * 4);
-  if (valid) std::memcpy(valid, mirror_of(ar, ta.valid), q);
-  return ORBFE_OK;
-}
-}  // namespace
-
-extern "C" int orbfe_project_last_frame(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
-                                        const int32_t* last_octave, const orbfe_camera_pose* pose, const float* scale_factors,
-                                        int n_levels, float th, int mode, uint8_t* valid, float* u, float* v, float* inv_z, float* ur,
-                                        float* radius) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "project_last_frame: NULL table");
-  if (!scale_factors || n_levels <= 0 || mode < 0 || mode > 2) return fail(ORBFE_ERR_INVALID, "project_last_frame: bad argument");
-  const int32_t offsets[2] = {0, n};
-  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), 1, offsets, slot, true, last_octave, pose, n_levels))
-    return fail(ORBFE_ERR_INVALID, std::string("project_last_frame: ") + e);
-  if (n == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  TrackProducer P;
-  P.table = *lock.table; P.form = 0; P.K = 1; P.mode = mode; P.offsets = offsets; P.slot = slot; P.skip = skip;
-  P.lastOctave = last_octave; P.pose = pose; P.th = &th; P.scale = scale_factors; P.nLevels = n_levels;
-  return project_track_run(lock.device, P, valid, u, v, inv_z, ur, radius);
-}
-
-extern "C" int orbfe_search_last_frame_mappoints(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
-                                                 const int32_t* last_octave, const float* last_angle, const orbfe_camera_pose* pose,
-                                                 const orbfe_frame_view* Cur, const float* scale_factors, int n_levels,
-                                                 const uint8_t* blocked, int mode, float th, int check_orientation,
-                                                 int32_t* match_cur, int32_t* n_matches, uint8_t* valid_out) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "search_last_frame_mappoints: NULL table");
-  const int32_t offsets[2] = {0, n};
-  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), 1, offsets, slot, true, last_octave, pose, n_levels))
-    return fail(ORBFE_ERR_INVALID, std::string("search_last_frame_mappoints: ") + e);
-  Cur = canon(Cur);
-  if (!frame_ok(Cur) || !scale_factors || n_levels <= 0 || !n_matches || mode < 0 || mode > 2 ||
-      (Cur->n > 0 && (!match_cur || !Cur->desc)) || (check_orientation && Cur->n > 0 && !Cur->angle) ||
-      (check_orientation && n > 0 && !last_angle))
-    return fail(ORBFE_ERR_INVALID, "search_last_frame_mappoints: bad argument");
-  for (int i = 0; i < Cur->n; i++) match_cur[i] = -1;
-  *n_matches = 0;
-  if (n == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  TrackProducer P;
-  P.table = *lock.table; P.form = 0; P.K = 1; P.mode = mode; P.offsets = offsets; P.slot = slot; P.skip = skip;
-  P.lastOctave = last_octave; P.pose = pose; P.th = &th; P.scale = scale_factors; P.nLevels = n_levels; P.validOut = valid_out;
-  if (Cur->n == 0)  // nothing to search: the flags alone
-    return valid_out ? project_track_run(lock.device, P, valid_out, nullptr, nullptr, nullptr, nullptr, nullptr) : ORBFE_OK;
-  ClaimSpec C = last_frame_claim(blocked, nullptr, last_angle, check_orientation, match_cur, n_matches);
-  WindowJob job;
-  job.f = Cur; job.nq = n;
-  job.claim = &C;
-  job.track = &P; job.trackK = 0;
-  return window_search_multi(lock.device, &job, 1, 32);
-}
-
-extern "C" int orbfe_project_keyframe(orbfe_mappoints* mp, int n_candidates, const int32_t* offsets, const int32_t* slot,
-                                      const uint8_t* skip, const orbfe_camera_pose* pose, uint8_t* valid, float* u, float* v,
-                                      float* inv_z, int32_t* level, float* dist) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "project_keyframe: NULL table");
-  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), n_candidates, offsets, slot, false, nullptr, pose, 0))
-    return fail(ORBFE_ERR_INVALID, std::string("project_keyframe: ") + e);
-  if (n_candidates == 0 || offsets[n_candidates] == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  TrackProducer P;
-  P.table = *lock.table; P.form = 1; P.K = n_candidates; P.offsets = offsets; P.slot = slot; P.skip = skip; P.pose = pose;
-  return project_track_run(lock.device, P, valid, u, v, inv_z, level, dist);
-}
-
-extern "C" int orbfe_search_keyframe_mappoints_multi(orbfe_mappoints* mp, const orbfe_frame_view* Cur, const float* scale_factors,
-                                                     int n_levels, int n_candidates, const int32_t* offsets, const int32_t* slot,
-                                                     const uint8_t* skip, const float* kf_angle, const orbfe_camera_pose* pose,
-                                                     const uint8_t* const* blocked, const float* th, const int32_t* orb_dist,
-                                                     int check_orientation, int32_t* match_cur, int32_t* n_matches) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "search_keyframe_mappoints_multi: NULL table");
-  const int K = n_candidates;
-  if (const char* e = track_check_operands(orbfe_mappoints_capacity(mp), K, offsets, slot, false, nullptr, pose, n_levels))
-    return fail(ORBFE_ERR_INVALID, std::string("search_keyframe_mappoints_multi: ") + e);
-  Cur = canon(Cur);
-  if (!frame_ok(Cur) || !scale_factors || n_levels <= 0 || (K > 0 && (!th || !orb_dist || !n_matches)) ||
-      (Cur->n > 0 && K > 0 && (!match_cur || !Cur->desc)) || (check_orientation && Cur->n > 0 && !Cur->angle) ||
-      (check_orientation && K > 0 && offsets[K] > 0 && !kf_angle))
-    return fail(ORBFE_ERR_INVALID, "search_keyframe_mappoints_multi: bad argument");
-  if (K == 0) return ORBFE_OK;
-  for (size_t i = 0; i < (size_t)K * Cur->n; i++) match_cur[i] = -1;
-  for (int k = 0; k < K; k++) n_matches[k] = 0;
-  if (offsets[K] == 0 || Cur->n == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  TrackProducer P;
-  P.table = *lock.table; P.form = 1; P.K = K; P.offsets = offsets; P.slot = slot; P.skip = skip; P.pose = pose; P.th = th;
-  P.scale = scale_factors; P.nLevels = n_levels;
-  std::vector<ClaimSpec> claims((size_t)K);
-  std::vector<WindowJob> wj;
-  for (int k = 0; k < K; k++) {
-    if (offsets[k + 1] == offsets[k]) continue;  // an empty candidate: its matches stay -1
-    claims[k] = keyframe_claim(blocked ? blocked[k] : nullptr, check_orientation ? kf_angle + offsets[k] : nullptr, orb_dist[k],
-                               check_orientation, match_cur + (size_t)k * Cur->n, &n_matches[k]);
-    WindowJob job;
-    job.f = Cur; job.nq = offsets[k + 1] - offsets[k];
-    job.claim = &claims[k];
-    job.track = &P; job.trackK = k;
-    wj.push_back(job);
-  }
-  // one claim workgroup per candidate behind the K window searches: one upload, one launch group, one download
-  return window_search_multi(lock.device, wj.data(), (int)wj.size(), 32);
 }
 
 extern "C" int orbfe_search_by_projection_sim3(int device, const orbfe_frame_view* KF, const float* scale_factors,
@@ -1715,105 +1235,6 @@ extern "C" int orbfe_fuse_search(int device, const orbfe_frame_view* KF, const f
   return window_best_multi("fuse_search", device, &job, 1, n_levels, th, chi2_gate != 0, 50 /* TH_LOW */);
 }
 
-namespace {
-// k_project_fuse alone (n > 0, K > 0, arguments checked, both handles held): slot list, mask, poses and kf slots up, one launch,
-// the six arrays back in one copy
-int project_fuse_run(int device, const MapPointsDevice& table, const ObsGraphDevice* graph, int n, const int32_t* slot, int K,
-                     const int32_t* kf_slot, const orbfe_camera_pose* pose, const uint8_t* skip, uint8_t* valid, float* u, float* v,
-                     float* ur, int32_t* level, float* dist) {
-  const size_t q = (size_t)K * n;
-  FuseProducer P;
-  P.table = table; P.graph = graph; P.slot = slot; P.skip = skip; P.pose = pose; P.kfSlot = kf_slot; P.n = n; P.K = K;
-  FuseDev F;
-  FuseArgs fa{};
-  Arena* ar;
-  auto stage = [&](Arena* a) -> hipError_t {
-    F = FuseDev{};
-    TRY(stage_fuse_inputs(a, P, &F));
-    fa = fuse_args(P, F);
-    // the outputs adjacent: one copy back
-    fa.level = carve<int32_t>(a, q); fa.u = carve<float>(a, q); fa.v = carve<float>(a, q); fa.ur = carve<float>(a, q);
-    fa.dist = carve<float>(a, q); fa.valid = carve<uint8_t>(a, q);
-    return hipSuccess;
-  };
-  HIPCHK(arena_stage(device, &ar, stage));
-  HIPCHK(flush(ar));
-  launch_project_fuse(ar->stream, fa);
-  HIPCHK(hipGetLastError());
-  HIPCHK(down_range(ar, fa.level, fa.valid + q));
-  HIPCHK(hipStreamSynchronize(ar->stream));
-  if (level) std::memcpy(level, mirror_of(ar, fa.level), q * 4);
-  if (u) std::memcpy(u, mirror_of(ar, fa.u), q * 4);
-  if (v) std::memcpy(v, mirror_of(ar, fa.v), q * 4);
-  if (ur) std::memcpy(ur, mirror_of(ar, fa.ur), q * 4);
-  if (dist) std::memcpy(dist, mirror_of(ar, fa.dist), q * 4);
-  if (valid) std::memcpy(valid, mirror_of(ar, fa.valid), q);
-  return ORBFE_OK;
-}
-}  // namespace
-
-extern "C" int orbfe_project_fuse(orbfe_mappoints* mp, orbfe_obsgraph* g, int n, const int32_t* slot, int n_keyframes,
-                                  const int32_t* kf_slot, const orbfe_camera_pose* pose, const uint8_t* skip, uint8_t* valid, float* u,
-                                  float* v, float* ur, int32_t* level, float* dist) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "project_fuse: NULL table");
-  ObsGraphLock glock(g);  // the graph's serialisation first, then the table's: the order of orbfe_obsgraph_*_mappoints
-  if (g && mappoints_device(mp) != glock.device) return fail(ORBFE_ERR_INVALID, "project_fuse: the graph and the map-point table are on different devices");
-  if (const char* e = fuse_check_operands(orbfe_mappoints_capacity(mp), n, slot, n_keyframes, kf_slot, g != nullptr, glock.kfCap, pose, 0))
-    return fail(ORBFE_ERR_INVALID, std::string("project_fuse: ") + e);
-  if (n == 0 || n_keyframes == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  if (int rc = glock.table_ready()) return rc;
-  return project_fuse_run(lock.device, *lock.table, glock.graph, n, slot, n_keyframes, kf_slot, pose, skip, valid, u, v, ur, level, dist);
-}
-
-extern "C" int orbfe_fuse_mappoints(orbfe_mappoints* mp, orbfe_obsgraph* g, int n, const int32_t* slot, int n_keyframes,
-                                    const orbfe_frame_view* const* KF, const int32_t* kf_slot, const orbfe_camera_pose* pose,
-                                    const uint8_t* skip, const float* scale_factors, const float* inv_level_sigma2, int n_levels,
-                                    float th, int chi2_gate, int32_t* best_idx, uint8_t* projected) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "fuse_mappoints: NULL table");
-  if (!scale_factors || n_levels <= 0 || (chi2_gate && !inv_level_sigma2) || (n_keyframes > 0 && !KF) ||
-      (n_keyframes > 0 && n > 0 && !best_idx))
-    return fail(ORBFE_ERR_INVALID, "fuse_mappoints: bad argument");
-  ObsGraphLock glock(g);  // the graph's serialisation first, then the table's: the order of orbfe_obsgraph_*_mappoints
-  if (g && mappoints_device(mp) != glock.device) return fail(ORBFE_ERR_INVALID, "fuse_mappoints: the graph and the map-point table are on different devices");
-  if (const char* e = fuse_check_operands(orbfe_mappoints_capacity(mp), n, slot, n_keyframes, kf_slot, g != nullptr, glock.kfCap, pose, n_levels))
-    return fail(ORBFE_ERR_INVALID, std::string("fuse_mappoints: ") + e);
-  std::vector<const orbfe_frame_view*> views;
-  for (int k = 0; k < n_keyframes; k++) {  // (orbfe_fuse_search_multi's checks of its key frames)
-    const orbfe_frame_view* f = canon(KF[k]);
-    if (!frame_ok(f) || (f->n > 0 && !f->desc)) return fail(ORBFE_ERR_INVALID, "fuse_mappoints: bad key frame view");
-    for (int i = 0; i < f->n; i++)
-      if (chi2_gate && (f->octave[i] < 0 || f->octave[i] >= n_levels))
-        return fail(ORBFE_ERR_INVALID, "fuse_mappoints: keypoint octave outside the pyramid");
-    views.push_back(f);
-  }
-  if (n == 0 || n_keyframes == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  if (int rc = glock.table_ready()) return rc;
-  for (size_t i = 0; i < (size_t)n_keyframes * n; i++) best_idx[i] = -1;
-  FuseProducer P;
-  P.table = *lock.table; P.graph = glock.graph; P.slot = slot; P.skip = skip; P.pose = pose; P.kfSlot = kf_slot; P.n = n; P.K = n_keyframes;
-  P.scale = scale_factors; P.invSigma2 = inv_level_sigma2; P.nLevels = n_levels; P.th = th; P.gate = chi2_gate != 0;
-  P.projectedOut = projected;
-  std::vector<WindowJob> wj;
-  for (int k = 0; k < n_keyframes; k++) {
-    if (views[(size_t)k]->n == 0) continue;  // nothing to search: every best_idx of the key frame stays -1
-    WindowJob w;
-    w.f = views[(size_t)k]; w.nq = n;
-    w.bestOut = best_idx + (size_t)k * n;
-    w.gate = P.gate ? 1 : 0; w.nLevels = n_levels; w.maxDist = 50 /* TH_LOW */;
-    w.fuse = &P; w.fuseK = k;
-    wj.push_back(w);
-  }
-  if (wj.empty())  // K empty key frames: the prologue alone, if the caller asked for it
-    return projected ? project_fuse_run(lock.device, *lock.table, glock.graph, n, slot, n_keyframes, kf_slot, pose, skip, projected, nullptr,
-                                        nullptr, nullptr, nullptr, nullptr)
-                     : ORBFE_OK;
-  return window_search_multi(lock.device, wj.data(), (int)wj.size(), 8);
-}
-
 extern "C" int orbfe_search_by_sim3(int device, const orbfe_frame_view* KF1, const orbfe_frame_view* KF2,
                                     const float* scale_factors1, const float* scale_factors2, int n_levels,
                                     const uint8_t* valid1, const float* u1, const float* v1, const int32_t* level1,
@@ -1840,178 +1261,4 @@ extern "C" int orbfe_search_by_sim3(int device, const orbfe_frame_view* KF1, con
   }
   *n_found = nFound;
   return ORBFE_OK;
-}
-
-namespace {
-// k_project_sim3 alone (a point to project, arguments checked, the table held): spans, legs, slots and the mask up, one
-// launch, the five arrays back in one copy
-int project_sim3_run(int device, const Sim3Producer& P, uint8_t* valid, float* u, float* v, int32_t* level, float* dist) {
-  const size_t q = P.nOut;
-  Sim3Dev S;
-  Sim3Args sa{};
-  Arena* ar;
-  auto stage = [&](Arena* a) -> hipError_t {
-    S = Sim3Dev{};
-    TRY(stage_sim3_inputs(a, P, &S));
-    sa = sim3_args(P, S);
-    open_span(a);
-    sa.level = carve<int32_t>(a, q); sa.u = carve<float>(a, q); sa.v = carve<float>(a, q); sa.dist = carve<float>(a, q);
-    sa.valid = carve<uint8_t>(a, q);
-    return close_span(a);
-  };
-  HIPCHK(arena_stage(device, &ar, stage));
-  HIPCHK(flush(ar));
-  launch_project_sim3(ar->stream, sa, P.longest());
-  HIPCHK(hipGetLastError());
-  HIPCHK(down_span(ar));
-  HIPCHK(hipStreamSynchronize(ar->stream));
-  if (level) std::memcpy(level, mirror_of(ar, sa.level), q * 4);
-  if (u) std::memcpy(u, mirror_of(ar, sa.u), q * 4);
-  if (v) std::memcpy(v, mirror_of(ar, sa.v), q * 4);
-  if (dist) std::memcpy(dist, mirror_of(ar, sa.dist), q * 4);
-  if (valid) std::memcpy(valid, mirror_of(ar, sa.valid), q);
-  return ORBFE_OK;
-}
-}  // namespace
-
-extern "C" int orbfe_project_sim3(orbfe_mappoints* mp, int n_legs, const int32_t* offsets, const int32_t* slot, const uint8_t* skip,
-                                  const orbfe_sim3_leg* legs, uint8_t* valid, float* u, float* v, int32_t* level, float* dist) {
-  if (!mp) return fail(ORBFE_ERR_INVALID, "project_sim3: NULL table");
-  if (const char* e = sim3_check_legs(orbfe_mappoints_capacity(mp), n_legs, offsets, slot, legs, 0))
-    return fail(ORBFE_ERR_INVALID, std::string("project_sim3: ") + e);
-  if (n_legs == 0 || offsets[n_legs] == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  std::vector<Sim3Span> span((size_t)n_legs);
-  for (int l = 0; l < n_legs; l++) span[(size_t)l] = Sim3Span{offsets[l], offsets[l + 1] - offsets[l], offsets[l], 0};
-  Sim3Producer P;
-  P.table = *lock.table; P.nLegs = n_legs; P.span = span.data(); P.leg = legs; P.slot = slot; P.nSlot = (size_t)offsets[n_legs];
-  P.skip = skip; P.nOut = P.nSlot;
-  return project_sim3_run(lock.device, P, valid, u, v, level, dist);
-}
-
-// SearchBySim3 for K candidates of one key frame: legs 2k (KF1 -> KF2_k) and 2k + 1 (KF2_k -> KF1) of ONE prologue launch, 2K
-// BEST window jobs of one search launch, the agreement check (:1461-1474) over the one download
-extern "C" int orbfe_search_by_sim3_mappoints_multi(orbfe_mappoints* mp, orbfe_obsgraph* g, const orbfe_frame_view* KF1,
-                                                    const int32_t* slot1, int n_candidates, const orbfe_frame_view* const* KF2,
-                                                    const int32_t* offsets2, const int32_t* slot2, const orbfe_sim3_leg* legs12,
-                                                    const orbfe_sim3_leg* legs21, const int32_t* matched12_in, const int32_t* kf2_slot,
-                                                    const uint8_t* already2, const float* scale_factors1, const float* scale_factors2,
-                                                    int n_levels, float th, int32_t* match12, int32_t* n_found) {
-  const char* who = "search_by_sim3_mappoints_multi: ";
-  if (!mp) return fail(ORBFE_ERR_INVALID, std::string(who) + "NULL table");
-  const int K = n_candidates;
-  KF1 = canon(KF1);
-  if (!frame_ok(KF1) || (KF1->n > 0 && !KF1->desc)) return fail(ORBFE_ERR_INVALID, std::string(who) + "bad key frame view");
-  const int N1 = KF1->n;
-  const bool withGraph = g != nullptr && kf2_slot != nullptr;
-  ObsGraphLock glock(withGraph ? g : nullptr);  // the graph's serialisation first, then the table's
-  if (withGraph && mappoints_device(mp) != glock.device)
-    return fail(ORBFE_ERR_INVALID, std::string(who) + "the graph and the map-point table are on different devices");
-  if (const char* e = sim3_check_search(orbfe_mappoints_capacity(mp), N1, slot1, K, offsets2, slot2, legs12, legs21, matched12_in, kf2_slot,
-                                        withGraph, glock.kfCap, n_levels))
-    return fail(ORBFE_ERR_INVALID, std::string(who) + e);
-  if (K == 0) return ORBFE_OK;
-  if (!KF2 || !scale_factors1 || !scale_factors2 || !n_found || (N1 > 0 && !match12))
-    return fail(ORBFE_ERR_INVALID, std::string(who) + "NULL argument");
-  std::vector<const orbfe_frame_view*> views((size_t)K);
-  for (int k = 0; k < K; k++) {
-    const orbfe_frame_view* f = canon(KF2[k]);
-    if (!frame_ok(f) || (f->n > 0 && !f->desc)) return fail(ORBFE_ERR_INVALID, std::string(who) + "bad key frame view");
-    if (f->n != offsets2[k + 1] - offsets2[k]) return fail(ORBFE_ERR_INVALID, std::string(who) + "slot2 does not hold KF2->n entries per candidate");
-    views[(size_t)k] = f;
-  }
-  for (size_t i = 0; i < (size_t)K * N1; i++) match12[i] = -1;
-  for (int k = 0; k < K; k++) n_found[k] = 0;
-  const size_t total2 = (size_t)offsets2[K], out2 = (size_t)K * N1;
-  if (N1 == 0 || total2 == 0) return ORBFE_OK;  // (a direction without a point finds nothing, so no pair can agree)
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  if (int rc = glock.table_ready()) return rc;
-  // what travels: KF1's list once, then the candidates'; the masks by output position (K x N1, then the candidates')
-  std::vector<int32_t> slot((size_t)N1 + total2);
-  std::memcpy(slot.data(), slot1, (size_t)N1 * 4);
-  std::memcpy(slot.data() + N1, slot2, total2 * 4);
-  std::vector<uint8_t> skip(out2 + total2, 0);
-  if (matched12_in)
-    for (size_t i = 0; i < out2; i++) skip[i] = matched12_in[i] >= 0;
-  if (already2)
-    for (size_t i = 0; i < total2; i++) skip[out2 + i] = already2[i] != 0;
-  std::vector<Sim3Span> span((size_t)2 * K);
-  std::vector<orbfe_sim3_leg> leg((size_t)2 * K);
-  for (int k = 0; k < K; k++) {
-    span[2 * (size_t)k] = Sim3Span{0, N1, (int32_t)((size_t)k * N1), (k == 0 ? 1 : 0) | 2};  // KF2_k's level table is the second
-    span[2 * (size_t)k + 1] = Sim3Span{N1 + offsets2[k], offsets2[k + 1] - offsets2[k], (int32_t)(out2 + (size_t)offsets2[k]), 1};
-    leg[2 * (size_t)k] = legs12[k];
-    leg[2 * (size_t)k + 1] = legs21[k];
-  }
-  std::vector<float> scale((size_t)2 * n_levels);
-  std::memcpy(scale.data(), scale_factors1, (size_t)n_levels * 4);
-  std::memcpy(scale.data() + n_levels, scale_factors2, (size_t)n_levels * 4);
-  Sim3Producer P;
-  P.table = *lock.table; P.nLegs = 2 * K; P.span = span.data(); P.leg = leg.data(); P.slot = slot.data(); P.nSlot = slot.size();
-  P.skip = skip.data(); P.nOut = skip.size(); P.scale = scale.data(); P.nScale = 2 * n_levels; P.nLevels = n_levels; P.th = th;
-  if (withGraph && matched12_in) {
-    P.graph = glock.graph; P.matched = matched12_in; P.kfSlot = kf2_slot; P.offsets2 = offsets2; P.K = K; P.n1 = N1; P.already2Off = out2;
-  }
-  std::vector<int32_t> m2(total2, -1);  // vnMatch2 of every candidate; match12 holds vnMatch1 until the agreement check
-  std::vector<WindowJob> wj;
-  for (int k = 0; k < K; k++) {
-    const int n2 = views[(size_t)k]->n;
-    if (n2 == 0) continue;  // nothing to search in either direction
-    WindowJob a, b;
-    a.f = views[(size_t)k]; a.nq = N1; a.bestOut = match12 + (size_t)k * N1; a.maxDist = 100 /* TH_HIGH */; a.nLevels = n_levels;
-    a.sim3 = &P; a.sim3Leg = 2 * k;
-    b.f = KF1; b.nq = n2; b.bestOut = m2.data() + offsets2[k]; b.maxDist = 100; b.nLevels = n_levels;
-    b.sim3 = &P; b.sim3Leg = 2 * k + 1;
-    wj.push_back(a);
-    wj.push_back(b);
-  }
-  if (int rc = window_search_multi(lock.device, wj.data(), (int)wj.size(), 8)) return rc;
-  for (int k = 0; k < K; k++) {
-    int32_t* m1 = match12 + (size_t)k * N1;
-    const int32_t* mk = m2.data() + offsets2[k];
-    int nFound = 0;
-    for (int i1 = 0; i1 < N1; i1++) {
-      const int idx2 = m1[i1];
-      if (idx2 >= 0 && mk[idx2] == i1) nFound++; else m1[i1] = -1;
-    }
-    n_found[k] = nFound;
-  }
-  return ORBFE_OK;
-}
-
-// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th): k_project_fuse at K = 1 without a graph in front of the claim loop
-extern "C" int orbfe_search_by_projection_sim3_mappoints(orbfe_mappoints* mp, int n, const int32_t* slot, const uint8_t* skip,
-                                                         const orbfe_camera_pose* pose, const orbfe_frame_view* KF,
-                                                         const float* scale_factors, int n_levels, const uint8_t* matched, float th,
-                                                         int32_t* match, int32_t* n_matches, uint8_t* projected) {
-  const char* who = "search_by_projection_sim3_mappoints: ";
-  if (!mp) return fail(ORBFE_ERR_INVALID, std::string(who) + "NULL table");
-  KF = canon(KF);
-  if (!frame_ok(KF) || !scale_factors || n_levels <= 0 || !n_matches || (KF->n > 0 && (!match || !KF->desc)))
-    return fail(ORBFE_ERR_INVALID, std::string(who) + "bad argument");
-  if (const char* e = fuse_check_operands(orbfe_mappoints_capacity(mp), n, slot, 1, nullptr, false, 0, pose, n_levels))
-    return fail(ORBFE_ERR_INVALID, std::string(who) + e);
-  for (int i = 0; i < KF->n; i++) match[i] = -1;
-  *n_matches = 0;
-  if (n == 0) return ORBFE_OK;
-  MapPointsLock lock(mp);
-  if (lock.rc) return lock.rc;
-  if (KF->n == 0)  // nothing to search: the flags alone
-    return projected ? project_fuse_run(lock.device, *lock.table, nullptr, n, slot, 1, nullptr, pose, skip, projected, nullptr, nullptr,
-                                        nullptr, nullptr, nullptr)
-                     : ORBFE_OK;
-  FuseProducer P;
-  P.table = *lock.table; P.slot = slot; P.skip = skip; P.pose = pose; P.n = n; P.K = 1;
-  P.scale = scale_factors; P.nLevels = n_levels; P.th = th; P.projectedOut = projected;
-  ClaimSpec C;  // claim loop :418-446 on the device
-  C.mode = CLAIM_BEST; C.maxDist = 50 /* TH_LOW */;
-  C.blocked = matched;
-  C.match = match; C.nMatches = n_matches;
-  WindowJob job;
-  job.f = KF; job.nq = n;
-  job.claim = &C;
-  job.fuse = &P; job.fuseK = 0;
-  return window_search_multi(lock.device, &job, 1, 32);
 }

@@ -70,7 +70,7 @@ def test_the_table_handle_is_private_to_mappoints_hip():
 
 def test_the_guard_notices_a_hand_summed_begin(tmp_path):
     """A scratch copy of csrc/ whose matcher.hip begins the arena by a size of its own again, one that writes the pinned
-    mirror by hand, and one that looks into the table handle."""
+    mirror by hand, and one whose mappoints_search.hip looks into the table handle."""
     for p in CSRC.iterdir():
         if p.suffix in (".hip", ".h", ".cpp", ".inc"):
             (tmp_path / p.name).write_text(p.read_text())
@@ -82,5 +82,8 @@ def test_the_guard_notices_a_hand_summed_begin(tmp_path):
     assert named_outside(ARENA_ONLY, ARENA, tmp_path) == [("matcher.hip", "arena_begin")]
     m.write_text(text.replace("  HIPCHK(flush(ar));\n", "  std::memset(ar->hmirror, 0, 256);\n  HIPCHK(flush(ar));\n", 1))
     assert named_outside(ARENA_ONLY, ARENA, tmp_path) == [("matcher.hip", "hmirror")]
-    m.write_text(text.replace("  MapPointsLock lock(mp);\n", "  std::lock_guard<std::mutex> lk(mp->m);\n", 1))
-    assert named_outside(TABLE_ONLY, {"mappoints.hip"}, tmp_path) == [("matcher.hip", "mp->m")]
+    m.write_text(text)
+    s = tmp_path / "mappoints_search.hip"  # (where the searches on the table are)
+    assert s.read_text().count("  MapPointsLock lock(mp);\n") >= 1
+    s.write_text(s.read_text().replace("  MapPointsLock lock(mp);\n", "  std::lock_guard<std::mutex> lk(mp->m);\n", 1))
+    assert named_outside(TABLE_ONLY, {"mappoints.hip"}, tmp_path) == [("mappoints_search.hip", "mp->m")]

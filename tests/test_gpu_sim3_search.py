@@ -400,6 +400,37 @@ def test_projection_sim3_equals_the_two_step_form(n, resident):
         assert nw > 10
 
 
+def test_projection_sim3_grows_its_lists():
+    """40 keypoints inside the window of one map point, more than the 32 entries the search's lists start with: the one call
+    (k_project_fuse at K = 1 writes the queries on the device) searches a second time with longer lists, behind a producer
+    whose staging starts anew, and still equals the two-step form.  The scene is the smallest of this file that holds a
+    searched point (the size-1 scene's only point is rejected)."""
+    import oracle_lib as O
+    n, n_crowd, th = 255, 40, 10
+    sc, slot, mp, pose, f = _projection_scene(20 + n, n)
+    s32 = fr.spec32(sc, poses=fr.sim3_poses(sc, 1.07), skip=np.zeros(n, np.uint8), in_kf=np.zeros(n, bool))
+    valid, u, v, level = s32["valid"][0], s32["u"][0], s32["v"][0], s32["level"][0]
+    p = int(np.flatnonzero((valid != 0) & (u > 40) & (u < 1200) & (v > 40) & (v < 330) & (level >= 1))[0])
+    lv = int(level[p])
+    rng = np.random.default_rng(43)
+    f = {k: a.copy() for k, a in f.items()}
+    kp = rng.choice(len(f["x"]), n_crowd, replace=False)
+    f["x"][kp] = (u[p] + rng.uniform(-3, 3, n_crowd)).astype(np.float32)
+    f["y"][kp] = (v[p] + rng.uniform(-3, 3, n_crowd)).astype(np.float32)
+    f["octave"][kp] = lv - rng.integers(0, 2, n_crowd)
+    f["desc"][kp] = sc["desc"][p] ^ (rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8) & rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8) &
+                                    rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8))
+    # the oracle's own window of that point (radius th * scale[level], octaves [level - 1, level]) holds the crowd
+    Fo = O.Frame(f["x"], f["y"], f["octave"], f["desc"], fr.BOUNDS)
+    assert Fo.features_in_area(u[p], v[p], th * sr.SF[lv], lv - 1, lv).size >= n_crowd > 32
+    for resident in (True, False):
+        KF = _view(f, resident)
+        (nw, mw), proj_w = _two_step_projection(mp, slot, pose, KF, th, None, None)
+        ng, mg, proj = mp.SearchByProjectionSim3(KF, slot, pose, sr.SF, th, return_projected=True)
+        assert ng == nw and np.array_equal(mg, mw) and np.array_equal(proj, proj_w) and np.array_equal(proj, valid)
+        assert ng == (mg >= 0).sum() and ng > 10 and (mg == p).sum() == 1
+
+
 def test_projection_sim3_chain_of_points_that_claim_one_keypoint():
     sc, slot, mp, pose, f = _projection_scene(31, 300)
     KF = _view(f)

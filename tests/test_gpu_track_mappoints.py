@@ -149,6 +149,42 @@ def test_last_frame_search_equals_the_two_step_form(mode, stereo, with_blocked, 
     assert nm3 > nm
 
 
+def test_last_frame_search_grows_its_lists():
+    """40 keypoints inside the window of one map point, more than the 32 entries the search's lists start with: the one call
+    (k_project_track writes the queries on the device) searches a second time with longer lists, behind a producer whose
+    staging starts anew, and still equals the two-step form.  The scene is the smallest of this file that holds a searched
+    point (the size-1 scene's only point projects outside the image)."""
+    import oracle_lib as O
+    seed, n, K = LAST_SCENES[2]
+    sc = tr.scene(seed, n, K)
+    s32 = tr.spec32(sc, "last", th=7.0)
+    p = int(np.flatnonzero((s32["valid"] != 0) & (s32["u"] > 40) & (s32["u"] < 1200) & (s32["v"] > 40) & (s32["v"] < 330) &
+                           (sc["last_octave"] >= 1))[0])
+    lv, n_crowd = int(sc["last_octave"][p]), 40
+    rng = np.random.default_rng(41)
+    f = {k: (v.copy() if v is not None else None) for k, v in sc["cur"].items()}
+    kp = rng.choice(tr.CUR_POINTS, n_crowd, replace=False)
+    f["x"][kp] = (s32["u"][p] + rng.uniform(-3, 3, n_crowd)).astype(np.float32)
+    f["y"][kp] = (s32["v"][p] + rng.uniform(-3, 3, n_crowd)).astype(np.float32)
+    f["octave"][kp] = lv - rng.integers(0, 2, n_crowd)
+    f["desc"][kp] = sc["desc"][p] ^ (rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8) & rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8) &
+                                    rng.integers(0, 256, (n_crowd, 32), dtype=np.uint8))
+    # the oracle's own window of that point (mode 0: octaves [lv - 1, lv + 1], src/ORBmatcher.cc:1541-1550) holds the crowd
+    Fo = O.Frame(f["x"], f["y"], f["octave"], f["desc"], tr.BOUNDS, angle=f["angle"])
+    assert Fo.features_in_area(s32["u"][p], s32["v"][p], s32["radius"][p], lv - 1, lv + 1).size >= n_crowd > 32
+    slot = _slots(n, seed)
+    mp = _table(sc, slot)
+    pose = _poses(sc)[0]
+    for resident in (True, False):
+        Cur = _view(f, resident)
+        nm, match, valid = mp.SearchByProjectionLastFrame(Cur, slot, sc["last_octave"], sc["angle"], pose, tr.SF, 7.0, mode=0,
+                                                          skip=sc["skip"], return_valid=True)
+        nm2, match2 = _two_step_last(mp, sc, slot, Cur, pose, 7.0, 0, None)
+        assert nm == nm2 and np.array_equal(match, match2)
+        assert np.array_equal(valid, s32["valid"])
+        assert nm == (match >= 0).sum() and nm > 20
+
+
 @pytest.mark.parametrize("n", [0, 1, 255, 256, 257])
 def test_last_frame_search_at_the_workgroup_boundary(n):
     seed = [s for s, m, _ in LAST_SCENES if m == n][0]
