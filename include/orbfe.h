@@ -1804,6 +1804,95 @@ int orbfe_search_by_projection_sim3_mappoints(orbfe_mappoints *mp, int n, const 
                                               const float *scale_factors, int n_levels, const uint8_t *matched, float th,
                                               int32_t *match, int32_t *n_matches, uint8_t *projected /* [n] or NULL */);
 
+/* ---- Loop correction: the head of LoopClosing::CorrectLoop (src/LoopClosing.cc:514-604) and the map update at the tail
+ * of LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:787-852).  Sim3 records are the project's
+ * qx qy qz qw tx ty tz s, binary64.  Poses are row-major 4 x 4 floats.
+ *
+ * The float cv::Mat products are restated as cv::gemm evaluates CV_32F operands (modules/core/src/matmul.cpp:
+ * GEMMSingleMul<float, double>, the accumulator is double), `R * P + t` folded by cv::MatExpr into one gemm with
+ * beta = 1 (modules/core/src/matop.cpp: MatOp_GEMM::add):
+ *   D_ij = (float)( (double)A_i0 B_0j + (double)A_i1 B_1j + ... [+ (double)C_ij] ), added left to right.
+ * A product of two binary32 values is exact in binary64, so contraction cannot change a bit.  SetPose, UpdateConnections,
+ * Replace / AddObservation of :609-625, LoopConnections, the mutexes and the threads stay with the caller. ---- */
+
+/* CorrectedSim3, NonCorrectedSim3 (:519-551) and the corrected poses (:590-596) of the K key frames of
+ * mvpCurrentConnectedKFs.  Tiw[k] = GetPose(), Twc_cur = mpCurrentKF->GetPoseInverse(), cur = its index in the list, Scw =
+ * mg2oScw.  Tic = Tiw * Twc as above; g2o::Sim3(R, t, 1) is Eigen's Quaterniond(Matrix3d); g2oSic * mg2oScw is g2o's
+ * product (sim3.h:266-272, no normalisation); Tiw_corrected = [R | t * (1 / s)] as floats.  corrected[cur] is Scw bit for
+ * bit; noncorrected[., 7] is exactly 1.  A non-finite input, a scale <= 0 and cur outside [0, K) return ORBFE_ERR_INVALID
+ * with nothing written.  Host code: needs no device. */
+int orbfe_correct_loop_sim3s(int K, const float *Tiw /* [K*16] */, const float *Twc_cur /* [16] */, int cur, const double *Scw /* [8] */,
+                             double *corrected /* [K*8] */, double *noncorrected /* [K*8] */, float *Tiw_corrected /* [K*16] */);
+/* The point loop of :558-587 on arrays: key frame k lists point[offsets[k] .. offsets[k+1]) (-1 = NULL); skip[p] =
+ * isBad() || mnCorrectedByKF == current (NULL = none).  corrected_ref[p] = the lowest k whose list names p (-1: untouched,
+ * xw copied through); xw_out[p] = corrected[k]^-1 .map( noncorrected[k] .map(xw[p]) ), the arithmetic of
+ * orbfe_essential_graph_correct_points: binary64, stored as float.  Deviation: the reference walks std::map<KeyFrame*, ..>
+ * in pointer order; here the order is the caller's list (ascending mnId is recommended).  Host code: needs no device. */
+int orbfe_correct_loop_points(int K, const double *corrected, const double *noncorrected, const int32_t *offsets /* [K+1] */,
+                              const int32_t *point, int n_points, const float *xw, const uint8_t *skip /* or NULL */, float *xw_out,
+                              int32_t *corrected_ref);
+/* The same loop, with MapPoint::UpdateNormalAndDepth (:586), on the resident state: g with key-frame rows enabled holds
+ * mvpMapPoints, the observation rows, the bad flags, the reference key frames and Ow; mp holds position, normal and range.
+ * kf_slot[K]: the key frames in visiting order.  Deviation: the reference visits std::map<KeyFrame*, ..> in pointer order,
+ * which differs from run to run; the call takes any order, ascending mnId is recommended (the row-order deviation of
+ * orbfe_obsgraph is the same kind).  skip_slot[n_skip]: the points with mnCorrectedByKF == current.
+ *   Claim.  Key frames in list order, a row's entries in idx order; an entry is passed over when it is -1, when the point is
+ *   bad or was never set, or when the point is in the skip list.  A point belongs to the lowest position
+ *   k * kf_row_width + idx that names it -- an integer minimum, never arrival order.  A kf slot named twice contributes
+ *   nothing the second time (and its first Ow_corrected is the one kept).
+ *   Correct.  The claimed point's position in mp is rewritten in place, bit-equal to orbfe_correct_loop_points.
+ *   Normal and depth.  orbfe_obsgraph_update_normal_depth's restatement at the new position, with one rule added: an
+ *   observing key frame whose place in the list is BELOW the claimant's uses Ow_corrected[place] (the reference has called
+ *   SetPose on it by then, :600); every other observer -- the claimant itself, later places, key frames outside the list --
+ *   uses the centre the graph holds.  The same rule picks the reference key frame's centre for the distance.  valid = 0 as
+ *   for orbfe_obsgraph_update_normal_depth: the position is still corrected, normal and range keep what they hold.
+ * slot_out[]: the claimed slots in claim order; ref_out[]: the claimant's place in the list (mnCorrectedReference; the
+ * ref_vertex of orbfe_essential_graph_correct_mappoints); valid_out[] (may be NULL); *count.  A count above `capacity`
+ * returns ORBFE_ERR_CAPACITY with *count set and both tables untouched.  On success the K key frames' Ow in g, host mirror
+ * and device, are Ow_corrected (the caller's GetCameraCenter() after SetPose(Tiw_corrected)): no set_keyframes is needed.
+ * ORBFE_ERR_INVALID before anything is enqueued: a kf slot out of range or never set, rows not enabled, K * kf_row_width
+ * >= 2^31, a non-finite record or centre, a scale <= 0, a skip slot out of range, handles on different devices or g with
+ * more point slots than mp, and a reference entry of a point the rows name whose octave is not below n_levels.  Takes g's
+ * serialisation, then mp's; complete on return. */
+int orbfe_correct_loop_mappoints(orbfe_obsgraph *g, orbfe_mappoints *mp, int K, const int32_t *kf_slot, const double *corrected,
+                                 const double *noncorrected, const float *Ow_corrected /* [K*3] */, int n_skip,
+                                 const int32_t *skip_slot, const float *scale_factors, int n_levels, int capacity, int32_t *slot_out,
+                                 int32_t *ref_out, uint8_t *valid_out /* or NULL */, int32_t *count);
+
+/* The spanning-tree walk of :788-815 on indices: origin[] = mvpKeyFrameOrigins, the children of key frame k =
+ * child[child_offsets[k] .. child_offsets[k+1]) (their order is immaterial: a child's result depends on its parent alone),
+ * Tcw / Twc = GetPose() / GetPoseInverse() at entry, in_gba[k] = (mnBAGlobalForKF == nLoopKF) at entry, Tcw_gba[k] = mTcwGBA,
+ * read where in_gba is set.  A child that was not in the GBA gets (:803-805) Tchildc = Tcw[child] * Twc[parent] and
+ * mTcwGBA = Tchildc * mTcwGBA[parent], two float products as above.  Tcw_new[k] = mTcwGBA after the walk (Tcw[k] for a key
+ * frame that was neither reached nor visited), reached[k] = the flag after the walk, visited[k] = the key frame was in the
+ * walk and receives SetPose(Tcw_new[k]) with mTcwBefGBA = Tcw[k].  An origin that was not in the GBA keeps its flag and, as in
+ * the reference (:813), receives whatever Tcw_gba holds for it: Tcw_gba is read for every origin as well.  ORBFE_ERR_INVALID
+ * with nothing written: an index out of range, a non-finite pose that would be read, a key frame visited twice (a cycle, or
+ * two parents).  Host code: needs no device. */
+int orbfe_gba_propagate_keyframes(int n, int n_origins, const int32_t *origin, const int32_t *child_offsets /* [n+1] */,
+                                  const int32_t *child, const float *Tcw, const float *Twc, const uint8_t *in_gba, const float *Tcw_gba,
+                                  float *Tcw_new, uint8_t *reached, uint8_t *visited);
+/* The point loop of :818-852 on arrays.  moved[p] = 0: skipped (the point is bad, its reference key frame was not reached,
+ * or -- deviation -- ref_kf[p] = -1, where the reference would dereference NULL) and xw is copied through; 1: the point
+ * took pos_gba (in_gba[p] = mnBAGlobalForKF == nLoopKF); 2: it was moved through its reference key frame,
+ *   Xc = Rcw_bef * P + tcw_bef;  P' = Rwc_new * Xc + twc_new,  each ONE gemm with beta = 1 as above:
+ *   Xc_i = (float)( (double)R_i0 P_0 + (double)R_i1 P_1 + (double)R_i2 P_2 + (double)t_i ), added left to right.
+ * Tcw_bef[k] = mTcwBefGBA, Twc_new[k] = GetPoseInverse() after SetPose, read where reached[k].  Host code. */
+int orbfe_gba_update_points(int n_points, const float *xw, const uint8_t *bad, const uint8_t *in_gba, const float *pos_gba,
+                            const int32_t *ref_kf, int n_kf, const uint8_t *reached, const float *Tcw_bef, const float *Twc_new,
+                            float *xw_out, uint8_t *moved);
+/* The same on the resident state: slot[n] = the caller's GetAllMapPoints (distinct slots), in_gba / pos_gba aligned with it;
+ * kf_slot[m] a compact list of distinct kf slots with reached / Tcw_bef / Twc_new aligned.  The bad flag and the reference
+ * kf slot come from g's point record (a slot never set counts as bad); a reference key frame that is not in the compact
+ * list counts as not reached.  Positions in mp are rewritten in place, bit-equal to orbfe_gba_update_points; moved[n] as
+ * there.  Normal and range are the caller's next orbfe_obsgraph_update_normal_depth_mappoints (the reference does not
+ * update them here either).  A slot or kf slot out of range or named twice, a non-finite pose or position that would be
+ * read, handles on different devices return ORBFE_ERR_INVALID before anything is enqueued.  Takes g's serialisation, then
+ * mp's; complete on return. */
+int orbfe_gba_update_mappoints(orbfe_obsgraph *g, orbfe_mappoints *mp, int n, const int32_t *slot, const uint8_t *in_gba,
+                               const float *pos_gba, int m, const int32_t *kf_slot, const uint8_t *reached, const float *Tcw_bef,
+                               const float *Twc_new, uint8_t *moved);
+
 #ifdef __cplusplus
 }
 #endif

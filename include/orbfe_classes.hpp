@@ -1101,6 +1101,54 @@ class MapPointTable {
     if (winnerIdx) winnerIdx->resize(slot.size());
     return valid;
   }
+  // The point loop at the head of LoopClosing::CorrectLoop (src/LoopClosing.cc:558-600) with UpdateNormalAndDepth, on the
+  // table (orbfe_correct_loop_mappoints): kfSlot = the key frames in visiting order (ascending mnId recommended), corrected /
+  // noncorrected 8 doubles each (LoopClosing::CorrectedSim3s), OwCorrected 3 floats each, skip = the slots with
+  // mnCorrectedByKF == current.  slots: the claimed slots in claim order; ref: the claimant's place in the list; valid:
+  // normal and range were rewritten.  The graph's Ow of the listed key frames are OwCorrected afterwards.
+  struct LoopCorrection {
+    std::vector<int32_t> slots, ref;
+    std::vector<uint8_t> valid;
+  };
+  LoopCorrection CorrectLoop(const ObservationGraph& graph, const std::vector<int32_t>& kfSlot, const std::vector<double>& corrected,
+                             const std::vector<double>& noncorrected, const std::vector<float>& OwCorrected,
+                             const std::vector<float>& mvScaleFactors, const std::vector<int32_t>& skip = {}) {
+    const size_t K = kfSlot.size();
+    if (corrected.size() != 8 * K || noncorrected.size() != 8 * K || OwCorrected.size() != 3 * K)
+      throw std::invalid_argument("MapPointTable::CorrectLoop: one entry per key frame");
+    LoopCorrection out;
+    size_t cap = 1024;
+    for (;;) {  // a count above the capacity changes nothing: grow to it and repeat
+      out.slots.assign(cap, 0); out.ref.assign(cap, 0); out.valid.assign(cap, 0);
+      int32_t n = 0;
+      const int rc = orbfe_correct_loop_mappoints(graph.handle(), h_, (int)K, kfSlot.data(), corrected.data(), noncorrected.data(),
+                                                  OwCorrected.data(), (int)skip.size(), skip.data(), mvScaleFactors.data(),
+                                                  (int)mvScaleFactors.size(), (int)cap, out.slots.data(), out.ref.data(),
+                                                  out.valid.data(), &n);
+      if (rc == ORBFE_ERR_CAPACITY && (size_t)n > cap) { cap = (size_t)n; continue; }
+      check(rc, "MapPointTable::CorrectLoop");
+      out.slots.resize((size_t)n); out.ref.resize((size_t)n); out.valid.resize((size_t)n);
+      return out;
+    }
+  }
+  // The map-point loop at the tail of LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:818-852) on the table
+  // (orbfe_gba_update_mappoints): slot = GetAllMapPoints (distinct), inGBA / posGBA (3 floats) aligned with it; kfSlot a compact
+  // list with reached, TcwBef = mTcwBefGBA and TwcNew = GetPoseInverse() after SetPose (16 floats each).  Returns moved[]: 0
+  // skipped, 1 took posGBA, 2 moved through its reference key frame.
+  std::vector<uint8_t> GlobalBundleAdjustmentUpdate(const ObservationGraph& graph, const std::vector<int32_t>& slot,
+                                                    const std::vector<uint8_t>& inGBA, const std::vector<float>& posGBA,
+                                                    const std::vector<int32_t>& kfSlot, const std::vector<uint8_t>& reached,
+                                                    const std::vector<float>& TcwBef, const std::vector<float>& TwcNew) {
+    const size_t n = slot.size(), m = kfSlot.size();
+    if (inGBA.size() != n || posGBA.size() != 3 * n || reached.size() != m || TcwBef.size() != 16 * m || TwcNew.size() != 16 * m)
+      throw std::invalid_argument("MapPointTable::GlobalBundleAdjustmentUpdate: the lists disagree in length");
+    std::vector<uint8_t> moved(n + 1, 0);
+    check(orbfe_gba_update_mappoints(graph.handle(), h_, (int)n, slot.data(), inGBA.data(), posGBA.data(), (int)m, kfSlot.data(),
+                                     reached.data(), TcwBef.data(), TwcNew.data(), moved.data()),
+          "MapPointTable::GlobalBundleAdjustmentUpdate");
+    moved.resize(n);
+    return moved;
+  }
   // GetDescriptor of slot[] as the table holds it (32 bytes each)
   std::vector<uint8_t> Descriptors(const std::vector<int32_t>& slot) const {
     std::vector<uint8_t> out(32 * slot.size() + 1);
@@ -1111,6 +1159,50 @@ class MapPointTable {
 
  private:
   orbfe_mappoints* h_ = nullptr;
+};
+
+// The host parts of LoopClosing::CorrectLoop (src/LoopClosing.cc:519-551, :590-596) and of the key-frame walk at the tail of
+// LoopClosing::RunGlobalBundleAdjustment (:788-815); the resident parts are MapPointTable::CorrectLoop and
+// MapPointTable::GlobalBundleAdjustmentUpdate.  Poses are row-major 4 x 4 floats, Sim3 records qx qy qz qw tx ty tz s.
+class LoopClosing {
+ public:
+  struct Sim3s {
+    std::vector<double> corrected, noncorrected;  // CorrectedSim3 / NonCorrectedSim3, 8 doubles per key frame
+    std::vector<float> TiwCorrected;              // what SetPose receives (:600), 16 floats per key frame
+  };
+  // Tiw = GetPose() of mvpCurrentConnectedKFs, TwcCur = mpCurrentKF->GetPoseInverse(), cur = its index, Scw = mg2oScw
+  static Sim3s CorrectedSim3s(const std::vector<float>& Tiw, const std::vector<float>& TwcCur, int cur, const std::vector<double>& Scw) {
+    if (Tiw.size() % 16 || TwcCur.size() != 16 || Scw.size() != 8)
+      throw std::invalid_argument("LoopClosing::CorrectedSim3s: 16 floats per pose, 8 doubles for Scw");
+    const size_t K = Tiw.size() / 16;
+    Sim3s out;
+    out.corrected.assign(8 * K + 1, 0.0); out.noncorrected.assign(8 * K + 1, 0.0); out.TiwCorrected.assign(16 * K + 1, 0.f);
+    check(orbfe_correct_loop_sim3s((int)K, Tiw.data(), TwcCur.data(), cur, Scw.data(), out.corrected.data(), out.noncorrected.data(),
+                                   out.TiwCorrected.data()), "LoopClosing::CorrectedSim3s");
+    out.corrected.resize(8 * K); out.noncorrected.resize(8 * K); out.TiwCorrected.resize(16 * K);
+    return out;
+  }
+  struct Propagation {
+    std::vector<float> TcwNew;              // mTcwGBA after the walk, 16 floats per key frame
+    std::vector<uint8_t> reached, visited;  // mnBAGlobalForKF == nLoopKF after the walk; the key frame receives SetPose
+  };
+  // origins = mvpKeyFrameOrigins as indices; the children of key frame k = child[childOffsets[k] .. childOffsets[k + 1]);
+  // Tcw / Twc at entry, inGBA[k] = mnBAGlobalForKF == nLoopKF at entry, TcwGBA = mTcwGBA
+  static Propagation PropagateGBA(const std::vector<int32_t>& origins, const std::vector<int32_t>& childOffsets,
+                                  const std::vector<int32_t>& child, const std::vector<float>& Tcw, const std::vector<float>& Twc,
+                                  const std::vector<uint8_t>& inGBA, const std::vector<float>& TcwGBA) {
+    const size_t n = inGBA.size();
+    if (Tcw.size() != 16 * n || Twc.size() != 16 * n || TcwGBA.size() != 16 * n || childOffsets.size() != n + 1 ||
+        (size_t)std::max(childOffsets.back(), 0) > child.size())
+      throw std::invalid_argument("LoopClosing::PropagateGBA: the lists disagree in length");
+    Propagation out;
+    out.TcwNew.assign(16 * n + 1, 0.f); out.reached.assign(n + 1, 0); out.visited.assign(n + 1, 0);
+    check(orbfe_gba_propagate_keyframes((int)n, (int)origins.size(), origins.data(), childOffsets.data(), child.data(), Tcw.data(),
+                                        Twc.data(), inGBA.data(), TcwGBA.data(), out.TcwNew.data(), out.reached.data(),
+                                        out.visited.data()), "LoopClosing::PropagateGBA");
+    out.TcwNew.resize(16 * n); out.reached.resize(n); out.visited.resize(n);
+    return out;
+  }
 };
 
 // Optimizer::PoseOptimization (src/Optimizer.cc:256-473), Optimizer::OptimizeSim3 (:1116-1323), Optimizer::LocalBundleAdjustment

@@ -12,7 +12,8 @@ from .optimizer import (bundle_adjustment, local_bundle_adjustment, optimize_sim
 from .local_mapping import KeyFrameCamera, triangulate_matches, triangulate_matches_multi  # noqa: F401
 from .relocalization import (PnPsolver, pnp_ransac, pnp_ransac_multi, pnp_refine_multi,  # noqa: F401
                              pnp_sets_from_draws, pnp_solve_multi)
-from .loop_closing import (Sim3Solver, sim3_legs, sim3_max_iterations, sim3_ransac, sim3_ransac_multi,  # noqa: F401
+from .loop_closing import (Sim3Solver, correct_loop_points, correct_loop_sim3s, gba_propagate_keyframes,  # noqa: F401
+                           gba_update_points, sim3_legs, sim3_max_iterations, sim3_ransac, sim3_ransac_multi,
                            sim3_triples_from_draws)
 from .initializer import (Initializer, initializer_normalize, initializer_ransac, initializer_ransac_multi,  # noqa: F401
                           initializer_reconstruct, initializer_reconstruct_multi, initializer_sets_from_draws)

@@ -145,6 +145,8 @@ EXPORTS = [
     "orbfe_project_last_frame", "orbfe_search_last_frame_mappoints", "orbfe_project_keyframe",
     "orbfe_search_keyframe_mappoints_multi",
     "orbfe_project_sim3", "orbfe_search_by_sim3_mappoints_multi", "orbfe_search_by_projection_sim3_mappoints",
+    "orbfe_correct_loop_sim3s", "orbfe_correct_loop_points", "orbfe_correct_loop_mappoints",
+    "orbfe_gba_propagate_keyframes", "orbfe_gba_update_points", "orbfe_gba_update_mappoints",
 ]
 
 _lib = None
@@ -383,6 +385,12 @@ def load():
     L.orbfe_project_sim3.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbfe_search_by_sim3_mappoints_multi.argtypes = [vp, vp, fwp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, cf, vp, vp]
     L.orbfe_search_by_projection_sim3_mappoints.argtypes = [vp, ci, vp, vp, cpp, fwp, vp, ci, vp, cf, vp, vp, vp]
+    L.orbfe_correct_loop_sim3s.argtypes = [ci, vp, vp, ci, vp, vp, vp, vp]
+    L.orbfe_correct_loop_points.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+    L.orbfe_correct_loop_mappoints.argtypes = [vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+    L.orbfe_gba_propagate_keyframes.argtypes = [ci, ci] + [vp] * 10
+    L.orbfe_gba_update_points.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_gba_update_mappoints.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -155,6 +155,8 @@ const char* kNotEnabled = "key-frame rows are not enabled (orbfe_obsgraph_enable
 
 }  // namespace
 
+int orbfe::obs_kf_ready(orbfe_obsgraph* g) { return kf_ready(g); }
+
 extern "C" int orbfe_obsgraph_enable_keyframe_points(orbfe_obsgraph* g, int kf_row_width) {
   if (!g) return obs_invalid("obsgraph_enable_keyframe_points", "NULL graph");
   std::lock_guard<std::mutex> lk(g->m);

@@ -26,6 +26,9 @@ struct orbfe_obsgraph {
   // KeyFrame::mDescriptors: a slab of its own, empty until the first set_keyframe_descriptors*; no host copy of the bytes
   orbfe::Slab descTable;
   orbfe::KfDescDevice dd{};
+  // kf slot -> place in the list of a loop-correction call (loopcorrect.hip): kf_capacity int32, -1 everywhere between
+  // calls; empty until the first such call
+  orbfe::DevBuf<int32_t> kfRank;
   // grow-only workspace + pinned staging in both directions
   orbfe::DevBuf<uint8_t> work;
   orbfe::PinBuf<uint8_t> pin;
@@ -43,5 +46,7 @@ int obs_stream(orbfe_obsgraph* g);
 // what every call that reads the table on the device starts with: device, stream, the slab, the marked rows written
 int obs_ready(orbfe_obsgraph* g);
 int obs_invalid(const char* fn, const char* what);
+// kfpoints.hip: obs_ready, then the key-frame rows' own slab and their marked rows (the rows enabled)
+int obs_kf_ready(orbfe_obsgraph* g);
 
 }  // namespace orbfe

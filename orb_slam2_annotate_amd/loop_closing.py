@@ -254,3 +254,82 @@ class Sim3Solver:
 
     def GetEstimatedScale(self):
         return float(self._best_sim3()[12])
+
+
+# ---- Loop correction: the head of CorrectLoop (src/LoopClosing.cc:514-604) and the map update at the tail of
+# RunGlobalBundleAdjustment (src/LoopClosing.cc:787-852).  The resident forms are MapPoints.correct_loop / gba_update. ----
+def _u8(a):
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _csr(lists):
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in lists])
+    flat = _i32(np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in lists])) if off[-1] else np.zeros(1, np.int32)
+    return off, flat
+
+
+def correct_loop_sim3s(Tiw, Twc_cur, cur: int, Scw):
+    """CorrectedSim3, NonCorrectedSim3 (:519-551) and the corrected poses (:590-596) of mvpCurrentConnectedKFs
+    (orbfe_correct_loop_sim3s): Tiw [K, 4, 4] = GetPose(), Twc_cur = the current key frame's GetPoseInverse(), cur its index,
+    Scw = mg2oScw as qx qy qz qw tx ty tz s -> (corrected [K, 8], noncorrected [K, 8], Tiw_corrected [K, 4, 4])."""
+    T = _f32(Tiw).reshape(-1, 16)
+    K = len(T)
+    tw = _f32(Twc_cur).reshape(16)
+    s = np.ascontiguousarray(Scw, dtype=np.float64).reshape(8)
+    cor, non, out = np.zeros((max(K, 1), 8)), np.zeros((max(K, 1), 8)), np.zeros((max(K, 1), 16), np.float32)
+    check(_lib.load().orbfe_correct_loop_sim3s(K, ptr(T), ptr(tw), int(cur), ptr(s), ptr(cor), ptr(non), ptr(out)))
+    return cor[:K], non[:K], out[:K].reshape(-1, 4, 4)
+
+
+def correct_loop_points(corrected, noncorrected, kf_points, xw, skip=None):
+    """The point loop of :558-587 on arrays (orbfe_correct_loop_points): kf_points[k] = the point indices key frame k lists
+    (-1 = NULL), skip[p] = isBad() or mnCorrectedByKF == current -> (xw_out [n, 3], corrected_ref [n]: the claiming list
+    position, -1 = untouched)."""
+    cor = np.ascontiguousarray(corrected, dtype=np.float64).reshape(-1, 8)
+    non = np.ascontiguousarray(noncorrected, dtype=np.float64).reshape(-1, 8)
+    if len(cor) != len(non) or len(cor) != len(kf_points):
+        raise ValueError("correct_loop_points: corrected, noncorrected and kf_points must hold one entry per key frame")
+    off, flat = _csr(kf_points)
+    x = _f32(xw).reshape(-1, 3)
+    n = len(x)
+    sk = None if skip is None else _u8(skip).reshape(-1)
+    if sk is not None and len(sk) != n:
+        raise ValueError("correct_loop_points: skip must hold one entry per point")
+    out, ref = np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.int32)
+    check(_lib.load().orbfe_correct_loop_points(len(cor), ptr(cor), ptr(non), ptr(off), ptr(flat), n, ptr(x), ptr(sk), ptr(out), ptr(ref)))
+    return out[:n], ref[:n]
+
+
+def gba_propagate_keyframes(origins, children, Tcw, Twc, in_gba, Tcw_gba):
+    """The spanning-tree walk of :788-815 (orbfe_gba_propagate_keyframes): origins = mvpKeyFrameOrigins as indices,
+    children[k] = the indices of key frame k's children, Tcw / Twc [n, 4, 4] at entry, in_gba[k] = mnBAGlobalForKF == nLoopKF,
+    Tcw_gba [n, 4, 4] = mTcwGBA (read where in_gba) -> (Tcw_new [n, 4, 4], reached [n], visited [n])."""
+    T, Tw, Tg = _f32(Tcw).reshape(-1, 16), _f32(Twc).reshape(-1, 16), _f32(Tcw_gba).reshape(-1, 16)
+    n = len(T)
+    g = _u8(in_gba).reshape(-1)
+    if not (len(Tw) == len(Tg) == len(g) == len(children) == n):
+        raise ValueError("gba_propagate_keyframes: every per-key-frame array must hold n entries")
+    o = _i32(origins).reshape(-1)
+    off, flat = _csr(children)
+    out, reached, visited = np.zeros((max(n, 1), 16), np.float32), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+    check(_lib.load().orbfe_gba_propagate_keyframes(n, len(o), ptr(o), ptr(off), ptr(flat), ptr(T), ptr(Tw), ptr(g), ptr(Tg), ptr(out),
+                                                    ptr(reached), ptr(visited)))
+    return out[:n].reshape(-1, 4, 4), reached[:n], visited[:n]
+
+
+def gba_update_points(xw, bad, in_gba, pos_gba, ref_kf, reached, Tcw_bef, Twc_new):
+    """The point loop of :818-852 on arrays (orbfe_gba_update_points) -> (xw_out [p, 3], moved [p]: 0 skipped, 1 took
+    pos_gba, 2 moved through its reference key frame ref_kf[p], an index into reached / Tcw_bef / Twc_new; -1 = none)."""
+    x, pg = _f32(xw).reshape(-1, 3), _f32(pos_gba).reshape(-1, 3)
+    p = len(x)
+    b, g, r = _u8(bad).reshape(-1), _u8(in_gba).reshape(-1), _i32(ref_kf).reshape(-1)
+    if not (len(pg) == len(b) == len(g) == len(r) == p):
+        raise ValueError("gba_update_points: every per-point array must hold p entries")
+    rc, tb, tn = _u8(reached).reshape(-1), _f32(Tcw_bef).reshape(-1, 16), _f32(Twc_new).reshape(-1, 16)
+    if not (len(tb) == len(tn) == len(rc)):
+        raise ValueError("gba_update_points: every per-key-frame array must hold one entry per key frame")
+    out, moved = np.zeros((max(p, 1), 3), np.float32), np.zeros(max(p, 1), np.uint8)
+    check(_lib.load().orbfe_gba_update_points(p, ptr(x), ptr(b), ptr(g), ptr(pg), ptr(r), len(rc), ptr(rc), ptr(tb), ptr(tn), ptr(out),
+                                              ptr(moved)))
+    return out[:p], moved[:p]

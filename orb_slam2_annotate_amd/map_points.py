@@ -468,6 +468,50 @@ class MapPoints:
             raise ValueError("MapPoints.essential_graph_correct: ref_vertex must hold one entry per slot")
         check(self._L.orbfe_essential_graph_correct_mappoints(self._h, len(s), ptr(s), ptr(so), len(sl), ptr(sl), ptr(r)))
 
+    def correct_loop(self, graph, kf_slots, corrected, noncorrected, Ow_corrected, scale_factors, skip=(), capacity=None):
+        """The point loop at the head of LoopClosing::CorrectLoop (src/LoopClosing.cc:558-600) with UpdateNormalAndDepth, on
+        the table (orbfe_correct_loop_mappoints): `graph` holds the key-frame rows, the observation rows and Ow; kf_slots the
+        key frames in visiting order (ascending mnId recommended), corrected / noncorrected [K, 8] from
+        loop_closing.correct_loop_sim3s, Ow_corrected [K, 3] the centres after SetPose, skip the slots with
+        mnCorrectedByKF == current -> (slots, ref, valid): the claimed slots in claim order, the claimant's list position
+        and whether normal and range were rewritten.  The graph's Ow of the K key frames are Ow_corrected afterwards."""
+        kf = np.ascontiguousarray(kf_slots, dtype=np.int32).reshape(-1)
+        K = len(kf)
+        cor = np.ascontiguousarray(corrected, dtype=np.float64).reshape(-1, 8)
+        non = np.ascontiguousarray(noncorrected, dtype=np.float64).reshape(-1, 8)
+        ow = np.ascontiguousarray(Ow_corrected, dtype=np.float32).reshape(-1, 3)
+        if not (len(cor) == len(non) == len(ow) == K):
+            raise ValueError("MapPoints.correct_loop: corrected, noncorrected and Ow_corrected must hold one entry per key frame")
+        sk = np.ascontiguousarray(skip, dtype=np.int32).reshape(-1)
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        cap = graph.point_capacity if capacity is None else int(capacity)
+        slots, ref, valid = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.uint8)
+        n = C.c_int32(0)
+        check(self._L.orbfe_correct_loop_mappoints(graph._h, self._h, K, ptr(kf), ptr(cor), ptr(non), ptr(ow), len(sk), ptr(sk), ptr(sf),
+                                                   len(sf), cap, ptr(slots), ptr(ref), ptr(valid), C.byref(n)))
+        return slots[:n.value].copy(), ref[:n.value].copy(), valid[:n.value].copy()
+
+    def gba_update(self, graph, slot, in_gba, pos_gba, kf_slots, reached, Tcw_bef, Twc_new):
+        """The map-point loop at the tail of LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:818-852) on the table
+        (orbfe_gba_update_mappoints): slot = GetAllMapPoints (distinct), in_gba / pos_gba aligned with it; kf_slots a compact
+        list with reached, Tcw_bef = mTcwBefGBA and Twc_new = GetPoseInverse() after SetPose.  The bad flag and the reference
+        key frame come from `graph` -> moved [n]: 0 skipped, 1 took pos_gba, 2 moved through its reference key frame."""
+        sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+        g = np.ascontiguousarray(in_gba, dtype=np.uint8).reshape(-1)
+        pg = np.ascontiguousarray(pos_gba, dtype=np.float32).reshape(-1, 3)
+        if not (len(g) == len(pg) == len(sl)):
+            raise ValueError("MapPoints.gba_update: in_gba and pos_gba must hold one entry per slot")
+        kf = np.ascontiguousarray(kf_slots, dtype=np.int32).reshape(-1)
+        rc = np.ascontiguousarray(reached, dtype=np.uint8).reshape(-1)
+        tb = np.ascontiguousarray(Tcw_bef, dtype=np.float32).reshape(-1, 16)
+        tn = np.ascontiguousarray(Twc_new, dtype=np.float32).reshape(-1, 16)
+        if not (len(rc) == len(tb) == len(tn) == len(kf)):
+            raise ValueError("MapPoints.gba_update: reached, Tcw_bef and Twc_new must hold one entry per kf slot")
+        moved = np.zeros(max(len(sl), 1), np.uint8)
+        check(self._L.orbfe_gba_update_mappoints(graph._h, self._h, len(sl), ptr(sl), ptr(g), ptr(pg), len(kf), ptr(kf), ptr(rc), ptr(tb),
+                                                 ptr(tn), ptr(moved)))
+        return moved[:len(sl)]
+
     def positions(self, slot):
         """orbfe_mappoints_positions: the world positions the table holds for slot[] -> [n, 3] float32."""
         sl = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
