@@ -1,12 +1,17 @@
-// arena.h -- the calling thread's device arena with its pinned mirror and stream, the thread's pinned staging buffer and the
-// event pool: what a host file of csrc/ includes to run a call on the thread's matcher stream.  Every thread owns a private
-// arena + stream per device (the reference constructs stack-local ORBmatcher objects on three threads concurrently,
-// src/LocalMapping.cc:261, src/LoopClosing.cc:294), so the entry points built on it are stateless and re-entrant.
+// arena.h -- a device arena with its pinned mirror and stream, the thread's pinned staging buffer and the event pool: what
+// a host file of csrc/ includes to run a call on a stream.  An arena has one of two kinds of owner:
+//   the calling thread   a private arena + stream per device (the reference constructs stack-local ORBmatcher objects on
+//                        three threads concurrently, src/LocalMapping.cc:261, src/LoopClosing.cc:294), so the entry
+//                        points built on it are stateless and re-entrant
+//   a handle             a member of the handle (orbfe_obsgraph, orbfe_kfdb), used with the handle locked: the handle's
+//                        calls run on its own stream, whichever thread makes them
 //
-// Two ways in, each of which begins the arena anew (what an earlier call of the thread left in it is gone):
+// Two ways in, each of which begins the arena anew (what an earlier call left in it is gone); `device, &ar` names the
+// calling thread's arena, `&own, device` one that a handle owns:
 //   arena_stage(device, &ar, stage)    a call that carves: up() / up_pack() / up_fill() / carve() inside `stage`, then
-//                                      flush(), the launches, down_span() / down_range(), a synchronisation, mirror_of()
-//   arena_stream(device, &ar)          ar->stream alone
+//   arena_stage(&own, device, stage)   flush(), the launches, down_span() / down_range(), a synchronisation, mirror_of()
+//   arena_stream(device, &ar)          the stream alone
+//   arena_stream(&own, device)
 // State and the non-templates: arena.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,7 +43,7 @@ struct Arena {
   struct OutSpan {
     size_t lo = 0, hi = 0;  // arena offsets: the start of the first output, the end of the last (not rounded up)
   } out;                    // open_span() / close_span() / down_span()
-  ~Arena() {  // (thread exit; the buffers free themselves behind this, on the device set here)
+  ~Arena() {  // (thread exit, or the owning handle's end; the buffers free themselves behind this, on the device set here)
     if (device >= 0) {
       (void)hipSetDevice(device);
       if (stream) (void)hipStreamDestroy(stream);
@@ -46,8 +51,10 @@ struct Arena {
   }
 };
 
-// begins the arena with room for `bytes`: behind arena_stage / arena_stream, which are what callers use
+// begin an arena with room for `bytes` -- the calling thread's of `device`, or `own` (its stream is made on `device` by the
+// first begin): behind arena_stage / arena_stream, which are what callers use
 hipError_t arena_begin(int device, size_t bytes, Arena** out);
+hipError_t arena_begin_owned(Arena* own, int device, size_t bytes);
 
 template <typename T>
 T* carve(Arena* a, size_t n) {
@@ -112,9 +119,28 @@ inline hipError_t close_span(Arena* a) {
   return a->sizing ? hipSuccess : grow_mirror(a, a->out.hi);  // the mirror reaches the outputs before flush() reads from it
 }
 inline hipError_t down_span(Arena* a) { return down_range(a, a->base + a->out.lo, a->base + a->out.hi); }
+inline size_t span_bytes(const Arena* a) { return a->out.hi - a->out.lo; }
+inline hipError_t zero_span(Arena* a) { return hipMemsetAsync(a->base + a->out.lo, 0, span_bytes(a), a->stream); }  // ONE fill
 template <typename T>
 const T* mirror_of(Arena* a, const T* d) {
   return reinterpret_cast<const T*>(a->hmirror + (reinterpret_cast<const uint8_t*>(d) - a->base));
+}
+// The few copies whose other end is a slab, not the arena, each ONE copy on the arena's stream.  fetch: n elements of device
+// memory at `src` into the mirror, at the place of the array carved at `at`, to be read through mirror_of() after a
+// synchronisation; the place must lie inside the closed output span, which the mirror reaches.  send: the n elements that
+// up() / up_pack() staged for the array carved at `at`, from the mirror to the device address `dst`; a call that only sends
+// does not flush(), so the bytes travel once.  Either fails with hipErrorInvalidValue, nothing enqueued, on another place.
+template <typename T>
+hipError_t fetch(Arena* a, T* at, const T* src, size_t n) {
+  const size_t off = (size_t)(reinterpret_cast<const uint8_t*>(at) - a->base);
+  if (off < a->out.lo || off + n * sizeof(T) > a->out.hi) return hipErrorInvalidValue;
+  return hipMemcpyAsync(a->hmirror + off, src, n * sizeof(T), hipMemcpyDeviceToHost, a->stream);
+}
+template <typename T>
+hipError_t send(Arena* a, T* dst, const T* at, size_t n) {
+  const size_t off = (size_t)(reinterpret_cast<const uint8_t*>(at) - a->base);
+  if (off < a->dirtyLo || off + n * sizeof(T) > a->dirtyHi) return hipErrorInvalidValue;
+  return hipMemcpyAsync(dst, a->hmirror + off, n * sizeof(T), hipMemcpyHostToDevice, a->stream);
 }
 // one H2D copy for everything staged since arena_begin(); call before the first kernel launch.  Whole 256-byte lines
 // travel (a copy that ends inside a line costs a microsecond more): carve() starts every array on a line and arena_begin()
@@ -122,21 +148,33 @@ const T* mirror_of(Arena* a, const T* d) {
 hipError_t flush(Arena* a);
 
 // Stages a call: runs `stage` -- the up*() / carve() calls of the call -- twice, first on a sizing arena that
-// only counts, then on the calling thread's arena of `device`, begun with exactly what the first pass carved: the size
+// only counts, then on the arena that begin(bytes, out) begins with exactly what the first pass carved: the size
 // cannot drift from the carving.  `stage` must carve the same sizes in both passes: one that does not fails the call
 // with hipErrorInvalidValue before anything is enqueued.
-template <typename F>
-hipError_t arena_stage(int device, Arena** out, F&& stage) {
+template <typename F, typename Begin>
+hipError_t stage_two_pass(Arena** out, F&& stage, Begin&& begin) {
   Arena sizing;
   sizing.sizing = true;
   hipError_t e = stage(&sizing);
-  if (e == hipSuccess) e = arena_begin(device, sizing.used, out);
+  if (e == hipSuccess) e = begin(sizing.used, out);
   if (e == hipSuccess) e = stage(*out);
   if (e == hipSuccess && (*out)->used != sizing.used) e = hipErrorInvalidValue;
   return e;
 }
-// the calling thread's stream on `device`, (*out)->stream, for a call that carves nothing
+// on the calling thread's arena of `device`
+template <typename F>
+hipError_t arena_stage(int device, Arena** out, F&& stage) {
+  return stage_two_pass(out, stage, [device](size_t bytes, Arena** o) { return arena_begin(device, bytes, o); });
+}
+// on an arena that a handle owns (the handle locked)
+template <typename F>
+hipError_t arena_stage(Arena* own, int device, F&& stage) {
+  Arena* ar;
+  return stage_two_pass(&ar, stage, [own, device](size_t bytes, Arena** o) { *o = own; return arena_begin_owned(own, device, bytes); });
+}
+// the stream alone -- (*out)->stream, own->stream -- for a call that carves nothing
 hipError_t arena_stream(int device, Arena** out);
+inline hipError_t arena_stream(Arena* own, int device) { return arena_begin_owned(own, device, 0); }
 
 // Pinned staging of the calling thread for copies whose destination is a slab, not the arena (frame builds,
 // orbfe_frame_set_featvec): the call packs what travels in the slab's own layout and sends it in ONE

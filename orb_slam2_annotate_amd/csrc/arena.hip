@@ -1,5 +1,6 @@
-// arena.hip -- the state behind arena.h: the thread-local arenas and staging buffer, the process-wide pool of device slabs
-// (host_internal.h: slab_get / slab_put) and events, and the two test hooks on the calling thread's stream.
+// arena.hip -- the state behind arena.h: the thread-local arenas and staging buffer, the begin of an arena whoever owns it,
+// the process-wide pool of device slabs (host_internal.h: slab_get / slab_put) and events, and the two test hooks on the
+// calling thread's stream.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -20,11 +21,10 @@ thread_local std::map<int, Arena> t_arenas;
 thread_local Staging t_staging;
 }  // namespace
 
-// Reserve `bytes` up front (sum of all buffers of a call), then carve.
-hipError_t arena_begin(int device, size_t bytes, Arena** out) {
-  hipError_t err = hipSetDevice(device);
-  if (err != hipSuccess) return err;
-  Arena& a = t_arenas[device];
+// Reserve `bytes` up front (sum of all buffers of a call), then carve.  Whose arena it is makes no difference here; the
+// device is current.
+static hipError_t begin_on(Arena& a, int device, size_t bytes) {
+  hipError_t err;
   bytes = (bytes + 255) & ~(size_t)255;
   if (a.device < 0) {
     a.device = device;
@@ -38,8 +38,20 @@ hipError_t arena_begin(int device, size_t bytes, Arena** out) {
   a.used = 0;
   a.dirtyLo = a.dirtyHi = 0;
   a.out = {};
-  *out = &a;
   return hipSuccess;
+}
+
+hipError_t arena_begin_owned(Arena* own, int device, size_t bytes) {
+  const hipError_t err = hipSetDevice(device);
+  return err != hipSuccess ? err : begin_on(*own, device, bytes);
+}
+hipError_t arena_begin(int device, size_t bytes, Arena** out) {
+  hipError_t err = hipSetDevice(device);
+  if (err != hipSuccess) return err;
+  Arena& a = t_arenas[device];
+  err = begin_on(a, device, bytes);
+  if (err == hipSuccess) *out = &a;
+  return err;
 }
 
 hipError_t arena_stream(int device, Arena** out) { return arena_begin(device, 0, out); }

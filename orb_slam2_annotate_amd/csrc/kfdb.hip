@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/orbfe.h"
+#include "arena.h"
 #include "host_internal.h"
 #include "kfdb_kernels.h"
 
@@ -34,8 +35,6 @@ struct HostSlot {
 struct orbfe_kfdb {
   int device = 0, nWords = 0;
   mutable std::mutex m;
-  bool ready = false;  // stream created
-  hipStream_t stream = nullptr;
   // host mirror
   std::vector<uint32_t> hWords;
   std::vector<double> hValues;
@@ -46,47 +45,27 @@ struct orbfe_kfdb {
   // device CSR: slabs of the pool that the resident frames use (host_internal.h), so a released database's arrays serve
   // the next database / the next doubling
   Slab dWords, dValues, dSlots;
-  // grow-only workspace of the queries + pinned staging in both directions
-  DevBuf<uint8_t> work;
-  PinBuf<uint8_t> pin;
+  // the handle's stream (made by the first call that touches the device), and what the two query calls stage through
+  Arena arena;
 };
 
 namespace {
 
-int kfdb_device(orbfe_kfdb* db) {
-  HIPCHK(hipSetDevice(db->device));
-  if (!db->ready) {
-    HIPCHK(hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
-    db->ready = true;
-  }
-  return ORBFE_OK;
-}
-
-// `have` (or `first` when there is nothing yet), doubled until it holds `need`
-size_t doubled(size_t have, size_t first, size_t need) {
-  size_t want = have ? have : first;
-  while (want < need) want *= 2;
-  return want;
-}
-
 // room for `need` bytes in *s, contents [0, used) kept: a doubled slab from the pool, one device-to-device copy
 int slab_reserve(orbfe_kfdb* db, Slab* s, size_t need, size_t used) {
   if (need <= s->cap) return ORBFE_OK;
+  size_t want = s->cap ? s->cap : (size_t)1 << 16;
+  while (want < need) want *= 2;
   Slab n;
-  HIPCHK(slab_get(db->device, doubled(s->cap, (size_t)1 << 16, need), &n));
+  HIPCHK(slab_get(db->device, want, &n));
   if (used) {
-    hipError_t e = hipMemcpyAsync(n.p, s->p, used, hipMemcpyDeviceToDevice, db->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
+    hipError_t e = hipMemcpyAsync(n.p, s->p, used, hipMemcpyDeviceToDevice, db->arena.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(db->arena.stream);
     if (e != hipSuccess) { slab_put(&n); HIPCHK(e); }
   }
   slab_put(s);
   *s = n;
   return ORBFE_OK;
-}
-
-int ensure_work(orbfe_kfdb* db, size_t devBytes, size_t pinBytes) {
-  const int rc = db->work.reserve(devBytes, doubled(db->work.cap, (size_t)1 << 20, devBytes));
-  return rc ? rc : db->pin.reserve(pinBytes, doubled(db->pin.cap, (size_t)1 << 16, pinBytes));
 }
 
 KfdbStore store_of(const orbfe_kfdb* db) {
@@ -112,11 +91,11 @@ int kfdb_compact(orbfe_kfdb* db) {
   }
   // (the slabs only ever grow, so everything fits)
   if (!w.empty()) {
-    HIPCHK(hipMemcpyAsync(db->dWords.p, w.data(), w.size() * 4, hipMemcpyHostToDevice, db->stream));
-    HIPCHK(hipMemcpyAsync(db->dValues.p, v.data(), v.size() * 8, hipMemcpyHostToDevice, db->stream));
+    HIPCHK(hipMemcpyAsync(db->dWords.p, w.data(), w.size() * 4, hipMemcpyHostToDevice, db->arena.stream));
+    HIPCHK(hipMemcpyAsync(db->dValues.p, v.data(), v.size() * 8, hipMemcpyHostToDevice, db->arena.stream));
   }
-  if (!rec.empty()) HIPCHK(hipMemcpyAsync(db->dSlots.p, rec.data(), rec.size() * sizeof(KfdbSlot), hipMemcpyHostToDevice, db->stream));
-  HIPCHK(hipStreamSynchronize(db->stream));
+  if (!rec.empty()) HIPCHK(hipMemcpyAsync(db->dSlots.p, rec.data(), rec.size() * sizeof(KfdbSlot), hipMemcpyHostToDevice, db->arena.stream));
+  HIPCHK(hipStreamSynchronize(db->arena.stream));
   db->stale = false;
   db->hWords.swap(w); db->hValues.swap(v); db->slots.swap(s);
   db->slotOf.clear();
@@ -126,9 +105,8 @@ int kfdb_compact(orbfe_kfdb* db) {
 
 // what every call that reads or writes the device arrays starts with
 int kfdb_ready(orbfe_kfdb* db) {
-  int rc = kfdb_device(db);
-  if (!rc && db->stale) rc = kfdb_compact(db);
-  return rc;
+  HIPCHK(arena_stream(&db->arena, db->device));
+  return db->stale ? kfdb_compact(db) : ORBFE_OK;
 }
 
 // a BowVector as the caller gives it: ids ascending and unique, all below n_words
@@ -153,15 +131,14 @@ extern "C" int orbfe_kfdb_create(int n_words, int device, orbfe_kfdb** out) {
 
 extern "C" void orbfe_kfdb_destroy(orbfe_kfdb* db) {
   if (!db) return;
-  if (db->ready) {
+  if (db->arena.stream) {
     (void)hipSetDevice(db->device);
-    (void)hipStreamSynchronize(db->stream);
+    (void)hipStreamSynchronize(db->arena.stream);
     slab_put(&db->dWords);
     slab_put(&db->dValues);
     slab_put(&db->dSlots);
-    (void)hipStreamDestroy(db->stream);
   }
-  delete db;
+  delete db;  // (the arena's end: the stream, then the buffers)
 }
 
 extern "C" int orbfe_kfdb_size(const orbfe_kfdb* db) {
@@ -185,11 +162,11 @@ extern "C" int orbfe_kfdb_add(orbfe_kfdb* db, int64_t kf_id, const uint32_t* wor
   if ((rc = slab_reserve(db, &db->dSlots, (nSlots + 1) * sizeof(KfdbSlot), nSlots * sizeof(KfdbSlot)))) return rc;
   const KfdbSlot rec = {(uint32_t)used, (uint32_t)n};
   if (n) {
-    HIPCHK(hipMemcpyAsync((uint32_t*)db->dWords.p + used, word_ids, (size_t)n * 4, hipMemcpyHostToDevice, db->stream));
-    HIPCHK(hipMemcpyAsync((double*)db->dValues.p + used, values, (size_t)n * 8, hipMemcpyHostToDevice, db->stream));
+    HIPCHK(hipMemcpyAsync((uint32_t*)db->dWords.p + used, word_ids, (size_t)n * 4, hipMemcpyHostToDevice, db->arena.stream));
+    HIPCHK(hipMemcpyAsync((double*)db->dValues.p + used, values, (size_t)n * 8, hipMemcpyHostToDevice, db->arena.stream));
   }
-  HIPCHK(hipMemcpyAsync((KfdbSlot*)db->dSlots.p + nSlots, &rec, sizeof rec, hipMemcpyHostToDevice, db->stream));
-  HIPCHK(hipStreamSynchronize(db->stream));
+  HIPCHK(hipMemcpyAsync((KfdbSlot*)db->dSlots.p + nSlots, &rec, sizeof rec, hipMemcpyHostToDevice, db->arena.stream));
+  HIPCHK(hipStreamSynchronize(db->arena.stream));
   // the device holds it: commit to the mirror
   db->hWords.insert(db->hWords.end(), word_ids, word_ids + n);
   db->hValues.insert(db->hValues.end(), values, values + n);
@@ -208,8 +185,8 @@ extern "C" int orbfe_kfdb_erase(orbfe_kfdb* db, int64_t kf_id) {
   if ((rc = kfdb_ready(db))) return rc;
   const int s = it->second;
   const KfdbSlot rec = {db->slots[(size_t)s].off, 0u};
-  HIPCHK(hipMemcpyAsync((KfdbSlot*)db->dSlots.p + s, &rec, sizeof rec, hipMemcpyHostToDevice, db->stream));
-  HIPCHK(hipStreamSynchronize(db->stream));
+  HIPCHK(hipMemcpyAsync((KfdbSlot*)db->dSlots.p + s, &rec, sizeof rec, hipMemcpyHostToDevice, db->arena.stream));
+  HIPCHK(hipStreamSynchronize(db->arena.stream));
   db->slots[(size_t)s].live = false;
   db->slotOf.erase(it);
   db->nLive--;
@@ -226,10 +203,6 @@ extern "C" int orbfe_kfdb_clear(orbfe_kfdb* db) {
   db->hWords.clear(); db->hValues.clear(); db->slots.clear(); db->slotOf.clear();
   db->nLive = 0;  // the slabs stay with the handle
   return ORBFE_OK;
-}
-
-namespace {
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 }
 
 extern "C" int orbfe_kfdb_query(orbfe_kfdb* db, int n_queries, const int32_t* q_offsets, const uint32_t* q_words,
@@ -266,52 +239,58 @@ extern "C" int orbfe_kfdb_query(orbfe_kfdb* db, int n_queries, const int32_t* q_
     for (int q = 0; q < Q; q++) count[q] = 0;
     return ORBFE_OK;
   }
-  const size_t N = db->slots.size(), cap = (size_t)capacity;
-  // upload block: qOff | exclOff | qWords | exclSlots | qValues     download block: nSurv | outSlot | outCommon | outScore
-  const size_t uOff = 0, uEx = align16(uOff + (Q + 1) * 4), uW = align16(uEx + (Q + 1) * 4), uXs = align16(uW + nq * 4),
-               uV = align16(uXs + nExcl * 4), upBytes = align16(uV + nq * 8);
-  const size_t oN = 0, oS = align16(oN + (size_t)Q * 4), oC = align16(oS + Q * cap * 4), oF = align16(oC + Q * cap * 4),
-               downBytes = align16(oF + Q * cap * 4);
-  const size_t wCommon = upBytes, wMin = wCommon + align16(Q * N * 4), wSurv = wMin + align16(Q * N * 4),
-               wOut = wSurv + align16(Q * N * 4);
-  // sized by the slot slab's capacity (>= N), so that the workspace doubles with the database instead of growing per key frame
-  const size_t slotCap = db->dSlots.cap / sizeof(KfdbSlot);
-  const size_t devBytes = upBytes + 3 * align16(Q * slotCap * 4) + downBytes;
-  if ((rc = ensure_work(db, devBytes, std::max(upBytes, downBytes)))) return rc;
-  uint8_t* h = db->pin;
-  uint8_t* d = db->work;
-  memcpy(h + uOff, q_offsets, (size_t)(Q + 1) * 4);
-  int32_t* hEx = (int32_t*)(h + uEx);
-  uint32_t* hXs = (uint32_t*)(h + uXs);
-  size_t nx = 0;
-  for (int q = 0; q < Q; q++) {  // ids -> slots; an id the database does not hold excludes nothing
-    hEx[q] = (int32_t)nx;
-    if (excl_offsets)
+  const size_t N = db->slots.size(), cap = (size_t)capacity, nQ = (size_t)Q;
+  // ids -> slots, packed in place (either array, or none: the count); an id the database does not hold excludes nothing
+  auto excluded = [&](int32_t* off, uint32_t* slots) {
+    int nx = 0;
+    for (int q = 0; q <= Q; q++) {
+      if (off) off[q] = nx;
+      if (q == Q || !excl_offsets) continue;
       for (int i = excl_offsets[q]; i < excl_offsets[q + 1]; i++) {
         auto it = db->slotOf.find(excl_ids[i]);
-        if (it != db->slotOf.end()) hXs[nx++] = (uint32_t)it->second;
+        if (it == db->slotOf.end()) continue;
+        if (slots) slots[nx] = (uint32_t)it->second;
+        nx++;
       }
-  }
-  hEx[Q] = (int32_t)nx;
-  if (nq) {
-    memcpy(h + uW, q_words, nq * 4);
-    memcpy(h + uV, q_values, nq * 8);
-  }
-  HIPCHK(hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, db->stream));
+    }
+    return nx;
+  };
+  Arena* ar = &db->arena;
   KfdbQueries p = {};
-  p.qOff = (const int32_t*)(d + uOff); p.qWords = (const uint32_t*)(d + uW); p.qValues = (const double*)(d + uV);
   p.maxWords = maxWords;
-  p.exclOff = (const int32_t*)(d + uEx); p.exclSlots = (const uint32_t*)(d + uXs); p.nExcl = (int)nx;
-  p.common = (uint32_t*)(d + wCommon); p.minWord = (uint32_t*)(d + wMin); p.surv = (uint32_t*)(d + wSurv);
-  p.nSurv = (int32_t*)(d + wOut + oN);
   p.capacity = capacity;
-  p.outSlot = (uint32_t*)(d + wOut + oS); p.outCommon = (int32_t*)(d + wOut + oC); p.outScore = (float*)(d + wOut + oF);
-  launch_kfdb_query(db->stream, store_of(db), p, Q);
+  int32_t *dOff, *dExOff;
+  uint32_t *dWords, *dExSlots;
+  double* dValues;
+  // (the three Q x slots work arrays grow per key frame; the arena grows by half and 1 MB, so a regrow stays rare)
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dOff, q_offsets, nQ + 1));
+    TRY(up_pack(a, &dExOff, nQ + 1, [&](int32_t* off) { p.nExcl = excluded(off, nullptr); }));
+    TRY(up(a, &dWords, q_words, nq));
+    TRY(up_pack(a, &dExSlots, nExcl, [&](uint32_t* slots) { excluded(nullptr, slots); }));
+    TRY(up(a, &dValues, q_values, nq));
+    open_span(a);
+    p.nSurv = carve<int32_t>(a, nQ);
+    p.outSlot = carve<uint32_t>(a, nQ * cap);
+    p.outCommon = carve<int32_t>(a, nQ * cap);
+    p.outScore = carve<float>(a, nQ * cap);
+    TRY(close_span(a));
+    p.common = carve<uint32_t>(a, nQ * N);
+    p.minWord = carve<uint32_t>(a, nQ * N);
+    p.surv = carve<uint32_t>(a, nQ * N);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(ar, db->device, stage));
+  p.qOff = dOff; p.qWords = dWords; p.qValues = dValues;
+  p.exclOff = dExOff; p.exclSlots = dExSlots;
+  HIPCHK(flush(ar));
+  launch_kfdb_query(ar->stream, store_of(db), p, Q);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h, d + wOut, downBytes, hipMemcpyDeviceToHost, db->stream));
-  HIPCHK(hipStreamSynchronize(db->stream));
-  const int32_t* ns = (const int32_t*)(h + oN);
-  const uint32_t* os = (const uint32_t*)(h + oS);
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  const int32_t *ns = mirror_of(ar, p.nSurv), *hCommon = mirror_of(ar, p.outCommon);
+  const uint32_t* os = mirror_of(ar, p.outSlot);
+  const float* hScore = mirror_of(ar, p.outScore);
   bool over = false;
   for (int q = 0; q < Q; q++) {
     count[q] = ns[q];
@@ -322,8 +301,8 @@ extern "C" int orbfe_kfdb_query(orbfe_kfdb* db, int n_queries, const int32_t* q_
       kf_id[q * cap + i] = s < N ? db->slots[s].id : -1;
     }
     if (m) {
-      memcpy(n_common + q * cap, h + oC + q * cap * 4, m * 4);
-      memcpy(score + q * cap, h + oF + q * cap * 4, m * 4);
+      memcpy(n_common + q * cap, hCommon + q * cap, m * 4);
+      memcpy(score + q * cap, hScore + q * cap, m * 4);
     }
   }
   if (over) return fail(ORBFE_ERR_CAPACITY, "kfdb_query: a query has more scored key frames than `capacity` (see count[])");
@@ -346,27 +325,30 @@ extern "C" int orbfe_kfdb_score(orbfe_kfdb* db, const uint32_t* q_words, const d
   }
   int rc;
   if ((rc = kfdb_ready(db))) return rc;
-  const size_t uOff = 0, uW = 16, uS = align16(uW + (size_t)n * 4), uV = align16(uS + (size_t)n_ids * 4),
-               upBytes = align16(uV + (size_t)n * 8), downBytes = (size_t)n_ids * 8;
-  if ((rc = ensure_work(db, upBytes + downBytes, std::max(upBytes, downBytes)))) return rc;
-  uint8_t* h = db->pin;
-  uint8_t* d = db->work;
+  Arena* ar = &db->arena;
   const int32_t off[2] = {0, n};
-  memcpy(h + uOff, off, sizeof off);
-  if (n) {
-    memcpy(h + uW, q_words, (size_t)n * 4);
-    memcpy(h + uV, q_values, (size_t)n * 8);
-  }
-  memcpy(h + uS, slotIds.data(), (size_t)n_ids * 4);
-  HIPCHK(hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, db->stream));
+  int32_t* dOff;
+  uint32_t *dWords, *dSlotIds;
+  double *dValues, *dScores;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dOff, off, 2));
+    TRY(up(a, &dWords, q_words, (size_t)n));
+    TRY(up(a, &dSlotIds, slotIds.data(), (size_t)n_ids));
+    TRY(up(a, &dValues, q_values, (size_t)n));
+    open_span(a);
+    dScores = carve<double>(a, (size_t)n_ids);
+    return close_span(a);
+  };
+  HIPCHK(arena_stage(ar, db->device, stage));
+  HIPCHK(flush(ar));
   KfdbQueries p = {};
-  p.qOff = (const int32_t*)(d + uOff); p.qWords = (const uint32_t*)(d + uW); p.qValues = (const double*)(d + uV);
+  p.qOff = dOff; p.qWords = dWords; p.qValues = dValues;
   p.maxWords = n;
-  launch_kfdb_score(db->stream, store_of(db), p, (const uint32_t*)(d + uS), n_ids, (double*)(d + upBytes));
+  launch_kfdb_score(ar->stream, store_of(db), p, dSlotIds, n_ids, dScores);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h, d + upBytes, downBytes, hipMemcpyDeviceToHost, db->stream));
-  HIPCHK(hipStreamSynchronize(db->stream));
-  memcpy(scores, h, downBytes);
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  memcpy(scores, mirror_of(ar, dScores), (size_t)n_ids * 8);
   return ORBFE_OK;
 }
 

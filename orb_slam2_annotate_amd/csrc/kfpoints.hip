@@ -33,42 +33,43 @@ constexpr size_t kUnionMaxFirst = (size_t)1 << 26, kUnionMaxBlocks = (size_t)1 <
 // up to this many bytes the counts and the lists come back in one copy; above, the counts first and then the filled part
 constexpr size_t kUnionOneCopyBytes = (size_t)256 << 10;
 
-size_t al(size_t x) { return obs_al(x); }
-
 // the marked key-frame rows onto the device; the marks are dropped only when everything has arrived
 int kf_flush(orbfe_obsgraph* g) {
   ObsGraphMirror& h = g->h;
+  Arena* ar = &g->arena;
   const size_t w = (size_t)h.kfRowWidth;
   const size_t perRow = 12 + w * 4;
   const size_t rowsPerChunk = std::max<size_t>(1, kObsFlushChunkBytes / perRow);
   for (size_t at = 0; at < h.dirtyKfRows.size(); at += rowsPerChunk) {
     const size_t n = std::min(rowsPerChunk, h.dirtyKfRows.size() - at);
-    const size_t oKf = 0, oLen = al(oKf + n * 4), oRowOf = al(oLen + n * 4), oRows = al(oRowOf + n * 4);
+    const int32_t* marked = h.dirtyKfRows.data() + at;
     size_t nRows = 0;
-    for (size_t i = 0; i < n; i++) nRows += !h.kfRows[(size_t)h.dirtyKfRows[at + i]].empty();
-    const size_t bytes = al(oRows + nRows * w * 4);
-    if (int rc = obs_ensure_work(g, bytes, bytes)) return rc;
-    uint8_t* p = g->pin;
-    uint8_t* d = g->work;
-    int32_t *hKf = (int32_t*)(p + oKf), *hLen = (int32_t*)(p + oLen), *hRowOf = (int32_t*)(p + oRowOf), *hRows = (int32_t*)(p + oRows);
-    size_t r = 0;
-    for (size_t i = 0; i < n; i++) {
-      const int32_t k = h.dirtyKfRows[at + i];
-      const std::vector<int32_t>& row = h.kfRows[(size_t)k];
-      hKf[i] = k;
-      hLen[i] = (int32_t)row.size();
-      hRowOf[i] = row.empty() ? -1 : (int32_t)r;
-      if (!row.empty()) {
-        std::memset(hRows + r * w, 0xff, w * 4);
-        std::memcpy(hRows + r * w, row.data(), row.size() * 4);
-        r++;
-      }
-    }
-    HIPCHK(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, g->stream));
-    launch_kf_scatter(g->stream, g->kd, (int)n, (const int32_t*)(d + oKf), (const int32_t*)(d + oLen), (const int32_t*)(d + oRowOf),
-                      (const int32_t*)(d + oRows));
+    for (size_t i = 0; i < n; i++) nRows += !h.kfRows[(size_t)marked[i]].empty();
+    int32_t *dKf, *dLen, *dRowOf, *dRows;
+    auto stage = [&](Arena* a) -> hipError_t {
+      TRY(up(a, &dKf, marked, n));
+      TRY(up_pack(a, &dLen, n, [&](int32_t* len) {
+        for (size_t i = 0; i < n; i++) len[i] = (int32_t)h.kfRows[(size_t)marked[i]].size();
+      }));
+      TRY(up_pack(a, &dRowOf, n, [&](int32_t* rowOf) {
+        int32_t r = 0;
+        for (size_t i = 0; i < n; i++) rowOf[i] = h.kfRows[(size_t)marked[i]].empty() ? -1 : r++;
+      }));
+      return up_pack(a, &dRows, nRows * w, [&](int32_t* rows) {  // the rows that hold something, each padded with -1
+        for (size_t i = 0; i < n; i++) {
+          const std::vector<int32_t>& row = h.kfRows[(size_t)marked[i]];
+          if (row.empty()) continue;
+          std::memset(rows, 0xff, w * 4);
+          std::memcpy(rows, row.data(), row.size() * 4);
+          rows += w;
+        }
+      });
+    };
+    HIPCHK(arena_stage(ar, g->device, stage));
+    HIPCHK(flush(ar));
+    launch_kf_scatter(ar->stream, g->kd, (int)n, dKf, dLen, dRowOf, dRows);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(g->stream));  // the staging block is reused by the next chunk
+    HIPCHK(hipStreamSynchronize(ar->stream));  // the arena is begun anew by the next chunk
   }
   h.kf_rows_flushed();
   return ORBFE_OK;
@@ -80,20 +81,26 @@ int kf_ready(orbfe_obsgraph* g) {
   if (int rc = obs_ready(g)) return rc;
   ObsGraphMirror& h = g->h;
   if (!g->kfTable.p) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };  // each of the slab's two arrays starts a line
     const size_t oLen = al((size_t)h.kfCap * h.kfRowWidth * 4), total = oLen + al((size_t)h.kfCap * 4);
-    if (int rc = obs_ensure_work(g, 0, (size_t)h.kfCap * 4)) return rc;
+    Arena* ar = &g->arena;
+    int32_t* lens;
+    auto stage = [&](Arena* a) -> hipError_t {
+      return up_pack(a, &lens, (size_t)h.kfCap, [&](int32_t* len) {
+        for (int k = 0; k < h.kfCap; k++) len[k] = (int32_t)h.kfRows[(size_t)k].size();
+      });
+    };
+    HIPCHK(arena_stage(ar, g->device, stage));
     Slab s;
     HIPCHK(slab_get(g->device, total, &s));
-    uint8_t* b = static_cast<uint8_t*>(s.p);
-    uint8_t* p = g->pin;
-    int32_t* lens = (int32_t*)p;
-    for (int k = 0; k < h.kfCap; k++) lens[k] = (int32_t)h.kfRows[(size_t)k].size();
-    hipError_t e = hipMemcpyAsync(b + oLen, lens, (size_t)h.kfCap * 4, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    int32_t* rows = static_cast<int32_t*>(s.p);
+    int32_t* len = rows + oLen / 4;
+    hipError_t e = send(ar, len, lens, (size_t)h.kfCap);
+    if (e == hipSuccess) e = hipStreamSynchronize(ar->stream);
     if (e != hipSuccess) { slab_put(&s); HIPCHK(e); }
     g->kfTable = s;
-    g->kd.rows = reinterpret_cast<int32_t*>(b);
-    g->kd.len = reinterpret_cast<int32_t*>(b + oLen);
+    g->kd.rows = rows;
+    g->kd.len = len;
     g->kd.width = h.kfRowWidth;
     h.mark_kf_rows_held();
   }
@@ -105,48 +112,53 @@ int union_group(orbfe_obsgraph* g, int q0, int q1, const int32_t* off, const int
                 int capDev, int32_t* slot_out, int32_t* count, bool* over) {
   const size_t Q = (size_t)(q1 - q0), nk = (size_t)(off[q1] - off[q0]), nBlocks = (size_t)(blkOff[(size_t)q1] - blkOff[(size_t)q0]);
   const size_t cap = (size_t)capDev, P = (size_t)g->h.pointCap;
-  const size_t uOff = 0, uBlk = al(uOff + (Q + 1) * 4), uKf = al(uBlk + (Q + 1) * 4), upBytes = al(uKf + nk * 4);
-  const size_t wFirst = upBytes, wMask = al(wFirst + Q * P * 4), wCount = al(wMask + nBlocks * kKfChunksPerBlock * 8),
-               wDown = al(wCount + nBlocks * 4);
-  const size_t oCount = 0, oOut = al(Q * 4), downBytes = oOut + al(Q * cap * 4);
-  if (int rc = obs_ensure_work(g, wDown + downBytes, std::max(upBytes, downBytes))) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  int32_t *hOff = (int32_t*)(p + uOff), *hBlk = (int32_t*)(p + uBlk);
-  for (size_t q = 0; q <= Q; q++) {
-    hOff[q] = off[(size_t)q0 + q] - off[q0];
-    hBlk[q] = (int32_t)(blkOff[(size_t)q0 + q] - blkOff[(size_t)q0]);
-  }
-  if (nk) std::memcpy(p + uKf, kfs + off[q0], nk * 4);
-  HIPCHK(hipMemcpyAsync(d, p, upBytes, hipMemcpyHostToDevice, g->stream));
-  uint8_t* o = d + wDown;
+  Arena* ar = &g->arena;
+  int32_t *dOff, *dBlk, *dKf;
   KfUnionArgs a;
   a.nQueries = (int)Q; a.nBlocks = (int)nBlocks; a.capacity = capDev;
-  a.qOff = (const int32_t*)(d + uOff); a.qKf = (const int32_t*)(d + uKf); a.blkOff = (const int32_t*)(d + uBlk);
-  a.first = (int32_t*)(d + wFirst); a.keepMask = (unsigned long long*)(d + wMask); a.blockCount = (int32_t*)(d + wCount);
-  a.out = (int32_t*)(o + oOut); a.count = (int32_t*)(o + oCount);
-  launch_kf_union(g->stream, g->d, g->kd, a);
+  auto stage = [&](Arena* s) -> hipError_t {
+    TRY(up_pack(s, &dOff, Q + 1, [&](int32_t* o) {
+      for (size_t q = 0; q <= Q; q++) o[q] = off[(size_t)q0 + q] - off[q0];
+    }));
+    TRY(up_pack(s, &dBlk, Q + 1, [&](int32_t* o) {
+      for (size_t q = 0; q <= Q; q++) o[q] = (int32_t)(blkOff[(size_t)q0 + q] - blkOff[(size_t)q0]);
+    }));
+    TRY(up(s, &dKf, kfs + off[q0], nk));
+    open_span(s);
+    a.count = carve<int32_t>(s, Q);
+    a.out = carve<int32_t>(s, Q * cap);
+    TRY(close_span(s));
+    a.first = carve<int32_t>(s, Q * P);
+    a.keepMask = carve<unsigned long long>(s, nBlocks * kKfChunksPerBlock);
+    a.blockCount = carve<int32_t>(s, nBlocks);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  a.qOff = dOff; a.qKf = dKf; a.blkOff = dBlk;
+  HIPCHK(flush(ar));
+  launch_kf_union(ar->stream, g->d, g->kd, a);
   HIPCHK(hipGetLastError());
-  const int32_t* ns = (const int32_t*)(p + oCount);
-  if (downBytes <= kUnionOneCopyBytes) {
-    HIPCHK(hipMemcpyAsync(p, o, downBytes, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
+  if (span_bytes(ar) <= kUnionOneCopyBytes) {
+    HIPCHK(down_span(ar));
+    HIPCHK(hipStreamSynchronize(ar->stream));
   } else {
-    HIPCHK(hipMemcpyAsync(p, o, Q * 4, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
+    HIPCHK(down_range(ar, a.count, a.count + Q));
+    HIPCHK(hipStreamSynchronize(ar->stream));
+    const int32_t* ns = mirror_of(ar, a.count);
     size_t filled = 0;  // entries up to the end of the last list that holds something
     for (size_t q = 0; q < Q; q++)
       if (ns[q] > 0) filled = q * cap + std::min((size_t)ns[q], cap);
     if (filled) {
-      HIPCHK(hipMemcpyAsync(p + oOut, o + oOut, filled * 4, hipMemcpyDeviceToHost, g->stream));
-      HIPCHK(hipStreamSynchronize(g->stream));
+      HIPCHK(down_range(ar, a.out, a.out + filled));
+      HIPCHK(hipStreamSynchronize(ar->stream));
     }
   }
+  const int32_t *ns = mirror_of(ar, a.count), *lists = mirror_of(ar, a.out);
   for (size_t q = 0; q < Q; q++) {
     count[(size_t)q0 + q] = ns[q];
     const size_t have = (size_t)std::max(ns[q], 0), m = std::min(have, cap);  // a count never exceeds point_capacity
     *over |= have > (size_t)capacity;
-    if (m) std::memcpy(slot_out + ((size_t)q0 + q) * (size_t)capacity, p + oOut + q * cap * 4, m * 4);
+    if (m) std::memcpy(slot_out + ((size_t)q0 + q) * (size_t)capacity, lists + q * cap, m * 4);
   }
   return ORBFE_OK;
 }
@@ -198,16 +210,16 @@ extern "C" int orbfe_obsgraph_get_keyframe_points(orbfe_obsgraph* g, int from_de
     return ORBFE_OK;
   }
   if (int rc = kf_ready(g)) return rc;
-  const size_t oRow = al(4), bytes = oRow + w * 4;
-  if (int rc = obs_ensure_work(g, 0, bytes)) return rc;
-  uint8_t* p = g->pin;
-  HIPCHK(hipMemcpyAsync(p, g->kd.len + kf_slot, 4, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipMemcpyAsync(p + oRow, g->kd.rows + (size_t)kf_slot * w, w * 4, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));
-  int32_t len;
-  std::memcpy(&len, p, 4);
+  Arena* ar = &g->arena;
+  int32_t *hLen, *hRow;
+  auto stage = [&](Arena* a) { open_span(a); hLen = carve<int32_t>(a, 1); hRow = carve<int32_t>(a, w); return close_span(a); };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  HIPCHK(fetch(ar, hLen, g->kd.len + kf_slot, 1));
+  HIPCHK(fetch(ar, hRow, g->kd.rows + (size_t)kf_slot * w, w));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  const int32_t len = *mirror_of(ar, hLen);
   const int live = std::min(std::max(len, 0), (int)w);
-  if (live) std::memcpy(slots, p + oRow, (size_t)live * 4);
+  if (live) std::memcpy(slots, mirror_of(ar, hRow), (size_t)live * 4);
   *n = len;
   return ORBFE_OK;
 }
@@ -254,16 +266,20 @@ extern "C" int orbfe_obsgraph_tracked_points(orbfe_obsgraph* g, int n_kf, const 
   if (!kf_slot || !count) return obs_invalid(fn, "NULL argument");
   if (const char* e = g->h.check_kf_list(n_kf, kf_slot)) return obs_invalid(fn, e);
   if (int rc = kf_ready(g)) return rc;
-  const size_t bytes = al((size_t)n_kf * 4);
-  if (int rc = obs_ensure_work(g, 2 * bytes, bytes)) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  std::memcpy(p, kf_slot, (size_t)n_kf * 4);
-  HIPCHK(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, g->stream));
-  launch_kf_tracked(g->stream, g->d, g->kd, n_kf, (const int32_t*)d, min_obs, (int32_t*)(d + bytes));
+  Arena* ar = &g->arena;
+  int32_t *dKf, *dCount;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dKf, kf_slot, (size_t)n_kf));
+    open_span(a);
+    dCount = carve<int32_t>(a, (size_t)n_kf);
+    return close_span(a);
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  HIPCHK(flush(ar));
+  launch_kf_tracked(ar->stream, g->d, g->kd, n_kf, dKf, min_obs, dCount);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p, d + bytes, bytes, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));
-  std::memcpy(count, p, (size_t)n_kf * 4);
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  std::memcpy(count, mirror_of(ar, dCount), (size_t)n_kf * 4);
   return ORBFE_OK;
 }

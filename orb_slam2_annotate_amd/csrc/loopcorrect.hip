@@ -26,8 +26,6 @@ using namespace orbfe;
 
 namespace {
 
-size_t al(size_t x) { return obs_al(x); }
-
 bool distinct(int n, const int32_t* v) {
   std::vector<int32_t> sorted(v, v + n);
   std::sort(sorted.begin(), sorted.end());
@@ -45,7 +43,7 @@ struct RankScope {
   int ready() {
     if (g->kfRank.p) return ORBFE_OK;
     if (int rc = g->kfRank.alloc((size_t)g->h.kfCap)) return rc;
-    HIPCHK(hipMemsetAsync(g->kfRank.p, 0xff, (size_t)g->h.kfCap * 4, g->stream));
+    HIPCHK(hipMemsetAsync(g->kfRank.p, 0xff, (size_t)g->h.kfCap * 4, g->arena.stream));
     return ORBFE_OK;
   }
 };
@@ -131,63 +129,68 @@ extern "C" int orbfe_correct_loop_mappoints(orbfe_obsgraph* g, orbfe_mappoints* 
   if (int rc = obs_kf_ready(g)) return rc;
   const size_t w = (size_t)h.kfRowWidth, nK = (size_t)K, L = (size_t)n_levels, nS = (size_t)n_skip;
   const size_t span = nK * w, nBlocks = (span + kLcBlockEntries - 1) / kLcBlockEntries, nOut = std::min(span, (size_t)h.pointCap);
-  const size_t uKf = 0, uFirst = al(uKf + nK * 4), uCor = al(uFirst + nK * 4), uNon = al(uCor + nK * 64), uOw = al(uNon + nK * 64),
-               uScale = al(uOw + nK * 12), uSkip = al(uScale + L * 4), upBytes = al(uSkip + nS * 4);
-  const size_t wFirstPt = upBytes, wMask = al(wFirstPt + (size_t)h.pointCap * 4), wBlock = al(wMask + nBlocks * kLcChunksPerBlock * 8),
-               wDown = al(wBlock + nBlocks * 4);
-  const size_t oCount = 0, oSlot = al(4), oRef = al(oSlot + nOut * 4), oValid = al(oRef + nOut * 4), downBytes = al(oValid + nOut);
-  if (int rc = obs_ensure_work(g, wDown + downBytes, std::max(upBytes, downBytes))) return rc;
-  RankScope ranks(g);
-  if (int rc = ranks.ready()) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  std::memcpy(p + uKf, kf_slot, nK * 4);
-  std::memcpy(p + uFirst, firstOf.data(), nK * 4);
-  std::memcpy(p + uCor, corrected, nK * 64);
-  std::memcpy(p + uNon, noncorrected, nK * 64);
-  std::memcpy(p + uOw, Ow_corrected, nK * 12);
-  std::memcpy(p + uScale, scale_factors, L * 4);
-  if (nS) std::memcpy(p + uSkip, skip_slot, nS * 4);
-  HIPCHK(hipMemcpyAsync(d, p, upBytes, hipMemcpyHostToDevice, g->stream));
-  uint8_t* o = d + wDown;
+  Arena* ar = &g->arena;
   LoopCorrectArgs a;
   a.K = K; a.nBlocks = (int)nBlocks; a.nSkip = n_skip; a.nLevels = n_levels;
-  a.kfSlot = (const int32_t*)(d + uKf); a.firstOf = (const int32_t*)(d + uFirst); a.skip = (const int32_t*)(d + uSkip);
-  a.corrected = (const double*)(d + uCor); a.noncorrected = (const double*)(d + uNon);
-  a.owCorrected = (const float*)(d + uOw); a.scale = (const float*)(d + uScale);
-  a.rank = g->kfRank.p; a.first = (int32_t*)(d + wFirstPt);
-  a.keepMask = (unsigned long long*)(d + wMask); a.blockCount = (int32_t*)(d + wBlock); a.count = (int32_t*)(o + oCount);
-  a.slotOut = (int32_t*)(o + oSlot); a.refOut = (int32_t*)(o + oRef); a.validOut = o + oValid;
-  launch_lc_claim(g->stream, g->d, g->kd, a);
+  int32_t *dKf, *dFirstOf, *dSkip;
+  double *dCor, *dNon;
+  float *dOw, *dScale;
+  auto stage = [&](Arena* s) -> hipError_t {
+    TRY(up(s, &dKf, kf_slot, nK));
+    TRY(up(s, &dFirstOf, firstOf.data(), nK));
+    TRY(up(s, &dCor, corrected, nK * 8));
+    TRY(up(s, &dNon, noncorrected, nK * 8));
+    TRY(up(s, &dOw, Ow_corrected, nK * 3));
+    TRY(up(s, &dScale, scale_factors, L));
+    TRY(up(s, &dSkip, skip_slot, nS));
+    open_span(s);  // what may come back; how much of it does is decided by the count
+    a.count = carve<int32_t>(s, 1);
+    a.slotOut = carve<int32_t>(s, nOut);
+    a.refOut = carve<int32_t>(s, nOut);
+    a.validOut = carve<uint8_t>(s, nOut);
+    TRY(close_span(s));
+    a.first = carve<int32_t>(s, (size_t)h.pointCap);
+    a.keepMask = carve<unsigned long long>(s, nBlocks * kLcChunksPerBlock);
+    a.blockCount = carve<int32_t>(s, nBlocks);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  RankScope ranks(g);
+  if (int rc = ranks.ready()) return rc;
+  a.kfSlot = dKf; a.firstOf = dFirstOf; a.skip = dSkip;
+  a.corrected = dCor; a.noncorrected = dNon;
+  a.owCorrected = dOw; a.scale = dScale;
+  a.rank = g->kfRank.p;
+  HIPCHK(flush(ar));
+  launch_lc_claim(ar->stream, g->d, g->kd, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p, o + oCount, 4, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));  // count first, mutate after
-  int32_t n;
-  std::memcpy(&n, p, 4);
+  HIPCHK(down_range(ar, a.count, a.count + 1));
+  HIPCHK(hipStreamSynchronize(ar->stream));  // count first, mutate after
+  const int32_t n = *mirror_of(ar, a.count);
   *count = n;
   if (n < 0 || (size_t)n > nOut) return fail(ORBFE_ERR_HIP, std::string(fn) + ": the device returned an impossible count");
   if (n > capacity) {
-    launch_lc_release(g->stream, a);
+    launch_lc_release(ar->stream, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(g->stream));
+    HIPCHK(hipStreamSynchronize(ar->stream));
     ranks.done = true;
     return fail(ORBFE_ERR_CAPACITY, std::string(fn) + ": more points are claimed than `capacity` (see *count); nothing was changed");
   }
-  launch_lc_apply(g->stream, g->d, g->kd, *lock.table, a, n);
-  launch_lc_release(g->stream, a);
+  launch_lc_apply(ar->stream, g->d, g->kd, *lock.table, a, n);
+  launch_lc_release(ar->stream, a);
   HIPCHK(hipGetLastError());
   const size_t cnt = (size_t)n;
   if (cnt) {
-    HIPCHK(hipMemcpyAsync(p + oSlot, o + oSlot, cnt * 4, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(p + oRef, o + oRef, cnt * 4, hipMemcpyDeviceToHost, g->stream));
-    if (valid_out) HIPCHK(hipMemcpyAsync(p + oValid, o + oValid, cnt, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(down_range(ar, a.slotOut, a.slotOut + cnt));
+    HIPCHK(down_range(ar, a.refOut, a.refOut + cnt));
+    if (valid_out) HIPCHK(down_range(ar, a.validOut, a.validOut + cnt));
   }
-  HIPCHK(hipStreamSynchronize(g->stream));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   ranks.done = true;
   if (cnt) {
-    std::memcpy(slot_out, p + oSlot, cnt * 4);
-    std::memcpy(ref_out, p + oRef, cnt * 4);
-    if (valid_out) std::memcpy(valid_out, p + oValid, cnt);
+    std::memcpy(slot_out, mirror_of(ar, a.slotOut), cnt * 4);
+    std::memcpy(ref_out, mirror_of(ar, a.refOut), cnt * 4);
+    if (valid_out) std::memcpy(valid_out, mirror_of(ar, a.validOut), cnt);
   }
   // the device holds the new centres already: the mirror follows without marking the key frames
   for (int k = 0; k < K; k++) {
@@ -221,33 +224,36 @@ extern "C" int orbfe_gba_update_mappoints(orbfe_obsgraph* g, orbfe_mappoints* mp
   if (lock.rc) return lock.rc;
   if (int rc = obs_ready(g)) return rc;
   const size_t nP = (size_t)n, nM = (size_t)m;
-  const size_t uSlot = 0, uIn = al(uSlot + nP * 4), uPos = al(uIn + nP), uKf = al(uPos + nP * 12), uReached = al(uKf + nM * 4),
-               uBef = al(uReached + nM), uNew = al(uBef + nM * 64), upBytes = al(uNew + nM * 64), downBytes = al(nP);
-  if (int rc = obs_ensure_work(g, upBytes + downBytes, std::max(upBytes, downBytes))) return rc;
-  RankScope ranks(g);
-  if (int rc = ranks.ready()) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  std::memcpy(p + uSlot, slot, nP * 4);
-  std::memcpy(p + uIn, in_gba, nP);
-  std::memcpy(p + uPos, pos_gba, nP * 12);
-  if (nM) {
-    std::memcpy(p + uKf, kf_slot, nM * 4);
-    std::memcpy(p + uReached, reached, nM);
-    std::memcpy(p + uBef, Tcw_bef, nM * 64);
-    std::memcpy(p + uNew, Twc_new, nM * 64);
-  }
-  HIPCHK(hipMemcpyAsync(d, p, upBytes, hipMemcpyHostToDevice, g->stream));
+  Arena* ar = &g->arena;
   GbaUpdateArgs a;
   a.n = n; a.m = m;
-  a.slot = (const int32_t*)(d + uSlot); a.inGba = d + uIn; a.posGba = (const float*)(d + uPos);
-  a.kfSlot = (const int32_t*)(d + uKf); a.reached = d + uReached; a.TcwBef = (const float*)(d + uBef); a.TwcNew = (const float*)(d + uNew);
-  a.index = g->kfRank.p; a.moved = d + upBytes;
-  launch_gba_update(g->stream, g->d, *lock.table, a);
+  int32_t *dSlot, *dKf;
+  uint8_t *dIn, *dReached;
+  float *dPos, *dBef, *dNew;
+  auto stage = [&](Arena* s) -> hipError_t {
+    TRY(up(s, &dSlot, slot, nP));
+    TRY(up(s, &dIn, in_gba, nP));
+    TRY(up(s, &dPos, pos_gba, nP * 3));
+    TRY(up(s, &dKf, kf_slot, nM));
+    TRY(up(s, &dReached, reached, nM));
+    TRY(up(s, &dBef, Tcw_bef, nM * 16));
+    TRY(up(s, &dNew, Twc_new, nM * 16));
+    open_span(s);
+    a.moved = carve<uint8_t>(s, nP);
+    return close_span(s);
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  RankScope ranks(g);
+  if (int rc = ranks.ready()) return rc;
+  a.slot = dSlot; a.inGba = dIn; a.posGba = dPos;
+  a.kfSlot = dKf; a.reached = dReached; a.TcwBef = dBef; a.TwcNew = dNew;
+  a.index = g->kfRank.p;
+  HIPCHK(flush(ar));
+  launch_gba_update(ar->stream, g->d, *lock.table, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p, d + upBytes, nP, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   ranks.done = true;
-  std::memcpy(moved, p, nP);
+  std::memcpy(moved, mirror_of(ar, a.moved), nP);
   return ORBFE_OK;
 }

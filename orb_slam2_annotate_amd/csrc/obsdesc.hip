@@ -30,13 +30,11 @@ using namespace orbfe;
 
 namespace {
 
-size_t al(size_t x) { return obs_al(x); }
-
 const char* kNotEnabled = "key-frame descriptors are not enabled (orbfe_obsgraph_enable_keyframe_descriptors)";
 
 // the device, the stream and the descriptors' slab (the handle locked, the store enabled)
 int desc_ready(orbfe_obsgraph* g) {
-  if (int rc = obs_stream(g)) return rc;
+  HIPCHK(arena_stream(&g->arena, g->device));
   if (!g->descTable.p) {
     HIPCHK(slab_get(g->device, (size_t)g->h.kfCap * (size_t)g->h.kfDescWidth * 32, &g->descTable));
     g->dd.desc = static_cast<const uint8_t*>(g->descTable.p);
@@ -55,28 +53,40 @@ int distinctive_run(orbfe_obsgraph* g, int n, const int32_t* slot, int32_t* best
   const size_t q = (size_t)n;
   int maxCount = 0;
   for (int i = 0; i < n; i++) maxCount = std::max(maxCount, (int)g->h.meta[(size_t)slot[i]].count);
-  const size_t upBytes = al(q * 4);
-  const size_t oValid = 0, oKf = al(oValid + q), oIdx = al(oKf + q * 4), oDesc = al(oIdx + q * 4), all = al(oDesc + (table ? 0 : q * 32));
-  const size_t downBytes = (!table && desc) ? all : ((best_kf_slot || best_idx) ? oDesc : oKf);
-  if (int rc = obs_ensure_work(g, upBytes + all, std::max(upBytes, downBytes))) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  std::memcpy(p, slot, q * 4);
-  HIPCHK(hipMemcpyAsync(d, p, upBytes, hipMemcpyHostToDevice, g->stream));
-  uint8_t* o = d + upBytes;
-  launch_obs_distinctive(g->stream, g->d, g->dd, n, (const int32_t*)d, maxCount, (int32_t*)(o + oKf), (int32_t*)(o + oIdx), o + oDesc,
-                         o + oValid, table);
+  // what comes back: valid always; the winners and the bytes where the caller asked (the winners lie between the two, so
+  // they travel with the bytes).  What the kernel writes and nobody asked for is carved behind the span.
+  const bool wantDesc = !table && desc, wantBest = best_kf_slot || best_idx || wantDesc;
+  Arena* ar = &g->arena;
+  int32_t *dSlot, *dKf = nullptr, *dIdx = nullptr;
+  uint8_t *dValid, *dDesc = nullptr;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dSlot, slot, q));
+    auto best = [&] { dKf = carve<int32_t>(a, q); dIdx = carve<int32_t>(a, q); };
+    open_span(a);
+    dValid = carve<uint8_t>(a, q);
+    if (wantBest) best();
+    if (wantDesc) dDesc = carve<uint8_t>(a, 32 * q);
+    TRY(close_span(a));
+    if (!wantBest) best();
+    if (!table && !desc) dDesc = carve<uint8_t>(a, 32 * q);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  HIPCHK(flush(ar));
+  launch_obs_distinctive(ar->stream, g->d, g->dd, n, dSlot, maxCount, dKf, dIdx, dDesc, dValid, table);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p, o, downBytes, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));
-  const uint8_t* v = p + oValid;
-  const int32_t *hk = (const int32_t*)(p + oKf), *hi = (const int32_t*)(p + oIdx);
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  const uint8_t* v = mirror_of(ar, dValid);
   std::memcpy(valid, v, q);
+  if (!wantBest) return ORBFE_OK;
+  const int32_t *hk = mirror_of(ar, dKf), *hi = mirror_of(ar, dIdx);
+  const uint8_t* hd = wantDesc ? mirror_of(ar, dDesc) : nullptr;
   for (size_t i = 0; i < q; i++) {  // valid = 0 writes nothing
     if (!v[i]) continue;
     if (best_kf_slot) best_kf_slot[i] = hk[i];
     if (best_idx) best_idx[i] = hi[i];
-    if (!table && desc) std::memcpy(desc + 32 * i, p + oDesc + 32 * i, 32);
+    if (wantDesc) std::memcpy(desc + 32 * i, hd + 32 * i, 32);
   }
   return ORBFE_OK;
 }
@@ -103,10 +113,11 @@ extern "C" int orbfe_obsgraph_set_keyframe_descriptors(orbfe_obsgraph* g, int kf
   if (int rc = desc_ready(g)) return rc;
   const size_t bytes = (size_t)n * 32;
   if (bytes) {
-    if (int rc = obs_ensure_work(g, 0, bytes)) return rc;
-    std::memcpy(g->pin, desc, bytes);
-    HIPCHK(hipMemcpyAsync(desc_row(g, kf_slot), g->pin, bytes, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
+    Arena* ar = &g->arena;
+    uint8_t* staged;
+    HIPCHK(arena_stage(ar, g->device, [&](Arena* a) { return up(a, &staged, desc, bytes); }));
+    HIPCHK(send(ar, desc_row(g, kf_slot), staged, bytes));
+    HIPCHK(hipStreamSynchronize(ar->stream));
   }
   g->h.descN[(size_t)kf_slot] = n;  // only now: a count always describes rows that have arrived
   return ORBFE_OK;
@@ -121,16 +132,11 @@ extern "C" int orbfe_obsgraph_set_keyframe_descriptors_frame(orbfe_obsgraph* g, 
   if (int rc = desc_ready(g)) return rc;
   const size_t bytes = (size_t)f->n * 32;
   if (bytes) {
-    // the copy reads the frame on the handle's stream: frame_use() orders a stream behind the frame's build, and the stream
-    // is all it reads of the arena it is given
+    // the copy reads the frame on the handle's stream: frame_use() orders the arena's stream behind the frame's build
     UnsettledScope unsettled;
-    Arena onHandle;
-    onHandle.stream = g->stream;
-    const hipError_t e = frame_use(&onHandle, f);
-    onHandle.stream = nullptr;
-    HIPCHK(e);
-    HIPCHK(hipMemcpyAsync(desc_row(g, kf_slot), f->ddesc, bytes, hipMemcpyDeviceToDevice, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));  // complete on return: the frame may be released
+    HIPCHK(frame_use(&g->arena, f));
+    HIPCHK(hipMemcpyAsync(desc_row(g, kf_slot), f->ddesc, bytes, hipMemcpyDeviceToDevice, g->arena.stream));
+    HIPCHK(hipStreamSynchronize(g->arena.stream));  // complete on return: the frame may be released
     frames_settle();
   }
   g->h.descN[(size_t)kf_slot] = f->n;
@@ -147,10 +153,13 @@ extern "C" int orbfe_obsgraph_get_keyframe_descriptors(orbfe_obsgraph* g, int kf
   if (n > 0) {  // (a count above 0 means the slab is there)
     const size_t bytes = (size_t)n * 32;
     if (int rc = desc_ready(g)) return rc;
-    if (int rc = obs_ensure_work(g, 0, bytes)) return rc;
-    HIPCHK(hipMemcpyAsync(g->pin, desc_row(g, kf_slot), bytes, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    std::memcpy(desc_out, g->pin, bytes);
+    Arena* ar = &g->arena;
+    uint8_t* got;
+    auto stage = [&](Arena* a) { open_span(a); got = carve<uint8_t>(a, bytes); return close_span(a); };
+    HIPCHK(arena_stage(ar, g->device, stage));
+    HIPCHK(fetch(ar, got, desc_row(g, kf_slot), bytes));
+    HIPCHK(hipStreamSynchronize(ar->stream));
+    std::memcpy(desc_out, mirror_of(ar, got), bytes);
   }
   *n_out = n;
   return ORBFE_OK;

@@ -31,95 +31,72 @@ static_assert(sizeof(orbfe_observation) == sizeof(ObsEntry), "orbfe_observation 
 
 namespace {
 
-constexpr size_t kFlushChunkBytes = kObsFlushChunkBytes;
-
-size_t al(size_t x) { return obs_al(x); }
-
-size_t grown(size_t have, size_t first, size_t need) {
-  size_t want = have ? have : first;
-  while (want < need) want *= 2;
-  return want;
-}
-
-int ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes) { return obs_ensure_work(g, devBytes, pinBytes); }
-
 // the marked rows and key frames onto the device; the marks are dropped only when everything has arrived
 int obs_flush(orbfe_obsgraph* g) {
   ObsGraphMirror& h = g->h;
+  Arena* ar = &g->arena;
   const size_t rw = (size_t)h.rowWidth;
   if (h.kfDirtyHi > h.kfDirtyLo)
     HIPCHK(hipMemcpyAsync(g->d.kf + h.kfDirtyLo, h.kfs.data() + h.kfDirtyLo, (size_t)(h.kfDirtyHi - h.kfDirtyLo) * sizeof(ObsKeyFrame),
-                          hipMemcpyHostToDevice, g->stream));
+                          hipMemcpyHostToDevice, ar->stream));
   const size_t perRow = 4 + sizeof(ObsPointMeta) + 4 + rw * sizeof(ObsEntry);
-  const size_t rowsPerChunk = std::max<size_t>(1, kFlushChunkBytes / perRow);
+  const size_t rowsPerChunk = std::max<size_t>(1, kObsFlushChunkBytes / perRow);
   for (size_t at = 0; at < h.dirtyRows.size(); at += rowsPerChunk) {
     const size_t n = std::min(rowsPerChunk, h.dirtyRows.size() - at);
-    const size_t oSlot = 0, oMeta = al(oSlot + n * 4), oRowOf = al(oMeta + n * sizeof(ObsPointMeta)), oRows = al(oRowOf + n * 4);
+    const int32_t* marked = h.dirtyRows.data() + at;
     size_t nRows = 0;
-    for (size_t i = 0; i < n; i++) nRows += !h.rows[(size_t)h.dirtyRows[at + i]].empty();
-    const size_t bytes = al(oRows + nRows * rw * sizeof(ObsEntry));
-    if (int rc = ensure_work(g, bytes, bytes)) return rc;
-    uint8_t* p = g->pin;
-    uint8_t* d = g->work;
-    int32_t* hSlot = (int32_t*)(p + oSlot);
-    ObsPointMeta* hMeta = (ObsPointMeta*)(p + oMeta);
-    int32_t* hRowOf = (int32_t*)(p + oRowOf);
-    ObsEntry* hRows = (ObsEntry*)(p + oRows);
-    size_t r = 0;
-    for (size_t i = 0; i < n; i++) {
-      const int32_t s = h.dirtyRows[at + i];
-      const std::vector<ObsEntry>& row = h.rows[(size_t)s];
-      hSlot[i] = s;
-      hMeta[i] = h.meta[(size_t)s];
-      hRowOf[i] = row.empty() ? -1 : (int32_t)r;
-      if (!row.empty()) {
-        std::memset(hRows + r * rw, 0, rw * sizeof(ObsEntry));
-        std::memcpy(hRows + r * rw, row.data(), row.size() * sizeof(ObsEntry));
-        r++;
-      }
-    }
-    HIPCHK(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, g->stream));
-    launch_obs_scatter(g->stream, g->d, (int)n, (const int32_t*)(d + oSlot), (const ObsPointMeta*)(d + oMeta),
-                       (const int32_t*)(d + oRowOf), (const ObsEntry*)(d + oRows));
+    for (size_t i = 0; i < n; i++) nRows += !h.rows[(size_t)marked[i]].empty();
+    int32_t *dSlot, *dRowOf;
+    ObsPointMeta* dMeta;
+    ObsEntry* dRows;
+    auto stage = [&](Arena* a) -> hipError_t {
+      TRY(up(a, &dSlot, marked, n));
+      TRY(up_pack(a, &dMeta, n, [&](ObsPointMeta* m) {
+        for (size_t i = 0; i < n; i++) m[i] = h.meta[(size_t)marked[i]];
+      }));
+      TRY(up_pack(a, &dRowOf, n, [&](int32_t* rowOf) {
+        int32_t r = 0;
+        for (size_t i = 0; i < n; i++) rowOf[i] = h.rows[(size_t)marked[i]].empty() ? -1 : r++;
+      }));
+      return up_pack(a, &dRows, nRows * rw, [&](ObsEntry* rows) {  // the rows that hold something, each padded with zeros
+        for (size_t i = 0; i < n; i++) {
+          const std::vector<ObsEntry>& row = h.rows[(size_t)marked[i]];
+          if (row.empty()) continue;
+          std::memset(rows, 0, rw * sizeof(ObsEntry));
+          std::memcpy(rows, row.data(), row.size() * sizeof(ObsEntry));
+          rows += rw;
+        }
+      });
+    };
+    HIPCHK(arena_stage(ar, g->device, stage));
+    HIPCHK(flush(ar));
+    launch_obs_scatter(ar->stream, g->d, (int)n, dSlot, dMeta, dRowOf, dRows);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(g->stream));  // the staging block is reused by the next chunk
+    HIPCHK(hipStreamSynchronize(ar->stream));  // the arena is begun anew by the next chunk
   }
-  HIPCHK(hipStreamSynchronize(g->stream));
+  HIPCHK(hipStreamSynchronize(ar->stream));
   h.flushed();
   return ORBFE_OK;
 }
 
 }  // namespace
 
-int orbfe::obs_ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes) {
-  const int rc = g->work.reserve(devBytes, grown(g->work.cap, (size_t)1 << 20, devBytes));
-  return rc ? rc : g->pin.reserve(pinBytes, grown(g->pin.cap, (size_t)1 << 16, pinBytes));
-}
-
 int orbfe::obs_invalid(const char* fn, const char* what) { return fail(ORBFE_ERR_INVALID, std::string(fn) + ": " + what); }
-
-int orbfe::obs_stream(orbfe_obsgraph* g) {
-  HIPCHK(hipSetDevice(g->device));
-  if (!g->ready) {
-    HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    g->ready = true;
-  }
-  return ORBFE_OK;
-}
 
 // what every call that reads the table on the device starts with (the handle locked)
 int orbfe::obs_ready(orbfe_obsgraph* g) {
-  if (int rc = obs_stream(g)) return rc;
+  HIPCHK(arena_stream(&g->arena, g->device));
   ObsGraphMirror& h = g->h;
   if (!g->table.p) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };  // each of the slab's three arrays starts a line
     const size_t oMeta = al((size_t)h.pointCap * h.rowWidth * sizeof(ObsEntry)), oKf = oMeta + al((size_t)h.pointCap * sizeof(ObsPointMeta)),
                  total = oKf + al((size_t)h.kfCap * sizeof(ObsKeyFrame));
     Slab s;
     HIPCHK(slab_get(g->device, total, &s));
     uint8_t* b = static_cast<uint8_t*>(s.p);
     // every record from the mirror; of the rows, the ones that hold something
-    hipError_t e = hipMemcpyAsync(b + oMeta, h.meta.data(), (size_t)h.pointCap * sizeof(ObsPointMeta), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    hipError_t e = hipMemcpyAsync(b + oMeta, h.meta.data(), (size_t)h.pointCap * sizeof(ObsPointMeta), hipMemcpyHostToDevice, g->arena.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->arena.stream);
     if (e != hipSuccess) { slab_put(&s); HIPCHK(e); }
     g->table = s;
     g->d.rows = reinterpret_cast<ObsEntry*>(b); g->d.meta = reinterpret_cast<ObsPointMeta*>(b + oMeta);
@@ -158,28 +135,34 @@ int invalid(const char* fn, const char* what) { return obs_invalid(fn, what); }
 // pos == NULL: the table form (positions from and results into *table)
 int normal_depth_run(orbfe_obsgraph* g, int n, const int32_t* slot, const float* pos, const float* scale, int n_levels, float* normal,
                      float* min_dist, float* max_dist, uint8_t* valid, const MapPointsDevice* table) {
-  const size_t q = (size_t)n, L = (size_t)n_levels;
-  const size_t uSlot = 0, uScale = al(uSlot + q * 4), uPos = al(uScale + L * 4), upBytes = al(uPos + (pos ? q * 12 : 0));
-  const size_t oValid = 0, oMin = al(oValid + q), oMax = al(oMin + q * 4), oNormal = al(oMax + q * 4),
-               downBytes = table ? al(q) : al(oNormal + q * 12);
-  if (int rc = ensure_work(g, upBytes + downBytes, std::max(upBytes, downBytes))) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  std::memcpy(p + uSlot, slot, q * 4);
-  std::memcpy(p + uScale, scale, L * 4);
-  if (pos) std::memcpy(p + uPos, pos, q * 12);
-  HIPCHK(hipMemcpyAsync(d, p, upBytes, hipMemcpyHostToDevice, g->stream));
-  uint8_t* o = d + upBytes;
-  launch_obs_normal_depth(g->stream, g->d, n, (const int32_t*)(d + uSlot), pos ? (const float*)(d + uPos) : nullptr,
-                          (const float*)(d + uScale), n_levels, (float*)(o + oNormal), (float*)(o + oMin), (float*)(o + oMax),
-                          o + oValid, table);
+  const size_t q = (size_t)n;
+  Arena* ar = &g->arena;
+  int32_t* dSlot;
+  float *dScale, *dPos = nullptr, *dNormal = nullptr, *dMin = nullptr, *dMax = nullptr;
+  uint8_t* dValid;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dSlot, slot, q));
+    TRY(up(a, &dScale, scale, (size_t)n_levels));
+    if (pos) TRY(up(a, &dPos, pos, 3 * q));
+    open_span(a);
+    dValid = carve<uint8_t>(a, q);
+    if (!table) {
+      dMin = carve<float>(a, q);
+      dMax = carve<float>(a, q);
+      dNormal = carve<float>(a, 3 * q);
+    }
+    return close_span(a);
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  HIPCHK(flush(ar));
+  launch_obs_normal_depth(ar->stream, g->d, n, dSlot, dPos, dScale, n_levels, dNormal, dMin, dMax, dValid, table);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p, o, downBytes, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));
-  const uint8_t* v = p + oValid;
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  const uint8_t* v = mirror_of(ar, dValid);
   if (valid) std::memcpy(valid, v, q);
   if (!table) {
-    const float *hn = (const float*)(p + oNormal), *lo = (const float*)(p + oMin), *hi = (const float*)(p + oMax);
+    const float *hn = mirror_of(ar, dNormal), *lo = mirror_of(ar, dMin), *hi = mirror_of(ar, dMax);
     for (size_t i = 0; i < q; i++) {  // valid = 0 writes nothing
       if (!v[i]) continue;
       normal[3 * i] = hn[3 * i]; normal[3 * i + 1] = hn[3 * i + 1]; normal[3 * i + 2] = hn[3 * i + 2];
@@ -216,15 +199,14 @@ extern "C" int orbfe_obsgraph_create(int device, int point_capacity, int kf_capa
 
 extern "C" void orbfe_obsgraph_destroy(orbfe_obsgraph* g) {
   if (!g) return;
-  if (g->ready) {
+  if (g->arena.stream) {
     (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->stream);
+    (void)hipStreamSynchronize(g->arena.stream);
     slab_put(&g->table);
     slab_put(&g->kfTable);
     slab_put(&g->descTable);
-    (void)hipStreamDestroy(g->stream);
   }
-  delete g;
+  delete g;  // (the arena's end: the stream, then the buffers)
 }
 
 extern "C" int orbfe_obsgraph_clear(orbfe_obsgraph* g) {
@@ -289,15 +271,17 @@ extern "C" int orbfe_obsgraph_get_row(orbfe_obsgraph* g, int from_device, int sl
     if (!r.empty()) std::memcpy(entries, r.data(), r.size() * sizeof(ObsEntry));
   } else {
     if (int rc = obs_ready(g)) return rc;
-    const size_t oRow = al(sizeof m), bytes = oRow + rw * sizeof(ObsEntry);
-    if (int rc = ensure_work(g, 0, bytes)) return rc;
-    uint8_t* p = g->pin;
-    HIPCHK(hipMemcpyAsync(p, g->d.meta + slot, sizeof m, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(p + oRow, g->d.rows + (size_t)slot * rw, rw * sizeof(ObsEntry), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    std::memcpy(&m, p, sizeof m);
+    Arena* ar = &g->arena;
+    ObsPointMeta* hMeta;
+    ObsEntry* hRow;
+    auto stage = [&](Arena* a) { open_span(a); hMeta = carve<ObsPointMeta>(a, 1); hRow = carve<ObsEntry>(a, rw); return close_span(a); };
+    HIPCHK(arena_stage(ar, g->device, stage));
+    HIPCHK(fetch(ar, hMeta, g->d.meta + slot, 1));
+    HIPCHK(fetch(ar, hRow, g->d.rows + (size_t)slot * rw, rw));
+    HIPCHK(hipStreamSynchronize(ar->stream));
+    m = *mirror_of(ar, hMeta);
     const int live = std::min(std::max(m.count, 0), (int)rw);
-    if (live) std::memcpy(entries, p + oRow, (size_t)live * sizeof(ObsEntry));
+    if (live) std::memcpy(entries, mirror_of(ar, hRow), (size_t)live * sizeof(ObsEntry));
   }
   *n_entries = m.count; *n_obs = m.nObs; *bad = (uint8_t)m.bad; *ref_kf_slot = m.ref;
   return ORBFE_OK;
@@ -321,32 +305,36 @@ extern "C" int orbfe_obsgraph_votes(orbfe_obsgraph* g, int n_queries, const int3
   if (!g->h.slots_ok((int)nq, q_slots)) return invalid(fn, "slot outside [0, point_capacity)");
   std::lock_guard<std::mutex> lk(g->m);
   if (int rc = obs_ready(g)) return rc;
-  const size_t cap = (size_t)capacity, K = (size_t)g->h.kfCap;
-  const size_t uOff = 0, uSelf = al(uOff + (Q + 1) * 4), uSlots = al(uSelf + (size_t)Q * 4), upBytes = al(uSlots + nq * 4);
-  const size_t oCount = 0, oKf = al(oCount + (size_t)Q * 4), oW = al(oKf + Q * cap * 4), downBytes = al(oW + Q * cap * 4);
-  const size_t counters = g->h.kfCap > kObsVotesLdsKeyFrames ? al((size_t)Q * K * 4) : 0;
-  if (int rc = ensure_work(g, upBytes + downBytes + counters, std::max(upBytes, downBytes))) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  std::memcpy(p + uOff, q_offsets, (size_t)(Q + 1) * 4);
-  std::memcpy(p + uSelf, self_kf_slot, (size_t)Q * 4);
-  if (nq) std::memcpy(p + uSlots, q_slots, nq * 4);
-  HIPCHK(hipMemcpyAsync(d, p, upBytes, hipMemcpyHostToDevice, g->stream));
-  uint8_t* o = d + upBytes;
-  launch_obs_votes(g->stream, g->d, Q, (const int32_t*)(d + uOff), (const int32_t*)(d + uSlots), (const int32_t*)(d + uSelf), capacity,
-                   (int32_t*)(o + oKf), (int32_t*)(o + oW), (int32_t*)(o + oCount), (int32_t*)(o + downBytes));
+  const size_t cap = (size_t)capacity, nQ = (size_t)Q;
+  Arena* ar = &g->arena;
+  int32_t *dOff, *dSelf, *dSlots, *dCount, *dKf, *dW, *dCounters = nullptr;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dOff, q_offsets, nQ + 1));
+    TRY(up(a, &dSelf, self_kf_slot, nQ));
+    TRY(up(a, &dSlots, q_slots, nq));
+    open_span(a);
+    dCount = carve<int32_t>(a, nQ);
+    dKf = carve<int32_t>(a, nQ * cap);
+    dW = carve<int32_t>(a, nQ * cap);
+    TRY(close_span(a));
+    if (g->h.kfCap > kObsVotesLdsKeyFrames) dCounters = carve<int32_t>(a, nQ * (size_t)g->h.kfCap);
+    return hipSuccess;
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  HIPCHK(flush(ar));
+  launch_obs_votes(ar->stream, g->d, Q, dOff, dSlots, dSelf, capacity, dKf, dW, dCount, dCounters);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p, o, downBytes, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));
-  const int32_t* ns = (const int32_t*)(p + oCount);
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  const int32_t *ns = mirror_of(ar, dCount), *hKf = mirror_of(ar, dKf), *hW = mirror_of(ar, dW);
   bool over = false;
   for (int q = 0; q < Q; q++) {
     count[q] = ns[q];
     const size_t m = std::min((size_t)std::max(ns[q], 0), cap);
     over |= (size_t)std::max(ns[q], 0) > cap;
     if (m) {
-      std::memcpy(kf_slot_out + q * cap, p + oKf + q * cap * 4, m * 4);
-      std::memcpy(weight_out + q * cap, p + oW + q * cap * 4, m * 4);
+      std::memcpy(kf_slot_out + q * cap, hKf + q * cap, m * 4);
+      std::memcpy(weight_out + q * cap, hW + q * cap, m * 4);
     }
   }
   if (over) return fail(ORBFE_ERR_CAPACITY, "obsgraph_votes: a query has more voted key frames than `capacity` (see count[])");
@@ -368,29 +356,31 @@ extern "C" int orbfe_obsgraph_culling_counts(orbfe_obsgraph* g, int n_kf, const 
   if (!g->h.slots_ok((int)F, slot)) return invalid(fn, "slot outside [0, point_capacity)");
   std::lock_guard<std::mutex> lk(g->m);
   if (int rc = obs_ready(g)) return rc;
-  const size_t uKf = 0, uCand = al(uKf + C * 4), uSlot = al(uCand + F * 4), uOct = al(uSlot + F * 4), upBytes = al(uOct + F);
-  const size_t oMps = 0, oRed = al(C * 4), downBytes = oRed + al(C * 4);
-  if (int rc = ensure_work(g, upBytes + downBytes, std::max(upBytes, downBytes))) return rc;
-  uint8_t* p = g->pin;
-  uint8_t* d = g->work;
-  std::memcpy(p + uKf, kf_slot, C * 4);
-  int32_t* hc = (int32_t*)(p + uCand);
-  for (int c = 0; c < n_kf; c++)
-    for (int f = offsets[c]; f < offsets[c + 1]; f++) hc[f] = c;
-  if (F) {
-    std::memcpy(p + uSlot, slot, F * 4);
-    std::memcpy(p + uOct, octave, F);
-  }
-  HIPCHK(hipMemcpyAsync(d, p, upBytes, hipMemcpyHostToDevice, g->stream));
-  uint8_t* o = d + upBytes;
-  HIPCHK(hipMemsetAsync(o, 0, downBytes, g->stream));
-  launch_obs_culling(g->stream, g->d, (int)F, (const int32_t*)(d + uCand), (const int32_t*)(d + uKf), (const int32_t*)(d + uSlot), d + uOct,
-                     (int32_t*)(o + oMps), (int32_t*)(o + oRed));
+  Arena* ar = &g->arena;
+  int32_t *dKf, *dCand, *dSlot, *dMps, *dRed;
+  uint8_t* dOct;
+  auto stage = [&](Arena* a) -> hipError_t {
+    TRY(up(a, &dKf, kf_slot, C));
+    TRY(up_pack(a, &dCand, F, [&](int32_t* cand) {
+      for (int c = 0; c < n_kf; c++)
+        for (int f = offsets[c]; f < offsets[c + 1]; f++) cand[f] = c;
+    }));
+    TRY(up(a, &dSlot, slot, F));
+    TRY(up(a, &dOct, octave, F));
+    open_span(a);
+    dMps = carve<int32_t>(a, C);
+    dRed = carve<int32_t>(a, C);
+    return close_span(a);
+  };
+  HIPCHK(arena_stage(ar, g->device, stage));
+  HIPCHK(flush(ar));
+  HIPCHK(zero_span(ar));  // both counts
+  launch_obs_culling(ar->stream, g->d, (int)F, dCand, dKf, dSlot, dOct, dMps, dRed);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p, o, downBytes, hipMemcpyDeviceToHost, g->stream));
-  HIPCHK(hipStreamSynchronize(g->stream));
-  std::memcpy(n_mps, p + oMps, C * 4);
-  std::memcpy(n_redundant, p + oRed, C * 4);
+  HIPCHK(down_span(ar));
+  HIPCHK(hipStreamSynchronize(ar->stream));
+  std::memcpy(n_mps, mirror_of(ar, dMps), C * 4);
+  std::memcpy(n_redundant, mirror_of(ar, dRed), C * 4);
   return ORBFE_OK;
 }
 

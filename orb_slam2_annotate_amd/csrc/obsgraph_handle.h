@@ -1,6 +1,7 @@
-// obsgraph_handle.h -- struct orbfe_obsgraph and what its three host files share (obsgraph.hip: the observation rows;
-// kfpoints.hip: the key-frame rows; obsdesc.hip: the key frames' descriptors).  Everything here is called with the handle
-// locked.
+// obsgraph_handle.h -- struct orbfe_obsgraph and what its host files share (obsgraph.hip: the observation rows;
+// kfpoints.hip: the key-frame rows; obsdesc.hip: the key frames' descriptors; loopcorrect.hip: the loop correction).
+// Everything here is called with the handle locked.  The handle owns an arena (arena.h): its calls stage through
+// arena_stage(&g->arena, g->device, stage) and run on g->arena.stream, whichever thread makes them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <string>
 
 #include "../../include/orbfe.h"
+#include "arena.h"
 #include "host_internal.h"
 #include "obsgraph_host.h"
 #include "obsgraph_kernels.h"
@@ -15,8 +17,6 @@
 struct orbfe_obsgraph {
   int device = 0;
   std::mutex m;  // a handle serialises its own calls
-  bool ready = false;  // stream created
-  hipStream_t stream = nullptr;
   orbfe::ObsGraphMirror h;
   orbfe::Slab table;  // empty until the first call that needs the device
   orbfe::ObsGraphDevice d{};
@@ -29,20 +29,14 @@ struct orbfe_obsgraph {
   // kf slot -> place in the list of a loop-correction call (loopcorrect.hip): kf_capacity int32, -1 everywhere between
   // calls; empty until the first such call
   orbfe::DevBuf<int32_t> kfRank;
-  // grow-only workspace + pinned staging in both directions
-  orbfe::DevBuf<uint8_t> work;
-  orbfe::PinBuf<uint8_t> pin;
+  // the handle's stream (made by the first call that touches the device), workspace and pinned mirror
+  orbfe::Arena arena;
 };
 
 namespace orbfe {
 
 constexpr size_t kObsFlushChunkBytes = (size_t)8 << 20;
 
-inline size_t obs_al(size_t x) { return (x + 255) & ~(size_t)255; }
-int obs_ensure_work(orbfe_obsgraph* g, size_t devBytes, size_t pinBytes);
-// the handle's device made current and its stream created: the first step of obs_ready, and all a call needs that
-// touches the device but not the table
-int obs_stream(orbfe_obsgraph* g);
 // what every call that reads the table on the device starts with: device, stream, the slab, the marked rows written
 int obs_ready(orbfe_obsgraph* g);
 int obs_invalid(const char* fn, const char* what);

@@ -11,8 +11,11 @@ ARENA = {"arena.h", "arena.hip"}
 # what only the arena's own files may name: the begin behind arena_stage / arena_stream, the hand sum's helper and the
 # pinned mirror (a call reads it through mirror_of() and writes it through up() / up_pack() / up_fill() / put()); what
 # only arena.hip may name: the thread-local state
-ARENA_ONLY = re.compile(r"\b(arena_begin|pad)\s*\(|\bhmirror\b")
+ARENA_ONLY = re.compile(r"\b(arena_begin|arena_begin_owned|pad)\s*\(|\bhmirror\b")
 STATE_ONLY = re.compile(r"\b(t_arenas|t_staging)\b")
+# the scheme the graph and the database had before they owned an arena: a workspace and a pinned block on the handle, sized
+# by hand sums and cut by offset tables
+HANDLE_BLOCKS = re.compile(r"\b(obs_ensure_work|obs_al)\b|\b(?:g|db|held)\s*->\s*(?:work|pin)\b")
 TABLE_ONLY = re.compile(r"\bmappoints_ready\b|\bmp\s*->\s*(?:slab|m|d)\b")
 
 
@@ -46,6 +49,17 @@ def test_the_caller_laid_block_is_gone():
 
 def test_only_the_arena_begins_the_arena_and_nothing_sums_by_hand():
     assert not named_outside(ARENA_ONLY, ARENA), "carve inside arena_stage(), or take arena_stream(); reach the mirror through up*() / mirror_of()"
+
+
+def test_no_handle_keeps_a_workspace_and_a_pinned_block_of_its_own():
+    f = files()
+    assert not named_outside(HANDLE_BLOCKS, set()), "stage through the handle's arena: arena_stage(&g->arena, g->device, stage)"
+    for handle, owner in (("orbfe_obsgraph", "obsgraph_handle.h"), ("orbfe_kfdb", "kfdb.hip")):
+        body = re.search(r"^struct\s+" + handle + r"\s*\{(.*?)^\};", f[owner], re.M | re.S).group(1)
+        assert re.search(r"\bArena\s+arena\s*;", body), f"{handle} owns no arena"
+        assert not re.search(r"\b(work|pin)\s*;", body), f"{handle} has a work / pin member again"
+    for owner in ("obsgraph.hip", "kfpoints.hip", "obsdesc.hip", "loopcorrect.hip", "kfdb.hip"):
+        assert re.search(r"\barena_stage\s*\(", f[owner]), f"{owner} stages nothing through the arena"
 
 
 def test_the_thread_local_state_is_named_only_in_arena_hip():
@@ -87,3 +101,9 @@ def test_the_guard_notices_a_hand_summed_begin(tmp_path):
     assert s.read_text().count("  MapPointsLock lock(mp);\n") >= 1
     s.write_text(s.read_text().replace("  MapPointsLock lock(mp);\n", "  std::lock_guard<std::mutex> lk(mp->m);\n", 1))
     assert named_outside(TABLE_ONLY, {"mappoints.hip"}, tmp_path) == [("mappoints_search.hip", "mp->m")]
+    assert not named_outside(HANDLE_BLOCKS, set(), tmp_path)
+    k = tmp_path / "kfpoints.hip"  # a call of the graph that reads its result from a pinned block of the handle again
+    line = "  std::memcpy(count, mirror_of(ar, dCount), (size_t)n_kf * 4);\n"
+    assert k.read_text().count(line) == 1
+    k.write_text(k.read_text().replace(line, "  std::memcpy(count, g->pin, (size_t)n_kf * 4);\n"))
+    assert named_outside(HANDLE_BLOCKS, set(), tmp_path) == [("kfpoints.hip", "g->pin")]

@@ -261,3 +261,39 @@ def test_local_points_feed_search_local_points():
     assert np.array_equal(m_got, m_want) and np.array_equal(iv_got, iv_want)
     mp.close()
     g.close()
+
+
+def test_a_larger_call_between_two_equal_small_ones_on_one_handle():
+    """The handle's workspace and pinned block grow with the largest call: a small union, then one far larger than anything
+    the handle has staged (64 lists of 3000 entries come back in two copies), then the small one again."""
+    rng = np.random.default_rng(6)
+    K, W, P = 40, 128, 3000
+    pool = rng.choice(P, 400, replace=False)
+    rows = {k: rng.choice(pool, int(rng.integers(40, W + 1))).tolist() for k in range(K)}
+    g, w = build(P, K, W, rows, bad=set(pool[:30].tolist()))
+    small = [[3, 1, 2]]
+    first = lists(g.keyframe_points_union(small, capacity=400))
+    assert first == [w.local_points(small[0])] and len(first[0]) > 50
+    large = [rng.permutation(K)[:int(rng.integers(1, K + 1))].tolist() for _ in range(64)]
+    assert lists(g.keyframe_points_union(large, capacity=P)) == [w.local_points(q) for q in large]
+    assert g.tracked_points(list(range(K)), 0).tolist() == [w.tracked_points(k, 0) for k in range(K)]
+    assert lists(g.keyframe_points_union(small, capacity=400)) == first
+    g.close()
+
+
+def test_a_flush_of_more_key_frame_rows_than_one_chunk_holds():
+    """kf_row_width 2048: a marked non-empty row is staged as 8 KiB and 12 bytes, so one 8 MiB chunk holds 1022 of them
+    and 1100 need two stagings.  The rows on both sides of the chunk boundary and the last one must have arrived."""
+    K, W, P = 1100, 2048, 600
+    rng = np.random.default_rng(7)
+    rows = {k: rng.integers(-1, P, int(rng.integers(1, 6))).tolist() for k in range(K)}
+    g, w = build(P, K, W, rows, bad=set(range(0, P, 11)))
+    per_chunk = (8 << 20) // (12 + W * 4)
+    assert per_chunk < K <= 2 * per_chunk
+    q = [K - 1, per_chunk, per_chunk - 1, 0, 500]
+    assert g.local_points(q).tolist() == w.local_points(q)  # the first call that reads the rows: the flush
+    for k in [0, 1, per_chunk - 2, per_chunk - 1, per_chunk, per_chunk + 1, K - 1] + list(range(5, K, 83)):
+        assert g.get_keyframe_points(k, from_device=True).tolist() == rows[k], k
+    everything = list(range(K))
+    assert g.local_points(everything).tolist() == w.local_points(everything)
+    g.close()

@@ -248,3 +248,34 @@ def test_mutation_between_two_vote_calls():
     check()
     assert g.erase_keyframe(kf_slot_of[ids[4]]).tolist() == w.erase_keyframe(ids[4])
     check()
+
+
+def test_a_flush_of_more_rows_than_one_chunk_holds():
+    """row_width 256 (the widest): a marked non-empty row is staged as 2 KiB and 24 bytes, so one 8 MiB chunk holds 4048 of
+    them and 4100 need two stagings.  Every row must have arrived, the ones on both sides of the chunk boundary and the last
+    one among them."""
+    rw, n_pts = 256, 4100
+    rng = np.random.default_rng(41)
+    ids = list(range(40, 52))
+    kf_slot_of = dict(zip(ids, KF_SLOTS))
+    w = orf.World()
+    for k in ids:
+        w.add_keyframe(k, rng.uniform(-1, 1, 3).astype(np.float32))
+    for p in range(n_pts):
+        obs = rng.choice(ids, size=int(rng.integers(1, 4)), replace=False).tolist()
+        w.add_point(p, ref=obs[0], bad=False)
+        for k in obs:
+            w.add_observation(p, k, int(rng.integers(0, 2000)), int(rng.integers(0, N_LEVELS)), bool(rng.integers(2)))
+    g = amd.ObservationGraph(n_pts, KF_CAP, rw)
+    orf.load(w, g, kf_slot_of, {p: p for p in range(n_pts)})
+    per_chunk = (8 << 20) // (4 + 16 + 4 + rw * 8)
+    assert per_chunk < n_pts <= 2 * per_chunk
+    q = list(range(n_pts))
+    (kf, wt), = g.votes([q])  # the first call that reads the table: the flush
+    assert as_counter(kf, wt, kf_slot_of) == w.votes(q)
+    for p in [0, 1, per_chunk - 2, per_chunk - 1, per_chunk, per_chunk + 1, n_pts - 1] + list(range(7, n_pts, 97)):
+        ent, nobs, isbad, ref = orf.mirror_row(w, p, kf_slot_of)
+        r = g.get_row(p, from_device=True)
+        assert [tuple(int(v) for v in e) for e in r["entries"]] == ent, p
+        assert (r["n_obs"], r["bad"], r["ref_kf_slot"]) == (nobs, isbad, ref), p
+    g.close()
