@@ -414,13 +414,18 @@ int orbfe_vocabulary_info(const orbfe_vocabulary *v, int *k, int *L, int *n_node
  * k-ary descent with FORB::distance.  Features with weight > 0 are the ones transform(features,
  * BowVector&, FeatureVector&, levelsup) (:1127-1194; called with levelsup = 4 at src/Frame.cc:438)
  * adds as BowVector.addWeight(word_id, weight) / FeatureVector.addFeature(node_id, i).  Returns
- * their number, or a negative status. */
+ * their number, or a negative status.  Runs on the calling thread's matcher stream and is complete on
+ * return; the tree is immutable after create and the call keeps nothing on the handle, so several
+ * threads may make it on one handle at once (Frame::ComputeBoW on tracking, KeyFrame::ComputeBoW on
+ * local mapping). */
 int orbfe_vocabulary_transform(orbfe_vocabulary *v, const uint8_t *descriptors, int n, int levelsup,
                                uint32_t *word_id, double *weight, uint32_t *node_id);
 
 /* Frame::ComputeBoW for every frame of a device-resident extractor batch: FeatureVector f as CSR at
  * d_fv_nodes[f*capacity ..] (ascending, d_fv_count[f] of them), d_fv_offsets[f*(capacity+1) ..],
- * d_fv_indices[f*capacity ..]; optional per-feature word ids / weights (both or neither). */
+ * d_fv_indices[f*capacity ..]; optional per-feature word ids / weights (both or neither).  Runs on the
+ * calling thread's matcher stream -- the caller's writes of the inputs must have completed -- and is
+ * complete on return; may be made on one handle from several threads at once, like the call above. */
 int orbfe_vocabulary_featvec_batch_device(orbfe_vocabulary *v, const uint8_t *d_descriptors,
                                           const int32_t *d_n, int n_frames, int capacity, int levelsup,
                                           uint32_t *d_fv_nodes, int32_t *d_fv_offsets,
@@ -518,10 +523,19 @@ int orbfe_kfdb_group_candidates(int mode, float min_score, int n, const int64_t 
 
 /* cv::cvtColor(im, im, CV_RGB2GRAY | CV_BGR2GRAY | CV_RGBA2GRAY | CV_BGRA2GRAY) of
  * Tracking::GrabImage{Stereo,RGBD,Monocular} (src/Tracking.cc:176-262), 8-bit, channels 3 or 4,
- * rgb_order != 0 for RGB(A) input: (R*4899 + G*9617 + B*1868 + 2^13) >> 14.  Host buffers. */
+ * rgb_order != 0 for RGB(A) input: (R*4899 + G*9617 + B*1868 + 2^13) >> 14.  Host buffers: `width`
+ * pixels of each row are read / written, the padding up to the stride is left alone.  This and the other
+ * host-array calls of this section and of the rectifier / undistortion section below (orbfe_distinctive_
+ * descriptors, orbfe_rectifier_create, orbfe_remap, orbfe_init_undistort_rectify_map, orbfe_undistort_points,
+ * orbfe_compute_image_bounds, orbfe_stereo_from_rgbd) run on the calling thread's matcher stream and are
+ * complete on return. */
 int orbfe_cvt_gray(int device, const uint8_t *src, int width, int height, int stride, int channels,
                    int rgb_order, uint8_t *dst, int dst_stride);
-/* Same on device-resident frames (so colour input never round-trips through the host). */
+/* Same on device-resident frames (so colour input never round-trips through the host).  This and the
+ * other two device-pointer calls of these sections (orbfe_remap_batch_device, orbfe_undistort_keypoints_
+ * batch_device) are enqueued on the default stream, complete on return: the library knows no stream for
+ * arrays the caller wrote, and the default stream orders the kernel behind the caller's default-stream
+ * work.  The call waits for that stream alone, not for the device. */
 int orbfe_cvt_gray_batch_device(int device, const uint8_t *d_src, int n_frames, int width, int height,
                                 int stride, size_t frame_stride, int channels, int rgb_order,
                                 uint8_t *d_dst, int dst_stride, size_t dst_frame_stride);
@@ -1405,7 +1419,8 @@ void orbfe_rectifier_destroy(orbfe_rectifier *r);
 /* Host buffers, one frame. */
 int orbfe_remap(orbfe_rectifier *r, const uint8_t *src, int src_width, int src_height, int src_stride,
                 uint8_t *dst, int dst_stride);
-/* Device-resident frames: rectified images are written where orbfe_extract_batch_device reads them. */
+/* Device-resident frames: rectified images are written where orbfe_extract_batch_device reads them.
+ * Enqueued on the default stream, complete on return (see orbfe_cvt_gray_batch_device). */
 int orbfe_remap_batch_device(orbfe_rectifier *r, const uint8_t *d_src, int n_frames, int src_width,
                              int src_height, int src_stride, size_t src_frame_stride, uint8_t *d_dst,
                              int dst_stride, size_t dst_frame_stride);
@@ -1430,7 +1445,8 @@ int orbfe_extract_stereo_rectified_batch_device_async(
 int orbfe_undistort_points(int device, const float *xy, int n, const float *K4, const float *dist,
                            int n_dist, float *out_xy);
 /* mvKeysUn of a device-resident extractor batch (the layout orbfe_extract_batch_device writes):
- * records copied, pt undistorted. */
+ * records copied, pt undistorted.  Enqueued on the default stream, complete on return (see
+ * orbfe_cvt_gray_batch_device). */
 int orbfe_undistort_keypoints_batch_device(int device, const orbfe_keypoint *d_keypoints,
                                            const int32_t *d_n, int n_frames, int capacity,
                                            const float *K4, const float *dist, int n_dist,

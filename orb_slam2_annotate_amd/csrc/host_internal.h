@@ -158,7 +158,7 @@ int orbfe_stereo_views_(orbfe_extractor* e, int frame, orbfe::PyramidViews* pv, 
 // extractor_debug.hip: test hooks that hold back / query a stream
 int orbfe_debug_stall_launch_(hipStream_t s, int usec);
 int orbfe_debug_stream_idle_(hipStream_t s);
-// ---- k_ingest.hip (struct orbfe_rectifier lives there) ----
+// ---- ingest.hip (struct orbfe_rectifier lives there) ----
 // the rectification of a sub-batch on that sub-batch's own stream; d_src == NULL only queries w / h / device
 int orbfe_remap_launch_(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride,
                         size_t sFrame, uint8_t* d_dst, int dstride, size_t dFrame, hipStream_t stream, int* w, int* h,

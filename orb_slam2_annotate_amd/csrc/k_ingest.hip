@@ -1,19 +1,12 @@
 // k_ingest.hip -- the per-pixel / per-map-point loops right next to the hot path (SURVEY.md 8(f)
 // ranks 3-4): colour -> gray conversion in front of the extractor (Tracking::GrabImage*,
 // src/Tracking.cc:176-262) and MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:269-333).
+// The kernels and their launchers (ingest_kernels.h); the entry points are ingest.hip.
 #include <hip/hip_runtime.h>
 
-#include <memory>
-#include <string>
-#include <vector>
+#include "ingest_kernels.h"
 
-#include "../../include/orbfe.h"
-#include "host_internal.h"
-#include "kernels.h"
-#include "orb_spec.h"
-
-using orbfe::DevBuf;
-using orbfe::fail;
+using namespace orbfe;
 
 namespace {
 
@@ -78,64 +71,6 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t* __restrict__
   if (tid == 0) best[m] = (int32_t)(bestKey & 0xffffu);
 }
 
-}  // namespace
-
-extern "C" int orbfe_cvt_gray(int device, const uint8_t* src, int width, int height, int stride, int channels,
-                              int rgb_order, uint8_t* dst, int dst_stride) {
-  if (!src || !dst || width <= 0 || height <= 0 || (channels != 3 && channels != 4) || stride < width * channels ||
-      dst_stride < width)
-    return fail(ORBFE_ERR_INVALID, "cvt_gray: bad argument");
-  HIPCHK(hipSetDevice(device));
-  DevBuf<uint8_t> ds, dd;
-  int rc;
-  if ((rc = ds.alloc((size_t)width * channels * height)) || (rc = dd.alloc((size_t)width * height))) return rc;
-  HIPCHK(hipMemcpy2D(ds, (size_t)width * channels, src, stride, (size_t)width * channels, height, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_cvt_gray, dim3((width + 1023) / 1024, height, 1), dim3(256), 0, 0, ds.p, width, height,
-                     width * channels, 0, channels, rgb_order, dd.p, width, 0);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy2D(dst, dst_stride, dd, width, width, height, hipMemcpyDeviceToHost));
-  return ORBFE_OK;
-}
-
-extern "C" int orbfe_cvt_gray_batch_device(int device, const uint8_t* d_src, int n_frames, int width, int height,
-                                           int stride, size_t frame_stride, int channels, int rgb_order,
-                                           uint8_t* d_dst, int dst_stride, size_t dst_frame_stride) {
-  if (!d_src || !d_dst || n_frames < 0 || width <= 0 || height <= 0 || (channels != 3 && channels != 4) ||
-      stride < width * channels || dst_stride < width)
-    return fail(ORBFE_ERR_INVALID, "cvt_gray_batch_device: bad argument");
-  if (n_frames == 0) return ORBFE_OK;
-  HIPCHK(hipSetDevice(device));
-  hipLaunchKernelGGL(k_cvt_gray, dim3((width + 1023) / 1024, height, n_frames), dim3(256), 0, 0, d_src, width, height,
-                     stride, frame_stride, channels, rgb_order, d_dst, dst_stride, dst_frame_stride);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  return ORBFE_OK;
-}
-
-extern "C" int orbfe_distinctive_descriptors(int device, const uint8_t* descriptors, const int32_t* offsets,
-                                             int n_points, int32_t* best_index) {
-  if (n_points < 0 || (n_points > 0 && (!descriptors || !offsets || !best_index)))
-    return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: bad argument");
-  if (n_points == 0) return ORBFE_OK;
-  for (int i = 0; i < n_points; i++)
-    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 65535)
-      return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: bad offsets (or more than 65535 observations)");
-  if (offsets[0] != 0) return fail(ORBFE_ERR_INVALID, "distinctive_descriptors: offsets[0] != 0");
-  const size_t total = (size_t)offsets[n_points];
-  HIPCHK(hipSetDevice(device));
-  DevBuf<uint8_t> dd;
-  DevBuf<int32_t> doff, dbest;
-  int rc;
-  if ((rc = dd.alloc(total * 32 + 32)) || (rc = doff.alloc((size_t)n_points + 1)) || (rc = dbest.alloc((size_t)n_points))) return rc;
-  if (total) HIPCHK(hipMemcpy(dd, descriptors, total * 32, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(doff, offsets, ((size_t)n_points + 1) * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_distinctive, dim3(n_points), dim3(256), 0, 0, dd.p, doff.p, dbest.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(best_index, dbest, (size_t)n_points * 4, hipMemcpyDeviceToHost));
-  return ORBFE_OK;
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // cv::remap(src, dst, M1 CV_32F, M2 CV_32F, INTER_LINEAR) -- the EuRoC stereo rectification in
@@ -145,15 +80,6 @@ extern "C" int orbfe_distinctive_descriptors(int device, const uint8_t* descript
 // to int16 (packed sx | sy << 16) and a 10-bit sub-pixel phase (fy*32 + fx); the per-frame kernel
 // then moves 6 map bytes + 1 source byte + 1 output byte per pixel.
 // ---------------------------------------------------------------------------------------------
-struct orbfe_rectifier {
-  int device = 0;
-  int width = 0, height = 0;  // destination size = map size
-  DevBuf<uint32_t> xy;        // [height][pitch]
-  DevBuf<uint16_t> phase;     // [height][pitch]
-  int pitch = 0;              // multiple of 4
-};
-
-namespace {
 
 __device__ __forceinline__ int cvround_sse(float v) {  // cvtss2si: out of range / NaN -> INT_MIN
   if (!(v >= -2147483648.0f && v < 2147483648.0f)) return (int)0x80000000;
@@ -221,86 +147,6 @@ __global__ __launch_bounds__(256) void k_remap(const uint32_t* __restrict__ xy, 
   }
 }
 
-int remap_launch(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride, size_t sFrame,
-                 uint8_t* d_dst, int dstride, size_t dFrame, hipStream_t stream) {
-  const int tilesX = (r->width + 255) / 256, tilesY = (r->height + 3) / 4;
-  hipLaunchKernelGGL(k_remap, dim3((unsigned)tilesX * tilesY * n_frames), dim3(256), 0, stream, r->xy.p, r->phase.p, r->pitch,
-                     r->width, r->height, tilesX, n_frames, d_src, sw, sh, sstride, sFrame, d_dst, dstride, dFrame);
-  HIPCHK(hipGetLastError());
-  return ORBFE_OK;
-}
-
-}  // namespace
-
-// internal (extractor.hip): the rectification of a sub-batch enqueued on that sub-batch's own stream
-extern "C" int orbfe_remap_launch_(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int sw, int sh, int sstride,
-                                   size_t sFrame, uint8_t* d_dst, int dstride, size_t dFrame, hipStream_t stream, int* w, int* h,
-                                   int* device) {
-  if (!r) return fail(ORBFE_ERR_INVALID, "NULL rectifier");
-  if (w) *w = r->width;
-  if (h) *h = r->height;
-  if (device) *device = r->device;
-  if (!d_src || n_frames <= 0) return ORBFE_OK;  // query only
-  return remap_launch(r, d_src, n_frames, sw, sh, sstride, sFrame, d_dst, dstride, dFrame, stream);
-}
-
-extern "C" int orbfe_rectifier_create(int device, const float* map_x, const float* map_y, int width, int height,
-                                  int map_stride, orbfe_rectifier** out) {
-  if (!map_x || !map_y || !out || width <= 0 || height <= 0 || map_stride < width || width > 32767 || height > 32767)
-    return fail(ORBFE_ERR_INVALID, "remap_create: bad argument");
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<orbfe_rectifier> r(new orbfe_rectifier());
-  r->device = device; r->width = width; r->height = height; r->pitch = (width + 3) & ~3;
-  DevBuf<float> dmx, dmy;
-  const size_t m = (size_t)width * height, n = (size_t)r->pitch * height;
-  int rc;
-  if ((rc = r->xy.alloc(n)) || (rc = r->phase.alloc(n)) || (rc = dmx.alloc(m)) || (rc = dmy.alloc(m))) return rc;
-  HIPCHK(hipMemcpy2D(dmx, (size_t)width * 4, map_x, (size_t)map_stride * 4, (size_t)width * 4, height, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy2D(dmy, (size_t)width * 4, map_y, (size_t)map_stride * 4, (size_t)width * 4, height, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_remap_convert, dim3((r->pitch + 255) / 256, height), dim3(256), 0, 0, dmx.p, dmy.p, width, width,
-                     height, r->pitch, r->xy.p, r->phase.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  *out = r.release();
-  return ORBFE_OK;
-}
-
-extern "C" void orbfe_rectifier_destroy(orbfe_rectifier* r) {
-  if (!r) return;
-  (void)hipSetDevice(r->device);
-  delete r;
-}
-
-extern "C" int orbfe_remap(orbfe_rectifier* r, const uint8_t* src, int src_width, int src_height, int src_stride,
-                           uint8_t* dst, int dst_stride) {
-  if (!r || !src || !dst || src_width <= 0 || src_height <= 0 || src_stride < src_width || dst_stride < r->width)
-    return fail(ORBFE_ERR_INVALID, "remap: bad argument");
-  HIPCHK(hipSetDevice(r->device));
-  DevBuf<uint8_t> ds, dd;
-  int rc;
-  if ((rc = ds.alloc((size_t)src_width * src_height)) || (rc = dd.alloc((size_t)r->pitch * r->height))) return rc;
-  HIPCHK(hipMemcpy2D(ds, src_width, src, src_stride, src_width, src_height, hipMemcpyHostToDevice));
-  if ((rc = remap_launch(r, ds, 1, src_width, src_height, src_width, 0, dd, r->pitch, 0, 0))) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy2D(dst, dst_stride, dd, r->pitch, r->width, r->height, hipMemcpyDeviceToHost));
-  return ORBFE_OK;
-}
-
-extern "C" int orbfe_remap_batch_device(orbfe_rectifier* r, const uint8_t* d_src, int n_frames, int src_width,
-                                        int src_height, int src_stride, size_t src_frame_stride, uint8_t* d_dst,
-                                        int dst_stride, size_t dst_frame_stride) {
-  if (!r || !d_src || !d_dst || n_frames < 0 || src_width <= 0 || src_height <= 0 || src_stride < src_width ||
-      dst_stride < r->width)
-    return fail(ORBFE_ERR_INVALID, "remap_batch_device: bad argument");
-  if (n_frames == 0) return ORBFE_OK;
-  HIPCHK(hipSetDevice(r->device));
-  const int rc = remap_launch(r, d_src, n_frames, src_width, src_height, src_stride, src_frame_stride, d_dst, dst_stride,
-                              dst_frame_stride, 0);
-  if (rc != ORBFE_OK) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  return ORBFE_OK;
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // Frame::UndistortKeyPoints / ComputeImageBounds (cv::undistortPoints with P = K,
@@ -308,13 +154,6 @@ extern "C" int orbfe_remap_batch_device(orbfe_rectifier* r, const uint8_t* d_src
 // loops between the extractor and the matchers.  Double precision, no FMA contraction (the
 // library is built with -ffp-contract=off), IEEE division: bit-identical to the host arithmetic.
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-struct UndistortParams {
-  double fx, fy, cx, cy, ifx, ify;
-  double k[8];
-  int iters;
-};
 
 __device__ __forceinline__ void undistort_one(const UndistortParams& p, float xin, float yin, float* xo, float* yo) {
   double x = (double)xin, y = (double)yin, x0, y0;
@@ -371,24 +210,10 @@ __global__ __launch_bounds__(256) void k_stereo_from_rgbd(const float* __restric
   depth[i] = dd;
 }
 
-bool undistort_params(const float* K4, const float* dist, int n_dist, UndistortParams* p) {
-  if (!K4 || n_dist < 0 || n_dist > 8 || (n_dist > 0 && !dist) || !(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8))
-    return false;
-  p->fx = (double)K4[0]; p->fy = (double)K4[1]; p->cx = (double)K4[2]; p->cy = (double)K4[3];
-  p->ifx = 1. / p->fx; p->ify = 1. / p->fy;
-  for (int i = 0; i < 8; i++) p->k[i] = i < n_dist ? (double)dist[i] : 0.0;
-  p->iters = n_dist > 0 ? 5 : 1;
-  return true;
-}
-
-}  // namespace
-
 // cv::initUndistortRectifyMap(K, D, R, P[:3,:3], size, CV_32F, M1, M2) as Examples/Stereo/stereo_euroc.cc:97-98 calls it,
 // once at start-up: the two float maps orbfe_rectifier_create takes.  One THREAD per map row -- the reference walks a row
 // with running sums (_x += ir[0], ...), so a row is a sequential chain in double precision; rows are independent.  No FMA
 // contraction (the build's -ffp-contract=off), IEEE division.
-namespace {
-struct RectifyMapParams { double ir[9], fx, fy, u0, v0, k1, k2, p1, p2, k3, k4, k5, k6; int w, h; };
 __global__ __launch_bounds__(64) void k_init_rectify_map(const RectifyMapParams p, float* __restrict__ mapX, float* __restrict__ mapY) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= p.h) return;
@@ -412,119 +237,48 @@ __global__ __launch_bounds__(64) void k_init_rectify_map(const RectifyMapParams 
 }
 }  // namespace
 
-extern "C" int orbfe_init_undistort_rectify_map(int device, const double* K, const double* D, int n_dist, const double* R,
-                                                const double* P, int width, int height, float* map_x, float* map_y) {
-  if (!K || width <= 0 || height <= 0 || !map_x || !map_y || !(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8) ||
-      (n_dist > 0 && !D))
-    return fail(ORBFE_ERR_INVALID, "init_undistort_rectify_map: bad argument (K, the maps and 0 / 4 / 5 / 8 distortion coefficients are required)");
-  static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  const double *Rm = R ? R : I3, *Ar = P ? P : K;
-  // iR = (P * R)^-1: nine dot products and cv::invert's closed 3 x 3 form -- a dozen double operations of set-up, evaluated
-  // here in the order the reference evaluates them (host: this translation unit is built with -ffp-contract=off)
-  double M[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double acc = 0;
-      for (int k = 0; k < 3; k++) acc += Ar[3 * i + k] * Rm[3 * k + j];
-      M[3 * i + j] = acc;
-    }
-  double d = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
-  if (d == 0) return fail(ORBFE_ERR_INVALID, "init_undistort_rectify_map: P * R is singular");
-  d = 1. / d;
-  RectifyMapParams p;
-  p.ir[0] = (M[4] * M[8] - M[5] * M[7]) * d; p.ir[1] = (M[2] * M[7] - M[1] * M[8]) * d; p.ir[2] = (M[1] * M[5] - M[2] * M[4]) * d;
-  p.ir[3] = (M[5] * M[6] - M[3] * M[8]) * d; p.ir[4] = (M[0] * M[8] - M[2] * M[6]) * d; p.ir[5] = (M[2] * M[3] - M[0] * M[5]) * d;
-  p.ir[6] = (M[3] * M[7] - M[4] * M[6]) * d; p.ir[7] = (M[1] * M[6] - M[0] * M[7]) * d; p.ir[8] = (M[0] * M[4] - M[1] * M[3]) * d;
-  p.fx = K[0]; p.fy = K[4]; p.u0 = K[2]; p.v0 = K[5];
-  p.k1 = n_dist > 0 ? D[0] : 0; p.k2 = n_dist > 1 ? D[1] : 0; p.p1 = n_dist > 2 ? D[2] : 0; p.p2 = n_dist > 3 ? D[3] : 0;
-  p.k3 = n_dist >= 5 ? D[4] : 0; p.k4 = n_dist >= 8 ? D[5] : 0; p.k5 = n_dist >= 8 ? D[6] : 0; p.k6 = n_dist >= 8 ? D[7] : 0;
-  p.w = width; p.h = height;
-  HIPCHK(hipSetDevice(device));
-  DevBuf<float> dmap;
-  const size_t n = (size_t)width * height;
-  const int rc = dmap.alloc(2 * n);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_init_rectify_map, dim3((height + 63) / 64), dim3(64), 0, 0, p, dmap.p, dmap.p + n);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(map_x, dmap, n * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(map_y, dmap + n, n * 4, hipMemcpyDeviceToHost));
-  return ORBFE_OK;
+namespace orbfe {
+
+void launch_cvt_gray(hipStream_t s, const uint8_t* src, int w, int h, int sstride, size_t sFrame, int channels, int rgbOrder,
+                     uint8_t* dst, int dstride, size_t dFrame, int nFrames) {
+  hipLaunchKernelGGL(k_cvt_gray, dim3((w + 1023) / 1024, h, nFrames), dim3(256), 0, s, src, w, h, sstride, sFrame, channels,
+                     rgbOrder, dst, dstride, dFrame);
 }
 
-extern "C" int orbfe_undistort_points(int device, const float* xy, int n, const float* K4, const float* dist,
-                                      int n_dist, float* out_xy) {
-  UndistortParams p;
-  if (n < 0 || (n > 0 && (!xy || !out_xy)) || !undistort_params(K4, dist, n_dist, &p))
-    return fail(ORBFE_ERR_INVALID, "undistort_points: bad argument");
-  if (n == 0) return ORBFE_OK;
-  HIPCHK(hipSetDevice(device));
-  DevBuf<float> din, dout;
-  int rc;
-  if ((rc = din.alloc((size_t)n * 2)) || (rc = dout.alloc((size_t)n * 2))) return rc;
-  HIPCHK(hipMemcpy(din, xy, (size_t)n * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, 0, p, din.p, n, dout.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(out_xy, dout, (size_t)n * 8, hipMemcpyDeviceToHost));
-  return ORBFE_OK;
+void launch_distinctive(hipStream_t s, const uint8_t* desc, const int32_t* offsets, int nPoints, int32_t* best) {
+  hipLaunchKernelGGL(k_distinctive, dim3(nPoints), dim3(256), 0, s, desc, offsets, best);
 }
 
-extern "C" int orbfe_undistort_keypoints_batch_device(int device, const orbfe_keypoint* d_keypoints,
-                                                      const int32_t* d_n, int n_frames, int capacity,
-                                                      const float* K4, const float* dist, int n_dist,
-                                                      orbfe_keypoint* d_keypoints_un) {
-  UndistortParams p;
-  if (!d_keypoints || !d_n || !d_keypoints_un || n_frames < 0 || capacity <= 0 || !undistort_params(K4, dist, n_dist, &p))
-    return fail(ORBFE_ERR_INVALID, "undistort_keypoints_batch_device: bad argument");
-  if (n_frames == 0) return ORBFE_OK;
-  HIPCHK(hipSetDevice(device));
-  hipLaunchKernelGGL(k_undistort_keypoints, dim3((capacity + 255) / 256, n_frames), dim3(256), 0, 0, p,
-                     reinterpret_cast<const float*>(d_keypoints), d_n, capacity, reinterpret_cast<float*>(d_keypoints_un));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipDeviceSynchronize());
-  return ORBFE_OK;
+void launch_remap_convert(hipStream_t s, const float* mx, const float* my, int mstride, int w, int h, int pitch, uint32_t* xy,
+                          uint16_t* phase) {
+  hipLaunchKernelGGL(k_remap_convert, dim3((pitch + 255) / 256, h), dim3(256), 0, s, mx, my, mstride, w, h, pitch, xy, phase);
 }
 
-extern "C" int orbfe_compute_image_bounds(int device, int cols, int rows, const float* K4, const float* dist,
-                                          int n_dist, float* bounds4) {
-  if (!bounds4 || cols <= 0 || rows <= 0) return fail(ORBFE_ERR_INVALID, "compute_image_bounds: bad argument");
-  if (n_dist > 0 && dist && dist[0] != 0.0) {
-    const float in[8] = {0.0f, 0.0f, (float)cols, 0.0f, 0.0f, (float)rows, (float)cols, (float)rows};
-    float out[8];
-    const int rc = orbfe_undistort_points(device, in, 4, K4, dist, n_dist, out);
-    if (rc != ORBFE_OK) return rc;
-    bounds4[0] = out[4] < out[0] ? out[4] : out[0];  // min(mat(0,0), mat(2,0)), src/Frame.cc:496-499
-    bounds4[1] = out[2] < out[6] ? out[6] : out[2];
-    bounds4[2] = out[3] < out[1] ? out[3] : out[1];
-    bounds4[3] = out[5] < out[7] ? out[7] : out[5];
-  } else {
-    bounds4[0] = 0.0f; bounds4[1] = (float)cols; bounds4[2] = 0.0f; bounds4[3] = (float)rows;
-  }
-  return ORBFE_OK;
+void launch_remap(hipStream_t s, const uint32_t* xy, const uint16_t* phase, int pitch, int w, int h, int nFrames,
+                  const uint8_t* src, int sw, int sh, int sstride, size_t sFrame, uint8_t* dst, int dstride, size_t dFrame) {
+  const int tilesX = (w + 255) / 256, tilesY = (h + 3) / 4;
+  hipLaunchKernelGGL(k_remap, dim3((unsigned)tilesX * tilesY * nFrames), dim3(256), 0, s, xy, phase, pitch, w, h, tilesX, nFrames,
+                     src, sw, sh, sstride, sFrame, dst, dstride, dFrame);
 }
 
-extern "C" int orbfe_stereo_from_rgbd(int device, const float* kx, const float* ky, const float* kux, int n,
-                                      const float* depth_image, int width, int height, int stride_floats, float mbf,
-                                      float* u_right, float* depth) {
-  if (n < 0 || width <= 0 || height <= 0 || stride_floats < width || !depth_image ||
-      (n > 0 && (!kx || !ky || !kux || !u_right || !depth)))
-    return fail(ORBFE_ERR_INVALID, "stereo_from_rgbd: bad argument");
-  for (int i = 0; i < n; i++)
-    if (!(kx[i] >= 0 && ky[i] >= 0 && (int)kx[i] < width && (int)ky[i] < height))
-      return fail(ORBFE_ERR_INVALID, "stereo_from_rgbd: keypoint outside the depth image");
-  if (n == 0) return ORBFE_OK;
-  HIPCHK(hipSetDevice(device));
-  DevBuf<float> buf;
-  const size_t img = (size_t)width * height;
-  const int rc = buf.alloc(img + 5 * (size_t)n);
-  if (rc) return rc;
-  float *dimg = buf, *dkx = buf + img, *dky = dkx + n, *dkux = dky + n, *dur = dkux + n, *ddp = dur + n;
-  HIPCHK(hipMemcpy2D(dimg, (size_t)width * 4, depth_image, (size_t)stride_floats * 4, (size_t)width * 4, height, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dkx, kx, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dky, ky, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dkux, kux, (size_t)n * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_stereo_from_rgbd, dim3((n + 255) / 256), dim3(256), 0, 0, dkx, dky, dkux, n, dimg, width, mbf, dur, ddp);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(u_right, dur, (size_t)n * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(depth, ddp, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return ORBFE_OK;
+void launch_init_rectify_map(hipStream_t s, const RectifyMapParams& p, float* mapX, float* mapY) {
+  hipLaunchKernelGGL(k_init_rectify_map, dim3((p.h + 63) / 64), dim3(64), 0, s, p, mapX, mapY);
 }
+
+void launch_undistort_points(hipStream_t s, const UndistortParams& p, const float* xy, int n, float* out) {
+  hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, s, p, xy, n, out);
+}
+
+void launch_undistort_keypoints(hipStream_t s, const UndistortParams& p, const float* kp, const int32_t* nKp, int capacity,
+                                int nFrames, float* out) {
+  hipLaunchKernelGGL(k_undistort_keypoints, dim3((capacity + 255) / 256, nFrames), dim3(256), 0, s, p, kp, nKp, capacity, out);
+}
+
+void launch_stereo_from_rgbd(hipStream_t s, const float* kx, const float* ky, const float* kux, int n, const float* depthImg,
+                             int stride, float mbf, float* uRight, float* depth) {
+  hipLaunchKernelGGL(k_stereo_from_rgbd, dim3((n + 255) / 256), dim3(256), 0, s, kx, ky, kux, n, depthImg, stride, mbf, uRight,
+                     depth);
+}
+
+}  // namespace orbfe
+

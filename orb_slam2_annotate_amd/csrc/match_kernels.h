@@ -56,7 +56,7 @@ struct StereoBatch {  // frames 2p / 2p+1 of an extractor batch are the left / r
   float* uRight; float* depth; int32_t* sad;   // [nPairs * capacity]
 };
 
-// DBoW2 vocabulary tree on the device (vocabulary.hip).  Nodes are renumbered breadth-first so that the children of a
+// DBoW2 vocabulary tree on the device (vocabulary.hip; its kernels: k_vocab.hip).  Nodes are renumbered breadth-first so that the children of a
 // node are ADJACENT records, in file order (the order TemplatedVocabulary::transform scans them in, :1236-1250): one
 // level of the descent is one contiguous read of nChild x 48 bytes, and the record a lane loads to take its child's
 // distance already carries what the next level needs if that child wins.
@@ -86,6 +86,11 @@ struct FeatVecBatch {
   int32_t* fvCount;          // [nFrames] nodes per frame
 };
 void launch_vocab_featvec(hipStream_t s, const VocabDevice& v, const FeatVecBatch& b, int nFrames, int nidLevel);
+// the descent alone (k_vocab.hip): descriptors [0, nPerFrame[f]) -- nPerFrame NULL: [0, nFixed) -- of every frame; word /
+// weight / node / keys each optional
+void launch_vocab_transform(hipStream_t s, const VocabDevice& v, const uint8_t* desc, const int32_t* nPerFrame, int nFixed,
+                            int capacity, int frameStep, int nFrames, int nidLevel, uint32_t* word, double* weight, uint32_t* node,
+                            unsigned long long* keys);
 
 struct BowBatch {  // consecutive-frame SearchByBoW over a device-resident batch
   const float* kp; const uint8_t* desc; int capacity;

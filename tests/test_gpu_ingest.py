@@ -289,3 +289,185 @@ def test_euroc_stereo_chain_matches_oracle(streams):
                 tot_bow += rn
             prev = (kL, dL, fv)
         assert tot_st > 0.4 * P * NF
+
+
+# ---- the host-array calls on the calling thread's arena: strides and padding, regrow, refused calls -------------------------
+PAD = 0xA5
+
+
+def _strided(a, stride):
+    """(buffer pre-filled with PAD whose rows are `stride` elements apart, its [h, w] view holding a)."""
+    h, w = a.shape
+    buf = np.full((h, stride), PAD, a.dtype) if a.dtype == np.uint8 else np.full((h, stride), np.nan, a.dtype)
+    buf[:, :w] = a
+    return buf, buf[:, :w]
+
+
+def _cvt_gray_c(img, rgb, stride, dst_stride):
+    """orbfe_cvt_gray through the C ABI: rows `stride` / `dst_stride` bytes apart -> (the result, the whole destination)."""
+    import orb_slam2_annotate_amd as amd
+    h, w, c = img.shape
+    src, _ = _strided(img.reshape(h, w * c), stride)
+    dst = np.full((h, dst_stride), PAD, np.uint8)
+    amd._lib.check(amd._lib.load().orbfe_cvt_gray(0, amd._lib.ptr(src), w, h, stride, c, int(rgb), amd._lib.ptr(dst), dst_stride))
+    return dst[:, :w], dst
+
+
+def _gray_ref(img, rgb):
+    h, w, c = img.shape
+    ref = np.zeros((h, w), np.uint8)
+    orc.lib().orc_cvt_gray(orc._p(img), w, h, w * c, c, int(rgb), orc._p(ref), w)
+    return ref
+
+
+@pytest.mark.parametrize("w,h", [(5, 3), (1025, 2)])  # (1025: across the 1024-pixel block edge and the 4-pixel store)
+@pytest.mark.parametrize("channels", [3, 4])
+def test_cvt_gray_strided_rows_leave_the_padding_alone(channels, w, h):
+    rng = np.random.default_rng(w + channels)
+    img = rng.integers(0, 256, size=(h, w, channels), dtype=np.uint8)
+    ref = _gray_ref(img, True)
+    got, whole = _cvt_gray_c(img, True, w * channels + 7, w + 3)
+    assert np.array_equal(got, ref)
+    assert (whole[:, w:] == PAD).all()
+    tight, _ = _cvt_gray_c(img, True, w * channels, w)
+    assert np.array_equal(tight, got)
+
+
+def test_remap_and_rectifier_create_strided_rows():
+    """131 x 77 source rows 140 bytes apart, 5 x 3 maps rows width + 5 floats apart, destination rows 9 bytes apart."""
+    import orb_slam2_annotate_amd as amd
+    L, ptr, check = amd._lib.load(), amd._lib.ptr, amd._lib.check
+    rng = np.random.default_rng(21)
+    sw, sh, w, h = 131, 77, 5, 3
+    img = rng.integers(0, 256, (sh, sw), dtype=np.uint8)
+    mx = rng.uniform(-2, sw + 1, (h, w)).astype(np.float32)
+    my = rng.uniform(-2, sh + 1, (h, w)).astype(np.float32)
+    ref = orc.remap_linear(img, mx, my)
+
+    def run(src_stride, map_stride, dst_stride):
+        src, _ = _strided(img, src_stride)
+        bx, _ = _strided(mx, map_stride)
+        by, _ = _strided(my, map_stride)
+        hd = C.c_void_p()
+        check(L.orbfe_rectifier_create(0, ptr(bx), ptr(by), w, h, map_stride, C.byref(hd)))
+        dst = np.full((h, dst_stride), PAD, np.uint8)
+        try:
+            check(L.orbfe_remap(hd, ptr(src), sw, sh, src_stride, ptr(dst), dst_stride))
+        finally:
+            L.orbfe_rectifier_destroy(hd)
+        assert np.isnan(bx[:, w:]).all() and np.isnan(by[:, w:]).all()  # (inputs: not written either)
+        return dst[:, :w], dst
+
+    got, whole = run(140, w + 5, 9)
+    assert np.array_equal(got, ref)
+    assert (whole[:, w:] == PAD).all()
+    assert np.array_equal(run(sw, w, w)[0], got)
+    assert np.array_equal(run(sw, w + 5, w)[0], got) and np.array_equal(run(140, w, 9)[0], got)
+
+
+@pytest.mark.parametrize("n", [1, 300])
+def test_stereo_from_rgbd_strided_depth_image(n):
+    import orb_slam2_annotate_amd as amd
+    L, ptr, check = amd._lib.load(), amd._lib.ptr, amd._lib.check
+    rng = np.random.default_rng(30 + n)
+    w, h, stride = 7, 5, 11
+    depth = np.where(rng.random((h, w)) < 0.7, rng.uniform(0.4, 8.0, (h, w)), 0.0).astype(np.float32)
+    kx = rng.uniform(0, w - 0.01, n).astype(np.float32)
+    ky = rng.uniform(0, h - 0.01, n).astype(np.float32)
+    kux = (kx + rng.normal(0, 0.5, n)).astype(np.float32)
+    ur_ref, dp_ref = orc.stereo_from_rgbd(kx, ky, kux, depth, 40.0)
+
+    def run(stride):
+        buf, _ = _strided(depth, stride)
+        ur, dp = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        check(L.orbfe_stereo_from_rgbd(0, ptr(kx), ptr(ky), ptr(kux), n, ptr(buf), w, h, stride, 40.0, ptr(ur), ptr(dp)))
+        assert np.isnan(buf[:, w:]).all()
+        return ur, dp
+
+    ur, dp = run(stride)
+    assert np.array_equal(ur, ur_ref[:n]) and np.array_equal(dp, dp_ref[:n])
+    ur_t, dp_t = run(w)
+    assert np.array_equal(ur_t.view(np.uint32), ur.view(np.uint32)) and np.array_equal(dp_t.view(np.uint32), dp.view(np.uint32))
+
+
+def test_the_thread_arena_regrows_and_is_reused_by_smaller_calls():
+    """5 x 3, 640 x 480, 5 x 3 again, then undistort_points with n = 1, 4, 2000 on the same thread: each equals the oracle."""
+    import orb_slam2_annotate_amd as amd
+    rng = np.random.default_rng(8)
+    for w, h in ((5, 3), (640, 480), (5, 3)):
+        img = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+        assert np.array_equal(amd.cvtColorToGray(img, True), _gray_ref(img, True)), (w, h)
+    for n in (1, 4, 2000):
+        pts = np.stack([rng.uniform(-20, 660, n), rng.uniform(-20, 500, n)], axis=1).astype(np.float32)
+        got = amd.undistortPoints(pts, TUM1_K, TUM1_D)
+        assert np.array_equal(got.view(np.uint32), orc.undistort_points(pts, TUM1_K, TUM1_D).view(np.uint32)), n
+
+
+def test_a_refused_call_enqueues_nothing_and_the_next_one_succeeds():
+    """One bad argument per moved call: ORBFE_ERR_INVALID with the text it always had, the thread's stream idle straight after
+    the refusal, and a good call of the same function on the same thread afterwards."""
+    torch = pytest.importorskip("torch")
+    import orb_slam2_annotate_amd as amd
+    L, ptr = amd._lib.load(), amd._lib.ptr
+    rng = np.random.default_rng(9)
+    img = rng.integers(0, 256, size=(3, 5, 3), dtype=np.uint8)
+    gray = np.zeros((3, 5), np.uint8)
+    desc = rng.integers(0, 256, size=(4, 32), dtype=np.uint8)
+    off = np.array([0, 4], np.int32)
+    best = np.zeros(1, np.int32)
+    x, y = np.meshgrid(np.arange(5, dtype=np.float32), np.arange(3, dtype=np.float32))
+    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    r = amd.Rectifier(x, y)
+    src = rng.integers(0, 256, (3, 5), dtype=np.uint8)
+    K = np.array([[500.0, 0, 2], [0, 500, 1], [0, 0, 1]])
+    D4 = np.zeros(4)
+    mx, my = np.zeros((3, 5), np.float32), np.zeros((3, 5), np.float32)
+    pts = np.array([[1.0, 2.0]], np.float32)
+    out = np.zeros_like(pts)
+    b4 = np.zeros(4, np.float32)
+    kx, ky = np.array([1.0], np.float32), np.array([1.0], np.float32)
+    depth = np.ones((3, 5), np.float32)
+    ur, dp = np.zeros(1, np.float32), np.zeros(1, np.float32)
+    hd = C.c_void_p()
+    dev = torch.device("cuda", 0)
+    d_img = torch.from_numpy(img).to(dev)
+    d_gray = torch.zeros((3, 5), dtype=torch.uint8, device=dev)
+    d_kp = torch.zeros((1, 8, 7), dtype=torch.float32, device=dev)
+    d_un = torch.zeros((1, 8, 7), dtype=torch.float32, device=dev)
+    d_n = torch.zeros((1,), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    dp_ = lambda t: C.c_void_p(t.data_ptr())
+    cases = [  # (text, the refused call, the good call)
+        ("cvt_gray: bad argument", lambda: L.orbfe_cvt_gray(0, ptr(img), 5, 3, 14, 3, 1, ptr(gray), 5),
+         lambda: L.orbfe_cvt_gray(0, ptr(img), 5, 3, 15, 3, 1, ptr(gray), 5)),
+        ("cvt_gray_batch_device: bad argument", lambda: L.orbfe_cvt_gray_batch_device(0, dp_(d_img), 1, 5, 3, 15, 45, 2, 1, dp_(d_gray), 5, 15),
+         lambda: L.orbfe_cvt_gray_batch_device(0, dp_(d_img), 1, 5, 3, 15, 45, 3, 1, dp_(d_gray), 5, 15)),
+        ("distinctive_descriptors: offsets[0] != 0", lambda: L.orbfe_distinctive_descriptors(0, ptr(desc), ptr(np.array([1, 4], np.int32)), 1, ptr(best)),
+         lambda: L.orbfe_distinctive_descriptors(0, ptr(desc), ptr(off), 1, ptr(best))),
+        ("remap_create: bad argument", lambda: L.orbfe_rectifier_create(0, ptr(x), ptr(y), 5, 3, 4, C.byref(hd)),
+         lambda: (L.orbfe_rectifier_create(0, ptr(x), ptr(y), 5, 3, 5, C.byref(hd)), L.orbfe_rectifier_destroy(hd))[0]),
+        ("remap: bad argument", lambda: L.orbfe_remap(r._h, ptr(src), 5, 3, 5, ptr(gray), 4),
+         lambda: L.orbfe_remap(r._h, ptr(src), 5, 3, 5, ptr(gray), 5)),
+        ("remap_batch_device: bad argument", lambda: L.orbfe_remap_batch_device(r._h, dp_(d_gray), 1, 5, 3, 4, 15, dp_(d_gray), 5, 15),
+         lambda: L.orbfe_remap_batch_device(r._h, dp_(d_img), 1, 5, 3, 5, 15, dp_(d_gray), 5, 15)),
+        ("init_undistort_rectify_map: bad argument (K, the maps and 0 / 4 / 5 / 8 distortion coefficients are required)",
+         lambda: L.orbfe_init_undistort_rectify_map(0, ptr(K), ptr(D4), 3, None, None, 5, 3, ptr(mx), ptr(my)),
+         lambda: L.orbfe_init_undistort_rectify_map(0, ptr(K), ptr(D4), 4, None, None, 5, 3, ptr(mx), ptr(my))),
+        ("undistort_points: bad argument", lambda: L.orbfe_undistort_points(0, ptr(pts), 1, ptr(TUM1_K), ptr(TUM1_D), 3, ptr(out)),
+         lambda: L.orbfe_undistort_points(0, ptr(pts), 1, ptr(TUM1_K), ptr(TUM1_D), 5, ptr(out))),
+        ("undistort_keypoints_batch_device: bad argument",
+         lambda: L.orbfe_undistort_keypoints_batch_device(0, dp_(d_kp), dp_(d_n), 1, 0, ptr(TUM1_K), ptr(TUM1_D), 5, dp_(d_un)),
+         lambda: L.orbfe_undistort_keypoints_batch_device(0, dp_(d_kp), dp_(d_n), 1, 8, ptr(TUM1_K), ptr(TUM1_D), 5, dp_(d_un))),
+        ("compute_image_bounds: bad argument", lambda: L.orbfe_compute_image_bounds(0, 0, 480, ptr(TUM1_K), ptr(TUM1_D), 5, ptr(b4)),
+         lambda: L.orbfe_compute_image_bounds(0, 640, 480, ptr(TUM1_K), ptr(TUM1_D), 5, ptr(b4))),
+        ("stereo_from_rgbd: keypoint outside the depth image",
+         lambda: L.orbfe_stereo_from_rgbd(0, ptr(np.array([5.0], np.float32)), ptr(ky), ptr(kx), 1, ptr(depth), 5, 3, 5, 40.0, ptr(ur), ptr(dp)),
+         lambda: L.orbfe_stereo_from_rgbd(0, ptr(kx), ptr(ky), ptr(kx), 1, ptr(depth), 5, 3, 5, 40.0, ptr(ur), ptr(dp))),
+    ]
+    assert L.orbfe_debug_thread_stream_idle(0) == 1  # (the stream exists and nothing is on it)
+    for text, refused, good in cases:
+        assert refused() == amd._lib.ERR_INVALID, text
+        assert L.orbfe_last_error().decode() == text
+        assert L.orbfe_debug_thread_stream_idle(0) == 1, text
+        assert good() == amd._lib.ORBFE_OK, (text, L.orbfe_last_error().decode())
+    assert b4[0] < b4[1] and np.array_equal(gray, src)  # (the last remap ran: the identity map)

@@ -412,3 +412,123 @@ def test_gpu_one_handle_regrows_its_buffers_like_fresh_handles(tmp_path):
         got, fresh = match(one, d_desc, d_kp, d_n, F, cap), match(handle(), d_desc, d_kp, d_n, F, cap)
         assert np.array_equal(got[0], fresh[0]) and np.array_equal(got[1], fresh[1]), (F, cap)
         assert got[1].min() > 0, got[1]  # (the pairs do match: the comparison is not of two empty results)
+
+
+# ---- transform and featvec_batch_device on the calling thread's arena: nothing kept on the handle --------------------------
+@pytest.fixture(scope="module")
+def k10_L2():
+    """(the arrays of a k = 10, L = 2 synthetic tree, the oracle built from them)"""
+    arrays = synthetic_vocabulary_arrays(10, 2, 7)
+    return arrays, orc.Vocabulary.from_arrays(arrays)
+
+
+def _same_transform(got, ref):
+    return np.array_equal(got[0], ref[1]) and np.array_equal(got[1], ref[2]) and np.array_equal(got[2], ref[3])
+
+
+@pytest.mark.gpu
+def test_gpu_transform_on_the_thread_arena_small_large_small(k10_L2):
+    """n = 1, 33 (one over a workgroup's 32 descriptors), 300, then 1 again on one handle and one thread."""
+    import orb_slam2_annotate_amd as amd
+    arrays, vo = k10_L2
+    voc = amd.ORBVocabulary()
+    assert voc.createFromArrays(arrays)
+    rng = np.random.default_rng(31)
+    for n in (1, 33, 300, 1):
+        desc = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+        assert _same_transform(voc.transform_features(desc, 1), vo.transform(desc, 1)), n
+
+
+@pytest.mark.gpu
+def test_gpu_featvec_batch_before_and_after_a_large_transform(k10_L2):
+    """2 frames x capacity 40 before and after a transform of n = 2000 on the same thread (the arena regrows in between)."""
+    torch = pytest.importorskip("torch")
+    import orb_slam2_annotate_amd as amd
+    arrays, vo = k10_L2
+    voc = amd.ORBVocabulary()
+    assert voc.createFromArrays(arrays)
+    rng = np.random.default_rng(32)
+    F, cap = 2, 40
+    dev = torch.device("cuda", 0)
+    desc = rng.integers(0, 256, size=(F, cap, 32), dtype=np.uint8)
+    n = np.array([cap, 23], np.int32)
+    d_desc, d_n = torch.from_numpy(desc).to(dev), torch.from_numpy(n).to(dev)
+
+    def featvec_equals_oracle():
+        out = [torch.zeros((F, cap), dtype=torch.int32, device=dev), torch.zeros((F, cap + 1), dtype=torch.int32, device=dev),
+               torch.zeros((F, cap), dtype=torch.int32, device=dev), torch.zeros((F,), dtype=torch.int32, device=dev)]
+        torch.cuda.synchronize()
+        voc.featvec_batch_device(d_desc.data_ptr(), d_n.data_ptr(), F, cap, *[t.data_ptr() for t in out], levelsup=1)
+        nodes, off, idx, cnt = [t.cpu().numpy() for t in out]
+        for f in range(F):
+            used, word, weight, node = vo.transform(desc[f, :n[f]], 1)
+            fv = orc.FeatVec(node, weight > 0)
+            c = int(cnt[f])
+            assert c == len(fv.node_ids) and c > 0
+            assert np.array_equal(nodes[f, :c].astype(np.uint32), fv.node_ids)
+            assert np.array_equal(off[f, :c + 1], fv.offsets)
+            assert np.array_equal(idx[f, :used].astype(np.uint32), fv.indices)
+
+    featvec_equals_oracle()
+    big = rng.integers(0, 256, size=(2000, 32), dtype=np.uint8)
+    assert _same_transform(voc.transform_features(big, 1), vo.transform(big, 1))
+    featvec_equals_oracle()
+
+
+@pytest.mark.gpu
+def test_gpu_two_threads_transform_on_one_handle(k10_L2):
+    """Two threads, 20 transform calls each on ONE handle, n alternating 7 and 300 on different descriptors: every result
+    equals the sequential result of the same input (the handle keeps no scratch: each thread stages through its own arena)."""
+    import threading
+
+    import orb_slam2_annotate_amd as amd
+    arrays, _ = k10_L2
+    voc = amd.ORBVocabulary()
+    assert voc.createFromArrays(arrays)
+    rng = np.random.default_rng(33)
+    inputs = [[rng.integers(0, 256, size=(7 if (i + t) % 2 else 300, 32), dtype=np.uint8) for i in range(20)] for t in range(2)]
+    sequential = [[voc.transform_features(d, 1) for d in row] for row in inputs]
+    got, errors = [[None] * 20, [None] * 20], []
+    barrier = threading.Barrier(2)
+
+    def work(t):
+        try:
+            barrier.wait(timeout=30)
+            for i, d in enumerate(inputs[t]):
+                got[t][i] = voc.transform_features(d, 1)
+        except Exception as e:  # noqa: BLE001 -- reported by the assertion below
+            errors.append((t, repr(e)))
+
+    threads = [threading.Thread(target=work, args=(t,)) for t in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors
+    for t in range(2):
+        for i in range(20):
+            assert all(np.array_equal(a, b) for a, b in zip(got[t][i], sequential[t][i])), (t, i)
+
+
+@pytest.mark.gpu
+def test_gpu_refused_vocabulary_calls_enqueue_nothing(k10_L2):
+    import ctypes as C
+
+    import orb_slam2_annotate_amd as amd
+    arrays, vo = k10_L2
+    voc = amd.ORBVocabulary()
+    assert voc.createFromArrays(arrays)
+    L, ptr = amd._lib.load(), amd._lib.ptr
+    desc = np.random.default_rng(34).integers(0, 256, size=(5, 32), dtype=np.uint8)
+    word, node, weight = np.zeros(5, np.uint32), np.zeros(5, np.uint32), np.zeros(5, np.float64)
+    assert L.orbfe_debug_thread_stream_idle(0) == 1
+    assert L.orbfe_vocabulary_transform(voc._h, ptr(desc), 5, 1, None, ptr(weight), ptr(node)) == amd._lib.ERR_INVALID
+    assert L.orbfe_last_error().decode() == "vocabulary_transform: bad argument"
+    assert L.orbfe_debug_thread_stream_idle(0) == 1
+    one = C.c_void_p(8)  # (a refused call dereferences nothing)
+    assert L.orbfe_vocabulary_featvec_batch_device(voc._h, one, one, 1, 0, 1, one, one, one, one, None, None) == amd._lib.ERR_INVALID
+    assert L.orbfe_last_error().decode() == "vocabulary_featvec_batch_device: bad argument"
+    assert L.orbfe_debug_thread_stream_idle(0) == 1
+    ref = vo.transform(desc, 1)
+    assert L.orbfe_vocabulary_transform(voc._h, ptr(desc), 5, 1, ptr(word), ptr(weight), ptr(node)) == ref[0]
+    assert _same_transform((word, weight, node), ref)
