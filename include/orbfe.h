@@ -1909,6 +1909,67 @@ int orbfe_gba_update_mappoints(orbfe_obsgraph *g, orbfe_mappoints *mp, int n, co
                                const float *pos_gba, int m, const int32_t *kf_slot, const uint8_t *reached, const float *Tcw_bef,
                                const float *Twc_new, uint8_t *moved);
 
+/* ---- Where stereo and RGB-D map points are born: Tracking::StereoInitialization (src/Tracking.cc:563-578, mode ALL),
+ * the depth-sorted loop of Tracking::CreateNewKeyFrame (:1182-1234, mode KEYFRAME) and the same loop of
+ * Tracking::UpdateLastFrame (:899-949, mode TEMPORAL: the visual-odometry points of localisation mode, made by the Frame
+ * constructor of MapPoint, src/MapPoint.cc:46-71).  IEEE binary32 with no contraction, binary64 where stated.
+ *   Selection.  Candidates are the keypoints with depth > 0: NaN, zero and negative depths are none, +inf is one.  ALL: the
+ *   candidates in ascending index, each created, the occupied mask not read.  KEYFRAME / TEMPORAL: the candidates ordered as
+ *   std::sort orders pair<float, int> (ascending z, ties by ascending index); candidate j = 0, 1, .. is created unless
+ *   occupied[i] (mvpMapPoints[i] && Observations() >= 1); after handling candidate j the walk stops when z_j > th_depth &&
+ *   j + 1 > 100 (nPoints grows in both branches of :1213-1229), so z == th_depth goes on and 100 or fewer candidates are
+ *   all handled.  KEYFRAME also returns cleared[i] = 1 for a created keypoint with stale[i] set (a point with
+ *   Observations() < 1, :1207-1211: the caller's mvpMapPoints[i] is dropped); occupied and stale on one keypoint is an error.
+ *   Either mask may be NULL (none set).
+ *   Frame::UnprojectStereo (src/Frame.cc:713-727).  x = ((u - cx) * z) * invfx, y likewise, u / v = mvKeysUn[i].pt, invfx =
+ *   1.0f / fx; P_r = (float)((double)Rwc_r0 x + (double)Rwc_r1 y + (double)Rwc_r2 z + (double)Ow_r), added left to right, Rwc the
+ *   exact transpose of pose.Rcw: the CV_32F gemm-with-beta restatement of the loop correction above (and, as there, not
+ *   checked against OpenCV's small-matrix path, whose source was not at hand).  A NaN that an infinite depth produces has
+ *   no defined sign or payload.
+ *   Normal and range.  orbfe_obsgraph_update_normal_depth for a row of one entry: d = P - C; nrm = sqrt(sum (double)d_i^2);
+ *   normal_i = (0.0f + d_i * (float)(1.0 / nrm)) * (float)(1.0 / 1); dist = (float)nrm; max_dist = dist *
+ *   scale_factors[octave_i]; min_dist = max_dist / scale_factors[n_levels - 1].  ALL / KEYFRAME: C is the key frame's centre;
+ *   TEMPORAL: C = pose.Ow (mNormalVector / cv::norm(mNormalVector) of the Frame constructor is the same expression).
+ *   The descriptor is the frame's row i.  Flags: not bad; ORBFE_MP_OBSERVED in ALL / KEYFRAME, clear in TEMPORAL (nObs == 0). */
+#define ORBFE_STEREO_ALL 0
+#define ORBFE_STEREO_KEYFRAME 1
+#define ORBFE_STEREO_TEMPORAL 2
+/* The definition, on arrays: x / y / octave / depth [n], occupied / stale [n] or NULL, centre [3] = C.  created_idx: the
+ * keypoint indices in creation order, *n_created of them, with pos / normal [.,3] and min_dist / max_dist aligned; cleared
+ * [n] (may be NULL); *n_walked: the candidates handled before the stop.  More created points than `capacity` returns
+ * ORBFE_ERR_CAPACITY with both counts set and no array written.  ORBFE_ERR_INVALID with nothing written: n < 0 or
+ * n > 16384, an unknown mode, n_levels outside 1 .. 256, an octave outside [0, n_levels), a non-finite pose or centre,
+ * fx == 0 or fy == 0, a keypoint both occupied and stale, NULL arrays.  Host code: needs no device. */
+int orbfe_stereo_points_select(int n, const float *x, const float *y, const int32_t *octave, const float *depth,
+                               const uint8_t *occupied, const uint8_t *stale, const orbfe_camera_pose *pose, float th_depth, int mode,
+                               const float *scale_factors, int n_levels, const float *centre, int capacity, int32_t *created_idx,
+                               float *pos, float *normal, float *min_dist, float *max_dist, uint8_t *cleared, int32_t *n_created,
+                               int32_t *n_walked);
+/* nTrackedClose / nNonTrackedClose of Tracking::NeedNewKeyFrame (:1100-1114): over the keypoints with 0 < depth < th_depth,
+ * strict on both sides, has_point[i] && !outlier[i] counts as tracked, every other one as not tracked.  Host code. */
+int orbfe_count_close_points(int n, const float *depth, const uint8_t *has_point, const uint8_t *outlier, float th_depth,
+                             int32_t *n_tracked_close, int32_t *n_non_tracked_close);
+/* The same selection and arithmetic on the resident state, in one call: keypoints, octaves, descriptors and the stereo bit
+ * are read from the resident frame F (n must be its keypoint count); the depth array, the two masks, the slot list, the pose
+ * and the level table go up; created point number j takes new_slot[j] (capacity entries) and its position, normal, range,
+ * descriptor and flags are written straight into mp's rows, bit-equal to orbfe_stereo_points_select with C = the centre g
+ * holds for kf_slot (TEMPORAL: pose.Ow) -- and so to a later orbfe_obsgraph_update_normal_depth_mappoints on the new slots.
+ * One kernel (the keys bits(z) << 32 | i sorted in one workgroup's LDS), one copy back: created_idx / created_slot
+ * [*n_created], cleared [n], *n_walked.  More created points than `capacity` returns ORBFE_ERR_CAPACITY with *n_created the
+ * needed count and neither table touched.  In modes ALL and KEYFRAME the map bookkeeping of :1216-1221 is then applied to
+ * g's mirror in creation order: set_points(bad = 0, ref = kf_slot), add_observations(slot, kf_slot, idx, octave, the frame's
+ * own mvuRight >= 0 bit) and, when key-frame rows are enabled, assign_keyframe_points.  TEMPORAL reads no graph (g may be
+ * NULL).  ORBFE_ERR_INVALID before anything is enqueued: what orbfe_stereo_points_select rejects; n != F's count; g NULL
+ * outside TEMPORAL; kf_slot out of range or never set; a new slot out of range, named twice, at or past g's point capacity,
+ * or whose graph row is live (only a slot never set, or bad with an empty row, is free); key-frame rows enabled and
+ * kf_slot's row shorter than n; handles on different devices.  n == 0 or no candidate is ORBFE_OK with zero counts and no
+ * launch.  Takes g's serialisation, then mp's; complete on return. */
+int orbfe_create_stereo_points(orbfe_mappoints *mp, orbfe_obsgraph *g /* NULL only in TEMPORAL */, const orbfe_frame *F, int kf_slot,
+                               const orbfe_camera_pose *pose, int n, const float *depth, const uint8_t *occupied,
+                               const uint8_t *stale, float th_depth, int mode, const float *scale_factors, int n_levels,
+                               const int32_t *new_slot, int capacity, int32_t *created_idx, int32_t *created_slot, uint8_t *cleared,
+                               int32_t *n_created, int32_t *n_walked);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1149,6 +1149,37 @@ class MapPointTable {
     moved.resize(n);
     return moved;
   }
+  // Where stereo / RGB-D map points are born, on the table (orbfe_create_stereo_points): Tracking::StereoInitialization
+  // (src/Tracking.cc:563-578, mode ORBFE_STEREO_ALL), the depth-sorted loop of Tracking::CreateNewKeyFrame (:1182-1234,
+  // ORBFE_STEREO_KEYFRAME) and of Tracking::UpdateLastFrame (:899-949, ORBFE_STEREO_TEMPORAL; graph may be NULL).  F must
+  // be resident; mvDepth one entry per keypoint; newSlot = free slots, taken in creation order (its size is the capacity);
+  // occupied (mvpMapPoints[i] && Observations() >= 1) and stale (a point with Observations() < 1) may be empty.  In modes
+  // ALL and KEYFRAME the graph receives the points, their observation by kfSlot and -- with key-frame rows enabled --
+  // kfSlot's mvpMapPoints entries.  More created points than newSlot holds throws with neither table touched.
+  struct StereoPoints {
+    std::vector<int32_t> idx, slot;  // keypoint index and slot of each created point, in creation order
+    std::vector<uint8_t> cleared;    // KEYFRAME: mvpMapPoints[i] was dropped before the new point took its place
+    int walked = 0;                  // candidates handled before the stop
+  };
+  StereoPoints CreateStereoPoints(const ObservationGraph* graph, const FrameArrays& F, int kfSlot, const orbfe_camera_pose& pose,
+                                  const std::vector<float>& mvDepth, float mThDepth, int mode, const std::vector<float>& mvScaleFactors,
+                                  const std::vector<int32_t>& newSlot, const std::vector<uint8_t>& occupied = {},
+                                  const std::vector<uint8_t>& stale = {}) {
+    const size_t n = mvDepth.size();
+    if ((!occupied.empty() && occupied.size() != n) || (!stale.empty() && stale.size() != n))
+      throw std::invalid_argument("MapPointTable::CreateStereoPoints: one mask entry per keypoint");
+    StereoPoints out;
+    out.idx.assign(newSlot.size() + 1, 0); out.slot.assign(newSlot.size() + 1, 0); out.cleared.assign(n + 1, 0);
+    int32_t created = 0, walked = 0;
+    check(orbfe_create_stereo_points(h_, graph ? graph->handle() : nullptr, F.resident(), kfSlot, &pose, (int)n, mvDepth.data(),
+                                     occupied.empty() ? nullptr : occupied.data(), stale.empty() ? nullptr : stale.data(), mThDepth,
+                                     mode, mvScaleFactors.data(), (int)mvScaleFactors.size(), newSlot.data(), (int)newSlot.size(),
+                                     out.idx.data(), out.slot.data(), out.cleared.data(), &created, &walked),
+          "MapPointTable::CreateStereoPoints");
+    out.idx.resize((size_t)created); out.slot.resize((size_t)created); out.cleared.resize(n);
+    out.walked = walked;
+    return out;
+  }
   // GetDescriptor of slot[] as the table holds it (32 bytes each)
   std::vector<uint8_t> Descriptors(const std::vector<int32_t>& slot) const {
     std::vector<uint8_t> out(32 * slot.size() + 1);
@@ -1202,6 +1233,54 @@ class LoopClosing {
                                         out.visited.data()), "LoopClosing::PropagateGBA");
     out.TcwNew.resize(16 * n); out.reached.resize(n); out.visited.resize(n);
     return out;
+  }
+};
+
+// The host definitions behind MapPointTable::CreateStereoPoints and the close-point counts of Tracking::NeedNewKeyFrame
+// (src/Tracking.cc:1100-1114); neither needs a device.
+class Tracking {
+ public:
+  struct StereoSelection {
+    std::vector<int32_t> idx;                  // created keypoints, in creation order
+    std::vector<float> pos, normal;            // 3 floats each
+    std::vector<float> minDist, maxDist;       // the raw mfMinDistance / mfMaxDistance
+    std::vector<uint8_t> cleared;
+    int walked = 0;
+  };
+  // orbfe_stereo_points_select: x / y / octave = mvKeysUn, centre = the camera centre normal and range are taken from (the
+  // key frame's; pose.Ow for the temporal points); occupied / stale may be empty
+  static StereoSelection SelectStereoPoints(const std::vector<float>& x, const std::vector<float>& y, const std::vector<int32_t>& octave,
+                                            const std::vector<float>& mvDepth, const orbfe_camera_pose& pose, float mThDepth, int mode,
+                                            const std::vector<float>& mvScaleFactors, const float centre[3],
+                                            const std::vector<uint8_t>& occupied = {}, const std::vector<uint8_t>& stale = {}) {
+    const size_t n = mvDepth.size();
+    if (x.size() != n || y.size() != n || octave.size() != n || (!occupied.empty() && occupied.size() != n) ||
+        (!stale.empty() && stale.size() != n))
+      throw std::invalid_argument("Tracking::SelectStereoPoints: one entry per keypoint");
+    StereoSelection out;
+    out.idx.assign(n + 1, 0); out.pos.assign(3 * n + 1, 0.f); out.normal.assign(3 * n + 1, 0.f);
+    out.minDist.assign(n + 1, 0.f); out.maxDist.assign(n + 1, 0.f); out.cleared.assign(n + 1, 0);
+    int32_t created = 0, walked = 0;
+    check(orbfe_stereo_points_select((int)n, x.data(), y.data(), octave.data(), mvDepth.data(), occupied.empty() ? nullptr : occupied.data(),
+                                     stale.empty() ? nullptr : stale.data(), &pose, mThDepth, mode, mvScaleFactors.data(),
+                                     (int)mvScaleFactors.size(), centre, (int)n, out.idx.data(), out.pos.data(), out.normal.data(),
+                                     out.minDist.data(), out.maxDist.data(), out.cleared.data(), &created, &walked),
+          "Tracking::SelectStereoPoints");
+    const size_t m = (size_t)created;
+    out.idx.resize(m); out.pos.resize(3 * m); out.normal.resize(3 * m); out.minDist.resize(m); out.maxDist.resize(m);
+    out.cleared.resize(n);
+    out.walked = walked;
+    return out;
+  }
+  // (nTrackedClose, nNonTrackedClose): 0 < mvDepth[i] < mThDepth; hasPoint[i] = mvpMapPoints[i] != NULL, outlier = mvbOutlier
+  static std::pair<int, int> CountClosePoints(const std::vector<float>& mvDepth, const std::vector<uint8_t>& hasPoint,
+                                              const std::vector<uint8_t>& outlier, float mThDepth) {
+    if (hasPoint.size() != mvDepth.size() || outlier.size() != mvDepth.size())
+      throw std::invalid_argument("Tracking::CountClosePoints: one entry per keypoint");
+    int32_t tracked = 0, nonTracked = 0;
+    check(orbfe_count_close_points((int)mvDepth.size(), mvDepth.data(), hasPoint.data(), outlier.data(), mThDepth, &tracked, &nonTracked),
+          "Tracking::CountClosePoints");
+    return {tracked, nonTracked};
   }
 };
 

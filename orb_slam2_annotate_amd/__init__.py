@@ -19,5 +19,6 @@ from .initializer import (Initializer, initializer_normalize, initializer_ransac
                           initializer_reconstruct, initializer_reconstruct_multi, initializer_sets_from_draws)
 from .keyframe_database import KeyFrameDatabase, bow_arrays, group_candidates  # noqa: F401
 from .observation_graph import ObservationGraph  # noqa: F401
+from .tracking import STEREO_ALL, STEREO_KEYFRAME, STEREO_TEMPORAL, count_close_points, stereo_points_select  # noqa: F401
 from .ingest import (ComputeDistinctiveDescriptors, ComputeImageBounds, ComputeStereoFromRGBD,  # noqa: F401
                      Rectifier, UndistortKeyPoints, cvtColorToGray, initUndistortRectifyMap, undistortPoints)  # noqa: F401

@@ -147,6 +147,7 @@ EXPORTS = [
     "orbfe_project_sim3", "orbfe_search_by_sim3_mappoints_multi", "orbfe_search_by_projection_sim3_mappoints",
     "orbfe_correct_loop_sim3s", "orbfe_correct_loop_points", "orbfe_correct_loop_mappoints",
     "orbfe_gba_propagate_keyframes", "orbfe_gba_update_points", "orbfe_gba_update_mappoints",
+    "orbfe_stereo_points_select", "orbfe_count_close_points", "orbfe_create_stereo_points",
 ]
 
 _lib = None
@@ -391,6 +392,9 @@ def load():
     L.orbfe_gba_propagate_keyframes.argtypes = [ci, ci] + [vp] * 10
     L.orbfe_gba_update_points.argtypes = [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
     L.orbfe_gba_update_mappoints.argtypes = [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_stereo_points_select.argtypes = [ci, vp, vp, vp, vp, vp, vp, cpp, cf, ci, vp, ci, vp, ci] + [vp] * 8
+    L.orbfe_count_close_points.argtypes = [ci, vp, vp, vp, cf, vp, vp]
+    L.orbfe_create_stereo_points.argtypes = [vp, vp, vp, ci, cpp, ci, vp, vp, vp, cf, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -305,6 +305,22 @@ struct ObsGraphMirror {
     return nullptr;
   }
 
+  // Everything set_points(bad = 0, ref = kf), add_observations(slot, kf, idx < nIdx, ..) and -- rows enabled --
+  // assign_keyframe_points(kf, idx < nIdx, slot) of n NEW points can refuse, for a caller that must know before it touches
+  // the device (stereopoints.hip): NULL when the three mutators will accept the points.  Distinct slots are the caller's.
+  const char* check_new_points(int n, const int32_t* slot, int kf, int nIdx) const {
+    if (kf < 0 || kf >= kfCap || kfs[(size_t)kf].id < 0) return "kf_slot was never set (orbfe_obsgraph_set_keyframes)";
+    if (rowWidth < 1) return "the rows hold no observation";
+    for (int j = 0; j < n; j++) {
+      if (slot[j] < 0 || slot[j] >= pointCap) return "a new slot is at or past the graph's point capacity";
+      const ObsPointMeta& m = meta[(size_t)slot[j]];
+      if (!m.bad || m.count != 0 || !rows[(size_t)slot[j]].empty()) return "a new slot's graph row is live";
+    }
+    if (nIdx > 65536) return "a keypoint index does not fit an observation";
+    if (kfRowWidth && (int)kfRows[(size_t)kf].size() < nIdx) return "kf_slot's row of map points is shorter than n";
+    return nullptr;
+  }
+
   // ---- KeyFrame::mvpMapPoints (src/KeyFrame.cc:220-243) ----
 
   void touch_kf_row(int k) {

@@ -526,6 +526,39 @@ class MapPoints:
         check(self._L.orbfe_mappoints_descriptors(self._h, len(sl), ptr(sl), ptr(out)))
         return out[:len(sl)]
 
+    def create_stereo_points(self, graph, frame, kf_slot, pose: CameraPoseC, depth, th_depth: float, mode: int, scale_factors,
+                             new_slot, occupied=None, stale=None):
+        """orbfe_create_stereo_points: the stereo / RGB-D points of Tracking::StereoInitialization (mode tracking.STEREO_ALL),
+        CreateNewKeyFrame (STEREO_KEYFRAME) or UpdateLastFrame (STEREO_TEMPORAL; graph may be None) born on the device.
+        `frame` is the ResidentFrame (keypoints, octaves, descriptors, stereo bit), depth its mvDepth, new_slot the free
+        slots the created points take in creation order (its length is the capacity), occupied / stale the masks of
+        tracking.stereo_points_select -> dict of created_idx, created_slot [m], cleared [n], n_created, n_walked.  In modes
+        ALL and KEYFRAME the graph's mirror receives the points, their observation by kf_slot and -- with key-frame rows
+        enabled -- kf_slot's mvpMapPoints entries.  More created points than len(new_slot) raises OrbfeError(ERR_CAPACITY)
+        with neither table touched."""
+        z = np.ascontiguousarray(depth, dtype=np.float32).reshape(-1)
+        n = len(z)
+        occ = None if occupied is None else np.ascontiguousarray(occupied, dtype=np.uint8).reshape(-1)
+        st = None if stale is None else np.ascontiguousarray(stale, dtype=np.uint8).reshape(-1)
+        if (occ is not None and len(occ) != n) or (st is not None and len(st) != n):
+            raise ValueError("create_stereo_points: the masks must hold one entry per keypoint")
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        ns = np.ascontiguousarray(new_slot, dtype=np.int32).reshape(-1)
+        cap = len(ns)
+        idx, slot = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        cleared = np.zeros(max(n, 1), np.uint8)
+        nc, nw = C.c_int32(0), C.c_int32(0)
+        rc = self._L.orbfe_create_stereo_points(self._h, graph._h if graph is not None else None, frame._h, int(kf_slot), C.byref(pose), n,
+                                                ptr(z), ptr(occ), ptr(st), float(th_depth), int(mode), ptr(sf), len(sf), ptr(ns), cap,
+                                                ptr(idx), ptr(slot), ptr(cleared), C.byref(nc), C.byref(nw))
+        if rc == _lib.ERR_CAPACITY:  # the needed count travels with the error
+            err = _lib.OrbfeError(rc, self._L.orbfe_last_error().decode("utf-8", "replace"))
+            err.n_created = nc.value
+            raise err
+        check(rc)
+        k = nc.value
+        return dict(created_idx=idx[:k].copy(), created_slot=slot[:k].copy(), cleared=cleared[:n].copy(), n_created=k, n_walked=nw.value)
+
     def compute_distinctive_descriptors(self, graph, slot):
         """MapPoint::ComputeDistinctiveDescriptors for slot[] on the device (orbfe_obsgraph_distinctive_descriptors_mappoints):
         `graph` is the ObservationGraph that holds the rows and the key frames' descriptors; the winners' bytes land in this
