@@ -1970,6 +1970,71 @@ int orbfe_create_stereo_points(orbfe_mappoints *mp, orbfe_obsgraph *g /* NULL on
                                const int32_t *new_slot, int capacity, int32_t *created_idx, int32_t *created_slot, uint8_t *cleared,
                                int32_t *n_created, int32_t *n_walked);
 
+/* ---- Where triangulated map points are born: the birth at the tail of LocalMapping::CreateNewMapPoints' pair loop
+ * (src/LocalMapping.cc:283-501; the neighbour loop :283, the pair loop :333, the birth :484-500), the only birth a monocular
+ * map has after initialisation.  IEEE binary32 with no contraction, binary64 where stated.
+ *   Per pair.  Status and position are orbfe_triangulate_matches_multi's, by the same code: the position is its x3d, bit
+ *   for bit.  cam.Ow is read where that call reads it (UnprojectStereo and the scale-consistency test, :465-481) and nowhere
+ *   else.
+ *   Who and in what order.  Pair (k, i1) makes a point when its status is ORBFE_TRI_CREATED and k is the smallest neighbour
+ *   index with a CREATED pair for i1 -- the `winner` rule above (AddMapPoint at :489 takes i1 out of every later
+ *   neighbour's search, src/ORBmatcher.cc:800-803).  Creation order is ascending (k, i1): the reference's two loops, with
+ *   vMatchedIndices ascending in idx1.  Created point number w takes new_slot[w].
+ *   Descriptor.  MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:269-333) at N = 2: both medians are the
+ *   self-distance 0 and `<` is strict, so the first entry of the row wins -- the key frame with the smaller mnId in the
+ *   ascending-mnId row order of orbfe_obsgraph.  The descriptor is that key frame's row (i1 of key frame 1, or i2 of the
+ *   neighbour): orbfe_obsgraph_distinctive_descriptors for a row of two entries.
+ *   Normal and range.  orbfe_obsgraph_update_normal_depth for the row of two entries A, B in ascending mnId, operation by
+ *   operation: d = P - C; a = (float)(1.0 / sqrt(sum (double)d_i^2)); normal_i = ((0.0f + dA_i * aA) + dB_i * aB) *
+ *   (float)(1.0 / 2).  The reference key frame is key frame 1 (mpRefKF = mpCurrentKeyFrame, :484): dist = (float)|P - C1|,
+ *   max_dist = dist * scale_factors[octave of keypoint i1], min_dist = max_dist / scale_factors[n_levels - 1].  In the
+ *   resident call C1 / C2 are the centres the graph holds for the kf slots -- the graph is the truth, as for
+ *   orbfe_create_stereo_points -- whatever cam.Ow says.
+ *   Flags: not bad, ORBFE_MP_OBSERVED. */
+/* The definition, on arrays: match12 / status / x3d as orbfe_triangulate_matches_multi takes and returns them ([k*n1 + i1]);
+ * kf1_id / kf2_id [K] the key frames' mnIds, centre1 [3] / centre2 [K*3] their centres, octave1 [n1] key frame 1's octaves.
+ * created_k / created_i1 / created_i2 [*n_created] in creation order with pos / normal [.,3], min_dist / max_dist and
+ * desc_from (0: key frame 1's descriptor row i1, 1: the neighbour's row i2) aligned.  More created points than `capacity`
+ * returns ORBFE_ERR_CAPACITY with *n_created set and no array written.  ORBFE_ERR_INVALID with nothing written: n1 outside
+ * [0, 16384], n_neighbours outside [0, 64], n_levels outside (0, ORBFE_MAX_LEVELS], a negative capacity or id, two equal ids,
+ * a non-finite centre, a match outside [-1, 16384), a status above ORBFE_TRI_SCALE or one that disagrees with match12 about
+ * which pairs exist, a keypoint i2 named twice within one neighbour, a created keypoint's octave outside [0, n_levels), NULL
+ * arrays.  Host code: needs no device. */
+int orbfe_triangulated_points_select(int n1, int n_neighbours, const int32_t *match12, const uint8_t *status, const float *x3d,
+                                     int64_t kf1_id, const int64_t *kf2_id, const float *centre1, const float *centre2,
+                                     const int32_t *octave1, const float *scale_factors, int n_levels, int capacity,
+                                     int32_t *created_k, int32_t *created_i1, int32_t *created_i2, float *pos, float *normal,
+                                     float *min_dist, float *max_dist, uint8_t *desc_from, int32_t *n_created);
+/* The triangulation and the birth on the resident state, in one call.  Keypoints, octaves, u_right and descriptors are read
+ * from the resident frames; the pair records (compacted from match12 in (k, i1) order), the K + 1 cameras, the K + 1 centres
+ * and mnIds g holds for kf1_slot / kf2_slot[k], the slot list and the level tables go up; one copy brings back the lists,
+ * the counts and the statuses.  Two launches on g's stream: one lane per pair solves it (as orbfe_triangulate_matches_multi)
+ * and names the winner by an integer minimum; one workgroup then places the kept pairs by prefix sums over the list and
+ * writes position, normal, range, descriptor and flags straight into mp's rows -- bit-equal to
+ * orbfe_triangulated_points_select on orbfe_triangulate_matches_multi's outputs, and so to orbfe_mappoints_update with
+ * those values followed by orbfe_obsgraph_distinctive_descriptors_mappoints and
+ * orbfe_obsgraph_update_normal_depth_mappoints on the new slots.  The map bookkeeping of :484-492 is then applied to g's
+ * mirror in creation order: set_points(bad = 0, ref = kf1_slot), add_observations(slot, kf1_slot, i1, octave1, stereo1) and
+ * (slot, kf2_slot[k], i2, octave2, stereo2) with the frames' own u_right >= 0 bit, and, when key-frame rows are enabled,
+ * assign_keyframe_points for both key frames (it overwrites, as AddMapPoint does).
+ * Outputs: created_k / created_i1 / created_i2 / created_slot [*n_created]; status [K*n1] as orbfe_triangulate_matches_multi
+ * (may be NULL); n_created_per_neighbour [K] = the points made with neighbour k (their sum is *n_created).  More created
+ * points than `capacity` returns ORBFE_ERR_CAPACITY with *n_created the needed count, the other counts and status set and
+ * neither table touched.  n_neighbours == 0 or no pair is ORBFE_OK with zero counts and no launch.
+ * ORBFE_ERR_INVALID before anything is enqueued: what orbfe_triangulate_matches_multi rejects of its inputs; a keypoint i2
+ * named twice within one neighbour; kf1_slot or a kf2_slot out of range, never set, bad, or named twice (kf1_slot among
+ * them); two key frames with the same mnId; a new slot out of range, named twice, at or past g's point capacity, or whose
+ * graph row is live; key-frame rows enabled and a row shorter than its frame's keypoint count; handles or frames on different devices; NULL arrays.  Takes g's serialisation, then mp's; complete on
+ * return. */
+int orbfe_create_triangulated_points(orbfe_mappoints *mp, orbfe_obsgraph *g, const orbfe_frame *kf1, int kf1_slot,
+                                     const orbfe_keyframe_camera *cam1, int n_neighbours, const orbfe_frame *const *kf2,
+                                     const int32_t *kf2_slot, const orbfe_keyframe_camera *cam2 /*[K]*/,
+                                     const int32_t *match12 /*[K*n1]*/, const float *scale_factors, const float *level_sigma2,
+                                     int n_levels, float ratio_factor, const int32_t *new_slot, int capacity,
+                                     int32_t *created_k, int32_t *created_i1, int32_t *created_i2, int32_t *created_slot,
+                                     uint8_t *status /*[K*n1], may be NULL*/, int32_t *n_created_per_neighbour /*[K]*/,
+                                     int32_t *n_created);
+
 #ifdef __cplusplus
 }
 #endif

@@ -444,6 +444,41 @@ class ORBmatcher {
     x3d.assign(xb.begin(), xb.begin() + (size_t)n1 * 3); status.assign(sb.begin(), sb.begin() + n1);
     return created;
   }
+  // Where the created pairs become map points (orbfe_triangulated_points_select; src/LocalMapping.cc:484-500), on the arrays
+  // TriangulateMatchesMulti returns: who is created and in what order (ascending (k, i1), the first neighbour that succeeds
+  // has the keypoint), the position, the two-observation normal and range, and which key frame's descriptor wins (descFrom
+  // 0: key frame 1's row i1, 1: the neighbour's row i2 -- the smaller mnId).  centre1 [3], centre2 [3 per neighbour]; octave1 =
+  // key frame 1's octaves.  Host code: needs no device.  More created points than `capacity` throws.
+  struct TriangulatedPoints {
+    std::vector<int32_t> k, i1, i2;
+    std::vector<float> pos, normal, minDist, maxDist;  // pos / normal: 3 per point
+    std::vector<uint8_t> descFrom;
+  };
+  static TriangulatedPoints TriangulatedPointsSelect(int n1, const std::vector<int32_t>& match12, const std::vector<uint8_t>& status,
+                                                     const std::vector<float>& x3d, int64_t kf1Id, const std::vector<int64_t>& kf2Id,
+                                                     const std::vector<float>& centre1, const std::vector<float>& centre2,
+                                                     const std::vector<int32_t>& octave1, const std::vector<float>& mvScaleFactors,
+                                                     int capacity) {
+    const int K = (int)kf2Id.size();
+    if (match12.size() != (size_t)K * n1 || status.size() != match12.size() || x3d.size() != 3 * match12.size() || centre1.size() != 3 ||
+        centre2.size() != 3 * (size_t)K || octave1.size() != (size_t)n1)
+      throw std::invalid_argument("ORBmatcher::TriangulatedPointsSelect: array sizes do not fit n1 and the neighbours");
+    const size_t cap = (size_t)(capacity > 0 ? capacity : 0);
+    TriangulatedPoints out;
+    out.k.assign(cap + 1, 0); out.i1.assign(cap + 1, 0); out.i2.assign(cap + 1, 0);
+    out.pos.assign(3 * cap + 1, 0.0f); out.normal.assign(3 * cap + 1, 0.0f); out.minDist.assign(cap + 1, 0.0f); out.maxDist.assign(cap + 1, 0.0f);
+    out.descFrom.assign(cap + 1, 0);
+    int32_t created = 0;
+    check(orbfe_triangulated_points_select(n1, K, match12.data(), status.data(), x3d.data(), kf1Id, kf2Id.data(), centre1.data(),
+                                           centre2.data(), octave1.data(), mvScaleFactors.data(), (int)mvScaleFactors.size(), capacity,
+                                           out.k.data(), out.i1.data(), out.i2.data(), out.pos.data(), out.normal.data(), out.minDist.data(),
+                                           out.maxDist.data(), out.descFrom.data(), &created),
+          "TriangulatedPointsSelect");
+    const size_t m = (size_t)created;
+    out.k.resize(m); out.i1.resize(m); out.i2.resize(m); out.pos.resize(3 * m); out.normal.resize(3 * m); out.minDist.resize(m);
+    out.maxDist.resize(m); out.descFrom.resize(m);
+    return out;
+  }
 
   // The loop of Tracking::Relocalization (src/Tracking.cc:1478-1498) in ONE call: SearchByBoW(pKF_k, mCurrentFrame,
   // vvpMapPointMatches[k]) for every candidate key frame.  All frames resident with their mFeatVec.  vnMatches[k][i2] =
@@ -1178,6 +1213,42 @@ class MapPointTable {
           "MapPointTable::CreateStereoPoints");
     out.idx.resize((size_t)created); out.slot.resize((size_t)created); out.cleared.resize(n);
     out.walked = walked;
+    return out;
+  }
+  // LocalMapping::CreateNewMapPoints' pair loop and the birth at its tail (src/LocalMapping.cc:331-501) on the table, in one
+  // call (orbfe_create_triangulated_points).  KF1 / neighbours must be resident; kf1Slot / kf2Slot are their kf slots in
+  // `graph`; match12 [k * n1 + i1] as SearchForTriangulationMulti returns it; newSlot = free slots, taken in creation order
+  // (its size is the capacity).  The graph receives the points, both observations and -- with key-frame rows enabled -- both
+  // key frames' mvpMapPoints entries.  More created points than newSlot holds throws with neither table touched.
+  struct CreatedTriangulatedPoints {
+    std::vector<int32_t> k, i1, i2, slot;  // the pair and the slot of each created point, in creation order
+    std::vector<uint8_t> status;           // [k * n1 + i1], ORBFE_TRI_*
+    std::vector<int32_t> perNeighbour;     // points made with neighbour k
+  };
+  CreatedTriangulatedPoints CreateTriangulatedPoints(const ObservationGraph& graph, const FrameArrays& KF1, int kf1Slot,
+                                                     const KeyFrameCamera& cam1, const std::vector<const FrameArrays*>& neighbours,
+                                                     const std::vector<int32_t>& kf2Slot, const std::vector<const KeyFrameCamera*>& cams,
+                                                     const std::vector<int32_t>& match12, const std::vector<float>& mvScaleFactors,
+                                                     const std::vector<float>& mvLevelSigma2, float ratioFactor,
+                                                     const std::vector<int32_t>& newSlot) {
+    const size_t K = neighbours.size(), n1 = (size_t)KF1.N(), cap = newSlot.size();
+    if (kf2Slot.size() != K || cams.size() != K || match12.size() != K * n1 || mvLevelSigma2.size() != mvScaleFactors.size())
+      throw std::invalid_argument("MapPointTable::CreateTriangulatedPoints: one kf slot, camera and match row per neighbour");
+    std::vector<const orbfe_frame*> frames(K + 1, nullptr);
+    std::vector<orbfe_keyframe_camera> cc(K + 1);
+    for (size_t k = 0; k < K; k++) { frames[k] = neighbours[k]->resident(); cc[k] = cams[k]->c(); }
+    const orbfe_keyframe_camera c1 = cam1.c();
+    CreatedTriangulatedPoints out;
+    out.k.assign(cap + 1, 0); out.i1.assign(cap + 1, 0); out.i2.assign(cap + 1, 0); out.slot.assign(cap + 1, 0);
+    out.status.assign(K * n1 + 1, 0); out.perNeighbour.assign(K + 1, 0);
+    int32_t created = 0;
+    check(orbfe_create_triangulated_points(h_, graph.handle(), KF1.resident(), kf1Slot, &c1, (int)K, frames.data(), kf2Slot.data(), cc.data(),
+                                           match12.data(), mvScaleFactors.data(), mvLevelSigma2.data(), (int)mvScaleFactors.size(),
+                                           ratioFactor, newSlot.data(), (int)cap, out.k.data(), out.i1.data(), out.i2.data(),
+                                           out.slot.data(), out.status.data(), out.perNeighbour.data(), &created),
+          "MapPointTable::CreateTriangulatedPoints");
+    const size_t m = (size_t)created;
+    out.k.resize(m); out.i1.resize(m); out.i2.resize(m); out.slot.resize(m); out.status.resize(K * n1); out.perNeighbour.resize(K);
     return out;
   }
   // GetDescriptor of slot[] as the table holds it (32 bytes each)

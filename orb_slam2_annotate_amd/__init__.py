@@ -9,7 +9,7 @@ from .vocabulary import ORBVocabulary, synthetic_vocabulary_arrays, write_synthe
 from .map_points import MapPoints, camera_pose, motion_model_mode, sim3_leg, track_with_motion_model  # noqa: F401
 from .optimizer import (bundle_adjustment, local_bundle_adjustment, optimize_sim3, optimize_sim3_multi,  # noqa: F401
                         pose_optimization, pose_optimization_batch, sim3_to_Rts)
-from .local_mapping import KeyFrameCamera, triangulate_matches, triangulate_matches_multi  # noqa: F401
+from .local_mapping import KeyFrameCamera, triangulate_matches, triangulate_matches_multi, triangulated_points_select  # noqa: F401
 from .relocalization import (PnPsolver, pnp_ransac, pnp_ransac_multi, pnp_refine_multi,  # noqa: F401
                              pnp_sets_from_draws, pnp_solve_multi)
 from .loop_closing import (Sim3Solver, correct_loop_points, correct_loop_sim3s, gba_propagate_keyframes,  # noqa: F401

@@ -148,6 +148,7 @@ EXPORTS = [
     "orbfe_correct_loop_sim3s", "orbfe_correct_loop_points", "orbfe_correct_loop_mappoints",
     "orbfe_gba_propagate_keyframes", "orbfe_gba_update_points", "orbfe_gba_update_mappoints",
     "orbfe_stereo_points_select", "orbfe_count_close_points", "orbfe_create_stereo_points",
+    "orbfe_triangulated_points_select", "orbfe_create_triangulated_points",
 ]
 
 _lib = None
@@ -395,6 +396,8 @@ def load():
     L.orbfe_stereo_points_select.argtypes = [ci, vp, vp, vp, vp, vp, vp, cpp, cf, ci, vp, ci, vp, ci] + [vp] * 8
     L.orbfe_count_close_points.argtypes = [ci, vp, vp, vp, cf, vp, vp]
     L.orbfe_create_stereo_points.argtypes = [vp, vp, vp, ci, cpp, ci, vp, vp, vp, cf, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    L.orbfe_triangulated_points_select.argtypes = [ci, ci, vp, vp, vp, i64, vp, vp, vp, vp, vp, ci, ci] + [vp] * 9
+    L.orbfe_create_triangulated_points.argtypes = [vp, vp, vp, ci, kcp, ci, vp, vp, kcp, vp, vp, vp, ci, cf, vp, ci] + [vp] * 7
     _lib = L
     return L
 

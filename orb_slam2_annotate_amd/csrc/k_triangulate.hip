@@ -10,17 +10,6 @@ namespace orbfe {
 
 namespace {
 
-__device__ inline TriKeypoint tri_keypoint(const TriangulateFrame& f, int i, float depth, float xraw, float yraw,
-                                           const float* scaleFactors, const float* levelSigma2) {
-  TriKeypoint k;
-  k.x = f.x[i]; k.y = f.y[i];
-  k.ur = f.ur ? f.ur[i] : -1.0f;
-  k.depth = depth; k.xraw = xraw; k.yraw = yraw;
-  const int o = f.octave[i];
-  k.sigma2 = levelSigma2[o]; k.scale = scaleFactors[o];
-  return k;
-}
-
 __global__ __launch_bounds__(kTriangulateThreads) void k_triangulate(TriangulateArgs A) {
   const int p = (int)(blockIdx.x * kTriangulateThreads + threadIdx.x);
   if (p >= A.nPairs) return;

@@ -321,6 +321,29 @@ struct ObsGraphMirror {
     return nullptr;
   }
 
+  // The same question for n NEW points with TWO observations each, by key frame kf[0] and by one of kf[1 .. nKf) (tripoints.hip):
+  // set_points(bad = 0, ref = kf[0]), two add_observations per point with idx < nIdx[j] for key frame kf[j], and -- rows
+  // enabled -- assign_keyframe_points for both.  Also refused, because ComputeDistinctiveDescriptors and UpdateNormalAndDepth
+  // for the row of two would not be what the caller computes: a bad key frame, a kf slot named twice, two equal mnIds.
+  // Distinct point slots are the caller's.
+  const char* check_new_pair_points(int n, const int32_t* slot, int nKf, const int32_t* kf, const int32_t* nIdx) const {
+    if (rowWidth < 2) return "the rows do not hold two observations";
+    for (int j = 0; j < nKf; j++) {
+      if (kf[j] < 0 || kf[j] >= kfCap || kfs[(size_t)kf[j]].id < 0) return "a kf slot is out of range or was never set (orbfe_obsgraph_set_keyframes)";
+      if (kfs[(size_t)kf[j]].bad) return "a key frame is bad";
+      for (int i = 0; i < j; i++)
+        if (kf[i] == kf[j] || kfs[(size_t)kf[i]].id == kfs[(size_t)kf[j]].id) return "a key frame is named twice";
+      if (nIdx[j] > 65536) return "a keypoint index does not fit an observation";
+      if (kfRowWidth && (int)kfRows[(size_t)kf[j]].size() < nIdx[j]) return "a key frame's row of map points is shorter than its frame";
+    }
+    for (int j = 0; j < n; j++) {
+      if (slot[j] < 0 || slot[j] >= pointCap) return "a new slot is at or past the graph's point capacity";
+      const ObsPointMeta& m = meta[(size_t)slot[j]];
+      if (!m.bad || m.count != 0 || !rows[(size_t)slot[j]].empty()) return "a new slot's graph row is live";
+    }
+    return nullptr;
+  }
+
   // ---- KeyFrame::mvpMapPoints (src/KeyFrame.cc:220-243) ----
 
   void touch_kf_row(int k) {

@@ -21,13 +21,13 @@ inline bool tri_view_ok(const orbfe_frame_view* f) {
 }
 inline bool tri_is_stereo(const orbfe_frame_view* f, int i) { return f->u_right && f->u_right[i] >= 0.0f; }
 
-// NULL when the arguments are fine, else what is wrong with them.  f1 / f2[k]: views with HOST arrays (of a resident frame:
-// the handle's own).  winner is only looked at when wantWinner (the multi form).
-inline const char* triangulate_check(const orbfe_frame_view* f1, const orbfe_keyframe_camera* cam1, int K,
-                                     const orbfe_frame_view* const* f2, const orbfe_keyframe_camera* cam2,
-                                     const int32_t* match12, const float* scale_factors, const float* level_sigma2,
-                                     int n_levels, const float* x3d, const uint8_t* status, const int32_t* n_created,
-                                     const int32_t* winner, bool wantWinner) {
+// NULL when what a call READS is fine, else what is wrong with it.  f1 / f2[k]: views with HOST arrays (of a resident
+// frame: the handle's own).  Shared by orbfe_triangulate_matches* and orbfe_create_triangulated_points (tripoints.hip),
+// whose outputs differ.
+inline const char* triangulate_check_inputs(const orbfe_frame_view* f1, const orbfe_keyframe_camera* cam1, int K,
+                                            const orbfe_frame_view* const* f2, const orbfe_keyframe_camera* cam2,
+                                            const int32_t* match12, const float* scale_factors, const float* level_sigma2,
+                                            int n_levels) {
   if (K < 0 || K > kTriHostMaxNeighbours) return "n_neighbours outside [0, 64]";
   if (!f1 || !cam1) return "NULL key frame";
   if (f1->n < 0 || f1->n > kTriHostMaxKeypoints) return "key frame 1 holds more than 16384 keypoints (or fewer than 0)";
@@ -35,9 +35,8 @@ inline const char* triangulate_check(const orbfe_frame_view* f1, const orbfe_key
   if (!scale_factors || !level_sigma2) return "NULL level table";
   if (n_levels <= 0 || n_levels > ORBFE_MAX_LEVELS) return "n_levels outside (0, ORBFE_MAX_LEVELS]";
   const int n1 = f1->n;
-  if (wantWinner && n1 > 0 && !winner) return "NULL winner";
-  if (K > 0 && (!f2 || !cam2 || !n_created)) return "NULL array";
-  if (K > 0 && n1 > 0 && (!match12 || !x3d || !status)) return "NULL array";
+  if (K > 0 && (!f2 || !cam2)) return "NULL array";
+  if (K > 0 && n1 > 0 && !match12) return "NULL array";
   for (int k = 0; k < K; k++) {
     const orbfe_frame_view* g = f2[k];
     if (!g) return "NULL neighbour";
@@ -59,6 +58,21 @@ inline const char* triangulate_check(const orbfe_frame_view* f1, const orbfe_key
       }
     }
   }
+  return nullptr;
+}
+
+// NULL when the arguments of orbfe_triangulate_matches* are fine, else what is wrong with them.  winner is only looked at
+// when wantWinner (the multi form).
+inline const char* triangulate_check(const orbfe_frame_view* f1, const orbfe_keyframe_camera* cam1, int K,
+                                     const orbfe_frame_view* const* f2, const orbfe_keyframe_camera* cam2,
+                                     const int32_t* match12, const float* scale_factors, const float* level_sigma2,
+                                     int n_levels, const float* x3d, const uint8_t* status, const int32_t* n_created,
+                                     const int32_t* winner, bool wantWinner) {
+  if (const char* e = triangulate_check_inputs(f1, cam1, K, f2, cam2, match12, scale_factors, level_sigma2, n_levels)) return e;
+  const int n1 = f1->n;
+  if (wantWinner && n1 > 0 && !winner) return "NULL winner";
+  if (K > 0 && !n_created) return "NULL array";
+  if (K > 0 && n1 > 0 && (!x3d || !status)) return "NULL array";
   return nullptr;
 }
 

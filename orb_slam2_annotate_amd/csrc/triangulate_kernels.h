@@ -32,4 +32,16 @@ struct TriangulateArgs {
 
 void launch_triangulate(hipStream_t s, const TriangulateArgs& a);
 
+// keypoint i of a frame as tri_pair reads it (k_triangulate.hip, k_tripoints.hip)
+__device__ inline TriKeypoint tri_keypoint(const TriangulateFrame& f, int i, float depth, float xraw, float yraw,
+                                           const float* scaleFactors, const float* levelSigma2) {
+  TriKeypoint k;
+  k.x = f.x[i]; k.y = f.y[i];
+  k.ur = f.ur ? f.ur[i] : -1.0f;
+  k.depth = depth; k.xraw = xraw; k.yraw = yraw;
+  const int o = f.octave[i];
+  k.sigma2 = levelSigma2[o]; k.scale = scaleFactors[o];
+  return k;
+}
+
 }  // namespace orbfe

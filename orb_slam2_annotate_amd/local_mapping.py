@@ -1,6 +1,8 @@
 """LocalMapping::CreateNewMapPoints' per-pair loop (src/LocalMapping.cc:331-501) on the device (include/orbfe.h:
 orbfe_triangulate_matches*): the triangulation of the pairs SearchForTriangulation matched, one kernel launch per call.
-ComputeF12, the baseline test and the MapPoint bookkeeping stay with the caller."""
+ComputeF12 and the baseline test stay with the caller.  Where the created pairs become map points -- who, in what order, with
+what descriptor, normal and range -- is orbfe_triangulated_points_select (triangulated_points_select below; on the resident
+state: MapPoints.create_triangulated_points)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -104,3 +106,39 @@ def triangulate_matches(kf1, cam1: KeyFrameCamera, kf2, cam2: KeyFrameCamera, ma
                                                 ptr(sf), ptr(sg), len(sf), float(ratio_factor), ptr(x3d), ptr(status),
                                                 C.byref(created)))
     return x3d[:n1], status[:n1], created.value
+
+
+def triangulated_points_select(match12, status, x3d, kf1_id: int, kf2_ids, centre1, centre2, octave1, scale_factors, capacity=None):
+    """orbfe_triangulated_points_select: the birth at the tail of CreateNewMapPoints' pair loop (src/LocalMapping.cc:484-500) on
+    the outputs of triangulate_matches_multi.  match12 / status [K, n1], x3d [K, n1, 3]; kf1_id / kf2_ids [K] the mnIds,
+    centre1 [3] / centre2 [K, 3] the camera centres, octave1 [n1] key frame 1's octaves -> dict of created_k, created_i1,
+    created_i2, pos [m, 3], normal [m, 3], min_dist, max_dist, desc_from (0: key frame 1's descriptor row i1, 1: the
+    neighbour's row i2) in creation order, n_created.  capacity None: room for every keypoint of key frame 1.  More created
+    points than capacity raises OrbfeError(ERR_CAPACITY) whose n_created is the needed count."""
+    ids = np.ascontiguousarray(kf2_ids, dtype=np.int64).reshape(-1)
+    K = len(ids)
+    oc = np.ascontiguousarray(octave1, dtype=np.int32).reshape(-1)
+    n1 = len(oc)
+    m = np.ascontiguousarray(np.asarray(match12, dtype=np.int32).reshape(K, n1))
+    st = np.ascontiguousarray(np.asarray(status, dtype=np.uint8).reshape(K, n1))
+    x = np.ascontiguousarray(np.asarray(x3d, dtype=np.float32).reshape(K, n1, 3))
+    c1 = _f32(centre1).reshape(3)
+    c2 = np.ascontiguousarray(np.asarray(centre2, dtype=np.float32).reshape(K, 3))
+    sf = _f32(scale_factors).reshape(-1)
+    cap = n1 if capacity is None else int(capacity)
+    room = max(cap, 1)
+    ck, ci1, ci2 = np.zeros(room, np.int32), np.zeros(room, np.int32), np.zeros(room, np.int32)
+    pos, nrm = np.zeros((room, 3), np.float32), np.zeros((room, 3), np.float32)
+    lo, hi, frm = np.zeros(room, np.float32), np.zeros(room, np.float32), np.zeros(room, np.uint8)
+    nc = C.c_int32(0)
+    L = _lib.load()
+    rc = L.orbfe_triangulated_points_select(n1, K, ptr(m), ptr(st), ptr(x), int(kf1_id), ptr(ids), ptr(c1), ptr(c2), ptr(oc), ptr(sf), len(sf),
+                                            cap, ptr(ck), ptr(ci1), ptr(ci2), ptr(pos), ptr(nrm), ptr(lo), ptr(hi), ptr(frm), C.byref(nc))
+    if rc == _lib.ERR_CAPACITY:  # the needed count travels with the error
+        err = _lib.OrbfeError(rc, L.orbfe_last_error().decode("utf-8", "replace"))
+        err.n_created = nc.value
+        raise err
+    check(rc)
+    k = nc.value
+    return dict(created_k=ck[:k].copy(), created_i1=ci1[:k].copy(), created_i2=ci2[:k].copy(), pos=pos[:k].copy(), normal=nrm[:k].copy(),
+                min_dist=lo[:k].copy(), max_dist=hi[:k].copy(), desc_from=frm[:k].copy(), n_created=k)

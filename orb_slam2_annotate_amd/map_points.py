@@ -559,6 +559,55 @@ class MapPoints:
         k = nc.value
         return dict(created_idx=idx[:k].copy(), created_slot=slot[:k].copy(), cleared=cleared[:n].copy(), n_created=k, n_walked=nw.value)
 
+    def create_triangulated_points(self, graph, kf1, kf1_slot, cam1, neighbours, kf2_slots, cams, match12, scale_factors, level_sigma2,
+                                   ratio_factor: float, new_slot):
+        """orbfe_create_triangulated_points: LocalMapping::CreateNewMapPoints' pair loop and the birth at its tail
+        (src/LocalMapping.cc:331-501) on the resident state, in one call.  kf1 / neighbours are ResidentFrames, kf1_slot /
+        kf2_slots their kf slots in `graph`, cam1 / cams local_mapping.KeyFrameCamera, match12 [K, n1] as
+        SearchForTriangulationMulti returns it, new_slot the free slots the created points take in creation order (its
+        length is the capacity) -> dict of created_k, created_i1, created_i2, created_slot [m], status [K, n1],
+        n_created_per_neighbour [K], n_created.  The graph's mirror receives the points, their two observations and -- with
+        key-frame rows enabled -- both key frames' mvpMapPoints entries.  More created points than len(new_slot) raises
+        OrbfeError(ERR_CAPACITY) with n_created set and neither table touched."""
+        from ._lib import KeyFrameCameraC
+        K, n1 = len(neighbours), kf1.N
+        if len(cams) != K or len(kf2_slots) != K:
+            raise ValueError("create_triangulated_points: one camera and one kf slot per neighbour")
+        m = np.ascontiguousarray(np.asarray(match12, dtype=np.int32).reshape(K, n1) if K else np.zeros((0, n1), np.int32))
+        for cm, n in [(cam1, n1)] + [(cm, nb.N) for cm, nb in zip(cams, neighbours)]:
+            for name in ("depth", "x_raw", "y_raw"):
+                a = getattr(cm, name)
+                if a is not None and len(a) != n:
+                    raise ValueError(f"create_triangulated_points: {name} must hold {n} entries, not {len(a)}")
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32).reshape(-1)
+        sg = np.ascontiguousarray(level_sigma2, dtype=np.float32).reshape(-1)
+        if len(sf) != len(sg):
+            raise ValueError("create_triangulated_points: scale_factors and level_sigma2 must hold one entry per level")
+        ns = np.ascontiguousarray(new_slot, dtype=np.int32).reshape(-1)
+        ks = np.ascontiguousarray(kf2_slots, dtype=np.int32).reshape(-1)
+        cap = len(ns)
+        frames = (C.c_void_p * max(K, 1))(*[nb._h.value for nb in neighbours])
+        cc = (KeyFrameCameraC * max(K, 1))()
+        for k, cm in enumerate(cams):
+            cm.fill(cc[k])
+        c1 = cam1.c
+        room = max(cap, 1)
+        ck, ci1, ci2, slot = (np.zeros(room, np.int32) for _ in range(4))
+        status = np.zeros((max(K, 1), max(n1, 1)), np.uint8)
+        per = np.zeros(max(K, 1), np.int32)
+        nc = C.c_int32(0)
+        rc = self._L.orbfe_create_triangulated_points(self._h, graph._h, kf1._h, int(kf1_slot), C.byref(c1), K, frames, ptr(ks), cc, ptr(m),
+                                                      ptr(sf), ptr(sg), len(sf), float(ratio_factor), ptr(ns), cap, ptr(ck), ptr(ci1),
+                                                      ptr(ci2), ptr(slot), ptr(status), ptr(per), C.byref(nc))
+        if rc == _lib.ERR_CAPACITY:  # the needed count travels with the error
+            err = _lib.OrbfeError(rc, self._L.orbfe_last_error().decode("utf-8", "replace"))
+            err.n_created = nc.value
+            raise err
+        check(rc)
+        k = nc.value
+        return dict(created_k=ck[:k].copy(), created_i1=ci1[:k].copy(), created_i2=ci2[:k].copy(), created_slot=slot[:k].copy(),
+                    status=status[:K, :n1].copy(), n_created_per_neighbour=per[:K].copy(), n_created=k)
+
     def compute_distinctive_descriptors(self, graph, slot):
         """MapPoint::ComputeDistinctiveDescriptors for slot[] on the device (orbfe_obsgraph_distinctive_descriptors_mappoints):
         `graph` is the ObservationGraph that holds the rows and the key frames' descriptors; the winners' bytes land in this
